@@ -10,6 +10,12 @@ without a host round trip per token.  N=1 runs BASELINE.json configs[1] (one pro
 N>1 runs configs[2] (independent prompts sharded over the ranks, 8 per GPU, weights broadcast once
 from rank 0 over RCCL, no collective in the timed region).  Weights/prompts are synthetic (seeded
 PRNG, bf16-representable) — there are no checkpoints offline.  One JSON line is printed by rank 0.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.  --full adds
+everything else the line can carry (roofline and per-kernel-class timings, the GEMM point, the
+whole-prompt pass, sampled generation, the other BASELINE configurations, the CPU baseline, the op
+tier, the native weight broadcast at N = 1, the scaling reference at N > 1).  --dump-outputs DIR
+writes the tokens of the last timed generation (rank 0's prompts) as DIR/tokens.npy, float64.
 """
 import argparse
 import ctypes as C
@@ -44,10 +50,18 @@ def parse():
     p.add_argument("--no-other-configs", action="store_true", help="skip the secondary block (8 prompts, XL, nano-char)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for the CPU baseline sample")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--full", action="store_true",
+                   help="also the measurements beside the headline (roofline, GEMM, prefill, sampled generation, other "
+                        "configs, CPU baseline, op tier, weight broadcast, scaling reference); the --no-* switches trim them")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write the tokens of the last timed generation (rank 0's prompts) as DIR/tokens.npy (float64)")
     p.add_argument("--dry-run", action="store_true",
                    help="CPU rehearsal of the launch path (gloo, no GPU, no kernels): rendezvous, prompt sharding, "
                         "weight-arena broadcast, barriers and the max-reduce; prints a line with dry_run=true")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.dry_run and a.dump_outputs:
+        p.error("--dump-outputs needs a real run: a dry run computes no tokens")
+    return a
 
 
 def self_launch(a):
@@ -444,7 +458,7 @@ def main():
     # to who else has queues on the device (the co-running groups: DESIGN §3.3; the op tier polls a completion word behind every
     # call — under a parent with a dozen idle queues it has read 600 tok/s where it reads 770-850 alone).
     early = {}
-    if world == 1 and a.gpus == 1:
+    if a.full and world == 1 and a.gpus == 1:
         from zig_gpt2_amd import synth as _synth
 
         cfg0 = _synth.CONFIGS[a.model]
@@ -505,90 +519,92 @@ def main():
         weights = synth.make_weights(cfg, seed=a.seed, bf16=not a.weights_f32)
         model.load_weights(weights)
     # The one collective of the multi-GPU case goes through the library's own RCCL path (zg_dist_* / zg_gpt_broadcast_weights,
-    # include/zgpt2.h): rank 0 makes the communicator id, torch.distributed only ships its 128 bytes.  With one rank the same calls
-    # run on a one-rank communicator, so the line always carries the device time of the broadcast.
+    # include/zgpt2.h): rank 0 makes the communicator id, torch.distributed only ships its 128 bytes.  With one rank the broadcast
+    # is a measurement only (--full): the same calls run on a one-rank communicator, so that line carries its device time too.
     import ctypes as C
 
     bcast_ms = None
     bcast_note = None
-    # (RCCL prints a version banner through C stdio when a communicator is made; this program's stdout carries ONE JSON line, so
-    # file descriptor 1 points at stderr while the library's RCCL calls run, and C's buffers are flushed before it is restored)
-    sys.stdout.flush()
-    saved_stdout = os.dup(1)
-    os.dup2(2, 1)
-    def all_ranks_ok(ok):  # every rank takes the same branch: the native path only if it worked everywhere
-        if not use_dist:
-            return ok
-        flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=coll_dev)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        return bool(flag.item())
+    ran_bcast = use_dist or a.full
+    if ran_bcast:
+        # (RCCL prints a version banner through C stdio when a communicator is made; this program's stdout carries ONE JSON line, so
+        # file descriptor 1 points at stderr while the library's RCCL calls run, and C's buffers are flushed before it is restored)
+        sys.stdout.flush()
+        saved_stdout = os.dup(1)
+        os.dup2(2, 1)
+        def all_ranks_ok(ok):  # every rank takes the same branch: the native path only if it worked everywhere
+            if not use_dist:
+                return ok
+            flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=coll_dev)
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            return bool(flag.item())
 
-    class NativeDistError(RuntimeError):
-        pass
+        class NativeDistError(RuntimeError):
+            pass
 
-    native_ok = False
-    try:
-        # zg_dist_init is a rendezvous (ncclCommInitRank): every rank enters it or none does.  So the ranks first agree that
-        # RCCL can be bound everywhere (zg_dist_available is not a collective), and only rank 0's id failing is left to ship.
-        ok, err = True, None
+        native_ok = False
         try:
-            _lib.check(lib.zg_dist_available())
-        except _lib.ZgError as e:
-            ok, err = False, str(e)
-        if not all_ranks_ok(ok):
-            raise NativeDistError(err or "RCCL cannot be bound on another rank")
-        uid = (C.c_ubyte * 128)()
-        if rank == 0:
+            # zg_dist_init is a rendezvous (ncclCommInitRank): every rank enters it or none does.  So the ranks first agree that
+            # RCCL can be bound everywhere (zg_dist_available is not a collective), and only rank 0's id failing is left to ship.
+            ok, err = True, None
             try:
-                _lib.check(lib.zg_dist_unique_id(uid, 128))
+                _lib.check(lib.zg_dist_available())
             except _lib.ZgError as e:
-                err = str(e)
-        if use_dist:
-            box = [None if err else bytes(uid), err]
-            dist.broadcast_object_list(box, src=0)
-            err = box[1]
-            if err is None:
-                uid = (C.c_ubyte * 128).from_buffer_copy(box[0])
-        if err is not None:
-            raise NativeDistError(err)
-        try:
-            _lib.check(lib.zg_dist_init(uid, 128, rank, world))
-        except _lib.ZgError as e:
-            ok, err = False, str(e)
-        if not all_ranks_ok(ok):
-            raise NativeDistError(err or "zg_dist_init failed on another rank")
-        torch.cuda.synchronize()
-        if use_dist:
+                ok, err = False, str(e)
+            if not all_ranks_ok(ok):
+                raise NativeDistError(err or "RCCL cannot be bound on another rank")
+            uid = (C.c_ubyte * 128)()
+            if rank == 0:
+                try:
+                    _lib.check(lib.zg_dist_unique_id(uid, 128))
+                except _lib.ZgError as e:
+                    err = str(e)
+            if use_dist:
+                box = [None if err else bytes(uid), err]
+                dist.broadcast_object_list(box, src=0)
+                err = box[1]
+                if err is None:
+                    uid = (C.c_ubyte * 128).from_buffer_copy(box[0])
+            if err is not None:
+                raise NativeDistError(err)
+            try:
+                _lib.check(lib.zg_dist_init(uid, 128, rank, world))
+            except _lib.ZgError as e:
+                ok, err = False, str(e)
+            if not all_ranks_ok(ok):
+                raise NativeDistError(err or "zg_dist_init failed on another rank")
+            torch.cuda.synchronize()
+            if use_dist:
+                dist.barrier()
+            ms = C.c_float(0.0)
+            try:
+                _lib.check(lib.zg_gpt_broadcast_weights(model.h, 0, C.byref(ms)))
+            except _lib.ZgError as e:
+                ok, err = False, str(e)
+            if not all_ranks_ok(ok):
+                raise NativeDistError(err or "zg_gpt_broadcast_weights failed on another rank")
+            bcast_ms = float(ms.value)
+            _lib.check(lib.zg_dist_finalize())
+            native_ok = True
+        except (NativeDistError, _lib.ZgError) as e:
+            lib.zg_dist_finalize()  # a communicator made before the failure must not outlive it (no-op without one)
+            bcast_note = f"native RCCL path unavailable ({e})"  # (a one-GPU box without librccl: nothing to broadcast to)
+        finally:
+            C.CDLL(None).fflush(None)
+            os.dup2(saved_stdout, 1)
+            os.close(saved_stdout)
+        if not native_ok and world > 1:
+            # the run must still measure the step: the same weight region through torch.distributed's broadcast (RCCL as well), and
+            # the line says so
+            ptr, nbytes = model.weight_arena()
+            arena = torch.as_tensor(_DevMem(ptr, nbytes), device=torch.device("cuda", dev_index))
+            torch.cuda.synchronize()
             dist.barrier()
-        ms = C.c_float(0.0)
-        try:
-            _lib.check(lib.zg_gpt_broadcast_weights(model.h, 0, C.byref(ms)))
-        except _lib.ZgError as e:
-            ok, err = False, str(e)
-        if not all_ranks_ok(ok):
-            raise NativeDistError(err or "zg_gpt_broadcast_weights failed on another rank")
-        bcast_ms = float(ms.value)
-        _lib.check(lib.zg_dist_finalize())
-        native_ok = True
-    except (NativeDistError, _lib.ZgError) as e:
-        lib.zg_dist_finalize()  # a communicator made before the failure must not outlive it (no-op without one)
-        bcast_note = f"native RCCL path unavailable ({e})"  # (a one-GPU box without librccl: nothing to broadcast to)
-    finally:
-        C.CDLL(None).fflush(None)
-        os.dup2(saved_stdout, 1)
-        os.close(saved_stdout)
-    if not native_ok and world > 1:
-        # the run must still measure the step: the same weight region through torch.distributed's broadcast (RCCL as well), and
-        # the line says so
-        ptr, nbytes = model.weight_arena()
-        arena = torch.as_tensor(_DevMem(ptr, nbytes), device=torch.device("cuda", dev_index))
-        torch.cuda.synchronize()
-        dist.barrier()
-        tb = time.perf_counter()
-        shard.broadcast_weights(arena, dist, src=0)
-        torch.cuda.synchronize()
-        bcast_ms = (time.perf_counter() - tb) * 1e3
-        bcast_note += "; weights broadcast by torch.distributed.broadcast over the same arena region (host wall clock)"
+            tb = time.perf_counter()
+            shard.broadcast_weights(arena, dist, src=0)
+            torch.cuda.synchronize()
+            bcast_ms = (time.perf_counter() - tb) * 1e3
+            bcast_note += "; weights broadcast by torch.distributed.broadcast over the same arena region (host wall clock)"
     setup_s = time.perf_counter() - t0
 
     # ---- prompts: one token each, distinct per global prompt index
@@ -604,9 +620,9 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # N > 1: the one-GPU figure with the same per-GPU work, taken by rank 0 alone before the collective region
+    # N > 1 (--full): the one-GPU figure with the same per-GPU work, taken by rank 0 alone before the collective region
     ref_value = None
-    if dist is not None:
+    if dist is not None and a.full:
         if rank == 0:
             one_generation()
             torch.cuda.synchronize()
@@ -642,7 +658,7 @@ def main():
     value = world * gen_tokens * a.steps / elapsed
 
     scaling_extra = {}
-    if dist is not None:
+    if dist is not None and a.full:
         _, wbytes_region = model.weight_arena()
         scaling_extra = scaling_fields(dist, torch, coll_dev, world, value, ref_value,
                                        gen_tokens * a.steps / own_s, bcast_ms, wbytes_region)
@@ -651,128 +667,167 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
+    if a.dump_outputs:  # what a caller of generate receives: the token matrix [prompts, ctx] (ids < 2^53: exact in float64)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "tokens.npy"), ids.astype(np.float64))
 
-    # ---- roofline: every kernel class of the decode step timed live (HIP events on the launch stream around a
-    # hipGraph chain of 64 launches of that one kernel, mid-context control block), priced per token by its launch
-    # count; `roofline` describes the class with the LARGEST share of the token time, lm_head and the whole step
-    # are reported beside it.
-    wbytes, _ = model.step_bytes(1)
-    wsz = 4 if a.weights_f32 else 2
-    kv_elem = 2 if a.kv_f16 else 3 if a.kv_b24 else 4
-    table, dom, lm = kernel_table(model, lib, cfg, ppg, wsz, kv_elem)
-    n_prof = min(64, ctx)
-    prof_lo = model.profile_step(1, n_prof)
-    prof_hi = model.profile_step(ctx - n_prof + 1, n_prof)
-    # HBM traffic per launch: PMC counters cannot be read from inside this process; the committed rocprofv3 passes
-    # (profiles/<round>_traffic.json: FETCH_SIZE doubled per MI355X_MICROARCH.md + WRITE_SIZE, per launch, taken at the
-    # same shapes) are quoted with their provenance, null when the file has no entry for this kernel / config.
-    traffic, traffic_src = None, None
-    try:
-        with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
-            tj = json.load(f)
-        key = f"{a.model}/{ppg}/{'f32' if a.weights_f32 else 'bf16'}"
-        ent = tj.get(key, {}).get(dom["class"])
-        if ent:
-            traffic, traffic_src = ent["bytes_per_launch"], ent["source"]
-    except Exception:
-        pass
-    gemm = None
-    if a.model == "124M" and world == 1:
+    full = {}  # the fields of --full
+    if a.full:
+        # ---- roofline: every kernel class of the decode step timed live (HIP events on the launch stream around a
+        # hipGraph chain of 64 launches of that one kernel, mid-context control block), priced per token by its launch
+        # count; `roofline` describes the class with the LARGEST share of the token time, lm_head and the whole step
+        # are reported beside it.
+        wbytes, _ = model.step_bytes(1)
+        wsz = 4 if a.weights_f32 else 2
+        kv_elem = 2 if a.kv_f16 else 3 if a.kv_b24 else 4
+        table, dom, lm = kernel_table(model, lib, cfg, ppg, wsz, kv_elem)
+        n_prof = min(64, ctx)
+        prof_lo = model.profile_step(1, n_prof)
+        prof_hi = model.profile_step(ctx - n_prof + 1, n_prof)
+        # HBM traffic per launch: PMC counters cannot be read from inside this process; the committed rocprofv3 passes
+        # (profiles/<round>_traffic.json: FETCH_SIZE doubled per MI355X_MICROARCH.md + WRITE_SIZE, per launch, taken at the
+        # same shapes) are quoted with their provenance, null when the file has no entry for this kernel / config.
+        traffic, traffic_src = None, None
         try:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            import bench_gemm
-
-            gemm = bench_gemm.measure(lib, 8192)  # BASELINE's point; the other heights beside it (same warm-up: the clocks need it)
-            keep = ("M", "N", "K", "gelu", "out", "us", "us_min", "tflops", "mfma_frac_of_2.5PF")
-            gemm["other_M"] = [{k: v for k, v in bench_gemm.measure(lib, m).items() if k in keep} for m in (64, 1024, 16384)]  # M in {64, 1024, 8192}
-            # the account beside the headline (same kernel, same launch path): the epilogue's share (bias only, no GELU), and the
-            # MLP's OTHER 768 x 3072 Linear — mlp c_proj, N = 768, K = 3072 (src/main.zig:81) — whose tiles see 4 x the K per
-            # epilogue: whole K at M = 16384 (256 tiles of 256 x 192 = one per CU); at M = 8192 its 128 tiles fill half the chip
-            gemm["account"] = {
-                "c_fc_bias_only_M8192": {k: v for k, v in bench_gemm.measure(lib, 8192, gelu=False).items() if k in keep},
-                "mlp_c_proj_N768_K3072_M16384": {k: v for k, v in bench_gemm.measure(lib, 16384, n=768, k=3072, gelu=False).items() if k in keep},
-                "mlp_c_proj_N768_K3072_M8192_half_chip": {k: v for k, v in bench_gemm.measure(lib, 8192, n=768, k=3072, gelu=False).items() if k in keep},
-                "note": "FLOP-based fractions of 2.5 PF; the counter-based MFMA-busy of the same launches is in profiles/round6_gemm_account_pmc.md",
-            }
-            _lib.check(lib.zg_set_stream(stream.cuda_stream))
-        except Exception as e:  # the headline metric must not die with the secondary one
-            gemm = {"error": str(e)}
-    # the prompt side of generate (src/main.zig:331-334) as one pass: zg_gpt_prefill of a (ctx - 1)-token prompt
-    prefill = None
-    if world == 1 and ctx > 1:
-        try:
-            n_p = ctx - 1
-            ptoks = np.stack([synth.rand_tokens(a.seed + 500 + b, n_p, cfg.vocab_size) for b in range(ppg)])
-            lin_flops = 2.0 * ppg * n_p * (12 * cfg.n_embed * cfg.n_embed) * cfg.n_layer  # the four Linears of every Block
-
-            def time_prefill(mdl):
-                for _ in range(3):
-                    mdl.prefill(ptoks, compute_logits=False)
-                t0 = time.perf_counter()
-                for _ in range(5):
-                    mdl.prefill(ptoks, compute_logits=False)
-                return (time.perf_counter() - t0) / 5 * 1e3
-
-            p_ms = time_prefill(model)
-            prefill = {"prompt_tokens": n_p, "prompts": ppg, "ms": round(p_ms, 3),
-                       "prompt_tokens_per_s": round(ppg * n_p / p_ms * 1e3, 1),
-                       **prefill_flops(cfg, ppg, n_p, p_ms),
-                       "vs_token_at_a_time": round((1e3 * elapsed / a.steps) * n_p / ctx / p_ms, 1),
-                       "how": "synchronous zg_gpt_prefill calls (host wall clock, 5 repetitions after 3 warm-ups); "
-                              + ("fp32 weights: both GEMM operands as exact bf16 plane triples, the six plane products as three "
-                                 "passes of one launch of the 128-row prompt GEMM per Linear" if a.weights_f32 else
-                                 "activations split exactly 3-way into bf16 for the MFMA GEMMs") + ", causal attention on the bf16 matrix cores with exact three-plane splits of q, k, v and the probabilities (six plane products per matrix product)"}
-            if not a.weights_f32:  # the two-plane mode (inside north_star's 1e-3, outside the tests' near-zero floor)
-                m2 = gpt.GPT(cfg, batch=ppg, use_graph=False, kv_f16=a.kv_f16, kv_b24=a.kv_b24, prefill_planes=2)
-                m2.load_weights(weights)
-                p2_ms = time_prefill(m2)
-                m2.close()
-                prefill["two_plane"] = {"ms": round(p2_ms, 3), "prompt_tokens_per_s": round(ppg * n_p / p2_ms * 1e3, 1),
-                                        "linear_tflops_useful": round(lin_flops / p2_ms / 1e9, 1)}
-        except Exception as e:
-            prefill = {"error": str(e)}
-    # generate as the reference runs it (src/main.zig:322-342: every token drawn by GPT.sample, temp 0.8 in main): the device loop
-    # with the sampler as a node of the captured step, and the per-token entry point zg_gpt_sample it replaces
-    sampled = None
-    if world == 1:
-        try:
-            model.generate_sample(prompts, ctx, 0.8, seed=a.seed)  # (captures the sampled graphs)
-            torch.cuda.synchronize()
-            t_s = time.perf_counter()
-            ids_s = model.generate_sample(prompts, ctx, 0.8, seed=a.seed)
-            s_wall = time.perf_counter() - t_s
-            n_pt = min(ctx, 128)
-            toks = [int(p[0]) for p in prompts]
-            model.sample(1, toks, 0.8, seed=a.seed)
-            t_s = time.perf_counter()
-            for T in range(1, n_pt + 1):
-                toks = [int(t) for t in model.sample(T, toks, 0.8, seed=a.seed)]
-            pt_wall = time.perf_counter() - t_s
-            sampled = {"temperature": 0.8, "device_loop_tokens_per_s": round(ppg * (ctx - 1) / s_wall, 1), "ms_per_generation": round(1e3 * s_wall, 3),
-                       "per_token_call_tokens_per_s": round(ppg * n_pt / pt_wall, 1), "per_token_positions": n_pt,
-                       "distinct_tokens_in_row_0": int(len(set(int(t) for t in ids_s[0]))),
-                       "how": "zg_gpt_generate_sample (sampler node in the captured decode step, uniforms from the library's counter PRNG) against a "
-                              "host loop over zg_gpt_sample; identical tokens for identical seeds (tests/test_sampled_generate_gpu.py)"}
-        except Exception as e:
-            sampled = {"error": str(e)}
-    # BASELINE.json configs[2..4] on this GPU, one handle after another (the headline handle stays: its numbers are above)
-    others = None
-    if a.model == "124M" and world == 1 and ppg == 1 and not a.weights_f32 and not a.kv_f16 and not a.kv_b24 and not a.no_other_configs:
-        others = []
-        for mname, mp, gens, b24 in (("124M", 8, 2, False), ("124M", 8, 2, True), ("xl", 1, 1, False), ("nano-char", 1, 3, False)):
+            with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
+                tj = json.load(f)
+            key = f"{a.model}/{ppg}/{'f32' if a.weights_f32 else 'bf16'}"
+            ent = tj.get(key, {}).get(dom["class"])
+            if ent:
+                traffic, traffic_src = ent["bytes_per_launch"], ent["source"]
+        except Exception:
+            pass
+        gemm = None
+        if a.model == "124M" and world == 1:
             try:
-                t_o = time.perf_counter()
-                o = other_config(lib, stream, mname, mp, gens, a.seed + 7, kv_b24=b24)
-                o["seconds_spent"] = round(time.perf_counter() - t_o, 1)
-                others.append(o)
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                import bench_gemm
+
+                gemm = bench_gemm.measure(lib, 8192)  # BASELINE's point; the other heights beside it (same warm-up: the clocks need it)
+                keep = ("M", "N", "K", "gelu", "out", "us", "us_min", "tflops", "mfma_frac_of_2.5PF")
+                gemm["other_M"] = [{k: v for k, v in bench_gemm.measure(lib, m).items() if k in keep} for m in (64, 1024, 16384)]  # M in {64, 1024, 8192}
+                # the account beside the headline (same kernel, same launch path): the epilogue's share (bias only, no GELU), and the
+                # MLP's OTHER 768 x 3072 Linear — mlp c_proj, N = 768, K = 3072 (src/main.zig:81) — whose tiles see 4 x the K per
+                # epilogue: whole K at M = 16384 (256 tiles of 256 x 192 = one per CU); at M = 8192 its 128 tiles fill half the chip
+                gemm["account"] = {
+                    "c_fc_bias_only_M8192": {k: v for k, v in bench_gemm.measure(lib, 8192, gelu=False).items() if k in keep},
+                    "mlp_c_proj_N768_K3072_M16384": {k: v for k, v in bench_gemm.measure(lib, 16384, n=768, k=3072, gelu=False).items() if k in keep},
+                    "mlp_c_proj_N768_K3072_M8192_half_chip": {k: v for k, v in bench_gemm.measure(lib, 8192, n=768, k=3072, gelu=False).items() if k in keep},
+                    "note": "FLOP-based fractions of 2.5 PF; the counter-based MFMA-busy of the same launches is in profiles/round6_gemm_account_pmc.md",
+                }
+                _lib.check(lib.zg_set_stream(stream.cuda_stream))
+            except Exception as e:  # the headline metric must not die with the secondary one
+                gemm = {"error": str(e)}
+        # the prompt side of generate (src/main.zig:331-334) as one pass: zg_gpt_prefill of a (ctx - 1)-token prompt
+        prefill = None
+        if world == 1 and ctx > 1:
+            try:
+                n_p = ctx - 1
+                ptoks = np.stack([synth.rand_tokens(a.seed + 500 + b, n_p, cfg.vocab_size) for b in range(ppg)])
+                lin_flops = 2.0 * ppg * n_p * (12 * cfg.n_embed * cfg.n_embed) * cfg.n_layer  # the four Linears of every Block
+
+                def time_prefill(mdl):
+                    for _ in range(3):
+                        mdl.prefill(ptoks, compute_logits=False)
+                    t0 = time.perf_counter()
+                    for _ in range(5):
+                        mdl.prefill(ptoks, compute_logits=False)
+                    return (time.perf_counter() - t0) / 5 * 1e3
+
+                p_ms = time_prefill(model)
+                prefill = {"prompt_tokens": n_p, "prompts": ppg, "ms": round(p_ms, 3),
+                           "prompt_tokens_per_s": round(ppg * n_p / p_ms * 1e3, 1),
+                           **prefill_flops(cfg, ppg, n_p, p_ms),
+                           "vs_token_at_a_time": round((1e3 * elapsed / a.steps) * n_p / ctx / p_ms, 1),
+                           "how": "synchronous zg_gpt_prefill calls (host wall clock, 5 repetitions after 3 warm-ups); "
+                                  + ("fp32 weights: both GEMM operands as exact bf16 plane triples, the six plane products as three "
+                                     "passes of one launch of the 128-row prompt GEMM per Linear" if a.weights_f32 else
+                                     "activations split exactly 3-way into bf16 for the MFMA GEMMs") + ", causal attention on the bf16 matrix cores with exact three-plane splits of q, k, v and the probabilities (six plane products per matrix product)"}
+                if not a.weights_f32:  # the two-plane mode (inside north_star's 1e-3, outside the tests' near-zero floor)
+                    m2 = gpt.GPT(cfg, batch=ppg, use_graph=False, kv_f16=a.kv_f16, kv_b24=a.kv_b24, prefill_planes=2)
+                    m2.load_weights(weights)
+                    p2_ms = time_prefill(m2)
+                    m2.close()
+                    prefill["two_plane"] = {"ms": round(p2_ms, 3), "prompt_tokens_per_s": round(ppg * n_p / p2_ms * 1e3, 1),
+                                            "linear_tflops_useful": round(lin_flops / p2_ms / 1e9, 1)}
             except Exception as e:
-                others.append({"workload": f"{mname} x {mp}", "error": str(e)})
-        if "groups" in early:
-            others.append(early["groups"])
-        _lib.check(lib.zg_set_stream(stream.cuda_stream))
-    # whole-step view: algorithmic bytes of all ctx steps / device time
-    kv_total = sum(kv_elem * 2 * t * cfg.n_embed * cfg.n_layer * ppg for t in range(1, ctx + 1))
-    step_bytes_total = wbytes * ctx + kv_total
+                prefill = {"error": str(e)}
+        # generate as the reference runs it (src/main.zig:322-342: every token drawn by GPT.sample, temp 0.8 in main): the device loop
+        # with the sampler as a node of the captured step, and the per-token entry point zg_gpt_sample it replaces
+        sampled = None
+        if world == 1:
+            try:
+                model.generate_sample(prompts, ctx, 0.8, seed=a.seed)  # (captures the sampled graphs)
+                torch.cuda.synchronize()
+                t_s = time.perf_counter()
+                ids_s = model.generate_sample(prompts, ctx, 0.8, seed=a.seed)
+                s_wall = time.perf_counter() - t_s
+                n_pt = min(ctx, 128)
+                toks = [int(p[0]) for p in prompts]
+                model.sample(1, toks, 0.8, seed=a.seed)
+                t_s = time.perf_counter()
+                for T in range(1, n_pt + 1):
+                    toks = [int(t) for t in model.sample(T, toks, 0.8, seed=a.seed)]
+                pt_wall = time.perf_counter() - t_s
+                sampled = {"temperature": 0.8, "device_loop_tokens_per_s": round(ppg * (ctx - 1) / s_wall, 1), "ms_per_generation": round(1e3 * s_wall, 3),
+                           "per_token_call_tokens_per_s": round(ppg * n_pt / pt_wall, 1), "per_token_positions": n_pt,
+                           "distinct_tokens_in_row_0": int(len(set(int(t) for t in ids_s[0]))),
+                           "how": "zg_gpt_generate_sample (sampler node in the captured decode step, uniforms from the library's counter PRNG) against a "
+                                  "host loop over zg_gpt_sample; identical tokens for identical seeds (tests/test_sampled_generate_gpu.py)"}
+            except Exception as e:
+                sampled = {"error": str(e)}
+        # BASELINE.json configs[2..4] on this GPU, one handle after another (the headline handle stays: its numbers are above)
+        others = None
+        if a.model == "124M" and world == 1 and ppg == 1 and not a.weights_f32 and not a.kv_f16 and not a.kv_b24 and not a.no_other_configs:
+            others = []
+            for mname, mp, gens, b24 in (("124M", 8, 2, False), ("124M", 8, 2, True), ("xl", 1, 1, False), ("nano-char", 1, 3, False)):
+                try:
+                    t_o = time.perf_counter()
+                    o = other_config(lib, stream, mname, mp, gens, a.seed + 7, kv_b24=b24)
+                    o["seconds_spent"] = round(time.perf_counter() - t_o, 1)
+                    others.append(o)
+                except Exception as e:
+                    others.append({"workload": f"{mname} x {mp}", "error": str(e)})
+            if "groups" in early:
+                others.append(early["groups"])
+            _lib.check(lib.zg_set_stream(stream.cuda_stream))
+        # whole-step view: algorithmic bytes of all ctx steps / device time
+        kv_total = sum(kv_elem * 2 * t * cfg.n_embed * cfg.n_layer * ppg for t in range(1, ctx + 1))
+        step_bytes_total = wbytes * ctx + kv_total
+        full = {
+            "roofline": {
+                "kernel": dom["class"], "kernel_symbol": dom["kernel_symbol"], "bound": "hbm", "achieved": dom["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": dom["frac_of_8TBps"], "traffic": traffic, "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"], "avg_launch_us": dom["avg_launch_us"],
+                "avg_launch_us_layers_walked": dom["avg_launch_us_layers_walked"],
+                "achieved_layers_walked": round(dom["algorithmic_bytes_per_launch"] / dom["avg_launch_us_layers_walked"] / 1e3, 1),
+                "frac_layers_walked": round(dom["algorithmic_bytes_per_launch"] / dom["avg_launch_us_layers_walked"] / 1e3 / HBM_PEAK_GBS, 4),
+                "share_of_token_time": dom["share_of_token_time"],
+                "how": "the kernel class with the largest share of the decode-step time; duration = HIP events on the launch "
+                       "stream around a hipGraph chain of that kernel (launch boundary included), measured in this run; "
+                       "kernel_classes also lists avg_launch_us_layers_walked: the same chain walking the layers, i.e. with "
+                       "weights / KV coming from the memory side as in the real step (lm_head has one matrix: identical)",
+            },
+            "kernel_classes": table,
+            "roofline_lm_head": {"kernel": lm["class"], "achieved": lm["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                 "frac": lm["frac_of_8TBps"], "avg_launch_us": lm["avg_launch_us"],
+                                 "algorithmic_bytes_per_launch": lm["algorithmic_bytes_per_launch"]},
+            "step_roofline": {
+                "bound": "hbm", "algorithmic_bytes_per_generation": int(step_bytes_total),
+                "achieved": round(step_bytes_total * a.steps / dev_s / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(step_bytes_total * a.steps / dev_s / 1e9 / HBM_PEAK_GBS, 4),
+                "us_per_token_device": round(1e6 * dev_s / (a.steps * ctx), 2),
+                # two clocks that do not share code: torch events around the whole generations (above) against the sum of the per-class
+                # chain timings of kernel_classes (the library's HIP events around hipGraph chains), priced per token with the embed launch
+                "sum_of_kernel_class_chains_us": round(sum(r["avg_launch_us_layers_walked"] * r["launches_per_token"] for r in table) + prof_lo.get("embed", 0.0), 2),
+                "per_kernel_class_us_eager_T_low": {k: round(v, 2) for k, v in prof_lo.items()},
+                "per_kernel_class_us_eager_T_high": {k: round(v, 2) for k, v in prof_hi.items()},
+            },
+            "mfma_gemm_768x3072": gemm,
+            "prefill": prefill,
+            "sampled_generation": sampled,
+            "other_configs": others,
+        }
     out = {
         "metric": "tokens/sec GPT-2-124M greedy 1024-ctx" if a.model == "124M" else f"tokens/sec {a.model} greedy {ctx}-ctx",
         "value": round(value, 1),
@@ -801,46 +856,16 @@ def main():
                              "--prompts-per-gpu pins the per-GPU work for all N") if a.prompts_per_gpu == 0 else
                             f"per-GPU work pinned by --prompts-per-gpu {ppg} for every N",
         },
-        "roofline": {
-            "kernel": dom["class"], "kernel_symbol": dom["kernel_symbol"], "bound": "hbm", "achieved": dom["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": dom["frac_of_8TBps"], "traffic": traffic, "traffic_source": traffic_src,
-            "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"], "avg_launch_us": dom["avg_launch_us"],
-            "avg_launch_us_layers_walked": dom["avg_launch_us_layers_walked"],
-            "achieved_layers_walked": round(dom["algorithmic_bytes_per_launch"] / dom["avg_launch_us_layers_walked"] / 1e3, 1),
-            "frac_layers_walked": round(dom["algorithmic_bytes_per_launch"] / dom["avg_launch_us_layers_walked"] / 1e3 / HBM_PEAK_GBS, 4),
-            "share_of_token_time": dom["share_of_token_time"],
-            "how": "the kernel class with the largest share of the decode-step time; duration = HIP events on the launch "
-                   "stream around a hipGraph chain of that kernel (launch boundary included), measured in this run; "
-                   "kernel_classes also lists avg_launch_us_layers_walked: the same chain walking the layers, i.e. with "
-                   "weights / KV coming from the memory side as in the real step (lm_head has one matrix: identical)",
-        },
-        "kernel_classes": table,
-        "roofline_lm_head": {"kernel": lm["class"], "achieved": lm["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": lm["frac_of_8TBps"], "avg_launch_us": lm["avg_launch_us"],
-                             "algorithmic_bytes_per_launch": lm["algorithmic_bytes_per_launch"]},
-        "step_roofline": {
-            "bound": "hbm", "algorithmic_bytes_per_generation": int(step_bytes_total),
-            "achieved": round(step_bytes_total * a.steps / dev_s / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(step_bytes_total * a.steps / dev_s / 1e9 / HBM_PEAK_GBS, 4),
-            "us_per_token_device": round(1e6 * dev_s / (a.steps * ctx), 2),
-            # two clocks that do not share code: torch events around the whole generations (above) against the sum of the per-class
-            # chain timings of kernel_classes (the library's HIP events around hipGraph chains), priced per token with the embed launch
-            "sum_of_kernel_class_chains_us": round(sum(r["avg_launch_us_layers_walked"] * r["launches_per_token"] for r in table) + prof_lo.get("embed", 0.0), 2),
-            "per_kernel_class_us_eager_T_low": {k: round(v, 2) for k, v in prof_lo.items()},
-            "per_kernel_class_us_eager_T_high": {k: round(v, 2) for k, v in prof_hi.items()},
-        },
-        "mfma_gemm_768x3072": gemm,
-        "prefill": prefill,
-        "sampled_generation": sampled,
-        "other_configs": others,
+        **full,
         "device_time_s": round(dev_s, 4),
         "setup_s": round(setup_s, 2),
-        "weight_broadcast_ms": None if bcast_ms is None else round(bcast_ms, 3),
-        "weight_broadcast": bcast_note or "zg_gpt_broadcast_weights: one ncclBroadcast of the arena's weight region on the library's stream (device time, HIP events)",
+        **({"weight_broadcast_ms": None if bcast_ms is None else round(bcast_ms, 3),
+            "weight_broadcast": bcast_note or "zg_gpt_broadcast_weights: one ncclBroadcast of the arena's weight region on the library's stream (device time, HIP events)"}
+           if ran_bcast else {}),
         "first_tokens": [int(t) for t in ids[0, :8]],
         **scaling_extra,
     }
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(cfg, weights, prompts[0], a.cpu_seconds)
     if "op_tier" in early:
         out["op_tier"] = early["op_tier"]

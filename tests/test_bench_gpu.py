@@ -25,7 +25,7 @@ def run(cmd, env_extra):
 
 
 def test_bench_line_single_process():
-    d = run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--ctx", "96", "--cpu-seconds", "2"], {})
+    d = run([sys.executable, "bench.py", "--full", "--steps", "1", "--warmup", "1", "--ctx", "96", "--cpu-seconds", "2"], {})
     for k in REQUIRED + ["cpu_baseline"]:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 1 and d["value"] > 0 and d["scaling"] == "weak"
@@ -36,9 +36,30 @@ def test_bench_line_single_process():
     assert d["prefill"]["prompt_tokens"] == 95 and d["prefill"]["prompt_tokens_per_s"] > 0
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run carries the headline only; --dump-outputs writes the last timed generation's tokens, the same from run to run
+    (seeded weights and prompts), whatever --steps is."""
+    import numpy as np
+
+    toks = []
+    for steps in (1, 2):
+        d = run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "1", "--ctx", "96",
+                 "--dump-outputs", str(tmp_path / f"s{steps}")], {})
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == steps and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - 95) < 0.5  # one step = one generation of 95 tokens
+        assert not {"roofline", "cpu_baseline", "prefill", "other_configs", "op_tier", "weight_broadcast_ms"} & set(d)
+        t = np.load(tmp_path / f"s{steps}" / "tokens.npy")
+        assert t.dtype == np.float64 and t.shape == (1, 96)
+        assert t[0, :8].tolist() == d["first_tokens"]
+        toks.append(t)
+    assert np.array_equal(toks[0], toks[1])
+
+
 def test_bench_rccl_leg_with_one_rank():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", "bench.py", "--gpus", "1", "--steps", "1", "--warmup", "1", "--ctx", "64", "--no-cpu-baseline"]
+           "--master-port", "29533", "bench.py", "--gpus", "1", "--full", "--steps", "1", "--warmup", "1", "--ctx", "64", "--no-cpu-baseline"]
     d = run(cmd, {"ZGPT2_FORCE_DIST": "1"})
     assert d["n_gpus"] == 1 and d["value"] > 0
     assert d["weight_broadcast_ms"] is not None and d["weight_broadcast_ms"] >= 0
@@ -62,7 +83,7 @@ def test_bench_two_ranks_on_one_gpu_over_the_stub_transport():
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", stub_so, stub_src])
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ZGPT2_RCCL_LIB=stub_so, ZGPT2_ALL_RANKS_ON_DEVICE="0")
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--ctx", "64", "--prompts-per-gpu", "2"],
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", "--steps", "1", "--warmup", "1", "--ctx", "64", "--prompts-per-gpu", "2"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -15,6 +15,6 @@ echo "== zero fill"; ZGPT2_GEMM_DBG=256 $B -k s4 -stamps -fill 1 -nocheck
 echo "== M=16384"; ZGPT2_GEMM_DBG=256 $B 16384 3072 768 -k s4 -stamps -nocheck
 echo "== M=1024"; ZGPT2_GEMM_DBG=256 $B 1024 3072 768 -k s4 -stamps -nocheck
 } > $out/gemm_a.txt 2>&1
-python bench.py --steps 3 --warmup 1 > $out/bench.json 2> $out/bench.err
+python bench.py --full --steps 3 --warmup 1 > $out/bench.json 2> $out/bench.err
 tail -5 $out/bench.err
 cat $out/gemm_a.txt

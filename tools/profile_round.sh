@@ -6,11 +6,11 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 export PYTHONPATH=$GRAFT_REPO_ROOT
 # 1. kernel trace + stats of the default benchmark command (full 1024-position context)
-timeout 600 rocprofv3 --kernel-trace --stats -d $out/trace -o bench -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $out/trace -o bench -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
 python tools/rocpd_stats.py $(find $out/trace -name "*.db" | head -1) $out/${tag}_kernel_stats.md > /dev/null
 rm -rf $out/trace
 # 1b. the same without the side-stream L2 prefetcher: the per-kernel durations it changes
-timeout 600 rocprofv3 --kernel-trace --stats -d $out/trace -o bench -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prefetch > $out/bench_under_rocprof_noprefetch.json 2> $out/bench_under_rocprof_noprefetch.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $out/trace -o bench -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-prefetch > $out/bench_under_rocprof_noprefetch.json 2> $out/bench_under_rocprof_noprefetch.err
 python tools/rocpd_stats.py $(find $out/trace -name "*.db" | head -1) $out/${tag}_kernel_stats_noprefetch.md > /dev/null
 rm -rf $out/trace
 # 2. HBM traffic counters of the same workload at the full 1024-position context, separate passes.  Eager launches
@@ -28,11 +28,11 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python tools/make_traffic_json.py $out $tag > /dev/null 2> $out/traffic.err
 # 3. un-profiled lines: the headline config and the other BASELINE configs
-python bench.py --steps 5 --warmup 1 > $out/${tag}_bench.json 2> $out/bench.err
-python bench.py --steps 5 --warmup 1 --no-prefetch --no-cpu-baseline > $out/${tag}_bench_noprefetch.json 2> $out/bench_noprefetch.err
-python bench.py --steps 3 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline > $out/${tag}_bench_8prompts.json 2> $out/bench_8prompts.err
-python bench.py --steps 2 --warmup 1 --model xl --no-cpu-baseline > $out/${tag}_bench_xl.json 2> $out/bench_xl.err
-python bench.py --steps 5 --warmup 1 --model nano-char --no-cpu-baseline > $out/${tag}_bench_nano_char.json 2> $out/bench_nano_char.err
+python bench.py --full --steps 5 --warmup 1 > $out/${tag}_bench.json 2> $out/bench.err
+python bench.py --full --steps 5 --warmup 1 --no-prefetch --no-cpu-baseline > $out/${tag}_bench_noprefetch.json 2> $out/bench_noprefetch.err
+python bench.py --full --steps 3 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline > $out/${tag}_bench_8prompts.json 2> $out/bench_8prompts.err
+python bench.py --full --steps 2 --warmup 1 --model xl --no-cpu-baseline > $out/${tag}_bench_xl.json 2> $out/bench_xl.err
+python bench.py --full --steps 5 --warmup 1 --model nano-char --no-cpu-baseline > $out/${tag}_bench_nano_char.json 2> $out/bench_nano_char.err
 # 4. the 768x3072 GEMM: kernel trace (durations) + counter passes
 rocprofv3 --kernel-trace --stats -d $out/gtrace -o g -- python3 tools/bench_gemm.py 8192 > $out/gemm_under_rocprof.json 2> $out/gemm_under_rocprof.err
 python tools/rocpd_stats.py $(find $out/gtrace -name "*.db" | head -1) $out/${tag}_gemm_kernel_stats.md > /dev/null
@@ -45,7 +45,7 @@ for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_VALU_MFMA_BUSY
   rm -rf $out/pg_$n
 done
 # 5. GPT-2 XL: kernel trace
-rocprofv3 --kernel-trace --stats -d $out/xtrace -o x -- python3 bench.py --model xl --steps 1 --warmup 1 --no-cpu-baseline > $out/xl_under_rocprof.json 2> $out/xl_under_rocprof.err
+rocprofv3 --kernel-trace --stats -d $out/xtrace -o x -- python3 bench.py --full --model xl --steps 1 --warmup 1 --no-cpu-baseline > $out/xl_under_rocprof.json 2> $out/xl_under_rocprof.err
 python tools/rocpd_stats.py $(find $out/xtrace -name "*.db" | head -1) $out/${tag}_xl_kernel_stats.md > /dev/null
 rm -rf $out/xtrace
 # 6. whole-prompt prefill: timings and kernel trace at 1023 prompt tokens

@@ -23,10 +23,10 @@ pmc() {  # pmc <name> <counter> <command...> -> $out/${tag}_<name>_pmc_<counter>
   done
 }
 # 1. kernel traces of the benchmark commands (full 1024-position context)
-trace 124m python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-trace 124m_noprefetch python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prefetch
-trace 124m_8prompts python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --prompts-per-gpu 8
-trace xl python3 bench.py --model xl --steps 1 --warmup 1 --no-cpu-baseline
+trace 124m python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+trace 124m_noprefetch python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-prefetch
+trace 124m_8prompts python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --prompts-per-gpu 8
+trace xl python3 bench.py --full --model xl --steps 1 --warmup 1 --no-cpu-baseline
 # 2. HBM traffic counters, separate passes, eager launches (tools/pmc_decode.py)
 for c in FETCH_SIZE WRITE_SIZE; do
   pmc 124m $c python3 tools/pmc_decode.py 124M 1
@@ -35,13 +35,13 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python tools/make_traffic_json.py $out $tag > /dev/null 2> $out/traffic.err
 # 3. un-profiled lines of every BASELINE config (+ the two optional modes)
-python bench.py --steps 5 --warmup 1 > $out/${tag}_bench.json 2> $out/bench.err
-python bench.py --steps 5 --warmup 1 --no-prefetch --no-cpu-baseline > $out/${tag}_bench_noprefetch.json 2> $out/bench_noprefetch.err
-python bench.py --steps 3 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline > $out/${tag}_bench_8prompts.json 2> $out/bench_8prompts.err
-python bench.py --steps 3 --warmup 1 --prompts-per-gpu 8 --kv-f16 --no-cpu-baseline > $out/${tag}_bench_8prompts_kvf16.json 2> $out/bench_8prompts_kvf16.err
-python bench.py --steps 2 --warmup 1 --model xl --no-cpu-baseline > $out/${tag}_bench_xl.json 2> $out/bench_xl.err
-python bench.py --steps 5 --warmup 1 --model nano-char --no-cpu-baseline > $out/${tag}_bench_nano_char.json 2> $out/bench_nano_char.err
-python bench.py --steps 3 --warmup 1 --weights-f32 --no-cpu-baseline > $out/${tag}_bench_weights_f32.json 2> $out/bench_weights_f32.err
+python bench.py --full --steps 5 --warmup 1 > $out/${tag}_bench.json 2> $out/bench.err
+python bench.py --full --steps 5 --warmup 1 --no-prefetch --no-cpu-baseline > $out/${tag}_bench_noprefetch.json 2> $out/bench_noprefetch.err
+python bench.py --full --steps 3 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline > $out/${tag}_bench_8prompts.json 2> $out/bench_8prompts.err
+python bench.py --full --steps 3 --warmup 1 --prompts-per-gpu 8 --kv-f16 --no-cpu-baseline > $out/${tag}_bench_8prompts_kvf16.json 2> $out/bench_8prompts_kvf16.err
+python bench.py --full --steps 2 --warmup 1 --model xl --no-cpu-baseline > $out/${tag}_bench_xl.json 2> $out/bench_xl.err
+python bench.py --full --steps 5 --warmup 1 --model nano-char --no-cpu-baseline > $out/${tag}_bench_nano_char.json 2> $out/bench_nano_char.err
+python bench.py --full --steps 3 --warmup 1 --weights-f32 --no-cpu-baseline > $out/${tag}_bench_weights_f32.json 2> $out/bench_weights_f32.err
 # 4. the 768x3072 GEMM: kernel trace (durations) + counter passes, both kernel generations
 for k in s4 p8; do
   ZGPT2_GEMM_KERNEL=$k trace gemm_$k python3 tools/bench_gemm.py 8192

@@ -23,19 +23,19 @@ pmc() {
     if [ -s $out/${tag}_${name}_pmc_$c.md.new ]; then mv $out/${tag}_${name}_pmc_$c.md.new $out/${tag}_${name}_pmc_$c.md; break; fi
   done
 }
-python bench.py --steps 5 --warmup 1 > $out/${tag}_bench.json 2> $out/bench.err
-python bench.py --steps 3 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline > $out/${tag}_bench_8prompts.json 2> $out/bench_8prompts.err
-python bench.py --steps 3 --warmup 1 --prompts-per-gpu 8 --kv-f16 --no-cpu-baseline > $out/${tag}_bench_8prompts_kvf16.json 2> $out/bench_8prompts_kvf16.err
-python bench.py --steps 3 --warmup 1 --prompts-per-gpu 8 --kv-b24 --no-cpu-baseline > $out/${tag}_bench_8prompts_kvb24.json 2> $out/bench_8prompts_kvb24.err
-python bench.py --steps 3 --warmup 1 --weights-f32 --no-cpu-baseline > $out/${tag}_bench_weights_f32.json 2> $out/bench_weights_f32.err
-trace 124m python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs
+python bench.py --full --steps 5 --warmup 1 > $out/${tag}_bench.json 2> $out/bench.err
+python bench.py --full --steps 3 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline > $out/${tag}_bench_8prompts.json 2> $out/bench_8prompts.err
+python bench.py --full --steps 3 --warmup 1 --prompts-per-gpu 8 --kv-f16 --no-cpu-baseline > $out/${tag}_bench_8prompts_kvf16.json 2> $out/bench_8prompts_kvf16.err
+python bench.py --full --steps 3 --warmup 1 --prompts-per-gpu 8 --kv-b24 --no-cpu-baseline > $out/${tag}_bench_8prompts_kvb24.json 2> $out/bench_8prompts_kvb24.err
+python bench.py --full --steps 3 --warmup 1 --weights-f32 --no-cpu-baseline > $out/${tag}_bench_weights_f32.json 2> $out/bench_weights_f32.err
+trace 124m python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs
 for c in FETCH_SIZE WRITE_SIZE; do
   pmc 124m $c python3 tools/pmc_decode.py 124M 1
   pmc 124m_8prompts $c python3 tools/pmc_decode.py 124M 8
   pmc xl $c python3 tools/pmc_decode.py xl 1
 done
-trace 124m_8prompts python3 bench.py --steps 2 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline
-trace xl python3 bench.py --model xl --steps 1 --warmup 1 --no-cpu-baseline
+trace 124m_8prompts python3 bench.py --full --steps 2 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline
+trace xl python3 bench.py --full --model xl --steps 1 --warmup 1 --no-cpu-baseline
 python tools/make_traffic_json.py $out $tag > /dev/null 2> $out/traffic.err
 ZGPT2_GEMM_KERNEL=s4 trace gemm_s4 python3 tools/bench_gemm.py 8192
 : > $out/${tag}_gemm_s4_pmc.md

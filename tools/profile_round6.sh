@@ -25,11 +25,11 @@ pmc() {
   done
 }
 if has bench; then
-  python bench.py --steps 5 --warmup 1 > $out/${tag}_bench.json 2> $out/bench.err
-  python bench.py --steps 3 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline --no-op-tier > $out/${tag}_bench_8prompts.json 2> $out/bench_8prompts.err
+  python bench.py --full --steps 5 --warmup 1 > $out/${tag}_bench.json 2> $out/bench.err
+  python bench.py --full --steps 3 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline --no-op-tier > $out/${tag}_bench_8prompts.json 2> $out/bench_8prompts.err
 fi
 if has trace; then
-  trace 124m python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --no-op-tier
+  trace 124m python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --no-op-tier
   rm -rf $out/tr_124m
 fi
 if has traffic; then
@@ -38,8 +38,8 @@ if has traffic; then
     pmc 124m_8prompts $c python3 tools/pmc_decode.py 124M 8
     pmc xl $c python3 tools/pmc_decode.py xl 1
   done
-  trace 124m_8prompts python3 bench.py --steps 2 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline --no-op-tier; rm -rf $out/tr_124m_8prompts
-  trace xl python3 bench.py --model xl --steps 1 --warmup 1 --no-cpu-baseline --no-op-tier; rm -rf $out/tr_xl
+  trace 124m_8prompts python3 bench.py --full --steps 2 --warmup 1 --prompts-per-gpu 8 --no-cpu-baseline --no-op-tier; rm -rf $out/tr_124m_8prompts
+  trace xl python3 bench.py --full --model xl --steps 1 --warmup 1 --no-cpu-baseline --no-op-tier; rm -rf $out/tr_xl
   python tools/make_traffic_json.py $out $tag > /dev/null 2> $out/traffic.err
 fi
 if has gemm; then
