@@ -77,6 +77,11 @@ struct zg_gpt {
     size_t sk_tag_bytes, part_tag_bytes;
     size_t epochs_since_clear;  // steps enqueued since the tagged words were last zeroed (note_steps)
     bool tags_on;
+    // one sequence: ln_1 + c_attn and the attention of a layer as ONE launch (attn_qkv.hip), q and the new k / v row handed over as
+    // (value, tag) words [3 E] (tags as above: the embed kernel advances the epoch)
+    unsigned long long* qkv_tag;
+    size_t qkv_tag_bytes;
+    bool fused_on;
     // LayerNorm statistics of x by 16-column tile, written by the producers of x (GemvArgs.st_out / st_in)
     float* xst;
     bool st_on;
@@ -217,6 +222,8 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
     g->sk_tag_bytes = ((E + 15) / 16) * 4 * 128 * 8;
     g->part_tag_bytes = 8 * c.n_heads * g->max_splits * kPartStride * 8;
     g->sk_tag = (unsigned long long*)P(g->sk_tag_bytes);
+    g->qkv_tag_bytes = 3 * E * 8;
+    g->qkv_tag = (unsigned long long*)P(g->qkv_tag_bytes);
     g->part_tag = (unsigned long long*)P(g->part_tag_bytes);
     g->sk_tiles = (int)((E + 15) / 16);
     g->sk_ws = (float*)P((size_t)g->sk_tiles * 4 * 128 * 4);
@@ -297,7 +304,7 @@ EmbedArgs embed_args(const zg_gpt* g, int finish_only) {
     e.x = g->x;
     e.pl_out = g->pl_on ? g->xp : nullptr;
     e.pl_g = g->layers[0].ln_1_g;
-    e.epoch = (g->pl_on && g->tags_on && finish_only != 1 && finish_only != 2) ? g->epoch : nullptr;
+    e.epoch = (((g->pl_on && g->tags_on) || g->fused_on) && finish_only != 1 && finish_only != 2) ? g->epoch : nullptr;
     e.st_out = g->st_on ? g->xst : nullptr;
     e.finish_only = finish_only;
     e.progress = g->pf_on ? &g->pf_ctl->progress : nullptr;
@@ -400,6 +407,49 @@ int ensure_ln_folded(zg_gpt* g, hipStream_t s) {
 // layer, so that consecutive launches of the chain never find each other's tags.
 int env_int(const char* name, int dflt);
 
+// ln_1 + c_attn + split_qkv + cache append (main.zig:121-123, ops.zig:143-157) and the attention over the cache (ops.zig:160 ->
+// :249-307) of layer y: the arguments of their launches
+GemvArgs c_attn_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
+    const size_t E = g->cfg.n_embed;
+    GemvArgs a = base_gemv(g, y.c_attn_w, y.c_attn_b, 3 * E, E, t_hi);
+    a.prologue = PRO_LAYERNORM;
+    a.x = g->x;
+    a.x_stride = (int)E;
+    a.ln_g = y.ln_1_g;
+    a.ln_b = y.ln_1_b;
+    a.ln_c2 = y.c_attn_c2;
+    a.ln_c3 = y.c_attn_c3;
+    a.epilogue = EPI_QKV;
+    a.pl_in = g->pl_on ? g->xp : nullptr;
+    a.st_in = g->st_on ? g->xst : nullptr;
+    a.q = g->q;
+    a.k_cache = y.k_cache;
+    a.v_cache = y.v_cache;
+    return a;
+}
+
+AttnArgs attn_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
+    const size_t E = g->cfg.n_embed;
+    AttnArgs a{};
+    a.q = g->q;
+    a.k = y.k_cache;
+    a.v = y.v_cache;
+    a.stride_b = (long)(g->cfg.context_size * E);
+    a.stride_h = (long)(g->cfg.context_size * 64);
+    a.stride_t = 64;
+    a.kv_mode = g->kv_mode;
+    a.kv_lo = g->batch * g->cfg.context_size * E * 2;
+    a.n_heads = (int)g->cfg.n_heads;
+    a.head_dim = 64;
+    a.batch = (int)g->batch;
+    a.ctrl = g->ctrl;
+    a.t_hi = t_hi;
+    a.max_splits = g->max_splits;
+    a.part = g->part;
+    a.progress = g->pf_on ? &g->pf_ctl->progress : nullptr;
+    return a;
+}
+
 int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, StepProf* prof = nullptr, int only = -1, size_t only_layer = 0,
                  std::vector<PfJob>* rec = nullptr, int salt = -1, bool with_sampler = false) {
     const size_t E = g->cfg.n_embed;
@@ -413,43 +463,26 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, StepProf*
     ZG_TRY(prof_mark(prof, 0, s));
     for (size_t l = (only < 0 ? 0 : only_layer); l < (only < 0 ? g->cfg.n_layer : only_layer + 1); ++l) {
         const zg_layer& y = g->layers[l];
-        if (only < 0 || only == 1) {   // ln_1 + c_attn + split_qkv + cache append: main.zig:121-123, ops.zig:143-157
-            GemvArgs a = base_gemv(g, y.c_attn_w, y.c_attn_b, 3 * E, E, t_hi);
-            a.prologue = PRO_LAYERNORM;
-            a.x = g->x;
-            a.x_stride = (int)E;
-            a.ln_g = y.ln_1_g;
-            a.ln_b = y.ln_1_b;
-            a.ln_c2 = y.c_attn_c2;
-            a.ln_c3 = y.c_attn_c3;
-            a.epilogue = EPI_QKV;
-            a.pl_in = g->pl_on ? g->xp : nullptr;
-            a.st_in = g->st_on ? g->xst : nullptr;
-            a.q = g->q;
-            a.k_cache = y.k_cache;
-            a.v_cache = y.v_cache;
+        // one sequence: classes 1 and 2 as one launch (attn_qkv.hip), timed as class 1; the prefetcher's table keeps both entries
+        const bool fused = g->fused_on && !rec && 2 * l + 2 <= 255;
+        if (fused && (only < 0 || only == 1)) {
+            GemvArgs a = c_attn_args(g, y, t_hi);
+            AttnArgs at = attn_args(g, y, t_hi);
+            at.launch_id = launch_id(l, 0);
+            at.fault = g->fault;
+            at.spin_limit = g->spin_limit;
+            ZG_TRY(launch_attn_qkv(a, g->wt, at, g->epoch, g->qkv_tag, s));
+            ZG_TRY(prof_mark(prof, 1, s));
+            ZG_TRY(prof_mark(prof, 2, s));
+        }
+        if (!fused && (only < 0 || only == 1)) {   // ln_1 + c_attn + split_qkv + cache append: main.zig:121-123, ops.zig:143-157
+            GemvArgs a = c_attn_args(g, y, t_hi);
             const int grid = gemv_plan(a, g->wt);
             ZG_TRY(emit_gemv(g, a, grid, s, rec, 1));
             ZG_TRY(prof_mark(prof, 1, s));
         }
-        if (only < 0 || only == 2) {   // scaled_dot_product_attention over the cache: ops.zig:160 -> :249-307
-            AttnArgs a{};
-            a.q = g->q;
-            a.k = y.k_cache;
-            a.v = y.v_cache;
-            a.stride_b = (long)(g->cfg.context_size * E);
-            a.stride_h = (long)(g->cfg.context_size * 64);
-            a.stride_t = 64;
-            a.kv_mode = g->kv_mode;
-            a.kv_lo = g->batch * g->cfg.context_size * E * 2;
-            a.n_heads = (int)g->cfg.n_heads;
-            a.head_dim = 64;
-            a.batch = (int)g->batch;
-            a.ctrl = g->ctrl;
-            a.t_hi = t_hi;
-            a.max_splits = g->max_splits;
-            a.part = g->part;
-            a.progress = g->pf_on ? &g->pf_ctl->progress : nullptr;
+        if ((!fused && only < 0) || only == 2) {   // scaled_dot_product_attention over the cache: ops.zig:160 -> :249-307
+            AttnArgs a = attn_args(g, y, t_hi);
             if (g->pl_on) {
                 a.pl_out = g->ap;
                 a.merge_cnt = g->attn_cnt;
@@ -620,7 +653,7 @@ int check_fault(zg_gpt* g) {
         g->sk_used = false;
         ZG_TRY(gemm_s4_fault(&sk));
     }
-    if (g->tags_on) {
+    if (g->tags_on || g->fused_on) {
         volatile unsigned* f = g->fault;
         tag = *f;
         if (tag) *f = 0;
@@ -641,12 +674,13 @@ int check_fault(zg_gpt* g) {
 // host counts the steps it enqueues and zeroes the tagged words (tag 0 is never valid: launch ids start at 1) on the stream
 // every 2^23 of them, in front of the steps of the call that crosses the mark.
 int note_steps(zg_gpt* g, size_t n, hipStream_t s) {
-    if (!g->tags_on) return ZG_OK;
+    if (!g->tags_on && !g->fused_on) return ZG_OK;
     g->epochs_since_clear += n;
     if (g->epochs_since_clear < ((size_t)1 << 23)) return ZG_OK;
     g->epochs_since_clear = n;
     ZG_HIP(hipMemsetAsync(g->sk_tag, 0, g->sk_tag_bytes, s));
     ZG_HIP(hipMemsetAsync(g->part_tag, 0, g->part_tag_bytes, s));
+    ZG_HIP(hipMemsetAsync(g->qkv_tag, 0, g->qkv_tag_bytes, s));
     return ZG_OK;
 }
 
@@ -972,6 +1006,10 @@ int zg_gpt_create_ex(zg_gpt** out, const zg_gpt_config* config, size_t batch, un
     }
     g->tags_on = g->pl_on && !(decode_paths_off() & 4);
     g->spin_limit = (unsigned)env_int("ZGPT2_TAG_SPIN_LIMIT", 1 << 20);
+    // one sequence on the fp32 cache: ln_1 + c_attn and the attention as one launch where c_attn runs on the LayerNorm-folding
+    // kernel (ZGPT2_DECODE_PATHS_OFF bit 64: two launches)
+    g->fused_on = batch == 1 && !(decode_paths_off() & 64) && c.n_layer <= 127 &&
+                  attn_qkv_ok(c_attn_args(g, g->layers[0], 0), attn_args(g, g->layers[0], (int)c.context_size));
     g->st_on = false;
     if (g->pl_on && !(decode_paths_off() & 8) && c.n_embed % 16 == 0 && c.n_embed / 16 <= 128) {
         // every producer and consumer of x must be the four-wave kernel
@@ -1665,7 +1703,7 @@ int zg_gpt_time_kernel(zg_gpt* g, int which_and_options, int iters, float* avg_u
     int st = ZG_OK;
     // tagged hand-overs: a new epoch per replay and a launch id per chain position, so that every merging split / slice
     // waits for ITS writers as in a real step (one more tiny launch per 64)
-    if (g->tags_on && which != 0) st = launch_epoch_bump(g->epoch, s);
+    if ((g->tags_on || g->fused_on) && which != 0) st = launch_epoch_bump(g->epoch, s);
     for (int i = 0; i < chain && st == ZG_OK; ++i)
         st = enqueue_step(g, true, bucket_t_hi(g, T), s, nullptr, which, cycle ? (size_t)i % g->cfg.n_layer : 0, nullptr, i);
     hipError_t ce = hipStreamEndCapture(s, &graph);

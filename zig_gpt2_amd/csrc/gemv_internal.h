@@ -372,6 +372,134 @@ inline int pl4_pairs(const GemvArgs& a) {
     return kp <= 5 ? kp : 0;
 }
 
+// Body of gemv_lnk_kernel (gemv_ksplit.hip; the LayerNorm fold is described there), shared with the c_attn role of the fused
+// ln_1 + c_attn + attention kernel (attn_qkv.hip).  blk = the workgroup's row block; pf_inc = what block 0 adds to the
+// prefetcher's launch counter.  TAGGED (EPI_QKV, one sequence): every output row is also stored as a (value, tag) word at
+// tagw[n], tag = *ew << 8 | launch_id, with an agent-scope relaxed store — the hand-over to the attention workgroups of the
+// same launch.  The value is the one the epilogue stored to q / the caches.
+template <typename WT, int LPR, int CPL, int NP, bool TAGGED>
+__device__ __forceinline__ void gemv_lnk_body(int blk, const void* __restrict__ Wv, const float* __restrict__ xin, unsigned ne, int K,
+                                              const float* __restrict__ ln_g, const float* __restrict__ c2, const float* __restrict__ c3,
+                                              const int* __restrict__ cw, const GemvArgs& a, unsigned pf_inc,
+                                              unsigned long long* __restrict__ tagw, const unsigned* __restrict__ ew, unsigned launch_id) {
+    const int N = (int)(ne & 0xffffffu), epilogue = (int)(ne >> 24);
+    ZG_STAMP_DECL();
+    ZG_STAMP(0);
+    constexpr int RPP = 64 / LPR, ROWS = NP * RPP;
+    __shared__ float part[4][ROWS];
+    __shared__ float stat[4][2];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane % LPR, rsub = lane / LPR;
+    // The wave's share of K.  bf16 rows of whole 128-byte lines (K % 64 == 0): whole lines per wave — 7, 6, 6, 6 of
+    // the 25 at K = 1600 instead of four times 6.25, whose quarters begin mid-line and make every wave touch the
+    // boundary lines of its neighbours as well (31 line touches per row instead of 25).
+    int kbeg, nchq;
+    if (sizeof(WT) == 2 && (K & 63) == 0 && ((K >> 6) & 3) != 0 && (((K >> 6) >> 2) + 1) * 8 <= LPR * CPL) {
+        const int lines = K >> 6, base = lines >> 2, rem = lines & 3;
+        kbeg = (wave * base + min(wave, rem)) * 64;
+        nchq = (base + (wave < rem ? 1 : 0)) * 8;
+    } else {
+        kbeg = wave * (K >> 2);
+        nchq = K >> 5;
+    }
+    const WT* W = reinterpret_cast<const WT*>(Wv) + kbeg;
+    const int row0 = blk * ROWS;
+    Raw<WT> wq[NP][CPL];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const WT* pr = W + (size_t)min(row0 + p * RPP + rsub, N - 1) * K;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) wq[p][i] = load_raw(pr, min(lr + LPR * i, nchq - 1));
+    }
+    W8 xr[CPL], gr[CPL];
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        const size_t off = (size_t)kbeg + (size_t)min(lr + LPR * i, nchq - 1) * 8;
+        xr[i] = load_x8(xin + off);
+        gr[i] = load_x8(ln_g + off);
+    }
+    float c2n = 0.0f, c3n = 0.0f;
+    if (tid < ROWS) {
+        const int n = min(row0 + tid, N - 1);
+        c2n = c2[n];
+        c3n = c3[n];
+    }
+    const int T = max(cw[1], 1);  // KV append position (EPI_QKV)
+    const unsigned epoch = TAGGED ? ew[0] : 0u;
+    ZG_STAMP(1);
+    {   // the argument-block fields of the tail, fetched under the vector loads (zg_common.h ZG_PIN)
+        ZG_PIN(a.progress); ZG_PIN(a.y); ZG_PIN(a.y_stride); ZG_PIN(a.epilogue); ZG_PIN(__float_as_uint(a.eps));
+        if (epilogue == EPI_QKV) {
+            ZG_PIN(a.q); ZG_PIN(a.k_cache); ZG_PIN(a.v_cache); ZG_PIN(a.N); ZG_PIN(a.head_dim); ZG_PIN(a.n_heads); ZG_PIN(a.ctx); ZG_PIN(a.kv_mode); ZG_PIN(a.kv_lo);
+        }
+    }
+    if (TAGGED) { ZG_PIN(tagw); ZG_PIN(launch_id); }
+    pf_count(a.progress, pf_inc);
+    ZG_STAMP(2);
+    // statistics of this wave's quarter (every LPR-lane group holds the whole quarter) and z = g x
+    float sx = 0.0f, sxx = 0.0f;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        if (lr + LPR * i >= nchq) xr[i] = zero_w8();  // clamped surplus chunks contribute nothing
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            sx += xr[i].v[j];
+            sxx = fmaf(xr[i].v[j], xr[i].v[j], sxx);
+            xr[i].v[j] *= gr[i].v[j];
+        }
+    }
+    sx = group_allsum<LPR>(sx);
+    sxx = group_allsum<LPR>(sxx);
+    auto dot = [&](const Raw<WT>(&w)[CPL]) {
+        float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const W8 u = unpack(w[i]);
+            p0 = fmaf(u.v[0], xr[i].v[0], p0); p1 = fmaf(u.v[1], xr[i].v[1], p1);
+            p2 = fmaf(u.v[2], xr[i].v[2], p2); p3 = fmaf(u.v[3], xr[i].v[3], p3);
+            p0 = fmaf(u.v[4], xr[i].v[4], p0); p1 = fmaf(u.v[5], xr[i].v[5], p1);
+            p2 = fmaf(u.v[6], xr[i].v[6], p2); p3 = fmaf(u.v[7], xr[i].v[7], p3);
+        }
+        return group_allsum<LPR>((p0 + p1) + (p2 + p3));
+    };
+    float sp[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) sp[p] = dot(wq[p]);
+    ZG_STAMP(3);
+    if (lr == 0) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) part[wave][p * RPP + rsub] = sp[p];
+    }
+    if (lane == 0) {
+        stat[wave][0] = sx;
+        stat[wave][1] = sxx;
+    }
+    __syncthreads();
+    ZG_STAMP(4);
+    if (tid < ROWS && row0 + tid < N) {
+        const int n = row0 + tid;
+        const float inv_k = 1.0f / (float)K;
+        const float mean = ((stat[0][0] + stat[1][0]) + (stat[2][0] + stat[3][0])) * inv_k;
+        // E[x^2] - mean^2 spelled out as ONE contraction (fmaf(inv_k, sum x^2, -mean^2)): left to the compiler, the contraction
+        // it picks depends on the surrounding kernel, and the fused c_attn role (attn_qkv.hip) must round as this kernel does
+        const float msq = mean * mean;
+        const float var = fmaf(((stat[0][1] + stat[1][1]) + (stat[2][1] + stat[3][1])), inv_k, -msq);
+        const float rstd = __builtin_amdgcn_rsqf(var + a.eps);
+        const float S1 = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+        const float y = fmaf(rstd, fmaf(-mean, c2n, S1), c3n);
+        Best nobest;
+        const float v = epilogue_row(a, 0, n, y, 0.0f, 0.0f, T - 1, nobest);
+        if (TAGGED)
+            __hip_atomic_store(tagw + n, ((unsigned long long)((epoch << 8) | launch_id) << 32) | __float_as_uint(v), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+    ZG_STAMP(5);
+    ZG_STAMP(6);
+    ZG_STAMP(7);
+    ZG_STAMP_FLUSH();
+}
+
 }  // namespace
 
 // ---- launchers of the units (gemv.hip decides which one a launch takes)

@@ -140,6 +140,12 @@ struct AttnArgs {
     unsigned spin_limit;
 };
 int launch_attn_decode(const AttnArgs& a, hipStream_t s);
+// One sequence, fp32 cache, head_dim 64, c_attn on the LayerNorm-folding kernel: ln_1 + c_attn + KV append (g, EPI_QKV) and the
+// attention (at) of the same layer in one launch (attn_qkv.hip).  q and the new k / v row reach the attention workgroups as
+// (value, tag) words in qkv_tag [3 E], tag = *epoch << 8 | at.launch_id; a timed-out wait raises at.fault.  Same results,
+// bit for bit, as launch_gemv + launch_attn_decode.
+bool attn_qkv_ok(const GemvArgs& g, const AttnArgs& at);
+int launch_attn_qkv(const GemvArgs& g, int weight_type, const AttnArgs& at, const unsigned* epoch, unsigned long long* qkv_tag, hipStream_t s);
 // the op tier's general path for head_dim != 64 (fp32, one workgroup per (sequence, head))
 int launch_attn_any_dim(const float* q, const float* k, const float* v, long stride_b, long stride_h, long stride_t, int batch, int n_heads,
                         int head_dim, int seq_len, float* out, hipStream_t s);
@@ -351,14 +357,15 @@ struct PfArgs {
 };
 int launch_prefetcher(const PfArgs& a, hipStream_t s);
 
-// Every decode kernel counts itself in at entry (one lane of block 0; fire and forget).
-__device__ __forceinline__ void pf_count(unsigned* progress) {
+// Every decode kernel counts itself in at entry (one lane of block 0; fire and forget).  A launch that does the work of n
+// launches of the job table (the fused ln_1 + c_attn + attention kernel: 2) counts n.
+__device__ __forceinline__ void pf_count(unsigned* progress, unsigned n = 1u) {
     if (progress != nullptr && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) {
 #ifdef ZG_STAMPS
-        const unsigned old = __hip_atomic_fetch_add(progress, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned old = __hip_atomic_fetch_add(progress, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         reinterpret_cast<PfCtl*>(progress)->xcd_log[old & 255u] = 0x100u | (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u);
 #else
-        __hip_atomic_fetch_add(progress, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(progress, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
     }
 }
