@@ -205,10 +205,15 @@ enum {
                                     identical either way; a measurement switch) */
     ZG_GPT_SAMPLED_GENERATE = 1 << 7, /* capture the decode graphs of zg_gpt_generate_sample_* at create as well (otherwise they are
                                       captured by the first sampled generation: the one place a generate call may allocate) */
-    ZG_GPT_KV_B24 = 1 << 6       /* store the KV cache as 24-bit floats (the fp32 value rounded to 16 mantissa bits, kept as a
+    ZG_GPT_KV_B24 = 1 << 6,      /* store the KV cache as 24-bit floats (the fp32 value rounded to 16 mantissa bits, kept as a
                                     bf16 plane + a plane of 8 more mantissa bits): 3/4 of the fp32 cache's traffic, 2^-17 per
                                     cached element — inside the 1e-3 parity bound at full context, unlike ZG_GPT_KV_F16 (which
                                     it excludes) */
+    ZG_GPT_WEIGHTS_B24 = 1 << 8  /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
+                                    value rounded to nearest even at 16 mantissa bits (never to inf), row r of an [out][in]
+                                    matrix = [in bf16-shaped upper halves | in low bytes].  3/4 of fp32's weight bytes, 2^-17
+                                    per weight — for fp32 checkpoints, which bf16 storage takes outside the 1e-3 bound.
+                                    Vectors stay fp32.  Excludes ZG_GPT_WEIGHTS_F32 (ZG_ERR_ARG) */
 };
 
 /* Per-block tensor slots (load_block, src/main.zig:271-302) and top-level slots (load_gpt,

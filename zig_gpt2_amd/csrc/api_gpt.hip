@@ -25,7 +25,7 @@ using namespace zg;
 
 struct zg_layer {
     void *c_attn_w, *c_proj_w, *c_fc_w, *mlp_proj_w;
-    // ZG_GPT_WEIGHTS_F32 handles only: the same matrices split exactly into bf16 planes [out][3 in] = [hi | mid | lo]
+    // ZG_GPT_WEIGHTS_F32 / _B24 handles only: the same matrices (the stored values) split exactly into bf16 planes [out][3 in] = [hi | mid | lo]
     // (filled when the tensor is loaded) — the B operand of the whole-prompt GEMMs
     bf16_t *c_attn_p, *c_proj_p, *c_fc_p, *mlp_proj_p;
     // LayerNorm folded out of the two LayerNorm-fed Linears (gemv_ksplit.hip, gemv_lnk_kernel): c2 = W g, c3 = W b + bias
@@ -38,9 +38,9 @@ struct zg_gpt {
     zg_gpt_config cfg;
     size_t batch;
     unsigned flags;
-    int wt;        // WT_BF16 / WT_F32
+    int wt;        // WT_BF16 / WT_F32 / WT_B24
     int kv_mode;
-    size_t wbytes;  // bytes per matrix element
+    size_t wbytes;  // bytes per matrix element (B24: 3, a row is [K upper halves | K low bytes])
     char* arena;
     size_t arena_bytes, weight_region_bytes, state_bytes;  // arena = [weight region (absent when borrowed) | state]
     size_t kv_region_bytes;  // the KV caches of all layers: one contiguous stretch of the arena from layers[0].k_cache
@@ -182,7 +182,7 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
         y.c_fc_c2 = (float*)P(4 * E * 4);
         y.c_fc_c3 = (float*)P(4 * E * 4);
         y.c_attn_p = y.c_proj_p = y.c_fc_p = y.mlp_proj_p = nullptr;
-        if (g->wt == WT_F32 && !(g->flags & ZG_GPT_NO_PREFILL)) {  // inside the weight region: broadcast with the weights
+        if (g->wt != WT_BF16 && !(g->flags & ZG_GPT_NO_PREFILL)) {  // inside the weight region: broadcast with the weights
             y.c_attn_p = (bf16_t*)P(3 * E * E * kSplit * 2);
             y.c_proj_p = (bf16_t*)P(E * E * kSplit * 2);
             y.c_fc_p = (bf16_t*)P(4 * E * E * kSplit * 2);
@@ -597,13 +597,13 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, StepProf*
 // pf_x.  With `last_block_full` false the last Block stops after its cache append: nothing downstream of
 // it is needed when generation re-feeds the last prompt token (main.zig:337).
 // fp32 weights (ZG_GPT_WEIGHTS_F32): the same pass; the weight operand is then the exact three-term bf16 split of the fp32
-// matrix (plane-major, made when the tensor is loaded) and every GEMM runs as three partial passes of the same kernel — the
+// matrix (plane-major, made when the tensor is loaded; B24 weights: the split of the 24-bit values, the same pass) and every GEMM runs as three partial passes of the same kernel — the
 // six plane products above 2^-24 of the leading one, fp32-sgemm grade (prefill.hip launch_prefill_gemm_wp).
 // (Measured and dropped in round 4: replaying this pass from a hipGraph per prompt length.  0.844 against 0.749 ms at 64
 // tokens, 1.645 against 1.553 ms at 1023 — the ~10 us a launch costs here is the kernels' own latency at these sizes, not host
 // overhead, and a graph launch adds its own ~10 us; profiles/round4_prefill_graph.jsonl.)
 int enqueue_prefill(zg_gpt* g, size_t P, bool last_block_full, hipStream_t s) {
-    const bool f32w = g->wt == WT_F32;
+    const bool f32w = g->wt != WT_BF16;
     const int np = f32w ? kWeightPlanes : (g->flags & ZG_GPT_PREFILL_2PLANE) ? 2 : kSplit;
     const size_t E = g->cfg.n_embed, L = g->cfg.n_layer, H = g->cfg.n_heads, C = g->cfg.context_size;
     const int B = (int)g->batch, M = (int)(g->batch * P), iE = (int)E;
@@ -903,6 +903,28 @@ int upload_f32(const float* src, size_t n, void* dst, bool as_bf16, hipStream_t 
     return ZG_OK;
 }
 
+// A matrix of n = rows K fp32 elements (host or device) into B24 rows (zg_common.h b24_t), rounded on the device.  Whole rows at a
+// time pass through the staging arena (also from device memory: the packer's 16-B loads then start aligned).  planes (optional):
+// the plane-major split of the stored values for the whole-prompt GEMMs, made from the B24 matrix itself.
+int upload_b24(const float* src, size_t n, size_t K, void* dst, bf16_t* planes, hipStream_t s) {
+    Ctx& c = ctx();
+    ZG_REQUIRE(K > 0 && K % 8 == 0 && n % K == 0 && K <= 65536, ZG_ERR_SHAPE, "B24 matrix: %zu elements in rows of %zu", n, K);
+    const size_t rows = n / K, cap_rows = c.stage_cap / (4 * K);
+    ZG_REQUIRE(cap_rows > 0, ZG_ERR_STAGING, "no staging arena for a %zu-float row", K);
+    const hipMemcpyKind kind = is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    for (size_t r = 0; r < rows; r += cap_rows) {
+        const size_t m = rows - r < cap_rows ? rows - r : cap_rows;
+        ZG_HIP(hipMemcpyAsync(c.stage, src + r * K, m * K * 4, kind, s));
+        ZG_TRY(launch_f32_to_b24(reinterpret_cast<const float*>(c.stage), m, (int)K, reinterpret_cast<char*>(dst) + r * 3 * K, s));
+        ZG_HIP(hipStreamSynchronize(s));
+    }
+    if (planes) {
+        ZG_TRY(launch_b24_split3(dst, rows, (int)K, planes, s));
+        ZG_HIP(hipStreamSynchronize(s));
+    }
+    return ZG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -919,7 +941,7 @@ int zg_gpt_create_ex(zg_gpt** out, const zg_gpt_config* config, size_t batch, un
     if (parent) {
         ZG_REQUIRE(parent->parent == nullptr, ZG_ERR_ARG, "zg_gpt_create_ex: share_weights_with must own its weights");
         ZG_REQUIRE(memcmp(&parent->cfg, config, sizeof(zg_gpt_config)) == 0, ZG_ERR_SHAPE, "zg_gpt_create_ex: a handle shares weights with one of the same config only");
-        const unsigned same = ZG_GPT_WEIGHTS_F32 | ZG_GPT_NO_PREFILL;  // what decides the layout of the weight region
+        const unsigned same = ZG_GPT_WEIGHTS_F32 | ZG_GPT_WEIGHTS_B24 | ZG_GPT_NO_PREFILL;  // what decides the layout of the weight region
         ZG_REQUIRE((parent->flags & same) == (flags & same), ZG_ERR_ARG, "zg_gpt_create_ex: weight type / prefill flags differ from the weight owner's");
     }
     ZG_REQUIRE(c.n_heads > 0 && c.n_embed % c.n_heads == 0 && c.n_embed / c.n_heads == 64, ZG_ERR_UNSUPPORTED,
@@ -928,12 +950,14 @@ int zg_gpt_create_ex(zg_gpt** out, const zg_gpt_config* config, size_t batch, un
     ZG_REQUIRE(batch >= 1 && batch <= 8, ZG_ERR_UNSUPPORTED, "batch %zu outside 1..8", batch);
     ZG_REQUIRE(c.vocab_size > 0 && c.context_size > 0 && c.n_layer > 0, ZG_ERR_ARG, "empty config");
     ZG_REQUIRE(!(flags & ZG_GPT_KV_F16) || !(flags & ZG_GPT_KV_B24), ZG_ERR_ARG, "ZG_GPT_KV_F16 and ZG_GPT_KV_B24 exclude each other");
+    ZG_REQUIRE(!(flags & ZG_GPT_WEIGHTS_F32) || !(flags & ZG_GPT_WEIGHTS_B24), ZG_ERR_ARG,
+               "ZG_GPT_WEIGHTS_F32 and ZG_GPT_WEIGHTS_B24 exclude each other");
     zg_gpt* g = new zg_gpt();
     g->cfg = c;
     g->batch = batch;
     g->flags = flags;
-    g->wt = (flags & ZG_GPT_WEIGHTS_F32) ? WT_F32 : WT_BF16;
-    g->wbytes = g->wt == WT_BF16 ? 2 : 4;
+    g->wt = (flags & ZG_GPT_WEIGHTS_F32) ? WT_F32 : (flags & ZG_GPT_WEIGHTS_B24) ? WT_B24 : WT_BF16;
+    g->wbytes = g->wt == WT_BF16 ? 2 : g->wt == WT_B24 ? 3 : 4;
     g->kv_mode = (flags & ZG_GPT_KV_F16) ? 1 : (flags & ZG_GPT_KV_B24) ? 2 : 0;
     g->max_splits = (int)((c.context_size + kAttnChunk - 1) / kAttnChunk);
     g->graph_stream = nullptr;
@@ -1133,6 +1157,10 @@ int zg_gpt_load_block_tensor(zg_gpt* g, size_t layer, int slot, const float* src
     }
     ZG_REQUIRE(len == n, ZG_ERR_SHAPE, "block slot %d expects %zu elements, got %zu", slot, n, len);
     g->ln_folded = false;
+    if (mat && g->wt == WT_B24) {
+        bf16_t* pl = slot == ZG_C_ATTN_W ? y.c_attn_p : slot == ZG_C_PROJ_W ? y.c_proj_p : slot == ZG_C_FC_W ? y.c_fc_p : y.mlp_proj_p;
+        return upload_b24(src, n, slot == ZG_MLP_PROJ_W ? 4 * E : E, dst, y.c_attn_p ? pl : nullptr, gs(g));  // K = the input width
+    }
     ZG_TRY(upload_f32(src, n, dst, mat && g->wt == WT_BF16, gs(g)));
     if (mat && g->wt == WT_F32 && y.c_attn_p) {  // exact bf16 planes of the fp32 matrix for the whole-prompt GEMMs
         bf16_t* pl = slot == ZG_C_ATTN_W ? y.c_attn_p : slot == ZG_C_PROJ_W ? y.c_proj_p : slot == ZG_C_FC_W ? y.c_fc_p : y.mlp_proj_p;
@@ -1161,6 +1189,7 @@ int zg_gpt_load_tensor(zg_gpt* g, int slot, const float* src, size_t len) {
     }
     ZG_REQUIRE(len == n, ZG_ERR_SHAPE, "slot %d expects %zu elements, got %zu", slot, n, len);
     g->ln_folded = false;
+    if (mat && g->wt == WT_B24) return upload_b24(src, n, E, dst, nullptr, gs(g));
     return upload_f32(src, n, dst, mat && g->wt == WT_BF16, gs(g));
 }
 

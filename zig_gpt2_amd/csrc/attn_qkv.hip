@@ -91,9 +91,13 @@ int launch_attn_qkv(const GemvArgs& g, int weight_type, const AttnArgs& at, cons
         const unsigned G = (unsigned)((g.N + rows - 1) / rows);                                                                    \
         f.a0 = (G + 7u) & ~7u;                                                                                                     \
         const unsigned grid = f.a0 + (unsigned)(at.n_heads * splits);                                                              \
-        note_kernel("attn_qkv_kernel<%s, %d, %d>", weight_type == WT_BF16 ? "unsigned short" : "float", LPR_, CPL_);               \
+        note_kernel("attn_qkv_kernel<%s, %d, %d>", weight_type == WT_BF16 ? "unsigned short" : weight_type == WT_B24 ? "b24" : "float", \
+                    LPR_, CPL_);                                                                                                   \
         if (weight_type == WT_BF16)                                                                                                \
             hipLaunchKernelGGL((attn_qkv_kernel<bf16_t, LPR_, CPL_>), dim3(grid), dim3(256), 0, s, g.W, g.x,                       \
+                               (unsigned)g.N | ((unsigned)g.epilogue << 24), (unsigned)g.K | (G << 16), g.ln_g, g.ln_c2, g.ln_c3, cw, g, f); \
+        else if (weight_type == WT_B24)                                                                                            \
+            hipLaunchKernelGGL((attn_qkv_kernel<b24_t, LPR_, CPL_>), dim3(grid), dim3(256), 0, s, g.W, g.x,                        \
                                (unsigned)g.N | ((unsigned)g.epilogue << 24), (unsigned)g.K | (G << 16), g.ln_g, g.ln_c2, g.ln_c3, cw, g, f); \
         else                                                                                                                       \
             hipLaunchKernelGGL((attn_qkv_kernel<float, LPR_, CPL_>), dim3(grid), dim3(256), 0, s, g.W, g.x,                        \

@@ -228,6 +228,52 @@ __global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ i
     }
 }
 
+// elements [k, k + 4) of row `row` of a B24 matrix [.][K] (k % 4 == 0): one 8-B load of upper halves, one 4-B load of low bytes
+__device__ __forceinline__ f32x4 load_b24x4(const void* w, size_t row, int K, int k) {
+    const char* r = reinterpret_cast<const char*>(w) + row * (size_t)(3 * K);
+    const u32x2 h = *reinterpret_cast<const u32x2*>(r + 2 * (size_t)k);
+    const uint32_t l = *reinterpret_cast<const uint32_t*>(r + 2 * (size_t)K + k);
+    return f32x4{__uint_as_float((h.x << 16) | ((l & 0xffu) << 8)), __uint_as_float((h.x & 0xffff0000u) | (l & 0xff00u)),
+                 __uint_as_float((h.y << 16) | ((l >> 8) & 0xff00u)), __uint_as_float((h.y & 0xffff0000u) | ((l >> 16) & 0xff00u))};
+}
+
+// fp32 [rows][K] -> B24 rows: one thread per 8 elements, a 16-B store of upper halves and an 8-B store of low bytes
+__global__ __launch_bounds__(256) void f32_to_b24_kernel(const float* __restrict__ in, size_t rows, int K, char* __restrict__ out) {
+    const size_t per_row = (size_t)(K / 8), n = rows * per_row;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / per_row, k = (i % per_row) * 8;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(in + r * K + k);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(in + r * K + k + 4);
+        const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        uint32_t q[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q[j] = b24_round(v[j]);  // 24 bits, right-aligned: upper half = q >> 8, low byte = q & 0xff
+        char* o = out + r * (size_t)(3 * K);
+        *reinterpret_cast<u32x4*>(o + 2 * k) = u32x4{(q[0] >> 8) | ((q[1] >> 8) << 16), (q[2] >> 8) | ((q[3] >> 8) << 16),
+                                                     (q[4] >> 8) | ((q[5] >> 8) << 16), (q[6] >> 8) | ((q[7] >> 8) << 16)};
+        *reinterpret_cast<u32x2*>(o + 2 * (size_t)K + k) =
+            u32x2{(q[0] & 0xffu) | (q[1] & 0xffu) << 8 | (q[2] & 0xffu) << 16 | (q[3] & 0xffu) << 24,
+                  (q[4] & 0xffu) | (q[5] & 0xffu) << 8 | (q[6] & 0xffu) << 16 | (q[7] & 0xffu) << 24};
+    }
+}
+
+// B24 [rows][K] -> plane-major [3][rows K]: split3_kernel's arithmetic on the values the matrix holds (the whole-prompt GEMMs'
+// weight operand; its planes are then bit for bit those of an fp32 matrix holding the same values)
+__global__ __launch_bounds__(256) void b24_split3_kernel(const char* __restrict__ in, size_t rows, int K, bf16_t* __restrict__ out) {
+    const size_t per_row = (size_t)(K / 4), n = rows * per_row, total = rows * (size_t)K;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / per_row, k = (i % per_row) * 4;
+        const f32x4 v = load_b24x4(in, r, K, (int)k);
+        uint32_t h0, m0, l0, h1, m1, l1;
+        split3_pk(v.x, v.y, h0, m0, l0);
+        split3_pk(v.z, v.w, h1, m1, l1);
+        bf16_t* o = out + r * K + k;
+        *reinterpret_cast<u32x2*>(o) = u32x2{h0, h1};
+        *reinterpret_cast<u32x2*>(o + total) = u32x2{m0, m1};
+        *reinterpret_cast<u32x2*>(o + 2 * total) = u32x2{l0, l1};
+    }
+}
+
 __device__ __forceinline__ float load_emb(const void* w, int wt, size_t off) {
     if (wt == WT_BF16) return __uint_as_float((uint32_t)reinterpret_cast<const bf16_t*>(w)[off] << 16);
     return reinterpret_cast<const float*>(w)[off];
@@ -344,6 +390,8 @@ __global__ __launch_bounds__(512) void embed_step_kernel(const EmbedArgs a) {
             o.y = bf16_hi(t.x) + bf16_hi(p.x);
             o.z = bf16_lo(t.y) + bf16_lo(p.y);
             o.w = bf16_hi(t.y) + bf16_hi(p.y);
+        } else if (a.weight_type == WT_B24) {
+            o = load_b24x4(a.wte, (size_t)tok, a.n_embed, e) + load_b24x4(a.wpe, (size_t)s, a.n_embed, e);
         } else {
             const f32x4 t = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(a.wte) + (size_t)tok * a.n_embed + e);
             const f32x4 p = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(a.wpe) + (size_t)s * a.n_embed + e);
@@ -635,6 +683,22 @@ int launch_kv_clear_tail(void* base, int n_caches, size_t cache_stride, size_t p
     ZG_REQUIRE(row_bytes % 64 == 0 && strips < 65536 * 32 && n_caches < 65536, ZG_ERR_UNSUPPORTED, "kv clear: %d-byte rows, %d strips", row_bytes, strips);
     hipLaunchKernelGGL(kv_clear_tail_kernel, dim3(strips, n_caches), dim3(256), 0, s, reinterpret_cast<char*>(base), cache_stride, plane_off, row_bytes,
                        strips, ctx, from_row);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_f32_to_b24(const float* in, size_t rows, int K, void* out, hipStream_t s) {
+    if (rows == 0) return ZG_OK;
+    ZG_REQUIRE(K % 8 == 0, ZG_ERR_UNSUPPORTED, "f32_to_b24: K=%d must be a multiple of 8", K);
+    hipLaunchKernelGGL(f32_to_b24_kernel, dim3(grid_for(rows * (size_t)(K / 8))), dim3(256), 0, s, in, rows, K, reinterpret_cast<char*>(out));
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_b24_split3(const void* in, size_t rows, int K, bf16_t* out, hipStream_t s) {
+    if (rows == 0) return ZG_OK;
+    ZG_REQUIRE(K % 8 == 0, ZG_ERR_UNSUPPORTED, "b24_split3: K=%d must be a multiple of 8", K);
+    hipLaunchKernelGGL(b24_split3_kernel, dim3(grid_for(rows * (size_t)(K / 4))), dim3(256), 0, s, reinterpret_cast<const char*>(in), rows, K, out);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

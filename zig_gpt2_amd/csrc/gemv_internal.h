@@ -79,6 +79,75 @@ __device__ __forceinline__ W8 unpack(const Raw<float>& r) {
     return w;
 }
 
+// B24 (zg_common.h b24_t): a chunk is 16 B of upper halves and the 8 low bytes of the same 8 elements
+template <>
+struct Raw<b24_t> {
+    u32x4 h;
+    u32x2 l;
+};
+
+// Weight matrices as the kernels address them: wmat = the matrix from column k0 on, wrow = one of its rows, the argument of
+// load_raw.  bf16 / fp32: plain pointers, W + k0 and W + row K.  B24: a row is 3 K bytes of two parts, so both are kept.
+template <typename WT>
+struct WMat {
+    typedef const WT* type;
+};
+struct B24Mat {
+    const char* base;
+    size_t k0;
+};
+struct B24Row {
+    const u32x4* hi;
+    const u32x2* lo;
+};
+template <>
+struct WMat<b24_t> {
+    typedef B24Mat type;
+};
+template <typename WT, typename I>
+__device__ __forceinline__ typename WMat<WT>::type wmat(const void* W, I k0) {
+    if constexpr (sizeof(WT) == 3) return B24Mat{reinterpret_cast<const char*>(W), (size_t)k0};
+    else return reinterpret_cast<const WT*>(W) + k0;
+}
+template <typename WT>
+__device__ __forceinline__ const WT* wrow(const WT* W, size_t row, int K) {
+    return W + row * K;
+}
+__device__ __forceinline__ B24Row wrow(const B24Mat& m, size_t row, int K) {
+    const char* r = m.base + row * (size_t)(3 * K);
+    return B24Row{reinterpret_cast<const u32x4*>(r + 2 * (size_t)m.k0), reinterpret_cast<const u32x2*>(r + 2 * (size_t)K + m.k0)};
+}
+
+__device__ __forceinline__ Raw<b24_t> load_raw(const B24Row& row, int c) {
+    Raw<b24_t> r;
+    r.h = __builtin_nontemporal_load(row.hi + c);
+    r.l = __builtin_nontemporal_load(row.lo + c);
+    return r;
+}
+__device__ __forceinline__ void zero_raw(Raw<b24_t>& r) {
+    r.h = u32x4{0u, 0u, 0u, 0u};
+    r.l = u32x2{0u, 0u};
+}
+// element j = (upper half j) << 16 | (low byte j) << 8: from here on the fp32 kernels' arithmetic
+__device__ __forceinline__ W8 unpack(const Raw<b24_t>& r) {
+    W8 w;
+    w.v[0] = __uint_as_float((r.h.x << 16) | ((r.l.x & 0xffu) << 8));
+    w.v[1] = __uint_as_float((r.h.x & 0xffff0000u) | (r.l.x & 0xff00u));
+    w.v[2] = __uint_as_float((r.h.y << 16) | ((r.l.x >> 8) & 0xff00u));
+    w.v[3] = __uint_as_float((r.h.y & 0xffff0000u) | ((r.l.x >> 16) & 0xff00u));
+    w.v[4] = __uint_as_float((r.h.z << 16) | ((r.l.y & 0xffu) << 8));
+    w.v[5] = __uint_as_float((r.h.z & 0xffff0000u) | (r.l.y & 0xff00u));
+    w.v[6] = __uint_as_float((r.h.w << 16) | ((r.l.y >> 8) & 0xff00u));
+    w.v[7] = __uint_as_float((r.h.w & 0xffff0000u) | ((r.l.y >> 16) & 0xff00u));
+    return w;
+}
+
+// Kernel-name spelling of the weight type (zg_debug_last_kernel)
+template <typename WT>
+inline const char* wt_name() {
+    return sizeof(WT) == 2 ? "unsigned short" : sizeof(WT) == 3 ? "b24" : "float";
+}
+
 __device__ __forceinline__ W8 zero_w8() {
     W8 w;
 #pragma unroll
@@ -229,9 +298,9 @@ __device__ __forceinline__ f32x4 merge_attn4(const GemvArgs& a, int m, int e0, i
 // loads sit in exec-masked branches, after which it falls back to vmcnt(0) and the pass pipeline
 // collapses).  A clamped chunk multiplies an input that is zero; a clamped row's result is discarded.
 template <typename WT, int LPR, int CPL>
-__device__ __forceinline__ void load_pass(Raw<WT> (&w)[CPL], const WT* W, int K, int nch, int row, int n_rows,
+__device__ __forceinline__ void load_pass(Raw<WT> (&w)[CPL], const typename WMat<WT>::type& W, int K, int nch, int row, int n_rows,
                                           int lr) {
-    const WT* wp = W + (size_t)max(min(row, n_rows - 1), 0) * K;  // n_rows = this wave's row_end: surplus slots re-read its own last row
+    const auto wp = wrow(W, (size_t)max(min(row, n_rows - 1), 0), K);  // n_rows = this wave's row_end: surplus slots re-read its own last row
 #pragma unroll
     for (int i = 0; i < CPL; ++i) w[i] = load_raw(wp, min(lr + LPR * i, nch - 1));
 }
@@ -403,12 +472,12 @@ __device__ __forceinline__ void gemv_lnk_body(int blk, const void* __restrict__ 
         kbeg = wave * (K >> 2);
         nchq = K >> 5;
     }
-    const WT* W = reinterpret_cast<const WT*>(Wv) + kbeg;
+    const auto W = wmat<WT>(Wv, kbeg);
     const int row0 = blk * ROWS;
     Raw<WT> wq[NP][CPL];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-        const WT* pr = W + (size_t)min(row0 + p * RPP + rsub, N - 1) * K;
+        const auto pr = wrow(W, (size_t)min(row0 + p * RPP + rsub, N - 1), K);
 #pragma unroll
         for (int i = 0; i < CPL; ++i) wq[p][i] = load_raw(pr, min(lr + LPR * i, nchq - 1));
     }

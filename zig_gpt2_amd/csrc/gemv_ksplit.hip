@@ -35,13 +35,13 @@ __global__ __launch_bounds__(256) void gemv_ksplit_kernel(const void* __restrict
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane % LPR, rsub = lane / LPR;
     const int Kq = K >> 2, nchq = Kq >> 3;
-    const WT* W = reinterpret_cast<const WT*>(Wv) + (size_t)wave * Kq;
+    const auto W = wmat<WT>(Wv, (size_t)wave * Kq);
     const int row0 = blockIdx.x * ROWS;
     // all loads of the kernel up front: NP passes of weights, the input quarter, the epilogue operands
     Raw<WT> wq[NP][CPL];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-        const WT* pr = W + (size_t)min(row0 + p * RPP + rsub, N - 1) * K;
+        const auto pr = wrow(W, (size_t)min(row0 + p * RPP + rsub, N - 1), K);
 #pragma unroll
         for (int i = 0; i < CPL; ++i) wq[p][i] = load_raw(pr, min(lr + LPR * i, nchq - 1));
     }
@@ -146,7 +146,7 @@ int launch_ksplit(const GemvArgs& a, hipStream_t s) {
 #define ZG_KS(LPR_, CPL_)                                                                                                \
     {                                                                                                                    \
         constexpr int rows = 2 * (64 / LPR_);                                                                            \
-        note_kernel("gemv_ksplit_kernel<%s, %d, %d, 2>", sizeof(WT) == 2 ? "unsigned short" : "float", LPR_, CPL_);         \
+        note_kernel("gemv_ksplit_kernel<%s, %d, %d, 2>", wt_name<WT>(), LPR_, CPL_);         \
         hipLaunchKernelGGL((gemv_ksplit_kernel<WT, LPR_, CPL_, 2>), dim3((a.N + rows - 1) / rows), dim3(256), 0, s, a.W,     \
                            a.x,                                                                                         \
                            a.N, a.K, em, a.part ? a.part : a.zero, a.max_splits, a.bias ? a.bias : a.zero,              \
@@ -201,6 +201,7 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const void* __restrict__ W
     for (int k = lane; k < K; k += 64) {
         float wv;
         if constexpr (sizeof(WT) == 2) wv = __uint_as_float((uint32_t)w[k] << 16);
+        else if constexpr (sizeof(WT) == 3) wv = b24_elem(Wv, (size_t)row, K, (size_t)k);  // c2 / c3 of the stored values
         else wv = w[k];
         s2 = fmaf(wv, g[k], s2);
         s3 = fmaf(wv, b[k], s3);
@@ -220,7 +221,7 @@ int launch_lnk(const GemvArgs& a, hipStream_t s) {
 #define ZG_LK(LPR_, CPL_)                                                                                              \
     {                                                                                                                  \
         constexpr int rows = 4 * (64 / LPR_);                                                                          \
-        note_kernel("gemv_lnk_kernel<%s, %d, %d, 4>", sizeof(WT) == 2 ? "unsigned short" : "float", LPR_, CPL_);       \
+        note_kernel("gemv_lnk_kernel<%s, %d, %d, 4>", wt_name<WT>(), LPR_, CPL_);       \
         hipLaunchKernelGGL((gemv_lnk_kernel<WT, LPR_, CPL_, 4>), dim3((a.N + rows - 1) / rows), dim3(256), 0, s, a.W, a.x, \
                            (unsigned)a.N | ((unsigned)a.epilogue << 24), a.K, a.ln_g, a.ln_c2, a.ln_c3,                 \
                            a.ctrl ? reinterpret_cast<const int*>(a.ctrl) : reinterpret_cast<const int*>(a.zero), a);   \
@@ -258,9 +259,11 @@ bool gemv_use_lnk(const GemvArgs& a) {
 }
 
 int gemv_launch_ksplit(const GemvArgs& a, int weight_type, hipStream_t s) {
+    if (weight_type == WT_B24) return launch_ksplit<b24_t>(a, s);
     return weight_type == WT_BF16 ? launch_ksplit<bf16_t>(a, s) : launch_ksplit<float>(a, s);
 }
 int gemv_launch_lnk(const GemvArgs& a, int weight_type, hipStream_t s) {
+    if (weight_type == WT_B24) return launch_lnk<b24_t>(a, s);
     return weight_type == WT_BF16 ? launch_lnk<bf16_t>(a, s) : launch_lnk<float>(a, s);
 }
 
@@ -268,6 +271,8 @@ int launch_ln_fold(const void* W, int weight_type, const float* g, const float* 
                    float* c3, hipStream_t s) {
     if (weight_type == WT_BF16)
         hipLaunchKernelGGL((ln_fold_kernel<bf16_t>), dim3((N + 3) / 4), dim3(256), 0, s, W, g, b, bias, N, K, c2, c3);
+    else if (weight_type == WT_B24)
+        hipLaunchKernelGGL((ln_fold_kernel<b24_t>), dim3((N + 3) / 4), dim3(256), 0, s, W, g, b, bias, N, K, c2, c3);
     else
         hipLaunchKernelGGL((ln_fold_kernel<float>), dim3((N + 3) / 4), dim3(256), 0, s, W, g, b, bias, N, K, c2, c3);
     ZG_HIP(hipGetLastError());

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ Wv, 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane % LPR, rsub = lane / LPR;
     const int nch = K >> 3, nq = K >> 2;
-    const WT* W = reinterpret_cast<const WT*>(Wv);
+    const auto W = wmat<WT>(Wv, 0);
     // M == 1: waves are independent (wave-private prologue), so the workgroup may be 1..4 waves: matrices with
     // few rows are launched as one-wave workgroups that the dispatcher spreads over all CUs
     const int wpw = PERWAVE ? (int)(mpew >> 12) : 4;
@@ -355,6 +355,7 @@ __global__ __launch_bounds__(256) void gemv_generic_kernel(const GemvArgs a) {
         for (int k = lane; k < a.K; k += 64) {
             float wv;
             if constexpr (sizeof(WT) == 2) wv = __uint_as_float((uint32_t)w[k] << 16);
+            else if constexpr (sizeof(WT) == 3) wv = b24_elem(a.W, (size_t)row, a.K, (size_t)k);
             else wv = w[k];
             acc = fmaf(wv, x[k], acc);
         }
@@ -377,7 +378,7 @@ int launch_inst(const GemvArgs& a, int grid, hipStream_t s) {
         }
     }
     ZG_REQUIRE(lds <= 160 * 1024, ZG_ERR_UNSUPPORTED, "gemv: M=%d x K=%d does not fit LDS", a.M, a.K);
-    note_kernel("gemv_kernel<%s, %d, %d, %d, %s>", sizeof(WT) == 2 ? "unsigned short" : "float", MT, LPR, CPL, ARGMAX ? "true" : "false");
+    note_kernel("gemv_kernel<%s, %d, %d, %d, %s>", wt_name<WT>(), MT, LPR, CPL, ARGMAX ? "true" : "false");
     hipLaunchKernelGGL((gemv_kernel<WT, MT, LPR, CPL, ARGMAX>), dim3(grid), dim3(64 * wpw), lds, s, a.W, a.x, a.N, a.K,
                        (unsigned)a.M | ((unsigned)a.prologue << 4) | ((unsigned)a.epilogue << 8) | ((unsigned)wpw << 12), a.rows_per_wave,
                        a.ln_g, a.ln_b, a.ctrl ? reinterpret_cast<const int*>(a.ctrl) : reinterpret_cast<const int*>(a.zero), a);
@@ -430,6 +431,7 @@ int launch_wt(const GemvArgs& a, int grid, hipStream_t s) {
 }  // namespace
 
 int gemv_launch_valu(const GemvArgs& a, int weight_type, int grid, hipStream_t s) {
+    if (weight_type == WT_B24) return launch_wt<b24_t>(a, grid, s);
     return weight_type == WT_BF16 ? launch_wt<bf16_t>(a, grid, s) : launch_wt<float>(a, grid, s);
 }
 

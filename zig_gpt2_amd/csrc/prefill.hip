@@ -45,6 +45,11 @@ __device__ __forceinline__ void store_split4(bf16_t* dst, size_t plane, f32x4 v)
 }
 
 // ------------------------------------------------------------------------------------------ embed
+// elements [k, k + 4) of row `row` of a B24 matrix [.][K] (zg_common.h b24_t)
+__device__ __forceinline__ f32x4 b24x4(const void* w, size_t row, int K, int k) {
+    return f32x4{b24_elem(w, row, K, k), b24_elem(w, row, K, k + 1), b24_elem(w, row, K, k + 2), b24_elem(w, row, K, k + 3)};
+}
+
 __global__ __launch_bounds__(256) void embed_prefill_kernel(const int* __restrict__ tokens, int token_stride, int P,
                                                             const void* __restrict__ wte, const void* __restrict__ wpe,
                                                             int weight_type, int E, float* __restrict__ x) {
@@ -59,6 +64,8 @@ __global__ __launch_bounds__(256) void embed_prefill_kernel(const int* __restric
             o.y = bf16_hi(w.x) + bf16_hi(p.x);
             o.z = bf16_lo(w.y) + bf16_lo(p.y);
             o.w = bf16_hi(w.y) + bf16_hi(p.y);
+        } else if (weight_type == WT_B24) {
+            o = b24x4(wte, (size_t)tok, E, e) + b24x4(wpe, (size_t)t, E, e);
         } else {
             o = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(wte) + (size_t)tok * E + e) +
                 *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(wpe) + (size_t)t * E + e);

@@ -76,6 +76,19 @@ __device__ __forceinline__ void b24_store(void* cache, size_t lo_off, size_t ele
     reinterpret_cast<uint8_t*>(cache)[lo_off + elem] = (uint8_t)r;
 }
 
+// B24 weights (ZG_GPT_WEIGHTS_B24): every matrix element is b24_round of the fp32 value, stored row-interleaved — row r of an
+// [N][K] matrix is [K bf16-shaped upper halves | K low bytes], 3 K r bytes from the matrix base.  A workgroup's rows stay one
+// contiguous stretch (the prefetcher's tiles), and K % 64 == 0 keeps every row 16-B aligned.  The type is a tag for the
+// templates: its size is what a row costs per element, it is never dereferenced.
+struct b24_t {
+    uint8_t b[3];
+};
+// Element (row, k) as the fp32 value it stands for (the decoders of one element: ln_fold, embeddings, plane split)
+__device__ __forceinline__ float b24_elem(const void* W, size_t row, int K, size_t k) {
+    const uint8_t* r = reinterpret_cast<const uint8_t*>(W) + row * (size_t)(3 * K);
+    return __uint_as_float(((uint32_t)reinterpret_cast<const uint16_t*>(r)[k] << 16) | ((uint32_t)r[2 * (size_t)K + k] << 8));
+}
+
 // Two fp32 values -> packed bf16 pair (round to nearest even), one gfx950 instruction (v_cvt_pk_bf16_f32); lo half = a.
 // Through the compiler's own conversion, NOT an asm statement: the hazard recognizer pads nothing around inline asm, and a
 // packed pair that an MFMA reads as an operand right behind the conversion was read half-written — alternating groups of four

@@ -16,14 +16,14 @@ struct StepCtrl {
 // ------------------------------------------------------------------------------------ GEMV
 enum GemvPrologue { PRO_NONE = 0, PRO_LAYERNORM = 1, PRO_ATTN_MERGE = 2 };
 enum GemvEpilogue { EPI_STORE = 0, EPI_RESIDUAL = 1, EPI_GELU = 2, EPI_QKV = 3, EPI_ARGMAX = 4 };
-enum WeightType { WT_BF16 = 0, WT_F32 = 1 };
+enum WeightType { WT_BF16 = 0, WT_F32 = 1, WT_B24 = 2 /* zg_common.h b24_t: rows of [K upper halves | K low bytes] */ };
 
 constexpr int kAttnChunk = 256;       // KV positions per attention workgroup (4 waves x 64)
 constexpr int kPartStride = 64 + 2;   // floats per attention partial: o[hd<=64], m, l
 
 struct GemvArgs {
     // y[m][n] = epilogue( sum_k prologue(x)[m][k] * W[n][k] + bias[n] ),  m < M, n < N
-    const void* W;  // [N][K], bf16 bits or fp32, K contiguous (ops.Linear.weight layout)
+    const void* W;  // [N][K], bf16 bits, fp32 or B24 rows, K contiguous (ops.Linear.weight layout)
     const float* bias;  // [N] or nullptr
     int N, K, M;
     int rows_per_wave;
@@ -176,6 +176,10 @@ int launch_copy_f32(const float* in, float* out, size_t n, hipStream_t s);
 int launch_f32_to_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 // fp32 [rows][K] -> bf16 [rows][3K] = [hi | mid | lo], hi + mid + lo == x exactly
 int launch_split3(const float* in, size_t rows, int K, bf16_t* out, hipStream_t s);
+// fp32 [rows][K] -> B24 rows (b24_round; zg_common.h b24_t), K a multiple of 8
+int launch_f32_to_b24(const float* in, size_t rows, int K, void* out, hipStream_t s);
+// B24 matrix [rows][K] -> plane-major bf16 [3][rows K], the split launch_split3(values, 1, rows K) makes of the values it holds
+int launch_b24_split3(const void* in, size_t rows, int K, bf16_t* out, hipStream_t s);
 // rows [from_row, ctx) of every (cache, sequence x head) strip set to zero: n_caches caches cache_stride bytes apart, each holding a
 // plane of [strips][ctx] rows of row_bytes at plane_off (api_gpt.hip clear_kv: what a new sequence must not inherit)
 int launch_kv_clear_tail(void* base, int n_caches, size_t cache_stride, size_t plane_off, int row_bytes, int strips, int ctx, int from_row,
@@ -280,7 +284,7 @@ struct EmbedArgs {
     int prompt_stride;
     // ... the rest is fetched from the kernarg segment under those loads
     const int* forced;       // [B] (mode 1)
-    const void* wte;  // [V][E] bf16 or fp32
+    const void* wte;  // [V][E] bf16, fp32 or B24
     const void* wpe;  // [ctx][E]
     int weight_type;
     int n_embed, vocab;

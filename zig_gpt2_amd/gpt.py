@@ -18,9 +18,11 @@ from .synth import GPTConfig
 class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
-                 sampled_generate=False):
+                 sampled_generate=False, weights_b24=False):
         """share_weights_with / own_stream / stream_priority: zg_gpt_options of zg_gpt_create_ex (a handle of an independent
-        prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config)."""
+        prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config).
+        weights_b24: matrices stored as 24-bit floats (ZG_GPT_WEIGHTS_B24: each fp32 weight rounded to 16 mantissa bits, 3/4 of
+        fp32's bytes); excludes weights_f32."""
         self.config, self.batch = config, batch
         L = _lib.load()
         flags = (_lib.GPT_WEIGHTS_F32 if weights_f32 else 0) | (0 if use_graph else _lib.GPT_NO_GRAPH)
@@ -30,6 +32,7 @@ class GPT:
         flags |= _lib.GPT_PREFILL_2PLANE if prefill_planes == 2 else 0
         flags |= 0 if prefetch else _lib.GPT_NO_PREFETCH
         flags |= _lib.GPT_SAMPLED_GENERATE if sampled_generate else 0
+        flags |= _lib.GPT_WEIGHTS_B24 if weights_b24 else 0
         cfg = _lib.GptConfig(config.vocab_size, config.context_size, config.n_layer, config.n_heads, config.n_embed)
         h = C.c_void_p()
         if share_weights_with is None and not own_stream:
@@ -42,14 +45,15 @@ class GPT:
         self._L = L
 
     @classmethod
-    def from_raw_dir(cls, path, config: GPTConfig, **kw):
+    def from_raw_dir(cls, path, config: GPTConfig, weights_b24=False, **kw):
         """load_gpt (src/main.zig:304-314) from a reference-format weight directory.  The matrices keep the reference's fp32
         unless every one of them is bf16-representable (weights_io.flags_for_checkpoint: bf16 storage of an ordinary fp32
-        checkpoint is 6e-3 of the logit scale away from the fp32 result, outside the 1e-3 bound)."""
+        checkpoint is 6e-3 of the logit scale away from the fp32 result, outside the 1e-3 bound).  weights_b24=True: such a
+        checkpoint is stored as 24-bit floats instead of fp32 (ZG_GPT_WEIGHTS_B24, 3/4 of the weight bytes)."""
         from . import weights_io
 
         w = weights_io.load_raw_dir(path, config)
-        flags = weights_io.flags_for_checkpoint(w)
+        flags = weights_io.flags_for_checkpoint(w, allow_b24=weights_b24)
         flags.update(kw)
         m = cls(config, **flags)
         m.load_weights(w)

@@ -9,6 +9,8 @@
 //
 //   zgpt2_main <tiny|tiny3|nano-char|124M> <weight_seed | raw weight directory> <tok,tok,...> <n_steps> [--model-tier]
 // prints the tokens after every step on one line (prompt tokens included, main.zig:339-340).
+// --weights-b24 (with --model-tier or --gpus, weights from a raw directory): the handle stores the matrices as 24-bit floats
+// (ZG_GPT_WEIGHTS_B24) instead of fp32.
 //   zgpt2_main <model> <weights> "<tok,tok,...;tok,...;...>" <n_steps> --gpus N [--plan]
 // the multi-GPU case: the ';'-separated prompts are independent units, block-partitioned over N processes, one
 // per GPU (rank r on device r); rank 0 loads the weights and ONE RCCL broadcast of the weight arena carries them to the
@@ -240,7 +242,11 @@ static std::vector<size_t> generate(GPT& gpt, const std::vector<size_t>& inputs,
 // a checkpoint read from a raw directory is ordinary fp32 (download_weights.py:57-64) — rounding it to bf16 moves the logits by
 // 6e-3 of their scale and flips 2 of 64 greedy picks at 124M (tests/test_weight_storage_gpu.py), outside the 1e-3 bound — so it
 // keeps the reference's fp32.  Decided from the SOURCE, not the values: every rank of a multi-GPU run must build the same arena.
-static unsigned weight_flags(bool from_dir) { return from_dir ? ZG_GPT_WEIGHTS_F32 : ZG_GPT_WEIGHTS_BF16; }
+// --weights-b24: such a checkpoint as 24-bit floats instead (2^-17 per weight, 3/4 of fp32's bytes).
+static bool g_weights_b24 = false;
+static unsigned weight_flags(bool from_dir) {
+    return from_dir ? (g_weights_b24 ? ZG_GPT_WEIGHTS_B24 : ZG_GPT_WEIGHTS_F32) : ZG_GPT_WEIGHTS_BF16;
+}
 
 static std::vector<size_t> generate_model_tier(const GPTConfig& c, const Weights& w, const std::vector<size_t>& inputs,
                                                size_t n_steps, bool from_dir) {
@@ -466,10 +472,15 @@ int main(int argc, char** argv) {
         if (std::string(argv[i]) == "--gpus" && i + 1 < argc && number(argv[i + 1], &v) && v >= 1 && v <= 64) gpus = (int)v, ++i;
         else if (std::string(argv[i]) == "--plan") plan_only = true;
         else if (std::string(argv[i]) == "--model-tier") model_tier = true;
+        else if (std::string(argv[i]) == "--weights-b24") g_weights_b24 = true;
         else {
-            fprintf(stderr, "unknown or incomplete option '%s' (--model-tier | --gpus N [--plan], N = 1..64)\n", argv[i]);
+            fprintf(stderr, "unknown or incomplete option '%s' (--model-tier | --gpus N [--plan] | --weights-b24, N = 1..64)\n", argv[i]);
             return 2;
         }
+    }
+    if (g_weights_b24 && (!from_dir || (!model_tier && gpus == 0))) {
+        fprintf(stderr, "--weights-b24: for --model-tier or --gpus runs with weights from a raw directory\n");
+        return 2;
     }
     auto tokens_of = [&](std::string item, std::vector<size_t>* out) {  // "tok,tok,...": ids below the vocabulary size
         for (char* p = strtok(item.data(), ","); p; p = strtok(nullptr, ",")) {

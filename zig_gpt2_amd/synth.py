@@ -40,6 +40,17 @@ def round_bf16(x):
     return b.view(np.float32)
 
 
+def round_b24(x):
+    """Round fp32 array to 24 bits (ties to even at 16 mantissa bits), returned as fp32: bit for bit the device's b24_round
+    (zg_common.h), the value a ZG_GPT_WEIGHTS_B24 handle (and the ZG_GPT_KV_B24 cache) holds.  A finite value never rounds up
+    to inf; inf stays inf."""
+    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    r = ((b + np.uint64(0x7F) + ((b >> np.uint64(8)) & np.uint64(1))) & np.uint64(0xFFFFFFFF)) >> np.uint64(8)
+    up_to_inf = ((r & np.uint64(0x7F8000)) == np.uint64(0x7F8000)) & ((b & np.uint64(0x7F800000)) != np.uint64(0x7F800000))
+    r = r - up_to_inf.astype(np.uint64)
+    return (r << np.uint64(8)).astype(np.uint32).view(np.float32).reshape(np.shape(x))
+
+
 def to_bf16_bits(x):
     """fp32 array -> uint16 bf16 bit patterns (RNE)."""
     return (round_bf16(x).view(np.uint32) >> np.uint32(16)).astype(np.uint16)

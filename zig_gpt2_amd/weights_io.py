@@ -56,10 +56,14 @@ def bf16_representable(a):
     return not bool(np.any(b & np.uint32(0xFFFF)))
 
 
-def flags_for_checkpoint(weights):
+def flags_for_checkpoint(weights, allow_b24=False):
     """How a handle should store the matrices of THIS checkpoint: bf16 storage is lossless only for bf16-representable
     weights (the synthetic ones); on an ordinary fp32 checkpoint it moves the logits by about 1e-2 of their scale
     (tests/test_weight_storage_gpu.py), outside north_star's 1e-3 — such a checkpoint gets ZG_GPT_WEIGHTS_F32, the reference's
-    own precision (src/main.zig:210-269 keeps fp32).  Returns keyword arguments for gpt.GPT."""
+    own precision (src/main.zig:210-269 keeps fp32), or with allow_b24 ZG_GPT_WEIGHTS_B24 (2^-17 per weight, 3/4 of fp32's
+    bytes).  Returns keyword arguments for gpt.GPT."""
     mats = [v for k, v in weights.items() if np.ndim(v) == 2]
-    return {"weights_f32": not all(bf16_representable(m) for m in mats)}
+    wide = not all(bf16_representable(m) for m in mats)
+    if allow_b24:
+        return {"weights_f32": False, "weights_b24": wide}
+    return {"weights_f32": wide}
