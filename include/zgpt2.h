@@ -334,8 +334,7 @@ int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_strid
 /* The same for the prompts of several handles at once (handles on distinct streams: zg_gpt_create_ex): prompts is
  * [sum of the handles' batches, prompt_stride], rows in handle order, prompt_lens alike; every handle generates its own rows.
  * A graph launch returns only when its hardware queue has room, so the handles are fed by one short-lived feeder thread each
- * (inside this call; ZGPT2_MANY_THREADS=0: one thread, one graph launch per handle in turn) — no queue starves while another
- * one is being filled.
+ * (inside this call; a single handle is fed by the calling thread) — no queue starves while another one is being filled.
  * zg_gpt_generate_fetch_many drains every handle and returns out_tokens [sum of batches, n_steps] in the same row order.
  * Token for token the result equals one handle per prompt (sequences never interact). */
 int zg_gpt_generate_enqueue_many(zg_gpt* const* handles, size_t n_handles, const size_t* prompts, size_t prompt_stride,

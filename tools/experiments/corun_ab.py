@@ -82,7 +82,7 @@ for G in a.groups:
     row = {"model": a.model, "prompts": a.prompts, "groups": G, "per_group": a.prompts // G, "priorities": a.prio, "prefetch": a.prefetch, "like_bench": a.like_bench,
            "hw_queues_env": os.environ.get("GPU_MAX_HW_QUEUES"), "tokens_per_s": round(a.prompts * (ctx - 1) * a.gens / wall, 1),
            "ms_per_generation": round(1e3 * wall / a.gens, 2), "us_per_step": round(1e6 * wall / a.gens / ctx, 2),
-           "host_enqueue_ms_per_generation": round(1e3 * t_enq / a.gens, 2), "feeder_threads": os.environ.get("ZGPT2_MANY_THREADS", "1"),
+           "host_enqueue_ms_per_generation": round(1e3 * t_enq / a.gens, 2),
            "short64_host_ms": round(1e3 * t_host_short, 2), "short64_total_ms": round(1e3 * t_all_short, 2),
            "ids_equal_first": bool(np.array_equal(ids, ref_ids)), "first_tokens": [int(t) for t in ids[0, :4]]}
     print(json.dumps(row), flush=True)

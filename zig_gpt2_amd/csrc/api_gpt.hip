@@ -90,14 +90,11 @@ struct zg_gpt {
     // pinned host mirrors for small control traffic
     StepCtrl* h_ctrl;
     int* h_ints;  // [batch * ctx] staging for prompts / tokens
-    // graphs: one per (64-position bucket of seq_len, with/without lm_head), captured on first use.
+    // graphs [GraphKind][n_buckets]: one per (kind, 64-position bucket of seq_len), captured on first use (graph_exec).
     // The bucket's upper bound t_hi is baked into the attention / merge kernels so that their loads
     // do not wait for the exact seq_len (which lives in device memory).
     std::vector<hipGraphExec_t> graphs;
-    std::vector<hipGraphExec_t> graphs_k;  // per bucket: graph_steps consecutive steps with lm_head in one graph (generate loop)
-    // generate with the sampler (zg_gpt_generate_sample_*): per bucket one step / graph_steps steps with lm_head AND the sampler
-    // node behind it; captured at create with ZG_GPT_SAMPLED_GENERATE, otherwise on the first sampled generation
-    std::vector<hipGraphExec_t> graphs_s, graphs_ks;
+    size_t n_buckets;         // ceil(context / 64)
     int* sampled;             // [batch]: the sampler's draw from the last step's logits
     float* samp_ws;           // segment sums of the sampler (sample_workspace_floats)
     SampleParams* samp;       // device: temperature and seed of the generation in flight
@@ -122,6 +119,7 @@ struct zg_gpt {
     // overlap on the chip, and a weight region borrowed from another handle of the same model
     hipStream_t stream;  // nullptr: the library stream of the moment (zg_set_stream)
     zg_gpt* parent;      // owner of the weight region this handle reads (nullptr: its own)
+    bool counted;        // this handle is one of its parent's n_children
     int n_children;      // handles borrowing this one's weight region
     char* wbase;         // the weight region: arena, or the parent's
     // a generation in flight between gen_begin and gen_end (zg_gpt_generate_enqueue / _many)
@@ -134,6 +132,11 @@ static inline zg_gpt* root(zg_gpt* g) { return g->parent ? g->parent : g; }
 
 namespace {
 
+int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
 struct Carver {
     size_t off = 0;
     size_t take(size_t bytes) {
@@ -144,12 +147,14 @@ struct Carver {
     }
 };
 
+size_t kv_elem_bytes(const zg_gpt* g) { return g->kv_mode == 1 ? 2 : g->kv_mode == 2 ? 3 : 4; }  // B24: a bf16 plane, then a byte plane
+
 // One pass computes sizes (both bases nullptr) or assigns pointers: the weight region from wbase (the handle's own arena or the
 // one it borrows), everything else — KV caches, scratch, control — from sbase.
 void carve(zg_gpt* g, char* wbase, char* sbase) {
     const zg_gpt_config& c = g->cfg;
     const size_t E = c.n_embed, V = c.vocab_size, C = c.context_size, L = c.n_layer, B = g->batch;
-    const size_t wb = g->wbytes, kvb = g->kv_mode == 1 ? 2 : g->kv_mode == 2 ? 3 : 4;  // B24: a bf16 plane, then a byte plane
+    const size_t wb = g->wbytes, kvb = kv_elem_bytes(g);
     Carver cv;
     char* base = wbase;
     auto P = [&](size_t bytes) -> char* {
@@ -343,27 +348,6 @@ int emit_gemv(const zg_gpt* g, const GemvArgs& a, int grid, hipStream_t s, std::
     return ZG_OK;
 }
 
-int enqueue_lm_head(zg_gpt* g, hipStream_t s, std::vector<PfJob>* rec = nullptr) {
-    const size_t E = g->cfg.n_embed, V = g->cfg.vocab_size;
-    // ln_f (main.zig:189) + lm_head = wte, no bias (main.zig:192-194, :312) + greedy partial argmax
-    GemvArgs a = base_gemv(g, g->wte, nullptr, V, E, 0);
-    a.prologue = PRO_LAYERNORM;
-    a.x = g->x;
-    a.x_stride = (int)E;
-    a.ln_g = g->ln_f_g;
-    a.ln_b = g->ln_f_b;
-    a.ln_c2 = g->lm_c2;
-    a.ln_c3 = g->lm_c3;
-    a.epilogue = EPI_ARGMAX;
-    a.logits = g->logits;
-    a.logits_stride = (int)V;
-    a.part_val = g->part_val;
-    a.part_idx = g->part_idx;
-    const int grid = gemv_plan(a, g->wt);
-    ZG_REQUIRE(grid == g->lm_grid, ZG_ERR_ARG, "lm_head grid changed");
-    return emit_gemv(g, a, grid, s, rec, 6);
-}
-
 // Optional per-kernel event recorder (zg_gpt_profile_step only).
 struct StepProf {
     std::vector<hipEvent_t> ev;
@@ -400,12 +384,9 @@ int ensure_ln_folded(zg_gpt* g, hipStream_t s) {
     return ZG_OK;
 }
 
-// One decode step = GPT.forward (main.zig:178-195) for all sequences.
-// `only` >= 0 (measurement): launch just that kernel class of layer `only_layer`.
-// rec != nullptr: nothing is launched; the step's launches are described for the prefetcher instead (emit_gemv).
-// salt >= 0 (measurement chains of one kernel class): launch ids of the tagged hand-overs by chain position instead of by
-// layer, so that consecutive launches of the chain never find each other's tags.
-int env_int(const char* name, int dflt);
+// The arguments of the decode launches of a Block and of lm_head, one builder per launch class: enqueue_step launches what they
+// return, and zg_gpt_create asks the shape predicates (gemv.hip) about the very same arguments.  The mode bits pl_on / st_on /
+// tags_on are read from the handle.
 
 // ln_1 + c_attn + split_qkv + cache append (main.zig:121-123, ops.zig:143-157) and the attention over the cache (ops.zig:160 ->
 // :249-307) of layer y: the arguments of their launches
@@ -450,10 +431,130 @@ AttnArgs attn_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
     return a;
 }
 
-int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, StepProf* prof = nullptr, int only = -1, size_t only_layer = 0,
-                 std::vector<PfJob>* rec = nullptr, int salt = -1, bool with_sampler = false) {
+// merge heads + attn c_proj + residual: ops.zig:171-172, main.zig:136-139
+GemvArgs c_proj_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
     const size_t E = g->cfg.n_embed;
-    auto launch_id = [&](size_t l, int k) { return (unsigned)(salt >= 0 ? 1 + (2 * salt + k) % 254 : 2 * (int)l + 1 + k); };
+    GemvArgs a = base_gemv(g, y.c_proj_w, y.c_proj_b, E, E, t_hi);
+    a.prologue = PRO_ATTN_MERGE;
+    a.part = g->part;
+    a.epilogue = EPI_RESIDUAL;
+    a.y = g->x;
+    a.y_stride = (int)E;
+    a.resid = g->x;
+    a.resid_stride = (int)E;
+    if (g->pl_on) {  // the heads arrive merged, as planes
+        a.prologue = PRO_NONE;
+        a.pl_in = g->ap;
+        a.pl_out = g->xp;
+        a.pl_g = y.ln_2_g;
+        a.st_out = g->st_on ? g->xst : nullptr;
+    }
+    return a;
+}
+
+// ln_2 + c_fc + gelu: main.zig:140, :79-80
+GemvArgs c_fc_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
+    const size_t E = g->cfg.n_embed;
+    GemvArgs a = base_gemv(g, y.c_fc_w, y.c_fc_b, 4 * E, E, t_hi);
+    a.prologue = PRO_LAYERNORM;
+    a.x = g->x;
+    a.x_stride = (int)E;
+    a.ln_g = y.ln_2_g;
+    a.ln_b = y.ln_2_b;
+    a.ln_c2 = y.c_fc_c2;
+    a.ln_c3 = y.c_fc_c3;
+    a.epilogue = EPI_GELU;
+    a.y = g->h4;
+    a.y_stride = (int)(4 * E);
+    if (g->pl_on) {  // gelu(c_fc) leaves as planes only
+        a.st_in = g->st_on ? g->xst : nullptr;
+        a.pl_in = g->xp;
+        a.pl_out = g->hp;
+        a.y = nullptr;
+    }
+    return a;
+}
+
+// mlp c_proj + residual of layer l (main.zig:81, :142-145).  A tagged hand-over gets everything but its launch id, which is the
+// caller's to give (a.sk_tag != nullptr says that one is due).
+GemvArgs mlp_proj_args(const zg_gpt* g, size_t l, int t_hi) {
+    const size_t E = g->cfg.n_embed;
+    const zg_layer& y = g->layers[l];
+    GemvArgs a = base_gemv(g, y.mlp_proj_w, y.mlp_proj_b, E, 4 * E, t_hi);
+    a.prologue = PRO_NONE;
+    a.x = g->h4;
+    a.x_stride = (int)(4 * E);
+    a.epilogue = EPI_RESIDUAL;
+    a.y = g->x;
+    a.y_stride = (int)E;
+    a.resid = g->x;
+    a.resid_stride = (int)E;
+    if (g->pl_on) {
+        if (g->tags_on && 2 * l + 2 <= 255) {
+            a.epoch = g->epoch;
+            a.sk_tag = g->sk_tag;
+            a.fault = g->fault;
+            a.spin_limit = g->spin_limit;
+        }
+        a.pl_in = g->hp;
+        if (l + 1 < g->cfg.n_layer) {  // the next Block's ln_1 + c_attn (ln_f + lm_head reads x itself)
+            a.pl_out = g->xp;
+            a.pl_g = g->layers[l + 1].ln_1_g;
+            a.st_out = g->st_on ? g->xst : nullptr;
+        }
+    }
+    return a;
+}
+
+// ln_f (main.zig:189) + lm_head = wte, no bias (main.zig:192-194, :312) + greedy partial argmax
+GemvArgs lm_head_args(const zg_gpt* g) {
+    const size_t E = g->cfg.n_embed, V = g->cfg.vocab_size;
+    GemvArgs a = base_gemv(g, g->wte, nullptr, V, E, 0);
+    a.prologue = PRO_LAYERNORM;
+    a.x = g->x;
+    a.x_stride = (int)E;
+    a.ln_g = g->ln_f_g;
+    a.ln_b = g->ln_f_b;
+    a.ln_c2 = g->lm_c2;
+    a.ln_c3 = g->lm_c3;
+    a.epilogue = EPI_ARGMAX;  // (the plan depends on the epilogue: workgroup width)
+    a.logits = g->logits;
+    a.logits_stride = (int)V;
+    a.part_val = g->part_val;
+    a.part_idx = g->part_idx;
+    return a;
+}
+
+int enqueue_lm_head(zg_gpt* g, hipStream_t s, std::vector<PfJob>* rec = nullptr) {
+    GemvArgs a = lm_head_args(g);
+    const int grid = gemv_plan(a, g->wt);
+    ZG_REQUIRE(grid == g->lm_grid, ZG_ERR_ARG, "lm_head grid changed");
+    return emit_gemv(g, a, grid, s, rec, 6);
+}
+
+// What enqueue_step does besides a plain step.
+struct StepOpts {
+    StepProf* prof = nullptr;  // zg_gpt_profile_step: an event behind every kernel class
+    int only = -1;             // >= 0 (measurement): launch just that kernel class of layer only_layer
+    size_t only_layer = 0;
+    std::vector<PfJob>* rec = nullptr;  // nothing is launched; the step's launches are described for the prefetcher instead (emit_gemv)
+    // >= 0 (measurement chains of one kernel class): launch ids of the tagged hand-overs by chain position instead of by
+    // layer, so that consecutive launches of the chain never find each other's tags
+    int salt = -1;
+    bool with_sampler = false;  // GPT.sample's tail behind lm_head (with_logits only)
+};
+
+// One decode step = GPT.forward (main.zig:178-195) for all sequences.
+int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const StepOpts& o = StepOpts()) {
+    StepProf* const prof = o.prof;
+    std::vector<PfJob>* const rec = o.rec;
+    const int only = o.only;
+    auto launch_id = [&](size_t l, int k) { return (unsigned)(o.salt >= 0 ? 1 + (2 * o.salt + k) % 254 : 2 * (int)l + 1 + k); };
+    auto gemv = [&](GemvArgs a, unsigned cls) {
+        const int grid = gemv_plan(a, g->wt);
+        ZG_TRY(emit_gemv(g, a, grid, s, rec, cls));
+        return prof_mark(prof, (int)cls, s);
+    };
     ZG_TRY(prof_mark(prof, -1, s));
     if (rec) rec->push_back(PfJob{});
     else if (only < 0 || only == 0) {
@@ -461,7 +562,7 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, StepProf*
         ZG_TRY(launch_embed_step(e, s));
     }
     ZG_TRY(prof_mark(prof, 0, s));
-    for (size_t l = (only < 0 ? 0 : only_layer); l < (only < 0 ? g->cfg.n_layer : only_layer + 1); ++l) {
+    for (size_t l = (only < 0 ? 0 : o.only_layer); l < (only < 0 ? g->cfg.n_layer : o.only_layer + 1); ++l) {
         const zg_layer& y = g->layers[l];
         // one sequence: classes 1 and 2 as one launch (attn_qkv.hip), timed as class 1; the prefetcher's table keeps both entries
         const bool fused = g->fused_on && !rec && 2 * l + 2 <= 255;
@@ -475,12 +576,7 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, StepProf*
             ZG_TRY(prof_mark(prof, 1, s));
             ZG_TRY(prof_mark(prof, 2, s));
         }
-        if (!fused && (only < 0 || only == 1)) {   // ln_1 + c_attn + split_qkv + cache append: main.zig:121-123, ops.zig:143-157
-            GemvArgs a = c_attn_args(g, y, t_hi);
-            const int grid = gemv_plan(a, g->wt);
-            ZG_TRY(emit_gemv(g, a, grid, s, rec, 1));
-            ZG_TRY(prof_mark(prof, 1, s));
-        }
+        if (!fused && (only < 0 || only == 1)) ZG_TRY(gemv(c_attn_args(g, y, t_hi), 1));
         if ((!fused && only < 0) || only == 2) {   // scaled_dot_product_attention over the cache: ops.zig:160 -> :249-307
             AttnArgs a = attn_args(g, y, t_hi);
             if (g->pl_on) {
@@ -509,76 +605,12 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, StepProf*
                 ZG_TRY(launch_attn_decode(a, s));
             ZG_TRY(prof_mark(prof, 2, s));
         }
-        if (only < 0 || only == 3) {   // merge heads + attn c_proj + residual: ops.zig:171-172, main.zig:136-139
-            GemvArgs a = base_gemv(g, y.c_proj_w, y.c_proj_b, E, E, t_hi);
-            a.prologue = PRO_ATTN_MERGE;
-            a.part = g->part;
-            a.epilogue = EPI_RESIDUAL;
-            a.y = g->x;
-            a.y_stride = (int)E;
-            a.resid = g->x;
-            a.resid_stride = (int)E;
-            if (g->pl_on) {  // the heads arrive merged, as planes
-                a.prologue = PRO_NONE;
-                a.pl_in = g->ap;
-                a.pl_out = g->xp;
-                a.pl_g = y.ln_2_g;
-                a.st_out = g->st_on ? g->xst : nullptr;
-            }
-            const int grid = gemv_plan(a, g->wt);
-            ZG_TRY(emit_gemv(g, a, grid, s, rec, 3));
-            ZG_TRY(prof_mark(prof, 3, s));
-        }
-        if (only < 0 || only == 4) {   // ln_2 + c_fc + gelu: main.zig:140, :79-80
-            GemvArgs a = base_gemv(g, y.c_fc_w, y.c_fc_b, 4 * E, E, t_hi);
-            a.prologue = PRO_LAYERNORM;
-            a.x = g->x;
-            a.x_stride = (int)E;
-            a.ln_g = y.ln_2_g;
-            a.ln_b = y.ln_2_b;
-            a.ln_c2 = y.c_fc_c2;
-            a.ln_c3 = y.c_fc_c3;
-            a.epilogue = EPI_GELU;
-            a.y = g->h4;
-            a.y_stride = (int)(4 * E);
-            if (g->pl_on) {  // gelu(c_fc) leaves as planes only
-                a.st_in = g->st_on ? g->xst : nullptr;
-                a.pl_in = g->xp;
-                a.pl_out = g->hp;
-                a.y = nullptr;
-            }
-            const int grid = gemv_plan(a, g->wt);
-            ZG_TRY(emit_gemv(g, a, grid, s, rec, 4));
-            ZG_TRY(prof_mark(prof, 4, s));
-        }
-        if (only < 0 || only == 5) {   // mlp c_proj + residual: main.zig:81, :142-145
-            GemvArgs a = base_gemv(g, y.mlp_proj_w, y.mlp_proj_b, E, 4 * E, t_hi);
-            a.prologue = PRO_NONE;
-            a.x = g->h4;
-            a.x_stride = (int)(4 * E);
-            a.epilogue = EPI_RESIDUAL;
-            a.y = g->x;
-            a.y_stride = (int)E;
-            a.resid = g->x;
-            a.resid_stride = (int)E;
-            if (g->pl_on) {
-                if (g->tags_on && 2 * l + 2 <= 255) {
-                    a.epoch = g->epoch;
-                    a.launch_id = launch_id(l, 1);
-                    a.sk_tag = g->sk_tag;
-                    a.fault = g->fault;
-                    a.spin_limit = g->spin_limit;
-                }
-                a.pl_in = g->hp;
-                if (l + 1 < g->cfg.n_layer) {  // the next Block's ln_1 + c_attn (ln_f + lm_head reads x itself)
-                    a.pl_out = g->xp;
-                    a.pl_g = g->layers[l + 1].ln_1_g;
-                    a.st_out = g->st_on ? g->xst : nullptr;
-                }
-            }
-            const int grid = gemv_plan(a, g->wt);
-            ZG_TRY(emit_gemv(g, a, grid, s, rec, 5));
-            ZG_TRY(prof_mark(prof, 5, s));
+        if (only < 0 || only == 3) ZG_TRY(gemv(c_proj_args(g, y, t_hi), 3));
+        if (only < 0 || only == 4) ZG_TRY(gemv(c_fc_args(g, y, t_hi), 4));
+        if (only < 0 || only == 5) {
+            GemvArgs a = mlp_proj_args(g, l, t_hi);
+            if (a.sk_tag) a.launch_id = launch_id(l, 1);
+            ZG_TRY(gemv(a, 5));
         }
     }
     if (with_logits && (only < 0 || only == 6)) {
@@ -586,7 +618,7 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, StepProf*
         ZG_TRY(prof_mark(prof, 6, s));
     }
     // GPT.sample's tail (main.zig:200-206) on the logits of this step: the next step's embed kernel feeds what it draws (mode 2)
-    if (with_sampler && with_logits && only < 0 && !rec)
+    if (o.with_sampler && with_logits && only < 0 && !rec)
         ZG_TRY(launch_sample_step(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, g->ctrl, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws,
                                   g->sampled, s));
     return ZG_OK;
@@ -684,18 +716,9 @@ int note_steps(zg_gpt* g, size_t n, hipStream_t s) {
     return ZG_OK;
 }
 
-int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 // Side-stream prefetcher (prefetch.hip): job table, control block, low-priority stream.  Called from zg_gpt_create
 // BEFORE the graphs are captured (the decode kernels get the progress counter as an argument).
 int setup_prefetcher(zg_gpt* g) {
-    g->pf_on = g->pf_ran = g->pf_stalled = false;
-    g->pf_strikes = g->pf_sit_out = 0;
-    g->pf_stream = nullptr;
-    g->pf_ev_main = g->pf_ev_side = nullptr;
     // Default: only where it was measured to pay — one sequence and Linears of a few MB (GPT-2 124M: 241 -> 224 us per
     // token; GPT-2 XL's 20 MB matrices cannot be fetched a launch ahead, 8 prompts gain < 1 %).  ZGPT2_PREFETCH=1 / 0 forces.
     // (not beside co-running handles: a handle with a private stream is one of several chains on the chip — §3.3 of DESIGN.md — and
@@ -705,7 +728,9 @@ int setup_prefetcher(zg_gpt* g) {
     if ((g->flags & ZG_GPT_NO_PREFETCH) || !want || gs(g) == nullptr) return ZG_OK;
     if (g->pf_njobs > 255) return ZG_OK;  // the progress word counts launches in 8 bits (n_layer >= 51): no prefetcher, not an error
     std::vector<PfJob> jobs;
-    ZG_TRY(enqueue_step(g, true, (int)g->cfg.context_size, nullptr, nullptr, -1, 0, &jobs));
+    StepOpts describe;
+    describe.rec = &jobs;
+    ZG_TRY(enqueue_step(g, true, (int)g->cfg.context_size, nullptr, describe));
     ZG_REQUIRE((int)jobs.size() == g->pf_njobs, ZG_ERR_ARG, "prefetcher: %zu launches per step", jobs.size());
     ZG_HIP(hipMemcpy(g->pf_jobs, jobs.data(), jobs.size() * sizeof(PfJob), hipMemcpyHostToDevice));
     int least = 0, greatest = 0;
@@ -781,77 +806,81 @@ int pf_stop(zg_gpt* g, hipStream_t s) {
 
 size_t prefill_min() { return 4; }  // shorter prompts go through the decode chain (measured: the whole-prompt pass pays from 4 tokens up)
 
+// The decode graphs of a handle, per 64-position bucket of the sequence length.
+enum GraphKind {
+    G_STEP = 0,        // one step without lm_head
+    G_STEP_LOGITS,     // one step with lm_head
+    // graph_steps consecutive steps (all with lm_head, all in one bucket) as ONE graph: the position lives in device memory, so
+    // the same kernels simply repeat; saves the gap between graph launches in the generate loop
+    G_MULTI,
+    // generate with the sampler (zg_gpt_generate_sample_*): one step / graph_steps steps with lm_head AND the sampler node behind
+    // it; captured at create with ZG_GPT_SAMPLED_GENERATE, otherwise on the first sampled generation
+    G_SAMPLED,
+    G_SAMPLED_MULTI,
+    G_KINDS
+};
+
+size_t bucket_of(size_t seq_len) { return (seq_len + 63) / 64 - 1; }
+
 void drop_graphs(zg_gpt* g) {
-    for (auto* v : {&g->graphs, &g->graphs_k, &g->graphs_s, &g->graphs_ks})
-        for (auto& e : *v)
-            if (e) {
-                (void)hipGraphExecDestroy(e);
-                e = nullptr;
-            }
+    for (auto& e : g->graphs)
+        if (e) {
+            (void)hipGraphExecDestroy(e);
+            e = nullptr;
+        }
 }
 
-// Run one decode step at sequence length seq_len: replay the graph of its bucket (capturing it on
-// first use), or launch eagerly when graphs are disabled / the stream cannot be captured.
-// n_steps consecutive steps captured on stream cs into *out
-int capture_steps(zg_gpt* g, hipGraphExec_t* out, bool with_logits, int t_hi, size_t n_steps, hipStream_t cs, bool with_sampler = false) {
+// What body() enqueues on stream cs, captured and instantiated into *out.  Nothing is left behind on failure.
+template <class Body>
+int capture_graph(hipStream_t cs, hipGraphExec_t* out, Body body) {
     hipGraph_t graph = nullptr;
     ZG_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-    int st = ZG_OK;
-    for (size_t i = 0; i < n_steps && st == ZG_OK; ++i) st = enqueue_step(g, with_logits, t_hi, cs, nullptr, -1, 0, nullptr, -1, with_sampler);
+    const int st = body();
     hipError_t e = hipStreamEndCapture(cs, &graph);
-    if (st != ZG_OK) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return st;
-    }
+    if (st == ZG_OK && e == hipSuccess) e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    if (graph) (void)hipGraphDestroy(graph);
+    ZG_TRY(st);
     ZG_HIP(e);
-    ZG_HIP(hipGraphInstantiate(out, graph, nullptr, nullptr, 0));
-    ZG_HIP(hipGraphDestroy(graph));
     return ZG_OK;
 }
 
-int capture_bucket(zg_gpt* g, size_t idx, hipStream_t s) {
-    const size_t seq_len = (idx / 2 + 1) * 64;  // any length of the bucket: only its upper bound is baked in
-    const bool with_logits = idx & 1;
-    if (g->graphs.size() <= idx) g->graphs.resize(idx + 1, nullptr);
-    if (g->graphs[idx]) return ZG_OK;
-    const int t_hi = bucket_t_hi(g, seq_len);
-    return capture_steps(g, &g->graphs[idx], with_logits, t_hi, 1, s);
+// The graph of (kind, bucket b) for stream s (the stream of g->graph_stream: capture_all), captured on first use.
+int graph_exec(zg_gpt* g, GraphKind kind, size_t b, hipStream_t s, hipGraphExec_t* out) {
+    hipGraphExec_t& e = g->graphs[kind * g->n_buckets + b];
+    if (!e) {
+        const int t_hi = bucket_t_hi(g, (b + 1) * 64);  // any length of the bucket: only its upper bound is baked in
+        const size_t n_steps = (kind == G_MULTI || kind == G_SAMPLED_MULTI) ? g->graph_steps : 1;
+        StepOpts o;
+        o.with_sampler = kind == G_SAMPLED || kind == G_SAMPLED_MULTI;
+        ZG_TRY(capture_graph(s, &e, [&] {
+            int st = ZG_OK;
+            for (size_t i = 0; i < n_steps && st == ZG_OK; ++i) st = enqueue_step(g, kind != G_STEP, t_hi, s, o);
+            return st;
+        }));
+    }
+    *out = e;
+    return ZG_OK;
 }
 
-// graph_steps consecutive decode steps (all with lm_head, all in 64-position bucket b) as ONE graph: the position lives
-// in device memory, so the same kernels simply repeat; saves the gap between graph launches in the generate loop.
-int capture_multi(zg_gpt* g, size_t b, hipStream_t s) {
-    if (g->graphs_k.size() <= b) g->graphs_k.resize(b + 1, nullptr);
-    if (g->graphs_k[b]) return ZG_OK;
-    const int t_hi = bucket_t_hi(g, (b + 1) * 64);
-    return capture_steps(g, &g->graphs_k[b], true, t_hi, g->graph_steps, s);
-}
-
-// The sampled twins of a bucket's graphs (one step / graph_steps steps, each with lm_head and the sampler node).
-int capture_sampled(zg_gpt* g, size_t b, bool multi, hipStream_t s) {
-    auto& v = multi ? g->graphs_ks : g->graphs_s;
-    if (v.size() <= b) v.resize(b + 1, nullptr);
-    if (v[b]) return ZG_OK;
-    return capture_steps(g, &v[b], true, bucket_t_hi(g, (b + 1) * 64), multi ? g->graph_steps : 1, s, true);
-}
-
-// All decode graphs of a handle (two per 64-position bucket: with / without lm_head) for stream s.  Called from
-// zg_gpt_create — the State.init moment (main.zig:46-64) — so that no forward allocates; a later zg_set_stream
-// re-captures them on the first call that sees the new stream.
+// All decode graphs of a handle for stream s.  Called from zg_gpt_create — the State.init moment (main.zig:46-64) — so that
+// no forward allocates; a later zg_set_stream re-captures them on the first call that sees the new stream.
 int capture_all(zg_gpt* g, hipStream_t s) {
     if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) return ZG_OK;
     if (g->graph_stream != s) {
         drop_graphs(g);
         g->graph_stream = s;
     }
-    const size_t n = ((g->cfg.context_size + 63) / 64) * 2;
-    for (size_t idx = 0; idx < n; ++idx) ZG_TRY(capture_bucket(g, idx, s));
+    hipGraphExec_t e;
+    for (size_t b = 0; b < g->n_buckets; ++b) {
+        ZG_TRY(graph_exec(g, G_STEP, b, s, &e));
+        ZG_TRY(graph_exec(g, G_STEP_LOGITS, b, s, &e));
+    }
     if (g->graph_steps > 1)
-        for (size_t b = 0; b < n / 2; ++b) ZG_TRY(capture_multi(g, b, s));
+        for (size_t b = 0; b < g->n_buckets; ++b) ZG_TRY(graph_exec(g, G_MULTI, b, s, &e));
     if (g->flags & ZG_GPT_SAMPLED_GENERATE)
-        for (size_t b = 0; b < n / 2; ++b) {
-            ZG_TRY(capture_sampled(g, b, false, s));
-            if (g->graph_steps > 1) ZG_TRY(capture_sampled(g, b, true, s));
+        for (size_t b = 0; b < g->n_buckets; ++b) {
+            ZG_TRY(graph_exec(g, G_SAMPLED, b, s, &e));
+            if (g->graph_steps > 1) ZG_TRY(graph_exec(g, G_SAMPLED_MULTI, b, s, &e));
         }
     return ZG_OK;
 }
@@ -860,19 +889,16 @@ int capture_all(zg_gpt* g, hipStream_t s) {
 // are disabled / the stream cannot be captured.
 int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, bool with_sampler = false) {
     ZG_TRY(ensure_ln_folded(g, s));
-    const int t_hi = bucket_t_hi(g, seq_len);
     with_sampler = with_sampler && with_logits;
-    if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) return enqueue_step(g, with_logits, t_hi, s, nullptr, -1, 0, nullptr, -1, with_sampler);
-    if (g->graph_stream != s) ZG_TRY(capture_all(g, s));  // the caller switched streams after zg_gpt_create
-    if (with_sampler) {
-        const size_t b = (seq_len + 63) / 64 - 1;
-        ZG_TRY(capture_sampled(g, b, false, s));
-        ZG_HIP(hipGraphLaunch(g->graphs_s[b], s));
-        return ZG_OK;
+    if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) {
+        StepOpts o;
+        o.with_sampler = with_sampler;
+        return enqueue_step(g, with_logits, bucket_t_hi(g, seq_len), s, o);
     }
-    const size_t idx = ((seq_len + 63) / 64 - 1) * 2 + (with_logits ? 1 : 0);
-    ZG_TRY(capture_bucket(g, idx, s));  // no-op: captured at create
-    ZG_HIP(hipGraphLaunch(g->graphs[idx], s));
+    if (g->graph_stream != s) ZG_TRY(capture_all(g, s));  // the caller switched streams after zg_gpt_create
+    hipGraphExec_t e;
+    ZG_TRY(graph_exec(g, with_sampler ? G_SAMPLED : with_logits ? G_STEP_LOGITS : G_STEP, bucket_of(seq_len), s, &e));
+    ZG_HIP(hipGraphLaunch(e, s));
     return ZG_OK;
 }
 
@@ -925,6 +951,111 @@ int upload_b24(const float* src, size_t n, size_t K, void* dst, bf16_t* planes, 
     return ZG_OK;
 }
 
+// The control block of the steps enqueued next, through its pinned mirror (n_partials is always the lm_head grid).
+int stage_ctrl(zg_gpt* g, size_t step, size_t seq_len, int mode, hipStream_t s) {
+    g->h_ctrl->step = (int)step;
+    g->h_ctrl->seq_len = (int)seq_len;
+    g->h_ctrl->mode = mode;
+    g->h_ctrl->n_partials = g->lm_grid;
+    ZG_HIP(hipMemcpyAsync(g->ctrl, g->h_ctrl, sizeof(StepCtrl), hipMemcpyHostToDevice, s));
+    return ZG_OK;
+}
+
+// n floats from device memory to a caller's pointer, which may be host or device.
+int copy_out_f32(float* dst, const float* src, size_t n, hipStream_t s) {
+    ZG_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    return ZG_OK;
+}
+
+// Everything a handle holds, also one that zg_gpt_create built only in part (new zg_gpt() zero-initialises): the only place
+// that frees.
+void release(zg_gpt* g) {
+    (void)hipStreamSynchronize(gs(g));
+    drop_prefetcher(g);
+    drop_graphs(g);
+    if (g->stream) (void)hipStreamDestroy(g->stream);
+    if (g->counted) --g->parent->n_children;
+    if (g->arena) (void)hipFree(g->arena);
+    if (g->h_ctrl) (void)hipHostFree(g->h_ctrl);
+    if (g->h_ints) (void)hipHostFree(g->h_ints);
+    delete g;
+}
+
+// zg_gpt_create behind the checks of its arguments: allocates, decides the decode modes, captures.  On failure the caller
+// releases whatever g holds by then.
+int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
+    const zg_gpt_config& c = g->cfg;
+    const size_t batch = g->batch;
+    zg_gpt* const parent = g->parent;
+    carve(g, nullptr, nullptr);
+    g->arena_bytes = (parent ? 0 : g->weight_region_bytes) + g->state_bytes;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->arena), g->arena_bytes);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(model arena)", __FILE__, __LINE__);
+    g->wbase = parent ? parent->wbase : g->arena;
+    char* const sbase = parent ? g->arena : g->arena + g->weight_region_bytes;
+    carve(g, g->wbase, sbase);
+    ZG_HIP(hipMemset(sbase, 0, g->state_bytes));  // (tags, counters and fault words start from zero)
+    if (opt && opt->own_stream) {  // a private stream: its priority decides the hardware queue it shares (profiles/NOTEBOOK.md §5)
+        int least = 0, greatest = 0;
+        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);  // numerically: greatest <= 0 <= least
+        const int pr = opt->stream_priority > 0 ? greatest : opt->stream_priority < 0 ? least : 0;
+        e = hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, pr);
+        if (e != hipSuccess) return hip_fail(e, "hipStreamCreateWithPriority(handle stream)", __FILE__, __LINE__);
+    }
+    // The decode modes, each decided by asking the shape predicates about the launches enqueue_step would make with the mode on
+    // (the builders read the bits: a candidate is switched on for its question and stays on if the answer is yes).
+    const zg_layer& y = g->layers[0];
+    {
+        GemvArgs a = lm_head_args(g);
+        g->lm_grid = gemv_plan(a, g->wt);
+    }
+    // the widest input of a Block (mlp c_proj: 4 E floats per sequence) must fit the batched kernels' LDS
+    ZG_REQUIRE(gemv_supported(mlp_proj_args(g, 0, 0), g->wt), ZG_ERR_UNSUPPORTED,
+               "batch %zu with n_embed %zu: %zu input rows of 4*n_embed floats do not fit the LDS (use a smaller batch)", batch, c.n_embed, batch);
+    auto every_linear = [&](bool (*ok)(const GemvArgs&, int)) {
+        return ok(c_attn_args(g, y, 0), g->wt) && ok(c_proj_args(g, y, 0), g->wt) && ok(c_fc_args(g, y, 0), g->wt) &&
+               ok(mlp_proj_args(g, 0, 0), g->wt);
+    };
+    if (g->wt == WT_BF16 && batch >= 2 && !(decode_paths_off() & 1)) {  // all plane-fed Linears on the matrix-core path?
+        g->pl_on = true;
+        g->pl_on = c.n_embed % 32 == 0 && every_linear(gemv_planes_ok);
+    }
+    g->tags_on = g->pl_on && !(decode_paths_off() & 4);
+    g->spin_limit = (unsigned)env_int("ZGPT2_TAG_SPIN_LIMIT", 1 << 20);
+    // one sequence on the fp32 cache: ln_1 + c_attn and the attention as one launch where c_attn runs on the LayerNorm-folding
+    // kernel (ZGPT2_DECODE_PATHS_OFF bit 64: two launches)
+    g->fused_on = batch == 1 && !(decode_paths_off() & 64) && c.n_layer <= 127 &&
+                  attn_qkv_ok(c_attn_args(g, y, 0), attn_args(g, y, (int)c.context_size));
+    if (g->pl_on && !(decode_paths_off() & 8) && c.n_embed % 16 == 0 && c.n_embed / 16 <= 128) {
+        g->st_on = true;
+        g->st_on = every_linear(gemv_pl4_ok);  // every producer and consumer of x must be the four-wave kernel
+    }
+    ZG_REQUIRE(g->lm_grid <= 4096, ZG_ERR_UNSUPPORTED, "lm_head grid %d exceeds the argmax partial buffer", g->lm_grid);
+    // (the control mirror and, 256 bytes behind it, the fault word of the tagged hand-overs: pinned, written by the kernels)
+    e = hipHostMalloc(reinterpret_cast<void**>(&g->h_ctrl), sizeof(StepCtrl) + 512, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_ints), (batch * c.context_size + batch) * sizeof(int), hipHostMallocDefault);
+    if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(control mirrors)", __FILE__, __LINE__);
+    static_assert(sizeof(StepCtrl) + sizeof(SampleParams) <= 256, "the fault word sits 256 bytes behind the control mirror");
+    g->h_samp = reinterpret_cast<SampleParams*>(reinterpret_cast<char*>(g->h_ctrl) + 128);  // (same pinned block)
+    g->fault = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g->h_ctrl) + 256);
+    *g->fault = 0;
+    {   // decode steps per graph in the generate loop: a graph launch costs ~7 us of idle queue (124M: 224.8 us per token
+        // with 1 step per graph, 220.4 with 2 / 4, 218.3 with 8, 219.5 with 16)
+        const int k = env_int("ZGPT2_GRAPH_STEPS", 8);
+        g->graph_steps = (k == 2 || k == 4 || k == 8 || k == 16 || k == 32 || k == 64) ? (size_t)k : 1;
+    }
+    g->n_buckets = (c.context_size + 63) / 64;
+    g->graphs.assign(G_KINDS * g->n_buckets, nullptr);
+    // every decode graph is captured and instantiated here, not on the first forward that needs it
+    ZG_TRY(setup_prefetcher(g));
+    ZG_TRY(capture_all(g, gs(g)));
+    if (parent) {
+        ++parent->n_children;
+        g->counted = true;
+    }
+    return ZG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -952,7 +1083,7 @@ int zg_gpt_create_ex(zg_gpt** out, const zg_gpt_config* config, size_t batch, un
     ZG_REQUIRE(!(flags & ZG_GPT_KV_F16) || !(flags & ZG_GPT_KV_B24), ZG_ERR_ARG, "ZG_GPT_KV_F16 and ZG_GPT_KV_B24 exclude each other");
     ZG_REQUIRE(!(flags & ZG_GPT_WEIGHTS_F32) || !(flags & ZG_GPT_WEIGHTS_B24), ZG_ERR_ARG,
                "ZG_GPT_WEIGHTS_F32 and ZG_GPT_WEIGHTS_B24 exclude each other");
-    zg_gpt* g = new zg_gpt();
+    zg_gpt* g = new zg_gpt();  // (every member zero: release() relies on it)
     g->cfg = c;
     g->batch = batch;
     g->flags = flags;
@@ -960,151 +1091,12 @@ int zg_gpt_create_ex(zg_gpt** out, const zg_gpt_config* config, size_t batch, un
     g->wbytes = g->wt == WT_BF16 ? 2 : g->wt == WT_B24 ? 3 : 4;
     g->kv_mode = (flags & ZG_GPT_KV_F16) ? 1 : (flags & ZG_GPT_KV_B24) ? 2 : 0;
     g->max_splits = (int)((c.context_size + kAttnChunk - 1) / kAttnChunk);
-    g->graph_stream = nullptr;
-    g->stream = nullptr;
     g->parent = parent;
-    g->n_children = 0;
-    g->gen_open = false;
-    g->pf_stream = nullptr;
-    g->pf_ev_main = g->pf_ev_side = nullptr;
-    carve(g, nullptr, nullptr);
-    g->arena_bytes = (parent ? 0 : g->weight_region_bytes) + g->state_bytes;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->arena), g->arena_bytes);
-    if (e != hipSuccess) {
-        delete g;
-        return hip_fail(e, "hipMalloc(model arena)", __FILE__, __LINE__);
+    const int st = build_handle(g, opt);
+    if (st != ZG_OK) {
+        release(g);
+        return st;
     }
-    g->wbase = parent ? parent->wbase : g->arena;
-    char* const sbase = parent ? g->arena : g->arena + g->weight_region_bytes;
-    carve(g, g->wbase, sbase);
-    (void)hipMemset(sbase, 0, g->state_bytes);
-    if (opt && opt->own_stream) {  // a private stream: its priority decides the hardware queue it shares (profiles/NOTEBOOK.md §5)
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);  // numerically: greatest <= 0 <= least
-        const int pr = opt->stream_priority > 0 ? greatest : opt->stream_priority < 0 ? least : 0;
-        e = hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, pr);
-        if (e != hipSuccess) {
-            (void)hipFree(g->arena);
-            delete g;
-            return hip_fail(e, "hipStreamCreateWithPriority(handle stream)", __FILE__, __LINE__);
-        }
-    }
-    {
-        GemvArgs a = base_gemv(g, g->wte, nullptr, c.vocab_size, c.n_embed, 0);
-        a.prologue = PRO_LAYERNORM;
-        a.epilogue = EPI_ARGMAX;  // the plan depends on the epilogue (workgroup width)
-        g->lm_grid = gemv_plan(a, g->wt);
-    }
-    {   // the widest input of a Block (mlp c_proj: 4 E floats per sequence) must fit the batched kernels' LDS
-        GemvArgs a = base_gemv(g, g->layers[0].mlp_proj_w, nullptr, c.n_embed, 4 * c.n_embed, 0);
-        if (!gemv_supported(a, g->wt)) {
-            if (g->stream) (void)hipStreamDestroy(g->stream);
-            (void)hipFree(g->arena);
-            delete g;
-            set_error("batch %zu with n_embed %zu: %zu input rows of 4*n_embed floats do not fit the LDS (use a smaller batch)",
-                      batch, c.n_embed, batch);
-            return ZG_ERR_UNSUPPORTED;
-        }
-    }
-    g->pl_on = false;
-    if (g->wt == WT_BF16 && batch >= 2 && !(decode_paths_off() & 1)) {  // all three plane-fed Linears on the matrix-core path?
-        const zg_layer& y = g->layers[0];
-        GemvArgs a1 = base_gemv(g, y.c_attn_w, y.c_attn_b, 3 * c.n_embed, c.n_embed, 0);
-        a1.prologue = PRO_LAYERNORM;
-        a1.ln_c2 = y.c_attn_c2;
-        a1.ln_c3 = y.c_attn_c3;
-        a1.epilogue = EPI_QKV;
-        GemvArgs a4 = base_gemv(g, y.c_fc_w, y.c_fc_b, 4 * c.n_embed, c.n_embed, 0);
-        a4.prologue = PRO_LAYERNORM;
-        a4.ln_c2 = y.c_fc_c2;
-        a4.ln_c3 = y.c_fc_c3;
-        a4.epilogue = EPI_GELU;
-        GemvArgs a5 = base_gemv(g, y.mlp_proj_w, y.mlp_proj_b, c.n_embed, 4 * c.n_embed, 0);
-        a5.prologue = PRO_NONE;
-        a5.epilogue = EPI_RESIDUAL;
-        GemvArgs a3 = base_gemv(g, y.c_proj_w, y.c_proj_b, c.n_embed, c.n_embed, 0);
-        a3.prologue = PRO_NONE;
-        a3.epilogue = EPI_RESIDUAL;
-        g->pl_on = c.n_embed % 32 == 0 && gemv_planes_ok(a1, g->wt) && gemv_planes_ok(a3, g->wt) && gemv_planes_ok(a4, g->wt) &&
-                   gemv_planes_ok(a5, g->wt);
-    }
-    g->tags_on = g->pl_on && !(decode_paths_off() & 4);
-    g->spin_limit = (unsigned)env_int("ZGPT2_TAG_SPIN_LIMIT", 1 << 20);
-    // one sequence on the fp32 cache: ln_1 + c_attn and the attention as one launch where c_attn runs on the LayerNorm-folding
-    // kernel (ZGPT2_DECODE_PATHS_OFF bit 64: two launches)
-    g->fused_on = batch == 1 && !(decode_paths_off() & 64) && c.n_layer <= 127 &&
-                  attn_qkv_ok(c_attn_args(g, g->layers[0], 0), attn_args(g, g->layers[0], (int)c.context_size));
-    g->st_on = false;
-    if (g->pl_on && !(decode_paths_off() & 8) && c.n_embed % 16 == 0 && c.n_embed / 16 <= 128) {
-        // every producer and consumer of x must be the four-wave kernel
-        const zg_layer& y = g->layers[0];
-        GemvArgs a1 = base_gemv(g, y.c_attn_w, y.c_attn_b, 3 * c.n_embed, c.n_embed, 0);
-        a1.prologue = PRO_LAYERNORM;
-        a1.x_stride = (int)c.n_embed;
-        a1.ln_c2 = y.c_attn_c2;
-        a1.ln_c3 = y.c_attn_c3;
-        a1.epilogue = EPI_QKV;
-        GemvArgs a4 = a1;
-        a4.N = (int)(4 * c.n_embed);
-        a4.epilogue = EPI_GELU;
-        GemvArgs a3 = base_gemv(g, y.c_proj_w, y.c_proj_b, c.n_embed, c.n_embed, 0);
-        a3.prologue = PRO_NONE;
-        a3.epilogue = EPI_RESIDUAL;
-        a3.resid_stride = (int)c.n_embed;
-        GemvArgs a5 = base_gemv(g, y.mlp_proj_w, y.mlp_proj_b, c.n_embed, 4 * c.n_embed, 0);
-        a5.prologue = PRO_NONE;
-        a5.epilogue = EPI_RESIDUAL;
-        a5.resid_stride = (int)c.n_embed;
-        g->st_on = gemv_pl4_ok(a1, g->wt) && gemv_pl4_ok(a3, g->wt) && gemv_pl4_ok(a4, g->wt) && gemv_pl4_ok(a5, g->wt);
-    }
-    if (g->lm_grid > 4096) {
-        if (g->stream) (void)hipStreamDestroy(g->stream);
-        (void)hipFree(g->arena);
-        delete g;
-        set_error("lm_head grid %d exceeds the argmax partial buffer", g->lm_grid);
-        return ZG_ERR_UNSUPPORTED;
-    }
-    g->h_ctrl = nullptr;
-    g->h_ints = nullptr;
-    // (the control mirror and, 256 bytes behind it, the fault word of the tagged hand-overs: pinned, written by the kernels)
-    hipError_t he = hipHostMalloc(reinterpret_cast<void**>(&g->h_ctrl), sizeof(StepCtrl) + 512, hipHostMallocDefault);
-    if (he == hipSuccess)
-        he = hipHostMalloc(reinterpret_cast<void**>(&g->h_ints), (batch * c.context_size + batch) * sizeof(int), hipHostMallocDefault);
-    if (he != hipSuccess) {
-        if (g->h_ctrl) (void)hipHostFree(g->h_ctrl);
-        if (g->stream) (void)hipStreamDestroy(g->stream);
-        (void)hipFree(g->arena);
-        delete g;
-        return hip_fail(he, "hipHostMalloc(control mirrors)", __FILE__, __LINE__);
-    }
-    static_assert(sizeof(StepCtrl) + sizeof(SampleParams) <= 256, "the fault word sits 256 bytes behind the control mirror");
-    g->h_samp = reinterpret_cast<SampleParams*>(reinterpret_cast<char*>(g->h_ctrl) + 128);  // (same pinned block)
-    g->gen_sampled = false;
-    g->fault = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g->h_ctrl) + 256);
-    *g->fault = 0;
-    g->steps_enqueued = 0;
-    g->epochs_since_clear = 0;
-    g->ln_folded = false;
-    {   // decode steps per graph in the generate loop: a graph launch costs ~7 us of idle queue (124M: 224.8 us per token
-        // with 1 step per graph, 220.4 with 2 / 4, 218.3 with 8, 219.5 with 16)
-        const int k = env_int("ZGPT2_GRAPH_STEPS", 8);
-        g->graph_steps = (k == 2 || k == 4 || k == 8 || k == 16 || k == 32 || k == 64) ? (size_t)k : 1;
-    }
-    {   // every decode graph is captured and instantiated here, not on the first forward that needs it
-        int st = setup_prefetcher(g);
-        if (st == ZG_OK) st = capture_all(g, gs(g));
-        if (st != ZG_OK) {
-            drop_prefetcher(g);
-            drop_graphs(g);
-            (void)hipHostFree(g->h_ctrl);
-            (void)hipHostFree(g->h_ints);
-            if (g->stream) (void)hipStreamDestroy(g->stream);
-            (void)hipFree(g->arena);
-            delete g;
-            return st;
-        }
-    }
-    if (parent) ++parent->n_children;
     *out = g;
     return ZG_OK;
 }
@@ -1112,15 +1104,7 @@ int zg_gpt_create_ex(zg_gpt** out, const zg_gpt_config* config, size_t batch, un
 int zg_gpt_destroy(zg_gpt* g) {
     if (!g) return ZG_OK;
     ZG_REQUIRE(g->n_children == 0, ZG_ERR_ARG, "zg_gpt_destroy: %d handle(s) still borrow this one's weights (destroy them first)", g->n_children);
-    (void)hipStreamSynchronize(gs(g));
-    drop_prefetcher(g);
-    drop_graphs(g);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    if (g->parent) --g->parent->n_children;
-    (void)hipFree(g->arena);
-    (void)hipHostFree(g->h_ctrl);
-    (void)hipHostFree(g->h_ints);
-    delete g;
+    release(g);
     return ZG_OK;
 }
 
@@ -1131,45 +1115,52 @@ int zg_gpt_stream(zg_gpt* g, void** hip_stream_out) {
     return ZG_OK;
 }
 
+// Where a tensor slot lives: a vector of n floats (K = 0), or a matrix of n elements in rows of K inputs with, on handles that
+// keep them, its bf16 planes for the whole-prompt GEMMs.
+struct Slot {
+    void* dst;
+    size_t n, K;
+    bf16_t* planes;
+};
+
+static int load_slot(zg_gpt* g, const Slot& t, const char* what, int slot, const float* src, size_t len) {
+    ZG_REQUIRE(t.dst != nullptr, ZG_ERR_ARG, "unknown %s %d", what, slot);
+    ZG_REQUIRE(len == t.n, ZG_ERR_SHAPE, "%s %d expects %zu elements, got %zu", what, slot, t.n, len);
+    const bool mat = t.K != 0;
+    g->ln_folded = false;
+    if (mat && g->wt == WT_B24) return upload_b24(src, t.n, t.K, t.dst, t.planes, gs(g));
+    ZG_TRY(upload_f32(src, t.n, t.dst, mat && g->wt == WT_BF16, gs(g)));
+    if (g->wt == WT_F32 && t.planes) {  // exact bf16 planes of the fp32 matrix for the whole-prompt GEMMs
+        // plane-major [3][out][in]: the matrix as ONE row of out * in elements
+        ZG_REQUIRE(t.n <= (size_t)2147483647 / 3, ZG_ERR_SHAPE, "weight matrix of %zu elements", t.n);  // (split3_kernel indexes 3 n in int)
+        ZG_TRY(launch_split3(reinterpret_cast<const float*>(t.dst), 1, (int)t.n, t.planes, gs(g)));
+        ZG_HIP(hipStreamSynchronize(gs(g)));
+    }
+    return ZG_OK;
+}
+
 int zg_gpt_load_block_tensor(zg_gpt* g, size_t layer, int slot, const float* src, size_t len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && src && layer < g->cfg.n_layer, ZG_ERR_ARG, "load_block_tensor: bad argument");
     ZG_REQUIRE(g->parent == nullptr, ZG_ERR_ARG, "load_block_tensor: this handle borrows its weights (load them into their owner)");
     const size_t E = g->cfg.n_embed;
     zg_layer& y = g->layers[layer];
-    void* dst = nullptr;
-    size_t n = 0;
-    bool mat = false;
-    switch (slot) {
-        case ZG_LN_1_G: dst = y.ln_1_g; n = E; break;
-        case ZG_LN_1_B: dst = y.ln_1_b; n = E; break;
-        case ZG_C_ATTN_W: dst = y.c_attn_w; n = 3 * E * E; mat = true; break;
-        case ZG_C_ATTN_B: dst = y.c_attn_b; n = 3 * E; break;
-        case ZG_C_PROJ_W: dst = y.c_proj_w; n = E * E; mat = true; break;
-        case ZG_C_PROJ_B: dst = y.c_proj_b; n = E; break;
-        case ZG_LN_2_G: dst = y.ln_2_g; n = E; break;
-        case ZG_LN_2_B: dst = y.ln_2_b; n = E; break;
-        case ZG_C_FC_W: dst = y.c_fc_w; n = 4 * E * E; mat = true; break;
-        case ZG_C_FC_B: dst = y.c_fc_b; n = 4 * E; break;
-        case ZG_MLP_PROJ_W: dst = y.mlp_proj_w; n = 4 * E * E; mat = true; break;
-        case ZG_MLP_PROJ_B: dst = y.mlp_proj_b; n = E; break;
-        default: ZG_REQUIRE(false, ZG_ERR_ARG, "unknown block slot %d", slot);
+    Slot t{};
+    switch (slot) {  // (a matrix: K = its input width)
+        case ZG_LN_1_G: t = {y.ln_1_g, E, 0, nullptr}; break;
+        case ZG_LN_1_B: t = {y.ln_1_b, E, 0, nullptr}; break;
+        case ZG_C_ATTN_W: t = {y.c_attn_w, 3 * E * E, E, y.c_attn_p}; break;
+        case ZG_C_ATTN_B: t = {y.c_attn_b, 3 * E, 0, nullptr}; break;
+        case ZG_C_PROJ_W: t = {y.c_proj_w, E * E, E, y.c_proj_p}; break;
+        case ZG_C_PROJ_B: t = {y.c_proj_b, E, 0, nullptr}; break;
+        case ZG_LN_2_G: t = {y.ln_2_g, E, 0, nullptr}; break;
+        case ZG_LN_2_B: t = {y.ln_2_b, E, 0, nullptr}; break;
+        case ZG_C_FC_W: t = {y.c_fc_w, 4 * E * E, E, y.c_fc_p}; break;
+        case ZG_C_FC_B: t = {y.c_fc_b, 4 * E, 0, nullptr}; break;
+        case ZG_MLP_PROJ_W: t = {y.mlp_proj_w, 4 * E * E, 4 * E, y.mlp_proj_p}; break;
+        case ZG_MLP_PROJ_B: t = {y.mlp_proj_b, E, 0, nullptr}; break;
     }
-    ZG_REQUIRE(len == n, ZG_ERR_SHAPE, "block slot %d expects %zu elements, got %zu", slot, n, len);
-    g->ln_folded = false;
-    if (mat && g->wt == WT_B24) {
-        bf16_t* pl = slot == ZG_C_ATTN_W ? y.c_attn_p : slot == ZG_C_PROJ_W ? y.c_proj_p : slot == ZG_C_FC_W ? y.c_fc_p : y.mlp_proj_p;
-        return upload_b24(src, n, slot == ZG_MLP_PROJ_W ? 4 * E : E, dst, y.c_attn_p ? pl : nullptr, gs(g));  // K = the input width
-    }
-    ZG_TRY(upload_f32(src, n, dst, mat && g->wt == WT_BF16, gs(g)));
-    if (mat && g->wt == WT_F32 && y.c_attn_p) {  // exact bf16 planes of the fp32 matrix for the whole-prompt GEMMs
-        bf16_t* pl = slot == ZG_C_ATTN_W ? y.c_attn_p : slot == ZG_C_PROJ_W ? y.c_proj_p : slot == ZG_C_FC_W ? y.c_fc_p : y.mlp_proj_p;
-        // plane-major [3][out][in]: the matrix as ONE row of out * in elements
-        ZG_REQUIRE(n <= (size_t)2147483647 / 3, ZG_ERR_SHAPE, "weight matrix of %zu elements", n);  // (split3_kernel indexes 3 n in int)
-        ZG_TRY(launch_split3(reinterpret_cast<const float*>(dst), 1, (int)n, pl, gs(g)));
-        ZG_HIP(hipStreamSynchronize(gs(g)));
-    }
-    return ZG_OK;
+    return load_slot(g, t, "block slot", slot, src, len);
 }
 
 int zg_gpt_load_tensor(zg_gpt* g, int slot, const float* src, size_t len) {
@@ -1177,20 +1168,14 @@ int zg_gpt_load_tensor(zg_gpt* g, int slot, const float* src, size_t len) {
     ZG_REQUIRE(g && src, ZG_ERR_ARG, "load_tensor: bad argument");
     ZG_REQUIRE(g->parent == nullptr, ZG_ERR_ARG, "load_tensor: this handle borrows its weights (load them into their owner)");
     const size_t E = g->cfg.n_embed;
-    void* dst = nullptr;
-    size_t n = 0;
-    bool mat = false;
+    Slot t{};
     switch (slot) {
-        case ZG_WTE: dst = g->wte; n = g->cfg.vocab_size * E; mat = true; break;
-        case ZG_WPE: dst = g->wpe; n = g->cfg.context_size * E; mat = true; break;
-        case ZG_LN_F_G: dst = g->ln_f_g; n = E; break;
-        case ZG_LN_F_B: dst = g->ln_f_b; n = E; break;
-        default: ZG_REQUIRE(false, ZG_ERR_ARG, "unknown slot %d", slot);
+        case ZG_WTE: t = {g->wte, g->cfg.vocab_size * E, E, nullptr}; break;
+        case ZG_WPE: t = {g->wpe, g->cfg.context_size * E, E, nullptr}; break;
+        case ZG_LN_F_G: t = {g->ln_f_g, E, 0, nullptr}; break;
+        case ZG_LN_F_B: t = {g->ln_f_b, E, 0, nullptr}; break;
     }
-    ZG_REQUIRE(len == n, ZG_ERR_SHAPE, "slot %d expects %zu elements, got %zu", slot, n, len);
-    g->ln_folded = false;
-    if (mat && g->wt == WT_B24) return upload_b24(src, n, E, dst, nullptr, gs(g));
-    return upload_f32(src, n, dst, mat && g->wt == WT_BF16, gs(g));
+    return load_slot(g, t, "slot", slot, src, len);
 }
 
 int zg_gpt_weight_arena(zg_gpt* g, void** device_ptr, size_t* bytes) {
@@ -1251,7 +1236,7 @@ static int clear_kv(zg_gpt* g, hipStream_t s, size_t from_row = 0) {
         ZG_HIP(hipMemsetAsync(g->layers[0].k_cache, 0, g->kv_region_bytes, s));
         return ZG_OK;
     }
-    const size_t elems = B * C * E, kvb = g->kv_mode == 1 ? 2 : g->kv_mode == 2 ? 3 : 4;
+    const size_t elems = B * C * E, kvb = kv_elem_bytes(g);
     const size_t stride = L > 1 ? (size_t)(reinterpret_cast<char*>(g->layers[1].k_cache) - reinterpret_cast<char*>(g->layers[0].k_cache)) / 2
                                 : (size_t)(reinterpret_cast<char*>(g->layers[0].v_cache) - reinterpret_cast<char*>(g->layers[0].k_cache));
     ZG_REQUIRE(stride >= elems * kvb && reinterpret_cast<char*>(g->layers[0].v_cache) - reinterpret_cast<char*>(g->layers[0].k_cache) == (ptrdiff_t)stride,
@@ -1267,7 +1252,7 @@ int zg_gpt_step_bytes(zg_gpt* g, size_t seq_len, size_t* weight_bytes, size_t* k
     const size_t E = g->cfg.n_embed;
     // wbytes * (sum_layers in*out + V*E) + kvbytes * 2 * T * E * L (per sequence)
     if (weight_bytes) *weight_bytes = g->wbytes * (g->cfg.n_layer * 12 * E * E + g->cfg.vocab_size * E);
-    if (kv_bytes) *kv_bytes = (g->kv_mode == 1 ? 2 : g->kv_mode == 2 ? 3 : 4) * 2 * seq_len * E * g->cfg.n_layer * g->batch;
+    if (kv_bytes) *kv_bytes = kv_elem_bytes(g) * 2 * seq_len * E * g->cfg.n_layer * g->batch;
     return ZG_OK;
 }
 
@@ -1286,20 +1271,13 @@ static int forward_enqueue(zg_gpt* g, size_t seq_len, const size_t* tokens, size
         ZG_REQUIRE(tokens[b] < V, ZG_ERR_SHAPE, "gpt_forward: token %zu >= vocab %zu", tokens[b], V);
         g->h_ints[b] = (int)tokens[b];
     }
-    g->h_ctrl->step = (int)seq_len - 1;
-    g->h_ctrl->seq_len = (int)seq_len;
-    g->h_ctrl->mode = 1;
-    g->h_ctrl->n_partials = g->lm_grid;
     ZG_HIP(hipMemcpyAsync(g->forced, g->h_ints, g->batch * sizeof(int), hipMemcpyHostToDevice, s));
-    ZG_HIP(hipMemcpyAsync(g->ctrl, g->h_ctrl, sizeof(StepCtrl), hipMemcpyHostToDevice, s));
+    ZG_TRY(stage_ctrl(g, seq_len - 1, seq_len, 1, s));
     if (seq_len == 1) ZG_TRY(clear_kv(g, s));
     ZG_TRY(note_steps(g, 1, s));
     ZG_TRY(ensure_ln_folded(g, s));
     ZG_TRY(run_step(g, compute_logits != 0, seq_len, s));
-    if (logits_out) {
-        ZG_HIP(hipMemcpyAsync(logits_out, g->logits, g->batch * V * sizeof(float),
-                              is_device_ptr(logits_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    }
+    if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, g->batch * V, s));
     return ZG_OK;
 }
 
@@ -1336,15 +1314,9 @@ int zg_gpt_prefill(zg_gpt* g, const size_t* tokens, size_t token_stride, size_t 
     if (compute_logits) {  // ln_f + lm_head of each sequence's last position through the decode kernels
         ZG_HIP(hipMemcpy2DAsync(g->x, E * 4, g->pf_x + (n_tokens - 1) * E, n_tokens * E * 4, E * 4, B,
                                 hipMemcpyDeviceToDevice, s));
-        g->h_ctrl->step = (int)n_tokens - 1;
-        g->h_ctrl->seq_len = (int)n_tokens;
-        g->h_ctrl->mode = 1;
-        g->h_ctrl->n_partials = g->lm_grid;
-        ZG_HIP(hipMemcpyAsync(g->ctrl, g->h_ctrl, sizeof(StepCtrl), hipMemcpyHostToDevice, s));
+        ZG_TRY(stage_ctrl(g, n_tokens - 1, n_tokens, 1, s));
         ZG_TRY(enqueue_lm_head(g, s));
-        if (logits_out)
-            ZG_HIP(hipMemcpyAsync(logits_out, g->logits, B * V * sizeof(float),
-                                  is_device_ptr(logits_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, B * V, s));
     }
     ZG_HIP(hipStreamSynchronize(s));
     return check_fault(g);
@@ -1389,9 +1361,7 @@ int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_toke
     ZG_TRY(launch_sample(g->logits, (int)B, (int)V, temp, d_u, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->cur_token, probs_out != nullptr,
                          s));  // main.zig:200-206
     ZG_HIP(hipMemcpyAsync(g->h_ints + B, g->cur_token, B * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (probs_out)
-        ZG_HIP(hipMemcpyAsync(probs_out, g->logits, B * V * sizeof(float),
-                              is_device_ptr(probs_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    if (probs_out) ZG_TRY(copy_out_f32(probs_out, g->logits, B * V, s));
     ZG_HIP(hipStreamSynchronize(s));
     ZG_TRY(check_fault(g));
     for (size_t b = 0; b < B; ++b) tokens_out[b] = (size_t)g->h_ints[B + b];
@@ -1402,13 +1372,12 @@ int zg_gpt_hidden(zg_gpt* g, float* x_out, size_t len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && x_out && len >= g->batch * g->cfg.n_embed, ZG_ERR_ARG, "gpt_hidden: bad argument");
     hipStream_t s = gs(g);
-    ZG_HIP(hipMemcpyAsync(x_out, g->x, g->batch * g->cfg.n_embed * sizeof(float),
-                          is_device_ptr(x_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    ZG_TRY(copy_out_f32(x_out, g->x, g->batch * g->cfg.n_embed, s));
     ZG_HIP(hipStreamSynchronize(s));
     return check_fault(g);
 }
 
-// A generation in three parts, so that several handles' generations can be fed to their streams turn by turn
+// A generation in three parts, so that several handles' generations can be fed to their streams side by side
 // (zg_gpt_generate_enqueue_many): gen_begin — prompts, cache clearing, the whole-prompt pass, the prefetcher's start;
 // gen_pump — ONE graph launch (graph_steps decode steps) or one single step, false when nothing is left; gen_end — the
 // prefetcher's stop word and the record of the last pick.  After a successful gen_begin, gen_end must run (also on failure:
@@ -1438,10 +1407,6 @@ static int gen_begin(zg_gpt* g, const size_t* prompts, size_t prompt_stride, con
     size_t first = 0;
     if (g->pf_x != nullptr && min_prompt >= prefill_min())
         first = min_prompt < n_steps ? min_prompt : n_steps;
-    g->h_ctrl->step = (int)first;
-    g->h_ctrl->seq_len = (int)first;
-    g->h_ctrl->mode = sampled ? 2 : 0;
-    g->h_ctrl->n_partials = g->lm_grid;
     g->gen_sampled = sampled;
     if (sampled) {
         g->h_samp->inv_temp = 1.0f / temp;
@@ -1451,7 +1416,7 @@ static int gen_begin(zg_gpt* g, const size_t* prompts, size_t prompt_stride, con
     }
     ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(g->prompt_len, g->h_ints + B * C, B * sizeof(int), hipMemcpyHostToDevice, s));
-    ZG_HIP(hipMemcpyAsync(g->ctrl, g->h_ctrl, sizeof(StepCtrl), hipMemcpyHostToDevice, s));
+    ZG_TRY(stage_ctrl(g, first, first, sampled ? 2 : 0, s));
     ZG_TRY(clear_kv(g, s, first));
     ZG_TRY(ensure_ln_folded(g, s));
     if (first > 0) {
@@ -1484,14 +1449,9 @@ static int gen_pump(zg_gpt* g, bool* more) {
     }
     if (K > 1 && st >= g->gen_min_prompt && st % K == 0 && st + K <= n_steps && st + K <= C) {
         if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
-        const size_t b = st / 64;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64)
-        if (g->gen_sampled) {
-            ZG_TRY(capture_sampled(g, b, true, s));
-            ZG_HIP(hipGraphLaunch(g->graphs_ks[b], s));
-        } else {
-            ZG_TRY(capture_multi(g, b, s));
-            ZG_HIP(hipGraphLaunch(g->graphs_k[b], s));
-        }
+        hipGraphExec_t e;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64)
+        ZG_TRY(graph_exec(g, g->gen_sampled ? G_SAMPLED_MULTI : G_MULTI, bucket_of(st + 1), s, &e));
+        ZG_HIP(hipGraphLaunch(e, s));
         g->gen_pos = st + K;
     } else {
         ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_sampled));
@@ -1499,6 +1459,13 @@ static int gen_pump(zg_gpt* g, bool* more) {
     }
     *more = g->gen_pos < n_steps;
     return ZG_OK;
+}
+
+// gen_pump until nothing is left or it fails
+static int gen_pump_all(zg_gpt* g) {
+    int rs = ZG_OK;
+    for (bool more = true; more && rs == ZG_OK;) rs = gen_pump(g, &more);
+    return rs;
 }
 
 static int gen_end(zg_gpt* g, int rs) {
@@ -1515,9 +1482,7 @@ int zg_gpt_generate_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stri
                             size_t n_steps) {
     ZG_TRY(require_init());
     ZG_TRY(gen_begin(g, prompts, prompt_stride, prompt_lens, n_steps));
-    int rs = ZG_OK;
-    for (bool more = true; more && rs == ZG_OK;) rs = gen_pump(g, &more);
-    return gen_end(g, rs);
+    return gen_end(g, gen_pump_all(g));
 }
 
 // generate (src/main.zig:322-342) AS THE REFERENCE RUNS IT: every token behind the prompt is drawn by GPT.sample
@@ -1531,9 +1496,7 @@ int zg_gpt_generate_sample_enqueue(zg_gpt* g, const size_t* prompts, size_t prom
     ZG_TRY(require_init());
     ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "generate_sample: temperature %f", temp);
     ZG_TRY(gen_begin(g, prompts, prompt_stride, prompt_lens, n_steps, true, temp, seed));
-    int rs = ZG_OK;
-    for (bool more = true; more && rs == ZG_OK;) rs = gen_pump(g, &more);
-    return gen_end(g, rs);
+    return gen_end(g, gen_pump_all(g));
 }
 
 int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps, float temp,
@@ -1546,8 +1509,8 @@ int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_strid
 // generate (src/main.zig:322-342) for the prompts of SEVERAL handles at once: independent sequences need not run in lock step
 // (the reference's batch restriction, ops.zig:126-128, lifted the other way) — every handle decodes its own prompts on its own
 // stream (zg_gpt_create_ex: own_stream) and the chip overlaps the chains, each of which leaves it idle across every one of its
-// launch boundaries.  The handles' graph launches are enqueued turn by turn: a hardware queue holds a fraction of a
-// generation's dispatches, and a host that fed one handle to the end first would block on that queue while the others idle.
+// launch boundaries.  The handles are fed side by side: a hardware queue holds a fraction of a generation's dispatches, and a
+// host that fed one handle to the end first would block on that queue while the others idle.
 int zg_gpt_generate_enqueue_many(zg_gpt* const* handles, size_t n_handles, const size_t* prompts, size_t prompt_stride,
                                  const size_t* prompt_lens, size_t n_steps) {
     ZG_TRY(require_init());
@@ -1568,8 +1531,7 @@ int zg_gpt_generate_enqueue_many(zg_gpt* const* handles, size_t n_handles, const
         row += handles[begun]->batch;
     }
     char msg[512] = "";
-    static const int feeders = env_int("ZGPT2_MANY_THREADS", 1);
-    if (rs == ZG_OK && feeders && begun > 1) {
+    if (rs == ZG_OK && begun > 1) {
         // one feeder thread per handle: a hipGraphLaunch returns only when its hardware queue has room for the graph's
         // dispatches, so one thread feeding all queues in turn stands still whenever the slowest chain's queue is full
         std::vector<std::thread> th;
@@ -1578,10 +1540,8 @@ int zg_gpt_generate_enqueue_many(zg_gpt* const* handles, size_t n_handles, const
         const int dev = ctx().device;
         for (size_t i = 0; i < begun; ++i)
             th.emplace_back([&, i]() {
-                int r = hipSetDevice(dev) == hipSuccess ? ZG_OK : ZG_ERR_HIP;
-                for (bool more = true; more && r == ZG_OK;) r = gen_pump(handles[i], &more);
-                res[i] = r;
-                if (r != ZG_OK) errs[i] = zg_last_error();  // (the message is thread-local)
+                res[i] = hipSetDevice(dev) == hipSuccess ? gen_pump_all(handles[i]) : ZG_ERR_HIP;
+                if (res[i] != ZG_OK) errs[i] = zg_last_error();  // (the message is thread-local)
             });
         for (auto& t : th) t.join();
         for (size_t i = 0; i < begun && rs == ZG_OK; ++i)
@@ -1589,16 +1549,8 @@ int zg_gpt_generate_enqueue_many(zg_gpt* const* handles, size_t n_handles, const
                 rs = res[i];
                 snprintf(msg, sizeof msg, "%s", errs[i].c_str());
             }
-    } else {
-        bool any = rs == ZG_OK;
-        while (any && rs == ZG_OK) {
-            any = false;
-            for (size_t i = 0; i < begun && rs == ZG_OK; ++i) {
-                bool more = false;
-                if (handles[i]->gen_pos < handles[i]->gen_n) rs = gen_pump(handles[i], &more);
-                any |= more;
-            }
-        }
+    } else {  // one handle: the calling thread pumps
+        if (rs == ZG_OK) rs = gen_pump_all(handles[0]);
         if (rs != ZG_OK) snprintf(msg, sizeof msg, "%s", zg_last_error());
     }
     int first_err = rs;
@@ -1668,20 +1620,18 @@ int zg_gpt_profile_step(zg_gpt* g, size_t seq_len, int iters, float* us_out, siz
     ZG_TRY(ensure_ln_folded(g, s));
     ZG_TRY(note_steps(g, (size_t)iters, s));
     for (size_t b = 0; b < g->batch; ++b) g->h_ints[b] = (int)(b % g->cfg.vocab_size);
-    g->h_ctrl->step = (int)seq_len - 1;
-    g->h_ctrl->seq_len = (int)seq_len;
-    g->h_ctrl->mode = 1;
-    g->h_ctrl->n_partials = g->lm_grid;
     ZG_HIP(hipMemcpyAsync(g->forced, g->h_ints, g->batch * sizeof(int), hipMemcpyHostToDevice, s));
-    ZG_HIP(hipMemcpyAsync(g->ctrl, g->h_ctrl, sizeof(StepCtrl), hipMemcpyHostToDevice, s));
+    ZG_TRY(stage_ctrl(g, seq_len - 1, seq_len, 1, s));
     static StepProf prof;  // events are created on first use and reused
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // All iterations are enqueued before the single synchronisation so that the queue stays ahead of
     // the GPU (an interval then is kernel + launch boundary, not kernel + host launch latency).
     prof.n = 0;
+    StepOpts timed;
+    timed.prof = &prof;
     double null_us = 0.0;
     for (int it = 0; it < iters; ++it) {
-        ZG_TRY(enqueue_step(g, true, bucket_t_hi(g, seq_len + it), s, &prof));  // eager; the embed kernel advances the position
+        ZG_TRY(enqueue_step(g, true, bucket_t_hi(g, seq_len + it), s, timed));  // eager; the embed kernel advances the position
         // calibration: a one-element copy recorded the same way = launch boundary + event overhead
         ZG_TRY(launch_copy_f32(g->q, g->q + 4, 1, s));
         ZG_TRY(prof_mark(&prof, 8, s));
@@ -1720,41 +1670,41 @@ int zg_gpt_time_kernel(zg_gpt* g, int which_and_options, int iters, float* avg_u
     ZG_HIP(hipStreamSynchronize(s));
     ZG_TRY(ensure_ln_folded(g, s));
     ZG_TRY(note_steps(g, (size_t)iters + 8, s));  // (one epoch per replay of the chain)
-    g->h_ctrl->step = (int)T - 1;
-    g->h_ctrl->seq_len = (int)T;
-    g->h_ctrl->mode = 1;
-    g->h_ctrl->n_partials = g->lm_grid;
-    ZG_HIP(hipMemcpyAsync(g->ctrl, g->h_ctrl, sizeof(StepCtrl), hipMemcpyHostToDevice, s));
-    const int chain = 64;
-    hipGraph_t graph = nullptr;
+    ZG_TRY(stage_ctrl(g, T - 1, T, 1, s));
+    const int chain = 64, reps = (iters + chain - 1) / chain;
     hipGraphExec_t exec = nullptr;
-    ZG_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    int st = ZG_OK;
-    // tagged hand-overs: a new epoch per replay and a launch id per chain position, so that every merging split / slice
-    // waits for ITS writers as in a real step (one more tiny launch per 64)
-    if ((g->tags_on || g->fused_on) && which != 0) st = launch_epoch_bump(g->epoch, s);
-    for (int i = 0; i < chain && st == ZG_OK; ++i)
-        st = enqueue_step(g, true, bucket_t_hi(g, T), s, nullptr, which, cycle ? (size_t)i % g->cfg.n_layer : 0, nullptr, i);
-    hipError_t ce = hipStreamEndCapture(s, &graph);
-    if (st != ZG_OK) return st;
-    ZG_HIP(ce);
-    ZG_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    hipEvent_t e0, e1;
-    ZG_HIP(hipEventCreate(&e0));
-    ZG_HIP(hipEventCreate(&e1));
-    ZG_HIP(hipGraphLaunch(exec, s));
-    ZG_HIP(hipStreamSynchronize(s));
-    const int reps = (iters + chain - 1) / chain;
-    ZG_HIP(hipEventRecord(e0, s));
-    for (int r = 0; r < reps; ++r) ZG_HIP(hipGraphLaunch(exec, s));
-    ZG_HIP(hipEventRecord(e1, s));
-    ZG_HIP(hipEventSynchronize(e1));
+    ZG_TRY(capture_graph(s, &exec, [&] {
+        // tagged hand-overs: a new epoch per replay and a launch id per chain position, so that every merging split / slice
+        // waits for ITS writers as in a real step (one more tiny launch per 64)
+        int st = ZG_OK;
+        if ((g->tags_on || g->fused_on) && which != 0) st = launch_epoch_bump(g->epoch, s);
+        StepOpts o;
+        o.only = which;
+        for (int i = 0; i < chain && st == ZG_OK; ++i) {
+            o.only_layer = cycle ? (size_t)i % g->cfg.n_layer : 0;
+            o.salt = i;
+            st = enqueue_step(g, true, bucket_t_hi(g, T), s, o);
+        }
+        return st;
+    }));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
     float ms = 0.0f;
-    ZG_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    const int st = [&]() -> int {
+        ZG_HIP(hipEventCreate(&e0));
+        ZG_HIP(hipEventCreate(&e1));
+        ZG_HIP(hipGraphLaunch(exec, s));
+        ZG_HIP(hipStreamSynchronize(s));
+        ZG_HIP(hipEventRecord(e0, s));
+        for (int r = 0; r < reps; ++r) ZG_HIP(hipGraphLaunch(exec, s));
+        ZG_HIP(hipEventRecord(e1, s));
+        ZG_HIP(hipEventSynchronize(e1));
+        ZG_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return ZG_OK;
+    }();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
     (void)hipGraphExecDestroy(exec);
-    (void)hipGraphDestroy(graph);
+    ZG_TRY(st);
     *avg_us = ms * 1000.0f / (float)(reps * chain);
     if (algorithmic_bytes) *algorithmic_bytes = bytes_tab[which];
     return check_fault(g);
