@@ -209,6 +209,9 @@ enum {
                                     bf16 plane + a plane of 8 more mantissa bits): 3/4 of the fp32 cache's traffic, 2^-17 per
                                     cached element — inside the 1e-3 parity bound at full context, unlike ZG_GPT_KV_F16 (which
                                     it excludes) */
+    ZG_GPT_TRUNCATED_GENERATE = 1 << 9, /* capture the decode graphs of zg_gpt_generate_sample_ex_* (top-k / top-p truncation) at
+                                      create as well (otherwise a truncated generation captures those of the buckets it
+                                      touches when it begins, before its first step: the one place such a call may allocate) */
     ZG_GPT_WEIGHTS_B24 = 1 << 8  /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
                                     value rounded to nearest even at 16 mantissa bits (never to inf), row r of an [out][in]
                                     matrix = [in bf16-shaped upper halves | in low bytes].  3/4 of fp32's weight bytes, 2^-17
@@ -331,6 +334,38 @@ int zg_gpt_generate_sample_enqueue(zg_gpt* g, const size_t* prompts, size_t prom
                                    float temp, uint64_t seed);
 int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps, float temp,
                            uint64_t seed, size_t* out_tokens, size_t out_len);
+/* Sampler options of the *_ex calls, the same for every row of a call.  temp > 0.  top_k: keep the top_k largest logits of a row
+ * (0 or >= vocab: off).  top_p in (0, 1]: of what top-k kept, keep the smallest set of largest logits whose probability mass
+ * reaches top_p (1: off) — the sequential order HF, vLLM and llama.cpp use.  For a row x: tau_k = the k-th largest value counting
+ * duplicates; e = exp(x / temp - max / temp) over K = { x >= tau_k }; tau_p = the largest value v of K with
+ * sum{ e : x >= v } >= top_p * sum{ e : K }; kept = { x >= max(tau_k, tau_p) }.  Ties at a threshold are all kept (the result never
+ * depends on a sort order; -0.0 and +0.0 are a tie), the most probable token always is.  The draw is zg_gpt_sample's over the
+ * kept weights (dropped indices weigh 0); probabilities are renormalised, exactly 0 where dropped.  The thresholds are found
+ * exactly (a radix select on the device, integer sums): the same inputs give the same tokens on every run.  A row holding a
+ * NaN gives some token < vocab. */
+typedef struct {
+    float temp;
+    size_t top_k;
+    float top_p;
+} zg_sample_options;
+/* zg_gpt_sample with options.  Both filters off: exactly zg_gpt_sample (bit-identical tokens and probabilities).  Bad options
+ * (NULL, temp <= 0, top_p <= 0, > 1 or NaN): ZG_ERR_ARG before anything is enqueued. */
+int zg_gpt_sample_ex(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* options,
+                     const float* uniforms, uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len);
+/* zg_gpt_generate_sample_* with options: the device loop with the selection kernels in front of the sampler node (graphs of
+ * their own: ZG_GPT_TRUNCATED_GENERATE; the option values live in device memory, one graph serves them all).  Returns exactly the
+ * tokens of the host loop over zg_gpt_sample_ex(..., options, NULL, seed, ...).  Both filters off: zg_gpt_generate_sample_*
+ * itself.  Bad options: ZG_ERR_ARG before anything is enqueued.  Results through zg_gpt_generate_fetch. */
+int zg_gpt_generate_sample_ex_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                      const zg_sample_options* options, uint64_t seed);
+int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                              const zg_sample_options* options, uint64_t seed, size_t* out_tokens, size_t out_len);
+/* Test entry: the sampler kernels of zg_gpt_sample_ex on the caller's logits [batch <= 64, vocab <= 262144] (host or device, as
+ * uniforms [batch] and the outputs), a small kernel standing in for lm_head's row-maximum partials.  Needs zg_init only.
+ * probs_out [batch, vocab] and thresholds_out [batch] (max(tau_k, tau_p) of each row; a zero threshold is +0.0; -inf with both
+ * filters off) may be NULL.  Allocates its workspace per call. */
+int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* options, const float* uniforms,
+                         size_t* tokens_out, float* probs_out_or_null, float* thresholds_out_or_null);
 /* The same for the prompts of several handles at once (handles on distinct streams: zg_gpt_create_ex): prompts is
  * [sum of the handles' batches, prompt_stride], rows in handle order, prompt_lens alike; every handle generates its own rows.
  * A graph launch returns only when its hardware queue has room, so the handles are fed by one short-lived feeder thread each

@@ -100,6 +100,8 @@ struct zg_gpt {
     SampleParams* samp;       // device: temperature and seed of the generation in flight
     SampleParams* h_samp;     // pinned mirror
     bool gen_sampled;         // the generation in flight draws its tokens
+    int gen_trunc;            // ... behind top-k / top-p truncation: filter launches per step (3: one filter, 6: both; 0: none)
+    FilterWs filt;            // selection workspace of the truncated sampler (sample_filter.h), zero at create
     size_t graph_steps;
     hipStream_t graph_stream;
     size_t steps_enqueued;
@@ -218,6 +220,7 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
     g->sampled = (int*)P(B * 4);
     g->samp = (SampleParams*)P(sizeof(SampleParams));
     g->samp_ws = (float*)P(sample_workspace_floats((int)B) * 4);
+    g->filt = filter_workspace(P(filter_workspace_bytes((int)B)), (int)B);
     g->xp = (bf16_t*)P(E * 48);
     g->hp = (bf16_t*)P(4 * E * 48);
     g->ap = (bf16_t*)P(E * 48);
@@ -542,6 +545,7 @@ struct StepOpts {
     // layer, so that consecutive launches of the chain never find each other's tags
     int salt = -1;
     bool with_sampler = false;  // GPT.sample's tail behind lm_head (with_logits only)
+    int trunc_levels = 0;       // ... behind top-k / top-p truncation: 3 (one filter) or 6 (both) selection launches in front of it
 };
 
 // One decode step = GPT.forward (main.zig:178-195) for all sequences.
@@ -618,7 +622,10 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         ZG_TRY(prof_mark(prof, 6, s));
     }
     // GPT.sample's tail (main.zig:200-206) on the logits of this step: the next step's embed kernel feeds what it draws (mode 2)
-    if (o.with_sampler && with_logits && only < 0 && !rec)
+    if (o.with_sampler && o.trunc_levels && with_logits && only < 0 && !rec)
+        ZG_TRY(launch_sample_filtered(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, o.trunc_levels, nullptr, g->ctrl, g->part_val, g->lm_grid,
+                                      g->lm_grid, g->samp_ws, g->filt, g->sampled, false, s));
+    else if (o.with_sampler && with_logits && only < 0 && !rec)
         ZG_TRY(launch_sample_step(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, g->ctrl, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws,
                                   g->sampled, s));
     return ZG_OK;
@@ -817,6 +824,13 @@ enum GraphKind {
     // it; captured at create with ZG_GPT_SAMPLED_GENERATE, otherwise on the first sampled generation
     G_SAMPLED,
     G_SAMPLED_MULTI,
+    // generate with the truncated sampler (zg_gpt_generate_sample_ex_*): the same with the selection launches of ONE filter
+    // (G_TRUNC*) or of top-k and top-p together (G_TRUNC2*) in front of the sampler; the option values are read on the device.
+    // Captured at create with ZG_GPT_TRUNCATED_GENERATE, otherwise when the first generation that needs them begins.
+    G_TRUNC,
+    G_TRUNC_MULTI,
+    G_TRUNC2,
+    G_TRUNC2_MULTI,
     G_KINDS
 };
 
@@ -849,9 +863,10 @@ int graph_exec(zg_gpt* g, GraphKind kind, size_t b, hipStream_t s, hipGraphExec_
     hipGraphExec_t& e = g->graphs[kind * g->n_buckets + b];
     if (!e) {
         const int t_hi = bucket_t_hi(g, (b + 1) * 64);  // any length of the bucket: only its upper bound is baked in
-        const size_t n_steps = (kind == G_MULTI || kind == G_SAMPLED_MULTI) ? g->graph_steps : 1;
+        const size_t n_steps = (kind == G_MULTI || kind == G_SAMPLED_MULTI || kind == G_TRUNC_MULTI || kind == G_TRUNC2_MULTI) ? g->graph_steps : 1;
         StepOpts o;
-        o.with_sampler = kind == G_SAMPLED || kind == G_SAMPLED_MULTI;
+        o.with_sampler = kind >= G_SAMPLED;
+        o.trunc_levels = (kind == G_TRUNC || kind == G_TRUNC_MULTI) ? 3 : (kind == G_TRUNC2 || kind == G_TRUNC2_MULTI) ? 6 : 0;
         ZG_TRY(capture_graph(s, &e, [&] {
             int st = ZG_OK;
             for (size_t i = 0; i < n_steps && st == ZG_OK; ++i) st = enqueue_step(g, kind != G_STEP, t_hi, s, o);
@@ -859,6 +874,20 @@ int graph_exec(zg_gpt* g, GraphKind kind, size_t b, hipStream_t s, hipGraphExec_
         }));
     }
     *out = e;
+    return ZG_OK;
+}
+
+GraphKind sampler_kind(int trunc_levels, bool multi) {
+    return trunc_levels == 3 ? (multi ? G_TRUNC_MULTI : G_TRUNC) : trunc_levels == 6 ? (multi ? G_TRUNC2_MULTI : G_TRUNC2) : (multi ? G_SAMPLED_MULTI : G_SAMPLED);
+}
+
+// The truncated sampler's graphs (trunc_levels 3 or 6) of buckets b0 .. b1
+int capture_truncated(zg_gpt* g, int trunc_levels, size_t b0, size_t b1, hipStream_t s) {
+    hipGraphExec_t e;
+    for (size_t b = b0; b <= b1 && b < g->n_buckets; ++b) {
+        ZG_TRY(graph_exec(g, sampler_kind(trunc_levels, false), b, s, &e));
+        if (g->graph_steps > 1) ZG_TRY(graph_exec(g, sampler_kind(trunc_levels, true), b, s, &e));
+    }
     return ZG_OK;
 }
 
@@ -882,22 +911,25 @@ int capture_all(zg_gpt* g, hipStream_t s) {
             ZG_TRY(graph_exec(g, G_SAMPLED, b, s, &e));
             if (g->graph_steps > 1) ZG_TRY(graph_exec(g, G_SAMPLED_MULTI, b, s, &e));
         }
+    if (g->flags & ZG_GPT_TRUNCATED_GENERATE)
+        for (int levels = 3; levels <= 6; levels += 3) ZG_TRY(capture_truncated(g, levels, 0, g->n_buckets - 1, s));
     return ZG_OK;
 }
 
 // Run one decode step at sequence length seq_len: replay the graph of its bucket, or launch eagerly when graphs
 // are disabled / the stream cannot be captured.
-int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, bool with_sampler = false) {
+int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, bool with_sampler = false, int trunc_levels = 0) {
     ZG_TRY(ensure_ln_folded(g, s));
     with_sampler = with_sampler && with_logits;
     if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) {
         StepOpts o;
         o.with_sampler = with_sampler;
+        o.trunc_levels = trunc_levels;
         return enqueue_step(g, with_logits, bucket_t_hi(g, seq_len), s, o);
     }
     if (g->graph_stream != s) ZG_TRY(capture_all(g, s));  // the caller switched streams after zg_gpt_create
     hipGraphExec_t e;
-    ZG_TRY(graph_exec(g, with_sampler ? G_SAMPLED : with_logits ? G_STEP_LOGITS : G_STEP, bucket_of(seq_len), s, &e));
+    ZG_TRY(graph_exec(g, with_sampler ? sampler_kind(trunc_levels, false) : with_logits ? G_STEP_LOGITS : G_STEP, bucket_of(seq_len), s, &e));
     ZG_HIP(hipGraphLaunch(e, s));
     return ZG_OK;
 }
@@ -1333,10 +1365,29 @@ int zg_gpt_argmax(zg_gpt* g, size_t* tokens_out, size_t n_tokens) {
     return ZG_OK;
 }
 
+static int fill_sample_params(zg_gpt* g, float temp, size_t top_k, float top_p, uint64_t seed);
+static int check_sample_options(const zg_sample_options* o, const char* who);
+static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, size_t top_k, float top_p, const float* uniforms,
+                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len);
+
 int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, const float* uniforms,
                   uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
     ZG_TRY(require_init());
-    ZG_REQUIRE(g && tokens && tokens_out && temp > 0.0f, ZG_ERR_ARG, "gpt_sample: bad argument");
+    ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "gpt_sample: bad argument");
+    return sample_impl(g, seq_len, tokens, n_tokens, temp, 0, 1.0f, uniforms, seed, tokens_out, probs_out, probs_len);
+}
+
+// zg_gpt_sample behind top-k / nucleus truncation (filters off: exactly zg_gpt_sample's launches)
+int zg_gpt_sample_ex(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const float* uniforms,
+                     uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, "gpt_sample_ex"));
+    return sample_impl(g, seq_len, tokens, n_tokens, opt->temp, opt->top_k, opt->top_p, uniforms, seed, tokens_out, probs_out, probs_len);
+}
+
+static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, size_t top_k, float top_p, const float* uniforms,
+                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
+    ZG_REQUIRE(g && tokens && tokens_out, ZG_ERR_ARG, "gpt_sample: bad argument");
     const size_t V = g->cfg.vocab_size, B = g->batch;
     ZG_REQUIRE(!probs_out || probs_len >= B * V, ZG_ERR_SHAPE, "gpt_sample: probs_out needs %zu elements", B * V);
     for (size_t b = 0; uniforms && b < B; ++b)  // (checked before anything is enqueued)
@@ -1358,8 +1409,14 @@ int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_toke
     }
     float* d_u = g->q;  // scratch: q is dead after the forward
     ZG_HIP(hipMemcpyAsync(d_u, h_u, B * sizeof(float), hipMemcpyHostToDevice, s));
-    ZG_TRY(launch_sample(g->logits, (int)B, (int)V, temp, d_u, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->cur_token, probs_out != nullptr,
-                         s));  // main.zig:200-206
+    const int levels = fill_sample_params(g, temp, top_k, top_p, seed);  // (h_samp: nothing in flight reads it, forward_enqueue's callers drain)
+    if (levels) {
+        ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
+        ZG_TRY(launch_sample_filtered(g->logits, (int)B, (int)V, g->samp, levels, d_u, nullptr, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->filt,
+                                      g->cur_token, probs_out != nullptr, s));
+    } else
+        ZG_TRY(launch_sample(g->logits, (int)B, (int)V, temp, d_u, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->cur_token, probs_out != nullptr,
+                             s));  // main.zig:200-206
     ZG_HIP(hipMemcpyAsync(g->h_ints + B, g->cur_token, B * sizeof(int), hipMemcpyDeviceToHost, s));
     if (probs_out) ZG_TRY(copy_out_f32(probs_out, g->logits, B * V, s));
     ZG_HIP(hipStreamSynchronize(s));
@@ -1377,13 +1434,32 @@ int zg_gpt_hidden(zg_gpt* g, float* x_out, size_t len) {
     return check_fault(g);
 }
 
+// The options of a sampler call into the pinned mirror of SampleParams (the caller uploads it); returns the selection launches
+// per step they need: 0 (no filter: the plain sampler), 3 (one filter) or 6 (both)
+static int fill_sample_params(zg_gpt* g, float temp, size_t top_k, float top_p, uint64_t seed) {
+    const bool k_on = top_k >= 1 && top_k < g->cfg.vocab_size, p_on = top_p < 1.0f;
+    g->h_samp->inv_temp = 1.0f / temp;
+    g->h_samp->top_k = k_on ? (unsigned)top_k : 0u;
+    g->h_samp->seed = seed;
+    g->h_samp->top_p = p_on ? top_p : 1.0f;
+    g->h_samp->pad = 0;
+    return k_on && p_on ? 6 : (k_on || p_on) ? 3 : 0;
+}
+
+static int check_sample_options(const zg_sample_options* o, const char* who) {
+    ZG_REQUIRE(o != nullptr, ZG_ERR_ARG, "%s: options is null", who);
+    ZG_REQUIRE(o->temp > 0.0f, ZG_ERR_ARG, "%s: temperature %f", who, o->temp);
+    ZG_REQUIRE(o->top_p > 0.0f && o->top_p <= 1.0f, ZG_ERR_ARG, "%s: top_p %f outside (0, 1]", who, o->top_p);  // (a NaN fails both)
+    return ZG_OK;
+}
+
 // A generation in three parts, so that several handles' generations can be fed to their streams side by side
 // (zg_gpt_generate_enqueue_many): gen_begin — prompts, cache clearing, the whole-prompt pass, the prefetcher's start;
 // gen_pump — ONE graph launch (graph_steps decode steps) or one single step, false when nothing is left; gen_end — the
 // prefetcher's stop word and the record of the last pick.  After a successful gen_begin, gen_end must run (also on failure:
 // the prefetcher must not wait for steps that never come).
 static int gen_begin(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps, bool sampled = false,
-                     float temp = 1.0f, uint64_t seed = 0) {
+                     float temp = 1.0f, uint64_t seed = 0, size_t top_k = 0, float top_p = 1.0f) {
     ZG_REQUIRE(g && prompts && prompt_lens, ZG_ERR_ARG, "generate: null argument");
     const size_t C = g->cfg.context_size, V = g->cfg.vocab_size, B = g->batch;
     ZG_REQUIRE(n_steps >= 1 && n_steps <= C, ZG_ERR_SHAPE, "generate: n_steps %zu outside 1..%zu", n_steps, C);
@@ -1408,10 +1484,9 @@ static int gen_begin(zg_gpt* g, const size_t* prompts, size_t prompt_stride, con
     if (g->pf_x != nullptr && min_prompt >= prefill_min())
         first = min_prompt < n_steps ? min_prompt : n_steps;
     g->gen_sampled = sampled;
+    g->gen_trunc = 0;
     if (sampled) {
-        g->h_samp->inv_temp = 1.0f / temp;
-        g->h_samp->pad = 0;
-        g->h_samp->seed = seed;
+        g->gen_trunc = fill_sample_params(g, temp, top_k, top_p, seed);
         ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     }
     ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
@@ -1424,6 +1499,10 @@ static int gen_begin(zg_gpt* g, const size_t* prompts, size_t prompt_stride, con
         ZG_TRY(enqueue_prefill(g, first, false, s));
     }
     if (!(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && g->graph_stream != s) ZG_TRY(capture_all(g, s));  // before the prefetcher starts its idle clock
+    // the truncated sampler's graphs of every bucket this generation touches, if create did not capture them: here, not in the
+    // loop (a capture between the steps would run against the prefetcher's idle clock)
+    if (g->gen_trunc && !(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && min_prompt < n_steps)
+        ZG_TRY(capture_truncated(g, g->gen_trunc, bucket_of(std::max(first, min_prompt) + 1), bucket_of(n_steps), s));
     ZG_TRY(note_steps(g, n_steps, s));
     ZG_TRY(pf_start(g, n_steps, s));
     g->gen_pos = first;
@@ -1450,11 +1529,11 @@ static int gen_pump(zg_gpt* g, bool* more) {
     if (K > 1 && st >= g->gen_min_prompt && st % K == 0 && st + K <= n_steps && st + K <= C) {
         if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
         hipGraphExec_t e;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64)
-        ZG_TRY(graph_exec(g, g->gen_sampled ? G_SAMPLED_MULTI : G_MULTI, bucket_of(st + 1), s, &e));
+        ZG_TRY(graph_exec(g, g->gen_sampled ? sampler_kind(g->gen_trunc, true) : G_MULTI, bucket_of(st + 1), s, &e));
         ZG_HIP(hipGraphLaunch(e, s));
         g->gen_pos = st + K;
     } else {
-        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_sampled));
+        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_sampled, g->gen_trunc));
         g->gen_pos = st + 1;
     }
     *more = g->gen_pos < n_steps;
@@ -1504,6 +1583,94 @@ int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_strid
     ZG_REQUIRE(g && out_tokens && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_sample: out_tokens too short");
     ZG_TRY(zg_gpt_generate_sample_enqueue(g, prompts, prompt_stride, prompt_lens, n_steps, temp, seed));
     return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
+}
+
+// The same behind top-k / nucleus truncation (include/zgpt2.h zg_sample_options; sample_filter.h): the selection launches sit in
+// front of the sampler node of graphs of their own (G_TRUNC*), the option values live in device memory.  Filters off: the calls above.
+int zg_gpt_generate_sample_ex_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                      const zg_sample_options* opt, uint64_t seed) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, "generate_sample_ex"));
+    ZG_TRY(gen_begin(g, prompts, prompt_stride, prompt_lens, n_steps, true, opt->temp, seed, opt->top_k, opt->top_p));
+    return gen_end(g, gen_pump_all(g));
+}
+
+int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                              const zg_sample_options* opt, uint64_t seed, size_t* out_tokens, size_t out_len) {
+    ZG_REQUIRE(g && out_tokens && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_sample_ex: out_tokens too short");
+    ZG_TRY(zg_gpt_generate_sample_ex_enqueue(g, prompts, prompt_stride, prompt_lens, n_steps, opt, seed));
+    return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
+}
+
+// The truncated sampler on the caller's logits (tests): the kernels of zg_gpt_sample_ex, a small kernel standing in for lm_head's
+// argmax partials.  Allocates its workspace per call.
+int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const float* uniforms, size_t* tokens_out,
+                         float* probs_out, float* thresholds_out) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, "debug_sample_rows"));
+    ZG_REQUIRE(logits && uniforms && tokens_out && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG,
+               "debug_sample_rows: bad argument");
+    const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
+    const bool k_on = opt->top_k >= 1 && opt->top_k < vocab, p_on = opt->top_p < 1.0f;
+    const int levels = k_on && p_on ? 6 : (k_on || p_on) ? 3 : 0;
+    const size_t fbytes = (filter_workspace_bytes(B) + 255) & ~(size_t)255, lbytes = (batch * vocab * 4 + 255) & ~(size_t)255;
+    const size_t sbytes = (sample_workspace_floats(B) * 4 + 255) & ~(size_t)255, pbytes = ((size_t)B * n_part * 4 + 255) & ~(size_t)255;
+    const size_t total = fbytes + lbytes + sbytes + pbytes + 256 * 3 + (((size_t)B * 8 + 255) & ~(size_t)255);
+    hipStream_t s = ctx().stream;
+    char* base = nullptr;
+    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), total));
+    struct Free {
+        char* p;
+        ~Free() { (void)hipFree(p); }
+    } guard{base};
+    char* p = base;
+    const FilterWs fws = filter_workspace(p, B);
+    p += fbytes;
+    float* d_logits = reinterpret_cast<float*>(p);
+    p += lbytes;
+    float* d_seg = reinterpret_cast<float*>(p);
+    p += sbytes;
+    float* d_part = reinterpret_cast<float*>(p);
+    p += pbytes;
+    SampleParams* d_par = reinterpret_cast<SampleParams*>(p);
+    p += 256;
+    float* d_u = reinterpret_cast<float*>(p);
+    p += 256;
+    int* d_tok = reinterpret_cast<int*>(p);
+    p += 256;
+    SampleParams hp{};
+    hp.inv_temp = 1.0f / opt->temp;
+    hp.top_k = k_on ? (unsigned)opt->top_k : 0u;
+    hp.top_p = p_on ? opt->top_p : 1.0f;
+    std::vector<int> h_tok(batch);
+    std::vector<float> h_u(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        float u;
+        ZG_HIP(hipMemcpy(&u, uniforms + b, 4, hipMemcpyDefault));
+        ZG_REQUIRE(u >= 0.0f && u < 1.0f, ZG_ERR_ARG, "debug_sample_rows: uniform %f outside [0,1)", u);
+        h_u[b] = u;
+    }
+    ZG_HIP(hipMemsetAsync(base, 0, fbytes, s));
+    ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemcpyAsync(d_u, h_u.data(), batch * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
+    ZG_TRY(launch_row_max_partials(d_logits, B, V, d_part, n_part, s));
+    if (levels)
+        ZG_TRY(launch_sample_filtered(d_logits, B, V, d_par, levels, d_u, nullptr, d_part, n_part, n_part, d_seg, fws, d_tok, probs_out != nullptr, s));
+    else  // filters off: the existing sampler
+        ZG_TRY(launch_sample(d_logits, B, V, opt->temp, d_u, d_part, n_part, n_part, d_seg, d_tok, probs_out != nullptr, s));
+    ZG_HIP(hipMemcpyAsync(h_tok.data(), d_tok, batch * 4, hipMemcpyDeviceToHost, s));
+    if (probs_out) ZG_HIP(hipMemcpyAsync(probs_out, d_logits, batch * vocab * 4, hipMemcpyDefault, s));
+    if (thresholds_out) {
+        if (levels) ZG_HIP(hipMemcpyAsync(thresholds_out, fws.tau, batch * 4, hipMemcpyDefault, s));
+        else {  // nothing dropped: -inf
+            std::vector<float> ninf(batch, -INFINITY);
+            ZG_HIP(hipMemcpy(thresholds_out, ninf.data(), batch * 4, hipMemcpyDefault));
+        }
+    }
+    ZG_HIP(hipStreamSynchronize(s));
+    for (size_t b = 0; b < batch; ++b) tokens_out[b] = (size_t)h_tok[b];
+    return ZG_OK;
 }
 
 // generate (src/main.zig:322-342) for the prompts of SEVERAL handles at once: independent sequences need not run in lock step

@@ -460,10 +460,14 @@ __global__ __launch_bounds__(256) void sample_seg_kernel(const float* __restrict
     if (blockIdx.x == 0 && tid == 0) so[kSegMax] = mx;
 }
 
+// FILT (top-k / top-p, sample_filter_* below): elements under the row's threshold tau[b] weigh nothing, and where rounding leaves
+// the point past every interval the pick falls on the last KEPT element (never on a dropped one)
+template <bool FILT>
 __global__ __launch_bounds__(64) void sample_pick_kernel(const float* __restrict__ logits, int vocab, const SampleParams* params, float inv_temp_arg,
                                                          const float* __restrict__ u_arr, const StepCtrl* ctrl, float* __restrict__ seg_io,
-                                                         int* __restrict__ token_out) {
+                                                         int* __restrict__ token_out, const float* __restrict__ tau_arr) {
     const int lane = threadIdx.x, b = blockIdx.x;
+    const float tau = FILT ? tau_arr[b] : 0.0f;
     const float inv_temp = params ? params->inv_temp : inv_temp_arg;
     const float* x = logits + (size_t)b * vocab;
     float* so = seg_io + (size_t)b * (kSegMax + 2);
@@ -490,7 +494,7 @@ __global__ __launch_bounds__(64) void sample_pick_kernel(const float* __restrict
     const float total = __shfl(incl, 63, 64);
     const float point = u * total;
     int pick = vocab - 1;
-    const unsigned long long hit = __builtin_amdgcn_ballot_w64(s0 < s1 && point < incl);
+    unsigned long long hit = __builtin_amdgcn_ballot_w64(s0 < s1 && point < incl);
     if (hit != 0ull) {
         const int owner = __builtin_ctzll(hit);
         int sg = 0;
@@ -510,15 +514,34 @@ __global__ __launch_bounds__(64) void sample_pick_kernel(const float* __restrict
         sg = __shfl(sg, owner, 64);
         before = __shfl(before, owner, 64);
         const int i = sg * 64 + lane;
-        float c = i < vocab ? __expf(x[i] * inv_temp - mx) : 0.0f;
+        const float xi = i < vocab ? x[i] : 0.0f;
+        const bool kept = i < vocab && (!FILT || xi >= tau);
+        float c = kept ? __expf(FILT ? (xi - mx) * inv_temp : xi * inv_temp - mx) : 0.0f;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
             const float up = __shfl_up(c, off, 64);
             if (lane >= off) c += up;
         }
-        const unsigned long long in = __builtin_amdgcn_ballot_w64(i < vocab && point < before + c);
+        const unsigned long long in = __builtin_amdgcn_ballot_w64(kept && point < before + c);
         // (rounding between the segment sum and its lane-by-lane scan can leave the point just past the last lane: that lane then)
         pick = sg * 64 + (in != 0ull ? __builtin_ctzll(in) : min(63, vocab - 1 - sg * 64));
+        if (FILT && in == 0ull) {
+            const unsigned long long kb = __builtin_amdgcn_ballot_w64(kept);
+            if (kb != 0ull) pick = sg * 64 + 63 - __builtin_clzll(kb);
+            else hit = 0ull;  // (the walk ended on a segment that keeps nothing: as below)
+        }
+    }
+    if (FILT && hit == 0ull) {  // the point at or past the total (u x total rounded up): the last kept element of the last segment that weighs anything
+        int ls = -1;
+        for (int k = s0; k < s1; ++k)
+            if (so[k] > 0.0f) ls = k;
+        const unsigned long long lb = __builtin_amdgcn_ballot_w64(ls >= 0);
+        if (lb != 0ull) {
+            const int sg = __shfl(ls, 63 - __builtin_clzll(lb), 64);
+            const int i = sg * 64 + lane;
+            const unsigned long long kb = __builtin_amdgcn_ballot_w64(i < vocab && x[i] >= tau);
+            if (kb != 0ull) pick = sg * 64 + 63 - __builtin_clzll(kb);
+        }
     }
     if (lane == 0) {
         token_out[b] = pick;
@@ -533,6 +556,8 @@ __global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vo
     const float mx = so[kSegMax], inv = 1.0f / so[kSegMax + 1];
     for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) x[i] = __expf(x[i] * inv_temp - mx) * inv;
 }
+
+#include "sample_filter.h"
 
 inline int grid_for(size_t n, int block = 256, int cap = 2048) {
     size_t g = (n + block - 1) / block;
@@ -718,7 +743,8 @@ static int sample_launches(float* logits, int batch, int vocab, const SamplePara
     const int nseg = (vocab + 63) / 64, nb = std::min(128, (nseg + 3) / 4);
     hipLaunchKernelGGL(sample_seg_kernel, dim3(nb, batch), dim3(256), 0, s, logits, vocab, params, inv_temp, part_val, n_part, part_stride, seg_ws);
     ZG_HIP(hipGetLastError());
-    hipLaunchKernelGGL(sample_pick_kernel, dim3(batch), dim3(64), 0, s, logits, vocab, params, inv_temp, u, ctrl, seg_ws, token_out);
+    hipLaunchKernelGGL(sample_pick_kernel<false>, dim3(batch), dim3(64), 0, s, logits, vocab, params, inv_temp, u, ctrl, seg_ws, token_out,
+                       (const float*)nullptr);
     ZG_HIP(hipGetLastError());
     if (write_probs) {
         hipLaunchKernelGGL(sample_probs_kernel, dim3(std::min(256, (vocab + 255) / 256), batch), dim3(256), 0, s, logits, vocab, inv_temp, seg_ws);
@@ -738,6 +764,51 @@ int launch_sample_step(float* logits, int batch, int vocab, const SampleParams* 
 }
 
 size_t sample_workspace_floats(int batch) { return (size_t)batch * (kSegMax + 2); }
+
+size_t filter_workspace_bytes(int batch) { return (size_t)batch * (3 * kFiltBins * 12 + 2 * sizeof(FilterState) + 8); }
+
+FilterWs filter_workspace(void* base, int batch) {
+    FilterWs w;
+    char* p = static_cast<char*>(base);
+    w.mass = reinterpret_cast<unsigned long long*>(p);
+    p += (size_t)batch * 3 * kFiltBins * 8;
+    w.cnt = reinterpret_cast<unsigned*>(p);
+    p += (size_t)batch * 3 * kFiltBins * 4;
+    w.st = p;
+    p += (size_t)batch * 2 * sizeof(FilterState);
+    w.tau = reinterpret_cast<float*>(p);
+    return w;
+}
+
+int launch_sample_filtered(float* logits, int batch, int vocab, const SampleParams* params, int n_levels, const float* u, const StepCtrl* ctrl,
+                           const float* part_val, int n_part, int part_stride, float* seg_ws, const FilterWs& fws, int* token_out, bool write_probs,
+                           hipStream_t s) {
+    ZG_REQUIRE(vocab >= 1 && vocab <= 64 * kSegMax, ZG_ERR_UNSUPPORTED, "sampler: vocabulary of %d beyond %d", vocab, 64 * kSegMax);
+    ZG_REQUIRE(params && part_val && n_part >= 1 && seg_ws && token_out && fws.mass && (n_levels == 3 || n_levels == 6) && (u || ctrl), ZG_ERR_ARG,
+               "truncated sampler: missing argument");
+    const int nlb = std::min(64, (vocab + 1023) / 1024);  // ~4 elements per thread: the level kernels pay per workgroup (bin scan, histogram flush)
+    for (int pos = 1; pos <= n_levels; ++pos) {
+        hipLaunchKernelGGL(filter_level_kernel, dim3(nlb, batch), dim3(256), 0, s, logits, vocab, params, part_val, n_part, part_stride, fws, pos, n_levels);
+        ZG_HIP(hipGetLastError());
+    }
+    const int nseg = (vocab + 63) / 64, nb = std::min(128, (nseg + 3) / 4);
+    hipLaunchKernelGGL(sample_seg_filt_kernel, dim3(nb, batch), dim3(256), 0, s, logits, vocab, params, part_val, n_part, part_stride, seg_ws, fws, n_levels);
+    ZG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sample_pick_kernel<true>, dim3(batch), dim3(64), 0, s, logits, vocab, params, 0.0f, u, ctrl, seg_ws, token_out, fws.tau);
+    ZG_HIP(hipGetLastError());
+    if (write_probs) {
+        hipLaunchKernelGGL(sample_probs_filt_kernel, dim3(std::min(256, (vocab + 255) / 256), batch), dim3(256), 0, s, logits, vocab, params, seg_ws, fws.tau);
+        ZG_HIP(hipGetLastError());
+    }
+    return ZG_OK;
+}
+
+int launch_row_max_partials(const float* logits, int batch, int vocab, float* part_val, int n_part, hipStream_t s) {
+    ZG_REQUIRE(logits && part_val && batch >= 1 && vocab >= 1 && n_part >= 1 && n_part <= 4096, ZG_ERR_ARG, "row_max_partials: bad argument");
+    hipLaunchKernelGGL(row_max_partials_kernel, dim3(n_part, batch), dim3(256), 0, s, logits, vocab, part_val);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
 
 int launch_embed_step(const EmbedArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(embed_step_kernel, dim3(1), dim3(a.batch > 4 ? 512 : 256), 0, s, a);  // one wave per sequence

@@ -306,11 +306,33 @@ int launch_embed_step(const EmbedArgs& a, hipStream_t s);
 // zg_gpt_sample uses when it is given no uniforms
 struct SampleParams {
     float inv_temp;
-    unsigned pad;
+    unsigned top_k;  // 0: off (the truncated sampler only; read on the device, so one captured graph serves every value)
     unsigned long long seed;
+    float top_p;     // 1: off
+    unsigned pad;
 };
 int launch_sample_step(float* logits, int batch, int vocab, const SampleParams* params, const StepCtrl* ctrl, const float* part_val, int n_part,
                        int part_stride, float* seg_ws, int* token_out, hipStream_t s);
+// The sampler behind top-k / top-p truncation (sample_filter.h: an exact radix select of the threshold, one launch per 11-bit
+// level, then the segment sums / pick / probabilities with weight 0 under the threshold).  n_levels: 3 = ONE filter is on (top-k
+// if params->top_k is, else the nucleus), 6 = both (top-k, then the nucleus over what it kept) — the launches are the same for
+// every option value, so a captured chain serves them all.  params lives in device memory; u (device, [batch]) or, when null, the
+// counter PRNG of (params->seed, ctrl->seq_len, b).  fws: filter_workspace_bytes(batch) bytes whose first
+// filter_workspace_zeroed_bytes(batch) were zero before the first chain (every chain leaves them so).  write_probs: the
+// renormalised probabilities (exact 0 where dropped) are left in the logits rows.
+struct FilterWs {
+    unsigned long long* mass;  // [batch][3][2048] fixed-point masses by histogram bin
+    unsigned* cnt;             // [batch][3][2048] counts
+    void* st;                  // [batch][2] descent state
+    float* tau;                // [batch] the threshold max(tau_k, tau_p)
+};
+size_t filter_workspace_bytes(int batch);
+FilterWs filter_workspace(void* base, int batch);
+int launch_sample_filtered(float* logits, int batch, int vocab, const SampleParams* params, int n_levels, const float* u, const StepCtrl* ctrl,
+                           const float* part_val, int n_part, int part_stride, float* seg_ws, const FilterWs& fws, int* token_out, bool write_probs,
+                           hipStream_t s);
+// part_val[batch][n_part] = maxima of n_part slices of every row (what lm_head's argmax epilogue leaves; zg_debug_sample_rows)
+int launch_row_max_partials(const float* logits, int batch, int vocab, float* part_val, int n_part, hipStream_t s);
 
 // ------------------------------------------------------------------------------------ multi-GPU (dist.hip)
 int dist_broadcast(void* buf, size_t bytes, int root, hipStream_t s);  // in place, over the communicator of zg_dist_init

@@ -18,11 +18,12 @@ from .synth import GPTConfig
 class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
-                 sampled_generate=False, weights_b24=False):
+                 sampled_generate=False, weights_b24=False, truncated_generate=False):
         """share_weights_with / own_stream / stream_priority: zg_gpt_options of zg_gpt_create_ex (a handle of an independent
         prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config).
         weights_b24: matrices stored as 24-bit floats (ZG_GPT_WEIGHTS_B24: each fp32 weight rounded to 16 mantissa bits, 3/4 of
-        fp32's bytes); excludes weights_f32."""
+        fp32's bytes); excludes weights_f32.  truncated_generate: the graphs of generate_sample(top_k=..., top_p=...) are captured
+        at create (ZG_GPT_TRUNCATED_GENERATE) instead of when the first such generation begins."""
         self.config, self.batch = config, batch
         L = _lib.load()
         flags = (_lib.GPT_WEIGHTS_F32 if weights_f32 else 0) | (0 if use_graph else _lib.GPT_NO_GRAPH)
@@ -33,6 +34,7 @@ class GPT:
         flags |= 0 if prefetch else _lib.GPT_NO_PREFETCH
         flags |= _lib.GPT_SAMPLED_GENERATE if sampled_generate else 0
         flags |= _lib.GPT_WEIGHTS_B24 if weights_b24 else 0
+        flags |= _lib.GPT_TRUNCATED_GENERATE if truncated_generate else 0
         cfg = _lib.GptConfig(config.vocab_size, config.context_size, config.n_layer, config.n_heads, config.n_embed)
         h = C.c_void_p()
         if share_weights_with is None and not own_stream:
@@ -115,14 +117,24 @@ class GPT:
                                      ptr(logits), ops._n(logits)))
         return logits
 
-    def sample(self, seq_len, tokens, temp, uniforms=None, seed=0, want_probs=False):
-        """GPT.sample (src/main.zig:198-207) with reproducible uniforms; returns tokens [batch] (and probs)."""
+    @staticmethod
+    def _truncated(top_k, top_p):
+        return top_k != 0 or top_p != 1.0
+
+    def sample(self, seq_len, tokens, temp, uniforms=None, seed=0, want_probs=False, top_k=0, top_p=1.0):
+        """GPT.sample (src/main.zig:198-207) with reproducible uniforms; returns tokens [batch] (and probs).  top_k / top_p:
+        truncation in front of the draw (zg_sample_options; the defaults are off and take zg_gpt_sample itself)."""
         tokens = np.ascontiguousarray(np.atleast_1d(tokens), dtype=np.uint64)
         u = None if uniforms is None else np.ascontiguousarray(np.atleast_1d(uniforms), dtype=np.float32)
         out = np.zeros(self.batch, np.uint64)
         probs = np.empty((self.batch, self.config.vocab_size), np.float32) if want_probs else None
-        check(self._L.zg_gpt_sample(self.h, seq_len, ptr(tokens), tokens.size, temp, ptr(u), seed, ptr(out), ptr(probs),
-                                    ops._n(probs)))
+        if self._truncated(top_k, top_p):
+            opt = _lib.SampleOptions(temp, top_k, top_p)
+            check(self._L.zg_gpt_sample_ex(self.h, seq_len, ptr(tokens), tokens.size, C.addressof(opt), ptr(u), seed, ptr(out), ptr(probs),
+                                           ops._n(probs)))
+        else:
+            check(self._L.zg_gpt_sample(self.h, seq_len, ptr(tokens), tokens.size, temp, ptr(u), seed, ptr(out), ptr(probs),
+                                        ops._n(probs)))
         return (out, probs) if want_probs else out
 
     def argmax(self):
@@ -163,17 +175,25 @@ class GPT:
         check(self._L.zg_gpt_generate_fetch(self.h, n_steps, ptr(out), out.size))
         return out
 
-    def generate_sample(self, prompts, n_steps, temp, seed=0):
+    def generate_sample(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0):
         """generate (src/main.zig:322-342) as the reference runs it — every token behind the prompt drawn by GPT.sample — with the
-        loop on the device; the tokens of the host loop over `sample(T, tok, temp, seed=seed)`."""
+        loop on the device; the tokens of the host loop over `sample(T, tok, temp, seed=seed)`.  top_k / top_p: as `sample`."""
         mat, lens, stride = self._prompts(prompts)
         out = np.zeros((self.batch, n_steps), np.uint64)
-        check(self._L.zg_gpt_generate_sample(self.h, ptr(mat), stride, ptr(lens), n_steps, temp, seed, ptr(out), out.size))
+        if self._truncated(top_k, top_p):
+            opt = _lib.SampleOptions(temp, top_k, top_p)
+            check(self._L.zg_gpt_generate_sample_ex(self.h, ptr(mat), stride, ptr(lens), n_steps, C.addressof(opt), seed, ptr(out), out.size))
+        else:
+            check(self._L.zg_gpt_generate_sample(self.h, ptr(mat), stride, ptr(lens), n_steps, temp, seed, ptr(out), out.size))
         return out
 
-    def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0):
+    def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0):
         mat, lens, stride = self._prompts(prompts)
-        check(self._L.zg_gpt_generate_sample_enqueue(self.h, ptr(mat), stride, ptr(lens), n_steps, temp, seed))
+        if self._truncated(top_k, top_p):
+            opt = _lib.SampleOptions(temp, top_k, top_p)
+            check(self._L.zg_gpt_generate_sample_ex_enqueue(self.h, ptr(mat), stride, ptr(lens), n_steps, C.addressof(opt), seed))
+        else:
+            check(self._L.zg_gpt_generate_sample_enqueue(self.h, ptr(mat), stride, ptr(lens), n_steps, temp, seed))
 
     PROFILE_CLASSES = ["embed", "ln1_c_attn_kv", "attention", "merge_attn_proj_resid", "ln2_c_fc_gelu",
                        "mlp_proj_resid", "lnf_lm_head_argmax", "step_total"]
