@@ -169,6 +169,13 @@ int zg_debug_prefill_linear(const uint16_t* A_planes, const uint16_t* W, const f
  * Device pointers. */
 int zg_debug_attn_prefill(const float* qkv, uint16_t* out, size_t batch, size_t n_tokens, size_t n_embed, size_t n_heads,
                           const float* k_cache, const float* v_cache, size_t ctx, float* ws, size_t ws_floats, int key_tiles);
+/* ... of a continuation (zg_gpt_extend): qkv holds only the n_tokens new rows of every sequence, positions past_len .. past_len +
+ * n_tokens - 1, and only their q columns are read.  EVERY key, cached and new, comes from the head-major caches
+ * [batch][heads][ctx][64], which hold positions 0 .. past_len + n_tokens - 1 in storage format kv_mode: 0 fp32, 1 fp16, 2 B24 (a
+ * bf16-shaped plane of batch heads ctx 64 elements, then a byte plane, as ZG_GPT_KV_B24 keeps it).  Rows behind the last
+ * position may hold anything.  past_len + n_tokens <= ctx; the rest as zg_debug_attn_prefill. */
+int zg_debug_attn_prefill_at(const float* qkv, uint16_t* out, size_t batch, size_t past_len, size_t n_tokens, size_t n_embed, size_t n_heads,
+                             const void* k_cache, const void* v_cache, int kv_mode, size_t ctx, float* ws, size_t ws_floats, int key_tiles);
 /* Test hook: pin the route of every whole-prompt Linear of this process until called again with (0, 0) — force_kernel / slices
  * as in zg_debug_prefill_linear; force_kernel >= 16: the library's rule with that many 256 x 192 tiles (x K slices) as the
  * threshold from which the persistent GEMM takes a Linear (default 192; tools/experiments/pf_route_ab.py).
@@ -295,6 +302,18 @@ int zg_gpt_forward(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tok
  * products: fp32-sgemm grade).  Not available on handles created with ZG_GPT_NO_PREFILL. */
 int zg_gpt_prefill(zg_gpt* g, const size_t* tokens, size_t token_stride, size_t n_tokens,
                    int compute_logits, float* logits_out, size_t logits_len);
+/* ---- Continuing a sequence from its KV cache.  The handle records how many positions its caches hold (all `batch`
+ * sequences in lock step): zg_gpt_forward sets the count to seq_len, zg_gpt_prefill / zg_gpt_extend to the end of their pass, the
+ * generate calls to the last position they fed.  A continuation names the position it starts at: past_len beyond the recorded count
+ * is ZG_ERR_ARG; past_len below it is a rollback — the positions from past_len on are discarded (the cache rows behind the
+ * continuation are cleared, the rows below past_len are untouched).  None of these calls allocates. */
+int zg_gpt_cached_len(zg_gpt* g, size_t* len_out);
+/* zg_gpt_prefill at an offset: tokens [batch][token_stride], n_tokens >= 1 of each row go to positions past_len .. past_len +
+ * n_tokens - 1 in ONE pass; the caches end up as n_tokens calls of zg_gpt_forward(past_len + i + 1, ...) would leave them.
+ * compute_logits: the logits of the last new position (zg_gpt_argmax / logits_out as zg_gpt_prefill).  past_len == 0 is exactly
+ * zg_gpt_prefill.  past_len + n_tokens <= context_size.  Not available on handles created with ZG_GPT_NO_PREFILL. */
+int zg_gpt_extend(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits, float* logits_out,
+                  size_t logits_len);
 /* argmax of the logits of the last zg_gpt_forward(compute_logits=1) per sequence (lowest index
  * wins ties; logits that are all NaN give index 0) — the greedy replacement for GPT.sample (src/main.zig:198-207). */
 int zg_gpt_argmax(zg_gpt* g, size_t* tokens_out, size_t n_tokens);
@@ -360,6 +379,14 @@ int zg_gpt_generate_sample_ex_enqueue(zg_gpt* g, const size_t* prompts, size_t p
                                       const zg_sample_options* options, uint64_t seed);
 int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
                               const zg_sample_options* options, uint64_t seed, size_t* out_tokens, size_t out_len);
+/* generate (src/main.zig:322-342) entered at s = past_len with `prompts` = the new tokens of each row: positions past_len ..
+ * past_len + n_steps - 1; prompt_lens[b] >= 1 new tokens are fed first (the last of them twice, as main.zig:334,337 does in the first
+ * turn too), the rest is picked.  options NULL: greedy; otherwise the sampler of zg_gpt_generate_sample_ex (uniform of (seed,
+ * absolute T, b)).  past_len + n_steps <= context_size.  Works on ZG_GPT_NO_PREFILL handles (through the decode loop). */
+int zg_gpt_generate_from_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens,
+                                 size_t n_steps, const zg_sample_options* options_or_null, uint64_t seed);
+/* tokens of positions first .. first + n - 1 of the last generation(s): out_tokens [batch, n] */
+int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len);
 /* Test entry: the sampler kernels of zg_gpt_sample_ex on the caller's logits [batch <= 64, vocab <= 262144] (host or device, as
  * uniforms [batch] and the outputs), a small kernel standing in for lm_head's row-maximum partials.  Needs zg_init only.
  * probs_out [batch, vocab] and thresholds_out [batch] (max(tau_k, tau_p) of each row; a zero threshold is +0.0; -inf with both

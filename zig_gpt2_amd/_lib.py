@@ -59,6 +59,7 @@ SIGNATURES = {
     "zg_debug_gemm_stamps": (C.c_int, [vp, sz]),
     "zg_debug_last_kernel": (C.c_int, [C.c_char_p, sz]),
     "zg_debug_attn_prefill": (C.c_int, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, sz, C.c_int]),
+    "zg_debug_attn_prefill_at": (C.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, vp, C.c_int, sz, vp, sz, C.c_int]),
     "zg_debug_prefill_route": (C.c_int, [C.c_int, C.c_int]),
     "zg_debug_prefill_linear": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, C.c_int, C.c_int, C.c_int, vp, sz]),
     "zg_linear_forward": (C.c_int, [sz, sz, vp, vp, vp, sz, vp, sz]),
@@ -91,6 +92,10 @@ SIGNATURES = {
     "zg_gpt_step_bytes": (C.c_int, [vp, sz, szp, szp]),
     "zg_gpt_forward": (C.c_int, [vp, sz, vp, sz, C.c_int, vp, sz]),
     "zg_gpt_prefill": (C.c_int, [vp, vp, sz, sz, C.c_int, vp, sz]),
+    "zg_gpt_cached_len": (C.c_int, [vp, szp]),
+    "zg_gpt_extend": (C.c_int, [vp, sz, vp, sz, sz, C.c_int, vp, sz]),
+    "zg_gpt_generate_from_enqueue": (C.c_int, [vp, sz, vp, sz, vp, sz, vp, C.c_uint64]),
+    "zg_gpt_generate_fetch_range": (C.c_int, [vp, sz, sz, vp, sz]),
     "zg_gpt_argmax": (C.c_int, [vp, vp, sz]),
     "zg_gpt_sample": (C.c_int, [vp, sz, vp, sz, C.c_float, vp, C.c_uint64, vp, vp, sz]),
     "zg_gpt_hidden": (C.c_int, [vp, vp, sz]),

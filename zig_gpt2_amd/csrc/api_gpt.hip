@@ -127,6 +127,9 @@ struct zg_gpt {
     // a generation in flight between gen_begin and gen_end (zg_gpt_generate_enqueue / _many)
     size_t gen_pos, gen_n, gen_min_prompt, gen_since_sync;
     bool gen_open;
+    // the session: positions the caches hold, and the row behind the last one written since the rows behind a pass
+    // were last cleared — a continuation clears [its end, context) only when something may be there
+    size_t cached_len, kv_dirty_hi;
 };
 
 static inline hipStream_t gs(const zg_gpt* g) { return g->stream ? g->stream : ctx().stream; }
@@ -641,18 +644,22 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
 // (Measured and dropped in round 4: replaying this pass from a hipGraph per prompt length.  0.844 against 0.749 ms at 64
 // tokens, 1.645 against 1.553 ms at 1023 — the ~10 us a launch costs here is the kernels' own latency at these sizes, not host
 // overhead, and a graph launch adds its own ~10 us; profiles/round4_prefill_graph.jsonl.)
-int enqueue_prefill(zg_gpt* g, size_t P, bool last_block_full, hipStream_t s) {
+// pos0 > 0 (a continuation, zg_gpt_extend): the P rows are positions pos0 .. pos0 + P - 1 (tokens g->prompt[b][pos0 + t]); they are
+// appended behind the pos0 cached rows, and the attention reads every key, old and new, from the caches in their storage format
+// (attn_prefill.hip, the *_at kernels).  pos0 == 0 launches what it always launched.
+int enqueue_prefill(zg_gpt* g, size_t P, bool last_block_full, hipStream_t s, size_t pos0 = 0) {
     const bool f32w = g->wt != WT_BF16;
     const int np = f32w ? kWeightPlanes : (g->flags & ZG_GPT_PREFILL_2PLANE) ? 2 : kSplit;
     const size_t E = g->cfg.n_embed, L = g->cfg.n_layer, H = g->cfg.n_heads, C = g->cfg.context_size;
     const int B = (int)g->batch, M = (int)(g->batch * P), iE = (int)E;
-    ZG_TRY(launch_embed_prefill(g->prompt, (int)C, B, (int)P, g->wte, g->wpe, g->wt, iE, g->pf_x, s));
+    ZG_TRY(launch_embed_prefill(g->prompt, (int)C, B, (int)P, g->wte, g->wpe, g->wt, iE, g->pf_x, s, (int)pos0));
     ZG_TRY(launch_ln_split(g->pf_x, M, iE, g->layers[0].ln_1_g, g->layers[0].ln_1_b, 1e-5f, g->pf_a, s));
     for (size_t l = 0; l < L; ++l) {
         const zg_layer& y = g->layers[l];
         // pf_a holds split(ln_1(x)) here: from the line above or from the tail of the previous Block's last GEMM
         // c_attn with the cache append of ops.zig:152-157 in its epilogue
         PrefillQkv qa{(int)P, iE, (int)H, (int)C, g->kv_mode, y.k_cache, y.v_cache, g->batch * C * E * 2};
+        qa.pos0 = (int)pos0;
         if (!f32w && g->sk_flags != nullptr) {  // (the persistent GEMM may hand half tiles over between workgroups: gemm_s4.hip SK)
             qa.sk_ws = g->pf_ws;
             qa.sk_ws_bytes = g->pf_ws_floats * 4;
@@ -665,6 +672,10 @@ int enqueue_prefill(zg_gpt* g, size_t P, bool last_block_full, hipStream_t s) {
                                    g->pf_ws, g->pf_ws_floats, nullptr, s, &qa, np));
         if (l + 1 == L && !last_block_full) break;
         // (an fp32 cache is read directly: the c_attn epilogue then need not store the k / v columns of qkv)
+        if (pos0 > 0)
+            ZG_TRY(launch_attn_prefill_at(g->pf_qkv, g->pf_a, B, (int)pos0, (int)P, iE, (int)H, g->pf_ws, g->pf_ws_floats, y.k_cache, y.v_cache, g->kv_mode,
+                                          g->batch * C * E * 2, (int)C, s));
+        else
         ZG_TRY(launch_attn_prefill(g->pf_qkv, g->pf_a, B, (int)P, iE, (int)H, g->pf_ws, g->pf_ws_floats, g->kv_mode == 0 ? (const float*)y.k_cache : nullptr,
                                        g->kv_mode == 0 ? (const float*)y.v_cache : nullptr, (int)C, s));
         const PrefillLn ln2{y.ln_2_g, y.ln_2_b, 1e-5f, g->pf_a};
@@ -1261,10 +1272,12 @@ int zg_gpt_broadcast_weights(zg_gpt* g, int root, float* ms_out) {
 // (tools/fuzz_errors_gpt.py).  124M, one sequence: 75 MB, ~20 us per generation of 217 ms.
 // from_row > 0 (a whole-prompt pass writes rows 0 .. from_row - 1 itself): only the rows behind it, strip by strip — eight
 // 1023-token prompts would otherwise pay a 600 MB memset (0.12 ms of a 5.4 ms pass) for one stale row per head.
-static int clear_kv(zg_gpt* g, hipStream_t s, size_t from_row = 0) {
+// keep_head (a continuation: rows below from_row are the session): never the memset of the whole region.
+static int clear_kv(zg_gpt* g, hipStream_t s, size_t from_row = 0, bool keep_head = false) {
     if (g->kv_region_bytes == 0 || g->arena == nullptr) return ZG_OK;
     const size_t C = g->cfg.context_size, E = g->cfg.n_embed, B = g->batch, L = g->cfg.n_layer;
-    if (from_row == 0 || from_row * 2 < C) {
+    if (keep_head && from_row >= C) return ZG_OK;
+    if (!keep_head && (from_row == 0 || from_row * 2 < C)) {
         ZG_HIP(hipMemsetAsync(g->layers[0].k_cache, 0, g->kv_region_bytes, s));
         return ZG_OK;
     }
@@ -1276,6 +1289,15 @@ static int clear_kv(zg_gpt* g, hipStream_t s, size_t from_row = 0) {
     const int strips = (int)(B * g->cfg.n_heads);
     ZG_TRY(launch_kv_clear_tail(g->layers[0].k_cache, (int)(2 * L), stride, 0, g->kv_mode == 0 ? 256 : 128, strips, (int)C, (int)from_row, s));
     if (g->kv_mode == 2) ZG_TRY(launch_kv_clear_tail(g->layers[0].k_cache, (int)(2 * L), stride, elems * 2, 64, strips, (int)C, (int)from_row, s));
+    return ZG_OK;
+}
+
+// A continuation at past_len whose pass ends at row `end`: the rows behind it are cleared if anything was written there since
+// they were last clean (a rollback, or zg_gpt_forward calls out of order) — the decode attention reads its whole 64-position
+// bucket, and what a discarded row holds (a NaN, say) must not come back.  Rows below past_len are never touched.
+static int clear_behind(zg_gpt* g, hipStream_t s, size_t end) {
+    if (g->kv_dirty_hi > end) ZG_TRY(clear_kv(g, s, end, true));
+    g->kv_dirty_hi = end;
     return ZG_OK;
 }
 
@@ -1305,7 +1327,12 @@ static int forward_enqueue(zg_gpt* g, size_t seq_len, const size_t* tokens, size
     }
     ZG_HIP(hipMemcpyAsync(g->forced, g->h_ints, g->batch * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_TRY(stage_ctrl(g, seq_len - 1, seq_len, 1, s));
-    if (seq_len == 1) ZG_TRY(clear_kv(g, s));
+    if (seq_len == 1) {
+        ZG_TRY(clear_kv(g, s));
+        g->kv_dirty_hi = 0;
+    }
+    g->cached_len = seq_len;
+    if (seq_len > g->kv_dirty_hi) g->kv_dirty_hi = seq_len;
     ZG_TRY(note_steps(g, 1, s));
     ZG_TRY(ensure_ln_folded(g, s));
     ZG_TRY(run_step(g, compute_logits != 0, seq_len, s));
@@ -1341,12 +1368,56 @@ int zg_gpt_prefill(zg_gpt* g, const size_t* tokens, size_t token_stride, size_t 
         }
     ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_TRY(clear_kv(g, s, n_tokens));
+    g->cached_len = g->kv_dirty_hi = n_tokens;
     ZG_TRY(ensure_ln_folded(g, s));
     ZG_TRY(enqueue_prefill(g, n_tokens, compute_logits != 0, s));
     if (compute_logits) {  // ln_f + lm_head of each sequence's last position through the decode kernels
         ZG_HIP(hipMemcpy2DAsync(g->x, E * 4, g->pf_x + (n_tokens - 1) * E, n_tokens * E * 4, E * 4, B,
                                 hipMemcpyDeviceToDevice, s));
         ZG_TRY(stage_ctrl(g, n_tokens - 1, n_tokens, 1, s));
+        ZG_TRY(enqueue_lm_head(g, s));
+        if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, B * V, s));
+    }
+    ZG_HIP(hipStreamSynchronize(s));
+    return check_fault(g);
+}
+
+int zg_gpt_cached_len(zg_gpt* g, size_t* len_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && len_out, ZG_ERR_ARG, "gpt_cached_len: null argument");
+    *len_out = g->cached_len;
+    return ZG_OK;
+}
+
+// zg_gpt_prefill behind past_len cached positions: one whole-prompt pass over the n_tokens new rows
+int zg_gpt_extend(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits, float* logits_out,
+                  size_t logits_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && tokens, ZG_ERR_ARG, "gpt_extend: null argument");
+    ZG_REQUIRE(g->pf_x != nullptr, ZG_ERR_UNSUPPORTED, "gpt_extend: the handle was created with ZG_GPT_NO_PREFILL");
+    const size_t C = g->cfg.context_size, V = g->cfg.vocab_size, B = g->batch, E = g->cfg.n_embed;
+    ZG_REQUIRE(past_len <= g->cached_len, ZG_ERR_ARG, "gpt_extend: past_len %zu beyond the %zu cached positions", past_len, g->cached_len);
+    ZG_REQUIRE(n_tokens >= 1 && past_len + n_tokens <= C && n_tokens <= token_stride, ZG_ERR_SHAPE,
+               "gpt_extend: %zu tokens behind %zu positions (context %zu, stride %zu)", n_tokens, past_len, C, token_stride);
+    ZG_REQUIRE(!logits_out || (compute_logits && logits_len >= B * V), ZG_ERR_SHAPE, "gpt_extend: logits_out needs compute_logits and %zu elements",
+               B * V);
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < n_tokens; ++i)
+            ZG_REQUIRE(tokens[b * token_stride + i] < V, ZG_ERR_SHAPE, "gpt_extend: token %zu >= vocab %zu", tokens[b * token_stride + i], V);
+    if (past_len == 0) return zg_gpt_prefill(g, tokens, token_stride, n_tokens, compute_logits, logits_out, logits_len);
+    hipStream_t s = gs(g);
+    ZG_HIP(hipStreamSynchronize(s));
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < n_tokens; ++i) g->h_ints[b * C + past_len + i] = (int)tokens[b * token_stride + i];
+    ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
+    const size_t end = past_len + n_tokens;
+    ZG_TRY(clear_behind(g, s, end));
+    g->cached_len = end;
+    ZG_TRY(ensure_ln_folded(g, s));
+    ZG_TRY(enqueue_prefill(g, n_tokens, compute_logits != 0, s, past_len));
+    if (compute_logits) {  // ln_f + lm_head of each sequence's last new position through the decode kernels
+        ZG_HIP(hipMemcpy2DAsync(g->x, E * 4, g->pf_x + (n_tokens - 1) * E, n_tokens * E * 4, E * 4, B, hipMemcpyDeviceToDevice, s));
+        ZG_TRY(stage_ctrl(g, end - 1, end, 1, s));
         ZG_TRY(enqueue_lm_head(g, s));
         if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, B * V, s));
     }
@@ -1458,24 +1529,30 @@ static int check_sample_options(const zg_sample_options* o, const char* who) {
 // gen_pump — ONE graph launch (graph_steps decode steps) or one single step, false when nothing is left; gen_end — the
 // prefetcher's stop word and the record of the last pick.  After a successful gen_begin, gen_end must run (also on failure:
 // the prefetcher must not wait for steps that never come).
+// past > 0 (zg_gpt_generate_from_enqueue): the loop is entered at s = past — `prompts` are the new tokens of each row, device
+// prompt[b][past + i], prompt_len[b] = past + prompt_lens[b]; everything the embed kernel and gen_pump compare is absolute, so the
+// steps are the ones an uninterrupted generation would run at these positions.  The caches keep rows 0 .. past - 1 and the
+// recorded tokens of positions below past stay where they are (zg_gpt_generate_fetch_range).
 static int gen_begin(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps, bool sampled = false,
-                     float temp = 1.0f, uint64_t seed = 0, size_t top_k = 0, float top_p = 1.0f) {
+                     float temp = 1.0f, uint64_t seed = 0, size_t top_k = 0, float top_p = 1.0f, size_t past = 0) {
     ZG_REQUIRE(g && prompts && prompt_lens, ZG_ERR_ARG, "generate: null argument");
     const size_t C = g->cfg.context_size, V = g->cfg.vocab_size, B = g->batch;
-    ZG_REQUIRE(n_steps >= 1 && n_steps <= C, ZG_ERR_SHAPE, "generate: n_steps %zu outside 1..%zu", n_steps, C);
+    ZG_REQUIRE(past <= g->cached_len, ZG_ERR_ARG, "generate: past_len %zu beyond the %zu cached positions", past, g->cached_len);
+    ZG_REQUIRE(n_steps >= 1 && past + n_steps <= C, ZG_ERR_SHAPE, "generate: n_steps %zu outside 1..%zu", n_steps, C - past);
+    for (size_t b = 0; b < B; ++b) {  // (everything is checked before the handle's state is touched)
+        const size_t np = prompt_lens[b];
+        ZG_REQUIRE(np >= 1 && past + np <= C && np <= prompt_stride, ZG_ERR_SHAPE, "generate: prompt %zu has length %zu", b, np);
+        for (size_t i = 0; i < np; ++i)
+            ZG_REQUIRE(prompts[b * prompt_stride + i] < V, ZG_ERR_SHAPE, "generate: token %zu >= vocab %zu", prompts[b * prompt_stride + i], V);
+    }
     hipStream_t s = gs(g);
     ZG_HIP(hipStreamSynchronize(s));  // pinned staging below is shared with earlier calls
     size_t min_prompt = C;
     memset(g->h_ints, 0, (B * C + B) * sizeof(int));
     for (size_t b = 0; b < B; ++b) {
         const size_t np = prompt_lens[b];
-        ZG_REQUIRE(np >= 1 && np <= C && np <= prompt_stride, ZG_ERR_SHAPE, "generate: prompt %zu has length %zu", b, np);
-        for (size_t i = 0; i < np; ++i) {
-            const size_t t = prompts[b * prompt_stride + i];
-            ZG_REQUIRE(t < V, ZG_ERR_SHAPE, "generate: token %zu >= vocab %zu", t, V);
-            g->h_ints[b * C + i] = (int)t;
-        }
-        g->h_ints[B * C + b] = (int)np;
+        for (size_t i = 0; i < np; ++i) g->h_ints[b * C + past + i] = (int)prompts[b * prompt_stride + i];
+        g->h_ints[B * C + b] = (int)(past + np);
         if (np < min_prompt) min_prompt = np;
     }
     // The positions every sequence has a prompt token for go through the Blocks together (prefill); the
@@ -1491,23 +1568,28 @@ static int gen_begin(zg_gpt* g, const size_t* prompts, size_t prompt_stride, con
     }
     ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(g->prompt_len, g->h_ints + B * C, B * sizeof(int), hipMemcpyHostToDevice, s));
-    ZG_TRY(stage_ctrl(g, first, first, sampled ? 2 : 0, s));
-    ZG_TRY(clear_kv(g, s, first));
+    ZG_TRY(stage_ctrl(g, past + first, past + first, sampled ? 2 : 0, s));
+    if (past == 0) ZG_TRY(clear_kv(g, s, first));
+    else ZG_TRY(clear_behind(g, s, past + first));
+    g->cached_len = g->kv_dirty_hi = past + n_steps;  // the last position the loop feeds
     ZG_TRY(ensure_ln_folded(g, s));
-    if (first > 0) {
+    if (first > 0 && past == 0) {
         ZG_HIP(hipMemcpyAsync(g->out_tokens, g->prompt, B * C * sizeof(int), hipMemcpyDeviceToDevice, s));
         ZG_TRY(enqueue_prefill(g, first, false, s));
+    } else if (first > 0) {  // only the new columns: the tokens recorded below past stay
+        ZG_HIP(hipMemcpy2DAsync(g->out_tokens + past, C * sizeof(int), g->prompt + past, C * sizeof(int), first * sizeof(int), B, hipMemcpyDeviceToDevice, s));
+        ZG_TRY(enqueue_prefill(g, first, false, s, past));
     }
     if (!(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && g->graph_stream != s) ZG_TRY(capture_all(g, s));  // before the prefetcher starts its idle clock
     // the truncated sampler's graphs of every bucket this generation touches, if create did not capture them: here, not in the
     // loop (a capture between the steps would run against the prefetcher's idle clock)
     if (g->gen_trunc && !(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && min_prompt < n_steps)
-        ZG_TRY(capture_truncated(g, g->gen_trunc, bucket_of(std::max(first, min_prompt) + 1), bucket_of(n_steps), s));
+        ZG_TRY(capture_truncated(g, g->gen_trunc, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
     ZG_TRY(note_steps(g, n_steps, s));
-    ZG_TRY(pf_start(g, n_steps, s));
-    g->gen_pos = first;
-    g->gen_n = n_steps;
-    g->gen_min_prompt = min_prompt;
+    ZG_TRY(pf_start(g, past + n_steps, s));
+    g->gen_pos = past + first;  // absolute, as gen_n and gen_min_prompt: gen_pump's steps, buckets and graph alignment follow the position
+    g->gen_n = past + n_steps;
+    g->gen_min_prompt = past + min_prompt;
     g->gen_since_sync = 0;
     g->gen_open = true;
     return ZG_OK;
@@ -1600,6 +1682,32 @@ int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_st
     ZG_REQUIRE(g && out_tokens && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_sample_ex: out_tokens too short");
     ZG_TRY(zg_gpt_generate_sample_ex_enqueue(g, prompts, prompt_stride, prompt_lens, n_steps, opt, seed));
     return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
+}
+
+// generate entered at s = past_len: the decode loop's own graphs at the absolute positions, the shortest new length
+// through the whole-prompt pass first where the handle has one.  options null: greedy.
+int zg_gpt_generate_from_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                 const zg_sample_options* opt, uint64_t seed) {
+    ZG_TRY(require_init());
+    if (opt) ZG_TRY(check_sample_options(opt, "generate_from"));
+    ZG_TRY(gen_begin(g, prompts, prompt_stride, prompt_lens, n_steps, opt != nullptr, opt ? opt->temp : 1.0f, seed, opt ? opt->top_k : 0,
+                     opt ? opt->top_p : 1.0f, past_len));
+    return gen_end(g, gen_pump_all(g));
+}
+
+int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && out_tokens, ZG_ERR_ARG, "generate_fetch_range: null argument");
+    const size_t C = g->cfg.context_size, B = g->batch;
+    ZG_REQUIRE(first <= C && n <= C - first && out_len >= B * n, ZG_ERR_SHAPE, "generate_fetch_range: positions %zu .. %zu of %zu, %zu elements", first,
+               first + n, C, out_len);
+    hipStream_t s = gs(g);
+    ZG_HIP(hipMemcpyAsync(g->h_ints, g->out_tokens, B * C * sizeof(int), hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < n; ++i) out_tokens[b * n + i] = (size_t)g->h_ints[b * C + first + i];
+    return ZG_OK;
 }
 
 // The truncated sampler on the caller's logits (tests): the kernels of zg_gpt_sample_ex, a small kernel standing in for lm_head's

@@ -614,6 +614,19 @@ int zg_debug_attn_prefill(const float* qkv, uint16_t* out, size_t batch, size_t 
                                key_tiles);
 }
 
+int zg_debug_attn_prefill_at(const float* qkv, uint16_t* out, size_t batch, size_t past_len, size_t n_tokens, size_t n_embed, size_t n_heads,
+                             const void* k_cache, const void* v_cache, int kv_mode, size_t ctx_len, float* ws, size_t ws_floats, int key_tiles) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(qkv && out && k_cache && v_cache && is_device_ptr(qkv) && is_device_ptr(out) && is_device_ptr(k_cache) && is_device_ptr(v_cache) &&
+                   (!ws || is_device_ptr(ws)),
+               ZG_ERR_ARG, "debug_attn_prefill_at: device pointers");
+    ZG_REQUIRE(batch >= 1 && n_tokens >= 1 && n_heads >= 1 && n_embed == 64 * n_heads && batch * n_tokens < (1u << 24) && n_embed < (1u << 16) &&
+                   ctx_len < (1u << 22) && past_len + n_tokens <= ctx_len && kv_mode >= 0 && kv_mode <= 2 && key_tiles >= 0 && key_tiles <= 255,
+               ZG_ERR_ARG, "debug_attn_prefill_at: arguments");
+    return launch_attn_prefill_at(qkv, out, (int)batch, (int)past_len, (int)n_tokens, (int)n_embed, (int)n_heads, ws, ws_floats, k_cache, v_cache, kv_mode,
+                                  batch * ctx_len * n_embed * 2, (int)ctx_len, ctx().stream, key_tiles);
+}
+
 int zg_debug_prefill_route(int force_kernel, int slices) {
     ZG_REQUIRE(force_kernel >= 0 && (force_kernel <= 2 || force_kernel >= 16) && slices >= 0, ZG_ERR_ARG, "debug_prefill_route: arguments");
     prefill_force_route(force_kernel, slices);

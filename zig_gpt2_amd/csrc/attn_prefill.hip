@@ -63,6 +63,27 @@ __device__ __forceinline__ void store_split4(bf16_t* dst, size_t plane, f32x4 v)
 // key tiles a group of four query blocks needs, and the key ranges (splits) it is cut into
 __host__ __device__ inline int group_tiles(int g, int nqb) { return 4 * g + 4 < nqb ? 4 * g + 4 : nqb; }
 __host__ __device__ inline int group_splits(int g, int nqb, int nts) { return (group_tiles(g, nqb) + nts - 1) / nts; }
+// ... with pos0 cached positions in front of the P new rows (the *_at kernels): query blocks count new rows, key tiles absolute
+// positions — the group's last query, new row min(128 (g + 1), P) - 1, sees keys 0 .. pos0 + that row
+__host__ __device__ inline int group_tiles_at(int g, int P, int pos0) { return (pos0 + (128 * (g + 1) < P ? 128 * (g + 1) : P) + 31) >> 5; }
+__host__ __device__ inline int group_splits_at(int g, int P, int pos0, int nts) { return (group_tiles_at(g, P, pos0) + nts - 1) / nts; }
+
+// Four consecutive elements of a K / V row as staged (raw) -> fp32.  FMT 0: fp32 rows.  FMT 1: fp16 rows (raw.xy = four halves).
+// FMT 2: B24 rows (zg_common.h b24_round; raw.xy = the four bf16-shaped upper halves, raw.z = the four low bytes).  Both
+// conversions are exact, and so is the three-plane split behind them: an fp16 value fills two planes, a B24 value three.
+template <int FMT>
+__device__ __forceinline__ f32x4 kv_expand(u32x4 raw) {
+    if constexpr (FMT == 1) {
+        const uint32_t lo = raw.x, hi = raw.y;  // (halves by shifts: a bit_cast of the vector's elements to half pairs read .x twice)
+        return f32x4{(float)__builtin_bit_cast(_Float16, (uint16_t)lo), (float)__builtin_bit_cast(_Float16, (uint16_t)(lo >> 16)),
+                     (float)__builtin_bit_cast(_Float16, (uint16_t)hi), (float)__builtin_bit_cast(_Float16, (uint16_t)(hi >> 16))};
+    } else if constexpr (FMT == 2) {
+        return f32x4{__uint_as_float((raw.x << 16) | ((raw.z & 0xffu) << 8)), __uint_as_float((raw.x & 0xffff0000u) | (raw.z & 0xff00u)),
+                     __uint_as_float((raw.y << 16) | ((raw.z >> 8) & 0xff00u)), __uint_as_float((raw.y & 0xffff0000u) | ((raw.z >> 16) & 0xff00u))};
+    } else {
+        return __builtin_bit_cast(f32x4, raw);
+    }
+}
 
 // geo = key tiles per split | most splits of a group << 8 | query groups << 16.  part: [B][H][P][max splits][66] (O^T[64], m, l).
 //
@@ -83,8 +104,15 @@ struct AttnKv {
     size_t stride_b, stride_h;
     unsigned stride_t;
 };
-__global__ __launch_bounds__(256, 2) void attn_prefill_pl_kernel(const float* __restrict__ qkv, bf16_t* __restrict__ out, float* __restrict__ part,
-                                                                 int P, int E, unsigned geo, const AttnKv kv) {
+//
+// AT (the *_at kernel, a continuation): the P rows of qkv are positions pos0 .. pos0 + P - 1 and EVERY key, the pos0 cached ones
+// and the new ones alike, is read from the head-major caches in their storage format FMT (kv_expand; B24: the byte plane kv_lo
+// bytes behind the bf16 plane, rows of half the stride).  Query t sees keys 0 .. pos0 + t; the 32-query blocks count new rows, the
+// 32-key tiles absolute positions, so the diagonal crosses a tile at any angle: a wave masks every tile that reaches past its first
+// query.  !AT is the whole-prompt kernel as it always was (pos0 = 0, fp32 rows): every AT branch below is a compile-time one.
+template <int FMT, bool AT>
+__device__ __forceinline__ void attn_prefill_body(const float* __restrict__ qkv, bf16_t* __restrict__ out, float* __restrict__ part, int P, int E,
+                                                  unsigned geo, const AttnKv& kv, size_t kv_lo, int pos0) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -96,7 +124,10 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_pl_kernel(const float* __
     const int xg = (int)blockIdx.z / max_s, s = (int)blockIdx.z - xg * max_s, g = ng - 1 - xg;
     const int h = blockIdx.x, b = blockIdx.y, H = gridDim.x;
     const int nqb = (P + 31) >> 5;
-    const int kt0 = s * nts, kt1 = min((s + 1) * nts, group_tiles(g, nqb));
+    int g_tiles;
+    if constexpr (AT) g_tiles = group_tiles_at(g, P, pos0);
+    else g_tiles = group_tiles(g, nqb);
+    const int kt0 = s * nts, kt1 = min((s + 1) * nts, g_tiles);
     if (kt0 >= kt1) return;
 #ifdef ZG_STAMPS  // diagnostic build: every workgroup's start / end (s_memrealtime, 100 MHz) and where it ran -> part[] (unsplit launches only)
     const unsigned long long stamp0 = __builtin_amdgcn_s_memrealtime();
@@ -133,23 +164,50 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_pl_kernel(const float* __
     // The descriptors end behind key P - 1 of this (sequence, head): later keys read as zero (a cache row past the prompt may hold
     // anything, and 0 x NaN would poison the second product; the scores of such keys are masked anyway).
     const size_t kv_base = (size_t)b * kv.stride_b + (size_t)h * kv.stride_h;
-    const unsigned kv_bytes = (unsigned)(P - 1) * kv.stride_t + 256u;
+    unsigned kv_bytes;
+    if constexpr (AT) kv_bytes = (unsigned)(pos0 + P) * kv.stride_t;  // (cache rows are as long as their stride)
+    else kv_bytes = (unsigned)(P - 1) * kv.stride_t + 256u;
     const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(kv.ksrc + kv_base), 0, kv_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(kv.vsrc + kv_base), 0, kv_bytes, 0x00020000);
     const int skey = wave * 8 + (lane >> 4), sd0 = (lane & 15) * 4;
     const int vkey = wave * 8 + ((lane & 15) >> 2), vd0 = 16 * (lane >> 4) + 4 * (lane & 3);
-    const unsigned kvo = (unsigned)skey * kv.stride_t + (unsigned)sd0 * 4u, vvo = (unsigned)vkey * kv.stride_t + (unsigned)vd0 * 4u;
+    constexpr unsigned kEb = FMT == 0 ? 4u : 2u;  // bytes of an element (B24: of its upper half)
+    const unsigned kvo = (unsigned)skey * kv.stride_t + (unsigned)sd0 * kEb, vvo = (unsigned)vkey * kv.stride_t + (unsigned)vd0 * kEb;
+    // B24: the byte planes, everything at half the offsets of the bf16 planes
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t rkl, rvl;
+    if constexpr (FMT == 2) {
+        rkl = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(kv.ksrc + kv_lo + (kv_base >> 1)), 0, kv_bytes >> 1, 0x00020000);
+        rvl = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(kv.vsrc + kv_lo + (kv_base >> 1)), 0, kv_bytes >> 1, 0x00020000);
+    }
     const unsigned row4 = 4u * kv.stride_t;  // four keys further on
     auto tile_off = [&](int kt) { return (unsigned)kt * 32u * kv.stride_t; };
     auto load_k = [&](int kt, u32x4(&kr)[2]) {
         const unsigned so = tile_off(kt);
-        kr[0] = __builtin_amdgcn_raw_buffer_load_b128(rk, kvo, so, 0);
-        kr[1] = __builtin_amdgcn_raw_buffer_load_b128(rk, kvo + row4, so, 0);
+        if constexpr (FMT == 0) {
+            kr[0] = __builtin_amdgcn_raw_buffer_load_b128(rk, kvo, so, 0);
+            kr[1] = __builtin_amdgcn_raw_buffer_load_b128(rk, kvo + row4, so, 0);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const u32x2 hi = __builtin_amdgcn_raw_buffer_load_b64(rk, kvo + j * row4, so, 0);
+                kr[j] = u32x4{hi.x, hi.y, 0u, 0u};
+                if constexpr (FMT == 2) kr[j].z = __builtin_amdgcn_raw_buffer_load_b32(rkl, (kvo + j * row4) >> 1, so >> 1, 0);
+            }
+        }
     };
     auto load_v = [&](int kt, u32x4(&vr)[2]) {
         const unsigned so = tile_off(kt);
-        vr[0] = __builtin_amdgcn_raw_buffer_load_b128(rv, vvo, so, 0);
-        vr[1] = __builtin_amdgcn_raw_buffer_load_b128(rv, vvo + row4, so, 0);
+        if constexpr (FMT == 0) {
+            vr[0] = __builtin_amdgcn_raw_buffer_load_b128(rv, vvo, so, 0);
+            vr[1] = __builtin_amdgcn_raw_buffer_load_b128(rv, vvo + row4, so, 0);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const u32x2 hi = __builtin_amdgcn_raw_buffer_load_b64(rv, vvo + j * row4, so, 0);
+                vr[j] = u32x4{hi.x, hi.y, 0u, 0u};
+                if constexpr (FMT == 2) vr[j].z = __builtin_amdgcn_raw_buffer_load_b32(rvl, (vvo + j * row4) >> 1, so >> 1, 0);
+            }
+        }
     };
     char* const kring = lds;                    // [2 slots][3 planes][32 keys][64 d]
     char* const vring = lds + 2 * 3 * kKPlane;  // [2 slots][3 planes][4 d blocks][32 keys][16 d]
@@ -160,7 +218,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_pl_kernel(const float* __
         char* st = kring + slot * 3 * kKPlane;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const f32x4 v = __builtin_bit_cast(f32x4, kr[j]);
+            const f32x4 v = kv_expand<FMT>(kr[j]);
             uint32_t a[3], c[3];
             split3_pk(v.x, v.y, a[0], a[1], a[2]);
             split3_pk(v.z, v.w, c[0], c[1], c[2]);
@@ -172,7 +230,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_pl_kernel(const float* __
         char* st = vring + slot * 3 * kVPlane;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const f32x4 v = __builtin_bit_cast(f32x4, vr[j]);
+            const f32x4 v = kv_expand<FMT>(vr[j]);
             uint32_t a[3], c[3];
             split3_pk(v.x, v.y, a[0], a[1], a[2]);
             split3_pk(v.z, v.w, c[0], c[1], c[2]);
@@ -233,11 +291,15 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_pl_kernel(const float* __
         constexpr bool WITH_S = decltype(WITH_S_T)::value;
         const int kt = kt0 + i;
         // sc[r] = log2(e) / 8 * q . k of key kt * 32 + (r & 3) + 8 (r >> 2) + 4 hl against query tq
-        if (kt >= qb) {  // diagonal tile (and the tiles past it, which a sibling wave needs): position tq sees keys 0 .. tq
+        bool diag;
+        if constexpr (AT) diag = kt * 32 + 31 > pos0 + qb * 32;  // the tile reaches past the wave's first query (position pos0 + 32 qb)
+        else diag = kt >= qb;
+        if (diag) {  // diagonal tile (and the tiles past it, which a sibling wave needs): position tq sees keys 0 .. tq
+            const int last = AT ? pos0 + tq : tq;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-                sc[r] = key <= tq ? sc[r] : -INFINITY;
+                sc[r] = key <= last ? sc[r] : -INFINITY;
             }
         }
         float mx = sc[0];
@@ -338,7 +400,10 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_pl_kernel(const float* __
     if (qb >= nqb || tq >= P) return;
 
     // O^T: the lane holds d = (r & 3) + 8 (r >> 2) + 4 hl (+ 32 in o1) of its query
-    if (group_splits(g, nqb, nts) == 1) {  // softmax divides by the sum (ops.zig:239); the c_proj GEMM takes the rows as planes
+    int g_splits;
+    if constexpr (AT) g_splits = (g_tiles + nts - 1) / nts;
+    else g_splits = group_splits(g, nqb, nts);
+    if (g_splits == 1) {  // softmax divides by the sum (ops.zig:239); the c_proj GEMM takes the rows as planes
         const float inv = 1.0f / lrun;
         bf16_t* hi = out + (row0 + tq) * kSplit * E + h * 64;
 #pragma unroll
@@ -361,17 +426,31 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_pl_kernel(const float* __
     }
 }
 
+__global__ __launch_bounds__(256, 2) void attn_prefill_pl_kernel(const float* __restrict__ qkv, bf16_t* __restrict__ out, float* __restrict__ part,
+                                                                 int P, int E, unsigned geo, const AttnKv kv) {
+    attn_prefill_body<0, false>(qkv, out, part, P, E, geo, kv, 0, 0);
+}
+// the P new rows of a continuation against the caches (FMT: 0 fp32, 1 fp16, 2 B24)
+template <int FMT>
+__global__ __launch_bounds__(256, 2) void attn_prefill_at_kernel(const float* __restrict__ qkv, bf16_t* __restrict__ out, float* __restrict__ part, int P,
+                                                                 int E, unsigned geo, const AttnKv kv, size_t kv_lo, int pos0) {
+    attn_prefill_body<FMT, true>(qkv, out, part, P, E, geo, kv, kv_lo, pos0);
+}
+
 // The key ranges of a query meet: weights 2^(m_s - max m), sums in split order, one division; rows of groups that ran as one
 // range were finished by the attention kernel itself.  One thread = four head dimensions of one (sequence, head, query).
-__global__ __launch_bounds__(256) void attn_prefill_merge_kernel(const float* __restrict__ part, bf16_t* __restrict__ out, int P, int E, int H, int B,
-                                                                 unsigned geo) {
+template <bool AT>
+__device__ __forceinline__ void attn_prefill_merge_body(const float* __restrict__ part, bf16_t* __restrict__ out, int P, int E, int H, int B, unsigned geo,
+                                                        int pos0) {
     const int nts = (int)(geo & 0xffu), max_s = (int)((geo >> 8) & 0xffu);
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const int d = (int)(i & 15) * 4;
     const size_t rec = i >> 4;  // (b, h, q)
     if (rec >= (size_t)B * H * P) return;
     const int q = (int)(rec % P), h = (int)((rec / P) % H), b = (int)(rec / ((size_t)P * H));
-    const int n = group_splits(q >> 7, (P + 31) >> 5, nts);
+    int n;
+    if constexpr (AT) n = group_splits_at(q >> 7, P, pos0, nts);
+    else n = group_splits(q >> 7, (P + 31) >> 5, nts);
     if (n == 1) return;
     const float* pp = part + rec * max_s * 66;
     float m = -INFINITY;
@@ -407,6 +486,14 @@ __global__ __launch_bounds__(256) void attn_prefill_merge_kernel(const float* __
     }
     const float inv = 1.0f / l;
     store_split4(out + ((size_t)b * P + q) * kSplit * E + h * 64 + d, E, f32x4{o.x * inv, o.y * inv, o.z * inv, o.w * inv});
+}
+__global__ __launch_bounds__(256) void attn_prefill_merge_kernel(const float* __restrict__ part, bf16_t* __restrict__ out, int P, int E, int H, int B,
+                                                                 unsigned geo) {
+    attn_prefill_merge_body<false>(part, out, P, E, H, B, geo, 0);
+}
+__global__ __launch_bounds__(256) void attn_prefill_merge_at_kernel(const float* __restrict__ part, bf16_t* __restrict__ out, int P, int E, int H, int B,
+                                                                    unsigned geo, int pos0) {
+    attn_prefill_merge_body<true>(part, out, P, E, H, B, geo, pos0);
 }
 
 }  // namespace
@@ -461,6 +548,60 @@ int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int P, int E, int 
     if (max_s > 1) {
         const size_t n = (size_t)B * H * P * 16;
         hipLaunchKernelGGL(attn_prefill_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, out, P, E, H, B, geo);
+        ZG_HIP(hipGetLastError());
+    }
+    return ZG_OK;
+}
+
+// The same for a continuation: qkv holds the P new rows of every sequence (positions pos0 .. pos0 + P - 1; only their q columns
+// are read), the head-major caches [b][h][ctx][64] hold positions 0 .. pos0 + P - 1 in storage format kv_mode (0 fp32, 1 fp16,
+// 2 B24 with its byte plane kv_lo bytes behind the bf16 plane) — the new rows appended by the c_attn epilogue just before.
+int launch_attn_prefill_at(const float* qkv, bf16_t* out, int B, int pos0, int P, int E, int H, float* ws, size_t ws_floats, const void* k_cache,
+                           const void* v_cache, int kv_mode, size_t kv_lo, int ctx, hipStream_t s, int force_tiles) {
+    static bool raised = false;
+    if (!raised) {
+        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_prefill_at_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
+        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_prefill_at_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
+        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_prefill_at_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
+        raised = true;
+    }
+    ZG_REQUIRE(E == H * 64, ZG_ERR_UNSUPPORTED, "attention prefill: head_dim must be 64 (n_embed %d, %d heads)", E, H);
+    ZG_REQUIRE(k_cache != nullptr && v_cache != nullptr && kv_mode >= 0 && kv_mode <= 2 && pos0 >= 0 && P >= 1 && pos0 + P <= ctx, ZG_ERR_ARG,
+               "attention prefill at %d: %d rows, context %d", pos0, P, ctx);
+    const int nqb = (P + 31) / 32, ng = (nqb + 3) / 4, nkt = (pos0 + P + 31) / 32;
+    // key tiles per workgroup by the whole-prompt kernel's rule (launch_attn_prefill), over the rectangle's own split counts
+    int nts = 32 * ((nkt + 31) / 32);
+    {
+        const long groups = (long)B * H * ng;
+        if (force_tiles > 0) nts = force_tiles;
+        else
+            for (int cand = nts; cand >= 4; cand /= 2) {
+                long wgs = 0;
+                for (int g = 0; g < ng; ++g) wgs += group_splits_at(g, P, pos0, cand);
+                nts = cand;
+                if (wgs * B * H >= 512 || groups >= 256) break;
+            }
+        if (nts > 255) nts = 255;
+    }
+    int max_s = group_splits_at(ng - 1, P, pos0, nts);
+    if (max_s > 1 && (ws == nullptr || (size_t)B * H * P * max_s * 66 > ws_floats)) {  // no room for partials: whole rows
+        nts = nkt < 255 ? nkt : 255;
+        max_s = group_splits_at(ng - 1, P, pos0, nts);
+        ZG_REQUIRE(max_s == 1, ZG_ERR_UNSUPPORTED, "attention prefill: %d positions without a workspace", pos0 + P);
+    }
+    ZG_REQUIRE(ng < 65536 && max_s < 256, ZG_ERR_UNSUPPORTED, "attention prefill: %d positions", pos0 + P);
+    const unsigned geo = (unsigned)nts | ((unsigned)max_s << 8) | ((unsigned)ng << 16);
+    const unsigned row = kv_mode == 0 ? 256u : 128u;
+    const AttnKv kv{reinterpret_cast<const char*>(k_cache), reinterpret_cast<const char*>(v_cache), (size_t)H * ctx * row, (size_t)ctx * row, row};
+    ZG_REQUIRE((size_t)(pos0 + P + 128) * kv.stride_t < ((size_t)1 << 31), ZG_ERR_SHAPE, "attention prefill: rows beyond a 32-bit buffer descriptor");
+    const dim3 grid(H, B, ng * max_s);
+    if (kv_mode == 0) hipLaunchKernelGGL(attn_prefill_at_kernel<0>, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv, kv_lo, pos0);
+    else if (kv_mode == 1) hipLaunchKernelGGL(attn_prefill_at_kernel<1>, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv, kv_lo, pos0);
+    else hipLaunchKernelGGL(attn_prefill_at_kernel<2>, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv, kv_lo, pos0);
+    ZG_HIP(hipGetLastError());
+    if (max_s > 1) {
+        const size_t n = (size_t)B * H * P * 16;
+        hipLaunchKernelGGL(attn_prefill_merge_at_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, out, P, E, H, B, geo, pos0);
         ZG_HIP(hipGetLastError());
     }
     return ZG_OK;

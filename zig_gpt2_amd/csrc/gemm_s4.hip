@@ -730,7 +730,7 @@ __global__ __launch_bounds__(256, 1) void gemm_s4_kernel(const bf16_t* __restric
                         if (r < 0) { --q; r += qa.P; }
                         if (r >= qa.P) { ++q; r -= qa.P; }
                         sb[k] = q;
-                        st[k] = r;
+                        st[k] = r + qa.pos0;  // the cache row
                     }
                 }
                 static_for<NT>([&](auto JT) {
@@ -920,7 +920,7 @@ __global__ __launch_bounds__(256, 1) void gemm_s4_kernel(const bf16_t* __restric
 #pragma unroll
         for (int i = 0; i < 4; ++i) dma_a(1, 0, i, s1);
         if constexpr (KIND == S4_QKV) {  // the epilogue's argument-block fields, fetched under the first DMA
-            ZG_PIN(qa.P); ZG_PIN(qa.E); ZG_PIN(qa.H); ZG_PIN(qa.ctx); ZG_PIN(qa.kv_mode); ZG_PIN(qa.kv_lo); ZG_PIN(qa.k_cache); ZG_PIN(qa.v_cache);
+            ZG_PIN(qa.P); ZG_PIN(qa.E); ZG_PIN(qa.H); ZG_PIN(qa.ctx); ZG_PIN(qa.kv_mode); ZG_PIN(qa.kv_lo); ZG_PIN(qa.k_cache); ZG_PIN(qa.v_cache); ZG_PIN(qa.pos0);
         }
         if constexpr (P::PB == 6) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");  // B and A half 0 of K-step 0 are in
         else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");

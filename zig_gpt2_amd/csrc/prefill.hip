@@ -50,10 +50,11 @@ __device__ __forceinline__ f32x4 b24x4(const void* w, size_t row, int K, int k) 
     return f32x4{b24_elem(w, row, K, k), b24_elem(w, row, K, k + 1), b24_elem(w, row, K, k + 2), b24_elem(w, row, K, k + 3)};
 }
 
+// (pos0: row t of a sequence is position pos0 + t — its token and its wpe row; x rows stay b P + t)
 __global__ __launch_bounds__(256) void embed_prefill_kernel(const int* __restrict__ tokens, int token_stride, int P,
                                                             const void* __restrict__ wte, const void* __restrict__ wpe,
-                                                            int weight_type, int E, float* __restrict__ x) {
-    const int m = blockIdx.x, b = m / P, t = m % P;
+                                                            int weight_type, int E, float* __restrict__ x, int pos0) {
+    const int m = blockIdx.x, b = m / P, t = pos0 + m % P;
     const int tok = tokens[(size_t)b * token_stride + t];
     for (int e = threadIdx.x * 4; e < E; e += 1024) {
         f32x4 o;
@@ -241,7 +242,7 @@ __device__ __forceinline__ void prefill_gemm_body(const bf16_t* __restrict__ A, 
     };
     if (t0 < nt) issue(t0);
     if (EPI == PF_QKV) {  // the epilogue's argument-block fields, fetched under the first DMA
-        ZG_PIN(qa.P); ZG_PIN(qa.E); ZG_PIN(qa.H); ZG_PIN(qa.ctx); ZG_PIN(qa.kv_mode); ZG_PIN(qa.kv_lo); ZG_PIN(qa.k_cache); ZG_PIN(qa.v_cache);
+        ZG_PIN(qa.P); ZG_PIN(qa.E); ZG_PIN(qa.H); ZG_PIN(qa.ctx); ZG_PIN(qa.kv_mode); ZG_PIN(qa.kv_lo); ZG_PIN(qa.k_cache); ZG_PIN(qa.v_cache); ZG_PIN(qa.pos0);
     }
 
     const int frow = lane & 31, fk = lane >> 5;
@@ -643,9 +644,9 @@ int launch_prefill_gemm_t(const bf16_t* A, const bf16_t* B, const float* bias, v
 }  // namespace
 
 int launch_embed_prefill(const int* tokens, int token_stride, int B, int P, const void* wte, const void* wpe,
-                         int weight_type, int E, float* x, hipStream_t s) {
+                         int weight_type, int E, float* x, hipStream_t s, int pos0) {
     hipLaunchKernelGGL(embed_prefill_kernel, dim3(B * P), dim3(256), 0, s, tokens, token_stride, P, wte, wpe, weight_type,
-                       E, x);
+                       E, x, pos0);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

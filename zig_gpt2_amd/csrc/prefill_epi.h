@@ -29,7 +29,7 @@ __device__ __forceinline__ void qkv_cache_store(const PrefillQkv& q, int m, int 
     const int which = n >= 2 * q.E;
     const int e = n - (which ? 2 * q.E : q.E);
     const int b = m / q.P, t = m - b * q.P;
-    kv_cache_store4(q, which ? q.v_cache : q.k_cache, (((size_t)b * q.H + (e >> 6)) * q.ctx + t) * 64 + (e & 63), v);
+    kv_cache_store4(q, which ? q.v_cache : q.k_cache, (((size_t)b * q.H + (e >> 6)) * q.ctx + q.pos0 + t) * 64 + (e & 63), v);
 }
 
 }  // namespace zg

@@ -222,8 +222,9 @@ void gemm_note_launch();
 // stored as planes [M][kSplit * K] = [hi | mid | lo].
 constexpr int kSplit = 3;
 enum PrefillEpilogue { PF_F32 = 0, PF_RESID = 1, PF_GELU_SPLIT = 2, PF_PARTIAL = 3 /* internal: split-K slice */, PF_QKV = 4 };
+// x[b P + t] = wte[tokens[b][pos0 + t]] + wpe[pos0 + t]
 int launch_embed_prefill(const int* tokens, int token_stride, int B, int P, const void* wte, const void* wpe,
-                         int weight_type, int E, float* x, hipStream_t s);
+                         int weight_type, int E, float* x, hipStream_t s, int pos0 = 0);
 int launch_ln_split(const float* x, int M, int E, const float* g, const float* b, float eps, bf16_t* out, hipStream_t s);
 // C = A[M][kSplit K] * W[N][K]^T + bias; PF_F32: fp32 C[M][ldc]; PF_RESID: C += ...; PF_GELU_SPLIT: bf16 C[M][kSplit N] = split(gelu(...))
 // ws: fp32 workspace for split-K partial sums (used when the output has too few tiles to fill the chip).
@@ -244,6 +245,7 @@ struct PrefillQkv {
     unsigned* sk_flags = nullptr;
     unsigned sk_flags_words = 0;  // words behind sk_flags (4 per shared tile: G / 2 tiles for G workgroups)
     unsigned sk_epoch = 0;
+    int pos0 = 0;  // a continuation (zg_gpt_extend): row t of a sequence is position pos0 + t, and that is its cache row
 };
 struct PrefillLn {
     const float* g;
@@ -261,6 +263,10 @@ void prefill_force_route(int kernel, int slices);  // zg_debug_prefill_route / _
 // (attn_prefill.hip: bf16 matrix cores on exact plane splits; ws = fp32 workspace for the partials of split key ranges)
 int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int P, int E, int H, float* ws, size_t ws_floats, const float* k_cache_or_null,
                         const float* v_cache_or_null, int ctx, hipStream_t s, int force_tiles = 0);  // force_tiles: key tiles per workgroup (tests)
+// ... of the P new rows of a continuation (positions pos0 .. pos0 + P - 1; qkv holds those rows only, their q columns are read)
+// against caches that hold positions 0 .. pos0 + P - 1 in storage format kv_mode (0 fp32, 1 fp16, 2 B24 with kv_lo)
+int launch_attn_prefill_at(const float* qkv, bf16_t* out, int B, int pos0, int P, int E, int H, float* ws, size_t ws_floats, const void* k_cache,
+                           const void* v_cache, int kv_mode, size_t kv_lo, int ctx, hipStream_t s, int force_tiles = 0);
 
 // GPT.sample tail: in-place softmax(logits / temp) per sequence + inverse-CDF draw with uniform u[b].
 // part_val / n_part / part_stride: the per-workgroup maxima lm_head's argmax epilogue left (the row maximum without a pass over the

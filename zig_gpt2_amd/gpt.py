@@ -117,6 +117,24 @@ class GPT:
                                      ptr(logits), ops._n(logits)))
         return logits
 
+    def cached_len(self):
+        """Positions the handle's caches hold (zg_gpt_cached_len)."""
+        n = C.c_size_t()
+        check(self._L.zg_gpt_cached_len(self.h, C.byref(n)))
+        return n.value
+
+    def extend(self, past_len, tokens, compute_logits=True, want_logits=True):
+        """prefill at an offset (zg_gpt_extend): tokens [batch, n] go to positions past_len .. past_len + n - 1 behind the cached
+        ones in one pass; returns the logits of the last new position ([batch, V]) or None.  past_len below cached_len() rolls back."""
+        tokens = np.ascontiguousarray(np.atleast_2d(tokens), dtype=np.uint64)
+        assert tokens.shape[0] == self.batch
+        logits = None
+        if compute_logits and want_logits:
+            logits = np.empty((self.batch, self.config.vocab_size), np.float32)
+        check(self._L.zg_gpt_extend(self.h, past_len, ptr(tokens), max(tokens.shape[1], 1), tokens.shape[1], int(compute_logits), ptr(logits),
+                                    ops._n(logits)))
+        return logits
+
     @staticmethod
     def _truncated(top_k, top_p):
         return top_k != 0 or top_p != 1.0
@@ -174,6 +192,22 @@ class GPT:
         out = np.zeros((self.batch, n_steps), np.uint64)
         check(self._L.zg_gpt_generate_fetch(self.h, n_steps, ptr(out), out.size))
         return out
+
+    def generate_fetch_range(self, first, n):
+        """Tokens of positions first .. first + n - 1 of the last generation(s): [batch, n]."""
+        out = np.zeros((self.batch, n), np.uint64)
+        check(self._L.zg_gpt_generate_fetch_range(self.h, first, n, ptr(out), out.size))
+        return out
+
+    def generate_from(self, past_len, prompts, n_steps, temp=None, seed=0, top_k=0, top_p=1.0):
+        """generate entered at position past_len (zg_gpt_generate_from_enqueue): `prompts` are the new tokens of each row, fed
+        behind the past_len cached positions; returns the tokens of positions past_len .. past_len + n_steps - 1 ([batch, n_steps]).
+        temp=None: greedy; otherwise the sampler of generate_sample (top_k / top_p as there)."""
+        mat, lens, stride = self._prompts(prompts)
+        opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
+        check(self._L.zg_gpt_generate_from_enqueue(self.h, past_len, ptr(mat), stride, ptr(lens), n_steps,
+                                                   None if opt is None else C.addressof(opt), seed))
+        return self.generate_fetch_range(past_len, n_steps)
 
     def generate_sample(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0):
         """generate (src/main.zig:322-342) as the reference runs it — every token behind the prompt drawn by GPT.sample — with the
