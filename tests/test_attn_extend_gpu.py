@@ -67,8 +67,10 @@ def planes_to_f64(bits, n):
 # (B, past, n, H, key_tiles, spike): one boundary each — a single row behind a single key; one row behind a short past; two rows
 # across the first tile edge; a tile-aligned past; an unaligned one with forced one-tile ranges; a rectangle that ends exactly on a
 # tile; two query groups with split ranges and a merge; a batch whose first group has a padded wave; a long past cut into ranges of
-# five tiles; a dominant key inside the past (the deferred rescale must fire)
-CASES = [(1, 1, 1, 2, 0, False), (2, 5, 1, 2, 0, False), (1, 31, 2, 2, 0, False), (1, 32, 32, 3, 0, False), (2, 33, 31, 2, 1, False),
+# five tiles; a dominant key inside the past (the deferred rescale must fire); 33 rows behind an empty past, across one tile edge (the
+# launcher's choice at past 0: the whole-prompt kernel on an fp32 cache, the continuation kernels at 0 on an fp16 / B24 one)
+CASES = [(1, 0, 33, 2, 0, False),
+         (1, 1, 1, 2, 0, False), (2, 5, 1, 2, 0, False), (1, 31, 2, 2, 0, False), (1, 32, 32, 3, 0, False), (2, 33, 31, 2, 1, False),
          (1, 7, 25, 2, 0, False), (1, 100, 130, 2, 2, False), (3, 130, 126, 2, 0, False), (1, 900, 123, 2, 5, False),
          (1, 150, 107, 2, 3, True)]
 

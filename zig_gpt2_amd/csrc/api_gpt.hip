@@ -3,7 +3,9 @@
 // live in a single arena allocated by zg_gpt_create (the State.init / load_gpt moment of the
 // reference); a decode step is a fixed chain of kernels captured once into a hipGraph whose
 // position, tokens and argmax all live in device memory, so a whole greedy generation is enqueued
-// without a host round trip per token.
+// without a host round trip per token.  Three things exist once each: the whole-prompt pass (pass_impl: zg_gpt_prefill is
+// zg_gpt_extend at 0), the generation request (GenRequest, run by gen_run for every zg_gpt_generate*_enqueue) and the shape of a
+// decode step (StepKey {with_logits, multi, SamplerMode}: what enqueue_step launches and which graph replays it).
 //
 // HBM layout (one hipMalloc, 256-B aligned sub-buffers):
 //   [ weights: wte | wpe | ln_f | per layer: c_attn_w c_proj_w c_fc_w mlp_proj_w + fp32 vectors ]
@@ -22,6 +24,11 @@
 #include "zg_runtime.h"
 
 using namespace zg;
+
+// What a step puts behind lm_head: nothing (greedy: the argmax partials of its epilogue are the pick), GPT.sample's tail, or that
+// tail behind the selection launches of one filter (top-k or top-p) / of both.  The one form "how are tokens chosen" travels in.
+enum SamplerMode { GREEDY = 0, PLAIN, ONE_FILTER, TWO_FILTERS };
+static inline int filter_launches(SamplerMode m) { return m == TWO_FILTERS ? 6 : m == ONE_FILTER ? 3 : 0; }  // sample_filter.h: three levels per descent
 
 struct zg_layer {
     void *c_attn_w, *c_proj_w, *c_fc_w, *mlp_proj_w;
@@ -90,7 +97,7 @@ struct zg_gpt {
     // pinned host mirrors for small control traffic
     StepCtrl* h_ctrl;
     int* h_ints;  // [batch * ctx] staging for prompts / tokens
-    // graphs [GraphKind][n_buckets]: one per (kind, 64-position bucket of seq_len), captured on first use (graph_exec).
+    // graphs [step_index(StepKey)][n_buckets]: one per (step shape, 64-position bucket of seq_len), captured on first use (graph_exec).
     // The bucket's upper bound t_hi is baked into the attention / merge kernels so that their loads
     // do not wait for the exact seq_len (which lives in device memory).
     std::vector<hipGraphExec_t> graphs;
@@ -99,8 +106,7 @@ struct zg_gpt {
     float* samp_ws;           // segment sums of the sampler (sample_workspace_floats)
     SampleParams* samp;       // device: temperature and seed of the generation in flight
     SampleParams* h_samp;     // pinned mirror
-    bool gen_sampled;         // the generation in flight draws its tokens
-    int gen_trunc;            // ... behind top-k / top-p truncation: filter launches per step (3: one filter, 6: both; 0: none)
+    SamplerMode gen_mode;     // how the generation in flight chooses its tokens
     FilterWs filt;            // selection workspace of the truncated sampler (sample_filter.h), zero at create
     size_t graph_steps;
     hipStream_t graph_stream;
@@ -253,7 +259,6 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
         g->pf_qkv = (float*)P(B * C * 3 * E * 4);
         g->pf_a = (bf16_t*)P(B * C * kSplit * E * 2);
         g->pf_h = (bf16_t*)P(B * C * kSplit * 4 * E * 2);
-        // bf16 weights: 64 MiB of split-K partial sums; fp32 weights: a full fp32 [rows][4 E] GEMM output
         // split-K partials of the prompt GEMMs; fp32 weights: three weight-plane passes of [B ctx, 4 E] at the least
         g->pf_ws_floats = g->wt == WT_BF16 ? (size_t)(16u << 20) : std::max((size_t)(16u << 20), 3 * B * C * 4 * E);
         g->pf_ws = (float*)P(g->pf_ws_floats * 4);
@@ -547,8 +552,7 @@ struct StepOpts {
     // >= 0 (measurement chains of one kernel class): launch ids of the tagged hand-overs by chain position instead of by
     // layer, so that consecutive launches of the chain never find each other's tags
     int salt = -1;
-    bool with_sampler = false;  // GPT.sample's tail behind lm_head (with_logits only)
-    int trunc_levels = 0;       // ... behind top-k / top-p truncation: 3 (one filter) or 6 (both) selection launches in front of it
+    SamplerMode sampler = GREEDY;  // what follows lm_head (with_logits only)
 };
 
 // One decode step = GPT.forward (main.zig:178-195) for all sequences.
@@ -625,10 +629,11 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         ZG_TRY(prof_mark(prof, 6, s));
     }
     // GPT.sample's tail (main.zig:200-206) on the logits of this step: the next step's embed kernel feeds what it draws (mode 2)
-    if (o.with_sampler && o.trunc_levels && with_logits && only < 0 && !rec)
-        ZG_TRY(launch_sample_filtered(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, o.trunc_levels, nullptr, g->ctrl, g->part_val, g->lm_grid,
+    if (o.sampler == GREEDY || !with_logits || only >= 0 || rec) return ZG_OK;
+    if (const int levels = filter_launches(o.sampler))
+        ZG_TRY(launch_sample_filtered(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, levels, nullptr, g->ctrl, g->part_val, g->lm_grid,
                                       g->lm_grid, g->samp_ws, g->filt, g->sampled, false, s));
-    else if (o.with_sampler && with_logits && only < 0 && !rec)
+    else
         ZG_TRY(launch_sample_step(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, g->ctrl, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws,
                                   g->sampled, s));
     return ZG_OK;
@@ -644,10 +649,9 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
 // (Measured and dropped in round 4: replaying this pass from a hipGraph per prompt length.  0.844 against 0.749 ms at 64
 // tokens, 1.645 against 1.553 ms at 1023 — the ~10 us a launch costs here is the kernels' own latency at these sizes, not host
 // overhead, and a graph launch adds its own ~10 us; profiles/round4_prefill_graph.jsonl.)
-// pos0 > 0 (a continuation, zg_gpt_extend): the P rows are positions pos0 .. pos0 + P - 1 (tokens g->prompt[b][pos0 + t]); they are
-// appended behind the pos0 cached rows, and the attention reads every key, old and new, from the caches in their storage format
-// (attn_prefill.hip, the *_at kernels).  pos0 == 0 launches what it always launched.
-int enqueue_prefill(zg_gpt* g, size_t P, bool last_block_full, hipStream_t s, size_t pos0 = 0) {
+// pos0 > 0 (a continuation): the P rows are positions pos0 .. pos0 + P - 1 (tokens g->prompt[b][pos0 + t]); they are appended
+// behind the pos0 cached rows, and the attention reads every key, old and new, from the caches in their storage format.
+int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipStream_t s) {
     const bool f32w = g->wt != WT_BF16;
     const int np = f32w ? kWeightPlanes : (g->flags & ZG_GPT_PREFILL_2PLANE) ? 2 : kSplit;
     const size_t E = g->cfg.n_embed, L = g->cfg.n_layer, H = g->cfg.n_heads, C = g->cfg.context_size;
@@ -671,13 +675,11 @@ int enqueue_prefill(zg_gpt* g, size_t P, bool last_block_full, hipStream_t s, si
         ZG_TRY(launch_prefill_gemm(g->pf_a, f32w ? y.c_attn_p : (const bf16_t*)y.c_attn_w, y.c_attn_b, g->pf_qkv, M, 3 * iE, iE, 3 * iE, PF_QKV,
                                    g->pf_ws, g->pf_ws_floats, nullptr, s, &qa, np));
         if (l + 1 == L && !last_block_full) break;
-        // (an fp32 cache is read directly: the c_attn epilogue then need not store the k / v columns of qkv)
-        if (pos0 > 0)
-            ZG_TRY(launch_attn_prefill_at(g->pf_qkv, g->pf_a, B, (int)pos0, (int)P, iE, (int)H, g->pf_ws, g->pf_ws_floats, y.k_cache, y.v_cache, g->kv_mode,
-                                          g->batch * C * E * 2, (int)C, s));
-        else
-        ZG_TRY(launch_attn_prefill(g->pf_qkv, g->pf_a, B, (int)P, iE, (int)H, g->pf_ws, g->pf_ws_floats, g->kv_mode == 0 ? (const float*)y.k_cache : nullptr,
-                                       g->kv_mode == 0 ? (const float*)y.v_cache : nullptr, (int)C, s));
+        // K and V: the caches — except a whole prompt on an fp16 / B24 cache, which reads the unrounded k / v columns of qkv (an fp32
+        // cache is read directly: the c_attn epilogue then need not store those columns)
+        PrefillKv kv;
+        if (pos0 > 0 || g->kv_mode == 0) kv = PrefillKv{y.k_cache, y.v_cache, g->kv_mode, g->batch * C * E * 2, (int)C};
+        ZG_TRY(launch_attn_prefill(g->pf_qkv, g->pf_a, B, (int)pos0, (int)P, iE, (int)H, g->pf_ws, g->pf_ws_floats, kv, s));
         const PrefillLn ln2{y.ln_2_g, y.ln_2_b, 1e-5f, g->pf_a};
         ZG_TRY(launch_prefill_gemm(g->pf_a, f32w ? y.c_proj_p : (const bf16_t*)y.c_proj_w, y.c_proj_b, g->pf_x, M, iE, iE, iE, PF_RESID, g->pf_ws,
                                    g->pf_ws_floats, &ln2, s, nullptr, np));
@@ -824,26 +826,19 @@ int pf_stop(zg_gpt* g, hipStream_t s) {
 
 size_t prefill_min() { return 4; }  // shorter prompts go through the decode chain (measured: the whole-prompt pass pays from 4 tokens up)
 
-// The decode graphs of a handle, per 64-position bucket of the sequence length.
-enum GraphKind {
-    G_STEP = 0,        // one step without lm_head
-    G_STEP_LOGITS,     // one step with lm_head
-    // graph_steps consecutive steps (all with lm_head, all in one bucket) as ONE graph: the position lives in device memory, so
-    // the same kernels simply repeat; saves the gap between graph launches in the generate loop
-    G_MULTI,
-    // generate with the sampler (zg_gpt_generate_sample_*): one step / graph_steps steps with lm_head AND the sampler node behind
-    // it; captured at create with ZG_GPT_SAMPLED_GENERATE, otherwise on the first sampled generation
-    G_SAMPLED,
-    G_SAMPLED_MULTI,
-    // generate with the truncated sampler (zg_gpt_generate_sample_ex_*): the same with the selection launches of ONE filter
-    // (G_TRUNC*) or of top-k and top-p together (G_TRUNC2*) in front of the sampler; the option values are read on the device.
-    // Captured at create with ZG_GPT_TRUNCATED_GENERATE, otherwise when the first generation that needs them begins.
-    G_TRUNC,
-    G_TRUNC_MULTI,
-    G_TRUNC2,
-    G_TRUNC2_MULTI,
-    G_KINDS
+// The decode graphs of a handle, per 64-position bucket of the sequence length, keyed by what the graph contains:
+//   with_logits  lm_head behind the Blocks (a step that only feeds a prompt token has none)
+//   multi        graph_steps consecutive steps (all with lm_head, all in one bucket) as ONE graph: the position lives in device
+//                memory, so the same kernels simply repeat; saves the gap between graph launches in the generate loop
+//   sampler      the sampler node(s) behind lm_head (zg_gpt_generate_sample_*; the option values are read on the device)
+// multi and a sampler imply with_logits: 9 shapes exist.  Captured at create — the sampled ones with ZG_GPT_SAMPLED_GENERATE /
+// ZG_GPT_TRUNCATED_GENERATE, otherwise when the first generation that needs them begins.
+struct StepKey {
+    bool with_logits, multi;
+    SamplerMode sampler;
 };
+constexpr size_t kStepShapes = 9;
+size_t step_index(StepKey k) { return k.sampler != GREEDY ? 1 + 2 * (size_t)k.sampler + k.multi : k.multi ? 2 : k.with_logits; }
 
 size_t bucket_of(size_t seq_len) { return (seq_len + 63) / 64 - 1; }
 
@@ -869,18 +864,17 @@ int capture_graph(hipStream_t cs, hipGraphExec_t* out, Body body) {
     return ZG_OK;
 }
 
-// The graph of (kind, bucket b) for stream s (the stream of g->graph_stream: capture_all), captured on first use.
-int graph_exec(zg_gpt* g, GraphKind kind, size_t b, hipStream_t s, hipGraphExec_t* out) {
-    hipGraphExec_t& e = g->graphs[kind * g->n_buckets + b];
+// The graph of (step shape k, bucket b) for stream s (the stream of g->graph_stream: capture_all), captured on first use.
+int graph_exec(zg_gpt* g, StepKey k, size_t b, hipStream_t s, hipGraphExec_t* out) {
+    hipGraphExec_t& e = g->graphs[step_index(k) * g->n_buckets + b];
     if (!e) {
         const int t_hi = bucket_t_hi(g, (b + 1) * 64);  // any length of the bucket: only its upper bound is baked in
-        const size_t n_steps = (kind == G_MULTI || kind == G_SAMPLED_MULTI || kind == G_TRUNC_MULTI || kind == G_TRUNC2_MULTI) ? g->graph_steps : 1;
+        const size_t n_steps = k.multi ? g->graph_steps : 1;
         StepOpts o;
-        o.with_sampler = kind >= G_SAMPLED;
-        o.trunc_levels = (kind == G_TRUNC || kind == G_TRUNC_MULTI) ? 3 : (kind == G_TRUNC2 || kind == G_TRUNC2_MULTI) ? 6 : 0;
+        o.sampler = k.sampler;
         ZG_TRY(capture_graph(s, &e, [&] {
             int st = ZG_OK;
-            for (size_t i = 0; i < n_steps && st == ZG_OK; ++i) st = enqueue_step(g, kind != G_STEP, t_hi, s, o);
+            for (size_t i = 0; i < n_steps && st == ZG_OK; ++i) st = enqueue_step(g, k.with_logits, t_hi, s, o);
             return st;
         }));
     }
@@ -888,16 +882,12 @@ int graph_exec(zg_gpt* g, GraphKind kind, size_t b, hipStream_t s, hipGraphExec_
     return ZG_OK;
 }
 
-GraphKind sampler_kind(int trunc_levels, bool multi) {
-    return trunc_levels == 3 ? (multi ? G_TRUNC_MULTI : G_TRUNC) : trunc_levels == 6 ? (multi ? G_TRUNC2_MULTI : G_TRUNC2) : (multi ? G_SAMPLED_MULTI : G_SAMPLED);
-}
-
-// The truncated sampler's graphs (trunc_levels 3 or 6) of buckets b0 .. b1
-int capture_truncated(zg_gpt* g, int trunc_levels, size_t b0, size_t b1, hipStream_t s) {
+// The single-step and (where the handle has them) multi-step graphs of a sampler mode, buckets b0 .. b1
+int capture_sampled(zg_gpt* g, SamplerMode mode, size_t b0, size_t b1, hipStream_t s) {
     hipGraphExec_t e;
     for (size_t b = b0; b <= b1 && b < g->n_buckets; ++b) {
-        ZG_TRY(graph_exec(g, sampler_kind(trunc_levels, false), b, s, &e));
-        if (g->graph_steps > 1) ZG_TRY(graph_exec(g, sampler_kind(trunc_levels, true), b, s, &e));
+        ZG_TRY(graph_exec(g, {true, false, mode}, b, s, &e));
+        if (g->graph_steps > 1) ZG_TRY(graph_exec(g, {true, true, mode}, b, s, &e));
     }
     return ZG_OK;
 }
@@ -912,35 +902,30 @@ int capture_all(zg_gpt* g, hipStream_t s) {
     }
     hipGraphExec_t e;
     for (size_t b = 0; b < g->n_buckets; ++b) {
-        ZG_TRY(graph_exec(g, G_STEP, b, s, &e));
-        ZG_TRY(graph_exec(g, G_STEP_LOGITS, b, s, &e));
+        ZG_TRY(graph_exec(g, {false, false, GREEDY}, b, s, &e));
+        ZG_TRY(graph_exec(g, {true, false, GREEDY}, b, s, &e));
     }
     if (g->graph_steps > 1)
-        for (size_t b = 0; b < g->n_buckets; ++b) ZG_TRY(graph_exec(g, G_MULTI, b, s, &e));
-    if (g->flags & ZG_GPT_SAMPLED_GENERATE)
-        for (size_t b = 0; b < g->n_buckets; ++b) {
-            ZG_TRY(graph_exec(g, G_SAMPLED, b, s, &e));
-            if (g->graph_steps > 1) ZG_TRY(graph_exec(g, G_SAMPLED_MULTI, b, s, &e));
-        }
+        for (size_t b = 0; b < g->n_buckets; ++b) ZG_TRY(graph_exec(g, {true, true, GREEDY}, b, s, &e));
+    if (g->flags & ZG_GPT_SAMPLED_GENERATE) ZG_TRY(capture_sampled(g, PLAIN, 0, g->n_buckets - 1, s));
     if (g->flags & ZG_GPT_TRUNCATED_GENERATE)
-        for (int levels = 3; levels <= 6; levels += 3) ZG_TRY(capture_truncated(g, levels, 0, g->n_buckets - 1, s));
+        for (SamplerMode m : {ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, 0, g->n_buckets - 1, s));
     return ZG_OK;
 }
 
 // Run one decode step at sequence length seq_len: replay the graph of its bucket, or launch eagerly when graphs
 // are disabled / the stream cannot be captured.
-int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, bool with_sampler = false, int trunc_levels = 0) {
+int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, SamplerMode sampler = GREEDY) {
     ZG_TRY(ensure_ln_folded(g, s));
-    with_sampler = with_sampler && with_logits;
+    if (!with_logits) sampler = GREEDY;  // (nothing to draw from)
     if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) {
         StepOpts o;
-        o.with_sampler = with_sampler;
-        o.trunc_levels = trunc_levels;
+        o.sampler = sampler;
         return enqueue_step(g, with_logits, bucket_t_hi(g, seq_len), s, o);
     }
     if (g->graph_stream != s) ZG_TRY(capture_all(g, s));  // the caller switched streams after zg_gpt_create
     hipGraphExec_t e;
-    ZG_TRY(graph_exec(g, with_sampler ? sampler_kind(trunc_levels, false) : with_logits ? G_STEP_LOGITS : G_STEP, bucket_of(seq_len), s, &e));
+    ZG_TRY(graph_exec(g, {with_logits, false, sampler}, bucket_of(seq_len), s, &e));
     ZG_HIP(hipGraphLaunch(e, s));
     return ZG_OK;
 }
@@ -1088,7 +1073,7 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
         g->graph_steps = (k == 2 || k == 4 || k == 8 || k == 16 || k == 32 || k == 64) ? (size_t)k : 1;
     }
     g->n_buckets = (c.context_size + 63) / 64;
-    g->graphs.assign(G_KINDS * g->n_buckets, nullptr);
+    g->graphs.assign(kStepShapes * g->n_buckets, nullptr);
     // every decode graph is captured and instantiated here, not on the first forward that needs it
     ZG_TRY(setup_prefetcher(g));
     ZG_TRY(capture_all(g, gs(g)));
@@ -1292,11 +1277,13 @@ static int clear_kv(zg_gpt* g, hipStream_t s, size_t from_row = 0, bool keep_hea
     return ZG_OK;
 }
 
-// A continuation at past_len whose pass ends at row `end`: the rows behind it are cleared if anything was written there since
-// they were last clean (a rollback, or zg_gpt_forward calls out of order) — the decode attention reads its whole 64-position
-// bucket, and what a discarded row holds (a NaN, say) must not come back.  Rows below past_len are never touched.
-static int clear_behind(zg_gpt* g, hipStream_t s, size_t end) {
-    if (g->kv_dirty_hi > end) ZG_TRY(clear_kv(g, s, end, true));
+// The cache policy of a whole-prompt pass over rows past .. end - 1.  past == 0, a new sequence: everything behind the pass is
+// cleared (clear_kv).  A continuation: the rows behind it are cleared if anything was written there since they were last clean (a
+// rollback, or zg_gpt_forward calls out of order) — the decode attention reads its whole 64-position bucket, and what a
+// discarded row holds (a NaN, say) must not come back.  Rows below past are never touched.
+static int clear_for_pass(zg_gpt* g, hipStream_t s, size_t past, size_t end) {
+    if (past == 0) ZG_TRY(clear_kv(g, s, end));
+    else if (g->kv_dirty_hi > end) ZG_TRY(clear_kv(g, s, end, true));
     g->kv_dirty_hi = end;
     return ZG_OK;
 }
@@ -1348,38 +1335,48 @@ int zg_gpt_forward(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tok
     return check_fault(g);
 }
 
-int zg_gpt_prefill(zg_gpt* g, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits,
-                   float* logits_out, size_t logits_len) {
+// The whole-prompt pass: n tokens of every sequence go to positions past_len .. past_len + n - 1 behind the cached
+// ones — the prompt loop of generate (main.zig:331-334) at an offset — and, on request, ln_f + lm_head of each sequence's last new
+// position run through the decode kernels.  Everything is checked before the handle or its staging is touched.
+static int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t stride, size_t n, int compute_logits, float* logits_out, size_t logits_len,
+                     const char* who) {
     ZG_TRY(require_init());
-    ZG_REQUIRE(g && tokens, ZG_ERR_ARG, "gpt_prefill: null argument");
-    ZG_REQUIRE(g->pf_x != nullptr, ZG_ERR_UNSUPPORTED, "gpt_prefill: the handle was created with ZG_GPT_NO_PREFILL");
+    ZG_REQUIRE(g && tokens, ZG_ERR_ARG, "%s: null argument", who);
+    ZG_REQUIRE(g->pf_x != nullptr, ZG_ERR_UNSUPPORTED, "%s: the handle was created with ZG_GPT_NO_PREFILL", who);
     const size_t C = g->cfg.context_size, V = g->cfg.vocab_size, B = g->batch, E = g->cfg.n_embed;
-    ZG_REQUIRE(n_tokens >= 1 && n_tokens <= C && n_tokens <= token_stride, ZG_ERR_SHAPE,
-               "gpt_prefill: n_tokens %zu outside 1..%zu (stride %zu)", n_tokens, C, token_stride);
-    ZG_REQUIRE(!logits_out || (compute_logits && logits_len >= B * V), ZG_ERR_SHAPE,
-               "gpt_prefill: logits_out needs compute_logits and %zu elements", B * V);
+    ZG_REQUIRE(past_len <= g->cached_len, ZG_ERR_ARG, "%s: past_len %zu beyond the %zu cached positions", who, past_len, g->cached_len);
+    ZG_REQUIRE(n >= 1 && past_len + n <= C && n <= stride, ZG_ERR_SHAPE, "%s: %zu tokens behind %zu positions (context %zu, stride %zu)", who, n, past_len, C,
+               stride);
+    ZG_REQUIRE(!logits_out || (compute_logits && logits_len >= B * V), ZG_ERR_SHAPE, "%s: logits_out needs compute_logits and %zu elements", who, B * V);
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < n; ++i) ZG_REQUIRE(tokens[b * stride + i] < V, ZG_ERR_SHAPE, "%s: token %zu >= vocab %zu", who, tokens[b * stride + i], V);
     hipStream_t s = gs(g);
     ZG_HIP(hipStreamSynchronize(s));
     for (size_t b = 0; b < B; ++b)
-        for (size_t i = 0; i < n_tokens; ++i) {
-            const size_t t = tokens[b * token_stride + i];
-            ZG_REQUIRE(t < V, ZG_ERR_SHAPE, "gpt_prefill: token %zu >= vocab %zu", t, V);
-            g->h_ints[b * C + i] = (int)t;
-        }
+        for (size_t i = 0; i < n; ++i) g->h_ints[b * C + past_len + i] = (int)tokens[b * stride + i];
     ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
-    ZG_TRY(clear_kv(g, s, n_tokens));
-    g->cached_len = g->kv_dirty_hi = n_tokens;
+    const size_t end = past_len + n;
+    ZG_TRY(clear_for_pass(g, s, past_len, end));
+    g->cached_len = end;
     ZG_TRY(ensure_ln_folded(g, s));
-    ZG_TRY(enqueue_prefill(g, n_tokens, compute_logits != 0, s));
-    if (compute_logits) {  // ln_f + lm_head of each sequence's last position through the decode kernels
-        ZG_HIP(hipMemcpy2DAsync(g->x, E * 4, g->pf_x + (n_tokens - 1) * E, n_tokens * E * 4, E * 4, B,
-                                hipMemcpyDeviceToDevice, s));
-        ZG_TRY(stage_ctrl(g, n_tokens - 1, n_tokens, 1, s));
+    ZG_TRY(enqueue_prefill(g, past_len, n, compute_logits != 0, s));
+    if (compute_logits) {
+        ZG_HIP(hipMemcpy2DAsync(g->x, E * 4, g->pf_x + (n - 1) * E, n * E * 4, E * 4, B, hipMemcpyDeviceToDevice, s));
+        ZG_TRY(stage_ctrl(g, end - 1, end, 1, s));
         ZG_TRY(enqueue_lm_head(g, s));
         if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, B * V, s));
     }
     ZG_HIP(hipStreamSynchronize(s));
     return check_fault(g);
+}
+
+int zg_gpt_prefill(zg_gpt* g, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits, float* logits_out, size_t logits_len) {
+    return pass_impl(g, 0, tokens, token_stride, n_tokens, compute_logits, logits_out, logits_len, "gpt_prefill");
+}
+
+int zg_gpt_extend(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits, float* logits_out,
+                  size_t logits_len) {
+    return pass_impl(g, past_len, tokens, token_stride, n_tokens, compute_logits, logits_out, logits_len, "gpt_extend");
 }
 
 int zg_gpt_cached_len(zg_gpt* g, size_t* len_out) {
@@ -1387,42 +1384,6 @@ int zg_gpt_cached_len(zg_gpt* g, size_t* len_out) {
     ZG_REQUIRE(g && len_out, ZG_ERR_ARG, "gpt_cached_len: null argument");
     *len_out = g->cached_len;
     return ZG_OK;
-}
-
-// zg_gpt_prefill behind past_len cached positions: one whole-prompt pass over the n_tokens new rows
-int zg_gpt_extend(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits, float* logits_out,
-                  size_t logits_len) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(g && tokens, ZG_ERR_ARG, "gpt_extend: null argument");
-    ZG_REQUIRE(g->pf_x != nullptr, ZG_ERR_UNSUPPORTED, "gpt_extend: the handle was created with ZG_GPT_NO_PREFILL");
-    const size_t C = g->cfg.context_size, V = g->cfg.vocab_size, B = g->batch, E = g->cfg.n_embed;
-    ZG_REQUIRE(past_len <= g->cached_len, ZG_ERR_ARG, "gpt_extend: past_len %zu beyond the %zu cached positions", past_len, g->cached_len);
-    ZG_REQUIRE(n_tokens >= 1 && past_len + n_tokens <= C && n_tokens <= token_stride, ZG_ERR_SHAPE,
-               "gpt_extend: %zu tokens behind %zu positions (context %zu, stride %zu)", n_tokens, past_len, C, token_stride);
-    ZG_REQUIRE(!logits_out || (compute_logits && logits_len >= B * V), ZG_ERR_SHAPE, "gpt_extend: logits_out needs compute_logits and %zu elements",
-               B * V);
-    for (size_t b = 0; b < B; ++b)
-        for (size_t i = 0; i < n_tokens; ++i)
-            ZG_REQUIRE(tokens[b * token_stride + i] < V, ZG_ERR_SHAPE, "gpt_extend: token %zu >= vocab %zu", tokens[b * token_stride + i], V);
-    if (past_len == 0) return zg_gpt_prefill(g, tokens, token_stride, n_tokens, compute_logits, logits_out, logits_len);
-    hipStream_t s = gs(g);
-    ZG_HIP(hipStreamSynchronize(s));
-    for (size_t b = 0; b < B; ++b)
-        for (size_t i = 0; i < n_tokens; ++i) g->h_ints[b * C + past_len + i] = (int)tokens[b * token_stride + i];
-    ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
-    const size_t end = past_len + n_tokens;
-    ZG_TRY(clear_behind(g, s, end));
-    g->cached_len = end;
-    ZG_TRY(ensure_ln_folded(g, s));
-    ZG_TRY(enqueue_prefill(g, n_tokens, compute_logits != 0, s, past_len));
-    if (compute_logits) {  // ln_f + lm_head of each sequence's last new position through the decode kernels
-        ZG_HIP(hipMemcpy2DAsync(g->x, E * 4, g->pf_x + (n_tokens - 1) * E, n_tokens * E * 4, E * 4, B, hipMemcpyDeviceToDevice, s));
-        ZG_TRY(stage_ctrl(g, end - 1, end, 1, s));
-        ZG_TRY(enqueue_lm_head(g, s));
-        if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, B * V, s));
-    }
-    ZG_HIP(hipStreamSynchronize(s));
-    return check_fault(g);
 }
 
 int zg_gpt_argmax(zg_gpt* g, size_t* tokens_out, size_t n_tokens) {
@@ -1436,16 +1397,16 @@ int zg_gpt_argmax(zg_gpt* g, size_t* tokens_out, size_t n_tokens) {
     return ZG_OK;
 }
 
-static int fill_sample_params(zg_gpt* g, float temp, size_t top_k, float top_p, uint64_t seed);
+static SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed);
 static int check_sample_options(const zg_sample_options* o, const char* who);
-static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, size_t top_k, float top_p, const float* uniforms,
-                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len);
+static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options& o, const float* uniforms, uint64_t seed,
+                       size_t* tokens_out, float* probs_out, size_t probs_len);
 
 int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, const float* uniforms,
                   uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "gpt_sample: bad argument");
-    return sample_impl(g, seq_len, tokens, n_tokens, temp, 0, 1.0f, uniforms, seed, tokens_out, probs_out, probs_len);
+    return sample_impl(g, seq_len, tokens, n_tokens, zg_sample_options{temp, 0, 1.0f}, uniforms, seed, tokens_out, probs_out, probs_len);
 }
 
 // zg_gpt_sample behind top-k / nucleus truncation (filters off: exactly zg_gpt_sample's launches)
@@ -1453,11 +1414,11 @@ int zg_gpt_sample_ex(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_t
                      uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
     ZG_TRY(require_init());
     ZG_TRY(check_sample_options(opt, "gpt_sample_ex"));
-    return sample_impl(g, seq_len, tokens, n_tokens, opt->temp, opt->top_k, opt->top_p, uniforms, seed, tokens_out, probs_out, probs_len);
+    return sample_impl(g, seq_len, tokens, n_tokens, *opt, uniforms, seed, tokens_out, probs_out, probs_len);
 }
 
-static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, size_t top_k, float top_p, const float* uniforms,
-                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
+static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options& o, const float* uniforms, uint64_t seed,
+                       size_t* tokens_out, float* probs_out, size_t probs_len) {
     ZG_REQUIRE(g && tokens && tokens_out, ZG_ERR_ARG, "gpt_sample: bad argument");
     const size_t V = g->cfg.vocab_size, B = g->batch;
     ZG_REQUIRE(!probs_out || probs_len >= B * V, ZG_ERR_SHAPE, "gpt_sample: probs_out needs %zu elements", B * V);
@@ -1480,13 +1441,13 @@ static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n
     }
     float* d_u = g->q;  // scratch: q is dead after the forward
     ZG_HIP(hipMemcpyAsync(d_u, h_u, B * sizeof(float), hipMemcpyHostToDevice, s));
-    const int levels = fill_sample_params(g, temp, top_k, top_p, seed);  // (h_samp: nothing in flight reads it, forward_enqueue's callers drain)
-    if (levels) {
+    // (h_samp: nothing in flight reads it, forward_enqueue's callers drain)
+    if (const int levels = filter_launches(fill_sample_params(g->h_samp, V, o, seed))) {
         ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
         ZG_TRY(launch_sample_filtered(g->logits, (int)B, (int)V, g->samp, levels, d_u, nullptr, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->filt,
                                       g->cur_token, probs_out != nullptr, s));
     } else
-        ZG_TRY(launch_sample(g->logits, (int)B, (int)V, temp, d_u, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->cur_token, probs_out != nullptr,
+        ZG_TRY(launch_sample(g->logits, (int)B, (int)V, o.temp, d_u, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->cur_token, probs_out != nullptr,
                              s));  // main.zig:200-206
     ZG_HIP(hipMemcpyAsync(g->h_ints + B, g->cur_token, B * sizeof(int), hipMemcpyDeviceToHost, s));
     if (probs_out) ZG_TRY(copy_out_f32(probs_out, g->logits, B * V, s));
@@ -1505,16 +1466,16 @@ int zg_gpt_hidden(zg_gpt* g, float* x_out, size_t len) {
     return check_fault(g);
 }
 
-// The options of a sampler call into the pinned mirror of SampleParams (the caller uploads it); returns the selection launches
-// per step they need: 0 (no filter: the plain sampler), 3 (one filter) or 6 (both)
-static int fill_sample_params(zg_gpt* g, float temp, size_t top_k, float top_p, uint64_t seed) {
-    const bool k_on = top_k >= 1 && top_k < g->cfg.vocab_size, p_on = top_p < 1.0f;
-    g->h_samp->inv_temp = 1.0f / temp;
-    g->h_samp->top_k = k_on ? (unsigned)top_k : 0u;
-    g->h_samp->seed = seed;
-    g->h_samp->top_p = p_on ? top_p : 1.0f;
-    g->h_samp->pad = 0;
-    return k_on && p_on ? 6 : (k_on || p_on) ? 3 : 0;
+// The options of a sampler call over `vocab` logits into *p, the host image of SampleParams (the caller uploads it); returns the
+// sampler they need: the plain one with both filters off
+static SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed) {
+    const bool k_on = o.top_k >= 1 && o.top_k < vocab, p_on = o.top_p < 1.0f;
+    p->inv_temp = 1.0f / o.temp;
+    p->top_k = k_on ? (unsigned)o.top_k : 0u;
+    p->seed = seed;
+    p->top_p = p_on ? o.top_p : 1.0f;
+    p->pad = 0;
+    return k_on && p_on ? TWO_FILTERS : (k_on || p_on) ? ONE_FILTER : PLAIN;
 }
 
 static int check_sample_options(const zg_sample_options* o, const char* who) {
@@ -1533,25 +1494,41 @@ static int check_sample_options(const zg_sample_options* o, const char* who) {
 // prompt[b][past + i], prompt_len[b] = past + prompt_lens[b]; everything the embed kernel and gen_pump compare is absolute, so the
 // steps are the ones an uninterrupted generation would run at these positions.  The caches keep rows 0 .. past - 1 and the
 // recorded tokens of positions below past stay where they are (zg_gpt_generate_fetch_range).
-static int gen_begin(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps, bool sampled = false,
-                     float temp = 1.0f, uint64_t seed = 0, size_t top_k = 0, float top_p = 1.0f, size_t past = 0) {
-    ZG_REQUIRE(g && prompts && prompt_lens, ZG_ERR_ARG, "generate: null argument");
+
+// What a generation is asked for: the one argument of every zg_gpt_generate*_enqueue entry point to gen_begin
+struct GenRequest {
+    const size_t* prompts;  // [rows][stride], lens[rows] tokens each
+    size_t stride;
+    const size_t* lens;
+    size_t n_steps, past;
+    SamplerMode mode;       // GREEDY (opt unused), or PLAIN: draw with opt — gen_begin raises it to the filters opt switches on
+    zg_sample_options opt;
+    uint64_t seed;
+    GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, const zg_sample_options* opt_or_null = nullptr, uint64_t seed = 0,
+               size_t past = 0)
+        : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past), mode(opt_or_null ? PLAIN : GREEDY),
+          opt(opt_or_null ? *opt_or_null : zg_sample_options{1.0f, 0, 1.0f}), seed(seed) {}
+};
+
+static int gen_begin(zg_gpt* g, const GenRequest& r) {
+    const size_t n_steps = r.n_steps, past = r.past;
+    ZG_REQUIRE(g && r.prompts && r.lens, ZG_ERR_ARG, "generate: null argument");
     const size_t C = g->cfg.context_size, V = g->cfg.vocab_size, B = g->batch;
     ZG_REQUIRE(past <= g->cached_len, ZG_ERR_ARG, "generate: past_len %zu beyond the %zu cached positions", past, g->cached_len);
     ZG_REQUIRE(n_steps >= 1 && past + n_steps <= C, ZG_ERR_SHAPE, "generate: n_steps %zu outside 1..%zu", n_steps, C - past);
     for (size_t b = 0; b < B; ++b) {  // (everything is checked before the handle's state is touched)
-        const size_t np = prompt_lens[b];
-        ZG_REQUIRE(np >= 1 && past + np <= C && np <= prompt_stride, ZG_ERR_SHAPE, "generate: prompt %zu has length %zu", b, np);
+        const size_t np = r.lens[b];
+        ZG_REQUIRE(np >= 1 && past + np <= C && np <= r.stride, ZG_ERR_SHAPE, "generate: prompt %zu has length %zu", b, np);
         for (size_t i = 0; i < np; ++i)
-            ZG_REQUIRE(prompts[b * prompt_stride + i] < V, ZG_ERR_SHAPE, "generate: token %zu >= vocab %zu", prompts[b * prompt_stride + i], V);
+            ZG_REQUIRE(r.prompts[b * r.stride + i] < V, ZG_ERR_SHAPE, "generate: token %zu >= vocab %zu", r.prompts[b * r.stride + i], V);
     }
     hipStream_t s = gs(g);
     ZG_HIP(hipStreamSynchronize(s));  // pinned staging below is shared with earlier calls
     size_t min_prompt = C;
     memset(g->h_ints, 0, (B * C + B) * sizeof(int));
     for (size_t b = 0; b < B; ++b) {
-        const size_t np = prompt_lens[b];
-        for (size_t i = 0; i < np; ++i) g->h_ints[b * C + past + i] = (int)prompts[b * prompt_stride + i];
+        const size_t np = r.lens[b];
+        for (size_t i = 0; i < np; ++i) g->h_ints[b * C + past + i] = (int)r.prompts[b * r.stride + i];
         g->h_ints[B * C + b] = (int)(past + np);
         if (np < min_prompt) min_prompt = np;
     }
@@ -1560,31 +1537,28 @@ static int gen_begin(zg_gpt* g, const size_t* prompts, size_t prompt_stride, con
     size_t first = 0;
     if (g->pf_x != nullptr && min_prompt >= prefill_min())
         first = min_prompt < n_steps ? min_prompt : n_steps;
-    g->gen_sampled = sampled;
-    g->gen_trunc = 0;
-    if (sampled) {
-        g->gen_trunc = fill_sample_params(g, temp, top_k, top_p, seed);
+    g->gen_mode = r.mode;
+    if (r.mode != GREEDY) {
+        g->gen_mode = fill_sample_params(g->h_samp, V, r.opt, r.seed);
         ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     }
     ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(g->prompt_len, g->h_ints + B * C, B * sizeof(int), hipMemcpyHostToDevice, s));
-    ZG_TRY(stage_ctrl(g, past + first, past + first, sampled ? 2 : 0, s));
-    if (past == 0) ZG_TRY(clear_kv(g, s, first));
-    else ZG_TRY(clear_behind(g, s, past + first));
+    ZG_TRY(stage_ctrl(g, past + first, past + first, r.mode != GREEDY ? 2 : 0, s));
+    ZG_TRY(clear_for_pass(g, s, past, past + first));
     g->cached_len = g->kv_dirty_hi = past + n_steps;  // the last position the loop feeds
     ZG_TRY(ensure_ln_folded(g, s));
-    if (first > 0 && past == 0) {
-        ZG_HIP(hipMemcpyAsync(g->out_tokens, g->prompt, B * C * sizeof(int), hipMemcpyDeviceToDevice, s));
-        ZG_TRY(enqueue_prefill(g, first, false, s));
-    } else if (first > 0) {  // only the new columns: the tokens recorded below past stay
-        ZG_HIP(hipMemcpy2DAsync(g->out_tokens + past, C * sizeof(int), g->prompt + past, C * sizeof(int), first * sizeof(int), B, hipMemcpyDeviceToDevice, s));
-        ZG_TRY(enqueue_prefill(g, first, false, s, past));
+    if (first > 0) {
+        if (past == 0) ZG_HIP(hipMemcpyAsync(g->out_tokens, g->prompt, B * C * sizeof(int), hipMemcpyDeviceToDevice, s));
+        else  // only the new columns: the tokens recorded below past stay
+            ZG_HIP(hipMemcpy2DAsync(g->out_tokens + past, C * sizeof(int), g->prompt + past, C * sizeof(int), first * sizeof(int), B, hipMemcpyDeviceToDevice, s));
+        ZG_TRY(enqueue_prefill(g, past, first, false, s));
     }
     if (!(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && g->graph_stream != s) ZG_TRY(capture_all(g, s));  // before the prefetcher starts its idle clock
     // the truncated sampler's graphs of every bucket this generation touches, if create did not capture them: here, not in the
     // loop (a capture between the steps would run against the prefetcher's idle clock)
-    if (g->gen_trunc && !(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && min_prompt < n_steps)
-        ZG_TRY(capture_truncated(g, g->gen_trunc, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
+    if (filter_launches(g->gen_mode) && !(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && min_prompt < n_steps)
+        ZG_TRY(capture_sampled(g, g->gen_mode, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
     ZG_TRY(note_steps(g, n_steps, s));
     ZG_TRY(pf_start(g, past + n_steps, s));
     g->gen_pos = past + first;  // absolute, as gen_n and gen_min_prompt: gen_pump's steps, buckets and graph alignment follow the position
@@ -1611,11 +1585,11 @@ static int gen_pump(zg_gpt* g, bool* more) {
     if (K > 1 && st >= g->gen_min_prompt && st % K == 0 && st + K <= n_steps && st + K <= C) {
         if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
         hipGraphExec_t e;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64)
-        ZG_TRY(graph_exec(g, g->gen_sampled ? sampler_kind(g->gen_trunc, true) : G_MULTI, bucket_of(st + 1), s, &e));
+        ZG_TRY(graph_exec(g, {true, true, g->gen_mode}, bucket_of(st + 1), s, &e));
         ZG_HIP(hipGraphLaunch(e, s));
         g->gen_pos = st + K;
     } else {
-        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_sampled, g->gen_trunc));
+        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_mode));
         g->gen_pos = st + 1;
     }
     *more = g->gen_pos < n_steps;
@@ -1639,171 +1613,18 @@ static int gen_end(zg_gpt* g, int rs) {
     return ZG_OK;
 }
 
-int zg_gpt_generate_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens,
-                            size_t n_steps) {
-    ZG_TRY(require_init());
-    ZG_TRY(gen_begin(g, prompts, prompt_stride, prompt_lens, n_steps));
-    return gen_end(g, gen_pump_all(g));
-}
-
-// generate (src/main.zig:322-342) AS THE REFERENCE RUNS IT: every token behind the prompt is drawn by GPT.sample
-// (main.zig:198-207, :336-338) — softmax(logits / temp), then the first index whose running sum exceeds u x total — with the
-// whole loop on the device: the sampler is a node of the captured decode step (sample_step_kernel) and the next step's embed
-// kernel feeds its draw.  The uniform of (sequence b, position T) is the counter PRNG of (seed, T, b) that zg_gpt_sample uses when
-// it is given no uniforms, so this call returns exactly the tokens of a host loop `tok = zg_gpt_sample(g, T, tok, temp, NULL,
-// seed, ...)` — without a host round trip per token.  Results through zg_gpt_generate_fetch.
-int zg_gpt_generate_sample_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
-                                   float temp, uint64_t seed) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "generate_sample: temperature %f", temp);
-    ZG_TRY(gen_begin(g, prompts, prompt_stride, prompt_lens, n_steps, true, temp, seed));
-    return gen_end(g, gen_pump_all(g));
-}
-
-int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps, float temp,
-                           uint64_t seed, size_t* out_tokens, size_t out_len) {
-    ZG_REQUIRE(g && out_tokens && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_sample: out_tokens too short");
-    ZG_TRY(zg_gpt_generate_sample_enqueue(g, prompts, prompt_stride, prompt_lens, n_steps, temp, seed));
-    return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
-}
-
-// The same behind top-k / nucleus truncation (include/zgpt2.h zg_sample_options; sample_filter.h): the selection launches sit in
-// front of the sampler node of graphs of their own (G_TRUNC*), the option values live in device memory.  Filters off: the calls above.
-int zg_gpt_generate_sample_ex_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
-                                      const zg_sample_options* opt, uint64_t seed) {
-    ZG_TRY(require_init());
-    ZG_TRY(check_sample_options(opt, "generate_sample_ex"));
-    ZG_TRY(gen_begin(g, prompts, prompt_stride, prompt_lens, n_steps, true, opt->temp, seed, opt->top_k, opt->top_p));
-    return gen_end(g, gen_pump_all(g));
-}
-
-int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
-                              const zg_sample_options* opt, uint64_t seed, size_t* out_tokens, size_t out_len) {
-    ZG_REQUIRE(g && out_tokens && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_sample_ex: out_tokens too short");
-    ZG_TRY(zg_gpt_generate_sample_ex_enqueue(g, prompts, prompt_stride, prompt_lens, n_steps, opt, seed));
-    return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
-}
-
-// generate entered at s = past_len (DESIGN §3.5): the decode loop's own graphs at the absolute positions, the shortest new length
-// through the whole-prompt pass first where the handle has one.  options null: greedy.
-int zg_gpt_generate_from_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
-                                 const zg_sample_options* opt, uint64_t seed) {
-    ZG_TRY(require_init());
-    if (opt) ZG_TRY(check_sample_options(opt, "generate_from"));
-    ZG_TRY(gen_begin(g, prompts, prompt_stride, prompt_lens, n_steps, opt != nullptr, opt ? opt->temp : 1.0f, seed, opt ? opt->top_k : 0,
-                     opt ? opt->top_p : 1.0f, past_len));
-    return gen_end(g, gen_pump_all(g));
-}
-
-int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(g && out_tokens, ZG_ERR_ARG, "generate_fetch_range: null argument");
-    const size_t C = g->cfg.context_size, B = g->batch;
-    ZG_REQUIRE(first <= C && n <= C - first && out_len >= B * n, ZG_ERR_SHAPE, "generate_fetch_range: positions %zu .. %zu of %zu, %zu elements", first,
-               first + n, C, out_len);
-    hipStream_t s = gs(g);
-    ZG_HIP(hipMemcpyAsync(g->h_ints, g->out_tokens, B * C * sizeof(int), hipMemcpyDeviceToHost, s));
-    ZG_HIP(hipStreamSynchronize(s));
-    ZG_TRY(check_fault(g));
-    for (size_t b = 0; b < B; ++b)
-        for (size_t i = 0; i < n; ++i) out_tokens[b * n + i] = (size_t)g->h_ints[b * C + first + i];
-    return ZG_OK;
-}
-
-// The truncated sampler on the caller's logits (tests): the kernels of zg_gpt_sample_ex, a small kernel standing in for lm_head's
-// argmax partials.  Allocates its workspace per call.
-int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const float* uniforms, size_t* tokens_out,
-                         float* probs_out, float* thresholds_out) {
-    ZG_TRY(require_init());
-    ZG_TRY(check_sample_options(opt, "debug_sample_rows"));
-    ZG_REQUIRE(logits && uniforms && tokens_out && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG,
-               "debug_sample_rows: bad argument");
-    const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
-    const bool k_on = opt->top_k >= 1 && opt->top_k < vocab, p_on = opt->top_p < 1.0f;
-    const int levels = k_on && p_on ? 6 : (k_on || p_on) ? 3 : 0;
-    const size_t fbytes = (filter_workspace_bytes(B) + 255) & ~(size_t)255, lbytes = (batch * vocab * 4 + 255) & ~(size_t)255;
-    const size_t sbytes = (sample_workspace_floats(B) * 4 + 255) & ~(size_t)255, pbytes = ((size_t)B * n_part * 4 + 255) & ~(size_t)255;
-    const size_t total = fbytes + lbytes + sbytes + pbytes + 256 * 3 + (((size_t)B * 8 + 255) & ~(size_t)255);
-    hipStream_t s = ctx().stream;
-    char* base = nullptr;
-    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), total));
-    struct Free {
-        char* p;
-        ~Free() { (void)hipFree(p); }
-    } guard{base};
-    char* p = base;
-    const FilterWs fws = filter_workspace(p, B);
-    p += fbytes;
-    float* d_logits = reinterpret_cast<float*>(p);
-    p += lbytes;
-    float* d_seg = reinterpret_cast<float*>(p);
-    p += sbytes;
-    float* d_part = reinterpret_cast<float*>(p);
-    p += pbytes;
-    SampleParams* d_par = reinterpret_cast<SampleParams*>(p);
-    p += 256;
-    float* d_u = reinterpret_cast<float*>(p);
-    p += 256;
-    int* d_tok = reinterpret_cast<int*>(p);
-    p += 256;
-    SampleParams hp{};
-    hp.inv_temp = 1.0f / opt->temp;
-    hp.top_k = k_on ? (unsigned)opt->top_k : 0u;
-    hp.top_p = p_on ? opt->top_p : 1.0f;
-    std::vector<int> h_tok(batch);
-    std::vector<float> h_u(batch);
-    for (size_t b = 0; b < batch; ++b) {
-        float u;
-        ZG_HIP(hipMemcpy(&u, uniforms + b, 4, hipMemcpyDefault));
-        ZG_REQUIRE(u >= 0.0f && u < 1.0f, ZG_ERR_ARG, "debug_sample_rows: uniform %f outside [0,1)", u);
-        h_u[b] = u;
-    }
-    ZG_HIP(hipMemsetAsync(base, 0, fbytes, s));
-    ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
-    ZG_HIP(hipMemcpyAsync(d_u, h_u.data(), batch * 4, hipMemcpyHostToDevice, s));
-    ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
-    ZG_TRY(launch_row_max_partials(d_logits, B, V, d_part, n_part, s));
-    if (levels)
-        ZG_TRY(launch_sample_filtered(d_logits, B, V, d_par, levels, d_u, nullptr, d_part, n_part, n_part, d_seg, fws, d_tok, probs_out != nullptr, s));
-    else  // filters off: the existing sampler
-        ZG_TRY(launch_sample(d_logits, B, V, opt->temp, d_u, d_part, n_part, n_part, d_seg, d_tok, probs_out != nullptr, s));
-    ZG_HIP(hipMemcpyAsync(h_tok.data(), d_tok, batch * 4, hipMemcpyDeviceToHost, s));
-    if (probs_out) ZG_HIP(hipMemcpyAsync(probs_out, d_logits, batch * vocab * 4, hipMemcpyDefault, s));
-    if (thresholds_out) {
-        if (levels) ZG_HIP(hipMemcpyAsync(thresholds_out, fws.tau, batch * 4, hipMemcpyDefault, s));
-        else {  // nothing dropped: -inf
-            std::vector<float> ninf(batch, -INFINITY);
-            ZG_HIP(hipMemcpy(thresholds_out, ninf.data(), batch * 4, hipMemcpyDefault));
-        }
-    }
-    ZG_HIP(hipStreamSynchronize(s));
-    for (size_t b = 0; b < batch; ++b) tokens_out[b] = (size_t)h_tok[b];
-    return ZG_OK;
-}
-
-// generate (src/main.zig:322-342) for the prompts of SEVERAL handles at once: independent sequences need not run in lock step
-// (the reference's batch restriction, ops.zig:126-128, lifted the other way) — every handle decodes its own prompts on its own
-// stream (zg_gpt_create_ex: own_stream) and the chip overlaps the chains, each of which leaves it idle across every one of its
-// launch boundaries.  The handles are fed side by side: a hardware queue holds a fraction of a generation's dispatches, and a
-// host that fed one handle to the end first would block on that queue while the others idle.
-int zg_gpt_generate_enqueue_many(zg_gpt* const* handles, size_t n_handles, const size_t* prompts, size_t prompt_stride,
-                                 const size_t* prompt_lens, size_t n_steps) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(handles && n_handles >= 1 && n_handles <= 64 && prompts && prompt_lens, ZG_ERR_ARG, "generate_many: bad argument");
-    for (size_t i = 0; i < n_handles; ++i) {
-        ZG_REQUIRE(handles[i] != nullptr, ZG_ERR_ARG, "generate_many: handle %zu is null", i);
-        for (size_t j = 0; j < i; ++j) {
-            ZG_REQUIRE(handles[i] != handles[j], ZG_ERR_ARG, "generate_many: handle %zu is handle %zu", i, j);
-            ZG_REQUIRE(n_handles == 1 || gs(handles[i]) != gs(handles[j]), ZG_ERR_ARG,
-                       "generate_many: handles %zu and %zu share a stream (create them with own_stream)", j, i);
-        }
-    }
-    size_t begun = 0, row = 0;
+// One request for the rows of n handles, handle by handle: gen_begin for each, the pumps side by side, gen_end for each that began.
+// Several handles: every handle decodes its own prompts on its own stream and the chip overlaps the chains, each of which leaves
+// it idle across every one of its launch boundaries.  The handles are fed side by side: a hardware queue holds a fraction of a
+// generation's dispatches, and a host that fed one handle to the end first would block on that queue while the others idle.
+static int gen_run(zg_gpt* const* handles, size_t n_handles, GenRequest req) {
+    size_t begun = 0;
     int rs = ZG_OK;
     for (; begun < n_handles && rs == ZG_OK; ++begun) {
-        rs = gen_begin(handles[begun], prompts + row * prompt_stride, prompt_stride, prompt_lens + row, n_steps);
+        rs = gen_begin(handles[begun], req);
         if (rs != ZG_OK) break;  // (its message is picked up below)
-        row += handles[begun]->batch;
+        req.prompts += handles[begun]->batch * req.stride;
+        req.lens += handles[begun]->batch;
     }
     char msg[512] = "";
     if (rs == ZG_OK && begun > 1) {
@@ -1838,6 +1659,158 @@ int zg_gpt_generate_enqueue_many(zg_gpt* const* handles, size_t n_handles, const
     }
     if (first_err != ZG_OK) set_error("%s", msg);
     return first_err;
+}
+
+int zg_gpt_generate_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps) {
+    ZG_TRY(require_init());
+    return gen_run(&g, 1, GenRequest(prompts, prompt_stride, prompt_lens, n_steps));
+}
+
+// generate (src/main.zig:322-342) AS THE REFERENCE RUNS IT: every token behind the prompt is drawn by GPT.sample
+// (main.zig:198-207, :336-338) — softmax(logits / temp), then the first index whose running sum exceeds u x total — with the
+// whole loop on the device: the sampler is a node of the captured decode step (sample_step_kernel) and the next step's embed
+// kernel feeds its draw.  The uniform of (sequence b, position T) is the counter PRNG of (seed, T, b) that zg_gpt_sample uses when
+// it is given no uniforms, so this call returns exactly the tokens of a host loop `tok = zg_gpt_sample(g, T, tok, temp, NULL,
+// seed, ...)` — without a host round trip per token.  Results through zg_gpt_generate_fetch.
+int zg_gpt_generate_sample_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                   float temp, uint64_t seed) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "generate_sample: temperature %f", temp);
+    const zg_sample_options plain{temp, 0, 1.0f};
+    return gen_run(&g, 1, GenRequest(prompts, prompt_stride, prompt_lens, n_steps, &plain, seed));
+}
+
+int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps, float temp,
+                           uint64_t seed, size_t* out_tokens, size_t out_len) {
+    ZG_REQUIRE(g && out_tokens && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_sample: out_tokens too short");
+    ZG_TRY(zg_gpt_generate_sample_enqueue(g, prompts, prompt_stride, prompt_lens, n_steps, temp, seed));
+    return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
+}
+
+// The same behind top-k / nucleus truncation (include/zgpt2.h zg_sample_options; sample_filter.h): the selection launches sit in
+// front of the sampler node of graphs of their own (StepKey.sampler), the option values live in device memory.  Filters off: the
+// calls above.
+int zg_gpt_generate_sample_ex_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                      const zg_sample_options* opt, uint64_t seed) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, "generate_sample_ex"));
+    return gen_run(&g, 1, GenRequest(prompts, prompt_stride, prompt_lens, n_steps, opt, seed));
+}
+
+int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                              const zg_sample_options* opt, uint64_t seed, size_t* out_tokens, size_t out_len) {
+    ZG_REQUIRE(g && out_tokens && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_sample_ex: out_tokens too short");
+    ZG_TRY(zg_gpt_generate_sample_ex_enqueue(g, prompts, prompt_stride, prompt_lens, n_steps, opt, seed));
+    return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
+}
+
+// generate entered at s = past_len (DESIGN §3.5): the decode loop's own graphs at the absolute positions, the shortest new length
+// through the whole-prompt pass first where the handle has one.  options null: greedy.
+int zg_gpt_generate_from_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                 const zg_sample_options* opt, uint64_t seed) {
+    ZG_TRY(require_init());
+    if (opt) ZG_TRY(check_sample_options(opt, "generate_from"));
+    return gen_run(&g, 1, GenRequest(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len));
+}
+
+int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && out_tokens, ZG_ERR_ARG, "generate_fetch_range: null argument");
+    const size_t C = g->cfg.context_size, B = g->batch;
+    ZG_REQUIRE(first <= C && n <= C - first && out_len >= B * n, ZG_ERR_SHAPE, "generate_fetch_range: positions %zu .. %zu of %zu, %zu elements", first,
+               first + n, C, out_len);
+    hipStream_t s = gs(g);
+    ZG_HIP(hipMemcpyAsync(g->h_ints, g->out_tokens, B * C * sizeof(int), hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < n; ++i) out_tokens[b * n + i] = (size_t)g->h_ints[b * C + first + i];
+    return ZG_OK;
+}
+
+// The truncated sampler on the caller's logits (tests): the kernels of zg_gpt_sample_ex, a small kernel standing in for lm_head's
+// argmax partials.  Allocates its workspace per call.
+int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const float* uniforms, size_t* tokens_out,
+                         float* probs_out, float* thresholds_out) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, "debug_sample_rows"));
+    ZG_REQUIRE(logits && uniforms && tokens_out && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG,
+               "debug_sample_rows: bad argument");
+    const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
+    SampleParams hp{};
+    const int levels = filter_launches(fill_sample_params(&hp, vocab, *opt, 0));
+    const size_t fbytes = (filter_workspace_bytes(B) + 255) & ~(size_t)255, lbytes = (batch * vocab * 4 + 255) & ~(size_t)255;
+    const size_t sbytes = (sample_workspace_floats(B) * 4 + 255) & ~(size_t)255, pbytes = ((size_t)B * n_part * 4 + 255) & ~(size_t)255;
+    const size_t total = fbytes + lbytes + sbytes + pbytes + 256 * 3 + (((size_t)B * 8 + 255) & ~(size_t)255);
+    hipStream_t s = ctx().stream;
+    char* base = nullptr;
+    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), total));
+    struct Free {
+        char* p;
+        ~Free() { (void)hipFree(p); }
+    } guard{base};
+    char* p = base;
+    const FilterWs fws = filter_workspace(p, B);
+    p += fbytes;
+    float* d_logits = reinterpret_cast<float*>(p);
+    p += lbytes;
+    float* d_seg = reinterpret_cast<float*>(p);
+    p += sbytes;
+    float* d_part = reinterpret_cast<float*>(p);
+    p += pbytes;
+    SampleParams* d_par = reinterpret_cast<SampleParams*>(p);
+    p += 256;
+    float* d_u = reinterpret_cast<float*>(p);
+    p += 256;
+    int* d_tok = reinterpret_cast<int*>(p);
+    p += 256;
+    std::vector<int> h_tok(batch);
+    std::vector<float> h_u(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        float u;
+        ZG_HIP(hipMemcpy(&u, uniforms + b, 4, hipMemcpyDefault));
+        ZG_REQUIRE(u >= 0.0f && u < 1.0f, ZG_ERR_ARG, "debug_sample_rows: uniform %f outside [0,1)", u);
+        h_u[b] = u;
+    }
+    ZG_HIP(hipMemsetAsync(base, 0, fbytes, s));
+    ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemcpyAsync(d_u, h_u.data(), batch * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
+    ZG_TRY(launch_row_max_partials(d_logits, B, V, d_part, n_part, s));
+    if (levels)
+        ZG_TRY(launch_sample_filtered(d_logits, B, V, d_par, levels, d_u, nullptr, d_part, n_part, n_part, d_seg, fws, d_tok, probs_out != nullptr, s));
+    else  // filters off: the existing sampler
+        ZG_TRY(launch_sample(d_logits, B, V, opt->temp, d_u, d_part, n_part, n_part, d_seg, d_tok, probs_out != nullptr, s));
+    ZG_HIP(hipMemcpyAsync(h_tok.data(), d_tok, batch * 4, hipMemcpyDeviceToHost, s));
+    if (probs_out) ZG_HIP(hipMemcpyAsync(probs_out, d_logits, batch * vocab * 4, hipMemcpyDefault, s));
+    if (thresholds_out) {
+        if (levels) ZG_HIP(hipMemcpyAsync(thresholds_out, fws.tau, batch * 4, hipMemcpyDefault, s));
+        else {  // nothing dropped: -inf
+            std::vector<float> ninf(batch, -INFINITY);
+            ZG_HIP(hipMemcpy(thresholds_out, ninf.data(), batch * 4, hipMemcpyDefault));
+        }
+    }
+    ZG_HIP(hipStreamSynchronize(s));
+    for (size_t b = 0; b < batch; ++b) tokens_out[b] = (size_t)h_tok[b];
+    return ZG_OK;
+}
+
+// generate (src/main.zig:322-342) for the prompts of SEVERAL handles at once: independent sequences need not run in lock step
+// (the reference's batch restriction, ops.zig:126-128, lifted the other way): gen_run with one stream per handle
+// (zg_gpt_create_ex: own_stream).
+int zg_gpt_generate_enqueue_many(zg_gpt* const* handles, size_t n_handles, const size_t* prompts, size_t prompt_stride,
+                                 const size_t* prompt_lens, size_t n_steps) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(handles && n_handles >= 1 && n_handles <= 64 && prompts && prompt_lens, ZG_ERR_ARG, "generate_many: bad argument");
+    for (size_t i = 0; i < n_handles; ++i) {
+        ZG_REQUIRE(handles[i] != nullptr, ZG_ERR_ARG, "generate_many: handle %zu is null", i);
+        for (size_t j = 0; j < i; ++j) {
+            ZG_REQUIRE(handles[i] != handles[j], ZG_ERR_ARG, "generate_many: handle %zu is handle %zu", i, j);
+            ZG_REQUIRE(n_handles == 1 || gs(handles[i]) != gs(handles[j]), ZG_ERR_ARG,
+                       "generate_many: handles %zu and %zu share a stream (create them with own_stream)", j, i);
+        }
+    }
+    return gen_run(handles, n_handles, GenRequest(prompts, prompt_stride, prompt_lens, n_steps));
 }
 
 int zg_gpt_generate_fetch_many(zg_gpt* const* handles, size_t n_handles, size_t n_steps, size_t* out_tokens, size_t out_len) {

@@ -610,8 +610,8 @@ int zg_debug_attn_prefill(const float* qkv, uint16_t* out, size_t batch, size_t 
     ZG_REQUIRE(batch >= 1 && n_tokens >= 1 && n_heads >= 1 && n_embed == 64 * n_heads && batch * n_tokens < (1u << 24) && n_embed < (1u << 16) && (!k_cache || ctx_len >= n_tokens) &&
                    key_tiles >= 0 && key_tiles <= 255,
                ZG_ERR_ARG, "debug_attn_prefill: arguments");
-    return launch_attn_prefill(qkv, out, (int)batch, (int)n_tokens, (int)n_embed, (int)n_heads, ws, ws_floats, k_cache, v_cache, (int)ctx_len, ctx().stream,
-                               key_tiles);
+    return launch_attn_prefill(qkv, out, (int)batch, 0, (int)n_tokens, (int)n_embed, (int)n_heads, ws, ws_floats, PrefillKv{k_cache, v_cache, 0, 0, (int)ctx_len},
+                               ctx().stream, key_tiles);
 }
 
 int zg_debug_attn_prefill_at(const float* qkv, uint16_t* out, size_t batch, size_t past_len, size_t n_tokens, size_t n_embed, size_t n_heads,
@@ -623,8 +623,8 @@ int zg_debug_attn_prefill_at(const float* qkv, uint16_t* out, size_t batch, size
     ZG_REQUIRE(batch >= 1 && n_tokens >= 1 && n_heads >= 1 && n_embed == 64 * n_heads && batch * n_tokens < (1u << 24) && n_embed < (1u << 16) &&
                    ctx_len < (1u << 22) && past_len + n_tokens <= ctx_len && kv_mode >= 0 && kv_mode <= 2 && key_tiles >= 0 && key_tiles <= 255,
                ZG_ERR_ARG, "debug_attn_prefill_at: arguments");
-    return launch_attn_prefill_at(qkv, out, (int)batch, (int)past_len, (int)n_tokens, (int)n_embed, (int)n_heads, ws, ws_floats, k_cache, v_cache, kv_mode,
-                                  batch * ctx_len * n_embed * 2, (int)ctx_len, ctx().stream, key_tiles);
+    return launch_attn_prefill(qkv, out, (int)batch, (int)past_len, (int)n_tokens, (int)n_embed, (int)n_heads, ws, ws_floats,
+                               PrefillKv{k_cache, v_cache, kv_mode, batch * ctx_len * n_embed * 2, (int)ctx_len}, ctx().stream, key_tiles);
 }
 
 int zg_debug_prefill_route(int force_kernel, int slices) {

@@ -498,78 +498,36 @@ __global__ __launch_bounds__(256) void attn_prefill_merge_at_kernel(const float*
 
 }  // namespace
 
-// out[M][kSplit E] = split(causal attention of the q / k / v columns of qkv[M][3E]), M = B P rows ordered (b, t).  ws: fp32
-// workspace for the partials of split key ranges (B H P max_splits 66 floats; none needed when every group runs as one range).
-// k_cache / v_cache != null: K and V come from the head-major fp32 caches [b][h][ctx][64] (positions 0 .. P - 1 just appended
-// by the c_attn epilogue) instead of the k / v columns of qkv.
-int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int P, int E, int H, float* ws, size_t ws_floats, const float* k_cache,
-                        const float* v_cache, int ctx, hipStream_t s, int force_tiles) {
+// out[M][kSplit E] = split(causal attention of the P rows of qkv[M][3E] per sequence), M = B P rows ordered (b, t): positions
+// pos0 .. pos0 + P - 1, query t against keys 0 .. pos0 + t.  K and V come from src (zg_kernels.h PrefillKv): the k / v columns of
+// the qkv rows (pos0 = 0 only), or head-major caches [b][h][ctx][64] that hold positions 0 .. pos0 + P - 1, the new rows appended
+// by the c_attn epilogue just before.  ws: fp32 workspace for the partials of split key ranges (B H P max_splits 66 floats; none
+// needed when every group runs as one range).
+int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int pos0, int P, int E, int H, float* ws, size_t ws_floats, const PrefillKv& src,
+                        hipStream_t s, int force_tiles) {
     static bool raised = false;
     if (!raised) {
-        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_prefill_pl_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
+        for (const void* f : {reinterpret_cast<const void*>(&attn_prefill_pl_kernel), reinterpret_cast<const void*>(&attn_prefill_at_kernel<0>),
+                              reinterpret_cast<const void*>(&attn_prefill_at_kernel<1>), reinterpret_cast<const void*>(&attn_prefill_at_kernel<2>)})
+            ZG_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
         raised = true;
     }
     ZG_REQUIRE(E == H * 64, ZG_ERR_UNSUPPORTED, "attention prefill: head_dim must be 64 (n_embed %d, %d heads)", E, H);
-    const int nqb = (P + 31) / 32, ng = (nqb + 3) / 4;
+    const bool cached = src.k != nullptr;
+    if (cached)
+        ZG_REQUIRE(src.v != nullptr && src.fmt >= 0 && src.fmt <= 2 && pos0 >= 0 && P >= 1 && pos0 + P <= src.ctx, ZG_ERR_ARG,
+                   "attention prefill at %d: %d rows, context %d", pos0, P, src.ctx);
+    else
+        ZG_REQUIRE(pos0 == 0 && P >= 1, ZG_ERR_ARG, "attention prefill at %d: %d rows of qkv columns", pos0, P);
+    // the whole-prompt kernel where it can read the rows (fp32, nothing cached in front); else the *_at kernels, also at pos0 = 0
+    const bool whole = pos0 == 0 && (!cached || src.fmt == 0);
+    const int ng = ((P + 31) / 32 + 3) / 4, nkt = (pos0 + P + 31) / 32;
     // key tiles per workgroup: whole rows once there is a group per CU (measured at 12 heads x 1023 tokens, tools/bench_attn_prefill.py:
     // 4 / 5 sequences = 384 / 480 groups run 57 / 66 us whole against 62 / 75 us cut in two with the merge kernel behind; 3 sequences
     // are even, 2 are faster cut), else ranges of >= 4 tiles chosen so that the launch fills the chip about twice (2 workgroups fit a
-    // CU) — as long as the partials fit the workspace
-    int nts = 32 * ((nqb + 31) / 32);
-    {
-        const long groups = (long)B * H * ng;
-        if (force_tiles > 0) nts = force_tiles;
-        else
-            for (int cand = nts; cand >= 4; cand /= 2) {
-                long wgs = 0;
-                for (int g = 0; g < ng; ++g) wgs += group_splits(g, nqb, cand);
-                nts = cand;
-                if (wgs * B * H >= 512 || groups >= 256) break;
-            }
-        if (nts > 255) nts = 255;
-    }
-    int max_s = group_splits(ng - 1, nqb, nts);
-    if (max_s > 1 && (ws == nullptr || (size_t)B * H * P * max_s * 66 > ws_floats)) {  // no room for partials: whole rows
-        nts = nqb < 255 ? nqb : 255;
-        max_s = group_splits(ng - 1, nqb, nts);
-        ZG_REQUIRE(max_s == 1, ZG_ERR_UNSUPPORTED, "attention prefill: %d positions without a workspace", P);
-    }
-    ZG_REQUIRE(ng < 65536 && max_s < 256, ZG_ERR_UNSUPPORTED, "attention prefill: %d positions", P);
-    const unsigned geo = (unsigned)nts | ((unsigned)max_s << 8) | ((unsigned)ng << 16);
-    AttnKv kv;
-    if (k_cache != nullptr) {  // head-major fp32 caches [b][h][ctx][64]
-        kv = AttnKv{reinterpret_cast<const char*>(k_cache), reinterpret_cast<const char*>(v_cache), (size_t)H * ctx * 256, (size_t)ctx * 256, 256u};
-    } else {  // the k / v columns of the qkv rows
-        kv = AttnKv{reinterpret_cast<const char*>(qkv + E), reinterpret_cast<const char*>(qkv + 2 * E), (size_t)P * 3 * E * 4, (size_t)256, (unsigned)(3 * E * 4)};
-    }
-    ZG_REQUIRE((size_t)P * kv.stride_t < ((size_t)1 << 31), ZG_ERR_SHAPE, "attention prefill: rows beyond a 32-bit buffer descriptor");
-    hipLaunchKernelGGL(attn_prefill_pl_kernel, dim3(H, B, ng * max_s), dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv);
-    ZG_HIP(hipGetLastError());
-    if (max_s > 1) {
-        const size_t n = (size_t)B * H * P * 16;
-        hipLaunchKernelGGL(attn_prefill_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, out, P, E, H, B, geo);
-        ZG_HIP(hipGetLastError());
-    }
-    return ZG_OK;
-}
-
-// The same for a continuation: qkv holds the P new rows of every sequence (positions pos0 .. pos0 + P - 1; only their q columns
-// are read), the head-major caches [b][h][ctx][64] hold positions 0 .. pos0 + P - 1 in storage format kv_mode (0 fp32, 1 fp16,
-// 2 B24 with its byte plane kv_lo bytes behind the bf16 plane) — the new rows appended by the c_attn epilogue just before.
-int launch_attn_prefill_at(const float* qkv, bf16_t* out, int B, int pos0, int P, int E, int H, float* ws, size_t ws_floats, const void* k_cache,
-                           const void* v_cache, int kv_mode, size_t kv_lo, int ctx, hipStream_t s, int force_tiles) {
-    static bool raised = false;
-    if (!raised) {
-        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_prefill_at_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
-        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_prefill_at_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
-        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_prefill_at_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
-        raised = true;
-    }
-    ZG_REQUIRE(E == H * 64, ZG_ERR_UNSUPPORTED, "attention prefill: head_dim must be 64 (n_embed %d, %d heads)", E, H);
-    ZG_REQUIRE(k_cache != nullptr && v_cache != nullptr && kv_mode >= 0 && kv_mode <= 2 && pos0 >= 0 && P >= 1 && pos0 + P <= ctx, ZG_ERR_ARG,
-               "attention prefill at %d: %d rows, context %d", pos0, P, ctx);
-    const int nqb = (P + 31) / 32, ng = (nqb + 3) / 4, nkt = (pos0 + P + 31) / 32;
-    // key tiles per workgroup by the whole-prompt kernel's rule (launch_attn_prefill), over the rectangle's own split counts
+    // CU) — as long as the partials fit the workspace.  One planner for both kernels: at pos0 = 0 it is the whole-prompt kernel's own
+    // (group_tiles), since group_tiles_at(g, P, 0) = (min(128 (g + 1), P) + 31) / 32 = min(4 g + 4, ceil(P / 32)) = group_tiles(g, nqb)
+    // and nkt = nqb.
     int nts = 32 * ((nkt + 31) / 32);
     {
         const long groups = (long)B * H * ng;
@@ -591,17 +549,25 @@ int launch_attn_prefill_at(const float* qkv, bf16_t* out, int B, int pos0, int P
     }
     ZG_REQUIRE(ng < 65536 && max_s < 256, ZG_ERR_UNSUPPORTED, "attention prefill: %d positions", pos0 + P);
     const unsigned geo = (unsigned)nts | ((unsigned)max_s << 8) | ((unsigned)ng << 16);
-    const unsigned row = kv_mode == 0 ? 256u : 128u;
-    const AttnKv kv{reinterpret_cast<const char*>(k_cache), reinterpret_cast<const char*>(v_cache), (size_t)H * ctx * row, (size_t)ctx * row, row};
-    ZG_REQUIRE((size_t)(pos0 + P + 128) * kv.stride_t < ((size_t)1 << 31), ZG_ERR_SHAPE, "attention prefill: rows beyond a 32-bit buffer descriptor");
+    AttnKv kv;
+    if (cached) {
+        const unsigned row = src.fmt == 0 ? 256u : 128u;
+        kv = AttnKv{static_cast<const char*>(src.k), static_cast<const char*>(src.v), (size_t)H * src.ctx * row, (size_t)src.ctx * row, row};
+    } else {
+        kv = AttnKv{reinterpret_cast<const char*>(qkv + E), reinterpret_cast<const char*>(qkv + 2 * E), (size_t)P * 3 * E * 4, (size_t)256, (unsigned)(3 * E * 4)};
+    }
+    // (the kernels address a (sequence, head)'s rows through 32-bit buffer descriptors; the *_at ones read up to a group past the end)
+    ZG_REQUIRE((size_t)(whole ? P : pos0 + P + 128) * kv.stride_t < ((size_t)1 << 31), ZG_ERR_SHAPE, "attention prefill: rows beyond a 32-bit buffer descriptor");
     const dim3 grid(H, B, ng * max_s);
-    if (kv_mode == 0) hipLaunchKernelGGL(attn_prefill_at_kernel<0>, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv, kv_lo, pos0);
-    else if (kv_mode == 1) hipLaunchKernelGGL(attn_prefill_at_kernel<1>, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv, kv_lo, pos0);
-    else hipLaunchKernelGGL(attn_prefill_at_kernel<2>, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv, kv_lo, pos0);
+    if (whole) hipLaunchKernelGGL(attn_prefill_pl_kernel, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv);
+    else if (src.fmt == 0) hipLaunchKernelGGL(attn_prefill_at_kernel<0>, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv, src.kv_lo, pos0);
+    else if (src.fmt == 1) hipLaunchKernelGGL(attn_prefill_at_kernel<1>, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv, src.kv_lo, pos0);
+    else hipLaunchKernelGGL(attn_prefill_at_kernel<2>, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv, src.kv_lo, pos0);
     ZG_HIP(hipGetLastError());
     if (max_s > 1) {
-        const size_t n = (size_t)B * H * P * 16;
-        hipLaunchKernelGGL(attn_prefill_merge_at_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, out, P, E, H, B, geo, pos0);
+        const dim3 mgrid((unsigned)(((size_t)B * H * P * 16 + 255) / 256));
+        if (whole) hipLaunchKernelGGL(attn_prefill_merge_kernel, mgrid, dim3(256), 0, s, ws, out, P, E, H, B, geo);
+        else hipLaunchKernelGGL(attn_prefill_merge_at_kernel, mgrid, dim3(256), 0, s, ws, out, P, E, H, B, geo, pos0);
         ZG_HIP(hipGetLastError());
     }
     return ZG_OK;

@@ -259,14 +259,20 @@ int launch_prefill_gemm(const bf16_t* A, const bf16_t* W, const float* bias, voi
                                                // kWeightPlanes: W is the plane-major three-term split [3][N][K] of an fp32 matrix
 constexpr int kWeightPlanes = 33;
 void prefill_force_route(int kernel, int slices);  // zg_debug_prefill_route / _linear: pin the GEMM family (1 gemm_s4, 2 the 128-row kernels) and the K slices
-// out[M][kSplit E] = split(causal attention of the q / k / v columns of qkv[M][3E]), M = B P rows ordered (b, t)
-// (attn_prefill.hip: bf16 matrix cores on exact plane splits; ws = fp32 workspace for the partials of split key ranges)
-int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int P, int E, int H, float* ws, size_t ws_floats, const float* k_cache_or_null,
-                        const float* v_cache_or_null, int ctx, hipStream_t s, int force_tiles = 0);  // force_tiles: key tiles per workgroup (tests)
-// ... of the P new rows of a continuation (positions pos0 .. pos0 + P - 1; qkv holds those rows only, their q columns are read)
-// against caches that hold positions 0 .. pos0 + P - 1 in storage format kv_mode (0 fp32, 1 fp16, 2 B24 with kv_lo)
-int launch_attn_prefill_at(const float* qkv, bf16_t* out, int B, int pos0, int P, int E, int H, float* ws, size_t ws_floats, const void* k_cache,
-                           const void* v_cache, int kv_mode, size_t kv_lo, int ctx, hipStream_t s, int force_tiles = 0);
+// Where the prompt attention reads K and V: the k / v columns of the qkv rows (k == nullptr; a whole prompt only), or head-major
+// caches [b][h][ctx][64] in storage format fmt (0 fp32, 1 fp16, 2 B24 with its byte plane kv_lo bytes behind the bf16 plane)
+struct PrefillKv {
+    const void* k = nullptr;
+    const void* v = nullptr;
+    int fmt = 0;
+    size_t kv_lo = 0;
+    int ctx = 0;
+};
+// out[M][kSplit E] = split(causal attention of the P rows per sequence of qkv[M][3E]), M = B P rows ordered (b, t), at positions
+// pos0 .. pos0 + P - 1 behind pos0 cached ones (attn_prefill.hip: bf16 matrix cores on exact plane splits; ws = fp32 workspace for
+// the partials of split key ranges; force_tiles: key tiles per workgroup, tests)
+int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int pos0, int P, int E, int H, float* ws, size_t ws_floats, const PrefillKv& kv,
+                        hipStream_t s, int force_tiles = 0);
 
 // GPT.sample tail: in-place softmax(logits / temp) per sequence + inverse-CDF draw with uniform u[b].
 // part_val / n_part / part_stride: the per-workgroup maxima lm_head's argmax epilogue left (the row maximum without a pass over the

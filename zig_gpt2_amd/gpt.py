@@ -15,6 +15,19 @@ from ._lib import check, ptr
 from .synth import GPTConfig
 
 
+def _pack_prompts(prompts, rows):
+    """`rows` prompts of any lengths -> (tokens [rows, stride] padded with zeros, lengths [rows], stride)."""
+    prompts = [np.atleast_1d(np.asarray(p, dtype=np.uint64)) for p in prompts]
+    assert len(prompts) == rows
+    stride = max(len(p) for p in prompts)
+    mat = np.zeros((rows, stride), np.uint64)
+    lens = np.zeros(rows, np.uint64)
+    for b, p in enumerate(prompts):
+        mat[b, : len(p)] = p
+        lens[b] = len(p)
+    return mat, lens, stride
+
+
 class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
@@ -95,12 +108,13 @@ class GPT:
         return w.value, kv.value
 
     # ------------------------------------------------------------------ GPT.forward / sample
+    def _logits_buf(self, compute_logits, want_logits):
+        return np.empty((self.batch, self.config.vocab_size), np.float32) if compute_logits and want_logits else None
+
     def forward(self, seq_len, tokens, compute_logits=True, want_logits=True):
         """GPT.forward (src/main.zig:178-195) for `batch` sequences; returns logits [batch, V] or None."""
         tokens = np.ascontiguousarray(np.atleast_1d(tokens), dtype=np.uint64)
-        logits = None
-        if compute_logits and want_logits:
-            logits = np.empty((self.batch, self.config.vocab_size), np.float32)
+        logits = self._logits_buf(compute_logits, want_logits)
         check(self._L.zg_gpt_forward(self.h, seq_len, ptr(tokens), tokens.size, int(compute_logits), ptr(logits),
                                      ops._n(logits)))
         return logits
@@ -110,9 +124,7 @@ class GPT:
         0..n-1; returns the logits of position n-1 ([batch, V]) or None."""
         tokens = np.ascontiguousarray(np.atleast_2d(tokens), dtype=np.uint64)
         assert tokens.shape[0] == self.batch
-        logits = None
-        if compute_logits and want_logits:
-            logits = np.empty((self.batch, self.config.vocab_size), np.float32)
+        logits = self._logits_buf(compute_logits, want_logits)
         check(self._L.zg_gpt_prefill(self.h, ptr(tokens), tokens.shape[1], tokens.shape[1], int(compute_logits),
                                      ptr(logits), ops._n(logits)))
         return logits
@@ -128,16 +140,19 @@ class GPT:
         ones in one pass; returns the logits of the last new position ([batch, V]) or None.  past_len below cached_len() rolls back."""
         tokens = np.ascontiguousarray(np.atleast_2d(tokens), dtype=np.uint64)
         assert tokens.shape[0] == self.batch
-        logits = None
-        if compute_logits and want_logits:
-            logits = np.empty((self.batch, self.config.vocab_size), np.float32)
+        logits = self._logits_buf(compute_logits, want_logits)
         check(self._L.zg_gpt_extend(self.h, past_len, ptr(tokens), max(tokens.shape[1], 1), tokens.shape[1], int(compute_logits), ptr(logits),
                                     ops._n(logits)))
         return logits
 
-    @staticmethod
-    def _truncated(top_k, top_p):
-        return top_k != 0 or top_p != 1.0
+    def _sampled(self, name, suffix, head, temp, top_k, top_p, tail):
+        """zg_gpt_<name><suffix>(h, *head, temp, *tail) while no filter is on (the defaults take the plain entry point itself),
+        else its _ex twin with zg_sample_options in temp's place."""
+        if top_k == 0 and top_p == 1.0:
+            check(getattr(self._L, f"zg_gpt_{name}{suffix}")(self.h, *head, temp, *tail))
+        else:
+            opt = _lib.SampleOptions(temp, top_k, top_p)
+            check(getattr(self._L, f"zg_gpt_{name}_ex{suffix}")(self.h, *head, C.addressof(opt), *tail))
 
     def sample(self, seq_len, tokens, temp, uniforms=None, seed=0, want_probs=False, top_k=0, top_p=1.0):
         """GPT.sample (src/main.zig:198-207) with reproducible uniforms; returns tokens [batch] (and probs).  top_k / top_p:
@@ -146,13 +161,7 @@ class GPT:
         u = None if uniforms is None else np.ascontiguousarray(np.atleast_1d(uniforms), dtype=np.float32)
         out = np.zeros(self.batch, np.uint64)
         probs = np.empty((self.batch, self.config.vocab_size), np.float32) if want_probs else None
-        if self._truncated(top_k, top_p):
-            opt = _lib.SampleOptions(temp, top_k, top_p)
-            check(self._L.zg_gpt_sample_ex(self.h, seq_len, ptr(tokens), tokens.size, C.addressof(opt), ptr(u), seed, ptr(out), ptr(probs),
-                                           ops._n(probs)))
-        else:
-            check(self._L.zg_gpt_sample(self.h, seq_len, ptr(tokens), tokens.size, temp, ptr(u), seed, ptr(out), ptr(probs),
-                                        ops._n(probs)))
+        self._sampled("sample", "", (seq_len, ptr(tokens), tokens.size), temp, top_k, top_p, (ptr(u), seed, ptr(out), ptr(probs), ops._n(probs)))
         return (out, probs) if want_probs else out
 
     def argmax(self):
@@ -167,15 +176,7 @@ class GPT:
 
     # ------------------------------------------------------------------ generate
     def _prompts(self, prompts):
-        prompts = [np.atleast_1d(np.asarray(p, dtype=np.uint64)) for p in prompts]
-        assert len(prompts) == self.batch
-        stride = max(len(p) for p in prompts)
-        mat = np.zeros((self.batch, stride), np.uint64)
-        lens = np.zeros(self.batch, np.uint64)
-        for b, p in enumerate(prompts):
-            mat[b, : len(p)] = p
-            lens[b] = len(p)
-        return mat, lens, stride
+        return _pack_prompts(prompts, self.batch)
 
     def generate(self, prompts, n_steps):
         """generate (src/main.zig:322-342), greedy; returns tokens [batch, n_steps]."""
@@ -214,20 +215,12 @@ class GPT:
         loop on the device; the tokens of the host loop over `sample(T, tok, temp, seed=seed)`.  top_k / top_p: as `sample`."""
         mat, lens, stride = self._prompts(prompts)
         out = np.zeros((self.batch, n_steps), np.uint64)
-        if self._truncated(top_k, top_p):
-            opt = _lib.SampleOptions(temp, top_k, top_p)
-            check(self._L.zg_gpt_generate_sample_ex(self.h, ptr(mat), stride, ptr(lens), n_steps, C.addressof(opt), seed, ptr(out), out.size))
-        else:
-            check(self._L.zg_gpt_generate_sample(self.h, ptr(mat), stride, ptr(lens), n_steps, temp, seed, ptr(out), out.size))
+        self._sampled("generate_sample", "", (ptr(mat), stride, ptr(lens), n_steps), temp, top_k, top_p, (seed, ptr(out), out.size))
         return out
 
     def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0):
         mat, lens, stride = self._prompts(prompts)
-        if self._truncated(top_k, top_p):
-            opt = _lib.SampleOptions(temp, top_k, top_p)
-            check(self._L.zg_gpt_generate_sample_ex_enqueue(self.h, ptr(mat), stride, ptr(lens), n_steps, C.addressof(opt), seed))
-        else:
-            check(self._L.zg_gpt_generate_sample_enqueue(self.h, ptr(mat), stride, ptr(lens), n_steps, temp, seed))
+        self._sampled("generate_sample", "_enqueue", (ptr(mat), stride, ptr(lens), n_steps), temp, top_k, top_p, (seed,))
 
     PROFILE_CLASSES = ["embed", "ln1_c_attn_kv", "attention", "merge_attn_proj_resid", "ln2_c_fc_gelu",
                        "mlp_proj_resid", "lnf_lm_head_argmax", "step_total"]
@@ -300,19 +293,8 @@ class GPTGroups:
     def load_weights(self, weights):
         self.members[0].load_weights(weights)
 
-    def _prompts(self, prompts):
-        prompts = [np.atleast_1d(np.asarray(p, dtype=np.uint64)) for p in prompts]
-        assert len(prompts) == self.n_prompts
-        stride = max(len(p) for p in prompts)
-        mat = np.zeros((self.n_prompts, stride), np.uint64)
-        lens = np.zeros(self.n_prompts, np.uint64)
-        for b, p in enumerate(prompts):
-            mat[b, : len(p)] = p
-            lens[b] = len(p)
-        return mat, lens, stride
-
     def generate_enqueue(self, prompts, n_steps):
-        mat, lens, stride = self._prompts(prompts)
+        mat, lens, stride = _pack_prompts(prompts, self.n_prompts)
         check(self._L.zg_gpt_generate_enqueue_many(self._harr, self.groups, ptr(mat), stride, ptr(lens), n_steps))
 
     def generate_fetch(self, n_steps):
