@@ -219,6 +219,10 @@ enum {
     ZG_GPT_TRUNCATED_GENERATE = 1 << 9, /* capture the decode graphs of zg_gpt_generate_sample_ex_* (top-k / top-p truncation) at
                                       create as well (otherwise a truncated generation captures those of the buckets it
                                       touches when it begins, before its first step: the one place such a call may allocate) */
+    ZG_GPT_PENALIZED_GENERATE = 1 << 10, /* capture the decode graphs of zg_gpt_generate_pen_enqueue (logit penalties in front of the
+                                      sampler, all three sampler forms) at create as well (otherwise a penalised generation
+                                      captures those of the buckets it touches when it begins, before its first step: the one
+                                      place such a call may allocate).  context_size > 8192: ZG_ERR_UNSUPPORTED */
     ZG_GPT_WEIGHTS_B24 = 1 << 8  /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
                                     value rounded to nearest even at 16 mantissa bits (never to inf), row r of an [out][in]
                                     matrix = [in bf16-shaped upper halves | in low bytes].  3/4 of fp32's weight bytes, 2^-17
@@ -385,6 +389,52 @@ int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_st
  * absolute T, b)).  past_len + n_steps <= context_size.  Works on ZG_GPT_NO_PREFILL handles (through the decode loop). */
 int zg_gpt_generate_from_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens,
                                  size_t n_steps, const zg_sample_options* options_or_null, uint64_t seed);
+/* ---- Penalties on tokens the sequence already holds, the same for every row of a call.  Let x be a logit of a row
+ * and c the number of times its index occurs in that row's history:
+ *   c == 0: x is untouched, bit for bit.
+ *   c >= 1: y = (x > 0 ? x / repetition : x * repetition); y = y - (presence + frequency * (float)c) — four separately rounded fp32
+ *           operations, the division correctly rounded, nothing contracted into an fma: bitwise the same expression in numpy
+ *           float32.  -0.0, +0.0 and negative logits take the product; a NaN logit stays NaN.
+ * Each distinct token is penalised exactly once however often it occurs (HF's gather-and-scatter; repetition is the CTRL / HF
+ * repetition_penalty, presence and frequency are the OpenAI-style pair).  Counts are exact integers: the same inputs give the same
+ * tokens on every run.  The penalties act on the raw logits, before temperature, top-k and top-p (HF's order); everything behind
+ * them is the sampler of zg_gpt_sample_ex on the penalised row.  repetition > 0 (1: off), presence and frequency finite (0: off),
+ * else ZG_ERR_ARG.  All three off: the call is exactly its unpenalised twin — identical tokens and probabilities, no launch added, the
+ * same graphs.  A history can hold at most context_size tokens, and the counting kernel keeps a row's distinct tokens in an LDS table
+ * of twice that many slots: handles with context_size > 8192 get ZG_ERR_UNSUPPORTED from these entry points (every GPT-2: 1024). */
+typedef struct {
+    float repetition; /* > 0; 1 = off.  CTRL / HF: x > 0 ? x / r : x * r */
+    float presence;   /* 0 = off.  x -= presence for a token that occurs in the history */
+    float frequency;  /* 0 = off.  x -= frequency * count */
+} zg_logit_penalties;
+/* zg_gpt_sample_ex with the penalty stage in front.  The caller passes the history: history [batch][history_stride] (host),
+ * history_lens[b] tokens of row b (history may be NULL when every length is 0).  options and penalties must be non-NULL; greedy
+ * picking with penalties is top_k = 1.  NULL or bad penalties: ZG_ERR_ARG; a length beyond history_stride or context_size, or a
+ * token >= vocab: ZG_ERR_SHAPE — before anything is enqueued and before the handle's state (zg_gpt_cached_len included) is touched.
+ * zg_gpt_argmax behind this call is the argmax of the penalised row. */
+int zg_gpt_sample_pen(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* options,
+                      const zg_logit_penalties* penalties, const size_t* history, size_t history_stride, const size_t* history_lens,
+                      const float* uniforms, uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len);
+/* zg_gpt_generate_from_enqueue with penalties (past_len == 0: a fresh generation; the same rules for past_len, rollback and n_steps).
+ * When the pick of step s is drawn, the history of row b is prior[b] followed by the tokens recorded at positions past_len .. s - 1:
+ * the row's new prompt tokens and every pick so far.  The reference's second feeding of the last prompt token (main.zig:334,337) is
+ * not a second occurrence.  Tokens recorded below past_len by earlier calls are not read: a caller who wants them (the second turn
+ * of a conversation) passes them as prior [batch][prior_stride] (host), prior_lens[b] tokens of row b; both NULL: no prior.
+ * prior_lens[b] <= prior_stride and prior_lens[b] + n_steps <= context_size (the history never outgrows the context), tokens <
+ * vocab, else ZG_ERR_SHAPE; bad options / penalties: ZG_ERR_ARG — all before anything is enqueued or the handle's state is touched.
+ * Returns exactly the tokens of the host loop over T of zg_gpt_sample_pen(g, T, &tok, ..., history = prior ++ the tokens recorded
+ * on [past_len, T - 1), NULL, seed, ...) that feeds the row's own prompt token while the prompt lasts.  The penalty stage is a node
+ * of the captured step (graphs of their own: ZG_GPT_PENALIZED_GENERATE); values, past_len and prior live in device memory, so one
+ * graph serves them all.  Does not allocate beyond that capture.  Results through zg_gpt_generate_fetch / _fetch_range. */
+int zg_gpt_generate_pen_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens,
+                                size_t n_steps, const zg_sample_options* options, const zg_logit_penalties* penalties,
+                                const size_t* prior_or_null, size_t prior_stride, const size_t* prior_lens_or_null, uint64_t seed);
+/* Test entry: the penalty kernels alone on the caller's rows, logits [batch <= 64, vocab <= 262144] (host or device, as logits_out
+ * and counts_out [batch, vocab]: how often each index occurs in its row's history; may be NULL); history and history_lens are host
+ * arrays as for zg_gpt_sample_pen, a history of more than 8192 tokens is ZG_ERR_UNSUPPORTED.  Needs zg_init only.  Allocates its
+ * workspace per call. */
+int zg_debug_penalize_rows(const float* logits, size_t batch, size_t vocab, const zg_logit_penalties* penalties, const size_t* history,
+                           size_t history_stride, const size_t* history_lens, float* logits_out, unsigned* counts_out_or_null);
 /* tokens of positions first .. first + n - 1 of the last generation(s): out_tokens [batch, n] */
 int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len);
 /* Test entry: the sampler kernels of zg_gpt_sample_ex on the caller's logits [batch <= 64, vocab <= 262144] (host or device, as

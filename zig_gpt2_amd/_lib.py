@@ -38,6 +38,12 @@ class SampleOptions(C.Structure):
     _fields_ = [("temp", C.c_float), ("top_k", sz), ("top_p", C.c_float)]
 
 
+class LogitPenalties(C.Structure):
+    """zg_logit_penalties of include/zgpt2.h."""
+
+    _fields_ = [("repetition", C.c_float), ("presence", C.c_float), ("frequency", C.c_float)]
+
+
 class GptOptions(C.Structure):
     """zg_gpt_options of include/zgpt2.h."""
 
@@ -108,6 +114,9 @@ SIGNATURES = {
     "zg_gpt_generate_sample_ex_enqueue": (C.c_int, [vp, vp, sz, vp, sz, vp, C.c_uint64]),
     "zg_gpt_generate_sample_ex": (C.c_int, [vp, vp, sz, vp, sz, vp, C.c_uint64, vp, sz]),
     "zg_debug_sample_rows": (C.c_int, [vp, sz, sz, vp, vp, vp, vp, vp]),
+    "zg_gpt_sample_pen": (C.c_int, [vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, C.c_uint64, vp, vp, sz]),
+    "zg_gpt_generate_pen_enqueue": (C.c_int, [vp, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp, C.c_uint64]),
+    "zg_debug_penalize_rows": (C.c_int, [vp, sz, sz, vp, vp, sz, vp, vp, vp]),
     "zg_gpt_time_kernel": (C.c_int, [vp, C.c_int, C.c_int, f32p, szp]),
     "zg_gpt_profile_step": (C.c_int, [vp, sz, C.c_int, f32p, sz]),
     "zg_debug_prefetch_stats": (C.c_int, [vp, vp, sz]),
@@ -123,6 +132,7 @@ GPT_KV_B24 = 64
 GPT_SAMPLED_GENERATE = 128
 GPT_WEIGHTS_B24 = 256
 GPT_TRUNCATED_GENERATE = 512
+GPT_PENALIZED_GENERATE = 1024
 BLOCK_SLOTS = ["ln_1_g", "ln_1_b", "c_attn_w", "c_attn_b", "c_proj_w", "c_proj_b",
                "ln_2_g", "ln_2_b", "c_fc_w", "c_fc_b", "mlp_proj_w", "mlp_proj_b"]
 TOP_SLOTS = ["wte", "wpe", "ln_f_g", "ln_f_b"]

@@ -5,7 +5,7 @@
 // position, tokens and argmax all live in device memory, so a whole greedy generation is enqueued
 // without a host round trip per token.  Three things exist once each: the whole-prompt pass (pass_impl: zg_gpt_prefill is
 // zg_gpt_extend at 0), the generation request (GenRequest, run by gen_run for every zg_gpt_generate*_enqueue) and the shape of a
-// decode step (StepKey {with_logits, multi, SamplerMode}: what enqueue_step launches and which graph replays it).
+// decode step (StepKey {with_logits, multi, SamplerMode, pen}: what enqueue_step launches and which graph replays it).
 //
 // HBM layout (one hipMalloc, 256-B aligned sub-buffers):
 //   [ weights: wte | wpe | ln_f | per layer: c_attn_w c_proj_w c_fc_w mlp_proj_w + fp32 vectors ]
@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <string>
 #include <thread>
 #include <vector>
@@ -108,6 +109,12 @@ struct zg_gpt {
     SampleParams* h_samp;     // pinned mirror
     SamplerMode gen_mode;     // how the generation in flight chooses its tokens
     FilterWs filt;            // selection workspace of the truncated sampler (sample_filter.h), zero at create
+    // logit penalties (sample_penalty.h): the caller's prior / explicit history [batch][ctx] with its lengths, the values
+    // of the call in flight, their pinned mirrors (h_prior: [batch * ctx] tokens, then [batch] lengths).  The kernels' table is LDS: no workspace
+    int *prior, *prior_len;
+    PenParams *pen, *h_pen;
+    int* h_prior;
+    bool gen_pen;             // the generation in flight penalises its logits
     size_t graph_steps;
     hipStream_t graph_stream;
     size_t steps_enqueued;
@@ -230,6 +237,9 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
     g->samp = (SampleParams*)P(sizeof(SampleParams));
     g->samp_ws = (float*)P(sample_workspace_floats((int)B) * 4);
     g->filt = filter_workspace(P(filter_workspace_bytes((int)B)), (int)B);
+    g->prior = (int*)P(B * C * 4);
+    g->prior_len = (int*)P(B * 4);
+    g->pen = (PenParams*)P(sizeof(PenParams));
     g->xp = (bf16_t*)P(E * 48);
     g->hp = (bf16_t*)P(4 * E * 48);
     g->ap = (bf16_t*)P(E * 48);
@@ -553,7 +563,24 @@ struct StepOpts {
     // layer, so that consecutive launches of the chain never find each other's tags
     int salt = -1;
     SamplerMode sampler = GREEDY;  // what follows lm_head (with_logits only)
+    bool pen = false;              // the penalty stage between lm_head and the sampler (a sampler only)
 };
+
+// The history the penalty stage of a handle reads: the prior buffer alone (zg_gpt_sample_pen: the caller's explicit history), or
+// followed by the generate loop's own record from PenParams.past_len on
+PenHistory pen_history(const zg_gpt* g, bool loop) {
+    PenHistory h{};
+    h.prior = g->prior;
+    h.prior_len = g->prior_len;
+    h.prior_stride = (int)g->cfg.context_size;
+    if (loop) {
+        h.rec = g->out_tokens;
+        h.rec_stride = (int)g->cfg.context_size;
+        h.ctrl = g->ctrl;
+    }
+    h.max_hist = (int)g->cfg.context_size;  // (the entry points hold prior + recorded tokens to the context)
+    return h;
+}
 
 // One decode step = GPT.forward (main.zig:178-195) for all sequences.
 int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const StepOpts& o = StepOpts()) {
@@ -630,6 +657,9 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
     }
     // GPT.sample's tail (main.zig:200-206) on the logits of this step: the next step's embed kernel feeds what it draws (mode 2)
     if (o.sampler == GREEDY || !with_logits || only >= 0 || rec) return ZG_OK;
+    // the penalties act on the raw logits (HF's order); the row-maximum partials both samplers start from are rebuilt behind them
+    if (o.pen)
+        ZG_TRY(launch_penalize(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->pen, pen_history(g, true), g->part_val, g->part_idx, g->lm_grid, nullptr, s));
     if (const int levels = filter_launches(o.sampler))
         ZG_TRY(launch_sample_filtered(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, levels, nullptr, g->ctrl, g->part_val, g->lm_grid,
                                       g->lm_grid, g->samp_ws, g->filt, g->sampled, false, s));
@@ -831,14 +861,19 @@ size_t prefill_min() { return 4; }  // shorter prompts go through the decode cha
 //   multi        graph_steps consecutive steps (all with lm_head, all in one bucket) as ONE graph: the position lives in device
 //                memory, so the same kernels simply repeat; saves the gap between graph launches in the generate loop
 //   sampler      the sampler node(s) behind lm_head (zg_gpt_generate_sample_*; the option values are read on the device)
-// multi and a sampler imply with_logits: 9 shapes exist.  Captured at create — the sampled ones with ZG_GPT_SAMPLED_GENERATE /
-// ZG_GPT_TRUNCATED_GENERATE, otherwise when the first generation that needs them begins.
+//   pen          the penalty stage in front of the sampler node(s) (zg_gpt_generate_pen_enqueue; a sampler only)
+// multi and a sampler imply with_logits: 15 shapes exist.  Captured at create — the sampled ones with ZG_GPT_SAMPLED_GENERATE /
+// ZG_GPT_TRUNCATED_GENERATE / ZG_GPT_PENALIZED_GENERATE, otherwise when the first generation that needs them begins.
 struct StepKey {
     bool with_logits, multi;
     SamplerMode sampler;
+    bool pen = false;
 };
-constexpr size_t kStepShapes = 9;
-size_t step_index(StepKey k) { return k.sampler != GREEDY ? 1 + 2 * (size_t)k.sampler + k.multi : k.multi ? 2 : k.with_logits; }
+constexpr size_t kStepShapes = 15;
+size_t step_index(StepKey k) {
+    if (k.sampler == GREEDY) return k.multi ? 2 : k.with_logits;
+    return (k.pen ? 7 : 1) + 2 * (size_t)k.sampler + k.multi;
+}
 
 size_t bucket_of(size_t seq_len) { return (seq_len + 63) / 64 - 1; }
 
@@ -872,6 +907,7 @@ int graph_exec(zg_gpt* g, StepKey k, size_t b, hipStream_t s, hipGraphExec_t* ou
         const size_t n_steps = k.multi ? g->graph_steps : 1;
         StepOpts o;
         o.sampler = k.sampler;
+        o.pen = k.pen;
         ZG_TRY(capture_graph(s, &e, [&] {
             int st = ZG_OK;
             for (size_t i = 0; i < n_steps && st == ZG_OK; ++i) st = enqueue_step(g, k.with_logits, t_hi, s, o);
@@ -883,11 +919,11 @@ int graph_exec(zg_gpt* g, StepKey k, size_t b, hipStream_t s, hipGraphExec_t* ou
 }
 
 // The single-step and (where the handle has them) multi-step graphs of a sampler mode, buckets b0 .. b1
-int capture_sampled(zg_gpt* g, SamplerMode mode, size_t b0, size_t b1, hipStream_t s) {
+int capture_sampled(zg_gpt* g, SamplerMode mode, bool pen, size_t b0, size_t b1, hipStream_t s) {
     hipGraphExec_t e;
     for (size_t b = b0; b <= b1 && b < g->n_buckets; ++b) {
-        ZG_TRY(graph_exec(g, {true, false, mode}, b, s, &e));
-        if (g->graph_steps > 1) ZG_TRY(graph_exec(g, {true, true, mode}, b, s, &e));
+        ZG_TRY(graph_exec(g, {true, false, mode, pen}, b, s, &e));
+        if (g->graph_steps > 1) ZG_TRY(graph_exec(g, {true, true, mode, pen}, b, s, &e));
     }
     return ZG_OK;
 }
@@ -907,25 +943,29 @@ int capture_all(zg_gpt* g, hipStream_t s) {
     }
     if (g->graph_steps > 1)
         for (size_t b = 0; b < g->n_buckets; ++b) ZG_TRY(graph_exec(g, {true, true, GREEDY}, b, s, &e));
-    if (g->flags & ZG_GPT_SAMPLED_GENERATE) ZG_TRY(capture_sampled(g, PLAIN, 0, g->n_buckets - 1, s));
+    if (g->flags & ZG_GPT_SAMPLED_GENERATE) ZG_TRY(capture_sampled(g, PLAIN, false, 0, g->n_buckets - 1, s));
     if (g->flags & ZG_GPT_TRUNCATED_GENERATE)
-        for (SamplerMode m : {ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, 0, g->n_buckets - 1, s));
+        for (SamplerMode m : {ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, false, 0, g->n_buckets - 1, s));
+    if (g->flags & ZG_GPT_PENALIZED_GENERATE)
+        for (SamplerMode m : {PLAIN, ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, true, 0, g->n_buckets - 1, s));
     return ZG_OK;
 }
 
 // Run one decode step at sequence length seq_len: replay the graph of its bucket, or launch eagerly when graphs
 // are disabled / the stream cannot be captured.
-int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, SamplerMode sampler = GREEDY) {
+int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, SamplerMode sampler = GREEDY, bool pen = false) {
     ZG_TRY(ensure_ln_folded(g, s));
     if (!with_logits) sampler = GREEDY;  // (nothing to draw from)
+    if (sampler == GREEDY) pen = false;
     if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) {
         StepOpts o;
         o.sampler = sampler;
+        o.pen = pen;
         return enqueue_step(g, with_logits, bucket_t_hi(g, seq_len), s, o);
     }
     if (g->graph_stream != s) ZG_TRY(capture_all(g, s));  // the caller switched streams after zg_gpt_create
     hipGraphExec_t e;
-    ZG_TRY(graph_exec(g, {with_logits, false, sampler}, bucket_of(seq_len), s, &e));
+    ZG_TRY(graph_exec(g, {with_logits, false, sampler, pen}, bucket_of(seq_len), s, &e));
     ZG_HIP(hipGraphLaunch(e, s));
     return ZG_OK;
 }
@@ -1061,12 +1101,17 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
     ZG_REQUIRE(g->lm_grid <= 4096, ZG_ERR_UNSUPPORTED, "lm_head grid %d exceeds the argmax partial buffer", g->lm_grid);
     // (the control mirror and, 256 bytes behind it, the fault word of the tagged hand-overs: pinned, written by the kernels)
     e = hipHostMalloc(reinterpret_cast<void**>(&g->h_ctrl), sizeof(StepCtrl) + 512, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_ints), (batch * c.context_size + batch) * sizeof(int), hipHostMallocDefault);
+    // (h_ints, and behind it the staging of the penalties' prior / history: the same shape)
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_ints), 2 * (batch * c.context_size + batch) * sizeof(int), hipHostMallocDefault);
     if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(control mirrors)", __FILE__, __LINE__);
     static_assert(sizeof(StepCtrl) + sizeof(SampleParams) <= 256, "the fault word sits 256 bytes behind the control mirror");
     g->h_samp = reinterpret_cast<SampleParams*>(reinterpret_cast<char*>(g->h_ctrl) + 128);  // (same pinned block)
     g->fault = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g->h_ctrl) + 256);
     *g->fault = 0;
+    g->h_pen = reinterpret_cast<PenParams*>(reinterpret_cast<char*>(g->h_ctrl) + 384);  // (behind zg_gpt_sample's uniforms at 320)
+    g->h_prior = g->h_ints + batch * c.context_size + batch;
+    ZG_REQUIRE(!(g->flags & ZG_GPT_PENALIZED_GENERATE) || c.context_size <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED,
+               "ZG_GPT_PENALIZED_GENERATE: context_size %zu beyond the %d tokens the penalty kernel's LDS table holds", c.context_size, kPenMaxHistory);
     {   // decode steps per graph in the generate loop: a graph launch costs ~7 us of idle queue (124M: 224.8 us per token
         // with 1 step per graph, 220.4 with 2 / 4, 218.3 with 8, 219.5 with 16)
         const int k = env_int("ZGPT2_GRAPH_STEPS", 8);
@@ -1399,8 +1444,20 @@ int zg_gpt_argmax(zg_gpt* g, size_t* tokens_out, size_t n_tokens) {
 
 static SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed);
 static int check_sample_options(const zg_sample_options* o, const char* who);
+// The explicit history of a penalised per-token call: [batch][stride] tokens, lens[b] of each row
+struct PenCall {
+    const zg_logit_penalties* pen;
+    const size_t* history;
+    size_t stride;
+    const size_t* lens;
+};
 static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options& o, const float* uniforms, uint64_t seed,
-                       size_t* tokens_out, float* probs_out, size_t probs_len);
+                       size_t* tokens_out, float* probs_out, size_t probs_len, const PenCall* pc = nullptr);
+static int check_penalties(const zg_logit_penalties* p, const char* who);
+static int check_pen_handle(const zg_gpt* g, const char* who);
+static int check_history(const zg_gpt* g, const size_t* tokens, size_t stride, const size_t* lens, size_t extra, const char* who);
+static int stage_penalties(zg_gpt* g, const zg_logit_penalties& p, size_t past, const size_t* tokens, size_t stride, const size_t* lens, hipStream_t s);
+static inline bool penalties_off(const zg_logit_penalties& p) { return p.repetition == 1.0f && p.presence == 0.0f && p.frequency == 0.0f; }
 
 int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, const float* uniforms,
                   uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
@@ -1417,8 +1474,23 @@ int zg_gpt_sample_ex(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_t
     return sample_impl(g, seq_len, tokens, n_tokens, *opt, uniforms, seed, tokens_out, probs_out, probs_len);
 }
 
+// zg_gpt_sample_ex with the penalty stage in front: the history is the caller's.  All penalties off: zg_gpt_sample_ex itself.
+int zg_gpt_sample_pen(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
+                      const size_t* history, size_t history_stride, const size_t* history_lens, const float* uniforms, uint64_t seed, size_t* tokens_out,
+                      float* probs_out, size_t probs_len) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, "gpt_sample_pen"));
+    ZG_TRY(check_penalties(pen, "gpt_sample_pen"));
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "gpt_sample_pen: null handle");
+    ZG_TRY(check_pen_handle(g, "gpt_sample_pen"));
+    ZG_TRY(check_history(g, history, history_stride, history_lens, 0, "gpt_sample_pen"));
+    const PenCall pc{pen, history, history_stride, history_lens};
+    if (!penalties_off(*pen)) ZG_HIP(hipStreamSynchronize(gs(g)));  // (an enqueued generation may still be reading the pinned mirrors; idle otherwise)
+    return sample_impl(g, seq_len, tokens, n_tokens, *opt, uniforms, seed, tokens_out, probs_out, probs_len, penalties_off(*pen) ? nullptr : &pc);
+}
+
 static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options& o, const float* uniforms, uint64_t seed,
-                       size_t* tokens_out, float* probs_out, size_t probs_len) {
+                       size_t* tokens_out, float* probs_out, size_t probs_len, const PenCall* pc) {
     ZG_REQUIRE(g && tokens && tokens_out, ZG_ERR_ARG, "gpt_sample: bad argument");
     const size_t V = g->cfg.vocab_size, B = g->batch;
     ZG_REQUIRE(!probs_out || probs_len >= B * V, ZG_ERR_SHAPE, "gpt_sample: probs_out needs %zu elements", B * V);
@@ -1426,6 +1498,10 @@ static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n
         ZG_REQUIRE(uniforms[b] >= 0.0f && uniforms[b] < 1.0f, ZG_ERR_ARG, "gpt_sample: uniform %f outside [0,1)", uniforms[b]);
     ZG_TRY(forward_enqueue(g, seq_len, tokens, n_tokens, 1, nullptr, 0));  // main.zig:199 (not drained: the sampler goes behind it)
     hipStream_t s = gs(g);
+    if (pc) {  // the raw logits are penalised and the row-maximum partials rebuilt before either sampler looks at them
+        ZG_TRY(stage_penalties(g, *pc->pen, 0, pc->history, pc->stride, pc->lens, s));
+        ZG_TRY(launch_penalize(g->logits, (int)B, (int)V, g->pen, pen_history(g, false), g->part_val, g->part_idx, g->lm_grid, nullptr, s));
+    }
     // (pinned, 320 bytes into the control block: h_ints[0 .. B) is still being read by the forward's token upload)
     float* h_u = reinterpret_cast<float*>(reinterpret_cast<char*>(g->h_ctrl) + 320);
     for (size_t b = 0; b < B; ++b) {
@@ -1478,6 +1554,55 @@ static SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sa
     return k_on && p_on ? TWO_FILTERS : (k_on || p_on) ? ONE_FILTER : PLAIN;
 }
 
+static int check_penalties(const zg_logit_penalties* p, const char* who) {
+    ZG_REQUIRE(p != nullptr, ZG_ERR_ARG, "%s: penalties is null", who);
+    ZG_REQUIRE(p->repetition > 0.0f, ZG_ERR_ARG, "%s: repetition penalty %f (must be > 0)", who, p->repetition);  // (a NaN fails it)
+    ZG_REQUIRE(std::isfinite(p->presence) && std::isfinite(p->frequency), ZG_ERR_ARG, "%s: presence %f / frequency %f penalty", who, p->presence,
+               p->frequency);
+    return ZG_OK;
+}
+
+// the counting kernel keeps a row's distinct tokens in an LDS table sized by the context
+static int check_pen_handle(const zg_gpt* g, const char* who) {
+    ZG_REQUIRE(g->cfg.context_size <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED, "%s: context_size %zu beyond the %d tokens the penalty kernel's LDS table holds",
+               who, g->cfg.context_size, kPenMaxHistory);
+    return ZG_OK;
+}
+
+// A caller's token lists for the penalties ([batch][stride], lens[b] each; tokens null: no lists): lengths within the stride and,
+// with `extra` more tokens to come from the loop's own record, within the context; tokens inside the vocabulary
+static int check_history(const zg_gpt* g, const size_t* tokens, size_t stride, const size_t* lens, size_t extra, const char* who) {
+    if (!tokens) {
+        for (size_t b = 0; lens && b < g->batch; ++b) ZG_REQUIRE(lens[b] == 0, ZG_ERR_ARG, "%s: row %zu lists %zu tokens but the lists are null", who, b, lens[b]);
+        return ZG_OK;
+    }
+    ZG_REQUIRE(lens != nullptr, ZG_ERR_ARG, "%s: token lists without their lengths", who);
+    const size_t C = g->cfg.context_size, V = g->cfg.vocab_size;
+    for (size_t b = 0; b < g->batch; ++b) {
+        ZG_REQUIRE(lens[b] <= stride && lens[b] <= C && lens[b] + extra <= C, ZG_ERR_SHAPE, "%s: row %zu lists %zu tokens (stride %zu, context %zu, %zu to come)",
+                   who, b, lens[b], stride, C, extra);
+        for (size_t i = 0; i < lens[b]; ++i)
+            ZG_REQUIRE(tokens[b * stride + i] < V, ZG_ERR_SHAPE, "%s: token %zu >= vocab %zu", who, tokens[b * stride + i], V);
+    }
+    return ZG_OK;
+}
+
+// The penalties of the call and its token lists (checked) through their pinned mirrors into the arena.  PRECONDITION: nothing in
+// flight reads the mirrors (every penalised call drains, or begins by draining).
+static int stage_penalties(zg_gpt* g, const zg_logit_penalties& p, size_t past, const size_t* tokens, size_t stride, const size_t* lens, hipStream_t s) {
+    const size_t C = g->cfg.context_size, B = g->batch;
+    *g->h_pen = PenParams{p.repetition, p.presence, p.frequency, (int)past};
+    int* h_len = g->h_prior + B * C;
+    for (size_t b = 0; b < B; ++b) {
+        h_len[b] = tokens ? (int)lens[b] : 0;
+        for (size_t i = 0; tokens && i < lens[b]; ++i) g->h_prior[b * C + i] = (int)tokens[b * stride + i];
+    }
+    ZG_HIP(hipMemcpyAsync(g->pen, g->h_pen, sizeof(PenParams), hipMemcpyHostToDevice, s));
+    if (tokens) ZG_HIP(hipMemcpyAsync(g->prior, g->h_prior, B * C * sizeof(int), hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(g->prior_len, h_len, B * sizeof(int), hipMemcpyHostToDevice, s));
+    return ZG_OK;
+}
+
 static int check_sample_options(const zg_sample_options* o, const char* who) {
     ZG_REQUIRE(o != nullptr, ZG_ERR_ARG, "%s: options is null", who);
     ZG_REQUIRE(o->temp > 0.0f, ZG_ERR_ARG, "%s: temperature %f", who, o->temp);
@@ -1504,6 +1629,13 @@ struct GenRequest {
     SamplerMode mode;       // GREEDY (opt unused), or PLAIN: draw with opt — gen_begin raises it to the filters opt switches on
     zg_sample_options opt;
     uint64_t seed;
+    // penalties (a sampler only; pen_on false: none, the request is what it was without them) and the caller's prior of every row of
+    // the ONE handle such a request goes to: [rows][prior_stride], prior_lens[rows] tokens each, or null
+    bool pen_on = false;
+    zg_logit_penalties pen{1.0f, 0.0f, 0.0f};
+    const size_t* prior = nullptr;
+    size_t prior_stride = 0;
+    const size_t* prior_lens = nullptr;
     GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, const zg_sample_options* opt_or_null = nullptr, uint64_t seed = 0,
                size_t past = 0)
         : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past), mode(opt_or_null ? PLAIN : GREEDY),
@@ -1521,6 +1653,11 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
         ZG_REQUIRE(np >= 1 && past + np <= C && np <= r.stride, ZG_ERR_SHAPE, "generate: prompt %zu has length %zu", b, np);
         for (size_t i = 0; i < np; ++i)
             ZG_REQUIRE(r.prompts[b * r.stride + i] < V, ZG_ERR_SHAPE, "generate: token %zu >= vocab %zu", r.prompts[b * r.stride + i], V);
+    }
+    const bool pen_on = r.pen_on && r.mode != GREEDY;
+    if (pen_on) {  // (a row's history, prior and recorded, never exceeds the context: the kernel's table is sized by it)
+        ZG_TRY(check_pen_handle(g, "generate_pen"));
+        ZG_TRY(check_history(g, r.prior, r.prior_stride, r.prior_lens, n_steps, "generate_pen"));
     }
     hipStream_t s = gs(g);
     ZG_HIP(hipStreamSynchronize(s));  // pinned staging below is shared with earlier calls
@@ -1542,6 +1679,8 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
         g->gen_mode = fill_sample_params(g->h_samp, V, r.opt, r.seed);
         ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     }
+    g->gen_pen = pen_on;
+    if (pen_on) ZG_TRY(stage_penalties(g, r.pen, past, r.prior, r.prior_stride, r.prior_lens, s));
     ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(g->prompt_len, g->h_ints + B * C, B * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_TRY(stage_ctrl(g, past + first, past + first, r.mode != GREEDY ? 2 : 0, s));
@@ -1557,8 +1696,9 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     if (!(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && g->graph_stream != s) ZG_TRY(capture_all(g, s));  // before the prefetcher starts its idle clock
     // the truncated sampler's graphs of every bucket this generation touches, if create did not capture them: here, not in the
     // loop (a capture between the steps would run against the prefetcher's idle clock)
-    if (filter_launches(g->gen_mode) && !(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && min_prompt < n_steps)
-        ZG_TRY(capture_sampled(g, g->gen_mode, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
+    // (and those of a penalised generation, whatever its sampler)
+    if ((filter_launches(g->gen_mode) || g->gen_pen) && !(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && min_prompt < n_steps)
+        ZG_TRY(capture_sampled(g, g->gen_mode, g->gen_pen, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
     ZG_TRY(note_steps(g, n_steps, s));
     ZG_TRY(pf_start(g, past + n_steps, s));
     g->gen_pos = past + first;  // absolute, as gen_n and gen_min_prompt: gen_pump's steps, buckets and graph alignment follow the position
@@ -1585,11 +1725,11 @@ static int gen_pump(zg_gpt* g, bool* more) {
     if (K > 1 && st >= g->gen_min_prompt && st % K == 0 && st + K <= n_steps && st + K <= C) {
         if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
         hipGraphExec_t e;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64)
-        ZG_TRY(graph_exec(g, {true, true, g->gen_mode}, bucket_of(st + 1), s, &e));
+        ZG_TRY(graph_exec(g, {true, true, g->gen_mode, g->gen_pen}, bucket_of(st + 1), s, &e));
         ZG_HIP(hipGraphLaunch(e, s));
         g->gen_pos = st + K;
     } else {
-        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_mode));
+        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_mode, g->gen_pen));
         g->gen_pos = st + 1;
     }
     *more = g->gen_pos < n_steps;
@@ -1713,6 +1853,28 @@ int zg_gpt_generate_from_enqueue(zg_gpt* g, size_t past_len, const size_t* promp
     return gen_run(&g, 1, GenRequest(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len));
 }
 
+// zg_gpt_generate_from_enqueue with penalties: the penalty stage is a node of graphs of their own (StepKey.pen), its
+// values, past_len and the prior live in device memory.  All penalties off: zg_gpt_generate_from_enqueue itself.
+int zg_gpt_generate_pen_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
+                                const size_t* prior_lens, uint64_t seed) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, "generate_pen"));
+    ZG_TRY(check_penalties(pen, "generate_pen"));
+    GenRequest r(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len);
+    if (!penalties_off(*pen)) {
+        r.pen_on = true;
+        r.pen = *pen;
+        r.prior = prior;
+        r.prior_stride = prior_stride;
+        r.prior_lens = prior_lens;
+    } else if (g) {  // (the lists are still the caller's to get right)
+        ZG_TRY(check_pen_handle(g, "generate_pen"));
+        ZG_TRY(check_history(g, prior, prior_stride, prior_lens, 0, "generate_pen"));
+    }
+    return gen_run(&g, 1, r);
+}
+
 int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && out_tokens, ZG_ERR_ARG, "generate_fetch_range: null argument");
@@ -1792,6 +1954,73 @@ int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const 
     }
     ZG_HIP(hipStreamSynchronize(s));
     for (size_t b = 0; b < batch; ++b) tokens_out[b] = (size_t)h_tok[b];
+    return ZG_OK;
+}
+
+// The penalty kernels on the caller's rows (tests): the launches of the penalised step, in place on a copy.  Allocates per call.
+int zg_debug_penalize_rows(const float* logits, size_t batch, size_t vocab, const zg_logit_penalties* pen, const size_t* history, size_t history_stride,
+                           const size_t* history_lens, float* logits_out, unsigned* counts_out) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_penalties(pen, "debug_penalize_rows"));
+    ZG_REQUIRE(logits && logits_out && history_lens && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG,
+               "debug_penalize_rows: bad argument");
+    size_t longest = 0;
+    for (size_t b = 0; b < batch; ++b) {
+        ZG_REQUIRE(history_lens[b] <= history_stride && (history_lens[b] == 0 || history), ZG_ERR_SHAPE, "debug_penalize_rows: row %zu lists %zu tokens (stride %zu)",
+                   b, history_lens[b], history_stride);
+        for (size_t i = 0; i < history_lens[b]; ++i)
+            ZG_REQUIRE(history[b * history_stride + i] < vocab, ZG_ERR_SHAPE, "debug_penalize_rows: token %zu >= vocab %zu", history[b * history_stride + i],
+                       vocab);
+        longest = std::max(longest, history_lens[b]);
+    }
+    ZG_REQUIRE(longest <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED, "debug_penalize_rows: a history of %zu tokens exceeds the %d the LDS table holds", longest,
+               kPenMaxHistory);
+    const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
+    const size_t stride = std::max(longest, (size_t)1);
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t lbytes = up(batch * vocab * 4), hbytes = up(batch * stride * 4), pbytes = up((size_t)B * n_part * 4), bbytes = up(batch * 4);
+    hipStream_t s = ctx().stream;
+    char* base = nullptr;
+    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), 2 * lbytes + hbytes + 2 * pbytes + bbytes + 256));
+    struct Free {
+        char* p;
+        ~Free() { (void)hipFree(p); }
+    } guard{base};
+    char* p = base;
+    float* d_logits = reinterpret_cast<float*>(p);
+    p += lbytes;
+    unsigned* d_counts = reinterpret_cast<unsigned*>(p);
+    p += lbytes;
+    int* d_hist = reinterpret_cast<int*>(p);
+    p += hbytes;
+    float* d_pv = reinterpret_cast<float*>(p);
+    p += pbytes;
+    int* d_pi = reinterpret_cast<int*>(p);
+    p += pbytes;
+    int* d_len = reinterpret_cast<int*>(p);
+    p += bbytes;
+    PenParams* d_par = reinterpret_cast<PenParams*>(p);
+    std::vector<int> h_hist(batch * stride, 0), h_len(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        h_len[b] = (int)history_lens[b];
+        for (size_t i = 0; i < history_lens[b]; ++i) h_hist[b * stride + i] = (int)history[b * history_stride + i];
+    }
+    const PenParams hp{pen->repetition, pen->presence, pen->frequency, 0};
+    ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemsetAsync(d_counts, 0, batch * vocab * 4, s));
+    ZG_HIP(hipMemcpyAsync(d_hist, h_hist.data(), batch * stride * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_len, h_len.data(), batch * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
+    PenHistory h{};
+    h.prior = d_hist;
+    h.prior_len = d_len;
+    h.prior_stride = (int)stride;
+    h.max_hist = (int)longest;
+    ZG_TRY(launch_penalize(d_logits, B, V, d_par, h, d_pv, d_pi, n_part, d_counts, s));
+    // all penalties off: the call is the identity on the rows (the counts are still the history's)
+    ZG_HIP(hipMemcpyAsync(logits_out, penalties_off(*pen) ? logits : d_logits, batch * vocab * 4, hipMemcpyDefault, s));
+    if (counts_out) ZG_HIP(hipMemcpyAsync(counts_out, d_counts, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipStreamSynchronize(s));
     return ZG_OK;
 }
 

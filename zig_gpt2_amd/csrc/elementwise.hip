@@ -558,6 +558,7 @@ __global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vo
 }
 
 #include "sample_filter.h"
+#include "sample_penalty.h"
 
 inline int grid_for(size_t n, int block = 256, int cap = 2048) {
     size_t g = (n + block - 1) / block;
@@ -806,6 +807,30 @@ int launch_sample_filtered(float* logits, int batch, int vocab, const SamplePara
 int launch_row_max_partials(const float* logits, int batch, int vocab, float* part_val, int n_part, hipStream_t s) {
     ZG_REQUIRE(logits && part_val && batch >= 1 && vocab >= 1 && n_part >= 1 && n_part <= 4096, ZG_ERR_ARG, "row_max_partials: bad argument");
     hipLaunchKernelGGL(row_max_partials_kernel, dim3(n_part, batch), dim3(256), 0, s, logits, vocab, part_val);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_penalize(float* logits, int batch, int vocab, const PenParams* params, const PenHistory& h, float* part_val, int* part_idx, int n_part,
+                    unsigned* counts_out, hipStream_t s) {
+    ZG_REQUIRE(logits && params && part_val && part_idx && batch >= 1 && vocab >= 1 && n_part >= 1 && n_part <= 4096, ZG_ERR_ARG,
+               "penalties: missing argument");
+    ZG_REQUIRE(h.max_hist >= 0 && h.max_hist <= kPenMaxHistory, ZG_ERR_UNSUPPORTED, "penalties: a history of %d tokens exceeds the %d the LDS table holds",
+               h.max_hist, kPenMaxHistory);
+    int slots = 64;
+    while (slots < 2 * h.max_hist) slots *= 2;
+    const size_t lds = (size_t)slots * 2 * sizeof(unsigned);
+    if (lds > 64 * 1024) {  // opt in once, like every other launcher here
+        static bool raised = false;
+        if (!raised) {
+            ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&penalty_apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       2 * kPenMaxHistory * 2 * (int)sizeof(unsigned)));
+            raised = true;
+        }
+    }
+    hipLaunchKernelGGL(penalty_apply_kernel, dim3(batch), dim3(256), lds, s, logits, vocab, params, h, slots, counts_out);
+    ZG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(row_argmax_partials_kernel, dim3(n_part, batch), dim3(256), 0, s, logits, vocab, part_val, part_idx);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

@@ -345,6 +345,30 @@ int launch_sample_filtered(float* logits, int batch, int vocab, const SamplePara
                            hipStream_t s);
 // part_val[batch][n_part] = maxima of n_part slices of every row (what lm_head's argmax epilogue leaves; zg_debug_sample_rows)
 int launch_row_max_partials(const float* logits, int batch, int vocab, float* part_val, int n_part, hipStream_t s);
+// Repetition / presence / frequency penalties on the raw logits, in front of either sampler (sample_penalty.h; include/zgpt2.h
+// zg_logit_penalties).  Two launches: one workgroup per row counts the row's history in an LDS table and rewrites every logit
+// whose index occurs in it, once; then part_val / part_idx [batch][n_part] are rebuilt as the maxima (lowest index on ties) of n_part
+// slices of the penalised rows, which is all the samplers and zg_gpt_argmax take from lm_head's argmax epilogue.
+// The history of row b: prior[b][0 .. prior_len[b]) followed, when ctrl is given (the generate loop), by
+// rec[b][params->past_len .. ctrl->step - 2] — the tokens recorded when the step in flight (ctrl->step - 1) is sampled.  All of it is
+// read on the device, so one captured launch serves every position and every value.  max_hist: the longest history a row may have
+// (<= kPenMaxHistory: the table of 2 max_hist slots lives in the LDS); anything longer is cut, a token >= vocab is skipped.
+struct PenParams {
+    float repetition, presence, frequency;
+    int past_len;  // first recorded position that belongs to the history (generate loop)
+};
+struct PenHistory {
+    const int* prior;      // [batch][prior_stride] or nullptr
+    const int* prior_len;  // [batch]
+    int prior_stride;
+    const int* rec;        // [batch][rec_stride] the loop's token record (with ctrl), or nullptr
+    int rec_stride;
+    const StepCtrl* ctrl;
+    int max_hist;
+};
+constexpr int kPenMaxHistory = 8192;  // 16384 slots x (key, count) = 128 KB of the 160 KB LDS
+int launch_penalize(float* logits, int batch, int vocab, const PenParams* params, const PenHistory& h, float* part_val, int* part_idx, int n_part,
+                    unsigned* counts_out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------ multi-GPU (dist.hip)
 int dist_broadcast(void* buf, size_t bytes, int root, hipStream_t s);  // in place, over the communicator of zg_dist_init

@@ -31,12 +31,13 @@ def _pack_prompts(prompts, rows):
 class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
-                 sampled_generate=False, weights_b24=False, truncated_generate=False):
+                 sampled_generate=False, weights_b24=False, truncated_generate=False, penalized_generate=False):
         """share_weights_with / own_stream / stream_priority: zg_gpt_options of zg_gpt_create_ex (a handle of an independent
         prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config).
         weights_b24: matrices stored as 24-bit floats (ZG_GPT_WEIGHTS_B24: each fp32 weight rounded to 16 mantissa bits, 3/4 of
         fp32's bytes); excludes weights_f32.  truncated_generate: the graphs of generate_sample(top_k=..., top_p=...) are captured
-        at create (ZG_GPT_TRUNCATED_GENERATE) instead of when the first such generation begins."""
+        at create (ZG_GPT_TRUNCATED_GENERATE) instead of when the first such generation begins; penalized_generate: the same for
+        the graphs of generations with repetition / presence / frequency penalties (ZG_GPT_PENALIZED_GENERATE)."""
         self.config, self.batch = config, batch
         L = _lib.load()
         flags = (_lib.GPT_WEIGHTS_F32 if weights_f32 else 0) | (0 if use_graph else _lib.GPT_NO_GRAPH)
@@ -48,6 +49,7 @@ class GPT:
         flags |= _lib.GPT_SAMPLED_GENERATE if sampled_generate else 0
         flags |= _lib.GPT_WEIGHTS_B24 if weights_b24 else 0
         flags |= _lib.GPT_TRUNCATED_GENERATE if truncated_generate else 0
+        flags |= _lib.GPT_PENALIZED_GENERATE if penalized_generate else 0
         cfg = _lib.GptConfig(config.vocab_size, config.context_size, config.n_layer, config.n_heads, config.n_embed)
         h = C.c_void_p()
         if share_weights_with is None and not own_stream:
@@ -154,13 +156,48 @@ class GPT:
             opt = _lib.SampleOptions(temp, top_k, top_p)
             check(getattr(self._L, f"zg_gpt_{name}_ex{suffix}")(self.h, *head, C.addressof(opt), *tail))
 
-    def sample(self, seq_len, tokens, temp, uniforms=None, seed=0, want_probs=False, top_k=0, top_p=1.0):
+    @staticmethod
+    def _penalties(repetition_penalty, presence_penalty, frequency_penalty):
+        """zg_logit_penalties, or None while all three are off (the call is then today's, through today's entry point)."""
+        if repetition_penalty == 1.0 and presence_penalty == 0.0 and frequency_penalty == 0.0:
+            return None
+        return _lib.LogitPenalties(repetition_penalty, presence_penalty, frequency_penalty)
+
+    def _token_lists(self, lists):
+        """One token list per row (None: none) -> (ptr or None, stride, ptr to lengths or None), with the arrays kept alive."""
+        if lists is None:
+            return None, 0, None, ()
+        mat, lens, stride = _pack_prompts([np.zeros(0, np.uint64) if h is None else h for h in lists], self.batch)
+        if mat.shape[1] == 0:
+            mat, stride = np.zeros((self.batch, 1), np.uint64), 1
+        return ptr(mat), stride, ptr(lens), (mat, lens)
+
+    def _generate_pen(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior):
+        mat, lens, stride = self._prompts(prompts)
+        opt = _lib.SampleOptions(temp, top_k, top_p)
+        pp, pstride, plens, keep = self._token_lists(prior)
+        check(self._L.zg_gpt_generate_pen_enqueue(self.h, past_len, ptr(mat), stride, ptr(lens), n_steps, C.addressof(opt), C.addressof(pen), pp, pstride,
+                                                  plens, seed))
+        del keep
+
+    def sample(self, seq_len, tokens, temp, uniforms=None, seed=0, want_probs=False, top_k=0, top_p=1.0, repetition_penalty=1.0,
+               presence_penalty=0.0, frequency_penalty=0.0, history=None):
         """GPT.sample (src/main.zig:198-207) with reproducible uniforms; returns tokens [batch] (and probs).  top_k / top_p:
-        truncation in front of the draw (zg_sample_options; the defaults are off and take zg_gpt_sample itself)."""
+        truncation in front of the draw (zg_sample_options; the defaults are off and take zg_gpt_sample itself).
+        repetition_penalty / presence_penalty / frequency_penalty: zg_logit_penalties on the tokens of `history` (one list per row),
+        applied to the raw logits first (zg_gpt_sample_pen; the defaults are off and take today's call)."""
         tokens = np.ascontiguousarray(np.atleast_1d(tokens), dtype=np.uint64)
         u = None if uniforms is None else np.ascontiguousarray(np.atleast_1d(uniforms), dtype=np.float32)
         out = np.zeros(self.batch, np.uint64)
         probs = np.empty((self.batch, self.config.vocab_size), np.float32) if want_probs else None
+        pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if pen is not None:
+            opt = _lib.SampleOptions(temp, top_k, top_p)
+            hp, hstride, hlens, keep = self._token_lists(history if history is not None else [None] * self.batch)
+            check(self._L.zg_gpt_sample_pen(self.h, seq_len, ptr(tokens), tokens.size, C.addressof(opt), C.addressof(pen), hp, hstride, hlens, ptr(u), seed,
+                                            ptr(out), ptr(probs), ops._n(probs)))
+            del keep
+            return (out, probs) if want_probs else out
         self._sampled("sample", "", (seq_len, ptr(tokens), tokens.size), temp, top_k, top_p, (ptr(u), seed, ptr(out), ptr(probs), ops._n(probs)))
         return (out, probs) if want_probs else out
 
@@ -200,25 +237,44 @@ class GPT:
         check(self._L.zg_gpt_generate_fetch_range(self.h, first, n, ptr(out), out.size))
         return out
 
-    def generate_from(self, past_len, prompts, n_steps, temp=None, seed=0, top_k=0, top_p=1.0):
+    def generate_from(self, past_len, prompts, n_steps, temp=None, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
+                      frequency_penalty=0.0, prior=None):
         """generate entered at position past_len (zg_gpt_generate_from_enqueue): `prompts` are the new tokens of each row, fed
         behind the past_len cached positions; returns the tokens of positions past_len .. past_len + n_steps - 1 ([batch, n_steps]).
-        temp=None: greedy; otherwise the sampler of generate_sample (top_k / top_p as there)."""
+        temp=None: greedy; otherwise the sampler of generate_sample (top_k / top_p as there).  Penalties as generate_sample; the
+        tokens below past_len count only when passed as `prior` (one list per row)."""
+        pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if pen is not None:
+            if temp is None:
+                raise ValueError("penalties need a sampler: greedy picking with penalties is temp=1.0, top_k=1")
+            self._generate_pen(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior)
+            return self.generate_fetch_range(past_len, n_steps)
         mat, lens, stride = self._prompts(prompts)
         opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
         check(self._L.zg_gpt_generate_from_enqueue(self.h, past_len, ptr(mat), stride, ptr(lens), n_steps,
                                                    None if opt is None else C.addressof(opt), seed))
         return self.generate_fetch_range(past_len, n_steps)
 
-    def generate_sample(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0):
+    def generate_sample(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
+                        frequency_penalty=0.0, prior=None):
         """generate (src/main.zig:322-342) as the reference runs it — every token behind the prompt drawn by GPT.sample — with the
-        loop on the device; the tokens of the host loop over `sample(T, tok, temp, seed=seed)`.  top_k / top_p: as `sample`."""
+        loop on the device; the tokens of the host loop over `sample(T, tok, temp, seed=seed)`.  top_k / top_p: as `sample`.
+        repetition_penalty / presence_penalty / frequency_penalty: on the tokens the row holds when a pick is drawn — `prior` (one
+        list per row, optional) followed by the row's prompt and picks so far (zg_gpt_generate_pen_enqueue; defaults: today's call)."""
+        pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if pen is not None:
+            self._generate_pen(0, prompts, n_steps, temp, seed, top_k, top_p, pen, prior)
+            return self.generate_fetch(n_steps)
         mat, lens, stride = self._prompts(prompts)
         out = np.zeros((self.batch, n_steps), np.uint64)
         self._sampled("generate_sample", "", (ptr(mat), stride, ptr(lens), n_steps), temp, top_k, top_p, (seed, ptr(out), out.size))
         return out
 
-    def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0):
+    def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
+                                frequency_penalty=0.0, prior=None):
+        pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if pen is not None:
+            return self._generate_pen(0, prompts, n_steps, temp, seed, top_k, top_p, pen, prior)
         mat, lens, stride = self._prompts(prompts)
         self._sampled("generate_sample", "_enqueue", (ptr(mat), stride, ptr(lens), n_steps), temp, top_k, top_p, (seed,))
 
