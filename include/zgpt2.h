@@ -184,6 +184,24 @@ int zg_debug_prefill_route(int force_kernel, int slices);
 /* Diagnostic: name of the kernel instantiation the last decode-kernel launcher of this thread picked (launches recorded
  * into a graph count; bench.py reports it as the symbol of the roofline kernel). */
 int zg_debug_last_kernel(char* out, size_t n);
+/* Diagnostic: the plan of a decode-regime Linear y[M][N] = x[M][K] W^T — which kernel it would take and how it is laid out —
+ * without launching anything; works without a GPU and without zg_init.  prologue 0 none, 1 LayerNorm, 2 head merge; epilogue
+ * 0 store, 1 residual, 2 GELU, 3 QKV + cache append, 4 partial argmax; weight_type 0 bf16, 1 fp32, 2 B24; operands: the optional
+ * operands present (ZG_PLAN_*); sk_tiles: tiles of the split-K workspace (ZG_PLAN_SPLIT_K); t_hi: launch-time bound of the
+ * sequence length (0 = none).  out[ZG_GEMV_PLAN_INTS]: route (0 VALU, 1 VALU in row groups, 2 generic K % 8 != 0, 3 K split,
+ * 4 folded LayerNorm, 5 matrix cores 16-wave, 6 ... K-sliced, 7 plane-fed four-wave, 8 ... K-sliced, 9 lm_head wave per tile),
+ * grid x, grid y = K slices, block threads, dynamic LDS bytes, batch rows held, lanes per row, chunks per lane, 32-k steps per
+ * wave, waves (16-wave kernel), line loads, planes from global memory, aliased partials, 64-k pairs, steps per tile, rows per wave
+ * or tiles per workgroup, waves per workgroup, row-group size, rows of W per workgroup and tiles as the prefetcher takes them,
+ * supported, may take planes, may write planes, four-wave kernel when given planes. */
+#define ZG_GEMV_PLAN_INTS 24
+#define ZG_PLAN_LN_FOLDED 1u      /* ln_c2 / ln_c3: the LayerNorm folded out of the dot product */
+#define ZG_PLAN_PLANES_IN 2u      /* pl_in */
+#define ZG_PLAN_STATS_IN 4u       /* st_in */
+#define ZG_PLAN_SPLIT_K 8u        /* sk_ws + sk_cnt with sk_tiles */
+#define ZG_PLAN_RAGGED_STRIDES 16u /* row strides of x / y / residual wider than the rows */
+int zg_debug_gemv_plan(int M, int N, int K, int prologue, int epilogue, int weight_type, unsigned operands, int sk_tiles, int t_hi, int* out,
+                       size_t n_out);
 int zg_f32_to_bf16(const float* src, uint16_t* dst_device, size_t len);
 
 /* ------------------------------------------------------------------ model tier: src/main.zig */

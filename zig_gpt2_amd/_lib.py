@@ -64,6 +64,7 @@ SIGNATURES = {
     "zg_debug_gemm_launches": (C.c_ulonglong, []),
     "zg_debug_gemm_stamps": (C.c_int, [vp, sz]),
     "zg_debug_last_kernel": (C.c_int, [C.c_char_p, sz]),
+    "zg_debug_gemv_plan": (C.c_int, [C.c_int] * 6 + [C.c_uint, C.c_int, C.c_int, vp, sz]),
     "zg_debug_attn_prefill": (C.c_int, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, sz, C.c_int]),
     "zg_debug_attn_prefill_at": (C.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, vp, C.c_int, sz, vp, sz, C.c_int]),
     "zg_debug_prefill_route": (C.c_int, [C.c_int, C.c_int]),

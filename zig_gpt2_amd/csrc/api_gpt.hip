@@ -340,17 +340,17 @@ EmbedArgs embed_args(const zg_gpt* g, int finish_only) {
 
 // A planned decode launch: enqueue it, or (rec != nullptr: building the prefetcher's job table at create) describe
 // the weight tiles its workgroups read.
-int emit_gemv(const zg_gpt* g, const GemvArgs& a, int grid, hipStream_t s, std::vector<PfJob>* rec, unsigned cls) {
-    if (!rec) return launch_gemv(a, g->wt, grid, s);
+int emit_gemv(const zg_gpt* g, const GemvArgs& a, const GemvPlan& p, hipStream_t s, std::vector<PfJob>* rec, unsigned cls) {
+    if (!rec) return launch_gemv(a, p, g->wt, s);
     PfJob j{};
     j.cls = cls;
-    const int rows = gemv_rows_per_wg(a, g->wt);
+    const int rows = p.rows_per_wg;
     if (rows > 0) {
         j.kind = PF_WEIGHTS;
         j.base = reinterpret_cast<const char*>(a.W);
         j.total_bytes = (size_t)a.N * a.K * g->wbytes;
         j.wg_bytes = (unsigned)((size_t)rows * a.K * g->wbytes);
-        j.n_wg = (unsigned)grid;
+        j.n_wg = (unsigned)p.pf_tiles;
         j.touch_bytes = j.wg_bytes;
         if (a.M == 1) {
             const bool lnk = a.prologue == PRO_LAYERNORM && a.ln_c2 != nullptr;
@@ -406,12 +406,16 @@ int ensure_ln_folded(zg_gpt* g, hipStream_t s) {
 }
 
 // The arguments of the decode launches of a Block and of lm_head, one builder per launch class: enqueue_step launches what they
-// return, and zg_gpt_create asks the shape predicates (gemv.hip) about the very same arguments.  The mode bits pl_on / st_on /
-// tags_on are read from the handle.
+// return, and zg_gpt_create plans (gemv_plan) the very same arguments.  The decode modes they lay the arguments out for are
+// passed in: the handle's own (modes_of) for a step, a candidate while zg_gpt_create decides them.
+struct StepModes {
+    bool pl, st, tags;  // as zg_gpt pl_on / st_on / tags_on
+};
+inline StepModes modes_of(const zg_gpt* g) { return StepModes{g->pl_on, g->st_on, g->tags_on}; }
 
 // ln_1 + c_attn + split_qkv + cache append (main.zig:121-123, ops.zig:143-157) and the attention over the cache (ops.zig:160 ->
 // :249-307) of layer y: the arguments of their launches
-GemvArgs c_attn_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
+GemvArgs c_attn_args(const zg_gpt* g, const zg_layer& y, int t_hi, const StepModes& m) {
     const size_t E = g->cfg.n_embed;
     GemvArgs a = base_gemv(g, y.c_attn_w, y.c_attn_b, 3 * E, E, t_hi);
     a.prologue = PRO_LAYERNORM;
@@ -422,8 +426,8 @@ GemvArgs c_attn_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
     a.ln_c2 = y.c_attn_c2;
     a.ln_c3 = y.c_attn_c3;
     a.epilogue = EPI_QKV;
-    a.pl_in = g->pl_on ? g->xp : nullptr;
-    a.st_in = g->st_on ? g->xst : nullptr;
+    a.pl_in = m.pl ? g->xp : nullptr;
+    a.st_in = m.st ? g->xst : nullptr;
     a.q = g->q;
     a.k_cache = y.k_cache;
     a.v_cache = y.v_cache;
@@ -453,7 +457,7 @@ AttnArgs attn_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
 }
 
 // merge heads + attn c_proj + residual: ops.zig:171-172, main.zig:136-139
-GemvArgs c_proj_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
+GemvArgs c_proj_args(const zg_gpt* g, const zg_layer& y, int t_hi, const StepModes& m) {
     const size_t E = g->cfg.n_embed;
     GemvArgs a = base_gemv(g, y.c_proj_w, y.c_proj_b, E, E, t_hi);
     a.prologue = PRO_ATTN_MERGE;
@@ -463,18 +467,18 @@ GemvArgs c_proj_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
     a.y_stride = (int)E;
     a.resid = g->x;
     a.resid_stride = (int)E;
-    if (g->pl_on) {  // the heads arrive merged, as planes
+    if (m.pl) {  // the heads arrive merged, as planes
         a.prologue = PRO_NONE;
         a.pl_in = g->ap;
         a.pl_out = g->xp;
         a.pl_g = y.ln_2_g;
-        a.st_out = g->st_on ? g->xst : nullptr;
+        a.st_out = m.st ? g->xst : nullptr;
     }
     return a;
 }
 
 // ln_2 + c_fc + gelu: main.zig:140, :79-80
-GemvArgs c_fc_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
+GemvArgs c_fc_args(const zg_gpt* g, const zg_layer& y, int t_hi, const StepModes& m) {
     const size_t E = g->cfg.n_embed;
     GemvArgs a = base_gemv(g, y.c_fc_w, y.c_fc_b, 4 * E, E, t_hi);
     a.prologue = PRO_LAYERNORM;
@@ -487,8 +491,8 @@ GemvArgs c_fc_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
     a.epilogue = EPI_GELU;
     a.y = g->h4;
     a.y_stride = (int)(4 * E);
-    if (g->pl_on) {  // gelu(c_fc) leaves as planes only
-        a.st_in = g->st_on ? g->xst : nullptr;
+    if (m.pl) {  // gelu(c_fc) leaves as planes only
+        a.st_in = m.st ? g->xst : nullptr;
         a.pl_in = g->xp;
         a.pl_out = g->hp;
         a.y = nullptr;
@@ -498,7 +502,7 @@ GemvArgs c_fc_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
 
 // mlp c_proj + residual of layer l (main.zig:81, :142-145).  A tagged hand-over gets everything but its launch id, which is the
 // caller's to give (a.sk_tag != nullptr says that one is due).
-GemvArgs mlp_proj_args(const zg_gpt* g, size_t l, int t_hi) {
+GemvArgs mlp_proj_args(const zg_gpt* g, size_t l, int t_hi, const StepModes& m) {
     const size_t E = g->cfg.n_embed;
     const zg_layer& y = g->layers[l];
     GemvArgs a = base_gemv(g, y.mlp_proj_w, y.mlp_proj_b, E, 4 * E, t_hi);
@@ -510,8 +514,8 @@ GemvArgs mlp_proj_args(const zg_gpt* g, size_t l, int t_hi) {
     a.y_stride = (int)E;
     a.resid = g->x;
     a.resid_stride = (int)E;
-    if (g->pl_on) {
-        if (g->tags_on && 2 * l + 2 <= 255) {
+    if (m.pl) {
+        if (m.tags && 2 * l + 2 <= 255) {
             a.epoch = g->epoch;
             a.sk_tag = g->sk_tag;
             a.fault = g->fault;
@@ -521,7 +525,7 @@ GemvArgs mlp_proj_args(const zg_gpt* g, size_t l, int t_hi) {
         if (l + 1 < g->cfg.n_layer) {  // the next Block's ln_1 + c_attn (ln_f + lm_head reads x itself)
             a.pl_out = g->xp;
             a.pl_g = g->layers[l + 1].ln_1_g;
-            a.st_out = g->st_on ? g->xst : nullptr;
+            a.st_out = m.st ? g->xst : nullptr;
         }
     }
     return a;
@@ -547,10 +551,10 @@ GemvArgs lm_head_args(const zg_gpt* g) {
 }
 
 int enqueue_lm_head(zg_gpt* g, hipStream_t s, std::vector<PfJob>* rec = nullptr) {
-    GemvArgs a = lm_head_args(g);
-    const int grid = gemv_plan(a, g->wt);
-    ZG_REQUIRE(grid == g->lm_grid, ZG_ERR_ARG, "lm_head grid changed");
-    return emit_gemv(g, a, grid, s, rec, 6);
+    const GemvArgs a = lm_head_args(g);
+    const GemvPlan p = gemv_plan(a, g->wt);
+    ZG_REQUIRE(p.grid == g->lm_grid, ZG_ERR_ARG, "lm_head grid changed");
+    return emit_gemv(g, a, p, s, rec, 6);
 }
 
 // What enqueue_step does besides a plain step.
@@ -588,9 +592,9 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
     std::vector<PfJob>* const rec = o.rec;
     const int only = o.only;
     auto launch_id = [&](size_t l, int k) { return (unsigned)(o.salt >= 0 ? 1 + (2 * o.salt + k) % 254 : 2 * (int)l + 1 + k); };
-    auto gemv = [&](GemvArgs a, unsigned cls) {
-        const int grid = gemv_plan(a, g->wt);
-        ZG_TRY(emit_gemv(g, a, grid, s, rec, cls));
+    const StepModes m = modes_of(g);
+    auto gemv = [&](const GemvArgs& a, unsigned cls) {
+        ZG_TRY(emit_gemv(g, a, gemv_plan(a, g->wt), s, rec, cls));
         return prof_mark(prof, (int)cls, s);
     };
     ZG_TRY(prof_mark(prof, -1, s));
@@ -605,16 +609,16 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         // one sequence: classes 1 and 2 as one launch (attn_qkv.hip), timed as class 1; the prefetcher's table keeps both entries
         const bool fused = g->fused_on && !rec && 2 * l + 2 <= 255;
         if (fused && (only < 0 || only == 1)) {
-            GemvArgs a = c_attn_args(g, y, t_hi);
+            const GemvArgs a = c_attn_args(g, y, t_hi, m);
             AttnArgs at = attn_args(g, y, t_hi);
             at.launch_id = launch_id(l, 0);
             at.fault = g->fault;
             at.spin_limit = g->spin_limit;
-            ZG_TRY(launch_attn_qkv(a, g->wt, at, g->epoch, g->qkv_tag, s));
+            ZG_TRY(launch_attn_qkv(a, gemv_plan(a, g->wt), g->wt, at, g->epoch, g->qkv_tag, s));
             ZG_TRY(prof_mark(prof, 1, s));
             ZG_TRY(prof_mark(prof, 2, s));
         }
-        if (!fused && (only < 0 || only == 1)) ZG_TRY(gemv(c_attn_args(g, y, t_hi), 1));
+        if (!fused && (only < 0 || only == 1)) ZG_TRY(gemv(c_attn_args(g, y, t_hi, m), 1));
         if ((!fused && only < 0) || only == 2) {   // scaled_dot_product_attention over the cache: ops.zig:160 -> :249-307
             AttnArgs a = attn_args(g, y, t_hi);
             if (g->pl_on) {
@@ -643,10 +647,10 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
                 ZG_TRY(launch_attn_decode(a, s));
             ZG_TRY(prof_mark(prof, 2, s));
         }
-        if (only < 0 || only == 3) ZG_TRY(gemv(c_proj_args(g, y, t_hi), 3));
-        if (only < 0 || only == 4) ZG_TRY(gemv(c_fc_args(g, y, t_hi), 4));
+        if (only < 0 || only == 3) ZG_TRY(gemv(c_proj_args(g, y, t_hi, m), 3));
+        if (only < 0 || only == 4) ZG_TRY(gemv(c_fc_args(g, y, t_hi, m), 4));
         if (only < 0 || only == 5) {
-            GemvArgs a = mlp_proj_args(g, l, t_hi);
+            GemvArgs a = mlp_proj_args(g, l, t_hi, m);
             if (a.sk_tag) a.launch_id = launch_id(l, 1);
             ZG_TRY(gemv(a, 5));
         }
@@ -1070,33 +1074,30 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
         e = hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, pr);
         if (e != hipSuccess) return hip_fail(e, "hipStreamCreateWithPriority(handle stream)", __FILE__, __LINE__);
     }
-    // The decode modes, each decided by asking the shape predicates about the launches enqueue_step would make with the mode on
-    // (the builders read the bits: a candidate is switched on for its question and stays on if the answer is yes).
+    // The decode modes, each decided from the plans (gemv_plan) of the launches enqueue_step would make with the mode on.
     const zg_layer& y = g->layers[0];
-    {
-        GemvArgs a = lm_head_args(g);
-        g->lm_grid = gemv_plan(a, g->wt);
-    }
+    const int off = decode_paths_off();
+    g->lm_grid = gemv_plan(lm_head_args(g), g->wt).grid;
     // the widest input of a Block (mlp c_proj: 4 E floats per sequence) must fit the batched kernels' LDS
-    ZG_REQUIRE(gemv_supported(mlp_proj_args(g, 0, 0), g->wt), ZG_ERR_UNSUPPORTED,
+    ZG_REQUIRE(gemv_plan(mlp_proj_args(g, 0, 0, StepModes{}), g->wt).supported, ZG_ERR_UNSUPPORTED,
                "batch %zu with n_embed %zu: %zu input rows of 4*n_embed floats do not fit the LDS (use a smaller batch)", batch, c.n_embed, batch);
-    auto every_linear = [&](bool (*ok)(const GemvArgs&, int)) {
-        return ok(c_attn_args(g, y, 0), g->wt) && ok(c_proj_args(g, y, 0), g->wt) && ok(c_fc_args(g, y, 0), g->wt) &&
-               ok(mlp_proj_args(g, 0, 0), g->wt);
-    };
-    if (g->wt == WT_BF16 && batch >= 2 && !(decode_paths_off() & 1)) {  // all plane-fed Linears on the matrix-core path?
-        g->pl_on = true;
-        g->pl_on = c.n_embed % 32 == 0 && every_linear(gemv_planes_ok);
+    if (g->wt == WT_BF16 && batch >= 2 && !(off & 1) && c.n_embed % 32 == 0) {
+        const StepModes cand{true, false, false};  // activation planes between the kernels
+        const GemvPlan lin[4] = {gemv_plan(c_attn_args(g, y, 0, cand), g->wt), gemv_plan(c_proj_args(g, y, 0, cand), g->wt),
+                                 gemv_plan(c_fc_args(g, y, 0, cand), g->wt), gemv_plan(mlp_proj_args(g, 0, 0, cand), g->wt)};
+        auto every_linear = [&](bool GemvPlan::*f) { return lin[0].*f && lin[1].*f && lin[2].*f && lin[3].*f; };
+        g->pl_on = every_linear(&GemvPlan::can_take_planes);  // all plane-fed Linears on the matrix-core path?
+        // LayerNorm statistics by tile: every producer and consumer of x must be the four-wave kernel (the statistics' only
+        // part in a plan is the bound on n_embed / 16 asked here)
+        g->st_on = g->pl_on && !(off & 8) && c.n_embed % 16 == 0 && c.n_embed / 16 <= 128 && every_linear(&GemvPlan::pl4_with_planes);
     }
-    g->tags_on = g->pl_on && !(decode_paths_off() & 4);
+    g->tags_on = g->pl_on && !(off & 4);
     g->spin_limit = (unsigned)env_int("ZGPT2_TAG_SPIN_LIMIT", 1 << 20);
     // one sequence on the fp32 cache: ln_1 + c_attn and the attention as one launch where c_attn runs on the LayerNorm-folding
     // kernel (ZGPT2_DECODE_PATHS_OFF bit 64: two launches)
-    g->fused_on = batch == 1 && !(decode_paths_off() & 64) && c.n_layer <= 127 &&
-                  attn_qkv_ok(c_attn_args(g, y, 0), attn_args(g, y, (int)c.context_size));
-    if (g->pl_on && !(decode_paths_off() & 8) && c.n_embed % 16 == 0 && c.n_embed / 16 <= 128) {
-        g->st_on = true;
-        g->st_on = every_linear(gemv_pl4_ok);  // every producer and consumer of x must be the four-wave kernel
+    if (batch == 1 && !(off & 64) && c.n_layer <= 127) {
+        const GemvArgs ca = c_attn_args(g, y, 0, modes_of(g));
+        g->fused_on = attn_qkv_ok(ca, gemv_plan(ca, g->wt), attn_args(g, y, (int)c.context_size));
     }
     ZG_REQUIRE(g->lm_grid <= 4096, ZG_ERR_UNSUPPORTED, "lm_head grid %d exceeds the argmax partial buffer", g->lm_grid);
     // (the control mirror and, 256 bytes behind it, the fault word of the tagged hand-overs: pinned, written by the kernels)

@@ -315,8 +315,7 @@ static int linear_device(size_t in_f, size_t out_f, const float* w, const float*
         a.y = y + m0 * out_f;
         a.y_stride = (int)out_f;
         a.zero = ctx().d_zero;
-        const int grid = gemv_plan(a);
-        ZG_TRY(launch_gemv(a, WT_F32, grid, s));
+        ZG_TRY(launch_gemv(a, gemv_plan(a, WT_F32), WT_F32, s));
     }
     return ZG_OK;
 }
@@ -362,8 +361,7 @@ static int linear_device_wide(Call& call, size_t in_f, size_t out_f, const float
                 a.resid = k0 == 0 ? nullptr : a.y;
                 a.resid_stride = (int)out_f;
                 a.zero = ctx().d_zero;
-                const int grid = gemv_plan(a);
-                ZG_TRY(launch_gemv(a, WT_F32, grid, s));
+                ZG_TRY(launch_gemv(a, gemv_plan(a, WT_F32), WT_F32, s));
             }
         }
     }
@@ -638,6 +636,39 @@ int zg_debug_gemm_stamps(unsigned long long* out, size_t n_words) { return gemm_
 int zg_debug_last_kernel(char* out, size_t n) {
     if (!out || n == 0) return ZG_ERR_ARG;
     snprintf(out, n, "%s", zg::g_kernel);
+    return ZG_OK;
+}
+
+// Plans a described decode-regime Linear (gemv_plan) without a GPU or zg_init.  Only null / non-null of the operands matters to
+// the planner, so present ones are any non-null address; nothing is dereferenced.
+int zg_debug_gemv_plan(int M, int N, int K, int prologue, int epilogue, int weight_type, unsigned operands, int sk_tiles, int t_hi, int* out,
+                       size_t n_out) {
+    ZG_REQUIRE(out != nullptr && n_out >= ZG_GEMV_PLAN_INTS, ZG_ERR_ARG, "debug_gemv_plan: %d ints of output", ZG_GEMV_PLAN_INTS);
+    static float some[2];
+    const bool ragged = (operands & ZG_PLAN_RAGGED_STRIDES) != 0;  // row strides wider than the rows
+    GemvArgs a{};
+    a.M = M;
+    a.N = N;
+    a.K = K;
+    a.prologue = prologue;
+    a.epilogue = epilogue;
+    a.head_dim = 64;
+    a.t_hi = t_hi;
+    a.x_stride = K + (ragged ? 8 : 0);
+    a.y_stride = a.resid_stride = N + (ragged ? 8 : 0);
+    if (operands & ZG_PLAN_LN_FOLDED) a.ln_c2 = a.ln_c3 = some;
+    if (operands & ZG_PLAN_PLANES_IN) a.pl_in = reinterpret_cast<const bf16_t*>(some);
+    if (operands & ZG_PLAN_STATS_IN) a.st_in = some;
+    if (operands & ZG_PLAN_SPLIT_K) {
+        a.sk_ws = some;
+        a.sk_cnt = reinterpret_cast<int*>(some);
+        a.sk_tiles = sk_tiles;
+    }
+    const GemvPlan p = gemv_plan(a, weight_type);
+    const int v[ZG_GEMV_PLAN_INTS] = {p.route, p.grid, p.kslices, p.block, p.lds, p.mt, p.lpr, p.cpl, p.ks, p.nw, p.line, p.gpl, p.alias, p.pairs,
+                                      p.steps, p.rows_per_wave, p.waves_per_wg, p.row_group, p.rows_per_wg, p.pf_tiles, p.supported,
+                                      p.can_take_planes, p.can_write_planes, p.pl4_with_planes};
+    memcpy(out, v, sizeof(v));
     return ZG_OK;
 }
 

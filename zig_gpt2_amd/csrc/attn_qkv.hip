@@ -61,14 +61,15 @@ __global__ __launch_bounds__(256) void attn_qkv_kernel(const void* __restrict__ 
 
 }  // namespace
 
-bool attn_qkv_ok(const GemvArgs& g, const AttnArgs& at) {
-    return gemv_use_lnk(g) && g.epilogue == EPI_QKV && g.M == 1 && g.K <= 0xffff && at.batch == 1 && at.kv_mode == 0 && at.head_dim == 64 &&
+bool attn_qkv_ok(const GemvArgs& g, const GemvPlan& p, const AttnArgs& at) {
+    return p.route == GR_LNK && g.epilogue == EPI_QKV && g.M == 1 && g.K <= 0xffff && at.batch == 1 && at.kv_mode == 0 && at.head_dim == 64 &&
            at.stride_t == 64 && at.ctrl != nullptr && at.pl_out == nullptr && at.part_tag == nullptr && g.head_dim == 64 &&
            g.N == 3 * at.n_heads * 64;
 }
 
-int launch_attn_qkv(const GemvArgs& g, int weight_type, const AttnArgs& at, const unsigned* epoch, unsigned long long* qkv_tag, hipStream_t s) {
-    ZG_REQUIRE(attn_qkv_ok(g, at) && epoch != nullptr && qkv_tag != nullptr && at.launch_id >= 1 && at.launch_id <= 255, ZG_ERR_ARG,
+int launch_attn_qkv(const GemvArgs& g, const GemvPlan& p, int weight_type, const AttnArgs& at, const unsigned* epoch, unsigned long long* qkv_tag,
+                    hipStream_t s) {
+    ZG_REQUIRE(attn_qkv_ok(g, p, at) && epoch != nullptr && qkv_tag != nullptr && at.launch_id >= 1 && at.launch_id <= 255, ZG_ERR_ARG,
                "fused c_attn + attention: unsupported arguments");
     ZG_REQUIRE(at.t_hi >= 1 && at.t_hi < (1 << 20) && at.n_heads < (1 << 12), ZG_ERR_UNSUPPORTED, "fused attention: t_hi %d / heads %d", at.t_hi,
                at.n_heads);
@@ -84,13 +85,12 @@ int launch_attn_qkv(const GemvArgs& g, int weight_type, const AttnArgs& at, cons
     f.ew = epoch;
     f.qkv_tag = qkv_tag;
     const int* cw = reinterpret_cast<const int*>(g.ctrl);
-    const int nchq = g.K / 32;
+    // the c_attn role: the row mapping and instantiation of the lnk plan
+    const unsigned G = (unsigned)p.grid;
+    f.a0 = (G + 7u) & ~7u;
+    const unsigned grid = f.a0 + (unsigned)(at.n_heads * splits);
 #define ZG_QA(LPR_, CPL_)                                                                                                          \
-    {                                                                                                                              \
-        constexpr int rows = 4 * (64 / LPR_);                                                                                      \
-        const unsigned G = (unsigned)((g.N + rows - 1) / rows);                                                                    \
-        f.a0 = (G + 7u) & ~7u;                                                                                                     \
-        const unsigned grid = f.a0 + (unsigned)(at.n_heads * splits);                                                              \
+    if (p.lpr == LPR_ && p.cpl == CPL_) {                                                                                          \
         note_kernel("attn_qkv_kernel<%s, %d, %d>", weight_type == WT_BF16 ? "unsigned short" : weight_type == WT_B24 ? "b24" : "float", \
                     LPR_, CPL_);                                                                                                   \
         if (weight_type == WT_BF16)                                                                                                \
@@ -105,13 +105,12 @@ int launch_attn_qkv(const GemvArgs& g, int weight_type, const AttnArgs& at, cons
         ZG_HIP(hipGetLastError());                                                                                                 \
         return ZG_OK;                                                                                                              \
     }
-    // the row mapping of launch_lnk (gemv_ksplit.hip)
-    if (nchq <= 16 * 2) ZG_QA(16, 2)
-    if (nchq <= 32 * 2) ZG_QA(32, 2)
-    if (nchq <= 32 * 3) ZG_QA(32, 3)
-    if (nchq <= 64 * 2) ZG_QA(64, 2)
+    ZG_QA(16, 2)
+    ZG_QA(32, 2)
+    ZG_QA(32, 3)
+    ZG_QA(64, 2)
 #undef ZG_QA
-    zg::set_error("fused c_attn + attention: K=%d too large", g.K);
+    zg::set_error("fused c_attn + attention: no instantiation for K=%d", g.K);
     return ZG_ERR_UNSUPPORTED;
 }
 

@@ -1,7 +1,8 @@
-// gemv_internal.h — what the GEMV translation units share (gemv.hip: planning and dispatch; gemv_valu.hip: the general VALU
+// gemv_internal.h — what the GEMV translation units share (gemv.hip: the plan and its dispatch; gemv_valu.hip: the general VALU
 // kernel; gemv_ksplit.hip: the two M = 1 K-split kernels; gemv_mfma16.hip: the 16-wave matrix-core kernel; gemv_pl4.hip: the
-// four-wave plane-fed kernel and the wave-per-tile lm_head).  Device helpers live in an anonymous namespace: every unit gets
-// its own copy.
+// four-wave plane-fed kernel and the wave-per-tile lm_head): device helpers and, at the end, the units' launchers.  No shape
+// test lives here — a launch's route and layout are gemv_plan's (gemv.hip).  Device helpers live in an anonymous namespace:
+// every unit gets its own copy.
 #pragma once
 #include <stdlib.h>
 
@@ -399,48 +400,6 @@ __device__ __forceinline__ void store_split4(char* planes, int S, int m, int k, 
     *reinterpret_cast<u32x2*>(planes + 2 * plane + off) = l;
 }
 
-// ---- host-side shape tests shared by the launchers and the planner
-inline int lm_wpt_steps(const GemvArgs& a) {
-    const int off = decode_paths_off() & 32;  // read per call: tests flip it between handles
-    if (off || a.epilogue != EPI_ARGMAX || a.prologue != PRO_LAYERNORM || a.M < 2 || a.M > kMfmaRows || a.K % 32 != 0) return 0;
-    const int ns = a.K / 32;
-    return (ns == 12 || ns == 24 || ns == 32) ? ns : 0;
-}
-inline int lm_wpt_tiles_per_wg() {  // a multiple of the four waves
-    constexpr int v = 8;  // (sweep: profiles/round4_lm_head_tiles_sweep.txt)
-    return v >= 4 ? (v / 4) * 4 : 4;
-}
-
-inline int gemv_mfma_waves(const GemvArgs& a) { return a.epilogue == EPI_ARGMAX ? 4 : 16; }
-
-inline size_t gemv_mfma_lds(int K, int nw, bool alias_partial = false, bool line = false, bool gpl = false) {
-    const size_t planes = gpl ? 0 : (size_t)3 * kMfmaRows * (2 * K + 16);
-    return planes + 64 * sizeof(float) + (alias_partial ? 0 : (size_t)2 * nw * 64 * 4 * sizeof(float)) + (line ? (size_t)nw * 2048 : 0);
-}
-// full-line weight loads (LINE instantiations): whole pairs of 32-k steps and room for one 2-KiB slot per wave
-inline bool gemv_mfma_line(int K, int nw, bool alias_partial, bool gpl = false) {
-    const int off = decode_paths_off() & 16;  // read per call: tests flip it between handles
-    return !off && !alias_partial && K % 64 == 0 && gemv_mfma_lds(K, nw, false, true, gpl) <= 160 * 1024;
-}
-
-// single-tile workgroups may let the partial tiles alias the planes (see the kernel)
-inline bool gemv_mfma_alias(const GemvArgs& a) {
-    return a.kslices <= 1 && a.epilogue != EPI_ARGMAX && a.rows_per_wave == 1 && gemv_mfma_lds(a.K, 16) > 160 * 1024;
-}
-
-// Plane-fed Linears as four-wave workgroups (gemv_pl4_kernel): one tile per workgroup, whole 64-k pairs, at most five
-// pairs per wave and slice (K <= 1280 per slice: every GPT-2 size but XL, which stays on the 16-wave kernel).
-inline int pl4_pairs(const GemvArgs& a) {
-    const int off = decode_paths_off() & 2;  // read per call: tests flip it between handles
-    if (off || a.pl_in == nullptr || a.epilogue == EPI_ARGMAX || a.rows_per_wave != 1) return 0;
-    if (a.N > 0xffff || (a.prologue == PRO_LAYERNORM && a.x_stride != a.K) || (a.epilogue == EPI_RESIDUAL && a.resid_stride != a.N)) return 0;
-    if (a.st_in != nullptr && a.K / 16 > 128) return 0;
-    const int ksl = a.kslices > 1 ? a.kslices : 1;
-    if (a.K % (64 * ksl) != 0) return 0;
-    const int kp = (a.K / ksl / 64 + 3) / 4;
-    return kp <= 5 ? kp : 0;
-}
-
 // Body of gemv_lnk_kernel (gemv_ksplit.hip; the LayerNorm fold is described there), shared with the c_attn role of the fused
 // ln_1 + c_attn + attention kernel (attn_qkv.hip).  blk = the workgroup's row block; pf_inc = what block 0 adds to the
 // prefetcher's launch counter.  TAGGED (EPI_QKV, one sequence): every output row is also stored as a (value, tag) word at
@@ -571,14 +530,14 @@ __device__ __forceinline__ void gemv_lnk_body(int blk, const void* __restrict__ 
 
 }  // namespace
 
-// ---- launchers of the units (gemv.hip decides which one a launch takes)
-bool gemv_use_ksplit(const GemvArgs& a);
-bool gemv_use_lnk(const GemvArgs& a);
-int gemv_launch_ksplit(const GemvArgs& a, int weight_type, hipStream_t s);
-int gemv_launch_lnk(const GemvArgs& a, int weight_type, hipStream_t s);
-int gemv_launch_valu(const GemvArgs& a, int weight_type, int grid, hipStream_t s);
-int gemv_launch_mfma16(const GemvArgs& a, int grid, hipStream_t s);            // 16-wave kernel (4 waves for lm_head), K slices
-int gemv_launch_pl4(const GemvArgs& a, int pairs, int grid, hipStream_t s);    // pairs = pl4_pairs(a) in 1..5
-int gemv_launch_lm_wpt(const GemvArgs& a, int steps, int grid, hipStream_t s);  // steps = lm_wpt_steps(a) in {12, 24, 32}
+// ---- launchers of the units: a = the arguments with the plan's layout written in (launch_gemv), p = the plan.  They map the
+// plan's template choice to an instantiation and launch dim3(p.grid, p.kslices) x p.block with p.lds bytes; no shape is judged here.
+constexpr size_t kGemvLdsMax = 160 * 1024;  // the LDS of a CU
+int gemv_launch_ksplit(const GemvArgs& a, const GemvPlan& p, int weight_type, hipStream_t s);
+int gemv_launch_lnk(const GemvArgs& a, const GemvPlan& p, int weight_type, hipStream_t s);
+int gemv_launch_valu(const GemvArgs& a, const GemvPlan& p, int weight_type, hipStream_t s);  // GR_VALU, GR_GENERIC
+int gemv_launch_mfma16(const GemvArgs& a, const GemvPlan& p, hipStream_t s);  // 16-wave kernel (4 waves for lm_head), K slices
+int gemv_launch_pl4(const GemvArgs& a, const GemvPlan& p, hipStream_t s);
+int gemv_launch_lm_wpt(const GemvArgs& a, const GemvPlan& p, hipStream_t s);
 
 }  // namespace zg

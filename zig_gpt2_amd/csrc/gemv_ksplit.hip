@@ -137,30 +137,28 @@ __global__ __launch_bounds__(256) void gemv_ksplit_kernel(const void* __restrict
 }
 
 template <typename WT>
-int launch_ksplit(const GemvArgs& a, hipStream_t s) {
-    const int nchq = a.K / 32;  // 16-B chunks per quarter row
+int launch_ksplit(const GemvArgs& a, const GemvPlan& pl, hipStream_t s) {
     const int merge_splits = a.prologue == PRO_ATTN_MERGE ? (a.t_hi + kAttnChunk - 1) / kAttnChunk : 0;
     const unsigned has_resid = a.epilogue == EPI_RESIDUAL ? 1u : 0u;
     const unsigned em = (unsigned)a.epilogue | ((unsigned)merge_splits << 8) | ((a.bias ? 1u : 0u) << 16) | (has_resid << 17);
-    // two passes of 64 / LPR rows per workgroup (four measured slower: 2.65 -> 3.3 us for mlp c_proj)
+    // two passes of 64 / LPR rows per workgroup
 #define ZG_KS(LPR_, CPL_)                                                                                                \
-    {                                                                                                                    \
-        constexpr int rows = 2 * (64 / LPR_);                                                                            \
+    if (pl.lpr == LPR_ && pl.cpl == CPL_) {                                                                              \
         note_kernel("gemv_ksplit_kernel<%s, %d, %d, 2>", wt_name<WT>(), LPR_, CPL_);         \
-        hipLaunchKernelGGL((gemv_ksplit_kernel<WT, LPR_, CPL_, 2>), dim3((a.N + rows - 1) / rows), dim3(256), 0, s, a.W,     \
+        hipLaunchKernelGGL((gemv_ksplit_kernel<WT, LPR_, CPL_, 2>), dim3(pl.grid), dim3(256), 0, s, a.W,                     \
                            a.x,                                                                                         \
                            a.N, a.K, em, a.part ? a.part : a.zero, a.max_splits, a.bias ? a.bias : a.zero,              \
                            has_resid ? a.resid : a.zero, a);                                                             \
         ZG_HIP(hipGetLastError());                                                                                       \
         return ZG_OK;                                                                                                    \
     }
-    if (nchq <= 16 * 2) ZG_KS(16, 2)
-    if (nchq <= 32 * 3) ZG_KS(32, 3)
-    if (nchq <= 32 * 5) ZG_KS(32, 5)
-    if (nchq <= 32 * 7) ZG_KS(32, 7)
-    if (nchq <= 64 * 4) ZG_KS(64, 4)
+    ZG_KS(16, 2)
+    ZG_KS(32, 3)
+    ZG_KS(32, 5)
+    ZG_KS(32, 7)
+    ZG_KS(64, 4)
 #undef ZG_KS
-    zg::set_error("gemv (K split): K=%d too large", a.K);
+    zg::set_error("gemv (K split): no instantiation for K=%d", a.K);
     return ZG_ERR_UNSUPPORTED;
 }
 
@@ -215,25 +213,23 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const void* __restrict__ W
 }
 
 template <typename WT>
-int launch_lnk(const GemvArgs& a, hipStream_t s) {
-    const int nchq = a.K / 32;
-    // four passes of 64 / LPR rows per workgroup (2.93 against 3.2 us per launch with two; +1 % tokens/s in situ)
+int launch_lnk(const GemvArgs& a, const GemvPlan& pl, hipStream_t s) {
+    // four passes of 64 / LPR rows per workgroup
 #define ZG_LK(LPR_, CPL_)                                                                                              \
-    {                                                                                                                  \
-        constexpr int rows = 4 * (64 / LPR_);                                                                          \
+    if (pl.lpr == LPR_ && pl.cpl == CPL_) {                                                                            \
         note_kernel("gemv_lnk_kernel<%s, %d, %d, 4>", wt_name<WT>(), LPR_, CPL_);       \
-        hipLaunchKernelGGL((gemv_lnk_kernel<WT, LPR_, CPL_, 4>), dim3((a.N + rows - 1) / rows), dim3(256), 0, s, a.W, a.x, \
+        hipLaunchKernelGGL((gemv_lnk_kernel<WT, LPR_, CPL_, 4>), dim3(pl.grid), dim3(256), 0, s, a.W, a.x,             \
                            (unsigned)a.N | ((unsigned)a.epilogue << 24), a.K, a.ln_g, a.ln_c2, a.ln_c3,                 \
                            a.ctrl ? reinterpret_cast<const int*>(a.ctrl) : reinterpret_cast<const int*>(a.zero), a);   \
         ZG_HIP(hipGetLastError());                                                                                     \
         return ZG_OK;                                                                                                  \
     }
-    if (nchq <= 16 * 2) ZG_LK(16, 2)
-    if (nchq <= 32 * 2) ZG_LK(32, 2)
-    if (nchq <= 32 * 3) ZG_LK(32, 3)
-    if (nchq <= 64 * 2) ZG_LK(64, 2)
+    ZG_LK(16, 2)
+    ZG_LK(32, 2)
+    ZG_LK(32, 3)
+    ZG_LK(64, 2)
 #undef ZG_LK
-    zg::set_error("gemv (LayerNorm, K split): K=%d too large", a.K);
+    zg::set_error("gemv (LayerNorm, K split): no instantiation for K=%d", a.K);
     return ZG_ERR_UNSUPPORTED;
 }
 
@@ -242,29 +238,13 @@ int launch_lnk(const GemvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-// M == 1 plain Linear over a wide input: the K-split kernel (measured against the shared-strip form in situ)
-bool gemv_use_ksplit(const GemvArgs& a) {
-    if (a.M != 1) return false;
-    if (a.epilogue != EPI_STORE && a.epilogue != EPI_RESIDUAL && a.epilogue != EPI_GELU) return false;
-    if (a.prologue == PRO_ATTN_MERGE)  // head merge folded into the lanes' own chunks: model tier, <= 4 splits known at launch
-        return a.head_dim == 64 && a.t_hi > 0 && (a.t_hi + kAttnChunk - 1) / kAttnChunk <= 4 && a.K % 32 == 0 && a.K <= 1024;  // wider rows (XL, K = 1600: three chunks per lane) measured slower than the shared strip
-    if (a.prologue != PRO_NONE) return false;
-    return a.K >= 2048 && a.K % 32 == 0 && a.K / 32 <= 256;
+int gemv_launch_ksplit(const GemvArgs& a, const GemvPlan& p, int weight_type, hipStream_t s) {
+    if (weight_type == WT_B24) return launch_ksplit<b24_t>(a, p, s);
+    return weight_type == WT_BF16 ? launch_ksplit<bf16_t>(a, p, s) : launch_ksplit<float>(a, p, s);
 }
-
-bool gemv_use_lnk(const GemvArgs& a) {
-    if (a.M != 1 || a.prologue != PRO_LAYERNORM || a.ln_c2 == nullptr || a.ln_c3 == nullptr) return false;
-    if (a.epilogue != EPI_STORE && a.epilogue != EPI_GELU && a.epilogue != EPI_QKV) return false;
-    return a.K % 32 == 0 && a.K / 32 <= 128 && a.N <= 16384;
-}
-
-int gemv_launch_ksplit(const GemvArgs& a, int weight_type, hipStream_t s) {
-    if (weight_type == WT_B24) return launch_ksplit<b24_t>(a, s);
-    return weight_type == WT_BF16 ? launch_ksplit<bf16_t>(a, s) : launch_ksplit<float>(a, s);
-}
-int gemv_launch_lnk(const GemvArgs& a, int weight_type, hipStream_t s) {
-    if (weight_type == WT_B24) return launch_lnk<b24_t>(a, s);
-    return weight_type == WT_BF16 ? launch_lnk<bf16_t>(a, s) : launch_lnk<float>(a, s);
+int gemv_launch_lnk(const GemvArgs& a, const GemvPlan& p, int weight_type, hipStream_t s) {
+    if (weight_type == WT_B24) return launch_lnk<b24_t>(a, p, s);
+    return weight_type == WT_BF16 ? launch_lnk<bf16_t>(a, p, s) : launch_lnk<float>(a, p, s);
 }
 
 int launch_ln_fold(const void* W, int weight_type, const float* g, const float* b, const float* bias, int N, int K, float* c2,

@@ -506,59 +506,51 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_kernel(const bf16_t* __rest
 }
 
 template <int KS, int NW, bool ARGMAX, int KSL, bool LINE, bool GPL = false>
-int launch_mfma_inst2(const GemvArgs& a, int grid, bool alias, hipStream_t s) {
-    const size_t lds = gemv_mfma_lds(a.K / KSL, NW, alias, LINE, GPL);
-    GemvArgs b = a;
-    b.waves_per_wg = alias ? -1 : NW;  // < 0: partial tiles alias the planes
+int launch_mfma_inst2(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
     static bool raised = false;
-    if (lds > 64 * 1024 && !raised) {
+    if (p.lds > 64 * 1024 && !raised) {
         ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_mfma_kernel<KS, NW, ARGMAX, KSL, LINE, GPL>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         raised = true;
     }
     note_kernel("gemv_mfma_kernel<%d, %d, %s, %d, %s, %s>", KS, NW, ARGMAX ? "true" : "false", KSL, LINE ? "true" : "false", GPL ? "true" : "false");
-    hipLaunchKernelGGL((gemv_mfma_kernel<KS, NW, ARGMAX, KSL, LINE, GPL>), dim3(grid, KSL), dim3(NW * 64), lds, s,
+    hipLaunchKernelGGL((gemv_mfma_kernel<KS, NW, ARGMAX, KSL, LINE, GPL>), dim3(p.grid, KSL), dim3(NW * 64), p.lds, s,
                        reinterpret_cast<const bf16_t*>(a.W), a.x, a.N, a.K / KSL, a.M, a.rows_per_wave, a.prologue,
-                       a.epilogue, a.ln_g, a.ln_b, b);
+                       a.epilogue, a.ln_g, a.ln_b, a);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }
 
 template <int KS, int NW, bool ARGMAX, int KSL = 1>
-int launch_mfma_inst(const GemvArgs& a, int grid, hipStream_t s) {
+int launch_mfma_inst(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
     if constexpr (!ARGMAX && NW == 16) {
-        if (a.pl_in) {  // input planes in global memory: no LDS planes, nothing to alias
-            if (gemv_mfma_line(a.K / KSL, NW, false, true)) return launch_mfma_inst2<KS, NW, ARGMAX, KSL, true, true>(a, grid, false, s);
-            return launch_mfma_inst2<KS, NW, ARGMAX, KSL, false, true>(a, grid, false, s);
+        if (p.gpl) {  // input planes in global memory
+            if (p.line) return launch_mfma_inst2<KS, NW, ARGMAX, KSL, true, true>(a, p, s);
+            return launch_mfma_inst2<KS, NW, ARGMAX, KSL, false, true>(a, p, s);
         }
     }
-    const bool alias = KSL == 1 && gemv_mfma_alias(a);
-    if (gemv_mfma_line(a.K / KSL, NW, alias)) return launch_mfma_inst2<KS, NW, ARGMAX, KSL, true>(a, grid, alias, s);
-    return launch_mfma_inst2<KS, NW, ARGMAX, KSL, false>(a, grid, alias, s);
+    if (p.line) return launch_mfma_inst2<KS, NW, ARGMAX, KSL, true>(a, p, s);
+    return launch_mfma_inst2<KS, NW, ARGMAX, KSL, false>(a, p, s);
 }
 
 
 }  // namespace
 
-int gemv_launch_mfma16(const GemvArgs& a, int grid, hipStream_t s) {
-    if (a.kslices == 4) {  // four K slices over four workgroups per tile (gemv_kslices)
-        const int ks = (a.K / 4 / 32 + 15) / 16;
-        if (ks <= 2) return launch_mfma_inst<2, 16, false, 4>(a, grid, s);
-        if (ks <= 4) return launch_mfma_inst<4, 16, false, 4>(a, grid, s);
-        return launch_mfma_inst<6, 16, false, 4>(a, grid, s);
+int gemv_launch_mfma16(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+    switch ((p.route == GR_MFMA16_KS ? 10000 : 0) + p.nw * 100 + p.ks) {
+        case 11602: return launch_mfma_inst<2, 16, false, 4>(a, p, s);  // four K slices over four workgroups per tile
+        case 11604: return launch_mfma_inst<4, 16, false, 4>(a, p, s);
+        case 11606: return launch_mfma_inst<6, 16, false, 4>(a, p, s);
+        case 403: return launch_mfma_inst<3, 4, true>(a, p, s);  // lm_head: 4 waves
+        case 406: return launch_mfma_inst<6, 4, true>(a, p, s);
+        case 413: return launch_mfma_inst<13, 4, true>(a, p, s);
+        case 424: return launch_mfma_inst<24, 4, true>(a, p, s);
+        case 1602: return launch_mfma_inst<2, 16, false>(a, p, s);
+        case 1604: return launch_mfma_inst<4, 16, false>(a, p, s);
+        case 1606: return launch_mfma_inst<6, 16, false>(a, p, s);
+        default: break;
     }
-    const int steps = a.K / 32;
-    if (a.epilogue == EPI_ARGMAX) {  // lm_head: 4 waves
-        const int ks = (steps + 3) / 4;
-        if (ks <= 3) return launch_mfma_inst<3, 4, true>(a, grid, s);
-        if (ks <= 6) return launch_mfma_inst<6, 4, true>(a, grid, s);
-        if (ks <= 13) return launch_mfma_inst<13, 4, true>(a, grid, s);
-        return launch_mfma_inst<24, 4, true>(a, grid, s);
-    }
-    const int ks = (steps + 15) / 16;
-    if (ks <= 2) return launch_mfma_inst<2, 16, false>(a, grid, s);
-    if (ks <= 4) return launch_mfma_inst<4, 16, false>(a, grid, s);
-    return launch_mfma_inst<6, 16, false>(a, grid, s);
+    ZG_REQUIRE(false, ZG_ERR_ARG, "gemv_mfma: no instantiation for %d waves x %d steps", p.nw, p.ks);
 }
 
 }  // namespace zg

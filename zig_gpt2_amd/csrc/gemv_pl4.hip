@@ -478,11 +478,10 @@ __global__ __launch_bounds__(256) void lm_head_wpt_kernel(const bf16_t* __restri
     }
 }
 
-// Which lm_head launches take the wave-per-tile kernel: the K values whose tile fits a wave's registers.
 template <int NS>
-int launch_lm_wpt(const GemvArgs& a, int grid, hipStream_t s) {
-    const size_t lds = (size_t)3 * kMfmaRows * (2 * a.K + 16) + 4 * kMfmaRows * sizeof(Best) + 4 * 4096;
-    if (lds > 64 * 1024) {  // K = 1024 (NS = 32): 66,176 B — opt in once per instantiation, like every other launcher here
+int launch_lm_wpt(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+    static_assert(sizeof(Best) == 8, "gemv_plan sizes this kernel's LDS with 8-byte (value, index) records");
+    if (p.lds > 64 * 1024) {  // K = 1024 (NS = 32): 66,176 B — opt in once per instantiation, like every other launcher here
         static bool raised = false;
         if (!raised) {
             ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lm_head_wpt_kernel<NS>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -491,16 +490,16 @@ int launch_lm_wpt(const GemvArgs& a, int grid, hipStream_t s) {
         }
     }
     note_kernel("lm_head_wpt_kernel<%d>", NS);
-    hipLaunchKernelGGL((lm_head_wpt_kernel<NS>), dim3(grid), dim3(256), lds, s, reinterpret_cast<const bf16_t*>(a.W), a.x, a.N, a.K,
+    hipLaunchKernelGGL((lm_head_wpt_kernel<NS>), dim3(p.grid), dim3(256), p.lds, s, reinterpret_cast<const bf16_t*>(a.W), a.x, a.N, a.K,
                        a.M, a.rows_per_wave, a.ln_g, a.ln_b, a);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }
 
 template <int KP>
-int launch_pl4(const GemvArgs& a, int grid, hipStream_t s) {
+int launch_pl4(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
     const bool ln = a.prologue == PRO_LAYERNORM;
-    const int ksl = a.kslices == 4 ? 4 : 1;
+    const int ksl = p.kslices, grid = p.grid;
     note_kernel("gemv_pl4_kernel<%d, %d>", KP, ksl);
     const unsigned nk = (unsigned)a.N | ((unsigned)(a.K / ksl) << 16);
     const float* e0 = ln ? a.ln_c2 : a.bias;
@@ -528,25 +527,25 @@ int launch_pl4(const GemvArgs& a, int grid, hipStream_t s) {
 
 }  // namespace
 
-int gemv_launch_pl4(const GemvArgs& a, int pairs, int grid, hipStream_t s) {
-    switch (pairs) {
-        case 1: return launch_pl4<1>(a, grid, s);
-        case 2: return launch_pl4<2>(a, grid, s);
-        case 3: return launch_pl4<3>(a, grid, s);
-        case 4: return launch_pl4<4>(a, grid, s);
-        case 5: return launch_pl4<5>(a, grid, s);
+int gemv_launch_pl4(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+    switch (p.pairs) {
+        case 1: return launch_pl4<1>(a, p, s);
+        case 2: return launch_pl4<2>(a, p, s);
+        case 3: return launch_pl4<3>(a, p, s);
+        case 4: return launch_pl4<4>(a, p, s);
+        case 5: return launch_pl4<5>(a, p, s);
         default: break;
     }
-    ZG_REQUIRE(false, ZG_ERR_ARG, "gemv_pl4: %d pairs per wave", pairs);
+    ZG_REQUIRE(false, ZG_ERR_ARG, "gemv_pl4: %d pairs per wave", p.pairs);
 }
-int gemv_launch_lm_wpt(const GemvArgs& a, int steps, int grid, hipStream_t s) {
-    switch (steps) {
-        case 12: return launch_lm_wpt<12>(a, grid, s);
-        case 24: return launch_lm_wpt<24>(a, grid, s);
-        case 32: return launch_lm_wpt<32>(a, grid, s);
+int gemv_launch_lm_wpt(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+    switch (p.steps) {
+        case 12: return launch_lm_wpt<12>(a, p, s);
+        case 24: return launch_lm_wpt<24>(a, p, s);
+        case 32: return launch_lm_wpt<32>(a, p, s);
         default: break;
     }
-    ZG_REQUIRE(false, ZG_ERR_ARG, "lm_head_wpt: %d steps per tile", steps);
+    ZG_REQUIRE(false, ZG_ERR_ARG, "lm_head_wpt: %d steps per tile", p.steps);
 }
 
 }  // namespace zg

@@ -366,10 +366,8 @@ __global__ __launch_bounds__(256) void gemv_generic_kernel(const GemvArgs a) {
 
 
 template <typename WT, int MT, int LPR, int CPL, bool ARGMAX>
-int launch_inst(const GemvArgs& a, int grid, hipStream_t s) {
-    const int wpw = (MT == 1 && a.waves_per_wg >= 1 && a.waves_per_wg <= 4) ? a.waves_per_wg : 4;
-    const size_t lds = ((size_t)(MT == 1 ? wpw : MT) * a.K + 4 * MT * 2 + 64) * sizeof(float);
-    if (lds > 64 * 1024) {
+int launch_inst(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+    if (p.lds > 64 * 1024) {
         static bool raised = false;  // opt in once per instantiation to >64 KiB dynamic LDS
         if (!raised) {
             ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<WT, MT, LPR, CPL, ARGMAX>),
@@ -377,62 +375,61 @@ int launch_inst(const GemvArgs& a, int grid, hipStream_t s) {
             raised = true;
         }
     }
-    ZG_REQUIRE(lds <= 160 * 1024, ZG_ERR_UNSUPPORTED, "gemv: M=%d x K=%d does not fit LDS", a.M, a.K);
     note_kernel("gemv_kernel<%s, %d, %d, %d, %s>", wt_name<WT>(), MT, LPR, CPL, ARGMAX ? "true" : "false");
-    hipLaunchKernelGGL((gemv_kernel<WT, MT, LPR, CPL, ARGMAX>), dim3(grid), dim3(64 * wpw), lds, s, a.W, a.x, a.N, a.K,
-                       (unsigned)a.M | ((unsigned)a.prologue << 4) | ((unsigned)a.epilogue << 8) | ((unsigned)wpw << 12), a.rows_per_wave,
+    hipLaunchKernelGGL((gemv_kernel<WT, MT, LPR, CPL, ARGMAX>), dim3(p.grid), dim3(p.block), p.lds, s, a.W, a.x, a.N, a.K,
+                       (unsigned)a.M | ((unsigned)a.prologue << 4) | ((unsigned)a.epilogue << 8) | ((unsigned)p.waves_per_wg << 12), a.rows_per_wave,
                        a.ln_g, a.ln_b, a.ctrl ? reinterpret_cast<const int*>(a.ctrl) : reinterpret_cast<const int*>(a.zero), a);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }
 
 template <typename WT, int MT, int LPR, int CPL>
-int launch_inst(const GemvArgs& a, int grid, hipStream_t s) {
+int launch_inst(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
     // The greedy-sampler epilogue is its own instantiation (distinct kernel name in profiles, and the
     // other kernels carry no argmax state).
-    if (a.epilogue == EPI_ARGMAX) return launch_inst<WT, MT, LPR, CPL, true>(a, grid, s);
-    return launch_inst<WT, MT, LPR, CPL, false>(a, grid, s);
+    if (a.epilogue == EPI_ARGMAX) return launch_inst<WT, MT, LPR, CPL, true>(a, p, s);
+    return launch_inst<WT, MT, LPR, CPL, false>(a, p, s);
 }
 
 template <typename WT, int MT>
-int launch_mt(const GemvArgs& a, int grid, hipStream_t s) {
-    const int nch = a.K / 8;
-    if (nch <= 16 * 2) return launch_inst<WT, MT, 16, 2>(a, grid, s);
-    if (nch <= 16 * 4) return launch_inst<WT, MT, 16, 4>(a, grid, s);
-    if (nch <= 16 * 6) return launch_inst<WT, MT, 16, 6>(a, grid, s);
-    if (nch <= 16 * 8) return launch_inst<WT, MT, 16, 8>(a, grid, s);
-    if (nch <= 32 * 6) return launch_inst<WT, MT, 32, 6>(a, grid, s);
-    if (nch <= 32 * 8) return launch_inst<WT, MT, 32, 8>(a, grid, s);
-    if (nch <= 64 * 6) return launch_inst<WT, MT, 64, 6>(a, grid, s);
-    if (nch <= 64 * 8) return launch_inst<WT, MT, 64, 8>(a, grid, s);
-    if (nch <= 64 * 16) return launch_inst<WT, MT, 64, 16>(a, grid, s);
-    zg::set_error("gemv: K=%d too large (max 8192)", a.K);
+int launch_mt(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+    switch (p.lpr * 100 + p.cpl) {
+        case 1602: return launch_inst<WT, MT, 16, 2>(a, p, s);
+        case 1604: return launch_inst<WT, MT, 16, 4>(a, p, s);
+        case 1606: return launch_inst<WT, MT, 16, 6>(a, p, s);
+        case 1608: return launch_inst<WT, MT, 16, 8>(a, p, s);
+        case 3206: return launch_inst<WT, MT, 32, 6>(a, p, s);
+        case 3208: return launch_inst<WT, MT, 32, 8>(a, p, s);
+        case 6406: return launch_inst<WT, MT, 64, 6>(a, p, s);
+        case 6408: return launch_inst<WT, MT, 64, 8>(a, p, s);
+        case 6416: return launch_inst<WT, MT, 64, 16>(a, p, s);
+        default: break;
+    }
+    zg::set_error("gemv: no instantiation for K=%d", a.K);
     return ZG_ERR_UNSUPPORTED;
 }
 
 template <typename WT>
-int launch_wt(const GemvArgs& a, int grid, hipStream_t s) {
-    if (a.K % 8 != 0) {
-        ZG_REQUIRE(a.prologue == PRO_NONE && a.epilogue == EPI_STORE, ZG_ERR_UNSUPPORTED,
-                   "gemv: K=%d not a multiple of 8 is only supported for plain Linear", a.K);
-        hipLaunchKernelGGL((gemv_generic_kernel<WT>), dim3((a.N + 3) / 4), dim3(256), 0, s, a);
+int launch_wt(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+    if (p.route == GR_GENERIC) {  // slow fallback for K % 8 != 0 (op tier only): one wave per row, scalar loads
+        hipLaunchKernelGGL((gemv_generic_kernel<WT>), dim3(p.grid), dim3(p.block), 0, s, a);
         ZG_HIP(hipGetLastError());
         return ZG_OK;
     }
-    if (a.M <= 1) return launch_mt<WT, 1>(a, grid, s);
-    if (a.M <= 2) return launch_mt<WT, 2>(a, grid, s);
-    if (a.M <= 4) return launch_mt<WT, 4>(a, grid, s);
-    if (a.M <= 8) return launch_mt<WT, 8>(a, grid, s);
-    zg::set_error("gemv: M=%d > 8 rows per launch", a.M);
-    return ZG_ERR_UNSUPPORTED;
+    switch (p.mt) {
+        case 1: return launch_mt<WT, 1>(a, p, s);
+        case 2: return launch_mt<WT, 2>(a, p, s);
+        case 4: return launch_mt<WT, 4>(a, p, s);
+        default: return launch_mt<WT, 8>(a, p, s);
+    }
 }
 
 
 }  // namespace
 
-int gemv_launch_valu(const GemvArgs& a, int weight_type, int grid, hipStream_t s) {
-    if (weight_type == WT_B24) return launch_wt<b24_t>(a, grid, s);
-    return weight_type == WT_BF16 ? launch_wt<bf16_t>(a, grid, s) : launch_wt<float>(a, grid, s);
+int gemv_launch_valu(const GemvArgs& a, const GemvPlan& p, int weight_type, hipStream_t s) {
+    if (weight_type == WT_B24) return launch_wt<b24_t>(a, p, s);
+    return weight_type == WT_BF16 ? launch_wt<bf16_t>(a, p, s) : launch_wt<float>(a, p, s);
 }
 
 }  // namespace zg

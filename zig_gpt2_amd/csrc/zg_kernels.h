@@ -26,8 +26,10 @@ struct GemvArgs {
     const void* W;  // [N][K], bf16 bits, fp32 or B24 rows, K contiguous (ops.Linear.weight layout)
     const float* bias;  // [N] or nullptr
     int N, K, M;
+    // The layout: written by launch_gemv from the GemvPlan just before the launch (kslices below too); no caller reads or writes
+    // them.  waves_per_wg < 0: the 16-wave kernel's partial tiles alias its planes (GemvPlan.alias).
     int rows_per_wave;
-    int waves_per_wg;  // filled by gemv_plan (M == 1 kernels may run as 1..4-wave workgroups)
+    int waves_per_wg;
     int prologue, epilogue;
     // PRO_NONE / PRO_LAYERNORM input
     const float* x;  // [M][x_stride]
@@ -63,7 +65,7 @@ struct GemvArgs {
     int* part_idx;
     // split-K over workgroups (batched wide Linears): combine workspace [sk_tiles][4][128] floats and FOUR counters per
     // tile (zero between launches: the last arriver resets its counter; the 16-wave kernel uses counter [tile], the
-    // four-wave plane-fed kernel one per wave, [4 tile + wave]); kslices is filled by gemv_plan
+    // four-wave plane-fed kernel one per wave, [4 tile + wave]); kslices is written by launch_gemv (see rows_per_wave)
     float* sk_ws;
     int* sk_cnt;
     int sk_tiles;
@@ -95,22 +97,48 @@ struct GemvArgs {
     unsigned* progress;       // launch counter followed by the side-stream prefetcher (prefetch.hip); null = not counted
 };
 
-// Whether launch_gemv can run this M x K at all (batched kernels keep the M input rows in LDS).
-bool gemv_supported(const GemvArgs& a, int weight_type);
-// Whether this launch may take its input rows as planes in global memory (GemvArgs.pl_in).
-bool gemv_planes_ok(const GemvArgs& a, int weight_type);
-// ... and whether it can write its output rows as planes (GemvArgs.pl_out).
-bool gemv_planes_producer_ok(const GemvArgs& a, int weight_type);
-// Whether a planned plane-fed launch runs as the four-wave kernel (the one that writes / reads the tile statistics).
-bool gemv_pl4_ok(const GemvArgs& a, int weight_type);
-// Fills rows_per_wave and returns the grid size for the given problem.
-int gemv_plan(GemvArgs& a, int weight_type = WT_F32);
-int gemv_kslices(const GemvArgs& a);
-// Rows of W that one workgroup of the planned launch reads (block b: rows b * r .. (b + 1) * r - 1); 0 = another mapping
-int gemv_rows_per_wg(const GemvArgs& a, int weight_type);
+// Which kernel a decode-regime Linear takes and how it is laid out: decided once per launch by gemv_plan (gemv.hip holds every
+// shape threshold), carried out by launch_gemv.  Callers read the outcome here instead of asking shape questions of their own.
+enum GemvRoute {
+    GR_VALU = 0,         // gemv_kernel: any prologue / epilogue, M <= 8 rows in LDS
+    GR_VALU_GROUPS = 1,  // the same in row groups of row_group rows that fit the LDS (plain Linears: the rows are independent)
+    GR_GENERIC = 2,      // K % 8 != 0: one wave per row, plain Linear only
+    GR_KSPLIT = 3,       // M == 1, wide plain input or the head merge: the four waves split K
+    GR_LNK = 4,          // M == 1, LayerNorm folded out of the dot product
+    GR_MFMA16 = 5,       // 2..8 rows on the matrix cores: 16 waves (4 for lm_head)
+    GR_MFMA16_KS = 6,    // ... in four K slices over as many workgroups
+    GR_PL4 = 7,          // plane-fed four-wave kernel
+    GR_PL4_KS = 8,       // ... in four K slices
+    GR_LM_WPT = 9,       // lm_head, one wave per tile
+};
+struct GemvPlan {
+    int route;
+    int grid, kslices;  // dim3(grid, kslices)
+    int block;          // threads per workgroup
+    int lds;            // dynamic LDS bytes
+    // the instantiation of the route's kernel
+    int mt, lpr, cpl;   // VALU / K split / lnk: batch rows held (1, 2, 4, 8), lanes per row, 16-byte chunks per lane
+    int ks, nw;         // 16-wave kernel: 32-k steps per wave (its template bound) and waves
+    bool line, gpl, alias;  // ... line-shaped weight loads, input planes from global memory, partial tiles alias the planes
+    int pairs;          // plane-fed kernel: 64-k pairs per wave and slice
+    int steps;          // wave-per-tile lm_head: 32-k steps per tile
+    // what launch_gemv writes into GemvArgs
+    int rows_per_wave;  // rows per wave, or 16-row tiles per workgroup on the matrix cores
+    int waves_per_wg;
+    int row_group;      // GR_VALU_GROUPS: rows per group (each group is laid out on its own; the other fields describe the first)
+    // the prefetcher's view (api_gpt.hip emit_gemv): workgroup b reads rows b * rows_per_wg .. of W (0 = another mapping), in
+    // pf_tiles tiles — on GR_KSPLIT / GR_LNK still the VALU layout's workgroup count, as its job table has always had it, not `grid`
+    int rows_per_wg, pf_tiles;
+    bool supported;         // launch_gemv runs it
+    bool can_take_planes;   // may take its input rows as planes (GemvArgs.pl_in)
+    bool can_write_planes;  // may write its output rows as planes (GemvArgs.pl_out)
+    bool pl4_with_planes;   // given input planes it runs as the four-wave kernel (the one that reads / writes the tile statistics)
+};
+// Pure host code: no HIP call, no allocation.  Reads ZGPT2_DECODE_PATHS_OFF once (per call: tests flip it between handles).
+GemvPlan gemv_plan(const GemvArgs& a, int weight_type);
+int launch_gemv(const GemvArgs& a, const GemvPlan& p, int weight_type, hipStream_t s);
 int launch_ln_fold(const void* W, int weight_type, const float* g, const float* b, const float* bias, int N, int K, float* c2,
                    float* c3, hipStream_t s);
-int launch_gemv(const GemvArgs& a, int weight_type, int grid, hipStream_t s);
 
 // ------------------------------------------------------------------------------------ attention
 struct AttnArgs {
@@ -144,8 +172,8 @@ int launch_attn_decode(const AttnArgs& a, hipStream_t s);
 // attention (at) of the same layer in one launch (attn_qkv.hip).  q and the new k / v row reach the attention workgroups as
 // (value, tag) words in qkv_tag [3 E], tag = *epoch << 8 | at.launch_id; a timed-out wait raises at.fault.  Same results,
 // bit for bit, as launch_gemv + launch_attn_decode.
-bool attn_qkv_ok(const GemvArgs& g, const AttnArgs& at);
-int launch_attn_qkv(const GemvArgs& g, int weight_type, const AttnArgs& at, const unsigned* epoch, unsigned long long* qkv_tag, hipStream_t s);
+bool attn_qkv_ok(const GemvArgs& g, const GemvPlan& p, const AttnArgs& at);  // p = gemv_plan(g, ...)
+int launch_attn_qkv(const GemvArgs& g, const GemvPlan& p, int weight_type, const AttnArgs& at, const unsigned* epoch, unsigned long long* qkv_tag, hipStream_t s);
 // the op tier's general path for head_dim != 64 (fp32, one workgroup per (sequence, head))
 int launch_attn_any_dim(const float* q, const float* k, const float* v, long stride_b, long stride_h, long stride_t, int batch, int n_heads,
                         int head_dim, int seq_len, float* out, hipStream_t s);
