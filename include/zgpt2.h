@@ -202,6 +202,27 @@ int zg_debug_last_kernel(char* out, size_t n);
 #define ZG_PLAN_RAGGED_STRIDES 16u /* row strides of x / y / residual wider than the rows */
 int zg_debug_gemv_plan(int M, int N, int K, int prologue, int epilogue, int weight_type, unsigned operands, int sk_tiles, int t_hi, int* out,
                        size_t n_out);
+/* Diagnostic: the plan of a whole-prompt Linear C[M][N] = A[M][3 K] W[N][K]^T as zg_gpt_prefill would launch it — which GEMM
+ * family, which instantiation, its grid, and what finishes it — without launching anything; works without a GPU and without
+ * zg_init.  epilogue: 0 fp32 store, 1 residual add, 2 GELU + split planes, 4 qkv store + cache append; nsplit: activation planes
+ * multiplied (2 or 3), or 33 = fp32 weights as three planes; ws_floats: the split-K workspace; operands: what is present
+ * (ZG_PFPLAN_*; the cache description has n_embed = N / 3); sk_ws_bytes / sk_flags_words: the stream-K hand-over's buffers;
+ * force_kernel / force_slices as in zg_debug_prefill_linear (the pin of zg_debug_prefill_route is not read); ZGPT2_GEMM_WGS caps
+ * the persistent kernel's workgroups as in a launch.  out[ZG_PREFILL_PLAN_INTS]: status (ZG_OK or the refusal a launch would
+ * return; the rest is 0 then), family (1 persistent four-wave GEMM, 2 128-row kernel, 3 128-row three-pass kernel for fp32
+ * weights), tail (0 none, 1 LayerNorm + split, 2 reduce, 3 reduce then LayerNorm + split, 4 reduce + residual + LayerNorm + split
+ * in one), partial slabs through the workspace, grid x, grid y, block threads, dynamic LDS bytes, K slices, slabs the tail sums,
+ * 128-row kernels: 64-column strips per wave, planes multiplied, rows of the XCD grid, tile columns; persistent kernel: epilogue
+ * kind (1 partial slabs, 2 qkv, 3 GELU + split), stream-K hand-over, tile-order band width, plane pairs, A plane bits, B plane
+ * bits, B plane-major. */
+#define ZG_PREFILL_PLAN_INTS 21
+#define ZG_PFPLAN_WS 1u        /* a split-K workspace */
+#define ZG_PFPLAN_LN 2u        /* a LayerNorm follows (residual adds) */
+#define ZG_PFPLAN_QKV 4u       /* the cache description of the qkv epilogue */
+#define ZG_PFPLAN_SK_WS 8u     /* ... with a stream-K workspace */
+#define ZG_PFPLAN_SK_FLAGS 16u /* ... and flag words */
+int zg_debug_prefill_plan(int M, int N, int K, int ldc, int epilogue, int nsplit, size_t ws_floats, unsigned operands, size_t sk_ws_bytes,
+                          unsigned sk_flags_words, int force_kernel, int force_slices, int* out, size_t n_out);
 int zg_f32_to_bf16(const float* src, uint16_t* dst_device, size_t len);
 
 /* ------------------------------------------------------------------ model tier: src/main.zig */

@@ -3,6 +3,8 @@ zg_gpt_prefill launches it) on both GEMM families — the persistent four-wave k
 planes in one K loop (K slices + partial slabs for the residual adds, GELU + three-plane split), and the 128-row kernels of
 prefill.hip — against a float64 product of the same operands.  The operands are exact (fp32 rows as three bf16 planes, bf16
 weights), so the only error is fp32 accumulation order: the reference tolerance of src/tests.zig:4-20 applies."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -68,3 +70,7 @@ def test_prefill_linear_matches_float64(zg, monkeypatch, kernel, M, N, K, epilog
         assert_ref_close(gelu64(ref), got, f"gelu-split {M}x{N}x{K} kernel {kernel}", scale_floor=2e-6)
     took_s4 = zg.zg_debug_gemm_launches() - before
     assert took_s4 == (1 if kernel == 1 else 0), "the forced GEMM family did not run"
+    # ... and it is the family the planner reports for the same Linear and force (family 1 = the persistent four-wave GEMM)
+    plan = (ctypes.c_int * 21)()
+    _lib.check(zg.zg_debug_prefill_plan(M, N, K, N if epilogue == 1 else 0, epilogue, 3, ws.numel(), 1, 0, 0, kernel, slices if epilogue == 1 else 0, plan, 21))
+    assert (plan[0], plan[1] == 1) == (0, took_s4 == 1), list(plan)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Whole-prompt pass with the library's routing threshold (gemm_s4 from 192 tiles x K slices) against lower ones
-(zg_debug_prefill_route) — where the threshold of prefill.hip (s4_route) should sit.
+(zg_debug_prefill_route) — where the threshold of prefill.hip (prefill_gemm_plan, s4_slices) should sit.
 usage: python tools/experiments/pf_route_ab.py [--weights-f32] batch [batch ...]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -68,6 +68,7 @@ SIGNATURES = {
     "zg_debug_attn_prefill": (C.c_int, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, sz, C.c_int]),
     "zg_debug_attn_prefill_at": (C.c_int, [vp, vp, sz, sz, sz, sz, sz, vp, vp, C.c_int, sz, vp, sz, C.c_int]),
     "zg_debug_prefill_route": (C.c_int, [C.c_int, C.c_int]),
+    "zg_debug_prefill_plan": (C.c_int, [C.c_int] * 6 + [sz, C.c_uint, sz, C.c_uint, C.c_int, C.c_int, vp, sz]),
     "zg_debug_prefill_linear": (C.c_int, [vp, vp, vp, vp, sz, sz, sz, C.c_int, C.c_int, C.c_int, vp, sz]),
     "zg_linear_forward": (C.c_int, [sz, sz, vp, vp, vp, sz, vp, sz]),
     "zg_embedding_forward": (C.c_int, [sz, vp, sz, vp, sz, vp, sz]),

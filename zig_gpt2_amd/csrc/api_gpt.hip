@@ -679,7 +679,7 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
 // it is needed when generation re-feeds the last prompt token (main.zig:337).
 // fp32 weights (ZG_GPT_WEIGHTS_F32): the same pass; the weight operand is then the exact three-term bf16 split of the fp32
 // matrix (plane-major, made when the tensor is loaded; B24 weights: the split of the 24-bit values, the same pass) and every GEMM runs as three partial passes of the same kernel — the
-// six plane products above 2^-24 of the leading one, fp32-sgemm grade (prefill.hip launch_prefill_gemm_wp).
+// six plane products above 2^-24 of the leading one, fp32-sgemm grade (prefill.hip prefill_gemm_wp_kernel).
 // (Measured and dropped in round 4: replaying this pass from a hipGraph per prompt length.  0.844 against 0.749 ms at 64
 // tokens, 1.645 against 1.553 ms at 1023 — the ~10 us a launch costs here is the kernels' own latency at these sizes, not host
 // overhead, and a graph launch adds its own ~10 us; profiles/round4_prefill_graph.jsonl.)

@@ -593,10 +593,9 @@ int zg_debug_prefill_linear(const uint16_t* A, const uint16_t* W, const float* b
                    force_kernel <= 2 && slices >= 0,
                ZG_ERR_ARG, "debug_prefill_linear: arguments");
     const int epi = epilogue == 0 ? PF_F32 : epilogue == 1 ? PF_RESID : PF_GELU_SPLIT;
-    prefill_force_route(force_kernel, slices);
-    const int st = launch_prefill_gemm(A, W, bias, C, (int)M, (int)N, (int)K, epi == PF_GELU_SPLIT ? 0 : (int)N, epi, ws, ws_floats, nullptr, ctx().stream);
-    prefill_force_route(0, 0);
-    return st;
+    const PrefillForce force{force_kernel, slices};
+    return launch_prefill_gemm(A, W, bias, C, (int)M, (int)N, (int)K, epi == PF_GELU_SPLIT ? 0 : (int)N, epi, ws, ws_floats, nullptr, ctx().stream, nullptr,
+                               kSplit, &force);
 }
 
 int zg_debug_attn_prefill(const float* qkv, uint16_t* out, size_t batch, size_t n_tokens, size_t n_embed, size_t n_heads, const float* k_cache,
@@ -668,6 +667,22 @@ int zg_debug_gemv_plan(int M, int N, int K, int prologue, int epilogue, int weig
     const int v[ZG_GEMV_PLAN_INTS] = {p.route, p.grid, p.kslices, p.block, p.lds, p.mt, p.lpr, p.cpl, p.ks, p.nw, p.line, p.gpl, p.alias, p.pairs,
                                       p.steps, p.rows_per_wave, p.waves_per_wg, p.row_group, p.rows_per_wg, p.pf_tiles, p.supported,
                                       p.can_take_planes, p.can_write_planes, p.pl4_with_planes};
+    memcpy(out, v, sizeof(v));
+    return ZG_OK;
+}
+
+// Plans a described whole-prompt Linear (prefill_gemm_plan) without a GPU or zg_init.  Presence flags stand in for the operands;
+// nothing is dereferenced.  The process-wide pin of zg_debug_prefill_route is not read: the force is this call's.
+int zg_debug_prefill_plan(int M, int N, int K, int ldc, int epilogue, int nsplit, size_t ws_floats, unsigned operands, size_t sk_ws_bytes,
+                          unsigned sk_flags_words, int force_kernel, int force_slices, int* out, size_t n_out) {
+    ZG_REQUIRE(out != nullptr && n_out >= ZG_PREFILL_PLAN_INTS, ZG_ERR_ARG, "debug_prefill_plan: %d ints of output", ZG_PREFILL_PLAN_INTS);
+    PrefillGemmShape sh{M, N, K, ldc, epilogue, nsplit, ws_floats, (operands & ZG_PFPLAN_WS) != 0, (operands & ZG_PFPLAN_LN) != 0,
+                        (operands & ZG_PFPLAN_QKV) ? N / 3 : 0, (operands & ZG_PFPLAN_SK_WS) != 0, (operands & ZG_PFPLAN_SK_FLAGS) != 0, sk_ws_bytes,
+                        sk_flags_words, PrefillForce{force_kernel, force_slices}};
+    const PrefillGemmPlan p = prefill_gemm_plan(sh);
+    const GemmPlanes& pl = p.planes;
+    const int v[ZG_PREFILL_PLAN_INTS] = {p.status, p.family, p.tail, p.partial, p.grid_x, p.grid_y, p.block, p.lds, p.slices, p.slabs, p.ns, p.nspl, p.xcd_rows,
+                                         p.tiles_n, p.s4_kind, p.stream_k, p.band, pl.npairs, (int)pl.pa_bits, (int)pl.pb_bits, pl.b_plane_major};
     memcpy(out, v, sizeof(v));
     return ZG_OK;
 }

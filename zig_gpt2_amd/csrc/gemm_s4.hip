@@ -968,7 +968,7 @@ __global__ __launch_bounds__(256, 1) void gemm_s4_kernel(const bf16_t* __restric
 
 template <int NT, int KIND, bool GELU, bool OUT_BF16, bool SK = false>
 int launch_s4_kind(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, const GemmPlanes& pl, int ldc, int n_sl,
-                  const PrefillQkv& qa, hipStream_t s) {
+                  int grid, int gw, const PrefillQkv& qa, hipStream_t s) {
     using P = S4<NT>;
     static bool raised = false;
     if (!raised) {
@@ -976,12 +976,6 @@ int launch_s4_kind(const bf16_t* A, const bf16_t* B, const float* bias, void* C,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, P::LDS));
         raised = true;
     }
-    const int tiles_m = (M + 255) / 256, tiles_n = (N + P::BN - 1) / P::BN, n_tiles = tiles_m * tiles_n * n_sl;
-    int gw = 8;  // tile-order band width (sweep 1 .. 16: profiles/NOTEBOOK.md)
-    if (gw > tiles_n) gw = tiles_n;
-    const int cus_env = getenv("ZGPT2_GEMM_WGS") ? atoi(getenv("ZGPT2_GEMM_WGS")) : 0;  // tests: few workgroups, many tiles each
-    const int cus = cus_env > 0 ? cus_env : 256;
-    const int grid = n_tiles < cus ? n_tiles : cus;
     const unsigned dbg = (unsigned)(getenv("ZGPT2_GEMM_DBG") ? atoi(getenv("ZGPT2_GEMM_DBG")) : 0);
     ZG_REQUIRE(gemm_s4_args_ok(pl, ldc) && gw < 256 && grid < 1024 && dbg < (1u << 10) && n_sl >= 1 && n_sl < 256, ZG_ERR_UNSUPPORTED,
                "gemm: lda %d / ldb %d / ldc %d / K beyond the packed kernel arguments", pl.lda, pl.ldb, ldc);
@@ -1000,7 +994,9 @@ int launch_s4_kind(const bf16_t* A, const bf16_t* B, const float* bias, void* C,
 template <int NT, bool GELU, bool OUT_BF16>
 int launch_s4(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, const GemmPlanes& pl, int ldc, hipStream_t s) {
     const PrefillQkv none{};
-    return launch_s4_kind<NT, S4_PLAIN, GELU, OUT_BF16>(A, B, bias, C, M, N, pl, ldc, 1, none, s);
+    const int tiles_n = (N + S4<NT>::BN - 1) / S4<NT>::BN;
+    const S4Grid g = gemm_s4_grid((M + 255) / 256 * tiles_n, tiles_n, gemm_s4_wg_cap());
+    return launch_s4_kind<NT, S4_PLAIN, GELU, OUT_BF16>(A, B, bias, C, M, N, pl, ldc, 1, g.grid, g.band, none, s);
 }
 
 template <int NT>
@@ -1018,6 +1014,16 @@ int launch_s4_nt(const bf16_t* A, const bf16_t* B, const float* bias, void* C, i
 // to the eight-wave kernel, whose arguments are not packed; api_ops.hip keeps ragged Linears beyond it on the GEMV path)
 bool gemm_s4_args_ok(const GemmPlanes& pl, int ldc) {
     return pl.lda > 0 && pl.ldb > 0 && pl.lda < 65536 && pl.ldb < 65536 && ldc < (1 << 20) && pl.kpp < 256 && pl.npairs <= 6;
+}
+
+int gemm_s4_wg_cap() {
+    const int cus_env = getenv("ZGPT2_GEMM_WGS") ? atoi(getenv("ZGPT2_GEMM_WGS")) : 0;
+    return cus_env > 0 ? cus_env : 256;
+}
+
+S4Grid gemm_s4_grid(int items, int tiles_n, int wg_cap) {
+    const int gw = 8;  // tile-order band width (sweep 1 .. 16: profiles/NOTEBOOK.md)
+    return S4Grid{items < wg_cap ? items : wg_cap, gw > tiles_n ? tiles_n : gw, S4<3>::LDS};
 }
 
 int gemm_s4_fault(unsigned* out) {  // stream-K hand-over timed out since the last call?  (drains the device; clears the word)
@@ -1043,58 +1049,24 @@ int launch_gemm_s4(const bf16_t* A, const bf16_t* B, const float* bias, void* C,
     return launch_s4_nt<3>(A, B, bias, C, M, N, pl, ldc, gelu, out_bf16, s);
 }
 
-// The whole-prompt Linears on the same kernel (prefill.hip decides when): A = the activation planes [M][nplanes K] (hi | mid | lo),
-// W = the bf16 weight [N][K]; the planes are plane pairs of ONE K loop, smallest first — a tile's accumulators see 3 K / 64
-// K-steps between two epilogues.  nplanes == kWeightPlanes: W = the three plane matrices [3][N][K] of an fp32 weight, and the six
-// plane products a_i w_j, i + j <= 2, are the pairs (6 K / 64 K-steps per tile; what is dropped is below 2^-24 of the leading
-// term).  kind: S4_PARTIAL (C = fp32 slabs [n_slices][M][N], bias must be null), S4_QKV (C = qkv [M][N] fp32 + cache append),
-// S4_SPLIT3 (C = bf16 planes [M][3 N] of gelu(...)).
-int launch_gemm_s4_prefill(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int nplanes, int kind, int n_slices,
-                           const PrefillQkv* qkv, hipStream_t s) {
-    ZG_REQUIRE(M > 0 && N % 64 == 0 && K % 64 == 0 && K >= 128 && (nplanes == 2 || nplanes == 3 || nplanes == kWeightPlanes), ZG_ERR_UNSUPPORTED,
-               "s4 prefill gemm: M=%d N=%d K=%d planes=%d", M, N, K, nplanes);
-    GemmPlanes pl{};
-    pl.lda = kSplit * K;  // the plane buffer always holds three planes per row; nplanes = 2 multiplies hi + mid only
-    pl.ldb = K;
-    pl.kpp = K / 64;
-    if (nplanes == kWeightPlanes) {  // (a, w) = (lo, hi) (mid, mid) (hi, lo) (mid, hi) (hi, mid) (hi, hi): smallest terms first
-        pl.npairs = 6;
-        pl.pa_bits = 0x001012u;
-        pl.pb_bits = 0x010210u;
-        pl.b_plane_major = true;
-        ZG_REQUIRE((size_t)N * K * 2 * 3 < ((size_t)1 << 31), ZG_ERR_SHAPE, "s4 prefill gemm: weight planes of %d x %d beyond a 32-bit buffer descriptor", N, K);
-    } else {
-        pl.npairs = nplanes;
-        pl.pa_bits = nplanes == 3 ? 0x012u : 0x01u;  // pair 0 = the smallest plane
-        pl.pb_bits = 0;
-    }
-    const int ldc = kind == S4_SPLIT3 ? kSplit * N : N;
-    const size_t out_bytes = (size_t)(kind == S4_PARTIAL ? n_slices : 1) * M * ldc * (kind == S4_SPLIT3 ? 2 : 4);
-    ZG_REQUIRE(out_bytes < ((size_t)1 << 32) && (size_t)M * pl.lda * 2 < ((size_t)1 << 31) && (size_t)N * K * 2 < ((size_t)1 << 31), ZG_ERR_SHAPE,
-               "s4 prefill gemm: operands of %d x %d x %d beyond the 32-bit buffer descriptors", M, N, K);
-    ZG_REQUIRE(n_slices >= 1 && pl.kpp % n_slices == 0 && pl.kpp / n_slices >= 2, ZG_ERR_ARG, "s4 prefill gemm: %d K slices of %d K-steps", n_slices, pl.kpp);
+// The whole-prompt Linears on the same kernel, as prefill_gemm_plan (prefill.hip) laid them out — nothing is decided here.  A = the
+// activation planes [M][3 K] (hi | mid | lo), W = the bf16 weight [N][K] or the three plane matrices [3][N][K] of an fp32 weight; the
+// plane products (p.planes: 3, or the six a_i w_j, i + j <= 2; what is dropped is below 2^-24 of the leading term) are plane pairs of
+// ONE K loop, smallest first.  p.s4_kind: S4_PARTIAL (C = fp32 slabs [p.slices][M][N], no bias), S4_SPLIT3 (C = bf16 planes [M][3 N]
+// of gelu(...)), S4_QKV (C = qkv [M][N] fp32 + cache append; p.stream_k: at 1.5 rounds of tiles — c_attn of eight 1023-token prompts:
+// 384 tiles, 256 CUs — the last half round is split in K halves over ALL workgroups with a partial hand-over, gemm_s4_kernel SK).
+int launch_gemm_s4_prefill(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, const PrefillGemmPlan& p, const PrefillQkv* qkv,
+                           hipStream_t s) {
     const PrefillQkv none{};
     gemm_note_launch();
-    switch (kind) {
-        case S4_PARTIAL:
-            ZG_REQUIRE(bias == nullptr, ZG_ERR_ARG, "s4 prefill gemm: partial slabs carry no bias");
-            return launch_s4_kind<3, S4_PARTIAL, false, false>(A, W, nullptr, C, M, N, pl, ldc, n_slices, none, s);
-        case S4_QKV: {
-            ZG_REQUIRE(qkv && N == 3 * qkv->E && n_slices == 1, ZG_ERR_ARG, "s4 prefill gemm: S4_QKV needs the cache description");
-            // 1.5 rounds of tiles (c_attn of eight 1023-token prompts: 384 tiles, 256 CUs): the last half round is split in K halves
-            // over ALL workgroups with a partial hand-over instead of running on half of the chip (gemm_s4_kernel, SK)
-            const int cus_env = getenv("ZGPT2_GEMM_WGS") ? atoi(getenv("ZGPT2_GEMM_WGS")) : 0;
-            const int G = cus_env > 0 ? cus_env : 256, tiles = ((M + 255) / 256) * ((N + 191) / 192);
-            if (qkv->sk_ws != nullptr && qkv->sk_flags != nullptr && G % 16 == 0 && tiles > G && (tiles % G) * 2 == G && pl.kpp % 2 == 0 &&
-                pl.kpp >= 4 && (size_t)(G / 2) * 196608 <= qkv->sk_ws_bytes && (size_t)(G / 2) * 4 <= qkv->sk_flags_words)
-                return launch_s4_kind<3, S4_QKV, false, false, true>(A, W, bias, C, M, N, pl, ldc, 1, *qkv, s);
-            return launch_s4_kind<3, S4_QKV, false, false>(A, W, bias, C, M, N, pl, ldc, 1, *qkv, s);
-        }
-        case S4_SPLIT3:
-            ZG_REQUIRE(n_slices == 1, ZG_ERR_ARG, "s4 prefill gemm: S4_SPLIT3 is not sliced");
-            return launch_s4_kind<3, S4_SPLIT3, true, true>(A, W, bias, C, M, N, pl, ldc, 1, none, s);
+    switch (p.s4_kind) {
+        case S4_PARTIAL: return launch_s4_kind<3, S4_PARTIAL, false, false>(A, W, nullptr, C, M, N, p.planes, p.s4_ldc, p.slices, p.grid_x, p.band, none, s);
+        case S4_QKV:
+            if (p.stream_k) return launch_s4_kind<3, S4_QKV, false, false, true>(A, W, bias, C, M, N, p.planes, p.s4_ldc, 1, p.grid_x, p.band, *qkv, s);
+            return launch_s4_kind<3, S4_QKV, false, false>(A, W, bias, C, M, N, p.planes, p.s4_ldc, 1, p.grid_x, p.band, *qkv, s);
+        case S4_SPLIT3: return launch_s4_kind<3, S4_SPLIT3, true, true>(A, W, bias, C, M, N, p.planes, p.s4_ldc, 1, p.grid_x, p.band, none, s);
     }
-    ZG_REQUIRE(false, ZG_ERR_ARG, "s4 prefill gemm: kind %d", kind);
+    ZG_REQUIRE(false, ZG_ERR_ARG, "s4 prefill gemm: kind %d", p.s4_kind);
 }
 
 }  // namespace zg

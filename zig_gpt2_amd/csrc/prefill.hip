@@ -18,6 +18,10 @@
 //                        F32 store | fp32 residual add | GELU + split        (ops.zig:21-46, main.zig:136-145, :79-80)
 //   (cache append)     K / V columns of the qkv rows -> head-major caches, in the c_attn GEMM epilogue (ops.zig:152-158)
 //   (attention)        causal softmax(q k^T / 8) v for all positions: attn_prefill.hip           (src/ops.zig:249-307)
+//
+// Host side.  prefill_gemm_plan decides a Linear once and holds every threshold: GEMM family (gemm_s4.hip's persistent kernel or the
+// 128-row kernels here), instantiation, grid, K slices, stream-K, tail.  launch_prefill_gemm is that plan, launch_gemm (one switch to
+// the instantiation) and finish() for the tail.
 #include <stdlib.h>
 
 #include "prefill_epi.h"
@@ -547,101 +551,128 @@ static unsigned xcd_grid_rows(int tiles_m, int tiles_n, size_t a_tile, size_t w_
     return best;
 }
 
-template <int EPI, int NS, int NSPL>
-int launch_prefill_gemm_np(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, int K, int ldc,
-                           float* ws, size_t ws_floats, const PrefillLn* ln, const PrefillQkv& qa, hipStream_t s) {
-    constexpr int nsplit = NSPL;
-    static bool raised = false;
-    if (!raised) {
-        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_gemm_kernel<EPI, NS, NSPL>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(NS)));
-        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_gemm_kernel<PF_PARTIAL, NS, NSPL>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(NS)));
-        raised = true;
-    }
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN * NS - 1) / (BN * NS), tiles = tiles_m * tiles_n;
-    // Few output tiles (N = n_embed, or a short prompt): slice K so that about one workgroup per CU exists
-    // (the LDS ring allows one), at least 3 K-steps per slice, partial sums through the workspace.
-    const int nt = K / BK;
-    int n_sp = 256 / tiles;
-    if (n_sp > nt / 3) n_sp = nt / 3;
-    if (n_sp < 1) n_sp = 1;
-    while (n_sp > 1 && (size_t)n_sp * M * N > ws_floats) --n_sp;
-    const unsigned xg = xcd_grid_rows(tiles_m, tiles_n, (size_t)BM * (K / (n_sp > 1 && ws ? n_sp : 1)) * 2 * nsplit,
-                                      (size_t)BN * NS * (K / (n_sp > 1 && ws ? n_sp : 1)) * 2);
-    if (n_sp <= 1 || !ws) {
-        hipLaunchKernelGGL((prefill_gemm_kernel<EPI, NS, NSPL>), dim3(tiles), dim3(256), lds_bytes(NS), s, A, B, bias, C, M, N, K,
-                           ldc, (unsigned)tiles_n | (1u << 12) | (xg << 24), tiles, qa);
-    } else {
-        hipLaunchKernelGGL((prefill_gemm_kernel<PF_PARTIAL, NS, NSPL>), dim3(tiles, n_sp), dim3(256), lds_bytes(NS), s, A, B, bias,
-                           (void*)ws, M, N, K, ldc, (unsigned)tiles_n | ((unsigned)n_sp << 12) | (xg << 24), tiles, qa);
-        if (EPI == PF_RESID && ln && ldc == N && N <= 2048) {
-            hipLaunchKernelGGL(prefill_reduce_resid_ln_kernel, dim3(M), dim3(256), 0, s, ws, n_sp, bias,
-                               reinterpret_cast<float*>(C), M, N, ln->g, ln->b, ln->eps, ln->out);
-            ZG_HIP(hipGetLastError());
-            return ZG_OK;
+// Large prompts (several sequences): the Linears run on the persistent four-wave kernel of gemm_s4.hip with the activation
+// planes as plane pairs of ONE K loop (K_eff = 3 K between two epilogues) once its 256 x 192 tiles fill most of the chip; the
+// N = n_embed Linears (residual adds) get there by slicing K over the tile list, their partial slabs summed by the reduce
+// kernels above in fixed order (which also apply bias, residual and the LayerNorm + split that follows).  Returns the slice
+// count, 0 = the 128-row kernels of this file take the launch.
+static int s4_slices(const PrefillGemmShape& sh) {
+    const int M = sh.M, N = sh.N, kpp = sh.K / 64, force = sh.force.kernel, fs = sh.force.slices;
+    int min_tiles = 192;  // tiles of 256 x 192 (x K slices) from which the persistent kernel takes the launch: three quarters of the CUs
+    if (force == 1) min_tiles = 1;
+    if (force >= 16) min_tiles = force;  // (measurement: another threshold)
+    if (force == 2 || kpp < 2 || kSplit * sh.K >= 65536) return 0;
+    const long tiles = (long)((M + 255) / 256) * ((N + 191) / 192);
+    if (sh.epi != PF_RESID) return tiles >= min_tiles ? 1 : 0;
+    if (!sh.have_ws) return 0;
+    // (at most four slices: a one-prompt mlp c_proj cut into twelve — 16 tiles — ran 21.8 + 8.0 us of GEMM + reduce against 15.5 + 6.8
+    // on the 128-row kernel: profiles/round5_prefill_1x1023_kernel_stats.md of the first pass).  Among the slice counts that divide
+    // the K-steps: the one whose items fill most of ONE round of 256 workgroups (four prompts: 64 tiles x 4 rather than x 3); more
+    // tiles than that run unsliced.
+    if (fs > 0) return (kpp % fs == 0 && fs <= kpp / 2 && (size_t)fs * M * N <= sh.ws_floats) ? fs : 0;
+    int best = 0;
+    long best_items = 0;
+    for (int n_sl = 1; n_sl <= 4 && n_sl <= kpp / 2; ++n_sl) {
+        const long items = tiles * n_sl;
+        if (kpp % n_sl != 0 || (size_t)n_sl * M * N > sh.ws_floats || items < min_tiles) continue;
+        if (best == 0 || (items <= 256 && items > best_items)) {
+            best = n_sl;
+            best_items = items;
         }
-        const size_t n = (size_t)M * (N / 4);
-        hipLaunchKernelGGL((prefill_reduce_kernel<EPI>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, n_sp, bias, C,
-                           M, N, ldc, qa);
     }
-    ZG_HIP(hipGetLastError());
-    if (EPI == PF_RESID && ln) return launch_ln_split(reinterpret_cast<const float*>(C), M, N, ln->g, ln->b, ln->eps, ln->out, s);
-    return ZG_OK;
+    return best;
 }
 
-// fp32 weights (nsplit = kWeightPlanes): prefill_gemm_wp_kernel + the reduce kernels (which apply the epilogue)
-template <int EPI, int NS>
-int launch_prefill_gemm_wp(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, int K, int ldc, float* ws,
-                           size_t ws_floats, const PrefillLn* ln, const PrefillQkv& qa, hipStream_t s) {
-    static bool raised = false;
-    if (!raised) {
-        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&prefill_gemm_wp_kernel<NS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(NS)));
-        raised = true;
-    }
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN * NS - 1) / (BN * NS), tiles = tiles_m * tiles_n;
-    const int nt = K / BK;
-    int n_sp = (256 + 3 * tiles - 1) / (3 * tiles);  // three passes per slice: about one workgroup per CU in all
-    if (n_sp > nt / 3) n_sp = nt / 3;
-    if (n_sp < 1) n_sp = 1;
-    while (n_sp > 1 && (size_t)3 * n_sp * M * N > ws_floats) --n_sp;
-    ZG_REQUIRE(ws && (size_t)3 * n_sp * M * N <= ws_floats, ZG_ERR_ARG, "prefill GEMM (fp32 weights): workspace of %zu floats for %d x %d", ws_floats, M, N);
-    const unsigned xg = xcd_grid_rows(tiles_m, tiles_n, (size_t)BM * (K / n_sp) * 2 * 3, (size_t)BN * NS * (K / n_sp) * 2);
-    hipLaunchKernelGGL((prefill_gemm_wp_kernel<NS>), dim3(tiles, 3 * n_sp), dim3(256), lds_bytes(NS), s, A, B, bias, (void*)ws, M, N, K, ldc,
-                       (unsigned)tiles_n | ((unsigned)n_sp << 12) | (xg << 24), tiles, qa);
-    if (EPI == PF_RESID && ln && ldc == N && N <= 2048) {
-        hipLaunchKernelGGL(prefill_reduce_resid_ln_kernel, dim3(M), dim3(256), 0, s, ws, 3 * n_sp, bias, reinterpret_cast<float*>(C), M, N, ln->g,
-                           ln->b, ln->eps, ln->out);
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
-    }
-    const size_t n = (size_t)M * (N / 4);
-    hipLaunchKernelGGL((prefill_reduce_kernel<EPI>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, 3 * n_sp, bias, C, M, N, ldc, qa);
-    ZG_HIP(hipGetLastError());
-    if (EPI == PF_RESID && ln) return launch_ln_split(reinterpret_cast<const float*>(C), M, N, ln->g, ln->b, ln->eps, ln->out, s);
-    return ZG_OK;
-}
-
-template <int EPI, int NS>
-int launch_prefill_gemm_ns(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, int K, int ldc,
-                           float* ws, size_t ws_floats, const PrefillLn* ln, const PrefillQkv& qa, int nsplit, hipStream_t s) {
-    if (nsplit == kWeightPlanes) return launch_prefill_gemm_wp<EPI, NS>(A, B, bias, C, M, N, K, ldc, ws, ws_floats, ln, qa, s);
-    if (nsplit == 2) return launch_prefill_gemm_np<EPI, NS, 2>(A, B, bias, C, M, N, K, ldc, ws, ws_floats, ln, qa, s);
-    return launch_prefill_gemm_np<EPI, NS, kSplit>(A, B, bias, C, M, N, K, ldc, ws, ws_floats, ln, qa, s);
-}
-
-// 128 x 256 tiles (the staged weight tile is shared by the three planes, so widening N is the cheap direction:
-// 157 FLOP per staged byte against 96) once there are enough rows to fill the chip with them, else 128 x 128.
-template <int EPI>
-int launch_prefill_gemm_t(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, int K, int ldc,
-                          float* ws, size_t ws_floats, const PrefillLn* ln, const PrefillQkv& qa, int nsplit, hipStream_t s) {
-    const int wide_tiles = ((M + BM - 1) / BM) * ((N + 2 * BN - 1) / (2 * BN));
-    const bool wide = wide_tiles >= 256 && N >= 2 * BN;
-    if (wide) return launch_prefill_gemm_ns<EPI, 2>(A, B, bias, C, M, N, K, ldc, ws, ws_floats, ln, qa, nsplit, s);
-    return launch_prefill_gemm_ns<EPI, 1>(A, B, bias, C, M, N, K, ldc, ws, ws_floats, ln, qa, nsplit, s);
+static PrefillGemmPlan refuse(int status, const char* why) {
+    PrefillGemmPlan p{};
+    p.status = status;
+    p.why = why;
+    return p;
 }
 
 }  // namespace
+
+PrefillGemmPlan prefill_gemm_plan(const PrefillGemmShape& sh) {
+    const int M = sh.M, N = sh.N, K = sh.K, epi = sh.epi, nsplit = sh.nsplit;
+    const size_t GiB2 = (size_t)1 << 31;
+    if (M <= 0 || N < 64 || N % 64 != 0 || K < 64 || K % 64 != 0) return refuse(ZG_ERR_UNSUPPORTED, "no rows, or N / K not a multiple of 64");
+    const bool planes_ok = nsplit == 2 || nsplit == kSplit || nsplit == kWeightPlanes, wp = nsplit == kWeightPlanes;
+    const bool ln = sh.have_ln && epi == PF_RESID, qkv_ok = sh.qkv_e > 0 && sh.ldc == N;
+    PrefillGemmPlan p{};
+    p.status = ZG_OK;
+    p.block = 256;
+    p.grid_y = 1;
+    p.slices = 1;
+    const int n_sl = s4_slices(sh);
+    if (n_sl > 0 && ((epi == PF_RESID && sh.ldc == N) || epi == PF_GELU_SPLIT || (epi == PF_QKV && qkv_ok))) {  // the persistent kernel
+        if (!planes_ok) return refuse(ZG_ERR_UNSUPPORTED, "activation planes");
+        p.family = PFF_S4;
+        p.s4_kind = epi == PF_RESID ? S4_PARTIAL : epi == PF_QKV ? S4_QKV : S4_SPLIT3;
+        p.partial = epi == PF_RESID;
+        p.slices = n_sl;  // (s4_slices: only a residual add is sliced)
+        // lda: the plane buffer always holds three planes per row (nsplit = 2 multiplies hi + mid only).  The planes are plane pairs
+        // of one K loop, the smallest first; fp32 weights (plane-major): (a, w) = (lo, hi) (mid, mid) (hi, lo) (mid, hi) (hi, mid) (hi, hi)
+        p.planes = wp ? GemmPlanes{kSplit * K, K, K / 64, 6, 0x001012u, 0x010210u, true}
+                      : GemmPlanes{kSplit * K, K, K / 64, nsplit, nsplit == 3 ? 0x012u : 0x01u, 0, false};
+        p.s4_ldc = epi == PF_GELU_SPLIT ? kSplit * N : N;
+        const size_t out_bytes = (size_t)n_sl * M * p.s4_ldc * (epi == PF_GELU_SPLIT ? 2 : 4);
+        const size_t a_bytes = (size_t)M * kSplit * K * 2, w_bytes = (size_t)N * K * 2 * (wp ? 3 : 1);
+        if (out_bytes >= 2 * GiB2 || a_bytes >= GiB2 || w_bytes >= GiB2)
+            return refuse(ZG_ERR_SHAPE, "operands beyond the persistent kernel's 32-bit buffer descriptors");
+        if (epi == PF_QKV && N != 3 * sh.qkv_e) return refuse(ZG_ERR_ARG, "PF_QKV needs the cache description");
+        const int tiles_n = (N + 191) / 192, tiles = (M + 255) / 256 * tiles_n, G = gemm_s4_wg_cap();
+        const S4Grid g = gemm_s4_grid(tiles * n_sl, tiles_n, G);
+        if (!gemm_s4_args_ok(p.planes, p.s4_ldc) || g.grid >= 1024) return refuse(ZG_ERR_UNSUPPORTED, "beyond the persistent kernel's packed arguments");
+        p.grid_x = g.grid;
+        p.band = g.band;
+        p.lds = g.lds;
+        // 1.5 rounds of tiles: the last half round in K halves over all workgroups (gemm_s4_kernel SK), given 196608 B of accumulators
+        // and 4 flag words per shared tile
+        p.stream_k = epi == PF_QKV && sh.have_sk_ws && sh.have_sk_flags && G % 16 == 0 && tiles > G && (tiles % G) * 2 == G && K % 128 == 0 && K >= 256 &&
+                     (size_t)(G / 2) * 196608 <= sh.sk_ws_bytes && (size_t)(G / 2) * 4 <= sh.sk_flags_words;
+    } else {  // the 128-row kernels of this file
+        // (the operands are addressed through 32-bit buffer descriptors; a piece is switched off by adding 2 GiB to its scalar offset,
+        // which must then lie past the descriptor's end without wrapping: operands < 2 GiB.  That a raw buffer access is range-checked
+        // on voffset + soffset — LLVM documents only voffset — is pinned on the hardware by tools/microbench/soffset_bounds_probe.hip,
+        // tests/test_hw_rules_gpu.py)
+        if ((size_t)M * kSplit * K * 2 >= GiB2 || (size_t)N * K * 2 >= GiB2) return refuse(ZG_ERR_UNSUPPORTED, "operands beyond 2 GiB");
+        if (!planes_ok) return refuse(ZG_ERR_ARG, "activation planes");
+        if (epi != PF_F32 && epi != PF_RESID && epi != PF_GELU_SPLIT && epi != PF_QKV) return refuse(ZG_ERR_ARG, "epilogue");
+        if (epi == PF_QKV && !(qkv_ok && N == 3 * sh.qkv_e)) return refuse(ZG_ERR_ARG, "PF_QKV needs the cache description");
+        // 128 x 256 tiles (the staged weight tile is shared by the three planes, so widening N is the cheap direction: 157 FLOP per
+        // staged byte against 96) once there are enough rows to fill the chip with them, else 128 x 128.
+        const int tiles_m = (M + BM - 1) / BM;
+        p.ns = (tiles_m * ((N + 2 * BN - 1) / (2 * BN)) >= 256 && N >= 2 * BN) ? 2 : 1;
+        p.tiles_n = (N + BN * p.ns - 1) / (BN * p.ns);
+        p.grid_x = tiles_m * p.tiles_n;
+        p.lds = lds_bytes(p.ns);
+        // Few output tiles (N = n_embed, or a short prompt): slice K so that about one workgroup per CU exists (the LDS ring allows one), at least
+        // 3 K-steps per slice, partial sums through the workspace.  fp32 weights: three passes per slice, always through the workspace.
+        const int passes = wp ? 3 : 1;
+        int n_sp = wp ? (256 + 3 * p.grid_x - 1) / (3 * p.grid_x) : 256 / p.grid_x;
+        if (n_sp > K / BK / 3) n_sp = K / BK / 3;
+        if (n_sp < 1) n_sp = 1;
+        while (n_sp > 1 && (size_t)passes * n_sp * M * N > sh.ws_floats) --n_sp;
+        if (wp && !(sh.have_ws && (size_t)3 * n_sp * M * N <= sh.ws_floats)) return refuse(ZG_ERR_ARG, "fp32 weights: workspace too small");
+        p.family = wp ? PFF_T128_WP : PFF_T128;
+        p.nspl = wp ? 0 : nsplit;
+        p.partial = wp || (n_sp > 1 && sh.have_ws);
+        if (p.partial) {
+            p.slices = n_sp;
+            p.grid_y = passes * n_sp;
+        }
+        p.xcd_rows = (int)xcd_grid_rows(tiles_m, p.tiles_n, (size_t)BM * (K / p.slices) * 2 * (wp ? 3 : nsplit), (size_t)BN * p.ns * (K / p.slices) * 2);
+    }
+    // behind the GEMM: the slabs summed in fixed order (+ bias, residual, and the LayerNorm + split where one kernel can do it all),
+    // and / or that LayerNorm on its own
+    if (!p.partial) {
+        p.tail = ln ? PFT_LN_SPLIT : PFT_NONE;
+    } else {
+        p.slabs = p.family == PFF_S4 ? p.slices : p.grid_y;
+        p.tail = (ln && sh.ldc == N && N <= 2048) ? PFT_REDUCE_RESID_LN : ln ? PFT_REDUCE_LN_SPLIT : PFT_REDUCE;
+    }
+    return p;
+}
 
 int launch_embed_prefill(const int* tokens, int token_stride, int B, int P, const void* wte, const void* wpe,
                          int weight_type, int E, float* x, hipStream_t s, int pos0) {
@@ -657,85 +688,110 @@ int launch_ln_split(const float* x, int M, int E, const float* g, const float* b
     return ZG_OK;
 }
 
-// Large prompts (several sequences): the Linears run on the persistent four-wave kernel of gemm_s4.hip with the activation
-// planes as plane pairs of ONE K loop (K_eff = 3 K between two epilogues) once its 256 x 192 tiles fill most of the chip; the
-// N = n_embed Linears (residual adds) get there by slicing K over the tile list, their partial slabs summed by the reduce
-// kernels above in fixed order (which also apply bias, residual and the LayerNorm + split that follows).  Returns the slice
-// count, 0 = the 128-row kernels of this file take the launch.
-static int g_force_kernel = 0, g_force_slices = 0;  // zg_debug_prefill_route / _linear: 1 = gemm_s4, 2 = the 128-row kernels; K slices
-void prefill_force_route(int kernel, int slices) {
-    g_force_kernel = kernel;
-    g_force_slices = slices;
-}
-static int s4_route(int M, int N, int K, int epi, size_t ws_floats, bool have_ws) {
-    int min_tiles = 192;  // tiles of 256 x 192 (x K slices) from which the persistent kernel takes the launch: three quarters of the CUs
-    if (g_force_kernel == 1) min_tiles = 1;
-    if (g_force_kernel >= 16) min_tiles = g_force_kernel;  // (measurement: another threshold)
-    if (g_force_kernel == 2) return 0;
-    const int kpp = K / 64;
-    if (K % 64 != 0 || kpp < 2 || kSplit * K >= 65536) return 0;
-    const long tiles = (long)((M + 255) / 256) * ((N + 191) / 192);
-    if (epi != PF_RESID) return tiles >= min_tiles ? 1 : 0;
-    if (!have_ws) return 0;
-    // (at most four slices: a one-prompt mlp c_proj cut into twelve — 16 tiles — ran 21.8 + 8.0 us of GEMM + reduce against 15.5 + 6.8
-    // on the 128-row kernel: profiles/round5_prefill_1x1023_kernel_stats.md of the first pass).  Among the slice counts that divide
-    // the K-steps: the one whose items fill most of ONE round of 256 workgroups (four prompts: 64 tiles x 4 rather than x 3); more
-    // tiles than that run unsliced.
-    if (g_force_slices > 0) return (kpp % g_force_slices == 0 && g_force_slices <= kpp / 2 && (size_t)g_force_slices * M * N <= ws_floats) ? g_force_slices : 0;
-    int best = 0;
-    long best_items = 0;
-    for (int n_sl = 1; n_sl <= 4 && n_sl <= kpp / 2; ++n_sl) {
-        if (kpp % n_sl != 0 || (size_t)n_sl * M * N > ws_floats) continue;
-        const long items = tiles * n_sl;
-        if (items < min_tiles) continue;
-        if (best == 0 || (items <= 256 && items > best_items)) {
-            best = n_sl;
-            best_items = items;
-        }
+namespace {
+
+struct PrefillOps {  // the operands of one launch_prefill_gemm
+    const bf16_t* A;
+    const bf16_t* B;
+    const float* bias;
+    void* C;
+    float* ws;
+    const PrefillLn* ln;
+    const PrefillQkv& qa;
+    hipStream_t s;
+};
+
+// the planned GEMM on one instantiation of the 128-row kernels: KERNEL = &prefill_gemm_kernel<EPI, NS, NSPL> or &prefill_gemm_wp_kernel<NS>
+template <auto KERNEL>
+int launch_t128(const PrefillGemmPlan& p, const PrefillGemmShape& sh, const PrefillOps& o) {
+    static bool raised = false;
+    if (!raised) {
+        ZG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+        raised = true;
     }
-    return best;
+    const unsigned tp = (unsigned)p.tiles_n | ((unsigned)p.slices << 12) | ((unsigned)p.xcd_rows << 24);
+    hipLaunchKernelGGL(KERNEL, dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds, o.s, o.A, o.B, o.bias, p.partial ? (void*)o.ws : o.C, sh.M, sh.N, sh.K, sh.ldc, tp,
+                       p.grid_x, o.qa);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
 }
 
-int launch_prefill_gemm(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, int K, int ldc, int epi,
-                        float* ws, size_t ws_floats, const PrefillLn* ln, hipStream_t s, const PrefillQkv* qkv, int nsplit) {
-    ZG_REQUIRE(M > 0 && N >= 64 && N % 64 == 0 && K >= 64 && K % 64 == 0, ZG_ERR_UNSUPPORTED, "prefill gemm: M=%d N=%d K=%d", M, N, K);
-    {
-        const int n_sl = s4_route(M, N, K, epi, ws_floats, ws != nullptr);
-        if (n_sl > 0 && epi == PF_RESID && ldc == N) {
-            ZG_TRY(launch_gemm_s4_prefill(A, B, nullptr, ws, M, N, K, nsplit, S4_PARTIAL, n_sl, nullptr, s));
-            if (ln && N <= 2048) {
-                hipLaunchKernelGGL(prefill_reduce_resid_ln_kernel, dim3(M), dim3(256), 0, s, ws, n_sl, bias, reinterpret_cast<float*>(C), M, N, ln->g,
-                                   ln->b, ln->eps, ln->out);
-                ZG_HIP(hipGetLastError());
-                return ZG_OK;
-            }
-            const size_t n = (size_t)M * (N / 4);
-            hipLaunchKernelGGL((prefill_reduce_kernel<PF_RESID>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, n_sl, bias, C, M, N, ldc,
-                               PrefillQkv{});
-            ZG_HIP(hipGetLastError());
-            if (ln) return launch_ln_split(reinterpret_cast<const float*>(C), M, N, ln->g, ln->b, ln->eps, ln->out, s);
-            return ZG_OK;
+// second level of launch_gemm's switch: strips per wave and planes of prefill_gemm_kernel<EPI, NS, NSPL>
+template <int EPI>
+int launch_t128_epi(const PrefillGemmPlan& p, const PrefillGemmShape& sh, const PrefillOps& o) {
+    switch (10 * p.ns + p.nspl) {
+        case 12: return launch_t128<&prefill_gemm_kernel<EPI, 1, 2>>(p, sh, o);
+        case 13: return launch_t128<&prefill_gemm_kernel<EPI, 1, 3>>(p, sh, o);
+        case 22: return launch_t128<&prefill_gemm_kernel<EPI, 2, 2>>(p, sh, o);
+        case 23: return launch_t128<&prefill_gemm_kernel<EPI, 2, 3>>(p, sh, o);
+    }
+    ZG_REQUIRE(false, ZG_ERR_ARG, "prefill gemm: no kernel with %d strips per wave and %d planes", p.ns, p.nspl);
+}
+
+// the planned GEMM: one switch from the plan to the instantiation
+int launch_gemm(const PrefillGemmPlan& p, const PrefillGemmShape& sh, const PrefillOps& o, const PrefillQkv* qkv) {
+    if (p.family == PFF_S4) return launch_gemm_s4_prefill(o.A, o.B, p.partial ? nullptr : o.bias, p.partial ? (void*)o.ws : o.C, sh.M, sh.N, p, qkv, o.s);
+    if (p.family == PFF_T128_WP) {
+        if (p.ns == 2) return launch_t128<&prefill_gemm_wp_kernel<2>>(p, sh, o);
+        return launch_t128<&prefill_gemm_wp_kernel<1>>(p, sh, o);
+    }
+    switch (p.partial ? PF_PARTIAL : sh.epi) {
+        case PF_F32: return launch_t128_epi<PF_F32>(p, sh, o);
+        case PF_RESID: return launch_t128_epi<PF_RESID>(p, sh, o);
+        case PF_GELU_SPLIT: return launch_t128_epi<PF_GELU_SPLIT>(p, sh, o);
+        case PF_QKV: return launch_t128_epi<PF_QKV>(p, sh, o);
+        case PF_PARTIAL: return launch_t128_epi<PF_PARTIAL>(p, sh, o);
+    }
+    ZG_REQUIRE(false, ZG_ERR_ARG, "prefill gemm: epilogue %d", sh.epi);
+}
+
+template <int EPI>
+void launch_reduce(const PrefillGemmPlan& p, const PrefillGemmShape& sh, const PrefillOps& o) {
+    const size_t n = (size_t)sh.M * (sh.N / 4);
+    hipLaunchKernelGGL((prefill_reduce_kernel<EPI>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o.s, o.ws, p.slabs, o.bias, o.C, sh.M, sh.N, sh.ldc, o.qa);
+}
+
+// the tail behind the GEMM (PrefillGemmPlan.tail)
+int finish(const PrefillGemmPlan& p, const PrefillGemmShape& sh, const PrefillOps& o) {
+    const int M = sh.M, N = sh.N;
+    if (p.tail == PFT_NONE) return ZG_OK;
+    if (p.tail == PFT_REDUCE_RESID_LN) {
+        hipLaunchKernelGGL(prefill_reduce_resid_ln_kernel, dim3(M), dim3(256), 0, o.s, o.ws, p.slabs, o.bias, reinterpret_cast<float*>(o.C), M, N, o.ln->g, o.ln->b,
+                           o.ln->eps, o.ln->out);
+        ZG_HIP(hipGetLastError());
+        return ZG_OK;
+    }
+    if (p.tail == PFT_REDUCE || p.tail == PFT_REDUCE_LN_SPLIT) {
+        switch (sh.epi) {
+            case PF_F32: launch_reduce<PF_F32>(p, sh, o); break;
+            case PF_RESID: launch_reduce<PF_RESID>(p, sh, o); break;
+            case PF_GELU_SPLIT: launch_reduce<PF_GELU_SPLIT>(p, sh, o); break;
+            case PF_QKV: launch_reduce<PF_QKV>(p, sh, o); break;
         }
-        if (n_sl == 1 && epi == PF_GELU_SPLIT) return launch_gemm_s4_prefill(A, B, bias, C, M, N, K, nsplit, S4_SPLIT3, 1, nullptr, s);
-        if (n_sl == 1 && epi == PF_QKV && qkv && ldc == N) return launch_gemm_s4_prefill(A, B, bias, C, M, N, K, nsplit, S4_QKV, 1, qkv, s);
+        ZG_HIP(hipGetLastError());
+        if (p.tail == PFT_REDUCE) return ZG_OK;
     }
-    // (the operands are addressed through 32-bit buffer descriptors; a piece is switched off by adding 2 GiB to its scalar offset,
-    // which must then lie past the descriptor's end without wrapping: operands < 2 GiB.  That a raw buffer access is range-checked
-    // on voffset + soffset — LLVM documents only voffset — is pinned on the hardware by tools/microbench/soffset_bounds_probe.hip,
-    // tests/test_hw_rules_gpu.py)
-    ZG_REQUIRE((size_t)M * kSplit * K * 2 < ((size_t)1 << 31) && (size_t)N * K * 2 < ((size_t)1 << 31), ZG_ERR_UNSUPPORTED,
-               "prefill gemm: operands of %d x %d x %d beyond 2 GiB", M, N, K);
-    ZG_REQUIRE(nsplit == 2 || nsplit == kSplit || nsplit == kWeightPlanes, ZG_ERR_ARG, "prefill gemm: %d activation planes", nsplit);
+    return launch_ln_split(reinterpret_cast<const float*>(o.C), M, N, o.ln->g, o.ln->b, o.ln->eps, o.ln->out, o.s);
+}
+
+PrefillForce g_force{0, 0};  // zg_debug_prefill_route
+
+}  // namespace
+
+void prefill_force_route(int kernel, int slices) { g_force = PrefillForce{kernel, slices}; }
+
+int launch_prefill_gemm(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, int K, int ldc, int epi,
+                        float* ws, size_t ws_floats, const PrefillLn* ln, hipStream_t s, const PrefillQkv* qkv, int nsplit, const PrefillForce* force) {
     const PrefillQkv none{};
-    switch (epi) {
-        case PF_F32: return launch_prefill_gemm_t<PF_F32>(A, B, bias, C, M, N, K, ldc, ws, ws_floats, nullptr, none, nsplit, s);
-        case PF_RESID: return launch_prefill_gemm_t<PF_RESID>(A, B, bias, C, M, N, K, ldc, ws, ws_floats, ln, none, nsplit, s);
-        case PF_GELU_SPLIT: return launch_prefill_gemm_t<PF_GELU_SPLIT>(A, B, bias, C, M, N, K, ldc, ws, ws_floats, nullptr, none, nsplit, s);
-        case PF_QKV:
-            ZG_REQUIRE(qkv && N == 3 * qkv->E && ldc == N, ZG_ERR_ARG, "prefill gemm: PF_QKV needs the cache description");
-            return launch_prefill_gemm_t<PF_QKV>(A, B, bias, C, M, N, K, ldc, ws, ws_floats, nullptr, *qkv, nsplit, s);
-    }
-    ZG_REQUIRE(false, ZG_ERR_ARG, "prefill gemm: epilogue %d", epi);
+    const PrefillQkv& q = qkv ? *qkv : none;
+    const PrefillGemmShape sh{M, N, K, ldc, epi, nsplit, ws_floats, ws != nullptr, ln != nullptr, q.E, q.sk_ws != nullptr, q.sk_flags != nullptr, q.sk_ws_bytes,
+                              q.sk_flags_words, force ? *force : g_force};  // (the one place the process-wide pin is read)
+    const PrefillGemmPlan p = prefill_gemm_plan(sh);
+    ZG_REQUIRE(p.status == ZG_OK, p.status, "prefill gemm: M=%d N=%d K=%d ldc=%d epilogue %d, %d planes, workspace %zu: %s", M, N, K, ldc, epi, nsplit, ws_floats,
+               p.why);
+    const PrefillOps o{A, B, bias, C, ws, ln, epi == PF_QKV ? q : none, s};
+    ZG_TRY(launch_gemm(p, sh, o, qkv));
+    return finish(p, sh, o);
 }
 
 #ifdef ZG_PF_STAMPS

@@ -234,11 +234,20 @@ int launch_gemm_planes(const bf16_t* A, const bf16_t* B, const float* bias, void
 int launch_gemm_s4(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, const GemmPlanes& pl, int ldc,
                    bool gelu, bool out_bf16, int bn, hipStream_t s);  // gemm_s4.hip
 bool gemm_s4_args_ok(const GemmPlanes& pl, int ldc);            // the bounds of gemm_s4_kernel's packed arguments
-// ... and its epilogue kinds for the whole-prompt Linears (gemm_s4.hip; PrefillQkv below)
+// The launch of the persistent kernel's 192-wide instantiation (NT = 3: the only one launched) over `items` 256 x 192 tiles (x K
+// slices) in tiles_n tile columns: at most wg_cap workgroups, each walking a range of the tile order in column bands `band` tiles
+// wide; lds = that instantiation's dynamic LDS bytes (what a plan reports; the launch takes them from the kernel's own traits)
+struct S4Grid {
+    int grid, band, lds;
+};
+int gemm_s4_wg_cap();  // 256, or ZGPT2_GEMM_WGS (tests: few workgroups, many tiles each)
+S4Grid gemm_s4_grid(int items, int tiles_n, int wg_cap);
+// ... and its epilogue kinds for the whole-prompt Linears (gemm_s4.hip; PrefillQkv, PrefillGemmPlan below)
 enum { S4_PLAIN = 0, S4_PARTIAL = 1, S4_QKV = 2, S4_SPLIT3 = 3 };
 struct PrefillQkv;
-int launch_gemm_s4_prefill(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int nplanes, int kind, int n_slices,
-                           const PrefillQkv* qkv, hipStream_t s);
+struct PrefillGemmPlan;
+int launch_gemm_s4_prefill(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, const PrefillGemmPlan& p, const PrefillQkv* qkv,
+                           hipStream_t s);
 int gemm_s4_stamps(unsigned long long* out, size_t n_words);  // diagnostic (ZGPT2_GEMM_DBG bit 256)
 int gemm_s4_fault(unsigned* out);  // 1: a stream-K consumer of gemm_s4 gave up waiting for its producer since the last call (results wrong)
 int gemm_debug_stamps(unsigned long long* out, size_t n_words);  // of the kernel generation launched last
@@ -281,12 +290,49 @@ struct PrefillLn {
     float eps;
     bf16_t* out;
 };
+constexpr int kWeightPlanes = 33;
+// A forced route (tests, measurements; zg_debug_prefill_route in include/zgpt2.h): kernel 0 = the library's rule; slices > 0 = the K slices of a residual Linear
+struct PrefillForce {
+    int kernel, slices;
+};
+// How one whole-prompt Linear runs: decided once per launch by prefill_gemm_plan (prefill.hip holds every threshold and all of the
+// slice, tile and stream-K arithmetic), carried out by launch_prefill_gemm, which derives nothing again.
+struct PrefillGemmShape {
+    int M, N, K, ldc, epi, nsplit;  // nsplit: 2, kSplit or kWeightPlanes
+    size_t ws_floats;
+    bool have_ws, have_ln;
+    int qkv_e;                       // PrefillQkv.E (0 = none given) and its stream-K operands
+    bool have_sk_ws, have_sk_flags;
+    size_t sk_ws_bytes;
+    unsigned sk_flags_words;
+    PrefillForce force;
+};
+enum PrefillFamily { PFF_S4 = 1 /* gemm_s4_kernel */, PFF_T128 = 2 /* prefill_gemm_kernel */, PFF_T128_WP = 3 /* prefill_gemm_wp_kernel: fp32 weights */ };
+enum PrefillTail { PFT_NONE = 0, PFT_LN_SPLIT = 1, PFT_REDUCE = 2, PFT_REDUCE_LN_SPLIT = 3, PFT_REDUCE_RESID_LN = 4 };
+struct PrefillGemmPlan {
+    int status;       // ZG_OK, or the refusal (then `why` says it and nothing else is set)
+    const char* why;
+    int family;
+    int s4_kind;      // PFF_S4: the epilogue kind, and S4_QKV with the half-tile hand-over
+    bool stream_k;
+    int ns, nspl;     // 128-row kernels: 64-column strips per wave (tile = 128 x 128 ns), activation planes multiplied (0 on PFF_T128_WP)
+    bool partial;     // the GEMM writes fp32 slabs to the workspace and the tail finishes (always so on PFF_T128_WP)
+    int grid_x, grid_y, block, lds;
+    int slices, slabs;      // K slices of the GEMM; slabs the tail sums (PFF_T128_WP: three passes per slice)
+    int xcd_rows, tiles_n;  // 128-row kernels: the packed tp word (prefill_gemm_body)
+    int band, s4_ldc;       // PFF_S4: tile-order band width, row length of its output, the plane pairs of its K loop
+    GemmPlanes planes;
+    int tail;
+};
+// Pure host code: no HIP call, no allocation.  Reads ZGPT2_GEMM_WGS once (per call: tests flip it between launches).
+PrefillGemmPlan prefill_gemm_plan(const PrefillGemmShape& sh);
+// force: null = the process-wide pin of prefill_force_route (zg_debug_prefill_route)
 int launch_prefill_gemm(const bf16_t* A, const bf16_t* W, const float* bias, void* C, int M, int N, int K, int ldc, int epi,
                         float* ws, size_t ws_floats, const PrefillLn* ln, hipStream_t s, const PrefillQkv* qkv = nullptr,
-                        int nsplit = kSplit);  // nsplit = 2: multiply the hi + mid planes only (2/3 of the matrix work);
-                                               // kWeightPlanes: W is the plane-major three-term split [3][N][K] of an fp32 matrix
-constexpr int kWeightPlanes = 33;
-void prefill_force_route(int kernel, int slices);  // zg_debug_prefill_route / _linear: pin the GEMM family (1 gemm_s4, 2 the 128-row kernels) and the K slices
+                        int nsplit = kSplit,  // nsplit = 2: multiply the hi + mid planes only (2/3 of the matrix work);
+                                              // kWeightPlanes: W is the plane-major three-term split [3][N][K] of an fp32 matrix
+                        const PrefillForce* force = nullptr);
+void prefill_force_route(int kernel, int slices);  // zg_debug_prefill_route: pin the route of every whole-prompt Linear of the process
 // Where the prompt attention reads K and V: the k / v columns of the qkv rows (k == nullptr; a whole prompt only), or head-major
 // caches [b][h][ctx][64] in storage format fmt (0 fp32, 1 fp16, 2 B24 with its byte plane kv_lo bytes behind the bf16 plane)
 struct PrefillKv {
