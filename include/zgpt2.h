@@ -360,6 +360,38 @@ int zg_gpt_extend(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token
 /* argmax of the logits of the last zg_gpt_forward(compute_logits=1) per sequence (lowest index
  * wins ties; logits that are all NaN give index 0) — the greedy replacement for GPT.sample (src/main.zig:198-207). */
 int zg_gpt_argmax(zg_gpt* g, size_t* tokens_out, size_t n_tokens);
+/* Diagnostic (tests): zg_gpt_forward(seq_len, tokens, compute_logits = 1) with every launch class of the step tapped.  The step is
+ * launched eagerly on the handle's stream (no graph) with the arguments, plans and launch ids of a plain step; behind each launch
+ * class device-to-device copies on the same stream save what it wrote, raw, in the storage the handle's modes use.  arena_out
+ * (host) receives the copies, table_out one zg_tap_entry per copy, in launch order; info[ZG_TAP_INFO_INTS]: activation planes on,
+ * tile statistics on, tagged hand-overs on, fused batch-1 launch on, max attention splits, lm_head grid, t_hi of the step, KV mode
+ * (0 fp32, 1 fp16, 2 B24), weight type (0 bf16, 1 fp32, 2 B24).  arena_out == NULL: nothing runs; *arena_used and *n_entries
+ * report what a call needs.  Classes: -1 the layer's caches as the step finds them, 0 embed, 1 ln_1 + c_attn, 2 attention,
+ * 3 attn c_proj, 4 ln_2 + c_fc, 5 mlp c_proj, 6 lm_head.  What is tapped:
+ *   0, 3, 5  x [B][E]; planes on: xp (plane layout, element (p, m, k) at (((k >> 5) * 3 + p) * 8 + m) * 32 + (k & 31), 3 x 8 x E
+ *            bf16) and, statistics on, xst [8][E / 16][2] (sum, sum of squares).  Behind class 5 of the last layer the planes and
+ *            statistics are tapped with ZG_TAP_NOT_WRITTEN: that launch must leave them alone
+ *   -1, 1    K and V rows of positions < seq_len, [B][H][seq_len][64]: fp32, fp16, or B24 as a bf16 plane (ZG_TAP_K / _V) and a
+ *            byte plane (ZG_TAP_K_LO / _V_LO); class 1 also q [B][E]
+ *   2        planes off: the attention partials [B][H][max_splits][66] (o[64], m, l; splits at or beyond ceil(t_hi / 256) are not
+ *            written); planes on: the merged heads ap (plane layout)
+ *   4        h4 [B][4 E], or planes on: hp (plane layout, 3 x 8 x 4 E)
+ *   6        logits [B][V], and the argmax partials (value, index) [B][lm_head grid]
+ * ZG_TAP_FUSED: classes 1 and 2 ran as the one batch-1 launch (attn_qkv): both are tapped behind it; it writes q, the new K / V
+ * rows and the partials as the two launches do. */
+typedef struct zg_tap_entry {
+    int cls, layer, buffer, type; /* ZG_TAP_X ..., ZG_TAP_F32 ... */
+    size_t offset, count;         /* bytes from the arena's start, elements */
+    unsigned flags, pad;
+} zg_tap_entry;
+enum { ZG_TAP_X = 0, ZG_TAP_XP, ZG_TAP_XST, ZG_TAP_Q, ZG_TAP_K, ZG_TAP_K_LO, ZG_TAP_V, ZG_TAP_V_LO, ZG_TAP_PART, ZG_TAP_AP, ZG_TAP_H4, ZG_TAP_HP,
+       ZG_TAP_LOGITS, ZG_TAP_PART_VAL, ZG_TAP_PART_IDX };
+enum { ZG_TAP_F32 = 0, ZG_TAP_F16, ZG_TAP_BF16, ZG_TAP_U8, ZG_TAP_I32 };
+#define ZG_TAP_FUSED 1u
+#define ZG_TAP_NOT_WRITTEN 2u
+#define ZG_TAP_INFO_INTS 9
+int zg_debug_gpt_step_taps(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, void* arena_out, size_t arena_bytes, size_t* arena_used,
+                           zg_tap_entry* table_out, size_t table_len, size_t* n_entries, int* info, size_t n_info);
 /* GPT.sample — src/main.zig:198-207 for all sequences: zg_gpt_forward(seq_len, tokens, logits), then
  * logits /= temp, softmax, and an index drawn with probability proportional to the result
  * (std.rand weightedIndex: first index whose running sum exceeds u * total).  The reference re-seeds

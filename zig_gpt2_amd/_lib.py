@@ -50,6 +50,13 @@ class GptOptions(C.Structure):
     _fields_ = [("share_weights_with", vp), ("own_stream", C.c_int), ("stream_priority", C.c_int)]
 
 
+class TapEntry(C.Structure):
+    """zg_tap_entry of include/zgpt2.h."""
+
+    _fields_ = [("cls", C.c_int), ("layer", C.c_int), ("buffer", C.c_int), ("type", C.c_int), ("offset", sz), ("count", sz),
+                ("flags", C.c_uint), ("pad", C.c_uint)]
+
+
 # name -> (restype, argtypes); every symbol include/zgpt2.h declares
 SIGNATURES = {
     "zg_init": (C.c_int, [C.c_int]),
@@ -105,6 +112,7 @@ SIGNATURES = {
     "zg_gpt_generate_from_enqueue": (C.c_int, [vp, sz, vp, sz, vp, sz, vp, C.c_uint64]),
     "zg_gpt_generate_fetch_range": (C.c_int, [vp, sz, sz, vp, sz]),
     "zg_gpt_argmax": (C.c_int, [vp, vp, sz]),
+    "zg_debug_gpt_step_taps": (C.c_int, [vp, sz, vp, sz, vp, sz, szp, vp, sz, szp, vp, sz]),
     "zg_gpt_sample": (C.c_int, [vp, sz, vp, sz, C.c_float, vp, C.c_uint64, vp, vp, sz]),
     "zg_gpt_hidden": (C.c_int, [vp, vp, sz]),
     "zg_gpt_generate_greedy": (C.c_int, [vp, vp, sz, vp, sz, vp, sz]),
@@ -139,6 +147,11 @@ BLOCK_SLOTS = ["ln_1_g", "ln_1_b", "c_attn_w", "c_attn_b", "c_proj_w", "c_proj_b
                "ln_2_g", "ln_2_b", "c_fc_w", "c_fc_b", "mlp_proj_w", "mlp_proj_b"]
 TOP_SLOTS = ["wte", "wpe", "ln_f_g", "ln_f_b"]
 TIME_LM_HEAD = 6
+# zg_debug_gpt_step_taps: buffers, element types (numpy: bf16 and the B24 byte plane stay raw), flags, info words
+TAP_BUFFERS = ["x", "xp", "xst", "q", "k", "k_lo", "v", "v_lo", "part", "ap", "h4", "hp", "logits", "part_val", "part_idx"]
+TAP_DTYPES = ["<f4", "<f2", "<u2", "u1", "<i4"]
+TAP_FUSED, TAP_NOT_WRITTEN = 1, 2
+TAP_INFO = ["planes", "stats", "tags", "fused", "max_splits", "lm_grid", "t_hi", "kv_mode", "weight_type"]
 
 
 def build(force=False):

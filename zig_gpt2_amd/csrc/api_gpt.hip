@@ -568,7 +568,81 @@ struct StepOpts {
     int salt = -1;
     SamplerMode sampler = GREEDY;  // what follows lm_head (with_logits only)
     bool pen = false;              // the penalty stage between lm_head and the sampler (a sampler only)
+    struct StepTaps* taps = nullptr;  // zg_debug_gpt_step_taps: behind every launch class, copies of what it wrote (eager steps only)
 };
+
+// The tap sink of a step (tests): an arena in device memory that device-to-device copies on the step's own stream fill behind
+// each launch class, and the table that says what lies where.  With no arena (base == nullptr) nothing is copied and the table
+// and `used` alone are built: the sizing pass.  The launches of a tapped step are those of a plain one.
+struct StepTaps {
+    char* base = nullptr;
+    size_t cap = 0, used = 0;
+    size_t seq_len = 0;
+    std::vector<zg_tap_entry> table;
+};
+
+// One buffer into the sink: `rows` rows of row_bytes, src_pitch bytes apart in the source, packed in the arena
+int tap_put(StepTaps* t, int cls, size_t layer, int buffer, int type, unsigned flags, const void* src, size_t rows, size_t row_bytes, size_t src_pitch,
+            hipStream_t s) {
+    static const size_t elem[5] = {4, 2, 2, 1, 4};
+    const size_t off = (t->used + 255) & ~(size_t)255;
+    zg_tap_entry e{};
+    e.cls = cls, e.layer = (int)layer, e.buffer = buffer, e.type = type;
+    e.offset = off, e.count = rows * row_bytes / elem[type], e.flags = flags;
+    ZG_REQUIRE(!t->base || off + rows * row_bytes <= t->cap, ZG_ERR_ARG, "step taps: %zu bytes at %zu beyond the arena's %zu", rows * row_bytes, off, t->cap);
+    t->table.push_back(e);
+    t->used = off + rows * row_bytes;
+    if (!t->base || rows * row_bytes == 0) return ZG_OK;
+    if (rows == 1 || src_pitch == row_bytes) ZG_HIP(hipMemcpyAsync(t->base + off, src, rows * row_bytes, hipMemcpyDeviceToDevice, s));
+    else ZG_HIP(hipMemcpy2DAsync(t->base + off, row_bytes, src, src_pitch, row_bytes, rows, hipMemcpyDeviceToDevice, s));
+    return ZG_OK;
+}
+
+// What launch class cls of layer l wrote (include/zgpt2.h zg_debug_gpt_step_taps lists it), raw, in the handle's storage.
+// cls -1: the layer's caches as the step finds them.  flags: ZG_TAP_* of the header.
+int tap_class(const zg_gpt* g, StepTaps* t, int cls, size_t l, unsigned flags, hipStream_t s) {
+    if (!t) return ZG_OK;
+    const size_t E = g->cfg.n_embed, B = g->batch, H = g->cfg.n_heads, C = g->cfg.context_size, V = g->cfg.vocab_size;
+    auto whole = [&](int buffer, int type, const void* src, size_t bytes, unsigned f) { return tap_put(t, cls, l, buffer, type, f, src, 1, bytes, bytes, s); };
+    auto x_side = [&](bool planes_written) -> int {  // x and, with planes on, what travels with it
+        ZG_TRY(whole(ZG_TAP_X, ZG_TAP_F32, g->x, B * E * 4, flags));
+        if (g->pl_on) ZG_TRY(whole(ZG_TAP_XP, ZG_TAP_BF16, g->xp, E * 48, flags | (planes_written ? 0u : ZG_TAP_NOT_WRITTEN)));
+        if (g->st_on) ZG_TRY(whole(ZG_TAP_XST, ZG_TAP_F32, g->xst, ((E + 15) / 16) * 8 * 2 * 4, flags | (planes_written ? 0u : ZG_TAP_NOT_WRITTEN)));
+        return ZG_OK;
+    };
+    auto caches = [&]() -> int {  // positions < seq_len of every (sequence, head): [B][H][seq_len][64]
+        const zg_layer& y = g->layers[l];
+        const size_t T = t->seq_len, lo = B * C * E * 2;
+        const void* kv[2] = {y.k_cache, y.v_cache};
+        for (int i = 0; i < 2; ++i) {
+            const char* p = reinterpret_cast<const char*>(kv[i]);
+            const int b0 = i ? ZG_TAP_V : ZG_TAP_K;
+            if (g->kv_mode == 0) ZG_TRY(tap_put(t, cls, l, b0, ZG_TAP_F32, flags, p, B * H, T * 256, C * 256, s));
+            else ZG_TRY(tap_put(t, cls, l, b0, g->kv_mode == 1 ? ZG_TAP_F16 : ZG_TAP_BF16, flags, p, B * H, T * 128, C * 128, s));
+            if (g->kv_mode == 2) ZG_TRY(tap_put(t, cls, l, b0 + 1, ZG_TAP_U8, flags, p + lo, B * H, T * 64, C * 64, s));
+        }
+        return ZG_OK;
+    };
+    switch (cls) {
+        case -1: return caches();
+        case 0: return x_side(true);
+        case 1:
+            ZG_TRY(whole(ZG_TAP_Q, ZG_TAP_F32, g->q, B * E * 4, flags));
+            return caches();
+        case 2:
+            if (g->pl_on) return whole(ZG_TAP_AP, ZG_TAP_BF16, g->ap, E * 48, flags);
+            return whole(ZG_TAP_PART, ZG_TAP_F32, g->part, B * H * g->max_splits * kPartStride * 4, flags);
+        case 3: return x_side(true);
+        case 4:
+            if (g->pl_on) return whole(ZG_TAP_HP, ZG_TAP_BF16, g->hp, 4 * E * 48, flags);
+            return whole(ZG_TAP_H4, ZG_TAP_F32, g->h4, B * 4 * E * 4, flags);
+        case 5: return x_side(l + 1 < g->cfg.n_layer);
+        default:
+            ZG_TRY(whole(ZG_TAP_LOGITS, ZG_TAP_F32, g->logits, B * V * 4, flags));
+            ZG_TRY(tap_put(t, cls, l, ZG_TAP_PART_VAL, ZG_TAP_F32, flags, g->part_val, B, (size_t)g->lm_grid * 4, (size_t)g->lm_grid * 4, s));
+            return tap_put(t, cls, l, ZG_TAP_PART_IDX, ZG_TAP_I32, flags, g->part_idx, B, (size_t)g->lm_grid * 4, (size_t)g->lm_grid * 4, s);
+    }
+}
 
 // The history the penalty stage of a handle reads: the prior buffer alone (zg_gpt_sample_pen: the caller's explicit history), or
 // followed by the generate loop's own record from PenParams.past_len on
@@ -602,12 +676,14 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
     else if (only < 0 || only == 0) {
         EmbedArgs e = embed_args(g, only == 0 ? 3 : 0);  // main.zig:179-183
         ZG_TRY(launch_embed_step(e, s));
+        ZG_TRY(tap_class(g, o.taps, 0, 0, 0, s));
     }
     ZG_TRY(prof_mark(prof, 0, s));
     for (size_t l = (only < 0 ? 0 : o.only_layer); l < (only < 0 ? g->cfg.n_layer : o.only_layer + 1); ++l) {
         const zg_layer& y = g->layers[l];
         // one sequence: classes 1 and 2 as one launch (attn_qkv.hip), timed as class 1; the prefetcher's table keeps both entries
         const bool fused = g->fused_on && !rec && 2 * l + 2 <= 255;
+        ZG_TRY(tap_class(g, o.taps, -1, l, 0, s));
         if (fused && (only < 0 || only == 1)) {
             const GemvArgs a = c_attn_args(g, y, t_hi, m);
             AttnArgs at = attn_args(g, y, t_hi);
@@ -617,8 +693,13 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
             ZG_TRY(launch_attn_qkv(a, gemv_plan(a, g->wt), g->wt, at, g->epoch, g->qkv_tag, s));
             ZG_TRY(prof_mark(prof, 1, s));
             ZG_TRY(prof_mark(prof, 2, s));
+            ZG_TRY(tap_class(g, o.taps, 1, l, ZG_TAP_FUSED, s));
+            ZG_TRY(tap_class(g, o.taps, 2, l, ZG_TAP_FUSED, s));
         }
-        if (!fused && (only < 0 || only == 1)) ZG_TRY(gemv(c_attn_args(g, y, t_hi, m), 1));
+        if (!fused && (only < 0 || only == 1)) {
+            ZG_TRY(gemv(c_attn_args(g, y, t_hi, m), 1));
+            ZG_TRY(tap_class(g, o.taps, 1, l, 0, s));
+        }
         if ((!fused && only < 0) || only == 2) {   // scaled_dot_product_attention over the cache: ops.zig:160 -> :249-307
             AttnArgs a = attn_args(g, y, t_hi);
             if (g->pl_on) {
@@ -646,18 +727,27 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
             } else
                 ZG_TRY(launch_attn_decode(a, s));
             ZG_TRY(prof_mark(prof, 2, s));
+            ZG_TRY(tap_class(g, o.taps, 2, l, 0, s));
         }
-        if (only < 0 || only == 3) ZG_TRY(gemv(c_proj_args(g, y, t_hi, m), 3));
-        if (only < 0 || only == 4) ZG_TRY(gemv(c_fc_args(g, y, t_hi, m), 4));
+        if (only < 0 || only == 3) {
+            ZG_TRY(gemv(c_proj_args(g, y, t_hi, m), 3));
+            ZG_TRY(tap_class(g, o.taps, 3, l, 0, s));
+        }
+        if (only < 0 || only == 4) {
+            ZG_TRY(gemv(c_fc_args(g, y, t_hi, m), 4));
+            ZG_TRY(tap_class(g, o.taps, 4, l, 0, s));
+        }
         if (only < 0 || only == 5) {
             GemvArgs a = mlp_proj_args(g, l, t_hi, m);
             if (a.sk_tag) a.launch_id = launch_id(l, 1);
             ZG_TRY(gemv(a, 5));
+            ZG_TRY(tap_class(g, o.taps, 5, l, 0, s));
         }
     }
     if (with_logits && (only < 0 || only == 6)) {
         ZG_TRY(enqueue_lm_head(g, s, rec));
         ZG_TRY(prof_mark(prof, 6, s));
+        ZG_TRY(tap_class(g, o.taps, 6, 0, 0, s));
     }
     // GPT.sample's tail (main.zig:200-206) on the logits of this step: the next step's embed kernel feeds what it draws (mode 2)
     if (o.sampler == GREEDY || !with_logits || only >= 0 || rec) return ZG_OK;
@@ -1344,7 +1434,9 @@ int zg_gpt_step_bytes(zg_gpt* g, size_t seq_len, size_t* weight_bytes, size_t* k
 }
 
 // GPT.forward enqueued on the handle's stream, nothing drained (zg_gpt_forward drains; zg_gpt_sample puts its sampler behind it first)
-static int forward_enqueue(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, int compute_logits, float* logits_out, size_t logits_len) {
+// taps (zg_debug_gpt_step_taps): the same step launched eagerly, with copies of what each launch class wrote behind it
+static int forward_enqueue(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, int compute_logits, float* logits_out, size_t logits_len,
+                           StepTaps* taps = nullptr) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && tokens, ZG_ERR_ARG, "gpt_forward: null argument");
     ZG_REQUIRE(n_tokens == g->batch, ZG_ERR_SHAPE, "gpt_forward: %zu tokens for batch %zu", n_tokens, g->batch);
@@ -1368,7 +1460,12 @@ static int forward_enqueue(zg_gpt* g, size_t seq_len, const size_t* tokens, size
     if (seq_len > g->kv_dirty_hi) g->kv_dirty_hi = seq_len;
     ZG_TRY(note_steps(g, 1, s));
     ZG_TRY(ensure_ln_folded(g, s));
-    ZG_TRY(run_step(g, compute_logits != 0, seq_len, s));
+    if (taps) {
+        StepOpts o;
+        o.taps = taps;
+        ZG_TRY(enqueue_step(g, compute_logits != 0, bucket_t_hi(g, seq_len), s, o));
+    } else
+        ZG_TRY(run_step(g, compute_logits != 0, seq_len, s));
     if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, g->batch * V, s));
     return ZG_OK;
 }
@@ -1379,6 +1476,52 @@ int zg_gpt_forward(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tok
     // h_ints / h_ctrl are reused by the next call: drain before returning.
     ZG_HIP(hipStreamSynchronize(gs(g)));
     return check_fault(g);
+}
+
+// zg_gpt_forward(seq_len, tokens, compute_logits = 1) as an eager step whose launch classes are tapped (tests; include/zgpt2.h).
+// arena_out == nullptr: nothing runs, the sizes alone are reported.  Allocates its device arena per call.
+int zg_debug_gpt_step_taps(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, void* arena_out, size_t arena_bytes, size_t* arena_used,
+                           zg_tap_entry* table_out, size_t table_len, size_t* n_entries, int* info, size_t n_info) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && tokens && arena_used && n_entries, ZG_ERR_ARG, "debug_gpt_step_taps: null argument");
+    ZG_REQUIRE(seq_len >= 1 && seq_len <= g->cfg.context_size, ZG_ERR_SHAPE, "debug_gpt_step_taps: seq_len %zu outside 1..%zu", seq_len, g->cfg.context_size);
+    const size_t L = g->cfg.n_layer;
+    StepTaps plan;  // the sizing pass: the table of the step, nothing copied
+    plan.seq_len = seq_len;
+    ZG_TRY(tap_class(g, &plan, 0, 0, 0, nullptr));
+    for (size_t l = 0; l < L; ++l)
+        for (int cls = -1; cls <= 5; ++cls)
+            if (cls != 0) ZG_TRY(tap_class(g, &plan, cls, l, 0, nullptr));
+    ZG_TRY(tap_class(g, &plan, 6, 0, 0, nullptr));
+    const size_t cap = plan.used + 256 * (plan.table.size() + 1);  // (the step's own order pads differently)
+    *arena_used = cap;
+    *n_entries = plan.table.size();
+    if (info && n_info >= ZG_TAP_INFO_INTS) {
+        const int v[ZG_TAP_INFO_INTS] = {g->pl_on, g->st_on, g->tags_on, g->fused_on, g->max_splits, g->lm_grid, bucket_t_hi(g, seq_len), g->kv_mode, g->wt};
+        memcpy(info, v, sizeof(v));
+    }
+    if (!arena_out) return ZG_OK;
+    ZG_REQUIRE(table_out && arena_bytes >= cap && table_len >= plan.table.size(), ZG_ERR_SHAPE, "debug_gpt_step_taps: %zu arena bytes and %zu table entries needed",
+               cap, plan.table.size());
+    hipStream_t s = gs(g);
+    StepTaps taps;
+    taps.seq_len = seq_len;
+    taps.cap = cap;
+    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&taps.base), cap));
+    struct Free {
+        char* p;
+        ~Free() { (void)hipFree(p); }
+    } guard{taps.base};
+    ZG_HIP(hipMemsetAsync(taps.base, 0, cap, s));
+    ZG_TRY(forward_enqueue(g, seq_len, tokens, n_tokens, 1, nullptr, 0, &taps));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    ZG_REQUIRE(taps.used <= cap && taps.table.size() == plan.table.size(), ZG_ERR_ARG, "debug_gpt_step_taps: the step tapped %zu entries in %zu bytes, planned %zu in %zu",
+               taps.table.size(), taps.used, plan.table.size(), cap);
+    ZG_HIP(hipMemcpy(arena_out, taps.base, taps.used, hipMemcpyDeviceToHost));
+    memcpy(table_out, taps.table.data(), taps.table.size() * sizeof(zg_tap_entry));
+    *arena_used = taps.used;
+    return ZG_OK;
 }
 
 // The whole-prompt pass: n tokens of every sequence go to positions past_len .. past_len + n - 1 behind the cached

@@ -131,6 +131,25 @@ class GPT:
                                      ptr(logits), ops._n(logits)))
         return logits
 
+    def step_taps(self, seq_len, tokens):
+        """zg_debug_gpt_step_taps: forward(seq_len, tokens) as an eager step with every launch class tapped.  Returns (taps, info):
+        taps is a list of dicts {cls, layer, name, flags, data} in launch order, data the raw buffer as a numpy array of its storage
+        type (bf16 planes as uint16); info the handle's decode modes by name (_lib.TAP_INFO)."""
+        tokens = np.ascontiguousarray(np.atleast_1d(tokens), dtype=np.uint64)
+        used, n = C.c_size_t(), C.c_size_t()
+        info = np.zeros(len(_lib.TAP_INFO), np.int32)
+        check(self._L.zg_debug_gpt_step_taps(self.h, seq_len, ptr(tokens), tokens.size, None, 0, C.byref(used), None, 0, C.byref(n), ptr(info), info.size))
+        arena = np.zeros(used.value, np.uint8)
+        table = (_lib.TapEntry * n.value)()
+        check(self._L.zg_debug_gpt_step_taps(self.h, seq_len, ptr(tokens), tokens.size, ptr(arena), arena.size, C.byref(used), C.addressof(table), n.value,
+                                             C.byref(n), ptr(info), info.size))
+        taps = []
+        for e in table[: n.value]:
+            dt = np.dtype(_lib.TAP_DTYPES[e.type])
+            data = arena[e.offset: e.offset + e.count * dt.itemsize].view(dt).copy()
+            taps.append({"cls": e.cls, "layer": e.layer, "name": _lib.TAP_BUFFERS[e.buffer], "flags": e.flags, "data": data})
+        return taps, dict(zip(_lib.TAP_INFO, (int(v) for v in info)))
+
     def cached_len(self):
         """Positions the handle's caches hold (zg_gpt_cached_len)."""
         n = C.c_size_t()
