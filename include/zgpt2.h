@@ -262,6 +262,10 @@ enum {
                                       sampler, all three sampler forms) at create as well (otherwise a penalised generation
                                       captures those of the buckets it touches when it begins, before its first step: the one
                                       place such a call may allocate).  context_size > 8192: ZG_ERR_UNSUPPORTED */
+    ZG_GPT_LOGPROBS_GENERATE = 1 << 11, /* capture the decode graphs of zg_gpt_generate_logprobs_enqueue at create as well: the
+                                      log-probability twins of every graph with lm_head that create captures (the greedy ones, and
+                                      those of the ZG_GPT_SAMPLED_ / _TRUNCATED_ / _PENALIZED_GENERATE flags given beside it);
+                                      otherwise such a generation captures those of the buckets it touches when it begins */
     ZG_GPT_WEIGHTS_B24 = 1 << 8  /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
                                     value rounded to nearest even at 16 mantissa bits (never to inf), row r of an [out][in]
                                     matrix = [in bf16-shaped upper halves | in low bytes].  3/4 of fp32's weight bytes, 2^-17
@@ -506,6 +510,39 @@ int zg_gpt_generate_pen_enqueue(zg_gpt* g, size_t past_len, const size_t* prompt
  * workspace per call. */
 int zg_debug_penalize_rows(const float* logits, size_t batch, size_t vocab, const zg_logit_penalties* penalties, const size_t* history,
                            size_t history_stride, const size_t* history_lens, float* logits_out, unsigned* counts_out_or_null);
+/* ---- Per-token log-probabilities and top-N alternatives from the device loop.  Step p (sequence length p + 1)
+ * records the pick of column p of row b.  Let x be that row of logits as the sampler stage receives it: the raw lm_head output, or,
+ * in a penalised generation, the row as the penalties leave it — always at temperature 1 and before any truncation (OpenAI and
+ * vLLM report the same: what the model, with the caller's penalties, thought — not what the sampler's temperature and filters
+ * made of it; with penalties off it is the model's own distribution).  With m = max x and S = sum exp(x_i - m):
+ *   logprob[b][p]         = (x[tok] - m) - log S, tok the token column p records.
+ *   top_ids[b][p][j]      = the indices of the top_n largest x, value descending, index ascending on ties (-0.0 and +0.0 tie, -inf
+ *                           is an ordinary value); exact, comparisons only.
+ *   top_logprobs[b][p][j] = the same expression for top_ids[b][p][j] with the same m and S: where the id is tok, bit for bit logprob.
+ * A column that records a prompt token (p < past_len + prompt_lens[b], the whole-prompt pass included) reads logprob = NaN and its
+ * ids mean nothing.  A row holding NaN or +inf gives unspecified values; its ids are still < vocab and nothing faults.  All sums run
+ * in a fixed order without atomics: the same inputs give the same bits on every run.  fp32 throughout: within
+ * 1e-5 + 2.5e-7 |logprob| of the float64 value.  top_n in 0 .. ZG_LOGPROBS_TOP_MAX and <= vocab_size, else ZG_ERR_ARG before anything
+ * is enqueued or the handle's state is touched. */
+#define ZG_LOGPROBS_TOP_MAX 20
+/* zg_gpt_generate_pen_enqueue / _from_enqueue with the log-probability stage.  options NULL: greedy (penalties must be NULL then,
+ * else ZG_ERR_ARG; greedy with penalties is top_k = 1).  penalties NULL or all off: none.  Tokens are exactly those of the same
+ * call without log-probabilities.  Two more launches per step in graphs of their own (ZG_GPT_LOGPROBS_GENERATE); top_n lives in
+ * device memory, one graph serves every value.  Does not allocate beyond that capture. */
+int zg_gpt_generate_logprobs_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens,
+                                     size_t n_steps, const zg_sample_options* options_or_null, const zg_logit_penalties* penalties_or_null,
+                                     const size_t* prior_or_null, size_t prior_stride, const size_t* prior_lens_or_null, uint64_t seed,
+                                     size_t top_n);
+/* Columns first .. first + n - 1, as zg_gpt_generate_fetch_range: logprobs_out [batch, n]; top_ids_out / top_logprobs_out
+ * [batch, n, top_n] (both NULL when top_n == 0).  top_n above the recording generation's, or no log-probability generation
+ * since the last generation without: ZG_ERR_ARG.  Columns below a continuation's past_len hold what earlier calls recorded. */
+int zg_gpt_generate_fetch_logprobs(zg_gpt* g, size_t first, size_t n, size_t top_n, float* logprobs_out, size_t logprobs_len,
+                                   size_t* top_ids_out, float* top_logprobs_out, size_t top_len);
+/* Test entry: the two kernels alone on the caller's rows, logits [batch <= 64, vocab <= 262144] and tokens [batch] (host or
+ * device), a small kernel standing in for lm_head's partials as in zg_debug_sample_rows.  A workgroup of the first kernel owns 1024
+ * consecutive elements of a row.  top_n > 20 or > vocab: ZG_ERR_ARG; a token >= vocab: ZG_ERR_SHAPE.  Needs zg_init only. */
+int zg_debug_logprob_rows(const float* logits, size_t batch, size_t vocab, const size_t* tokens, size_t top_n, float* logprobs_out,
+                          size_t* top_ids_out_or_null, float* top_logprobs_out_or_null);
 /* tokens of positions first .. first + n - 1 of the last generation(s): out_tokens [batch, n] */
 int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len);
 /* Test entry: the sampler kernels of zg_gpt_sample_ex on the caller's logits [batch <= 64, vocab <= 262144] (host or device, as

@@ -123,4 +123,18 @@ inline void scaled_dot_product_attention(Slice<const float> q, Slice<const float
                                           outputs.ptr, outputs.len, _attn.ptr, _attn.len));
 }
 
+// Model tier, no reference counterpart (src/main.zig's generate returns token ids only): generate entered at past_len with the
+// log-probability of every pick and its top_n alternatives recorded on the device (zgpt2.h zg_gpt_generate_logprobs_enqueue).
+// options / penalties: nullptr for greedy / none.  Slices as above; prompts is [batch, prompt_stride].
+inline void generate_logprobs(zg_gpt* g, size_t past_len, Slice<const size_t> prompts, size_t prompt_stride, Slice<const size_t> prompt_lens,
+                              size_t n_steps, const zg_sample_options* options, const zg_logit_penalties* penalties, uint64_t seed, size_t top_n) {
+    check(zg_gpt_generate_logprobs_enqueue(g, past_len, prompts.ptr, prompt_stride, prompt_lens.ptr, n_steps, options, penalties, nullptr, 0, nullptr,
+                                           seed, top_n));
+}
+// columns first .. first + n - 1: logprobs [batch, n] (NaN where a column records a prompt token), top_ids / top_logprobs [batch, n, top_n]
+inline void generate_fetch_logprobs(zg_gpt* g, size_t first, size_t n, size_t top_n, Slice<float> logprobs, Slice<size_t> top_ids,
+                                    Slice<float> top_logprobs) {
+    check(zg_gpt_generate_fetch_logprobs(g, first, n, top_n, logprobs.ptr, logprobs.len, top_ids.ptr, top_logprobs.ptr, top_ids.len));
+}
+
 }  // namespace ops

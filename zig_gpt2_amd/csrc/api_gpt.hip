@@ -5,7 +5,7 @@
 // position, tokens and argmax all live in device memory, so a whole greedy generation is enqueued
 // without a host round trip per token.  Three things exist once each: the whole-prompt pass (pass_impl: zg_gpt_prefill is
 // zg_gpt_extend at 0), the generation request (GenRequest, run by gen_run for every zg_gpt_generate*_enqueue) and the shape of a
-// decode step (StepKey {with_logits, multi, SamplerMode, pen}: what enqueue_step launches and which graph replays it).
+// decode step (StepKey {with_logits, multi, SamplerMode, pen, lp}: what enqueue_step launches and which graph replays it).
 //
 // HBM layout (one hipMalloc, 256-B aligned sub-buffers):
 //   [ weights: wte | wpe | ln_f | per layer: c_attn_w c_proj_w c_fc_w mlp_proj_w + fp32 vectors ]
@@ -115,6 +115,16 @@ struct zg_gpt {
     PenParams *pen, *h_pen;
     int* h_prior;
     bool gen_pen;             // the generation in flight penalises its logits
+    // log-probabilities (sample_logprob.h): the chunk workspace, top_n of the generation in flight (device word and
+    // its place in the pinned control block), the record buffers [batch][ctx] / [batch][ctx][20] and the pinned mirror a fetch
+    // copies its columns through ([batch * ctx] log-probabilities, then [batch * ctx * 20] ids, then as many values)
+    LogprobWs lp_ws;
+    LogprobRec lp_rec;
+    int *lp_top, *h_lp_top;
+    float* h_lp;
+    bool gen_lp;              // the generation in flight records them
+    bool lp_valid;            // the last generation did: the record can be fetched
+    size_t lp_top_n;          // ... with this many alternatives
     size_t graph_steps;
     hipStream_t graph_stream;
     size_t steps_enqueued;
@@ -274,6 +284,13 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
         g->pf_ws = (float*)P(g->pf_ws_floats * 4);
         g->sk_flags = (unsigned*)P(2048);
     }
+    // (behind everything else: handles that never ask for log-probabilities keep the layout they had)
+    g->lp_ws = logprob_workspace(P(logprob_workspace_bytes((int)B, (int)V)), (int)B, (int)V);
+    g->lp_top = (int*)P(256);
+    g->lp_rec.logprob = (float*)P(B * C * 4);
+    g->lp_rec.top_ids = (int*)P(B * C * ZG_LOGPROBS_TOP_MAX * 4);
+    g->lp_rec.top_logprobs = (float*)P(B * C * ZG_LOGPROBS_TOP_MAX * 4);
+    g->lp_rec.stride = (int)C;
     g->state_bytes = (cv.off + 255) & ~(size_t)255;
 }
 
@@ -568,6 +585,7 @@ struct StepOpts {
     int salt = -1;
     SamplerMode sampler = GREEDY;  // what follows lm_head (with_logits only)
     bool pen = false;              // the penalty stage between lm_head and the sampler (a sampler only)
+    bool lp = false;               // the log-probability stage behind the sampler (greedy: behind lm_head); with_logits only
     struct StepTaps* taps = nullptr;  // zg_debug_gpt_step_taps: behind every launch class, copies of what it wrote (eager steps only)
 };
 
@@ -750,6 +768,12 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         ZG_TRY(tap_class(g, o.taps, 6, 0, 0, s));
     }
     // GPT.sample's tail (main.zig:200-206) on the logits of this step: the next step's embed kernel feeds what it draws (mode 2)
+    // the log-probability stage reads the row the sampler read and the token the next step's embed kernel will record
+    auto logprobs = [&](const int* tokens) {
+        return launch_logprob(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->part_val, g->part_idx, g->lm_grid, g->lm_grid, g->lp_top, g->lp_ws,
+                              tokens, g->ctrl, g->prompt_len, g->lp_rec, s);
+    };
+    if (o.sampler == GREEDY && o.lp && with_logits && only < 0 && !rec) ZG_TRY(logprobs(nullptr));  // (the greedy graphs have no sampler node)
     if (o.sampler == GREEDY || !with_logits || only >= 0 || rec) return ZG_OK;
     // the penalties act on the raw logits (HF's order); the row-maximum partials both samplers start from are rebuilt behind them
     if (o.pen)
@@ -760,6 +784,7 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
     else
         ZG_TRY(launch_sample_step(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, g->ctrl, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws,
                                   g->sampled, s));
+    if (o.lp) ZG_TRY(logprobs(g->sampled));
     return ZG_OK;
 }
 
@@ -956,17 +981,21 @@ size_t prefill_min() { return 4; }  // shorter prompts go through the decode cha
 //                memory, so the same kernels simply repeat; saves the gap between graph launches in the generate loop
 //   sampler      the sampler node(s) behind lm_head (zg_gpt_generate_sample_*; the option values are read on the device)
 //   pen          the penalty stage in front of the sampler node(s) (zg_gpt_generate_pen_enqueue; a sampler only)
-// multi and a sampler imply with_logits: 15 shapes exist.  Captured at create — the sampled ones with ZG_GPT_SAMPLED_GENERATE /
-// ZG_GPT_TRUNCATED_GENERATE / ZG_GPT_PENALIZED_GENERATE, otherwise when the first generation that needs them begins.
+//   lp           the log-probability stage behind the sampler node(s), or behind lm_head of a greedy step (with_logits only)
+// multi and a sampler imply with_logits: 15 shapes exist without lp and 14 with it (the two greedy ones with lm_head, the twelve
+// sampled ones).  Captured at create — the sampled ones with ZG_GPT_SAMPLED_GENERATE / ZG_GPT_TRUNCATED_GENERATE /
+// ZG_GPT_PENALIZED_GENERATE, the lp twins of what create captures with ZG_GPT_LOGPROBS_GENERATE — otherwise when the first
+// generation that needs them begins.
 struct StepKey {
     bool with_logits, multi;
     SamplerMode sampler;
     bool pen = false;
+    bool lp = false;
 };
-constexpr size_t kStepShapes = 15;
+constexpr size_t kStepShapes = 29;
 size_t step_index(StepKey k) {
-    if (k.sampler == GREEDY) return k.multi ? 2 : k.with_logits;
-    return (k.pen ? 7 : 1) + 2 * (size_t)k.sampler + k.multi;
+    if (k.sampler == GREEDY) return k.lp ? 15 + (size_t)k.multi : k.multi ? 2 : k.with_logits;
+    return (k.lp ? 14 : 0) + (k.pen ? 7 : 1) + 2 * (size_t)k.sampler + k.multi;
 }
 
 size_t bucket_of(size_t seq_len) { return (seq_len + 63) / 64 - 1; }
@@ -1002,6 +1031,7 @@ int graph_exec(zg_gpt* g, StepKey k, size_t b, hipStream_t s, hipGraphExec_t* ou
         StepOpts o;
         o.sampler = k.sampler;
         o.pen = k.pen;
+        o.lp = k.lp;
         ZG_TRY(capture_graph(s, &e, [&] {
             int st = ZG_OK;
             for (size_t i = 0; i < n_steps && st == ZG_OK; ++i) st = enqueue_step(g, k.with_logits, t_hi, s, o);
@@ -1013,11 +1043,12 @@ int graph_exec(zg_gpt* g, StepKey k, size_t b, hipStream_t s, hipGraphExec_t* ou
 }
 
 // The single-step and (where the handle has them) multi-step graphs of a sampler mode, buckets b0 .. b1
-int capture_sampled(zg_gpt* g, SamplerMode mode, bool pen, size_t b0, size_t b1, hipStream_t s) {
+// (lp: their twins with the log-probability stage; then also of GREEDY, whose plain graphs capture_all holds)
+int capture_sampled(zg_gpt* g, SamplerMode mode, bool pen, size_t b0, size_t b1, hipStream_t s, bool lp = false) {
     hipGraphExec_t e;
     for (size_t b = b0; b <= b1 && b < g->n_buckets; ++b) {
-        ZG_TRY(graph_exec(g, {true, false, mode, pen}, b, s, &e));
-        if (g->graph_steps > 1) ZG_TRY(graph_exec(g, {true, true, mode, pen}, b, s, &e));
+        ZG_TRY(graph_exec(g, {true, false, mode, pen, lp}, b, s, &e));
+        if (g->graph_steps > 1) ZG_TRY(graph_exec(g, {true, true, mode, pen, lp}, b, s, &e));
     }
     return ZG_OK;
 }
@@ -1042,24 +1073,33 @@ int capture_all(zg_gpt* g, hipStream_t s) {
         for (SamplerMode m : {ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, false, 0, g->n_buckets - 1, s));
     if (g->flags & ZG_GPT_PENALIZED_GENERATE)
         for (SamplerMode m : {PLAIN, ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, true, 0, g->n_buckets - 1, s));
+    if (g->flags & ZG_GPT_LOGPROBS_GENERATE) {  // the twins of everything above that has lm_head
+        ZG_TRY(capture_sampled(g, GREEDY, false, 0, g->n_buckets - 1, s, true));
+        if (g->flags & ZG_GPT_SAMPLED_GENERATE) ZG_TRY(capture_sampled(g, PLAIN, false, 0, g->n_buckets - 1, s, true));
+        if (g->flags & ZG_GPT_TRUNCATED_GENERATE)
+            for (SamplerMode m : {ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, false, 0, g->n_buckets - 1, s, true));
+        if (g->flags & ZG_GPT_PENALIZED_GENERATE)
+            for (SamplerMode m : {PLAIN, ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, true, 0, g->n_buckets - 1, s, true));
+    }
     return ZG_OK;
 }
 
 // Run one decode step at sequence length seq_len: replay the graph of its bucket, or launch eagerly when graphs
 // are disabled / the stream cannot be captured.
-int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, SamplerMode sampler = GREEDY, bool pen = false) {
+int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, SamplerMode sampler = GREEDY, bool pen = false, bool lp = false) {
     ZG_TRY(ensure_ln_folded(g, s));
-    if (!with_logits) sampler = GREEDY;  // (nothing to draw from)
+    if (!with_logits) sampler = GREEDY, lp = false;  // (nothing to draw from)
     if (sampler == GREEDY) pen = false;
     if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) {
         StepOpts o;
         o.sampler = sampler;
         o.pen = pen;
+        o.lp = lp;
         return enqueue_step(g, with_logits, bucket_t_hi(g, seq_len), s, o);
     }
     if (g->graph_stream != s) ZG_TRY(capture_all(g, s));  // the caller switched streams after zg_gpt_create
     hipGraphExec_t e;
-    ZG_TRY(graph_exec(g, {with_logits, false, sampler, pen}, bucket_of(seq_len), s, &e));
+    ZG_TRY(graph_exec(g, {with_logits, false, sampler, pen, lp}, bucket_of(seq_len), s, &e));
     ZG_HIP(hipGraphLaunch(e, s));
     return ZG_OK;
 }
@@ -1140,6 +1180,7 @@ void release(zg_gpt* g) {
     if (g->arena) (void)hipFree(g->arena);
     if (g->h_ctrl) (void)hipHostFree(g->h_ctrl);
     if (g->h_ints) (void)hipHostFree(g->h_ints);
+    if (g->h_lp) (void)hipHostFree(g->h_lp);
     delete g;
 }
 
@@ -1194,6 +1235,9 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
     e = hipHostMalloc(reinterpret_cast<void**>(&g->h_ctrl), sizeof(StepCtrl) + 512, hipHostMallocDefault);
     // (h_ints, and behind it the staging of the penalties' prior / history: the same shape)
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_ints), 2 * (batch * c.context_size + batch) * sizeof(int), hipHostMallocDefault);
+    // (the mirror of the log-probability record: a fetch copies its columns through it)
+    if (e == hipSuccess)
+        e = hipHostMalloc(reinterpret_cast<void**>(&g->h_lp), batch * c.context_size * (1 + 2 * ZG_LOGPROBS_TOP_MAX) * sizeof(float), hipHostMallocDefault);
     if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(control mirrors)", __FILE__, __LINE__);
     static_assert(sizeof(StepCtrl) + sizeof(SampleParams) <= 256, "the fault word sits 256 bytes behind the control mirror");
     g->h_samp = reinterpret_cast<SampleParams*>(reinterpret_cast<char*>(g->h_ctrl) + 128);  // (same pinned block)
@@ -1201,6 +1245,7 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
     *g->fault = 0;
     g->h_pen = reinterpret_cast<PenParams*>(reinterpret_cast<char*>(g->h_ctrl) + 384);  // (behind zg_gpt_sample's uniforms at 320)
     g->h_prior = g->h_ints + batch * c.context_size + batch;
+    g->h_lp_top = reinterpret_cast<int*>(reinterpret_cast<char*>(g->h_ctrl) + 416);  // (behind h_pen)
     ZG_REQUIRE(!(g->flags & ZG_GPT_PENALIZED_GENERATE) || c.context_size <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED,
                "ZG_GPT_PENALIZED_GENERATE: context_size %zu beyond the %d tokens the penalty kernel's LDS table holds", c.context_size, kPenMaxHistory);
     {   // decode steps per graph in the generate loop: a graph launch costs ~7 us of idle queue (124M: 224.8 us per token
@@ -1780,6 +1825,9 @@ struct GenRequest {
     const size_t* prior = nullptr;
     size_t prior_stride = 0;
     const size_t* prior_lens = nullptr;
+    // the log-probability stage behind every pick with top_n alternatives; lp_on false: the request is what it was
+    bool lp_on = false;
+    size_t top_n = 0;
     GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, const zg_sample_options* opt_or_null = nullptr, uint64_t seed = 0,
                size_t past = 0)
         : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past), mode(opt_or_null ? PLAIN : GREEDY),
@@ -1803,6 +1851,11 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
         ZG_TRY(check_pen_handle(g, "generate_pen"));
         ZG_TRY(check_history(g, r.prior, r.prior_stride, r.prior_lens, n_steps, "generate_pen"));
     }
+    if (r.lp_on) {
+        ZG_REQUIRE(r.top_n <= (size_t)ZG_LOGPROBS_TOP_MAX && r.top_n <= V, ZG_ERR_ARG, "generate_logprobs: top_n %zu outside 0..%zu", r.top_n,
+                   std::min((size_t)ZG_LOGPROBS_TOP_MAX, V));
+        ZG_REQUIRE(V <= (size_t)64 * 4096, ZG_ERR_UNSUPPORTED, "generate_logprobs: vocabulary of %zu beyond %d", V, 64 * 4096);
+    }
     hipStream_t s = gs(g);
     ZG_HIP(hipStreamSynchronize(s));  // pinned staging below is shared with earlier calls
     size_t min_prompt = C;
@@ -1825,6 +1878,16 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     }
     g->gen_pen = pen_on;
     if (pen_on) ZG_TRY(stage_penalties(g, r.pen, past, r.prior, r.prior_stride, r.prior_lens, s));
+    g->gen_lp = g->lp_valid = r.lp_on;
+    if (r.lp_on) {
+        g->lp_top_n = r.top_n;
+        *g->h_lp_top = (int)r.top_n;
+        ZG_HIP(hipMemcpyAsync(g->lp_top, g->h_lp_top, sizeof(int), hipMemcpyHostToDevice, s));
+        // the new columns no step with lm_head reaches (the whole-prompt pass, steps that only feed a prompt token) record prompt
+        // tokens: NaN (every byte 0xff); the stage itself writes the NaN of a longer row's prompt columns
+        const size_t fed = std::min(min_prompt, n_steps);
+        ZG_HIP(hipMemset2DAsync(g->lp_rec.logprob + past, C * sizeof(float), 0xff, fed * sizeof(float), B, s));
+    }
     ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(g->prompt_len, g->h_ints + B * C, B * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_TRY(stage_ctrl(g, past + first, past + first, r.mode != GREEDY ? 2 : 0, s));
@@ -1843,6 +1906,9 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     // (and those of a penalised generation, whatever its sampler)
     if ((filter_launches(g->gen_mode) || g->gen_pen) && !(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && min_prompt < n_steps)
         ZG_TRY(capture_sampled(g, g->gen_mode, g->gen_pen, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
+    // (and the twins with the log-probability stage, the greedy ones too)
+    if (g->gen_lp && !(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && min_prompt < n_steps)
+        ZG_TRY(capture_sampled(g, g->gen_mode, g->gen_pen, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s, true));
     ZG_TRY(note_steps(g, n_steps, s));
     ZG_TRY(pf_start(g, past + n_steps, s));
     g->gen_pos = past + first;  // absolute, as gen_n and gen_min_prompt: gen_pump's steps, buckets and graph alignment follow the position
@@ -1869,11 +1935,11 @@ static int gen_pump(zg_gpt* g, bool* more) {
     if (K > 1 && st >= g->gen_min_prompt && st % K == 0 && st + K <= n_steps && st + K <= C) {
         if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
         hipGraphExec_t e;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64)
-        ZG_TRY(graph_exec(g, {true, true, g->gen_mode, g->gen_pen}, bucket_of(st + 1), s, &e));
+        ZG_TRY(graph_exec(g, {true, true, g->gen_mode, g->gen_pen, g->gen_lp}, bucket_of(st + 1), s, &e));
         ZG_HIP(hipGraphLaunch(e, s));
         g->gen_pos = st + K;
     } else {
-        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_mode, g->gen_pen));
+        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_mode, g->gen_pen, g->gen_lp));
         g->gen_pos = st + 1;
     }
     *more = g->gen_pos < n_steps;
@@ -2017,6 +2083,138 @@ int zg_gpt_generate_pen_enqueue(zg_gpt* g, size_t past_len, const size_t* prompt
         ZG_TRY(check_history(g, prior, prior_stride, prior_lens, 0, "generate_pen"));
     }
     return gen_run(&g, 1, r);
+}
+
+// zg_gpt_generate_pen_enqueue / _from_enqueue with the log-probability stage: a node pair of graphs of their own
+// (StepKey.lp) behind the sampler node, or behind lm_head of a greedy step; top_n lives in device memory.  The stage only reads
+// what the step left, so the tokens are those of the call without it.
+int zg_gpt_generate_logprobs_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                     const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
+                                     const size_t* prior_lens, uint64_t seed, size_t top_n) {
+    ZG_TRY(require_init());
+    if (opt) ZG_TRY(check_sample_options(opt, "generate_logprobs"));
+    ZG_REQUIRE(opt || !pen, ZG_ERR_ARG, "generate_logprobs: penalties without sampler options (greedy picking with penalties is top_k = 1)");
+    if (pen) ZG_TRY(check_penalties(pen, "generate_logprobs"));
+    GenRequest r(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len);
+    r.lp_on = true;
+    r.top_n = top_n;
+    if (pen && !penalties_off(*pen)) {
+        r.pen_on = true;
+        r.pen = *pen;
+        r.prior = prior;
+        r.prior_stride = prior_stride;
+        r.prior_lens = prior_lens;
+    } else if (pen && g) {  // (the lists are still the caller's to get right)
+        ZG_TRY(check_pen_handle(g, "generate_logprobs"));
+        ZG_TRY(check_history(g, prior, prior_stride, prior_lens, 0, "generate_logprobs"));
+    }
+    return gen_run(&g, 1, r);
+}
+
+int zg_gpt_generate_fetch_logprobs(zg_gpt* g, size_t first, size_t n, size_t top_n, float* logprobs_out, size_t logprobs_len, size_t* top_ids_out,
+                                   float* top_logprobs_out, size_t top_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && logprobs_out, ZG_ERR_ARG, "generate_fetch_logprobs: null argument");
+    const size_t C = g->cfg.context_size, B = g->batch, K = ZG_LOGPROBS_TOP_MAX;
+    ZG_REQUIRE(g->lp_valid, ZG_ERR_ARG, "generate_fetch_logprobs: the last generation recorded no log-probabilities");
+    ZG_REQUIRE(top_n <= g->lp_top_n, ZG_ERR_ARG, "generate_fetch_logprobs: top_n %zu above the %zu the generation recorded", top_n, g->lp_top_n);
+    ZG_REQUIRE(top_n == 0 || (top_ids_out && top_logprobs_out), ZG_ERR_ARG, "generate_fetch_logprobs: top_n %zu without its outputs", top_n);
+    ZG_REQUIRE(first <= C && n <= C - first && logprobs_len >= B * n && (top_n == 0 || top_len >= B * n * top_n), ZG_ERR_SHAPE,
+               "generate_fetch_logprobs: positions %zu .. %zu of %zu, %zu and %zu elements", first, first + n, C, logprobs_len, top_len);
+    if (n == 0) return ZG_OK;
+    hipStream_t s = gs(g);
+    float* h_lp = g->h_lp;
+    int* h_ids = reinterpret_cast<int*>(g->h_lp + B * C);
+    float* h_top = g->h_lp + B * C * (1 + K);
+    // the columns asked for, packed [batch][n] and [batch][n][20]
+    ZG_HIP(hipMemcpy2DAsync(h_lp, n * 4, g->lp_rec.logprob + first, C * 4, n * 4, B, hipMemcpyDeviceToHost, s));
+    if (top_n) {
+        ZG_HIP(hipMemcpy2DAsync(h_ids, n * K * 4, g->lp_rec.top_ids + first * K, C * K * 4, n * K * 4, B, hipMemcpyDeviceToHost, s));
+        ZG_HIP(hipMemcpy2DAsync(h_top, n * K * 4, g->lp_rec.top_logprobs + first * K, C * K * 4, n * K * 4, B, hipMemcpyDeviceToHost, s));
+    }
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    memcpy(logprobs_out, h_lp, B * n * sizeof(float));
+    for (size_t i = 0; i < B * n; ++i)
+        for (size_t j = 0; j < top_n; ++j) {
+            top_ids_out[i * top_n + j] = (size_t)h_ids[i * K + j];
+            top_logprobs_out[i * top_n + j] = h_top[i * K + j];
+        }
+    return ZG_OK;
+}
+
+// The log-probability kernels on the caller's rows (tests): the two launches of the stage, a small kernel standing in for
+// lm_head's partials.  Allocates its workspace per call.
+int zg_debug_logprob_rows(const float* logits, size_t batch, size_t vocab, const size_t* tokens, size_t top_n, float* logprobs_out, size_t* top_ids_out,
+                          float* top_logprobs_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(logits && tokens && logprobs_out && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG,
+               "debug_logprob_rows: bad argument");
+    ZG_REQUIRE(top_n <= (size_t)ZG_LOGPROBS_TOP_MAX && top_n <= vocab, ZG_ERR_ARG, "debug_logprob_rows: top_n %zu outside 0..%zu", top_n,
+               std::min((size_t)ZG_LOGPROBS_TOP_MAX, vocab));
+    ZG_REQUIRE(top_n == 0 || (top_ids_out && top_logprobs_out), ZG_ERR_ARG, "debug_logprob_rows: top_n %zu without its outputs", top_n);
+    const size_t K = ZG_LOGPROBS_TOP_MAX;
+    std::vector<int> h_tok(batch), h_ids(batch * K);
+    std::vector<size_t> h_tok_in(batch);
+    ZG_HIP(hipMemcpy(h_tok_in.data(), tokens, batch * sizeof(size_t), hipMemcpyDefault));
+    for (size_t b = 0; b < batch; ++b) {
+        ZG_REQUIRE(h_tok_in[b] < vocab, ZG_ERR_SHAPE, "debug_logprob_rows: token %zu >= vocab %zu", h_tok_in[b], vocab);
+        h_tok[b] = (int)h_tok_in[b];
+    }
+    const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t lbytes = up(batch * vocab * 4), wbytes = up(logprob_workspace_bytes(B, V)), pbytes = up((size_t)B * n_part * 4), bbytes = up(batch * 4),
+                 rbytes = up(batch * K * 4);
+    hipStream_t s = ctx().stream;
+    char* base = nullptr;
+    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), lbytes + wbytes + pbytes + 3 * bbytes + 2 * rbytes));
+    struct Free {
+        char* p;
+        ~Free() { (void)hipFree(p); }
+    } guard{base};
+    char* p = base;
+    float* d_logits = reinterpret_cast<float*>(p);
+    p += lbytes;
+    const LogprobWs ws = logprob_workspace(p, B, V);
+    p += wbytes;
+    float* d_part = reinterpret_cast<float*>(p);
+    p += pbytes;
+    int* d_tok = reinterpret_cast<int*>(p);
+    p += bbytes;
+    int* d_top = reinterpret_cast<int*>(p);
+    p += bbytes;
+    LogprobRec rec{};
+    rec.logprob = reinterpret_cast<float*>(p);
+    p += bbytes;
+    rec.top_ids = reinterpret_cast<int*>(p);
+    p += rbytes;
+    rec.top_logprobs = reinterpret_cast<float*>(p);
+    rec.stride = 1;
+    const int h_top_n = (int)top_n;
+    std::vector<float> h_top(batch * K);
+    ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemcpyAsync(d_tok, h_tok.data(), batch * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_top, &h_top_n, 4, hipMemcpyHostToDevice, s));
+    ZG_TRY(launch_row_max_partials(d_logits, B, V, d_part, n_part, s));
+    ZG_TRY(launch_logprob(d_logits, B, V, d_part, nullptr, n_part, n_part, d_top, ws, d_tok, nullptr, nullptr, rec, s));
+    ZG_HIP(hipMemcpyAsync(logprobs_out, rec.logprob, batch * 4, hipMemcpyDefault, s));
+    if (top_n) {
+        ZG_HIP(hipMemcpyAsync(h_ids.data(), rec.top_ids, batch * K * 4, hipMemcpyDeviceToHost, s));
+        ZG_HIP(hipMemcpyAsync(h_top.data(), rec.top_logprobs, batch * K * 4, hipMemcpyDeviceToHost, s));
+    }
+    ZG_HIP(hipStreamSynchronize(s));
+    if (top_n) {  // (outputs host or device: packed on the host, one copy each)
+        std::vector<size_t> ids(batch * top_n);
+        std::vector<float> vals(batch * top_n);
+        for (size_t b = 0; b < batch; ++b)
+            for (size_t j = 0; j < top_n; ++j) {
+                ids[b * top_n + j] = (size_t)h_ids[b * K + j];
+                vals[b * top_n + j] = h_top[b * K + j];
+            }
+        ZG_HIP(hipMemcpy(top_ids_out, ids.data(), ids.size() * sizeof(size_t), hipMemcpyDefault));
+        ZG_HIP(hipMemcpy(top_logprobs_out, vals.data(), vals.size() * 4, hipMemcpyDefault));
+    }
+    return ZG_OK;
 }
 
 int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len) {

@@ -559,6 +559,7 @@ __global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vo
 
 #include "sample_filter.h"
 #include "sample_penalty.h"
+#include "sample_logprob.h"
 
 inline int grid_for(size_t n, int block = 256, int cap = 2048) {
     size_t g = (n + block - 1) / block;
@@ -831,6 +832,35 @@ int launch_penalize(float* logits, int batch, int vocab, const PenParams* params
     hipLaunchKernelGGL(penalty_apply_kernel, dim3(batch), dim3(256), lds, s, logits, vocab, params, h, slots, counts_out);
     ZG_HIP(hipGetLastError());
     hipLaunchKernelGGL(row_argmax_partials_kernel, dim3(n_part, batch), dim3(256), 0, s, logits, vocab, part_val, part_idx);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+static inline int logprob_chunks(int vocab) { return (vocab + kLpChunk - 1) / kLpChunk; }
+
+size_t logprob_workspace_bytes(int batch, int vocab) { return (size_t)batch * logprob_chunks(vocab) * (1 + 2 * kLpTopMax) * 4; }
+
+LogprobWs logprob_workspace(void* base, int batch, int vocab) {
+    const size_t slots = (size_t)batch * logprob_chunks(vocab);
+    LogprobWs w;
+    w.sum = static_cast<float*>(base);
+    w.val = w.sum + slots;
+    w.idx = reinterpret_cast<int*>(w.val + slots * kLpTopMax);
+    return w;
+}
+
+int launch_logprob(const float* logits, int batch, int vocab, const float* part_val, const int* part_idx, int n_part, int part_stride, const int* top_n,
+                   const LogprobWs& ws, const int* tokens, const StepCtrl* ctrl, const int* prompt_len, const LogprobRec& rec, hipStream_t s) {
+    ZG_REQUIRE(vocab >= 1 && vocab <= kLpChunk * kLpMaxChunks, ZG_ERR_UNSUPPORTED, "log-probabilities: vocabulary of %d beyond %d", vocab,
+               kLpChunk * kLpMaxChunks);
+    ZG_REQUIRE(logits && part_val && (tokens || part_idx) && n_part >= 1 && top_n && ws.sum && rec.logprob && rec.top_ids && rec.top_logprobs &&
+                   rec.stride >= 1 && batch >= 1,
+               ZG_ERR_ARG, "log-probabilities: missing argument");
+    const int nc = logprob_chunks(vocab);
+    hipLaunchKernelGGL(logprob_part_kernel, dim3(nc, batch), dim3(256), 0, s, logits, vocab, part_val, n_part, part_stride, top_n, ws, nc);
+    ZG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(logprob_finish_kernel, dim3(batch), dim3(256), 0, s, logits, vocab, part_val, part_idx, n_part, part_stride, top_n, ws, nc, tokens,
+                       ctrl, prompt_len, rec);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

@@ -444,6 +444,27 @@ constexpr int kPenMaxHistory = 8192;  // 16384 slots x (key, count) = 128 KB of 
 int launch_penalize(float* logits, int batch, int vocab, const PenParams* params, const PenHistory& h, float* part_val, int* part_idx, int n_part,
                     unsigned* counts_out, hipStream_t s);
 
+// The log-probability stage behind the sampler (sample_logprob.h; include/zgpt2.h zg_gpt_generate_logprobs_enqueue): for every row,
+// the log-probability of the token the step records and the *top_n (device memory, 0 .. 20) largest logits with theirs, written
+// into column ctrl->seq_len - 1 of the record buffers (ctrl null: column 0) — NaN where that column is below prompt_len[b] (null:
+// never).  tokens (device, [batch]): the sampler's draw; null: the lowest-index argmax of part_val / part_idx (greedy).  Two
+// launches; part_val as for the samplers.  vocab <= 262144.
+struct LogprobWs {
+    float* sum;  // [batch][chunks] sum of exp(x - max) by chunk
+    float* val;  // [batch][chunks][20] the chunk's largest values, in order
+    int* idx;    // ... and their indices
+};
+struct LogprobRec {
+    float* logprob;       // [batch][stride]
+    int* top_ids;         // [batch][stride][20]
+    float* top_logprobs;  // [batch][stride][20]
+    int stride;           // columns of a row (the context)
+};
+size_t logprob_workspace_bytes(int batch, int vocab);
+LogprobWs logprob_workspace(void* base, int batch, int vocab);
+int launch_logprob(const float* logits, int batch, int vocab, const float* part_val, const int* part_idx, int n_part, int part_stride, const int* top_n,
+                   const LogprobWs& ws, const int* tokens, const StepCtrl* ctrl, const int* prompt_len, const LogprobRec& rec, hipStream_t s);
+
 // ------------------------------------------------------------------------------------ multi-GPU (dist.hip)
 int dist_broadcast(void* buf, size_t bytes, int root, hipStream_t s);  // in place, over the communicator of zg_dist_init
 

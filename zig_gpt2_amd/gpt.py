@@ -31,13 +31,14 @@ def _pack_prompts(prompts, rows):
 class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
-                 sampled_generate=False, weights_b24=False, truncated_generate=False, penalized_generate=False):
+                 sampled_generate=False, weights_b24=False, truncated_generate=False, penalized_generate=False, logprobs_generate=False):
         """share_weights_with / own_stream / stream_priority: zg_gpt_options of zg_gpt_create_ex (a handle of an independent
         prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config).
         weights_b24: matrices stored as 24-bit floats (ZG_GPT_WEIGHTS_B24: each fp32 weight rounded to 16 mantissa bits, 3/4 of
         fp32's bytes); excludes weights_f32.  truncated_generate: the graphs of generate_sample(top_k=..., top_p=...) are captured
         at create (ZG_GPT_TRUNCATED_GENERATE) instead of when the first such generation begins; penalized_generate: the same for
-        the graphs of generations with repetition / presence / frequency penalties (ZG_GPT_PENALIZED_GENERATE)."""
+        the graphs of generations with repetition / presence / frequency penalties (ZG_GPT_PENALIZED_GENERATE);
+        logprobs_generate: the same for the log-probability twins of every graph create captures (ZG_GPT_LOGPROBS_GENERATE)."""
         self.config, self.batch = config, batch
         L = _lib.load()
         flags = (_lib.GPT_WEIGHTS_F32 if weights_f32 else 0) | (0 if use_graph else _lib.GPT_NO_GRAPH)
@@ -50,6 +51,7 @@ class GPT:
         flags |= _lib.GPT_WEIGHTS_B24 if weights_b24 else 0
         flags |= _lib.GPT_TRUNCATED_GENERATE if truncated_generate else 0
         flags |= _lib.GPT_PENALIZED_GENERATE if penalized_generate else 0
+        flags |= _lib.GPT_LOGPROBS_GENERATE if logprobs_generate else 0
         cfg = _lib.GptConfig(config.vocab_size, config.context_size, config.n_layer, config.n_heads, config.n_embed)
         h = C.c_void_p()
         if share_weights_with is None and not own_stream:
@@ -199,6 +201,27 @@ class GPT:
                                                   plens, seed))
         del keep
 
+    def _generate_logprobs(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, top_n):
+        """zg_gpt_generate_logprobs_enqueue: the generation of the same arguments with the log-probability stage (temp None: greedy)."""
+        if pen is not None and temp is None:
+            raise ValueError("penalties need a sampler: greedy picking with penalties is temp=1.0, top_k=1")
+        mat, lens, stride = self._prompts(prompts)
+        opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
+        pp, pstride, plens, keep = self._token_lists(prior if pen is not None else None)
+        check(self._L.zg_gpt_generate_logprobs_enqueue(self.h, past_len, ptr(mat), stride, ptr(lens), n_steps, None if opt is None else C.addressof(opt),
+                                                       None if pen is None else C.addressof(pen), pp, pstride, plens, seed, int(top_n)))
+        del keep
+
+    def generate_fetch_logprobs(self, first, n, top_n):
+        """zg_gpt_generate_fetch_logprobs of columns first .. first + n - 1: (logprobs [batch, n] float32 — NaN where the column
+        records a prompt token —, top_ids [batch, n, top_n] uint64, top_logprobs [batch, n, top_n] float32)."""
+        lp = np.zeros((self.batch, n), np.float32)
+        ids = np.zeros((self.batch, n, top_n), np.uint64)
+        top = np.zeros((self.batch, n, top_n), np.float32)
+        check(self._L.zg_gpt_generate_fetch_logprobs(self.h, first, n, top_n, ptr(lp), lp.size, ptr(ids) if top_n else None,
+                                                     ptr(top) if top_n else None, ids.size))
+        return lp, ids, top
+
     def sample(self, seq_len, tokens, temp, uniforms=None, seed=0, want_probs=False, top_k=0, top_p=1.0, repetition_penalty=1.0,
                presence_penalty=0.0, frequency_penalty=0.0, history=None):
         """GPT.sample (src/main.zig:198-207) with reproducible uniforms; returns tokens [batch] (and probs).  top_k / top_p:
@@ -234,8 +257,13 @@ class GPT:
     def _prompts(self, prompts):
         return _pack_prompts(prompts, self.batch)
 
-    def generate(self, prompts, n_steps):
-        """generate (src/main.zig:322-342), greedy; returns tokens [batch, n_steps]."""
+    def generate(self, prompts, n_steps, logprobs=None):
+        """generate (src/main.zig:322-342), greedy; returns tokens [batch, n_steps].  logprobs=top_n (an int, 0 .. 20): the same
+        tokens with the log-probability of every pick and its top_n alternatives — returns (tokens, logprobs,
+        top_ids, top_logprobs) as generate_fetch_logprobs gives them."""
+        if logprobs is not None:
+            self._generate_logprobs(0, prompts, n_steps, None, 0, 0, 1.0, None, None, logprobs)
+            return (self.generate_fetch(n_steps),) + self.generate_fetch_logprobs(0, n_steps, logprobs)
         mat, lens, stride = self._prompts(prompts)
         out = np.zeros((self.batch, n_steps), np.uint64)
         check(self._L.zg_gpt_generate_greedy(self.h, ptr(mat), stride, ptr(lens), n_steps, ptr(out), out.size))
@@ -257,12 +285,16 @@ class GPT:
         return out
 
     def generate_from(self, past_len, prompts, n_steps, temp=None, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
-                      frequency_penalty=0.0, prior=None):
+                      frequency_penalty=0.0, prior=None, logprobs=None):
         """generate entered at position past_len (zg_gpt_generate_from_enqueue): `prompts` are the new tokens of each row, fed
         behind the past_len cached positions; returns the tokens of positions past_len .. past_len + n_steps - 1 ([batch, n_steps]).
         temp=None: greedy; otherwise the sampler of generate_sample (top_k / top_p as there).  Penalties as generate_sample; the
-        tokens below past_len count only when passed as `prior` (one list per row)."""
+        tokens below past_len count only when passed as `prior` (one list per row).  logprobs=top_n: as `generate`, for the
+        columns past_len .. past_len + n_steps - 1."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if logprobs is not None:
+            self._generate_logprobs(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
+            return (self.generate_fetch_range(past_len, n_steps),) + self.generate_fetch_logprobs(past_len, n_steps, logprobs)
         if pen is not None:
             if temp is None:
                 raise ValueError("penalties need a sampler: greedy picking with penalties is temp=1.0, top_k=1")
@@ -275,12 +307,16 @@ class GPT:
         return self.generate_fetch_range(past_len, n_steps)
 
     def generate_sample(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
-                        frequency_penalty=0.0, prior=None):
+                        frequency_penalty=0.0, prior=None, logprobs=None):
         """generate (src/main.zig:322-342) as the reference runs it — every token behind the prompt drawn by GPT.sample — with the
         loop on the device; the tokens of the host loop over `sample(T, tok, temp, seed=seed)`.  top_k / top_p: as `sample`.
         repetition_penalty / presence_penalty / frequency_penalty: on the tokens the row holds when a pick is drawn — `prior` (one
-        list per row, optional) followed by the row's prompt and picks so far (zg_gpt_generate_pen_enqueue; defaults: today's call)."""
+        list per row, optional) followed by the row's prompt and picks so far (zg_gpt_generate_pen_enqueue; defaults: today's call).
+        logprobs=top_n: as `generate` — of the row the sampler received, at temperature 1 and before truncation."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if logprobs is not None:
+            self._generate_logprobs(0, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
+            return (self.generate_fetch(n_steps),) + self.generate_fetch_logprobs(0, n_steps, logprobs)
         if pen is not None:
             self._generate_pen(0, prompts, n_steps, temp, seed, top_k, top_p, pen, prior)
             return self.generate_fetch(n_steps)
@@ -290,8 +326,11 @@ class GPT:
         return out
 
     def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
-                                frequency_penalty=0.0, prior=None):
+                                frequency_penalty=0.0, prior=None, logprobs=None):
+        """logprobs=top_n: with the log-probability stage; results through generate_fetch and generate_fetch_logprobs."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if logprobs is not None:
+            return self._generate_logprobs(0, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
         if pen is not None:
             return self._generate_pen(0, prompts, n_steps, temp, seed, top_k, top_p, pen, prior)
         mat, lens, stride = self._prompts(prompts)
