@@ -266,6 +266,12 @@ enum {
                                       log-probability twins of every graph with lm_head that create captures (the greedy ones, and
                                       those of the ZG_GPT_SAMPLED_ / _TRUNCATED_ / _PENALIZED_GENERATE flags given beside it);
                                       otherwise such a generation captures those of the buckets it touches when it begins */
+    ZG_GPT_SCORE = 1 << 12,      /* carve what zg_gpt_score needs behind everything else in the scratch region: the logits of one block
+                                    of 256 rows on the GEMMs' 64-column grid, the chunk workspace of that block, and the lm_head
+                                    operand beside the weight region (bf16 weights: the last vocab % 64 rows of wte as a [64][n_embed]
+                                    strip; fp32 / B24 weights: wte's bf16 planes and the slab workspace of that launch).  54 MB at
+                                    GPT-2 124M whatever the batch.  Without it zg_gpt_score is ZG_ERR_UNSUPPORTED and
+                                    the handle has bit for bit the layout and behaviour it has without this flag's existence */
     ZG_GPT_WEIGHTS_B24 = 1 << 8  /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
                                     value rounded to nearest even at 16 mantissa bits (never to inf), row r of an [out][in]
                                     matrix = [in bf16-shaped upper halves | in low bytes].  3/4 of fp32's weight bytes, 2^-17
@@ -543,6 +549,32 @@ int zg_gpt_generate_fetch_logprobs(zg_gpt* g, size_t first, size_t n, size_t top
  * consecutive elements of a row.  top_n > 20 or > vocab: ZG_ERR_ARG; a token >= vocab: ZG_ERR_SHAPE.  Needs zg_init only. */
 int zg_debug_logprob_rows(const float* logits, size_t batch, size_t vocab, const size_t* tokens, size_t top_n, float* logprobs_out,
                           size_t* top_ids_out_or_null, float* top_logprobs_out_or_null);
+/* ---- Scoring a given text: the pass of zg_gpt_extend(g, past_len, tokens, token_stride, n_tokens, compute_logits = 1,
+ * NULL, 0) — the same checks, rollback rule, launches, cache effect and refusal on ZG_GPT_NO_PREFILL; zg_gpt_argmax and a generation
+ * continued behind it behave as behind zg_gpt_extend, bit for bit — which also records, for every position it feeds, how likely
+ * the token there was.  Row b of the pass at position p (past_len <= p < past_len + n_tokens - 1) holds the logits x that predict
+ * position p + 1; with tok = tokens[b][p + 1 - past_len], column p + 1 of row b of the log-probability record receives
+ *   logprob = (x[tok] - m) - log S  and  top_ids / top_logprobs of that x,
+ * m, S, the order of the ids and the bit-for-bit equality where an id is tok exactly as defined above for the device loop.  Column
+ * past_len reads NaN: its predicting row is not part of the pass — to score a continuation behind a cached context, or the second
+ * chunk of a long text, roll back by one: past_len = len - 1 and the last cached token first.  Columns below past_len keep what
+ * earlier calls recorded.  The call counts as a log-probability generation with this top_n: the results leave through
+ * zg_gpt_generate_fetch_logprobs, and zg_gpt_generate_logprobs_enqueue(past_len = the end, ...) behind it continues the same record.
+ * top_n in 0 .. ZG_LOGPROBS_TOP_MAX and <= vocab_size, else ZG_ERR_ARG.  logits_out (host or device, [batch][n_tokens][vocab];
+ * logits_len below that: ZG_ERR_SHAPE; may be NULL) receives the logits of every position as the pass computed them — the lm_head
+ * of all rows on the matrix cores, 256 rows at a time; the logits of all positions are never held at once.  Needs a handle created
+ * with ZG_GPT_SCORE (else ZG_ERR_UNSUPPORTED).  Every refusal happens before anything is enqueued or the handle's state
+ * (zg_gpt_cached_len, the record) is touched.  Synchronous; allocates nothing.  fp32 sums in a fixed order without atomics: the same
+ * inputs give the same bits on every run, within 1e-5 + 2.5e-7 |logprob| of the float64 value of the pass's own logits. */
+int zg_gpt_score(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_stride, size_t n_tokens, size_t top_n, float* logits_out_or_null,
+                 size_t logits_len);
+/* Test entry: the two statistics kernels of zg_gpt_score alone on the caller's rows, logits [rows <= 4096][row_stride >= vocab] (host
+ * or device, as targets [rows] and the outputs [rows] / [rows, top_n]); only columns < vocab of a row are read.  A workgroup of the
+ * first kernel owns 1024 consecutive columns of a row and the row maximum comes from the chunks.  The error codes of
+ * zg_debug_logprob_rows: top_n > 20 or > vocab, or a bad argument: ZG_ERR_ARG; a target >= vocab: ZG_ERR_SHAPE.  Needs zg_init only.
+ * Allocates its workspace per call. */
+int zg_debug_score_rows(const float* logits, size_t rows, size_t vocab, size_t row_stride, const size_t* targets, size_t top_n, float* logprobs_out,
+                        size_t* top_ids_out_or_null, float* top_logprobs_out_or_null);
 /* tokens of positions first .. first + n - 1 of the last generation(s): out_tokens [batch, n] */
 int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len);
 /* Test entry: the sampler kernels of zg_gpt_sample_ex on the caller's logits [batch <= 64, vocab <= 262144] (host or device, as

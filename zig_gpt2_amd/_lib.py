@@ -130,6 +130,8 @@ SIGNATURES = {
     "zg_gpt_generate_logprobs_enqueue": (C.c_int, [vp, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp, C.c_uint64, sz]),
     "zg_gpt_generate_fetch_logprobs": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, vp, sz]),
     "zg_debug_logprob_rows": (C.c_int, [vp, sz, sz, vp, sz, vp, vp, vp]),
+    "zg_gpt_score": (C.c_int, [vp, sz, vp, sz, sz, sz, vp, sz]),
+    "zg_debug_score_rows": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, vp, vp]),
     "zg_gpt_time_kernel": (C.c_int, [vp, C.c_int, C.c_int, f32p, szp]),
     "zg_gpt_profile_step": (C.c_int, [vp, sz, C.c_int, f32p, sz]),
     "zg_debug_prefetch_stats": (C.c_int, [vp, vp, sz]),
@@ -147,6 +149,7 @@ GPT_WEIGHTS_B24 = 256
 GPT_TRUNCATED_GENERATE = 512
 GPT_PENALIZED_GENERATE = 1024
 GPT_LOGPROBS_GENERATE = 2048
+GPT_SCORE = 4096
 LOGPROBS_TOP_MAX = 20
 BLOCK_SLOTS = ["ln_1_g", "ln_1_b", "c_attn_w", "c_attn_b", "c_proj_w", "c_proj_b",
                "ln_2_g", "ln_2_b", "c_fc_w", "c_fc_b", "mlp_proj_w", "mlp_proj_b"]

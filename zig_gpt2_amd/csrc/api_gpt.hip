@@ -125,6 +125,17 @@ struct zg_gpt {
     bool gen_lp;              // the generation in flight records them
     bool lp_valid;            // the last generation did: the record can be fetched
     size_t lp_top_n;          // ... with this many alternatives
+    // scoring (zg_gpt_score; sample_score.h), carved under ZG_GPT_SCORE only: the logits of one block of kScoreRows rows
+    // [kScoreRows][sc_v64] (sc_v64 = the vocabulary on the GEMMs' 64-column grid), the chunk workspace of that block, and the lm_head
+    // operand the whole-prompt GEMM cannot take from the weight region: bf16 weights — the last vocab % 64 rows of wte as a [64][E]
+    // strip, zero rows behind them; fp32 / B24 weights — wte's planes [3][sc_v64][E], zero rows behind the vocabulary, and the
+    // slab workspace of that launch.  sc_gen: w_gen + 1 of the weights the strip / planes were made from (0: never made)
+    float* sc_logits;
+    ScoreWs sc_ws;
+    bf16_t *sc_tail, *sc_planes;
+    float* sc_gemm_ws;
+    size_t sc_gemm_ws_floats, sc_v64, sc_gen;
+    size_t w_gen;             // (the owner of a weight region) bumped whenever its wte may have changed
     size_t graph_steps;
     hipStream_t graph_stream;
     size_t steps_enqueued;
@@ -154,6 +165,13 @@ struct zg_gpt {
     // were last cleared — a continuation clears [its end, context) only when something may be there
     size_t cached_len, kv_dirty_hi;
 };
+
+// rows of pf_x per lm_head block of zg_gpt_score: one constant, decided by one measurement (profiles/NOTEBOOK.md §16: 256 rows take
+// the 128 x 256 tiles and half the launches; -DZG_SCORE_ROWS=128 builds the other candidate)
+#ifndef ZG_SCORE_ROWS
+#define ZG_SCORE_ROWS 256
+#endif
+constexpr size_t kScoreRows = ZG_SCORE_ROWS;
 
 static inline hipStream_t gs(const zg_gpt* g) { return g->stream ? g->stream : ctx().stream; }
 static inline zg_gpt* root(zg_gpt* g) { return g->parent ? g->parent : g; }
@@ -291,6 +309,24 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
     g->lp_rec.top_ids = (int*)P(B * C * ZG_LOGPROBS_TOP_MAX * 4);
     g->lp_rec.top_logprobs = (float*)P(B * C * ZG_LOGPROBS_TOP_MAX * 4);
     g->lp_rec.stride = (int)C;
+    // (and behind those: handles that never ask for scoring keep the layout they had)
+    g->sc_logits = nullptr;
+    g->sc_ws = ScoreWs{};
+    g->sc_tail = g->sc_planes = nullptr;
+    g->sc_gemm_ws = nullptr;
+    g->sc_gemm_ws_floats = 0;
+    g->sc_v64 = (V + 63) / 64 * 64;
+    if ((g->flags & ZG_GPT_SCORE) && !(g->flags & ZG_GPT_NO_PREFILL)) {
+        g->sc_logits = (float*)P(kScoreRows * g->sc_v64 * 4);
+        g->sc_ws = score_workspace(P(score_workspace_bytes((int)kScoreRows, (int)V)), (int)kScoreRows, (int)V);
+        if (g->wt == WT_BF16) {
+            if (V % 64) g->sc_tail = (bf16_t*)P(64 * E * 2);
+        } else {  // the three-pass GEMM sums its slabs [3][rows][sc_v64] through a workspace: more than pf_ws holds at a real vocabulary
+            g->sc_planes = (bf16_t*)P(kSplit * g->sc_v64 * E * 2);
+            g->sc_gemm_ws_floats = 3 * kScoreRows * g->sc_v64;
+            g->sc_gemm_ws = (float*)P(g->sc_gemm_ws_floats * 4);
+        }
+    }
     g->state_bytes = (cv.off + 255) & ~(size_t)255;
 }
 
@@ -419,6 +455,20 @@ int ensure_ln_folded(zg_gpt* g, hipStream_t s) {
     // handles that share the region run on other streams: the vectors must be complete before any of them reads the flag
     if (r->n_children > 0 || g->parent) ZG_HIP(hipStreamSynchronize(s));
     r->ln_folded = true;
+    return ZG_OK;
+}
+
+// (Re)derive what the scoring lm_head reads beside the weight region (the tail strip, or wte's planes) from the wte in the arena:
+// after ZG_WTE was loaded, and on handles whose region was filled some other way (a borrowed region, a broadcast).
+int ensure_score_weights(zg_gpt* g, hipStream_t s) {
+    if (!g->sc_logits || g->sc_gen == root(g)->w_gen + 1) return ZG_OK;
+    const size_t E = g->cfg.n_embed, V = g->cfg.vocab_size, head = V / 64 * 64;
+    if (g->wt != WT_BF16) ZG_TRY(launch_wte_planes(g->wte, g->wt, V, g->sc_v64, (int)E, g->sc_planes, s));
+    else if (g->sc_tail) {
+        ZG_HIP(hipMemsetAsync(g->sc_tail, 0, 64 * E * 2, s));
+        ZG_HIP(hipMemcpyAsync(g->sc_tail, reinterpret_cast<const bf16_t*>(g->wte) + head * E, (V - head) * E * 2, hipMemcpyDeviceToDevice, s));
+    }
+    g->sc_gen = root(g)->w_gen + 1;
     return ZG_OK;
 }
 
@@ -1384,7 +1434,13 @@ int zg_gpt_load_tensor(zg_gpt* g, int slot, const float* src, size_t len) {
         case ZG_LN_F_G: t = {g->ln_f_g, E, 0, nullptr}; break;
         case ZG_LN_F_B: t = {g->ln_f_b, E, 0, nullptr}; break;
     }
-    return load_slot(g, t, "slot", slot, src, len);
+    ZG_TRY(load_slot(g, t, "slot", slot, src, len));
+    if (slot == ZG_WTE) {  // the scoring lm_head's strip / planes of the new wte: here for this handle, at their next score for its borrowers
+        ++g->w_gen;
+        ZG_TRY(ensure_score_weights(g, gs(g)));
+        ZG_HIP(hipStreamSynchronize(gs(g)));
+    }
+    return ZG_OK;
 }
 
 int zg_gpt_weight_arena(zg_gpt* g, void** device_ptr, size_t* bytes) {
@@ -1399,6 +1455,7 @@ int zg_gpt_weight_arena(zg_gpt* g, void** device_ptr, size_t* bytes) {
         ZG_HIP(hipStreamSynchronize(gs(g)));
     }
     root(g)->ln_folded = false;
+    ++root(g)->w_gen;  // (zg_gpt_score re-derives its strip / planes likewise)
     *device_ptr = g->wbase;
     *bytes = g->weight_region_bytes;
     return ZG_OK;
@@ -1572,16 +1629,61 @@ int zg_debug_gpt_step_taps(zg_gpt* g, size_t seq_len, const size_t* tokens, size
 // The whole-prompt pass: n tokens of every sequence go to positions past_len .. past_len + n - 1 behind the cached
 // ones — the prompt loop of generate (main.zig:331-334) at an offset — and, on request, ln_f + lm_head of each sequence's last new
 // position run through the decode kernels.  Everything is checked before the handle or its staging is touched.
+// sc (zg_gpt_score): behind the pass, the scoring stage over all of its rows.
+struct ScoreCall {
+    size_t top_n;
+    float* logits_out;  // [batch][n][vocab], host or device, or null
+    size_t logits_len;
+};
+
+// The scoring stage of a pass of n new positions per sequence behind `past` cached ones, whose residual stream of every row is
+// in pf_x: ln_f of all rows once (pf_a is free: the pass is over), then block by block of kScoreRows rows the lm_head on the
+// matrix cores into sc_logits, the two statistics launches, and on request the block's logits to the caller.
+static int enqueue_score(zg_gpt* g, size_t past, size_t n, float* logits_out, hipStream_t s) {
+    const size_t E = g->cfg.n_embed, V = g->cfg.vocab_size, C = g->cfg.context_size, V64 = g->sc_v64, head = V / 64 * 64, M = g->batch * n;
+    const int iE = (int)E, ld = (int)V64;
+    const int np = (g->flags & ZG_GPT_PREFILL_2PLANE) ? 2 : kSplit;
+    ZG_TRY(ensure_score_weights(g, s));
+    ZG_TRY(launch_ln_split(g->pf_x, (int)M, iE, g->ln_f_g, g->ln_f_b, 1e-5f, g->pf_a, s));
+    for (size_t r0 = 0; r0 < M; r0 += kScoreRows) {
+        const int rows = (int)std::min(kScoreRows, M - r0);
+        const bf16_t* A = g->pf_a + r0 * kSplit * E;
+        if (g->wt != WT_BF16) {  // the planes hold zero rows up to V64: one launch
+            ZG_TRY(launch_prefill_gemm(A, g->sc_planes, nullptr, g->sc_logits, rows, ld, iE, ld, PF_F32, g->sc_gemm_ws, g->sc_gemm_ws_floats, nullptr, s, nullptr,
+                                       kWeightPlanes));
+        } else {  // the whole 64-row groups of wte where they lie, then the strip: no row behind V - 1 of wte is read
+            if (head)
+                ZG_TRY(launch_prefill_gemm(A, reinterpret_cast<const bf16_t*>(g->wte), nullptr, g->sc_logits, rows, (int)head, iE, ld, PF_F32, g->pf_ws,
+                                           g->pf_ws_floats, nullptr, s, nullptr, np));
+            if (g->sc_tail)
+                ZG_TRY(launch_prefill_gemm(A, g->sc_tail, nullptr, g->sc_logits + head, rows, 64, iE, ld, PF_F32, g->pf_ws, g->pf_ws_floats, nullptr, s, nullptr, np));
+        }
+        const ScoreTargets tg{g->prompt, (int)C, (int)n, (int)past, (int)r0};
+        ZG_TRY(launch_score(g->sc_logits, rows, (int)V, ld, g->lp_top, g->sc_ws, tg, g->lp_rec, s));
+        if (logits_out)
+            ZG_HIP(hipMemcpy2DAsync(logits_out + r0 * V, V * 4, g->sc_logits, V64 * 4, V * 4, (size_t)rows,
+                                    is_device_ptr(logits_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    }
+    return ZG_OK;
+}
+
 static int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t stride, size_t n, int compute_logits, float* logits_out, size_t logits_len,
-                     const char* who) {
+                     const char* who, const ScoreCall* sc = nullptr) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && tokens, ZG_ERR_ARG, "%s: null argument", who);
     ZG_REQUIRE(g->pf_x != nullptr, ZG_ERR_UNSUPPORTED, "%s: the handle was created with ZG_GPT_NO_PREFILL", who);
     const size_t C = g->cfg.context_size, V = g->cfg.vocab_size, B = g->batch, E = g->cfg.n_embed;
+    if (sc) {
+        ZG_REQUIRE(g->sc_logits != nullptr, ZG_ERR_UNSUPPORTED, "%s: the handle was created without ZG_GPT_SCORE", who);
+        ZG_REQUIRE(sc->top_n <= (size_t)ZG_LOGPROBS_TOP_MAX && sc->top_n <= V, ZG_ERR_ARG, "%s: top_n %zu outside 0..%zu", who, sc->top_n,
+                   std::min((size_t)ZG_LOGPROBS_TOP_MAX, V));
+        ZG_REQUIRE(V <= (size_t)64 * 4096, ZG_ERR_UNSUPPORTED, "%s: vocabulary of %zu beyond %d", who, V, 64 * 4096);
+    }
     ZG_REQUIRE(past_len <= g->cached_len, ZG_ERR_ARG, "%s: past_len %zu beyond the %zu cached positions", who, past_len, g->cached_len);
     ZG_REQUIRE(n >= 1 && past_len + n <= C && n <= stride, ZG_ERR_SHAPE, "%s: %zu tokens behind %zu positions (context %zu, stride %zu)", who, n, past_len, C,
                stride);
     ZG_REQUIRE(!logits_out || (compute_logits && logits_len >= B * V), ZG_ERR_SHAPE, "%s: logits_out needs compute_logits and %zu elements", who, B * V);
+    ZG_REQUIRE(!sc || !sc->logits_out || sc->logits_len >= B * n * V, ZG_ERR_SHAPE, "%s: logits_out needs %zu elements", who, B * n * V);
     for (size_t b = 0; b < B; ++b)
         for (size_t i = 0; i < n; ++i) ZG_REQUIRE(tokens[b * stride + i] < V, ZG_ERR_SHAPE, "%s: token %zu >= vocab %zu", who, tokens[b * stride + i], V);
     hipStream_t s = gs(g);
@@ -1600,8 +1702,23 @@ static int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t st
         ZG_TRY(enqueue_lm_head(g, s));
         if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, B * V, s));
     }
+    if (sc) {  // a log-probability generation with this top_n: the record continues behind it (generate_from) and leaves through the same fetch
+        g->gen_lp = false;
+        g->lp_valid = true;
+        g->lp_top_n = sc->top_n;
+        *g->h_lp_top = (int)sc->top_n;
+        ZG_HIP(hipMemcpyAsync(g->lp_top, g->h_lp_top, sizeof(int), hipMemcpyHostToDevice, s));
+        // column past_len: its predicting row is not part of the pass (NaN: every byte 0xff)
+        ZG_HIP(hipMemset2DAsync(g->lp_rec.logprob + past_len, C * sizeof(float), 0xff, sizeof(float), B, s));
+        ZG_TRY(enqueue_score(g, past_len, n, sc->logits_out, s));
+    }
     ZG_HIP(hipStreamSynchronize(s));
     return check_fault(g);
+}
+
+int zg_gpt_score(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_stride, size_t n_tokens, size_t top_n, float* logits_out, size_t logits_len) {
+    const ScoreCall sc{top_n, logits_out, logits_len};
+    return pass_impl(g, past_len, tokens, token_stride, n_tokens, 1, nullptr, 0, "gpt_score", &sc);
 }
 
 int zg_gpt_prefill(zg_gpt* g, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits, float* logits_out, size_t logits_len) {
@@ -2210,6 +2327,78 @@ int zg_debug_logprob_rows(const float* logits, size_t batch, size_t vocab, const
             for (size_t j = 0; j < top_n; ++j) {
                 ids[b * top_n + j] = (size_t)h_ids[b * K + j];
                 vals[b * top_n + j] = h_top[b * K + j];
+            }
+        ZG_HIP(hipMemcpy(top_ids_out, ids.data(), ids.size() * sizeof(size_t), hipMemcpyDefault));
+        ZG_HIP(hipMemcpy(top_logprobs_out, vals.data(), vals.size() * 4, hipMemcpyDefault));
+    }
+    return ZG_OK;
+}
+
+// The scoring kernels on the caller's rows (tests): the two launches of zg_gpt_score's statistics stage, the rows standing for one
+// sequence of rows + 1 positions whose position r + 1 holds targets[r].  Allocates its workspace per call.
+int zg_debug_score_rows(const float* logits, size_t rows, size_t vocab, size_t row_stride, const size_t* targets, size_t top_n, float* logprobs_out,
+                        size_t* top_ids_out, float* top_logprobs_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(logits && targets && logprobs_out && rows >= 1 && rows <= 4096 && vocab >= 1 && vocab <= (size_t)64 * 4096 && row_stride >= vocab &&
+                   row_stride <= (size_t)1 << 20,
+               ZG_ERR_ARG, "debug_score_rows: bad argument");
+    ZG_REQUIRE(top_n <= (size_t)ZG_LOGPROBS_TOP_MAX && top_n <= vocab, ZG_ERR_ARG, "debug_score_rows: top_n %zu outside 0..%zu", top_n,
+               std::min((size_t)ZG_LOGPROBS_TOP_MAX, vocab));
+    ZG_REQUIRE(top_n == 0 || (top_ids_out && top_logprobs_out), ZG_ERR_ARG, "debug_score_rows: top_n %zu without its outputs", top_n);
+    const size_t K = ZG_LOGPROBS_TOP_MAX, cols = rows + 1;
+    std::vector<int> h_tok(cols, 0), h_ids(cols * K);
+    std::vector<size_t> h_tok_in(rows);
+    ZG_HIP(hipMemcpy(h_tok_in.data(), targets, rows * sizeof(size_t), hipMemcpyDefault));
+    for (size_t r = 0; r < rows; ++r) {
+        ZG_REQUIRE(h_tok_in[r] < vocab, ZG_ERR_SHAPE, "debug_score_rows: target %zu >= vocab %zu", h_tok_in[r], vocab);
+        h_tok[r + 1] = (int)h_tok_in[r];
+    }
+    const int R = (int)rows, V = (int)vocab;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t lbytes = up(rows * row_stride * 4), wbytes = up(score_workspace_bytes(R, V)), cbytes = up(cols * 4), rbytes = up(cols * K * 4);
+    hipStream_t s = ctx().stream;
+    char* base = nullptr;
+    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), lbytes + wbytes + 256 + 2 * cbytes + 2 * rbytes));
+    struct Free {
+        char* p;
+        ~Free() { (void)hipFree(p); }
+    } guard{base};
+    char* p = base;
+    float* d_logits = reinterpret_cast<float*>(p);
+    p += lbytes;
+    const ScoreWs ws = score_workspace(p, R, V);
+    p += wbytes;
+    int* d_top = reinterpret_cast<int*>(p);
+    p += 256;
+    int* d_tok = reinterpret_cast<int*>(p);
+    p += cbytes;
+    LogprobRec rec{};
+    rec.logprob = reinterpret_cast<float*>(p);
+    p += cbytes;
+    rec.top_ids = reinterpret_cast<int*>(p);
+    p += rbytes;
+    rec.top_logprobs = reinterpret_cast<float*>(p);
+    rec.stride = (int)cols;
+    const int h_top_n = (int)top_n;
+    std::vector<float> h_top(cols * K);
+    ZG_HIP(hipMemcpyAsync(d_logits, logits, rows * row_stride * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemcpyAsync(d_tok, h_tok.data(), cols * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_top, &h_top_n, 4, hipMemcpyHostToDevice, s));
+    const ScoreTargets tg{d_tok, (int)cols, (int)cols, 0, 0};
+    ZG_TRY(launch_score(d_logits, R, V, (int)row_stride, d_top, ws, tg, rec, s));
+    ZG_HIP(hipMemcpyAsync(logprobs_out, rec.logprob + 1, rows * 4, hipMemcpyDefault, s));
+    if (top_n) {
+        ZG_HIP(hipMemcpyAsync(h_ids.data(), rec.top_ids, cols * K * 4, hipMemcpyDeviceToHost, s));
+        ZG_HIP(hipMemcpyAsync(h_top.data(), rec.top_logprobs, cols * K * 4, hipMemcpyDeviceToHost, s));
+    }
+    ZG_HIP(hipStreamSynchronize(s));
+    if (top_n) {  // (outputs host or device: packed on the host, one copy each)
+        std::vector<size_t> ids(rows * top_n);
+        std::vector<float> vals(rows * top_n);
+        for (size_t r = 0; r < rows; ++r)
+            for (size_t j = 0; j < top_n; ++j) {
+                ids[r * top_n + j] = (size_t)h_ids[(r + 1) * K + j];
+                vals[r * top_n + j] = h_top[(r + 1) * K + j];
             }
         ZG_HIP(hipMemcpy(top_ids_out, ids.data(), ids.size() * sizeof(size_t), hipMemcpyDefault));
         ZG_HIP(hipMemcpy(top_logprobs_out, vals.data(), vals.size() * 4, hipMemcpyDefault));

@@ -560,6 +560,7 @@ __global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vo
 #include "sample_filter.h"
 #include "sample_penalty.h"
 #include "sample_logprob.h"
+#include "sample_score.h"
 
 inline int grid_for(size_t n, int block = 256, int cap = 2048) {
     size_t g = (n + block - 1) / block;
@@ -861,6 +862,39 @@ int launch_logprob(const float* logits, int batch, int vocab, const float* part_
     ZG_HIP(hipGetLastError());
     hipLaunchKernelGGL(logprob_finish_kernel, dim3(batch), dim3(256), 0, s, logits, vocab, part_val, part_idx, n_part, part_stride, top_n, ws, nc, tokens,
                        ctrl, prompt_len, rec);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+size_t score_workspace_bytes(int rows, int vocab) { return (size_t)rows * logprob_chunks(vocab) * (2 + 2 * kLpTopMax) * 4; }
+
+ScoreWs score_workspace(void* base, int rows, int vocab) {
+    const size_t slots = (size_t)rows * logprob_chunks(vocab);
+    ScoreWs w;
+    w.sum = static_cast<float*>(base);
+    w.max = w.sum + slots;
+    w.val = w.max + slots;
+    w.idx = reinterpret_cast<int*>(w.val + slots * kLpTopMax);
+    return w;
+}
+
+int launch_score(const float* logits, int rows, int vocab, int row_stride, const int* top_n, const ScoreWs& ws, const ScoreTargets& tg, const LogprobRec& rec,
+                 hipStream_t s) {
+    ZG_REQUIRE(vocab >= 1 && vocab <= kLpChunk * kLpMaxChunks, ZG_ERR_UNSUPPORTED, "score: vocabulary of %d beyond %d", vocab, kLpChunk * kLpMaxChunks);
+    ZG_REQUIRE(logits && top_n && ws.sum && tg.tokens && tg.token_stride >= 1 && tg.n >= 1 && tg.past >= 0 && tg.row0 >= 0 && rec.logprob && rec.top_ids &&
+                   rec.top_logprobs && rec.stride >= 1 && rows >= 1 && rows <= 65535 && row_stride >= vocab,
+               ZG_ERR_ARG, "score: missing argument");
+    const int nc = logprob_chunks(vocab);
+    hipLaunchKernelGGL(score_part_kernel, dim3(nc, rows), dim3(256), 0, s, logits, vocab, row_stride, top_n, ws, nc);
+    ZG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(score_finish_kernel, dim3(rows), dim3(256), 0, s, logits, vocab, row_stride, top_n, ws, nc, tg, rec);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_wte_planes(const void* wte, int weight_type, size_t V, size_t V64, int K, bf16_t* out, hipStream_t s) {
+    ZG_REQUIRE(wte && out && V >= 1 && V64 >= V && K % 8 == 0 && (weight_type == WT_F32 || weight_type == WT_B24), ZG_ERR_ARG, "wte planes: bad argument");
+    hipLaunchKernelGGL(wte_planes_kernel, dim3(grid_for(V64 * (size_t)(K / 4))), dim3(256), 0, s, wte, weight_type, V, V64, K, out);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

@@ -464,6 +464,29 @@ size_t logprob_workspace_bytes(int batch, int vocab);
 LogprobWs logprob_workspace(void* base, int batch, int vocab);
 int launch_logprob(const float* logits, int batch, int vocab, const float* part_val, const int* part_idx, int n_part, int part_stride, const int* top_n,
                    const LogprobWs& ws, const int* tokens, const StepCtrl* ctrl, const int* prompt_len, const LogprobRec& rec, hipStream_t s);
+// The scoring stage behind a whole-prompt pass (sample_score.h; include/zgpt2.h zg_gpt_score): `rows` rows of logits [rows][row_stride]
+// (only columns < vocab are read) that are rows tg.row0 .. of a pass of tg.n new positions per sequence behind tg.past cached ones.
+// Row t of sequence b predicts position tg.past + t + 1: its target is tg.tokens[b][that position] and column that position of the
+// record buffers receives the target's log-probability and the *top_n largest logits with theirs; the last row of a sequence
+// writes nothing.  Two launches; the row maximum comes from the chunks.  vocab <= 262144.
+struct ScoreWs {
+    float* sum;  // [rows][chunks] sum of exp(x - max[chunk]) by chunk
+    float* max;  // [rows][chunks] the chunk's own maximum
+    float* val;  // [rows][chunks][20] the chunk's largest values, in order
+    int* idx;    // ... and their indices
+};
+struct ScoreTargets {
+    const int* tokens;  // [batch][token_stride], indexed by absolute position
+    int token_stride;
+    int n, past, row0;
+};
+size_t score_workspace_bytes(int rows, int vocab);
+ScoreWs score_workspace(void* base, int rows, int vocab);
+int launch_score(const float* logits, int rows, int vocab, int row_stride, const int* top_n, const ScoreWs& ws, const ScoreTargets& tg, const LogprobRec& rec,
+                 hipStream_t s);
+// wte [V][K] (fp32 or B24) -> its exact bf16 planes, plane-major [3][V64][K] with zero rows behind row V - 1: the weight operand of
+// the scoring lm_head on handles whose whole-prompt GEMMs read weight planes
+int launch_wte_planes(const void* wte, int weight_type, size_t V, size_t V64, int K, bf16_t* out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------ multi-GPU (dist.hip)
 int dist_broadcast(void* buf, size_t bytes, int root, hipStream_t s);  // in place, over the communicator of zg_dist_init

@@ -31,14 +31,16 @@ def _pack_prompts(prompts, rows):
 class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
-                 sampled_generate=False, weights_b24=False, truncated_generate=False, penalized_generate=False, logprobs_generate=False):
+                 sampled_generate=False, weights_b24=False, truncated_generate=False, penalized_generate=False, logprobs_generate=False,
+                 score=False):
         """share_weights_with / own_stream / stream_priority: zg_gpt_options of zg_gpt_create_ex (a handle of an independent
         prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config).
         weights_b24: matrices stored as 24-bit floats (ZG_GPT_WEIGHTS_B24: each fp32 weight rounded to 16 mantissa bits, 3/4 of
         fp32's bytes); excludes weights_f32.  truncated_generate: the graphs of generate_sample(top_k=..., top_p=...) are captured
         at create (ZG_GPT_TRUNCATED_GENERATE) instead of when the first such generation begins; penalized_generate: the same for
         the graphs of generations with repetition / presence / frequency penalties (ZG_GPT_PENALIZED_GENERATE);
-        logprobs_generate: the same for the log-probability twins of every graph create captures (ZG_GPT_LOGPROBS_GENERATE)."""
+        logprobs_generate: the same for the log-probability twins of every graph create captures (ZG_GPT_LOGPROBS_GENERATE).
+        score: carve what `score` / `loglikelihood` need (ZG_GPT_SCORE); without it they raise ZG_ERR_UNSUPPORTED."""
         self.config, self.batch = config, batch
         L = _lib.load()
         flags = (_lib.GPT_WEIGHTS_F32 if weights_f32 else 0) | (0 if use_graph else _lib.GPT_NO_GRAPH)
@@ -52,6 +54,7 @@ class GPT:
         flags |= _lib.GPT_TRUNCATED_GENERATE if truncated_generate else 0
         flags |= _lib.GPT_PENALIZED_GENERATE if penalized_generate else 0
         flags |= _lib.GPT_LOGPROBS_GENERATE if logprobs_generate else 0
+        flags |= _lib.GPT_SCORE if score else 0
         cfg = _lib.GptConfig(config.vocab_size, config.context_size, config.n_layer, config.n_heads, config.n_embed)
         h = C.c_void_p()
         if share_weights_with is None and not own_stream:
@@ -167,6 +170,37 @@ class GPT:
         check(self._L.zg_gpt_extend(self.h, past_len, ptr(tokens), max(tokens.shape[1], 1), tokens.shape[1], int(compute_logits), ptr(logits),
                                     ops._n(logits)))
         return logits
+
+    def score(self, tokens, past_len=0, top_n=0, want_logits=False):
+        """zg_gpt_score: the pass of extend(past_len, tokens) which also records how likely every token it feeds was.
+        tokens [batch, n].  Returns (logprobs [batch, n] float32, top_ids [batch, n, top_n] uint64, top_logprobs [batch, n, top_n]
+        float32) of columns past_len .. past_len + n - 1 — column j holds log P(tokens[:, j] | everything before it) and the top_n
+        alternatives there; the first column is NaN (its predicting row is not part of the pass) — and, with want_logits, the
+        logits of every position [batch, n, V] as the pass computed them."""
+        tokens = np.ascontiguousarray(np.atleast_2d(tokens), dtype=np.uint64)
+        assert tokens.shape[0] == self.batch
+        n = tokens.shape[1]
+        logits = np.empty((self.batch, n, self.config.vocab_size), np.float32) if want_logits else None
+        check(self._L.zg_gpt_score(self.h, past_len, ptr(tokens), max(n, 1), n, int(top_n), ptr(logits), ops._n(logits)))
+        out = self.generate_fetch_logprobs(past_len, n, int(top_n))
+        return out + (logits,) if want_logits else out
+
+    def loglikelihood(self, contexts, continuations):
+        """The `loglikelihood(context, continuation)` request of evaluation harnesses for `batch` rows in ONE call of `score`:
+        contexts and continuations are lists of token lists, one pair per row (a context of at least one token).  Returns a list of
+        (sum of the continuation's log-probabilities, is_greedy) per row — is_greedy: every continuation token was the most likely
+        one.  Rows are padded at the end to the longest; causality keeps the padding from reaching a row's own columns, which are
+        the only ones read."""
+        assert len(contexts) == self.batch and len(continuations) == self.batch
+        rows = [np.r_[np.asarray(c, np.uint64), np.asarray(k, np.uint64)] for c, k in zip(contexts, continuations)]
+        assert all(len(c) >= 1 for c in contexts), "a continuation's first token needs a token in front of it"
+        mat, _, _ = _pack_prompts(rows, self.batch)
+        lp, ids, _ = self.score(mat, top_n=1)
+        out = []
+        for b, (c, k) in enumerate(zip(contexts, continuations)):
+            cols = slice(len(c), len(c) + len(k))
+            out.append((float(lp[b, cols].astype(np.float64).sum()), bool(np.array_equal(ids[b, cols, 0], mat[b, cols]))))
+        return out
 
     def _sampled(self, name, suffix, head, temp, top_k, top_p, tail):
         """zg_gpt_<name><suffix>(h, *head, temp, *tail) while no filter is on (the defaults take the plain entry point itself),
