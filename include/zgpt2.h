@@ -249,23 +249,23 @@ enum {
                                       outside the tests' near-zero floor); bf16-weight handles only */
     ZG_GPT_NO_PREFETCH = 1 << 5, /* zg_gpt_generate_*: no side-stream L2 prefetcher beside the decode chain (results are
                                     identical either way; a measurement switch) */
-    ZG_GPT_SAMPLED_GENERATE = 1 << 7, /* capture the decode graphs of zg_gpt_generate_sample_* at create as well (otherwise they are
-                                      captured by the first sampled generation: the one place a generate call may allocate) */
+    ZG_GPT_SAMPLED_GENERATE = 1 << 7, /* capture the decode graphs of zg_gpt_generate_sample_* at create as well.  The rule of all
+                                      four *_GENERATE flags: create captures the greedy graphs and those the flags name; a
+                                      generation that needs others captures them, for the 64-position buckets it touches, when it
+                                      begins — before its first step: the one place a generate call may allocate */
     ZG_GPT_KV_B24 = 1 << 6,      /* store the KV cache as 24-bit floats (the fp32 value rounded to 16 mantissa bits, kept as a
                                     bf16 plane + a plane of 8 more mantissa bits): 3/4 of the fp32 cache's traffic, 2^-17 per
                                     cached element — inside the 1e-3 parity bound at full context, unlike ZG_GPT_KV_F16 (which
                                     it excludes) */
     ZG_GPT_TRUNCATED_GENERATE = 1 << 9, /* capture the decode graphs of zg_gpt_generate_sample_ex_* (top-k / top-p truncation) at
-                                      create as well (otherwise a truncated generation captures those of the buckets it
-                                      touches when it begins, before its first step: the one place such a call may allocate) */
+                                      create as well (the rule: ZG_GPT_SAMPLED_GENERATE) */
     ZG_GPT_PENALIZED_GENERATE = 1 << 10, /* capture the decode graphs of zg_gpt_generate_pen_enqueue (logit penalties in front of the
-                                      sampler, all three sampler forms) at create as well (otherwise a penalised generation
-                                      captures those of the buckets it touches when it begins, before its first step: the one
-                                      place such a call may allocate).  context_size > 8192: ZG_ERR_UNSUPPORTED */
+                                      sampler, all three sampler forms) at create as well (the rule: ZG_GPT_SAMPLED_GENERATE).
+                                      context_size > 8192: ZG_ERR_UNSUPPORTED */
     ZG_GPT_LOGPROBS_GENERATE = 1 << 11, /* capture the decode graphs of zg_gpt_generate_logprobs_enqueue at create as well: the
                                       log-probability twins of every graph with lm_head that create captures (the greedy ones, and
-                                      those of the ZG_GPT_SAMPLED_ / _TRUNCATED_ / _PENALIZED_GENERATE flags given beside it);
-                                      otherwise such a generation captures those of the buckets it touches when it begins */
+                                      those of the ZG_GPT_SAMPLED_ / _TRUNCATED_ / _PENALIZED_GENERATE flags given beside it; the
+                                      rule: ZG_GPT_SAMPLED_GENERATE) */
     ZG_GPT_SCORE = 1 << 12,      /* carve what zg_gpt_score needs behind everything else in the scratch region: the logits of one block
                                     of 256 rows on the GEMMs' 64-column grid, the chunk workspace of that block, and the lm_head
                                     operand beside the weight region (bf16 weights: the last vocab % 64 rows of wte as a [64][n_embed]

@@ -44,14 +44,19 @@ def host_loop(m, prompts, n_steps, temp, seed):
     return out
 
 
-@pytest.mark.parametrize("name,batch,graph", [("tiny", 1, True), ("tiny3", 3, True), ("tiny", 8, True), ("nano-char", 2, False)])
-def test_device_loop_equals_host_loop_over_the_per_token_sampler(zg, name, batch, graph):
+# flagged: ZG_GPT_SAMPLED_GENERATE, the plain sampler's graphs captured at create; the unflagged batch-1 graph handle captures them
+# when its first sampled generation begins
+@pytest.mark.parametrize("name,batch,graph,flagged", [
+    pytest.param("tiny", 1, True, True, id="tiny-1-True"), pytest.param("tiny", 1, True, False, id="tiny-1-True-unflagged"),
+    pytest.param("tiny3", 3, True, False, id="tiny3-3-True"), pytest.param("tiny", 8, True, False, id="tiny-8-True"),
+    pytest.param("nano-char", 2, False, False, id="nano-char-2-False")])
+def test_device_loop_equals_host_loop_over_the_per_token_sampler(zg, name, batch, graph, flagged):
     cfg = synth.CONFIGS[name]
     w = synth.make_weights(cfg, seed=61, bf16=True)
     prompts = [synth.rand_tokens(610 + b, 1 + b % 3, cfg.vocab_size) for b in range(batch)]  # below the whole-prompt threshold: one kernel path
     n_steps = min(cfg.context_size, 70)
     for temp, seed in ((0.8, 5), (1.7, 123456789)):
-        m = zgpt.GPT(cfg, batch=batch, use_graph=graph, sampled_generate=graph and batch == 1)
+        m = zgpt.GPT(cfg, batch=batch, use_graph=graph, sampled_generate=flagged)
         m.load_weights(w)
         got = m.generate_sample(prompts, n_steps, temp, seed=seed)
         again = m.generate_sample(prompts, n_steps, temp, seed=seed)   # reproducible: same seed, same tokens

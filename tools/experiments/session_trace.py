@@ -67,9 +67,24 @@ def session(tag, cfg, w, B, long=True, prefill=True, **kw):
         r[f"fwd{T}"] = m.forward(T, toks(50 + T, B, 1, V)[:, 0])
     r["sample"] = m.sample(4, toks(60, B, 1, V)[:, 0], 0.9, seed=3)
     r["sample_ex"] = m.sample(5, toks(61, B, 1, V)[:, 0], 0.9, seed=3, top_k=40, top_p=0.9)
+    # the sampling tail: penalties with a prior, log-probabilities behind the greedy pick and behind both filters, both on a continuation
+    pen = dict(repetition_penalty=1.3, presence_penalty=0.4, frequency_penalty=0.2)
+    prior = [synth.rand_tokens(80 + b, 5, V) for b in range(B)]  # (prior + steps stay within the context: 5 steps fewer)
+    r["samp_pen"] = m.generate_sample(prompts, upto - 5, 0.9, seed=5, prior=prior, **pen)
+    r["greedy_lp5"] = m.generate(prompts, upto, logprobs=5)
+    r["samp_kp_lp5"] = m.generate_sample(prompts, upto, 0.9, seed=5, top_k=40, top_p=0.95, logprobs=5)
+    m.generate(prompts, past)
+    r["from_pen_lp20"] = m.generate_from(past, new, upto - past - 5, temp=0.8, seed=7, prior=prior, logprobs=20, **pen)
+    m.forward(1, toks(62, B, 1, V)[:, 0], compute_logits=False)
+    r["sample_pen"] = m.sample(2, toks(63, B, 1, V)[:, 0], 0.9, seed=3, history=[synth.rand_tokens(90 + b, 7, V) for b in range(B)], **pen)
+    if kw.get("score"):
+        n = (300 if B == 1 else 70) if long else min(20, Cx)  # (more than one block of lm_head rows where the model is large)
+        r["score0"] = m.score(toks(9, B, n, V), top_n=0, want_logits=True)
+        r["score20"] = m.score(toks(10, B, 12, V), past_len=n // 2, top_n=20, want_logits=True)
     m.close()
     for k, v in r.items():
-        out[f"{tag}/{k}"] = np.asarray(v)
+        for i, a in enumerate(v if isinstance(v, tuple) else (v,)):  # (tokens, logprobs, top_ids, top_logprobs[, logits]): one array each
+            out[f"{tag}/{k}" + (f"/{i}" if isinstance(v, tuple) else "")] = np.asarray(a)
     marks.append(tag)
     mark()
     print("done", tag, flush=True)
@@ -79,10 +94,10 @@ cfg = synth.CONFIGS["124M"]
 w = weights(cfg)
 mark()
 for B in (1, 4):
-    session(f"124M b{B} bf16", cfg, w, B)
+    session(f"124M b{B} bf16", cfg, w, B, score=True)
     session(f"124M b{B} bf16 kv_f16", cfg, w, B, kv_f16=True)
     session(f"124M b{B} bf16 kv_b24", cfg, w, B, kv_b24=True)
-    session(f"124M b{B} f32w", cfg, w, B, weights_f32=True)
+    session(f"124M b{B} f32w", cfg, w, B, weights_f32=True, score=B == 1)
     session(f"124M b{B} b24w kv_f16", cfg, w, B, weights_b24=True, kv_f16=True)
 session("124M b1 no_graph", cfg, w, 1, use_graph=False)
 session("124M b1 no_prefill", cfg, w, 1, prefill=False)
@@ -98,7 +113,7 @@ del w
 
 for name, B in (("tiny3", 3), ("nano-char", 1)):
     c = synth.CONFIGS[name]
-    session(f"{name} b{B}", c, weights(c), B, long=False)
+    session(f"{name} b{B}", c, weights(c), B, long=False, score=True)
 
 np.savez(sys.argv[1], **out)
 open(sys.argv[1] + ".marks", "w").write("\n".join(marks) + "\n")

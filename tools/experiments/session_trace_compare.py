@@ -1,4 +1,5 @@
-"""python tools/experiments/session_trace_compare.py DIR_PARENT DIR_NEW MARKS OUT.md — per handle and hardware queue, ordered (kernel, grid, workgroup) lists."""
+"""python tools/experiments/session_trace_compare.py DIR_PARENT DIR_NEW MARKS OUT.md [NPZ_PARENT NPZ_NEW] — per handle and hardware queue,
+ordered (kernel, grid, workgroup) lists; with the two sessions' result files, also which of their arrays differ bytewise."""
 import csv, glob, gzip, os, sqlite3, sys
 
 
@@ -83,6 +84,13 @@ def main():
         lines.append(f"| {nm} | {' + '.join(str(len(x)) for x in qa)} | {' + '.join(str(len(x)) for x in qb)} | {'identical' if same else 'DIFFERENT'} |")
     lines.append("")
     lines.append(f"{len(a)} / {len(b)} dispatches per trace (copy kernels included); {bad} handles differ")
+    if len(sys.argv) > 6:
+        import numpy as np
+
+        za, zb = np.load(sys.argv[5]), np.load(sys.argv[6])
+        diff = [k for k in sorted(set(za.files) | set(zb.files))
+                if k not in za.files or k not in zb.files or za[k].dtype != zb[k].dtype or za[k].shape != zb[k].shape or za[k].tobytes() != zb[k].tobytes()]
+        lines.append(f"{len(za.files)} / {len(zb.files)} result arrays; {len(diff)} differ bytewise" + (": " + ", ".join(diff[:20]) if diff else ""))
     open(out, "w").write("\n".join(lines) + "\n")
     print("\n".join(lines))
 

@@ -5,7 +5,12 @@
 // position, tokens and argmax all live in device memory, so a whole greedy generation is enqueued
 // without a host round trip per token.  Three things exist once each: the whole-prompt pass (pass_impl: zg_gpt_prefill is
 // zg_gpt_extend at 0), the generation request (GenRequest, run by gen_run for every zg_gpt_generate*_enqueue) and the shape of a
-// decode step (StepKey {with_logits, multi, SamplerMode, pen, lp}: what enqueue_step launches and which graph replays it).
+// decode step (StepKey {with_logits, multi, StepTail}: what enqueue_step launches and which graph replays it).  What follows
+// lm_head — which sampler, penalties or not, log-probabilities or not — travels as ONE value, StepTail, from the request to the
+// launches: a generation holds one (zg_gpt::gen_tail), a step is told one (StepOpts::tail), a graph is keyed by one, and the graph
+// table is indexed by its fields as mixed-radix digits (step_index).  ONE rule says which graphs exist when: create captures the
+// default tail's and those of the tails its flags name (tails_of_flags), and a generation whose tail is another one captures that
+// tail's graphs for the buckets it will touch when it begins (gen_begin), before its steps are counted and the prefetcher starts.
 //
 // HBM layout (one hipMalloc, 256-B aligned sub-buffers):
 //   [ weights: wte | wpe | ln_f | per layer: c_attn_w c_proj_w c_fc_w mlp_proj_w + fp32 vectors ]
@@ -29,7 +34,23 @@ using namespace zg;
 // What a step puts behind lm_head: nothing (greedy: the argmax partials of its epilogue are the pick), GPT.sample's tail, or that
 // tail behind the selection launches of one filter (top-k or top-p) / of both.  The one form "how are tokens chosen" travels in.
 enum SamplerMode { GREEDY = 0, PLAIN, ONE_FILTER, TWO_FILTERS };
+constexpr size_t kSamplerModes = TWO_FILTERS + 1;
 static inline int filter_launches(SamplerMode m) { return m == TWO_FILTERS ? 6 : m == ONE_FILTER ? 3 : 0; }  // sample_filter.h: three levels per descent
+
+// Everything that follows lm_head in a decode step, as one value: the sampler, the penalty stage between lm_head and the sampler
+// (DESIGN §3.6), the log-probability stage behind the sampler — of a greedy step: behind lm_head.  The default is
+// the greedy step the reference's argmax loop runs.
+struct StepTail {
+    SamplerMode sampler = GREEDY;
+    bool pen = false, lp = false;
+    bool operator==(const StepTail& o) const { return sampler == o.sampler && pen == o.pen && lp == o.lp; }
+};
+// The tail a step can have: nothing is drawn from a step without lm_head (the default tail), and a greedy pick has no penalties
+static inline StepTail normalized(StepTail t, bool with_logits) {
+    if (!with_logits) return StepTail{};
+    if (t.sampler == GREEDY) t.pen = false;
+    return t;
+}
 
 struct zg_layer {
     void *c_attn_w, *c_proj_w, *c_fc_w, *mlp_proj_w;
@@ -107,14 +128,13 @@ struct zg_gpt {
     float* samp_ws;           // segment sums of the sampler (sample_workspace_floats)
     SampleParams* samp;       // device: temperature and seed of the generation in flight
     SampleParams* h_samp;     // pinned mirror
-    SamplerMode gen_mode;     // how the generation in flight chooses its tokens
+    StepTail gen_tail;        // what follows lm_head in the steps of the generation in flight (normalized)
     FilterWs filt;            // selection workspace of the truncated sampler (sample_filter.h), zero at create
     // logit penalties (sample_penalty.h): the caller's prior / explicit history [batch][ctx] with its lengths, the values
     // of the call in flight, their pinned mirrors (h_prior: [batch * ctx] tokens, then [batch] lengths).  The kernels' table is LDS: no workspace
     int *prior, *prior_len;
     PenParams *pen, *h_pen;
     int* h_prior;
-    bool gen_pen;             // the generation in flight penalises its logits
     // log-probabilities (sample_logprob.h): the chunk workspace, top_n of the generation in flight (device word and
     // its place in the pinned control block), the record buffers [batch][ctx] / [batch][ctx][20] and the pinned mirror a fetch
     // copies its columns through ([batch * ctx] log-probabilities, then [batch * ctx * 20] ids, then as many values)
@@ -122,8 +142,7 @@ struct zg_gpt {
     LogprobRec lp_rec;
     int *lp_top, *h_lp_top;
     float* h_lp;
-    bool gen_lp;              // the generation in flight records them
-    bool lp_valid;            // the last generation did: the record can be fetched
+    bool lp_valid;            // the last generation (or zg_gpt_score) recorded them: the record can be fetched
     size_t lp_top_n;          // ... with this many alternatives
     // scoring (zg_gpt_score; sample_score.h), carved under ZG_GPT_SCORE only: the logits of one block of kScoreRows rows
     // [kScoreRows][sc_v64] (sc_v64 = the vocabulary on the GEMMs' 64-column grid), the chunk workspace of that block, and the lm_head
@@ -190,6 +209,31 @@ struct Carver {
         const size_t o = off;
         off += bytes;
         return o;
+    }
+};
+
+// The device scratch of a per-call entry point (the zg_debug_* functions): one hipMalloc, freed on scope exit, handed out as typed
+// 256-byte-aligned sub-buffers.  Sized the way carve() sizes the arena: the entry point's carving code runs once with no base
+// (null pointers; the total is what it took) and once more with it.
+struct DevScratch {
+    Carver cv;
+    char* base = nullptr;
+    DevScratch() = default;
+    DevScratch(const DevScratch&) = delete;
+    ~DevScratch() { (void)hipFree(base); }
+    template <class T>
+    T* take(size_t bytes) {
+        const size_t o = cv.take(bytes);
+        return base ? reinterpret_cast<T*>(base + o) : nullptr;
+    }
+    template <class Carving>
+    int carve(Carving carving) {
+        carving();
+        const size_t total = (cv.off + 255) & ~(size_t)255;
+        cv = Carver{};
+        ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), total));
+        carving();
+        return ZG_OK;
     }
 };
 
@@ -633,9 +677,7 @@ struct StepOpts {
     // >= 0 (measurement chains of one kernel class): launch ids of the tagged hand-overs by chain position instead of by
     // layer, so that consecutive launches of the chain never find each other's tags
     int salt = -1;
-    SamplerMode sampler = GREEDY;  // what follows lm_head (with_logits only)
-    bool pen = false;              // the penalty stage between lm_head and the sampler (a sampler only)
-    bool lp = false;               // the log-probability stage behind the sampler (greedy: behind lm_head); with_logits only
+    StepTail tail;             // what follows lm_head (normalized: the default one without lm_head)
     struct StepTaps* taps = nullptr;  // zg_debug_gpt_step_taps: behind every launch class, copies of what it wrote (eager steps only)
 };
 
@@ -823,18 +865,19 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         return launch_logprob(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->part_val, g->part_idx, g->lm_grid, g->lm_grid, g->lp_top, g->lp_ws,
                               tokens, g->ctrl, g->prompt_len, g->lp_rec, s);
     };
-    if (o.sampler == GREEDY && o.lp && with_logits && only < 0 && !rec) ZG_TRY(logprobs(nullptr));  // (the greedy graphs have no sampler node)
-    if (o.sampler == GREEDY || !with_logits || only >= 0 || rec) return ZG_OK;
+    const StepTail tail = o.tail;
+    if (tail.sampler == GREEDY && tail.lp && with_logits && only < 0 && !rec) ZG_TRY(logprobs(nullptr));  // (the greedy graphs have no sampler node)
+    if (tail.sampler == GREEDY || !with_logits || only >= 0 || rec) return ZG_OK;
     // the penalties act on the raw logits (HF's order); the row-maximum partials both samplers start from are rebuilt behind them
-    if (o.pen)
+    if (tail.pen)
         ZG_TRY(launch_penalize(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->pen, pen_history(g, true), g->part_val, g->part_idx, g->lm_grid, nullptr, s));
-    if (const int levels = filter_launches(o.sampler))
+    if (const int levels = filter_launches(tail.sampler))
         ZG_TRY(launch_sample_filtered(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, levels, nullptr, g->ctrl, g->part_val, g->lm_grid,
                                       g->lm_grid, g->samp_ws, g->filt, g->sampled, false, s));
     else
         ZG_TRY(launch_sample_step(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, g->ctrl, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws,
                                   g->sampled, s));
-    if (o.lp) ZG_TRY(logprobs(g->sampled));
+    if (tail.lp) ZG_TRY(logprobs(g->sampled));
     return ZG_OK;
 }
 
@@ -1029,24 +1072,15 @@ size_t prefill_min() { return 4; }  // shorter prompts go through the decode cha
 //   with_logits  lm_head behind the Blocks (a step that only feeds a prompt token has none)
 //   multi        graph_steps consecutive steps (all with lm_head, all in one bucket) as ONE graph: the position lives in device
 //                memory, so the same kernels simply repeat; saves the gap between graph launches in the generate loop
-//   sampler      the sampler node(s) behind lm_head (zg_gpt_generate_sample_*; the option values are read on the device)
-//   pen          the penalty stage in front of the sampler node(s) (zg_gpt_generate_pen_enqueue; a sampler only)
-//   lp           the log-probability stage behind the sampler node(s), or behind lm_head of a greedy step (with_logits only)
-// multi and a sampler imply with_logits: 15 shapes exist without lp and 14 with it (the two greedy ones with lm_head, the twelve
-// sampled ones).  Captured at create — the sampled ones with ZG_GPT_SAMPLED_GENERATE / ZG_GPT_TRUNCATED_GENERATE /
-// ZG_GPT_PENALIZED_GENERATE, the lp twins of what create captures with ZG_GPT_LOGPROBS_GENERATE — otherwise when the first
-// generation that needs them begins.
+//   tail         what follows lm_head (StepTail, normalized; the option values are read on the device)
+// The table has a slot for every combination of the fields, indexed by them as mixed-radix digits; the slots of combinations
+// that cannot occur (multi or a tail without lm_head, penalties in front of a greedy pick) simply stay null.
 struct StepKey {
     bool with_logits, multi;
-    SamplerMode sampler;
-    bool pen = false;
-    bool lp = false;
+    StepTail tail;
 };
-constexpr size_t kStepShapes = 29;
-size_t step_index(StepKey k) {
-    if (k.sampler == GREEDY) return k.lp ? 15 + (size_t)k.multi : k.multi ? 2 : k.with_logits;
-    return (k.lp ? 14 : 0) + (k.pen ? 7 : 1) + 2 * (size_t)k.sampler + k.multi;
-}
+constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2;  // the radices of step_index
+size_t step_index(StepKey k) { return ((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp; }
 
 size_t bucket_of(size_t seq_len) { return (seq_len + 63) / 64 - 1; }
 
@@ -1079,9 +1113,7 @@ int graph_exec(zg_gpt* g, StepKey k, size_t b, hipStream_t s, hipGraphExec_t* ou
         const int t_hi = bucket_t_hi(g, (b + 1) * 64);  // any length of the bucket: only its upper bound is baked in
         const size_t n_steps = k.multi ? g->graph_steps : 1;
         StepOpts o;
-        o.sampler = k.sampler;
-        o.pen = k.pen;
-        o.lp = k.lp;
+        o.tail = k.tail;
         ZG_TRY(capture_graph(s, &e, [&] {
             int st = ZG_OK;
             for (size_t i = 0; i < n_steps && st == ZG_OK; ++i) st = enqueue_step(g, k.with_logits, t_hi, s, o);
@@ -1092,19 +1124,36 @@ int graph_exec(zg_gpt* g, StepKey k, size_t b, hipStream_t s, hipGraphExec_t* ou
     return ZG_OK;
 }
 
-// The single-step and (where the handle has them) multi-step graphs of a sampler mode, buckets b0 .. b1
-// (lp: their twins with the log-probability stage; then also of GREEDY, whose plain graphs capture_all holds)
-int capture_sampled(zg_gpt* g, SamplerMode mode, bool pen, size_t b0, size_t b1, hipStream_t s, bool lp = false) {
+// The single-step and (where the handle has them) multi-step graphs of a tail, buckets b0 .. b1
+int capture_tail(zg_gpt* g, StepTail tail, size_t b0, size_t b1, hipStream_t s) {
     hipGraphExec_t e;
     for (size_t b = b0; b <= b1 && b < g->n_buckets; ++b) {
-        ZG_TRY(graph_exec(g, {true, false, mode, pen, lp}, b, s, &e));
-        if (g->graph_steps > 1) ZG_TRY(graph_exec(g, {true, true, mode, pen, lp}, b, s, &e));
+        ZG_TRY(graph_exec(g, {true, false, tail}, b, s, &e));
+        if (g->graph_steps > 1) ZG_TRY(graph_exec(g, {true, true, tail}, b, s, &e));
     }
     return ZG_OK;
 }
 
+// The tails whose graphs zg_gpt_create captures besides the default one, by the handle's flags: each *_GENERATE flag names the
+// samplers it is for, and ZG_GPT_LOGPROBS_GENERATE the twins with the log-probability stage of the default tail and of those
+std::vector<StepTail> tails_of_flags(unsigned flags) {
+    std::vector<StepTail> t;
+    if (flags & ZG_GPT_SAMPLED_GENERATE) t.push_back({PLAIN, false, false});
+    if (flags & ZG_GPT_TRUNCATED_GENERATE)
+        for (SamplerMode m : {ONE_FILTER, TWO_FILTERS}) t.push_back({m, false, false});
+    if (flags & ZG_GPT_PENALIZED_GENERATE)
+        for (SamplerMode m : {PLAIN, ONE_FILTER, TWO_FILTERS}) t.push_back({m, true, false});
+    if (flags & ZG_GPT_LOGPROBS_GENERATE) {
+        const size_t n = t.size();
+        t.push_back({GREEDY, false, true});
+        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, true});
+    }
+    return t;
+}
+
 // All decode graphs of a handle for stream s.  Called from zg_gpt_create — the State.init moment (main.zig:46-64) — so that
-// no forward allocates; a later zg_set_stream re-captures them on the first call that sees the new stream.
+// no forward allocates; a later zg_set_stream re-captures them on the first call that sees the new stream.  A generation whose
+// tail create did not capture adds that tail's graphs when it begins (gen_begin).
 int capture_all(zg_gpt* g, hipStream_t s) {
     if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) return ZG_OK;
     if (g->graph_stream != s) {
@@ -1112,44 +1161,25 @@ int capture_all(zg_gpt* g, hipStream_t s) {
         g->graph_stream = s;
     }
     hipGraphExec_t e;
-    for (size_t b = 0; b < g->n_buckets; ++b) {
-        ZG_TRY(graph_exec(g, {false, false, GREEDY}, b, s, &e));
-        ZG_TRY(graph_exec(g, {true, false, GREEDY}, b, s, &e));
-    }
-    if (g->graph_steps > 1)
-        for (size_t b = 0; b < g->n_buckets; ++b) ZG_TRY(graph_exec(g, {true, true, GREEDY}, b, s, &e));
-    if (g->flags & ZG_GPT_SAMPLED_GENERATE) ZG_TRY(capture_sampled(g, PLAIN, false, 0, g->n_buckets - 1, s));
-    if (g->flags & ZG_GPT_TRUNCATED_GENERATE)
-        for (SamplerMode m : {ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, false, 0, g->n_buckets - 1, s));
-    if (g->flags & ZG_GPT_PENALIZED_GENERATE)
-        for (SamplerMode m : {PLAIN, ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, true, 0, g->n_buckets - 1, s));
-    if (g->flags & ZG_GPT_LOGPROBS_GENERATE) {  // the twins of everything above that has lm_head
-        ZG_TRY(capture_sampled(g, GREEDY, false, 0, g->n_buckets - 1, s, true));
-        if (g->flags & ZG_GPT_SAMPLED_GENERATE) ZG_TRY(capture_sampled(g, PLAIN, false, 0, g->n_buckets - 1, s, true));
-        if (g->flags & ZG_GPT_TRUNCATED_GENERATE)
-            for (SamplerMode m : {ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, false, 0, g->n_buckets - 1, s, true));
-        if (g->flags & ZG_GPT_PENALIZED_GENERATE)
-            for (SamplerMode m : {PLAIN, ONE_FILTER, TWO_FILTERS}) ZG_TRY(capture_sampled(g, m, true, 0, g->n_buckets - 1, s, true));
-    }
+    for (size_t b = 0; b < g->n_buckets; ++b) ZG_TRY(graph_exec(g, {false, false, StepTail{}}, b, s, &e));
+    ZG_TRY(capture_tail(g, StepTail{}, 0, g->n_buckets - 1, s));
+    for (const StepTail& t : tails_of_flags(g->flags)) ZG_TRY(capture_tail(g, t, 0, g->n_buckets - 1, s));
     return ZG_OK;
 }
 
 // Run one decode step at sequence length seq_len: replay the graph of its bucket, or launch eagerly when graphs
 // are disabled / the stream cannot be captured.
-int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, SamplerMode sampler = GREEDY, bool pen = false, bool lp = false) {
+int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, StepTail tail = StepTail{}) {
     ZG_TRY(ensure_ln_folded(g, s));
-    if (!with_logits) sampler = GREEDY, lp = false;  // (nothing to draw from)
-    if (sampler == GREEDY) pen = false;
+    tail = normalized(tail, with_logits);
     if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) {
         StepOpts o;
-        o.sampler = sampler;
-        o.pen = pen;
-        o.lp = lp;
+        o.tail = tail;
         return enqueue_step(g, with_logits, bucket_t_hi(g, seq_len), s, o);
     }
     if (g->graph_stream != s) ZG_TRY(capture_all(g, s));  // the caller switched streams after zg_gpt_create
     hipGraphExec_t e;
-    ZG_TRY(graph_exec(g, {with_logits, false, sampler, pen, lp}, bucket_of(seq_len), s, &e));
+    ZG_TRY(graph_exec(g, {with_logits, false, tail}, bucket_of(seq_len), s, &e));
     ZG_HIP(hipGraphLaunch(e, s));
     return ZG_OK;
 }
@@ -1609,11 +1639,8 @@ int zg_debug_gpt_step_taps(zg_gpt* g, size_t seq_len, const size_t* tokens, size
     StepTaps taps;
     taps.seq_len = seq_len;
     taps.cap = cap;
-    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&taps.base), cap));
-    struct Free {
-        char* p;
-        ~Free() { (void)hipFree(p); }
-    } guard{taps.base};
+    DevScratch ds;
+    ZG_TRY(ds.carve([&] { taps.base = ds.take<char>(cap); }));
     ZG_HIP(hipMemsetAsync(taps.base, 0, cap, s));
     ZG_TRY(forward_enqueue(g, seq_len, tokens, n_tokens, 1, nullptr, 0, &taps));
     ZG_HIP(hipStreamSynchronize(s));
@@ -1624,6 +1651,31 @@ int zg_debug_gpt_step_taps(zg_gpt* g, size_t seq_len, const size_t* tokens, size
     memcpy(table_out, taps.table.data(), taps.table.size() * sizeof(zg_tap_entry));
     *arena_used = taps.used;
     return ZG_OK;
+}
+
+// How many alternatives a log-probability record may be asked for: the one check of every entry point that takes a top_n
+static int check_top_n(size_t top_n, size_t vocab, const char* who) {
+    ZG_REQUIRE(top_n <= (size_t)ZG_LOGPROBS_TOP_MAX && top_n <= vocab, ZG_ERR_ARG, "%s: top_n %zu outside 0..%zu", who, top_n,
+               std::min((size_t)ZG_LOGPROBS_TOP_MAX, vocab));
+    return ZG_OK;
+}
+
+// top_n of the record the call in flight writes, through its pinned word into the arena: from here on a fetch finds that record
+static int stage_top_n(zg_gpt* g, size_t top_n, hipStream_t s) {
+    g->lp_valid = true;
+    g->lp_top_n = top_n;
+    *g->h_lp_top = (int)top_n;
+    ZG_HIP(hipMemcpyAsync(g->lp_top, g->h_lp_top, sizeof(int), hipMemcpyHostToDevice, s));
+    return ZG_OK;
+}
+
+// `rows` records [ZG_LOGPROBS_TOP_MAX] of ids and values (host) into the packed [rows][top_n] arrays (host) a caller receives
+static void unpack_top(const int* ids, const float* vals, size_t rows, size_t top_n, size_t* ids_out, float* vals_out) {
+    for (size_t i = 0; i < rows; ++i)
+        for (size_t j = 0; j < top_n; ++j) {
+            ids_out[i * top_n + j] = (size_t)ids[i * ZG_LOGPROBS_TOP_MAX + j];
+            vals_out[i * top_n + j] = vals[i * ZG_LOGPROBS_TOP_MAX + j];
+        }
 }
 
 // The whole-prompt pass: n tokens of every sequence go to positions past_len .. past_len + n - 1 behind the cached
@@ -1675,8 +1727,7 @@ static int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t st
     const size_t C = g->cfg.context_size, V = g->cfg.vocab_size, B = g->batch, E = g->cfg.n_embed;
     if (sc) {
         ZG_REQUIRE(g->sc_logits != nullptr, ZG_ERR_UNSUPPORTED, "%s: the handle was created without ZG_GPT_SCORE", who);
-        ZG_REQUIRE(sc->top_n <= (size_t)ZG_LOGPROBS_TOP_MAX && sc->top_n <= V, ZG_ERR_ARG, "%s: top_n %zu outside 0..%zu", who, sc->top_n,
-                   std::min((size_t)ZG_LOGPROBS_TOP_MAX, V));
+        ZG_TRY(check_top_n(sc->top_n, V, who));
         ZG_REQUIRE(V <= (size_t)64 * 4096, ZG_ERR_UNSUPPORTED, "%s: vocabulary of %zu beyond %d", who, V, 64 * 4096);
     }
     ZG_REQUIRE(past_len <= g->cached_len, ZG_ERR_ARG, "%s: past_len %zu beyond the %zu cached positions", who, past_len, g->cached_len);
@@ -1703,11 +1754,7 @@ static int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t st
         if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, B * V, s));
     }
     if (sc) {  // a log-probability generation with this top_n: the record continues behind it (generate_from) and leaves through the same fetch
-        g->gen_lp = false;
-        g->lp_valid = true;
-        g->lp_top_n = sc->top_n;
-        *g->h_lp_top = (int)sc->top_n;
-        ZG_HIP(hipMemcpyAsync(g->lp_top, g->h_lp_top, sizeof(int), hipMemcpyHostToDevice, s));
+        ZG_TRY(stage_top_n(g, sc->top_n, s));
         // column past_len: its predicting row is not part of the pass (NaN: every byte 0xff)
         ZG_HIP(hipMemset2DAsync(g->lp_rec.logprob + past_len, C * sizeof(float), 0xff, sizeof(float), B, s));
         ZG_TRY(enqueue_score(g, past_len, n, sc->logits_out, s));
@@ -1969,8 +2016,7 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
         ZG_TRY(check_history(g, r.prior, r.prior_stride, r.prior_lens, n_steps, "generate_pen"));
     }
     if (r.lp_on) {
-        ZG_REQUIRE(r.top_n <= (size_t)ZG_LOGPROBS_TOP_MAX && r.top_n <= V, ZG_ERR_ARG, "generate_logprobs: top_n %zu outside 0..%zu", r.top_n,
-                   std::min((size_t)ZG_LOGPROBS_TOP_MAX, V));
+        ZG_TRY(check_top_n(r.top_n, V, "generate_logprobs"));
         ZG_REQUIRE(V <= (size_t)64 * 4096, ZG_ERR_UNSUPPORTED, "generate_logprobs: vocabulary of %zu beyond %d", V, 64 * 4096);
     }
     hipStream_t s = gs(g);
@@ -1988,18 +2034,15 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     size_t first = 0;
     if (g->pf_x != nullptr && min_prompt >= prefill_min())
         first = min_prompt < n_steps ? min_prompt : n_steps;
-    g->gen_mode = r.mode;
+    g->gen_tail = StepTail{r.mode, pen_on, r.lp_on};  // (normalized: pen_on only with a sampler, and the steps it is for have lm_head)
     if (r.mode != GREEDY) {
-        g->gen_mode = fill_sample_params(g->h_samp, V, r.opt, r.seed);
+        g->gen_tail.sampler = fill_sample_params(g->h_samp, V, r.opt, r.seed);
         ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     }
-    g->gen_pen = pen_on;
     if (pen_on) ZG_TRY(stage_penalties(g, r.pen, past, r.prior, r.prior_stride, r.prior_lens, s));
-    g->gen_lp = g->lp_valid = r.lp_on;
+    g->lp_valid = false;
     if (r.lp_on) {
-        g->lp_top_n = r.top_n;
-        *g->h_lp_top = (int)r.top_n;
-        ZG_HIP(hipMemcpyAsync(g->lp_top, g->h_lp_top, sizeof(int), hipMemcpyHostToDevice, s));
+        ZG_TRY(stage_top_n(g, r.top_n, s));
         // the new columns no step with lm_head reaches (the whole-prompt pass, steps that only feed a prompt token) record prompt
         // tokens: NaN (every byte 0xff); the stage itself writes the NaN of a longer row's prompt columns
         const size_t fed = std::min(min_prompt, n_steps);
@@ -2017,15 +2060,14 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
             ZG_HIP(hipMemcpy2DAsync(g->out_tokens + past, C * sizeof(int), g->prompt + past, C * sizeof(int), first * sizeof(int), B, hipMemcpyDeviceToDevice, s));
         ZG_TRY(enqueue_prefill(g, past, first, false, s));
     }
-    if (!(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && g->graph_stream != s) ZG_TRY(capture_all(g, s));  // before the prefetcher starts its idle clock
-    // the truncated sampler's graphs of every bucket this generation touches, if create did not capture them: here, not in the
-    // loop (a capture between the steps would run against the prefetcher's idle clock)
-    // (and those of a penalised generation, whatever its sampler)
-    if ((filter_launches(g->gen_mode) || g->gen_pen) && !(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && min_prompt < n_steps)
-        ZG_TRY(capture_sampled(g, g->gen_mode, g->gen_pen, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
-    // (and the twins with the log-probability stage, the greedy ones too)
-    if (g->gen_lp && !(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr && min_prompt < n_steps)
-        ZG_TRY(capture_sampled(g, g->gen_mode, g->gen_pen, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s, true));
+    // Every graph the loop will replay exists before the prefetcher starts its idle clock (a capture between the steps would run
+    // against it): all of create's on a stream create did not see, and this generation's own tail — whatever create did not
+    // capture of it (graph_exec skips what exists) — for the buckets of its steps with lm_head
+    if (!(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr) {
+        if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
+        if (!(g->gen_tail == StepTail{}) && min_prompt < n_steps)
+            ZG_TRY(capture_tail(g, g->gen_tail, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
+    }
     ZG_TRY(note_steps(g, n_steps, s));
     ZG_TRY(pf_start(g, past + n_steps, s));
     g->gen_pos = past + first;  // absolute, as gen_n and gen_min_prompt: gen_pump's steps, buckets and graph alignment follow the position
@@ -2051,12 +2093,12 @@ static int gen_pump(zg_gpt* g, bool* more) {
     }
     if (K > 1 && st >= g->gen_min_prompt && st % K == 0 && st + K <= n_steps && st + K <= C) {
         if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
-        hipGraphExec_t e;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64)
-        ZG_TRY(graph_exec(g, {true, true, g->gen_mode, g->gen_pen, g->gen_lp}, bucket_of(st + 1), s, &e));
+        hipGraphExec_t e;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64); captured by gen_begin (first use: the backstop)
+        ZG_TRY(graph_exec(g, {true, true, g->gen_tail}, bucket_of(st + 1), s, &e));
         ZG_HIP(hipGraphLaunch(e, s));
         g->gen_pos = st + K;
     } else {
-        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_mode, g->gen_pen, g->gen_lp));
+        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_tail));
         g->gen_pos = st + 1;
     }
     *more = g->gen_pos < n_steps;
@@ -2155,7 +2197,7 @@ int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_strid
 }
 
 // The same behind top-k / nucleus truncation (include/zgpt2.h zg_sample_options; sample_filter.h): the selection launches sit in
-// front of the sampler node of graphs of their own (StepKey.sampler), the option values live in device memory.  Filters off: the
+// front of the sampler node of graphs of their own (StepTail.sampler), the option values live in device memory.  Filters off: the
 // calls above.
 int zg_gpt_generate_sample_ex_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
                                       const zg_sample_options* opt, uint64_t seed) {
@@ -2180,30 +2222,38 @@ int zg_gpt_generate_from_enqueue(zg_gpt* g, size_t past_len, const size_t* promp
     return gen_run(&g, 1, GenRequest(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len));
 }
 
-// zg_gpt_generate_from_enqueue with penalties: the penalty stage is a node of graphs of their own (StepKey.pen), its
-// values, past_len and the prior live in device memory.  All penalties off: zg_gpt_generate_from_enqueue itself.
-int zg_gpt_generate_pen_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
-                                const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
-                                const size_t* prior_lens, uint64_t seed) {
-    ZG_TRY(require_init());
-    ZG_TRY(check_sample_options(opt, "generate_pen"));
-    ZG_TRY(check_penalties(pen, "generate_pen"));
-    GenRequest r(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len);
+// The penalties of an entry point and the caller's prior into the request.  All penalties off: the request stays what it was
+// without them, but the lists are still the caller's to get right.
+static int request_penalties(const zg_gpt* g, GenRequest& r, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride, const size_t* prior_lens,
+                             const char* who) {
+    ZG_TRY(check_penalties(pen, who));
     if (!penalties_off(*pen)) {
         r.pen_on = true;
         r.pen = *pen;
         r.prior = prior;
         r.prior_stride = prior_stride;
         r.prior_lens = prior_lens;
-    } else if (g) {  // (the lists are still the caller's to get right)
-        ZG_TRY(check_pen_handle(g, "generate_pen"));
-        ZG_TRY(check_history(g, prior, prior_stride, prior_lens, 0, "generate_pen"));
+    } else if (g) {
+        ZG_TRY(check_pen_handle(g, who));
+        ZG_TRY(check_history(g, prior, prior_stride, prior_lens, 0, who));
     }
+    return ZG_OK;
+}
+
+// zg_gpt_generate_from_enqueue with penalties: the penalty stage is a node of graphs of their own (StepTail.pen), its
+// values, past_len and the prior live in device memory.  All penalties off: zg_gpt_generate_from_enqueue itself.
+int zg_gpt_generate_pen_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
+                                const size_t* prior_lens, uint64_t seed) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, "generate_pen"));
+    GenRequest r(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len);
+    ZG_TRY(request_penalties(g, r, pen, prior, prior_stride, prior_lens, "generate_pen"));
     return gen_run(&g, 1, r);
 }
 
 // zg_gpt_generate_pen_enqueue / _from_enqueue with the log-probability stage: a node pair of graphs of their own
-// (StepKey.lp) behind the sampler node, or behind lm_head of a greedy step; top_n lives in device memory.  The stage only reads
+// (StepTail.lp) behind the sampler node, or behind lm_head of a greedy step; top_n lives in device memory.  The stage only reads
 // what the step left, so the tokens are those of the call without it.
 int zg_gpt_generate_logprobs_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
                                      const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
@@ -2211,20 +2261,10 @@ int zg_gpt_generate_logprobs_enqueue(zg_gpt* g, size_t past_len, const size_t* p
     ZG_TRY(require_init());
     if (opt) ZG_TRY(check_sample_options(opt, "generate_logprobs"));
     ZG_REQUIRE(opt || !pen, ZG_ERR_ARG, "generate_logprobs: penalties without sampler options (greedy picking with penalties is top_k = 1)");
-    if (pen) ZG_TRY(check_penalties(pen, "generate_logprobs"));
     GenRequest r(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len);
     r.lp_on = true;
     r.top_n = top_n;
-    if (pen && !penalties_off(*pen)) {
-        r.pen_on = true;
-        r.pen = *pen;
-        r.prior = prior;
-        r.prior_stride = prior_stride;
-        r.prior_lens = prior_lens;
-    } else if (pen && g) {  // (the lists are still the caller's to get right)
-        ZG_TRY(check_pen_handle(g, "generate_logprobs"));
-        ZG_TRY(check_history(g, prior, prior_stride, prior_lens, 0, "generate_logprobs"));
-    }
+    if (pen) ZG_TRY(request_penalties(g, r, pen, prior, prior_stride, prior_lens, "generate_logprobs"));
     return gen_run(&g, 1, r);
 }
 
@@ -2252,11 +2292,44 @@ int zg_gpt_generate_fetch_logprobs(zg_gpt* g, size_t first, size_t n, size_t top
     ZG_HIP(hipStreamSynchronize(s));
     ZG_TRY(check_fault(g));
     memcpy(logprobs_out, h_lp, B * n * sizeof(float));
-    for (size_t i = 0; i < B * n; ++i)
-        for (size_t j = 0; j < top_n; ++j) {
-            top_ids_out[i * top_n + j] = (size_t)h_ids[i * K + j];
-            top_logprobs_out[i * top_n + j] = h_top[i * K + j];
-        }
+    unpack_top(h_ids, h_top, B * n, top_n, top_ids_out, top_logprobs_out);
+    return ZG_OK;
+}
+
+// What the two debug entry points below share: the checks on top_n and its outputs ...
+static int check_debug_top_n(size_t top_n, size_t vocab, const size_t* top_ids_out, const float* top_logprobs_out, const char* who) {
+    ZG_TRY(check_top_n(top_n, vocab, who));
+    ZG_REQUIRE(top_n == 0 || (top_ids_out && top_logprobs_out), ZG_ERR_ARG, "%s: top_n %zu without its outputs", who, top_n);
+    return ZG_OK;
+}
+// ... record buffers [rows][stride], carved from the call's scratch ...
+static LogprobRec debug_record(DevScratch& ds, size_t rows, size_t stride) {
+    LogprobRec rec{};
+    rec.logprob = ds.take<float>(rows * stride * 4);
+    rec.top_ids = ds.take<int>(rows * stride * ZG_LOGPROBS_TOP_MAX * 4);
+    rec.top_logprobs = ds.take<float>(rows * stride * ZG_LOGPROBS_TOP_MAX * 4);
+    rec.stride = (int)stride;
+    return rec;
+}
+// ... and the way back of its elements col0 .. col0 + n - 1: the outputs may be host or device memory, so the
+// alternatives are packed on the host and leave in one copy each.  Drains the stream.
+static int debug_record_out(const LogprobRec& rec, size_t col0, size_t n, size_t top_n, float* logprobs_out, size_t* top_ids_out, float* top_logprobs_out,
+                            hipStream_t s) {
+    const size_t K = ZG_LOGPROBS_TOP_MAX;
+    std::vector<int> h_ids(n * K);
+    std::vector<float> h_top(n * K);
+    ZG_HIP(hipMemcpyAsync(logprobs_out, rec.logprob + col0, n * 4, hipMemcpyDefault, s));
+    if (top_n) {
+        ZG_HIP(hipMemcpyAsync(h_ids.data(), rec.top_ids + col0 * K, n * K * 4, hipMemcpyDeviceToHost, s));
+        ZG_HIP(hipMemcpyAsync(h_top.data(), rec.top_logprobs + col0 * K, n * K * 4, hipMemcpyDeviceToHost, s));
+    }
+    ZG_HIP(hipStreamSynchronize(s));
+    if (!top_n) return ZG_OK;
+    std::vector<size_t> ids(n * top_n);
+    std::vector<float> vals(n * top_n);
+    unpack_top(h_ids.data(), h_top.data(), n, top_n, ids.data(), vals.data());
+    ZG_HIP(hipMemcpy(top_ids_out, ids.data(), ids.size() * sizeof(size_t), hipMemcpyDefault));
+    ZG_HIP(hipMemcpy(top_logprobs_out, vals.data(), vals.size() * 4, hipMemcpyDefault));
     return ZG_OK;
 }
 
@@ -2267,11 +2340,8 @@ int zg_debug_logprob_rows(const float* logits, size_t batch, size_t vocab, const
     ZG_TRY(require_init());
     ZG_REQUIRE(logits && tokens && logprobs_out && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG,
                "debug_logprob_rows: bad argument");
-    ZG_REQUIRE(top_n <= (size_t)ZG_LOGPROBS_TOP_MAX && top_n <= vocab, ZG_ERR_ARG, "debug_logprob_rows: top_n %zu outside 0..%zu", top_n,
-               std::min((size_t)ZG_LOGPROBS_TOP_MAX, vocab));
-    ZG_REQUIRE(top_n == 0 || (top_ids_out && top_logprobs_out), ZG_ERR_ARG, "debug_logprob_rows: top_n %zu without its outputs", top_n);
-    const size_t K = ZG_LOGPROBS_TOP_MAX;
-    std::vector<int> h_tok(batch), h_ids(batch * K);
+    ZG_TRY(check_debug_top_n(top_n, vocab, top_ids_out, top_logprobs_out, "debug_logprob_rows"));
+    std::vector<int> h_tok(batch);
     std::vector<size_t> h_tok_in(batch);
     ZG_HIP(hipMemcpy(h_tok_in.data(), tokens, batch * sizeof(size_t), hipMemcpyDefault));
     for (size_t b = 0; b < batch; ++b) {
@@ -2279,59 +2349,27 @@ int zg_debug_logprob_rows(const float* logits, size_t batch, size_t vocab, const
         h_tok[b] = (int)h_tok_in[b];
     }
     const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t lbytes = up(batch * vocab * 4), wbytes = up(logprob_workspace_bytes(B, V)), pbytes = up((size_t)B * n_part * 4), bbytes = up(batch * 4),
-                 rbytes = up(batch * K * 4);
     hipStream_t s = ctx().stream;
-    char* base = nullptr;
-    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), lbytes + wbytes + pbytes + 3 * bbytes + 2 * rbytes));
-    struct Free {
-        char* p;
-        ~Free() { (void)hipFree(p); }
-    } guard{base};
-    char* p = base;
-    float* d_logits = reinterpret_cast<float*>(p);
-    p += lbytes;
-    const LogprobWs ws = logprob_workspace(p, B, V);
-    p += wbytes;
-    float* d_part = reinterpret_cast<float*>(p);
-    p += pbytes;
-    int* d_tok = reinterpret_cast<int*>(p);
-    p += bbytes;
-    int* d_top = reinterpret_cast<int*>(p);
-    p += bbytes;
-    LogprobRec rec{};
-    rec.logprob = reinterpret_cast<float*>(p);
-    p += bbytes;
-    rec.top_ids = reinterpret_cast<int*>(p);
-    p += rbytes;
-    rec.top_logprobs = reinterpret_cast<float*>(p);
-    rec.stride = 1;
+    DevScratch ds;
+    float *d_logits, *d_part;
+    int *d_tok, *d_top;
+    LogprobWs ws;
+    LogprobRec rec;
+    ZG_TRY(ds.carve([&] {
+        d_logits = ds.take<float>(batch * vocab * 4);
+        ws = logprob_workspace(ds.take<char>(logprob_workspace_bytes(B, V)), B, V);
+        d_part = ds.take<float>((size_t)B * n_part * 4);
+        d_tok = ds.take<int>(batch * 4);
+        d_top = ds.take<int>(4);
+        rec = debug_record(ds, batch, 1);
+    }));
     const int h_top_n = (int)top_n;
-    std::vector<float> h_top(batch * K);
     ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
     ZG_HIP(hipMemcpyAsync(d_tok, h_tok.data(), batch * 4, hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(d_top, &h_top_n, 4, hipMemcpyHostToDevice, s));
     ZG_TRY(launch_row_max_partials(d_logits, B, V, d_part, n_part, s));
     ZG_TRY(launch_logprob(d_logits, B, V, d_part, nullptr, n_part, n_part, d_top, ws, d_tok, nullptr, nullptr, rec, s));
-    ZG_HIP(hipMemcpyAsync(logprobs_out, rec.logprob, batch * 4, hipMemcpyDefault, s));
-    if (top_n) {
-        ZG_HIP(hipMemcpyAsync(h_ids.data(), rec.top_ids, batch * K * 4, hipMemcpyDeviceToHost, s));
-        ZG_HIP(hipMemcpyAsync(h_top.data(), rec.top_logprobs, batch * K * 4, hipMemcpyDeviceToHost, s));
-    }
-    ZG_HIP(hipStreamSynchronize(s));
-    if (top_n) {  // (outputs host or device: packed on the host, one copy each)
-        std::vector<size_t> ids(batch * top_n);
-        std::vector<float> vals(batch * top_n);
-        for (size_t b = 0; b < batch; ++b)
-            for (size_t j = 0; j < top_n; ++j) {
-                ids[b * top_n + j] = (size_t)h_ids[b * K + j];
-                vals[b * top_n + j] = h_top[b * K + j];
-            }
-        ZG_HIP(hipMemcpy(top_ids_out, ids.data(), ids.size() * sizeof(size_t), hipMemcpyDefault));
-        ZG_HIP(hipMemcpy(top_logprobs_out, vals.data(), vals.size() * 4, hipMemcpyDefault));
-    }
-    return ZG_OK;
+    return debug_record_out(rec, 0, batch, top_n, logprobs_out, top_ids_out, top_logprobs_out, s);
 }
 
 // The scoring kernels on the caller's rows (tests): the two launches of zg_gpt_score's statistics stage, the rows standing for one
@@ -2342,11 +2380,9 @@ int zg_debug_score_rows(const float* logits, size_t rows, size_t vocab, size_t r
     ZG_REQUIRE(logits && targets && logprobs_out && rows >= 1 && rows <= 4096 && vocab >= 1 && vocab <= (size_t)64 * 4096 && row_stride >= vocab &&
                    row_stride <= (size_t)1 << 20,
                ZG_ERR_ARG, "debug_score_rows: bad argument");
-    ZG_REQUIRE(top_n <= (size_t)ZG_LOGPROBS_TOP_MAX && top_n <= vocab, ZG_ERR_ARG, "debug_score_rows: top_n %zu outside 0..%zu", top_n,
-               std::min((size_t)ZG_LOGPROBS_TOP_MAX, vocab));
-    ZG_REQUIRE(top_n == 0 || (top_ids_out && top_logprobs_out), ZG_ERR_ARG, "debug_score_rows: top_n %zu without its outputs", top_n);
-    const size_t K = ZG_LOGPROBS_TOP_MAX, cols = rows + 1;
-    std::vector<int> h_tok(cols, 0), h_ids(cols * K);
+    ZG_TRY(check_debug_top_n(top_n, vocab, top_ids_out, top_logprobs_out, "debug_score_rows"));
+    const size_t cols = rows + 1;
+    std::vector<int> h_tok(cols, 0);
     std::vector<size_t> h_tok_in(rows);
     ZG_HIP(hipMemcpy(h_tok_in.data(), targets, rows * sizeof(size_t), hipMemcpyDefault));
     for (size_t r = 0; r < rows; ++r) {
@@ -2354,55 +2390,37 @@ int zg_debug_score_rows(const float* logits, size_t rows, size_t vocab, size_t r
         h_tok[r + 1] = (int)h_tok_in[r];
     }
     const int R = (int)rows, V = (int)vocab;
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t lbytes = up(rows * row_stride * 4), wbytes = up(score_workspace_bytes(R, V)), cbytes = up(cols * 4), rbytes = up(cols * K * 4);
     hipStream_t s = ctx().stream;
-    char* base = nullptr;
-    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), lbytes + wbytes + 256 + 2 * cbytes + 2 * rbytes));
-    struct Free {
-        char* p;
-        ~Free() { (void)hipFree(p); }
-    } guard{base};
-    char* p = base;
-    float* d_logits = reinterpret_cast<float*>(p);
-    p += lbytes;
-    const ScoreWs ws = score_workspace(p, R, V);
-    p += wbytes;
-    int* d_top = reinterpret_cast<int*>(p);
-    p += 256;
-    int* d_tok = reinterpret_cast<int*>(p);
-    p += cbytes;
-    LogprobRec rec{};
-    rec.logprob = reinterpret_cast<float*>(p);
-    p += cbytes;
-    rec.top_ids = reinterpret_cast<int*>(p);
-    p += rbytes;
-    rec.top_logprobs = reinterpret_cast<float*>(p);
-    rec.stride = (int)cols;
+    DevScratch ds;
+    float* d_logits;
+    int *d_tok, *d_top;
+    ScoreWs ws;
+    LogprobRec rec;
+    ZG_TRY(ds.carve([&] {
+        d_logits = ds.take<float>(rows * row_stride * 4);
+        ws = score_workspace(ds.take<char>(score_workspace_bytes(R, V)), R, V);
+        d_top = ds.take<int>(4);
+        d_tok = ds.take<int>(cols * 4);
+        rec = debug_record(ds, 1, cols);
+    }));
     const int h_top_n = (int)top_n;
-    std::vector<float> h_top(cols * K);
     ZG_HIP(hipMemcpyAsync(d_logits, logits, rows * row_stride * 4, hipMemcpyDefault, s));
     ZG_HIP(hipMemcpyAsync(d_tok, h_tok.data(), cols * 4, hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(d_top, &h_top_n, 4, hipMemcpyHostToDevice, s));
     const ScoreTargets tg{d_tok, (int)cols, (int)cols, 0, 0};
     ZG_TRY(launch_score(d_logits, R, V, (int)row_stride, d_top, ws, tg, rec, s));
-    ZG_HIP(hipMemcpyAsync(logprobs_out, rec.logprob + 1, rows * 4, hipMemcpyDefault, s));
-    if (top_n) {
-        ZG_HIP(hipMemcpyAsync(h_ids.data(), rec.top_ids, cols * K * 4, hipMemcpyDeviceToHost, s));
-        ZG_HIP(hipMemcpyAsync(h_top.data(), rec.top_logprobs, cols * K * 4, hipMemcpyDeviceToHost, s));
-    }
+    return debug_record_out(rec, 1, rows, top_n, logprobs_out, top_ids_out, top_logprobs_out, s);
+}
+
+// The recorded tokens of positions first .. first + n - 1, packed [batch][n]: the body of both fetches (their arguments checked)
+static int fetch_tokens(zg_gpt* g, size_t first, size_t n, size_t* out_tokens) {
+    const size_t C = g->cfg.context_size, B = g->batch;
+    hipStream_t s = gs(g);
+    ZG_HIP(hipMemcpyAsync(g->h_ints, g->out_tokens, B * C * sizeof(int), hipMemcpyDeviceToHost, s));
     ZG_HIP(hipStreamSynchronize(s));
-    if (top_n) {  // (outputs host or device: packed on the host, one copy each)
-        std::vector<size_t> ids(rows * top_n);
-        std::vector<float> vals(rows * top_n);
-        for (size_t r = 0; r < rows; ++r)
-            for (size_t j = 0; j < top_n; ++j) {
-                ids[r * top_n + j] = (size_t)h_ids[(r + 1) * K + j];
-                vals[r * top_n + j] = h_top[(r + 1) * K + j];
-            }
-        ZG_HIP(hipMemcpy(top_ids_out, ids.data(), ids.size() * sizeof(size_t), hipMemcpyDefault));
-        ZG_HIP(hipMemcpy(top_logprobs_out, vals.data(), vals.size() * 4, hipMemcpyDefault));
-    }
+    ZG_TRY(check_fault(g));
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < n; ++i) out_tokens[b * n + i] = (size_t)g->h_ints[b * C + first + i];
     return ZG_OK;
 }
 
@@ -2412,13 +2430,7 @@ int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_t
     const size_t C = g->cfg.context_size, B = g->batch;
     ZG_REQUIRE(first <= C && n <= C - first && out_len >= B * n, ZG_ERR_SHAPE, "generate_fetch_range: positions %zu .. %zu of %zu, %zu elements", first,
                first + n, C, out_len);
-    hipStream_t s = gs(g);
-    ZG_HIP(hipMemcpyAsync(g->h_ints, g->out_tokens, B * C * sizeof(int), hipMemcpyDeviceToHost, s));
-    ZG_HIP(hipStreamSynchronize(s));
-    ZG_TRY(check_fault(g));
-    for (size_t b = 0; b < B; ++b)
-        for (size_t i = 0; i < n; ++i) out_tokens[b * n + i] = (size_t)g->h_ints[b * C + first + i];
-    return ZG_OK;
+    return fetch_tokens(g, first, n, out_tokens);
 }
 
 // The truncated sampler on the caller's logits (tests): the kernels of zg_gpt_sample_ex, a small kernel standing in for lm_head's
@@ -2432,31 +2444,23 @@ int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const 
     const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
     SampleParams hp{};
     const int levels = filter_launches(fill_sample_params(&hp, vocab, *opt, 0));
-    const size_t fbytes = (filter_workspace_bytes(B) + 255) & ~(size_t)255, lbytes = (batch * vocab * 4 + 255) & ~(size_t)255;
-    const size_t sbytes = (sample_workspace_floats(B) * 4 + 255) & ~(size_t)255, pbytes = ((size_t)B * n_part * 4 + 255) & ~(size_t)255;
-    const size_t total = fbytes + lbytes + sbytes + pbytes + 256 * 3 + (((size_t)B * 8 + 255) & ~(size_t)255);
     hipStream_t s = ctx().stream;
-    char* base = nullptr;
-    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), total));
-    struct Free {
-        char* p;
-        ~Free() { (void)hipFree(p); }
-    } guard{base};
-    char* p = base;
-    const FilterWs fws = filter_workspace(p, B);
-    p += fbytes;
-    float* d_logits = reinterpret_cast<float*>(p);
-    p += lbytes;
-    float* d_seg = reinterpret_cast<float*>(p);
-    p += sbytes;
-    float* d_part = reinterpret_cast<float*>(p);
-    p += pbytes;
-    SampleParams* d_par = reinterpret_cast<SampleParams*>(p);
-    p += 256;
-    float* d_u = reinterpret_cast<float*>(p);
-    p += 256;
-    int* d_tok = reinterpret_cast<int*>(p);
-    p += 256;
+    DevScratch ds;
+    char* d_filt;
+    FilterWs fws;
+    float *d_logits, *d_seg, *d_part, *d_u;
+    SampleParams* d_par;
+    int* d_tok;
+    ZG_TRY(ds.carve([&] {
+        d_filt = ds.take<char>(filter_workspace_bytes(B));
+        fws = filter_workspace(d_filt, B);
+        d_logits = ds.take<float>(batch * vocab * 4);
+        d_seg = ds.take<float>(sample_workspace_floats(B) * 4);
+        d_part = ds.take<float>((size_t)B * n_part * 4);
+        d_par = ds.take<SampleParams>(sizeof(SampleParams));
+        d_u = ds.take<float>(batch * 4);
+        d_tok = ds.take<int>(batch * 4);
+    }));
     std::vector<int> h_tok(batch);
     std::vector<float> h_u(batch);
     for (size_t b = 0; b < batch; ++b) {
@@ -2465,7 +2469,7 @@ int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const 
         ZG_REQUIRE(u >= 0.0f && u < 1.0f, ZG_ERR_ARG, "debug_sample_rows: uniform %f outside [0,1)", u);
         h_u[b] = u;
     }
-    ZG_HIP(hipMemsetAsync(base, 0, fbytes, s));
+    ZG_HIP(hipMemsetAsync(d_filt, 0, filter_workspace_bytes(B), s));  // (the selection chain starts from a zeroed workspace and leaves it so)
     ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
     ZG_HIP(hipMemcpyAsync(d_u, h_u.data(), batch * 4, hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
@@ -2508,29 +2512,21 @@ int zg_debug_penalize_rows(const float* logits, size_t batch, size_t vocab, cons
                kPenMaxHistory);
     const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
     const size_t stride = std::max(longest, (size_t)1);
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t lbytes = up(batch * vocab * 4), hbytes = up(batch * stride * 4), pbytes = up((size_t)B * n_part * 4), bbytes = up(batch * 4);
     hipStream_t s = ctx().stream;
-    char* base = nullptr;
-    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&base), 2 * lbytes + hbytes + 2 * pbytes + bbytes + 256));
-    struct Free {
-        char* p;
-        ~Free() { (void)hipFree(p); }
-    } guard{base};
-    char* p = base;
-    float* d_logits = reinterpret_cast<float*>(p);
-    p += lbytes;
-    unsigned* d_counts = reinterpret_cast<unsigned*>(p);
-    p += lbytes;
-    int* d_hist = reinterpret_cast<int*>(p);
-    p += hbytes;
-    float* d_pv = reinterpret_cast<float*>(p);
-    p += pbytes;
-    int* d_pi = reinterpret_cast<int*>(p);
-    p += pbytes;
-    int* d_len = reinterpret_cast<int*>(p);
-    p += bbytes;
-    PenParams* d_par = reinterpret_cast<PenParams*>(p);
+    DevScratch ds;
+    float *d_logits, *d_pv;
+    unsigned* d_counts;
+    int *d_hist, *d_pi, *d_len;
+    PenParams* d_par;
+    ZG_TRY(ds.carve([&] {
+        d_logits = ds.take<float>(batch * vocab * 4);
+        d_counts = ds.take<unsigned>(batch * vocab * 4);
+        d_hist = ds.take<int>(batch * stride * 4);
+        d_pv = ds.take<float>((size_t)B * n_part * 4);
+        d_pi = ds.take<int>((size_t)B * n_part * 4);
+        d_len = ds.take<int>(batch * 4);
+        d_par = ds.take<PenParams>(sizeof(PenParams));
+    }));
     std::vector<int> h_hist(batch * stride, 0), h_len(batch);
     for (size_t b = 0; b < batch; ++b) {
         h_len[b] = (int)history_lens[b];
@@ -2600,15 +2596,8 @@ int zg_gpt_generate_fetch_many(zg_gpt* const* handles, size_t n_handles, size_t 
 int zg_gpt_generate_fetch(zg_gpt* g, size_t n_steps, size_t* out_tokens, size_t out_len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && out_tokens, ZG_ERR_ARG, "generate_fetch: null argument");
-    const size_t C = g->cfg.context_size, B = g->batch;
-    ZG_REQUIRE(n_steps <= C && out_len >= B * n_steps, ZG_ERR_SHAPE, "generate_fetch: out_tokens too short");
-    hipStream_t s = gs(g);
-    ZG_HIP(hipMemcpyAsync(g->h_ints, g->out_tokens, B * C * sizeof(int), hipMemcpyDeviceToHost, s));
-    ZG_HIP(hipStreamSynchronize(s));
-    ZG_TRY(check_fault(g));
-    for (size_t b = 0; b < B; ++b)
-        for (size_t i = 0; i < n_steps; ++i) out_tokens[b * n_steps + i] = (size_t)g->h_ints[b * C + i];
-    return ZG_OK;
+    ZG_REQUIRE(n_steps <= g->cfg.context_size && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_fetch: out_tokens too short");
+    return fetch_tokens(g, 0, n_steps, out_tokens);
 }
 
 int zg_gpt_generate_greedy(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens,

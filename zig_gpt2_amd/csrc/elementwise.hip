@@ -871,17 +871,17 @@ size_t score_workspace_bytes(int rows, int vocab) { return (size_t)rows * logpro
 ScoreWs score_workspace(void* base, int rows, int vocab) {
     const size_t slots = (size_t)rows * logprob_chunks(vocab);
     ScoreWs w;
-    w.sum = static_cast<float*>(base);
-    w.max = w.sum + slots;
-    w.val = w.max + slots;
-    w.idx = reinterpret_cast<int*>(w.val + slots * kLpTopMax);
+    w.lp.sum = static_cast<float*>(base);
+    w.max = w.lp.sum + slots;
+    w.lp.val = w.max + slots;
+    w.lp.idx = reinterpret_cast<int*>(w.lp.val + slots * kLpTopMax);
     return w;
 }
 
 int launch_score(const float* logits, int rows, int vocab, int row_stride, const int* top_n, const ScoreWs& ws, const ScoreTargets& tg, const LogprobRec& rec,
                  hipStream_t s) {
     ZG_REQUIRE(vocab >= 1 && vocab <= kLpChunk * kLpMaxChunks, ZG_ERR_UNSUPPORTED, "score: vocabulary of %d beyond %d", vocab, kLpChunk * kLpMaxChunks);
-    ZG_REQUIRE(logits && top_n && ws.sum && tg.tokens && tg.token_stride >= 1 && tg.n >= 1 && tg.past >= 0 && tg.row0 >= 0 && rec.logprob && rec.top_ids &&
+    ZG_REQUIRE(logits && top_n && ws.lp.sum && tg.tokens && tg.token_stride >= 1 && tg.n >= 1 && tg.past >= 0 && tg.row0 >= 0 && rec.logprob && rec.top_ids &&
                    rec.top_logprobs && rec.stride >= 1 && rows >= 1 && rows <= 65535 && row_stride >= vocab,
                ZG_ERR_ARG, "score: missing argument");
     const int nc = logprob_chunks(vocab);

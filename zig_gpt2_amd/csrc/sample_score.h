@@ -5,12 +5,12 @@
 //
 // No lm_head partials exist behind a GEMM, and a pass for the row maximum would read the block twice, so the maximum comes from
 // the chunks themselves (an online softmax over chunks):
-//   score_part_kernel     grid (chunks, rows): a workgroup owns kLpChunk consecutive columns of one row, four per lane, read once.
-//                         Its own maximum m_c (never below -3e38, as lp_row_max), the sum of expf(x - m_c) in
-//                         logprob_part_kernel's order, its best min(top_n, chunk) candidates by the same rounds.  Only columns
+//   score_part_kernel     grid (chunks, rows): a workgroup owns kLpChunk consecutive columns of one row, four per lane, read once
+//                         (lp_chunk_load).  Its own maximum m_c (never below -3e38, as lp_row_max), the sum of expf(x - m_c)
+//                         (lp_chunk_sum), its best min(top_n, chunk) candidates (lp_chunk_rounds).  Only columns
 //                         < vocab are read: the pad columns of the GEMM's 64-column grid never are.
 //   score_finish_kernel   one workgroup per row: m = max m_c; S = sum over c in index order of s_c * expf(m_c - m), by one lane,
-//                         logf once; the candidate lists merged as logprob_finish_kernel merges them.  Row t of sequence b predicts
+//                         logf once; the candidate lists merged and the column stored by lp_lists_merge_store.  Row t of sequence b predicts
 //                         position past + t + 1: the target is prompt[b][past + t + 1], the column written is past + t + 1; the
 //                         last row of a sequence has no target and writes nothing.
 // Plain vector stores, no atomics, no fences (everything crosses a launch boundary): the same inputs give the same bits on every
@@ -21,55 +21,23 @@ __global__ __launch_bounds__(256) void score_part_kernel(const float* __restrict
                                                          ScoreWs ws, int n_chunks) {
     __shared__ float s_mx[4], s_sum[4], s_v[4], s_ov[kLpTopMax];
     __shared__ int s_i[4], s_oi[kLpTopMax];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = blockIdx.x, r = blockIdx.y;
+    const int tid = threadIdx.x, c = blockIdx.x, r = blockIdx.y;
     const int top_n = lp_top_n(top_n_ptr);
-    const float* x = logits + (size_t)r * row_stride;
     float v[4];
-    unsigned taken = 0u;
+    const unsigned taken = lp_chunk_load(logits + (size_t)r * row_stride, vocab, c, v);
     float mx = -3.0e38f;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int i = c * kLpChunk + j * 256 + tid;
-        v[j] = i < vocab ? x[i] : -INFINITY;
-        if (i >= vocab) taken |= 1u << j;
-        mx = fmaxf(mx, v[j]);
-    }
+    for (int j = 0; j < 4; ++j) mx = fmaxf(mx, v[j]);
     mx = wave_allmax(mx);
-    if (lane == 0) s_mx[wave] = mx;
+    if ((tid & 63) == 0) s_mx[tid >> 6] = mx;
     __syncthreads();
     const float m_c = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
-    float e = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) e += (taken >> j) & 1u ? 0.0f : expf(v[j] - m_c);
-    e = wave_allsum(e);
-    if (lane == 0) s_sum[wave] = e;
-    __syncthreads();
     const size_t slot = (size_t)r * n_chunks + c;
-    const float chunk_sum = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-    for (int q = 0; q < top_n; ++q) {  // logprob_part_kernel's rounds
-        float bv = -INFINITY;
-        int bi = kLpNone;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = c * kLpChunk + j * 256 + tid;
-            if (!((taken >> j) & 1u) && lp_before(v[j], i, bv, bi)) { bv = v[j]; bi = i; }
-        }
-        lp_block_first(bv, bi, s_v, s_i);
-        if (tid == 0) {
-            s_ov[q] = bv;
-            s_oi[q] = bi;
-        }
-        const int loc = bi - c * kLpChunk;  // (kLpNone: no lane's)
-        if (bi != kLpNone && (loc & 255) == tid) taken |= 1u << ((loc >> 8) & 3);
-    }
-    __syncthreads();
+    const float chunk_sum = lp_chunk_sum(v, taken, m_c, s_sum);
+    lp_chunk_rounds(v, taken, c, top_n, s_v, s_i, s_ov, s_oi, ws.lp.val + slot * kLpTopMax, ws.lp.idx + slot * kLpTopMax);
     if (tid == 0) {
-        ws.sum[slot] = chunk_sum;
+        ws.lp.sum[slot] = chunk_sum;
         ws.max[slot] = m_c;
-    }
-    if (tid < top_n) {
-        ws.val[slot * kLpTopMax + tid] = s_ov[tid];
-        ws.idx[slot * kLpTopMax + tid] = s_oi[tid];
     }
 }
 
@@ -90,15 +58,8 @@ __global__ __launch_bounds__(256) void score_finish_kernel(const float* __restri
     int tok = tg.tokens[(size_t)b * tg.token_stride + min(pos, tg.token_stride - 1)];
     tok = (unsigned)tok < (unsigned)vocab ? tok : 0;
     const float* x = logits + (size_t)r * row_stride;
-    if (tid < n_chunks) {
-        s_sum[tid] = ws.sum[(size_t)r * n_chunks + tid];
-        s_max[tid] = ws.max[(size_t)r * n_chunks + tid];
-    }
-    for (int k = tid; k < n_chunks * top_n; k += 256) {
-        const int c = k / top_n, j = k - c * top_n;
-        s_cv[c * kLpTopMax + j] = ws.val[((size_t)r * n_chunks + c) * kLpTopMax + j];
-        s_ci[c * kLpTopMax + j] = ws.idx[((size_t)r * n_chunks + c) * kLpTopMax + j];
-    }
+    lp_lists_load(ws.lp, (size_t)r, n_chunks, top_n, s_sum, s_cv, s_ci);
+    if (tid < n_chunks) s_max[tid] = ws.max[(size_t)r * n_chunks + tid];
     __syncthreads();
     float m = wave_allmax(tid < n_chunks ? s_max[tid] : -3.0e38f);
     if ((tid & 63) == 0) s_mx[tid >> 6] = m;
@@ -111,31 +72,7 @@ __global__ __launch_bounds__(256) void score_finish_kernel(const float* __restri
         log_s = logf(total);
         lp_tok = (x[tok] - m) - log_s;
     }
-    // (logprob_finish_kernel's merge: the lists are in order and the chunks are index ranges)
-    int at = 0;
-    const bool mine = tid < n_chunks && top_n > 0;
-    float hv = mine ? s_cv[tid * kLpTopMax] : -INFINITY;
-    int hi = mine ? s_ci[tid * kLpTopMax] : kLpNone;
-    for (int q = 0; q < top_n; ++q) {
-        float bv = hv;
-        int bi = hi;
-        lp_block_first(bv, bi, s_v, s_i);
-        if (tid == 0) {
-            s_oi[q] = (unsigned)bi < (unsigned)vocab ? bi : 0;
-            s_ov[q] = (bv - m) - log_s;
-        }
-        if (mine && bi != kLpNone && hi == bi) {  // the winner's list moves on
-            ++at;
-            hv = at < top_n ? s_cv[tid * kLpTopMax + at] : -INFINITY;
-            hi = at < top_n ? s_ci[tid * kLpTopMax + at] : kLpNone;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) rec.logprob[out] = lp_tok;
-    if (tid < top_n) {
-        rec.top_ids[out * kLpTopMax + tid] = s_oi[tid];
-        rec.top_logprobs[out * kLpTopMax + tid] = s_ov[tid];
-    }
+    lp_lists_merge_store(n_chunks, top_n, vocab, m, log_s, lp_tok, s_cv, s_ci, s_v, s_i, s_ov, s_oi, rec, out);
 }
 
 // The B operand of the scoring lm_head on fp32 / B24 handles: the stored values of wte [V][K] split exactly into bf16 planes,

@@ -470,10 +470,8 @@ int launch_logprob(const float* logits, int batch, int vocab, const float* part_
 // record buffers receives the target's log-probability and the *top_n largest logits with theirs; the last row of a sequence
 // writes nothing.  Two launches; the row maximum comes from the chunks.  vocab <= 262144.
 struct ScoreWs {
-    float* sum;  // [rows][chunks] sum of exp(x - max[chunk]) by chunk
-    float* max;  // [rows][chunks] the chunk's own maximum
-    float* val;  // [rows][chunks][20] the chunk's largest values, in order
-    int* idx;    // ... and their indices
+    LogprobWs lp;  // over [rows][chunks]; sum: of exp(x - max[chunk])
+    float* max;    // [rows][chunks] the chunk's own maximum, in memory between lp.sum and lp.val
 };
 struct ScoreTargets {
     const int* tokens;  // [batch][token_stride], indexed by absolute position

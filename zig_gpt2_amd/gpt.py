@@ -227,24 +227,44 @@ class GPT:
             mat, stride = np.zeros((self.batch, 1), np.uint64), 1
         return ptr(mat), stride, ptr(lens), (mat, lens)
 
-    def _generate_pen(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior):
-        mat, lens, stride = self._prompts(prompts)
-        opt = _lib.SampleOptions(temp, top_k, top_p)
-        pp, pstride, plens, keep = self._token_lists(prior)
-        check(self._L.zg_gpt_generate_pen_enqueue(self.h, past_len, ptr(mat), stride, ptr(lens), n_steps, C.addressof(opt), C.addressof(pen), pp, pstride,
-                                                  plens, seed))
-        del keep
-
-    def _generate_logprobs(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, top_n):
-        """zg_gpt_generate_logprobs_enqueue: the generation of the same arguments with the log-probability stage (temp None: greedy)."""
+    def _generate(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=True):
+        """Every generation of this class: enqueue through the entry point its arguments ask for, then (fetch) return what the
+        public method returns.  past_len None: not a continuation.  temp None: greedy.  pen: `_penalties(...)`.  logprobs: top_n or
+        None.  With penalties and log-probabilities off the plain entry points run (zg_gpt_generate_greedy / _enqueue,
+        zg_gpt_generate_sample[_ex][_enqueue], zg_gpt_generate_from_enqueue), else zg_gpt_generate_pen_enqueue, else (logprobs)
+        zg_gpt_generate_logprobs_enqueue."""
         if pen is not None and temp is None:
             raise ValueError("penalties need a sampler: greedy picking with penalties is temp=1.0, top_k=1")
         mat, lens, stride = self._prompts(prompts)
+        head = (ptr(mat), stride, ptr(lens), n_steps)
         opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
-        pp, pstride, plens, keep = self._token_lists(prior if pen is not None else None)
-        check(self._L.zg_gpt_generate_logprobs_enqueue(self.h, past_len, ptr(mat), stride, ptr(lens), n_steps, None if opt is None else C.addressof(opt),
-                                                       None if pen is None else C.addressof(pen), pp, pstride, plens, seed, int(top_n)))
-        del keep
+        opt_p = None if opt is None else C.addressof(opt)
+        out = None
+        if logprobs is not None or pen is not None:
+            pp, pstride, plens, keep = self._token_lists(prior if pen is not None else None)
+            tail = (opt_p, None if pen is None else C.addressof(pen), pp, pstride, plens, seed)
+            if logprobs is not None:
+                check(self._L.zg_gpt_generate_logprobs_enqueue(self.h, past_len or 0, *head, *tail, int(logprobs)))
+            else:
+                check(self._L.zg_gpt_generate_pen_enqueue(self.h, past_len or 0, *head, *tail))
+            del keep
+        elif past_len is not None:
+            check(self._L.zg_gpt_generate_from_enqueue(self.h, past_len, *head, opt_p, seed))
+        elif fetch:  # the calls that enqueue and fetch in one
+            out = np.zeros((self.batch, n_steps), np.uint64)
+            if temp is None:
+                check(self._L.zg_gpt_generate_greedy(self.h, *head, ptr(out), out.size))
+            else:
+                self._sampled("generate_sample", "", head, temp, top_k, top_p, (seed, ptr(out), out.size))
+        elif temp is None:
+            check(self._L.zg_gpt_generate_enqueue(self.h, *head))
+        else:
+            self._sampled("generate_sample", "_enqueue", head, temp, top_k, top_p, (seed,))
+        if not fetch:
+            return None
+        if out is None:
+            out = self.generate_fetch(n_steps) if past_len is None else self.generate_fetch_range(past_len, n_steps)
+        return out if logprobs is None else (out,) + self.generate_fetch_logprobs(past_len or 0, n_steps, logprobs)
 
     def generate_fetch_logprobs(self, first, n, top_n):
         """zg_gpt_generate_fetch_logprobs of columns first .. first + n - 1: (logprobs [batch, n] float32 — NaN where the column
@@ -295,17 +315,10 @@ class GPT:
         """generate (src/main.zig:322-342), greedy; returns tokens [batch, n_steps].  logprobs=top_n (an int, 0 .. 20): the same
         tokens with the log-probability of every pick and its top_n alternatives — returns (tokens, logprobs,
         top_ids, top_logprobs) as generate_fetch_logprobs gives them."""
-        if logprobs is not None:
-            self._generate_logprobs(0, prompts, n_steps, None, 0, 0, 1.0, None, None, logprobs)
-            return (self.generate_fetch(n_steps),) + self.generate_fetch_logprobs(0, n_steps, logprobs)
-        mat, lens, stride = self._prompts(prompts)
-        out = np.zeros((self.batch, n_steps), np.uint64)
-        check(self._L.zg_gpt_generate_greedy(self.h, ptr(mat), stride, ptr(lens), n_steps, ptr(out), out.size))
-        return out
+        return self._generate(None, prompts, n_steps, None, 0, 0, 1.0, None, None, logprobs)
 
     def generate_enqueue(self, prompts, n_steps):
-        mat, lens, stride = self._prompts(prompts)
-        check(self._L.zg_gpt_generate_enqueue(self.h, ptr(mat), stride, ptr(lens), n_steps))
+        self._generate(None, prompts, n_steps, None, 0, 0, 1.0, None, None, None, fetch=False)
 
     def generate_fetch(self, n_steps):
         out = np.zeros((self.batch, n_steps), np.uint64)
@@ -326,19 +339,7 @@ class GPT:
         tokens below past_len count only when passed as `prior` (one list per row).  logprobs=top_n: as `generate`, for the
         columns past_len .. past_len + n_steps - 1."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
-        if logprobs is not None:
-            self._generate_logprobs(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
-            return (self.generate_fetch_range(past_len, n_steps),) + self.generate_fetch_logprobs(past_len, n_steps, logprobs)
-        if pen is not None:
-            if temp is None:
-                raise ValueError("penalties need a sampler: greedy picking with penalties is temp=1.0, top_k=1")
-            self._generate_pen(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior)
-            return self.generate_fetch_range(past_len, n_steps)
-        mat, lens, stride = self._prompts(prompts)
-        opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
-        check(self._L.zg_gpt_generate_from_enqueue(self.h, past_len, ptr(mat), stride, ptr(lens), n_steps,
-                                                   None if opt is None else C.addressof(opt), seed))
-        return self.generate_fetch_range(past_len, n_steps)
+        return self._generate(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
 
     def generate_sample(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
                         frequency_penalty=0.0, prior=None, logprobs=None):
@@ -348,27 +349,13 @@ class GPT:
         list per row, optional) followed by the row's prompt and picks so far (zg_gpt_generate_pen_enqueue; defaults: today's call).
         logprobs=top_n: as `generate` — of the row the sampler received, at temperature 1 and before truncation."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
-        if logprobs is not None:
-            self._generate_logprobs(0, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
-            return (self.generate_fetch(n_steps),) + self.generate_fetch_logprobs(0, n_steps, logprobs)
-        if pen is not None:
-            self._generate_pen(0, prompts, n_steps, temp, seed, top_k, top_p, pen, prior)
-            return self.generate_fetch(n_steps)
-        mat, lens, stride = self._prompts(prompts)
-        out = np.zeros((self.batch, n_steps), np.uint64)
-        self._sampled("generate_sample", "", (ptr(mat), stride, ptr(lens), n_steps), temp, top_k, top_p, (seed, ptr(out), out.size))
-        return out
+        return self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
 
     def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
                                 frequency_penalty=0.0, prior=None, logprobs=None):
-        """logprobs=top_n: with the log-probability stage; results through generate_fetch and generate_fetch_logprobs."""
+        """generate_sample without the fetch; results through generate_fetch and (logprobs=top_n) generate_fetch_logprobs."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
-        if logprobs is not None:
-            return self._generate_logprobs(0, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
-        if pen is not None:
-            return self._generate_pen(0, prompts, n_steps, temp, seed, top_k, top_p, pen, prior)
-        mat, lens, stride = self._prompts(prompts)
-        self._sampled("generate_sample", "_enqueue", (ptr(mat), stride, ptr(lens), n_steps), temp, top_k, top_p, (seed,))
+        self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=False)
 
     PROFILE_CLASSES = ["embed", "ln1_c_attn_kv", "attention", "merge_attn_proj_resid", "ln2_c_fc_gelu",
                        "mlp_proj_resid", "lnf_lm_head_argmax", "step_total"]
