@@ -272,6 +272,10 @@ enum {
                                     strip; fp32 / B24 weights: wte's bf16 planes and the slab workspace of that launch).  54 MB at
                                     GPT-2 124M whatever the batch.  Without it zg_gpt_score is ZG_ERR_UNSUPPORTED and
                                     the handle has bit for bit the layout and behaviour it has without this flag's existence */
+    ZG_GPT_STOP_GENERATE = 1 << 13, /* capture the decode graphs of zg_gpt_generate_stop_enqueue at create as well: the stop twins of
+                                      every graph with lm_head that create captures (the greedy ones, those of the other *_GENERATE
+                                      flags given beside it, their log-probability twins under ZG_GPT_LOGPROBS_GENERATE; the rule:
+                                      ZG_GPT_SAMPLED_GENERATE) */
     ZG_GPT_WEIGHTS_B24 = 1 << 8  /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
                                     value rounded to nearest even at 16 mantissa bits (never to inf), row r of an [out][in]
                                     matrix = [in bf16-shaped upper halves | in low bytes].  3/4 of fp32's weight bytes, 2^-17
@@ -575,6 +579,57 @@ int zg_gpt_score(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_
  * Allocates its workspace per call. */
 int zg_debug_score_rows(const float* logits, size_t rows, size_t vocab, size_t row_stride, const size_t* targets, size_t top_n, float* logprobs_out,
                         size_t* top_ids_out_or_null, float* top_logprobs_out_or_null);
+/* ---- Stop tokens and stop sequences in the device loop, with an early end.
+ * Matching.  Row b picks the tokens of columns p >= past_len + prompt_lens[b]; columns below that record prompt tokens.  The
+ * conditions are numbered over the concatenated list: j < n_ids is stop token ids[j], n_ids + k is stop sequence k (seq_lens[k]
+ * tokens at seqs + k * seq_stride).  Condition j matches at column p of row b when p is a picked column and either it is a stop
+ * token and the token recorded at p equals ids[j], or it is a stop sequence of L tokens, columns p - L + 1 .. p are ALL picked
+ * columns of the row and hold the L tokens of the sequence — a match never reaches into the prompt (OpenAI and vLLM match generated
+ * text only).  finish_col[b] is the lowest column at which any condition matches and reason[b] the lowest j matching there; a row
+ * that never matches has finish_col[b] = ZG_STOP_NONE and reason[b] = -1.  Once a row has finished its values do not change.
+ * Matching is exact integer comparison of recorded tokens: the same inputs give the same finish_col and reason on every run.
+ * The loop.  Rows stay in lock step and a finished row keeps decoding.  The stop stage is one more launch per step, last in the
+ * step's tail; it only reads, so every column below `end` holds, bit for bit, the token (and, with log-probabilities, the record)
+ * the same call without stop conditions leaves there.  When the last unfinished row finishes at column f the loop is fed no
+ * further: the generation ends at `end` (exclusive, absolute) with f + 1 <= end <= min(past_len + n_steps, f + 1 + lookahead + 64);
+ * if some row never finishes, end = past_len + n_steps.  `end` may differ from run to run inside that bound; nothing else may.
+ * Afterwards zg_gpt_cached_len == end, the caches hold positions < end, zg_gpt_generate_fetch / _fetch_range / _fetch_logprobs serve
+ * columns < end (columns from `end` on keep what earlier calls left there), and a continuation rolls back with past_len <= end as
+ * after any other call.  The host learns of the device's progress from two words in pinned memory that the stop kernel stores to;
+ * it feeds a piece of the loop (up to 64 steps) only while it is at most `lookahead` steps ahead of them, so the device never idles
+ * and never waits for the host, and no step costs a host round trip.  lookahead 0: the library's default. */
+#define ZG_STOP_MAX_IDS 16
+#define ZG_STOP_MAX_SEQS 8
+#define ZG_STOP_MAX_SEQ_LEN 16
+#define ZG_STOP_NONE ((size_t)-1)
+typedef struct {
+    const size_t* ids;      size_t n_ids;      /* stop tokens */
+    const size_t* seqs;     size_t seq_stride; /* [n_seqs][seq_stride] */
+    const size_t* seq_lens; size_t n_seqs;     /* 1..ZG_STOP_MAX_SEQ_LEN tokens each */
+    size_t lookahead;                          /* steps the host may run ahead of the device; 0 = the library's default */
+} zg_stop_conditions;
+/* zg_gpt_generate_logprobs_enqueue's arguments; logprobs == 0: no log-probability stage (top_n ignored).  stop NULL, or n_ids ==
+ * n_seqs == 0: exactly zg_gpt_generate_logprobs_enqueue (logprobs != 0) or zg_gpt_generate_pen_enqueue / _from_enqueue (logprobs ==
+ * 0) — the same graphs, no added launch, no pacing, end = past_len + n_steps.  n_ids > 16, n_seqs > 8, a sequence length of 0, above
+ * 16 or above seq_stride, a NULL array with a non-zero count, greedy with penalties: ZG_ERR_ARG; a stop token or sequence token >=
+ * vocab_size: ZG_ERR_SHAPE — all before anything is enqueued or the handle's state (zg_gpt_cached_len, the log-probability record)
+ * is touched.  With conditions the call does NOT return immediately: it returns when the last step it will run has been enqueued,
+ * at most lookahead + 64 steps of device work before the end.  Graphs of their own (ZG_GPT_STOP_GENERATE); the conditions live in
+ * device memory, one graph serves every set.  Does not allocate beyond that capture.  A stop generation runs without a stall strike
+ * against the side-stream prefetcher: an early end reaches it as the ordinary end of a generation. */
+int zg_gpt_generate_stop_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens,
+                                 size_t n_steps, const zg_sample_options* options_or_null, const zg_logit_penalties* penalties_or_null,
+                                 const size_t* prior_or_null, size_t prior_stride, const size_t* prior_lens_or_null, uint64_t seed,
+                                 int logprobs, size_t top_n, const zg_stop_conditions* stop_or_null);
+/* Drains the stream and reports `end`, finish_col [batch] and reason [batch] of the last generation, which must have been one with
+ * stop conditions: before any, or behind a generation without, ZG_ERR_ARG. */
+int zg_gpt_generate_stop_result(zg_gpt* g, size_t* end_out, size_t* finish_cols_out, int* reasons_out);
+/* Test entry: the stop kernel alone.  For s = 0 .. n_cols - 1 it is launched once per column, eagerly, over the caller's host
+ * tokens [batch <= 8][stride >= n_cols]: the pick of column s is tokens[b][s] and first_cols[b] plays past_len + prompt_lens[b].
+ * done_col_out: the highest finish column + 1, or 0 when some row never finishes.  The refusals of zg_gpt_generate_stop_enqueue on
+ * the conditions (a token of 2^31 - 1 or above standing for the vocabulary).  Needs zg_init only.  Allocates per call. */
+int zg_debug_stop_rows(const size_t* tokens, size_t batch, size_t stride, const size_t* first_cols, size_t n_cols,
+                       const zg_stop_conditions* stop, size_t* finish_cols_out, int* reasons_out, size_t* done_col_out);
 /* tokens of positions first .. first + n - 1 of the last generation(s): out_tokens [batch, n] */
 int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len);
 /* Test entry: the sampler kernels of zg_gpt_sample_ex on the caller's logits [batch <= 64, vocab <= 262144] (host or device, as

@@ -44,6 +44,12 @@ class LogitPenalties(C.Structure):
     _fields_ = [("repetition", C.c_float), ("presence", C.c_float), ("frequency", C.c_float)]
 
 
+class StopConditions(C.Structure):
+    """zg_stop_conditions of include/zgpt2.h."""
+
+    _fields_ = [("ids", vp), ("n_ids", sz), ("seqs", vp), ("seq_stride", sz), ("seq_lens", vp), ("n_seqs", sz), ("lookahead", sz)]
+
+
 class GptOptions(C.Structure):
     """zg_gpt_options of include/zgpt2.h."""
 
@@ -130,6 +136,9 @@ SIGNATURES = {
     "zg_gpt_generate_logprobs_enqueue": (C.c_int, [vp, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp, C.c_uint64, sz]),
     "zg_gpt_generate_fetch_logprobs": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, vp, sz]),
     "zg_debug_logprob_rows": (C.c_int, [vp, sz, sz, vp, sz, vp, vp, vp]),
+    "zg_gpt_generate_stop_enqueue": (C.c_int, [vp, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp, C.c_uint64, C.c_int, sz, vp]),
+    "zg_gpt_generate_stop_result": (C.c_int, [vp, szp, vp, vp]),
+    "zg_debug_stop_rows": (C.c_int, [vp, sz, sz, vp, sz, vp, vp, vp, szp]),
     "zg_gpt_score": (C.c_int, [vp, sz, vp, sz, sz, sz, vp, sz]),
     "zg_debug_score_rows": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, vp, vp]),
     "zg_gpt_time_kernel": (C.c_int, [vp, C.c_int, C.c_int, f32p, szp]),
@@ -150,7 +159,26 @@ GPT_TRUNCATED_GENERATE = 512
 GPT_PENALIZED_GENERATE = 1024
 GPT_LOGPROBS_GENERATE = 2048
 GPT_SCORE = 4096
+GPT_STOP_GENERATE = 8192
 LOGPROBS_TOP_MAX = 20
+STOP_MAX_IDS, STOP_MAX_SEQS, STOP_MAX_SEQ_LEN = 16, 8, 16
+STOP_NONE = (1 << 64) - 1
+
+
+def stop_conditions(stop_token_ids=None, stop=None, lookahead=0):
+    """zg_stop_conditions from a list of stop tokens and a list of stop sequences (token-id lists): (the structure, the arrays it
+    points into — keep them alive while it is in use)."""
+    import numpy as np
+
+    ids = np.ascontiguousarray([] if stop_token_ids is None else stop_token_ids, dtype=np.uint64).reshape(-1)
+    seqs = [np.ascontiguousarray(q, dtype=np.uint64).reshape(-1) for q in (stop or [])]
+    lens = np.ascontiguousarray([len(q) for q in seqs], dtype=np.uint64)
+    stride = max([len(q) for q in seqs] + [1])
+    mat = np.zeros((len(seqs), stride), np.uint64)
+    for k, q in enumerate(seqs):
+        mat[k, : len(q)] = q
+    c = StopConditions(ptr(ids) if ids.size else None, ids.size, ptr(mat) if seqs else None, stride, ptr(lens) if seqs else None, len(seqs), int(lookahead))
+    return c, (ids, mat, lens)
 BLOCK_SLOTS = ["ln_1_g", "ln_1_b", "c_attn_w", "c_attn_b", "c_proj_w", "c_proj_b",
                "ln_2_g", "ln_2_b", "c_fc_w", "c_fc_b", "mlp_proj_w", "mlp_proj_b"]
 TOP_SLOTS = ["wte", "wpe", "ln_f_g", "ln_f_b"]

@@ -22,6 +22,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <chrono>
 #include <cmath>
 #include <string>
 #include <thread>
@@ -38,12 +39,12 @@ constexpr size_t kSamplerModes = TWO_FILTERS + 1;
 static inline int filter_launches(SamplerMode m) { return m == TWO_FILTERS ? 6 : m == ONE_FILTER ? 3 : 0; }  // sample_filter.h: three levels per descent
 
 // Everything that follows lm_head in a decode step, as one value: the sampler, the penalty stage between lm_head and the sampler
-// (DESIGN §3.6), the log-probability stage behind the sampler — of a greedy step: behind lm_head.  The default is
-// the greedy step the reference's argmax loop runs.
+// (DESIGN §3.6), the log-probability stage behind the sampler — of a greedy step: behind lm_head —, the stop stage
+// behind everything.  The default is the greedy step the reference's argmax loop runs.
 struct StepTail {
     SamplerMode sampler = GREEDY;
-    bool pen = false, lp = false;
-    bool operator==(const StepTail& o) const { return sampler == o.sampler && pen == o.pen && lp == o.lp; }
+    bool pen = false, lp = false, stop = false;
+    bool operator==(const StepTail& o) const { return sampler == o.sampler && pen == o.pen && lp == o.lp && stop == o.stop; }
 };
 // The tail a step can have: nothing is drawn from a step without lm_head (the default tail), and a greedy pick has no penalties
 static inline StepTail normalized(StepTail t, bool with_logits) {
@@ -144,6 +145,20 @@ struct zg_gpt {
     float* h_lp;
     bool lp_valid;            // the last generation (or zg_gpt_score) recorded them: the record can be fetched
     size_t lp_top_n;          // ... with this many alternatives
+    // stop conditions (sample_stop.h): the conditions of the generation in flight, finish column and reason of every
+    // row (-1: none), and ONE pinned block: the staging mirror of the conditions, the way back of the two arrays, and the two
+    // words the stop kernel stores to (host.progress, host.done_col)
+    StopConds* stop;
+    int *stop_fin, *stop_reason;
+    struct StopPinned {
+        StopConds conds;
+        int fin[kStopMaxRows], reason[kStopMaxRows];
+        alignas(64) StopHost host;
+    }* h_stop;
+    bool gen_stop;            // the generation in flight has conditions: gen_pump paces itself and may end early
+    size_t gen_lookahead;     // ... at most this many steps ahead of host.progress before each piece
+    bool stop_valid;          // the last generation was one with conditions: zg_gpt_generate_stop_result can report it
+    size_t stop_end;          // ... and ended here
     // scoring (zg_gpt_score; sample_score.h), carved under ZG_GPT_SCORE only: the logits of one block of kScoreRows rows
     // [kScoreRows][sc_v64] (sc_v64 = the vocabulary on the GEMMs' 64-column grid), the chunk workspace of that block, and the lm_head
     // operand the whole-prompt GEMM cannot take from the weight region: bf16 weights — the last vocab % 64 rows of wte as a [64][E]
@@ -371,6 +386,10 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
             g->sc_gemm_ws = (float*)P(g->sc_gemm_ws_floats * 4);
         }
     }
+    // (and behind everything: the stop stage's conditions and its two words per row; every layout above is what it was)
+    g->stop = (StopConds*)P(sizeof(StopConds));
+    g->stop_fin = (int*)P(kStopMaxRows * 4);
+    g->stop_reason = (int*)P(kStopMaxRows * 4);
     g->state_bytes = (cv.off + 255) & ~(size_t)255;
 }
 
@@ -865,8 +884,31 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         return launch_logprob(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->part_val, g->part_idx, g->lm_grid, g->lm_grid, g->lp_top, g->lp_ws,
                               tokens, g->ctrl, g->prompt_len, g->lp_rec, s);
     };
+    // the stop stage, last: it learns the pick of its own step the way the log-probability stage does
+    auto stop = [&](const int* picks) {
+        StopArgs a{};
+        a.conds = g->stop;
+        a.tokens = g->out_tokens;
+        a.stride = (int)g->cfg.context_size;
+        a.prompt_len = g->prompt_len;
+        a.batch = (int)g->batch;
+        a.vocab = (int)g->cfg.vocab_size;
+        a.ctrl = g->ctrl;
+        a.col = -1;
+        a.picks = picks;
+        a.part_val = g->part_val;
+        a.part_idx = g->part_idx;
+        a.n_part = a.part_stride = g->lm_grid;
+        a.finish_col = g->stop_fin;
+        a.reason = g->stop_reason;
+        a.host = &g->h_stop->host;
+        return launch_stop(a, s);
+    };
     const StepTail tail = o.tail;
-    if (tail.sampler == GREEDY && tail.lp && with_logits && only < 0 && !rec) ZG_TRY(logprobs(nullptr));  // (the greedy graphs have no sampler node)
+    if (tail.sampler == GREEDY && with_logits && only < 0 && !rec) {  // (the greedy graphs have no sampler node)
+        if (tail.lp) ZG_TRY(logprobs(nullptr));
+        if (tail.stop) ZG_TRY(stop(nullptr));
+    }
     if (tail.sampler == GREEDY || !with_logits || only >= 0 || rec) return ZG_OK;
     // the penalties act on the raw logits (HF's order); the row-maximum partials both samplers start from are rebuilt behind them
     if (tail.pen)
@@ -878,6 +920,7 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         ZG_TRY(launch_sample_step(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, g->ctrl, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws,
                                   g->sampled, s));
     if (tail.lp) ZG_TRY(logprobs(g->sampled));
+    if (tail.stop) ZG_TRY(stop(g->sampled));
     return ZG_OK;
 }
 
@@ -1079,8 +1122,10 @@ struct StepKey {
     bool with_logits, multi;
     StepTail tail;
 };
-constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2;  // the radices of step_index
-size_t step_index(StepKey k) { return ((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp; }
+constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2 * 2;  // the radices of step_index
+size_t step_index(StepKey k) {
+    return (((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp) * 2 + k.tail.stop;
+}
 
 size_t bucket_of(size_t seq_len) { return (seq_len + 63) / 64 - 1; }
 
@@ -1135,7 +1180,8 @@ int capture_tail(zg_gpt* g, StepTail tail, size_t b0, size_t b1, hipStream_t s) 
 }
 
 // The tails whose graphs zg_gpt_create captures besides the default one, by the handle's flags: each *_GENERATE flag names the
-// samplers it is for, and ZG_GPT_LOGPROBS_GENERATE the twins with the log-probability stage of the default tail and of those
+// samplers it is for, ZG_GPT_LOGPROBS_GENERATE the twins with the log-probability stage of the default tail and of those, and
+// ZG_GPT_STOP_GENERATE the twins with the stop stage of all of these
 std::vector<StepTail> tails_of_flags(unsigned flags) {
     std::vector<StepTail> t;
     if (flags & ZG_GPT_SAMPLED_GENERATE) t.push_back({PLAIN, false, false});
@@ -1147,6 +1193,11 @@ std::vector<StepTail> tails_of_flags(unsigned flags) {
         const size_t n = t.size();
         t.push_back({GREEDY, false, true});
         for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, true});
+    }
+    if (flags & ZG_GPT_STOP_GENERATE) {  // the stop twins of the default tail and of everything above
+        const size_t n = t.size();
+        t.push_back({GREEDY, false, false, true});
+        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, t[i].lp, true});
     }
     return t;
 }
@@ -1261,6 +1312,7 @@ void release(zg_gpt* g) {
     if (g->h_ctrl) (void)hipHostFree(g->h_ctrl);
     if (g->h_ints) (void)hipHostFree(g->h_ints);
     if (g->h_lp) (void)hipHostFree(g->h_lp);
+    if (g->h_stop) (void)hipHostFree(g->h_stop);
     delete g;
 }
 
@@ -1318,7 +1370,10 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
     // (the mirror of the log-probability record: a fetch copies its columns through it)
     if (e == hipSuccess)
         e = hipHostMalloc(reinterpret_cast<void**>(&g->h_lp), batch * c.context_size * (1 + 2 * ZG_LOGPROBS_TOP_MAX) * sizeof(float), hipHostMallocDefault);
+    // (the stop stage's block: a few hundred bytes, always there)
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_stop), sizeof(*g->h_stop), hipHostMallocDefault);
     if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(control mirrors)", __FILE__, __LINE__);
+    memset(g->h_stop, 0, sizeof(*g->h_stop));
     static_assert(sizeof(StepCtrl) + sizeof(SampleParams) <= 256, "the fault word sits 256 bytes behind the control mirror");
     g->h_samp = reinterpret_cast<SampleParams*>(reinterpret_cast<char*>(g->h_ctrl) + 128);  // (same pinned block)
     g->fault = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g->h_ctrl) + 256);
@@ -1967,7 +2022,9 @@ static int check_sample_options(const zg_sample_options* o, const char* who) {
 // (zg_gpt_generate_enqueue_many): gen_begin — prompts, cache clearing, the whole-prompt pass, the prefetcher's start;
 // gen_pump — ONE graph launch (graph_steps decode steps) or one single step, false when nothing is left; gen_end — the
 // prefetcher's stop word and the record of the last pick.  After a successful gen_begin, gen_end must run (also on failure:
-// the prefetcher must not wait for steps that never come).
+// the prefetcher must not wait for steps that never come).  A generation with stop conditions is the same three parts:
+// gen_pump paces itself by the stop stage's progress word and feeds nothing once every row has finished (stop_pace), and gen_end
+// sets the handle's lengths to the column actually reached.
 // past > 0 (zg_gpt_generate_from_enqueue): the loop is entered at s = past — `prompts` are the new tokens of each row, device
 // prompt[b][past + i], prompt_len[b] = past + prompt_lens[b]; everything the embed kernel and gen_pump compare is absolute, so the
 // steps are the ones an uninterrupted generation would run at these positions.  The caches keep rows 0 .. past - 1 and the
@@ -1992,11 +2049,47 @@ struct GenRequest {
     // the log-probability stage behind every pick with top_n alternatives; lp_on false: the request is what it was
     bool lp_on = false;
     size_t top_n = 0;
+    // stop conditions, checked by the entry point (check_stop); stop_on false: the request is what it was
+    bool stop_on = false;
+    zg_stop_conditions stop{};
     GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, const zg_sample_options* opt_or_null = nullptr, uint64_t seed = 0,
                size_t past = 0)
         : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past), mode(opt_or_null ? PLAIN : GREEDY),
           opt(opt_or_null ? *opt_or_null : zg_sample_options{1.0f, 0, 1.0f}), seed(seed) {}
 };
+
+// Steps the host may be ahead of the stop stage's progress word before it feeds the next piece, where the caller names none:
+// the smallest value whose rate is inside the run-to-run spread of an unpaced loop (tools/bench_stop.py)
+constexpr size_t kStopLookahead = 16;
+
+// The refusals of a set of stop conditions (include/zgpt2.h), vocab standing for the first token that cannot occur
+static int check_stop(const zg_stop_conditions* c, size_t vocab, const char* who) {
+    ZG_REQUIRE(c != nullptr, ZG_ERR_ARG, "%s: stop conditions are null", who);
+    ZG_REQUIRE(c->n_ids <= ZG_STOP_MAX_IDS && c->n_seqs <= ZG_STOP_MAX_SEQS, ZG_ERR_ARG, "%s: %zu stop tokens / %zu stop sequences above %d / %d", who,
+               c->n_ids, c->n_seqs, ZG_STOP_MAX_IDS, ZG_STOP_MAX_SEQS);
+    ZG_REQUIRE((c->n_ids == 0 || c->ids) && (c->n_seqs == 0 || (c->seqs && c->seq_lens)), ZG_ERR_ARG, "%s: a null array with a non-zero count", who);
+    for (size_t k = 0; k < c->n_seqs; ++k)
+        ZG_REQUIRE(c->seq_lens[k] >= 1 && c->seq_lens[k] <= ZG_STOP_MAX_SEQ_LEN && c->seq_lens[k] <= c->seq_stride, ZG_ERR_ARG,
+                   "%s: stop sequence %zu has length %zu (1 .. %d, stride %zu)", who, k, c->seq_lens[k], ZG_STOP_MAX_SEQ_LEN, c->seq_stride);
+    for (size_t j = 0; j < c->n_ids; ++j) ZG_REQUIRE(c->ids[j] < vocab, ZG_ERR_SHAPE, "%s: stop token %zu >= vocab %zu", who, c->ids[j], vocab);
+    for (size_t k = 0; k < c->n_seqs; ++k)
+        for (size_t i = 0; i < c->seq_lens[k]; ++i)
+            ZG_REQUIRE(c->seqs[k * c->seq_stride + i] < vocab, ZG_ERR_SHAPE, "%s: token %zu of stop sequence %zu >= vocab %zu", who,
+                       c->seqs[k * c->seq_stride + i], k, vocab);
+    return ZG_OK;
+}
+
+// Checked conditions as the kernel reads them
+static void fill_stop(StopConds* d, const zg_stop_conditions& c) {
+    memset(d, 0, sizeof(*d));
+    d->n_ids = (int)c.n_ids;
+    d->n_seqs = (int)c.n_seqs;
+    for (size_t j = 0; j < c.n_ids; ++j) d->ids[j] = (int)c.ids[j];
+    for (size_t k = 0; k < c.n_seqs; ++k) {
+        d->seq_len[k] = (int)c.seq_lens[k];
+        for (size_t i = 0; i < c.seq_lens[k]; ++i) d->seq[k][i] = (int)c.seqs[k * c.seq_stride + i];
+    }
+}
 
 static int gen_begin(zg_gpt* g, const GenRequest& r) {
     const size_t n_steps = r.n_steps, past = r.past;
@@ -2034,7 +2127,17 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     size_t first = 0;
     if (g->pf_x != nullptr && min_prompt >= prefill_min())
         first = min_prompt < n_steps ? min_prompt : n_steps;
-    g->gen_tail = StepTail{r.mode, pen_on, r.lp_on};  // (normalized: pen_on only with a sampler, and the steps it is for have lm_head)
+    g->gen_tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on};  // (normalized: pen_on only with a sampler, and the steps it is for have lm_head)
+    g->stop_valid = false;
+    g->gen_stop = r.stop_on;
+    if (r.stop_on) {  // the conditions of this call; no row has finished; the stage has seen nothing (the stream is drained: the words are the host's)
+        fill_stop(&g->h_stop->conds, r.stop);
+        ZG_HIP(hipMemcpyAsync(g->stop, &g->h_stop->conds, sizeof(StopConds), hipMemcpyHostToDevice, s));
+        ZG_HIP(hipMemsetAsync(g->stop_fin, 0xff, kStopMaxRows * 4, s));
+        ZG_HIP(hipMemsetAsync(g->stop_reason, 0xff, kStopMaxRows * 4, s));
+        g->h_stop->host.progress = g->h_stop->host.done_col = 0u;
+        g->gen_lookahead = r.stop.lookahead ? std::min(r.stop.lookahead, C) : kStopLookahead;  // (beyond the context: never waits)
+    }
     if (r.mode != GREEDY) {
         g->gen_tail.sampler = fill_sample_params(g->h_samp, V, r.opt, r.seed);
         ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
@@ -2078,11 +2181,49 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     return ZG_OK;
 }
 
+// A stop generation before each piece it feeds: *ended when every row has finished — nothing more is fed —, else
+// wait while the host is more than gen_lookahead steps ahead of the stop stage.  The stage counts steps with lm_head only, so the
+// steps below gen_min_prompt (the default tail) are not paced over.  progress is read BEFORE done_col and the kernel stores them
+// the other way round: a done_col still 0 then means that the finishing step had not announced itself when progress was read, which
+// is what bounds `end`.  The wait is bounded by the device's state, not by a count: whenever the word has stood still over 16 polls
+// the stream is asked, and a drained or failed stream ends the wait — a faulted device ends the call instead of spinning the host.
+static int stop_pace(zg_gpt* g, hipStream_t s, bool* ended) {
+    StopHost* const h = &g->h_stop->host;
+    *ended = false;
+    unsigned seen = ~0u;  // progress at the last look at the stream
+    for (unsigned polls = 0;; ++polls) {
+        const unsigned p = __atomic_load_n(&h->progress, __ATOMIC_ACQUIRE);
+        const unsigned d = __atomic_load_n(&h->done_col, __ATOMIC_ACQUIRE);
+        if (d != 0u) {
+            *ended = true;
+            return ZG_OK;
+        }
+        if (g->gen_pos <= std::max((size_t)p, g->gen_min_prompt) + g->gen_lookahead) return ZG_OK;
+        if (polls < 64) continue;  // (a short wait costs no system call)
+        if (polls % 16 == 0) {  // the stream is asked only while the word stands still: a healthy device moves it every step
+            if (p == seen) {
+                const hipError_t q = hipStreamQuery(s);
+                if (q != hipErrorNotReady) {
+                    if (q != hipSuccess) return hip_fail(q, "hipStreamQuery(stop generation)", __FILE__, __LINE__);
+                    if (__atomic_load_n(&h->progress, __ATOMIC_ACQUIRE) == p) return ZG_OK;  // drained and nothing moved: nothing will
+                }
+            }
+            seen = p;
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+}
+
 static int gen_pump(zg_gpt* g, bool* more) {
     hipStream_t s = gs(g);
     const size_t C = g->cfg.context_size, n_steps = g->gen_n, st = g->gen_pos;
     *more = false;
     if (st >= n_steps) return ZG_OK;
+    if (g->gen_stop && st > g->gen_min_prompt) {  // (behind the first step with lm_head: nothing can have finished before)
+        bool ended = false;
+        ZG_TRY(stop_pace(g, s, &ended));
+        if (ended) return ZG_OK;
+    }
     const size_t K = ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) ? 1 : g->graph_steps;
     // ZGPT2_SYNC_EVERY=n (profiling only): drain the stream every n steps — rocprofv3's counter collection has crashed
     // on this stack when tens of thousands of dispatches were queued ahead of it
@@ -2118,6 +2259,10 @@ static int gen_end(zg_gpt* g, int rs) {
     ZG_TRY(pf_stop(g, s));  // also after a failed launch: the prefetcher must not wait for steps that never come
     ZG_TRY(rs);
     ZG_TRY(launch_embed_step(embed_args(g, 1), s));  // record the pick of the last step
+    if (g->gen_stop) {  // the column actually reached: the one place that corrects what gen_begin set up front
+        g->gen_n = g->cached_len = g->kv_dirty_hi = g->stop_end = g->gen_pos;
+        g->stop_valid = true;
+    }
     g->steps_enqueued = g->gen_n;
     return ZG_OK;
 }
@@ -2266,6 +2411,117 @@ int zg_gpt_generate_logprobs_enqueue(zg_gpt* g, size_t past_len, const size_t* p
     r.top_n = top_n;
     if (pen) ZG_TRY(request_penalties(g, r, pen, prior, prior_stride, prior_lens, "generate_logprobs"));
     return gen_run(&g, 1, r);
+}
+
+// zg_gpt_generate_logprobs_enqueue / _pen_enqueue / _from_enqueue with the stop stage: one more node, last in the tail, of
+// graphs of their own (StepTail.stop); the conditions live in device memory.  No conditions: the request is one of theirs.
+int zg_gpt_generate_stop_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                 const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
+                                 const size_t* prior_lens, uint64_t seed, int logprobs, size_t top_n, const zg_stop_conditions* stop) {
+    ZG_TRY(require_init());
+    const char* who = "generate_stop";
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null argument", who);
+    if (opt) ZG_TRY(check_sample_options(opt, who));
+    ZG_REQUIRE(opt || !pen, ZG_ERR_ARG, "%s: penalties without sampler options (greedy picking with penalties is top_k = 1)", who);
+    GenRequest r(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len);
+    if (logprobs) {
+        r.lp_on = true;
+        r.top_n = top_n;
+    }
+    if (pen) ZG_TRY(request_penalties(g, r, pen, prior, prior_stride, prior_lens, who));
+    if (stop && (stop->n_ids || stop->n_seqs)) {
+        ZG_REQUIRE(g->batch <= (size_t)kStopMaxRows, ZG_ERR_UNSUPPORTED, "%s: batch %zu above %d", who, g->batch, kStopMaxRows);
+        ZG_TRY(check_stop(stop, g->cfg.vocab_size, who));
+        r.stop_on = true;
+        r.stop = *stop;
+    }
+    return gen_run(&g, 1, r);
+}
+
+int zg_gpt_generate_stop_result(zg_gpt* g, size_t* end_out, size_t* finish_cols_out, int* reasons_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && end_out && finish_cols_out && reasons_out, ZG_ERR_ARG, "generate_stop_result: null argument");
+    ZG_REQUIRE(g->stop_valid, ZG_ERR_ARG, "generate_stop_result: the last generation had no stop conditions");
+    hipStream_t s = gs(g);
+    ZG_HIP(hipMemcpyAsync(g->h_stop->fin, g->stop_fin, g->batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(g->h_stop->reason, g->stop_reason, g->batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    *end_out = g->stop_end;
+    for (size_t b = 0; b < g->batch; ++b) {
+        const int f = g->h_stop->fin[b];
+        finish_cols_out[b] = f < 0 ? ZG_STOP_NONE : (size_t)f;
+        reasons_out[b] = f < 0 ? -1 : g->h_stop->reason[b];
+    }
+    return ZG_OK;
+}
+
+// The stop kernel alone on the caller's token rows (tests): one eager launch per column, the pick of column s being tokens[b][s].
+// Allocates per call: the device scratch, and the pinned words the kernel stores to.
+int zg_debug_stop_rows(const size_t* tokens, size_t batch, size_t stride, const size_t* first_cols, size_t n_cols, const zg_stop_conditions* stop,
+                       size_t* finish_cols_out, int* reasons_out, size_t* done_col_out) {
+    ZG_TRY(require_init());
+    const size_t lim = 0x7fffffff;
+    ZG_REQUIRE(tokens && first_cols && finish_cols_out && reasons_out && done_col_out && batch >= 1 && batch <= (size_t)kStopMaxRows && n_cols >= 1 &&
+                   n_cols <= stride && stride <= (size_t)1 << 20,
+               ZG_ERR_ARG, "debug_stop_rows: bad argument");
+    ZG_TRY(check_stop(stop, lim, "debug_stop_rows"));
+    std::vector<int> h_tok(batch * stride), h_first(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        h_first[b] = (int)std::min(first_cols[b], lim);
+        for (size_t i = 0; i < n_cols; ++i) {
+            ZG_REQUIRE(tokens[b * stride + i] < lim, ZG_ERR_SHAPE, "debug_stop_rows: token %zu", tokens[b * stride + i]);
+            h_tok[b * stride + i] = (int)tokens[b * stride + i];
+        }
+    }
+    StopConds h_conds;
+    fill_stop(&h_conds, *stop);
+    struct Pinned {
+        StopHost* p = nullptr;
+        ~Pinned() { (void)hipHostFree(p); }
+    } host;
+    ZG_HIP(hipHostMalloc(reinterpret_cast<void**>(&host.p), sizeof(StopHost), hipHostMallocDefault));
+    host.p->progress = host.p->done_col = 0u;
+    hipStream_t s = ctx().stream;
+    DevScratch ds;
+    StopArgs a{};
+    int *d_tok, *d_first;
+    StopConds* d_conds;
+    ZG_TRY(ds.carve([&] {
+        d_tok = ds.take<int>(batch * stride * 4);
+        d_first = ds.take<int>(batch * 4);
+        d_conds = ds.take<StopConds>(sizeof(StopConds));
+        a.finish_col = ds.take<int>(batch * 4);
+        a.reason = ds.take<int>(batch * 4);
+    }));
+    ZG_HIP(hipMemcpyAsync(d_tok, h_tok.data(), batch * stride * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_first, h_first.data(), batch * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_conds, &h_conds, sizeof(StopConds), hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemsetAsync(a.finish_col, 0xff, batch * 4, s));
+    ZG_HIP(hipMemsetAsync(a.reason, 0xff, batch * 4, s));
+    a.conds = d_conds;
+    a.tokens = d_tok;
+    a.stride = (int)stride;
+    a.prompt_len = d_first;
+    a.batch = (int)batch;
+    a.vocab = (int)lim;
+    a.pick_from_record = 1;
+    a.host = host.p;
+    for (size_t c = 0; c < n_cols; ++c) {
+        a.col = (int)c;
+        ZG_TRY(launch_stop(a, s));
+    }
+    std::vector<int> fin(batch), reason(batch);
+    ZG_HIP(hipMemcpyAsync(fin.data(), a.finish_col, batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(reason.data(), a.reason, batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_REQUIRE(host.p->progress == (unsigned)n_cols, ZG_ERR_HIP, "debug_stop_rows: the kernel reported column %u of %zu", host.p->progress, n_cols);
+    for (size_t b = 0; b < batch; ++b) {
+        finish_cols_out[b] = fin[b] < 0 ? ZG_STOP_NONE : (size_t)fin[b];
+        reasons_out[b] = fin[b] < 0 ? -1 : reason[b];
+    }
+    *done_col_out = host.p->done_col;
+    return ZG_OK;
 }
 
 int zg_gpt_generate_fetch_logprobs(zg_gpt* g, size_t first, size_t n, size_t top_n, float* logprobs_out, size_t logprobs_len, size_t* top_ids_out,

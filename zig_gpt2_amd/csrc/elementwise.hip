@@ -561,6 +561,7 @@ __global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vo
 #include "sample_penalty.h"
 #include "sample_logprob.h"
 #include "sample_score.h"
+#include "sample_stop.h"
 
 inline int grid_for(size_t n, int block = 256, int cap = 2048) {
     size_t g = (n + block - 1) / block;
@@ -888,6 +889,15 @@ int launch_score(const float* logits, int rows, int vocab, int row_stride, const
     hipLaunchKernelGGL(score_part_kernel, dim3(nc, rows), dim3(256), 0, s, logits, vocab, row_stride, top_n, ws, nc);
     ZG_HIP(hipGetLastError());
     hipLaunchKernelGGL(score_finish_kernel, dim3(rows), dim3(256), 0, s, logits, vocab, row_stride, top_n, ws, nc, tg, rec);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_stop(const StopArgs& a, hipStream_t s) {
+    ZG_REQUIRE(a.conds && a.tokens && a.prompt_len && a.finish_col && a.reason && a.stride >= 1 && a.batch >= 1 && a.batch <= kStopMaxRows && a.vocab >= 1 &&
+                   (a.col >= 0 ? a.col < a.stride : a.ctrl != nullptr) && (a.picks || a.pick_from_record || (a.part_val && a.part_idx && a.n_part >= 1)),
+               ZG_ERR_ARG, "stop stage: missing argument");
+    hipLaunchKernelGGL(stop_step_kernel, dim3(1), dim3(a.batch > 4 ? 512 : 256), 0, s, a);  // one wave per row
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

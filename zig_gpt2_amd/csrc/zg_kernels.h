@@ -482,6 +482,39 @@ size_t score_workspace_bytes(int rows, int vocab);
 ScoreWs score_workspace(void* base, int rows, int vocab);
 int launch_score(const float* logits, int rows, int vocab, int row_stride, const int* top_n, const ScoreWs& ws, const ScoreTargets& tg, const LogprobRec& rec,
                  hipStream_t s);
+// The stop stage, last in the tail of a step (sample_stop.h; include/zgpt2.h zg_stop_conditions): one launch, one wave per row
+// (batch <= kStopMaxRows).  The conditions live in device memory, so one captured launch serves every set.  finish_col / reason
+// [batch]: -1 while a row has none, written once.  host (pinned, optional): progress = column + 1 every launch, done_col = the
+// highest finish column + 1 once every row has one — stored by the kernel itself, read by the host without a copy.
+constexpr int kStopMaxIds = 16, kStopMaxSeqs = 8, kStopMaxSeqLen = 16, kStopMaxRows = 8;  // ZG_STOP_MAX_* of the header
+struct StopConds {
+    int n_ids, n_seqs;
+    int ids[kStopMaxIds];
+    int seq_len[kStopMaxSeqs];
+    int seq[kStopMaxSeqs][kStopMaxSeqLen];
+};
+struct StopHost {
+    unsigned progress;  // columns the stage has seen: the last launch's column + 1
+    unsigned done_col;  // 0 until every row has finished
+};
+struct StopArgs {
+    const StopConds* conds;
+    const int* tokens;       // [batch][stride] the loop's record (columns below the one in flight)
+    int stride;
+    const int* prompt_len;   // [batch] first picked column of a row
+    int batch, vocab;
+    const StepCtrl* ctrl;    // the column in flight is ctrl->seq_len - 1 ...
+    int col;                 // ... unless this is >= 0 (zg_debug_stop_rows)
+    const int* picks;        // [batch] the sampler's draw of this step; null: ...
+    int pick_from_record;    // ... tokens[b][column] (zg_debug_stop_rows), or the argmax of the partials (greedy)
+    const float* part_val;
+    const int* part_idx;
+    int n_part, part_stride;
+    int* finish_col;
+    int* reason;
+    StopHost* host;
+};
+int launch_stop(const StopArgs& a, hipStream_t s);
 // wte [V][K] (fp32 or B24) -> its exact bf16 planes, plane-major [3][V64][K] with zero rows behind row V - 1: the weight operand of
 // the scoring lm_head on handles whose whole-prompt GEMMs read weight planes
 int launch_wte_planes(const void* wte, int weight_type, size_t V, size_t V64, int K, bf16_t* out, hipStream_t s);

@@ -32,7 +32,7 @@ class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
                  sampled_generate=False, weights_b24=False, truncated_generate=False, penalized_generate=False, logprobs_generate=False,
-                 score=False):
+                 score=False, stop_generate=False):
         """share_weights_with / own_stream / stream_priority: zg_gpt_options of zg_gpt_create_ex (a handle of an independent
         prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config).
         weights_b24: matrices stored as 24-bit floats (ZG_GPT_WEIGHTS_B24: each fp32 weight rounded to 16 mantissa bits, 3/4 of
@@ -40,7 +40,8 @@ class GPT:
         at create (ZG_GPT_TRUNCATED_GENERATE) instead of when the first such generation begins; penalized_generate: the same for
         the graphs of generations with repetition / presence / frequency penalties (ZG_GPT_PENALIZED_GENERATE);
         logprobs_generate: the same for the log-probability twins of every graph create captures (ZG_GPT_LOGPROBS_GENERATE).
-        score: carve what `score` / `loglikelihood` need (ZG_GPT_SCORE); without it they raise ZG_ERR_UNSUPPORTED."""
+        score: carve what `score` / `loglikelihood` need (ZG_GPT_SCORE); without it they raise ZG_ERR_UNSUPPORTED.
+        stop_generate: the stop twins of every graph create captures (ZG_GPT_STOP_GENERATE), as the other *_generate flags."""
         self.config, self.batch = config, batch
         L = _lib.load()
         flags = (_lib.GPT_WEIGHTS_F32 if weights_f32 else 0) | (0 if use_graph else _lib.GPT_NO_GRAPH)
@@ -55,6 +56,7 @@ class GPT:
         flags |= _lib.GPT_PENALIZED_GENERATE if penalized_generate else 0
         flags |= _lib.GPT_LOGPROBS_GENERATE if logprobs_generate else 0
         flags |= _lib.GPT_SCORE if score else 0
+        flags |= _lib.GPT_STOP_GENERATE if stop_generate else 0
         cfg = _lib.GptConfig(config.vocab_size, config.context_size, config.n_layer, config.n_heads, config.n_embed)
         h = C.c_void_p()
         if share_weights_with is None and not own_stream:
@@ -227,6 +229,34 @@ class GPT:
             mat, stride = np.zeros((self.batch, 1), np.uint64), 1
         return ptr(mat), stride, ptr(lens), (mat, lens)
 
+    def _generate_stop(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead):
+        """A generation with stop conditions (zg_gpt_generate_stop_enqueue): what `_generate` returns, cut at `end` —
+        columns past_len .. end - 1.  `stop_result()` tells where every row finished and why."""
+        if pen is not None and temp is None:
+            raise ValueError("penalties need a sampler: greedy picking with penalties is temp=1.0, top_k=1")
+        past = past_len or 0
+        mat, lens, stride = self._prompts(prompts)
+        opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
+        pp, pstride, plens, keep = self._token_lists(prior if pen is not None else None)
+        conds, keep_conds = _lib.stop_conditions(stop_token_ids, stop, lookahead)
+        check(self._L.zg_gpt_generate_stop_enqueue(self.h, past, ptr(mat), stride, ptr(lens), n_steps, None if opt is None else C.addressof(opt),
+                                                   None if pen is None else C.addressof(pen), pp, pstride, plens, seed, int(logprobs is not None),
+                                                   int(logprobs or 0), C.addressof(conds)))
+        del keep, keep_conds
+        n = self.stop_result()[0] - past if conds.n_ids or conds.n_seqs else n_steps  # (no conditions: the plain call ran)
+        out = self.generate_fetch_range(past, n)
+        return out if logprobs is None else (out,) + self.generate_fetch_logprobs(past, n, logprobs)
+
+    def stop_result(self):
+        """zg_gpt_generate_stop_result of the last generation with stop conditions: (end, finish_cols, reasons) — `end` the absolute
+        column the generation ended at (exclusive), per row the absolute column it finished at (None: it never did) and the index
+        of the condition that matched there (stop tokens first, then the sequences; -1: none)."""
+        end = C.c_size_t()
+        cols = np.zeros(self.batch, np.uint64)
+        reasons = np.zeros(self.batch, np.int32)
+        check(self._L.zg_gpt_generate_stop_result(self.h, C.byref(end), ptr(cols), ptr(reasons)))
+        return end.value, [None if int(c) == _lib.STOP_NONE else int(c) for c in cols], [int(r) for r in reasons]
+
     def _generate(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=True):
         """Every generation of this class: enqueue through the entry point its arguments ask for, then (fetch) return what the
         public method returns.  past_len None: not a continuation.  temp None: greedy.  pen: `_penalties(...)`.  logprobs: top_n or
@@ -311,10 +341,15 @@ class GPT:
     def _prompts(self, prompts):
         return _pack_prompts(prompts, self.batch)
 
-    def generate(self, prompts, n_steps, logprobs=None):
+    def generate(self, prompts, n_steps, logprobs=None, stop_token_ids=None, stop=None, lookahead=0):
         """generate (src/main.zig:322-342), greedy; returns tokens [batch, n_steps].  logprobs=top_n (an int, 0 .. 20): the same
         tokens with the log-probability of every pick and its top_n alternatives — returns (tokens, logprobs,
-        top_ids, top_logprobs) as generate_fetch_logprobs gives them."""
+        top_ids, top_logprobs) as generate_fetch_logprobs gives them.  stop_token_ids (token ids) / stop (a list of token-id lists):
+        the generation ends soon after every row has picked a stop token or completed a stop sequence, and what is
+        returned is cut at its end: columns 0 .. end - 1, the same tokens as without the conditions; `stop_result()` tells where
+        every row finished.  lookahead: steps the host may run ahead of the device (0: the default)."""
+        if stop_token_ids is not None or stop is not None:
+            return self._generate_stop(None, prompts, n_steps, None, 0, 0, 1.0, None, None, logprobs, stop_token_ids, stop, lookahead)
         return self._generate(None, prompts, n_steps, None, 0, 0, 1.0, None, None, logprobs)
 
     def generate_enqueue(self, prompts, n_steps):
@@ -332,23 +367,29 @@ class GPT:
         return out
 
     def generate_from(self, past_len, prompts, n_steps, temp=None, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
-                      frequency_penalty=0.0, prior=None, logprobs=None):
+                      frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0):
         """generate entered at position past_len (zg_gpt_generate_from_enqueue): `prompts` are the new tokens of each row, fed
         behind the past_len cached positions; returns the tokens of positions past_len .. past_len + n_steps - 1 ([batch, n_steps]).
         temp=None: greedy; otherwise the sampler of generate_sample (top_k / top_p as there).  Penalties as generate_sample; the
         tokens below past_len count only when passed as `prior` (one list per row).  logprobs=top_n: as `generate`, for the
-        columns past_len .. past_len + n_steps - 1."""
+        columns past_len .. past_len + n_steps - 1.  stop_token_ids / stop / lookahead: as `generate`; the columns are absolute and
+        what is returned is columns past_len .. end - 1."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if stop_token_ids is not None or stop is not None:
+            return self._generate_stop(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead)
         return self._generate(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
 
     def generate_sample(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
-                        frequency_penalty=0.0, prior=None, logprobs=None):
+                        frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0):
         """generate (src/main.zig:322-342) as the reference runs it — every token behind the prompt drawn by GPT.sample — with the
         loop on the device; the tokens of the host loop over `sample(T, tok, temp, seed=seed)`.  top_k / top_p: as `sample`.
         repetition_penalty / presence_penalty / frequency_penalty: on the tokens the row holds when a pick is drawn — `prior` (one
         list per row, optional) followed by the row's prompt and picks so far (zg_gpt_generate_pen_enqueue; defaults: today's call).
-        logprobs=top_n: as `generate` — of the row the sampler received, at temperature 1 and before truncation."""
+        logprobs=top_n: as `generate` — of the row the sampler received, at temperature 1 and before truncation.
+        stop_token_ids / stop / lookahead: as `generate`."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if stop_token_ids is not None or stop is not None:
+            return self._generate_stop(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead)
         return self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
 
     def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
