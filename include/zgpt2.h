@@ -399,13 +399,47 @@ typedef struct zg_tap_entry {
     unsigned flags, pad;
 } zg_tap_entry;
 enum { ZG_TAP_X = 0, ZG_TAP_XP, ZG_TAP_XST, ZG_TAP_Q, ZG_TAP_K, ZG_TAP_K_LO, ZG_TAP_V, ZG_TAP_V_LO, ZG_TAP_PART, ZG_TAP_AP, ZG_TAP_H4, ZG_TAP_HP,
-       ZG_TAP_LOGITS, ZG_TAP_PART_VAL, ZG_TAP_PART_IDX };
+       ZG_TAP_LOGITS, ZG_TAP_PART_VAL, ZG_TAP_PART_IDX,
+       /* zg_debug_gpt_pass_taps only */ ZG_TAP_A, ZG_TAP_QKV_KV, ZG_TAP_PLAN, ZG_TAP_GEO };
 enum { ZG_TAP_F32 = 0, ZG_TAP_F16, ZG_TAP_BF16, ZG_TAP_U8, ZG_TAP_I32 };
 #define ZG_TAP_FUSED 1u
 #define ZG_TAP_NOT_WRITTEN 2u
 #define ZG_TAP_INFO_INTS 9
 int zg_debug_gpt_step_taps(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, void* arena_out, size_t arena_bytes, size_t* arena_used,
                            zg_tap_entry* table_out, size_t table_len, size_t* n_entries, int* info, size_t n_info);
+/* Diagnostic (tests): the whole-prompt pass with every launch tapped — zg_gpt_extend(past_len, tokens, compute_logits, logits_out)
+ * (past_len 0: zg_gpt_prefill), or with score != 0 zg_gpt_score(past_len, tokens, top_n, logits_out [batch][n][vocab]) on a
+ * ZG_GPT_SCORE handle — with the arguments, plans and launches of the plain call; behind each launch device-to-device copies on
+ * the same stream save what it wrote, raw.  The same zg_tap_entry table as zg_debug_gpt_step_taps, in launch order.  arena_out ==
+ * NULL: nothing runs; *arena_used and *n_entries report an upper bound of what a call needs (a call returns what it used).
+ * Rows are ordered (sequence, new position): M = batch * n_tokens rows, row b n + t at position past_len + t.  A plane buffer is
+ * row-major [M][3 K] bf16: the hi, mid and lo plane of a row side by side.  T = min(context, past_len + n_tokens +
+ * ZG_PASS_TAP_ROWS_BEHIND).  Classes and what is tapped (layer: the Block; class 7: the 256-row block of the score stage):
+ *   -1  in front of c_attn: the layer's K / V rows of positions < T as the pass finds them, [B][H][T][64] in storage format
+ *       (ZG_TAP_K / _V and, B24, ZG_TAP_K_LO / _V_LO as in the step taps); the rows at and behind past_len are what an earlier
+ *       call or the clearing left
+ *    0  embed: x = pf_x [M][E] fp32
+ *    1  the first LayerNorm + split: a = pf_a [M][3 E] planes (the ln_1 planes of later Blocks are class 6 of the Block before)
+ *    2  c_attn: its plan; q [M][E] fp32 and qkv_kv [M][2 E] fp32, the q and the k | v columns of pf_qkv — ZG_TAP_NOT_WRITTEN on
+ *       qkv_kv where the epilogue stores those columns to the cache alone (the persistent GEMM with an fp32 cache); the K / V
+ *       rows of positions < T, which now hold the appended rows past_len .. past_len + n_tokens - 1
+ *    3  attention (+ merge): geo = 3 ints — the geometry word (key tiles per range | max splits << 8 | query groups << 16), the
+ *       kernel (0 the whole-prompt kernel, 1 / 2 / 3 the continuation kernel for an fp32 / fp16 / B24 cache), merge kernel
+ *       launched; a = pf_a [M][3 E] planes of the heads
+ *    4  attn c_proj + residual (and its tail): its plan; x; a = the ln_2 planes
+ *    5  c_fc + GELU + split: its plan; hp = pf_h [M][12 E] planes
+ *    6  mlp c_proj + residual (and its tail): its plan; x; a = the next Block's ln_1 planes, ZG_TAP_NOT_WRITTEN in the last Block
+ *    7  score: layer 0 first a = the ln_f planes of all rows; then per block each lm_head GEMM's plan (fp32 / B24 weights: one;
+ *       bf16: the whole 64-row groups of wte, then the strip) and logits = the block's rows of sc_logits [rows][V64] fp32
+ * plan: the ZG_PREFILL_PLAN_INTS ints of zg_debug_prefill_plan, of the plan the launch used.  A pass whose last Block stops behind
+ * its cache append (compute_logits == 0) taps nothing behind class 2 of that Block.
+ * info[ZG_PASS_INFO_INTS]: activation planes multiplied (2 or 3), KV mode, weight type, pf_ws_floats, stream-K operands given
+ * to c_attn, V64 (the vocabulary on the score GEMMs' 64-column grid), rows of a score block. */
+#define ZG_PASS_TAP_ROWS_BEHIND 4
+#define ZG_PASS_INFO_INTS 7
+int zg_debug_gpt_pass_taps(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits, int score, size_t top_n,
+                           float* logits_out, size_t logits_len, void* arena_out, size_t arena_bytes, size_t* arena_used, zg_tap_entry* table_out,
+                           size_t table_len, size_t* n_entries, int* info, size_t n_info);
 /* GPT.sample — src/main.zig:198-207 for all sequences: zg_gpt_forward(seq_len, tokens, logits), then
  * logits /= temp, softmax, and an index drawn with probability proportional to the result
  * (std.rand weightedIndex: first index whose running sum exceeds u * total).  The reference re-seeds

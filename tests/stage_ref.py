@@ -1,5 +1,5 @@
-"""The float64 side of the decode-stage tests (test_decode_stages_gpu.py, test_decode_stage_cases_cpu.py): decoders of the raw
-buffers a tapped decode step returns (zg_debug_gpt_step_taps) and plain numpy float64 versions of each stage of a decode step,
+"""The float64 side of the stage tests (test_decode_stages_gpu.py, test_pass_stages_gpu.py and their *_cases_cpu.py): decoders of the raw
+buffers a tapped decode step or whole-prompt pass returns (zg_debug_gpt_step_taps, zg_debug_gpt_pass_taps) and plain numpy float64 versions of each stage,
 written from the operations' definitions (LayerNorm, Linear, split_qkv, softmax attention, the merge of split partials,
 tanh-GELU, the residual add) — nothing here calls the library.
 
@@ -191,8 +191,10 @@ def merge_partials(part, n_splits, dtype=np.float64):
 
 
 def metric(got, ref64, s):
-    """Worst |got - ref64| / s over the outputs."""
-    return float(np.max(np.abs(np.asarray(got, np.float64) - ref64) / s))
+    """Worst |got - ref64| / s over the outputs.  An output whose s is 0 (a query that sees one key whose V element is an exact
+    zero) must be exact: 0 there if it is, infinite if not."""
+    d, s = np.abs(np.asarray(got, np.float64) - ref64), np.asarray(s, np.float64)
+    return float(np.max(np.where(s > 0, d / np.where(s > 0, s, 1.0), np.where(d == 0, 0.0, np.inf))))
 
 
 # ---------------------------------------------------------------------------------------------- a Linear stage, both sides
@@ -229,7 +231,16 @@ LOGIT_ULPS = 4 * 2.0 ** -23
 # yardstick is a blocked sum.  Measured: 11 launches, 10 within 3 Y, one (E = 1024, 8 rows) at 3.69 Y = 1.14e-6 on an ordinary
 # logit.  Raised to 6 Y; the three defects still exceed that by 1.5 x at its widths (test_decode_stage_cases_cpu.py asserts it:
 # 5.8 x 3 Y is the least any lm_head shape measures).
-BOUND_Y = {"GR_LM_WPT": 6.0}
+# PF_T128 / PF_S4 (the whole-prompt GEMMs of prefill.hip and gemm_s4.hip with bf16 weights, test_pass_stages_gpu.py): every output
+# is ONE accumulator through the whole K loop, the planes of a 16-column K step one behind the other (lo, mid, hi): a sequential
+# chain of 3 K / 16 v_mfma_f32_32x32x16_bf16 accumulations (24 at K = 128, 300 at K = 1600; K / slices on the sliced launches)
+# — correct by reading, and every product is exact, but the yardstick is a blocked sum whose blocks numpy adds pairwise.
+# Measured on MI355X over 176 launches of the two families: the kernels' worst value is 1.0e-6 .. 2.9e-6 of the metric whatever
+# the shape, about 2e-7 x sqrt(chain length); seven launches lie above 3 Y — PF_T128 at K = 128 4.25 Y (c_attn at M = 1, where Y is
+# one row's 2.5e-7), 3.23 Y, 3.07 Y; PF_S4 3.07 Y at K = 768 and 3.67 / 3.74 / 3.97 Y at K = 1600.  Raised to 6 Y for both;
+# the five defects of test_pass_stage_cases_cpu.py still exceed that by 1.5 x at every width (asserted there: the least is 4.0 x 3 Y
+# = 2.0 x 6 Y).  The three-pass kernel for fp32 / B24 weights (PF_T128_WP, 2.57 Y at the most) keeps 3.
+BOUND_Y = {"GR_LM_WPT": 6.0, "PF_T128": 6.0, "PF_S4": 6.0}
 
 
 def bound_y(route):
@@ -252,3 +263,73 @@ def tile_stats(x):
     ref = np.stack([t.sum(axis=2), (t * t).sum(axis=2)], axis=-1)
     s = np.stack([np.sqrt((t * t).sum(axis=2)), np.sqrt((t ** 4).sum(axis=2))], axis=-1)
     return ref, s
+
+
+# ---------------------------------------------------------------------------------------------- the whole-prompt pass
+def decode_row_planes(raw_u16, M, K):
+    """The pass's plane buffers are row-major, [M][3 K] = hi | mid | lo of a row side by side -> fp32 [3][M][K]."""
+    raw = np.asarray(raw_u16, np.uint16)
+    assert raw.size == 3 * M * K, (raw.size, M, K)
+    return bf16_bits_to_f32(np.ascontiguousarray(raw.reshape(M, 3, K).transpose(1, 0, 2)))
+
+
+def causal_attention(q, K, V, past, dtype=np.float64, shift=0):
+    """Causal attention of n new positions behind `past` cached ones: q [B][H][n][64], K / V [B][H][past + n][64] — the values the
+    device reads: the cache's stored values, or the unrounded qkv columns where the pass reads those.  Query t sees keys
+    0 .. past + t (+ shift: the emulated off-by-one mask of the teeth test).  Returns out [B][H][n][64] and s, the l2 norm of the
+    weighted V terms (always float64)."""
+    q, K, V = (np.asarray(t, dtype) for t in (q, K, V))
+    n, T = q.shape[2], K.shape[2]
+    sc = np.einsum("bhqd,bhtd->bhqt", q, K) * dtype(0.125)
+    seen = np.arange(T)[None, :] <= past + np.arange(n)[:, None] + shift
+    sc = np.where(seen, sc, dtype(-np.inf))
+    p = np.exp(sc - sc.max(axis=-1, keepdims=True))
+    p = p / p.sum(axis=-1, keepdims=True, dtype=dtype)
+    out = np.einsum("bhqt,bhtd->bhqd", p, V)
+    s = np.sqrt(np.einsum("bhqt,bhtd->bhqd", p.astype(np.float64) ** 2, V.astype(np.float64) ** 2))
+    return out, s
+
+
+def layernorm_stage(x, g, b):
+    """One LayerNorm launch from its input rows x [M][E]: ref64, the metric's s = |g| (|x| + |mean|) / sigma + |b| — the size of
+    the terms the output is made of, so that a value near the mean is not held to a relative bound — and y32, the float32 numpy
+    evaluation (the yardstick)."""
+    x64, g64, b64 = (np.asarray(t, np.float64) for t in (x, g, b))
+    mean = x64.mean(axis=-1, keepdims=True)
+    sd = np.sqrt(((x64 - mean) ** 2).mean(axis=-1, keepdims=True) + EPS)
+    s = np.abs(g64) * (np.abs(x64) + np.abs(mean)) / sd + np.abs(b64)
+    return layernorm(x, g, b), s, layernorm(x, g, b, np.float32)
+
+
+def yardstick_rows(M, n_seq, seed=0, at_least=64):
+    """The rows a pass Linear's yardstick is taken over: all of them up to 256; beyond, a fixed sample — the first and the last
+    row, both sides of every 128- and 256-row tile edge and of every sequence boundary (rows are ordered (sequence, position): a
+    boundary every n_seq rows), and seeded others up to `at_least`."""
+    if M <= 256:
+        return np.arange(M)
+    rows = {0, M - 1}
+    for edge in list(range(128, M, 128)) + list(range(n_seq, M, n_seq)):
+        rows |= {edge - 1, edge}
+    rest = np.setdiff1d(np.arange(M), sorted(rows))
+    extra = np.random.default_rng(seed).choice(rest, max(at_least - len(rows), 0), replace=False)
+    return np.array(sorted(rows | set(int(r) for r in extra)))
+
+
+def pass_linear_stage(a, W, bias, *, resid=None, act=None, n_seq=1, yardstick=True):
+    """A whole-prompt Linear from the activations a [M][K] the device fed it (the value of its planes): (ref64 [M][N], s [M][N],
+    Y).  Y is linear_stage's — the blocked float32 sum, row by row — over yardstick_rows; ref64 and s cover every row, ref64 as
+    one float64 matrix product (which differs from the blocked float64 sum by 1e-16 of s, nine orders below Y)."""
+    a64, W64 = np.asarray(a, np.float64), np.asarray(W, np.float64)
+    ref = a64 @ W64.T
+    if bias is not None:
+        ref = ref + np.asarray(bias, np.float64)
+    if resid is not None:
+        ref = ref + np.asarray(resid, np.float64)
+    if act == "gelu":
+        ref = gelu(ref)
+    s = linear_scale(a64, W64, bias, resid)
+    if not yardstick:
+        return ref, s, None
+    rows = yardstick_rows(a64.shape[0], n_seq)
+    r64, rs, y32 = linear_stage(np.asarray(a)[rows], W, bias, resid=None if resid is None else np.asarray(resid)[rows], act=act)
+    return ref, s, metric(y32, r64, rs)

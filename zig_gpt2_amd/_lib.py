@@ -119,6 +119,7 @@ SIGNATURES = {
     "zg_gpt_generate_fetch_range": (C.c_int, [vp, sz, sz, vp, sz]),
     "zg_gpt_argmax": (C.c_int, [vp, vp, sz]),
     "zg_debug_gpt_step_taps": (C.c_int, [vp, sz, vp, sz, vp, sz, szp, vp, sz, szp, vp, sz]),
+    "zg_debug_gpt_pass_taps": (C.c_int, [vp, sz, vp, sz, sz, C.c_int, C.c_int, sz, vp, sz, vp, sz, szp, vp, sz, szp, vp, sz]),
     "zg_gpt_sample": (C.c_int, [vp, sz, vp, sz, C.c_float, vp, C.c_uint64, vp, vp, sz]),
     "zg_gpt_hidden": (C.c_int, [vp, vp, sz]),
     "zg_gpt_generate_greedy": (C.c_int, [vp, vp, sz, vp, sz, vp, sz]),
@@ -184,9 +185,12 @@ BLOCK_SLOTS = ["ln_1_g", "ln_1_b", "c_attn_w", "c_attn_b", "c_proj_w", "c_proj_b
 TOP_SLOTS = ["wte", "wpe", "ln_f_g", "ln_f_b"]
 TIME_LM_HEAD = 6
 # zg_debug_gpt_step_taps: buffers, element types (numpy: bf16 and the B24 byte plane stay raw), flags, info words
-TAP_BUFFERS = ["x", "xp", "xst", "q", "k", "k_lo", "v", "v_lo", "part", "ap", "h4", "hp", "logits", "part_val", "part_idx"]
+TAP_BUFFERS = ["x", "xp", "xst", "q", "k", "k_lo", "v", "v_lo", "part", "ap", "h4", "hp", "logits", "part_val", "part_idx",
+               "a", "qkv_kv", "plan", "geo"]  # (the last four: zg_debug_gpt_pass_taps only)
 TAP_DTYPES = ["<f4", "<f2", "<u2", "u1", "<i4"]
 TAP_FUSED, TAP_NOT_WRITTEN = 1, 2
+PASS_INFO = ["planes", "kv_mode", "weight_type", "pf_ws_floats", "stream_k_operands", "v64", "score_rows"]  # zg_debug_gpt_pass_taps
+PASS_TAP_ROWS_BEHIND = 4
 TAP_INFO = ["planes", "stats", "tags", "fused", "max_splits", "lm_grid", "t_hi", "kv_mode", "weight_type"]
 
 

@@ -18,6 +18,7 @@
 //                                                            contiguous [ctx, 64] slab, so no
 //                                                            per-step transpose (ops.zig:153,158)
 //   [ scratch: x q h4 attention partials logits argmax partials, control block, token buffers ]
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -26,6 +27,7 @@
 #include <cmath>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "zg_runtime.h"
@@ -206,6 +208,7 @@ struct zg_gpt {
 #define ZG_SCORE_ROWS 256
 #endif
 constexpr size_t kScoreRows = ZG_SCORE_ROWS;
+constexpr size_t kPassTapRowsBehind = ZG_PASS_TAP_ROWS_BEHIND;  // cache rows a tapped pass copies behind its last position
 
 static inline hipStream_t gs(const zg_gpt* g) { return g->stream ? g->stream : ctx().stream; }
 static inline zg_gpt* root(zg_gpt* g) { return g->parent ? g->parent : g; }
@@ -708,6 +711,7 @@ struct StepTaps {
     size_t cap = 0, used = 0;
     size_t seq_len = 0;
     std::vector<zg_tap_entry> table;
+    std::vector<std::pair<size_t, std::vector<int>>> words;  // tap_words: (arena offset, ints) the host writes behind the read-back
 };
 
 // One buffer into the sink: `rows` rows of row_bytes, src_pitch bytes apart in the source, packed in the arena
@@ -727,11 +731,41 @@ int tap_put(StepTaps* t, int cls, size_t layer, int buffer, int type, unsigned f
     return ZG_OK;
 }
 
+// Host ints (a launch's plan, the attention's geometry) into the sink: a table entry and room in the arena like any tap, filled on
+// the host once the arena has been read back (zg_debug_gpt_pass_taps)
+int tap_words(StepTaps* t, int cls, size_t layer, int buffer, const int* w, size_t n) {
+    const size_t off = (t->used + 255) & ~(size_t)255;
+    zg_tap_entry e{};
+    e.cls = cls, e.layer = (int)layer, e.buffer = buffer, e.type = ZG_TAP_I32;
+    e.offset = off, e.count = n;
+    ZG_REQUIRE(!t->base || off + n * 4 <= t->cap, ZG_ERR_ARG, "taps: %zu bytes at %zu beyond the arena's %zu", n * 4, off, t->cap);
+    t->table.push_back(e);
+    t->used = off + n * 4;
+    t->words.emplace_back(off, std::vector<int>(w, w + n));
+    return ZG_OK;
+}
+
+// The K and V rows of positions < T of every (sequence, head) of layer l, [B][H][T][64] in storage format
+int tap_caches(const zg_gpt* g, StepTaps* t, int cls, size_t l, unsigned flags, size_t T, hipStream_t s) {
+    const size_t E = g->cfg.n_embed, B = g->batch, H = g->cfg.n_heads, C = g->cfg.context_size;
+    const zg_layer& y = g->layers[l];
+    const size_t lo = B * C * E * 2;
+    const void* kv[2] = {y.k_cache, y.v_cache};
+    for (int i = 0; i < 2; ++i) {
+        const char* p = reinterpret_cast<const char*>(kv[i]);
+        const int b0 = i ? ZG_TAP_V : ZG_TAP_K;
+        if (g->kv_mode == 0) ZG_TRY(tap_put(t, cls, l, b0, ZG_TAP_F32, flags, p, B * H, T * 256, C * 256, s));
+        else ZG_TRY(tap_put(t, cls, l, b0, g->kv_mode == 1 ? ZG_TAP_F16 : ZG_TAP_BF16, flags, p, B * H, T * 128, C * 128, s));
+        if (g->kv_mode == 2) ZG_TRY(tap_put(t, cls, l, b0 + 1, ZG_TAP_U8, flags, p + lo, B * H, T * 64, C * 64, s));
+    }
+    return ZG_OK;
+}
+
 // What launch class cls of layer l wrote (include/zgpt2.h zg_debug_gpt_step_taps lists it), raw, in the handle's storage.
 // cls -1: the layer's caches as the step finds them.  flags: ZG_TAP_* of the header.
 int tap_class(const zg_gpt* g, StepTaps* t, int cls, size_t l, unsigned flags, hipStream_t s) {
     if (!t) return ZG_OK;
-    const size_t E = g->cfg.n_embed, B = g->batch, H = g->cfg.n_heads, C = g->cfg.context_size, V = g->cfg.vocab_size;
+    const size_t E = g->cfg.n_embed, B = g->batch, H = g->cfg.n_heads, V = g->cfg.vocab_size;
     auto whole = [&](int buffer, int type, const void* src, size_t bytes, unsigned f) { return tap_put(t, cls, l, buffer, type, f, src, 1, bytes, bytes, s); };
     auto x_side = [&](bool planes_written) -> int {  // x and, with planes on, what travels with it
         ZG_TRY(whole(ZG_TAP_X, ZG_TAP_F32, g->x, B * E * 4, flags));
@@ -739,19 +773,7 @@ int tap_class(const zg_gpt* g, StepTaps* t, int cls, size_t l, unsigned flags, h
         if (g->st_on) ZG_TRY(whole(ZG_TAP_XST, ZG_TAP_F32, g->xst, ((E + 15) / 16) * 8 * 2 * 4, flags | (planes_written ? 0u : ZG_TAP_NOT_WRITTEN)));
         return ZG_OK;
     };
-    auto caches = [&]() -> int {  // positions < seq_len of every (sequence, head): [B][H][seq_len][64]
-        const zg_layer& y = g->layers[l];
-        const size_t T = t->seq_len, lo = B * C * E * 2;
-        const void* kv[2] = {y.k_cache, y.v_cache};
-        for (int i = 0; i < 2; ++i) {
-            const char* p = reinterpret_cast<const char*>(kv[i]);
-            const int b0 = i ? ZG_TAP_V : ZG_TAP_K;
-            if (g->kv_mode == 0) ZG_TRY(tap_put(t, cls, l, b0, ZG_TAP_F32, flags, p, B * H, T * 256, C * 256, s));
-            else ZG_TRY(tap_put(t, cls, l, b0, g->kv_mode == 1 ? ZG_TAP_F16 : ZG_TAP_BF16, flags, p, B * H, T * 128, C * 128, s));
-            if (g->kv_mode == 2) ZG_TRY(tap_put(t, cls, l, b0 + 1, ZG_TAP_U8, flags, p + lo, B * H, T * 64, C * 64, s));
-        }
-        return ZG_OK;
-    };
+    auto caches = [&]() { return tap_caches(g, t, cls, l, flags, t->seq_len, s); };  // positions < seq_len
     switch (cls) {
         case -1: return caches();
         case 0: return x_side(true);
@@ -936,13 +958,29 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
 // overhead, and a graph launch adds its own ~10 us; profiles/round4_prefill_graph.jsonl.)
 // pos0 > 0 (a continuation): the P rows are positions pos0 .. pos0 + P - 1 (tokens g->prompt[b][pos0 + t]); they are appended
 // behind the pos0 cached rows, and the attention reads every key, old and new, from the caches in their storage format.
-int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipStream_t s) {
+// taps (zg_debug_gpt_pass_taps): behind every launch, copies of what it wrote (include/zgpt2.h lists them); the launches are the same.
+int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipStream_t s, StepTaps* taps = nullptr) {
     const bool f32w = g->wt != WT_BF16;
     const int np = f32w ? kWeightPlanes : (g->flags & ZG_GPT_PREFILL_2PLANE) ? 2 : kSplit;
     const size_t E = g->cfg.n_embed, L = g->cfg.n_layer, H = g->cfg.n_heads, C = g->cfg.context_size;
     const int B = (int)g->batch, M = (int)(g->batch * P), iE = (int)E;
+    const size_t Mz = (size_t)M, T_tap = std::min(C, pos0 + P + kPassTapRowsBehind);
+    PrefillGemmPlan plan{};
+    PrefillGemmPlan* const plan_out = taps ? &plan : nullptr;
+    auto tap_x = [&](int cls, size_t l) { return taps ? tap_put(taps, cls, l, ZG_TAP_X, ZG_TAP_F32, 0, g->pf_x, 1, Mz * E * 4, Mz * E * 4, s) : ZG_OK; };
+    auto tap_a = [&](int cls, size_t l, unsigned f) {
+        return taps ? tap_put(taps, cls, l, ZG_TAP_A, ZG_TAP_BF16, f, g->pf_a, 1, Mz * kSplit * E * 2, Mz * kSplit * E * 2, s) : ZG_OK;
+    };
+    auto tap_plan = [&](int cls, size_t l) {
+        if (!taps) return (int)ZG_OK;
+        int v[ZG_PREFILL_PLAN_INTS];
+        prefill_plan_ints(plan, v);
+        return tap_words(taps, cls, l, ZG_TAP_PLAN, v, ZG_PREFILL_PLAN_INTS);
+    };
     ZG_TRY(launch_embed_prefill(g->prompt, (int)C, B, (int)P, g->wte, g->wpe, g->wt, iE, g->pf_x, s, (int)pos0));
+    ZG_TRY(tap_x(0, 0));
     ZG_TRY(launch_ln_split(g->pf_x, M, iE, g->layers[0].ln_1_g, g->layers[0].ln_1_b, 1e-5f, g->pf_a, s));
+    ZG_TRY(tap_a(1, 0, 0));
     for (size_t l = 0; l < L; ++l) {
         const zg_layer& y = g->layers[l];
         // pf_a holds split(ln_1(x)) here: from the line above or from the tail of the previous Block's last GEMM
@@ -957,23 +995,42 @@ int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipS
             qa.sk_epoch = ++g->sk_epoch;
             g->sk_used = true;
         }
+        if (taps) ZG_TRY(tap_caches(g, taps, -1, l, 0, T_tap, s));
         ZG_TRY(launch_prefill_gemm(g->pf_a, f32w ? y.c_attn_p : (const bf16_t*)y.c_attn_w, y.c_attn_b, g->pf_qkv, M, 3 * iE, iE, 3 * iE, PF_QKV,
-                                   g->pf_ws, g->pf_ws_floats, nullptr, s, &qa, np));
+                                   g->pf_ws, g->pf_ws_floats, nullptr, s, &qa, np, nullptr, plan_out));
+        if (taps) {  // q, then the k | v columns: the persistent kernel leaves those to an fp32 cache (gemm_s4.hip S4_QKV)
+            const unsigned kv_cols = plan.family == PFF_S4 && g->kv_mode == 0 ? ZG_TAP_NOT_WRITTEN : 0u;
+            ZG_TRY(tap_plan(2, l));
+            ZG_TRY(tap_put(taps, 2, l, ZG_TAP_Q, ZG_TAP_F32, 0, g->pf_qkv, Mz, E * 4, 3 * E * 4, s));
+            ZG_TRY(tap_put(taps, 2, l, ZG_TAP_QKV_KV, ZG_TAP_F32, kv_cols, g->pf_qkv + E, Mz, 2 * E * 4, 3 * E * 4, s));
+            ZG_TRY(tap_caches(g, taps, 2, l, 0, T_tap, s));
+        }
         if (l + 1 == L && !last_block_full) break;
         // K and V: the caches — except a whole prompt on an fp16 / B24 cache, which reads the unrounded k / v columns of qkv (an fp32
         // cache is read directly: the c_attn epilogue then need not store those columns)
         PrefillKv kv;
         if (pos0 > 0 || g->kv_mode == 0) kv = PrefillKv{y.k_cache, y.v_cache, g->kv_mode, g->batch * C * E * 2, (int)C};
-        ZG_TRY(launch_attn_prefill(g->pf_qkv, g->pf_a, B, (int)pos0, (int)P, iE, (int)H, g->pf_ws, g->pf_ws_floats, kv, s));
+        int ran[3] = {0, 0, 0};
+        ZG_TRY(launch_attn_prefill(g->pf_qkv, g->pf_a, B, (int)pos0, (int)P, iE, (int)H, g->pf_ws, g->pf_ws_floats, kv, s, 0, taps ? ran : nullptr));
+        if (taps) ZG_TRY(tap_words(taps, 3, l, ZG_TAP_GEO, ran, 3));
+        ZG_TRY(tap_a(3, l, 0));
         const PrefillLn ln2{y.ln_2_g, y.ln_2_b, 1e-5f, g->pf_a};
         ZG_TRY(launch_prefill_gemm(g->pf_a, f32w ? y.c_proj_p : (const bf16_t*)y.c_proj_w, y.c_proj_b, g->pf_x, M, iE, iE, iE, PF_RESID, g->pf_ws,
-                                   g->pf_ws_floats, &ln2, s, nullptr, np));
+                                   g->pf_ws_floats, &ln2, s, nullptr, np, nullptr, plan_out));
+        ZG_TRY(tap_plan(4, l));
+        ZG_TRY(tap_x(4, l));
+        ZG_TRY(tap_a(4, l, 0));
         ZG_TRY(launch_prefill_gemm(g->pf_a, f32w ? y.c_fc_p : (const bf16_t*)y.c_fc_w, y.c_fc_b, g->pf_h, M, 4 * iE, iE, 0, PF_GELU_SPLIT, g->pf_ws,
-                                   g->pf_ws_floats, nullptr, s, nullptr, np));
+                                   g->pf_ws_floats, nullptr, s, nullptr, np, nullptr, plan_out));
+        ZG_TRY(tap_plan(5, l));
+        if (taps) ZG_TRY(tap_put(taps, 5, l, ZG_TAP_HP, ZG_TAP_BF16, 0, g->pf_h, 1, Mz * kSplit * 4 * E * 2, Mz * kSplit * 4 * E * 2, s));
         const bool more = l + 1 < L;
         const PrefillLn ln1{more ? g->layers[l + 1].ln_1_g : nullptr, more ? g->layers[l + 1].ln_1_b : nullptr, 1e-5f, g->pf_a};
         ZG_TRY(launch_prefill_gemm(g->pf_h, f32w ? y.mlp_proj_p : (const bf16_t*)y.mlp_proj_w, y.mlp_proj_b, g->pf_x, M, iE, 4 * iE, iE, PF_RESID, g->pf_ws,
-                                   g->pf_ws_floats, more ? &ln1 : nullptr, s, nullptr, np));
+                                   g->pf_ws_floats, more ? &ln1 : nullptr, s, nullptr, np, nullptr, plan_out));
+        ZG_TRY(tap_plan(6, l));
+        ZG_TRY(tap_x(6, l));
+        ZG_TRY(tap_a(6, l, more ? 0u : ZG_TAP_NOT_WRITTEN));
     }
     return ZG_OK;
 }
@@ -1746,25 +1803,42 @@ struct ScoreCall {
 // The scoring stage of a pass of n new positions per sequence behind `past` cached ones, whose residual stream of every row is
 // in pf_x: ln_f of all rows once (pf_a is free: the pass is over), then block by block of kScoreRows rows the lm_head on the
 // matrix cores into sc_logits, the two statistics launches, and on request the block's logits to the caller.
-static int enqueue_score(zg_gpt* g, size_t past, size_t n, float* logits_out, hipStream_t s) {
+// taps (zg_debug_gpt_pass_taps): class 7 — the ln_f planes, then per block (the table's layer field) each GEMM's plan and the block's rows of sc_logits.
+static int enqueue_score(zg_gpt* g, size_t past, size_t n, float* logits_out, hipStream_t s, StepTaps* taps = nullptr) {
     const size_t E = g->cfg.n_embed, V = g->cfg.vocab_size, C = g->cfg.context_size, V64 = g->sc_v64, head = V / 64 * 64, M = g->batch * n;
     const int iE = (int)E, ld = (int)V64;
     const int np = (g->flags & ZG_GPT_PREFILL_2PLANE) ? 2 : kSplit;
     ZG_TRY(ensure_score_weights(g, s));
     ZG_TRY(launch_ln_split(g->pf_x, (int)M, iE, g->ln_f_g, g->ln_f_b, 1e-5f, g->pf_a, s));
+    PrefillGemmPlan plan{};
+    PrefillGemmPlan* const plan_out = taps ? &plan : nullptr;
+    auto tap_plan = [&](size_t block) {
+        if (!taps) return (int)ZG_OK;
+        int v[ZG_PREFILL_PLAN_INTS];
+        prefill_plan_ints(plan, v);
+        return tap_words(taps, 7, block, ZG_TAP_PLAN, v, ZG_PREFILL_PLAN_INTS);
+    };
+    if (taps) ZG_TRY(tap_put(taps, 7, 0, ZG_TAP_A, ZG_TAP_BF16, 0, g->pf_a, 1, M * kSplit * E * 2, M * kSplit * E * 2, s));
     for (size_t r0 = 0; r0 < M; r0 += kScoreRows) {
         const int rows = (int)std::min(kScoreRows, M - r0);
         const bf16_t* A = g->pf_a + r0 * kSplit * E;
         if (g->wt != WT_BF16) {  // the planes hold zero rows up to V64: one launch
             ZG_TRY(launch_prefill_gemm(A, g->sc_planes, nullptr, g->sc_logits, rows, ld, iE, ld, PF_F32, g->sc_gemm_ws, g->sc_gemm_ws_floats, nullptr, s, nullptr,
-                                       kWeightPlanes));
+                                       kWeightPlanes, nullptr, plan_out));
+            ZG_TRY(tap_plan(r0 / kScoreRows));
         } else {  // the whole 64-row groups of wte where they lie, then the strip: no row behind V - 1 of wte is read
-            if (head)
+            if (head) {
                 ZG_TRY(launch_prefill_gemm(A, reinterpret_cast<const bf16_t*>(g->wte), nullptr, g->sc_logits, rows, (int)head, iE, ld, PF_F32, g->pf_ws,
-                                           g->pf_ws_floats, nullptr, s, nullptr, np));
-            if (g->sc_tail)
-                ZG_TRY(launch_prefill_gemm(A, g->sc_tail, nullptr, g->sc_logits + head, rows, 64, iE, ld, PF_F32, g->pf_ws, g->pf_ws_floats, nullptr, s, nullptr, np));
+                                           g->pf_ws_floats, nullptr, s, nullptr, np, nullptr, plan_out));
+                ZG_TRY(tap_plan(r0 / kScoreRows));
+            }
+            if (g->sc_tail) {
+                ZG_TRY(launch_prefill_gemm(A, g->sc_tail, nullptr, g->sc_logits + head, rows, 64, iE, ld, PF_F32, g->pf_ws, g->pf_ws_floats, nullptr, s, nullptr, np,
+                                           nullptr, plan_out));
+                ZG_TRY(tap_plan(r0 / kScoreRows));
+            }
         }
+        if (taps) ZG_TRY(tap_put(taps, 7, r0 / kScoreRows, ZG_TAP_LOGITS, ZG_TAP_F32, 0, g->sc_logits, 1, (size_t)rows * V64 * 4, (size_t)rows * V64 * 4, s));
         const ScoreTargets tg{g->prompt, (int)C, (int)n, (int)past, (int)r0};
         ZG_TRY(launch_score(g->sc_logits, rows, (int)V, ld, g->lp_top, g->sc_ws, tg, g->lp_rec, s));
         if (logits_out)
@@ -1775,7 +1849,7 @@ static int enqueue_score(zg_gpt* g, size_t past, size_t n, float* logits_out, hi
 }
 
 static int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t stride, size_t n, int compute_logits, float* logits_out, size_t logits_len,
-                     const char* who, const ScoreCall* sc = nullptr) {
+                     const char* who, const ScoreCall* sc = nullptr, StepTaps* taps = nullptr) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && tokens, ZG_ERR_ARG, "%s: null argument", who);
     ZG_REQUIRE(g->pf_x != nullptr, ZG_ERR_UNSUPPORTED, "%s: the handle was created with ZG_GPT_NO_PREFILL", who);
@@ -1801,7 +1875,7 @@ static int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t st
     ZG_TRY(clear_for_pass(g, s, past_len, end));
     g->cached_len = end;
     ZG_TRY(ensure_ln_folded(g, s));
-    ZG_TRY(enqueue_prefill(g, past_len, n, compute_logits != 0, s));
+    ZG_TRY(enqueue_prefill(g, past_len, n, compute_logits != 0, s, taps));
     if (compute_logits) {
         ZG_HIP(hipMemcpy2DAsync(g->x, E * 4, g->pf_x + (n - 1) * E, n * E * 4, E * 4, B, hipMemcpyDeviceToDevice, s));
         ZG_TRY(stage_ctrl(g, end - 1, end, 1, s));
@@ -1812,7 +1886,7 @@ static int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t st
         ZG_TRY(stage_top_n(g, sc->top_n, s));
         // column past_len: its predicting row is not part of the pass (NaN: every byte 0xff)
         ZG_HIP(hipMemset2DAsync(g->lp_rec.logprob + past_len, C * sizeof(float), 0xff, sizeof(float), B, s));
-        ZG_TRY(enqueue_score(g, past_len, n, sc->logits_out, s));
+        ZG_TRY(enqueue_score(g, past_len, n, sc->logits_out, s, taps));
     }
     ZG_HIP(hipStreamSynchronize(s));
     return check_fault(g);
@@ -1830,6 +1904,55 @@ int zg_gpt_prefill(zg_gpt* g, const size_t* tokens, size_t token_stride, size_t 
 int zg_gpt_extend(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits, float* logits_out,
                   size_t logits_len) {
     return pass_impl(g, past_len, tokens, token_stride, n_tokens, compute_logits, logits_out, logits_len, "gpt_extend");
+}
+
+// zg_gpt_prefill / zg_gpt_extend / zg_gpt_score with every launch of the pass tapped (tests; include/zgpt2.h).  arena_out == nullptr:
+// nothing runs; an upper bound of what a call needs is reported.  Allocates its device arena per call.
+int zg_debug_gpt_pass_taps(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits, int score, size_t top_n,
+                           float* logits_out, size_t logits_len, void* arena_out, size_t arena_bytes, size_t* arena_used, zg_tap_entry* table_out,
+                           size_t table_len, size_t* n_entries, int* info, size_t n_info) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && tokens && arena_used && n_entries, ZG_ERR_ARG, "debug_gpt_pass_taps: null argument");
+    ZG_REQUIRE(g->pf_x != nullptr, ZG_ERR_UNSUPPORTED, "debug_gpt_pass_taps: the handle was created with ZG_GPT_NO_PREFILL");
+    const size_t C = g->cfg.context_size, E = g->cfg.n_embed, L = g->cfg.n_layer, B = g->batch;
+    ZG_REQUIRE(n_tokens >= 1 && past_len + n_tokens <= C, ZG_ERR_SHAPE, "debug_gpt_pass_taps: %zu tokens behind %zu positions (context %zu)", n_tokens, past_len, C);
+    ZG_REQUIRE(!score || g->sc_logits != nullptr, ZG_ERR_UNSUPPORTED, "debug_gpt_pass_taps: the handle was created without ZG_GPT_SCORE");
+    // an upper bound of the pass's taps: per layer two cache taps of K and V (at most 4 bytes an element, and the B24 byte plane
+    // within that), x twice, pf_a four times, qkv, pf_h, three plans and the geometry; class 0 and 1 once; the score stage
+    const size_t M = B * n_tokens, T = std::min(C, past_len + n_tokens + kPassTapRowsBehind), blocks = (M + kScoreRows - 1) / kScoreRows;
+    const size_t per_layer = 4 * B * E * T * 4 + 2 * M * E * 4 + 4 * M * kSplit * E * 2 + M * 3 * E * 4 + M * kSplit * 4 * E * 2;
+    const size_t entries = 2 + L * 24 + (score ? 1 + 3 * blocks : 0);
+    const size_t cap = L * per_layer + M * E * 4 + M * kSplit * E * 2 + (score ? M * kSplit * E * 2 + M * g->sc_v64 * 4 : 0) + 256 * (entries + 1);
+    *arena_used = cap;
+    *n_entries = entries;
+    if (info && n_info >= ZG_PASS_INFO_INTS) {
+        const bool f32w = g->wt != WT_BF16;
+        const int v[ZG_PASS_INFO_INTS] = {f32w ? kSplit : (g->flags & ZG_GPT_PREFILL_2PLANE) ? 2 : kSplit, g->kv_mode, g->wt,
+                                          (int)std::min(g->pf_ws_floats, (size_t)INT_MAX), !f32w && g->sk_flags != nullptr, (int)g->sc_v64, (int)kScoreRows};
+        memcpy(info, v, sizeof(v));
+    }
+    if (!arena_out) return ZG_OK;
+    ZG_REQUIRE(table_out && arena_bytes >= cap && table_len >= entries, ZG_ERR_SHAPE, "debug_gpt_pass_taps: %zu arena bytes and %zu table entries needed", cap,
+               entries);
+    hipStream_t s = gs(g);
+    StepTaps taps;
+    taps.cap = cap;
+    DevScratch ds;
+    ZG_TRY(ds.carve([&] { taps.base = ds.take<char>(cap); }));
+    ZG_HIP(hipMemsetAsync(taps.base, 0, cap, s));
+    if (score) {
+        const ScoreCall sc{top_n, logits_out, logits_len};
+        ZG_TRY(pass_impl(g, past_len, tokens, token_stride, n_tokens, 1, nullptr, 0, "debug_gpt_pass_taps", &sc, &taps));
+    } else
+        ZG_TRY(pass_impl(g, past_len, tokens, token_stride, n_tokens, compute_logits, logits_out, logits_len, "debug_gpt_pass_taps", nullptr, &taps));
+    ZG_REQUIRE(taps.used <= cap && taps.table.size() <= entries, ZG_ERR_ARG, "debug_gpt_pass_taps: the pass tapped %zu entries in %zu bytes, bound %zu in %zu",
+               taps.table.size(), taps.used, entries, cap);
+    ZG_HIP(hipMemcpy(arena_out, taps.base, taps.used, hipMemcpyDeviceToHost));
+    for (const auto& w : taps.words) memcpy(static_cast<char*>(arena_out) + w.first, w.second.data(), w.second.size() * 4);
+    memcpy(table_out, taps.table.data(), taps.table.size() * sizeof(zg_tap_entry));
+    *arena_used = taps.used;
+    *n_entries = taps.table.size();
+    return ZG_OK;
 }
 
 int zg_gpt_cached_len(zg_gpt* g, size_t* len_out) {

@@ -680,10 +680,8 @@ int zg_debug_prefill_plan(int M, int N, int K, int ldc, int epilogue, int nsplit
                         (operands & ZG_PFPLAN_QKV) ? N / 3 : 0, (operands & ZG_PFPLAN_SK_WS) != 0, (operands & ZG_PFPLAN_SK_FLAGS) != 0, sk_ws_bytes,
                         sk_flags_words, PrefillForce{force_kernel, force_slices}};
     const PrefillGemmPlan p = prefill_gemm_plan(sh);
-    const GemmPlanes& pl = p.planes;
-    const int v[ZG_PREFILL_PLAN_INTS] = {p.status, p.family, p.tail, p.partial, p.grid_x, p.grid_y, p.block, p.lds, p.slices, p.slabs, p.ns, p.nspl, p.xcd_rows,
-                                         p.tiles_n, p.s4_kind, p.stream_k, p.band, pl.npairs, (int)pl.pa_bits, (int)pl.pb_bits, pl.b_plane_major};
-    memcpy(out, v, sizeof(v));
+    static_assert(ZG_PREFILL_PLAN_INTS == 21, "prefill_plan_ints packs 21");
+    prefill_plan_ints(p, out);
     return ZG_OK;
 }
 

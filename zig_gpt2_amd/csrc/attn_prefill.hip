@@ -504,7 +504,7 @@ __global__ __launch_bounds__(256) void attn_prefill_merge_at_kernel(const float*
 // by the c_attn epilogue just before.  ws: fp32 workspace for the partials of split key ranges (B H P max_splits 66 floats; none
 // needed when every group runs as one range).
 int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int pos0, int P, int E, int H, float* ws, size_t ws_floats, const PrefillKv& src,
-                        hipStream_t s, int force_tiles) {
+                        hipStream_t s, int force_tiles, int* ran_out) {
     static bool raised = false;
     if (!raised) {
         for (const void* f : {reinterpret_cast<const void*>(&attn_prefill_pl_kernel), reinterpret_cast<const void*>(&attn_prefill_at_kernel<0>),
@@ -558,6 +558,7 @@ int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int pos0, int P, i
     }
     // (the kernels address a (sequence, head)'s rows through 32-bit buffer descriptors; the *_at ones read up to a group past the end)
     ZG_REQUIRE((size_t)(whole ? P : pos0 + P + 128) * kv.stride_t < ((size_t)1 << 31), ZG_ERR_SHAPE, "attention prefill: rows beyond a 32-bit buffer descriptor");
+    if (ran_out) ran_out[0] = (int)geo, ran_out[1] = whole ? 0 : 1 + src.fmt, ran_out[2] = max_s > 1;
     const dim3 grid(H, B, ng * max_s);
     if (whole) hipLaunchKernelGGL(attn_prefill_pl_kernel, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv);
     else if (src.fmt == 0) hipLaunchKernelGGL(attn_prefill_at_kernel<0>, grid, dim3(256), kLds, s, qkv, out, ws, P, E, geo, kv, src.kv_lo, pos0);

@@ -781,7 +781,8 @@ PrefillForce g_force{0, 0};  // zg_debug_prefill_route
 void prefill_force_route(int kernel, int slices) { g_force = PrefillForce{kernel, slices}; }
 
 int launch_prefill_gemm(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, int K, int ldc, int epi,
-                        float* ws, size_t ws_floats, const PrefillLn* ln, hipStream_t s, const PrefillQkv* qkv, int nsplit, const PrefillForce* force) {
+                        float* ws, size_t ws_floats, const PrefillLn* ln, hipStream_t s, const PrefillQkv* qkv, int nsplit, const PrefillForce* force,
+                        PrefillGemmPlan* plan_out) {
     const PrefillQkv none{};
     const PrefillQkv& q = qkv ? *qkv : none;
     const PrefillGemmShape sh{M, N, K, ldc, epi, nsplit, ws_floats, ws != nullptr, ln != nullptr, q.E, q.sk_ws != nullptr, q.sk_flags != nullptr, q.sk_ws_bytes,
@@ -789,6 +790,7 @@ int launch_prefill_gemm(const bf16_t* A, const bf16_t* B, const float* bias, voi
     const PrefillGemmPlan p = prefill_gemm_plan(sh);
     ZG_REQUIRE(p.status == ZG_OK, p.status, "prefill gemm: M=%d N=%d K=%d ldc=%d epilogue %d, %d planes, workspace %zu: %s", M, N, K, ldc, epi, nsplit, ws_floats,
                p.why);
+    if (plan_out) *plan_out = p;
     const PrefillOps o{A, B, bias, C, ws, ln, epi == PF_QKV ? q : none, s};
     ZG_TRY(launch_gemm(p, sh, o, qkv));
     return finish(p, sh, o);

@@ -331,7 +331,15 @@ int launch_prefill_gemm(const bf16_t* A, const bf16_t* W, const float* bias, voi
                         float* ws, size_t ws_floats, const PrefillLn* ln, hipStream_t s, const PrefillQkv* qkv = nullptr,
                         int nsplit = kSplit,  // nsplit = 2: multiply the hi + mid planes only (2/3 of the matrix work);
                                               // kWeightPlanes: W is the plane-major three-term split [3][N][K] of an fp32 matrix
-                        const PrefillForce* force = nullptr);
+                        const PrefillForce* force = nullptr,
+                        PrefillGemmPlan* plan_out = nullptr);  // plan_out (zg_debug_gpt_pass_taps): receives the plan the launch used
+// The ZG_PREFILL_PLAN_INTS (21) ints zg_debug_prefill_plan and zg_debug_gpt_pass_taps report of a plan (include/zgpt2.h lists them)
+inline void prefill_plan_ints(const PrefillGemmPlan& p, int* v) {
+    const GemmPlanes& pl = p.planes;
+    const int w[21] = {p.status, p.family, p.tail, p.partial, p.grid_x, p.grid_y, p.block, p.lds, p.slices, p.slabs, p.ns, p.nspl, p.xcd_rows,
+                       p.tiles_n, p.s4_kind, p.stream_k, p.band, pl.npairs, (int)pl.pa_bits, (int)pl.pb_bits, pl.b_plane_major};
+    for (int i = 0; i < 21; ++i) v[i] = w[i];
+}
 void prefill_force_route(int kernel, int slices);  // zg_debug_prefill_route: pin the route of every whole-prompt Linear of the process
 // Where the prompt attention reads K and V: the k / v columns of the qkv rows (k == nullptr; a whole prompt only), or head-major
 // caches [b][h][ctx][64] in storage format fmt (0 fp32, 1 fp16, 2 B24 with its byte plane kv_lo bytes behind the bf16 plane)
@@ -344,9 +352,11 @@ struct PrefillKv {
 };
 // out[M][kSplit E] = split(causal attention of the P rows per sequence of qkv[M][3E]), M = B P rows ordered (b, t), at positions
 // pos0 .. pos0 + P - 1 behind pos0 cached ones (attn_prefill.hip: bf16 matrix cores on exact plane splits; ws = fp32 workspace for
-// the partials of split key ranges; force_tiles: key tiles per workgroup, tests)
+// the partials of split key ranges; force_tiles: key tiles per workgroup, tests; ran_out (zg_debug_gpt_pass_taps): receives the
+// geometry word (key tiles per range | max splits << 8 | groups << 16), the kernel (0 whole-prompt, 1 + fmt: the continuation
+// kernel of that cache format) and whether the merge kernel ran)
 int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int pos0, int P, int E, int H, float* ws, size_t ws_floats, const PrefillKv& kv,
-                        hipStream_t s, int force_tiles = 0);
+                        hipStream_t s, int force_tiles = 0, int* ran_out = nullptr);
 
 // GPT.sample tail: in-place softmax(logits / temp) per sequence + inverse-CDF draw with uniform u[b].
 // part_val / n_part / part_stride: the per-workgroup maxima lm_head's argmax epilogue left (the row maximum without a pass over the

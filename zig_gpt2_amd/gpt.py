@@ -150,12 +150,34 @@ class GPT:
         table = (_lib.TapEntry * n.value)()
         check(self._L.zg_debug_gpt_step_taps(self.h, seq_len, ptr(tokens), tokens.size, ptr(arena), arena.size, C.byref(used), C.addressof(table), n.value,
                                              C.byref(n), ptr(info), info.size))
+        return self._tap_list(arena, table, n.value), dict(zip(_lib.TAP_INFO, (int(v) for v in info)))
+
+    @staticmethod
+    def _tap_list(arena, table, n):
         taps = []
-        for e in table[: n.value]:
+        for e in table[:n]:
             dt = np.dtype(_lib.TAP_DTYPES[e.type])
             data = arena[e.offset: e.offset + e.count * dt.itemsize].view(dt).copy()
             taps.append({"cls": e.cls, "layer": e.layer, "name": _lib.TAP_BUFFERS[e.buffer], "flags": e.flags, "data": data})
-        return taps, dict(zip(_lib.TAP_INFO, (int(v) for v in info)))
+        return taps
+
+    def pass_taps(self, tokens, past_len=0, compute_logits=True, score=False, top_n=0):
+        """zg_debug_gpt_pass_taps: extend(past_len, tokens, compute_logits) — or, with score, score(tokens, past_len, top_n,
+        want_logits=True) without the fetch of the records — with every launch of the pass tapped.  Returns (taps, info, logits):
+        taps as step_taps (in launch order; include/zgpt2.h lists the classes), info by name (_lib.PASS_INFO), logits [batch, V] of
+        the last new position (None without compute_logits), or [batch, n, V] of every position for score."""
+        tokens = np.ascontiguousarray(np.atleast_2d(tokens), dtype=np.uint64)
+        assert tokens.shape[0] == self.batch
+        n_tok = tokens.shape[1]
+        logits = np.empty((self.batch, n_tok, self.config.vocab_size), np.float32) if score else self._logits_buf(compute_logits, True)
+        used, n = C.c_size_t(), C.c_size_t()
+        info = np.zeros(len(_lib.PASS_INFO), np.int32)
+        head = (self.h, past_len, ptr(tokens), n_tok, n_tok, int(compute_logits), int(score), int(top_n), ptr(logits), ops._n(logits))
+        check(self._L.zg_debug_gpt_pass_taps(*head, None, 0, C.byref(used), None, 0, C.byref(n), ptr(info), info.size))
+        arena = np.zeros(used.value, np.uint8)
+        table = (_lib.TapEntry * n.value)()
+        check(self._L.zg_debug_gpt_pass_taps(*head, ptr(arena), arena.size, C.byref(used), C.addressof(table), n.value, C.byref(n), ptr(info), info.size))
+        return self._tap_list(arena, table, n.value), dict(zip(_lib.PASS_INFO, (int(v) for v in info))), logits
 
     def cached_len(self):
         """Positions the handle's caches hold (zg_gpt_cached_len)."""
