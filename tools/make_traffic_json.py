@@ -16,9 +16,10 @@ CLASSES = {
     "124M/1/bf16": ("124m", {
         "ln_1 + c_attn + KV append": r"gemv_lnk_kernel<unsigned short, 16, 2, 4>",
         "attention (split-KV decode)": r"attn_decode_kernel<float>",
-        "head merge + attn c_proj + residual": r"gemv_ksplit_kernel<unsigned short, 16, 2, 2>",
+        # (one instantiation per split count, <..., NS, NH>: the first row is the one with the most time, four splits)
+        "head merge + attn c_proj + residual": r"gemv_ksplit_kernel<unsigned short, 16, 2, 2, \d, \d>",
         "ln_2 + c_fc + GELU": r"gemv_lnk_kernel<unsigned short, 16, 2, 4>",
-        "mlp c_proj + residual": r"gemv_ksplit_kernel<unsigned short, 32, 3, 2>",
+        "mlp c_proj + residual": r"gemv_ksplit_kernel<unsigned short, 32, 3, 2, 0, 0>",
         "ln_f + lm_head + argmax": r"gemv_kernel<unsigned short, 1, 16, 6, true>",
     }),
     "124M/8/bf16": ("124m_8prompts", {
@@ -34,7 +35,7 @@ CLASSES = {
         "attention (split-KV decode)": r"attn_decode_kernel<float>",
         "head merge + attn c_proj + residual": r"gemv_kernel<unsigned short, 1, 32, 8, false>",
         "ln_2 + c_fc + GELU": r"gemv_lnk_kernel<unsigned short, 32, 2, 4>",
-        "mlp c_proj + residual": r"gemv_ksplit_kernel<unsigned short, 32, 7, 2>",
+        "mlp c_proj + residual": r"gemv_ksplit_kernel<unsigned short, 32, 7, 2, 0, 0>",
         "ln_f + lm_head + argmax": r"gemv_kernel<unsigned short, 1, 32, 8, true>",
     }),
 }

@@ -286,14 +286,19 @@ __device__ __forceinline__ float load_emb(const void* w, int wt, size_t off) {
 // Latency-bound: the argmax partials of the previous step are fetched speculatively together with
 // the control words (one memory round trip), one wave per sequence; only the wte row depends on
 // the chosen token (second round trip).
-__global__ __launch_bounds__(512) void embed_step_kernel(const EmbedArgs a) {
+__global__ __launch_bounds__(512) void embed_step_kernel(StepCtrl* ctrl, const float* part_val, const int* part_idx, int part_stride, int n_partials,
+                                                         const int* prompt, const int* prompt_len, int batch, int prompt_stride, const EmbedArgs a) {
+    // 14 preloaded dwords (zg_common.h ZG_PIN, rule 1): what the loads at entry are addressed by — the control block, the argmax
+    // partials with their count and stride, the prompt rows — so the control words and the partials leave in one round trip.  `a`
+    // is the whole block as the host fills it (launch_embed_step passes those nine again as its leading parameters); the kernel
+    // reads only its other fields from it, pinned under the partial loads.
     __shared__ int s_tok[8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int s = a.ctrl->step;
-    const int mode = a.ctrl->mode;
-    const int npart = a.n_partials;
-    const int n_waves = a.batch > 4 ? 8 : 4;  // as launched (blockDim is a scalar load from the kernarg segment)
-    for (int b = wave; b < a.batch; b += n_waves) {
+    const int s = ctrl->step;
+    const int mode = ctrl->mode;
+    const int npart = n_partials;
+    const int n_waves = batch > 4 ? 8 : 4;  // as launched (blockDim is a scalar load from the kernarg segment)
+    for (int b = wave; b < batch; b += n_waves) {
         // speculative fetch of this sequence's partial maxima (valid memory whether or not needed)
         float bv = -3.0e38f;
         int bi = 0x7fffffff;
@@ -305,17 +310,18 @@ __global__ __launch_bounds__(512) void embed_step_kernel(const EmbedArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int p = min(base + lane + 64 * j, npart - 1);
-                pv[j] = a.part_val[(size_t)b * a.part_stride + p];
-                pi[j] = a.part_idx[(size_t)b * a.part_stride + p];
+                pv[j] = part_val[(size_t)b * part_stride + p];
+                pi[j] = part_idx[(size_t)b * part_stride + p];
+            }
+            {   // the argument-block fields used further down, fetched under the partial-maxima loads (zg_common.h ZG_PIN, rule 2)
+                ZG_PIN(a.forced); ZG_PIN(a.wte); ZG_PIN(a.wpe); ZG_PIN(a.weight_type); ZG_PIN(a.n_embed); ZG_PIN(a.cur_token); ZG_PIN(a.out_tokens);
+                ZG_PIN(a.out_stride); ZG_PIN(a.x); ZG_PIN(a.pl_out); ZG_PIN(a.pl_g); ZG_PIN(a.epoch); ZG_PIN(a.finish_only); ZG_PIN(a.st_out); ZG_PIN(a.vocab);
+                ZG_PIN(a.progress); ZG_PIN(a.sampled);
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {  // (a clamped duplicate of the last partial changes nothing)
                 if (pv[j] > bv || (pv[j] == bv && pi[j] < bi)) { bv = pv[j]; bi = pi[j]; }
             }
-        }
-        {   // the argument-block fields used behind the partial-maxima loads (zg_common.h ZG_PIN)
-            ZG_PIN(a.forced); ZG_PIN(a.wte); ZG_PIN(a.wpe); ZG_PIN(a.weight_type); ZG_PIN(a.n_embed); ZG_PIN(a.cur_token); ZG_PIN(a.out_tokens);
-            ZG_PIN(a.out_stride); ZG_PIN(a.x); ZG_PIN(a.pl_out); ZG_PIN(a.pl_g); ZG_PIN(a.epoch); ZG_PIN(a.finish_only); ZG_PIN(a.st_out); ZG_PIN(a.vocab);
         }
         if (b == 0 && a.progress != nullptr && a.finish_only == 0 && lane == 0) {
             // a step at sequence length s + 1 starts; block 0 of every launch of this queue lands on the XCD this block is on
@@ -327,9 +333,9 @@ __global__ __launch_bounds__(512) void embed_step_kernel(const EmbedArgs a) {
             reinterpret_cast<PfCtl*>(a.progress)->xcd_log[0] = 0x100u | xcc;
 #endif
         }
-        const int np = a.prompt_len ? a.prompt_len[b] : 0;
-        const int p_cur = a.prompt[(size_t)b * a.prompt_stride + min(s, a.prompt_stride - 1)];
-        const int p_last = a.prompt[(size_t)b * a.prompt_stride + max(min(np, a.prompt_stride) - 1, 0)];
+        const int np = prompt_len ? prompt_len[b] : 0;
+        const int p_cur = prompt[(size_t)b * prompt_stride + min(s, prompt_stride - 1)];
+        const int p_last = prompt[(size_t)b * prompt_stride + max(min(np, prompt_stride) - 1, 0)];
         const int forced = a.forced[b];
         const int drawn = a.sampled[b];  // (mode 2; always a readable address)
         // argmax over the wave: DPP row rotations inside the 16-lane rows, then the four row winners through v_readlane
@@ -378,7 +384,7 @@ __global__ __launch_bounds__(512) void embed_step_kernel(const EmbedArgs a) {
     }
     if (a.finish_only == 1 || a.finish_only == 2) return;
     __syncthreads();
-    const int total4 = a.batch * (a.n_embed >> 2);
+    const int total4 = batch * (a.n_embed >> 2);
     for (int i = threadIdx.x; i < total4; i += 64 * n_waves) {
         const int b = i / (a.n_embed >> 2), e = (i % (a.n_embed >> 2)) * 4;
         const int tok = s_tok[b];
@@ -417,8 +423,8 @@ __global__ __launch_bounds__(512) void embed_step_kernel(const EmbedArgs a) {
     }
     if (threadIdx.x == 0 && a.epoch) *a.epoch += 1u;  // a step starts: new tags for its hand-overs
     if (threadIdx.x == 0 && a.finish_only == 0) {
-        a.ctrl->seq_len = s + 1;
-        a.ctrl->step = s + 1;
+        ctrl->seq_len = s + 1;
+        ctrl->step = s + 1;
     }
 }
 
@@ -910,7 +916,8 @@ int launch_wte_planes(const void* wte, int weight_type, size_t V, size_t V64, in
 }
 
 int launch_embed_step(const EmbedArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(embed_step_kernel, dim3(1), dim3(a.batch > 4 ? 512 : 256), 0, s, a);  // one wave per sequence
+    hipLaunchKernelGGL(embed_step_kernel, dim3(1), dim3(a.batch > 4 ? 512 : 256), 0, s, a.ctrl, a.part_val, a.part_idx, a.part_stride, a.n_partials,
+                       a.prompt, a.prompt_len, a.batch, a.prompt_stride, a);  // one wave per sequence
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

@@ -165,6 +165,7 @@ GemvPlan gemv_plan(const GemvArgs& a, int weight_type) {
              // plain Linear over a wide input (measured against the shared-strip form in situ)
              : a.prologue == PRO_NONE && a.K >= 2048 && nchq <= 256)) {
         take(GR_KSPLIT, rung(kKsplitLadder, nchq), 2);  // two passes of 64 / LPR rows per workgroup (four measured slower: 2.65 -> 3.3 us for mlp c_proj)
+        p.merge_generic = (off & 128) != 0, p.merge_ml_vector = (off & 256) != 0;  // (launch_ksplit: which merge prologue)
     } else if (a.M == 1 && a.prologue == PRO_LAYERNORM && a.ln_c2 != nullptr && a.ln_c3 != nullptr &&
                (a.epilogue == EPI_STORE || a.epilogue == EPI_GELU || a.epilogue == EPI_QKV) && a.K % 32 == 0 && nchq <= 128 && a.N <= 16384) {
         take(GR_LNK, rung(kLnkLadder, nchq), 4);  // four passes (2.93 against 3.2 us per launch with two; +1 % tokens/s in situ)

@@ -1,4 +1,6 @@
 // gemv_ksplit.hip — M == 1: the K-split kernel (wide plain inputs, the head-merging c_proj) and the linearised-LayerNorm kernel; see gemv.hip
+#include <algorithm>
+
 #include "gemv_internal.h"
 
 namespace zg {
@@ -14,7 +16,28 @@ namespace {
 // straight from global memory into registers (fetched next to the weights, no LDS, no barrier), every wave streams
 // the same 2 * RPP rows (quarter-row segments of >= 1.5 KB, fully coalesced), and the four partial sums per row
 // meet in LDS after the arithmetic, where one thread per row runs the epilogue.
-template <typename WT, int LPR, int CPL, int NP = 2>  // NP passes of 64 / LPR rows per workgroup
+//
+// The input prologue is the compile-time NS (launch_ksplit picks it; a captured graph has one t_hi per bucket, so one NS):
+//   NS == 0               plain input row (mlp c_proj): no merge code in the instantiation
+//   NS == 1 .. 4          attn c_proj: the input is the head merge of exactly NS attention split partials
+//   NS == kNsGeneric      the merge as it was before NS existed: four slots whatever the split count, read from `em` — kept as
+//                         the reference of tests/test_merge_splits_gpu.py and the A/B switch (ZGPT2_DECODE_PATHS_OFF bit 128)
+// NH (NS 1..4 only): how the (m, l) words of a partial reach the lanes.  0: every lane loads those of its own chunks (vector
+// loads).  1..4: they are the same for every lane whose chunk lies in the same head, and a wave's K quarter touches at most NH
+// heads, so the wave fetches NH x NS pairs with wave-uniform (scalar) loads and every lane selects its head's.
+constexpr int kNsGeneric = 5;
+
+// One chunk's 8 merged-input elements from the partials: the loads of split partial `ps` (d0 = the chunk's offset in its head)
+__device__ __forceinline__ W8 load_part8(const float* ps, int d0) {
+    const float2 a0 = *reinterpret_cast<const float2*>(ps + d0), a1 = *reinterpret_cast<const float2*>(ps + d0 + 2);
+    const float2 a2 = *reinterpret_cast<const float2*>(ps + d0 + 4), a3 = *reinterpret_cast<const float2*>(ps + d0 + 6);
+    W8 o;
+    o.v[0] = a0.x; o.v[1] = a0.y; o.v[2] = a1.x; o.v[3] = a1.y;
+    o.v[4] = a2.x; o.v[5] = a2.y; o.v[6] = a3.x; o.v[7] = a3.y;
+    return o;
+}
+
+template <typename WT, int LPR, int CPL, int NP, int NS, int NH>  // NP passes of 64 / LPR rows per workgroup
 __global__ __launch_bounds__(256) void gemv_ksplit_kernel(const void* __restrict__ Wv, const float* __restrict__ xin, int N,
                                                           int K, unsigned em, const float* __restrict__ part_in, int max_splits,
                                                           const float* __restrict__ bias, const float* __restrict__ resid,
@@ -25,10 +48,11 @@ __global__ __launch_bounds__(256) void gemv_ksplit_kernel(const void* __restrict
     const int has_bias = (int)((em >> 16) & 1u), has_resid = (int)((em >> 17) & 1u);
     ZG_STAMP_DECL();
     ZG_STAMP(0);
-    // merge_splits > 0 (attn c_proj): the input is the head merge of the attention partials — every lane combines
+    // NS > 0 (attn c_proj): the input is the head merge of the attention partials — every lane combines
     // the <= 4 split partials of ITS OWN 8-element chunks (a chunk lies inside one head), all loads issued with the
     // weights; no shared strip, no barrier in front of the FMAs (the merge through an LDS strip cost 3.9 us per
     // launch against 2.55 us for the plain K-split kernel).
+    static_assert(NS >= 0 && NS <= kNsGeneric && NH >= 0 && NH <= 4 && (NH == 0 || (NS >= 1 && NS <= 4)), "see the table above");
     constexpr int RPP = 64 / LPR, ROWS = NP * RPP;
     __shared__ float part[4][ROWS];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -46,7 +70,66 @@ __global__ __launch_bounds__(256) void gemv_ksplit_kernel(const void* __restrict
         for (int i = 0; i < CPL; ++i) wq[p][i] = load_raw(pr, min(lr + LPR * i, nchq - 1));
     }
     W8 xr[CPL];
-    if (merge_splits > 0) {
+    if constexpr (NS >= 1 && NS < kNsGeneric) {
+        // Exactly NS partials per chunk, every load unconditional.  The arithmetic is the generic prologue's (next branch), term
+        // by term — the maximum over the present m, weights __expf(m_s - mx), FMAs in split order, one reciprocal — without its
+        // surplus slots.  Those re-read a present partial with m = -1e30: weight __expf(-1e30 - mx) == 0 for every mx > -1e30
+        // (any finite attention score), so each added fmaf(0, finite, r) == r to l and to every element (r starts at +0, and an
+        // FMA onto +0 never yields -0).  The condition is a finite partial; a non-finite one poisons the result through its own
+        // term in both forms.
+        float2 mlh[NH > 0 ? NH : 1][NS];
+        const int h0w = (wave * Kq) >> 6;  // first head of this wave's K quarter: wave-uniform (`wave` went through readfirstlane)
+        if constexpr (NH > 0) {
+            const int hlast = (K >> 6) - 1;
+#pragma unroll
+            for (int j = 0; j < NH; ++j) {
+                const int hj = min(h0w + j, hlast);  // (a quarter that touches fewer heads re-reads its last)
+#pragma unroll
+                for (int sp = 0; sp < NS; ++sp)
+                    mlh[j][sp] = *reinterpret_cast<const float2*>(part_in + ((size_t)hj * max_splits + sp) * kPartStride + 64);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int e0 = wave * Kq + min(lr + LPR * i, nchq - 1) * 8;
+            const int h = e0 >> 6, d0 = e0 & 63;  // head_dim 64
+            const float* p = part_in + ((size_t)h * max_splits) * kPartStride;
+            float ms[NS], ls[NS];
+            W8 o[NS];
+#pragma unroll
+            for (int sp = 0; sp < NS; ++sp) {
+                const float* ps = p + sp * kPartStride;
+                o[sp] = load_part8(ps, d0);
+                if constexpr (NH == 0) {
+                    ms[sp] = ps[64];
+                    ls[sp] = ps[65];
+                } else {
+                    float2 ml = mlh[0][sp];
+#pragma unroll
+                    for (int j = 1; j < NH; ++j)
+                        if (h - h0w >= j) ml = mlh[j][sp];
+                    ms[sp] = ml.x;
+                    ls[sp] = ml.y;
+                }
+            }
+            float mx = ms[0];
+            if constexpr (NS == 2) mx = fmaxf(ms[0], ms[1]);
+            if constexpr (NS == 3) mx = fmaxf(fmaxf(ms[0], ms[1]), ms[2]);
+            if constexpr (NS == 4) mx = fmaxf(fmaxf(ms[0], ms[1]), fmaxf(ms[2], ms[3]));
+            float l = 0.0f;
+            W8 r = zero_w8();
+#pragma unroll
+            for (int sp = 0; sp < NS; ++sp) {
+                const float w = __expf(ms[sp] - mx);
+                l = fmaf(w, ls[sp], l);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) r.v[j] = fmaf(w, o[sp].v[j], r.v[j]);
+            }
+            const float inv = 1.0f / l;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) xr[i].v[j] = r.v[j] * inv;
+        }
+    } else if constexpr (NS == kNsGeneric) {
         constexpr int MAXS = 4;
         const int nsplit = merge_splits;
 #pragma unroll
@@ -61,10 +144,7 @@ __global__ __launch_bounds__(256) void gemv_ksplit_kernel(const void* __restrict
                 const float* ps = p + min(sp, nsplit - 1) * kPartStride;
                 ms[sp] = ps[64];
                 ls[sp] = ps[65];
-                const float2 a0 = *reinterpret_cast<const float2*>(ps + d0), a1 = *reinterpret_cast<const float2*>(ps + d0 + 2);
-                const float2 a2 = *reinterpret_cast<const float2*>(ps + d0 + 4), a3 = *reinterpret_cast<const float2*>(ps + d0 + 6);
-                o[sp].v[0] = a0.x; o[sp].v[1] = a0.y; o[sp].v[2] = a1.x; o[sp].v[3] = a1.y;
-                o[sp].v[4] = a2.x; o[sp].v[5] = a2.y; o[sp].v[6] = a3.x; o[sp].v[7] = a3.y;
+                o[sp] = load_part8(ps, d0);
             }
 #pragma unroll
             for (int sp = 0; sp < MAXS; ++sp)
@@ -141,24 +221,41 @@ int launch_ksplit(const GemvArgs& a, const GemvPlan& pl, hipStream_t s) {
     const int merge_splits = a.prologue == PRO_ATTN_MERGE ? (a.t_hi + kAttnChunk - 1) / kAttnChunk : 0;
     const unsigned has_resid = a.epilogue == EPI_RESIDUAL ? 1u : 0u;
     const unsigned em = (unsigned)a.epilogue | ((unsigned)merge_splits << 8) | ((a.bias ? 1u : 0u) << 16) | (has_resid << 17);
+    // The merge prologue's instantiation: NS = the split count (gemv_plan admits the merge for 1..4 splits only), or the generic
+    // four-slot form where the plan keeps it.  NH = the most heads a wave's K quarter touches, where the scalar fetch of (m, l)
+    // pays: at most Kq / 64 + 1 of them (whole heads, E = 768 / 1024; inside one head, E = 128; E = 384 straddles into 2) and
+    // at most the 4 the kernel is instantiated for — otherwise 0, the lanes' own vector loads.
+    int ns = merge_splits, nh = 0;
+    if (merge_splits > 0 && (pl.merge_generic || merge_splits > 4)) ns = kNsGeneric;
+    if (ns >= 1 && ns <= 4 && !pl.merge_ml_vector) {
+        const int Kq = a.K >> 2;
+        for (int w = 0; w < 4; ++w) nh = std::max(nh, (((w + 1) * Kq - 1) >> 6) - ((w * Kq) >> 6) + 1);
+        if (nh > Kq / 64 + 1 || nh > 4) nh = 0;
+    }
     // two passes of 64 / LPR rows per workgroup
-#define ZG_KS(LPR_, CPL_)                                                                                                \
-    if (pl.lpr == LPR_ && pl.cpl == CPL_) {                                                                              \
-        note_kernel("gemv_ksplit_kernel<%s, %d, %d, 2>", wt_name<WT>(), LPR_, CPL_);         \
-        hipLaunchKernelGGL((gemv_ksplit_kernel<WT, LPR_, CPL_, 2>), dim3(pl.grid), dim3(256), 0, s, a.W,                     \
-                           a.x,                                                                                         \
+#define ZG_KS(LPR_, CPL_, NS_, NH_)                                                                                      \
+    if (pl.lpr == LPR_ && pl.cpl == CPL_ && ns == NS_ && nh == NH_) {                                                    \
+        note_kernel("gemv_ksplit_kernel<%s, %d, %d, 2, %d, %d>", wt_name<WT>(), LPR_, CPL_, NS_, NH_);                   \
+        hipLaunchKernelGGL((gemv_ksplit_kernel<WT, LPR_, CPL_, 2, NS_, NH_>), dim3(pl.grid), dim3(256), 0, s, a.W, a.x,  \
                            a.N, a.K, em, a.part ? a.part : a.zero, a.max_splits, a.bias ? a.bias : a.zero,              \
                            has_resid ? a.resid : a.zero, a);                                                             \
         ZG_HIP(hipGetLastError());                                                                                       \
         return ZG_OK;                                                                                                    \
     }
-    ZG_KS(16, 2)
-    ZG_KS(32, 3)
-    ZG_KS(32, 5)
-    ZG_KS(32, 7)
-    ZG_KS(64, 4)
+#define ZG_KS_MERGE(NS_) ZG_KS(16, 2, NS_, 0) ZG_KS(16, 2, NS_, 1) ZG_KS(16, 2, NS_, 2) ZG_KS(16, 2, NS_, 3) ZG_KS(16, 2, NS_, 4)
+    // the merge (K <= 1024: at most 32 chunks per quarter) lives on the first rung, the wide plain inputs (K >= 2048) on the others
+    ZG_KS_MERGE(1)
+    ZG_KS_MERGE(2)
+    ZG_KS_MERGE(3)
+    ZG_KS_MERGE(4)
+    ZG_KS(16, 2, kNsGeneric, 0)
+    ZG_KS(32, 3, 0, 0)
+    ZG_KS(32, 5, 0, 0)
+    ZG_KS(32, 7, 0, 0)
+    ZG_KS(64, 4, 0, 0)
+#undef ZG_KS_MERGE
 #undef ZG_KS
-    zg::set_error("gemv (K split): no instantiation for K=%d", a.K);
+    zg::set_error("gemv (K split): no instantiation for K=%d, %d merge splits", a.K, merge_splits);
     return ZG_ERR_UNSUPPORTED;
 }
 

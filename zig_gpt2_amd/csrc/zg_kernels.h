@@ -133,6 +133,10 @@ struct GemvPlan {
     bool can_take_planes;   // may take its input rows as planes (GemvArgs.pl_in)
     bool can_write_planes;  // may write its output rows as planes (GemvArgs.pl_out)
     bool pl4_with_planes;   // given input planes it runs as the four-wave kernel (the one that reads / writes the tile statistics)
+    // launcher matters of GR_KSPLIT's head merge (not among the fields zg_debug_gemv_plan reports): the four-slot prologue that
+    // serves any split count instead of the one specialised by it (ZGPT2_DECODE_PATHS_OFF bit 128), and the specialised one's
+    // (m, l) words through the lanes' vector loads instead of wave-uniform ones (bit 256)
+    bool merge_generic, merge_ml_vector;
 };
 // Pure host code: no HIP call, no allocation.  Reads ZGPT2_DECODE_PATHS_OFF once (per call: tests flip it between handles).
 GemvPlan gemv_plan(const GemvArgs& a, int weight_type);
@@ -368,7 +372,8 @@ size_t sample_workspace_floats(int batch);
 // Decode-step head kernel: token selection (+ argmax finalisation of the previous step) and
 // x = wte[token] + wpe[pos].
 struct EmbedArgs {
-    // the first 14 dwords are preloaded into SGPRs (zg_common.h ZG_PIN): what the first loads of the kernel depend on
+    // these nine (14 dwords) are what the first loads of the kernel depend on: launch_embed_step hands them to the kernel as
+    // leading scalar parameters, which are preloaded into SGPRs (zg_common.h ZG_PIN) — a by-value block never is
     StepCtrl* ctrl;
     const float* part_val;   // [B][n_partials]
     const int* part_idx;
@@ -378,7 +383,7 @@ struct EmbedArgs {
     const int* prompt_len;   // [B]
     int batch;
     int prompt_stride;
-    // ... the rest is fetched from the kernarg segment under those loads
+    // ... the rest the kernel reads from the block it is passed, fetched from the kernarg segment under those loads
     const int* forced;       // [B] (mode 1)
     const void* wte;  // [V][E] bf16, fp32 or B24
     const void* wpe;  // [ctx][E]
