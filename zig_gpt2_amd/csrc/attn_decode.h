@@ -76,6 +76,34 @@ __device__ __forceinline__ float row16_reduce_scatter(float (&s)[16], int lr) {
     }
 }
 
+// Diagnostic build (-DZG_STAMPS; tools/kernel_stamps.py): lane 0 of every wave of the attention workgroups of head 0 records
+// s_memtime at t0 entry, t1 K / V loads issued, t2 first poll round back, t3 tags matched, t4 arithmetic done, t5 published (wave
+// 0; the others: behind the barrier), then the rounds consumed and whether it held row T - 1; word 8 = 0x10000 | split << 4 | wave.
+#ifdef ZG_STAMPS
+#define ZG_ASTAMP_DECL() unsigned long long zg_at[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define ZG_ASTAMP(i) zg_at[i] = __builtin_amdgcn_s_memtime()
+#define ZG_ASTAMP_SET(i, v) zg_at[i] = (v)
+// (behind the round's verdict, so behind the wait for its loads; bit 0: that round did not match)
+#define ZG_ASTAMP_FIRST_ROUND(i, spins, ok) \
+    if ((spins) == 0) zg_at[i] = (ok) ? __builtin_amdgcn_s_memtime() & ~1ull : __builtin_amdgcn_s_memtime() | 1ull
+#define ZG_ASTAMP_FLUSH()                                                                  \
+    if (FUSED && a.dbg && h == 0 && lane == 0) {                                           \
+        const unsigned long long slot = atomicAdd(a.dbg, 1ull);                            \
+        if (slot < 4096) {                                                                 \
+            unsigned long long* d = a.dbg + 16 + slot * 10;                                \
+            for (int i = 0; i < 8; ++i) d[i] = zg_at[i];                                   \
+            d[8] = 0x10000ull | ((unsigned long long)split << 4) | (unsigned long long)wave; \
+            d[9] = __builtin_amdgcn_s_memtime();                                           \
+        }                                                                                  \
+    }
+#else
+#define ZG_ASTAMP_DECL()
+#define ZG_ASTAMP(i)
+#define ZG_ASTAMP_SET(i, v)
+#define ZG_ASTAMP_FIRST_ROUND(i, spins, ok)
+#define ZG_ASTAMP_FLUSH()
+#endif
+
 // Wave 0 of a split hands over its partial (o[lane], M, l).  Op tier / one sequence: plain stores, the consumer merges
 // (attn_merge_kernel, or the c_proj prologue).  Lock-step batch with activation planes (AttnArgs.pl_out): the LAST split
 // of (b, h) to arrive merges all of them — same arithmetic as merge_attn4 in gemv_internal.h: weights exp(m_s - max m), sums
@@ -282,6 +310,8 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
 
     float m_w = kNegBig, l_w = 0.0f;
     f32x4 o4 = {0.0f, 0.0f, 0.0f, 0.0f};
+    ZG_ASTAMP_DECL();
+    ZG_ASTAMP(0);
     if (base < t_hi) {
         // ---- all K and V loads up front: position t = base + 4*i + g, dims 4*lr .. 4*lr+3
         // Branch-free: positions at or beyond t_hi re-read the last valid row (their probability is exactly 0 below: t >= t_hi
@@ -297,6 +327,7 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
         }
         ZG_PIN(a.progress); ZG_PIN(a.part); ZG_PIN(a.max_splits); ZG_PIN(a.pl_out); ZG_PIN(a.part_tag); ZG_PIN(a.launch_id); ZG_PIN(a.merge_cnt); ZG_PIN(a.fault); ZG_PIN(a.spin_limit);
         pf_count(a.progress);
+        ZG_ASTAMP(1);
         if (FUSED) {
             // ---- this step's q of head h and, in the wave that holds position T - 1, the new k / v row: (value, tag) words the
             // c_attn workgroups of this launch store (gemv_lnk_body TAGGED), polled with a bound behind the K / V loads above.
@@ -312,7 +343,8 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
             const bool holder = (unsigned)rel < 64u;
             const u64* wq = qkv_tag + h * 64 + lr * 4;
             u64 wv[12];
-            for (unsigned spins = 0;; ++spins) {
+            unsigned spins = 0;
+            for (;; ++spins) {
                 bool ok = true;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -327,13 +359,18 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
                         ok = ok && (unsigned)(wv[4 + j] >> 32) == tag && (unsigned)(wv[8 + j] >> 32) == tag;
                     }
                 }
-                if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
+                const bool all = __builtin_amdgcn_ballot_w64(!ok) == 0;
+                ZG_ASTAMP_FIRST_ROUND(2, spins, all);
+                if (all) break;
                 if (spins >= a.spin_limit) {  // bounded: never hang the queue — and never pass silently (check_fault)
                     if (lane == 0 && a.fault) __hip_atomic_store(a.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     break;
                 }
                 __builtin_amdgcn_s_sleep(1);
             }
+            ZG_ASTAMP(3);
+            ZG_ASTAMP_SET(6, spins + 1);
+            ZG_ASTAMP_SET(7, (unsigned long long)holder);
             q4 = f32x4{__uint_as_float((unsigned)wv[0]), __uint_as_float((unsigned)wv[1]), __uint_as_float((unsigned)wv[2]),
                        __uint_as_float((unsigned)wv[3])};
             if (holder && g == (rel & 3)) {
@@ -379,6 +416,7 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
         o4.z += __shfl_xor(o4.z, 16, 64); o4.w += __shfl_xor(o4.w, 16, 64);
         o4.x += __shfl_xor(o4.x, 32, 64); o4.y += __shfl_xor(o4.y, 32, 64);
         o4.z += __shfl_xor(o4.z, 32, 64); o4.w += __shfl_xor(o4.w, 32, 64);
+        ZG_ASTAMP(4);
     }
     if (lane < 16) *reinterpret_cast<f32x4*>(&s_o[wave][lane * 4]) = o4;
     if (lane == 0) {
@@ -397,6 +435,8 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
         }
         publish_partial(a, n_heads, (t_hi + kAttnChunk - 1) / kAttnChunk, b, h, split, lane, o, M, l, (epoch << 8) | a.launch_id);
     }
+    ZG_ASTAMP(5);
+    ZG_ASTAMP_FLUSH();
 }
 
 }  // namespace

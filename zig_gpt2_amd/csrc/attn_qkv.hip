@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void attn_qkv_kernel(const void* __restrict__ 
     const unsigned blk = blockIdx.x;
     if (blk < (kg >> 16)) {
         gemv_lnk_body<WT, LPR, CPL, 4, true>((int)blk, Wv, xin, ne, (int)(kg & 0xffffu), ln_g, c2, c3, cw, a, 2u, f.qkv_tag, f.ew,
-                                             f.at.launch_id);
+                                             f.at.launch_id, (f.at.tail_off & kAttnTailStoreLast) == 0);
         return;
     }
     if (blk < f.a0) return;

@@ -404,12 +404,14 @@ __device__ __forceinline__ void store_split4(char* planes, int S, int m, int k, 
 // ln_1 + c_attn + attention kernel (attn_qkv.hip).  blk = the workgroup's row block; pf_inc = what block 0 adds to the
 // prefetcher's launch counter.  TAGGED (EPI_QKV, one sequence): every output row is also stored as a (value, tag) word at
 // tagw[n], tag = *ew << 8 | launch_id, with an agent-scope relaxed store — the hand-over to the attention workgroups of the
-// same launch.  The value is the one the epilogue stored to q / the caches.
+// same launch.  The value is the one the epilogue stores to q / the caches; tag_first: the word is stored in front of them
+// (AttnArgs.tail_off kAttnTailStoreLast clear).
 template <typename WT, int LPR, int CPL, int NP, bool TAGGED>
 __device__ __forceinline__ void gemv_lnk_body(int blk, const void* __restrict__ Wv, const float* __restrict__ xin, unsigned ne, int K,
                                               const float* __restrict__ ln_g, const float* __restrict__ c2, const float* __restrict__ c3,
                                               const int* __restrict__ cw, const GemvArgs& a, unsigned pf_inc,
-                                              unsigned long long* __restrict__ tagw, const unsigned* __restrict__ ew, unsigned launch_id) {
+                                              unsigned long long* __restrict__ tagw, const unsigned* __restrict__ ew, unsigned launch_id,
+                                              bool tag_first = false) {
     const int N = (int)(ne & 0xffffffu), epilogue = (int)(ne >> 24);
     ZG_STAMP_DECL();
     ZG_STAMP(0);
@@ -462,7 +464,7 @@ __device__ __forceinline__ void gemv_lnk_body(int blk, const void* __restrict__ 
             ZG_PIN(a.q); ZG_PIN(a.k_cache); ZG_PIN(a.v_cache); ZG_PIN(a.N); ZG_PIN(a.head_dim); ZG_PIN(a.n_heads); ZG_PIN(a.ctx); ZG_PIN(a.kv_mode); ZG_PIN(a.kv_lo);
         }
     }
-    if (TAGGED) { ZG_PIN(tagw); ZG_PIN(launch_id); }
+    if (TAGGED) { ZG_PIN(tagw); ZG_PIN(launch_id); ZG_PIN((unsigned)tag_first); }
     pf_count(a.progress, pf_inc);
     ZG_STAMP(2);
     // statistics of this wave's quarter (every LPR-lane group holds the whole quarter) and z = g x
@@ -517,10 +519,15 @@ __device__ __forceinline__ void gemv_lnk_body(int blk, const void* __restrict__ 
         const float S1 = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
         const float y = fmaf(rstd, fmaf(-mean, c2n, S1), c3n);
         Best nobest;
-        const float v = epilogue_row(a, 0, n, y, 0.0f, 0.0f, T - 1, nobest);
-        if (TAGGED)
-            __hip_atomic_store(tagw + n, ((unsigned long long)((epoch << 8) | launch_id) << 32) | __float_as_uint(v), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+        // TAGGED: the word the attention workgroups of this launch wait for leaves FIRST (tag_first), in front of the epilogue's
+        // address arithmetic and its q / cache store: it carries the epilogue's own value, acc + bias with the bias in c3
+        const float bias_n = 0.0f;
+        const unsigned long long tagged_hi = (unsigned long long)((epoch << 8) | launch_id) << 32;
+        if (TAGGED && tag_first)
+            __hip_atomic_store(tagw + n, tagged_hi | __float_as_uint(y + bias_n), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const float v = epilogue_row(a, 0, n, y, bias_n, 0.0f, T - 1, nobest);
+        if (TAGGED && !tag_first)
+            __hip_atomic_store(tagw + n, tagged_hi | __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     ZG_STAMP(5);
     ZG_STAMP(6);

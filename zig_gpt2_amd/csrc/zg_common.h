@@ -19,7 +19,9 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 // 1 activation planes between kernels, 2 the four-wave plane-fed Linear, 4 tagged hand-overs (tickets instead), 8 LayerNorm
 // statistics by tile, 16 line-shaped weight loads, 32 the wave-per-tile lm_head; and at batch 1: 64 ln_1 + c_attn and the attention
 // as one launch (attn_qkv.hip) — set, they run as two; 128 the head merge of attn c_proj specialised by split count — set, the
-// four-slot prologue that serves every count (gemv_ksplit.hip); 256 its (m, l) words by wave-uniform loads — set, by the lanes' own.
+// four-slot prologue that serves every count (gemv_ksplit.hip); 256 its (m, l) words by wave-uniform loads — set, by the lanes' own;
+// 512 the fused launch's c_attn role stores its tagged word in front of the q / cache store — set, behind it (read once at create:
+// zg_kernels.h kAttnTailStoreLast).
 int decode_paths_off();
 
 #define ZG_HIP(expr)                                                         \
