@@ -1,4 +1,4 @@
-"""The float64 side of the stage tests (test_decode_stages_gpu.py, test_pass_stages_gpu.py and their *_cases_cpu.py): decoders of the raw
+"""The float64 side of the stage tests (test_decode_stages_gpu.py, test_pass_stages_gpu.py, test_op_stages_gpu.py and their *_cases_cpu.py): decoders of the raw
 buffers a tapped decode step or whole-prompt pass returns (zg_debug_gpt_step_taps, zg_debug_gpt_pass_taps) and plain numpy float64 versions of each stage,
 written from the operations' definitions (LayerNorm, Linear, split_qkv, softmax attention, the merge of split partials,
 tanh-GELU, the residual add) — nothing here calls the library.
@@ -169,11 +169,11 @@ def split_qkv(y, E):
     return y[:, :E], y[:, E:2 * E], y[:, 2 * E:]
 
 
-def attention(q, K, V, dtype=np.float64):
-    """Softmax attention of one new position over the cache: q [B][H][64], K / V [B][H][T][64] -> out [B][H][64] and the l2
-    norm of the weighted V terms (always float64)."""
+def attention(q, K, V, dtype=np.float64, scale=0.125):
+    """Softmax attention of one new position over the cache: q [B][H][D], K / V [B][H][T][D] -> out [B][H][D] and the l2
+    norm of the weighted V terms (always float64).  scale = 1 / sqrt(D): 0.125 for the model tier's 64."""
     q, K, V = (np.asarray(t, dtype) for t in (q, K, V))
-    sc = np.einsum("bhd,bhtd->bht", q, K) * dtype(0.125)
+    sc = np.einsum("bhd,bhtd->bht", q, K) * dtype(scale)
     p = np.exp(sc - sc.max(axis=-1, keepdims=True))
     p = p / p.sum(axis=-1, keepdims=True, dtype=dtype)
     out = np.einsum("bht,bhtd->bhd", p, V)
@@ -240,7 +240,14 @@ LOGIT_ULPS = 4 * 2.0 ** -23
 # one row's 2.5e-7), 3.23 Y, 3.07 Y; PF_S4 3.07 Y at K = 768 and 3.67 / 3.74 / 3.97 Y at K = 1600.  Raised to 6 Y for both;
 # the five defects of test_pass_stage_cases_cpu.py still exceed that by 1.5 x at every width (asserted there: the least is 4.0 x 3 Y
 # = 2.0 x 6 Y).  The three-pass kernel for fp32 / B24 weights (PF_T128_WP, 2.57 Y at the most) keeps 3.
-BOUND_Y = {"GR_LM_WPT": 6.0, "PF_T128": 6.0, "PF_S4": 6.0}
+# OP_S4 / OP_P8_192 / OP_P8_256 (the op tier's batch >= 16 Linear: six plane products of two fp32 operands on gemm_s4_kernel and the two
+# gemm_p8_kernel widths, test_op_stages_gpu.py): the same one-accumulator chain as PF_S4 with twice the pairs, 6 K / 16 accumulations
+# per output (48 at K = 128, 600 at K = 1600, 6144 at the K = 16384 fall-through), smallest products first — correct by reading, every
+# product exact.  Measured on MI355X over 45 launches: the three kernels return the same bits for the same shape; K = 128 / 192 within
+# 1.5 Y; K = 768 2.07 .. 3.19 Y; K = 1600 3.05 .. 3.80 Y (2.2e-6); K = 16384 4.11 Y (3.8e-6).  Raised to 6 Y for the three; the six
+# defects of test_op_stage_cases_cpu.py measure 13.7 Y and more at K <= 1600, 2.3 x that bound (asserted there), and 9.1 Y at K = 16384,
+# the one shape that test exempts by name.
+BOUND_Y = {"GR_LM_WPT": 6.0, "PF_T128": 6.0, "PF_S4": 6.0, "OP_S4": 6.0, "OP_P8_192": 6.0, "OP_P8_256": 6.0}
 
 
 def bound_y(route):
@@ -290,15 +297,27 @@ def causal_attention(q, K, V, past, dtype=np.float64, shift=0):
     return out, s
 
 
-def layernorm_stage(x, g, b):
+def layernorm_single_pass(x, g, b, dtype=np.float32):
+    """The form ops.zig:88-101 and include/zgpt2.h prescribe for LayerNorm.forward: one pass of sum and sum of squares,
+    std = sqrt(E[x^2] - E[x]^2 + eps).  Equal to layernorm() in exact arithmetic; in floating point the subtraction loses
+    E[x^2] / var = 1 + (mean / sigma)^2 ulps of the variance."""
+    x, g, b = (np.asarray(t, dtype) for t in (x, g, b))
+    n = dtype(x.shape[-1])
+    mean = x.sum(axis=-1, keepdims=True, dtype=dtype) / n
+    std = np.sqrt((x * x).sum(axis=-1, keepdims=True, dtype=dtype) / n - mean * mean + dtype(EPS))
+    return (x - mean) / std * g + b
+
+
+def layernorm_stage(x, g, b, single_pass=False):
     """One LayerNorm launch from its input rows x [M][E]: ref64, the metric's s = |g| (|x| + |mean|) / sigma + |b| — the size of
     the terms the output is made of, so that a value near the mean is not held to a relative bound — and y32, the float32 numpy
-    evaluation (the yardstick)."""
+    evaluation (the yardstick): of the two-pass definition, or (single_pass: the op tier, whose kernel is documented to evaluate
+    that form) of layernorm_single_pass.  ref64 is the two-pass definition in float64 either way."""
     x64, g64, b64 = (np.asarray(t, np.float64) for t in (x, g, b))
     mean = x64.mean(axis=-1, keepdims=True)
     sd = np.sqrt(((x64 - mean) ** 2).mean(axis=-1, keepdims=True) + EPS)
     s = np.abs(g64) * (np.abs(x64) + np.abs(mean)) / sd + np.abs(b64)
-    return layernorm(x, g, b), s, layernorm(x, g, b, np.float32)
+    return layernorm(x, g, b), s, layernorm_single_pass(x, g, b) if single_pass else layernorm(x, g, b, np.float32)
 
 
 def yardstick_rows(M, n_seq, seed=0, at_least=64):
@@ -333,3 +352,50 @@ def pass_linear_stage(a, W, bias, *, resid=None, act=None, n_seq=1, yardstick=Tr
     rows = yardstick_rows(a64.shape[0], n_seq)
     r64, rs, y32 = linear_stage(np.asarray(a)[rows], W, bias, resid=None if resid is None else np.asarray(resid)[rows], act=act)
     return ref, s, metric(y32, r64, rs)
+
+
+# ---------------------------------------------------------------------------------------------- the op tier (test_op_stages_gpu.py)
+def gelu_stage(x):
+    """ops.gelu from its input: ref64, the metric's s = |x| (gelu(x) = x sigmoid(2u): an error of the sigmoid, which lies in 0 .. 1,
+    is an error of that size relative to x), and y32, the float32 numpy evaluation of the same tanh formula."""
+    return gelu(x), np.abs(np.asarray(x, np.float64)), gelu(x, np.float32)
+
+
+def gelu_tail(x, dtype=np.float64):
+    """The form the kernel evaluates, x / (1 + exp(-2u)), u = sqrt(2 / pi) x (1 + 0.044715 x^2): equal to the tanh form, and the
+    one that keeps its relative accuracy where 1 + tanh cancels (x << 0)."""
+    x = np.asarray(x, dtype)
+    u = x * dtype(0.7978845608028654) * (dtype(1.0) + dtype(0.044715) * x * x)
+    with np.errstate(over="ignore"):
+        return x / (dtype(1.0) + np.exp(dtype(-2.0) * u))
+
+
+def softmax_stage(x):
+    """ops.softmax of rows x [R][n] (each row one call): ref64 = p, s = p — a probability is held relative to itself, the small
+    ones too — and y32, exp(x - max) / sum in float32 numpy."""
+    out = []
+    for dt in (np.float64, np.float32):
+        v = np.atleast_2d(np.asarray(x, dt))
+        e = np.exp(v - v.max(axis=-1, keepdims=True))
+        out.append(e / e.sum(axis=-1, keepdims=True, dtype=dt))
+    return out[0], out[0], out[1]
+
+
+def attention_stage(q, K, V, scale):
+    """One attention launch from the q / K / V it read: ref64, s and the float32 numpy evaluation."""
+    ref, s = attention(q, K, V, np.float64, scale)
+    return ref, s, attention(q, K, V, np.float32, scale)[0]
+
+
+# the six plane products of the op tier's batch >= 16 Linear as (activation plane, weight plane), 0 = hi, 1 = mid, 2 = lo: every
+# a_i w_j with i + j <= 2 (api_ops.hip linear_mfma: pa_bits / pb_bits, one hex digit per pair, smallest product first)
+SIX_PAIRS = ((2, 0), (1, 1), (0, 2), (1, 0), (0, 1), (0, 0))
+
+
+def plane_products(x, W, bias, pairs=SIX_PAIRS, x_planes=None):
+    """sum over (i, j) in pairs of a_i w_j^T (+ bias) in float64 from the exact three-plane splits of x [M][K] and W [N][K] — what a
+    matrix-core Linear that runs exactly these products in exact arithmetic returns."""
+    a = (split3(x) if x_planes is None else x_planes).astype(np.float64)
+    w = split3(W).astype(np.float64)
+    y = sum(a[i] @ w[j].T for i, j in pairs)
+    return y if bias is None else y + np.asarray(bias, np.float64)

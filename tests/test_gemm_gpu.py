@@ -1,13 +1,17 @@
 """MFMA GEMM (batched-regime Linear, src/ops.zig:21-46 for M >> 1) vs the CPU oracle's Linear and a
 plain fp32 matmul of the same bf16-rounded operands.  Tolerance: operands are identical bf16
 values on both sides and accumulation is fp32, so only accumulation order differs — reference
-tolerance (src/tests.zig:4-20) with the sweep floor of golden_io.assert_ref_close."""
+tolerance (src/tests.zig:4-20) with the sweep floor of golden_io.assert_ref_close.  Beside it the fp32-output launches are held to
+the stage metric of the stage tests against float64 of the same bf16 operands: |got - ref64| / s within stage_ref.bound_y("PF_S4")
+x Y, Y the blocked float32 sum's own error — the four-wave and the eight-wave kernel are one family with one chain shape (one
+accumulator through the whole K loop), so they share the entry the whole-prompt GEMMs measured."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import oracle
+import stage_ref as sr
 from golden_io import assert_ref_close
 from zig_gpt2_amd import _lib, synth
 
@@ -30,8 +34,22 @@ def run_gemm(zg, a, b, bias, gelu, out_bf16):
     return cd.float().cpu().numpy()
 
 
+def last_kernel(zg):
+    sym = C.create_string_buffer(160)
+    _lib.check(zg.zg_debug_last_kernel(sym, 160))
+    return sym.value.decode()
+
+
+def assert_stage_metric(what, got, a, b, bias, gelu):
+    """The stage metric on the bf16-rounded operands, Y over the same outputs as the worst: printed, then asserted."""
+    ref, s, y32 = sr.linear_stage(a, b, bias, act="gelu" if gelu else None)
+    Y, worst, bound = sr.metric(y32, ref, s), sr.metric(got, ref, s), sr.bound_y("PF_S4")
+    print(f"STAGE {what} | Y {Y:.3e} worst {worst:.3e} = {worst / Y:.2f} Y, bound {bound:.0f} Y")
+    assert worst <= bound * Y, (what, worst, Y)
+
+
 @pytest.mark.parametrize("m,n,k", [(128, 128, 128), (128, 256, 768), (256, 3072, 768), (384, 128, 3072), (1024, 768, 768),
-                                   (100, 136, 192), (1000, 200, 128), (1023, 2304, 768), (16, 8, 1600),
+                                   (100, 136, 192), (1000, 200, 128), (1023, 2304, 768), (16, 8, 1600), (129, 256, 768),
                                    (64, 126, 128), (300, 131, 192), (257, 7, 128)])  # fp32 output: widths that are not multiples of 4
 @pytest.mark.parametrize("gelu", [False, True])
 def test_gemm_matches_oracle_linear(zg, m, n, k, gelu):
@@ -43,6 +61,25 @@ def test_gemm_matches_oracle_linear(zg, m, n, k, gelu):
         exp = oracle.gelu(exp)
     got = run_gemm(zg, a, b, bias, gelu, out_bf16=False)
     assert_ref_close(exp, got, f"gemm {m}x{n}x{k} gelu={gelu}", scale_floor=4e-6)
+    assert_stage_metric(f"gemm {m}x{n}x{k} gelu={gelu} on {last_kernel(zg)}", got, a, b, bias, gelu)
+
+
+@pytest.mark.parametrize("gelu", [False, True])
+def test_gemm_odd_k_step_count_on_the_wide_tiles(zg, gelu, monkeypatch):
+    """K = 192 (three K-steps of 64: the two-steps-per-trip loop ends after its first half) on gemm_p8_kernel<256>, which the
+    dispatcher picks for no shape of this size by itself; M = 300 is one tile and 44 rows."""
+    monkeypatch.setenv("ZGPT2_GEMM_KERNEL", "p8:256")
+    m, n, k = 300, 256, 192
+    a = synth.fill_normal(1000 + m, m * k, 0.0, 1.0, bf16=True).reshape(m, k)
+    b = synth.fill_normal(2000 + n, n * k, 0.0, 0.05, bf16=True).reshape(n, k)
+    bias = synth.fill_normal(3000 + n, n, 0.0, 0.5)
+    exp = oracle.linear_forward(k, n, b, bias, a)
+    if gelu:
+        exp = oracle.gelu(exp)
+    got = run_gemm(zg, a, b, bias, gelu, out_bf16=False)
+    assert last_kernel(zg) == "gemm_p8_kernel<256>, 1 pairs"
+    assert_ref_close(exp, got, f"gemm {m}x{n}x{k} gelu={gelu} p8:256", scale_floor=4e-6)
+    assert_stage_metric(f"gemm {m}x{n}x{k} gelu={gelu} on {last_kernel(zg)}", got, a, b, bias, gelu)
 
 
 def test_gemm_asymmetric_identity_detects_transposes(zg):
@@ -97,6 +134,7 @@ def test_gemm_many_tiles_per_workgroup(zg, bn, wgs, out_bf16, monkeypatch):
         assert np.array_equal(runs[0], synth.round_bf16(run_gemm(zg, a, b, bias, True, out_bf16=False)))
     else:
         assert_ref_close(exp, runs[0], f"gemm bn={bn} wgs={wgs}", scale_floor=4e-6)
+        assert_stage_metric(f"gemm {m}x{n}x{k} gelu bn={bn} wgs={wgs} on {last_kernel(zg)}", runs[0], a, b, bias, True)
     assert all(np.array_equal(runs[0], r) for r in runs[1:])
 
 

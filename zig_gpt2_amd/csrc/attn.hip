@@ -316,6 +316,7 @@ int launch_attn_any_dim(const float* q, const float* k, const float* v, long str
     if (batch == 0) return ZG_OK;  // k.len below one sequence: the reference's loop over the batch does nothing (ops.zig:259-261)
     ZG_REQUIRE(head_dim >= 1 && head_dim <= 2048 && n_heads >= 1 && n_heads < 65536 && batch >= 1 && seq_len >= 1, ZG_ERR_UNSUPPORTED,
                "attention: head_dim %d / heads %d / batch %d", head_dim, n_heads, batch);
+    note_kernel("attn_any_dim_kernel");
     for (int b0 = 0; b0 < batch; b0 += 65535) {  // (the grid's y extent ends at 65535)
         const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
         hipLaunchKernelGGL(attn_any_dim_kernel, dim3(n_heads, nb), dim3(256), 0, s, q + (size_t)b0 * n_heads * head_dim, k + (size_t)b0 * stride_b,

@@ -504,6 +504,7 @@ int launch_p8(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int 
     const int cus_env = getenv("ZGPT2_GEMM_WGS") ? atoi(getenv("ZGPT2_GEMM_WGS")) : 0;  // tests: few workgroups, many tiles each
     const int cus = cus_env > 0 ? cus_env : 256;
     const int grid = n_tiles < cus ? n_tiles : cus;
+    note_kernel("gemm_p8_kernel<%d>, %d pairs", BN, pl.npairs);
     hipLaunchKernelGGL((gemm_p8_kernel<BN, GELU, OUT_BF16>), dim3(grid), dim3(512), P::LDS, s, A, B, bias, C, M, N, pl,
                        ldc, tiles_m, tiles_n, gw, getenv("ZGPT2_GEMM_DBG") ? atoi(getenv("ZGPT2_GEMM_DBG")) : 0);
     ZG_HIP(hipGetLastError());

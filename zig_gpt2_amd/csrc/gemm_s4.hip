@@ -1046,6 +1046,7 @@ int gemm_s4_stamps(unsigned long long* out, size_t n_words) {
 int launch_gemm_s4(const bf16_t* A, const bf16_t* B, const float* bias, void* C, int M, int N, const GemmPlanes& pl, int ldc,
                    bool gelu, bool out_bf16, int bn, hipStream_t s) {
     (void)bn;  // 192-wide tiles only: 256 x 256 needs all 256 accumulator registers plus 128 of B fragments
+    note_kernel("gemm_s4_kernel<3>, %d pairs", pl.npairs);
     return launch_s4_nt<3>(A, B, bias, C, M, N, pl, ldc, gelu, out_bf16, s);
 }
 

@@ -412,6 +412,7 @@ int launch_mt(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
 template <typename WT>
 int launch_wt(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
     if (p.route == GR_GENERIC) {  // slow fallback for K % 8 != 0 (op tier only): one wave per row, scalar loads
+        note_kernel("gemv_generic_kernel<%s>", wt_name<WT>());
         hipLaunchKernelGGL((gemv_generic_kernel<WT>), dim3(p.grid), dim3(p.block), 0, s, a);
         ZG_HIP(hipGetLastError());
         return ZG_OK;
