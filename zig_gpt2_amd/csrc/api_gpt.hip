@@ -104,7 +104,7 @@ struct zg_gpt {
     // tagged hand-overs (GemvArgs.sk_tag, AttnArgs.part_tag): step counter advanced by the embed kernel, (value, tag) words
     unsigned* epoch;
     unsigned spin_limit;  // polls before a poller of a tagged hand-over gives up
-    unsigned tail_off;    // AttnArgs.tail_off: ZGPT2_DECODE_PATHS_OFF bit 512, read once at create
+    unsigned tail_off;    // AttnArgs.tail_off: ZGPT2_DECODE_PATHS_OFF bits 512 and 1024 (kStepPathsAtCreate), read once at create
     unsigned* fault;  // set by a poller of a tagged hand-over whose bounded wait ran out; checked wherever a call drains the stream
     unsigned long long *sk_tag, *part_tag;
     size_t sk_tag_bytes, part_tag_bytes;
@@ -1416,7 +1416,7 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
     }
     g->tags_on = g->pl_on && !(off & 4);
     g->spin_limit = (unsigned)env_int("ZGPT2_TAG_SPIN_LIMIT", 1 << 20);
-    g->tail_off = (unsigned)off & kAttnTailStoreLast;
+    g->tail_off = (unsigned)off & kStepPathsAtCreate;
     // one sequence on the fp32 cache: ln_1 + c_attn and the attention as one launch where c_attn runs on the LayerNorm-folding
     // kernel (ZGPT2_DECODE_PATHS_OFF bit 64: two launches)
     if (batch == 1 && !(off & 64) && c.n_layer <= 127) {

@@ -78,7 +78,8 @@ __device__ __forceinline__ float row16_reduce_scatter(float (&s)[16], int lr) {
 
 // Diagnostic build (-DZG_STAMPS; tools/kernel_stamps.py): lane 0 of every wave of the attention workgroups of head 0 records
 // s_memtime at t0 entry, t1 K / V loads issued, t2 first poll round back, t3 tags matched, t4 arithmetic done, t5 published (wave
-// 0; the others: behind the barrier), then the rounds consumed and whether it held row T - 1; word 8 = 0x10000 | split << 4 | wave.
+// 0; the others: behind the barrier); word 6 = the rounds consumed | held row T - 1 << 32, word 7 = the new row in place (behind
+// the row switch, in front of the arithmetic; the compiler may move arithmetic across it); word 8 = 0x10000 | split << 4 | wave.
 #ifdef ZG_STAMPS
 #define ZG_ASTAMP_DECL() unsigned long long zg_at[8] = {0, 0, 0, 0, 0, 0, 0, 0}
 #define ZG_ASTAMP(i) zg_at[i] = __builtin_amdgcn_s_memtime()
@@ -325,7 +326,7 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
             k4[i] = load_kv4<KV>(K + (size_t)t * stride_t + lr * 4);
             v4[i] = load_kv4<KV>(V + (size_t)t * stride_t + lr * 4);
         }
-        ZG_PIN(a.progress); ZG_PIN(a.part); ZG_PIN(a.max_splits); ZG_PIN(a.pl_out); ZG_PIN(a.part_tag); ZG_PIN(a.launch_id); ZG_PIN(a.merge_cnt); ZG_PIN(a.fault); ZG_PIN(a.spin_limit);
+        ZG_PIN(a.progress); ZG_PIN(a.part); ZG_PIN(a.max_splits); ZG_PIN(a.pl_out); ZG_PIN(a.part_tag); ZG_PIN(a.launch_id); ZG_PIN(a.merge_cnt); ZG_PIN(a.fault); ZG_PIN(a.spin_limit); ZG_PIN(a.tail_off);
         pf_count(a.progress);
         ZG_ASTAMP(1);
         if (FUSED) {
@@ -342,21 +343,59 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
             const int rel = __builtin_amdgcn_readfirstlane(T - 1 - base);  // position T - 1 within this wave's 64
             const bool holder = (unsigned)rel < 64u;
             const u64* wq = qkv_tag + h * 64 + lr * 4;
+            // A lane's four words of q (of k, of v) are 32 contiguous, 32-byte-aligned bytes: two 16-byte sc1 loads instead of four
+            // 8-byte ones — a round of 2 (holder: 6) vector-memory instructions instead of 4 (12), so the holder samples the
+            // producers' words at twice the rate (AttnArgs.tail_off kAttnPollNarrow set: the 8-byte loads).  Every 8-byte half is
+            // still validated by its own tag.  What this relies on: an aligned 8-byte (value, tag) word stored by ONE store is never
+            // seen torn inside a 16-byte sc1 load — observed on gfx950, as for the 8-byte load, not an architectural guarantee; the
+            // two words of one load may be of different steps, which the per-word tags catch.  The loads go through a buffer
+            // descriptor over the 3 E words (sc1 = aux bit 4: served by the L2 like the agent-scope loads).
+            const bool wide = (a.tail_off & kAttnPollNarrow) == 0;
+            const __amdgpu_buffer_rsrc_t rt =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<u64*>(qkv_tag), 0, (unsigned)(3 * E) * 8u, 0x00020000);
+            const unsigned oq = (unsigned)(h * 64 + lr * 4) * 8u, oe = (unsigned)E * 8u;
             u64 wv[12];
             unsigned spins = 0;
             for (;; ++spins) {
                 bool ok = true;
+                if (wide) {
+                    asm volatile("" ::: "memory");  // (a poll: every round loads again)
+                    u32x4 w[6];
+                    w[0] = __builtin_amdgcn_raw_buffer_load_b128(rt, oq, 0, 16);
+                    w[1] = __builtin_amdgcn_raw_buffer_load_b128(rt, oq + 16u, 0, 16);
+                    if (holder) {
+                        w[2] = __builtin_amdgcn_raw_buffer_load_b128(rt, oq + oe, 0, 16);
+                        w[3] = __builtin_amdgcn_raw_buffer_load_b128(rt, oq + oe + 16u, 0, 16);
+                        w[4] = __builtin_amdgcn_raw_buffer_load_b128(rt, oq + 2u * oe, 0, 16);
+                        w[5] = __builtin_amdgcn_raw_buffer_load_b128(rt, oq + 2u * oe + 16u, 0, 16);
+                    }
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    wv[j] = __hip_atomic_load(wq + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ok = ok && (unsigned)(wv[j] >> 32) == tag;
-                }
-                if (holder) {
+                    for (int j = 0; j < 2; ++j) {
+                        wv[2 * j] = ((u64)w[j].y << 32) | w[j].x;
+                        wv[2 * j + 1] = ((u64)w[j].w << 32) | w[j].z;
+                        ok = ok && w[j].y == tag && w[j].w == tag;
+                    }
+                    if (holder) {
+#pragma unroll
+                        for (int j = 2; j < 6; ++j) {
+                            wv[2 * j] = ((u64)w[j].y << 32) | w[j].x;
+                            wv[2 * j + 1] = ((u64)w[j].w << 32) | w[j].z;
+                            ok = ok && w[j].y == tag && w[j].w == tag;
+                        }
+                    }
+                } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        wv[4 + j] = __hip_atomic_load(wq + E + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        wv[8 + j] = __hip_atomic_load(wq + 2 * E + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ok = ok && (unsigned)(wv[4 + j] >> 32) == tag && (unsigned)(wv[8 + j] >> 32) == tag;
+                        wv[j] = __hip_atomic_load(wq + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        ok = ok && (unsigned)(wv[j] >> 32) == tag;
+                    }
+                    if (holder) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            wv[4 + j] = __hip_atomic_load(wq + E + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            wv[8 + j] = __hip_atomic_load(wq + 2 * E + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            ok = ok && (unsigned)(wv[4 + j] >> 32) == tag && (unsigned)(wv[8 + j] >> 32) == tag;
+                        }
                     }
                 }
                 const bool all = __builtin_amdgcn_ballot_w64(!ok) == 0;
@@ -369,8 +408,7 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
                 __builtin_amdgcn_s_sleep(1);
             }
             ZG_ASTAMP(3);
-            ZG_ASTAMP_SET(6, spins + 1);
-            ZG_ASTAMP_SET(7, (unsigned long long)holder);
+            ZG_ASTAMP_SET(6, (unsigned long long)(spins + 1) | ((unsigned long long)holder << 32));
             q4 = f32x4{__uint_as_float((unsigned)wv[0]), __uint_as_float((unsigned)wv[1]), __uint_as_float((unsigned)wv[2]),
                        __uint_as_float((unsigned)wv[3])};
             if (holder && g == (rel & 3)) {
@@ -378,6 +416,8 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
                                   __uint_as_float((unsigned)wv[7])};
                 const f32x4 vn = {__uint_as_float((unsigned)wv[8]), __uint_as_float((unsigned)wv[9]), __uint_as_float((unsigned)wv[10]),
                                   __uint_as_float((unsigned)wv[11])};
+                // (this branch — code only the holder wave runs, once per launch — costs it 770 ticks of s_memtime; two ways round
+                // it were built and measured, and neither gained anything in the step that clears the noise: profiles/NOTEBOOK.md §22)
                 switch (rel >> 2) {  // (uniform: a scalar branch to one register pair)
 #define ZG_NEW_ROW(i) case i: k4[i] = kn; v4[i] = vn; break;
                     ZG_NEW_ROW(0) ZG_NEW_ROW(1) ZG_NEW_ROW(2) ZG_NEW_ROW(3) ZG_NEW_ROW(4) ZG_NEW_ROW(5) ZG_NEW_ROW(6) ZG_NEW_ROW(7)
@@ -385,6 +425,7 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
 #undef ZG_NEW_ROW
                 }
             }
+            ZG_ASTAMP(7);
         }
         // ---- partial dots, then reduce-scatter: lane (g, j) ends with the score of t = base + 4*j + g
         float s[16];

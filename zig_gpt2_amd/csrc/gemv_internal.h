@@ -442,6 +442,7 @@ __device__ __forceinline__ void gemv_lnk_body(int blk, const void* __restrict__ 
 #pragma unroll
         for (int i = 0; i < CPL; ++i) wq[p][i] = load_raw(pr, min(lr + LPR * i, nchq - 1));
     }
+    ZG_STAMP(6);  // (6 and 7 split the issue phase: the weight loads issued, then those of x and ln_g)
     W8 xr[CPL], gr[CPL];
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
@@ -449,6 +450,7 @@ __device__ __forceinline__ void gemv_lnk_body(int blk, const void* __restrict__ 
         xr[i] = load_x8(xin + off);
         gr[i] = load_x8(ln_g + off);
     }
+    ZG_STAMP(7);
     float c2n = 0.0f, c3n = 0.0f;
     if (tid < ROWS) {
         const int n = min(row0 + tid, N - 1);
@@ -530,8 +532,6 @@ __device__ __forceinline__ void gemv_lnk_body(int blk, const void* __restrict__ 
             __hip_atomic_store(tagw + n, tagged_hi | __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     ZG_STAMP(5);
-    ZG_STAMP(6);
-    ZG_STAMP(7);
     ZG_STAMP_FLUSH();
 }
 

@@ -21,7 +21,8 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 // as one launch (attn_qkv.hip) — set, they run as two; 128 the head merge of attn c_proj specialised by split count — set, the
 // four-slot prologue that serves every count (gemv_ksplit.hip); 256 its (m, l) words by wave-uniform loads — set, by the lanes' own;
 // 512 the fused launch's c_attn role stores its tagged word in front of the q / cache store — set, behind it (read once at create:
-// zg_kernels.h kAttnTailStoreLast).
+// zg_kernels.h kAttnTailStoreLast).  Read once at create as well: 1024 the fused launch's attention role polls the tagged words
+// with 16-byte loads — set, with 8-byte ones (kAttnPollNarrow).
 int decode_paths_off();
 
 #define ZG_HIP(expr)                                                         \

@@ -171,11 +171,13 @@ struct AttnArgs {
     unsigned* fault;  // see GemvArgs.fault
     unsigned spin_limit;
     // ZGPT2_DECODE_PATHS_OFF bit 512 as the handle read it at create (kAttnTailStoreLast): the A/B switch of the producer side of
-    // the fused launch's hand-over (gemv_lnk_body TAGGED)
+    // the fused launch's hand-over (gemv_lnk_body TAGGED); likewise bit 1024, the consumer side (kAttnPollNarrow)
     unsigned tail_off;
     unsigned long long* dbg;  // diagnostic timestamps of the fused launch's attention role (only read by -DZG_STAMPS builds)
 };
 constexpr unsigned kAttnTailStoreLast = 512;  // set: the c_attn role stores its tagged word behind the q / cache store
+constexpr unsigned kAttnPollNarrow = 1024;    // set: the attention role polls the tagged words with 8-byte loads, four per row
+constexpr unsigned kStepPathsAtCreate = kAttnTailStoreLast | kAttnPollNarrow;
 int launch_attn_decode(const AttnArgs& a, hipStream_t s);
 // One sequence, fp32 cache, head_dim 64, c_attn on the LayerNorm-folding kernel: ln_1 + c_attn + KV append (g, EPI_QKV) and the
 // attention (at) of the same layer in one launch (attn_qkv.hip).  q and the new k / v row reach the attention workgroups as
