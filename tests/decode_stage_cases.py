@@ -63,6 +63,9 @@ def _cases():
         c.append(Case(128, 3, seq_len=t, ctx=320, layers=2))
     c += [Case(128, 1, kv="f16", seq_len=257, ctx=320), Case(128, 2, kv="b24", seq_len=257, ctx=320), Case(128, 2, off=4, seq_len=320, ctx=320),
           Case(128, 1, off=64, seq_len=257, ctx=320), Case(128, 4, off=1, seq_len=257, ctx=320)]
+    # six attention splits: more than the four slots of the consumer-side head merge, so attn c_proj runs merge_attn4's two-pass
+    # loop (one sequence without the fused launch; a lock-step batch without planes)
+    c += [Case(128, 1, off=64, seq_len=1300, ctx=1536), Case(128, 2, off=1, seq_len=1300, ctx=1536)]
     return c
 
 

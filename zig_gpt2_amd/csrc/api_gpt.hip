@@ -104,7 +104,7 @@ struct zg_gpt {
     // tagged hand-overs (GemvArgs.sk_tag, AttnArgs.part_tag): step counter advanced by the embed kernel, (value, tag) words
     unsigned* epoch;
     unsigned spin_limit;  // polls before a poller of a tagged hand-over gives up
-    unsigned tail_off;    // AttnArgs.tail_off: ZGPT2_DECODE_PATHS_OFF bits 512 and 1024 (kStepPathsAtCreate), read once at create
+    unsigned tail_off;    // AttnArgs.tail_off: ZGPT2_DECODE_PATHS_OFF's kStepPathsAtCreate bits, read once at create
     unsigned* fault;  // set by a poller of a tagged hand-over whose bounded wait ran out; checked wherever a call drains the stream
     unsigned long long *sk_tag, *part_tag;
     size_t sk_tag_bytes, part_tag_bytes;
@@ -1404,7 +1404,7 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
     // the widest input of a Block (mlp c_proj: 4 E floats per sequence) must fit the batched kernels' LDS
     ZG_REQUIRE(gemv_plan(mlp_proj_args(g, 0, 0, StepModes{}), g->wt).supported, ZG_ERR_UNSUPPORTED,
                "batch %zu with n_embed %zu: %zu input rows of 4*n_embed floats do not fit the LDS (use a smaller batch)", batch, c.n_embed, batch);
-    if (g->wt == WT_BF16 && batch >= 2 && !(off & 1) && c.n_embed % 32 == 0) {
+    if (g->wt == WT_BF16 && batch >= 2 && !(off & kOffPlanes) && c.n_embed % 32 == 0) {
         const StepModes cand{true, false, false};  // activation planes between the kernels
         const GemvPlan lin[4] = {gemv_plan(c_attn_args(g, y, 0, cand), g->wt), gemv_plan(c_proj_args(g, y, 0, cand), g->wt),
                                  gemv_plan(c_fc_args(g, y, 0, cand), g->wt), gemv_plan(mlp_proj_args(g, 0, 0, cand), g->wt)};
@@ -1412,14 +1412,14 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
         g->pl_on = every_linear(&GemvPlan::can_take_planes);  // all plane-fed Linears on the matrix-core path?
         // LayerNorm statistics by tile: every producer and consumer of x must be the four-wave kernel (the statistics' only
         // part in a plan is the bound on n_embed / 16 asked here)
-        g->st_on = g->pl_on && !(off & 8) && c.n_embed % 16 == 0 && c.n_embed / 16 <= 128 && every_linear(&GemvPlan::pl4_with_planes);
+        g->st_on = g->pl_on && !(off & kOffTileStats) && c.n_embed % 16 == 0 && c.n_embed / 16 <= 128 && every_linear(&GemvPlan::pl4_with_planes);
     }
-    g->tags_on = g->pl_on && !(off & 4);
+    g->tags_on = g->pl_on && !(off & kOffTags);
     g->spin_limit = (unsigned)env_int("ZGPT2_TAG_SPIN_LIMIT", 1 << 20);
     g->tail_off = (unsigned)off & kStepPathsAtCreate;
     // one sequence on the fp32 cache: ln_1 + c_attn and the attention as one launch where c_attn runs on the LayerNorm-folding
-    // kernel (ZGPT2_DECODE_PATHS_OFF bit 64: two launches)
-    if (batch == 1 && !(off & 64) && c.n_layer <= 127) {
+    // kernel (ZGPT2_DECODE_PATHS_OFF kOffFusedAttn: two launches)
+    if (batch == 1 && !(off & kOffFusedAttn) && c.n_layer <= 127) {
         const GemvArgs ca = c_attn_args(g, y, 0, modes_of(g));
         g->fused_on = attn_qkv_ok(ca, gemv_plan(ca, g->wt), attn_args(g, y, (int)c.context_size));
     }

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void attn_decode_h8_kernel(const float* __rest
             k8[i].load(kp, a.kv_lo, head0 + (size_t)t * stride_t + c * 8);
             v8[i].load(vp, a.kv_lo, head0 + (size_t)t * stride_t + c * 8);
         }
-        ZG_PIN(a.progress); ZG_PIN(a.part); ZG_PIN(a.max_splits); ZG_PIN(a.pl_out); ZG_PIN(a.part_tag); ZG_PIN(a.launch_id); ZG_PIN(a.merge_cnt); ZG_PIN(a.fault); ZG_PIN(a.spin_limit);
+        ZG_PIN_ATTN_TAIL(a);
         pf_count(a.progress);
         float s[8];
 #pragma unroll

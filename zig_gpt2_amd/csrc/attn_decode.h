@@ -105,12 +105,18 @@ __device__ __forceinline__ float row16_reduce_scatter(float (&s)[16], int lr) {
 #define ZG_ASTAMP_FLUSH()
 #endif
 
+// The argument-block fields the end of an attention workgroup needs (publish_partial), fetched under the K / V loads
+#define ZG_PIN_ATTN_TAIL(a) \
+    ZG_PIN(a.progress); ZG_PIN(a.part); ZG_PIN(a.max_splits); ZG_PIN(a.pl_out); ZG_PIN(a.part_tag); ZG_PIN(a.launch_id); ZG_PIN(a.merge_cnt); ZG_PIN(a.fault); ZG_PIN(a.spin_limit)
+// A (value, tag) word of a tagged hand-over, as the pollers read it: one agent-scope relaxed load; the value is the lower half
+__device__ __forceinline__ unsigned long long tagged_load(const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float tag_value(unsigned long long w) { return __uint_as_float((unsigned)w); }
+
 // Wave 0 of a split hands over its partial (o[lane], M, l).  Op tier / one sequence: plain stores, the consumer merges
-// (attn_merge_kernel, or the c_proj prologue).  Lock-step batch with activation planes (AttnArgs.pl_out): the LAST split
-// of (b, h) to arrive merges all of them — same arithmetic as merge_attn4 in gemv_internal.h: weights exp(m_s - max m), sums
-// in split order, one reciprocal — and writes the head's 64 outputs as the three bf16 planes the c_proj Linear loads as
-// MFMA A fragments (zg_common.h plane_elem).  Publish with write-through (agent-scope relaxed atomic) stores, drain
-// them, take a ticket, read back with agent-scope loads: the fence-free pattern of the split-K Linears (gemv_mfma16.hip).
+// (attn_merge_kernel, or the c_proj prologue).  Lock-step batch with activation planes (AttnArgs.pl_out): one split of (b, h)
+// merges all of them — same arithmetic as merge_attn4 in gemv_internal.h: weights exp(m_s - max m), sums in split order, one
+// reciprocal — and writes the head's 64 outputs as the three bf16 planes the c_proj Linear loads as MFMA A fragments
+// (zg_common.h plane_elem): the last split by tagged words, or the last to arrive by ticket.
 __device__ __forceinline__ void publish_partial(const AttnArgs& a, int n_heads, int nsplit, int b, int h, int split, int lane, float o,
                                                 float M, float l, unsigned tag) {
     float* part = a.part + (((size_t)b * n_heads + h) * a.max_splits + split) * kPartStride;
@@ -123,6 +129,7 @@ __device__ __forceinline__ void publish_partial(const AttnArgs& a, int n_heads, 
         return;
     }
     // nsplit = the launched splits: every one of them publishes
+    constexpr int MAXS = 4;  // ctx 1024 / 256; more splits take the loops
     float r = o, lsum = l;
     if (nsplit > 1 && a.part_tag) {
         // Tagged hand-over: every split but the LAST stores (value, tag) words and is done; the last split polls them — one
@@ -143,10 +150,8 @@ __device__ __forceinline__ void publish_partial(const AttnArgs& a, int n_heads, 
             }
             return;
         }
-        float mx = M;
         r = 0.0f;
         lsum = 0.0f;
-        constexpr int MAXS = 4;
         if (nsplit <= MAXS) {
             u64 vo[MAXS - 1], vm[MAXS - 1], vl[MAXS - 1];
             for (int spins = 0;; ++spins) {
@@ -154,9 +159,9 @@ __device__ __forceinline__ void publish_partial(const AttnArgs& a, int n_heads, 
 #pragma unroll
                 for (int s = 0; s < MAXS - 1; ++s) {  // splits 0 .. last - 1; surplus slots re-read the last of them (unused below)
                     const u64* ps = pt0 + min(s, last - 1) * kPartStride;
-                    vo[s] = __hip_atomic_load(ps + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    vm[s] = __hip_atomic_load(ps + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    vl[s] = __hip_atomic_load(ps + 65, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    vo[s] = tagged_load(ps + lane);
+                    vm[s] = tagged_load(ps + 64);
+                    vl[s] = tagged_load(ps + 65);
                     ok = ok && (unsigned)(vo[s] >> 32) == tag && (unsigned)(vm[s] >> 32) == tag && (unsigned)(vl[s] >> 32) == tag;
                 }
                 if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
@@ -170,18 +175,20 @@ __device__ __forceinline__ void publish_partial(const AttnArgs& a, int n_heads, 
 #pragma unroll
             for (int s = 0; s < MAXS; ++s) {  // slot s = split s: polled below `last`, this workgroup's own at `last`, weight 0 above
                 const bool polled = s < last && s < MAXS - 1;
-                ms[s] = polled ? __uint_as_float((unsigned)vm[s < MAXS - 1 ? s : 0]) : s == last ? M : -1e30f;
-                ls[s] = polled ? __uint_as_float((unsigned)vl[s < MAXS - 1 ? s : 0]) : l;
-                os[s] = polled ? __uint_as_float((unsigned)vo[s < MAXS - 1 ? s : 0]) : o;
+                ms[s] = polled ? tag_value(vm[s < MAXS - 1 ? s : 0]) : s == last ? M : -1e30f;
+                ls[s] = polled ? tag_value(vl[s < MAXS - 1 ? s : 0]) : l;
+                os[s] = polled ? tag_value(vo[s < MAXS - 1 ? s : 0]) : o;
             }
-            mx = fmaxf(fmaxf(ms[0], ms[1]), fmaxf(ms[2], ms[3]));
+            const float mx = fmaxf(fmaxf(ms[0], ms[1]), fmaxf(ms[2], ms[3]));
 #pragma unroll
             for (int s = 0; s < MAXS; ++s) {
                 const float w = __expf(ms[s] - mx);
                 lsum = fmaf(w, ls[s], lsum);
                 r = fmaf(w, os[s], r);
             }
-        } else {  // long contexts: one split at a time, running maximum; this workgroup's own partial last
+        } else {
+            // Long contexts: one split is polled at a time, so the maximum is a RUNNING one and this workgroup's own partial comes last:
+            // another summation order than the two-pass form, bitwise different by design (test_long_context_merges_more_than_four_splits)
             float mrun = -1e30f;
             for (int s = 0; s <= last; ++s) {
                 float m_s = M, o_s = o, l_s = l;
@@ -189,9 +196,9 @@ __device__ __forceinline__ void publish_partial(const AttnArgs& a, int n_heads, 
                     const u64* ps = pt0 + s * kPartStride;
                     u64 vo, vm, vl;
                     for (int spins = 0;; ++spins) {
-                        vo = __hip_atomic_load(ps + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        vm = __hip_atomic_load(ps + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        vl = __hip_atomic_load(ps + 65, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        vo = tagged_load(ps + lane);
+                        vm = tagged_load(ps + 64);
+                        vl = tagged_load(ps + 65);
                         const bool ok = (unsigned)(vo >> 32) == tag && (unsigned)(vm >> 32) == tag && (unsigned)(vl >> 32) == tag;
                         if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
                         if ((unsigned)spins >= a.spin_limit) {
@@ -200,9 +207,9 @@ __device__ __forceinline__ void publish_partial(const AttnArgs& a, int n_heads, 
                         }
                         __builtin_amdgcn_s_sleep(1);
                     }
-                    m_s = __uint_as_float((unsigned)vm);
-                    o_s = __uint_as_float((unsigned)vo);
-                    l_s = __uint_as_float((unsigned)vl);
+                    m_s = tag_value(vm);
+                    o_s = tag_value(vo);
+                    l_s = tag_value(vl);
                 }
                 const float mnew = fmaxf(mrun, m_s);
                 const float w0 = __expf(mrun - mnew), w1 = __expf(m_s - mnew);
@@ -227,22 +234,21 @@ __device__ __forceinline__ void publish_partial(const AttnArgs& a, int n_heads, 
         if (ticket != nsplit - 1) return;
         if (lane == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // next launch
         const gu32* p0 = (const gu32*)(a.part + ((size_t)b * n_heads + h) * a.max_splits * kPartStride);
-        constexpr int MAXS = 4;  // ctx 1024 / 256; more splits take the loop below
+        r = 0.0f;
+        lsum = 0.0f;
+        auto word = [&](int s, int i) { return __uint_as_float(__hip_atomic_load(p0 + s * kPartStride + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); };
         if (nsplit <= MAXS) {
             float ms[MAXS], ls[MAXS], os[MAXS];
 #pragma unroll
             for (int s = 0; s < MAXS; ++s) {  // branch-free: surplus splits re-read the last valid one ...
-                const gu32* ps = p0 + min(s, nsplit - 1) * kPartStride;
-                ms[s] = __uint_as_float(__hip_atomic_load(ps + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                ls[s] = __uint_as_float(__hip_atomic_load(ps + 65, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                os[s] = __uint_as_float(__hip_atomic_load(ps + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                ms[s] = word(min(s, nsplit - 1), 64);
+                ls[s] = word(min(s, nsplit - 1), 65);
+                os[s] = word(min(s, nsplit - 1), lane);
             }
 #pragma unroll
             for (int s = 0; s < MAXS; ++s)
                 if (s >= nsplit) ms[s] = -1e30f;  // ... and get weight exp(-1e30 - max) == 0
             const float mx = fmaxf(fmaxf(ms[0], ms[1]), fmaxf(ms[2], ms[3]));
-            r = 0.0f;
-            lsum = 0.0f;
 #pragma unroll
             for (int s = 0; s < MAXS; ++s) {
                 const float w = __expf(ms[s] - mx);
@@ -251,20 +257,16 @@ __device__ __forceinline__ void publish_partial(const AttnArgs& a, int n_heads, 
             }
         } else {
             float mx = -1e30f;
-            for (int s = 0; s < nsplit; ++s)
-                mx = fmaxf(mx, __uint_as_float(__hip_atomic_load(p0 + s * kPartStride + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
-            r = 0.0f;
-            lsum = 0.0f;
+            for (int s = 0; s < nsplit; ++s) mx = fmaxf(mx, word(s, 64));
             for (int s = 0; s < nsplit; ++s) {
-                const gu32* ps = p0 + s * kPartStride;
-                const float w = __expf(__uint_as_float(__hip_atomic_load(ps + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) - mx);
-                lsum = fmaf(w, __uint_as_float(__hip_atomic_load(ps + 65, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)), lsum);
-                r = fmaf(w, __uint_as_float(__hip_atomic_load(ps + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)), r);
+                const float w = __expf(word(s, 64) - mx);
+                lsum = fmaf(w, word(s, 65), lsum);
+                r = fmaf(w, word(s, lane), r);
             }
         }
     }
     const float v = r * (1.0f / lsum);
-    uint32_t hi, mid, lo;
+    uint32_t hi, mid, lo;  // (store_planes, spelled out: the element index is formed behind the split here)
     split3_pk(v, 0.0f, hi, mid, lo);
     const int k = h * 64 + lane;
     a.pl_out[plane_elem(0, b, k)] = (bf16_t)hi;
@@ -326,7 +328,7 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
             k4[i] = load_kv4<KV>(K + (size_t)t * stride_t + lr * 4);
             v4[i] = load_kv4<KV>(V + (size_t)t * stride_t + lr * 4);
         }
-        ZG_PIN(a.progress); ZG_PIN(a.part); ZG_PIN(a.max_splits); ZG_PIN(a.pl_out); ZG_PIN(a.part_tag); ZG_PIN(a.launch_id); ZG_PIN(a.merge_cnt); ZG_PIN(a.fault); ZG_PIN(a.spin_limit); ZG_PIN(a.tail_off);
+        ZG_PIN_ATTN_TAIL(a); ZG_PIN(a.tail_off);
         pf_count(a.progress);
         ZG_ASTAMP(1);
         if (FUSED) {
@@ -386,14 +388,14 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        wv[j] = __hip_atomic_load(wq + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        wv[j] = tagged_load(wq + j);
                         ok = ok && (unsigned)(wv[j] >> 32) == tag;
                     }
                     if (holder) {
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            wv[4 + j] = __hip_atomic_load(wq + E + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            wv[8 + j] = __hip_atomic_load(wq + 2 * E + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            wv[4 + j] = tagged_load(wq + E + j);
+                            wv[8 + j] = tagged_load(wq + 2 * E + j);
                             ok = ok && (unsigned)(wv[4 + j] >> 32) == tag && (unsigned)(wv[8 + j] >> 32) == tag;
                         }
                     }
@@ -409,13 +411,10 @@ __device__ __forceinline__ void attn_decode_body(int h, int split, int b, const 
             }
             ZG_ASTAMP(3);
             ZG_ASTAMP_SET(6, (unsigned long long)(spins + 1) | ((unsigned long long)holder << 32));
-            q4 = f32x4{__uint_as_float((unsigned)wv[0]), __uint_as_float((unsigned)wv[1]), __uint_as_float((unsigned)wv[2]),
-                       __uint_as_float((unsigned)wv[3])};
+            q4 = f32x4{tag_value(wv[0]), tag_value(wv[1]), tag_value(wv[2]), tag_value(wv[3])};
             if (holder && g == (rel & 3)) {
-                const f32x4 kn = {__uint_as_float((unsigned)wv[4]), __uint_as_float((unsigned)wv[5]), __uint_as_float((unsigned)wv[6]),
-                                  __uint_as_float((unsigned)wv[7])};
-                const f32x4 vn = {__uint_as_float((unsigned)wv[8]), __uint_as_float((unsigned)wv[9]), __uint_as_float((unsigned)wv[10]),
-                                  __uint_as_float((unsigned)wv[11])};
+                const f32x4 kn = {tag_value(wv[4]), tag_value(wv[5]), tag_value(wv[6]), tag_value(wv[7])};
+                const f32x4 vn = {tag_value(wv[8]), tag_value(wv[9]), tag_value(wv[10]), tag_value(wv[11])};
                 // (this branch — code only the holder wave runs, once per launch — costs it 770 ticks of s_memtime; two ways round
                 // it were built and measured, and neither gained anything in the step that clears the noise: profiles/NOTEBOOK.md §22)
                 switch (rel >> 2) {  // (uniform: a scalar branch to one register pair)

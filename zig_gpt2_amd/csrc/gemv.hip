@@ -104,7 +104,7 @@ bool plan_mfma(const GemvArgs& a, int off, GemvPlan& p) {
     p.kslices = sliced ? 4 : 1;
     const int Ks = a.K / p.kslices, steps = Ks / 32;
     // the wave-per-tile lm_head: the K values whose tile fits a wave's registers
-    const bool wpt = !(off & 32) && argmax && ln && (steps == 12 || steps == 24 || steps == 32);
+    const bool wpt = !(off & kOffLmWpt) && argmax && ln && (steps == 12 || steps == 24 || steps == 32);
     // tiles per workgroup: one per workgroup and slice; eight for the four waves of the wave-per-tile kernel (a multiple of
     // four; sweep: profiles/round4_lm_head_tiles_sweep.txt); otherwise at most 768 workgroups, ~4 per CU for the widest matrices
     p.rows_per_wave = sliced ? 1 : (wpt ? 8 : ceil_div(ntiles, 768));
@@ -115,7 +115,7 @@ bool plan_mfma(const GemvArgs& a, int off, GemvPlan& p) {
     // Plane-fed Linears as four-wave workgroups (gemv_pl4_kernel): one tile per workgroup, whole 64-k pairs, at most five
     // pairs per wave and slice (K <= 1280 per slice: every GPT-2 size but XL, which stays on the 16-wave kernel).
     const int pairs = (Ks / 64 + 3) / 4;
-    const bool pl4_shape = !(off & 2) && !argmax && p.rows_per_wave == 1 && a.N <= 0xffff && !(ln && a.x_stride != a.K) &&
+    const bool pl4_shape = !(off & kOffPl4) && !argmax && p.rows_per_wave == 1 && a.N <= 0xffff && !(ln && a.x_stride != a.K) &&
                            !(a.epilogue == EPI_RESIDUAL && a.resid_stride != a.N) && !(a.st_in != nullptr && a.K / 16 > 128) &&
                            a.K % (64 * p.kslices) == 0 && pairs >= 1 && pairs <= 5;
     p.pl4_with_planes = p.can_take_planes && pl4_shape;
@@ -139,7 +139,7 @@ bool plan_mfma(const GemvArgs& a, int off, GemvPlan& p) {
         // single-tile workgroups let the partial tiles alias the planes when both do not fit (see the kernel)
         p.alias = !p.gpl && !sliced && !argmax && p.rows_per_wave == 1 && mfma_lds(a.K, 16, false, false, false) > kGemvLdsMax;
         // full-line weight loads (LINE instantiations): whole pairs of 32-k steps and room for one 2-KiB slot per wave
-        p.line = !(off & 16) && !p.alias && Ks % 64 == 0 && mfma_lds(Ks, p.nw, false, true, p.gpl) <= kGemvLdsMax;
+        p.line = !(off & kOffLineLoads) && !p.alias && Ks % 64 == 0 && mfma_lds(Ks, p.nw, false, true, p.gpl) <= kGemvLdsMax;
         p.lds = (int)mfma_lds(Ks, p.nw, p.alias, p.line, p.gpl);
         p.waves_per_wg = p.nw;
         p.block = 64 * p.nw;
@@ -165,7 +165,7 @@ GemvPlan gemv_plan(const GemvArgs& a, int weight_type) {
              // plain Linear over a wide input (measured against the shared-strip form in situ)
              : a.prologue == PRO_NONE && a.K >= 2048 && nchq <= 256)) {
         take(GR_KSPLIT, rung(kKsplitLadder, nchq), 2);  // two passes of 64 / LPR rows per workgroup (four measured slower: 2.65 -> 3.3 us for mlp c_proj)
-        p.merge_generic = (off & 128) != 0, p.merge_ml_vector = (off & 256) != 0;  // (launch_ksplit: which merge prologue)
+        p.merge_generic = (off & kOffMergeByCount) != 0, p.merge_ml_vector = (off & kOffMergeMlScalar) != 0;  // (launch_ksplit: which merge prologue)
     } else if (a.M == 1 && a.prologue == PRO_LAYERNORM && a.ln_c2 != nullptr && a.ln_c3 != nullptr &&
                (a.epilogue == EPI_STORE || a.epilogue == EPI_GELU || a.epilogue == EPI_QKV) && a.K % 32 == 0 && nchq <= 128 && a.N <= 16384) {
         take(GR_LNK, rung(kLnkLadder, nchq), 4);  // four passes (2.93 against 3.2 us per launch with two; +1 % tokens/s in situ)

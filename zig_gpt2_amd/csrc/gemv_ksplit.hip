@@ -21,7 +21,7 @@ namespace {
 //   NS == 0               plain input row (mlp c_proj): no merge code in the instantiation
 //   NS == 1 .. 4          attn c_proj: the input is the head merge of exactly NS attention split partials
 //   NS == kNsGeneric      the merge as it was before NS existed: four slots whatever the split count, read from `em` — kept as
-//                         the reference of tests/test_merge_splits_gpu.py and the A/B switch (ZGPT2_DECODE_PATHS_OFF bit 128)
+//                         the reference of tests/test_merge_splits_gpu.py and the A/B switch (ZGPT2_DECODE_PATHS_OFF kOffMergeByCount)
 // NH (NS 1..4 only): how the (m, l) words of a partial reach the lanes.  0: every lane loads those of its own chunks (vector
 // loads).  1..4: they are the same for every lane whose chunk lies in the same head, and a wave's K quarter touches at most NH
 // heads, so the wave fetches NH x NS pairs with wave-uniform (scalar) loads and every lane selects its head's.

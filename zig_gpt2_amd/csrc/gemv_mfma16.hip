@@ -467,13 +467,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_mfma_kernel(const bf16_t* __rest
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int m = bq * 4 + r;
-                        if (m < M) {
-                            uint32_t hi, mid, lo;
-                            split3_pk(a.pl_g ? sum[r] * gn : sum[r], 0.0f, hi, mid, lo);
-                            a.pl_out[plane_elem(0, m, n)] = (bf16_t)hi;
-                            a.pl_out[plane_elem(1, m, n)] = (bf16_t)mid;
-                            a.pl_out[plane_elem(2, m, n)] = (bf16_t)lo;
-                        }
+                        if (m < M) store_planes(a.pl_out, m, n, a.pl_g ? sum[r] * gn : sum[r]);
                     }
                 }
             }

@@ -284,13 +284,7 @@ __global__ __launch_bounds__(256) void gemv_pl4_kernel(const bf16_t* __restrict_
         }
         Best nobest;
         out = epilogue_row(a, m_out, n, y, e_bias, e_res, T - 1, nobest);
-        if (a.pl_out) {  // the next Linear reads this row as planes (of g * y when a LayerNorm follows)
-            uint32_t hi, mid, lo;
-            split3_pk(has_g ? out * e_g : out, 0.0f, hi, mid, lo);
-            a.pl_out[plane_elem(0, m_out, n)] = (bf16_t)hi;
-            a.pl_out[plane_elem(1, m_out, n)] = (bf16_t)mid;
-            a.pl_out[plane_elem(2, m_out, n)] = (bf16_t)lo;
-        }
+        if (a.pl_out) store_planes(a.pl_out, m_out, n, has_g ? out * e_g : out);  // the next Linear reads this row as planes (of g * y when a LayerNorm follows)
     }
     if (a.st_out != nullptr && run) {  // tile sums of the rows written, for the LayerNorm of the next Linear (uniform branch)
         const float v = valid ? out : 0.0f;

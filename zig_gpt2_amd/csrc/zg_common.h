@@ -15,14 +15,21 @@ void set_error(const char* fmt, ...);
 void note_kernel(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
 // Test hook ZGPT2_DECODE_PATHS_OFF (bit mask, read per call): the lock-step decode's newer paths switched off so that the paths
-// they replaced — still the route of shapes the newer kernels do not take — can be held to the same tokens (tests/test_planes_gpu.py):
-// 1 activation planes between kernels, 2 the four-wave plane-fed Linear, 4 tagged hand-overs (tickets instead), 8 LayerNorm
-// statistics by tile, 16 line-shaped weight loads, 32 the wave-per-tile lm_head; and at batch 1: 64 ln_1 + c_attn and the attention
-// as one launch (attn_qkv.hip) — set, they run as two; 128 the head merge of attn c_proj specialised by split count — set, the
-// four-slot prologue that serves every count (gemv_ksplit.hip); 256 its (m, l) words by wave-uniform loads — set, by the lanes' own;
-// 512 the fused launch's c_attn role stores its tagged word in front of the q / cache store — set, behind it (read once at create:
-// zg_kernels.h kAttnTailStoreLast).  Read once at create as well: 1024 the fused launch's attention role polls the tagged words
-// with 16-byte loads — set, with 8-byte ones (kAttnPollNarrow).
+// they replaced — still the route of shapes the newer kernels do not take — can be held to the same tokens (tests/test_planes_gpu.py).
+// One line per bit: the default path; what the bit restores; when it is read (per plan = every gemv_plan call, at create = zg_gpt_create).
+enum DecodePathsOff : int {
+    kOffPlanes = 1,            // activation planes between the lock-step kernels; fp32 rows, split by the consumer; at create
+    kOffPl4 = 2,               // the four-wave plane-fed Linear; the 16-wave kernel; per plan
+    kOffTags = 4,              // tagged hand-overs; tickets; at create
+    kOffTileStats = 8,         // LayerNorm statistics by tile from the producer; the consumer's own sums over x; at create
+    kOffLineLoads = 16,        // line-shaped weight loads of the 16-wave kernel; fragment-shaped ones; per plan
+    kOffLmWpt = 32,            // the wave-per-tile lm_head; the 16-wave kernel in K steps; per plan
+    kOffFusedAttn = 64,        // batch 1: ln_1 + c_attn and the attention as one launch (attn_qkv.hip); two launches; at create
+    kOffMergeByCount = 128,    // attn c_proj's head merge specialised by split count; the four-slot prologue (gemv_ksplit.hip); per plan
+    kOffMergeMlScalar = 256,   // that merge's (m, l) words by wave-uniform loads; by the lanes' own vector loads; per plan
+    kAttnTailStoreLast = 512,  // the fused launch's c_attn role stores its tagged word in front of the q / cache store; behind it; at create
+    kAttnPollNarrow = 1024,    // its attention role polls the tagged words with 16-byte loads; with 8-byte ones, four per row; at create
+};
 int decode_paths_off();
 
 #define ZG_HIP(expr)                                                         \
@@ -120,6 +127,13 @@ __device__ __forceinline__ void split3_pk(float x0, float x1, uint32_t& hi, uint
 // i.e. the three planes of the 8 rows of one 32-k MFMA step are 1536 contiguous bytes; a triple takes 48 K bytes.
 constexpr int kPlaneStep = 3 * 8 * 32;  // elements per 32-k step
 __host__ __device__ inline size_t plane_elem(int p, int m, int k) { return ((size_t)((k >> 5) * 3 + p) * 8 + m) * 32 + (k & 31); }
+__device__ __forceinline__ void store_planes(bf16_t* pl_out, int m, int k, float v) {  // element (m, k) of an output row as its planes
+    uint32_t hi, mid, lo;
+    split3_pk(v, 0.0f, hi, mid, lo);
+    pl_out[plane_elem(0, m, k)] = (bf16_t)hi;
+    pl_out[plane_elem(1, m, k)] = (bf16_t)mid;
+    pl_out[plane_elem(2, m, k)] = (bf16_t)lo;
+}
 
 // Kernel-argument hygiene of the decode kernels.  Only the first 14 dwords of the arguments are preloaded into SGPRs at
 // wave launch (-amdgpu-kernarg-preload-count=16, two of them hold the kernarg pointer); any other field costs a scalar

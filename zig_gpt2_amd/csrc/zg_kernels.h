@@ -134,8 +134,8 @@ struct GemvPlan {
     bool can_write_planes;  // may write its output rows as planes (GemvArgs.pl_out)
     bool pl4_with_planes;   // given input planes it runs as the four-wave kernel (the one that reads / writes the tile statistics)
     // launcher matters of GR_KSPLIT's head merge (not among the fields zg_debug_gemv_plan reports): the four-slot prologue that
-    // serves any split count instead of the one specialised by it (ZGPT2_DECODE_PATHS_OFF bit 128), and the specialised one's
-    // (m, l) words through the lanes' vector loads instead of wave-uniform ones (bit 256)
+    // serves any split count instead of the one specialised by it (ZGPT2_DECODE_PATHS_OFF kOffMergeByCount), and the specialised one's
+    // (m, l) words through the lanes' vector loads instead of wave-uniform ones (kOffMergeMlScalar)
     bool merge_generic, merge_ml_vector;
 };
 // Pure host code: no HIP call, no allocation.  Reads ZGPT2_DECODE_PATHS_OFF once (per call: tests flip it between handles).
@@ -170,14 +170,12 @@ struct AttnArgs {
     unsigned long long* part_tag;
     unsigned* fault;  // see GemvArgs.fault
     unsigned spin_limit;
-    // ZGPT2_DECODE_PATHS_OFF bit 512 as the handle read it at create (kAttnTailStoreLast): the A/B switch of the producer side of
-    // the fused launch's hand-over (gemv_lnk_body TAGGED); likewise bit 1024, the consumer side (kAttnPollNarrow)
+    // ZGPT2_DECODE_PATHS_OFF kAttnTailStoreLast as the handle read it at create: the A/B switch of the producer side of
+    // the fused launch's hand-over (gemv_lnk_body TAGGED); likewise kAttnPollNarrow, the consumer side
     unsigned tail_off;
     unsigned long long* dbg;  // diagnostic timestamps of the fused launch's attention role (only read by -DZG_STAMPS builds)
 };
-constexpr unsigned kAttnTailStoreLast = 512;  // set: the c_attn role stores its tagged word behind the q / cache store
-constexpr unsigned kAttnPollNarrow = 1024;    // set: the attention role polls the tagged words with 8-byte loads, four per row
-constexpr unsigned kStepPathsAtCreate = kAttnTailStoreLast | kAttnPollNarrow;
+constexpr unsigned kStepPathsAtCreate = kAttnTailStoreLast | kAttnPollNarrow;  // (zg_common.h DecodePathsOff)
 int launch_attn_decode(const AttnArgs& a, hipStream_t s);
 // One sequence, fp32 cache, head_dim 64, c_attn on the LayerNorm-folding kernel: ln_1 + c_attn + KV append (g, EPI_QKV) and the
 // attention (at) of the same layer in one launch (attn_qkv.hip).  q and the new k / v row reach the attention workgroups as
