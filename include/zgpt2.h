@@ -276,6 +276,10 @@ enum {
                                       every graph with lm_head that create captures (the greedy ones, those of the other *_GENERATE
                                       flags given beside it, their log-probability twins under ZG_GPT_LOGPROBS_GENERATE; the rule:
                                       ZG_GPT_SAMPLED_GENERATE) */
+    ZG_GPT_EDITED_GENERATE = 1 << 14, /* capture the decode graphs of zg_gpt_generate_request_enqueue with edits at create as well: min-p
+                                      alone, and the edit stage in front of all four sampler forms (plain, one filter, two filters,
+                                      min-p alone), unpenalised; with ZG_GPT_LOGPROBS_ / _STOP_GENERATE beside it their twins too (the
+                                      rule: ZG_GPT_SAMPLED_GENERATE; a penalised and edited generation captures its graphs when it begins) */
     ZG_GPT_WEIGHTS_B24 = 1 << 8  /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
                                     value rounded to nearest even at 16 mantissa bits (never to inf), row r of an [out][in]
                                     matrix = [in bf16-shaped upper halves | in low bytes].  3/4 of fp32's weight bytes, 2^-17
@@ -664,6 +668,78 @@ int zg_gpt_generate_stop_result(zg_gpt* g, size_t* end_out, size_t* finish_cols_
  * the conditions (a token of 2^31 - 1 or above standing for the vocabulary).  Needs zg_init only.  Allocates per call. */
 int zg_debug_stop_rows(const size_t* tokens, size_t batch, size_t stride, const size_t* first_cols, size_t n_cols,
                        const zg_stop_conditions* stop, size_t* finish_cols_out, int* reasons_out, size_t* done_col_out);
+/* ---- Edits of the logit row by token id, and min-p: OpenAI / vLLM logit_bias, vLLM allowed_token_ids (HF
+ * prefix_allowed_tokens_fn in its static form), vLLM bad_words / HF bad_words_ids for single tokens, and min_p (vLLM, HF, llama.cpp).
+ * The same set for every row of a call, like zg_sample_options and zg_logit_penalties.
+ * Row edit.  Let x be the row as the stage finds it: the raw lm_head output, or the penalised row when the call penalises —
+ * penalties come first, then the edits, then temperature, top-k, top-p and min-p (HF's processor and warper order).  With
+ * keep[i] = (n_allowed == 0 or i is in allowed_ids) and i is not in banned_ids:
+ *   y[i] = keep[i] ? (i in bias_ids ? x[i] + v_i : x[i]) : -inf
+ * The addition is one rounded fp32 add: bitwise numpy float32.  An index that is kept and unbiased is untouched bit for bit (-0.0,
+ * NaN and -inf stay what they are); a bias on a token that is not kept leaves it -inf.  Everything behind the stage sees y: the
+ * sampler, zg_gpt_argmax, the log-probability stage (the logprob of a banned token is -inf; the top-N order treats -inf as an
+ * ordinary value) and the stop stage.
+ * min-p belongs to the sampler, not to the row (the log-probability record stays at temperature 1 and before truncation).  The host
+ * computes once per call d = (float)((double)temp * log((double)min_p)) (-inf when min_p == 0; zg_debug_min_p_offset); on the device
+ * tau_m = m + d is one fp32 add, m the row maximum of y, and kept = { y >= max(tau_k, tau_p, tau_m) } with tau_k and tau_p exactly as
+ * in zg_sample_options (HF applies min-p last; its test p_i >= min_p * p_max is a ratio, so the renormalisation before it does not
+ * matter).  Ties at the threshold stay together, the top token is always kept, probabilities are renormalised and exactly 0 where
+ * dropped.  The threshold is comparison-only: the same inputs give the same tokens on every run.
+ * Refusals, all before anything is enqueued or the handle's state is touched.  ZG_ERR_ARG: NULL edits where edits are required,
+ * n_bias > ZG_EDIT_MAX_BIAS, a duplicate bias id, a non-finite bias value, min_p < 0, >= 1 or NaN, a NULL array with a non-zero
+ * count, an empty kept set (both lists are the host's: a row of -inf alone never reaches a kernel), greedy (options == NULL) with
+ * any edit on — as with penalties, greedy with edits is top_k = 1.  ZG_ERR_SHAPE: an id >= vocab_size.
+ * Everything off (n_bias, n_allowed, n_banned and min_p all 0): the call is exactly its twin without edits — identical tokens,
+ * probabilities and records, no added launch, the same graphs.
+ * Cost: ONE added launch per step, which edits every row and leaves the row-maximum partials rebuilt from what it wrote; min-p adds
+ * none to a truncated sampler and, alone, swaps the sampler's two tail kernels for their threshold-aware twins.  The keep set lives
+ * in device memory as a bitmap of vocab_size bits built by the host (the lists have no count limit), the bias as pairs sorted by
+ * id; both are read on the device, so one captured graph serves every set. */
+#define ZG_EDIT_MAX_BIAS 512
+typedef struct {
+    const size_t* bias_ids; const float* bias_values; size_t n_bias; /* <= ZG_EDIT_MAX_BIAS, ids distinct, values finite */
+    const size_t* allowed_ids; size_t n_allowed;                     /* 0: every token is allowed; any count up to vocab */
+    const size_t* banned_ids;  size_t n_banned;                      /* any count; duplicates are harmless */
+    float min_p;                                                     /* in [0, 1); 0 = off */
+} zg_logit_edits;
+/* zg_gpt_sample_pen with the edit stage behind the penalties.  penalties_or_null NULL (history is not read then) or all off: no
+ * penalty stage.  options and edits must be non-NULL.  Everything off: zg_gpt_sample_pen / zg_gpt_sample_ex itself, bit for bit.
+ * zg_gpt_argmax behind this call is the argmax of the edited row. */
+int zg_gpt_sample_edit(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens,
+                       const zg_sample_options* options, const zg_logit_penalties* penalties_or_null,
+                       const size_t* history, size_t history_stride, const size_t* history_lens,
+                       const zg_logit_edits* edits, const float* uniforms, uint64_t seed,
+                       size_t* tokens_out, float* probs_out, size_t probs_len);
+/* The request form of the generate call, the superset from now on: every argument of zg_gpt_generate_stop_enqueue by name, plus
+ * edits.  size must be sizeof(zg_generate_request) (else ZG_ERR_ARG).  edits NULL: zg_gpt_generate_stop_enqueue exactly.  With edits
+ * it returns exactly the tokens of the host loop over zg_gpt_sample_edit (history as zg_gpt_generate_pen_enqueue states it).  The
+ * edit stage is a node of the captured step (graphs of their own: ZG_GPT_EDITED_GENERATE).  Does not allocate beyond that capture.
+ * Results through zg_gpt_generate_fetch / _fetch_range / _fetch_logprobs / _stop_result. */
+typedef struct {
+    size_t size;
+    size_t past_len;
+    const size_t* prompts; size_t prompt_stride; const size_t* prompt_lens;
+    size_t n_steps;
+    const zg_sample_options* options;     /* NULL: greedy */
+    const zg_logit_penalties* penalties;  /* NULL: none */
+    const size_t* prior; size_t prior_stride; const size_t* prior_lens;
+    uint64_t seed;
+    int logprobs; size_t top_n;
+    const zg_stop_conditions* stop;       /* NULL: none */
+    const zg_logit_edits* edits;          /* NULL: none */
+} zg_generate_request;
+int zg_gpt_generate_request_enqueue(zg_gpt* g, const zg_generate_request* r);
+/* Test entry: the edit stage and the sampler behind it alone on the caller's rows, logits [batch <= 64, vocab <= 262144] (host or
+ * device, as uniforms [batch] and the outputs), a small kernel standing in for lm_head's row-maximum partials.  edited_out
+ * [batch, vocab]: the rows as the stage leaves them; tokens_out, probs_out and thresholds_out (max(tau_k, tau_p, tau_m) of each
+ * row; -inf when nothing truncates) as zg_debug_sample_rows.  Everything off: zg_debug_sample_rows bit for bit.  Needs zg_init only.
+ * Allocates its workspace per call. */
+int zg_debug_edit_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* options,
+                       const zg_logit_edits* edits, const float* uniforms,
+                       float* edited_out_or_null, size_t* tokens_out,
+                       float* probs_out_or_null, float* thresholds_out_or_null);
+/* d of min-p as the library computes it (temp > 0, min_p in [0, 1), else ZG_ERR_ARG).  Needs neither a GPU nor zg_init. */
+int zg_debug_min_p_offset(float temp, float min_p, float* d_out);
 /* tokens of positions first .. first + n - 1 of the last generation(s): out_tokens [batch, n] */
 int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len);
 /* Test entry: the sampler kernels of zg_gpt_sample_ex on the caller's logits [batch <= 64, vocab <= 262144] (host or device, as

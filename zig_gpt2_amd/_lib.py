@@ -50,6 +50,28 @@ class StopConditions(C.Structure):
     _fields_ = [("ids", vp), ("n_ids", sz), ("seqs", vp), ("seq_stride", sz), ("seq_lens", vp), ("n_seqs", sz), ("lookahead", sz)]
 
 
+class LogitEdits(C.Structure):
+    """zg_logit_edits of include/zgpt2.h."""
+
+    _fields_ = [("bias_ids", vp), ("bias_values", vp), ("n_bias", sz), ("allowed_ids", vp), ("n_allowed", sz), ("banned_ids", vp), ("n_banned", sz),
+                ("min_p", C.c_float)]
+
+
+class GenerateRequest(C.Structure):
+    """zg_generate_request of include/zgpt2.h (`size` is filled by generate_request())."""
+
+    _fields_ = [("size", sz), ("past_len", sz), ("prompts", vp), ("prompt_stride", sz), ("prompt_lens", vp), ("n_steps", sz), ("options", vp),
+                ("penalties", vp), ("prior", vp), ("prior_stride", sz), ("prior_lens", vp), ("seed", C.c_uint64), ("logprobs", C.c_int), ("top_n", sz),
+                ("stop", vp), ("edits", vp)]
+
+
+def generate_request(**fields):
+    """A zg_generate_request with its size set and every field not named left 0 / NULL."""
+    r = GenerateRequest(**fields)
+    r.size = C.sizeof(GenerateRequest)
+    return r
+
+
 class GptOptions(C.Structure):
     """zg_gpt_options of include/zgpt2.h."""
 
@@ -140,6 +162,10 @@ SIGNATURES = {
     "zg_gpt_generate_stop_enqueue": (C.c_int, [vp, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp, C.c_uint64, C.c_int, sz, vp]),
     "zg_gpt_generate_stop_result": (C.c_int, [vp, szp, vp, vp]),
     "zg_debug_stop_rows": (C.c_int, [vp, sz, sz, vp, sz, vp, vp, vp, szp]),
+    "zg_gpt_sample_edit": (C.c_int, [vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, C.c_uint64, vp, vp, sz]),
+    "zg_gpt_generate_request_enqueue": (C.c_int, [vp, vp]),
+    "zg_debug_edit_rows": (C.c_int, [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]),
+    "zg_debug_min_p_offset": (C.c_int, [C.c_float, C.c_float, f32p]),
     "zg_gpt_score": (C.c_int, [vp, sz, vp, sz, sz, sz, vp, sz]),
     "zg_debug_score_rows": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, vp, vp]),
     "zg_gpt_time_kernel": (C.c_int, [vp, C.c_int, C.c_int, f32p, szp]),
@@ -161,6 +187,8 @@ GPT_PENALIZED_GENERATE = 1024
 GPT_LOGPROBS_GENERATE = 2048
 GPT_SCORE = 4096
 GPT_STOP_GENERATE = 8192
+GPT_EDITED_GENERATE = 16384
+EDIT_MAX_BIAS = 512
 LOGPROBS_TOP_MAX = 20
 STOP_MAX_IDS, STOP_MAX_SEQS, STOP_MAX_SEQ_LEN = 16, 8, 16
 STOP_NONE = (1 << 64) - 1
@@ -180,6 +208,23 @@ def stop_conditions(stop_token_ids=None, stop=None, lookahead=0):
         mat[k, : len(q)] = q
     c = StopConditions(ptr(ids) if ids.size else None, ids.size, ptr(mat) if seqs else None, stride, ptr(lens) if seqs else None, len(seqs), int(lookahead))
     return c, (ids, mat, lens)
+
+
+def logit_edits(logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_p=0.0):
+    """zg_logit_edits from a {token id: bias} mapping, an allow-list, a ban-list and min_p: (the structure, the arrays it points
+    into — keep them alive while it is in use)."""
+    import numpy as np
+
+    bias = dict(logit_bias or {})
+    ids = np.ascontiguousarray(list(bias.keys()), dtype=np.uint64).reshape(-1)
+    vals = np.ascontiguousarray(list(bias.values()), dtype=np.float32).reshape(-1)
+    allowed = np.ascontiguousarray([] if allowed_token_ids is None else allowed_token_ids, dtype=np.uint64).reshape(-1)
+    banned = np.ascontiguousarray([] if banned_token_ids is None else banned_token_ids, dtype=np.uint64).reshape(-1)
+    e = LogitEdits(ptr(ids) if ids.size else None, ptr(vals) if ids.size else None, ids.size, ptr(allowed) if allowed.size else None, allowed.size,
+                   ptr(banned) if banned.size else None, banned.size, float(min_p))
+    return e, (ids, vals, allowed, banned)
+
+
 BLOCK_SLOTS = ["ln_1_g", "ln_1_b", "c_attn_w", "c_attn_b", "c_proj_w", "c_proj_b",
                "ln_2_g", "ln_2_b", "c_fc_w", "c_fc_b", "mlp_proj_w", "mlp_proj_b"]
 TOP_SLOTS = ["wte", "wpe", "ln_f_g", "ln_f_b"]

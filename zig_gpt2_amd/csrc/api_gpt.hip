@@ -23,6 +23,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <string>
@@ -36,22 +37,26 @@ using namespace zg;
 
 // What a step puts behind lm_head: nothing (greedy: the argmax partials of its epilogue are the pick), GPT.sample's tail, or that
 // tail behind the selection launches of one filter (top-k or top-p) / of both.  The one form "how are tokens chosen" travels in.
-enum SamplerMode { GREEDY = 0, PLAIN, ONE_FILTER, TWO_FILTERS };
-constexpr size_t kSamplerModes = TWO_FILTERS + 1;
+// MINP_ONLY: min-p with both filters off — the threshold-aware tail kernels with no selection launch in front.
+enum SamplerMode { GREEDY = 0, PLAIN, ONE_FILTER, TWO_FILTERS, MINP_ONLY };
+constexpr size_t kSamplerModes = MINP_ONLY + 1;
 static inline int filter_launches(SamplerMode m) { return m == TWO_FILTERS ? 6 : m == ONE_FILTER ? 3 : 0; }  // sample_filter.h: three levels per descent
+static inline bool threshold_sampler(SamplerMode m) { return m == ONE_FILTER || m == TWO_FILTERS || m == MINP_ONLY; }  // the tail kernels that read tau
 
 // Everything that follows lm_head in a decode step, as one value: the sampler, the penalty stage between lm_head and the sampler
-// (DESIGN §3.6), the log-probability stage behind the sampler — of a greedy step: behind lm_head —, the stop stage
-// behind everything.  The default is the greedy step the reference's argmax loop runs.
+// (DESIGN §3.6), the edit stage — logit bias, allow / ban lists — behind the penalties, the log-probability stage
+// behind the sampler — of a greedy step: behind lm_head —, the stop stage behind everything.  The
+// default is the greedy step the reference's argmax loop runs.
 struct StepTail {
     SamplerMode sampler = GREEDY;
-    bool pen = false, lp = false, stop = false;
-    bool operator==(const StepTail& o) const { return sampler == o.sampler && pen == o.pen && lp == o.lp && stop == o.stop; }
+    bool pen = false, lp = false, stop = false, edit = false;
+    bool operator==(const StepTail& o) const { return sampler == o.sampler && pen == o.pen && lp == o.lp && stop == o.stop && edit == o.edit; }
 };
-// The tail a step can have: nothing is drawn from a step without lm_head (the default tail), and a greedy pick has no penalties
+// The tail a step can have: nothing is drawn from a step without lm_head (the default tail), and a greedy pick has neither
+// penalties nor edits
 static inline StepTail normalized(StepTail t, bool with_logits) {
     if (!with_logits) return StepTail{};
-    if (t.sampler == GREEDY) t.pen = false;
+    if (t.sampler == GREEDY) t.pen = t.edit = false;
     return t;
 }
 
@@ -158,6 +163,13 @@ struct zg_gpt {
         int fin[kStopMaxRows], reason[kStopMaxRows];
         alignas(64) StopHost host;
     }* h_stop;
+    // logit edits (sample_edit.h): the bias table and, behind it, the keep bitmap of vocab bits — one block in the
+    // arena, its pinned mirror, and plain host memory of the same size in which a call's set is built and checked before anything
+    // else is touched (edit_build)
+    EditTable* edit_tab;
+    unsigned* edit_keep;
+    char* h_edit;
+    std::vector<char> edit_build;
     bool gen_stop;            // the generation in flight has conditions: gen_pump paces itself and may end early
     size_t gen_lookahead;     // ... at most this many steps ahead of host.progress before each piece
     bool stop_valid;          // the last generation was one with conditions: zg_gpt_generate_stop_result can report it
@@ -255,6 +267,9 @@ struct DevScratch {
         return ZG_OK;
     }
 };
+
+// the edit stage's block: the bias table, then the keep bitmap of `vocab` bits
+size_t edit_block_bytes(size_t vocab) { return sizeof(EditTable) + (vocab + 31) / 32 * 4; }
 
 size_t kv_elem_bytes(const zg_gpt* g) { return g->kv_mode == 1 ? 2 : g->kv_mode == 2 ? 3 : 4; }  // B24: a bf16 plane, then a byte plane
 
@@ -394,6 +409,9 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
     g->stop = (StopConds*)P(sizeof(StopConds));
     g->stop_fin = (int*)P(kStopMaxRows * 4);
     g->stop_reason = (int*)P(kStopMaxRows * 4);
+    // (and the edit stage's bias table with the keep bitmap behind it)
+    g->edit_tab = (EditTable*)P(edit_block_bytes(V));
+    g->edit_keep = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g->edit_tab) + sizeof(EditTable));
     g->state_bytes = (cv.off + 255) & ~(size_t)255;
 }
 
@@ -935,12 +953,17 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         if (tail.stop) ZG_TRY(stop(nullptr));
     }
     if (tail.sampler == GREEDY || !with_logits || only >= 0 || rec) return ZG_OK;
-    // the penalties act on the raw logits (HF's order); the row-maximum partials both samplers start from are rebuilt behind them
+    // the penalties act on the raw logits (HF's order); the row-maximum partials both samplers start from are rebuilt behind them —
+    // by the edit stage's own launch where one follows (the partials need rebuilding only behind the last stage that rewrites the row)
     if (tail.pen)
-        ZG_TRY(launch_penalize(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->pen, pen_history(g, true), g->part_val, g->part_idx, g->lm_grid, nullptr, s));
-    if (const int levels = filter_launches(tail.sampler))
-        ZG_TRY(launch_sample_filtered(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, levels, nullptr, g->ctrl, g->part_val, g->lm_grid,
-                                      g->lm_grid, g->samp_ws, g->filt, g->sampled, false, s));
+        ZG_TRY(launch_penalize(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->pen, pen_history(g, true), g->part_val, g->part_idx, g->lm_grid, nullptr, s,
+                               !tail.edit));
+    // the edits act on the row the penalties leave (HF's processor order) and leave the partials rebuilt from what they wrote
+    if (tail.edit)
+        ZG_TRY(launch_logit_edit(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->edit_tab, g->edit_keep, g->part_val, g->part_idx, g->lm_grid, s));
+    if (threshold_sampler(tail.sampler))
+        ZG_TRY(launch_sample_filtered(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, filter_launches(tail.sampler), nullptr, g->ctrl, g->part_val,
+                                      g->lm_grid, g->lm_grid, g->samp_ws, g->filt, g->sampled, false, s));
     else
         ZG_TRY(launch_sample_step(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, g->ctrl, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws,
                                   g->sampled, s));
@@ -1177,14 +1200,14 @@ size_t prefill_min() { return 4; }  // shorter prompts go through the decode cha
 //                memory, so the same kernels simply repeat; saves the gap between graph launches in the generate loop
 //   tail         what follows lm_head (StepTail, normalized; the option values are read on the device)
 // The table has a slot for every combination of the fields, indexed by them as mixed-radix digits; the slots of combinations
-// that cannot occur (multi or a tail without lm_head, penalties in front of a greedy pick) simply stay null.
+// that cannot occur (multi or a tail without lm_head, penalties or edits in front of a greedy pick) simply stay null.
 struct StepKey {
     bool with_logits, multi;
     StepTail tail;
 };
-constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2 * 2;  // the radices of step_index
+constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2 * 2 * 2;  // the radices of step_index
 size_t step_index(StepKey k) {
-    return (((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp) * 2 + k.tail.stop;
+    return ((((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp) * 2 + k.tail.stop) * 2 + k.tail.edit;
 }
 
 size_t bucket_of(size_t seq_len) { return (seq_len + 63) / 64 - 1; }
@@ -1249,15 +1272,19 @@ std::vector<StepTail> tails_of_flags(unsigned flags) {
         for (SamplerMode m : {ONE_FILTER, TWO_FILTERS}) t.push_back({m, false, false});
     if (flags & ZG_GPT_PENALIZED_GENERATE)
         for (SamplerMode m : {PLAIN, ONE_FILTER, TWO_FILTERS}) t.push_back({m, true, false});
+    if (flags & ZG_GPT_EDITED_GENERATE) {  // min-p alone, and the edit stage in front of every sampler form (unpenalised)
+        t.push_back({MINP_ONLY, false, false});
+        for (SamplerMode m : {PLAIN, ONE_FILTER, TWO_FILTERS, MINP_ONLY}) t.push_back({m, false, false, false, true});
+    }
     if (flags & ZG_GPT_LOGPROBS_GENERATE) {
         const size_t n = t.size();
         t.push_back({GREEDY, false, true});
-        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, true});
+        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, true, false, t[i].edit});
     }
     if (flags & ZG_GPT_STOP_GENERATE) {  // the stop twins of the default tail and of everything above
         const size_t n = t.size();
         t.push_back({GREEDY, false, false, true});
-        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, t[i].lp, true});
+        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, t[i].lp, true, t[i].edit});
     }
     return t;
 }
@@ -1373,6 +1400,7 @@ void release(zg_gpt* g) {
     if (g->h_ints) (void)hipHostFree(g->h_ints);
     if (g->h_lp) (void)hipHostFree(g->h_lp);
     if (g->h_stop) (void)hipHostFree(g->h_stop);
+    if (g->h_edit) (void)hipHostFree(g->h_edit);
     delete g;
 }
 
@@ -1433,7 +1461,10 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
         e = hipHostMalloc(reinterpret_cast<void**>(&g->h_lp), batch * c.context_size * (1 + 2 * ZG_LOGPROBS_TOP_MAX) * sizeof(float), hipHostMallocDefault);
     // (the stop stage's block: a few hundred bytes, always there)
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_stop), sizeof(*g->h_stop), hipHostMallocDefault);
+    // (the edit stage's mirror: the bias table and the keep bitmap)
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_edit), edit_block_bytes(c.vocab_size), hipHostMallocDefault);
     if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(control mirrors)", __FILE__, __LINE__);
+    g->edit_build.assign(edit_block_bytes(c.vocab_size), 0);
     memset(g->h_stop, 0, sizeof(*g->h_stop));
     static_assert(sizeof(StepCtrl) + sizeof(SampleParams) <= 256, "the fault word sits 256 bytes behind the control mirror");
     g->h_samp = reinterpret_cast<SampleParams*>(reinterpret_cast<char*>(g->h_ctrl) + 128);  // (same pinned block)
@@ -1977,7 +2008,7 @@ int zg_gpt_argmax(zg_gpt* g, size_t* tokens_out, size_t n_tokens) {
     return ZG_OK;
 }
 
-static SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed);
+static SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed, float min_p = 0.0f);
 static int check_sample_options(const zg_sample_options* o, const char* who);
 // The explicit history of a penalised per-token call: [batch][stride] tokens, lens[b] of each row
 struct PenCall {
@@ -1987,12 +2018,79 @@ struct PenCall {
     const size_t* lens;
 };
 static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options& o, const float* uniforms, uint64_t seed,
-                       size_t* tokens_out, float* probs_out, size_t probs_len, const PenCall* pc = nullptr);
+                       size_t* tokens_out, float* probs_out, size_t probs_len, const PenCall* pc = nullptr, const struct EditCall* ec = nullptr);
 static int check_penalties(const zg_logit_penalties* p, const char* who);
 static int check_pen_handle(const zg_gpt* g, const char* who);
 static int check_history(const zg_gpt* g, const size_t* tokens, size_t stride, const size_t* lens, size_t extra, const char* who);
 static int stage_penalties(zg_gpt* g, const zg_logit_penalties& p, size_t past, const size_t* tokens, size_t stride, const size_t* lens, hipStream_t s);
 static inline bool penalties_off(const zg_logit_penalties& p) { return p.repetition == 1.0f && p.presence == 0.0f && p.frequency == 0.0f; }
+
+// ---- Logit edits (include/zgpt2.h zg_logit_edits).  What a checked set asks of a call: the edit stage (any of the
+// three lists) and / or the sampler's min-p threshold
+struct EditCall {
+    bool stage_on;  // the set built in the handle's edit_build goes to the device and the edit launch runs
+    float min_p;
+};
+static inline bool edits_off(const zg_logit_edits& e) { return e.n_bias == 0 && e.n_allowed == 0 && e.n_banned == 0 && e.min_p == 0.0f; }
+
+// temp x log(min_p) in double, rounded once: what the sampler adds to the row maximum (min_p 0: -inf, nothing is cut)
+static float min_p_offset(float temp, float min_p) { return min_p == 0.0f ? -INFINITY : (float)((double)temp * log((double)min_p)); }
+
+// The refusals of a set of edits over `vocab` logits (include/zgpt2.h), and — where any list is given — the set as the kernel
+// reads it, built into `block` (edit_block_bytes(vocab) bytes of plain host memory): the bias pairs sorted by id, then the keep
+// bitmap.  Nothing else is touched.
+static int build_edits(const zg_logit_edits* e, size_t vocab, const char* who, char* block, bool* stage_on) {
+    ZG_REQUIRE(e != nullptr, ZG_ERR_ARG, "%s: edits is null", who);
+    ZG_REQUIRE(e->min_p >= 0.0f && e->min_p < 1.0f, ZG_ERR_ARG, "%s: min_p %f outside [0, 1)", who, e->min_p);  // (a NaN fails it)
+    ZG_REQUIRE(e->n_bias <= (size_t)ZG_EDIT_MAX_BIAS, ZG_ERR_ARG, "%s: %zu biases above %d", who, e->n_bias, ZG_EDIT_MAX_BIAS);
+    ZG_REQUIRE((e->n_bias == 0 || (e->bias_ids && e->bias_values)) && (e->n_allowed == 0 || e->allowed_ids) && (e->n_banned == 0 || e->banned_ids), ZG_ERR_ARG,
+               "%s: a null array with a non-zero count", who);
+    for (size_t i = 0; i < e->n_bias; ++i) ZG_REQUIRE(e->bias_ids[i] < vocab, ZG_ERR_SHAPE, "%s: bias id %zu >= vocab %zu", who, e->bias_ids[i], vocab);
+    for (size_t i = 0; i < e->n_allowed; ++i) ZG_REQUIRE(e->allowed_ids[i] < vocab, ZG_ERR_SHAPE, "%s: allowed id %zu >= vocab %zu", who, e->allowed_ids[i], vocab);
+    for (size_t i = 0; i < e->n_banned; ++i) ZG_REQUIRE(e->banned_ids[i] < vocab, ZG_ERR_SHAPE, "%s: banned id %zu >= vocab %zu", who, e->banned_ids[i], vocab);
+    std::pair<int, float> pairs[ZG_EDIT_MAX_BIAS];
+    for (size_t i = 0; i < e->n_bias; ++i) {
+        ZG_REQUIRE(std::isfinite(e->bias_values[i]), ZG_ERR_ARG, "%s: bias %f on token %zu", who, e->bias_values[i], e->bias_ids[i]);
+        pairs[i] = {(int)e->bias_ids[i], e->bias_values[i]};
+    }
+    std::sort(pairs, pairs + e->n_bias, [](const std::pair<int, float>& a, const std::pair<int, float>& b) { return a.first < b.first; });
+    for (size_t i = 1; i < e->n_bias; ++i) ZG_REQUIRE(pairs[i].first != pairs[i - 1].first, ZG_ERR_ARG, "%s: token %d is biased twice", who, pairs[i].first);
+    *stage_on = e->n_bias != 0 || e->n_allowed != 0 || e->n_banned != 0;
+    if (!*stage_on) return ZG_OK;
+    EditTable* tab = reinterpret_cast<EditTable*>(block);
+    unsigned* keep = reinterpret_cast<unsigned*>(block + sizeof(EditTable));
+    const size_t words = (vocab + 31) / 32;
+    memset(tab, 0, sizeof(EditTable));
+    tab->n_bias = (int)e->n_bias;
+    for (size_t i = 0; i < e->n_bias; ++i) {
+        tab->ids[i] = pairs[i].first;
+        tab->vals[i] = pairs[i].second;
+    }
+    memset(keep, e->n_allowed ? 0x00 : 0xff, words * 4);
+    for (size_t i = 0; i < e->n_allowed; ++i) keep[e->allowed_ids[i] >> 5] |= 1u << (e->allowed_ids[i] & 31);
+    for (size_t i = 0; i < e->n_banned; ++i) keep[e->banned_ids[i] >> 5] &= ~(1u << (e->banned_ids[i] & 31));
+    if (vocab & 31) keep[words - 1] &= (1u << (vocab & 31)) - 1u;  // (bits behind the vocabulary: never read, not counted)
+    size_t kept = 0;
+    for (size_t w = 0; w < words; ++w) kept += (size_t)__builtin_popcount(keep[w]);
+    // (both lists are the host's: a row of -inf alone never reaches a kernel)
+    ZG_REQUIRE(kept >= 1, ZG_ERR_ARG, "%s: the allow and ban lists leave no token", who);
+    return ZG_OK;
+}
+
+// The set built in edit_build through its pinned mirror into the arena.  PRECONDITION: nothing in flight reads the mirror (every
+// edited call drains, or begins by draining).
+static int stage_edits(zg_gpt* g, hipStream_t s) {
+    const size_t bytes = g->edit_build.size();
+    memcpy(g->h_edit, g->edit_build.data(), bytes);
+    ZG_HIP(hipMemcpyAsync(g->edit_tab, g->h_edit, bytes, hipMemcpyHostToDevice, s));
+    return ZG_OK;
+}
+
+int zg_debug_min_p_offset(float temp, float min_p, float* d_out) {
+    ZG_REQUIRE(d_out != nullptr && temp > 0.0f && min_p >= 0.0f && min_p < 1.0f, ZG_ERR_ARG, "debug_min_p_offset: temp %f, min_p %f", temp, min_p);
+    *d_out = min_p_offset(temp, min_p);
+    return ZG_OK;
+}
 
 int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, const float* uniforms,
                   uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
@@ -2024,8 +2122,33 @@ int zg_gpt_sample_pen(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_
     return sample_impl(g, seq_len, tokens, n_tokens, *opt, uniforms, seed, tokens_out, probs_out, probs_len, penalties_off(*pen) ? nullptr : &pc);
 }
 
+// zg_gpt_sample_pen with the edit stage behind the penalties.  penalties NULL or all off: none.  Everything off:
+// zg_gpt_sample_pen / _ex itself.
+int zg_gpt_sample_edit(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
+                       const size_t* history, size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits, const float* uniforms,
+                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
+    ZG_TRY(require_init());
+    const char* who = "gpt_sample_edit";
+    ZG_TRY(check_sample_options(opt, who));
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null handle", who);
+    const bool pen_on = pen != nullptr;
+    if (pen_on) {
+        ZG_TRY(check_penalties(pen, who));
+        ZG_TRY(check_pen_handle(g, who));
+        ZG_TRY(check_history(g, history, history_stride, history_lens, 0, who));
+    }
+    EditCall ec{false, 0.0f};
+    ZG_TRY(build_edits(edits, g->cfg.vocab_size, who, g->edit_build.data(), &ec.stage_on));
+    ec.min_p = edits->min_p;
+    const PenCall pc{pen, history, history_stride, history_lens};
+    const bool pen_runs = pen_on && !penalties_off(*pen);
+    if (pen_runs || ec.stage_on) ZG_HIP(hipStreamSynchronize(gs(g)));  // (an enqueued generation may still be reading the pinned mirrors; idle otherwise)
+    return sample_impl(g, seq_len, tokens, n_tokens, *opt, uniforms, seed, tokens_out, probs_out, probs_len, pen_runs ? &pc : nullptr,
+                       edits_off(*edits) ? nullptr : &ec);
+}
+
 static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options& o, const float* uniforms, uint64_t seed,
-                       size_t* tokens_out, float* probs_out, size_t probs_len, const PenCall* pc) {
+                       size_t* tokens_out, float* probs_out, size_t probs_len, const PenCall* pc, const EditCall* ec) {
     ZG_REQUIRE(g && tokens && tokens_out, ZG_ERR_ARG, "gpt_sample: bad argument");
     const size_t V = g->cfg.vocab_size, B = g->batch;
     ZG_REQUIRE(!probs_out || probs_len >= B * V, ZG_ERR_SHAPE, "gpt_sample: probs_out needs %zu elements", B * V);
@@ -2035,7 +2158,12 @@ static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n
     hipStream_t s = gs(g);
     if (pc) {  // the raw logits are penalised and the row-maximum partials rebuilt before either sampler looks at them
         ZG_TRY(stage_penalties(g, *pc->pen, 0, pc->history, pc->stride, pc->lens, s));
-        ZG_TRY(launch_penalize(g->logits, (int)B, (int)V, g->pen, pen_history(g, false), g->part_val, g->part_idx, g->lm_grid, nullptr, s));
+        ZG_TRY(launch_penalize(g->logits, (int)B, (int)V, g->pen, pen_history(g, false), g->part_val, g->part_idx, g->lm_grid, nullptr, s,
+                               !(ec && ec->stage_on)));  // (the edit launch below rebuilds the partials behind both stages)
+    }
+    if (ec && ec->stage_on) {  // the edits act on the row the penalties leave; the partials are rebuilt by the same launch
+        ZG_TRY(stage_edits(g, s));
+        ZG_TRY(launch_logit_edit(g->logits, (int)B, (int)V, g->edit_tab, g->edit_keep, g->part_val, g->part_idx, g->lm_grid, s));
     }
     // (pinned, 320 bytes into the control block: h_ints[0 .. B) is still being read by the forward's token upload)
     float* h_u = reinterpret_cast<float*>(reinterpret_cast<char*>(g->h_ctrl) + 320);
@@ -2053,9 +2181,10 @@ static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n
     float* d_u = g->q;  // scratch: q is dead after the forward
     ZG_HIP(hipMemcpyAsync(d_u, h_u, B * sizeof(float), hipMemcpyHostToDevice, s));
     // (h_samp: nothing in flight reads it, forward_enqueue's callers drain)
-    if (const int levels = filter_launches(fill_sample_params(g->h_samp, V, o, seed))) {
+    const SamplerMode mode = fill_sample_params(g->h_samp, V, o, seed, ec ? ec->min_p : 0.0f);
+    if (threshold_sampler(mode)) {
         ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
-        ZG_TRY(launch_sample_filtered(g->logits, (int)B, (int)V, g->samp, levels, d_u, nullptr, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->filt,
+        ZG_TRY(launch_sample_filtered(g->logits, (int)B, (int)V, g->samp, filter_launches(mode), d_u, nullptr, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->filt,
                                       g->cur_token, probs_out != nullptr, s));
     } else
         ZG_TRY(launch_sample(g->logits, (int)B, (int)V, o.temp, d_u, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->cur_token, probs_out != nullptr,
@@ -2078,15 +2207,15 @@ int zg_gpt_hidden(zg_gpt* g, float* x_out, size_t len) {
 }
 
 // The options of a sampler call over `vocab` logits into *p, the host image of SampleParams (the caller uploads it); returns the
-// sampler they need: the plain one with both filters off
-static SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed) {
+// sampler they need: the plain one with both filters and min-p off, the threshold-aware tail alone for min-p alone
+static SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed, float min_p) {
     const bool k_on = o.top_k >= 1 && o.top_k < vocab, p_on = o.top_p < 1.0f;
     p->inv_temp = 1.0f / o.temp;
     p->top_k = k_on ? (unsigned)o.top_k : 0u;
     p->seed = seed;
     p->top_p = p_on ? o.top_p : 1.0f;
-    p->pad = 0;
-    return k_on && p_on ? TWO_FILTERS : (k_on || p_on) ? ONE_FILTER : PLAIN;
+    p->min_p_off = min_p_offset(o.temp, min_p);
+    return k_on && p_on ? TWO_FILTERS : (k_on || p_on) ? ONE_FILTER : min_p != 0.0f ? MINP_ONLY : PLAIN;
 }
 
 static int check_penalties(const zg_logit_penalties* p, const char* who) {
@@ -2179,6 +2308,10 @@ struct GenRequest {
     // stop conditions, checked by the entry point (check_stop); stop_on false: the request is what it was
     bool stop_on = false;
     zg_stop_conditions stop{};
+    // logit edits, checked by the entry point, which has built the set in the ONE handle's edit_build: edit_on — the
+    // edit stage runs; min_p — the sampler's threshold (0: off).  Both off: the request is what it was
+    bool edit_on = false;
+    float min_p = 0.0f;
     GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, const zg_sample_options* opt_or_null = nullptr, uint64_t seed = 0,
                size_t past = 0)
         : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past), mode(opt_or_null ? PLAIN : GREEDY),
@@ -2254,7 +2387,8 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     size_t first = 0;
     if (g->pf_x != nullptr && min_prompt >= prefill_min())
         first = min_prompt < n_steps ? min_prompt : n_steps;
-    g->gen_tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on};  // (normalized: pen_on only with a sampler, and the steps it is for have lm_head)
+    const bool edit_on = r.edit_on && r.mode != GREEDY;
+    g->gen_tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on, edit_on};  // (normalized: pen_on / edit_on only with a sampler, and the steps it is for have lm_head)
     g->stop_valid = false;
     g->gen_stop = r.stop_on;
     if (r.stop_on) {  // the conditions of this call; no row has finished; the stage has seen nothing (the stream is drained: the words are the host's)
@@ -2266,10 +2400,11 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
         g->gen_lookahead = r.stop.lookahead ? std::min(r.stop.lookahead, C) : kStopLookahead;  // (beyond the context: never waits)
     }
     if (r.mode != GREEDY) {
-        g->gen_tail.sampler = fill_sample_params(g->h_samp, V, r.opt, r.seed);
+        g->gen_tail.sampler = fill_sample_params(g->h_samp, V, r.opt, r.seed, r.min_p);
         ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     }
     if (pen_on) ZG_TRY(stage_penalties(g, r.pen, past, r.prior, r.prior_stride, r.prior_lens, s));
+    if (edit_on) ZG_TRY(stage_edits(g, s));
     g->lp_valid = false;
     if (r.lp_on) {
         ZG_TRY(stage_top_n(g, r.top_n, s));
@@ -2542,11 +2677,14 @@ int zg_gpt_generate_logprobs_enqueue(zg_gpt* g, size_t past_len, const size_t* p
 
 // zg_gpt_generate_logprobs_enqueue / _pen_enqueue / _from_enqueue with the stop stage: one more node, last in the tail, of
 // graphs of their own (StepTail.stop); the conditions live in device memory.  No conditions: the request is one of theirs.
-int zg_gpt_generate_stop_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
-                                 const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
-                                 const size_t* prior_lens, uint64_t seed, int logprobs, size_t top_n, const zg_stop_conditions* stop) {
+// ... and with the edit stage: one more node between the penalties and the sampler, of graphs of their own
+// (StepTail.edit), the set in device memory; min-p is the sampler's (SampleParams.min_p_off; alone: StepTail.sampler MINP_ONLY).
+// Everything of the generate family in one place: zg_gpt_generate_stop_enqueue is this with edits null.
+static int generate_request(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                            const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
+                            const size_t* prior_lens, uint64_t seed, int logprobs, size_t top_n, const zg_stop_conditions* stop, const zg_logit_edits* edits,
+                            const char* who) {
     ZG_TRY(require_init());
-    const char* who = "generate_stop";
     ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null argument", who);
     if (opt) ZG_TRY(check_sample_options(opt, who));
     ZG_REQUIRE(opt || !pen, ZG_ERR_ARG, "%s: penalties without sampler options (greedy picking with penalties is top_k = 1)", who);
@@ -2562,7 +2700,25 @@ int zg_gpt_generate_stop_enqueue(zg_gpt* g, size_t past_len, const size_t* promp
         r.stop_on = true;
         r.stop = *stop;
     }
+    if (edits) {
+        ZG_TRY(build_edits(edits, g->cfg.vocab_size, who, g->edit_build.data(), &r.edit_on));
+        ZG_REQUIRE(opt || edits_off(*edits), ZG_ERR_ARG, "%s: edits without sampler options (greedy picking with edits is top_k = 1)", who);
+        r.min_p = edits->min_p;
+    }
     return gen_run(&g, 1, r);
+}
+
+int zg_gpt_generate_stop_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                 const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
+                                 const size_t* prior_lens, uint64_t seed, int logprobs, size_t top_n, const zg_stop_conditions* stop) {
+    return generate_request(g, past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, pen, prior, prior_stride, prior_lens, seed, logprobs, top_n, stop,
+                            nullptr, "generate_stop");
+}
+
+int zg_gpt_generate_request_enqueue(zg_gpt* g, const zg_generate_request* r) {
+    ZG_REQUIRE(r != nullptr && r->size == sizeof(zg_generate_request), ZG_ERR_ARG, "generate_request: null request, or its size field is not sizeof(zg_generate_request)");
+    return generate_request(g, r->past_len, r->prompts, r->prompt_stride, r->prompt_lens, r->n_steps, r->options, r->penalties, r->prior, r->prior_stride,
+                            r->prior_lens, r->seed, r->logprobs, r->top_n, r->stop, r->edits, "generate_request");
 }
 
 int zg_gpt_generate_stop_result(zg_gpt* g, size_t* end_out, size_t* finish_cols_out, int* reasons_out) {
@@ -2870,6 +3026,70 @@ int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const 
             ZG_HIP(hipMemcpy(thresholds_out, ninf.data(), batch * 4, hipMemcpyDefault));
         }
     }
+    ZG_HIP(hipStreamSynchronize(s));
+    for (size_t b = 0; b < batch; ++b) tokens_out[b] = (size_t)h_tok[b];
+    return ZG_OK;
+}
+
+// The edit stage and the sampler behind it on the caller's rows (tests).  Everything off: zg_debug_sample_rows' launches.  Allocates per call.
+int zg_debug_edit_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const zg_logit_edits* edits, const float* uniforms,
+                       float* edited_out, size_t* tokens_out, float* probs_out, float* thresholds_out) {
+    ZG_TRY(require_init());
+    const char* who = "debug_edit_rows";
+    ZG_TRY(check_sample_options(opt, who));
+    ZG_REQUIRE(logits && uniforms && tokens_out && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG, "%s: bad argument", who);
+    std::vector<char> block(edit_block_bytes(vocab));
+    bool stage_on = false;
+    ZG_TRY(build_edits(edits, vocab, who, block.data(), &stage_on));
+    const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
+    SampleParams hp{};
+    const SamplerMode mode = fill_sample_params(&hp, vocab, *opt, 0, edits->min_p);
+    hipStream_t s = ctx().stream;
+    DevScratch ds;
+    char *d_filt, *d_edit;
+    FilterWs fws;
+    float *d_logits, *d_seg, *d_part, *d_u;
+    SampleParams* d_par;
+    int *d_tok, *d_pi;
+    ZG_TRY(ds.carve([&] {
+        d_filt = ds.take<char>(filter_workspace_bytes(B));
+        fws = filter_workspace(d_filt, B);
+        d_logits = ds.take<float>(batch * vocab * 4);
+        d_seg = ds.take<float>(sample_workspace_floats(B) * 4);
+        d_part = ds.take<float>((size_t)B * n_part * 4);
+        d_pi = ds.take<int>((size_t)B * n_part * 4);
+        d_par = ds.take<SampleParams>(sizeof(SampleParams));
+        d_u = ds.take<float>(batch * 4);
+        d_tok = ds.take<int>(batch * 4);
+        d_edit = ds.take<char>(block.size());
+    }));
+    std::vector<int> h_tok(batch);
+    std::vector<float> h_u(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        float u;
+        ZG_HIP(hipMemcpy(&u, uniforms + b, 4, hipMemcpyDefault));
+        ZG_REQUIRE(u >= 0.0f && u < 1.0f, ZG_ERR_ARG, "%s: uniform %f outside [0,1)", who, u);
+        h_u[b] = u;
+    }
+    ZG_HIP(hipMemsetAsync(d_filt, 0, filter_workspace_bytes(B), s));
+    ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemcpyAsync(d_u, h_u.data(), batch * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
+    ZG_TRY(launch_row_max_partials(d_logits, B, V, d_part, n_part, s));  // (lm_head's stand-in: the partials of the row as the stage finds it)
+    if (stage_on) {
+        ZG_HIP(hipMemcpyAsync(d_edit, block.data(), block.size(), hipMemcpyHostToDevice, s));
+        ZG_TRY(launch_logit_edit(d_logits, B, V, reinterpret_cast<const EditTable*>(d_edit), reinterpret_cast<const unsigned*>(d_edit + sizeof(EditTable)), d_part,
+                                 d_pi, n_part, s));
+    }
+    if (edited_out) ZG_HIP(hipMemcpyAsync(edited_out, d_logits, batch * vocab * 4, hipMemcpyDefault, s));
+    if (threshold_sampler(mode))
+        ZG_TRY(launch_sample_filtered(d_logits, B, V, d_par, filter_launches(mode), d_u, nullptr, d_part, n_part, n_part, d_seg, fws, d_tok, probs_out != nullptr, s));
+    else
+        ZG_TRY(launch_sample(d_logits, B, V, opt->temp, d_u, d_part, n_part, n_part, d_seg, d_tok, probs_out != nullptr, s));
+    ZG_HIP(hipMemcpyAsync(h_tok.data(), d_tok, batch * 4, hipMemcpyDeviceToHost, s));
+    if (probs_out) ZG_HIP(hipMemcpyAsync(probs_out, d_logits, batch * vocab * 4, hipMemcpyDefault, s));
+    std::vector<float> ninf(batch, -INFINITY);
+    if (thresholds_out) ZG_HIP(hipMemcpyAsync(thresholds_out, threshold_sampler(mode) ? fws.tau : ninf.data(), batch * 4, hipMemcpyDefault, s));
     ZG_HIP(hipStreamSynchronize(s));
     for (size_t b = 0; b < batch; ++b) tokens_out[b] = (size_t)h_tok[b];
     return ZG_OK;

@@ -565,6 +565,7 @@ __global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vo
 
 #include "sample_filter.h"
 #include "sample_penalty.h"
+#include "sample_edit.h"
 #include "sample_logprob.h"
 #include "sample_score.h"
 #include "sample_stop.h"
@@ -794,7 +795,7 @@ int launch_sample_filtered(float* logits, int batch, int vocab, const SamplePara
                            const float* part_val, int n_part, int part_stride, float* seg_ws, const FilterWs& fws, int* token_out, bool write_probs,
                            hipStream_t s) {
     ZG_REQUIRE(vocab >= 1 && vocab <= 64 * kSegMax, ZG_ERR_UNSUPPORTED, "sampler: vocabulary of %d beyond %d", vocab, 64 * kSegMax);
-    ZG_REQUIRE(params && part_val && n_part >= 1 && seg_ws && token_out && fws.mass && (n_levels == 3 || n_levels == 6) && (u || ctrl), ZG_ERR_ARG,
+    ZG_REQUIRE(params && part_val && n_part >= 1 && seg_ws && token_out && fws.mass && (n_levels == 0 || n_levels == 3 || n_levels == 6) && (u || ctrl), ZG_ERR_ARG,
                "truncated sampler: missing argument");
     const int nlb = std::min(64, (vocab + 1023) / 1024);  // ~4 elements per thread: the level kernels pay per workgroup (bin scan, histogram flush)
     for (int pos = 1; pos <= n_levels; ++pos) {
@@ -821,7 +822,7 @@ int launch_row_max_partials(const float* logits, int batch, int vocab, float* pa
 }
 
 int launch_penalize(float* logits, int batch, int vocab, const PenParams* params, const PenHistory& h, float* part_val, int* part_idx, int n_part,
-                    unsigned* counts_out, hipStream_t s) {
+                    unsigned* counts_out, hipStream_t s, bool rebuild) {
     ZG_REQUIRE(logits && params && part_val && part_idx && batch >= 1 && vocab >= 1 && n_part >= 1 && n_part <= 4096, ZG_ERR_ARG,
                "penalties: missing argument");
     ZG_REQUIRE(h.max_hist >= 0 && h.max_hist <= kPenMaxHistory, ZG_ERR_UNSUPPORTED, "penalties: a history of %d tokens exceeds the %d the LDS table holds",
@@ -839,7 +840,17 @@ int launch_penalize(float* logits, int batch, int vocab, const PenParams* params
     }
     hipLaunchKernelGGL(penalty_apply_kernel, dim3(batch), dim3(256), lds, s, logits, vocab, params, h, slots, counts_out);
     ZG_HIP(hipGetLastError());
+    if (!rebuild) return ZG_OK;
     hipLaunchKernelGGL(row_argmax_partials_kernel, dim3(n_part, batch), dim3(256), 0, s, logits, vocab, part_val, part_idx);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_logit_edit(float* logits, int batch, int vocab, const EditTable* tab, const unsigned* keep, float* part_val, int* part_idx, int n_part,
+                      hipStream_t s) {
+    ZG_REQUIRE(logits && tab && keep && part_val && part_idx && batch >= 1 && vocab >= 1 && n_part >= 1 && n_part <= 4096, ZG_ERR_ARG,
+               "logit edits: missing argument");
+    hipLaunchKernelGGL(logit_edit_kernel, dim3(n_part, batch), dim3(256), 0, s, logits, vocab, tab, keep, part_val, part_idx);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

@@ -22,6 +22,9 @@
 // (the arena is zeroed at create, launch 3 and 6 leave it zero).  The state of the descent (key prefix, rank left, mass above, target,
 // tau_k's key) goes from launch to launch through two slots per row used in turn, written by workgroup 0.
 // NaN logits: keys above +inf, weight 0; whatever threshold comes out, every index stays below the vocabulary.
+// min-p (include/zgpt2.h zg_logit_edits): tau_m = row maximum + SampleParams.min_p_off joins the threshold where sample_seg_filt_kernel
+// completes it — kept = { x >= max(tau_k, tau_p, tau_m) } —, and alone (both filters off) it is a chain of zero levels: no selection
+// launch, sample_seg_filt_kernel with tau = tau_m and the threshold-aware pick / probability kernels behind it.
 
 constexpr int kFiltBins = 2048;
 constexpr float kFiltScale = 4294967296.0f;  // fixed-point masses: e in [0, 1] x 2^32; a row of 2^18 elements sums below 2^51 (exact in a double)
@@ -236,7 +239,8 @@ __global__ __launch_bounds__(256) void filter_level_kernel(const float* __restri
     }
 }
 
-// sample_seg_kernel behind a chain of n_levels filter launches: the last search completes the key of tau
+// sample_seg_kernel behind a chain of n_levels filter launches: the last search completes the key of tau (n_levels 0: no chain,
+// tau is min-p's alone)
 __global__ __launch_bounds__(256) void sample_seg_filt_kernel(const float* __restrict__ logits, int vocab, const SampleParams* __restrict__ params,
                                                               const float* __restrict__ part_val, int n_part, int part_stride, float* __restrict__ seg_out,
                                                               FilterWs ws, int n_levels) {
@@ -246,14 +250,20 @@ __global__ __launch_bounds__(256) void sample_seg_filt_kernel(const float* __res
     const float inv_temp = params->inv_temp;
     const unsigned top_k = params->top_k;
     const int pos = n_levels + 1;
-    filter_zero(r, (pos + 1) % 3);
-    FilterState st;
-    filter_advance(r, pos, n_levels, top_k != 0u && top_k < (unsigned)vocab, params->top_p, st);
-    const float tau = filter_unkey(st.prefix);
-    if (blockIdx.x == 0 && tid == 0) ws.tau[b] = tau;
+    float tau = -INFINITY;
+    if (n_levels != 0) {  // (0: min-p alone — no chain ran, the workspace is not touched)
+        filter_zero(r, (pos + 1) % 3);
+        FilterState st;
+        filter_advance(r, pos, n_levels, top_k != 0u && top_k < (unsigned)vocab, params->top_p, st);
+        tau = filter_unkey(st.prefix);
+    }
     const float* x = logits + (size_t)b * vocab;
     float* so = seg_out + (size_t)b * (kSegMax + 2);
     const float mx = filter_row_max(part_val + (size_t)b * part_stride, n_part, s_red);  // [kSegMax] holds the row maximum itself here
+    // min-p (applied last, as HF does): tau_m = max + temp x log(min_p), one fp32 add; off (-inf): tau keeps its own bits, a NaN's too
+    const float d = params->min_p_off;
+    if (d > -INFINITY) tau = fmaxf(tau, mx + d);
+    if (blockIdx.x == 0 && tid == 0) ws.tau[b] = tau;
     const int nseg = (vocab + 63) >> 6;
     for (int sg = blockIdx.x * 4 + wave; sg < nseg; sg += gridDim.x * 4) {
         const int i = sg * 64 + lane;

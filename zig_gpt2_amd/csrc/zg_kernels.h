@@ -415,14 +415,15 @@ struct SampleParams {
     unsigned top_k;  // 0: off (the truncated sampler only; read on the device, so one captured graph serves every value)
     unsigned long long seed;
     float top_p;     // 1: off
-    unsigned pad;
+    float min_p_off; // min-p: temp x log(min_p), added to the row maximum for the threshold tau_m (-inf: off; the filtered sampler kernels only)
 };
 int launch_sample_step(float* logits, int batch, int vocab, const SampleParams* params, const StepCtrl* ctrl, const float* part_val, int n_part,
                        int part_stride, float* seg_ws, int* token_out, hipStream_t s);
 // The sampler behind top-k / top-p truncation (sample_filter.h: an exact radix select of the threshold, one launch per 11-bit
 // level, then the segment sums / pick / probabilities with weight 0 under the threshold).  n_levels: 3 = ONE filter is on (top-k
 // if params->top_k is, else the nucleus), 6 = both (top-k, then the nucleus over what it kept) — the launches are the same for
-// every option value, so a captured chain serves them all.  params lives in device memory; u (device, [batch]) or, when null, the
+// every option value, so a captured chain serves them all; 0 = min-p alone: no selection launch, the threshold-aware tail kernels
+// with tau = row maximum + params->min_p_off (with 3 or 6 the same threshold is folded into max(tau_k, tau_p)).  params lives in device memory; u (device, [batch]) or, when null, the
 // counter PRNG of (params->seed, ctrl->seq_len, b).  fws: filter_workspace_bytes(batch) bytes whose first
 // filter_workspace_zeroed_bytes(batch) were zero before the first chain (every chain leaves them so).  write_probs: the
 // renormalised probabilities (exact 0 where dropped) are left in the logits rows.
@@ -461,8 +462,25 @@ struct PenHistory {
     int max_hist;
 };
 constexpr int kPenMaxHistory = 8192;  // 16384 slots x (key, count) = 128 KB of the 160 KB LDS
+// rebuild false: the second launch is left out — for a tail whose edit stage (launch_logit_edit) follows and rebuilds the partials from
+// the row it leaves; nothing between the two reads them.
 int launch_penalize(float* logits, int batch, int vocab, const PenParams* params, const PenHistory& h, float* part_val, int* part_idx, int n_part,
-                    unsigned* counts_out, hipStream_t s);
+                    unsigned* counts_out, hipStream_t s, bool rebuild = true);
+
+// Logit bias and token allow / ban lists on the logit row, behind the penalties and in front of either sampler (sample_edit.h;
+// include/zgpt2.h zg_logit_edits).  ONE launch, grid (n_part, batch): every workgroup edits one slice of a row — -inf where the keep
+// set's bit is clear, x + v where a kept index has a bias — and leaves that slice's maximum (lowest index on ties) in part_val /
+// part_idx [batch][n_part], the geometry of launch_penalize's rebuild.  tab (device): the bias pairs, distinct ids; keep (device):
+// a bitmap of vocab bits, (vocab + 31) / 32 words.  Count and ids are read on the device and bounds-checked there, so one captured
+// launch serves every set.
+constexpr int kEditMaxBias = 512;
+struct EditTable {
+    int n_bias, pad[3];
+    int ids[kEditMaxBias];
+    float vals[kEditMaxBias];
+};
+int launch_logit_edit(float* logits, int batch, int vocab, const EditTable* tab, const unsigned* keep, float* part_val, int* part_idx, int n_part,
+                      hipStream_t s);
 
 // The log-probability stage behind the sampler (sample_logprob.h; include/zgpt2.h zg_gpt_generate_logprobs_enqueue): for every row,
 // the log-probability of the token the step records and the *top_n (device memory, 0 .. 20) largest logits with theirs, written

@@ -32,7 +32,7 @@ class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
                  sampled_generate=False, weights_b24=False, truncated_generate=False, penalized_generate=False, logprobs_generate=False,
-                 score=False, stop_generate=False):
+                 score=False, stop_generate=False, edited_generate=False):
         """share_weights_with / own_stream / stream_priority: zg_gpt_options of zg_gpt_create_ex (a handle of an independent
         prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config).
         weights_b24: matrices stored as 24-bit floats (ZG_GPT_WEIGHTS_B24: each fp32 weight rounded to 16 mantissa bits, 3/4 of
@@ -41,7 +41,8 @@ class GPT:
         the graphs of generations with repetition / presence / frequency penalties (ZG_GPT_PENALIZED_GENERATE);
         logprobs_generate: the same for the log-probability twins of every graph create captures (ZG_GPT_LOGPROBS_GENERATE).
         score: carve what `score` / `loglikelihood` need (ZG_GPT_SCORE); without it they raise ZG_ERR_UNSUPPORTED.
-        stop_generate: the stop twins of every graph create captures (ZG_GPT_STOP_GENERATE), as the other *_generate flags."""
+        stop_generate: the stop twins of every graph create captures (ZG_GPT_STOP_GENERATE), as the other *_generate flags.
+        edited_generate: the graphs of generations with logit edits or min-p (ZG_GPT_EDITED_GENERATE), as the other *_generate flags."""
         self.config, self.batch = config, batch
         L = _lib.load()
         flags = (_lib.GPT_WEIGHTS_F32 if weights_f32 else 0) | (0 if use_graph else _lib.GPT_NO_GRAPH)
@@ -57,6 +58,7 @@ class GPT:
         flags |= _lib.GPT_LOGPROBS_GENERATE if logprobs_generate else 0
         flags |= _lib.GPT_SCORE if score else 0
         flags |= _lib.GPT_STOP_GENERATE if stop_generate else 0
+        flags |= _lib.GPT_EDITED_GENERATE if edited_generate else 0
         cfg = _lib.GptConfig(config.vocab_size, config.context_size, config.n_layer, config.n_heads, config.n_embed)
         h = C.c_void_p()
         if share_weights_with is None and not own_stream:
@@ -242,6 +244,30 @@ class GPT:
             return None
         return _lib.LogitPenalties(repetition_penalty, presence_penalty, frequency_penalty)
 
+    @staticmethod
+    def _edits(logit_bias, allowed_token_ids, banned_token_ids, min_p):
+        """(zg_logit_edits, its arrays), or None while everything is off (the call is then today's, through today's entry point).
+        An allow-list that is given but empty is not "off": it reaches the library, which refuses it."""
+        if not logit_bias and allowed_token_ids is None and not len(banned_token_ids if banned_token_ids is not None else ()) and min_p == 0.0:
+            return None
+        if allowed_token_ids is not None and len(allowed_token_ids) == 0:
+            raise ValueError("allowed_token_ids is empty: no token could be picked")
+        return _lib.logit_edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
+
+    def _request_enqueue(self, past, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, conds, edits):
+        """zg_gpt_generate_request_enqueue: the one call every generation with penalties, log-probabilities, stop conditions or
+        edits goes through.  conds: a zg_stop_conditions or None; edits: `_edits(...)`."""
+        if (pen is not None or edits is not None) and temp is None:
+            raise ValueError("penalties and edits need a sampler: greedy picking with them is temp=1.0, top_k=1")
+        opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
+        pp, pstride, plens, keep = self._token_lists(prior if pen is not None else None)
+        r = _lib.generate_request(past_len=past, prompts=ptr(mat), prompt_stride=stride, prompt_lens=ptr(lens), n_steps=n_steps,
+                                  options=None if opt is None else C.addressof(opt), penalties=None if pen is None else C.addressof(pen), prior=pp,
+                                  prior_stride=pstride, prior_lens=plens, seed=seed, logprobs=int(logprobs is not None), top_n=int(logprobs or 0),
+                                  stop=None if conds is None else C.addressof(conds), edits=None if edits is None else C.addressof(edits[0]))
+        check(self._L.zg_gpt_generate_request_enqueue(self.h, C.addressof(r)))
+        del keep
+
     def _token_lists(self, lists):
         """One token list per row (None: none) -> (ptr or None, stride, ptr to lengths or None), with the arrays kept alive."""
         if lists is None:
@@ -251,20 +277,14 @@ class GPT:
             mat, stride = np.zeros((self.batch, 1), np.uint64), 1
         return ptr(mat), stride, ptr(lens), (mat, lens)
 
-    def _generate_stop(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead):
-        """A generation with stop conditions (zg_gpt_generate_stop_enqueue): what `_generate` returns, cut at `end` —
+    def _generate_stop(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits=None):
+        """A generation with stop conditions (the request call): what `_generate` returns, cut at `end` —
         columns past_len .. end - 1.  `stop_result()` tells where every row finished and why."""
-        if pen is not None and temp is None:
-            raise ValueError("penalties need a sampler: greedy picking with penalties is temp=1.0, top_k=1")
         past = past_len or 0
         mat, lens, stride = self._prompts(prompts)
-        opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
-        pp, pstride, plens, keep = self._token_lists(prior if pen is not None else None)
         conds, keep_conds = _lib.stop_conditions(stop_token_ids, stop, lookahead)
-        check(self._L.zg_gpt_generate_stop_enqueue(self.h, past, ptr(mat), stride, ptr(lens), n_steps, None if opt is None else C.addressof(opt),
-                                                   None if pen is None else C.addressof(pen), pp, pstride, plens, seed, int(logprobs is not None),
-                                                   int(logprobs or 0), C.addressof(conds)))
-        del keep, keep_conds
+        self._request_enqueue(past, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, conds, edits)
+        del keep_conds
         n = self.stop_result()[0] - past if conds.n_ids or conds.n_seqs else n_steps  # (no conditions: the plain call ran)
         out = self.generate_fetch_range(past, n)
         return out if logprobs is None else (out,) + self.generate_fetch_logprobs(past, n, logprobs)
@@ -279,27 +299,21 @@ class GPT:
         check(self._L.zg_gpt_generate_stop_result(self.h, C.byref(end), ptr(cols), ptr(reasons)))
         return end.value, [None if int(c) == _lib.STOP_NONE else int(c) for c in cols], [int(r) for r in reasons]
 
-    def _generate(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=True):
+    def _generate(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=True, edits=None):
         """Every generation of this class: enqueue through the entry point its arguments ask for, then (fetch) return what the
         public method returns.  past_len None: not a continuation.  temp None: greedy.  pen: `_penalties(...)`.  logprobs: top_n or
-        None.  With penalties and log-probabilities off the plain entry points run (zg_gpt_generate_greedy / _enqueue,
-        zg_gpt_generate_sample[_ex][_enqueue], zg_gpt_generate_from_enqueue), else zg_gpt_generate_pen_enqueue, else (logprobs)
-        zg_gpt_generate_logprobs_enqueue."""
-        if pen is not None and temp is None:
-            raise ValueError("penalties need a sampler: greedy picking with penalties is temp=1.0, top_k=1")
+        None.  edits: `_edits(...)`.  With penalties, log-probabilities and edits off the plain entry points run
+        (zg_gpt_generate_greedy / _enqueue, zg_gpt_generate_sample[_ex][_enqueue], zg_gpt_generate_from_enqueue), else the request
+        call (zg_gpt_generate_request_enqueue)."""
+        if (pen is not None or edits is not None) and temp is None:
+            raise ValueError("penalties and edits need a sampler: greedy picking with them is temp=1.0, top_k=1")
         mat, lens, stride = self._prompts(prompts)
         head = (ptr(mat), stride, ptr(lens), n_steps)
         opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
         opt_p = None if opt is None else C.addressof(opt)
         out = None
-        if logprobs is not None or pen is not None:
-            pp, pstride, plens, keep = self._token_lists(prior if pen is not None else None)
-            tail = (opt_p, None if pen is None else C.addressof(pen), pp, pstride, plens, seed)
-            if logprobs is not None:
-                check(self._L.zg_gpt_generate_logprobs_enqueue(self.h, past_len or 0, *head, *tail, int(logprobs)))
-            else:
-                check(self._L.zg_gpt_generate_pen_enqueue(self.h, past_len or 0, *head, *tail))
-            del keep
+        if logprobs is not None or pen is not None or edits is not None:
+            self._request_enqueue(past_len or 0, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, None, edits)
         elif past_len is not None:
             check(self._L.zg_gpt_generate_from_enqueue(self.h, past_len, *head, opt_p, seed))
         elif fetch:  # the calls that enqueue and fetch in one
@@ -329,16 +343,26 @@ class GPT:
         return lp, ids, top
 
     def sample(self, seq_len, tokens, temp, uniforms=None, seed=0, want_probs=False, top_k=0, top_p=1.0, repetition_penalty=1.0,
-               presence_penalty=0.0, frequency_penalty=0.0, history=None):
+               presence_penalty=0.0, frequency_penalty=0.0, history=None, logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_p=0.0):
         """GPT.sample (src/main.zig:198-207) with reproducible uniforms; returns tokens [batch] (and probs).  top_k / top_p:
         truncation in front of the draw (zg_sample_options; the defaults are off and take zg_gpt_sample itself).
         repetition_penalty / presence_penalty / frequency_penalty: zg_logit_penalties on the tokens of `history` (one list per row),
-        applied to the raw logits first (zg_gpt_sample_pen; the defaults are off and take today's call)."""
+        applied to the raw logits first (zg_gpt_sample_pen; the defaults are off and take today's call).  logit_bias ({id: value}) /
+        allowed_token_ids / banned_token_ids: edits of the row behind the penalties; min_p: the sampler's min-p truncation
+        (zg_logit_edits; zg_gpt_sample_edit; the defaults are off and take today's call)."""
         tokens = np.ascontiguousarray(np.atleast_1d(tokens), dtype=np.uint64)
         u = None if uniforms is None else np.ascontiguousarray(np.atleast_1d(uniforms), dtype=np.float32)
         out = np.zeros(self.batch, np.uint64)
         probs = np.empty((self.batch, self.config.vocab_size), np.float32) if want_probs else None
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
+        if edits is not None:
+            opt = _lib.SampleOptions(temp, top_k, top_p)
+            hp, hstride, hlens, keep = self._token_lists((history if history is not None else [None] * self.batch) if pen is not None else None)
+            check(self._L.zg_gpt_sample_edit(self.h, seq_len, ptr(tokens), tokens.size, C.addressof(opt), None if pen is None else C.addressof(pen), hp, hstride,
+                                             hlens, C.addressof(edits[0]), ptr(u), seed, ptr(out), ptr(probs), ops._n(probs)))
+            del keep
+            return (out, probs) if want_probs else out
         if pen is not None:
             opt = _lib.SampleOptions(temp, top_k, top_p)
             hp, hstride, hlens, keep = self._token_lists(history if history is not None else [None] * self.batch)
@@ -389,36 +413,43 @@ class GPT:
         return out
 
     def generate_from(self, past_len, prompts, n_steps, temp=None, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
-                      frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0):
+                      frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0, logit_bias=None,
+                      allowed_token_ids=None, banned_token_ids=None, min_p=0.0):
         """generate entered at position past_len (zg_gpt_generate_from_enqueue): `prompts` are the new tokens of each row, fed
         behind the past_len cached positions; returns the tokens of positions past_len .. past_len + n_steps - 1 ([batch, n_steps]).
         temp=None: greedy; otherwise the sampler of generate_sample (top_k / top_p as there).  Penalties as generate_sample; the
         tokens below past_len count only when passed as `prior` (one list per row).  logprobs=top_n: as `generate`, for the
         columns past_len .. past_len + n_steps - 1.  stop_token_ids / stop / lookahead: as `generate`; the columns are absolute and
-        what is returned is columns past_len .. end - 1."""
+        what is returned is columns past_len .. end - 1.  logit_bias / allowed_token_ids / banned_token_ids / min_p: as `sample`."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
         if stop_token_ids is not None or stop is not None:
-            return self._generate_stop(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead)
-        return self._generate(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
+            return self._generate_stop(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits)
+        return self._generate(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, edits=edits)
 
     def generate_sample(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
-                        frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0):
+                        frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0, logit_bias=None,
+                        allowed_token_ids=None, banned_token_ids=None, min_p=0.0):
         """generate (src/main.zig:322-342) as the reference runs it — every token behind the prompt drawn by GPT.sample — with the
         loop on the device; the tokens of the host loop over `sample(T, tok, temp, seed=seed)`.  top_k / top_p: as `sample`.
         repetition_penalty / presence_penalty / frequency_penalty: on the tokens the row holds when a pick is drawn — `prior` (one
         list per row, optional) followed by the row's prompt and picks so far (zg_gpt_generate_pen_enqueue; defaults: today's call).
         logprobs=top_n: as `generate` — of the row the sampler received, at temperature 1 and before truncation.
-        stop_token_ids / stop / lookahead: as `generate`."""
+        stop_token_ids / stop / lookahead: as `generate`.  logit_bias ({id: value}) / allowed_token_ids / banned_token_ids: edits of
+        every step's row behind the penalties; min_p: min-p truncation (defaults: today's call)."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
         if stop_token_ids is not None or stop is not None:
-            return self._generate_stop(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead)
-        return self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs)
+            return self._generate_stop(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits)
+        return self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, edits=edits)
 
     def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
-                                frequency_penalty=0.0, prior=None, logprobs=None):
+                                frequency_penalty=0.0, prior=None, logprobs=None, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
+                                min_p=0.0):
         """generate_sample without the fetch; results through generate_fetch and (logprobs=top_n) generate_fetch_logprobs."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
-        self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=False)
+        edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
+        self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=False, edits=edits)
 
     PROFILE_CLASSES = ["embed", "ln1_c_attn_kv", "attention", "merge_attn_proj_resid", "ln2_c_fc_gelu",
                        "mlp_proj_resid", "lnf_lm_head_argmax", "step_total"]
