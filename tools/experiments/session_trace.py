@@ -1,4 +1,5 @@
 """Scripted session for the launch-trace comparison: python tools/experiments/session_trace.py OUT.npz  (library chosen by ZGPT2_LIB)."""
+import ctypes as C
 import os
 import sys
 
@@ -77,6 +78,22 @@ def session(tag, cfg, w, B, long=True, prefill=True, **kw):
     r["from_pen_lp20"] = m.generate_from(past, new, upto - past - 5, temp=0.8, seed=7, prior=prior, logprobs=20, **pen)
     m.forward(1, toks(62, B, 1, V)[:, 0], compute_logits=False)
     r["sample_pen"] = m.sample(2, toks(63, B, 1, V)[:, 0], 0.9, seed=3, history=[synth.rand_tokens(90 + b, 7, V) for b in range(B)], **pen)
+    # the rest of the sampler chain: the stop stage (a stop sequence of two tokens that neither run it is added to ever picks in a
+    # row: the generation runs to its end, so the launches do not depend on when the host saw the device finish), a bias list, an
+    # allow list behind penalties, min-p alone, and the per-token call with edits and with penalties and edits together
+    seen = {(int(x[i]), int(x[i + 1])) for a in (r["greedy"], r["samp_k"]) for x in a for i in range(len(x) - 1)}
+    never = next([a, b] for a in range(V) for b in range(V) if (a, b) not in seen)
+    r["greedy_stop"] = m.generate(prompts, upto, stop=[never])
+    r["samp_k_stop_lp5"] = m.generate_sample(prompts, upto, 0.9, seed=5, top_k=40, logprobs=5, stop=[never])
+    assert m.stop_result()[0] == upto
+    bias = {int(t): 1.5 - 0.5 * i for i, t in enumerate(sorted(set(int(t) for t in synth.rand_tokens(95, 6, V))))}
+    allowed = sorted(set(int(t) for t in synth.rand_tokens(96, V // 3, V)))
+    r["samp_bias"] = m.generate_sample(prompts, upto, 0.9, seed=5, logit_bias=bias, banned_token_ids=[int(t) for t in synth.rand_tokens(97, 3, V)])
+    r["samp_allow_pen"] = m.generate_sample(prompts, upto - 5, 0.9, seed=5, top_p=0.9, prior=prior, allowed_token_ids=allowed, **pen)
+    r["samp_minp"] = m.generate_sample(prompts, upto, 0.9, seed=5, min_p=0.1)
+    r["sample_edit"] = m.sample(3, toks(64, B, 1, V)[:, 0], 0.9, seed=3, top_k=40, logit_bias=bias, allowed_token_ids=allowed, min_p=0.05)
+    r["sample_pen_edit"] = m.sample(4, toks(65, B, 1, V)[:, 0], 0.9, seed=3, history=[synth.rand_tokens(90 + b, 7, V) for b in range(B)],
+                                    logit_bias=bias, **pen)
     if kw.get("score"):
         n = (300 if B == 1 else 70) if long else min(20, Cx)  # (more than one block of lm_head rows where the model is large)
         r["score0"] = m.score(toks(9, B, n, V), top_n=0, want_logits=True)
@@ -114,6 +131,27 @@ del w
 for name, B in (("tiny3", 3), ("nano-char", 1)):
     c = synth.CONFIGS[name]
     session(f"{name} b{B}", c, weights(c), B, long=False, score=True)
+
+# the sampler chain on rows of the caller's (no handle): one call each of the three debug entry points at a vocabulary of 1000
+B, V = 3, 1000
+rng = np.random.default_rng(11)
+x = (rng.standard_normal((B, V)) * 3).astype(np.float32)
+u = rng.random(B).astype(np.float32)
+tok, probs, thr, edited = np.zeros(B, np.uint64), np.zeros((B, V), np.float32), np.zeros(B, np.float32), np.zeros((B, V), np.float32)
+opt = _lib.SampleOptions(0.9, 40, 0.9)
+_lib.check(lib.zg_debug_sample_rows(_lib.ptr(x), B, V, C.addressof(opt), _lib.ptr(u), _lib.ptr(tok), _lib.ptr(probs), _lib.ptr(thr)))
+out["rows/sample/0"], out["rows/sample/1"], out["rows/sample/2"] = tok.copy(), probs.copy(), thr.copy()
+e, keep = _lib.logit_edits({5: 2.0, 999: -1.0}, None, [7, 8, 9], 0.05)
+_lib.check(lib.zg_debug_edit_rows(_lib.ptr(x), B, V, C.addressof(opt), C.addressof(e), _lib.ptr(u), _lib.ptr(edited), _lib.ptr(tok), _lib.ptr(probs), _lib.ptr(thr)))
+out["rows/edit/0"], out["rows/edit/1"], out["rows/edit/2"], out["rows/edit/3"] = edited.copy(), tok.copy(), probs.copy(), thr.copy()
+hist = np.ascontiguousarray(rng.integers(0, V, (B, 40)), np.uint64)
+lens = np.array([40, 0, 17], np.uint64)
+pen = _lib.LogitPenalties(1.3, 0.4, 0.2)
+counts = np.zeros((B, V), np.uint32)
+_lib.check(lib.zg_debug_penalize_rows(_lib.ptr(x), B, V, C.addressof(pen), _lib.ptr(hist), 40, _lib.ptr(lens), _lib.ptr(edited), _lib.ptr(counts)))
+out["rows/penalize/0"], out["rows/penalize/1"] = edited.copy(), counts.copy()
+marks.append("debug rows")
+mark()
 
 np.savez(sys.argv[1], **out)
 open(sys.argv[1] + ".marks", "w").write("\n".join(marks) + "\n")

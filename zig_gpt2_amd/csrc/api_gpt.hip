@@ -4,8 +4,9 @@
 // reference); a decode step is a fixed chain of kernels captured once into a hipGraph whose
 // position, tokens and argmax all live in device memory, so a whole greedy generation is enqueued
 // without a host round trip per token.  Three things exist once each: the whole-prompt pass (pass_impl: zg_gpt_prefill is
-// zg_gpt_extend at 0), the generation request (GenRequest, run by gen_run for every zg_gpt_generate*_enqueue) and the shape of a
-// decode step (StepKey {with_logits, multi, StepTail}: what enqueue_step launches and which graph replays it).  What follows
+// zg_gpt_extend at 0), the generation request (every zg_gpt_generate*_enqueue fills a zg_generate_request, generate_request alone
+// makes the GenRequest gen_run runs) and the shape of a decode step (StepKey {with_logits, multi, StepTail}: what enqueue_step
+// launches and which graph replays it; the sampler chain behind lm_head is emitted by emit_sampler_chain for every user).  What follows
 // lm_head — which sampler, penalties or not, log-probabilities or not — travels as ONE value, StepTail, from the request to the
 // launches: a generation holds one (zg_gpt::gen_tail), a step is told one (StepOpts::tail), a graph is keyed by one, and the graph
 // table is indexed by its fields as mixed-radix digits (step_index).  ONE rule says which graphs exist when: create captures the
@@ -832,6 +833,59 @@ PenHistory pen_history(const zg_gpt* g, bool loop) {
     return h;
 }
 
+// What the sampler chain — penalties, edits, selection launches, sampler — reads and writes.  The draw comes from one of two
+// sources: the loop's control block (ctrl: the uniform is the counter PRNG of the position it holds), or a per-call buffer of
+// uniforms (u, with the call's temperature and whether the probabilities are written back over the row).
+struct SamplerChain {
+    float* logits;
+    int batch, vocab;
+    float* part_val;  // row-maximum partials [batch][n_part] as lm_head's epilogue leaves them, and their indices
+    int* part_idx;
+    int n_part;
+    const PenParams* pen;
+    PenHistory hist;
+    unsigned* counts;  // (zg_debug_penalize_rows: the counts of every row's history)
+    const EditTable* edit_tab;
+    const unsigned* edit_keep;
+    const SampleParams* params;
+    float* seg_ws;
+    FilterWs filt;
+    const StepCtrl* ctrl;  // the loop's draws ...
+    const float* u;        // ... or a call's
+    float temp;
+    bool write_probs;
+    int* pick;
+};
+
+// The chain of a handle: the loop's (draws by its control block into `sampled`, history = prior + its own record), or that of a
+// per-token call, whose draw source and destination are the caller's to add
+SamplerChain handle_chain(const zg_gpt* g, bool loop) {
+    SamplerChain c{};
+    c.logits = g->logits, c.batch = (int)g->batch, c.vocab = (int)g->cfg.vocab_size;
+    c.part_val = g->part_val, c.part_idx = g->part_idx, c.n_part = g->lm_grid;
+    c.pen = g->pen, c.hist = pen_history(g, loop);
+    c.edit_tab = g->edit_tab, c.edit_keep = g->edit_keep;
+    c.params = g->samp, c.seg_ws = g->samp_ws, c.filt = g->filt;
+    if (loop) c.ctrl = g->ctrl, c.pick = g->sampled;
+    return c;
+}
+
+// The launches of tail t behind lm_head, up to the pick: GPT.sample's tail (main.zig:200-206) behind the stages that rewrite the
+// row.  Launches only — what they read is staged by the caller (enqueue_step runs under capture).  A GREEDY tail has no sampler
+// launch: the partials are the pick.
+int emit_sampler_chain(const SamplerChain& c, StepTail t, hipStream_t s) {
+    // the penalties act on the raw logits, the edits on the row the penalties leave (HF's processor order); the row-maximum
+    // partials every sampler starts from are rebuilt only behind the LAST stage that rewrites the row — the edit launch does it itself
+    if (t.pen) ZG_TRY(launch_penalize(c.logits, c.batch, c.vocab, c.pen, c.hist, c.part_val, c.part_idx, c.n_part, c.counts, s, !t.edit));
+    if (t.edit) ZG_TRY(launch_logit_edit(c.logits, c.batch, c.vocab, c.edit_tab, c.edit_keep, c.part_val, c.part_idx, c.n_part, s));
+    if (t.sampler == GREEDY) return ZG_OK;
+    if (threshold_sampler(t.sampler))  // a filter or min-p: the selection launches, then the tail kernels that read tau
+        return launch_sample_filtered(c.logits, c.batch, c.vocab, c.params, filter_launches(t.sampler), c.u, c.ctrl, c.part_val, c.n_part, c.n_part, c.seg_ws,
+                                      c.filt, c.pick, c.write_probs, s);
+    if (c.ctrl) return launch_sample_step(c.logits, c.batch, c.vocab, c.params, c.ctrl, c.part_val, c.n_part, c.n_part, c.seg_ws, c.pick, s);
+    return launch_sample(c.logits, c.batch, c.vocab, c.temp, c.u, c.part_val, c.n_part, c.n_part, c.seg_ws, c.pick, c.write_probs, s);
+}
+
 // One decode step = GPT.forward (main.zig:178-195) for all sequences.
 int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const StepOpts& o = StepOpts()) {
     StepProf* const prof = o.prof;
@@ -948,27 +1002,11 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         return launch_stop(a, s);
     };
     const StepTail tail = o.tail;
-    if (tail.sampler == GREEDY && with_logits && only < 0 && !rec) {  // (the greedy graphs have no sampler node)
-        if (tail.lp) ZG_TRY(logprobs(nullptr));
-        if (tail.stop) ZG_TRY(stop(nullptr));
-    }
-    if (tail.sampler == GREEDY || !with_logits || only >= 0 || rec) return ZG_OK;
-    // the penalties act on the raw logits (HF's order); the row-maximum partials both samplers start from are rebuilt behind them —
-    // by the edit stage's own launch where one follows (the partials need rebuilding only behind the last stage that rewrites the row)
-    if (tail.pen)
-        ZG_TRY(launch_penalize(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->pen, pen_history(g, true), g->part_val, g->part_idx, g->lm_grid, nullptr, s,
-                               !tail.edit));
-    // the edits act on the row the penalties leave (HF's processor order) and leave the partials rebuilt from what they wrote
-    if (tail.edit)
-        ZG_TRY(launch_logit_edit(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->edit_tab, g->edit_keep, g->part_val, g->part_idx, g->lm_grid, s));
-    if (threshold_sampler(tail.sampler))
-        ZG_TRY(launch_sample_filtered(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, filter_launches(tail.sampler), nullptr, g->ctrl, g->part_val,
-                                      g->lm_grid, g->lm_grid, g->samp_ws, g->filt, g->sampled, false, s));
-    else
-        ZG_TRY(launch_sample_step(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->samp, g->ctrl, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws,
-                                  g->sampled, s));
-    if (tail.lp) ZG_TRY(logprobs(g->sampled));
-    if (tail.stop) ZG_TRY(stop(g->sampled));
+    if (!with_logits || only >= 0 || rec) return ZG_OK;
+    const int* const picks = tail.sampler == GREEDY ? nullptr : g->sampled;  // (the greedy graphs have no sampler node)
+    ZG_TRY(emit_sampler_chain(handle_chain(g, true), tail, s));
+    if (tail.lp) ZG_TRY(logprobs(picks));
+    if (tail.stop) ZG_TRY(stop(picks));
     return ZG_OK;
 }
 
@@ -2008,29 +2046,11 @@ int zg_gpt_argmax(zg_gpt* g, size_t* tokens_out, size_t n_tokens) {
     return ZG_OK;
 }
 
-static SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed, float min_p = 0.0f);
-static int check_sample_options(const zg_sample_options* o, const char* who);
-// The explicit history of a penalised per-token call: [batch][stride] tokens, lens[b] of each row
-struct PenCall {
-    const zg_logit_penalties* pen;
-    const size_t* history;
-    size_t stride;
-    const size_t* lens;
-};
-static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options& o, const float* uniforms, uint64_t seed,
-                       size_t* tokens_out, float* probs_out, size_t probs_len, const PenCall* pc = nullptr, const struct EditCall* ec = nullptr);
-static int check_penalties(const zg_logit_penalties* p, const char* who);
-static int check_pen_handle(const zg_gpt* g, const char* who);
-static int check_history(const zg_gpt* g, const size_t* tokens, size_t stride, const size_t* lens, size_t extra, const char* who);
-static int stage_penalties(zg_gpt* g, const zg_logit_penalties& p, size_t past, const size_t* tokens, size_t stride, const size_t* lens, hipStream_t s);
 static inline bool penalties_off(const zg_logit_penalties& p) { return p.repetition == 1.0f && p.presence == 0.0f && p.frequency == 0.0f; }
 
-// ---- Logit edits (include/zgpt2.h zg_logit_edits).  What a checked set asks of a call: the edit stage (any of the
-// three lists) and / or the sampler's min-p threshold
-struct EditCall {
-    bool stage_on;  // the set built in the handle's edit_build goes to the device and the edit launch runs
-    float min_p;
-};
+// ---- Logit edits (include/zgpt2.h zg_logit_edits).  A checked set asks a call for the edit stage (any of the three
+// lists: build_edits' stage_on — the set built in the handle's edit_build goes to the device and the edit launch runs) and / or for
+// the sampler's min-p threshold
 static inline bool edits_off(const zg_logit_edits& e) { return e.n_bias == 0 && e.n_allowed == 0 && e.n_banned == 0 && e.min_p == 0.0f; }
 
 // temp x log(min_p) in double, rounded once: what the sampler adds to the row maximum (min_p 0: -inf, nothing is cut)
@@ -2089,111 +2109,6 @@ static int stage_edits(zg_gpt* g, hipStream_t s) {
 int zg_debug_min_p_offset(float temp, float min_p, float* d_out) {
     ZG_REQUIRE(d_out != nullptr && temp > 0.0f && min_p >= 0.0f && min_p < 1.0f, ZG_ERR_ARG, "debug_min_p_offset: temp %f, min_p %f", temp, min_p);
     *d_out = min_p_offset(temp, min_p);
-    return ZG_OK;
-}
-
-int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, const float* uniforms,
-                  uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "gpt_sample: bad argument");
-    return sample_impl(g, seq_len, tokens, n_tokens, zg_sample_options{temp, 0, 1.0f}, uniforms, seed, tokens_out, probs_out, probs_len);
-}
-
-// zg_gpt_sample behind top-k / nucleus truncation (filters off: exactly zg_gpt_sample's launches)
-int zg_gpt_sample_ex(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const float* uniforms,
-                     uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
-    ZG_TRY(require_init());
-    ZG_TRY(check_sample_options(opt, "gpt_sample_ex"));
-    return sample_impl(g, seq_len, tokens, n_tokens, *opt, uniforms, seed, tokens_out, probs_out, probs_len);
-}
-
-// zg_gpt_sample_ex with the penalty stage in front: the history is the caller's.  All penalties off: zg_gpt_sample_ex itself.
-int zg_gpt_sample_pen(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
-                      const size_t* history, size_t history_stride, const size_t* history_lens, const float* uniforms, uint64_t seed, size_t* tokens_out,
-                      float* probs_out, size_t probs_len) {
-    ZG_TRY(require_init());
-    ZG_TRY(check_sample_options(opt, "gpt_sample_pen"));
-    ZG_TRY(check_penalties(pen, "gpt_sample_pen"));
-    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "gpt_sample_pen: null handle");
-    ZG_TRY(check_pen_handle(g, "gpt_sample_pen"));
-    ZG_TRY(check_history(g, history, history_stride, history_lens, 0, "gpt_sample_pen"));
-    const PenCall pc{pen, history, history_stride, history_lens};
-    if (!penalties_off(*pen)) ZG_HIP(hipStreamSynchronize(gs(g)));  // (an enqueued generation may still be reading the pinned mirrors; idle otherwise)
-    return sample_impl(g, seq_len, tokens, n_tokens, *opt, uniforms, seed, tokens_out, probs_out, probs_len, penalties_off(*pen) ? nullptr : &pc);
-}
-
-// zg_gpt_sample_pen with the edit stage behind the penalties.  penalties NULL or all off: none.  Everything off:
-// zg_gpt_sample_pen / _ex itself.
-int zg_gpt_sample_edit(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
-                       const size_t* history, size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits, const float* uniforms,
-                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
-    ZG_TRY(require_init());
-    const char* who = "gpt_sample_edit";
-    ZG_TRY(check_sample_options(opt, who));
-    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null handle", who);
-    const bool pen_on = pen != nullptr;
-    if (pen_on) {
-        ZG_TRY(check_penalties(pen, who));
-        ZG_TRY(check_pen_handle(g, who));
-        ZG_TRY(check_history(g, history, history_stride, history_lens, 0, who));
-    }
-    EditCall ec{false, 0.0f};
-    ZG_TRY(build_edits(edits, g->cfg.vocab_size, who, g->edit_build.data(), &ec.stage_on));
-    ec.min_p = edits->min_p;
-    const PenCall pc{pen, history, history_stride, history_lens};
-    const bool pen_runs = pen_on && !penalties_off(*pen);
-    if (pen_runs || ec.stage_on) ZG_HIP(hipStreamSynchronize(gs(g)));  // (an enqueued generation may still be reading the pinned mirrors; idle otherwise)
-    return sample_impl(g, seq_len, tokens, n_tokens, *opt, uniforms, seed, tokens_out, probs_out, probs_len, pen_runs ? &pc : nullptr,
-                       edits_off(*edits) ? nullptr : &ec);
-}
-
-static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options& o, const float* uniforms, uint64_t seed,
-                       size_t* tokens_out, float* probs_out, size_t probs_len, const PenCall* pc, const EditCall* ec) {
-    ZG_REQUIRE(g && tokens && tokens_out, ZG_ERR_ARG, "gpt_sample: bad argument");
-    const size_t V = g->cfg.vocab_size, B = g->batch;
-    ZG_REQUIRE(!probs_out || probs_len >= B * V, ZG_ERR_SHAPE, "gpt_sample: probs_out needs %zu elements", B * V);
-    for (size_t b = 0; uniforms && b < B; ++b)  // (checked before anything is enqueued)
-        ZG_REQUIRE(uniforms[b] >= 0.0f && uniforms[b] < 1.0f, ZG_ERR_ARG, "gpt_sample: uniform %f outside [0,1)", uniforms[b]);
-    ZG_TRY(forward_enqueue(g, seq_len, tokens, n_tokens, 1, nullptr, 0));  // main.zig:199 (not drained: the sampler goes behind it)
-    hipStream_t s = gs(g);
-    if (pc) {  // the raw logits are penalised and the row-maximum partials rebuilt before either sampler looks at them
-        ZG_TRY(stage_penalties(g, *pc->pen, 0, pc->history, pc->stride, pc->lens, s));
-        ZG_TRY(launch_penalize(g->logits, (int)B, (int)V, g->pen, pen_history(g, false), g->part_val, g->part_idx, g->lm_grid, nullptr, s,
-                               !(ec && ec->stage_on)));  // (the edit launch below rebuilds the partials behind both stages)
-    }
-    if (ec && ec->stage_on) {  // the edits act on the row the penalties leave; the partials are rebuilt by the same launch
-        ZG_TRY(stage_edits(g, s));
-        ZG_TRY(launch_logit_edit(g->logits, (int)B, (int)V, g->edit_tab, g->edit_keep, g->part_val, g->part_idx, g->lm_grid, s));
-    }
-    // (pinned, 320 bytes into the control block: h_ints[0 .. B) is still being read by the forward's token upload)
-    float* h_u = reinterpret_cast<float*>(reinterpret_cast<char*>(g->h_ctrl) + 320);
-    for (size_t b = 0; b < B; ++b) {
-        if (uniforms) {
-            h_u[b] = uniforms[b];
-        } else {  // counter PRNG (splitmix64 finaliser, 24 random bits), same construction as the synthetic weights
-            uint64_t z = seed * 0x9E3779B97F4A7C15ULL + (uint64_t)seq_len * 0xD1B54A32D192ED03ULL + b + 1;
-            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-            z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-            z ^= z >> 31;
-            h_u[b] = (float)(uint32_t)(z >> 40) * 5.9604644775390625e-08f;
-        }
-    }
-    float* d_u = g->q;  // scratch: q is dead after the forward
-    ZG_HIP(hipMemcpyAsync(d_u, h_u, B * sizeof(float), hipMemcpyHostToDevice, s));
-    // (h_samp: nothing in flight reads it, forward_enqueue's callers drain)
-    const SamplerMode mode = fill_sample_params(g->h_samp, V, o, seed, ec ? ec->min_p : 0.0f);
-    if (threshold_sampler(mode)) {
-        ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
-        ZG_TRY(launch_sample_filtered(g->logits, (int)B, (int)V, g->samp, filter_launches(mode), d_u, nullptr, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->filt,
-                                      g->cur_token, probs_out != nullptr, s));
-    } else
-        ZG_TRY(launch_sample(g->logits, (int)B, (int)V, o.temp, d_u, g->part_val, g->lm_grid, g->lm_grid, g->samp_ws, g->cur_token, probs_out != nullptr,
-                             s));  // main.zig:200-206
-    ZG_HIP(hipMemcpyAsync(g->h_ints + B, g->cur_token, B * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (probs_out) ZG_TRY(copy_out_f32(probs_out, g->logits, B * V, s));
-    ZG_HIP(hipStreamSynchronize(s));
-    ZG_TRY(check_fault(g));
-    for (size_t b = 0; b < B; ++b) tokens_out[b] = (size_t)g->h_ints[B + b];
     return ZG_OK;
 }
 
@@ -2274,6 +2189,97 @@ static int check_sample_options(const zg_sample_options* o, const char* who) {
     return ZG_OK;
 }
 
+// GPT.sample (main.zig:198-207) behind one forward step: the checked body of the per-token family — zg_gpt_sample_edit's, under the
+// name of the entry point that calls it; each entry point keeps in front what it is stricter about.  penalties null: none, the
+// history is not read; an entry point without edits passes kNoEdits.  Everything the chain reads is staged first: the chain only launches.
+static const zg_logit_edits kNoEdits{};
+static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
+                       const size_t* history, size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits, const float* uniforms,
+                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len, const char* who) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, who));
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null handle", who);
+    if (pen) {
+        ZG_TRY(check_penalties(pen, who));
+        ZG_TRY(check_pen_handle(g, who));
+        ZG_TRY(check_history(g, history, history_stride, history_lens, 0, who));
+    }
+    bool edit_on = false;
+    ZG_TRY(build_edits(edits, g->cfg.vocab_size, who, g->edit_build.data(), &edit_on));
+    const bool pen_on = pen && !penalties_off(*pen);
+    if (pen_on || edit_on) ZG_HIP(hipStreamSynchronize(gs(g)));  // (an enqueued generation may still be reading the pinned mirrors; idle otherwise)
+    ZG_REQUIRE(tokens && tokens_out, ZG_ERR_ARG, "gpt_sample: bad argument");
+    const size_t V = g->cfg.vocab_size, B = g->batch;
+    ZG_REQUIRE(!probs_out || probs_len >= B * V, ZG_ERR_SHAPE, "gpt_sample: probs_out needs %zu elements", B * V);
+    for (size_t b = 0; uniforms && b < B; ++b)  // (checked before anything is enqueued)
+        ZG_REQUIRE(uniforms[b] >= 0.0f && uniforms[b] < 1.0f, ZG_ERR_ARG, "gpt_sample: uniform %f outside [0,1)", uniforms[b]);
+    ZG_TRY(forward_enqueue(g, seq_len, tokens, n_tokens, 1, nullptr, 0));  // main.zig:199 (not drained: the sampler goes behind it)
+    hipStream_t s = gs(g);
+    if (pen_on) ZG_TRY(stage_penalties(g, *pen, 0, history, history_stride, history_lens, s));
+    if (edit_on) ZG_TRY(stage_edits(g, s));
+    // (pinned, 320 bytes into the control block: h_ints[0 .. B) is still being read by the forward's token upload)
+    float* h_u = reinterpret_cast<float*>(reinterpret_cast<char*>(g->h_ctrl) + 320);
+    for (size_t b = 0; b < B; ++b) {
+        if (uniforms) {
+            h_u[b] = uniforms[b];
+        } else {  // counter PRNG (splitmix64 finaliser, 24 random bits), same construction as the synthetic weights
+            uint64_t z = seed * 0x9E3779B97F4A7C15ULL + (uint64_t)seq_len * 0xD1B54A32D192ED03ULL + b + 1;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+            z ^= z >> 31;
+            h_u[b] = (float)(uint32_t)(z >> 40) * 5.9604644775390625e-08f;
+        }
+    }
+    SamplerChain c = handle_chain(g, false);
+    float* d_u = g->q;  // scratch: q is dead after the forward
+    ZG_HIP(hipMemcpyAsync(d_u, h_u, B * sizeof(float), hipMemcpyHostToDevice, s));
+    // (h_samp: nothing in flight reads it, forward_enqueue's callers drain; the plain sampler takes its temperature by value)
+    const SamplerMode mode = fill_sample_params(g->h_samp, V, *opt, seed, edits->min_p);
+    if (threshold_sampler(mode)) ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
+    c.u = d_u, c.temp = opt->temp, c.write_probs = probs_out != nullptr, c.pick = g->cur_token;
+    ZG_TRY(emit_sampler_chain(c, StepTail{mode, pen_on, false, false, edit_on}, s));  // main.zig:200-206
+    ZG_HIP(hipMemcpyAsync(g->h_ints + B, g->cur_token, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (probs_out) ZG_TRY(copy_out_f32(probs_out, g->logits, B * V, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    for (size_t b = 0; b < B; ++b) tokens_out[b] = (size_t)g->h_ints[B + b];
+    return ZG_OK;
+}
+
+int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, const float* uniforms,
+                  uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "gpt_sample: bad argument");
+    const zg_sample_options plain{temp, 0, 1.0f};
+    return sample_impl(g, seq_len, tokens, n_tokens, &plain, nullptr, nullptr, 0, nullptr, &kNoEdits, uniforms, seed, tokens_out, probs_out, probs_len,
+                       "gpt_sample");
+}
+
+// zg_gpt_sample behind top-k / nucleus truncation (filters off: exactly zg_gpt_sample's launches)
+int zg_gpt_sample_ex(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const float* uniforms,
+                     uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
+    return sample_impl(g, seq_len, tokens, n_tokens, opt, nullptr, nullptr, 0, nullptr, &kNoEdits, uniforms, seed, tokens_out, probs_out, probs_len,
+                       "gpt_sample_ex");
+}
+
+// ... with the penalty stage in front, on the caller's history: here the penalties are required
+int zg_gpt_sample_pen(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
+                      const size_t* history, size_t history_stride, const size_t* history_lens, const float* uniforms, uint64_t seed, size_t* tokens_out,
+                      float* probs_out, size_t probs_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(pen != nullptr, ZG_ERR_ARG, "gpt_sample_pen: penalties is null");
+    return sample_impl(g, seq_len, tokens, n_tokens, opt, pen, history, history_stride, history_lens, &kNoEdits, uniforms, seed, tokens_out, probs_out,
+                       probs_len, "gpt_sample_pen");
+}
+
+// ... and with the edit stage behind the penalties and min-p in the sampler: here the edits are required
+int zg_gpt_sample_edit(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
+                       const size_t* history, size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits, const float* uniforms,
+                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
+    return sample_impl(g, seq_len, tokens, n_tokens, opt, pen, history, history_stride, history_lens, edits, uniforms, seed, tokens_out, probs_out,
+                       probs_len, "gpt_sample_edit");
+}
+
 // A generation in three parts, so that several handles' generations can be fed to their streams side by side
 // (zg_gpt_generate_enqueue_many): gen_begin — prompts, cache clearing, the whole-prompt pass, the prefetcher's start;
 // gen_pump — ONE graph launch (graph_steps decode steps) or one single step, false when nothing is left; gen_end — the
@@ -2286,7 +2292,7 @@ static int check_sample_options(const zg_sample_options* o, const char* who) {
 // steps are the ones an uninterrupted generation would run at these positions.  The caches keep rows 0 .. past - 1 and the
 // recorded tokens of positions below past stay where they are (zg_gpt_generate_fetch_range).
 
-// What a generation is asked for: the one argument of every zg_gpt_generate*_enqueue entry point to gen_begin
+// What a generation is asked for, checked: what generate_request makes of a zg_generate_request for gen_begin
 struct GenRequest {
     const size_t* prompts;  // [rows][stride], lens[rows] tokens each
     size_t stride;
@@ -2305,10 +2311,10 @@ struct GenRequest {
     // the log-probability stage behind every pick with top_n alternatives; lp_on false: the request is what it was
     bool lp_on = false;
     size_t top_n = 0;
-    // stop conditions, checked by the entry point (check_stop); stop_on false: the request is what it was
+    // stop conditions, checked (check_stop); stop_on false: the request is what it was
     bool stop_on = false;
     zg_stop_conditions stop{};
-    // logit edits, checked by the entry point, which has built the set in the ONE handle's edit_build: edit_on — the
+    // logit edits, checked, the set built in the ONE handle's edit_build: edit_on — the
     // edit stage runs; min_p — the sampler's threshold (0: off).  Both off: the request is what it was
     bool edit_on = false;
     float min_p = 0.0f;
@@ -2577,9 +2583,63 @@ static int gen_run(zg_gpt* const* handles, size_t n_handles, GenRequest req) {
     return first_err;
 }
 
-int zg_gpt_generate_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps) {
+// Everything of the generate family in one place: the one builder of a GenRequest, for every zg_gpt_generate*_enqueue entry point
+// under its own name.  Each stage is a node of graphs of their own, its values in device memory: the selection launches in front of
+// the sampler node (StepTail.sampler; filters off: the plain sampler's graphs), the penalty stage (StepTail.pen), the
+// log-probability stage behind the sampler node, or behind lm_head of a greedy step (StepTail.lp; it only reads, so
+// the tokens are those of the call without it), the stop stage last (StepTail.stop), the edit stage between the
+// penalties and the sampler (StepTail.edit; min-p is the sampler's: SampleParams.min_p_off, alone MINP_ONLY).  A
+// stage whose argument is null or all off leaves the request what it was without it.  Penalties, conditions and edits go to ONE
+// handle, the first (zg_gpt_generate_enqueue_many has none of them).
+static int generate_request(zg_gpt* const* handles, size_t n_handles, const zg_generate_request& q, const char* who) {
     ZG_TRY(require_init());
-    return gen_run(&g, 1, GenRequest(prompts, prompt_stride, prompt_lens, n_steps));
+    zg_gpt* const g = handles[0];
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null argument", who);
+    if (q.options) ZG_TRY(check_sample_options(q.options, who));
+    ZG_REQUIRE(q.options || !q.penalties, ZG_ERR_ARG, "%s: penalties without sampler options (greedy picking with penalties is top_k = 1)", who);
+    GenRequest r(q.prompts, q.prompt_stride, q.prompt_lens, q.n_steps, q.options, q.seed, q.past_len);
+    if (q.logprobs) {
+        r.lp_on = true;
+        r.top_n = q.top_n;
+    }
+    if (q.penalties) {
+        ZG_TRY(check_penalties(q.penalties, who));
+        if (!penalties_off(*q.penalties)) {
+            r.pen_on = true;
+            r.pen = *q.penalties;
+            r.prior = q.prior;
+            r.prior_stride = q.prior_stride;
+            r.prior_lens = q.prior_lens;
+        } else {  // all off: the request stays what it was without them, but the lists are still the caller's to get right
+            ZG_TRY(check_pen_handle(g, who));
+            ZG_TRY(check_history(g, q.prior, q.prior_stride, q.prior_lens, 0, who));
+        }
+    }
+    if (q.stop && (q.stop->n_ids || q.stop->n_seqs)) {
+        ZG_REQUIRE(g->batch <= (size_t)kStopMaxRows, ZG_ERR_UNSUPPORTED, "%s: batch %zu above %d", who, g->batch, kStopMaxRows);
+        ZG_TRY(check_stop(q.stop, g->cfg.vocab_size, who));
+        r.stop_on = true;
+        r.stop = *q.stop;
+    }
+    if (q.edits) {
+        ZG_TRY(build_edits(q.edits, g->cfg.vocab_size, who, g->edit_build.data(), &r.edit_on));
+        ZG_REQUIRE(q.options || edits_off(*q.edits), ZG_ERR_ARG, "%s: edits without sampler options (greedy picking with edits is top_k = 1)", who);
+        r.min_p = q.edits->min_p;
+    }
+    return gen_run(handles, n_handles, r);
+}
+
+// The positional arguments of the entry points as a request; what an entry point does not name is null / 0
+static zg_generate_request request_of(size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                      const zg_sample_options* opt = nullptr, uint64_t seed = 0, const zg_logit_penalties* pen = nullptr,
+                                      const size_t* prior = nullptr, size_t prior_stride = 0, const size_t* prior_lens = nullptr, int logprobs = 0,
+                                      size_t top_n = 0, const zg_stop_conditions* stop = nullptr) {
+    return zg_generate_request{sizeof(zg_generate_request), past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, pen, prior, prior_stride, prior_lens, seed,
+                               logprobs, top_n, stop, nullptr};  // (the fields in the header's order)
+}
+
+int zg_gpt_generate_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps) {
+    return generate_request(&g, 1, request_of(0, prompts, prompt_stride, prompt_lens, n_steps), "generate");
 }
 
 // generate (src/main.zig:322-342) AS THE REFERENCE RUNS IT: every token behind the prompt is drawn by GPT.sample
@@ -2593,7 +2653,7 @@ int zg_gpt_generate_sample_enqueue(zg_gpt* g, const size_t* prompts, size_t prom
     ZG_TRY(require_init());
     ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "generate_sample: temperature %f", temp);
     const zg_sample_options plain{temp, 0, 1.0f};
-    return gen_run(&g, 1, GenRequest(prompts, prompt_stride, prompt_lens, n_steps, &plain, seed));
+    return generate_request(&g, 1, request_of(0, prompts, prompt_stride, prompt_lens, n_steps, &plain, seed), "generate_sample");
 }
 
 int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps, float temp,
@@ -2603,14 +2663,12 @@ int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_strid
     return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
 }
 
-// The same behind top-k / nucleus truncation (include/zgpt2.h zg_sample_options; sample_filter.h): the selection launches sit in
-// front of the sampler node of graphs of their own (StepTail.sampler), the option values live in device memory.  Filters off: the
-// calls above.
+// The same behind top-k / nucleus truncation (include/zgpt2.h zg_sample_options; sample_filter.h); here the options are required
 int zg_gpt_generate_sample_ex_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
                                       const zg_sample_options* opt, uint64_t seed) {
     ZG_TRY(require_init());
-    ZG_TRY(check_sample_options(opt, "generate_sample_ex"));
-    return gen_run(&g, 1, GenRequest(prompts, prompt_stride, prompt_lens, n_steps, opt, seed));
+    ZG_REQUIRE(opt != nullptr, ZG_ERR_ARG, "generate_sample_ex: options is null");
+    return generate_request(&g, 1, request_of(0, prompts, prompt_stride, prompt_lens, n_steps, opt, seed), "generate_sample_ex");
 }
 
 int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
@@ -2624,101 +2682,37 @@ int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_st
 // through the whole-prompt pass first where the handle has one.  options null: greedy.
 int zg_gpt_generate_from_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
                                  const zg_sample_options* opt, uint64_t seed) {
-    ZG_TRY(require_init());
-    if (opt) ZG_TRY(check_sample_options(opt, "generate_from"));
-    return gen_run(&g, 1, GenRequest(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len));
+    return generate_request(&g, 1, request_of(past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, seed), "generate_from");
 }
 
-// The penalties of an entry point and the caller's prior into the request.  All penalties off: the request stays what it was
-// without them, but the lists are still the caller's to get right.
-static int request_penalties(const zg_gpt* g, GenRequest& r, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride, const size_t* prior_lens,
-                             const char* who) {
-    ZG_TRY(check_penalties(pen, who));
-    if (!penalties_off(*pen)) {
-        r.pen_on = true;
-        r.pen = *pen;
-        r.prior = prior;
-        r.prior_stride = prior_stride;
-        r.prior_lens = prior_lens;
-    } else if (g) {
-        ZG_TRY(check_pen_handle(g, who));
-        ZG_TRY(check_history(g, prior, prior_stride, prior_lens, 0, who));
-    }
-    return ZG_OK;
-}
-
-// zg_gpt_generate_from_enqueue with penalties: the penalty stage is a node of graphs of their own (StepTail.pen), its
-// values, past_len and the prior live in device memory.  All penalties off: zg_gpt_generate_from_enqueue itself.
+// zg_gpt_generate_from_enqueue with penalties; here options and penalties are required
 int zg_gpt_generate_pen_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
                                 const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
                                 const size_t* prior_lens, uint64_t seed) {
     ZG_TRY(require_init());
-    ZG_TRY(check_sample_options(opt, "generate_pen"));
-    GenRequest r(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len);
-    ZG_TRY(request_penalties(g, r, pen, prior, prior_stride, prior_lens, "generate_pen"));
-    return gen_run(&g, 1, r);
+    ZG_REQUIRE(opt != nullptr && pen != nullptr, ZG_ERR_ARG, "generate_pen: options or penalties is null");
+    return generate_request(&g, 1, request_of(past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, seed, pen, prior, prior_stride, prior_lens),
+                            "generate_pen");
 }
 
-// zg_gpt_generate_pen_enqueue / _from_enqueue with the log-probability stage: a node pair of graphs of their own
-// (StepTail.lp) behind the sampler node, or behind lm_head of a greedy step; top_n lives in device memory.  The stage only reads
-// what the step left, so the tokens are those of the call without it.
 int zg_gpt_generate_logprobs_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
                                      const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
                                      const size_t* prior_lens, uint64_t seed, size_t top_n) {
-    ZG_TRY(require_init());
-    if (opt) ZG_TRY(check_sample_options(opt, "generate_logprobs"));
-    ZG_REQUIRE(opt || !pen, ZG_ERR_ARG, "generate_logprobs: penalties without sampler options (greedy picking with penalties is top_k = 1)");
-    GenRequest r(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len);
-    r.lp_on = true;
-    r.top_n = top_n;
-    if (pen) ZG_TRY(request_penalties(g, r, pen, prior, prior_stride, prior_lens, "generate_logprobs"));
-    return gen_run(&g, 1, r);
-}
-
-// zg_gpt_generate_logprobs_enqueue / _pen_enqueue / _from_enqueue with the stop stage: one more node, last in the tail, of
-// graphs of their own (StepTail.stop); the conditions live in device memory.  No conditions: the request is one of theirs.
-// ... and with the edit stage: one more node between the penalties and the sampler, of graphs of their own
-// (StepTail.edit), the set in device memory; min-p is the sampler's (SampleParams.min_p_off; alone: StepTail.sampler MINP_ONLY).
-// Everything of the generate family in one place: zg_gpt_generate_stop_enqueue is this with edits null.
-static int generate_request(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
-                            const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
-                            const size_t* prior_lens, uint64_t seed, int logprobs, size_t top_n, const zg_stop_conditions* stop, const zg_logit_edits* edits,
-                            const char* who) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null argument", who);
-    if (opt) ZG_TRY(check_sample_options(opt, who));
-    ZG_REQUIRE(opt || !pen, ZG_ERR_ARG, "%s: penalties without sampler options (greedy picking with penalties is top_k = 1)", who);
-    GenRequest r(prompts, prompt_stride, prompt_lens, n_steps, opt, seed, past_len);
-    if (logprobs) {
-        r.lp_on = true;
-        r.top_n = top_n;
-    }
-    if (pen) ZG_TRY(request_penalties(g, r, pen, prior, prior_stride, prior_lens, who));
-    if (stop && (stop->n_ids || stop->n_seqs)) {
-        ZG_REQUIRE(g->batch <= (size_t)kStopMaxRows, ZG_ERR_UNSUPPORTED, "%s: batch %zu above %d", who, g->batch, kStopMaxRows);
-        ZG_TRY(check_stop(stop, g->cfg.vocab_size, who));
-        r.stop_on = true;
-        r.stop = *stop;
-    }
-    if (edits) {
-        ZG_TRY(build_edits(edits, g->cfg.vocab_size, who, g->edit_build.data(), &r.edit_on));
-        ZG_REQUIRE(opt || edits_off(*edits), ZG_ERR_ARG, "%s: edits without sampler options (greedy picking with edits is top_k = 1)", who);
-        r.min_p = edits->min_p;
-    }
-    return gen_run(&g, 1, r);
+    return generate_request(&g, 1, request_of(past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, seed, pen, prior, prior_stride, prior_lens, 1, top_n),
+                            "generate_logprobs");
 }
 
 int zg_gpt_generate_stop_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
                                  const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
                                  const size_t* prior_lens, uint64_t seed, int logprobs, size_t top_n, const zg_stop_conditions* stop) {
-    return generate_request(g, past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, pen, prior, prior_stride, prior_lens, seed, logprobs, top_n, stop,
-                            nullptr, "generate_stop");
+    return generate_request(
+        &g, 1, request_of(past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, seed, pen, prior, prior_stride, prior_lens, logprobs, top_n, stop),
+        "generate_stop");
 }
 
 int zg_gpt_generate_request_enqueue(zg_gpt* g, const zg_generate_request* r) {
     ZG_REQUIRE(r != nullptr && r->size == sizeof(zg_generate_request), ZG_ERR_ARG, "generate_request: null request, or its size field is not sizeof(zg_generate_request)");
-    return generate_request(g, r->past_len, r->prompts, r->prompt_stride, r->prompt_lens, r->n_steps, r->options, r->penalties, r->prior, r->prior_stride,
-                            r->prior_lens, r->seed, r->logprobs, r->top_n, r->stop, r->edits, "generate_request");
+    return generate_request(&g, 1, *r, "generate_request");
 }
 
 int zg_gpt_generate_stop_result(zg_gpt* g, size_t* end_out, size_t* finish_cols_out, int* reasons_out) {
@@ -2972,127 +2966,78 @@ int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_t
     return fetch_tokens(g, first, n, out_tokens);
 }
 
-// The truncated sampler on the caller's logits (tests): the kernels of zg_gpt_sample_ex, a small kernel standing in for lm_head's
-// argmax partials.  Allocates its workspace per call.
-int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const float* uniforms, size_t* tokens_out,
-                         float* probs_out, float* thresholds_out) {
-    ZG_TRY(require_init());
-    ZG_TRY(check_sample_options(opt, "debug_sample_rows"));
-    ZG_REQUIRE(logits && uniforms && tokens_out && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG,
-               "debug_sample_rows: bad argument");
-    const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
-    SampleParams hp{};
-    const int levels = filter_launches(fill_sample_params(&hp, vocab, *opt, 0));
-    hipStream_t s = ctx().stream;
-    DevScratch ds;
-    char* d_filt;
-    FilterWs fws;
-    float *d_logits, *d_seg, *d_part, *d_u;
-    SampleParams* d_par;
-    int* d_tok;
-    ZG_TRY(ds.carve([&] {
-        d_filt = ds.take<char>(filter_workspace_bytes(B));
-        fws = filter_workspace(d_filt, B);
-        d_logits = ds.take<float>(batch * vocab * 4);
-        d_seg = ds.take<float>(sample_workspace_floats(B) * 4);
-        d_part = ds.take<float>((size_t)B * n_part * 4);
-        d_par = ds.take<SampleParams>(sizeof(SampleParams));
-        d_u = ds.take<float>(batch * 4);
-        d_tok = ds.take<int>(batch * 4);
-    }));
-    std::vector<int> h_tok(batch);
-    std::vector<float> h_u(batch);
-    for (size_t b = 0; b < batch; ++b) {
-        float u;
-        ZG_HIP(hipMemcpy(&u, uniforms + b, 4, hipMemcpyDefault));
-        ZG_REQUIRE(u >= 0.0f && u < 1.0f, ZG_ERR_ARG, "debug_sample_rows: uniform %f outside [0,1)", u);
-        h_u[b] = u;
-    }
-    ZG_HIP(hipMemsetAsync(d_filt, 0, filter_workspace_bytes(B), s));  // (the selection chain starts from a zeroed workspace and leaves it so)
-    ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
-    ZG_HIP(hipMemcpyAsync(d_u, h_u.data(), batch * 4, hipMemcpyHostToDevice, s));
-    ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
-    ZG_TRY(launch_row_max_partials(d_logits, B, V, d_part, n_part, s));
-    if (levels)
-        ZG_TRY(launch_sample_filtered(d_logits, B, V, d_par, levels, d_u, nullptr, d_part, n_part, n_part, d_seg, fws, d_tok, probs_out != nullptr, s));
-    else  // filters off: the existing sampler
-        ZG_TRY(launch_sample(d_logits, B, V, opt->temp, d_u, d_part, n_part, n_part, d_seg, d_tok, probs_out != nullptr, s));
-    ZG_HIP(hipMemcpyAsync(h_tok.data(), d_tok, batch * 4, hipMemcpyDeviceToHost, s));
-    if (probs_out) ZG_HIP(hipMemcpyAsync(probs_out, d_logits, batch * vocab * 4, hipMemcpyDefault, s));
-    if (thresholds_out) {
-        if (levels) ZG_HIP(hipMemcpyAsync(thresholds_out, fws.tau, batch * 4, hipMemcpyDefault, s));
-        else {  // nothing dropped: -inf
-            std::vector<float> ninf(batch, -INFINITY);
-            ZG_HIP(hipMemcpy(thresholds_out, ninf.data(), batch * 4, hipMemcpyDefault));
-        }
-    }
-    ZG_HIP(hipStreamSynchronize(s));
-    for (size_t b = 0; b < batch; ++b) tokens_out[b] = (size_t)h_tok[b];
-    return ZG_OK;
-}
-
-// The edit stage and the sampler behind it on the caller's rows (tests).  Everything off: zg_debug_sample_rows' launches.  Allocates per call.
-int zg_debug_edit_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const zg_logit_edits* edits, const float* uniforms,
-                       float* edited_out, size_t* tokens_out, float* probs_out, float* thresholds_out) {
-    ZG_TRY(require_init());
-    const char* who = "debug_edit_rows";
+// The sampler chain on the caller's rows (tests), a small kernel standing in for lm_head's row-maximum partials: the body of
+// zg_debug_edit_rows, and with edits null — no edit stage, no min-p — of zg_debug_sample_rows.  Allocates its workspace per call.
+static int debug_sample_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const zg_logit_edits* edits, const float* uniforms,
+                             float* edited_out, size_t* tokens_out, float* probs_out, float* thresholds_out, const char* who) {
     ZG_TRY(check_sample_options(opt, who));
     ZG_REQUIRE(logits && uniforms && tokens_out && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG, "%s: bad argument", who);
-    std::vector<char> block(edit_block_bytes(vocab));
+    std::vector<char> block(edits ? edit_block_bytes(vocab) : 0);
     bool stage_on = false;
-    ZG_TRY(build_edits(edits, vocab, who, block.data(), &stage_on));
+    if (edits) ZG_TRY(build_edits(edits, vocab, who, block.data(), &stage_on));
     const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
     SampleParams hp{};
-    const SamplerMode mode = fill_sample_params(&hp, vocab, *opt, 0, edits->min_p);
+    const SamplerMode mode = fill_sample_params(&hp, vocab, *opt, 0, edits ? edits->min_p : 0.0f);
     hipStream_t s = ctx().stream;
     DevScratch ds;
     char *d_filt, *d_edit;
-    FilterWs fws;
-    float *d_logits, *d_seg, *d_part, *d_u;
     SampleParams* d_par;
-    int *d_tok, *d_pi;
+    float* d_u;
+    SamplerChain c{};
+    c.batch = B, c.vocab = V, c.n_part = n_part, c.temp = opt->temp, c.write_probs = probs_out != nullptr;
     ZG_TRY(ds.carve([&] {
         d_filt = ds.take<char>(filter_workspace_bytes(B));
-        fws = filter_workspace(d_filt, B);
-        d_logits = ds.take<float>(batch * vocab * 4);
-        d_seg = ds.take<float>(sample_workspace_floats(B) * 4);
-        d_part = ds.take<float>((size_t)B * n_part * 4);
-        d_pi = ds.take<int>((size_t)B * n_part * 4);
-        d_par = ds.take<SampleParams>(sizeof(SampleParams));
-        d_u = ds.take<float>(batch * 4);
-        d_tok = ds.take<int>(batch * 4);
+        c.filt = filter_workspace(d_filt, B);
+        c.logits = ds.take<float>(batch * vocab * 4);
+        c.seg_ws = ds.take<float>(sample_workspace_floats(B) * 4);
+        c.part_val = ds.take<float>((size_t)B * n_part * 4);
+        c.part_idx = ds.take<int>((size_t)B * n_part * 4);
+        c.params = d_par = ds.take<SampleParams>(sizeof(SampleParams));
+        c.u = d_u = ds.take<float>(batch * 4);
+        c.pick = ds.take<int>(batch * 4);
         d_edit = ds.take<char>(block.size());
     }));
+    c.edit_tab = reinterpret_cast<const EditTable*>(d_edit);
+    c.edit_keep = reinterpret_cast<const unsigned*>(d_edit + sizeof(EditTable));
     std::vector<int> h_tok(batch);
     std::vector<float> h_u(batch);
-    for (size_t b = 0; b < batch; ++b) {
+    for (size_t b = 0; b < batch; ++b) {  // (host or device memory)
         float u;
         ZG_HIP(hipMemcpy(&u, uniforms + b, 4, hipMemcpyDefault));
         ZG_REQUIRE(u >= 0.0f && u < 1.0f, ZG_ERR_ARG, "%s: uniform %f outside [0,1)", who, u);
         h_u[b] = u;
     }
-    ZG_HIP(hipMemsetAsync(d_filt, 0, filter_workspace_bytes(B), s));
-    ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemsetAsync(d_filt, 0, filter_workspace_bytes(B), s));  // (the selection chain starts from a zeroed workspace and leaves it so)
+    ZG_HIP(hipMemcpyAsync(c.logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
     ZG_HIP(hipMemcpyAsync(d_u, h_u.data(), batch * 4, hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
-    ZG_TRY(launch_row_max_partials(d_logits, B, V, d_part, n_part, s));  // (lm_head's stand-in: the partials of the row as the stage finds it)
-    if (stage_on) {
-        ZG_HIP(hipMemcpyAsync(d_edit, block.data(), block.size(), hipMemcpyHostToDevice, s));
-        ZG_TRY(launch_logit_edit(d_logits, B, V, reinterpret_cast<const EditTable*>(d_edit), reinterpret_cast<const unsigned*>(d_edit + sizeof(EditTable)), d_part,
-                                 d_pi, n_part, s));
-    }
-    if (edited_out) ZG_HIP(hipMemcpyAsync(edited_out, d_logits, batch * vocab * 4, hipMemcpyDefault, s));
-    if (threshold_sampler(mode))
-        ZG_TRY(launch_sample_filtered(d_logits, B, V, d_par, filter_launches(mode), d_u, nullptr, d_part, n_part, n_part, d_seg, fws, d_tok, probs_out != nullptr, s));
-    else
-        ZG_TRY(launch_sample(d_logits, B, V, opt->temp, d_u, d_part, n_part, n_part, d_seg, d_tok, probs_out != nullptr, s));
-    ZG_HIP(hipMemcpyAsync(h_tok.data(), d_tok, batch * 4, hipMemcpyDeviceToHost, s));
-    if (probs_out) ZG_HIP(hipMemcpyAsync(probs_out, d_logits, batch * vocab * 4, hipMemcpyDefault, s));
-    std::vector<float> ninf(batch, -INFINITY);
-    if (thresholds_out) ZG_HIP(hipMemcpyAsync(thresholds_out, threshold_sampler(mode) ? fws.tau : ninf.data(), batch * 4, hipMemcpyDefault, s));
+    ZG_TRY(launch_row_max_partials(c.logits, B, V, c.part_val, n_part, s));  // (lm_head's stand-in: the partials of the row as the chain finds it)
+    if (stage_on) ZG_HIP(hipMemcpyAsync(d_edit, block.data(), block.size(), hipMemcpyHostToDevice, s));
+    // the chain in two parts, the edited rows leaving between them: the row stage (no sampler), then the sampler alone
+    ZG_TRY(emit_sampler_chain(c, StepTail{GREEDY, false, false, false, stage_on}, s));
+    if (edited_out) ZG_HIP(hipMemcpyAsync(edited_out, c.logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_TRY(emit_sampler_chain(c, StepTail{mode}, s));
+    ZG_HIP(hipMemcpyAsync(h_tok.data(), c.pick, batch * 4, hipMemcpyDeviceToHost, s));
+    if (probs_out) ZG_HIP(hipMemcpyAsync(probs_out, c.logits, batch * vocab * 4, hipMemcpyDefault, s));
+    std::vector<float> ninf(batch, -INFINITY);  // nothing truncates: nothing is dropped
+    if (thresholds_out) ZG_HIP(hipMemcpyAsync(thresholds_out, threshold_sampler(mode) ? c.filt.tau : ninf.data(), batch * 4, hipMemcpyDefault, s));
     ZG_HIP(hipStreamSynchronize(s));
     for (size_t b = 0; b < batch; ++b) tokens_out[b] = (size_t)h_tok[b];
     return ZG_OK;
+}
+
+int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const float* uniforms, size_t* tokens_out,
+                         float* probs_out, float* thresholds_out) {
+    ZG_TRY(require_init());
+    return debug_sample_rows(logits, batch, vocab, opt, nullptr, uniforms, nullptr, tokens_out, probs_out, thresholds_out, "debug_sample_rows");
+}
+
+// ... with the edit stage in front of the sampler and min-p in it; here the edits are required.  Everything off: zg_debug_sample_rows.
+int zg_debug_edit_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const zg_logit_edits* edits, const float* uniforms,
+                       float* edited_out, size_t* tokens_out, float* probs_out, float* thresholds_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(edits != nullptr, ZG_ERR_ARG, "debug_edit_rows: edits is null");
+    return debug_sample_rows(logits, batch, vocab, opt, edits, uniforms, edited_out, tokens_out, probs_out, thresholds_out, "debug_edit_rows");
 }
 
 // The penalty kernels on the caller's rows (tests): the launches of the penalised step, in place on a copy.  Allocates per call.
@@ -3117,18 +3062,20 @@ int zg_debug_penalize_rows(const float* logits, size_t batch, size_t vocab, cons
     const size_t stride = std::max(longest, (size_t)1);
     hipStream_t s = ctx().stream;
     DevScratch ds;
-    float *d_logits, *d_pv;
+    float* d_logits;
     unsigned* d_counts;
-    int *d_hist, *d_pi, *d_len;
+    int *d_hist, *d_len;
     PenParams* d_par;
+    SamplerChain c{};  // the penalty stage alone, with the counts
+    c.batch = B, c.vocab = V, c.n_part = n_part;
     ZG_TRY(ds.carve([&] {
-        d_logits = ds.take<float>(batch * vocab * 4);
-        d_counts = ds.take<unsigned>(batch * vocab * 4);
+        c.logits = d_logits = ds.take<float>(batch * vocab * 4);
+        c.counts = d_counts = ds.take<unsigned>(batch * vocab * 4);
         d_hist = ds.take<int>(batch * stride * 4);
-        d_pv = ds.take<float>((size_t)B * n_part * 4);
-        d_pi = ds.take<int>((size_t)B * n_part * 4);
+        c.part_val = ds.take<float>((size_t)B * n_part * 4);
+        c.part_idx = ds.take<int>((size_t)B * n_part * 4);
         d_len = ds.take<int>(batch * 4);
-        d_par = ds.take<PenParams>(sizeof(PenParams));
+        c.pen = d_par = ds.take<PenParams>(sizeof(PenParams));
     }));
     std::vector<int> h_hist(batch * stride, 0), h_len(batch);
     for (size_t b = 0; b < batch; ++b) {
@@ -3141,12 +3088,11 @@ int zg_debug_penalize_rows(const float* logits, size_t batch, size_t vocab, cons
     ZG_HIP(hipMemcpyAsync(d_hist, h_hist.data(), batch * stride * 4, hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(d_len, h_len.data(), batch * 4, hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
-    PenHistory h{};
-    h.prior = d_hist;
-    h.prior_len = d_len;
-    h.prior_stride = (int)stride;
-    h.max_hist = (int)longest;
-    ZG_TRY(launch_penalize(d_logits, B, V, d_par, h, d_pv, d_pi, n_part, d_counts, s));
+    c.hist.prior = d_hist;
+    c.hist.prior_len = d_len;
+    c.hist.prior_stride = (int)stride;
+    c.hist.max_hist = (int)longest;
+    ZG_TRY(emit_sampler_chain(c, StepTail{GREEDY, true}, s));
     // all penalties off: the call is the identity on the rows (the counts are still the history's)
     ZG_HIP(hipMemcpyAsync(logits_out, penalties_off(*pen) ? logits : d_logits, batch * vocab * 4, hipMemcpyDefault, s));
     if (counts_out) ZG_HIP(hipMemcpyAsync(counts_out, d_counts, batch * vocab * 4, hipMemcpyDefault, s));
@@ -3169,7 +3115,7 @@ int zg_gpt_generate_enqueue_many(zg_gpt* const* handles, size_t n_handles, const
                        "generate_many: handles %zu and %zu share a stream (create them with own_stream)", j, i);
         }
     }
-    return gen_run(handles, n_handles, GenRequest(prompts, prompt_stride, prompt_lens, n_steps));
+    return generate_request(handles, n_handles, request_of(0, prompts, prompt_stride, prompt_lens, n_steps), "generate_many");
 }
 
 int zg_gpt_generate_fetch_many(zg_gpt* const* handles, size_t n_handles, size_t n_steps, size_t* out_tokens, size_t out_len) {
