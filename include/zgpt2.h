@@ -668,6 +668,12 @@ int zg_gpt_generate_stop_result(zg_gpt* g, size_t* end_out, size_t* finish_cols_
  * the conditions (a token of 2^31 - 1 or above standing for the vocabulary).  Needs zg_init only.  Allocates per call. */
 int zg_debug_stop_rows(const size_t* tokens, size_t batch, size_t stride, const size_t* first_cols, size_t n_cols,
                        const zg_stop_conditions* stop, size_t* finish_cols_out, int* reasons_out, size_t* done_col_out);
+/* Test entry: the greedy pick alone.  The caller's host partials part_val / part_idx [batch][n_part] — (maximum, index) pairs as
+ * lm_head's argmax epilogue leaves them — go to the device and the decode step's head kernel picks from them in the form
+ * zg_gpt_argmax launches: the first pair in the order "greater value first, lower index on ties", starting from (-3.0e38, 2^31 - 1);
+ * picks_out [batch] receives its index, or 0 when that is not in [0, vocab).  batch 1 .. 8, n_part 1 .. 4096, vocab 1 .. 2^31 - 1,
+ * anything else: ZG_ERR_ARG.  Needs zg_init only.  Allocates per call. */
+int zg_debug_pick_rows(const float* part_val, const int32_t* part_idx, size_t batch, size_t n_part, size_t vocab, size_t* picks_out);
 /* ---- Edits of the logit row by token id, and min-p: OpenAI / vLLM logit_bias, vLLM allowed_token_ids (HF
  * prefix_allowed_tokens_fn in its static form), vLLM bad_words / HF bad_words_ids for single tokens, and min_p (vLLM, HF, llama.cpp).
  * The same set for every row of a call, like zg_sample_options and zg_logit_penalties.

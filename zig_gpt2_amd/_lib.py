@@ -162,6 +162,7 @@ SIGNATURES = {
     "zg_gpt_generate_stop_enqueue": (C.c_int, [vp, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp, C.c_uint64, C.c_int, sz, vp]),
     "zg_gpt_generate_stop_result": (C.c_int, [vp, szp, vp, vp]),
     "zg_debug_stop_rows": (C.c_int, [vp, sz, sz, vp, sz, vp, vp, vp, szp]),
+    "zg_debug_pick_rows": (C.c_int, [vp, vp, sz, sz, sz, vp]),
     "zg_gpt_sample_edit": (C.c_int, [vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, C.c_uint64, vp, vp, sz]),
     "zg_gpt_generate_request_enqueue": (C.c_int, [vp, vp]),
     "zg_debug_edit_rows": (C.c_int, [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]),

@@ -2219,17 +2219,8 @@ static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n
     if (edit_on) ZG_TRY(stage_edits(g, s));
     // (pinned, 320 bytes into the control block: h_ints[0 .. B) is still being read by the forward's token upload)
     float* h_u = reinterpret_cast<float*>(reinterpret_cast<char*>(g->h_ctrl) + 320);
-    for (size_t b = 0; b < B; ++b) {
-        if (uniforms) {
-            h_u[b] = uniforms[b];
-        } else {  // counter PRNG (splitmix64 finaliser, 24 random bits), same construction as the synthetic weights
-            uint64_t z = seed * 0x9E3779B97F4A7C15ULL + (uint64_t)seq_len * 0xD1B54A32D192ED03ULL + b + 1;
-            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-            z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-            z ^= z >> 31;
-            h_u[b] = (float)(uint32_t)(z >> 40) * 5.9604644775390625e-08f;
-        }
-    }
+    // (no uniforms: the counter PRNG the device loop's sampler draws from, zg_common.h)
+    for (size_t b = 0; b < B; ++b) h_u[b] = uniforms ? uniforms[b] : counter_uniform(seed, seq_len, b);
     SamplerChain c = handle_chain(g, false);
     float* d_u = g->q;  // scratch: q is dead after the forward
     ZG_HIP(hipMemcpyAsync(d_u, h_u, B * sizeof(float), hipMemcpyHostToDevice, s));
@@ -2798,6 +2789,47 @@ int zg_debug_stop_rows(const size_t* tokens, size_t batch, size_t stride, const 
         reasons_out[b] = fin[b] < 0 ? -1 : reason[b];
     }
     *done_col_out = host.p->done_col;
+    return ZG_OK;
+}
+
+// The greedy pick alone on the caller's partials (tests): the product's embed_step_kernel as zg_gpt_argmax launches it, on a scratch
+// control block (step 0, generate mode).  Allocates per call.
+int zg_debug_pick_rows(const float* part_val, const int32_t* part_idx, size_t batch, size_t n_part, size_t vocab, size_t* picks_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(part_val && part_idx && picks_out && batch >= 1 && batch <= 8 && n_part >= 1 && n_part <= 4096 && vocab >= 1 && vocab <= (size_t)0x7fffffff,
+               ZG_ERR_ARG, "debug_pick_rows: bad argument");
+    hipStream_t s = ctx().stream;
+    DevScratch ds;
+    float* d_val;
+    int *d_idx, *d_zero, *d_pick;
+    StepCtrl* d_ctrl;
+    ZG_TRY(ds.carve([&] {
+        d_val = ds.take<float>(batch * n_part * 4);
+        d_idx = ds.take<int>(batch * n_part * 4);
+        d_ctrl = ds.take<StepCtrl>(sizeof(StepCtrl));
+        d_zero = ds.take<int>(batch * 4);  // what the kernel reads beside the partials and does not use in this form
+        d_pick = ds.take<int>(batch * 4);
+    }));
+    ZG_HIP(hipMemcpyAsync(d_val, part_val, batch * n_part * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemcpyAsync(d_idx, part_idx, batch * n_part * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemsetAsync(d_ctrl, 0, sizeof(StepCtrl), s));
+    ZG_HIP(hipMemsetAsync(d_zero, 0, batch * 4, s));
+    EmbedArgs e{};
+    e.ctrl = d_ctrl;
+    e.part_val = d_val;
+    e.part_idx = d_idx;
+    e.part_stride = e.n_partials = (int)n_part;
+    e.prompt = e.forced = e.sampled = d_zero;  // one token per row, no prompt lengths
+    e.prompt_stride = 1;
+    e.batch = (int)batch;
+    e.vocab = (int)vocab;
+    e.cur_token = d_pick;
+    e.finish_only = 2;
+    ZG_TRY(launch_embed_step(e, s));
+    int h_pick[8];
+    ZG_HIP(hipMemcpyAsync(h_pick, d_pick, batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    for (size_t b = 0; b < batch; ++b) picks_out[b] = (size_t)h_pick[b];
     return ZG_OK;
 }
 

@@ -171,6 +171,8 @@ __device__ __forceinline__ float dot8(const W8& w, const W8& x, float acc) {
     return acc;
 }
 
+// The order of the argmax partials, in the form the lm_head epilogues were compiled with (zg_common.h pick_before is its one
+// definition for every reader of the partials; expressed through it, these kernels' register allocation changes)
 struct Best {
     float val;
     int idx;

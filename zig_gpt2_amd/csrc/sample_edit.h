@@ -1,5 +1,5 @@
 // sample_edit.h — logit bias and token allow / ban lists on the logit row, between the penalty stage and the sampler: the kernel
-// (included by elementwise.hip behind sample_penalty.h, inside its unnamed namespace).  include/zgpt2.h zg_logit_edits is the contract.
+// (included by sample.hip behind sample_penalty.h, inside its unnamed namespace).  include/zgpt2.h zg_logit_edits is the contract.
 //
 // For one row x[0..V): keep[i] = bit i of the keep set the host built from the two lists (bit set: allowed and not banned);
 // y[i] = keep[i] ? (i biased ? x[i] + v : x[i]) : -inf.  The sum is one rounded fp32 add; a kept, unbiased index is not written.
@@ -18,10 +18,9 @@ __global__ __launch_bounds__(256) void logit_edit_kernel(float* __restrict__ log
                                                          const unsigned* __restrict__ keep, float* __restrict__ part_val, int* __restrict__ part_idx) {
     __shared__ float s_red[4];
     __shared__ int s_idx;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+    const int tid = threadIdx.x, b = blockIdx.y;
     const int stride = gridDim.x * 256;
     float* x = logits + (size_t)b * vocab;
-    if (tid == 0) s_idx = 0x7fffffff;
     const int n_bias = min(max(tab->n_bias, 0), kEditMaxBias);
     for (int p = tid; p < n_bias; p += 256) {
         const unsigned id = (unsigned)tab->ids[p];
@@ -36,20 +35,7 @@ __global__ __launch_bounds__(256) void logit_edit_kernel(float* __restrict__ log
         if ((keep[i >> 5] >> (i & 31)) & 1u) m = fmaxf(m, x[i]);
         else x[i] = -INFINITY;
     }
-    m = wave_allmax(m);
-    if (lane == 0) s_red[wave] = m;
-    __syncthreads();
-    const float mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-    int first = 0x7fffffff;
-    for (int i = blockIdx.x * 256 + tid; i < vocab; i += stride)
-        if (x[i] == mx) {  // (a dropped index holds -inf, which this thread wrote itself; mx is never below the start value)
-            first = i;
-            break;
-        }
-    if (first != 0x7fffffff) atomicMin(&s_idx, first);
-    __syncthreads();
-    if (tid == 0) {
-        part_val[(size_t)b * gridDim.x + blockIdx.x] = mx;
-        part_idx[(size_t)b * gridDim.x + blockIdx.x] = s_idx;
-    }
+    // (the index search reads the slice again: a dropped index holds -inf, which this thread wrote itself; the slice maximum is
+    // never below the start value)
+    slice_partial_store(x, vocab, m, s_red, &s_idx, part_val, part_idx);
 }

@@ -1,5 +1,5 @@
-// sample_filter.h — top-k / nucleus (top-p) truncation in front of the sampler: the kernels (included by elementwise.hip
-// beside sample_seg / sample_pick / sample_probs, inside its unnamed namespace).
+// sample_filter.h — top-k / nucleus (top-p) truncation in front of the sampler: the kernels (included by sample.hip
+// behind sample_seg / sample_pick / sample_probs, inside its unnamed namespace).
 //
 // For one row x[0..V): tau_k = the k-th largest value (duplicates counted), K = { x >= tau_k }; e = exp(x / temp - max / temp) over
 // K, tau_p = the largest value v of K with sum{ e : x >= v } >= top_p * sum{ e : K }; kept = { x >= max(tau_k, tau_p) } — ties at
@@ -164,16 +164,6 @@ __device__ __forceinline__ unsigned long long filter_mass(float x, float inv_tem
     return (unsigned long long)(e * kFiltScale);
 }
 
-__device__ __forceinline__ float filter_row_max(const float* __restrict__ part_val, int n_part, float* s_red) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float mxr = -3.0e38f;
-    for (int p = tid; p < n_part; p += 256) mxr = fmaxf(mxr, part_val[p]);
-    mxr = wave_allmax(mxr);
-    if (lane == 0) s_red[wave] = mxr;
-    __syncthreads();
-    return fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-}
-
 __device__ __forceinline__ void filter_zero(const FilterRow& r, int which) {
     for (int bin = blockIdx.x * 256 + threadIdx.x; bin < kFiltBins; bin += gridDim.x * 256) {
         r.cnt[which * kFiltBins + bin] = 0u;
@@ -216,7 +206,7 @@ __global__ __launch_bounds__(256) void filter_level_kernel(const float* __restri
         s_cnt[i] = 0u;
         s_mass[i] = 0ull;
     }
-    const float mx = filter_row_max(part_val + (size_t)b * part_stride, n_part, s_red);  // (its barrier also covers the zeroing above)
+    const float mx = row_max_from_partials(part_val + (size_t)b * part_stride, n_part, s_red);  // (its barrier also covers the zeroing above)
     const float* x = logits + (size_t)b * vocab;
     const int msh = lv == 1 ? 21 : 10;  // the prefix bits a key must match at levels 1 and 2
     for (int i = blockIdx.x * 256 + tid; i < vocab; i += gridDim.x * 256) {
@@ -259,7 +249,7 @@ __global__ __launch_bounds__(256) void sample_seg_filt_kernel(const float* __res
     }
     const float* x = logits + (size_t)b * vocab;
     float* so = seg_out + (size_t)b * (kSegMax + 2);
-    const float mx = filter_row_max(part_val + (size_t)b * part_stride, n_part, s_red);  // [kSegMax] holds the row maximum itself here
+    const float mx = row_max_from_partials(part_val + (size_t)b * part_stride, n_part, s_red);  // [kSegMax] holds the row maximum itself here
     // min-p (applied last, as HF does): tau_m = max + temp x log(min_p), one fp32 add; off (-inf): tau keeps its own bits, a NaN's too
     const float d = params->min_p_off;
     if (d > -INFINITY) tau = fmaxf(tau, mx + d);
@@ -291,12 +281,6 @@ __global__ __launch_bounds__(256) void sample_probs_filt_kernel(float* logits, i
 // the row maxima by slice, as lm_head's argmax epilogue leaves them (zg_debug_sample_rows: logits without an lm_head)
 __global__ __launch_bounds__(256) void row_max_partials_kernel(const float* __restrict__ logits, int vocab, float* __restrict__ part_val) {
     __shared__ float s_red[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
-    const float* x = logits + (size_t)b * vocab;
-    float m = -3.0e38f;
-    for (int i = blockIdx.x * 256 + tid; i < vocab; i += gridDim.x * 256) m = fmaxf(m, x[i]);
-    m = wave_allmax(m);
-    if (lane == 0) s_red[wave] = m;
-    __syncthreads();
-    if (tid == 0) part_val[(size_t)b * gridDim.x + blockIdx.x] = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    const float* x = logits + (size_t)blockIdx.y * vocab;
+    slice_partial_store(x, vocab, slice_thread_max(x, vocab), s_red, nullptr, part_val, nullptr);  // (the index is not wanted)
 }

@@ -1,5 +1,5 @@
 // sample_logprob.h — the log-probability of the token a decode step picks and the top-N alternatives of its row, as one more
-// optional stage behind the sampler: the kernels (included by elementwise.hip behind sample_penalty.h, inside its unnamed
+// optional stage behind the sampler: the kernels (included by sample.hip behind sample_edit.h, inside its unnamed
 // namespace).  include/zgpt2.h zg_gpt_generate_logprobs_enqueue is the contract.
 //
 // For one row x[0..V) as the sampler stage receives it (raw, or as the penalties leave it; temperature 1, nothing truncated),
@@ -24,30 +24,11 @@ constexpr int kLpMaxChunks = 256;   // vocab <= 262144, as the samplers
 constexpr int kLpTopMax = 20;       // ZG_LOGPROBS_TOP_MAX: the candidate lists and the record buffers have this many slots
 constexpr int kLpNone = 0x7fffffff; // the index of "nothing left": loses every tie, also against a real -inf
 
-__device__ __forceinline__ bool lp_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
-
-// (value, index) first in the order above over a workgroup of four waves; every lane receives it.  DPP row rotations inside the
-// 16-lane rows, the four row winners through v_readlane (embed_step_kernel's argmax), the four waves through the LDS.
+// (value, index) first under pick_before over a workgroup of four waves; every lane receives it: wave_first, then the four waves
+// through the LDS.
 __device__ __forceinline__ void lp_block_first(float& bv, int& bi, float* s_v, int* s_i) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#define ZG_LP_STEP(N)                                                                                                   \
-    {                                                                                                                   \
-        const float ov = dpp_row_ror<N>(bv);                                                                            \
-        const int oi = __builtin_amdgcn_update_dpp(0, bi, 0x120 | N, 0xF, 0xF, true);                                   \
-        if (lp_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }                                                            \
-    }
-    ZG_LP_STEP(8) ZG_LP_STEP(4) ZG_LP_STEP(2) ZG_LP_STEP(1)
-#undef ZG_LP_STEP
-    {
-        const float rv = bv;
-        const int ri = bi;
-#pragma unroll
-        for (int r = 0; r < 64; r += 16) {
-            const float ov = lane_value(rv, r);
-            const int oi = __builtin_amdgcn_readlane(ri, r);
-            if (lp_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-    }
+    wave_first(bv, bi);
     __syncthreads();  // (the previous round's readers are done)
     if (lane == 0) {
         s_v[wave] = bv;
@@ -58,17 +39,7 @@ __device__ __forceinline__ void lp_block_first(float& bv, int& bi, float* s_v, i
     bi = s_i[0];
 #pragma unroll
     for (int w = 1; w < 4; ++w)
-        if (lp_before(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; }
-}
-
-// the row maximum from the per-workgroup maxima lm_head's argmax epilogue (or the penalty stage behind it) left
-__device__ __forceinline__ float lp_row_max(const float* __restrict__ part_val, int n_part, float* s_mx) {
-    float mxr = -3.0e38f;
-    for (int p = threadIdx.x; p < n_part; p += 256) mxr = fmaxf(mxr, part_val[p]);
-    mxr = wave_allmax(mxr);
-    if ((threadIdx.x & 63) == 0) s_mx[threadIdx.x >> 6] = mxr;
-    __syncthreads();
-    return fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
+        if (pick_before(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; }
 }
 
 __device__ __forceinline__ int lp_top_n(const int* top_n) { return min(max(*top_n, 0), kLpTopMax); }
@@ -108,7 +79,7 @@ __device__ __forceinline__ void lp_chunk_rounds(const float (&v)[4], unsigned ta
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int i = c * kLpChunk + j * 256 + tid;
-            if (!((taken >> j) & 1u) && lp_before(v[j], i, bv, bi)) { bv = v[j]; bi = i; }
+            if (!((taken >> j) & 1u) && pick_before(v[j], i, bv, bi)) { bv = v[j]; bi = i; }
         }
         lp_block_first(bv, bi, s_v, s_i);
         if (tid == 0) {
@@ -150,7 +121,7 @@ __device__ __forceinline__ void lp_lists_merge_store(int n_chunks, int top_n, in
         int bi = hi;
         lp_block_first(bv, bi, s_v, s_i);
         if (tid == 0) {  // (kept in the LDS until the rounds are over, as in the part kernels)
-            s_oi[r] = (unsigned)bi < (unsigned)vocab ? bi : 0;
+            s_oi[r] = clamp_token(bi, vocab);
             s_ov[r] = (bv - m) - log_s;
         }
         if (mine && bi != kLpNone && hi == bi) {  // the winner's list moves on
@@ -173,7 +144,7 @@ __global__ __launch_bounds__(256) void logprob_part_kernel(const float* __restri
     __shared__ int s_i[4], s_oi[kLpTopMax];
     const int c = blockIdx.x, b = blockIdx.y;
     const int top_n = lp_top_n(top_n_ptr);
-    const float m = lp_row_max(part_val + (size_t)b * part_stride, n_part, s_mx);
+    const float m = row_max_from_partials(part_val + (size_t)b * part_stride, n_part, s_mx);
     float v[4];
     const unsigned taken = lp_chunk_load(logits + (size_t)b * vocab, vocab, c, v);
     const size_t slot = (size_t)b * n_chunks + c;
@@ -202,21 +173,12 @@ __global__ __launch_bounds__(256) void logprob_finish_kernel(const float* __rest
         return;
     }
     const float* x = logits + (size_t)b * vocab;
-    const float m = lp_row_max(part_val + (size_t)b * part_stride, n_part, s_mx);
-    int tok;
-    if (tokens) tok = tokens[b];
-    else {  // greedy: the lowest-index argmax of the partials, as embed_step_kernel takes it one step later
-        float bv = -3.0e38f;
-        int bi = kLpNone;
-        for (int p = tid; p < n_part; p += 256) {
-            const float pv = part_val[(size_t)b * part_stride + p];
-            const int pi = part_idx[(size_t)b * part_stride + p];
-            if (lp_before(pv, pi, bv, bi)) { bv = pv; bi = pi; }
-        }
-        lp_block_first(bv, bi, s_v, s_i);
-        tok = bi;
-    }
-    tok = (unsigned)tok < (unsigned)vocab ? tok : 0;  // (embed_step_kernel's clamp)
+    const float m = row_max_from_partials(part_val + (size_t)b * part_stride, n_part, s_mx);
+    // the token the step records — thread 0 alone follows it, so wave 0 alone finds it.  Greedy: partials_first, the very pick
+    // embed_step_kernel makes of these partials one step later
+    int tok = 0;
+    if (tid < 64)
+        tok = clamp_token(tokens ? tokens[b] : partials_first(part_val + (size_t)b * part_stride, part_idx + (size_t)b * part_stride, n_part), vocab);
     lp_lists_load(ws, (size_t)b, n_chunks, top_n, s_sum, s_cv, s_ci);
     __syncthreads();
     float log_s = 0.0f, lp_tok = 0.0f;

@@ -1,5 +1,5 @@
 // sample_penalty.h — repetition / presence / frequency penalties on the raw logits, in front of the sampler: the kernels (included
-// by elementwise.hip behind sample_filter.h, inside its unnamed namespace).  include/zgpt2.h zg_logit_penalties is the contract.
+// by sample.hip behind sample_filter.h, inside its unnamed namespace).  include/zgpt2.h zg_logit_penalties is the contract.
 //
 // For one row x[0..V) and its history (token ids, any order, duplicates allowed): c[i] = occurrences of i in the history;
 // c == 0 leaves x[i] alone, c >= 1 gives ((x > 0 ? x / r : x * r) - (presence + frequency * c)), every operation rounded on its
@@ -68,31 +68,11 @@ __global__ __launch_bounds__(256) void penalty_apply_kernel(float* __restrict__ 
     }
 }
 
-// row_max_partials_kernel with the index beside the maximum (the lowest one on ties; a slice that holds nothing comparable: the
-// start value and an index the readers clamp)
+// row_max_partials_kernel with the index beside the maximum (sample_common.h slice_partial_store: the lowest one on ties)
 __global__ __launch_bounds__(256) void row_argmax_partials_kernel(const float* __restrict__ logits, int vocab, float* __restrict__ part_val,
                                                                   int* __restrict__ part_idx) {
     __shared__ float s_red[4];
     __shared__ int s_idx;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
-    const float* x = logits + (size_t)b * vocab;
-    if (tid == 0) s_idx = 0x7fffffff;
-    float m = -3.0e38f;
-    for (int i = blockIdx.x * 256 + tid; i < vocab; i += gridDim.x * 256) m = fmaxf(m, x[i]);
-    m = wave_allmax(m);
-    if (lane == 0) s_red[wave] = m;
-    __syncthreads();
-    const float mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-    int first = 0x7fffffff;
-    for (int i = blockIdx.x * 256 + tid; i < vocab; i += gridDim.x * 256)
-        if (x[i] == mx) {
-            first = i;
-            break;
-        }
-    if (first != 0x7fffffff) atomicMin(&s_idx, first);
-    __syncthreads();
-    if (tid == 0) {
-        part_val[(size_t)b * gridDim.x + blockIdx.x] = mx;
-        part_idx[(size_t)b * gridDim.x + blockIdx.x] = s_idx;
-    }
+    const float* x = logits + (size_t)blockIdx.y * vocab;
+    slice_partial_store(x, vocab, slice_thread_max(x, vocab), s_red, &s_idx, part_val, part_idx);
 }

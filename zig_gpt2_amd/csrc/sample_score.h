@@ -1,12 +1,12 @@
 // sample_score.h — the log-probability of a GIVEN token at every position of a whole-prompt pass and the top-N alternatives there
 // (zg_gpt_score): the statistics kernels over a block of logits rows [rows][row_stride] the lm_head GEMM just wrote
-// (included by elementwise.hip behind sample_logprob.h, whose order, rounds and record buffers they share).  include/zgpt2.h
+// (included by sample.hip behind sample_logprob.h, whose order, rounds and record buffers they share).  include/zgpt2.h
 // zg_gpt_score is the contract; the definitions of logprob, top_ids and top_logprobs are §3.7's to the letter.
 //
 // No lm_head partials exist behind a GEMM, and a pass for the row maximum would read the block twice, so the maximum comes from
 // the chunks themselves (an online softmax over chunks):
 //   score_part_kernel     grid (chunks, rows): a workgroup owns kLpChunk consecutive columns of one row, four per lane, read once
-//                         (lp_chunk_load).  Its own maximum m_c (never below -3e38, as lp_row_max), the sum of expf(x - m_c)
+//                         (lp_chunk_load).  Its own maximum m_c (never below -3e38, as row_max_from_partials), the sum of expf(x - m_c)
 //                         (lp_chunk_sum), its best min(top_n, chunk) candidates (lp_chunk_rounds).  Only columns
 //                         < vocab are read: the pad columns of the GEMM's 64-column grid never are.
 //   score_finish_kernel   one workgroup per row: m = max m_c; S = sum over c in index order of s_c * expf(m_c - m), by one lane,
@@ -28,10 +28,7 @@ __global__ __launch_bounds__(256) void score_part_kernel(const float* __restrict
     float mx = -3.0e38f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) mx = fmaxf(mx, v[j]);
-    mx = wave_allmax(mx);
-    if ((tid & 63) == 0) s_mx[tid >> 6] = mx;
-    __syncthreads();
-    const float m_c = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
+    const float m_c = block4_allmax(mx, s_mx);
     const size_t slot = (size_t)r * n_chunks + c;
     const float chunk_sum = lp_chunk_sum(v, taken, m_c, s_sum);
     lp_chunk_rounds(v, taken, c, top_n, s_v, s_i, s_ov, s_oi, ws.lp.val + slot * kLpTopMax, ws.lp.idx + slot * kLpTopMax);
@@ -56,15 +53,12 @@ __global__ __launch_bounds__(256) void score_finish_kernel(const float* __restri
     const int pos = max(tg.past + t + 1, 0);
     const size_t out = (size_t)b * rec.stride + min(pos, rec.stride - 1);
     int tok = tg.tokens[(size_t)b * tg.token_stride + min(pos, tg.token_stride - 1)];
-    tok = (unsigned)tok < (unsigned)vocab ? tok : 0;
+    tok = clamp_token(tok, vocab);
     const float* x = logits + (size_t)r * row_stride;
     lp_lists_load(ws.lp, (size_t)r, n_chunks, top_n, s_sum, s_cv, s_ci);
     if (tid < n_chunks) s_max[tid] = ws.max[(size_t)r * n_chunks + tid];
     __syncthreads();
-    float m = wave_allmax(tid < n_chunks ? s_max[tid] : -3.0e38f);
-    if ((tid & 63) == 0) s_mx[tid >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
+    const float m = block4_allmax(tid < n_chunks ? s_max[tid] : -3.0e38f, s_mx);
     float log_s = 0.0f, lp_tok = 0.0f;
     if (tid == 0) {  // the chunk sums brought to the row maximum, in index order
         float total = 0.0f;
@@ -73,22 +67,4 @@ __global__ __launch_bounds__(256) void score_finish_kernel(const float* __restri
         lp_tok = (x[tok] - m) - log_s;
     }
     lp_lists_merge_store(n_chunks, top_n, vocab, m, log_s, lp_tok, s_cv, s_ci, s_v, s_i, s_ov, s_oi, rec, out);
-}
-
-// The B operand of the scoring lm_head on fp32 / B24 handles: the stored values of wte [V][K] split exactly into bf16 planes,
-// plane-major [3][V64][K] as the whole-prompt GEMMs read weight planes, rows V .. V64 - 1 zero.
-__global__ __launch_bounds__(256) void wte_planes_kernel(const void* __restrict__ wte, int weight_type, size_t V, size_t V64, int K, bf16_t* __restrict__ out) {
-    const size_t per_row = (size_t)(K / 4), n = V64 * per_row, plane = V64 * (size_t)K;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = i / per_row, k = (i % per_row) * 4;
-        f32x4 v{0.0f, 0.0f, 0.0f, 0.0f};
-        if (r < V) v = weight_type == WT_B24 ? load_b24x4(wte, r, K, (int)k) : *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(wte) + r * K + k);
-        uint32_t h0, m0, l0, h1, m1, l1;
-        split3_pk(v.x, v.y, h0, m0, l0);
-        split3_pk(v.z, v.w, h1, m1, l1);
-        bf16_t* o = out + r * K + k;
-        *reinterpret_cast<u32x2*>(o) = u32x2{h0, h1};
-        *reinterpret_cast<u32x2*>(o + plane) = u32x2{m0, m1};
-        *reinterpret_cast<u32x2*>(o + 2 * plane) = u32x2{l0, l1};
-    }
 }

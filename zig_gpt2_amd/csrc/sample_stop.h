@@ -1,5 +1,5 @@
 // sample_stop.h — stop tokens and stop sequences of the device loop, as the last optional stage of a decode step: the kernel
-// (included by elementwise.hip behind sample_score.h, inside its unnamed namespace).  include/zgpt2.h zg_stop_conditions is the
+// (included by sample.hip behind sample_score.h, inside its unnamed namespace).  include/zgpt2.h zg_stop_conditions is the
 // contract.
 //
 // One launch per step, one workgroup, one wave per row.  The step in flight records column col = ctrl->seq_len - 1; row b picked a
@@ -14,8 +14,6 @@
 // still 0 knows that the step of column f had not announced itself when progress was read.  Nothing here waits for the host.
 // Every length read from device memory is clamped to its array; tokens are compared, never followed.
 
-__device__ __forceinline__ bool stop_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
-
 __global__ __launch_bounds__(512) void stop_step_kernel(const StopArgs a) {
     __shared__ int s_fin[kStopMaxRows];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -29,33 +27,9 @@ __global__ __launch_bounds__(512) void stop_step_kernel(const StopArgs a) {
             int tok;
             if (a.picks) tok = a.picks[b];
             else if (a.pick_from_record) tok = a.tokens[(size_t)b * a.stride + col];
-            else {  // greedy: the argmax of the partials as embed_step_kernel takes it one step later
-                float bv = -3.0e38f;
-                int bi = 0x7fffffff;
-                // (eight partials per lane per round, loads first and clamped, as embed_step_kernel reads them: one memory round trip
-                // per 512 partials; a clamped duplicate of the last partial changes nothing)
-                for (int base = 0; base < a.n_part; base += 512) {
-                    float pv[8];
-                    int pi[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int p = min(base + lane + 64 * j, a.n_part - 1);
-                        pv[j] = a.part_val[(size_t)b * a.part_stride + p];
-                        pi[j] = a.part_idx[(size_t)b * a.part_stride + p];
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        if (stop_before(pv[j], pi[j], bv, bi)) { bv = pv[j]; bi = pi[j]; }
-                }
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {  // (a total order on what can win: both sides of a pair keep the same one)
-                    const float ov = __shfl_xor(bv, d, 64);
-                    const int oi = __shfl_xor(bi, d, 64);
-                    if (stop_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-                }
-                tok = bi;
-            }
-            tok = (unsigned)tok < (unsigned)a.vocab ? tok : 0;  // (embed_step_kernel's clamp)
+            else  // greedy: partials_first, the very pick embed_step_kernel makes of these partials one step later
+                tok = partials_first(a.part_val + (size_t)b * a.part_stride, a.part_idx + (size_t)b * a.part_stride, a.n_part);
+            tok = clamp_token(tok, a.vocab);
             const int n_ids = min(max(c->n_ids, 0), kStopMaxIds), n_seqs = min(max(c->n_seqs, 0), kStopMaxSeqs);
             bool hit = false;
             if (lane < n_ids) hit = c->ids[lane] == tok;

@@ -120,6 +120,45 @@ __device__ __forceinline__ void split3_pk(float x0, float x1, uint32_t& hi, uint
     lo = cvt_pk_bf16(r0 - bf16_lo(mid), r1 - bf16_hi(mid));
 }
 
+// Four consecutive fp32 values as their three bf16 planes: two split3_pk and three 8-byte stores, plane p at o + p * plane_stride
+// elements (the row-wise [hi | mid | lo] layout, the plane-major one and a batch row's 32-k step of plane_elem alike)
+__device__ __forceinline__ void store_split3x4(bf16_t* o, size_t plane_stride, f32x4 v) {
+    uint32_t h0, m0, l0, h1, m1, l1;
+    split3_pk(v.x, v.y, h0, m0, l0);
+    split3_pk(v.z, v.w, h1, m1, l1);
+    *reinterpret_cast<u32x2*>(o) = u32x2{h0, h1};
+    *reinterpret_cast<u32x2*>(o + plane_stride) = u32x2{m0, m1};
+    *reinterpret_cast<u32x2*>(o + 2 * plane_stride) = u32x2{l0, l1};
+}
+
+// elements [k, k + 4) of row `row` of a B24 matrix [.][K] (k % 4 == 0): one 8-B load of upper halves, one 4-B load of low bytes
+__device__ __forceinline__ f32x4 load_b24x4(const void* w, size_t row, int K, int k) {
+    const char* r = reinterpret_cast<const char*>(w) + row * (size_t)(3 * K);
+    const u32x2 h = *reinterpret_cast<const u32x2*>(r + 2 * (size_t)k);
+    const uint32_t l = *reinterpret_cast<const uint32_t*>(r + 2 * (size_t)K + k);
+    return f32x4{__uint_as_float((h.x << 16) | ((l & 0xffu) << 8)), __uint_as_float((h.x & 0xffff0000u) | (l & 0xff00u)),
+                 __uint_as_float((h.y << 16) | ((l >> 8) & 0xff00u)), __uint_as_float((h.y & 0xffff0000u) | ((l >> 16) & 0xff00u))};
+}
+
+// THE order of (value, index) pairs that decides which token a greedy step emits: greater value first, lower index on ties.  A NaN
+// never comes before anything.  lm_head's argmax epilogues produce a row's partials under it (gemv_internal.h better), the step head, the
+// log-probability stage and the stop stage pick from them under it (sample_common.h wave_first / partials_*), the top-N lists are
+// in it (tests/pick_ref.py states it for the tests).
+__device__ __forceinline__ bool pick_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
+// A picked index as a token: anything outside the vocabulary (the start index of a row that held nothing comparable, a corrupted
+// record) is token 0 — never an address past a table
+__device__ __forceinline__ int clamp_token(int t, int vocab) { return (unsigned)t < (unsigned)vocab ? t : 0; }
+
+// The counter PRNG of (seed, sequence length, row): a splitmix64 finaliser, its upper 24 bits as a uniform in [0, 1).  Integer
+// operations and one exact conversion: the host (zg_gpt_sample) and the device (sample_pick_kernel) agree to the bit.
+__host__ __device__ inline float counter_uniform(unsigned long long seed, unsigned long long seq_len, unsigned long long b) {
+    unsigned long long z = seed * 0x9E3779B97F4A7C15ULL + seq_len * 0xD1B54A32D192ED03ULL + b + 1ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    z ^= z >> 31;
+    return (float)(unsigned)(z >> 40) * 5.9604644775390625e-08f;
+}
+
 // Activation planes of the lock-step batch in global memory: the epilogue of the producing kernel writes the exact
 // three-term bf16 split of its output row, the consuming Linear loads them as MFMA A fragments — no LDS staging and no
 // split in front of its MFMAs.  Element (plane p, batch row m < 8, column k) of a [3][8][K] triple sits at

@@ -217,6 +217,9 @@ int launch_split3(const float* in, size_t rows, int K, bf16_t* out, hipStream_t 
 int launch_f32_to_b24(const float* in, size_t rows, int K, void* out, hipStream_t s);
 // B24 matrix [rows][K] -> plane-major bf16 [3][rows K], the split launch_split3(values, 1, rows K) makes of the values it holds
 int launch_b24_split3(const void* in, size_t rows, int K, bf16_t* out, hipStream_t s);
+// wte [V][K] (fp32 or B24) -> its exact bf16 planes, plane-major [3][V64][K] with zero rows behind row V - 1: the weight operand of
+// the scoring lm_head on handles whose whole-prompt GEMMs read weight planes
+int launch_wte_planes(const void* wte, int weight_type, size_t V, size_t V64, int K, bf16_t* out, hipStream_t s);
 // rows [from_row, ctx) of every (cache, sequence x head) strip set to zero: n_caches caches cache_stride bytes apart, each holding a
 // plane of [strips][ctx] rows of row_bytes at plane_off (api_gpt.hip clear_kv: what a new sequence must not inherit)
 int launch_kv_clear_tail(void* base, int n_caches, size_t cache_stride, size_t plane_off, int row_bytes, int strips, int ctx, int from_row,
@@ -367,6 +370,7 @@ struct PrefillKv {
 int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int pos0, int P, int E, int H, float* ws, size_t ws_floats, const PrefillKv& kv,
                         hipStream_t s, int force_tiles = 0, int* ran_out = nullptr);
 
+// ------------------------------------------------------------------------------------ step head and sampler stages (sample.hip)
 // GPT.sample tail: in-place softmax(logits / temp) per sequence + inverse-CDF draw with uniform u[b].
 // part_val / n_part / part_stride: the per-workgroup maxima lm_head's argmax epilogue left (the row maximum without a pass over the
 // logits); seg_ws: sample_workspace_floats(batch) floats; write_probs: leave softmax(logits / temp) in the logits rows
@@ -553,9 +557,6 @@ struct StopArgs {
     StopHost* host;
 };
 int launch_stop(const StopArgs& a, hipStream_t s);
-// wte [V][K] (fp32 or B24) -> its exact bf16 planes, plane-major [3][V64][K] with zero rows behind row V - 1: the weight operand of
-// the scoring lm_head on handles whose whole-prompt GEMMs read weight planes
-int launch_wte_planes(const void* wte, int weight_type, size_t V, size_t V64, int K, bf16_t* out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------ multi-GPU (dist.hip)
 int dist_broadcast(void* buf, size_t bytes, int root, hipStream_t s);  // in place, over the communicator of zg_dist_init
