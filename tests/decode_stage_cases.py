@@ -9,16 +9,21 @@ import ctypes as C
 import os
 from dataclasses import dataclass
 
+import numpy as np
+
 from test_gemv_plan_cpu import (B24, BF16, EPI_ARGMAX, EPI_GELU, EPI_QKV, EPI_RESID, F32, FIELDS, LN_FOLDED, PLANES_IN, PRO_LN, PRO_MERGE, PRO_NONE,
                                 SPLIT_K, STATS_IN)
 
-from zig_gpt2_amd import _lib
+import score_regimes
+from zig_gpt2_amd import _lib, synth
 
 ROUTES = ["GR_VALU", "GR_VALU_GROUPS", "GR_GENERIC", "GR_KSPLIT", "GR_LNK", "GR_MFMA16", "GR_MFMA16_KS", "GR_PL4", "GR_PL4_KS", "GR_LM_WPT"]
 MODEL_ROUTES = [r for r in ROUTES if r not in ("GR_VALU_GROUPS", "GR_GENERIC")]  # those two: plain op-tier Linears only
 WT = {"bf16": BF16, "f32": F32, "b24": B24}
 CLASS_NAMES = {1: "ln_1 + c_attn", 3: "attn c_proj", 4: "ln_2 + c_fc", 5: "mlp c_proj", 6: "lm_head"}
 VOCAB = 333  # a few hundred, 20 tiles of 16 and 13 rows over
+TOK_MEAN, TOK_OUT = VOCAB - 3, VOCAB - 4  # wte rows with mean 0.3 / std 2, and with a few 30 x outlier channels
+TOK_LO = VOCAB // 2                        # input tokens come from [TOK_LO, VOCAB - 2]: the rows below and row V - 1 are free for the ties
 
 
 @dataclass(frozen=True)
@@ -32,10 +37,11 @@ class Case:
     ctx: int = 64
     layers: int = 1
     ties: bool = False  # also the argmax ties (lm_head again with duplicated wte rows)
+    regime: str = ""    # the attention scores' regime (score_regimes): "" = N(0, 0.02) weights, "trained", "one-key@P", "far-below"
 
     @property
     def id(self):
-        return f"E{self.E}-b{self.batch}-{self.wt}-kv{self.kv}-off{self.off}-t{self.seq_len}-L{self.layers}"
+        return f"E{self.E}-b{self.batch}-{self.wt}-kv{self.kv}-off{self.off}-t{self.seq_len}-L{self.layers}" + (f"-{self.regime}" if self.regime else "")
 
     @property
     def heads(self):
@@ -70,6 +76,67 @@ def _cases():
 
 
 CASES = _cases()
+
+
+def _regime_cases():
+    """The attention paths again where exp(s - m) is not 1 (score_regimes): one layer, E = 128 unless the route needs more."""
+    c = []
+    one = lambda *hot: [f"one-key@{p}" for p in hot]
+    # one sequence, the fused launch: every regime, every hot position there is at that T (0, the ends of the first chunk of 256,
+    # the row this step appends)
+    for t, hot in ((6, (0, 5)), (257, (0, 255, 256)), (320, (0, 255, 256, 319))):
+        c += [Case(128, 1, seq_len=t, ctx=320, regime=r) for r in ["trained", "far-below"] + one(*hot)]
+    # one sequence without the fused launch: partials, merged by attn c_proj (two-pass above four splits: hot in the last and in the first)
+    c += [Case(128, 1, off=64, seq_len=257, ctx=320, regime=r) for r in ["trained", "far-below"] + one(256)]
+    c += [Case(128, 1, off=64, seq_len=1300, ctx=1536, regime=r) for r in ["trained"] + one(1290, 3)]
+    # lock step: merged by the last split, by tag and by ticket; without planes (partials, the two-pass merge)
+    c += [Case(128, 3, seq_len=257, ctx=320, regime=r) for r in ["trained"] + one(255)]
+    c += [Case(128, 3, seq_len=320, ctx=320, regime=r) for r in ["trained", "far-below"] + one(319)]
+    c += [Case(128, 2, off=4, seq_len=320, ctx=320, regime=r) for r in ["trained"] + one(256)]
+    c += [Case(128, 2, off=1, seq_len=1300, ctx=1536, regime=r) for r in ["trained"] + one(1290, 3)]
+    # the 16- and 24-bit caches, one sequence and two
+    for kv, hot in (("f16", (0, 256)), ("b24", (255, 256))):
+        for batch, p in zip((1, 2), hot):
+            c += [Case(128, batch, kv=kv, seq_len=257, ctx=320, regime=r) for r in ["trained"] + one(p)]
+    # twelve heads (48 keys: the range of six scores varies by more than the factor 60 / 8 over 96 heads, whatever the gain)
+    c += [Case(768, 1, seq_len=48, regime="trained"), Case(768, 8, seq_len=48, regime="trained")]
+    return c
+
+
+REGIME_CASES = _regime_cases()
+
+
+def make_weights(case, cfg):
+    """Tensor set, shapes and init scale of synth.make_weights from numpy's generator (as fast_weights of test_full_configs_gpu);
+    bf16-representable for bf16 handles, full fp32 otherwise (so that B24 and fp32 storage hold more than bf16 could); an outlier
+    row and a mean-shifted row of wte; then what the case's score regime changes (score_regimes.apply)."""
+    rng = np.random.default_rng(1000 + case.E + 7 * case.batch + 31 * case.off)
+    w = {}
+    for name, shape, mean, _ in synth.tensor_specs(cfg):
+        v = rng.standard_normal(int(np.prod(shape)), dtype=np.float32) * np.float32(0.02) + np.float32(mean)
+        w[name] = (synth.round_bf16(v) if case.wt == "bf16" else v).reshape(shape)
+    row = rng.standard_normal(case.E, dtype=np.float32) * np.float32(2.0) + np.float32(0.3)
+    w["wte"][TOK_MEAN] = synth.round_bf16(row)
+    row = w["wte"][TOK_OUT].copy()
+    row[rng.choice(case.E, 4, replace=False)] *= np.float32(30.0)
+    w["wte"][TOK_OUT] = synth.round_bf16(row)
+    if case.regime:
+        assert case.layers == 1 and case.wt == "bf16", case.id
+        score_regimes.apply(w, case.regime, case.E, case.seq_len, seed=case.seq_len)
+    return w
+
+
+def make_tokens(case):
+    """(prompt [B][max(seq_len - 1, 1)], the tokens the tapped step feeds [B])."""
+    B, T = case.batch, case.seq_len
+    rng = np.random.default_rng(77 + T + B)
+    prompt = rng.integers(TOK_LO, VOCAB - 1, size=(B, max(T - 1, 1))).astype(np.uint64)
+    toks = rng.integers(TOK_LO, VOCAB - 1, size=B).astype(np.uint64)
+    toks[0] = TOK_MEAN if case.off == 0 or B > 1 else TOK_OUT
+    if B > 1:
+        toks[1] = TOK_OUT
+    name = score_regimes.parse(case.regime)[0]
+    return score_regimes.same_token_rows(name, prompt, TOK_MEAN, TOK_OUT), score_regimes.same_token_rows(name, toks, TOK_MEAN, TOK_OUT)
 
 
 def plan(off, M, N, K, pro, epi, wt, ops, sk_tiles, t_hi):
@@ -134,3 +201,24 @@ def instantiation(p):
     if r == "GR_LM_WPT":
         return [("steps", p["steps"])]
     return []
+
+
+def attention_operands(case):
+    """float64 q [B][H][1][64] of the tapped step, K / V [B][H][T][64] and past = T - 1 from the case's own one-layer model."""
+    from zig_gpt2_amd.synth import GPTConfig
+    assert case.layers == 1 and case.wt == "bf16", case.id
+    prompt, toks = make_tokens(case)
+    T = case.seq_len
+    w = make_weights(case, GPTConfig(VOCAB, case.ctx, 1, case.heads, case.E))
+    q, K, V = score_regimes.qkv_of(w, np.concatenate([prompt[:, :T - 1], toks[:, None]], axis=1))
+    return q[:, :, T - 1:], K, V, T - 1
+
+
+def attention_how(case, modes=None):
+    """How the attention of the case's step is merged, as test_decode_stages_gpu.py reports it."""
+    modes = modes or plan_case(case)[0]
+    if modes["planes"]:
+        return "attention, merged by its last split (" + ("tagged" if modes["tags"] else "tickets") + ")"
+    n_splits = (t_hi_of(case) + 255) // 256
+    consumer = " (fused launch)" if modes["fused"] else ", attn c_proj's two-pass merge behind" if n_splits > 4 else ""
+    return "attention partials, merged in float64" + consumer

@@ -10,12 +10,17 @@ import ctypes as C
 import os
 from dataclasses import dataclass
 
+import numpy as np
+
 from test_prefill_plan_cpu import FIELDS, LN, PF_F32, PF_GELU_SPLIT, PF_QKV, PF_RESID, QKV, SK_FLAGS, SK_WS, WEIGHT_PLANES, WS
 
-from zig_gpt2_amd import _lib
+import score_regimes
+from zig_gpt2_amd import _lib, synth
 
 VOCAB = 333      # on the score GEMM's grid: 320 rows of wte in place and a strip of 13
 V64 = 384
+TOK_MEAN, TOK_OUT = VOCAB - 3, VOCAB - 4  # wte rows with mean 0.3 / std 2, and with a few 30 x outlier channels
+TOK_LO = VOCAB // 2
 SCORE_ROWS = 256
 FAMILY = {1: "S4", 2: "T128", 3: "T128_WP"}
 TAIL = {0: "NO_TAIL", 1: "LN_SPLIT", 2: "REDUCE", 3: "REDUCE_LN_SPLIT", 4: "REDUCE_RESID_LN"}
@@ -38,10 +43,12 @@ class Case:
     logits: bool = True  # compute_logits (False: the last Block stops behind its cache append)
     ctx: int = 0        # 0: past + n + 8
     twice: bool = False  # the tapped pass runs a second time on the same handle (the stream-K flags carry an epoch)
+    regime: str = ""     # the attention scores' regime (score_regimes): "" = N(0, 0.02) weights, "trained", "one-key@P", "far-below"
 
     @property
     def id(self):
         tail = ("-score" if self.score else "") + ("" if self.logits else "-nologits") + (f"-wgs{self.wgs}" if self.wgs else "") + ("-x2" if self.twice else "")
+        tail += f"-{self.regime}" if self.regime else ""
         return f"E{self.E}-L{self.layers}-b{self.batch}-n{self.n}-p{self.past}-{self.wt}-kv{self.kv}-pl{self.planes}-pin{self.pin[0]}.{self.pin[1]}{tail}"
 
     @property
@@ -169,6 +176,66 @@ def attention_plan(case):
     return kernel, nts, max_s, ng
 
 
+def first_range_last_key(case):
+    """The last key of the attention's first key range: its ranges are attention_plan's key tiles per range of 32 keys each."""
+    return 32 * attention_plan(case)[1] - 1
+
+
+def _regime_cases():
+    """The attention paths again where exp(s - m) is not 1 (score_regimes): one layer, E = 128 unless the route pin asks for more.
+    Hot keys of one-key: position 0 (every row's sink), the last key of the first key range, a key among the cached ones."""
+    c = []
+
+    def add(base, *regimes):
+        for r in regimes:
+            hot = {"one-key@range": f"one-key@{first_range_last_key(base)}"}.get(r, r)
+            c.append(Case(**{**base.__dict__, "regime": hot}))
+
+    add(Case(128, 2, 64, pin=(1, 0)), "trained", "one-key@0", "far-below")                          # one range
+    add(Case(128, 1, 257, pin=(1, 0)), "trained", "one-key@0", "one-key@range", "one-key@200")      # split ranges + merge (200: in the second range)
+    add(Case(128, 1, 320, ctx=320), "trained", "one-key@range")                                     # ... the whole context
+    add(Case(128, 2, 70, past=60, pin=(1, 0), ctx=160), "trained", "one-key@30")                    # the continuation kernel, fp32 cache
+    add(Case(128, 1, 120, past=200, kv="f16", ctx=320), "trained", "one-key@0", "one-key@range")    # ... fp16 cache, ranges merged
+    add(Case(128, 2, 43, past=33, pin=(2, 0), kv="b24", ctx=76), "trained", "one-key@10")           # ... B24 cache
+    add(Case(128, 2, 1, past=127, kv="f16", ctx=128), "trained", "one-key@0")                       # n = 1 at the end of the context
+    add(Case(384, 2, 64, pin=(1, 0)), "trained")                                                    # six heads under each route pin
+    add(Case(384, 3, 43, pin=(2, 0)), "trained")
+    return c
+
+
+REGIME_CASES = _regime_cases()
+
+
+def make_weights(case, cfg):
+    """As make_weights of decode_stage_cases.py: the tensor set, shapes and init scale of synth.make_weights from numpy's
+    generator; bf16-representable for bf16 handles, full fp32 otherwise; an outlier row and a mean-shifted row of wte; then what
+    the case's score regime changes (score_regimes.apply)."""
+    rng = np.random.default_rng(2000 + case.E + 7 * case.batch + 31 * case.n + case.past)
+    w = {}
+    for name, shape, mean, _ in synth.tensor_specs(cfg):
+        v = rng.standard_normal(int(np.prod(shape)), dtype=np.float32) * np.float32(0.02) + np.float32(mean)
+        w[name] = (synth.round_bf16(v) if case.wt == "bf16" else v).reshape(shape)
+    row = rng.standard_normal(case.E, dtype=np.float32) * np.float32(2.0) + np.float32(0.3)
+    w["wte"][TOK_MEAN] = synth.round_bf16(row)
+    row = w["wte"][TOK_OUT].copy()
+    row[rng.choice(case.E, 4, replace=False)] *= np.float32(30.0)
+    w["wte"][TOK_OUT] = synth.round_bf16(row)
+    if case.regime:
+        assert case.layers == 1 and case.wt == "bf16", case.id
+        score_regimes.apply(w, case.regime, case.E, case.past + case.n, seed=case.past + case.n)
+    return w
+
+
+def make_tokens(case):
+    """(the tokens of positions 0 .. past + n - 1 [B][past + n], the generator the GPU test draws its step on top from)."""
+    B, n, past = case.batch, case.n, case.past
+    rng = np.random.default_rng(99 + n + B)
+    toks = rng.integers(TOK_LO, VOCAB - 1, size=(B, past + n)).astype(np.uint64)
+    toks[0, past] = TOK_MEAN
+    toks[B - 1, past + n - 1] = TOK_OUT if B * n > 1 else TOK_MEAN
+    return score_regimes.same_token_rows(score_regimes.parse(case.regime)[0], toks, TOK_MEAN, TOK_OUT), rng
+
+
 def plan_case(case):
     """([(class, layer, role, plan dict)] of every GEMM launch in launch order, the attention's plan)."""
     return [(cls, l, role, plan(case.wgs, *args)) for cls, l, role, args in gemm_rows(case)], attention_plan(case)
@@ -186,3 +253,18 @@ def pass_route(p):
     if p["family"] == 1:
         return f"PF_S4 ({p['npairs']} plane pairs, {p['slices']} K slice(s){', stream-K' if p['stream_k'] else ''})"
     return f"PF_{FAMILY[p['family']]} ({'through the workspace' if p['partial'] else 'whole'}" + (f", {p['nspl']} planes)" if p["nspl"] else ")")
+
+
+def attention_operands(case):
+    """float64 q [B][H][n][64] of the pass's new positions, K / V [B][H][past + n][64] and past from the case's own one-layer model."""
+    from zig_gpt2_amd.synth import GPTConfig
+    assert case.layers == 1 and case.wt == "bf16", case.id
+    w = make_weights(case, GPTConfig(VOCAB, case.context, 1, case.heads, case.E))
+    q, K, V = score_regimes.qkv_of(w, make_tokens(case)[0])
+    return q[:, :, case.past:], K, V, case.past
+
+
+def attention_how(case, att=None):
+    """The attention's kernel and ranges, as test_pass_stages_gpu.py reports them."""
+    att = att or attention_plan(case)
+    return ("whole-prompt kernel" if att[0] == 0 else f"continuation kernel, {case.kv} cache") + (f", {att[2]} ranges merged" if att[2] > 1 else ", one range")

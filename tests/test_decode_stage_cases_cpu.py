@@ -1,15 +1,21 @@
 """The case list of test_decode_stages_gpu.py, judged on the CPU: (1) the launches zg_debug_gemv_plan plans for it reach every
 model-tier route and every kernel instantiation tests/golden/gemv_plan.json records, or the test names what it cannot reach and
 why; (2) the bound the GPU test applies, 3 x Y with Y the float32 numpy evaluation's own error (stage_ref), has teeth: three
-emulated defects fed through stage_ref exceed it by 1.5 x at every width, weight type and batch of the list."""
+emulated defects fed through stage_ref exceed it by 1.5 x at every width, weight type and batch of the list; (3) the score
+regimes (score_regimes.py): every regime case meets its regime's conditions in a float64 forward of its own model, the regimes
+reach every attention path and cache format the list has, and four emulated attention defects that pass at the old cases' scale
+exceed the regime cases' bounds by half."""
+import dataclasses
+import functools
 import json
 
 import numpy as np
 import pytest
 
+import score_regimes as rg
 import stage_ref as sr
 import test_gemv_plan_cpu as gp
-from decode_stage_cases import CASES, MODEL_ROUTES, ROUTES, VOCAB, instantiation, plan_case
+from decode_stage_cases import CASES, MODEL_ROUTES, REGIME_CASES, ROUTES, VOCAB, attention_how, attention_operands, instantiation, plan_case
 
 TWO_BITS = "needs two bits of ZGPT2_DECODE_PATHS_OFF at once ({}); the list sets one bit per handle"
 NO_WORKSPACE = ("K = 3072 in one slice: a launch without the split-K workspace; the model tier gives every launch its workspace (base_gemv), so "
@@ -129,3 +135,80 @@ def test_three_defects_exceed_the_bound_by_half(E, wt):
                     bound = factor[cls] * fig["Y"]
                     print(f"E {E} {wt} M {M} {fig['N']}x{fig['K']}: Y {fig['Y']:.2e}  {name} {fig[name]:.2e}  ({fig[name] / bound:.1f} x the bound of {factor[cls]:.0f} Y)")
                     assert fig[name] >= 1.5 * bound, (E, wt, M, fig)
+
+
+# ---------------------------------------------------------------------------------------------- the score regimes (score_regimes.py)
+# What the cases above cannot see, printed by the teeth test below at each regime case's shape with N(0, 0.02) weights (score spread
+# 0.1 .. 0.4, E 768: 1.5): the query cut to two planes measures 0.08 .. 0.90 x the 3 Y bound, a maximum started at 0 and a merge
+# relative to the first split 0.05 .. 0.39 x, the unbroken emulation's own figure — all pass; scores rounded to 16 mantissa bits
+# 0.05 .. 0.6 x at E 128 and 1.5 / 4.2 x at E 768, the one defect of the four that the widest of those cases could see.
+@functools.lru_cache(maxsize=None)
+def regime_teeth(case):
+    q, K, V, past = attention_operands(case)
+    return rg.teeth(case.id, case.regime, q, K, V, past, 256)
+
+
+def test_the_regime_cases_are_new_cases_beside_an_unchanged_list():
+    assert all(c.regime == "" for c in CASES) and all(rg.parse(c.regime)[0] for c in REGIME_CASES)
+    ids = [c.id for c in CASES + REGIME_CASES]
+    assert len(set(ids)) == len(ids) and len(REGIME_CASES) <= 48
+    assert all(c.layers == 1 and c.wt == "bf16" and c.id.endswith("-" + c.regime) for c in REGIME_CASES)
+    for c in REGIME_CASES:  # one-key: the hot position is a cached one or the row the step appends
+        hot = rg.parse(c.regime)[1]
+        assert hot is None or 0 <= hot < c.seq_len, c.id
+
+
+@pytest.mark.parametrize("case", REGIME_CASES, ids=lambda c: c.id)
+def test_a_regime_case_meets_its_regimes_conditions_in_float64(case):
+    q, K, V, past = attention_operands(case)
+    sc = rg.scores(q, K, past)
+    print(f"REGIME {case.id}: {rg.describe(sc)}")
+    assert rg.conditions(case.regime, sc, past) == []
+    if case.regime == "trained":
+        q, K, V = (t.astype(np.float32) for t in (q, K, V))
+        ref, s = sr.causal_attention(q, K, V, past)
+        Y = sr.metric(sr.causal_attention(q, K, V, past, np.float32)[0], ref, s)
+        assert Y >= rg.Y_FLOOR, (case.id, Y)
+
+
+def test_the_regimes_reach_every_attention_path():
+    seen = {}
+    for c in REGIME_CASES:
+        modes, _ = plan_case(c)
+        seen.setdefault(rg.parse(c.regime)[0], set()).add((attention_how(c, modes), c.kv, c.batch == 1))
+    hows = {attention_how(c) for c in CASES}
+    assert len(hows) == 5 and {h for h in hows if "two-pass" in h} and {h for h in hows if "fused" in h}, hows
+    for name in ("trained", "one-key"):
+        assert {h for h, _, _ in seen[name]} == hows, (name, hows - {h for h, _, _ in seen[name]})
+        assert {(kv, one) for _, kv, one in seen[name]} >= {(kv, one) for kv in ("f16", "b24") for one in (True, False)}, name
+    far = {h for h, _, _ in seen["far-below"]}
+    assert any("fused" in h for h in far) and any("merged by its last split" in h for h in far) and any(h.endswith("merged in float64") for h in far), far
+    # one-key: every hot position the fused launch has at each T, and the first and the last of six splits under both two-pass cases
+    hot = lambda pick: {(c.seq_len, rg.parse(c.regime)[1]) for c in REGIME_CASES if rg.parse(c.regime)[0] == "one-key" and pick(c)}
+    assert hot(lambda c: plan_case(c)[0]["fused"]) == {(6, 0), (6, 5), (257, 0), (257, 255), (257, 256), (320, 0), (320, 255), (320, 256), (320, 319)}
+    for batch in (1, 2):
+        assert hot(lambda c: c.seq_len == 1300 and c.batch == batch) == {(1300, 3), (1300, 1290)}
+
+
+@pytest.mark.parametrize("case", REGIME_CASES, ids=lambda c: c.id)
+def test_the_regime_bounds_have_teeth(case):
+    """Under `trained` the query cut to two planes and scores of 16 mantissa bits exceed 3 Y by half at every width and T of the
+    list; under far-below a maximum started at 0 does (it returns 0 / 0).  The same defects at the case's shape with today's
+    N(0, 0.02) weights are printed beside them."""
+    bites = regime_teeth(case)
+    name = rg.parse(case.regime)[0]
+    if name == "trained":
+        regime_teeth(dataclasses.replace(case, regime=""))
+        assert bites["two planes"] and bites["scores b24"], (case.id, bites)
+    elif name == "far-below":
+        assert bites["max from 0"], (case.id, bites)
+
+
+def test_every_emulated_defect_exceeds_its_bound_in_some_regime():
+    by_regime = {}
+    for c in REGIME_CASES:
+        for d, hit in regime_teeth(c).items():
+            if hit:
+                by_regime.setdefault(d, set()).add(rg.parse(c.regime)[0])
+    assert set(by_regime) == set(rg.DEFECTS), by_regime
+    assert "one-key" in by_regime["merge from first"]  # exp(m_s - m_first) overflows where the hot key sits in a later split

@@ -3,14 +3,21 @@ families and the fp32-weight three-pass kernel for every Linear role, the K slic
 the row counts around the tiles and every attention path the issue of this test lists — or the test names what a model-level
 pass cannot reach within these sizes and why; (2) no case exceeds the row budget that keeps its float64 references to a few
 seconds; (3) the bound the GPU test applies, 3 x Y with Y the float32 numpy evaluation's own error (stage_ref), has teeth: five
-emulated defects measured in the same metric exceed it by 1.5 x at the list's widths, weight types and smallest and largest M."""
+emulated defects measured in the same metric exceed it by 1.5 x at the list's widths, weight types and smallest and largest M;
+(4) the score regimes (score_regimes.py): every regime case meets its regime's conditions in a float64 forward of its own model,
+the regimes reach every attention kernel, range count and cache format, and emulated attention defects that pass at the old
+cases' scale exceed the regime cases' bounds by half."""
+import dataclasses
+import functools
 import time
 
 import numpy as np
 import pytest
 
+import score_regimes as rg
 import stage_ref as sr
-from pass_stage_cases import CASES, VOCAB, outcome, pass_route, plan_case
+from pass_stage_cases import (CASES, REGIME_CASES, VOCAB, attention_how, attention_operands, attention_plan, first_range_last_key, outcome, pass_route,
+                              plan_case)
 
 ROLES = ("c_attn", "attn c_proj", "c_fc", "mlp c_proj")
 # What test_prefill_plan_cpu.py's table holds that a model-level pass cannot reach within the row budget, each with its reason.
@@ -166,3 +173,79 @@ def test_the_defects_exceed_the_bound_by_half(E, wt):
                     print(f"E {E} {wt} M {c.M} {fig['role']} {fig['N']}x{fig['K']}: Y {fig['Y']:.2e}  {name} {fig[name]:.2e}  ({fig[name] / bound:.1f} x the bound of {f:.0f} Y)")
                     assert fig[name] >= 1.5 * bound, (E, wt, c.M, fig)
     assert time.perf_counter() - t0 < 60, "the references of one width must stay quick"
+
+
+# ---------------------------------------------------------------------------------------------- the score regimes (score_regimes.py)
+# What the cases above cannot see, printed by the teeth test below at each regime case's shape with N(0, 0.02) weights: the query
+# cut to two planes — the product the six plane products exist for — measures 0.12 .. 0.49 x the 3 Y bound, scores rounded to 16
+# mantissa bits 0.14 .. 0.5 x at E 128 and 1.2 x at E 384, a maximum started at 0 and a merge relative to the first range
+# 0.13 .. 0.38 x, the unbroken emulation's own figure: all of them pass, or fall short of the margin of a half.
+@functools.lru_cache(maxsize=None)
+def regime_teeth(case):
+    q, K, V, past = attention_operands(case)
+    return rg.teeth(case.id, case.regime, q, K, V, past, 32 * attention_plan(case)[1], wide=sr.bound_y("PF_ATTN_WIDE"))
+
+
+def test_the_regime_cases_are_new_cases_beside_an_unchanged_list():
+    assert all(c.regime == "" for c in CASES) and all(rg.parse(c.regime)[0] for c in REGIME_CASES)
+    ids = [c.id for c in CASES + REGIME_CASES]
+    assert len(set(ids)) == len(ids) and len(REGIME_CASES) <= 32
+    for c in REGIME_CASES:
+        assert c.layers == 1 and c.wt == "bf16" and c.planes == 3 and c.id.endswith("-" + c.regime) and c.M <= 512, c.id
+        hot = rg.parse(c.regime)[1]
+        assert hot is None or 0 <= hot < c.past + c.n - 1, c.id  # one-key: a position some query of the pass looks back at
+
+
+@pytest.mark.parametrize("case", REGIME_CASES, ids=lambda c: c.id)
+def test_a_regime_case_meets_its_regimes_conditions_in_float64(case):
+    q, K, V, past = attention_operands(case)
+    sc = rg.scores(q, K, past)
+    print(f"REGIME {case.id}: {rg.describe(sc)}")
+    assert rg.conditions(case.regime, sc, past) == []
+    if case.regime == "trained":
+        q, K, V = (t.astype(np.float32) for t in (q, K, V))
+        ref, s = sr.causal_attention(q, K, V, past)
+        Y = sr.metric(sr.causal_attention(q, K, V, past, np.float32)[0], ref, s)
+        assert Y >= rg.Y_FLOOR, (case.id, Y)
+
+
+def test_the_regimes_reach_every_attention_path():
+    seen = {}
+    for c in REGIME_CASES:
+        seen.setdefault(rg.parse(c.regime)[0], set()).add((attention_how(c).split(",")[0] + (", merged" if attention_plan(c)[2] > 1 else ", one range"), c.kv))
+    # the whole-prompt kernel with one range and with ranges merged; the continuation kernel per cache format, one range and merged
+    want = {("whole-prompt kernel, one range", "f32"), ("whole-prompt kernel, merged", "f32"), ("continuation kernel, merged", "f32"),
+            ("continuation kernel, one range", "f16"), ("continuation kernel, merged", "f16"), ("continuation kernel, one range", "b24")}
+    for name in ("trained", "one-key"):
+        assert seen[name] >= want, (name, want - seen[name])
+    assert seen["far-below"]
+    # one-key: the sink every row looks at, the last key of the first key range (whole prompt and continuation), a key among the cached ones
+    hot = [(c, rg.parse(c.regime)[1]) for c in REGIME_CASES if rg.parse(c.regime)[0] == "one-key"]
+    assert any(h == 0 and c.past == 0 for c, h in hot) and any(0 < h < c.past for c, h in hot)
+    assert {c.past > 0 for c, h in hot if h == first_range_last_key(c) and attention_plan(c)[2] > 1} == {False, True}
+    # six heads under each route pin
+    assert {c.pin[0] for c in REGIME_CASES if c.E == 384 and c.regime == "trained"} == {1, 2}
+
+
+@pytest.mark.parametrize("case", REGIME_CASES, ids=lambda c: c.id)
+def test_the_regime_bounds_have_teeth(case):
+    """Under `trained` the query cut to two planes and scores of 16 mantissa bits exceed the bound — 6 Y, stage_ref.BOUND_Y's
+    PF_ATTN_WIDE — by half at every width and shape of the list; under far-below a maximum started at 0 does.  The same defects at the case's shape with today's N(0, 0.02) weights
+    are printed beside them."""
+    bites = regime_teeth(case)
+    name = rg.parse(case.regime)[0]
+    if name == "trained":
+        regime_teeth(dataclasses.replace(case, regime=""))
+        assert bites["two planes"] and bites["scores b24"], (case.id, bites)
+    elif name == "far-below":
+        assert bites["max from 0"], (case.id, bites)
+
+
+def test_every_emulated_defect_exceeds_its_bound_in_some_regime():
+    by_regime = {}
+    for c in REGIME_CASES:
+        for d, hit in regime_teeth(c).items():
+            if hit:
+                by_regime.setdefault(d, set()).add(rg.parse(c.regime)[0])
+    assert set(by_regime) == set(rg.DEFECTS), by_regime
+    assert "one-key" in by_regime["merge from first"]  # exp(m_s - m_first) overflows where the hot key sits in a later key range
