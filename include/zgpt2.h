@@ -153,6 +153,13 @@ unsigned long long zg_debug_gemm_launches(void);
 /* Diagnostic: shader-clock stamps {count, start, end} of workgroup 0 / wave 0 of the last GEMM launched with
  * ZGPT2_GEMM_DBG bit 256 (tools/microbench/gemm_bench.cpp: cycles vs wall time = the clock the chip ran at). */
 int zg_debug_gemm_stamps(unsigned long long* out, size_t n_words);
+/* Diagnostic (tests): the completion word of the op tier.  Every op-tier call polls a pinned word for its own 32-bit sequence
+ * number (compared for equality); a call whose word never arrives drains the stream instead.  zg_debug_ops_set_done_seq sets the
+ * number the next call continues from (tests: in front of its wrap); zg_debug_ops_done_state: out[0] = the sequence number last
+ * given out, out[1] = the pinned word, out[2] = calls so far that polled to the end without seeing their number and drained
+ * the stream.  n_out >= 3.  Both need zg_init. */
+int zg_debug_ops_set_done_seq(unsigned seq);
+int zg_debug_ops_done_state(unsigned long long* out, size_t n_out);
 /* Diagnostic / test entry: ONE whole-prompt Linear exactly as zg_gpt_prefill launches it (src/ops.zig:21-46 for M = batch x
  * prompt rows).  A = the activation planes [M][3 K] bf16 (hi | mid | lo: the exact split of the fp32 rows), W = bf16 weights
  * [N][K], all device pointers.  epilogue: 0 fp32 C[M][N] = A W^T + bias; 1 C[M][N] += ... (residual add; ws required);
@@ -444,6 +451,24 @@ int zg_debug_gpt_step_taps(zg_gpt* g, size_t seq_len, const size_t* tokens, size
 int zg_debug_gpt_pass_taps(zg_gpt* g, size_t past_len, const size_t* tokens, size_t token_stride, size_t n_tokens, int compute_logits, int score, size_t top_n,
                            float* logits_out, size_t logits_len, void* arena_out, size_t arena_bytes, size_t* arena_used, zg_tap_entry* table_out,
                            size_t table_len, size_t* n_entries, int* info, size_t n_info);
+/* Diagnostic (tests): the hand-over state that changes only over a handle's lifetime ("What ages").  A decode tag is
+ * (device epoch << 8 | launch id): 24 bits of the step counter the embed kernel advances; the host counts the steps it enqueues
+ * and zeroes the tagged words every 2^23 of them.  The stream-K c_attn GEMM of the whole-prompt pass stamps its flag words with a
+ * per-launch epoch of 32 bits.
+ * zg_debug_gpt_age: act as if n_steps decode steps had been enqueued and run, none of which wrote a tagged slot — the host's
+ * own counting and clearing rule runs for n_steps, and a one-thread kernel on the handle's stream adds n_steps (mod 2^32) to the
+ * device epoch.  A handle with neither tagged hand-overs nor the fused launch has no such state: nothing happens.  set_sk_epoch
+ * != 0 (any handle): the epoch the next stream-K launch is handed follows sk_epoch.
+ * zg_debug_gpt_age_state: drains the stream; out[ZG_AGE_STATE_WORDS] = device epoch word, steps counted since the tagged words
+ * were last zeroed, steps counted in total, clears of the tagged words enqueued, the stream-K epoch last handed to a launch (or
+ * set), restarts of the stream-K epoch (its flag words zeroed on the stream).
+ * zg_debug_gpt_tag_census: drains the stream, copies the words to the host and counts there: counts[0..2] = words of the split-K
+ * tags, the attention-partial tags and the fused launch's q / k / v tags whose tag is valid (launch id != 0) and carries epoch24
+ * in its epoch field; counts[3] = stream-K flag words equal to sk_flag_value (0 on a handle without a whole-prompt path). */
+#define ZG_AGE_STATE_WORDS 6
+int zg_debug_gpt_age(zg_gpt* g, size_t n_steps, int set_sk_epoch, unsigned sk_epoch);
+int zg_debug_gpt_age_state(zg_gpt* g, unsigned long long* out, size_t n_out);
+int zg_debug_gpt_tag_census(zg_gpt* g, unsigned epoch24, unsigned sk_flag_value, size_t* counts, size_t n_counts);
 /* GPT.sample — src/main.zig:198-207 for all sequences: zg_gpt_forward(seq_len, tokens, logits), then
  * logits /= temp, softmax, and an index drawn with probability proportional to the result
  * (std.rand weightedIndex: first index whose running sum exceeds u * total).  The reference re-seeds

@@ -30,6 +30,21 @@ def test_every_header_symbol_is_exported_and_bound(header_symbols):
     assert not extra, f"bound but not declared in the header: {extra}"
 
 
+def test_the_handle_age_entries_are_declared_and_bound(header_symbols):
+    """The debug entries test_handle_age_gpu.py sets a handle's age and reads its hand-over state through: declared, bound with the
+    header's argument counts, and the words of the state and the census named as the header lists them."""
+    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER).read(), flags=re.S)
+    for name in ("zg_debug_gpt_age", "zg_debug_gpt_age_state", "zg_debug_gpt_tag_census", "zg_debug_ops_set_done_seq", "zg_debug_ops_done_state"):
+        assert name in header_symbols and name in _lib.SIGNATURES, name
+        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1)
+        assert len(_lib.SIGNATURES[name][1]) == len(args.split(",")), (name, args)
+    assert int(re.search(r"#define ZG_AGE_STATE_WORDS (\d+)", text).group(1)) == len(_lib.AGE_STATE) == 6
+    assert _lib.AGE_STATE[:5] == ["device_epoch", "steps_since_clear", "steps_total", "clears", "sk_epoch"] and len(_lib.TAG_CENSUS) == 4
+    lib = _lib.load()
+    out = (ctypes.c_ulonglong * 6)()
+    assert lib.zg_debug_gpt_age_state(None, out, 6) != 0  # no handle (and here no zg_init): refused
+
+
 def test_uninitialised_calls_fail_loudly():
     lib = _lib.load()
     # No GPU here: zg_init must fail with a HIP error, and compute entry points must refuse to run

@@ -98,6 +98,8 @@ SIGNATURES = {
     "zg_unregister_all": (C.c_int, []),
     "zg_debug_gemm_launches": (C.c_ulonglong, []),
     "zg_debug_gemm_stamps": (C.c_int, [vp, sz]),
+    "zg_debug_ops_set_done_seq": (C.c_int, [C.c_uint]),
+    "zg_debug_ops_done_state": (C.c_int, [vp, sz]),
     "zg_debug_last_kernel": (C.c_int, [C.c_char_p, sz]),
     "zg_debug_gemv_plan": (C.c_int, [C.c_int] * 6 + [C.c_uint, C.c_int, C.c_int, vp, sz]),
     "zg_debug_attn_prefill": (C.c_int, [vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, sz, C.c_int]),
@@ -141,6 +143,9 @@ SIGNATURES = {
     "zg_gpt_generate_fetch_range": (C.c_int, [vp, sz, sz, vp, sz]),
     "zg_gpt_argmax": (C.c_int, [vp, vp, sz]),
     "zg_debug_gpt_step_taps": (C.c_int, [vp, sz, vp, sz, vp, sz, szp, vp, sz, szp, vp, sz]),
+    "zg_debug_gpt_age": (C.c_int, [vp, sz, C.c_int, C.c_uint]),
+    "zg_debug_gpt_age_state": (C.c_int, [vp, vp, sz]),
+    "zg_debug_gpt_tag_census": (C.c_int, [vp, C.c_uint, C.c_uint, vp, sz]),
     "zg_debug_gpt_pass_taps": (C.c_int, [vp, sz, vp, sz, sz, C.c_int, C.c_int, sz, vp, sz, vp, sz, szp, vp, sz, szp, vp, sz]),
     "zg_gpt_sample": (C.c_int, [vp, sz, vp, sz, C.c_float, vp, C.c_uint64, vp, vp, sz]),
     "zg_gpt_hidden": (C.c_int, [vp, vp, sz]),
@@ -237,6 +242,8 @@ TAP_DTYPES = ["<f4", "<f2", "<u2", "u1", "<i4"]
 TAP_FUSED, TAP_NOT_WRITTEN = 1, 2
 PASS_INFO = ["planes", "kv_mode", "weight_type", "pf_ws_floats", "stream_k_operands", "v64", "score_rows"]  # zg_debug_gpt_pass_taps
 PASS_TAP_ROWS_BEHIND = 4
+AGE_STATE = ["device_epoch", "steps_since_clear", "steps_total", "clears", "sk_epoch", "sk_restarts"]  # zg_debug_gpt_age_state
+TAG_CENSUS = ["sk_tag", "part_tag", "qkv_tag", "sk_flags"]  # zg_debug_gpt_tag_census
 TAP_INFO = ["planes", "stats", "tags", "fused", "max_splits", "lm_grid", "t_hi", "kv_mode", "weight_type"]
 
 

@@ -61,6 +61,8 @@ static inline StepTail normalized(StepTail t, bool with_logits) {
     return t;
 }
 
+constexpr size_t kSkFlagWords = 512;  // flag words of the stream-K hand-over (zg_gpt.sk_flags): four per shared tile, 128 shared tiles
+
 struct zg_layer {
     void *c_attn_w, *c_proj_w, *c_fc_w, *mlp_proj_w;
     // ZG_GPT_WEIGHTS_F32 / _B24 handles only: the same matrices (the stored values) split exactly into bf16 planes [out][3 in] = [hi | mid | lo]
@@ -97,8 +99,9 @@ struct zg_gpt {
     // whole-prompt (prefill) scratch, rows = batch * ctx: x fp32 [E], qkv fp32 [3E], split bf16 [kSplit E] and [kSplit 4E]
     float *pf_x, *pf_qkv, *pf_ws;
     size_t pf_ws_floats;
-    unsigned* sk_flags;   // stream-K hand-over of the c_attn GEMM (PrefillQkv.sk_*): 512 flag words, zeroed at create
-    unsigned sk_epoch;
+    unsigned* sk_flags;   // stream-K hand-over of the c_attn GEMM (PrefillQkv.sk_*): kSkFlagWords flag words, zeroed at create
+    unsigned sk_epoch;    // the epoch last handed to a stream-K launch: never 0, the value of a flag word no launch has written (next_sk_epoch)
+    size_t sk_restarts;   // times the epoch wrapped: the flag words were zeroed on the stream and the count began again at 1
     bool sk_used;         // a stream-K launch since the last check of gemm_s4_fault
     bf16_t *pf_a, *pf_h;
     // lock-step batch with bf16 weights: activation planes between the kernels of a Block (GemvArgs.pl_in / pl_out):
@@ -115,6 +118,7 @@ struct zg_gpt {
     unsigned long long *sk_tag, *part_tag;
     size_t sk_tag_bytes, part_tag_bytes;
     size_t epochs_since_clear;  // steps enqueued since the tagged words were last zeroed (note_steps)
+    size_t steps_counted, tag_clears;  // steps note_steps has counted in all, clears it has enqueued (zg_debug_gpt_age_state)
     bool tags_on;
     // one sequence: ln_1 + c_attn and the attention of a layer as ONE launch (attn_qkv.hip), q and the new k / v row handed over as
     // (value, tag) words [3 E] (tags as above: the embed kernel advances the epoch)
@@ -368,6 +372,7 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
     g->pf_x = g->pf_qkv = g->pf_ws = nullptr;
     g->sk_flags = nullptr;
     g->sk_epoch = 0;
+    g->sk_restarts = 0;
     g->sk_used = false;
     g->pf_a = g->pf_h = nullptr;
     g->pf_ws_floats = 0;
@@ -379,7 +384,7 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
         // split-K partials of the prompt GEMMs; fp32 weights: three weight-plane passes of [B ctx, 4 E] at the least
         g->pf_ws_floats = g->wt == WT_BF16 ? (size_t)(16u << 20) : std::max((size_t)(16u << 20), 3 * B * C * 4 * E);
         g->pf_ws = (float*)P(g->pf_ws_floats * 4);
-        g->sk_flags = (unsigned*)P(2048);
+        g->sk_flags = (unsigned*)P(kSkFlagWords * sizeof(unsigned));
     }
     // (behind everything else: handles that never ask for log-probabilities keep the layout they had)
     g->lp_ws = logprob_workspace(P(logprob_workspace_bytes((int)B, (int)V)), (int)B, (int)V);
@@ -1010,6 +1015,22 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
     return ZG_OK;
 }
 
+// The epoch of the next stream-K launch (gemm_s4.hip SK: the producer stores it into sk_flags, the consumer waits until its flag
+// word equals it).  One per layer per pass in 32 bits: days of continuous prefill wrap it.  0 is what every flag word holds that no
+// launch has written, and behind the wrap a small value is what a word may still hold from the handle's first launches — a
+// consumer would take a half tile nobody produced, with no fault raised.  So 0 is never handed out, and where the count begins
+// again the flag words are zeroed on the stream in front of the launch (as note_steps does for the decode tags): every word then
+// holds 0, and from there on every epoch handed out is larger than every word written before it.
+int next_sk_epoch(zg_gpt* g, hipStream_t s, unsigned* out) {
+    if (++g->sk_epoch == 0u) {
+        ZG_HIP(hipMemsetAsync(g->sk_flags, 0, kSkFlagWords * sizeof(unsigned), s));
+        g->sk_epoch = 1u;
+        ++g->sk_restarts;
+    }
+    *out = g->sk_epoch;
+    return ZG_OK;
+}
+
 // Whole-prompt forward of positions 0..P-1 of every sequence (tokens in g->prompt): fills the KV caches
 // exactly as P calls of GPT.forward would (main.zig:331-334) and leaves the residual stream of all rows in
 // pf_x.  With `last_block_full` false the last Block stops after its cache append: nothing downstream of
@@ -1055,8 +1076,8 @@ int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipS
             qa.sk_ws = g->pf_ws;
             qa.sk_ws_bytes = g->pf_ws_floats * 4;
             qa.sk_flags = g->sk_flags;
-            qa.sk_flags_words = 512;  // (carve: 2048 bytes)
-            qa.sk_epoch = ++g->sk_epoch;
+            qa.sk_flags_words = (unsigned)kSkFlagWords;
+            ZG_TRY(next_sk_epoch(g, s, &qa.sk_epoch));
             g->sk_used = true;
         }
         if (taps) ZG_TRY(tap_caches(g, taps, -1, l, 0, T_tap, s));
@@ -1131,11 +1152,15 @@ int check_fault(zg_gpt* g) {
 // contexts (the high attention splits) could meet its own tag again 2^24 steps later — about an hour of decoding.  So the
 // host counts the steps it enqueues and zeroes the tagged words (tag 0 is never valid: launch ids start at 1) on the stream
 // every 2^23 of them, in front of the steps of the call that crosses the mark.
+// The rule holds while the device runs fewer than two steps per counted one: every path that advances the epoch counts its steps
+// here (an upper bound is fine), and tests/test_handle_age_gpu.py holds each to that (zg_debug_gpt_age_state).
 int note_steps(zg_gpt* g, size_t n, hipStream_t s) {
     if (!g->tags_on && !g->fused_on) return ZG_OK;
     g->epochs_since_clear += n;
+    g->steps_counted += n;
     if (g->epochs_since_clear < ((size_t)1 << 23)) return ZG_OK;
     g->epochs_since_clear = n;
+    ++g->tag_clears;
     ZG_HIP(hipMemsetAsync(g->sk_tag, 0, g->sk_tag_bytes, s));
     ZG_HIP(hipMemsetAsync(g->part_tag, 0, g->part_tag_bytes, s));
     ZG_HIP(hipMemsetAsync(g->qkv_tag, 0, g->qkv_tag_bytes, s));
@@ -3247,9 +3272,11 @@ int zg_gpt_time_kernel(zg_gpt* g, int which_and_options, int iters, float* avg_u
     if (t_opt >= 1 && t_opt <= g->cfg.context_size) T = t_opt;
     ZG_HIP(hipStreamSynchronize(s));
     ZG_TRY(ensure_ln_folded(g, s));
-    ZG_TRY(note_steps(g, (size_t)iters + 8, s));  // (one epoch per replay of the chain)
-    ZG_TRY(stage_ctrl(g, T - 1, T, 1, s));
     const int chain = 64, reps = (iters + chain - 1) / chain;
+    // one epoch per replay of the chain, warm-up included — and class 0 IS the embed kernel, which advances the epoch itself at
+    // every one of the chain's launches
+    ZG_TRY(note_steps(g, (size_t)(reps + 1) * (which == 0 ? (size_t)chain : 1), s));
+    ZG_TRY(stage_ctrl(g, T - 1, T, 1, s));
     hipGraphExec_t exec = nullptr;
     ZG_TRY(capture_graph(s, &exec, [&] {
         // tagged hand-overs: a new epoch per replay and a launch id per chain position, so that every merging split / slice
@@ -3286,6 +3313,58 @@ int zg_gpt_time_kernel(zg_gpt* g, int which_and_options, int iters, float* avg_u
     *avg_us = ms * 1000.0f / (float)(reps * chain);
     if (algorithmic_bytes) *algorithmic_bytes = bytes_tab[which];
     return check_fault(g);
+}
+
+// A handle's age (tests; include/zgpt2.h): n_steps steps that wrote no tagged slot, counted by the production rule and added to
+// the device epoch on the stream; the stream-K epoch on request.
+int zg_debug_gpt_age(zg_gpt* g, size_t n_steps, int set_sk_epoch, unsigned sk_epoch) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g, ZG_ERR_ARG, "debug_gpt_age: null argument");
+    if (set_sk_epoch) g->sk_epoch = sk_epoch;
+    if (!g->tags_on && !g->fused_on) return ZG_OK;
+    hipStream_t s = gs(g);
+    ZG_TRY(note_steps(g, n_steps, s));
+    return launch_epoch_add(g->epoch, (unsigned)n_steps, s);
+}
+
+int zg_debug_gpt_age_state(zg_gpt* g, unsigned long long* out, size_t n_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && out && n_out >= ZG_AGE_STATE_WORDS, ZG_ERR_ARG, "debug_gpt_age_state: need %d words", ZG_AGE_STATE_WORDS);
+    ZG_HIP(hipStreamSynchronize(gs(g)));
+    unsigned epoch = 0;
+    ZG_HIP(hipMemcpy(&epoch, g->epoch, sizeof(unsigned), hipMemcpyDeviceToHost));
+    out[0] = epoch;
+    out[1] = g->epochs_since_clear;
+    out[2] = g->steps_counted;
+    out[3] = g->tag_clears;
+    out[4] = g->sk_epoch;
+    out[5] = g->sk_restarts;
+    return ZG_OK;
+}
+
+int zg_debug_gpt_tag_census(zg_gpt* g, unsigned epoch24, unsigned sk_flag_value, size_t* counts, size_t n_counts) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && counts && n_counts >= 4 && epoch24 < (1u << 24), ZG_ERR_ARG, "debug_gpt_tag_census: need 4 counts and a 24-bit epoch");
+    ZG_HIP(hipStreamSynchronize(gs(g)));
+    const unsigned long long* const words[3] = {g->sk_tag, g->part_tag, g->qkv_tag};
+    const size_t bytes[3] = {g->sk_tag_bytes, g->part_tag_bytes, g->qkv_tag_bytes};
+    std::vector<unsigned long long> h;
+    for (int i = 0; i < 3; ++i) {
+        h.resize(bytes[i] / 8);
+        ZG_HIP(hipMemcpy(h.data(), words[i], bytes[i], hipMemcpyDeviceToHost));
+        counts[i] = 0;
+        for (const unsigned long long w : h) {  // (value, tag): the tag is the upper word, epoch << 8 | launch id
+            const unsigned tag = (unsigned)(w >> 32);
+            if ((tag & 0xffu) != 0u && (tag >> 8) == epoch24) ++counts[i];
+        }
+    }
+    counts[3] = 0;
+    if (g->sk_flags != nullptr) {
+        unsigned f[kSkFlagWords];
+        ZG_HIP(hipMemcpy(f, g->sk_flags, sizeof(f), hipMemcpyDeviceToHost));
+        for (const unsigned w : f) counts[3] += w == sk_flag_value;
+    }
+    return ZG_OK;
 }
 
 int zg_debug_prefetch_stats(zg_gpt* g, unsigned* out, size_t n_out) {

@@ -223,12 +223,13 @@ int Call::finish() {
     // Op-tier calls are synchronous on return: the reference's host code reads the buffers next.  The host polls a pinned
     // completion word stored in stream order behind the call's work (cheaper than the runtime's wake-up); every 256th call —
     // and any call whose word does not arrive — drains the stream the ordinary way, which also surfaces asynchronous errors.
-    bool drained = false;
+    bool drained = false, polled = false;
     if (c.done_flag != nullptr && ++c.calls_since_sync < 256) {
         // (a reserved sequence number nobody announced is simply skipped: the next one is larger)
         const bool own = reserved_ && announced_;
         const unsigned seq = own ? reserved_seq_ : ++c.done_seq;
         const int st = own ? ZG_OK : fused ? launch_copy_out_done(segs, c.done_flag, seq, s_) : launch_done_flag(c.done_flag, seq, s_);
+        polled = st == ZG_OK;
         if (st == ZG_OK)
             for (long spins = 0; spins < (1L << 24) && !drained; ++spins) {
                 drained = __atomic_load_n(c.done_flag, __ATOMIC_ACQUIRE) == seq;
@@ -238,6 +239,7 @@ int Call::finish() {
             return st;  // (the outputs have not left: the call failed)
     }
     if (!drained) {
+        if (polled) ++c.done_missed;
         ZG_HIP(hipStreamSynchronize(s_));
         c.calls_since_sync = 0;
     }
@@ -632,6 +634,25 @@ int zg_debug_prefill_route(int force_kernel, int slices) {
 
 unsigned long long zg_debug_gemm_launches(void) { return gemm_mfma_launch_count(); }
 int zg_debug_gemm_stamps(unsigned long long* out, size_t n_words) { return gemm_debug_stamps(out, n_words); }
+// The op tier's completion word in front of its wrap / what became of it (tests; include/zgpt2.h).  The library stream is drained
+// first: no call is in flight whose number the word still has to take.
+int zg_debug_ops_set_done_seq(unsigned seq) {
+    ZG_TRY(require_init());
+    Ctx& c = ctx();
+    ZG_HIP(hipStreamSynchronize(c.stream));
+    c.done_seq = seq;
+    return ZG_OK;
+}
+int zg_debug_ops_done_state(unsigned long long* out, size_t n_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(out && n_out >= 3, ZG_ERR_ARG, "ops_done_state: need 3 words");
+    Ctx& c = ctx();
+    ZG_HIP(hipStreamSynchronize(c.stream));
+    out[0] = c.done_seq;
+    out[1] = c.done_flag ? __atomic_load_n(c.done_flag, __ATOMIC_ACQUIRE) : 0u;
+    out[2] = c.done_missed;
+    return ZG_OK;
+}
 int zg_debug_last_kernel(char* out, size_t n) {
     if (!out || n == 0) return ZG_ERR_ARG;
     snprintf(out, n, "%s", zg::g_kernel);

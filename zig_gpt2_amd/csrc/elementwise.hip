@@ -357,6 +357,12 @@ int launch_epoch_bump(unsigned* epoch, hipStream_t s) {
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }
+__global__ void epoch_add_kernel(unsigned* epoch, unsigned n) { *epoch += n; }
+int launch_epoch_add(unsigned* epoch, unsigned n, hipStream_t s) {
+    hipLaunchKernelGGL(epoch_add_kernel, dim3(1), dim3(1), 0, s, epoch, n);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
 
 int launch_embedding(const float* w, size_t emb_dim, const size_t* idx, size_t n_idx, size_t n_rows,
                      float* out, int* d_oob, hipStream_t s, unsigned* done_flag, unsigned done_seq, bool* announced) {

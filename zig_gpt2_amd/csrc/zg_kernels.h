@@ -192,6 +192,7 @@ int launch_attn_merge(const float* part, int batch, int n_heads, int head_dim, i
 
 // ------------------------------------------------------------------------------------ elementwise
 int launch_epoch_bump(unsigned* epoch, hipStream_t s);  // measurement chains: advance the tag epoch (api_gpt.hip zg_gpt_time_kernel)
+int launch_epoch_add(unsigned* epoch, unsigned n, hipStream_t s);  // tests: n steps at once (api_gpt.hip zg_debug_gpt_age)
 int launch_layernorm(float* x, int rows, int n, const float* g, const float* b, float eps, hipStream_t s, unsigned* done_flag = nullptr,
                      unsigned done_seq = 0, bool* announced = nullptr, float* shadow = nullptr);
 int launch_gelu(float* x, size_t n, hipStream_t s, unsigned* done_flag = nullptr, unsigned done_seq = 0, bool* announced = nullptr, float* shadow = nullptr);

@@ -49,6 +49,7 @@ struct Ctx {
     unsigned* done_flag = nullptr;  // pinned completion word of op-tier calls (d_flag + 8), its sequence number, calls since a real drain
     unsigned done_seq = 0;
     unsigned calls_since_sync = 0;
+    unsigned long long done_missed = 0;  // calls that polled to the end without seeing their number and drained the stream (zg_debug_ops_done_state)
     int* d_flag = nullptr;         // pinned host int the kernels raise for index-range checks (read after the call's drain)
     float* d_zero = nullptr;       // 64 zero bytes (stand-in operand for absent bias / residual)
     float* attn_part = nullptr;    // op-tier attention partials (sized at init)

@@ -181,6 +181,24 @@ class GPT:
         check(self._L.zg_debug_gpt_pass_taps(*head, ptr(arena), arena.size, C.byref(used), C.addressof(table), n.value, C.byref(n), ptr(info), info.size))
         return self._tap_list(arena, table, n.value), dict(zip(_lib.PASS_INFO, (int(v) for v in info))), logits
 
+    def age(self, n_steps=0, sk_epoch=None):
+        """zg_debug_gpt_age: as if n_steps decode steps that wrote no tagged slot had been enqueued and run (nothing on a handle
+        without tagged hand-overs); sk_epoch: the epoch the next stream-K launch of the whole-prompt pass continues from."""
+        check(self._L.zg_debug_gpt_age(self.h, int(n_steps), int(sk_epoch is not None), int(sk_epoch or 0) & 0xFFFFFFFF))
+
+    def age_state(self):
+        """zg_debug_gpt_age_state (drains the stream): dict by _lib.AGE_STATE."""
+        out = np.zeros(len(_lib.AGE_STATE), np.uint64)
+        check(self._L.zg_debug_gpt_age_state(self.h, ptr(out), out.size))
+        return dict(zip(_lib.AGE_STATE, (int(v) for v in out)))
+
+    def tag_census(self, epoch24, sk_flag_value=0):
+        """zg_debug_gpt_tag_census: how many tagged words carry epoch24 in their tag's epoch field, by array, and how many stream-K
+        flag words equal sk_flag_value: dict by _lib.TAG_CENSUS."""
+        out = np.zeros(len(_lib.TAG_CENSUS), np.uintp)
+        check(self._L.zg_debug_gpt_tag_census(self.h, int(epoch24), int(sk_flag_value), ptr(out), out.size))
+        return dict(zip(_lib.TAG_CENSUS, (int(v) for v in out)))
+
     def cached_len(self):
         """Positions the handle's caches hold (zg_gpt_cached_len)."""
         n = C.c_size_t()
