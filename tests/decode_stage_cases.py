@@ -2,7 +2,7 @@
 
 A case is one small model, one batch, one storage choice, one ZGPT2_DECODE_PATHS_OFF value and one position.  plan_case() mirrors
 zg_gpt_create's mode decisions (activation planes, tile statistics, tagged hand-overs, the fused batch-1 launch) from the plans
-zg_debug_gemv_plan returns for the arguments the *_args builders of api_gpt.hip lay out, and then plans the five Linear launches
+zg_debug_gemv_plan returns for the arguments the *_args builders of api_gpt_step.hip lay out, and then plans the five Linear launches
 of a step; test_decode_stages_gpu.py holds the handle's own report (zg_debug_gpt_step_taps info) to these predictions, so the
 coverage test_decode_stage_cases_cpu.py asserts on the CPU is the coverage the GPU test runs."""
 import ctypes as C
@@ -160,7 +160,7 @@ def t_hi_of(case):
 
 
 def launch_rows(case, pl, st, t_hi):
-    """The arguments of the five Linear launches of a step (api_gpt.hip *_args; base_gemv gives every launch the split-K
+    """The arguments of the five Linear launches of a step (api_gpt_step.hip *_args; base_gemv gives every launch the split-K
     workspace of n_embed / 16 tiles and the folded-LayerNorm vectors) as rows of zg_debug_gemv_plan, by launch class."""
     E, M, wt, skt = case.E, case.batch, WT[case.wt], (case.E + 15) // 16
     fed = SPLIT_K | (PLANES_IN if pl else 0)

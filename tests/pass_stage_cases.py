@@ -2,7 +2,7 @@
 
 A case is one small model, one batch, one storage choice, one route pin (zg_debug_prefill_route), one ZGPT2_GEMM_WGS value and one
 whole-prompt pass: n new positions behind past_len cached ones, plain or with the score stage.  plan_case() predicts every GEMM
-launch of the pass with zg_debug_prefill_plan from the arguments enqueue_prefill / enqueue_score of api_gpt.hip lay out, and the
+launch of the pass with zg_debug_prefill_plan from the arguments enqueue_prefill / enqueue_score of api_gpt_pass.hip lay out, and the
 attention's kernel and key-range geometry from launch_attn_prefill's rule; test_pass_stages_gpu.py holds the plans the tapped pass
 reports (zg_debug_gpt_pass_taps) to these predictions, so the coverage test_pass_stage_cases_cpu.py asserts on the CPU is the
 coverage the GPU test runs."""

@@ -19,7 +19,7 @@ M64 = (1 << 64) - 1
 
 
 def uniform(seed, seq_len, b):
-    """zg_gpt_sample's uniform for uniforms == NULL (csrc/api_gpt.hip): splitmix64 finaliser of (seed, seq_len, b), 24 random bits."""
+    """zg_gpt_sample's uniform for uniforms == NULL (csrc/api_gpt_generate.hip): splitmix64 finaliser of (seed, seq_len, b), 24 random bits."""
     z = (seed * 0x9E3779B97F4A7C15 + seq_len * 0xD1B54A32D192ED03 + b + 1) & M64
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64

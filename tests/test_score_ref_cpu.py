@@ -21,7 +21,7 @@ from zig_gpt2_amd import _lib, synth
 
 PF_F32, WS, WEIGHT_PLANES = 0, 1, 33
 T128, T128_WP = 2, 3
-R = 256  # kScoreRows of csrc/api_gpt.hip
+R = 256  # kScoreRows of csrc/api_gpt.h
 
 
 def test_every_position_is_a_distribution():

@@ -1,0 +1,693 @@
+// api_gpt_generate.hip — model tier of the C ABI: drawing tokens from a handle.  The per-token calls (sample_impl) and the
+// generation request, which exists once (every zg_gpt_generate*_enqueue fills a zg_generate_request, generate_request alone
+// makes the GenRequest gen_run runs); a whole generation is enqueued without a host round trip per token.
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "api_gpt.h"
+
+using namespace zg;
+
+namespace zg {  // offered to the other units: api_gpt.h declares them
+
+// top_n of the record the call in flight writes, through its pinned word into the arena: from here on a fetch finds that record
+int stage_top_n(zg_gpt* g, size_t top_n, hipStream_t s) {
+    g->lp_valid = true;
+    g->lp_top_n = top_n;
+    *g->h_lp_top = (int)top_n;
+    ZG_HIP(hipMemcpyAsync(g->lp_top, g->h_lp_top, sizeof(int), hipMemcpyHostToDevice, s));
+    return ZG_OK;
+}
+
+}  // namespace zg
+
+extern "C" {
+
+// The set built in edit_build through its pinned mirror into the arena.  PRECONDITION: nothing in flight reads the mirror (every
+// edited call drains, or begins by draining).
+static int stage_edits(zg_gpt* g, hipStream_t s) {
+    const size_t bytes = g->edit_build.size();
+    memcpy(g->h_edit, g->edit_build.data(), bytes);
+    ZG_HIP(hipMemcpyAsync(g->edit_tab, g->h_edit, bytes, hipMemcpyHostToDevice, s));
+    return ZG_OK;
+}
+
+// the counting kernel keeps a row's distinct tokens in an LDS table sized by the context
+static int check_pen_handle(const zg_gpt* g, const char* who) {
+    ZG_REQUIRE(g->cfg.context_size <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED, "%s: context_size %zu beyond the %d tokens the penalty kernel's LDS table holds",
+               who, g->cfg.context_size, kPenMaxHistory);
+    return ZG_OK;
+}
+
+// A caller's token lists for the penalties ([batch][stride], lens[b] each; tokens null: no lists): lengths within the stride and,
+// with `extra` more tokens to come from the loop's own record, within the context; tokens inside the vocabulary
+static int check_history(const zg_gpt* g, const size_t* tokens, size_t stride, const size_t* lens, size_t extra, const char* who) {
+    if (!tokens) {
+        for (size_t b = 0; lens && b < g->batch; ++b) ZG_REQUIRE(lens[b] == 0, ZG_ERR_ARG, "%s: row %zu lists %zu tokens but the lists are null", who, b, lens[b]);
+        return ZG_OK;
+    }
+    ZG_REQUIRE(lens != nullptr, ZG_ERR_ARG, "%s: token lists without their lengths", who);
+    const size_t C = g->cfg.context_size, V = g->cfg.vocab_size;
+    for (size_t b = 0; b < g->batch; ++b) {
+        ZG_REQUIRE(lens[b] <= stride && lens[b] <= C && lens[b] + extra <= C, ZG_ERR_SHAPE, "%s: row %zu lists %zu tokens (stride %zu, context %zu, %zu to come)",
+                   who, b, lens[b], stride, C, extra);
+        for (size_t i = 0; i < lens[b]; ++i)
+            ZG_REQUIRE(tokens[b * stride + i] < V, ZG_ERR_SHAPE, "%s: token %zu >= vocab %zu", who, tokens[b * stride + i], V);
+    }
+    return ZG_OK;
+}
+
+// The penalties of the call and its token lists (checked) through their pinned mirrors into the arena.  PRECONDITION: nothing in
+// flight reads the mirrors (every penalised call drains, or begins by draining).
+static int stage_penalties(zg_gpt* g, const zg_logit_penalties& p, size_t past, const size_t* tokens, size_t stride, const size_t* lens, hipStream_t s) {
+    const size_t C = g->cfg.context_size, B = g->batch;
+    *g->h_pen = PenParams{p.repetition, p.presence, p.frequency, (int)past};
+    int* h_len = g->h_prior + B * C;
+    for (size_t b = 0; b < B; ++b) {
+        h_len[b] = tokens ? (int)lens[b] : 0;
+        for (size_t i = 0; tokens && i < lens[b]; ++i) g->h_prior[b * C + i] = (int)tokens[b * stride + i];
+    }
+    ZG_HIP(hipMemcpyAsync(g->pen, g->h_pen, sizeof(PenParams), hipMemcpyHostToDevice, s));
+    if (tokens) ZG_HIP(hipMemcpyAsync(g->prior, g->h_prior, B * C * sizeof(int), hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(g->prior_len, h_len, B * sizeof(int), hipMemcpyHostToDevice, s));
+    return ZG_OK;
+}
+
+// GPT.sample (main.zig:198-207) behind one forward step: the checked body of the per-token family — zg_gpt_sample_edit's, under the
+// name of the entry point that calls it; each entry point keeps in front what it is stricter about.  penalties null: none, the
+// history is not read; an entry point without edits passes kNoEdits.  Everything the chain reads is staged first: the chain only launches.
+static const zg_logit_edits kNoEdits{};
+static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
+                       const size_t* history, size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits, const float* uniforms,
+                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len, const char* who) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, who));
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null handle", who);
+    if (pen) {
+        ZG_TRY(check_penalties(pen, who));
+        ZG_TRY(check_pen_handle(g, who));
+        ZG_TRY(check_history(g, history, history_stride, history_lens, 0, who));
+    }
+    bool edit_on = false;
+    ZG_TRY(build_edits(edits, g->cfg.vocab_size, who, g->edit_build.data(), &edit_on));
+    const bool pen_on = pen && !penalties_off(*pen);
+    if (pen_on || edit_on) ZG_HIP(hipStreamSynchronize(gs(g)));  // (an enqueued generation may still be reading the pinned mirrors; idle otherwise)
+    ZG_REQUIRE(tokens && tokens_out, ZG_ERR_ARG, "gpt_sample: bad argument");
+    const size_t V = g->cfg.vocab_size, B = g->batch;
+    ZG_REQUIRE(!probs_out || probs_len >= B * V, ZG_ERR_SHAPE, "gpt_sample: probs_out needs %zu elements", B * V);
+    for (size_t b = 0; uniforms && b < B; ++b)  // (checked before anything is enqueued)
+        ZG_REQUIRE(uniforms[b] >= 0.0f && uniforms[b] < 1.0f, ZG_ERR_ARG, "gpt_sample: uniform %f outside [0,1)", uniforms[b]);
+    ZG_TRY(forward_enqueue(g, seq_len, tokens, n_tokens, 1, nullptr, 0));  // main.zig:199 (not drained: the sampler goes behind it)
+    hipStream_t s = gs(g);
+    if (pen_on) ZG_TRY(stage_penalties(g, *pen, 0, history, history_stride, history_lens, s));
+    if (edit_on) ZG_TRY(stage_edits(g, s));
+    // (pinned, 320 bytes into the control block: h_ints[0 .. B) is still being read by the forward's token upload)
+    float* h_u = reinterpret_cast<float*>(reinterpret_cast<char*>(g->h_ctrl) + 320);
+    // (no uniforms: the counter PRNG the device loop's sampler draws from, zg_common.h)
+    for (size_t b = 0; b < B; ++b) h_u[b] = uniforms ? uniforms[b] : counter_uniform(seed, seq_len, b);
+    SamplerChain c = handle_chain(g, false);
+    float* d_u = g->q;  // scratch: q is dead after the forward
+    ZG_HIP(hipMemcpyAsync(d_u, h_u, B * sizeof(float), hipMemcpyHostToDevice, s));
+    // (h_samp: nothing in flight reads it, forward_enqueue's callers drain; the plain sampler takes its temperature by value)
+    const SamplerMode mode = fill_sample_params(g->h_samp, V, *opt, seed, edits->min_p);
+    if (threshold_sampler(mode)) ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
+    c.u = d_u, c.temp = opt->temp, c.write_probs = probs_out != nullptr, c.pick = g->cur_token;
+    ZG_TRY(emit_sampler_chain(c, StepTail{mode, pen_on, false, false, edit_on}, s));  // main.zig:200-206
+    ZG_HIP(hipMemcpyAsync(g->h_ints + B, g->cur_token, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (probs_out) ZG_TRY(copy_out_f32(probs_out, g->logits, B * V, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    for (size_t b = 0; b < B; ++b) tokens_out[b] = (size_t)g->h_ints[B + b];
+    return ZG_OK;
+}
+
+int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, const float* uniforms,
+                  uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "gpt_sample: bad argument");
+    const zg_sample_options plain{temp, 0, 1.0f};
+    return sample_impl(g, seq_len, tokens, n_tokens, &plain, nullptr, nullptr, 0, nullptr, &kNoEdits, uniforms, seed, tokens_out, probs_out, probs_len,
+                       "gpt_sample");
+}
+
+// zg_gpt_sample behind top-k / nucleus truncation (filters off: exactly zg_gpt_sample's launches)
+int zg_gpt_sample_ex(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const float* uniforms,
+                     uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
+    return sample_impl(g, seq_len, tokens, n_tokens, opt, nullptr, nullptr, 0, nullptr, &kNoEdits, uniforms, seed, tokens_out, probs_out, probs_len,
+                       "gpt_sample_ex");
+}
+
+// ... with the penalty stage in front, on the caller's history: here the penalties are required
+int zg_gpt_sample_pen(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
+                      const size_t* history, size_t history_stride, const size_t* history_lens, const float* uniforms, uint64_t seed, size_t* tokens_out,
+                      float* probs_out, size_t probs_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(pen != nullptr, ZG_ERR_ARG, "gpt_sample_pen: penalties is null");
+    return sample_impl(g, seq_len, tokens, n_tokens, opt, pen, history, history_stride, history_lens, &kNoEdits, uniforms, seed, tokens_out, probs_out,
+                       probs_len, "gpt_sample_pen");
+}
+
+// ... and with the edit stage behind the penalties and min-p in the sampler: here the edits are required
+int zg_gpt_sample_edit(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
+                       const size_t* history, size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits, const float* uniforms,
+                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
+    return sample_impl(g, seq_len, tokens, n_tokens, opt, pen, history, history_stride, history_lens, edits, uniforms, seed, tokens_out, probs_out,
+                       probs_len, "gpt_sample_edit");
+}
+
+// A generation in three parts, so that several handles' generations can be fed to their streams side by side
+// (zg_gpt_generate_enqueue_many): gen_begin — prompts, cache clearing, the whole-prompt pass, the prefetcher's start;
+// gen_pump — ONE graph launch (graph_steps decode steps) or one single step, false when nothing is left; gen_end — the
+// prefetcher's stop word and the record of the last pick.  After a successful gen_begin, gen_end must run (also on failure:
+// the prefetcher must not wait for steps that never come).  A generation with stop conditions is the same three parts:
+// gen_pump paces itself by the stop stage's progress word and feeds nothing once every row has finished (stop_pace), and gen_end
+// sets the handle's lengths to the column actually reached.
+// past > 0 (zg_gpt_generate_from_enqueue): the loop is entered at s = past — `prompts` are the new tokens of each row, device
+// prompt[b][past + i], prompt_len[b] = past + prompt_lens[b]; everything the embed kernel and gen_pump compare is absolute, so the
+// steps are the ones an uninterrupted generation would run at these positions.  The caches keep rows 0 .. past - 1 and the
+// recorded tokens of positions below past stay where they are (zg_gpt_generate_fetch_range).
+
+// What a generation is asked for, checked: what generate_request makes of a zg_generate_request for gen_begin
+struct GenRequest {
+    const size_t* prompts;  // [rows][stride], lens[rows] tokens each
+    size_t stride;
+    const size_t* lens;
+    size_t n_steps, past;
+    SamplerMode mode;       // GREEDY (opt unused), or PLAIN: draw with opt — gen_begin raises it to the filters opt switches on
+    zg_sample_options opt;
+    uint64_t seed;
+    // penalties (a sampler only; pen_on false: none, the request is what it was without them) and the caller's prior of every row of
+    // the ONE handle such a request goes to: [rows][prior_stride], prior_lens[rows] tokens each, or null
+    bool pen_on = false;
+    zg_logit_penalties pen{1.0f, 0.0f, 0.0f};
+    const size_t* prior = nullptr;
+    size_t prior_stride = 0;
+    const size_t* prior_lens = nullptr;
+    // the log-probability stage behind every pick with top_n alternatives; lp_on false: the request is what it was
+    bool lp_on = false;
+    size_t top_n = 0;
+    // stop conditions, checked (check_stop); stop_on false: the request is what it was
+    bool stop_on = false;
+    zg_stop_conditions stop{};
+    // logit edits, checked, the set built in the ONE handle's edit_build: edit_on — the
+    // edit stage runs; min_p — the sampler's threshold (0: off).  Both off: the request is what it was
+    bool edit_on = false;
+    float min_p = 0.0f;
+    GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, const zg_sample_options* opt_or_null = nullptr, uint64_t seed = 0,
+               size_t past = 0)
+        : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past), mode(opt_or_null ? PLAIN : GREEDY),
+          opt(opt_or_null ? *opt_or_null : zg_sample_options{1.0f, 0, 1.0f}), seed(seed) {}
+};
+
+// Steps the host may be ahead of the stop stage's progress word before it feeds the next piece, where the caller names none:
+// the smallest value whose rate is inside the run-to-run spread of an unpaced loop (tools/bench_stop.py)
+constexpr size_t kStopLookahead = 16;
+
+static int gen_begin(zg_gpt* g, const GenRequest& r) {
+    const size_t n_steps = r.n_steps, past = r.past;
+    ZG_REQUIRE(g && r.prompts && r.lens, ZG_ERR_ARG, "generate: null argument");
+    const size_t C = g->cfg.context_size, V = g->cfg.vocab_size, B = g->batch;
+    ZG_REQUIRE(past <= g->cached_len, ZG_ERR_ARG, "generate: past_len %zu beyond the %zu cached positions", past, g->cached_len);
+    ZG_REQUIRE(n_steps >= 1 && past + n_steps <= C, ZG_ERR_SHAPE, "generate: n_steps %zu outside 1..%zu", n_steps, C - past);
+    for (size_t b = 0; b < B; ++b) {  // (everything is checked before the handle's state is touched)
+        const size_t np = r.lens[b];
+        ZG_REQUIRE(np >= 1 && past + np <= C && np <= r.stride, ZG_ERR_SHAPE, "generate: prompt %zu has length %zu", b, np);
+        for (size_t i = 0; i < np; ++i)
+            ZG_REQUIRE(r.prompts[b * r.stride + i] < V, ZG_ERR_SHAPE, "generate: token %zu >= vocab %zu", r.prompts[b * r.stride + i], V);
+    }
+    const bool pen_on = r.pen_on && r.mode != GREEDY;
+    if (pen_on) {  // (a row's history, prior and recorded, never exceeds the context: the kernel's table is sized by it)
+        ZG_TRY(check_pen_handle(g, "generate_pen"));
+        ZG_TRY(check_history(g, r.prior, r.prior_stride, r.prior_lens, n_steps, "generate_pen"));
+    }
+    if (r.lp_on) {
+        ZG_TRY(check_top_n(r.top_n, V, "generate_logprobs"));
+        ZG_REQUIRE(V <= (size_t)64 * 4096, ZG_ERR_UNSUPPORTED, "generate_logprobs: vocabulary of %zu beyond %d", V, 64 * 4096);
+    }
+    hipStream_t s = gs(g);
+    ZG_HIP(hipStreamSynchronize(s));  // pinned staging below is shared with earlier calls
+    size_t min_prompt = C;
+    memset(g->h_ints, 0, (B * C + B) * sizeof(int));
+    for (size_t b = 0; b < B; ++b) {
+        const size_t np = r.lens[b];
+        for (size_t i = 0; i < np; ++i) g->h_ints[b * C + past + i] = (int)r.prompts[b * r.stride + i];
+        g->h_ints[B * C + b] = (int)(past + np);
+        if (np < min_prompt) min_prompt = np;
+    }
+    // The positions every sequence has a prompt token for go through the Blocks together (prefill); the
+    // rest of the loop is main.zig:330-338 one position at a time.
+    size_t first = 0;
+    if (g->pf_x != nullptr && min_prompt >= prefill_min())
+        first = min_prompt < n_steps ? min_prompt : n_steps;
+    const bool edit_on = r.edit_on && r.mode != GREEDY;
+    g->gen_tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on, edit_on};  // (normalized: pen_on / edit_on only with a sampler, and the steps it is for have lm_head)
+    g->stop_valid = false;
+    g->gen_stop = r.stop_on;
+    if (r.stop_on) {  // the conditions of this call; no row has finished; the stage has seen nothing (the stream is drained: the words are the host's)
+        fill_stop(&g->h_stop->conds, r.stop);
+        ZG_HIP(hipMemcpyAsync(g->stop, &g->h_stop->conds, sizeof(StopConds), hipMemcpyHostToDevice, s));
+        ZG_HIP(hipMemsetAsync(g->stop_fin, 0xff, kStopMaxRows * 4, s));
+        ZG_HIP(hipMemsetAsync(g->stop_reason, 0xff, kStopMaxRows * 4, s));
+        g->h_stop->host.progress = g->h_stop->host.done_col = 0u;
+        g->gen_lookahead = r.stop.lookahead ? std::min(r.stop.lookahead, C) : kStopLookahead;  // (beyond the context: never waits)
+    }
+    if (r.mode != GREEDY) {
+        g->gen_tail.sampler = fill_sample_params(g->h_samp, V, r.opt, r.seed, r.min_p);
+        ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
+    }
+    if (pen_on) ZG_TRY(stage_penalties(g, r.pen, past, r.prior, r.prior_stride, r.prior_lens, s));
+    if (edit_on) ZG_TRY(stage_edits(g, s));
+    g->lp_valid = false;
+    if (r.lp_on) {
+        ZG_TRY(stage_top_n(g, r.top_n, s));
+        // the new columns no step with lm_head reaches (the whole-prompt pass, steps that only feed a prompt token) record prompt
+        // tokens: NaN (every byte 0xff); the stage itself writes the NaN of a longer row's prompt columns
+        const size_t fed = std::min(min_prompt, n_steps);
+        ZG_HIP(hipMemset2DAsync(g->lp_rec.logprob + past, C * sizeof(float), 0xff, fed * sizeof(float), B, s));
+    }
+    ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(g->prompt_len, g->h_ints + B * C, B * sizeof(int), hipMemcpyHostToDevice, s));
+    ZG_TRY(stage_ctrl(g, past + first, past + first, r.mode != GREEDY ? 2 : 0, s));
+    ZG_TRY(clear_for_pass(g, s, past, past + first));
+    g->cached_len = g->kv_dirty_hi = past + n_steps;  // the last position the loop feeds
+    ZG_TRY(ensure_ln_folded(g, s));
+    if (first > 0) {
+        if (past == 0) ZG_HIP(hipMemcpyAsync(g->out_tokens, g->prompt, B * C * sizeof(int), hipMemcpyDeviceToDevice, s));
+        else  // only the new columns: the tokens recorded below past stay
+            ZG_HIP(hipMemcpy2DAsync(g->out_tokens + past, C * sizeof(int), g->prompt + past, C * sizeof(int), first * sizeof(int), B, hipMemcpyDeviceToDevice, s));
+        ZG_TRY(enqueue_prefill(g, past, first, false, s));
+    }
+    // Every graph the loop will replay exists before the prefetcher starts its idle clock (a capture between the steps would run
+    // against it): all of create's on a stream create did not see, and this generation's own tail — whatever create did not
+    // capture of it (graph_exec skips what exists) — for the buckets of its steps with lm_head
+    if (!(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr) {
+        if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
+        if (!(g->gen_tail == StepTail{}) && min_prompt < n_steps)
+            ZG_TRY(capture_tail(g, g->gen_tail, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
+    }
+    ZG_TRY(note_steps(g, n_steps, s));
+    ZG_TRY(pf_start(g, past + n_steps, s));
+    g->gen_pos = past + first;  // absolute, as gen_n and gen_min_prompt: gen_pump's steps, buckets and graph alignment follow the position
+    g->gen_n = past + n_steps;
+    g->gen_min_prompt = past + min_prompt;
+    g->gen_since_sync = 0;
+    g->gen_open = true;
+    return ZG_OK;
+}
+
+// A stop generation before each piece it feeds: *ended when every row has finished — nothing more is fed —, else
+// wait while the host is more than gen_lookahead steps ahead of the stop stage.  The stage counts steps with lm_head only, so the
+// steps below gen_min_prompt (the default tail) are not paced over.  progress is read BEFORE done_col and the kernel stores them
+// the other way round: a done_col still 0 then means that the finishing step had not announced itself when progress was read, which
+// is what bounds `end`.  The wait is bounded by the device's state, not by a count: whenever the word has stood still over 16 polls
+// the stream is asked, and a drained or failed stream ends the wait — a faulted device ends the call instead of spinning the host.
+static int stop_pace(zg_gpt* g, hipStream_t s, bool* ended) {
+    StopHost* const h = &g->h_stop->host;
+    *ended = false;
+    unsigned seen = ~0u;  // progress at the last look at the stream
+    for (unsigned polls = 0;; ++polls) {
+        const unsigned p = __atomic_load_n(&h->progress, __ATOMIC_ACQUIRE);
+        const unsigned d = __atomic_load_n(&h->done_col, __ATOMIC_ACQUIRE);
+        if (d != 0u) {
+            *ended = true;
+            return ZG_OK;
+        }
+        if (g->gen_pos <= std::max((size_t)p, g->gen_min_prompt) + g->gen_lookahead) return ZG_OK;
+        if (polls < 64) continue;  // (a short wait costs no system call)
+        if (polls % 16 == 0) {  // the stream is asked only while the word stands still: a healthy device moves it every step
+            if (p == seen) {
+                const hipError_t q = hipStreamQuery(s);
+                if (q != hipErrorNotReady) {
+                    if (q != hipSuccess) return hip_fail(q, "hipStreamQuery(stop generation)", __FILE__, __LINE__);
+                    if (__atomic_load_n(&h->progress, __ATOMIC_ACQUIRE) == p) return ZG_OK;  // drained and nothing moved: nothing will
+                }
+            }
+            seen = p;
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+}
+
+static int gen_pump(zg_gpt* g, bool* more) {
+    hipStream_t s = gs(g);
+    const size_t C = g->cfg.context_size, n_steps = g->gen_n, st = g->gen_pos;
+    *more = false;
+    if (st >= n_steps) return ZG_OK;
+    if (g->gen_stop && st > g->gen_min_prompt) {  // (behind the first step with lm_head: nothing can have finished before)
+        bool ended = false;
+        ZG_TRY(stop_pace(g, s, &ended));
+        if (ended) return ZG_OK;
+    }
+    const size_t K = ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) ? 1 : g->graph_steps;
+    // ZGPT2_SYNC_EVERY=n (profiling only): drain the stream every n steps — rocprofv3's counter collection has crashed
+    // on this stack when tens of thousands of dispatches were queued ahead of it
+    static const int sync_every = env_int("ZGPT2_SYNC_EVERY", 0);
+    if (sync_every > 0 && ++g->gen_since_sync >= (size_t)sync_every) {
+        g->gen_since_sync = 0;
+        (void)hipStreamSynchronize(s);
+    }
+    if (K > 1 && st >= g->gen_min_prompt && st % K == 0 && st + K <= n_steps && st + K <= C) {
+        if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
+        hipGraphExec_t e;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64); captured by gen_begin (first use: the backstop)
+        ZG_TRY(graph_exec(g, {true, true, g->gen_tail}, bucket_of(st + 1), s, &e));
+        ZG_HIP(hipGraphLaunch(e, s));
+        g->gen_pos = st + K;
+    } else {
+        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_tail));
+        g->gen_pos = st + 1;
+    }
+    *more = g->gen_pos < n_steps;
+    return ZG_OK;
+}
+
+// gen_pump until nothing is left or it fails
+static int gen_pump_all(zg_gpt* g) {
+    int rs = ZG_OK;
+    for (bool more = true; more && rs == ZG_OK;) rs = gen_pump(g, &more);
+    return rs;
+}
+
+static int gen_end(zg_gpt* g, int rs) {
+    hipStream_t s = gs(g);
+    g->gen_open = false;
+    ZG_TRY(pf_stop(g, s));  // also after a failed launch: the prefetcher must not wait for steps that never come
+    ZG_TRY(rs);
+    ZG_TRY(launch_embed_step(embed_args(g, 1), s));  // record the pick of the last step
+    if (g->gen_stop) {  // the column actually reached: the one place that corrects what gen_begin set up front
+        g->gen_n = g->cached_len = g->kv_dirty_hi = g->stop_end = g->gen_pos;
+        g->stop_valid = true;
+    }
+    g->steps_enqueued = g->gen_n;
+    return ZG_OK;
+}
+
+// One request for the rows of n handles, handle by handle: gen_begin for each, the pumps side by side, gen_end for each that began.
+// Several handles: every handle decodes its own prompts on its own stream and the chip overlaps the chains, each of which leaves
+// it idle across every one of its launch boundaries.  The handles are fed side by side: a hardware queue holds a fraction of a
+// generation's dispatches, and a host that fed one handle to the end first would block on that queue while the others idle.
+static int gen_run(zg_gpt* const* handles, size_t n_handles, GenRequest req) {
+    size_t begun = 0;
+    int rs = ZG_OK;
+    for (; begun < n_handles && rs == ZG_OK; ++begun) {
+        rs = gen_begin(handles[begun], req);
+        if (rs != ZG_OK) break;  // (its message is picked up below)
+        req.prompts += handles[begun]->batch * req.stride;
+        req.lens += handles[begun]->batch;
+    }
+    char msg[512] = "";
+    if (rs == ZG_OK && begun > 1) {
+        // one feeder thread per handle: a hipGraphLaunch returns only when its hardware queue has room for the graph's
+        // dispatches, so one thread feeding all queues in turn stands still whenever the slowest chain's queue is full
+        std::vector<std::thread> th;
+        std::vector<int> res(begun, ZG_OK);
+        std::vector<std::string> errs(begun);
+        const int dev = ctx().device;
+        for (size_t i = 0; i < begun; ++i)
+            th.emplace_back([&, i]() {
+                res[i] = hipSetDevice(dev) == hipSuccess ? gen_pump_all(handles[i]) : ZG_ERR_HIP;
+                if (res[i] != ZG_OK) errs[i] = zg_last_error();  // (the message is thread-local)
+            });
+        for (auto& t : th) t.join();
+        for (size_t i = 0; i < begun && rs == ZG_OK; ++i)
+            if (res[i] != ZG_OK) {
+                rs = res[i];
+                snprintf(msg, sizeof msg, "%s", errs[i].c_str());
+            }
+    } else {  // one handle: the calling thread pumps
+        if (rs == ZG_OK) rs = gen_pump_all(handles[0]);
+        if (rs != ZG_OK) snprintf(msg, sizeof msg, "%s", zg_last_error());
+    }
+    int first_err = rs;
+    for (size_t i = 0; i < begun; ++i) {
+        const int e = gen_end(handles[i], rs);
+        if (first_err == ZG_OK && e != ZG_OK) {
+            first_err = e;
+            snprintf(msg, sizeof msg, "%s", zg_last_error());
+        }
+    }
+    if (first_err != ZG_OK) set_error("%s", msg);
+    return first_err;
+}
+
+// Everything of the generate family in one place: the one builder of a GenRequest, for every zg_gpt_generate*_enqueue entry point
+// under its own name.  Each stage is a node of graphs of their own, its values in device memory: the selection launches in front of
+// the sampler node (StepTail.sampler; filters off: the plain sampler's graphs), the penalty stage (StepTail.pen), the
+// log-probability stage behind the sampler node, or behind lm_head of a greedy step (StepTail.lp; it only reads, so
+// the tokens are those of the call without it), the stop stage last (StepTail.stop), the edit stage between the
+// penalties and the sampler (StepTail.edit; min-p is the sampler's: SampleParams.min_p_off, alone MINP_ONLY).  A
+// stage whose argument is null or all off leaves the request what it was without it.  Penalties, conditions and edits go to ONE
+// handle, the first (zg_gpt_generate_enqueue_many has none of them).
+static int generate_request(zg_gpt* const* handles, size_t n_handles, const zg_generate_request& q, const char* who) {
+    ZG_TRY(require_init());
+    zg_gpt* const g = handles[0];
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null argument", who);
+    if (q.options) ZG_TRY(check_sample_options(q.options, who));
+    ZG_REQUIRE(q.options || !q.penalties, ZG_ERR_ARG, "%s: penalties without sampler options (greedy picking with penalties is top_k = 1)", who);
+    GenRequest r(q.prompts, q.prompt_stride, q.prompt_lens, q.n_steps, q.options, q.seed, q.past_len);
+    if (q.logprobs) {
+        r.lp_on = true;
+        r.top_n = q.top_n;
+    }
+    if (q.penalties) {
+        ZG_TRY(check_penalties(q.penalties, who));
+        if (!penalties_off(*q.penalties)) {
+            r.pen_on = true;
+            r.pen = *q.penalties;
+            r.prior = q.prior;
+            r.prior_stride = q.prior_stride;
+            r.prior_lens = q.prior_lens;
+        } else {  // all off: the request stays what it was without them, but the lists are still the caller's to get right
+            ZG_TRY(check_pen_handle(g, who));
+            ZG_TRY(check_history(g, q.prior, q.prior_stride, q.prior_lens, 0, who));
+        }
+    }
+    if (q.stop && (q.stop->n_ids || q.stop->n_seqs)) {
+        ZG_REQUIRE(g->batch <= (size_t)kStopMaxRows, ZG_ERR_UNSUPPORTED, "%s: batch %zu above %d", who, g->batch, kStopMaxRows);
+        ZG_TRY(check_stop(q.stop, g->cfg.vocab_size, who));
+        r.stop_on = true;
+        r.stop = *q.stop;
+    }
+    if (q.edits) {
+        ZG_TRY(build_edits(q.edits, g->cfg.vocab_size, who, g->edit_build.data(), &r.edit_on));
+        ZG_REQUIRE(q.options || edits_off(*q.edits), ZG_ERR_ARG, "%s: edits without sampler options (greedy picking with edits is top_k = 1)", who);
+        r.min_p = q.edits->min_p;
+    }
+    return gen_run(handles, n_handles, r);
+}
+
+// The positional arguments of the entry points as a request; what an entry point does not name is null / 0
+static zg_generate_request request_of(size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                      const zg_sample_options* opt = nullptr, uint64_t seed = 0, const zg_logit_penalties* pen = nullptr,
+                                      const size_t* prior = nullptr, size_t prior_stride = 0, const size_t* prior_lens = nullptr, int logprobs = 0,
+                                      size_t top_n = 0, const zg_stop_conditions* stop = nullptr) {
+    return zg_generate_request{sizeof(zg_generate_request), past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, pen, prior, prior_stride, prior_lens, seed,
+                               logprobs, top_n, stop, nullptr};  // (the fields in the header's order)
+}
+
+int zg_gpt_generate_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps) {
+    return generate_request(&g, 1, request_of(0, prompts, prompt_stride, prompt_lens, n_steps), "generate");
+}
+
+// generate (src/main.zig:322-342) AS THE REFERENCE RUNS IT: every token behind the prompt is drawn by GPT.sample
+// (main.zig:198-207, :336-338) — softmax(logits / temp), then the first index whose running sum exceeds u x total — with the
+// whole loop on the device: the sampler is a node of the captured decode step (sample_step_kernel) and the next step's embed
+// kernel feeds its draw.  The uniform of (sequence b, position T) is the counter PRNG of (seed, T, b) that zg_gpt_sample uses when
+// it is given no uniforms, so this call returns exactly the tokens of a host loop `tok = zg_gpt_sample(g, T, tok, temp, NULL,
+// seed, ...)` — without a host round trip per token.  Results through zg_gpt_generate_fetch.
+int zg_gpt_generate_sample_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                   float temp, uint64_t seed) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "generate_sample: temperature %f", temp);
+    const zg_sample_options plain{temp, 0, 1.0f};
+    return generate_request(&g, 1, request_of(0, prompts, prompt_stride, prompt_lens, n_steps, &plain, seed), "generate_sample");
+}
+
+int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps, float temp,
+                           uint64_t seed, size_t* out_tokens, size_t out_len) {
+    ZG_REQUIRE(g && out_tokens && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_sample: out_tokens too short");
+    ZG_TRY(zg_gpt_generate_sample_enqueue(g, prompts, prompt_stride, prompt_lens, n_steps, temp, seed));
+    return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
+}
+
+// The same behind top-k / nucleus truncation (include/zgpt2.h zg_sample_options; sample_filter.h); here the options are required
+int zg_gpt_generate_sample_ex_enqueue(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                      const zg_sample_options* opt, uint64_t seed) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(opt != nullptr, ZG_ERR_ARG, "generate_sample_ex: options is null");
+    return generate_request(&g, 1, request_of(0, prompts, prompt_stride, prompt_lens, n_steps, opt, seed), "generate_sample_ex");
+}
+
+int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                              const zg_sample_options* opt, uint64_t seed, size_t* out_tokens, size_t out_len) {
+    ZG_REQUIRE(g && out_tokens && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_sample_ex: out_tokens too short");
+    ZG_TRY(zg_gpt_generate_sample_ex_enqueue(g, prompts, prompt_stride, prompt_lens, n_steps, opt, seed));
+    return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
+}
+
+// generate entered at s = past_len: the decode loop's own graphs at the absolute positions, the shortest new length
+// through the whole-prompt pass first where the handle has one.  options null: greedy.
+int zg_gpt_generate_from_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                 const zg_sample_options* opt, uint64_t seed) {
+    return generate_request(&g, 1, request_of(past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, seed), "generate_from");
+}
+
+// zg_gpt_generate_from_enqueue with penalties; here options and penalties are required
+int zg_gpt_generate_pen_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
+                                const size_t* prior_lens, uint64_t seed) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(opt != nullptr && pen != nullptr, ZG_ERR_ARG, "generate_pen: options or penalties is null");
+    return generate_request(&g, 1, request_of(past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, seed, pen, prior, prior_stride, prior_lens),
+                            "generate_pen");
+}
+
+int zg_gpt_generate_logprobs_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                     const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
+                                     const size_t* prior_lens, uint64_t seed, size_t top_n) {
+    return generate_request(&g, 1, request_of(past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, seed, pen, prior, prior_stride, prior_lens, 1, top_n),
+                            "generate_logprobs");
+}
+
+int zg_gpt_generate_stop_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps,
+                                 const zg_sample_options* opt, const zg_logit_penalties* pen, const size_t* prior, size_t prior_stride,
+                                 const size_t* prior_lens, uint64_t seed, int logprobs, size_t top_n, const zg_stop_conditions* stop) {
+    return generate_request(
+        &g, 1, request_of(past_len, prompts, prompt_stride, prompt_lens, n_steps, opt, seed, pen, prior, prior_stride, prior_lens, logprobs, top_n, stop),
+        "generate_stop");
+}
+
+int zg_gpt_generate_request_enqueue(zg_gpt* g, const zg_generate_request* r) {
+    ZG_REQUIRE(r != nullptr && r->size == sizeof(zg_generate_request), ZG_ERR_ARG, "generate_request: null request, or its size field is not sizeof(zg_generate_request)");
+    return generate_request(&g, 1, *r, "generate_request");
+}
+
+int zg_gpt_generate_stop_result(zg_gpt* g, size_t* end_out, size_t* finish_cols_out, int* reasons_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && end_out && finish_cols_out && reasons_out, ZG_ERR_ARG, "generate_stop_result: null argument");
+    ZG_REQUIRE(g->stop_valid, ZG_ERR_ARG, "generate_stop_result: the last generation had no stop conditions");
+    hipStream_t s = gs(g);
+    ZG_HIP(hipMemcpyAsync(g->h_stop->fin, g->stop_fin, g->batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(g->h_stop->reason, g->stop_reason, g->batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    *end_out = g->stop_end;
+    for (size_t b = 0; b < g->batch; ++b) {
+        const int f = g->h_stop->fin[b];
+        finish_cols_out[b] = f < 0 ? ZG_STOP_NONE : (size_t)f;
+        reasons_out[b] = f < 0 ? -1 : g->h_stop->reason[b];
+    }
+    return ZG_OK;
+}
+
+int zg_gpt_generate_fetch_logprobs(zg_gpt* g, size_t first, size_t n, size_t top_n, float* logprobs_out, size_t logprobs_len, size_t* top_ids_out,
+                                   float* top_logprobs_out, size_t top_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && logprobs_out, ZG_ERR_ARG, "generate_fetch_logprobs: null argument");
+    const size_t C = g->cfg.context_size, B = g->batch, K = ZG_LOGPROBS_TOP_MAX;
+    ZG_REQUIRE(g->lp_valid, ZG_ERR_ARG, "generate_fetch_logprobs: the last generation recorded no log-probabilities");
+    ZG_REQUIRE(top_n <= g->lp_top_n, ZG_ERR_ARG, "generate_fetch_logprobs: top_n %zu above the %zu the generation recorded", top_n, g->lp_top_n);
+    ZG_REQUIRE(top_n == 0 || (top_ids_out && top_logprobs_out), ZG_ERR_ARG, "generate_fetch_logprobs: top_n %zu without its outputs", top_n);
+    ZG_REQUIRE(first <= C && n <= C - first && logprobs_len >= B * n && (top_n == 0 || top_len >= B * n * top_n), ZG_ERR_SHAPE,
+               "generate_fetch_logprobs: positions %zu .. %zu of %zu, %zu and %zu elements", first, first + n, C, logprobs_len, top_len);
+    if (n == 0) return ZG_OK;
+    hipStream_t s = gs(g);
+    float* h_lp = g->h_lp;
+    int* h_ids = reinterpret_cast<int*>(g->h_lp + B * C);
+    float* h_top = g->h_lp + B * C * (1 + K);
+    // the columns asked for, packed [batch][n] and [batch][n][20]
+    ZG_HIP(hipMemcpy2DAsync(h_lp, n * 4, g->lp_rec.logprob + first, C * 4, n * 4, B, hipMemcpyDeviceToHost, s));
+    if (top_n) {
+        ZG_HIP(hipMemcpy2DAsync(h_ids, n * K * 4, g->lp_rec.top_ids + first * K, C * K * 4, n * K * 4, B, hipMemcpyDeviceToHost, s));
+        ZG_HIP(hipMemcpy2DAsync(h_top, n * K * 4, g->lp_rec.top_logprobs + first * K, C * K * 4, n * K * 4, B, hipMemcpyDeviceToHost, s));
+    }
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    memcpy(logprobs_out, h_lp, B * n * sizeof(float));
+    unpack_top(h_ids, h_top, B * n, top_n, top_ids_out, top_logprobs_out);
+    return ZG_OK;
+}
+
+// The recorded tokens of positions first .. first + n - 1, packed [batch][n]: the body of both fetches (their arguments checked)
+static int fetch_tokens(zg_gpt* g, size_t first, size_t n, size_t* out_tokens) {
+    const size_t C = g->cfg.context_size, B = g->batch;
+    hipStream_t s = gs(g);
+    ZG_HIP(hipMemcpyAsync(g->h_ints, g->out_tokens, B * C * sizeof(int), hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < n; ++i) out_tokens[b * n + i] = (size_t)g->h_ints[b * C + first + i];
+    return ZG_OK;
+}
+
+int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && out_tokens, ZG_ERR_ARG, "generate_fetch_range: null argument");
+    const size_t C = g->cfg.context_size, B = g->batch;
+    ZG_REQUIRE(first <= C && n <= C - first && out_len >= B * n, ZG_ERR_SHAPE, "generate_fetch_range: positions %zu .. %zu of %zu, %zu elements", first,
+               first + n, C, out_len);
+    return fetch_tokens(g, first, n, out_tokens);
+}
+
+// generate (src/main.zig:322-342) for the prompts of SEVERAL handles at once: independent sequences need not run in lock step
+// (the reference's batch restriction, ops.zig:126-128, lifted the other way): gen_run with one stream per handle
+// (zg_gpt_create_ex: own_stream).
+int zg_gpt_generate_enqueue_many(zg_gpt* const* handles, size_t n_handles, const size_t* prompts, size_t prompt_stride,
+                                 const size_t* prompt_lens, size_t n_steps) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(handles && n_handles >= 1 && n_handles <= 64 && prompts && prompt_lens, ZG_ERR_ARG, "generate_many: bad argument");
+    for (size_t i = 0; i < n_handles; ++i) {
+        ZG_REQUIRE(handles[i] != nullptr, ZG_ERR_ARG, "generate_many: handle %zu is null", i);
+        for (size_t j = 0; j < i; ++j) {
+            ZG_REQUIRE(handles[i] != handles[j], ZG_ERR_ARG, "generate_many: handle %zu is handle %zu", i, j);
+            ZG_REQUIRE(n_handles == 1 || gs(handles[i]) != gs(handles[j]), ZG_ERR_ARG,
+                       "generate_many: handles %zu and %zu share a stream (create them with own_stream)", j, i);
+        }
+    }
+    return generate_request(handles, n_handles, request_of(0, prompts, prompt_stride, prompt_lens, n_steps), "generate_many");
+}
+
+int zg_gpt_generate_fetch_many(zg_gpt* const* handles, size_t n_handles, size_t n_steps, size_t* out_tokens, size_t out_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(handles && n_handles >= 1 && out_tokens, ZG_ERR_ARG, "generate_fetch_many: null argument");
+    size_t rows = 0;
+    for (size_t i = 0; i < n_handles; ++i) {
+        ZG_REQUIRE(handles[i] != nullptr, ZG_ERR_ARG, "generate_fetch_many: handle %zu is null", i);
+        rows += handles[i]->batch;
+    }
+    ZG_REQUIRE(out_len >= rows * n_steps, ZG_ERR_SHAPE, "generate_fetch_many: out_tokens too short");
+    size_t row = 0;
+    int first_err = ZG_OK;
+    char msg[512];
+    for (size_t i = 0; i < n_handles; ++i) {  // every handle is drained, also behind a failed one
+        const int e = zg_gpt_generate_fetch(handles[i], n_steps, out_tokens + row * n_steps, handles[i]->batch * n_steps);
+        if (first_err == ZG_OK && e != ZG_OK) {
+            first_err = e;
+            snprintf(msg, sizeof msg, "%s", zg_last_error());
+        }
+        row += handles[i]->batch;
+    }
+    if (first_err != ZG_OK) set_error("%s", msg);
+    return first_err;
+}
+
+int zg_gpt_generate_fetch(zg_gpt* g, size_t n_steps, size_t* out_tokens, size_t out_len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && out_tokens, ZG_ERR_ARG, "generate_fetch: null argument");
+    ZG_REQUIRE(n_steps <= g->cfg.context_size && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate_fetch: out_tokens too short");
+    return fetch_tokens(g, 0, n_steps, out_tokens);
+}
+
+int zg_gpt_generate_greedy(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens,
+                           size_t n_steps, size_t* out_tokens, size_t out_len) {
+    ZG_REQUIRE(g && out_tokens && out_len >= g->batch * n_steps, ZG_ERR_SHAPE, "generate: out_tokens too short");
+    ZG_TRY(zg_gpt_generate_enqueue(g, prompts, prompt_stride, prompt_lens, n_steps));
+    return zg_gpt_generate_fetch(g, n_steps, out_tokens, out_len);
+}
+
+}  // extern "C"

@@ -1,0 +1,76 @@
+// sampler_chain.h — the handle-free host side of the sampler (sampler_chain.hip).  What follows lm_head — which sampler, penalties or
+// not, log-probabilities or not — travels as ONE value, StepTail, from the request to the launches; the sampler chain behind
+// lm_head is emitted by emit_sampler_chain for every user: the decode step of a handle (api_gpt_step.hip), the per-token calls
+// (api_gpt_generate.hip) and the row harnesses on a caller's rows (api_gpt_debug.hip).  Nothing here knows a handle.
+#pragma once
+
+#include "zg_runtime.h"
+
+using namespace zg;
+
+// What a step puts behind lm_head: nothing (greedy: the argmax partials of its epilogue are the pick), GPT.sample's tail, or that
+// tail behind the selection launches of one filter (top-k or top-p) / of both.  The one form "how are tokens chosen" travels in.
+// MINP_ONLY: min-p with both filters off — the threshold-aware tail kernels with no selection launch in front.
+enum SamplerMode { GREEDY = 0, PLAIN, ONE_FILTER, TWO_FILTERS, MINP_ONLY };
+constexpr size_t kSamplerModes = MINP_ONLY + 1;
+static inline int filter_launches(SamplerMode m) { return m == TWO_FILTERS ? 6 : m == ONE_FILTER ? 3 : 0; }  // sample_filter.h: three levels per descent
+static inline bool threshold_sampler(SamplerMode m) { return m == ONE_FILTER || m == TWO_FILTERS || m == MINP_ONLY; }  // the tail kernels that read tau
+
+// Everything that follows lm_head in a decode step, as one value: the sampler, the penalty stage between lm_head and the sampler
+// (DESIGN §3.6), the edit stage — logit bias, allow / ban lists — behind the penalties, the log-probability stage
+// behind the sampler — of a greedy step: behind lm_head —, the stop stage behind everything.  The
+// default is the greedy step the reference's argmax loop runs.
+struct StepTail {
+    SamplerMode sampler = GREEDY;
+    bool pen = false, lp = false, stop = false, edit = false;
+    bool operator==(const StepTail& o) const { return sampler == o.sampler && pen == o.pen && lp == o.lp && stop == o.stop && edit == o.edit; }
+};
+// The tail a step can have: nothing is drawn from a step without lm_head (the default tail), and a greedy pick has neither
+// penalties nor edits
+static inline StepTail normalized(StepTail t, bool with_logits) {
+    if (!with_logits) return StepTail{};
+    if (t.sampler == GREEDY) t.pen = t.edit = false;
+    return t;
+}
+
+namespace zg {
+
+// What the sampler chain — penalties, edits, selection launches, sampler — reads and writes.  The draw comes from one of two
+// sources: the loop's control block (ctrl: the uniform is the counter PRNG of the position it holds), or a per-call buffer of
+// uniforms (u, with the call's temperature and whether the probabilities are written back over the row).
+struct SamplerChain {
+    float* logits;
+    int batch, vocab;
+    float* part_val;  // row-maximum partials [batch][n_part] as lm_head's epilogue leaves them, and their indices
+    int* part_idx;
+    int n_part;
+    const PenParams* pen;
+    PenHistory hist;
+    unsigned* counts;  // (zg_debug_penalize_rows: the counts of every row's history)
+    const EditTable* edit_tab;
+    const unsigned* edit_keep;
+    const SampleParams* params;
+    float* seg_ws;
+    FilterWs filt;
+    const StepCtrl* ctrl;  // the loop's draws ...
+    const float* u;        // ... or a call's
+    float temp;
+    bool write_probs;
+    int* pick;
+};
+
+// ---- sampler_chain.hip
+size_t edit_block_bytes(size_t vocab);
+int emit_sampler_chain(const SamplerChain& c, StepTail t, hipStream_t s);
+int check_top_n(size_t top_n, size_t vocab, const char* who);
+void unpack_top(const int* ids, const float* vals, size_t rows, size_t top_n, size_t* ids_out, float* vals_out);
+bool penalties_off(const zg_logit_penalties& p);
+bool edits_off(const zg_logit_edits& e);
+int build_edits(const zg_logit_edits* e, size_t vocab, const char* who, char* block, bool* stage_on);
+SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed, float min_p);
+int check_penalties(const zg_logit_penalties* p, const char* who);
+int check_sample_options(const zg_sample_options* o, const char* who);
+int check_stop(const zg_stop_conditions* c, size_t vocab, const char* who);
+void fill_stop(StopConds* d, const zg_stop_conditions& c);
+
+}  // namespace zg

@@ -1,0 +1,171 @@
+// sampler_chain.hip — the handle-free host side of the sampler: the sampler chain behind lm_head, emitted by emit_sampler_chain for
+// every user, and the checks and fills of what a sampler call is given (options, penalties, edits, stop conditions, top_n).
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <utility>
+
+#include "sampler_chain.h"
+
+using namespace zg;
+
+namespace {  // this unit only
+
+// temp x log(min_p) in double, rounded once: what the sampler adds to the row maximum (min_p 0: -inf, nothing is cut)
+static float min_p_offset(float temp, float min_p) { return min_p == 0.0f ? -INFINITY : (float)((double)temp * log((double)min_p)); }
+
+}  // namespace
+
+namespace zg {  // offered to the model tier: sampler_chain.h declares them
+
+// the edit stage's block: the bias table, then the keep bitmap of `vocab` bits
+size_t edit_block_bytes(size_t vocab) { return sizeof(EditTable) + (vocab + 31) / 32 * 4; }
+
+// The launches of tail t behind lm_head, up to the pick: GPT.sample's tail (main.zig:200-206) behind the stages that rewrite the
+// row.  Launches only — what they read is staged by the caller (enqueue_step runs under capture).  A GREEDY tail has no sampler
+// launch: the partials are the pick.
+int emit_sampler_chain(const SamplerChain& c, StepTail t, hipStream_t s) {
+    // the penalties act on the raw logits, the edits on the row the penalties leave (HF's processor order); the row-maximum
+    // partials every sampler starts from are rebuilt only behind the LAST stage that rewrites the row — the edit launch does it itself
+    if (t.pen) ZG_TRY(launch_penalize(c.logits, c.batch, c.vocab, c.pen, c.hist, c.part_val, c.part_idx, c.n_part, c.counts, s, !t.edit));
+    if (t.edit) ZG_TRY(launch_logit_edit(c.logits, c.batch, c.vocab, c.edit_tab, c.edit_keep, c.part_val, c.part_idx, c.n_part, s));
+    if (t.sampler == GREEDY) return ZG_OK;
+    if (threshold_sampler(t.sampler))  // a filter or min-p: the selection launches, then the tail kernels that read tau
+        return launch_sample_filtered(c.logits, c.batch, c.vocab, c.params, filter_launches(t.sampler), c.u, c.ctrl, c.part_val, c.n_part, c.n_part, c.seg_ws,
+                                      c.filt, c.pick, c.write_probs, s);
+    if (c.ctrl) return launch_sample_step(c.logits, c.batch, c.vocab, c.params, c.ctrl, c.part_val, c.n_part, c.n_part, c.seg_ws, c.pick, s);
+    return launch_sample(c.logits, c.batch, c.vocab, c.temp, c.u, c.part_val, c.n_part, c.n_part, c.seg_ws, c.pick, c.write_probs, s);
+}
+
+// How many alternatives a log-probability record may be asked for: the one check of every entry point that takes a top_n
+int check_top_n(size_t top_n, size_t vocab, const char* who) {
+    ZG_REQUIRE(top_n <= (size_t)ZG_LOGPROBS_TOP_MAX && top_n <= vocab, ZG_ERR_ARG, "%s: top_n %zu outside 0..%zu", who, top_n,
+               std::min((size_t)ZG_LOGPROBS_TOP_MAX, vocab));
+    return ZG_OK;
+}
+
+// `rows` records [ZG_LOGPROBS_TOP_MAX] of ids and values (host) into the packed [rows][top_n] arrays (host) a caller receives
+void unpack_top(const int* ids, const float* vals, size_t rows, size_t top_n, size_t* ids_out, float* vals_out) {
+    for (size_t i = 0; i < rows; ++i)
+        for (size_t j = 0; j < top_n; ++j) {
+            ids_out[i * top_n + j] = (size_t)ids[i * ZG_LOGPROBS_TOP_MAX + j];
+            vals_out[i * top_n + j] = vals[i * ZG_LOGPROBS_TOP_MAX + j];
+        }
+}
+
+bool penalties_off(const zg_logit_penalties& p) { return p.repetition == 1.0f && p.presence == 0.0f && p.frequency == 0.0f; }
+
+// ---- Logit edits (include/zgpt2.h zg_logit_edits).  A checked set asks a call for the edit stage (any of the three
+// lists: build_edits' stage_on — the set built in the handle's edit_build goes to the device and the edit launch runs) and / or for
+// the sampler's min-p threshold
+bool edits_off(const zg_logit_edits& e) { return e.n_bias == 0 && e.n_allowed == 0 && e.n_banned == 0 && e.min_p == 0.0f; }
+
+// The refusals of a set of edits over `vocab` logits (include/zgpt2.h), and — where any list is given — the set as the kernel
+// reads it, built into `block` (edit_block_bytes(vocab) bytes of plain host memory): the bias pairs sorted by id, then the keep
+// bitmap.  Nothing else is touched.
+int build_edits(const zg_logit_edits* e, size_t vocab, const char* who, char* block, bool* stage_on) {
+    ZG_REQUIRE(e != nullptr, ZG_ERR_ARG, "%s: edits is null", who);
+    ZG_REQUIRE(e->min_p >= 0.0f && e->min_p < 1.0f, ZG_ERR_ARG, "%s: min_p %f outside [0, 1)", who, e->min_p);  // (a NaN fails it)
+    ZG_REQUIRE(e->n_bias <= (size_t)ZG_EDIT_MAX_BIAS, ZG_ERR_ARG, "%s: %zu biases above %d", who, e->n_bias, ZG_EDIT_MAX_BIAS);
+    ZG_REQUIRE((e->n_bias == 0 || (e->bias_ids && e->bias_values)) && (e->n_allowed == 0 || e->allowed_ids) && (e->n_banned == 0 || e->banned_ids), ZG_ERR_ARG,
+               "%s: a null array with a non-zero count", who);
+    for (size_t i = 0; i < e->n_bias; ++i) ZG_REQUIRE(e->bias_ids[i] < vocab, ZG_ERR_SHAPE, "%s: bias id %zu >= vocab %zu", who, e->bias_ids[i], vocab);
+    for (size_t i = 0; i < e->n_allowed; ++i) ZG_REQUIRE(e->allowed_ids[i] < vocab, ZG_ERR_SHAPE, "%s: allowed id %zu >= vocab %zu", who, e->allowed_ids[i], vocab);
+    for (size_t i = 0; i < e->n_banned; ++i) ZG_REQUIRE(e->banned_ids[i] < vocab, ZG_ERR_SHAPE, "%s: banned id %zu >= vocab %zu", who, e->banned_ids[i], vocab);
+    std::pair<int, float> pairs[ZG_EDIT_MAX_BIAS];
+    for (size_t i = 0; i < e->n_bias; ++i) {
+        ZG_REQUIRE(std::isfinite(e->bias_values[i]), ZG_ERR_ARG, "%s: bias %f on token %zu", who, e->bias_values[i], e->bias_ids[i]);
+        pairs[i] = {(int)e->bias_ids[i], e->bias_values[i]};
+    }
+    std::sort(pairs, pairs + e->n_bias, [](const std::pair<int, float>& a, const std::pair<int, float>& b) { return a.first < b.first; });
+    for (size_t i = 1; i < e->n_bias; ++i) ZG_REQUIRE(pairs[i].first != pairs[i - 1].first, ZG_ERR_ARG, "%s: token %d is biased twice", who, pairs[i].first);
+    *stage_on = e->n_bias != 0 || e->n_allowed != 0 || e->n_banned != 0;
+    if (!*stage_on) return ZG_OK;
+    EditTable* tab = reinterpret_cast<EditTable*>(block);
+    unsigned* keep = reinterpret_cast<unsigned*>(block + sizeof(EditTable));
+    const size_t words = (vocab + 31) / 32;
+    memset(tab, 0, sizeof(EditTable));
+    tab->n_bias = (int)e->n_bias;
+    for (size_t i = 0; i < e->n_bias; ++i) {
+        tab->ids[i] = pairs[i].first;
+        tab->vals[i] = pairs[i].second;
+    }
+    memset(keep, e->n_allowed ? 0x00 : 0xff, words * 4);
+    for (size_t i = 0; i < e->n_allowed; ++i) keep[e->allowed_ids[i] >> 5] |= 1u << (e->allowed_ids[i] & 31);
+    for (size_t i = 0; i < e->n_banned; ++i) keep[e->banned_ids[i] >> 5] &= ~(1u << (e->banned_ids[i] & 31));
+    if (vocab & 31) keep[words - 1] &= (1u << (vocab & 31)) - 1u;  // (bits behind the vocabulary: never read, not counted)
+    size_t kept = 0;
+    for (size_t w = 0; w < words; ++w) kept += (size_t)__builtin_popcount(keep[w]);
+    // (both lists are the host's: a row of -inf alone never reaches a kernel)
+    ZG_REQUIRE(kept >= 1, ZG_ERR_ARG, "%s: the allow and ban lists leave no token", who);
+    return ZG_OK;
+}
+
+// The options of a sampler call over `vocab` logits into *p, the host image of SampleParams (the caller uploads it); returns the
+// sampler they need: the plain one with both filters and min-p off, the threshold-aware tail alone for min-p alone
+SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed, float min_p) {
+    const bool k_on = o.top_k >= 1 && o.top_k < vocab, p_on = o.top_p < 1.0f;
+    p->inv_temp = 1.0f / o.temp;
+    p->top_k = k_on ? (unsigned)o.top_k : 0u;
+    p->seed = seed;
+    p->top_p = p_on ? o.top_p : 1.0f;
+    p->min_p_off = min_p_offset(o.temp, min_p);
+    return k_on && p_on ? TWO_FILTERS : (k_on || p_on) ? ONE_FILTER : min_p != 0.0f ? MINP_ONLY : PLAIN;
+}
+
+int check_penalties(const zg_logit_penalties* p, const char* who) {
+    ZG_REQUIRE(p != nullptr, ZG_ERR_ARG, "%s: penalties is null", who);
+    ZG_REQUIRE(p->repetition > 0.0f, ZG_ERR_ARG, "%s: repetition penalty %f (must be > 0)", who, p->repetition);  // (a NaN fails it)
+    ZG_REQUIRE(std::isfinite(p->presence) && std::isfinite(p->frequency), ZG_ERR_ARG, "%s: presence %f / frequency %f penalty", who, p->presence,
+               p->frequency);
+    return ZG_OK;
+}
+
+int check_sample_options(const zg_sample_options* o, const char* who) {
+    ZG_REQUIRE(o != nullptr, ZG_ERR_ARG, "%s: options is null", who);
+    ZG_REQUIRE(o->temp > 0.0f, ZG_ERR_ARG, "%s: temperature %f", who, o->temp);
+    ZG_REQUIRE(o->top_p > 0.0f && o->top_p <= 1.0f, ZG_ERR_ARG, "%s: top_p %f outside (0, 1]", who, o->top_p);  // (a NaN fails both)
+    return ZG_OK;
+}
+
+// The refusals of a set of stop conditions (include/zgpt2.h), vocab standing for the first token that cannot occur
+int check_stop(const zg_stop_conditions* c, size_t vocab, const char* who) {
+    ZG_REQUIRE(c != nullptr, ZG_ERR_ARG, "%s: stop conditions are null", who);
+    ZG_REQUIRE(c->n_ids <= ZG_STOP_MAX_IDS && c->n_seqs <= ZG_STOP_MAX_SEQS, ZG_ERR_ARG, "%s: %zu stop tokens / %zu stop sequences above %d / %d", who,
+               c->n_ids, c->n_seqs, ZG_STOP_MAX_IDS, ZG_STOP_MAX_SEQS);
+    ZG_REQUIRE((c->n_ids == 0 || c->ids) && (c->n_seqs == 0 || (c->seqs && c->seq_lens)), ZG_ERR_ARG, "%s: a null array with a non-zero count", who);
+    for (size_t k = 0; k < c->n_seqs; ++k)
+        ZG_REQUIRE(c->seq_lens[k] >= 1 && c->seq_lens[k] <= ZG_STOP_MAX_SEQ_LEN && c->seq_lens[k] <= c->seq_stride, ZG_ERR_ARG,
+                   "%s: stop sequence %zu has length %zu (1 .. %d, stride %zu)", who, k, c->seq_lens[k], ZG_STOP_MAX_SEQ_LEN, c->seq_stride);
+    for (size_t j = 0; j < c->n_ids; ++j) ZG_REQUIRE(c->ids[j] < vocab, ZG_ERR_SHAPE, "%s: stop token %zu >= vocab %zu", who, c->ids[j], vocab);
+    for (size_t k = 0; k < c->n_seqs; ++k)
+        for (size_t i = 0; i < c->seq_lens[k]; ++i)
+            ZG_REQUIRE(c->seqs[k * c->seq_stride + i] < vocab, ZG_ERR_SHAPE, "%s: token %zu of stop sequence %zu >= vocab %zu", who,
+                       c->seqs[k * c->seq_stride + i], k, vocab);
+    return ZG_OK;
+}
+
+// Checked conditions as the kernel reads them
+void fill_stop(StopConds* d, const zg_stop_conditions& c) {
+    memset(d, 0, sizeof(*d));
+    d->n_ids = (int)c.n_ids;
+    d->n_seqs = (int)c.n_seqs;
+    for (size_t j = 0; j < c.n_ids; ++j) d->ids[j] = (int)c.ids[j];
+    for (size_t k = 0; k < c.n_seqs; ++k) {
+        d->seq_len[k] = (int)c.seq_lens[k];
+        for (size_t i = 0; i < c.seq_lens[k]; ++i) d->seq[k][i] = (int)c.seqs[k * c.seq_stride + i];
+    }
+}
+
+}  // namespace zg
+
+extern "C" {
+
+int zg_debug_min_p_offset(float temp, float min_p, float* d_out) {
+    ZG_REQUIRE(d_out != nullptr && temp > 0.0f && min_p >= 0.0f && min_p < 1.0f, ZG_ERR_ARG, "debug_min_p_offset: temp %f, min_p %f", temp, min_p);
+    *d_out = min_p_offset(temp, min_p);
+    return ZG_OK;
+}
+
+}  // extern "C"

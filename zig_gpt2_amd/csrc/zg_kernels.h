@@ -126,7 +126,7 @@ struct GemvPlan {
     int rows_per_wave;  // rows per wave, or 16-row tiles per workgroup on the matrix cores
     int waves_per_wg;
     int row_group;      // GR_VALU_GROUPS: rows per group (each group is laid out on its own; the other fields describe the first)
-    // the prefetcher's view (api_gpt.hip emit_gemv): workgroup b reads rows b * rows_per_wg .. of W (0 = another mapping), in
+    // the prefetcher's view (api_gpt_step.hip emit_gemv): workgroup b reads rows b * rows_per_wg .. of W (0 = another mapping), in
     // pf_tiles tiles — on GR_KSPLIT / GR_LNK still the VALU layout's workgroup count, as its job table has always had it, not `grid`
     int rows_per_wg, pf_tiles;
     bool supported;         // launch_gemv runs it
@@ -191,8 +191,8 @@ int launch_attn_merge(const float* part, int batch, int n_heads, int head_dim, i
                       int seq_len, float* out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------ elementwise
-int launch_epoch_bump(unsigned* epoch, hipStream_t s);  // measurement chains: advance the tag epoch (api_gpt.hip zg_gpt_time_kernel)
-int launch_epoch_add(unsigned* epoch, unsigned n, hipStream_t s);  // tests: n steps at once (api_gpt.hip zg_debug_gpt_age)
+int launch_epoch_bump(unsigned* epoch, hipStream_t s);  // measurement chains: advance the tag epoch (api_gpt_debug.hip zg_gpt_time_kernel)
+int launch_epoch_add(unsigned* epoch, unsigned n, hipStream_t s);  // tests: n steps at once (api_gpt_debug.hip zg_debug_gpt_age)
 int launch_layernorm(float* x, int rows, int n, const float* g, const float* b, float eps, hipStream_t s, unsigned* done_flag = nullptr,
                      unsigned done_seq = 0, bool* announced = nullptr, float* shadow = nullptr);
 int launch_gelu(float* x, size_t n, hipStream_t s, unsigned* done_flag = nullptr, unsigned done_seq = 0, bool* announced = nullptr, float* shadow = nullptr);
