@@ -8,6 +8,7 @@
 //   api_gpt_debug.hip     everything that exists for tests and measurements
 #pragma once
 
+#include <stddef.h>
 #include <stdlib.h>
 
 #include <utility>
@@ -15,7 +16,7 @@
 
 #include "sampler_chain.h"
 
-constexpr size_t kSkFlagWords = 512;  // flag words of the stream-K hand-over (zg_gpt.sk_flags): four per shared tile, 128 shared tiles
+constexpr size_t kSkFlagWords = 512;  // flag words of the stream-K hand-over (zg_gpt.pass.sk_flags): four per shared tile, 128 shared tiles
 
 struct zg_layer {
     void *c_attn_w, *c_proj_w, *c_fc_w, *mlp_proj_w;
@@ -27,6 +28,27 @@ struct zg_layer {
     float *ln_1_g, *ln_1_b, *c_attn_b, *c_proj_b, *ln_2_g, *ln_2_b, *c_fc_b, *mlp_proj_b;
     void *k_cache, *v_cache;
 };
+
+// The decode modes the step unit's builders lay the arguments out for: the handle's own (zg_gpt.modes) for a step, a candidate
+// while decide_step_modes decides them
+struct StepModes {
+    bool pl, st, tags;  // activation planes between the kernels / LayerNorm statistics by tile / tagged hand-overs (lock-step batch)
+    bool fused;         // one sequence: ln_1 + c_attn and the attention of a layer as ONE launch (attn_qkv.hip)
+};
+
+// The ONE pinned block behind zg_gpt.h_ctrl: the control mirror and the small words that travel beside it.  The kernels store to
+// `fault`, the host stages the rest; the groups of zg_gpt hold pointers to their members.
+struct PinnedCtrl {
+    StepCtrl ctrl;
+    alignas(128) SampleParams samp;  // samp.h_params
+    alignas(128) unsigned fault;     // hand.fault: written by the kernels
+    alignas(64) float uniforms[8];   // the per-token family's draws (batch <= 8): h_ints[0 .. batch) is still being read by the forward's token upload
+    alignas(128) PenParams pen;      // pen.h_params
+    alignas(32) int top_n;           // lp.h_top
+};
+static_assert(offsetof(PinnedCtrl, samp) == 128 && offsetof(PinnedCtrl, fault) == 256 && offsetof(PinnedCtrl, uniforms) == 320 &&
+                  offsetof(PinnedCtrl, pen) == 384 && offsetof(PinnedCtrl, top_n) == 416,
+              "the pinned control block keeps its layout");
 
 struct zg_gpt {
     zg_gpt_config cfg;
@@ -50,115 +72,22 @@ struct zg_gpt {
     float* sk_ws;
     int* sk_cnt;
     int sk_tiles;
-    // whole-prompt (prefill) scratch, rows = batch * ctx: x fp32 [E], qkv fp32 [3E], split bf16 [kSplit E] and [kSplit 4E]
-    float *pf_x, *pf_qkv, *pf_ws;
-    size_t pf_ws_floats;
-    unsigned* sk_flags;   // stream-K hand-over of the c_attn GEMM (PrefillQkv.sk_*): kSkFlagWords flag words, zeroed at create
-    unsigned sk_epoch;    // the epoch last handed to a stream-K launch: never 0, the value of a flag word no launch has written (next_sk_epoch)
-    size_t sk_restarts;   // times the epoch wrapped: the flag words were zeroed on the stream and the count began again at 1
-    bool sk_used;         // a stream-K launch since the last check of gemm_s4_fault
-    bf16_t *pf_a, *pf_h;
     // lock-step batch with bf16 weights: activation planes between the kernels of a Block (GemvArgs.pl_in / pl_out):
     // xp = planes of g * x for the next LayerNorm-fed Linear [48 E bytes], hp = planes of gelu(c_fc) [48 * 4E bytes]
     // ap = planes of the merged attention output [48 E bytes], written by the last split of every (sequence, head)
     // (AttnArgs.pl_out; attn_cnt = its arrival counters)
     bf16_t *xp, *hp, *ap;
     int* attn_cnt;
-    // tagged hand-overs (GemvArgs.sk_tag, AttnArgs.part_tag): step counter advanced by the embed kernel, (value, tag) words
-    unsigned* epoch;
-    unsigned spin_limit;  // polls before a poller of a tagged hand-over gives up
     unsigned tail_off;    // AttnArgs.tail_off: ZGPT2_DECODE_PATHS_OFF's kStepPathsAtCreate bits, read once at create
-    unsigned* fault;  // set by a poller of a tagged hand-over whose bounded wait ran out; checked wherever a call drains the stream
-    unsigned long long *sk_tag, *part_tag;
-    size_t sk_tag_bytes, part_tag_bytes;
-    size_t epochs_since_clear;  // steps enqueued since the tagged words were last zeroed (note_steps)
-    size_t steps_counted, tag_clears;  // steps note_steps has counted in all, clears it has enqueued (zg_debug_gpt_age_state)
-    bool tags_on;
-    // one sequence: ln_1 + c_attn and the attention of a layer as ONE launch (attn_qkv.hip), q and the new k / v row handed over as
-    // (value, tag) words [3 E] (tags as above: the embed kernel advances the epoch)
-    unsigned long long* qkv_tag;
-    size_t qkv_tag_bytes;
-    bool fused_on;
     // LayerNorm statistics of x by 16-column tile, written by the producers of x (GemvArgs.st_out / st_in)
     float* xst;
-    bool st_on;
-    bool pl_on;
     int max_splits, lm_grid;
     // pinned host mirrors for small control traffic
-    StepCtrl* h_ctrl;
+    PinnedCtrl* h_ctrl;
     int* h_ints;  // [batch * ctx] staging for prompts / tokens
-    // graphs [step_index(StepKey)][n_buckets]: one per (step shape, 64-position bucket of seq_len), captured on first use (graph_exec).
-    // The bucket's upper bound t_hi is baked into the attention / merge kernels so that their loads
-    // do not wait for the exact seq_len (which lives in device memory).
-    std::vector<hipGraphExec_t> graphs;
-    size_t n_buckets;         // ceil(context / 64)
-    int* sampled;             // [batch]: the sampler's draw from the last step's logits
-    float* samp_ws;           // segment sums of the sampler (sample_workspace_floats)
-    SampleParams* samp;       // device: temperature and seed of the generation in flight
-    SampleParams* h_samp;     // pinned mirror
-    StepTail gen_tail;        // what follows lm_head in the steps of the generation in flight (normalized)
-    FilterWs filt;            // selection workspace of the truncated sampler (sample_filter.h), zero at create
-    // logit penalties (sample_penalty.h): the caller's prior / explicit history [batch][ctx] with its lengths, the values
-    // of the call in flight, their pinned mirrors (h_prior: [batch * ctx] tokens, then [batch] lengths).  The kernels' table is LDS: no workspace
-    int *prior, *prior_len;
-    PenParams *pen, *h_pen;
-    int* h_prior;
-    // log-probabilities (sample_logprob.h): the chunk workspace, top_n of the generation in flight (device word and
-    // its place in the pinned control block), the record buffers [batch][ctx] / [batch][ctx][20] and the pinned mirror a fetch
-    // copies its columns through ([batch * ctx] log-probabilities, then [batch * ctx * 20] ids, then as many values)
-    LogprobWs lp_ws;
-    LogprobRec lp_rec;
-    int *lp_top, *h_lp_top;
-    float* h_lp;
-    bool lp_valid;            // the last generation (or zg_gpt_score) recorded them: the record can be fetched
-    size_t lp_top_n;          // ... with this many alternatives
-    // stop conditions (sample_stop.h): the conditions of the generation in flight, finish column and reason of every
-    // row (-1: none), and ONE pinned block: the staging mirror of the conditions, the way back of the two arrays, and the two
-    // words the stop kernel stores to (host.progress, host.done_col)
-    StopConds* stop;
-    int *stop_fin, *stop_reason;
-    struct StopPinned {
-        StopConds conds;
-        int fin[kStopMaxRows], reason[kStopMaxRows];
-        alignas(64) StopHost host;
-    }* h_stop;
-    // logit edits (sample_edit.h): the bias table and, behind it, the keep bitmap of vocab bits — one block in the
-    // arena, its pinned mirror, and plain host memory of the same size in which a call's set is built and checked before anything
-    // else is touched (edit_build)
-    EditTable* edit_tab;
-    unsigned* edit_keep;
-    char* h_edit;
-    std::vector<char> edit_build;
-    bool gen_stop;            // the generation in flight has conditions: gen_pump paces itself and may end early
-    size_t gen_lookahead;     // ... at most this many steps ahead of host.progress before each piece
-    bool stop_valid;          // the last generation was one with conditions: zg_gpt_generate_stop_result can report it
-    size_t stop_end;          // ... and ended here
-    // scoring (zg_gpt_score; sample_score.h), carved under ZG_GPT_SCORE only: the logits of one block of kScoreRows rows
-    // [kScoreRows][sc_v64] (sc_v64 = the vocabulary on the GEMMs' 64-column grid), the chunk workspace of that block, and the lm_head
-    // operand the whole-prompt GEMM cannot take from the weight region: bf16 weights — the last vocab % 64 rows of wte as a [64][E]
-    // strip, zero rows behind them; fp32 / B24 weights — wte's planes [3][sc_v64][E], zero rows behind the vocabulary, and the
-    // slab workspace of that launch.  sc_gen: w_gen + 1 of the weights the strip / planes were made from (0: never made)
-    float* sc_logits;
-    ScoreWs sc_ws;
-    bf16_t *sc_tail, *sc_planes;
-    float* sc_gemm_ws;
-    size_t sc_gemm_ws_floats, sc_v64, sc_gen;
     size_t w_gen;             // (the owner of a weight region) bumped whenever its wte may have changed
-    size_t graph_steps;
-    hipStream_t graph_stream;
     size_t steps_enqueued;
     bool ln_folded;  // c2 / c3 of every layer match the weights currently in the arena
-    // side-stream L2 prefetcher of the decode chain (prefetch.hip); runs during zg_gpt_generate_enqueue only
-    PfCtl* pf_ctl;
-    PfJob* pf_jobs;  // [pf_njobs]: embed, 5 per layer, lm_head
-    int pf_njobs;
-    bool pf_on;
-    bool pf_ran;      // a prefetcher was launched by the last generate call
-    bool pf_stalled;  // one left on its idle limit (no concurrency with the decode stream, or a host hiccup): sitting out
-    int pf_strikes;   // idle-limit exits so far; the third one is final
-    int pf_sit_out;   // generate calls left before a stalled prefetcher is tried again
-    hipStream_t pf_stream;
-    hipEvent_t pf_ev_main, pf_ev_side;
     // independent prompt groups on one GPU (zg_gpt_create_ex): a private stream, so that the decode chains of several handles
     // overlap on the chip, and a weight region borrowed from another handle of the same model
     hipStream_t stream;  // nullptr: the library stream of the moment (zg_set_stream)
@@ -166,15 +95,137 @@ struct zg_gpt {
     bool counted;        // this handle is one of its parent's n_children
     int n_children;      // handles borrowing this one's weight region
     char* wbase;         // the weight region: arena, or the parent's
-    // a generation in flight between gen_begin and gen_end (zg_gpt_generate_enqueue / _many)
-    size_t gen_pos, gen_n, gen_min_prompt, gen_since_sync;
-    bool gen_open;
     // the session: positions the caches hold, and the row behind the last one written since the rows behind a pass
     // were last cleared — a continuation clears [its end, context) only when something may be there
     size_t cached_len, kv_dirty_hi;
+
+    // What follows belongs to one unit each, which the comment names.  Every group is an aggregate that value-initialises to zeros
+    // (new zg_gpt() zeroes the whole handle: release() relies on it); carve() and build_handle fill the pointers of all of them.
+
+    // step (decided once at create: decide_step_modes): the decode modes of this handle's steps
+    StepModes modes;
+    // handle (note_steps, check_fault) — tagged hand-overs (GemvArgs.sk_tag, AttnArgs.part_tag): step counter advanced by the embed
+    // kernel, (value, tag) words; the step unit hands the pointers to the launches
+    struct {
+        unsigned* epoch;
+        unsigned spin_limit;  // polls before a poller of a tagged hand-over gives up
+        unsigned* fault;  // set by a poller of a tagged hand-over whose bounded wait ran out; checked wherever a call drains the stream
+        unsigned long long *sk_tag, *part_tag;
+        size_t sk_tag_bytes, part_tag_bytes;
+        size_t epochs_since_clear;  // steps enqueued since the tagged words were last zeroed (note_steps)
+        size_t steps_counted, tag_clears;  // steps note_steps has counted in all, clears it has enqueued (zg_debug_gpt_age_state)
+        // the fused launch of one sequence (modes.fused): q and the new k / v row handed over as (value, tag) words [3 E] (tags as
+        // above: the embed kernel advances the epoch)
+        unsigned long long* qkv_tag;
+        size_t qkv_tag_bytes;
+    } hand;
+    // step — graphs [step_index(StepKey)][n_buckets]: one per (step shape, 64-position bucket of seq_len), captured on first use
+    // (graph_exec).  The bucket's upper bound t_hi is baked into the attention / merge kernels so that their loads do not wait
+    // for the exact seq_len (which lives in device memory).
+    struct {
+        std::vector<hipGraphExec_t> execs;
+        size_t n_buckets;  // ceil(context / 64)
+        size_t steps;      // decode steps per multi-step graph (ZGPT2_GRAPH_STEPS)
+        hipStream_t stream;
+    } graph;
+    // step — side-stream L2 prefetcher of the decode chain (prefetch.hip); runs during zg_gpt_generate_enqueue only
+    struct {
+        PfCtl* ctl;
+        PfJob* jobs;  // [njobs]: embed, 5 per layer, lm_head
+        int njobs;
+        bool on;
+        bool ran;      // a prefetcher was launched by the last generate call
+        bool stalled;  // one left on its idle limit (no concurrency with the decode stream, or a host hiccup): sitting out
+        int strikes;   // idle-limit exits so far; the third one is final
+        int sit_out;   // generate calls left before a stalled prefetcher is tried again
+        hipStream_t stream;
+        hipEvent_t ev_main, ev_side;
+    } prefetch;
+    // pass — whole-prompt (prefill) scratch, rows = batch * ctx: x fp32 [E], qkv fp32 [3E], split bf16 a [kSplit E] and h [kSplit 4E]
+    // (the pf_x, pf_qkv, pf_a and pf_h of the pass taps, include/zgpt2.h), the split-K partials ws; all null under ZG_GPT_NO_PREFILL
+    struct {
+        float *x, *qkv, *ws;
+        size_t ws_floats;
+        unsigned* sk_flags;   // stream-K hand-over of the c_attn GEMM (PrefillQkv.sk_*): kSkFlagWords flag words, zeroed at create
+        unsigned sk_epoch;    // the epoch last handed to a stream-K launch: never 0, the value of a flag word no launch has written (next_sk_epoch)
+        size_t sk_restarts;   // times the epoch wrapped: the flag words were zeroed on the stream and the count began again at 1
+        bool sk_used;         // a stream-K launch since the last check of gemm_s4_fault
+        bf16_t *a, *h;
+    } pass;
+    // pass — scoring (zg_gpt_score; sample_score.h), carved under ZG_GPT_SCORE only: the logits of one block of kScoreRows
+    // rows [kScoreRows][v64] (v64 = the vocabulary on the GEMMs' 64-column grid), the chunk workspace of that block, and the lm_head
+    // operand the whole-prompt GEMM cannot take from the weight region: bf16 weights — the last vocab % 64 rows of wte as a [64][E]
+    // strip, zero rows behind them; fp32 / B24 weights — wte's planes [3][v64][E], zero rows behind the vocabulary, and the
+    // slab workspace of that launch.  gen: w_gen + 1 of the weights the strip / planes were made from (0: never made)
+    struct {
+        float* logits;
+        ScoreWs ws;
+        bf16_t *tail, *planes;
+        float* gemm_ws;
+        size_t gemm_ws_floats, v64, gen;
+    } score;
+    // generate / the step tail — the sampler of the generation in flight or of a per-token call
+    struct {
+        int* sampled;            // [batch]: the sampler's draw from the last step's logits
+        float* ws;               // segment sums of the sampler (sample_workspace_floats)
+        SampleParams* params;    // device: temperature and seed of the generation in flight
+        SampleParams* h_params;  // pinned mirror (PinnedCtrl.samp)
+        FilterWs filt;           // selection workspace of the truncated sampler (sample_filter.h), zero at create
+    } samp;
+    // generate — logit penalties (sample_penalty.h): the caller's prior / explicit history [batch][ctx] with its lengths,
+    // the values of the call in flight, their pinned mirrors (h_params: PinnedCtrl.pen; h_prior: [batch * ctx] tokens, then [batch]
+    // lengths, behind h_ints).  The kernels' table is LDS: no workspace
+    struct {
+        int *prior, *prior_len;
+        PenParams *params, *h_params;
+        int* h_prior;
+    } pen;
+    // generate — log-probabilities (sample_logprob.h): the chunk workspace, top_n of the generation in flight (device
+    // word `top` and its place in the pinned control block, `h_top`), the record buffers [batch][ctx] / [batch][ctx][20] and the
+    // pinned mirror a fetch copies its columns through (h_rec: [batch * ctx] log-probabilities, then [batch * ctx * 20] ids, then
+    // as many values)
+    struct {
+        LogprobWs ws;
+        LogprobRec rec;
+        int *top, *h_top;
+        float* h_rec;
+        bool valid;    // the last generation (or zg_gpt_score) recorded them: the record can be fetched
+        size_t top_n;  // ... with this many alternatives
+    } lp;
+    // generate — stop conditions (sample_stop.h): the conditions of the generation in flight, finish column and reason of
+    // every row (-1: none), and ONE pinned block: the staging mirror of the conditions, the way back of the two arrays, and the two
+    // words the stop kernel stores to (host.progress, host.done_col)
+    struct {
+        StopConds* conds;
+        int *fin, *reason;
+        struct StopPinned {
+            StopConds conds;
+            int fin[kStopMaxRows], reason[kStopMaxRows];
+            alignas(64) StopHost host;
+        }* pinned;
+    } stop;
+    // generate — logit edits (sample_edit.h): the bias table and, behind it, the keep bitmap of vocab bits — one block
+    // in the arena, its pinned mirror, and plain host memory of the same size in which a call's set is built and checked before
+    // anything else is touched (build)
+    struct {
+        EditTable* tab;
+        unsigned* keep;
+        char* h_block;
+        std::vector<char> build;
+    } edit;
+    // generate — a generation in flight between gen_begin and gen_end (zg_gpt_generate_enqueue / _many), and what the last one left
+    struct {
+        size_t pos, n, min_prompt, since_sync;
+        bool open;
+        StepTail tail;      // what follows lm_head in the steps of the generation in flight (normalized)
+        bool stop;          // the generation in flight has conditions: gen_pump paces itself and may end early
+        size_t lookahead;   // ... at most this many steps ahead of host.progress before each piece
+        bool stop_valid;    // the last generation was one with conditions: zg_gpt_generate_stop_result can report it
+        size_t stop_end;    // ... and ended here
+    } gen;
 };
 
-// rows of pf_x per lm_head block of zg_gpt_score: one constant, decided by one measurement (profiles/NOTEBOOK.md §16: 256 rows take
+// rows of pass.x per lm_head block of zg_gpt_score: one constant, decided by one measurement (profiles/NOTEBOOK.md §16: 256 rows take
 // the 128 x 256 tiles and half the launches; -DZG_SCORE_ROWS=128 builds the other candidate)
 #ifndef ZG_SCORE_ROWS
 #define ZG_SCORE_ROWS 256
@@ -209,12 +260,6 @@ struct StepProf {
     size_t n = 0;
 };
 
-// The decode modes the *_args builders lay the arguments out for (api_gpt_step.hip)
-struct StepModes {
-    bool pl, st, tags;  // as zg_gpt pl_on / st_on / tags_on
-};
-inline StepModes modes_of(const zg_gpt* g) { return StepModes{g->pl_on, g->st_on, g->tags_on}; }
-
 // What enqueue_step does besides a plain step.
 struct StepOpts {
     StepProf* prof = nullptr;  // zg_gpt_profile_step: an event behind every kernel class
@@ -241,7 +286,7 @@ struct StepTaps {
 
 // The decode graphs of a handle, per 64-position bucket of the sequence length, keyed by what the graph contains:
 //   with_logits  lm_head behind the Blocks (a step that only feeds a prompt token has none)
-//   multi        graph_steps consecutive steps (all with lm_head, all in one bucket) as ONE graph: the position lives in device
+//   multi        graph.steps consecutive steps (all with lm_head, all in one bucket) as ONE graph: the position lives in device
 //                memory, so the same kernels simply repeat; saves the gap between graph launches in the generate loop
 //   tail         what follows lm_head (StepTail, normalized; the option values are read on the device)
 // The table has a slot for every combination of the fields, indexed by them as mixed-radix digits; the slots of combinations
@@ -287,12 +332,7 @@ int forward_enqueue(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_to
 int bucket_t_hi(const zg_gpt* g, size_t seq_len);
 EmbedArgs embed_args(const zg_gpt* g, int finish_only);
 int prof_mark(StepProf* p, int cls, hipStream_t s);
-GemvArgs c_attn_args(const zg_gpt* g, const zg_layer& y, int t_hi, const StepModes& m);
-AttnArgs attn_args(const zg_gpt* g, const zg_layer& y, int t_hi);
-GemvArgs c_proj_args(const zg_gpt* g, const zg_layer& y, int t_hi, const StepModes& m);
-GemvArgs c_fc_args(const zg_gpt* g, const zg_layer& y, int t_hi, const StepModes& m);
-GemvArgs mlp_proj_args(const zg_gpt* g, size_t l, int t_hi, const StepModes& m);
-GemvArgs lm_head_args(const zg_gpt* g);
+int decide_step_modes(zg_gpt* g);
 int enqueue_lm_head(zg_gpt* g, hipStream_t s, std::vector<PfJob>* rec = nullptr);
 SamplerChain handle_chain(const zg_gpt* g, bool loop);
 int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const StepOpts& o = StepOpts());

@@ -89,80 +89,80 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
     g->forced = (int*)P(B * 4);
     g->cur_token = (int*)P(B * 4);
     g->out_tokens = (int*)P(B * C * 4);
-    g->sampled = (int*)P(B * 4);
-    g->samp = (SampleParams*)P(sizeof(SampleParams));
-    g->samp_ws = (float*)P(sample_workspace_floats((int)B) * 4);
-    g->filt = filter_workspace(P(filter_workspace_bytes((int)B)), (int)B);
-    g->prior = (int*)P(B * C * 4);
-    g->prior_len = (int*)P(B * 4);
-    g->pen = (PenParams*)P(sizeof(PenParams));
+    g->samp.sampled = (int*)P(B * 4);
+    g->samp.params = (SampleParams*)P(sizeof(SampleParams));
+    g->samp.ws = (float*)P(sample_workspace_floats((int)B) * 4);
+    g->samp.filt = filter_workspace(P(filter_workspace_bytes((int)B)), (int)B);
+    g->pen.prior = (int*)P(B * C * 4);
+    g->pen.prior_len = (int*)P(B * 4);
+    g->pen.params = (PenParams*)P(sizeof(PenParams));
     g->xp = (bf16_t*)P(E * 48);
     g->hp = (bf16_t*)P(4 * E * 48);
     g->ap = (bf16_t*)P(E * 48);
     g->attn_cnt = (int*)P(8 * c.n_heads * 4);
-    g->epoch = (unsigned*)P(256);
+    g->hand.epoch = (unsigned*)P(256);
     g->xst = (float*)P(((E + 15) / 16) * 8 * 2 * 4);
-    g->sk_tag_bytes = ((E + 15) / 16) * 4 * 128 * 8;
-    g->part_tag_bytes = 8 * c.n_heads * g->max_splits * kPartStride * 8;
-    g->sk_tag = (unsigned long long*)P(g->sk_tag_bytes);
-    g->qkv_tag_bytes = 3 * E * 8;
-    g->qkv_tag = (unsigned long long*)P(g->qkv_tag_bytes);
-    g->part_tag = (unsigned long long*)P(g->part_tag_bytes);
+    g->hand.sk_tag_bytes = ((E + 15) / 16) * 4 * 128 * 8;
+    g->hand.part_tag_bytes = 8 * c.n_heads * g->max_splits * kPartStride * 8;
+    g->hand.sk_tag = (unsigned long long*)P(g->hand.sk_tag_bytes);
+    g->hand.qkv_tag_bytes = 3 * E * 8;
+    g->hand.qkv_tag = (unsigned long long*)P(g->hand.qkv_tag_bytes);
+    g->hand.part_tag = (unsigned long long*)P(g->hand.part_tag_bytes);
     g->sk_tiles = (int)((E + 15) / 16);
     g->sk_ws = (float*)P((size_t)g->sk_tiles * 4 * 128 * 4);
     g->sk_cnt = (int*)P((size_t)g->sk_tiles * 4 * 4);  // [tile][4]: the four-wave plane-fed kernel takes one ticket per wave
-    g->pf_njobs = (int)(2 + 5 * L);
-    g->pf_ctl = (PfCtl*)P(sizeof(PfCtl));
-    g->pf_jobs = (PfJob*)P((size_t)g->pf_njobs * sizeof(PfJob));
-    g->pf_x = g->pf_qkv = g->pf_ws = nullptr;
-    g->sk_flags = nullptr;
-    g->sk_epoch = 0;
-    g->sk_restarts = 0;
-    g->sk_used = false;
-    g->pf_a = g->pf_h = nullptr;
-    g->pf_ws_floats = 0;
+    g->prefetch.njobs = (int)(2 + 5 * L);
+    g->prefetch.ctl = (PfCtl*)P(sizeof(PfCtl));
+    g->prefetch.jobs = (PfJob*)P((size_t)g->prefetch.njobs * sizeof(PfJob));
+    g->pass.x = g->pass.qkv = g->pass.ws = nullptr;
+    g->pass.sk_flags = nullptr;
+    g->pass.sk_epoch = 0;
+    g->pass.sk_restarts = 0;
+    g->pass.sk_used = false;
+    g->pass.a = g->pass.h = nullptr;
+    g->pass.ws_floats = 0;
     if (!(g->flags & ZG_GPT_NO_PREFILL)) {
-        g->pf_x = (float*)P(B * C * E * 4);
-        g->pf_qkv = (float*)P(B * C * 3 * E * 4);
-        g->pf_a = (bf16_t*)P(B * C * kSplit * E * 2);
-        g->pf_h = (bf16_t*)P(B * C * kSplit * 4 * E * 2);
+        g->pass.x = (float*)P(B * C * E * 4);
+        g->pass.qkv = (float*)P(B * C * 3 * E * 4);
+        g->pass.a = (bf16_t*)P(B * C * kSplit * E * 2);
+        g->pass.h = (bf16_t*)P(B * C * kSplit * 4 * E * 2);
         // split-K partials of the prompt GEMMs; fp32 weights: three weight-plane passes of [B ctx, 4 E] at the least
-        g->pf_ws_floats = g->wt == WT_BF16 ? (size_t)(16u << 20) : std::max((size_t)(16u << 20), 3 * B * C * 4 * E);
-        g->pf_ws = (float*)P(g->pf_ws_floats * 4);
-        g->sk_flags = (unsigned*)P(kSkFlagWords * sizeof(unsigned));
+        g->pass.ws_floats = g->wt == WT_BF16 ? (size_t)(16u << 20) : std::max((size_t)(16u << 20), 3 * B * C * 4 * E);
+        g->pass.ws = (float*)P(g->pass.ws_floats * 4);
+        g->pass.sk_flags = (unsigned*)P(kSkFlagWords * sizeof(unsigned));
     }
     // (behind everything else: handles that never ask for log-probabilities keep the layout they had)
-    g->lp_ws = logprob_workspace(P(logprob_workspace_bytes((int)B, (int)V)), (int)B, (int)V);
-    g->lp_top = (int*)P(256);
-    g->lp_rec.logprob = (float*)P(B * C * 4);
-    g->lp_rec.top_ids = (int*)P(B * C * ZG_LOGPROBS_TOP_MAX * 4);
-    g->lp_rec.top_logprobs = (float*)P(B * C * ZG_LOGPROBS_TOP_MAX * 4);
-    g->lp_rec.stride = (int)C;
+    g->lp.ws = logprob_workspace(P(logprob_workspace_bytes((int)B, (int)V)), (int)B, (int)V);
+    g->lp.top = (int*)P(256);
+    g->lp.rec.logprob = (float*)P(B * C * 4);
+    g->lp.rec.top_ids = (int*)P(B * C * ZG_LOGPROBS_TOP_MAX * 4);
+    g->lp.rec.top_logprobs = (float*)P(B * C * ZG_LOGPROBS_TOP_MAX * 4);
+    g->lp.rec.stride = (int)C;
     // (and behind those: handles that never ask for scoring keep the layout they had)
-    g->sc_logits = nullptr;
-    g->sc_ws = ScoreWs{};
-    g->sc_tail = g->sc_planes = nullptr;
-    g->sc_gemm_ws = nullptr;
-    g->sc_gemm_ws_floats = 0;
-    g->sc_v64 = (V + 63) / 64 * 64;
+    g->score.logits = nullptr;
+    g->score.ws = ScoreWs{};
+    g->score.tail = g->score.planes = nullptr;
+    g->score.gemm_ws = nullptr;
+    g->score.gemm_ws_floats = 0;
+    g->score.v64 = (V + 63) / 64 * 64;
     if ((g->flags & ZG_GPT_SCORE) && !(g->flags & ZG_GPT_NO_PREFILL)) {
-        g->sc_logits = (float*)P(kScoreRows * g->sc_v64 * 4);
-        g->sc_ws = score_workspace(P(score_workspace_bytes((int)kScoreRows, (int)V)), (int)kScoreRows, (int)V);
+        g->score.logits = (float*)P(kScoreRows * g->score.v64 * 4);
+        g->score.ws = score_workspace(P(score_workspace_bytes((int)kScoreRows, (int)V)), (int)kScoreRows, (int)V);
         if (g->wt == WT_BF16) {
-            if (V % 64) g->sc_tail = (bf16_t*)P(64 * E * 2);
-        } else {  // the three-pass GEMM sums its slabs [3][rows][sc_v64] through a workspace: more than pf_ws holds at a real vocabulary
-            g->sc_planes = (bf16_t*)P(kSplit * g->sc_v64 * E * 2);
-            g->sc_gemm_ws_floats = 3 * kScoreRows * g->sc_v64;
-            g->sc_gemm_ws = (float*)P(g->sc_gemm_ws_floats * 4);
+            if (V % 64) g->score.tail = (bf16_t*)P(64 * E * 2);
+        } else {  // the three-pass GEMM sums its slabs [3][rows][score.v64] through a workspace: more than pass.ws holds at a real vocabulary
+            g->score.planes = (bf16_t*)P(kSplit * g->score.v64 * E * 2);
+            g->score.gemm_ws_floats = 3 * kScoreRows * g->score.v64;
+            g->score.gemm_ws = (float*)P(g->score.gemm_ws_floats * 4);
         }
     }
     // (and behind everything: the stop stage's conditions and its two words per row; every layout above is what it was)
-    g->stop = (StopConds*)P(sizeof(StopConds));
-    g->stop_fin = (int*)P(kStopMaxRows * 4);
-    g->stop_reason = (int*)P(kStopMaxRows * 4);
+    g->stop.conds = (StopConds*)P(sizeof(StopConds));
+    g->stop.fin = (int*)P(kStopMaxRows * 4);
+    g->stop.reason = (int*)P(kStopMaxRows * 4);
     // (and the edit stage's bias table with the keep bitmap behind it)
-    g->edit_tab = (EditTable*)P(edit_block_bytes(V));
-    g->edit_keep = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g->edit_tab) + sizeof(EditTable));
+    g->edit.tab = (EditTable*)P(edit_block_bytes(V));
+    g->edit.keep = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g->edit.tab) + sizeof(EditTable));
     g->state_bytes = (cv.off + 255) & ~(size_t)255;
 }
 
@@ -226,9 +226,9 @@ void release(zg_gpt* g) {
     if (g->arena) (void)hipFree(g->arena);
     if (g->h_ctrl) (void)hipHostFree(g->h_ctrl);
     if (g->h_ints) (void)hipHostFree(g->h_ints);
-    if (g->h_lp) (void)hipHostFree(g->h_lp);
-    if (g->h_stop) (void)hipHostFree(g->h_stop);
-    if (g->h_edit) (void)hipHostFree(g->h_edit);
+    if (g->lp.h_rec) (void)hipHostFree(g->lp.h_rec);
+    if (g->stop.pinned) (void)hipHostFree(g->stop.pinned);
+    if (g->edit.h_block) (void)hipHostFree(g->edit.h_block);
     delete g;
 }
 
@@ -253,63 +253,36 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
         e = hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, pr);
         if (e != hipSuccess) return hip_fail(e, "hipStreamCreateWithPriority(handle stream)", __FILE__, __LINE__);
     }
-    // The decode modes, each decided from the plans (gemv_plan) of the launches enqueue_step would make with the mode on.
-    const zg_layer& y = g->layers[0];
-    const int off = decode_paths_off();
-    g->lm_grid = gemv_plan(lm_head_args(g), g->wt).grid;
-    // the widest input of a Block (mlp c_proj: 4 E floats per sequence) must fit the batched kernels' LDS
-    ZG_REQUIRE(gemv_plan(mlp_proj_args(g, 0, 0, StepModes{}), g->wt).supported, ZG_ERR_UNSUPPORTED,
-               "batch %zu with n_embed %zu: %zu input rows of 4*n_embed floats do not fit the LDS (use a smaller batch)", batch, c.n_embed, batch);
-    if (g->wt == WT_BF16 && batch >= 2 && !(off & kOffPlanes) && c.n_embed % 32 == 0) {
-        const StepModes cand{true, false, false};  // activation planes between the kernels
-        const GemvPlan lin[4] = {gemv_plan(c_attn_args(g, y, 0, cand), g->wt), gemv_plan(c_proj_args(g, y, 0, cand), g->wt),
-                                 gemv_plan(c_fc_args(g, y, 0, cand), g->wt), gemv_plan(mlp_proj_args(g, 0, 0, cand), g->wt)};
-        auto every_linear = [&](bool GemvPlan::*f) { return lin[0].*f && lin[1].*f && lin[2].*f && lin[3].*f; };
-        g->pl_on = every_linear(&GemvPlan::can_take_planes);  // all plane-fed Linears on the matrix-core path?
-        // LayerNorm statistics by tile: every producer and consumer of x must be the four-wave kernel (the statistics' only
-        // part in a plan is the bound on n_embed / 16 asked here)
-        g->st_on = g->pl_on && !(off & kOffTileStats) && c.n_embed % 16 == 0 && c.n_embed / 16 <= 128 && every_linear(&GemvPlan::pl4_with_planes);
-    }
-    g->tags_on = g->pl_on && !(off & kOffTags);
-    g->spin_limit = (unsigned)env_int("ZGPT2_TAG_SPIN_LIMIT", 1 << 20);
-    g->tail_off = (unsigned)off & kStepPathsAtCreate;
-    // one sequence on the fp32 cache: ln_1 + c_attn and the attention as one launch where c_attn runs on the LayerNorm-folding
-    // kernel (ZGPT2_DECODE_PATHS_OFF kOffFusedAttn: two launches)
-    if (batch == 1 && !(off & kOffFusedAttn) && c.n_layer <= 127) {
-        const GemvArgs ca = c_attn_args(g, y, 0, modes_of(g));
-        g->fused_on = attn_qkv_ok(ca, gemv_plan(ca, g->wt), attn_args(g, y, (int)c.context_size));
-    }
-    ZG_REQUIRE(g->lm_grid <= 4096, ZG_ERR_UNSUPPORTED, "lm_head grid %d exceeds the argmax partial buffer", g->lm_grid);
-    // (the control mirror and, 256 bytes behind it, the fault word of the tagged hand-overs: pinned, written by the kernels)
-    e = hipHostMalloc(reinterpret_cast<void**>(&g->h_ctrl), sizeof(StepCtrl) + 512, hipHostMallocDefault);
+    ZG_TRY(decide_step_modes(g));
+    // (the control mirror and, in the same block, the fault word of the tagged hand-overs: pinned, written by the kernels)
+    e = hipHostMalloc(reinterpret_cast<void**>(&g->h_ctrl), sizeof(PinnedCtrl), hipHostMallocDefault);
     // (h_ints, and behind it the staging of the penalties' prior / history: the same shape)
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_ints), 2 * (batch * c.context_size + batch) * sizeof(int), hipHostMallocDefault);
     // (the mirror of the log-probability record: a fetch copies its columns through it)
     if (e == hipSuccess)
-        e = hipHostMalloc(reinterpret_cast<void**>(&g->h_lp), batch * c.context_size * (1 + 2 * ZG_LOGPROBS_TOP_MAX) * sizeof(float), hipHostMallocDefault);
+        e = hipHostMalloc(reinterpret_cast<void**>(&g->lp.h_rec), batch * c.context_size * (1 + 2 * ZG_LOGPROBS_TOP_MAX) * sizeof(float), hipHostMallocDefault);
     // (the stop stage's block: a few hundred bytes, always there)
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_stop), sizeof(*g->h_stop), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->stop.pinned), sizeof(*g->stop.pinned), hipHostMallocDefault);
     // (the edit stage's mirror: the bias table and the keep bitmap)
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->h_edit), edit_block_bytes(c.vocab_size), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->edit.h_block), edit_block_bytes(c.vocab_size), hipHostMallocDefault);
     if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(control mirrors)", __FILE__, __LINE__);
-    g->edit_build.assign(edit_block_bytes(c.vocab_size), 0);
-    memset(g->h_stop, 0, sizeof(*g->h_stop));
-    static_assert(sizeof(StepCtrl) + sizeof(SampleParams) <= 256, "the fault word sits 256 bytes behind the control mirror");
-    g->h_samp = reinterpret_cast<SampleParams*>(reinterpret_cast<char*>(g->h_ctrl) + 128);  // (same pinned block)
-    g->fault = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g->h_ctrl) + 256);
-    *g->fault = 0;
-    g->h_pen = reinterpret_cast<PenParams*>(reinterpret_cast<char*>(g->h_ctrl) + 384);  // (behind zg_gpt_sample's uniforms at 320)
-    g->h_prior = g->h_ints + batch * c.context_size + batch;
-    g->h_lp_top = reinterpret_cast<int*>(reinterpret_cast<char*>(g->h_ctrl) + 416);  // (behind h_pen)
+    g->edit.build.assign(edit_block_bytes(c.vocab_size), 0);
+    memset(g->stop.pinned, 0, sizeof(*g->stop.pinned));
+    g->samp.h_params = &g->h_ctrl->samp;
+    g->hand.fault = &g->h_ctrl->fault;
+    *g->hand.fault = 0;
+    g->pen.h_params = &g->h_ctrl->pen;
+    g->pen.h_prior = g->h_ints + batch * c.context_size + batch;
+    g->lp.h_top = &g->h_ctrl->top_n;
     ZG_REQUIRE(!(g->flags & ZG_GPT_PENALIZED_GENERATE) || c.context_size <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED,
                "ZG_GPT_PENALIZED_GENERATE: context_size %zu beyond the %d tokens the penalty kernel's LDS table holds", c.context_size, kPenMaxHistory);
     {   // decode steps per graph in the generate loop: a graph launch costs ~7 us of idle queue (124M: 224.8 us per token
         // with 1 step per graph, 220.4 with 2 / 4, 218.3 with 8, 219.5 with 16)
         const int k = env_int("ZGPT2_GRAPH_STEPS", 8);
-        g->graph_steps = (k == 2 || k == 4 || k == 8 || k == 16 || k == 32 || k == 64) ? (size_t)k : 1;
+        g->graph.steps = (k == 2 || k == 4 || k == 8 || k == 16 || k == 32 || k == 64) ? (size_t)k : 1;
     }
-    g->n_buckets = (c.context_size + 63) / 64;
-    g->graphs.assign(kStepShapes * g->n_buckets, nullptr);
+    g->graph.n_buckets = (c.context_size + 63) / 64;
+    g->graph.execs.assign(kStepShapes * g->graph.n_buckets, nullptr);
     // every decode graph is captured and instantiated here, not on the first forward that needs it
     ZG_TRY(setup_prefetcher(g));
     ZG_TRY(capture_all(g, gs(g)));
@@ -376,12 +349,12 @@ int check_fault(zg_gpt* g) {
     // both words are read and cleared before anything is reported: a tag fault left latched behind a stream-K fault of the same
     // drain would be charged to a later, healthy call
     unsigned sk = 0, tag = 0;
-    if (g->sk_used) {  // a whole-prompt pass may have handed half tiles over inside gemm_s4: did a consumer give up waiting?
-        g->sk_used = false;
+    if (g->pass.sk_used) {  // a whole-prompt pass may have handed half tiles over inside gemm_s4: did a consumer give up waiting?
+        g->pass.sk_used = false;
         ZG_TRY(gemm_s4_fault(&sk));
     }
-    if (g->tags_on || g->fused_on) {
-        volatile unsigned* f = g->fault;
+    if (g->modes.tags || g->modes.fused) {
+        volatile unsigned* f = g->hand.fault;
         tag = *f;
         if (tag) *f = 0;
     }
@@ -390,7 +363,7 @@ int check_fault(zg_gpt* g) {
         return ZG_ERR_HIP;
     }
     if (tag) {
-        set_error("a tagged hand-over of the decode step timed out (a workgroup waited %u polls for its writers): results discarded", g->spin_limit);
+        set_error("a tagged hand-over of the decode step timed out (a workgroup waited %u polls for its writers): results discarded", g->hand.spin_limit);
         return ZG_ERR_HIP;
     }
     return ZG_OK;
@@ -403,25 +376,26 @@ int check_fault(zg_gpt* g) {
 // The rule holds while the device runs fewer than two steps per counted one: every path that advances the epoch counts its steps
 // here (an upper bound is fine), and tests/test_handle_age_gpu.py holds each to that (zg_debug_gpt_age_state).
 int note_steps(zg_gpt* g, size_t n, hipStream_t s) {
-    if (!g->tags_on && !g->fused_on) return ZG_OK;
-    g->epochs_since_clear += n;
-    g->steps_counted += n;
-    if (g->epochs_since_clear < ((size_t)1 << 23)) return ZG_OK;
-    g->epochs_since_clear = n;
-    ++g->tag_clears;
-    ZG_HIP(hipMemsetAsync(g->sk_tag, 0, g->sk_tag_bytes, s));
-    ZG_HIP(hipMemsetAsync(g->part_tag, 0, g->part_tag_bytes, s));
-    ZG_HIP(hipMemsetAsync(g->qkv_tag, 0, g->qkv_tag_bytes, s));
+    if (!g->modes.tags && !g->modes.fused) return ZG_OK;
+    g->hand.epochs_since_clear += n;
+    g->hand.steps_counted += n;
+    if (g->hand.epochs_since_clear < ((size_t)1 << 23)) return ZG_OK;
+    g->hand.epochs_since_clear = n;
+    ++g->hand.tag_clears;
+    ZG_HIP(hipMemsetAsync(g->hand.sk_tag, 0, g->hand.sk_tag_bytes, s));
+    ZG_HIP(hipMemsetAsync(g->hand.part_tag, 0, g->hand.part_tag_bytes, s));
+    ZG_HIP(hipMemsetAsync(g->hand.qkv_tag, 0, g->hand.qkv_tag_bytes, s));
     return ZG_OK;
 }
 
 // The control block of the steps enqueued next, through its pinned mirror (n_partials is always the lm_head grid).
 int stage_ctrl(zg_gpt* g, size_t step, size_t seq_len, int mode, hipStream_t s) {
-    g->h_ctrl->step = (int)step;
-    g->h_ctrl->seq_len = (int)seq_len;
-    g->h_ctrl->mode = mode;
-    g->h_ctrl->n_partials = g->lm_grid;
-    ZG_HIP(hipMemcpyAsync(g->ctrl, g->h_ctrl, sizeof(StepCtrl), hipMemcpyHostToDevice, s));
+    StepCtrl& h = g->h_ctrl->ctrl;
+    h.step = (int)step;
+    h.seq_len = (int)seq_len;
+    h.mode = mode;
+    h.n_partials = g->lm_grid;
+    ZG_HIP(hipMemcpyAsync(g->ctrl, &h, sizeof(StepCtrl), hipMemcpyHostToDevice, s));
     return ZG_OK;
 }
 

@@ -98,8 +98,8 @@ int tap_class(const zg_gpt* g, StepTaps* t, int cls, size_t l, unsigned flags, h
     auto whole = [&](int buffer, int type, const void* src, size_t bytes, unsigned f) { return tap_put(t, cls, l, buffer, type, f, src, 1, bytes, bytes, s); };
     auto x_side = [&](bool planes_written) -> int {  // x and, with planes on, what travels with it
         ZG_TRY(whole(ZG_TAP_X, ZG_TAP_F32, g->x, B * E * 4, flags));
-        if (g->pl_on) ZG_TRY(whole(ZG_TAP_XP, ZG_TAP_BF16, g->xp, E * 48, flags | (planes_written ? 0u : ZG_TAP_NOT_WRITTEN)));
-        if (g->st_on) ZG_TRY(whole(ZG_TAP_XST, ZG_TAP_F32, g->xst, ((E + 15) / 16) * 8 * 2 * 4, flags | (planes_written ? 0u : ZG_TAP_NOT_WRITTEN)));
+        if (g->modes.pl) ZG_TRY(whole(ZG_TAP_XP, ZG_TAP_BF16, g->xp, E * 48, flags | (planes_written ? 0u : ZG_TAP_NOT_WRITTEN)));
+        if (g->modes.st) ZG_TRY(whole(ZG_TAP_XST, ZG_TAP_F32, g->xst, ((E + 15) / 16) * 8 * 2 * 4, flags | (planes_written ? 0u : ZG_TAP_NOT_WRITTEN)));
         return ZG_OK;
     };
     auto caches = [&]() { return tap_caches(g, t, cls, l, flags, t->seq_len, s); };  // positions < seq_len
@@ -110,11 +110,11 @@ int tap_class(const zg_gpt* g, StepTaps* t, int cls, size_t l, unsigned flags, h
             ZG_TRY(whole(ZG_TAP_Q, ZG_TAP_F32, g->q, B * E * 4, flags));
             return caches();
         case 2:
-            if (g->pl_on) return whole(ZG_TAP_AP, ZG_TAP_BF16, g->ap, E * 48, flags);
+            if (g->modes.pl) return whole(ZG_TAP_AP, ZG_TAP_BF16, g->ap, E * 48, flags);
             return whole(ZG_TAP_PART, ZG_TAP_F32, g->part, B * H * g->max_splits * kPartStride * 4, flags);
         case 3: return x_side(true);
         case 4:
-            if (g->pl_on) return whole(ZG_TAP_HP, ZG_TAP_BF16, g->hp, 4 * E * 48, flags);
+            if (g->modes.pl) return whole(ZG_TAP_HP, ZG_TAP_BF16, g->hp, 4 * E * 48, flags);
             return whole(ZG_TAP_H4, ZG_TAP_F32, g->h4, B * 4 * E * 4, flags);
         case 5: return x_side(l + 1 < g->cfg.n_layer);
         default:
@@ -147,7 +147,7 @@ int zg_debug_gpt_step_taps(zg_gpt* g, size_t seq_len, const size_t* tokens, size
     *arena_used = cap;
     *n_entries = plan.table.size();
     if (info && n_info >= ZG_TAP_INFO_INTS) {
-        const int v[ZG_TAP_INFO_INTS] = {g->pl_on, g->st_on, g->tags_on, g->fused_on, g->max_splits, g->lm_grid, bucket_t_hi(g, seq_len), g->kv_mode, g->wt};
+        const int v[ZG_TAP_INFO_INTS] = {g->modes.pl, g->modes.st, g->modes.tags, g->modes.fused, g->max_splits, g->lm_grid, bucket_t_hi(g, seq_len), g->kv_mode, g->wt};
         memcpy(info, v, sizeof(v));
     }
     if (!arena_out) return ZG_OK;
@@ -178,22 +178,22 @@ int zg_debug_gpt_pass_taps(zg_gpt* g, size_t past_len, const size_t* tokens, siz
                            size_t table_len, size_t* n_entries, int* info, size_t n_info) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && tokens && arena_used && n_entries, ZG_ERR_ARG, "debug_gpt_pass_taps: null argument");
-    ZG_REQUIRE(g->pf_x != nullptr, ZG_ERR_UNSUPPORTED, "debug_gpt_pass_taps: the handle was created with ZG_GPT_NO_PREFILL");
+    ZG_REQUIRE(g->pass.x != nullptr, ZG_ERR_UNSUPPORTED, "debug_gpt_pass_taps: the handle was created with ZG_GPT_NO_PREFILL");
     const size_t C = g->cfg.context_size, E = g->cfg.n_embed, L = g->cfg.n_layer, B = g->batch;
     ZG_REQUIRE(n_tokens >= 1 && past_len + n_tokens <= C, ZG_ERR_SHAPE, "debug_gpt_pass_taps: %zu tokens behind %zu positions (context %zu)", n_tokens, past_len, C);
-    ZG_REQUIRE(!score || g->sc_logits != nullptr, ZG_ERR_UNSUPPORTED, "debug_gpt_pass_taps: the handle was created without ZG_GPT_SCORE");
+    ZG_REQUIRE(!score || g->score.logits != nullptr, ZG_ERR_UNSUPPORTED, "debug_gpt_pass_taps: the handle was created without ZG_GPT_SCORE");
     // an upper bound of the pass's taps: per layer two cache taps of K and V (at most 4 bytes an element, and the B24 byte plane
-    // within that), x twice, pf_a four times, qkv, pf_h, three plans and the geometry; class 0 and 1 once; the score stage
+    // within that), x twice, pass.a four times, qkv, pass.h, three plans and the geometry; class 0 and 1 once; the score stage
     const size_t M = B * n_tokens, T = std::min(C, past_len + n_tokens + kPassTapRowsBehind), blocks = (M + kScoreRows - 1) / kScoreRows;
     const size_t per_layer = 4 * B * E * T * 4 + 2 * M * E * 4 + 4 * M * kSplit * E * 2 + M * 3 * E * 4 + M * kSplit * 4 * E * 2;
     const size_t entries = 2 + L * 24 + (score ? 1 + 3 * blocks : 0);
-    const size_t cap = L * per_layer + M * E * 4 + M * kSplit * E * 2 + (score ? M * kSplit * E * 2 + M * g->sc_v64 * 4 : 0) + 256 * (entries + 1);
+    const size_t cap = L * per_layer + M * E * 4 + M * kSplit * E * 2 + (score ? M * kSplit * E * 2 + M * g->score.v64 * 4 : 0) + 256 * (entries + 1);
     *arena_used = cap;
     *n_entries = entries;
     if (info && n_info >= ZG_PASS_INFO_INTS) {
         const bool f32w = g->wt != WT_BF16;
         const int v[ZG_PASS_INFO_INTS] = {f32w ? kSplit : (g->flags & ZG_GPT_PREFILL_2PLANE) ? 2 : kSplit, g->kv_mode, g->wt,
-                                          (int)std::min(g->pf_ws_floats, (size_t)INT_MAX), !f32w && g->sk_flags != nullptr, (int)g->sc_v64, (int)kScoreRows};
+                                          (int)std::min(g->pass.ws_floats, (size_t)INT_MAX), !f32w && g->pass.sk_flags != nullptr, (int)g->score.v64, (int)kScoreRows};
         memcpy(info, v, sizeof(v));
     }
     if (!arena_out) return ZG_OK;
@@ -648,7 +648,7 @@ int zg_gpt_time_kernel(zg_gpt* g, int which_and_options, int iters, float* avg_u
         // tagged hand-overs: a new epoch per replay and a launch id per chain position, so that every merging split / slice
         // waits for ITS writers as in a real step (one more tiny launch per 64)
         int st = ZG_OK;
-        if ((g->tags_on || g->fused_on) && which != 0) st = launch_epoch_bump(g->epoch, s);
+        if ((g->modes.tags || g->modes.fused) && which != 0) st = launch_epoch_bump(g->hand.epoch, s);
         StepOpts o;
         o.only = which;
         for (int i = 0; i < chain && st == ZG_OK; ++i) {
@@ -686,11 +686,11 @@ int zg_gpt_time_kernel(zg_gpt* g, int which_and_options, int iters, float* avg_u
 int zg_debug_gpt_age(zg_gpt* g, size_t n_steps, int set_sk_epoch, unsigned sk_epoch) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g, ZG_ERR_ARG, "debug_gpt_age: null argument");
-    if (set_sk_epoch) g->sk_epoch = sk_epoch;
-    if (!g->tags_on && !g->fused_on) return ZG_OK;
+    if (set_sk_epoch) g->pass.sk_epoch = sk_epoch;
+    if (!g->modes.tags && !g->modes.fused) return ZG_OK;
     hipStream_t s = gs(g);
     ZG_TRY(note_steps(g, n_steps, s));
-    return launch_epoch_add(g->epoch, (unsigned)n_steps, s);
+    return launch_epoch_add(g->hand.epoch, (unsigned)n_steps, s);
 }
 
 int zg_debug_gpt_age_state(zg_gpt* g, unsigned long long* out, size_t n_out) {
@@ -698,13 +698,13 @@ int zg_debug_gpt_age_state(zg_gpt* g, unsigned long long* out, size_t n_out) {
     ZG_REQUIRE(g && out && n_out >= ZG_AGE_STATE_WORDS, ZG_ERR_ARG, "debug_gpt_age_state: need %d words", ZG_AGE_STATE_WORDS);
     ZG_HIP(hipStreamSynchronize(gs(g)));
     unsigned epoch = 0;
-    ZG_HIP(hipMemcpy(&epoch, g->epoch, sizeof(unsigned), hipMemcpyDeviceToHost));
+    ZG_HIP(hipMemcpy(&epoch, g->hand.epoch, sizeof(unsigned), hipMemcpyDeviceToHost));
     out[0] = epoch;
-    out[1] = g->epochs_since_clear;
-    out[2] = g->steps_counted;
-    out[3] = g->tag_clears;
-    out[4] = g->sk_epoch;
-    out[5] = g->sk_restarts;
+    out[1] = g->hand.epochs_since_clear;
+    out[2] = g->hand.steps_counted;
+    out[3] = g->hand.tag_clears;
+    out[4] = g->pass.sk_epoch;
+    out[5] = g->pass.sk_restarts;
     return ZG_OK;
 }
 
@@ -712,8 +712,8 @@ int zg_debug_gpt_tag_census(zg_gpt* g, unsigned epoch24, unsigned sk_flag_value,
     ZG_TRY(require_init());
     ZG_REQUIRE(g && counts && n_counts >= 4 && epoch24 < (1u << 24), ZG_ERR_ARG, "debug_gpt_tag_census: need 4 counts and a 24-bit epoch");
     ZG_HIP(hipStreamSynchronize(gs(g)));
-    const unsigned long long* const words[3] = {g->sk_tag, g->part_tag, g->qkv_tag};
-    const size_t bytes[3] = {g->sk_tag_bytes, g->part_tag_bytes, g->qkv_tag_bytes};
+    const unsigned long long* const words[3] = {g->hand.sk_tag, g->hand.part_tag, g->hand.qkv_tag};
+    const size_t bytes[3] = {g->hand.sk_tag_bytes, g->hand.part_tag_bytes, g->hand.qkv_tag_bytes};
     std::vector<unsigned long long> h;
     for (int i = 0; i < 3; ++i) {
         h.resize(bytes[i] / 8);
@@ -725,9 +725,9 @@ int zg_debug_gpt_tag_census(zg_gpt* g, unsigned epoch24, unsigned sk_flag_value,
         }
     }
     counts[3] = 0;
-    if (g->sk_flags != nullptr) {
+    if (g->pass.sk_flags != nullptr) {
         unsigned f[kSkFlagWords];
-        ZG_HIP(hipMemcpy(f, g->sk_flags, sizeof(f), hipMemcpyDeviceToHost));
+        ZG_HIP(hipMemcpy(f, g->pass.sk_flags, sizeof(f), hipMemcpyDeviceToHost));
         for (const unsigned w : f) counts[3] += w == sk_flag_value;
     }
     return ZG_OK;
@@ -737,12 +737,12 @@ int zg_debug_prefetch_stats(zg_gpt* g, unsigned* out, size_t n_out) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && out && n_out >= 25, ZG_ERR_ARG, "prefetch_stats: need 25 words");
     memset(out, 0, n_out * sizeof(unsigned));
-    out[0] = g->pf_on ? (g->pf_stalled ? 2u : 1u) : 0u;
-    if (!g->pf_on) return ZG_OK;
+    out[0] = g->prefetch.on ? (g->prefetch.stalled ? 2u : 1u) : 0u;
+    if (!g->prefetch.on) return ZG_OK;
     ZG_HIP(hipStreamSynchronize(gs(g)));
-    ZG_HIP(hipStreamSynchronize(g->pf_stream));
+    ZG_HIP(hipStreamSynchronize(g->prefetch.stream));
     PfCtl h;
-    ZG_HIP(hipMemcpy(&h, g->pf_ctl, sizeof(PfCtl), hipMemcpyDeviceToHost));
+    ZG_HIP(hipMemcpy(&h, g->prefetch.ctl, sizeof(PfCtl), hipMemcpyDeviceToHost));
     for (int x = 0; x < 8; ++x) {
         out[1 + x] = h.ticket[x];
         out[9 + x] = h.exit_reason[x];

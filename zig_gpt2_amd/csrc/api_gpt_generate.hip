@@ -18,10 +18,10 @@ namespace zg {  // offered to the other units: api_gpt.h declares them
 
 // top_n of the record the call in flight writes, through its pinned word into the arena: from here on a fetch finds that record
 int stage_top_n(zg_gpt* g, size_t top_n, hipStream_t s) {
-    g->lp_valid = true;
-    g->lp_top_n = top_n;
-    *g->h_lp_top = (int)top_n;
-    ZG_HIP(hipMemcpyAsync(g->lp_top, g->h_lp_top, sizeof(int), hipMemcpyHostToDevice, s));
+    g->lp.valid = true;
+    g->lp.top_n = top_n;
+    *g->lp.h_top = (int)top_n;
+    ZG_HIP(hipMemcpyAsync(g->lp.top, g->lp.h_top, sizeof(int), hipMemcpyHostToDevice, s));
     return ZG_OK;
 }
 
@@ -29,12 +29,12 @@ int stage_top_n(zg_gpt* g, size_t top_n, hipStream_t s) {
 
 extern "C" {
 
-// The set built in edit_build through its pinned mirror into the arena.  PRECONDITION: nothing in flight reads the mirror (every
+// The set built in edit.build through its pinned mirror into the arena.  PRECONDITION: nothing in flight reads the mirror (every
 // edited call drains, or begins by draining).
 static int stage_edits(zg_gpt* g, hipStream_t s) {
-    const size_t bytes = g->edit_build.size();
-    memcpy(g->h_edit, g->edit_build.data(), bytes);
-    ZG_HIP(hipMemcpyAsync(g->edit_tab, g->h_edit, bytes, hipMemcpyHostToDevice, s));
+    const size_t bytes = g->edit.build.size();
+    memcpy(g->edit.h_block, g->edit.build.data(), bytes);
+    ZG_HIP(hipMemcpyAsync(g->edit.tab, g->edit.h_block, bytes, hipMemcpyHostToDevice, s));
     return ZG_OK;
 }
 
@@ -67,15 +67,15 @@ static int check_history(const zg_gpt* g, const size_t* tokens, size_t stride, c
 // flight reads the mirrors (every penalised call drains, or begins by draining).
 static int stage_penalties(zg_gpt* g, const zg_logit_penalties& p, size_t past, const size_t* tokens, size_t stride, const size_t* lens, hipStream_t s) {
     const size_t C = g->cfg.context_size, B = g->batch;
-    *g->h_pen = PenParams{p.repetition, p.presence, p.frequency, (int)past};
-    int* h_len = g->h_prior + B * C;
+    *g->pen.h_params = PenParams{p.repetition, p.presence, p.frequency, (int)past};
+    int* h_len = g->pen.h_prior + B * C;
     for (size_t b = 0; b < B; ++b) {
         h_len[b] = tokens ? (int)lens[b] : 0;
-        for (size_t i = 0; tokens && i < lens[b]; ++i) g->h_prior[b * C + i] = (int)tokens[b * stride + i];
+        for (size_t i = 0; tokens && i < lens[b]; ++i) g->pen.h_prior[b * C + i] = (int)tokens[b * stride + i];
     }
-    ZG_HIP(hipMemcpyAsync(g->pen, g->h_pen, sizeof(PenParams), hipMemcpyHostToDevice, s));
-    if (tokens) ZG_HIP(hipMemcpyAsync(g->prior, g->h_prior, B * C * sizeof(int), hipMemcpyHostToDevice, s));
-    ZG_HIP(hipMemcpyAsync(g->prior_len, h_len, B * sizeof(int), hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(g->pen.params, g->pen.h_params, sizeof(PenParams), hipMemcpyHostToDevice, s));
+    if (tokens) ZG_HIP(hipMemcpyAsync(g->pen.prior, g->pen.h_prior, B * C * sizeof(int), hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(g->pen.prior_len, h_len, B * sizeof(int), hipMemcpyHostToDevice, s));
     return ZG_OK;
 }
 
@@ -95,7 +95,7 @@ static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n
         ZG_TRY(check_history(g, history, history_stride, history_lens, 0, who));
     }
     bool edit_on = false;
-    ZG_TRY(build_edits(edits, g->cfg.vocab_size, who, g->edit_build.data(), &edit_on));
+    ZG_TRY(build_edits(edits, g->cfg.vocab_size, who, g->edit.build.data(), &edit_on));
     const bool pen_on = pen && !penalties_off(*pen);
     if (pen_on || edit_on) ZG_HIP(hipStreamSynchronize(gs(g)));  // (an enqueued generation may still be reading the pinned mirrors; idle otherwise)
     ZG_REQUIRE(tokens && tokens_out, ZG_ERR_ARG, "gpt_sample: bad argument");
@@ -107,16 +107,15 @@ static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n
     hipStream_t s = gs(g);
     if (pen_on) ZG_TRY(stage_penalties(g, *pen, 0, history, history_stride, history_lens, s));
     if (edit_on) ZG_TRY(stage_edits(g, s));
-    // (pinned, 320 bytes into the control block: h_ints[0 .. B) is still being read by the forward's token upload)
-    float* h_u = reinterpret_cast<float*>(reinterpret_cast<char*>(g->h_ctrl) + 320);
+    float* h_u = g->h_ctrl->uniforms;  // (pinned: h_ints[0 .. B) is still being read by the forward's token upload)
     // (no uniforms: the counter PRNG the device loop's sampler draws from, zg_common.h)
     for (size_t b = 0; b < B; ++b) h_u[b] = uniforms ? uniforms[b] : counter_uniform(seed, seq_len, b);
     SamplerChain c = handle_chain(g, false);
     float* d_u = g->q;  // scratch: q is dead after the forward
     ZG_HIP(hipMemcpyAsync(d_u, h_u, B * sizeof(float), hipMemcpyHostToDevice, s));
-    // (h_samp: nothing in flight reads it, forward_enqueue's callers drain; the plain sampler takes its temperature by value)
-    const SamplerMode mode = fill_sample_params(g->h_samp, V, *opt, seed, edits->min_p);
-    if (threshold_sampler(mode)) ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
+    // (samp.h_params: nothing in flight reads it, forward_enqueue's callers drain; the plain sampler takes its temperature by value)
+    const SamplerMode mode = fill_sample_params(g->samp.h_params, V, *opt, seed, edits->min_p);
+    if (threshold_sampler(mode)) ZG_HIP(hipMemcpyAsync(g->samp.params, g->samp.h_params, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     c.u = d_u, c.temp = opt->temp, c.write_probs = probs_out != nullptr, c.pick = g->cur_token;
     ZG_TRY(emit_sampler_chain(c, StepTail{mode, pen_on, false, false, edit_on}, s));  // main.zig:200-206
     ZG_HIP(hipMemcpyAsync(g->h_ints + B, g->cur_token, B * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -163,7 +162,7 @@ int zg_gpt_sample_edit(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n
 
 // A generation in three parts, so that several handles' generations can be fed to their streams side by side
 // (zg_gpt_generate_enqueue_many): gen_begin — prompts, cache clearing, the whole-prompt pass, the prefetcher's start;
-// gen_pump — ONE graph launch (graph_steps decode steps) or one single step, false when nothing is left; gen_end — the
+// gen_pump — ONE graph launch (graph.steps decode steps) or one single step, false when nothing is left; gen_end — the
 // prefetcher's stop word and the record of the last pick.  After a successful gen_begin, gen_end must run (also on failure:
 // the prefetcher must not wait for steps that never come).  A generation with stop conditions is the same three parts:
 // gen_pump paces itself by the stop stage's progress word and feeds nothing once every row has finished (stop_pace), and gen_end
@@ -195,7 +194,7 @@ struct GenRequest {
     // stop conditions, checked (check_stop); stop_on false: the request is what it was
     bool stop_on = false;
     zg_stop_conditions stop{};
-    // logit edits, checked, the set built in the ONE handle's edit_build: edit_on — the
+    // logit edits, checked, the set built in the ONE handle's edit.build: edit_on — the
     // edit stage runs; min_p — the sampler's threshold (0: off).  Both off: the request is what it was
     bool edit_on = false;
     float min_p = 0.0f;
@@ -243,33 +242,33 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     // The positions every sequence has a prompt token for go through the Blocks together (prefill); the
     // rest of the loop is main.zig:330-338 one position at a time.
     size_t first = 0;
-    if (g->pf_x != nullptr && min_prompt >= prefill_min())
+    if (g->pass.x != nullptr && min_prompt >= prefill_min())
         first = min_prompt < n_steps ? min_prompt : n_steps;
     const bool edit_on = r.edit_on && r.mode != GREEDY;
-    g->gen_tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on, edit_on};  // (normalized: pen_on / edit_on only with a sampler, and the steps it is for have lm_head)
-    g->stop_valid = false;
-    g->gen_stop = r.stop_on;
+    g->gen.tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on, edit_on};  // (normalized: pen_on / edit_on only with a sampler, and the steps it is for have lm_head)
+    g->gen.stop_valid = false;
+    g->gen.stop = r.stop_on;
     if (r.stop_on) {  // the conditions of this call; no row has finished; the stage has seen nothing (the stream is drained: the words are the host's)
-        fill_stop(&g->h_stop->conds, r.stop);
-        ZG_HIP(hipMemcpyAsync(g->stop, &g->h_stop->conds, sizeof(StopConds), hipMemcpyHostToDevice, s));
-        ZG_HIP(hipMemsetAsync(g->stop_fin, 0xff, kStopMaxRows * 4, s));
-        ZG_HIP(hipMemsetAsync(g->stop_reason, 0xff, kStopMaxRows * 4, s));
-        g->h_stop->host.progress = g->h_stop->host.done_col = 0u;
-        g->gen_lookahead = r.stop.lookahead ? std::min(r.stop.lookahead, C) : kStopLookahead;  // (beyond the context: never waits)
+        fill_stop(&g->stop.pinned->conds, r.stop);
+        ZG_HIP(hipMemcpyAsync(g->stop.conds, &g->stop.pinned->conds, sizeof(StopConds), hipMemcpyHostToDevice, s));
+        ZG_HIP(hipMemsetAsync(g->stop.fin, 0xff, kStopMaxRows * 4, s));
+        ZG_HIP(hipMemsetAsync(g->stop.reason, 0xff, kStopMaxRows * 4, s));
+        g->stop.pinned->host.progress = g->stop.pinned->host.done_col = 0u;
+        g->gen.lookahead = r.stop.lookahead ? std::min(r.stop.lookahead, C) : kStopLookahead;  // (beyond the context: never waits)
     }
     if (r.mode != GREEDY) {
-        g->gen_tail.sampler = fill_sample_params(g->h_samp, V, r.opt, r.seed, r.min_p);
-        ZG_HIP(hipMemcpyAsync(g->samp, g->h_samp, sizeof(SampleParams), hipMemcpyHostToDevice, s));
+        g->gen.tail.sampler = fill_sample_params(g->samp.h_params, V, r.opt, r.seed, r.min_p);
+        ZG_HIP(hipMemcpyAsync(g->samp.params, g->samp.h_params, sizeof(SampleParams), hipMemcpyHostToDevice, s));
     }
     if (pen_on) ZG_TRY(stage_penalties(g, r.pen, past, r.prior, r.prior_stride, r.prior_lens, s));
     if (edit_on) ZG_TRY(stage_edits(g, s));
-    g->lp_valid = false;
+    g->lp.valid = false;
     if (r.lp_on) {
         ZG_TRY(stage_top_n(g, r.top_n, s));
         // the new columns no step with lm_head reaches (the whole-prompt pass, steps that only feed a prompt token) record prompt
         // tokens: NaN (every byte 0xff); the stage itself writes the NaN of a longer row's prompt columns
         const size_t fed = std::min(min_prompt, n_steps);
-        ZG_HIP(hipMemset2DAsync(g->lp_rec.logprob + past, C * sizeof(float), 0xff, fed * sizeof(float), B, s));
+        ZG_HIP(hipMemset2DAsync(g->lp.rec.logprob + past, C * sizeof(float), 0xff, fed * sizeof(float), B, s));
     }
     ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(g->prompt_len, g->h_ints + B * C, B * sizeof(int), hipMemcpyHostToDevice, s));
@@ -287,28 +286,28 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     // against it): all of create's on a stream create did not see, and this generation's own tail — whatever create did not
     // capture of it (graph_exec skips what exists) — for the buckets of its steps with lm_head
     if (!(g->flags & ZG_GPT_NO_GRAPH) && s != nullptr) {
-        if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
-        if (!(g->gen_tail == StepTail{}) && min_prompt < n_steps)
-            ZG_TRY(capture_tail(g, g->gen_tail, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
+        if (g->graph.stream != s) ZG_TRY(capture_all(g, s));
+        if (!(g->gen.tail == StepTail{}) && min_prompt < n_steps)
+            ZG_TRY(capture_tail(g, g->gen.tail, bucket_of(past + std::max(first, min_prompt) + 1), bucket_of(past + n_steps), s));
     }
     ZG_TRY(note_steps(g, n_steps, s));
     ZG_TRY(pf_start(g, past + n_steps, s));
-    g->gen_pos = past + first;  // absolute, as gen_n and gen_min_prompt: gen_pump's steps, buckets and graph alignment follow the position
-    g->gen_n = past + n_steps;
-    g->gen_min_prompt = past + min_prompt;
-    g->gen_since_sync = 0;
-    g->gen_open = true;
+    g->gen.pos = past + first;  // absolute, as gen.n and gen.min_prompt: gen_pump's steps, buckets and graph alignment follow the position
+    g->gen.n = past + n_steps;
+    g->gen.min_prompt = past + min_prompt;
+    g->gen.since_sync = 0;
+    g->gen.open = true;
     return ZG_OK;
 }
 
 // A stop generation before each piece it feeds: *ended when every row has finished — nothing more is fed —, else
-// wait while the host is more than gen_lookahead steps ahead of the stop stage.  The stage counts steps with lm_head only, so the
-// steps below gen_min_prompt (the default tail) are not paced over.  progress is read BEFORE done_col and the kernel stores them
+// wait while the host is more than gen.lookahead steps ahead of the stop stage.  The stage counts steps with lm_head only, so the
+// steps below gen.min_prompt (the default tail) are not paced over.  progress is read BEFORE done_col and the kernel stores them
 // the other way round: a done_col still 0 then means that the finishing step had not announced itself when progress was read, which
 // is what bounds `end`.  The wait is bounded by the device's state, not by a count: whenever the word has stood still over 16 polls
 // the stream is asked, and a drained or failed stream ends the wait — a faulted device ends the call instead of spinning the host.
 static int stop_pace(zg_gpt* g, hipStream_t s, bool* ended) {
-    StopHost* const h = &g->h_stop->host;
+    StopHost* const h = &g->stop.pinned->host;
     *ended = false;
     unsigned seen = ~0u;  // progress at the last look at the stream
     for (unsigned polls = 0;; ++polls) {
@@ -318,7 +317,7 @@ static int stop_pace(zg_gpt* g, hipStream_t s, bool* ended) {
             *ended = true;
             return ZG_OK;
         }
-        if (g->gen_pos <= std::max((size_t)p, g->gen_min_prompt) + g->gen_lookahead) return ZG_OK;
+        if (g->gen.pos <= std::max((size_t)p, g->gen.min_prompt) + g->gen.lookahead) return ZG_OK;
         if (polls < 64) continue;  // (a short wait costs no system call)
         if (polls % 16 == 0) {  // the stream is asked only while the word stands still: a healthy device moves it every step
             if (p == seen) {
@@ -336,33 +335,33 @@ static int stop_pace(zg_gpt* g, hipStream_t s, bool* ended) {
 
 static int gen_pump(zg_gpt* g, bool* more) {
     hipStream_t s = gs(g);
-    const size_t C = g->cfg.context_size, n_steps = g->gen_n, st = g->gen_pos;
+    const size_t C = g->cfg.context_size, n_steps = g->gen.n, st = g->gen.pos;
     *more = false;
     if (st >= n_steps) return ZG_OK;
-    if (g->gen_stop && st > g->gen_min_prompt) {  // (behind the first step with lm_head: nothing can have finished before)
+    if (g->gen.stop && st > g->gen.min_prompt) {  // (behind the first step with lm_head: nothing can have finished before)
         bool ended = false;
         ZG_TRY(stop_pace(g, s, &ended));
         if (ended) return ZG_OK;
     }
-    const size_t K = ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) ? 1 : g->graph_steps;
+    const size_t K = ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) ? 1 : g->graph.steps;
     // ZGPT2_SYNC_EVERY=n (profiling only): drain the stream every n steps — rocprofv3's counter collection has crashed
     // on this stack when tens of thousands of dispatches were queued ahead of it
     static const int sync_every = env_int("ZGPT2_SYNC_EVERY", 0);
-    if (sync_every > 0 && ++g->gen_since_sync >= (size_t)sync_every) {
-        g->gen_since_sync = 0;
+    if (sync_every > 0 && ++g->gen.since_sync >= (size_t)sync_every) {
+        g->gen.since_sync = 0;
         (void)hipStreamSynchronize(s);
     }
-    if (K > 1 && st >= g->gen_min_prompt && st % K == 0 && st + K <= n_steps && st + K <= C) {
-        if (g->graph_stream != s) ZG_TRY(capture_all(g, s));
+    if (K > 1 && st >= g->gen.min_prompt && st % K == 0 && st + K <= n_steps && st + K <= C) {
+        if (g->graph.stream != s) ZG_TRY(capture_all(g, s));
         hipGraphExec_t e;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64); captured by gen_begin (first use: the backstop)
-        ZG_TRY(graph_exec(g, {true, true, g->gen_tail}, bucket_of(st + 1), s, &e));
+        ZG_TRY(graph_exec(g, {true, true, g->gen.tail}, bucket_of(st + 1), s, &e));
         ZG_HIP(hipGraphLaunch(e, s));
-        g->gen_pos = st + K;
+        g->gen.pos = st + K;
     } else {
-        ZG_TRY(run_step(g, st >= g->gen_min_prompt, st + 1, s, g->gen_tail));
-        g->gen_pos = st + 1;
+        ZG_TRY(run_step(g, st >= g->gen.min_prompt, st + 1, s, g->gen.tail));
+        g->gen.pos = st + 1;
     }
-    *more = g->gen_pos < n_steps;
+    *more = g->gen.pos < n_steps;
     return ZG_OK;
 }
 
@@ -375,15 +374,15 @@ static int gen_pump_all(zg_gpt* g) {
 
 static int gen_end(zg_gpt* g, int rs) {
     hipStream_t s = gs(g);
-    g->gen_open = false;
+    g->gen.open = false;
     ZG_TRY(pf_stop(g, s));  // also after a failed launch: the prefetcher must not wait for steps that never come
     ZG_TRY(rs);
     ZG_TRY(launch_embed_step(embed_args(g, 1), s));  // record the pick of the last step
-    if (g->gen_stop) {  // the column actually reached: the one place that corrects what gen_begin set up front
-        g->gen_n = g->cached_len = g->kv_dirty_hi = g->stop_end = g->gen_pos;
-        g->stop_valid = true;
+    if (g->gen.stop) {  // the column actually reached: the one place that corrects what gen_begin set up front
+        g->gen.n = g->cached_len = g->kv_dirty_hi = g->gen.stop_end = g->gen.pos;
+        g->gen.stop_valid = true;
     }
-    g->steps_enqueued = g->gen_n;
+    g->steps_enqueued = g->gen.n;
     return ZG_OK;
 }
 
@@ -474,7 +473,7 @@ static int generate_request(zg_gpt* const* handles, size_t n_handles, const zg_g
         r.stop = *q.stop;
     }
     if (q.edits) {
-        ZG_TRY(build_edits(q.edits, g->cfg.vocab_size, who, g->edit_build.data(), &r.edit_on));
+        ZG_TRY(build_edits(q.edits, g->cfg.vocab_size, who, g->edit.build.data(), &r.edit_on));
         ZG_REQUIRE(q.options || edits_off(*q.edits), ZG_ERR_ARG, "%s: edits without sampler options (greedy picking with edits is top_k = 1)", who);
         r.min_p = q.edits->min_p;
     }
@@ -570,17 +569,17 @@ int zg_gpt_generate_request_enqueue(zg_gpt* g, const zg_generate_request* r) {
 int zg_gpt_generate_stop_result(zg_gpt* g, size_t* end_out, size_t* finish_cols_out, int* reasons_out) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && end_out && finish_cols_out && reasons_out, ZG_ERR_ARG, "generate_stop_result: null argument");
-    ZG_REQUIRE(g->stop_valid, ZG_ERR_ARG, "generate_stop_result: the last generation had no stop conditions");
+    ZG_REQUIRE(g->gen.stop_valid, ZG_ERR_ARG, "generate_stop_result: the last generation had no stop conditions");
     hipStream_t s = gs(g);
-    ZG_HIP(hipMemcpyAsync(g->h_stop->fin, g->stop_fin, g->batch * 4, hipMemcpyDeviceToHost, s));
-    ZG_HIP(hipMemcpyAsync(g->h_stop->reason, g->stop_reason, g->batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(g->stop.pinned->fin, g->stop.fin, g->batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(g->stop.pinned->reason, g->stop.reason, g->batch * 4, hipMemcpyDeviceToHost, s));
     ZG_HIP(hipStreamSynchronize(s));
     ZG_TRY(check_fault(g));
-    *end_out = g->stop_end;
+    *end_out = g->gen.stop_end;
     for (size_t b = 0; b < g->batch; ++b) {
-        const int f = g->h_stop->fin[b];
+        const int f = g->stop.pinned->fin[b];
         finish_cols_out[b] = f < 0 ? ZG_STOP_NONE : (size_t)f;
-        reasons_out[b] = f < 0 ? -1 : g->h_stop->reason[b];
+        reasons_out[b] = f < 0 ? -1 : g->stop.pinned->reason[b];
     }
     return ZG_OK;
 }
@@ -590,21 +589,21 @@ int zg_gpt_generate_fetch_logprobs(zg_gpt* g, size_t first, size_t n, size_t top
     ZG_TRY(require_init());
     ZG_REQUIRE(g && logprobs_out, ZG_ERR_ARG, "generate_fetch_logprobs: null argument");
     const size_t C = g->cfg.context_size, B = g->batch, K = ZG_LOGPROBS_TOP_MAX;
-    ZG_REQUIRE(g->lp_valid, ZG_ERR_ARG, "generate_fetch_logprobs: the last generation recorded no log-probabilities");
-    ZG_REQUIRE(top_n <= g->lp_top_n, ZG_ERR_ARG, "generate_fetch_logprobs: top_n %zu above the %zu the generation recorded", top_n, g->lp_top_n);
+    ZG_REQUIRE(g->lp.valid, ZG_ERR_ARG, "generate_fetch_logprobs: the last generation recorded no log-probabilities");
+    ZG_REQUIRE(top_n <= g->lp.top_n, ZG_ERR_ARG, "generate_fetch_logprobs: top_n %zu above the %zu the generation recorded", top_n, g->lp.top_n);
     ZG_REQUIRE(top_n == 0 || (top_ids_out && top_logprobs_out), ZG_ERR_ARG, "generate_fetch_logprobs: top_n %zu without its outputs", top_n);
     ZG_REQUIRE(first <= C && n <= C - first && logprobs_len >= B * n && (top_n == 0 || top_len >= B * n * top_n), ZG_ERR_SHAPE,
                "generate_fetch_logprobs: positions %zu .. %zu of %zu, %zu and %zu elements", first, first + n, C, logprobs_len, top_len);
     if (n == 0) return ZG_OK;
     hipStream_t s = gs(g);
-    float* h_lp = g->h_lp;
-    int* h_ids = reinterpret_cast<int*>(g->h_lp + B * C);
-    float* h_top = g->h_lp + B * C * (1 + K);
+    float* h_lp = g->lp.h_rec;
+    int* h_ids = reinterpret_cast<int*>(g->lp.h_rec + B * C);
+    float* h_top = g->lp.h_rec + B * C * (1 + K);
     // the columns asked for, packed [batch][n] and [batch][n][20]
-    ZG_HIP(hipMemcpy2DAsync(h_lp, n * 4, g->lp_rec.logprob + first, C * 4, n * 4, B, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpy2DAsync(h_lp, n * 4, g->lp.rec.logprob + first, C * 4, n * 4, B, hipMemcpyDeviceToHost, s));
     if (top_n) {
-        ZG_HIP(hipMemcpy2DAsync(h_ids, n * K * 4, g->lp_rec.top_ids + first * K, C * K * 4, n * K * 4, B, hipMemcpyDeviceToHost, s));
-        ZG_HIP(hipMemcpy2DAsync(h_top, n * K * 4, g->lp_rec.top_logprobs + first * K, C * K * 4, n * K * 4, B, hipMemcpyDeviceToHost, s));
+        ZG_HIP(hipMemcpy2DAsync(h_ids, n * K * 4, g->lp.rec.top_ids + first * K, C * K * 4, n * K * 4, B, hipMemcpyDeviceToHost, s));
+        ZG_HIP(hipMemcpy2DAsync(h_top, n * K * 4, g->lp.rec.top_logprobs + first * K, C * K * 4, n * K * 4, B, hipMemcpyDeviceToHost, s));
     }
     ZG_HIP(hipStreamSynchronize(s));
     ZG_TRY(check_fault(g));

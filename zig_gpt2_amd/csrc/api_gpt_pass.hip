@@ -15,25 +15,25 @@ namespace {  // this unit only
 // again the flag words are zeroed on the stream in front of the launch (as note_steps does for the decode tags): every word then
 // holds 0, and from there on every epoch handed out is larger than every word written before it.
 int next_sk_epoch(zg_gpt* g, hipStream_t s, unsigned* out) {
-    if (++g->sk_epoch == 0u) {
-        ZG_HIP(hipMemsetAsync(g->sk_flags, 0, kSkFlagWords * sizeof(unsigned), s));
-        g->sk_epoch = 1u;
-        ++g->sk_restarts;
+    if (++g->pass.sk_epoch == 0u) {
+        ZG_HIP(hipMemsetAsync(g->pass.sk_flags, 0, kSkFlagWords * sizeof(unsigned), s));
+        g->pass.sk_epoch = 1u;
+        ++g->pass.sk_restarts;
     }
-    *out = g->sk_epoch;
+    *out = g->pass.sk_epoch;
     return ZG_OK;
 }
 
 // The scoring stage of a pass of n new positions per sequence behind `past` cached ones, whose residual stream of every row is
-// in pf_x: ln_f of all rows once (pf_a is free: the pass is over), then block by block of kScoreRows rows the lm_head on the
-// matrix cores into sc_logits, the two statistics launches, and on request the block's logits to the caller.
-// taps (zg_debug_gpt_pass_taps): class 7 — the ln_f planes, then per block (the table's layer field) each GEMM's plan and the block's rows of sc_logits.
+// in pass.x: ln_f of all rows once (pass.a is free: the pass is over), then block by block of kScoreRows rows the lm_head on the
+// matrix cores into score.logits, the two statistics launches, and on request the block's logits to the caller.
+// taps (zg_debug_gpt_pass_taps): class 7 — the ln_f planes, then per block (the table's layer field) each GEMM's plan and the block's rows of score.logits.
 static int enqueue_score(zg_gpt* g, size_t past, size_t n, float* logits_out, hipStream_t s, StepTaps* taps = nullptr) {
-    const size_t E = g->cfg.n_embed, V = g->cfg.vocab_size, C = g->cfg.context_size, V64 = g->sc_v64, head = V / 64 * 64, M = g->batch * n;
+    const size_t E = g->cfg.n_embed, V = g->cfg.vocab_size, C = g->cfg.context_size, V64 = g->score.v64, head = V / 64 * 64, M = g->batch * n;
     const int iE = (int)E, ld = (int)V64;
     const int np = (g->flags & ZG_GPT_PREFILL_2PLANE) ? 2 : kSplit;
     ZG_TRY(ensure_score_weights(g, s));
-    ZG_TRY(launch_ln_split(g->pf_x, (int)M, iE, g->ln_f_g, g->ln_f_b, 1e-5f, g->pf_a, s));
+    ZG_TRY(launch_ln_split(g->pass.x, (int)M, iE, g->ln_f_g, g->ln_f_b, 1e-5f, g->pass.a, s));
     PrefillGemmPlan plan{};
     PrefillGemmPlan* const plan_out = taps ? &plan : nullptr;
     auto tap_plan = [&](size_t block) {
@@ -42,31 +42,31 @@ static int enqueue_score(zg_gpt* g, size_t past, size_t n, float* logits_out, hi
         prefill_plan_ints(plan, v);
         return tap_words(taps, 7, block, ZG_TAP_PLAN, v, ZG_PREFILL_PLAN_INTS);
     };
-    if (taps) ZG_TRY(tap_put(taps, 7, 0, ZG_TAP_A, ZG_TAP_BF16, 0, g->pf_a, 1, M * kSplit * E * 2, M * kSplit * E * 2, s));
+    if (taps) ZG_TRY(tap_put(taps, 7, 0, ZG_TAP_A, ZG_TAP_BF16, 0, g->pass.a, 1, M * kSplit * E * 2, M * kSplit * E * 2, s));
     for (size_t r0 = 0; r0 < M; r0 += kScoreRows) {
         const int rows = (int)std::min(kScoreRows, M - r0);
-        const bf16_t* A = g->pf_a + r0 * kSplit * E;
+        const bf16_t* A = g->pass.a + r0 * kSplit * E;
         if (g->wt != WT_BF16) {  // the planes hold zero rows up to V64: one launch
-            ZG_TRY(launch_prefill_gemm(A, g->sc_planes, nullptr, g->sc_logits, rows, ld, iE, ld, PF_F32, g->sc_gemm_ws, g->sc_gemm_ws_floats, nullptr, s, nullptr,
+            ZG_TRY(launch_prefill_gemm(A, g->score.planes, nullptr, g->score.logits, rows, ld, iE, ld, PF_F32, g->score.gemm_ws, g->score.gemm_ws_floats, nullptr, s, nullptr,
                                        kWeightPlanes, nullptr, plan_out));
             ZG_TRY(tap_plan(r0 / kScoreRows));
         } else {  // the whole 64-row groups of wte where they lie, then the strip: no row behind V - 1 of wte is read
             if (head) {
-                ZG_TRY(launch_prefill_gemm(A, reinterpret_cast<const bf16_t*>(g->wte), nullptr, g->sc_logits, rows, (int)head, iE, ld, PF_F32, g->pf_ws,
-                                           g->pf_ws_floats, nullptr, s, nullptr, np, nullptr, plan_out));
+                ZG_TRY(launch_prefill_gemm(A, reinterpret_cast<const bf16_t*>(g->wte), nullptr, g->score.logits, rows, (int)head, iE, ld, PF_F32, g->pass.ws,
+                                           g->pass.ws_floats, nullptr, s, nullptr, np, nullptr, plan_out));
                 ZG_TRY(tap_plan(r0 / kScoreRows));
             }
-            if (g->sc_tail) {
-                ZG_TRY(launch_prefill_gemm(A, g->sc_tail, nullptr, g->sc_logits + head, rows, 64, iE, ld, PF_F32, g->pf_ws, g->pf_ws_floats, nullptr, s, nullptr, np,
+            if (g->score.tail) {
+                ZG_TRY(launch_prefill_gemm(A, g->score.tail, nullptr, g->score.logits + head, rows, 64, iE, ld, PF_F32, g->pass.ws, g->pass.ws_floats, nullptr, s, nullptr, np,
                                            nullptr, plan_out));
                 ZG_TRY(tap_plan(r0 / kScoreRows));
             }
         }
-        if (taps) ZG_TRY(tap_put(taps, 7, r0 / kScoreRows, ZG_TAP_LOGITS, ZG_TAP_F32, 0, g->sc_logits, 1, (size_t)rows * V64 * 4, (size_t)rows * V64 * 4, s));
+        if (taps) ZG_TRY(tap_put(taps, 7, r0 / kScoreRows, ZG_TAP_LOGITS, ZG_TAP_F32, 0, g->score.logits, 1, (size_t)rows * V64 * 4, (size_t)rows * V64 * 4, s));
         const ScoreTargets tg{g->prompt, (int)C, (int)n, (int)past, (int)r0};
-        ZG_TRY(launch_score(g->sc_logits, rows, (int)V, ld, g->lp_top, g->sc_ws, tg, g->lp_rec, s));
+        ZG_TRY(launch_score(g->score.logits, rows, (int)V, ld, g->lp.top, g->score.ws, tg, g->lp.rec, s));
         if (logits_out)
-            ZG_HIP(hipMemcpy2DAsync(logits_out + r0 * V, V * 4, g->sc_logits, V64 * 4, V * 4, (size_t)rows,
+            ZG_HIP(hipMemcpy2DAsync(logits_out + r0 * V, V * 4, g->score.logits, V64 * 4, V * 4, (size_t)rows,
                                     is_device_ptr(logits_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     }
     return ZG_OK;
@@ -79,20 +79,20 @@ namespace zg {  // offered to the other units: api_gpt.h declares them
 // (Re)derive what the scoring lm_head reads beside the weight region (the tail strip, or wte's planes) from the wte in the arena:
 // after ZG_WTE was loaded, and on handles whose region was filled some other way (a borrowed region, a broadcast).
 int ensure_score_weights(zg_gpt* g, hipStream_t s) {
-    if (!g->sc_logits || g->sc_gen == root(g)->w_gen + 1) return ZG_OK;
+    if (!g->score.logits || g->score.gen == root(g)->w_gen + 1) return ZG_OK;
     const size_t E = g->cfg.n_embed, V = g->cfg.vocab_size, head = V / 64 * 64;
-    if (g->wt != WT_BF16) ZG_TRY(launch_wte_planes(g->wte, g->wt, V, g->sc_v64, (int)E, g->sc_planes, s));
-    else if (g->sc_tail) {
-        ZG_HIP(hipMemsetAsync(g->sc_tail, 0, 64 * E * 2, s));
-        ZG_HIP(hipMemcpyAsync(g->sc_tail, reinterpret_cast<const bf16_t*>(g->wte) + head * E, (V - head) * E * 2, hipMemcpyDeviceToDevice, s));
+    if (g->wt != WT_BF16) ZG_TRY(launch_wte_planes(g->wte, g->wt, V, g->score.v64, (int)E, g->score.planes, s));
+    else if (g->score.tail) {
+        ZG_HIP(hipMemsetAsync(g->score.tail, 0, 64 * E * 2, s));
+        ZG_HIP(hipMemcpyAsync(g->score.tail, reinterpret_cast<const bf16_t*>(g->wte) + head * E, (V - head) * E * 2, hipMemcpyDeviceToDevice, s));
     }
-    g->sc_gen = root(g)->w_gen + 1;
+    g->score.gen = root(g)->w_gen + 1;
     return ZG_OK;
 }
 
 // Whole-prompt forward of positions 0..P-1 of every sequence (tokens in g->prompt): fills the KV caches
 // exactly as P calls of GPT.forward would (main.zig:331-334) and leaves the residual stream of all rows in
-// pf_x.  With `last_block_full` false the last Block stops after its cache append: nothing downstream of
+// pass.x.  With `last_block_full` false the last Block stops after its cache append: nothing downstream of
 // it is needed when generation re-feeds the last prompt token (main.zig:337).
 // fp32 weights (ZG_GPT_WEIGHTS_F32): the same pass; the weight operand is then the exact three-term bf16 split of the fp32
 // matrix (plane-major, made when the tensor is loaded; B24 weights: the split of the 24-bit values, the same pass) and every GEMM runs as three partial passes of the same kernel — the
@@ -111,9 +111,9 @@ int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipS
     const size_t Mz = (size_t)M, T_tap = std::min(C, pos0 + P + kPassTapRowsBehind);
     PrefillGemmPlan plan{};
     PrefillGemmPlan* const plan_out = taps ? &plan : nullptr;
-    auto tap_x = [&](int cls, size_t l) { return taps ? tap_put(taps, cls, l, ZG_TAP_X, ZG_TAP_F32, 0, g->pf_x, 1, Mz * E * 4, Mz * E * 4, s) : ZG_OK; };
+    auto tap_x = [&](int cls, size_t l) { return taps ? tap_put(taps, cls, l, ZG_TAP_X, ZG_TAP_F32, 0, g->pass.x, 1, Mz * E * 4, Mz * E * 4, s) : ZG_OK; };
     auto tap_a = [&](int cls, size_t l, unsigned f) {
-        return taps ? tap_put(taps, cls, l, ZG_TAP_A, ZG_TAP_BF16, f, g->pf_a, 1, Mz * kSplit * E * 2, Mz * kSplit * E * 2, s) : ZG_OK;
+        return taps ? tap_put(taps, cls, l, ZG_TAP_A, ZG_TAP_BF16, f, g->pass.a, 1, Mz * kSplit * E * 2, Mz * kSplit * E * 2, s) : ZG_OK;
     };
     auto tap_plan = [&](int cls, size_t l) {
         if (!taps) return (int)ZG_OK;
@@ -121,32 +121,32 @@ int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipS
         prefill_plan_ints(plan, v);
         return tap_words(taps, cls, l, ZG_TAP_PLAN, v, ZG_PREFILL_PLAN_INTS);
     };
-    ZG_TRY(launch_embed_prefill(g->prompt, (int)C, B, (int)P, g->wte, g->wpe, g->wt, iE, g->pf_x, s, (int)pos0));
+    ZG_TRY(launch_embed_prefill(g->prompt, (int)C, B, (int)P, g->wte, g->wpe, g->wt, iE, g->pass.x, s, (int)pos0));
     ZG_TRY(tap_x(0, 0));
-    ZG_TRY(launch_ln_split(g->pf_x, M, iE, g->layers[0].ln_1_g, g->layers[0].ln_1_b, 1e-5f, g->pf_a, s));
+    ZG_TRY(launch_ln_split(g->pass.x, M, iE, g->layers[0].ln_1_g, g->layers[0].ln_1_b, 1e-5f, g->pass.a, s));
     ZG_TRY(tap_a(1, 0, 0));
     for (size_t l = 0; l < L; ++l) {
         const zg_layer& y = g->layers[l];
-        // pf_a holds split(ln_1(x)) here: from the line above or from the tail of the previous Block's last GEMM
+        // pass.a holds split(ln_1(x)) here: from the line above or from the tail of the previous Block's last GEMM
         // c_attn with the cache append of ops.zig:152-157 in its epilogue
         PrefillQkv qa{(int)P, iE, (int)H, (int)C, g->kv_mode, y.k_cache, y.v_cache, g->batch * C * E * 2};
         qa.pos0 = (int)pos0;
-        if (!f32w && g->sk_flags != nullptr) {  // (the persistent GEMM may hand half tiles over between workgroups: gemm_s4.hip SK)
-            qa.sk_ws = g->pf_ws;
-            qa.sk_ws_bytes = g->pf_ws_floats * 4;
-            qa.sk_flags = g->sk_flags;
+        if (!f32w && g->pass.sk_flags != nullptr) {  // (the persistent GEMM may hand half tiles over between workgroups: gemm_s4.hip SK)
+            qa.sk_ws = g->pass.ws;
+            qa.sk_ws_bytes = g->pass.ws_floats * 4;
+            qa.sk_flags = g->pass.sk_flags;
             qa.sk_flags_words = (unsigned)kSkFlagWords;
             ZG_TRY(next_sk_epoch(g, s, &qa.sk_epoch));
-            g->sk_used = true;
+            g->pass.sk_used = true;
         }
         if (taps) ZG_TRY(tap_caches(g, taps, -1, l, 0, T_tap, s));
-        ZG_TRY(launch_prefill_gemm(g->pf_a, f32w ? y.c_attn_p : (const bf16_t*)y.c_attn_w, y.c_attn_b, g->pf_qkv, M, 3 * iE, iE, 3 * iE, PF_QKV,
-                                   g->pf_ws, g->pf_ws_floats, nullptr, s, &qa, np, nullptr, plan_out));
+        ZG_TRY(launch_prefill_gemm(g->pass.a, f32w ? y.c_attn_p : (const bf16_t*)y.c_attn_w, y.c_attn_b, g->pass.qkv, M, 3 * iE, iE, 3 * iE, PF_QKV,
+                                   g->pass.ws, g->pass.ws_floats, nullptr, s, &qa, np, nullptr, plan_out));
         if (taps) {  // q, then the k | v columns: the persistent kernel leaves those to an fp32 cache (gemm_s4.hip S4_QKV)
             const unsigned kv_cols = plan.family == PFF_S4 && g->kv_mode == 0 ? ZG_TAP_NOT_WRITTEN : 0u;
             ZG_TRY(tap_plan(2, l));
-            ZG_TRY(tap_put(taps, 2, l, ZG_TAP_Q, ZG_TAP_F32, 0, g->pf_qkv, Mz, E * 4, 3 * E * 4, s));
-            ZG_TRY(tap_put(taps, 2, l, ZG_TAP_QKV_KV, ZG_TAP_F32, kv_cols, g->pf_qkv + E, Mz, 2 * E * 4, 3 * E * 4, s));
+            ZG_TRY(tap_put(taps, 2, l, ZG_TAP_Q, ZG_TAP_F32, 0, g->pass.qkv, Mz, E * 4, 3 * E * 4, s));
+            ZG_TRY(tap_put(taps, 2, l, ZG_TAP_QKV_KV, ZG_TAP_F32, kv_cols, g->pass.qkv + E, Mz, 2 * E * 4, 3 * E * 4, s));
             ZG_TRY(tap_caches(g, taps, 2, l, 0, T_tap, s));
         }
         if (l + 1 == L && !last_block_full) break;
@@ -155,23 +155,23 @@ int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipS
         PrefillKv kv;
         if (pos0 > 0 || g->kv_mode == 0) kv = PrefillKv{y.k_cache, y.v_cache, g->kv_mode, g->batch * C * E * 2, (int)C};
         int ran[3] = {0, 0, 0};
-        ZG_TRY(launch_attn_prefill(g->pf_qkv, g->pf_a, B, (int)pos0, (int)P, iE, (int)H, g->pf_ws, g->pf_ws_floats, kv, s, 0, taps ? ran : nullptr));
+        ZG_TRY(launch_attn_prefill(g->pass.qkv, g->pass.a, B, (int)pos0, (int)P, iE, (int)H, g->pass.ws, g->pass.ws_floats, kv, s, 0, taps ? ran : nullptr));
         if (taps) ZG_TRY(tap_words(taps, 3, l, ZG_TAP_GEO, ran, 3));
         ZG_TRY(tap_a(3, l, 0));
-        const PrefillLn ln2{y.ln_2_g, y.ln_2_b, 1e-5f, g->pf_a};
-        ZG_TRY(launch_prefill_gemm(g->pf_a, f32w ? y.c_proj_p : (const bf16_t*)y.c_proj_w, y.c_proj_b, g->pf_x, M, iE, iE, iE, PF_RESID, g->pf_ws,
-                                   g->pf_ws_floats, &ln2, s, nullptr, np, nullptr, plan_out));
+        const PrefillLn ln2{y.ln_2_g, y.ln_2_b, 1e-5f, g->pass.a};
+        ZG_TRY(launch_prefill_gemm(g->pass.a, f32w ? y.c_proj_p : (const bf16_t*)y.c_proj_w, y.c_proj_b, g->pass.x, M, iE, iE, iE, PF_RESID, g->pass.ws,
+                                   g->pass.ws_floats, &ln2, s, nullptr, np, nullptr, plan_out));
         ZG_TRY(tap_plan(4, l));
         ZG_TRY(tap_x(4, l));
         ZG_TRY(tap_a(4, l, 0));
-        ZG_TRY(launch_prefill_gemm(g->pf_a, f32w ? y.c_fc_p : (const bf16_t*)y.c_fc_w, y.c_fc_b, g->pf_h, M, 4 * iE, iE, 0, PF_GELU_SPLIT, g->pf_ws,
-                                   g->pf_ws_floats, nullptr, s, nullptr, np, nullptr, plan_out));
+        ZG_TRY(launch_prefill_gemm(g->pass.a, f32w ? y.c_fc_p : (const bf16_t*)y.c_fc_w, y.c_fc_b, g->pass.h, M, 4 * iE, iE, 0, PF_GELU_SPLIT, g->pass.ws,
+                                   g->pass.ws_floats, nullptr, s, nullptr, np, nullptr, plan_out));
         ZG_TRY(tap_plan(5, l));
-        if (taps) ZG_TRY(tap_put(taps, 5, l, ZG_TAP_HP, ZG_TAP_BF16, 0, g->pf_h, 1, Mz * kSplit * 4 * E * 2, Mz * kSplit * 4 * E * 2, s));
+        if (taps) ZG_TRY(tap_put(taps, 5, l, ZG_TAP_HP, ZG_TAP_BF16, 0, g->pass.h, 1, Mz * kSplit * 4 * E * 2, Mz * kSplit * 4 * E * 2, s));
         const bool more = l + 1 < L;
-        const PrefillLn ln1{more ? g->layers[l + 1].ln_1_g : nullptr, more ? g->layers[l + 1].ln_1_b : nullptr, 1e-5f, g->pf_a};
-        ZG_TRY(launch_prefill_gemm(g->pf_h, f32w ? y.mlp_proj_p : (const bf16_t*)y.mlp_proj_w, y.mlp_proj_b, g->pf_x, M, iE, 4 * iE, iE, PF_RESID, g->pf_ws,
-                                   g->pf_ws_floats, more ? &ln1 : nullptr, s, nullptr, np, nullptr, plan_out));
+        const PrefillLn ln1{more ? g->layers[l + 1].ln_1_g : nullptr, more ? g->layers[l + 1].ln_1_b : nullptr, 1e-5f, g->pass.a};
+        ZG_TRY(launch_prefill_gemm(g->pass.h, f32w ? y.mlp_proj_p : (const bf16_t*)y.mlp_proj_w, y.mlp_proj_b, g->pass.x, M, iE, 4 * iE, iE, PF_RESID, g->pass.ws,
+                                   g->pass.ws_floats, more ? &ln1 : nullptr, s, nullptr, np, nullptr, plan_out));
         ZG_TRY(tap_plan(6, l));
         ZG_TRY(tap_x(6, l));
         ZG_TRY(tap_a(6, l, more ? 0u : ZG_TAP_NOT_WRITTEN));
@@ -189,10 +189,10 @@ int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t stride, s
               const char* who, const ScoreCall* sc, StepTaps* taps) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && tokens, ZG_ERR_ARG, "%s: null argument", who);
-    ZG_REQUIRE(g->pf_x != nullptr, ZG_ERR_UNSUPPORTED, "%s: the handle was created with ZG_GPT_NO_PREFILL", who);
+    ZG_REQUIRE(g->pass.x != nullptr, ZG_ERR_UNSUPPORTED, "%s: the handle was created with ZG_GPT_NO_PREFILL", who);
     const size_t C = g->cfg.context_size, V = g->cfg.vocab_size, B = g->batch, E = g->cfg.n_embed;
     if (sc) {
-        ZG_REQUIRE(g->sc_logits != nullptr, ZG_ERR_UNSUPPORTED, "%s: the handle was created without ZG_GPT_SCORE", who);
+        ZG_REQUIRE(g->score.logits != nullptr, ZG_ERR_UNSUPPORTED, "%s: the handle was created without ZG_GPT_SCORE", who);
         ZG_TRY(check_top_n(sc->top_n, V, who));
         ZG_REQUIRE(V <= (size_t)64 * 4096, ZG_ERR_UNSUPPORTED, "%s: vocabulary of %zu beyond %d", who, V, 64 * 4096);
     }
@@ -214,7 +214,7 @@ int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t stride, s
     ZG_TRY(ensure_ln_folded(g, s));
     ZG_TRY(enqueue_prefill(g, past_len, n, compute_logits != 0, s, taps));
     if (compute_logits) {
-        ZG_HIP(hipMemcpy2DAsync(g->x, E * 4, g->pf_x + (n - 1) * E, n * E * 4, E * 4, B, hipMemcpyDeviceToDevice, s));
+        ZG_HIP(hipMemcpy2DAsync(g->x, E * 4, g->pass.x + (n - 1) * E, n * E * 4, E * 4, B, hipMemcpyDeviceToDevice, s));
         ZG_TRY(stage_ctrl(g, end - 1, end, 1, s));
         ZG_TRY(enqueue_lm_head(g, s));
         if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, B * V, s));
@@ -222,7 +222,7 @@ int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t stride, s
     if (sc) {  // a log-probability generation with this top_n: the record continues behind it (generate_from) and leaves through the same fetch
         ZG_TRY(stage_top_n(g, sc->top_n, s));
         // column past_len: its predicting row is not part of the pass (NaN: every byte 0xff)
-        ZG_HIP(hipMemset2DAsync(g->lp_rec.logprob + past_len, C * sizeof(float), 0xff, sizeof(float), B, s));
+        ZG_HIP(hipMemset2DAsync(g->lp.rec.logprob + past_len, C * sizeof(float), 0xff, sizeof(float), B, s));
         ZG_TRY(enqueue_score(g, past_len, n, sc->logits_out, s, taps));
     }
     ZG_HIP(hipStreamSynchronize(s));

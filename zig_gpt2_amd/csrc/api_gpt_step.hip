@@ -2,7 +2,7 @@
 // exists once, as StepKey {with_logits, multi, StepTail}: what enqueue_step launches and which graph replays it (the sampler chain
 // behind lm_head is emitted by emit_sampler_chain for every user: sampler_chain.hip).  What follows
 // lm_head — which sampler, penalties or not, log-probabilities or not — travels as ONE value, StepTail, from the request to the
-// launches: a generation holds one (zg_gpt::gen_tail), a step is told one (StepOpts::tail), a graph is keyed by one, and the graph
+// launches: a generation holds one (zg_gpt::gen.tail), a step is told one (StepOpts::tail), a graph is keyed by one, and the graph
 // table is indexed by its fields as mixed-radix digits (step_index).  ONE rule says which graphs exist when: create captures the
 // default tail's and those of the tails its flags name (tails_of_flags), and a generation whose tail is another one captures that
 // tail's graphs for the buckets it will touch when it begins (gen_begin), before its steps are counted and the prefetcher starts.
@@ -35,7 +35,7 @@ GemvArgs base_gemv(const zg_gpt* g, const void* W, const float* bias, size_t N, 
     a.sk_ws = g->sk_ws;
     a.sk_cnt = g->sk_cnt;
     a.sk_tiles = g->sk_tiles;
-    a.progress = g->pf_on ? &g->pf_ctl->progress : nullptr;
+    a.progress = g->prefetch.on ? &g->prefetch.ctl->progress : nullptr;
     return a;
 }
 
@@ -74,8 +74,8 @@ int emit_gemv(const zg_gpt* g, const GemvArgs& a, const GemvPlan& p, hipStream_t
 // followed by the generate loop's own record from PenParams.past_len on
 PenHistory pen_history(const zg_gpt* g, bool loop) {
     PenHistory h{};
-    h.prior = g->prior;
-    h.prior_len = g->prior_len;
+    h.prior = g->pen.prior;
+    h.prior_len = g->pen.prior_len;
     h.prior_stride = (int)g->cfg.context_size;
     if (loop) {
         h.rec = g->out_tokens;
@@ -117,62 +117,9 @@ std::vector<StepTail> tails_of_flags(unsigned flags) {
     return t;
 }
 
-}  // namespace
-
-namespace zg {  // offered to the other units: api_gpt.h declares them
-
-int bucket_t_hi(const zg_gpt* g, size_t seq_len) {
-    const size_t hi = ((seq_len + 63) / 64) * 64;
-    return (int)(hi < g->cfg.context_size ? hi : g->cfg.context_size);
-}
-
-EmbedArgs embed_args(const zg_gpt* g, int finish_only) {
-    EmbedArgs e{};
-    e.ctrl = g->ctrl;
-    e.wte = g->wte;
-    e.wpe = g->wpe;
-    e.weight_type = g->wt;
-    e.n_embed = (int)g->cfg.n_embed;
-    e.batch = (int)g->batch;
-    e.vocab = (int)g->cfg.vocab_size;
-    e.prompt = g->prompt;
-    e.prompt_stride = (int)g->cfg.context_size;
-    e.prompt_len = g->prompt_len;
-    e.forced = g->forced;
-    e.cur_token = g->cur_token;
-    e.out_tokens = g->out_tokens;
-    e.out_stride = (int)g->cfg.context_size;
-    e.part_val = g->part_val;
-    e.part_idx = g->part_idx;
-    e.part_stride = g->lm_grid;  // the lm_head GEMV writes partials [batch][gridDim.x]
-    e.n_partials = g->lm_grid;
-    e.x = g->x;
-    e.pl_out = g->pl_on ? g->xp : nullptr;
-    e.pl_g = g->layers[0].ln_1_g;
-    e.epoch = (((g->pl_on && g->tags_on) || g->fused_on) && finish_only != 1 && finish_only != 2) ? g->epoch : nullptr;
-    e.st_out = g->st_on ? g->xst : nullptr;
-    e.finish_only = finish_only;
-    e.progress = g->pf_on ? &g->pf_ctl->progress : nullptr;
-    e.sampled = g->sampled;
-    return e;
-}
-
-int prof_mark(StepProf* p, int cls, hipStream_t s) {
-    if (!p) return ZG_OK;
-    if (p->n == p->ev.size()) {
-        hipEvent_t e;
-        ZG_HIP(hipEventCreate(&e));
-        p->ev.push_back(e);
-        p->cls.push_back(cls);
-    }
-    p->cls[p->n] = cls;
-    ZG_HIP(hipEventRecord(p->ev[p->n++], s));
-    return ZG_OK;
-}
-
 // The arguments of the decode launches of a Block and of lm_head, one builder per launch class: enqueue_step launches what they
-// return, and zg_gpt_create plans (gemv_plan) the very same arguments.  The decode modes they lay the arguments out for are
-// passed in: the handle's own (modes_of) for a step, a candidate while zg_gpt_create decides them.
+// return, and decide_step_modes plans (gemv_plan) the very same arguments.  The decode modes they lay the arguments out for are
+// passed in: the handle's own (zg_gpt::modes) for a step, a candidate while decide_step_modes decides them.
 
 // ln_1 + c_attn + split_qkv + cache append (main.zig:121-123, ops.zig:143-157) and the attention over the cache (ops.zig:160 ->
 // :249-307) of layer y: the arguments of their launches
@@ -213,7 +160,7 @@ AttnArgs attn_args(const zg_gpt* g, const zg_layer& y, int t_hi) {
     a.t_hi = t_hi;
     a.max_splits = g->max_splits;
     a.part = g->part;
-    a.progress = g->pf_on ? &g->pf_ctl->progress : nullptr;
+    a.progress = g->prefetch.on ? &g->prefetch.ctl->progress : nullptr;
     a.tail_off = g->tail_off;
     a.dbg = ctx().dbg;
     return a;
@@ -279,10 +226,10 @@ GemvArgs mlp_proj_args(const zg_gpt* g, size_t l, int t_hi, const StepModes& m) 
     a.resid_stride = (int)E;
     if (m.pl) {
         if (m.tags && 2 * l + 2 <= 255) {
-            a.epoch = g->epoch;
-            a.sk_tag = g->sk_tag;
-            a.fault = g->fault;
-            a.spin_limit = g->spin_limit;
+            a.epoch = g->hand.epoch;
+            a.sk_tag = g->hand.sk_tag;
+            a.fault = g->hand.fault;
+            a.spin_limit = g->hand.spin_limit;
         }
         a.pl_in = g->hp;
         if (l + 1 < g->cfg.n_layer) {  // the next Block's ln_1 + c_attn (ln_f + lm_head reads x itself)
@@ -313,6 +260,59 @@ GemvArgs lm_head_args(const zg_gpt* g) {
     return a;
 }
 
+}  // namespace
+
+namespace zg {  // offered to the other units: api_gpt.h declares them
+
+int bucket_t_hi(const zg_gpt* g, size_t seq_len) {
+    const size_t hi = ((seq_len + 63) / 64) * 64;
+    return (int)(hi < g->cfg.context_size ? hi : g->cfg.context_size);
+}
+
+EmbedArgs embed_args(const zg_gpt* g, int finish_only) {
+    EmbedArgs e{};
+    e.ctrl = g->ctrl;
+    e.wte = g->wte;
+    e.wpe = g->wpe;
+    e.weight_type = g->wt;
+    e.n_embed = (int)g->cfg.n_embed;
+    e.batch = (int)g->batch;
+    e.vocab = (int)g->cfg.vocab_size;
+    e.prompt = g->prompt;
+    e.prompt_stride = (int)g->cfg.context_size;
+    e.prompt_len = g->prompt_len;
+    e.forced = g->forced;
+    e.cur_token = g->cur_token;
+    e.out_tokens = g->out_tokens;
+    e.out_stride = (int)g->cfg.context_size;
+    e.part_val = g->part_val;
+    e.part_idx = g->part_idx;
+    e.part_stride = g->lm_grid;  // the lm_head GEMV writes partials [batch][gridDim.x]
+    e.n_partials = g->lm_grid;
+    e.x = g->x;
+    e.pl_out = g->modes.pl ? g->xp : nullptr;
+    e.pl_g = g->layers[0].ln_1_g;
+    e.epoch = (((g->modes.pl && g->modes.tags) || g->modes.fused) && finish_only != 1 && finish_only != 2) ? g->hand.epoch : nullptr;
+    e.st_out = g->modes.st ? g->xst : nullptr;
+    e.finish_only = finish_only;
+    e.progress = g->prefetch.on ? &g->prefetch.ctl->progress : nullptr;
+    e.sampled = g->samp.sampled;
+    return e;
+}
+
+int prof_mark(StepProf* p, int cls, hipStream_t s) {
+    if (!p) return ZG_OK;
+    if (p->n == p->ev.size()) {
+        hipEvent_t e;
+        ZG_HIP(hipEventCreate(&e));
+        p->ev.push_back(e);
+        p->cls.push_back(cls);
+    }
+    p->cls[p->n] = cls;
+    ZG_HIP(hipEventRecord(p->ev[p->n++], s));
+    return ZG_OK;
+}
+
 int enqueue_lm_head(zg_gpt* g, hipStream_t s, std::vector<PfJob>* rec) {
     const GemvArgs a = lm_head_args(g);
     const GemvPlan p = gemv_plan(a, g->wt);
@@ -326,11 +326,46 @@ SamplerChain handle_chain(const zg_gpt* g, bool loop) {
     SamplerChain c{};
     c.logits = g->logits, c.batch = (int)g->batch, c.vocab = (int)g->cfg.vocab_size;
     c.part_val = g->part_val, c.part_idx = g->part_idx, c.n_part = g->lm_grid;
-    c.pen = g->pen, c.hist = pen_history(g, loop);
-    c.edit_tab = g->edit_tab, c.edit_keep = g->edit_keep;
-    c.params = g->samp, c.seg_ws = g->samp_ws, c.filt = g->filt;
-    if (loop) c.ctrl = g->ctrl, c.pick = g->sampled;
+    c.pen = g->pen.params, c.hist = pen_history(g, loop);
+    c.edit_tab = g->edit.tab, c.edit_keep = g->edit.keep;
+    c.params = g->samp.params, c.seg_ws = g->samp.ws, c.filt = g->samp.filt;
+    if (loop) c.ctrl = g->ctrl, c.pick = g->samp.sampled;
     return c;
+}
+
+// The decode modes of a handle (zg_gpt_create, once the arena is carved), each decided from the plans (gemv_plan) of the launches
+// enqueue_step would make with the mode on; with them lm_grid, tail_off and the spin limit of the tagged hand-overs.
+int decide_step_modes(zg_gpt* g) {
+    const zg_gpt_config& c = g->cfg;
+    const size_t batch = g->batch;
+    const zg_layer& y = g->layers[0];
+    const int off = decode_paths_off();
+    StepModes& m = g->modes;
+    g->lm_grid = gemv_plan(lm_head_args(g), g->wt).grid;
+    // the widest input of a Block (mlp c_proj: 4 E floats per sequence) must fit the batched kernels' LDS
+    ZG_REQUIRE(gemv_plan(mlp_proj_args(g, 0, 0, StepModes{}), g->wt).supported, ZG_ERR_UNSUPPORTED,
+               "batch %zu with n_embed %zu: %zu input rows of 4*n_embed floats do not fit the LDS (use a smaller batch)", batch, c.n_embed, batch);
+    if (g->wt == WT_BF16 && batch >= 2 && !(off & kOffPlanes) && c.n_embed % 32 == 0) {
+        const StepModes cand{true, false, false};  // activation planes between the kernels
+        const GemvPlan lin[4] = {gemv_plan(c_attn_args(g, y, 0, cand), g->wt), gemv_plan(c_proj_args(g, y, 0, cand), g->wt),
+                                 gemv_plan(c_fc_args(g, y, 0, cand), g->wt), gemv_plan(mlp_proj_args(g, 0, 0, cand), g->wt)};
+        auto every_linear = [&](bool GemvPlan::*f) { return lin[0].*f && lin[1].*f && lin[2].*f && lin[3].*f; };
+        m.pl = every_linear(&GemvPlan::can_take_planes);  // all plane-fed Linears on the matrix-core path?
+        // LayerNorm statistics by tile: every producer and consumer of x must be the four-wave kernel (the statistics' only
+        // part in a plan is the bound on n_embed / 16 asked here)
+        m.st = m.pl && !(off & kOffTileStats) && c.n_embed % 16 == 0 && c.n_embed / 16 <= 128 && every_linear(&GemvPlan::pl4_with_planes);
+    }
+    m.tags = m.pl && !(off & kOffTags);
+    g->hand.spin_limit = (unsigned)env_int("ZGPT2_TAG_SPIN_LIMIT", 1 << 20);
+    g->tail_off = (unsigned)off & kStepPathsAtCreate;
+    // one sequence on the fp32 cache: ln_1 + c_attn and the attention as one launch where c_attn runs on the LayerNorm-folding
+    // kernel (ZGPT2_DECODE_PATHS_OFF kOffFusedAttn: two launches)
+    if (batch == 1 && !(off & kOffFusedAttn) && c.n_layer <= 127) {
+        const GemvArgs ca = c_attn_args(g, y, 0, m);
+        m.fused = attn_qkv_ok(ca, gemv_plan(ca, g->wt), attn_args(g, y, (int)c.context_size));
+    }
+    ZG_REQUIRE(g->lm_grid <= 4096, ZG_ERR_UNSUPPORTED, "lm_head grid %d exceeds the argmax partial buffer", g->lm_grid);
+    return ZG_OK;
 }
 
 // One decode step = GPT.forward (main.zig:178-195) for all sequences.
@@ -339,7 +374,7 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
     std::vector<PfJob>* const rec = o.rec;
     const int only = o.only;
     auto launch_id = [&](size_t l, int k) { return (unsigned)(o.salt >= 0 ? 1 + (2 * o.salt + k) % 254 : 2 * (int)l + 1 + k); };
-    const StepModes m = modes_of(g);
+    const StepModes& m = g->modes;
     auto gemv = [&](const GemvArgs& a, unsigned cls) {
         ZG_TRY(emit_gemv(g, a, gemv_plan(a, g->wt), s, rec, cls));
         return prof_mark(prof, (int)cls, s);
@@ -355,15 +390,15 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
     for (size_t l = (only < 0 ? 0 : o.only_layer); l < (only < 0 ? g->cfg.n_layer : o.only_layer + 1); ++l) {
         const zg_layer& y = g->layers[l];
         // one sequence: classes 1 and 2 as one launch (attn_qkv.hip), timed as class 1; the prefetcher's table keeps both entries
-        const bool fused = g->fused_on && !rec && 2 * l + 2 <= 255;
+        const bool fused = g->modes.fused && !rec && 2 * l + 2 <= 255;
         ZG_TRY(tap_class(g, o.taps, -1, l, 0, s));
         if (fused && (only < 0 || only == 1)) {
             const GemvArgs a = c_attn_args(g, y, t_hi, m);
             AttnArgs at = attn_args(g, y, t_hi);
             at.launch_id = launch_id(l, 0);
-            at.fault = g->fault;
-            at.spin_limit = g->spin_limit;
-            ZG_TRY(launch_attn_qkv(a, gemv_plan(a, g->wt), g->wt, at, g->epoch, g->qkv_tag, s));
+            at.fault = g->hand.fault;
+            at.spin_limit = g->hand.spin_limit;
+            ZG_TRY(launch_attn_qkv(a, gemv_plan(a, g->wt), g->wt, at, g->hand.epoch, g->hand.qkv_tag, s));
             ZG_TRY(prof_mark(prof, 1, s));
             ZG_TRY(prof_mark(prof, 2, s));
             ZG_TRY(tap_class(g, o.taps, 1, l, ZG_TAP_FUSED, s));
@@ -375,15 +410,15 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         }
         if ((!fused && only < 0) || only == 2) {   // scaled_dot_product_attention over the cache: ops.zig:160 -> :249-307
             AttnArgs a = attn_args(g, y, t_hi);
-            if (g->pl_on) {
+            if (g->modes.pl) {
                 a.pl_out = g->ap;
                 a.merge_cnt = g->attn_cnt;
-                if (g->tags_on && 2 * l + 2 <= 255) {
-                    a.epoch = g->epoch;
+                if (g->modes.tags && 2 * l + 2 <= 255) {
+                    a.epoch = g->hand.epoch;
                     a.launch_id = launch_id(l, 0);
-                    a.part_tag = g->part_tag;
-                    a.fault = g->fault;
-                    a.spin_limit = g->spin_limit;
+                    a.part_tag = g->hand.part_tag;
+                    a.fault = g->hand.fault;
+                    a.spin_limit = g->hand.spin_limit;
                 }
             }
             if (rec) {  // the K and V rows of earlier positions, laid out for this grid
@@ -425,13 +460,13 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
     // GPT.sample's tail (main.zig:200-206) on the logits of this step: the next step's embed kernel feeds what it draws (mode 2)
     // the log-probability stage reads the row the sampler read and the token the next step's embed kernel will record
     auto logprobs = [&](const int* tokens) {
-        return launch_logprob(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->part_val, g->part_idx, g->lm_grid, g->lm_grid, g->lp_top, g->lp_ws,
-                              tokens, g->ctrl, g->prompt_len, g->lp_rec, s);
+        return launch_logprob(g->logits, (int)g->batch, (int)g->cfg.vocab_size, g->part_val, g->part_idx, g->lm_grid, g->lm_grid, g->lp.top, g->lp.ws,
+                              tokens, g->ctrl, g->prompt_len, g->lp.rec, s);
     };
     // the stop stage, last: it learns the pick of its own step the way the log-probability stage does
     auto stop = [&](const int* picks) {
         StopArgs a{};
-        a.conds = g->stop;
+        a.conds = g->stop.conds;
         a.tokens = g->out_tokens;
         a.stride = (int)g->cfg.context_size;
         a.prompt_len = g->prompt_len;
@@ -443,14 +478,14 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
         a.part_val = g->part_val;
         a.part_idx = g->part_idx;
         a.n_part = a.part_stride = g->lm_grid;
-        a.finish_col = g->stop_fin;
-        a.reason = g->stop_reason;
-        a.host = &g->h_stop->host;
+        a.finish_col = g->stop.fin;
+        a.reason = g->stop.reason;
+        a.host = &g->stop.pinned->host;
         return launch_stop(a, s);
     };
     const StepTail tail = o.tail;
     if (!with_logits || only >= 0 || rec) return ZG_OK;
-    const int* const picks = tail.sampler == GREEDY ? nullptr : g->sampled;  // (the greedy graphs have no sampler node)
+    const int* const picks = tail.sampler == GREEDY ? nullptr : g->samp.sampled;  // (the greedy graphs have no sampler node)
     ZG_TRY(emit_sampler_chain(handle_chain(g, true), tail, s));
     if (tail.lp) ZG_TRY(logprobs(picks));
     if (tail.stop) ZG_TRY(stop(picks));
@@ -467,65 +502,65 @@ int setup_prefetcher(zg_gpt* g) {
     const bool small = g->stream == nullptr && g->batch == 1 && 4 * g->cfg.n_embed * g->cfg.n_embed * g->wbytes <= ((size_t)6 << 20);
     const int want = env_int("ZGPT2_PREFETCH", small ? 1 : 0);
     if ((g->flags & ZG_GPT_NO_PREFETCH) || !want || gs(g) == nullptr) return ZG_OK;
-    if (g->pf_njobs > 255) return ZG_OK;  // the progress word counts launches in 8 bits (n_layer >= 51): no prefetcher, not an error
+    if (g->prefetch.njobs > 255) return ZG_OK;  // the progress word counts launches in 8 bits (n_layer >= 51): no prefetcher, not an error
     std::vector<PfJob> jobs;
     StepOpts describe;
     describe.rec = &jobs;
     ZG_TRY(enqueue_step(g, true, (int)g->cfg.context_size, nullptr, describe));
-    ZG_REQUIRE((int)jobs.size() == g->pf_njobs, ZG_ERR_ARG, "prefetcher: %zu launches per step", jobs.size());
-    ZG_HIP(hipMemcpy(g->pf_jobs, jobs.data(), jobs.size() * sizeof(PfJob), hipMemcpyHostToDevice));
+    ZG_REQUIRE((int)jobs.size() == g->prefetch.njobs, ZG_ERR_ARG, "prefetcher: %zu launches per step", jobs.size());
+    ZG_HIP(hipMemcpy(g->prefetch.jobs, jobs.data(), jobs.size() * sizeof(PfJob), hipMemcpyHostToDevice));
     int least = 0, greatest = 0;
     ZG_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    ZG_HIP(hipStreamCreateWithPriority(&g->pf_stream, hipStreamNonBlocking, least));
-    ZG_HIP(hipEventCreateWithFlags(&g->pf_ev_main, hipEventDisableTiming));
-    ZG_HIP(hipEventCreateWithFlags(&g->pf_ev_side, hipEventDisableTiming));
-    g->pf_on = true;
+    ZG_HIP(hipStreamCreateWithPriority(&g->prefetch.stream, hipStreamNonBlocking, least));
+    ZG_HIP(hipEventCreateWithFlags(&g->prefetch.ev_main, hipEventDisableTiming));
+    ZG_HIP(hipEventCreateWithFlags(&g->prefetch.ev_side, hipEventDisableTiming));
+    g->prefetch.on = true;
     return ZG_OK;
 }
 
 void drop_prefetcher(zg_gpt* g) {
-    if (g->pf_stream) {
-        (void)hipStreamSynchronize(g->pf_stream);
-        (void)hipStreamDestroy(g->pf_stream);
+    if (g->prefetch.stream) {
+        (void)hipStreamSynchronize(g->prefetch.stream);
+        (void)hipStreamDestroy(g->prefetch.stream);
     }
-    if (g->pf_ev_main) (void)hipEventDestroy(g->pf_ev_main);
-    if (g->pf_ev_side) (void)hipEventDestroy(g->pf_ev_side);
-    g->pf_stream = nullptr;
-    g->pf_ev_main = g->pf_ev_side = nullptr;
-    g->pf_on = false;
+    if (g->prefetch.ev_main) (void)hipEventDestroy(g->prefetch.ev_main);
+    if (g->prefetch.ev_side) (void)hipEventDestroy(g->prefetch.ev_side);
+    g->prefetch.stream = nullptr;
+    g->prefetch.ev_main = g->prefetch.ev_side = nullptr;
+    g->prefetch.on = false;
 }
 
 // Start the prefetcher for a run of decode steps ending at sequence length last_T: the control block is cleared on
 // the side stream (behind the previous run's prefetcher), the decode stream waits for that, and the prefetcher
 // starts once the decode stream reaches this point.  pf_stop() goes behind the last step.
 int pf_start(zg_gpt* g, size_t last_T, hipStream_t s) {
-    if (!g->pf_on || s == nullptr) return ZG_OK;
-    if (g->pf_ran) {  // how did the previous one leave?  (the decode stream was synchronised by the caller)
-        ZG_HIP(hipStreamSynchronize(g->pf_stream));
+    if (!g->prefetch.on || s == nullptr) return ZG_OK;
+    if (g->prefetch.ran) {  // how did the previous one leave?  (the decode stream was synchronised by the caller)
+        ZG_HIP(hipStreamSynchronize(g->prefetch.stream));
         unsigned why[8];
-        ZG_HIP(hipMemcpy(why, g->pf_ctl->exit_reason, sizeof(why), hipMemcpyDeviceToHost));
+        ZG_HIP(hipMemcpy(why, g->prefetch.ctl->exit_reason, sizeof(why), hipMemcpyDeviceToHost));
         bool idle_exit = false;
         for (unsigned w : why) idle_exit |= w == 2u;
-        g->pf_ran = false;
+        g->prefetch.ran = false;
         if (idle_exit) {  // a strike, not a verdict: one slow host moment inside a generate loop produces the same exit
-            g->pf_stalled = true;
-            ++g->pf_strikes;
-            g->pf_sit_out = 8;  // generate calls without it before the next try
+            g->prefetch.stalled = true;
+            ++g->prefetch.strikes;
+            g->prefetch.sit_out = 8;  // generate calls without it before the next try
         }
     }
-    if (g->pf_stalled) {
-        if (g->pf_strikes >= 3 || g->pf_sit_out-- > 0) return ZG_OK;
-        g->pf_stalled = false;  // try again
+    if (g->prefetch.stalled) {
+        if (g->prefetch.strikes >= 3 || g->prefetch.sit_out-- > 0) return ZG_OK;
+        g->prefetch.stalled = false;  // try again
     }
-    ZG_HIP(hipMemsetAsync(g->pf_ctl, 0, sizeof(PfCtl), g->pf_stream));
-    ZG_HIP(hipEventRecord(g->pf_ev_side, g->pf_stream));
-    ZG_HIP(hipStreamWaitEvent(s, g->pf_ev_side, 0));
-    ZG_HIP(hipEventRecord(g->pf_ev_main, s));
-    ZG_HIP(hipStreamWaitEvent(g->pf_stream, g->pf_ev_main, 0));
+    ZG_HIP(hipMemsetAsync(g->prefetch.ctl, 0, sizeof(PfCtl), g->prefetch.stream));
+    ZG_HIP(hipEventRecord(g->prefetch.ev_side, g->prefetch.stream));
+    ZG_HIP(hipStreamWaitEvent(s, g->prefetch.ev_side, 0));
+    ZG_HIP(hipEventRecord(g->prefetch.ev_main, s));
+    ZG_HIP(hipStreamWaitEvent(g->prefetch.stream, g->prefetch.ev_main, 0));
     PfArgs a{};
-    a.ctl = g->pf_ctl;
-    a.jobs = g->pf_jobs;
-    a.njobs = g->pf_njobs;
+    a.ctl = g->prefetch.ctl;
+    a.jobs = g->prefetch.jobs;
+    a.njobs = g->prefetch.njobs;
     // the measured optimum of the round-2 / round-3 sweeps (profiles/NOTEBOOK.md), constants since round 5
     a.lead = 2;    // launches ahead of the running one
     a.nsub = 12;   // prefetcher workgroups per XCD
@@ -535,32 +570,32 @@ int pf_start(zg_gpt* g, size_t last_T, hipStream_t s) {
     a.cls_mask = 0x3e;  // every class but lm_head (its head start measured a net loss)
     a.line_shift = 7;   // one touch per 128-byte line
     a.cap_bytes = 0;
-    g->pf_ran = true;
-    return launch_prefetcher(a, g->pf_stream);
+    g->prefetch.ran = true;
+    return launch_prefetcher(a, g->prefetch.stream);
 }
 
 int pf_stop(zg_gpt* g, hipStream_t s) {
-    if (!g->pf_on || s == nullptr) return ZG_OK;
-    ZG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&g->pf_ctl->progress), (int)PF_STOP, 1, s));
+    if (!g->prefetch.on || s == nullptr) return ZG_OK;
+    ZG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&g->prefetch.ctl->progress), (int)PF_STOP, 1, s));
     return ZG_OK;
 }
 
 size_t bucket_of(size_t seq_len) { return (seq_len + 63) / 64 - 1; }
 
 void drop_graphs(zg_gpt* g) {
-    for (auto& e : g->graphs)
+    for (auto& e : g->graph.execs)
         if (e) {
             (void)hipGraphExecDestroy(e);
             e = nullptr;
         }
 }
 
-// The graph of (step shape k, bucket b) for stream s (the stream of g->graph_stream: capture_all), captured on first use.
+// The graph of (step shape k, bucket b) for stream s (the stream of g->graph.stream: capture_all), captured on first use.
 int graph_exec(zg_gpt* g, StepKey k, size_t b, hipStream_t s, hipGraphExec_t* out) {
-    hipGraphExec_t& e = g->graphs[step_index(k) * g->n_buckets + b];
+    hipGraphExec_t& e = g->graph.execs[step_index(k) * g->graph.n_buckets + b];
     if (!e) {
         const int t_hi = bucket_t_hi(g, (b + 1) * 64);  // any length of the bucket: only its upper bound is baked in
-        const size_t n_steps = k.multi ? g->graph_steps : 1;
+        const size_t n_steps = k.multi ? g->graph.steps : 1;
         StepOpts o;
         o.tail = k.tail;
         ZG_TRY(capture_graph(s, &e, [&] {
@@ -576,9 +611,9 @@ int graph_exec(zg_gpt* g, StepKey k, size_t b, hipStream_t s, hipGraphExec_t* ou
 // The single-step and (where the handle has them) multi-step graphs of a tail, buckets b0 .. b1
 int capture_tail(zg_gpt* g, StepTail tail, size_t b0, size_t b1, hipStream_t s) {
     hipGraphExec_t e;
-    for (size_t b = b0; b <= b1 && b < g->n_buckets; ++b) {
+    for (size_t b = b0; b <= b1 && b < g->graph.n_buckets; ++b) {
         ZG_TRY(graph_exec(g, {true, false, tail}, b, s, &e));
-        if (g->graph_steps > 1) ZG_TRY(graph_exec(g, {true, true, tail}, b, s, &e));
+        if (g->graph.steps > 1) ZG_TRY(graph_exec(g, {true, true, tail}, b, s, &e));
     }
     return ZG_OK;
 }
@@ -588,14 +623,14 @@ int capture_tail(zg_gpt* g, StepTail tail, size_t b0, size_t b1, hipStream_t s) 
 // tail create did not capture adds that tail's graphs when it begins (gen_begin).
 int capture_all(zg_gpt* g, hipStream_t s) {
     if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) return ZG_OK;
-    if (g->graph_stream != s) {
+    if (g->graph.stream != s) {
         drop_graphs(g);
-        g->graph_stream = s;
+        g->graph.stream = s;
     }
     hipGraphExec_t e;
-    for (size_t b = 0; b < g->n_buckets; ++b) ZG_TRY(graph_exec(g, {false, false, StepTail{}}, b, s, &e));
-    ZG_TRY(capture_tail(g, StepTail{}, 0, g->n_buckets - 1, s));
-    for (const StepTail& t : tails_of_flags(g->flags)) ZG_TRY(capture_tail(g, t, 0, g->n_buckets - 1, s));
+    for (size_t b = 0; b < g->graph.n_buckets; ++b) ZG_TRY(graph_exec(g, {false, false, StepTail{}}, b, s, &e));
+    ZG_TRY(capture_tail(g, StepTail{}, 0, g->graph.n_buckets - 1, s));
+    for (const StepTail& t : tails_of_flags(g->flags)) ZG_TRY(capture_tail(g, t, 0, g->graph.n_buckets - 1, s));
     return ZG_OK;
 }
 
@@ -609,7 +644,7 @@ int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, StepTai
         o.tail = tail;
         return enqueue_step(g, with_logits, bucket_t_hi(g, seq_len), s, o);
     }
-    if (g->graph_stream != s) ZG_TRY(capture_all(g, s));  // the caller switched streams after zg_gpt_create
+    if (g->graph.stream != s) ZG_TRY(capture_all(g, s));  // the caller switched streams after zg_gpt_create
     hipGraphExec_t e;
     ZG_TRY(graph_exec(g, {with_logits, false, tail}, bucket_of(seq_len), s, &e));
     ZG_HIP(hipGraphLaunch(e, s));

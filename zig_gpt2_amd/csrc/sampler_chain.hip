@@ -57,7 +57,7 @@ void unpack_top(const int* ids, const float* vals, size_t rows, size_t top_n, si
 bool penalties_off(const zg_logit_penalties& p) { return p.repetition == 1.0f && p.presence == 0.0f && p.frequency == 0.0f; }
 
 // ---- Logit edits (include/zgpt2.h zg_logit_edits).  A checked set asks a call for the edit stage (any of the three
-// lists: build_edits' stage_on — the set built in the handle's edit_build goes to the device and the edit launch runs) and / or for
+// lists: build_edits' stage_on — the set built in the handle's edit.build goes to the device and the edit launch runs) and / or for
 // the sampler's min-p threshold
 bool edits_off(const zg_logit_edits& e) { return e.n_bias == 0 && e.n_allowed == 0 && e.n_banned == 0 && e.min_p == 0.0f; }
 
