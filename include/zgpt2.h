@@ -505,7 +505,7 @@ int zg_gpt_generate_sample_enqueue(zg_gpt* g, const size_t* prompts, size_t prom
                                    float temp, uint64_t seed);
 int zg_gpt_generate_sample(zg_gpt* g, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens, size_t n_steps, float temp,
                            uint64_t seed, size_t* out_tokens, size_t out_len);
-/* Sampler options of the *_ex calls, the same for every row of a call.  temp > 0.  top_k: keep the top_k largest logits of a row
+/* Sampler options of the *_ex calls: per call here, per row through zg_row_sampling.  temp > 0.  top_k: keep the top_k largest logits of a row
  * (0 or >= vocab: off).  top_p in (0, 1]: of what top-k kept, keep the smallest set of largest logits whose probability mass
  * reaches top_p (1: off) — the sequential order HF, vLLM and llama.cpp use.  For a row x: tau_k = the k-th largest value counting
  * duplicates; e = exp(x / temp - max / temp) over K = { x >= tau_k }; tau_p = the largest value v of K with
@@ -537,7 +537,7 @@ int zg_gpt_generate_sample_ex(zg_gpt* g, const size_t* prompts, size_t prompt_st
  * absolute T, b)).  past_len + n_steps <= context_size.  Works on ZG_GPT_NO_PREFILL handles (through the decode loop). */
 int zg_gpt_generate_from_enqueue(zg_gpt* g, size_t past_len, const size_t* prompts, size_t prompt_stride, const size_t* prompt_lens,
                                  size_t n_steps, const zg_sample_options* options_or_null, uint64_t seed);
-/* ---- Penalties on tokens the sequence already holds, the same for every row of a call.  Let x be a logit of a row
+/* ---- Penalties on tokens the sequence already holds: per call here, per row through zg_row_sampling.  Let x be a logit of a row
  * and c the number of times its index occurs in that row's history:
  *   c == 0: x is untouched, bit for bit.
  *   c >= 1: y = (x > 0 ? x / repetition : x * repetition); y = y - (presence + frequency * (float)c) — four separately rounded fp32
@@ -701,7 +701,7 @@ int zg_debug_stop_rows(const size_t* tokens, size_t batch, size_t stride, const 
 int zg_debug_pick_rows(const float* part_val, const int32_t* part_idx, size_t batch, size_t n_part, size_t vocab, size_t* picks_out);
 /* ---- Edits of the logit row by token id, and min-p: OpenAI / vLLM logit_bias, vLLM allowed_token_ids (HF
  * prefix_allowed_tokens_fn in its static form), vLLM bad_words / HF bad_words_ids for single tokens, and min_p (vLLM, HF, llama.cpp).
- * The same set for every row of a call, like zg_sample_options and zg_logit_penalties.
+ * The three lists are per call; min_p is per call here, per row through zg_row_sampling.
  * Row edit.  Let x be the row as the stage finds it: the raw lm_head output, or the penalised row when the call penalises —
  * penalties come first, then the edits, then temperature, top-k, top-p and min-p (HF's processor and warper order).  With
  * keep[i] = (n_allowed == 0 or i is in allowed_ids) and i is not in banned_ids:
@@ -760,6 +760,48 @@ typedef struct {
     const zg_logit_edits* edits;          /* NULL: none */
 } zg_generate_request;
 int zg_gpt_generate_request_enqueue(zg_gpt* g, const zg_generate_request* r);
+/* ---- Sampling parameters per row.  A handle decodes its rows in lock step, and the rows may belong to different
+ * requests: one zg_row_sampling per row carries everything that shapes a pick.  Sequences never interact, so row b of a per-row
+ * call is, BIT FOR BIT, row b of the uniform call on the same handle that is given rows[b].options, rows[b].min_p,
+ * rows[b].penalties and rows[b].seed for every row — tokens, probabilities, thresholds, the log-probability record, finish columns
+ * and reasons.  Every row has the sampler form its own parameters ask for (plain, one filter, both, min-p alone) and that form's
+ * arithmetic, whatever its neighbours run; a row whose penalties are off is not touched by the penalty stage.  The chain is
+ * launched once for all rows, in the union of their needs: the selection launches of the row that needs most (0 / 3 / 6), the
+ * threshold-aware tail if any row has a filter or min-p, the penalty stage if any row is penalised — the graphs of
+ * ZG_GPT_TRUNCATED_ / _PENALIZED_ / _EDITED_ / _LOGPROBS_ / _STOP_GENERATE serve these calls as they are.  There is no per-row
+ * greedy flag: greedy is top_k = 1 (it differs from zg_gpt_generate_greedy only on exact fp32 ties of the row maximum).
+ * Per call, not per row: the edit lists, the stop conditions, top_n, n_steps, past_len and the prior's layout.
+ * Refusals, all before anything is enqueued or the handle's state (zg_gpt_cached_len, the records) is touched, the message naming
+ * the row.  ZG_ERR_ARG: a row with bad options (temp <= 0, top_p outside (0, 1]), bad penalties or min_p outside [0, 1); n_rows !=
+ * the handle's batch; NULL rows; options, penalties or a non-zero edits->min_p given beside rows.  ZG_ERR_UNSUPPORTED: any row
+ * penalised on a handle with context_size > 8192. */
+typedef struct {
+    zg_sample_options options;     /* temp > 0; top_k (0 or >= vocab: off); top_p in (0, 1] (1: off) */
+    float min_p;                   /* in [0, 1); 0 = off */
+    zg_logit_penalties penalties;  /* {1, 0, 0} = off */
+    uint64_t seed;                 /* the row's draws: counter PRNG of (seed, absolute T, b), b the row's index in the handle */
+} zg_row_sampling;
+/* zg_gpt_generate_request_enqueue with the sampler parameters taken per row: rows [n_rows], n_rows == the handle's batch.
+ * r->options and r->penalties must be NULL, r->edits (if given) must have min_p == 0, r->seed is not read; prior, logprobs / top_n,
+ * stop, the three edit lists and past_len stay per call and work as there. */
+int zg_gpt_generate_each_enqueue(zg_gpt* g, const zg_generate_request* r, const zg_row_sampling* rows, size_t n_rows);
+/* zg_gpt_sample_edit with rows (the per-token twin).  uniforms NULL: the draw of row b is the counter PRNG of (rows[b].seed,
+ * seq_len, b).  edits_or_null: the three lists (min_p must be 0).  The history is read when any row is penalised. */
+int zg_gpt_sample_each(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_row_sampling* rows, size_t n_rows,
+                       const size_t* history, size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits_or_null,
+                       const float* uniforms, size_t* tokens_out, float* probs_out, size_t probs_len);
+/* Test entries: zg_debug_edit_rows and zg_debug_penalize_rows with one zg_row_sampling per row (n_rows == batch <= 64, vocab <=
+ * 262144; edits_or_null: the three lists, min_p 0).  thresholds_out: -inf for a row that truncates nothing.  Need zg_init only. */
+int zg_debug_sample_rows_each(const float* logits, size_t batch, size_t vocab, const zg_row_sampling* rows, size_t n_rows,
+                              const zg_logit_edits* edits_or_null, const float* uniforms, float* edited_out_or_null, size_t* tokens_out,
+                              float* probs_out_or_null, float* thresholds_out_or_null);
+int zg_debug_penalize_rows_each(const float* logits, size_t batch, size_t vocab, const zg_row_sampling* rows, size_t n_rows,
+                                const size_t* history, size_t history_stride, const size_t* history_lens, float* logits_out,
+                                unsigned* counts_out_or_null);
+/* What a table of rows is launched as (needs neither a GPU nor zg_init): out[0] = the sampler form of the chain — 1 plain, 2 one
+ * filter, 3 two filters, 4 min-p alone —, out[1] = whether the penalty stage runs, out[2 + b] = the form row b itself has; n_out >=
+ * 2 + n_rows, n_rows <= 64.  Returns the refusal a call over `vocab` logits would return for the table. */
+int zg_debug_each_plan(const zg_row_sampling* rows, size_t n_rows, size_t vocab, int* out, size_t n_out);
 /* Test entry: the edit stage and the sampler behind it alone on the caller's rows, logits [batch <= 64, vocab <= 262144] (host or
  * device, as uniforms [batch] and the outputs), a small kernel standing in for lm_head's row-maximum partials.  edited_out
  * [batch, vocab]: the rows as the stage leaves them; tokens_out, probs_out and thresholds_out (max(tau_k, tau_p, tau_m) of each

@@ -57,6 +57,29 @@ class LogitEdits(C.Structure):
                 ("min_p", C.c_float)]
 
 
+class RowSampling(C.Structure):
+    """zg_row_sampling of include/zgpt2.h."""
+
+    _fields_ = [("options", SampleOptions), ("min_p", C.c_float), ("penalties", LogitPenalties), ("seed", C.c_uint64)]
+
+
+def row_sampling(rows):
+    """An array of zg_row_sampling from a list of dicts with generate_sample's keyword names (temp, top_k, top_p, min_p,
+    repetition_penalty, presence_penalty, frequency_penalty) plus seed.  A row's temp 0 / None is greedy: {temp 1, top_k 1}."""
+    arr = (RowSampling * max(len(rows), 1))()
+    known = {"temp", "top_k", "top_p", "min_p", "repetition_penalty", "presence_penalty", "frequency_penalty", "seed"}
+    for b, r in enumerate(rows):
+        if set(r) - known:
+            raise TypeError(f"row {b}: unknown sampling parameter(s) {sorted(set(r) - known)}")
+        temp, top_k = r.get("temp", 1.0), int(r.get("top_k", 0))
+        if temp is None or float(temp) == 0.0:
+            temp, top_k = 1.0, 1
+        arr[b] = RowSampling(SampleOptions(float(temp), top_k, float(r.get("top_p", 1.0))), float(r.get("min_p", 0.0)),
+                             LogitPenalties(float(r.get("repetition_penalty", 1.0)), float(r.get("presence_penalty", 0.0)),
+                                            float(r.get("frequency_penalty", 0.0))), int(r.get("seed", 0)))
+    return arr
+
+
 class GenerateRequest(C.Structure):
     """zg_generate_request of include/zgpt2.h (`size` is filled by generate_request())."""
 
@@ -172,6 +195,11 @@ SIGNATURES = {
     "zg_gpt_generate_request_enqueue": (C.c_int, [vp, vp]),
     "zg_debug_edit_rows": (C.c_int, [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]),
     "zg_debug_min_p_offset": (C.c_int, [C.c_float, C.c_float, f32p]),
+    "zg_gpt_generate_each_enqueue": (C.c_int, [vp, vp, vp, sz]),
+    "zg_gpt_sample_each": (C.c_int, [vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, sz]),
+    "zg_debug_sample_rows_each": (C.c_int, [vp, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]),
+    "zg_debug_penalize_rows_each": (C.c_int, [vp, sz, sz, vp, sz, vp, sz, vp, vp, vp]),
+    "zg_debug_each_plan": (C.c_int, [vp, sz, sz, vp, sz]),
     "zg_gpt_score": (C.c_int, [vp, sz, vp, sz, sz, sz, vp, sz]),
     "zg_debug_score_rows": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, vp, vp]),
     "zg_gpt_time_kernel": (C.c_int, [vp, C.c_int, C.c_int, f32p, szp]),

@@ -16,6 +16,7 @@
 
 #include "sampler_chain.h"
 
+constexpr size_t kRowsMax = 8;  // rows of a handle (zg_gpt_create: batch <= 8): entries of the per-row parameter arrays
 constexpr size_t kSkFlagWords = 512;  // flag words of the stream-K hand-over (zg_gpt.pass.sk_flags): four per shared tile, 128 shared tiles
 
 struct zg_layer {
@@ -40,14 +41,14 @@ struct StepModes {
 // `fault`, the host stages the rest; the groups of zg_gpt hold pointers to their members.
 struct PinnedCtrl {
     StepCtrl ctrl;
-    alignas(128) SampleParams samp;  // samp.h_params
+    alignas(128) SampleParams samp[kRowsMax];  // samp.h_params: one entry per row (batch <= 8)
     alignas(128) unsigned fault;     // hand.fault: written by the kernels
     alignas(64) float uniforms[8];   // the per-token family's draws (batch <= 8): h_ints[0 .. batch) is still being read by the forward's token upload
-    alignas(128) PenParams pen;      // pen.h_params
+    alignas(128) PenParams pen[kRowsMax];      // pen.h_params: one entry per row
     alignas(32) int top_n;           // lp.h_top
 };
-static_assert(offsetof(PinnedCtrl, samp) == 128 && offsetof(PinnedCtrl, fault) == 256 && offsetof(PinnedCtrl, uniforms) == 320 &&
-                  offsetof(PinnedCtrl, pen) == 384 && offsetof(PinnedCtrl, top_n) == 416,
+static_assert(sizeof(SampleParams) == 24 && sizeof(PenParams) == 16 && offsetof(PinnedCtrl, samp) == 128 && offsetof(PinnedCtrl, fault) == 384 &&
+                  offsetof(PinnedCtrl, uniforms) == 448 && offsetof(PinnedCtrl, pen) == 512 && offsetof(PinnedCtrl, top_n) == 640,
               "the pinned control block keeps its layout");
 
 struct zg_gpt {
@@ -168,12 +169,12 @@ struct zg_gpt {
     struct {
         int* sampled;            // [batch]: the sampler's draw from the last step's logits
         float* ws;               // segment sums of the sampler (sample_workspace_floats)
-        SampleParams* params;    // device: temperature and seed of the generation in flight
+        SampleParams* params;    // device [kRowsMax]: each row's temperature, filters and seed of the generation in flight
         SampleParams* h_params;  // pinned mirror (PinnedCtrl.samp)
         FilterWs filt;           // selection workspace of the truncated sampler (sample_filter.h), zero at create
     } samp;
     // generate — logit penalties (sample_penalty.h): the caller's prior / explicit history [batch][ctx] with its lengths,
-    // the values of the call in flight, their pinned mirrors (h_params: PinnedCtrl.pen; h_prior: [batch * ctx] tokens, then [batch]
+    // the values of the call in flight, one entry per row ([kRowsMax]), their pinned mirrors (h_params: PinnedCtrl.pen; h_prior: [batch * ctx] tokens, then [batch]
     // lengths, behind h_ints).  The kernels' table is LDS: no workspace
     struct {
         int *prior, *prior_len;

@@ -90,12 +90,12 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
     g->cur_token = (int*)P(B * 4);
     g->out_tokens = (int*)P(B * C * 4);
     g->samp.sampled = (int*)P(B * 4);
-    g->samp.params = (SampleParams*)P(sizeof(SampleParams));
+    g->samp.params = (SampleParams*)P(kRowsMax * sizeof(SampleParams));
     g->samp.ws = (float*)P(sample_workspace_floats((int)B) * 4);
     g->samp.filt = filter_workspace(P(filter_workspace_bytes((int)B)), (int)B);
     g->pen.prior = (int*)P(B * C * 4);
     g->pen.prior_len = (int*)P(B * 4);
-    g->pen.params = (PenParams*)P(sizeof(PenParams));
+    g->pen.params = (PenParams*)P(kRowsMax * sizeof(PenParams));
     g->xp = (bf16_t*)P(E * 48);
     g->hp = (bf16_t*)P(4 * E * 48);
     g->ap = (bf16_t*)P(E * 48);
@@ -268,10 +268,10 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
     if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(control mirrors)", __FILE__, __LINE__);
     g->edit.build.assign(edit_block_bytes(c.vocab_size), 0);
     memset(g->stop.pinned, 0, sizeof(*g->stop.pinned));
-    g->samp.h_params = &g->h_ctrl->samp;
+    g->samp.h_params = g->h_ctrl->samp;
     g->hand.fault = &g->h_ctrl->fault;
     *g->hand.fault = 0;
-    g->pen.h_params = &g->h_ctrl->pen;
+    g->pen.h_params = g->h_ctrl->pen;
     g->pen.h_prior = g->h_ints + batch * c.context_size + batch;
     g->lp.h_top = &g->h_ctrl->top_n;
     ZG_REQUIRE(!(g->flags & ZG_GPT_PENALIZED_GENERATE) || c.context_size <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED,

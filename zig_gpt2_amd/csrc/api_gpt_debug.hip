@@ -446,24 +446,30 @@ int zg_debug_score_rows(const float* logits, size_t rows, size_t vocab, size_t r
 }
 
 // The sampler chain on the caller's rows (tests), a small kernel standing in for lm_head's row-maximum partials: the body of
-// zg_debug_edit_rows, and with edits null — no edit stage, no min-p — of zg_debug_sample_rows.  Allocates its workspace per call.
-static int debug_sample_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const zg_logit_edits* edits, const float* uniforms,
-                             float* edited_out, size_t* tokens_out, float* probs_out, float* thresholds_out, const char* who) {
-    ZG_TRY(check_sample_options(opt, who));
+// zg_debug_edit_rows, and with edits null — no edit stage, no min-p — of zg_debug_sample_rows; with a table of the caller's
+// (opt null, per_row), of zg_debug_sample_rows_each.  Allocates its workspace per call.
+static int debug_sample_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const zg_row_sampling* each,
+                             const zg_logit_edits* edits, const float* uniforms, float* edited_out, size_t* tokens_out, float* probs_out,
+                             float* thresholds_out, const char* who) {
+    if (!each) ZG_TRY(check_sample_options(opt, who));
     ZG_REQUIRE(logits && uniforms && tokens_out && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG, "%s: bad argument", who);
     std::vector<char> block(edits ? edit_block_bytes(vocab) : 0);
     bool stage_on = false;
     if (edits) ZG_TRY(build_edits(edits, vocab, who, block.data(), &stage_on));
     const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
-    SampleParams hp{};
-    const SamplerMode mode = fill_sample_params(&hp, vocab, *opt, 0, edits ? edits->min_p : 0.0f);
+    std::vector<zg_row_sampling> table(batch);
+    if (!each) uniform_rows(table.data(), batch, *opt, edits ? edits->min_p : 0.0f, nullptr, 0);
+    std::vector<SampleParams> hp(batch);
+    StepTail plan;
+    ZG_TRY(plan_rows(each ? each : table.data(), batch, vocab, 0, who, hp.data(), nullptr, nullptr, &plan));
+    const SamplerMode mode = plan.sampler;
     hipStream_t s = ctx().stream;
     DevScratch ds;
     char *d_filt, *d_edit;
     SampleParams* d_par;
     float* d_u;
     SamplerChain c{};
-    c.batch = B, c.vocab = V, c.n_part = n_part, c.temp = opt->temp, c.write_probs = probs_out != nullptr;
+    c.batch = B, c.vocab = V, c.n_part = n_part, c.temp = each ? 1.0f : opt->temp, c.per_row = each != nullptr, c.write_probs = probs_out != nullptr;
     ZG_TRY(ds.carve([&] {
         d_filt = ds.take<char>(filter_workspace_bytes(B));
         c.filt = filter_workspace(d_filt, B);
@@ -471,7 +477,7 @@ static int debug_sample_rows(const float* logits, size_t batch, size_t vocab, co
         c.seg_ws = ds.take<float>(sample_workspace_floats(B) * 4);
         c.part_val = ds.take<float>((size_t)B * n_part * 4);
         c.part_idx = ds.take<int>((size_t)B * n_part * 4);
-        c.params = d_par = ds.take<SampleParams>(sizeof(SampleParams));
+        c.params = d_par = ds.take<SampleParams>(batch * sizeof(SampleParams));
         c.u = d_u = ds.take<float>(batch * 4);
         c.pick = ds.take<int>(batch * 4);
         d_edit = ds.take<char>(block.size());
@@ -489,7 +495,7 @@ static int debug_sample_rows(const float* logits, size_t batch, size_t vocab, co
     ZG_HIP(hipMemsetAsync(d_filt, 0, filter_workspace_bytes(B), s));  // (the selection chain starts from a zeroed workspace and leaves it so)
     ZG_HIP(hipMemcpyAsync(c.logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
     ZG_HIP(hipMemcpyAsync(d_u, h_u.data(), batch * 4, hipMemcpyHostToDevice, s));
-    ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_par, hp.data(), batch * sizeof(SampleParams), hipMemcpyHostToDevice, s));
     ZG_TRY(launch_row_max_partials(c.logits, B, V, c.part_val, n_part, s));  // (lm_head's stand-in: the partials of the row as the chain finds it)
     if (stage_on) ZG_HIP(hipMemcpyAsync(d_edit, block.data(), block.size(), hipMemcpyHostToDevice, s));
     // the chain in two parts, the edited rows leaving between them: the row stage (no sampler), then the sampler alone
@@ -508,7 +514,7 @@ static int debug_sample_rows(const float* logits, size_t batch, size_t vocab, co
 int zg_debug_sample_rows(const float* logits, size_t batch, size_t vocab, const zg_sample_options* opt, const float* uniforms, size_t* tokens_out,
                          float* probs_out, float* thresholds_out) {
     ZG_TRY(require_init());
-    return debug_sample_rows(logits, batch, vocab, opt, nullptr, uniforms, nullptr, tokens_out, probs_out, thresholds_out, "debug_sample_rows");
+    return debug_sample_rows(logits, batch, vocab, opt, nullptr, nullptr, uniforms, nullptr, tokens_out, probs_out, thresholds_out, "debug_sample_rows");
 }
 
 // ... with the edit stage in front of the sampler and min-p in it; here the edits are required.  Everything off: zg_debug_sample_rows.
@@ -516,14 +522,23 @@ int zg_debug_edit_rows(const float* logits, size_t batch, size_t vocab, const zg
                        float* edited_out, size_t* tokens_out, float* probs_out, float* thresholds_out) {
     ZG_TRY(require_init());
     ZG_REQUIRE(edits != nullptr, ZG_ERR_ARG, "debug_edit_rows: edits is null");
-    return debug_sample_rows(logits, batch, vocab, opt, edits, uniforms, edited_out, tokens_out, probs_out, thresholds_out, "debug_edit_rows");
+    return debug_sample_rows(logits, batch, vocab, opt, nullptr, edits, uniforms, edited_out, tokens_out, probs_out, thresholds_out, "debug_edit_rows");
 }
 
-// The penalty kernels on the caller's rows (tests): the launches of the penalised step, in place on a copy.  Allocates per call.
-int zg_debug_penalize_rows(const float* logits, size_t batch, size_t vocab, const zg_logit_penalties* pen, const size_t* history, size_t history_stride,
-                           const size_t* history_lens, float* logits_out, unsigned* counts_out) {
+// ... with one zg_row_sampling per row; the edits carry lists only and may be null
+int zg_debug_sample_rows_each(const float* logits, size_t batch, size_t vocab, const zg_row_sampling* rows, size_t n_rows, const zg_logit_edits* edits,
+                              const float* uniforms, float* edited_out, size_t* tokens_out, float* probs_out, float* thresholds_out) {
     ZG_TRY(require_init());
-    ZG_TRY(check_penalties(pen, "debug_penalize_rows"));
+    ZG_REQUIRE(rows != nullptr, ZG_ERR_ARG, "debug_sample_rows_each: rows is null");
+    ZG_REQUIRE(n_rows == batch, ZG_ERR_ARG, "debug_sample_rows_each: %zu rows for a batch of %zu", n_rows, batch);
+    ZG_REQUIRE(!edits || edits->min_p == 0.0f, ZG_ERR_ARG, "debug_sample_rows_each: edits->min_p %f beside rows (min-p is the row's)", edits->min_p);
+    return debug_sample_rows(logits, batch, vocab, nullptr, rows, edits, uniforms, edited_out, tokens_out, probs_out, thresholds_out, "debug_sample_rows_each");
+}
+
+// The penalty kernels on the caller's rows (tests): the launches of the penalised step, in place on a copy — the body of
+// zg_debug_penalize_rows (pen: the same for every row) and of zg_debug_penalize_rows_each (each: the row's own).  Allocates per call.
+static int debug_penalize_rows(const float* logits, size_t batch, size_t vocab, const zg_logit_penalties* pen, const zg_row_sampling* each,
+                               const size_t* history, size_t history_stride, const size_t* history_lens, float* logits_out, unsigned* counts_out) {
     ZG_REQUIRE(logits && logits_out && history_lens && batch >= 1 && batch <= 64 && vocab >= 1 && vocab <= (size_t)64 * 4096, ZG_ERR_ARG,
                "debug_penalize_rows: bad argument");
     size_t longest = 0;
@@ -554,29 +569,51 @@ int zg_debug_penalize_rows(const float* logits, size_t batch, size_t vocab, cons
         c.part_val = ds.take<float>((size_t)B * n_part * 4);
         c.part_idx = ds.take<int>((size_t)B * n_part * 4);
         d_len = ds.take<int>(batch * 4);
-        c.pen = d_par = ds.take<PenParams>(sizeof(PenParams));
+        c.pen = d_par = ds.take<PenParams>(batch * sizeof(PenParams));
     }));
     std::vector<int> h_hist(batch * stride, 0), h_len(batch);
     for (size_t b = 0; b < batch; ++b) {
         h_len[b] = (int)history_lens[b];
         for (size_t i = 0; i < history_lens[b]; ++i) h_hist[b * stride + i] = (int)history[b * history_stride + i];
     }
-    const PenParams hp{pen->repetition, pen->presence, pen->frequency, 0};
+    std::vector<PenParams> hp(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        const zg_logit_penalties& p = each ? each[b].penalties : *pen;
+        hp[b] = PenParams{p.repetition, p.presence, p.frequency, 0};
+    }
     ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
     ZG_HIP(hipMemsetAsync(d_counts, 0, batch * vocab * 4, s));
     ZG_HIP(hipMemcpyAsync(d_hist, h_hist.data(), batch * stride * 4, hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(d_len, h_len.data(), batch * 4, hipMemcpyHostToDevice, s));
-    ZG_HIP(hipMemcpyAsync(d_par, &hp, sizeof(hp), hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_par, hp.data(), batch * sizeof(PenParams), hipMemcpyHostToDevice, s));
     c.hist.prior = d_hist;
     c.hist.prior_len = d_len;
     c.hist.prior_stride = (int)stride;
     c.hist.max_hist = (int)longest;
     ZG_TRY(emit_sampler_chain(c, StepTail{GREEDY, true}, s));
-    // all penalties off: the call is the identity on the rows (the counts are still the history's)
-    ZG_HIP(hipMemcpyAsync(logits_out, penalties_off(*pen) ? logits : d_logits, batch * vocab * 4, hipMemcpyDefault, s));
+    // all penalties off: the call is the identity on the rows (the counts are still the history's); per row, the kernel leaves such
+    // a row alone itself
+    ZG_HIP(hipMemcpyAsync(logits_out, pen && penalties_off(*pen) ? logits : d_logits, batch * vocab * 4, hipMemcpyDefault, s));
     if (counts_out) ZG_HIP(hipMemcpyAsync(counts_out, d_counts, batch * vocab * 4, hipMemcpyDefault, s));
     ZG_HIP(hipStreamSynchronize(s));
     return ZG_OK;
+}
+
+int zg_debug_penalize_rows(const float* logits, size_t batch, size_t vocab, const zg_logit_penalties* pen, const size_t* history, size_t history_stride,
+                           const size_t* history_lens, float* logits_out, unsigned* counts_out) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_penalties(pen, "debug_penalize_rows"));
+    return debug_penalize_rows(logits, batch, vocab, pen, nullptr, history, history_stride, history_lens, logits_out, counts_out);
+}
+
+int zg_debug_penalize_rows_each(const float* logits, size_t batch, size_t vocab, const zg_row_sampling* rows, size_t n_rows, const size_t* history,
+                                size_t history_stride, const size_t* history_lens, float* logits_out, unsigned* counts_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(rows != nullptr, ZG_ERR_ARG, "debug_penalize_rows_each: rows is null");
+    ZG_REQUIRE(n_rows == batch && batch <= 64, ZG_ERR_ARG, "debug_penalize_rows_each: %zu rows for a batch of %zu (<= 64)", n_rows, batch);
+    StepTail plan;
+    ZG_TRY(plan_rows(rows, n_rows, vocab ? vocab : 1, 0, "debug_penalize_rows_each", nullptr, nullptr, nullptr, &plan));
+    return debug_penalize_rows(logits, batch, vocab, nullptr, rows, history, history_stride, history_lens, logits_out, counts_out);
 }
 
 int zg_gpt_profile_step(zg_gpt* g, size_t seq_len, int iters, float* us_out, size_t n_out) {

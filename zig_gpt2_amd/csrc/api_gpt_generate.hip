@@ -63,40 +63,43 @@ static int check_history(const zg_gpt* g, const size_t* tokens, size_t stride, c
     return ZG_OK;
 }
 
-// The penalties of the call and its token lists (checked) through their pinned mirrors into the arena.  PRECONDITION: nothing in
-// flight reads the mirrors (every penalised call drains, or begins by draining).
-static int stage_penalties(zg_gpt* g, const zg_logit_penalties& p, size_t past, const size_t* tokens, size_t stride, const size_t* lens, hipStream_t s) {
+// The penalties of the call — pp[batch], one entry per row as plan_rows fills them — and its token lists (checked) through their
+// pinned mirrors into the arena.  PRECONDITION: nothing in flight reads the mirrors (every penalised call drains, or begins by draining).
+static int stage_penalties(zg_gpt* g, const PenParams* pp, const size_t* tokens, size_t stride, const size_t* lens, hipStream_t s) {
     const size_t C = g->cfg.context_size, B = g->batch;
-    *g->pen.h_params = PenParams{p.repetition, p.presence, p.frequency, (int)past};
+    memcpy(g->pen.h_params, pp, B * sizeof(PenParams));
     int* h_len = g->pen.h_prior + B * C;
     for (size_t b = 0; b < B; ++b) {
         h_len[b] = tokens ? (int)lens[b] : 0;
         for (size_t i = 0; tokens && i < lens[b]; ++i) g->pen.h_prior[b * C + i] = (int)tokens[b * stride + i];
     }
-    ZG_HIP(hipMemcpyAsync(g->pen.params, g->pen.h_params, sizeof(PenParams), hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(g->pen.params, g->pen.h_params, B * sizeof(PenParams), hipMemcpyHostToDevice, s));
     if (tokens) ZG_HIP(hipMemcpyAsync(g->pen.prior, g->pen.h_prior, B * C * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(g->pen.prior_len, h_len, B * sizeof(int), hipMemcpyHostToDevice, s));
     return ZG_OK;
 }
 
-// GPT.sample (main.zig:198-207) behind one forward step: the checked body of the per-token family — zg_gpt_sample_edit's, under the
-// name of the entry point that calls it; each entry point keeps in front what it is stricter about.  penalties null: none, the
-// history is not read; an entry point without edits passes kNoEdits.  Everything the chain reads is staged first: the chain only launches.
+// GPT.sample (main.zig:198-207) behind one forward step: the checked body of the per-token family, under the name of the entry
+// point that calls it; each entry point keeps in front what it is stricter about.  rows [batch]: the table of the call (a uniform
+// entry point's: equal entries, per_row false — its plain sampler takes the temperature by value and stages nothing); with_history:
+// the history is the caller's to get right (penalties were given / a row is penalised), else it is not read; an entry point without
+// edits passes kNoEdits.  Everything the chain reads is staged first: the chain only launches.
 static const zg_logit_edits kNoEdits{};
-static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
+static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_row_sampling* rows, bool per_row, bool with_history,
                        const size_t* history, size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits, const float* uniforms,
-                       uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len, const char* who) {
-    ZG_TRY(require_init());
-    ZG_TRY(check_sample_options(opt, who));
-    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null handle", who);
-    if (pen) {
-        ZG_TRY(check_penalties(pen, who));
+                       size_t* tokens_out, float* probs_out, size_t probs_len, const char* who) {
+    if (with_history) {
         ZG_TRY(check_pen_handle(g, who));
         ZG_TRY(check_history(g, history, history_stride, history_lens, 0, who));
     }
     bool edit_on = false;
     ZG_TRY(build_edits(edits, g->cfg.vocab_size, who, g->edit.build.data(), &edit_on));
-    const bool pen_on = pen && !penalties_off(*pen);
+    SampleParams sp[kRowsMax];
+    PenParams pp[kRowsMax];
+    StepTail plan;
+    ZG_TRY(plan_rows(rows, g->batch, g->cfg.vocab_size, 0, who, sp, pp, nullptr, &plan));
+    const bool pen_on = plan.pen;
+    const SamplerMode mode = plan.sampler;
     if (pen_on || edit_on) ZG_HIP(hipStreamSynchronize(gs(g)));  // (an enqueued generation may still be reading the pinned mirrors; idle otherwise)
     ZG_REQUIRE(tokens && tokens_out, ZG_ERR_ARG, "gpt_sample: bad argument");
     const size_t V = g->cfg.vocab_size, B = g->batch;
@@ -105,18 +108,18 @@ static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n
         ZG_REQUIRE(uniforms[b] >= 0.0f && uniforms[b] < 1.0f, ZG_ERR_ARG, "gpt_sample: uniform %f outside [0,1)", uniforms[b]);
     ZG_TRY(forward_enqueue(g, seq_len, tokens, n_tokens, 1, nullptr, 0));  // main.zig:199 (not drained: the sampler goes behind it)
     hipStream_t s = gs(g);
-    if (pen_on) ZG_TRY(stage_penalties(g, *pen, 0, history, history_stride, history_lens, s));
+    if (pen_on) ZG_TRY(stage_penalties(g, pp, history, history_stride, history_lens, s));
     if (edit_on) ZG_TRY(stage_edits(g, s));
     float* h_u = g->h_ctrl->uniforms;  // (pinned: h_ints[0 .. B) is still being read by the forward's token upload)
-    // (no uniforms: the counter PRNG the device loop's sampler draws from, zg_common.h)
-    for (size_t b = 0; b < B; ++b) h_u[b] = uniforms ? uniforms[b] : counter_uniform(seed, seq_len, b);
+    // (no uniforms: the counter PRNG the device loop's sampler draws from, zg_common.h — of the row's own seed)
+    for (size_t b = 0; b < B; ++b) h_u[b] = uniforms ? uniforms[b] : counter_uniform(sp[b].seed, seq_len, b);
     SamplerChain c = handle_chain(g, false);
     float* d_u = g->q;  // scratch: q is dead after the forward
     ZG_HIP(hipMemcpyAsync(d_u, h_u, B * sizeof(float), hipMemcpyHostToDevice, s));
-    // (samp.h_params: nothing in flight reads it, forward_enqueue's callers drain; the plain sampler takes its temperature by value)
-    const SamplerMode mode = fill_sample_params(g->samp.h_params, V, *opt, seed, edits->min_p);
-    if (threshold_sampler(mode)) ZG_HIP(hipMemcpyAsync(g->samp.params, g->samp.h_params, sizeof(SampleParams), hipMemcpyHostToDevice, s));
-    c.u = d_u, c.temp = opt->temp, c.write_probs = probs_out != nullptr, c.pick = g->cur_token;
+    // (samp.h_params: nothing in flight reads it, forward_enqueue's callers drain; a uniform plain sampler takes its temperature by value)
+    memcpy(g->samp.h_params, sp, B * sizeof(SampleParams));
+    if (threshold_sampler(mode) || per_row) ZG_HIP(hipMemcpyAsync(g->samp.params, g->samp.h_params, B * sizeof(SampleParams), hipMemcpyHostToDevice, s));
+    c.u = d_u, c.temp = rows[0].options.temp, c.per_row = per_row, c.write_probs = probs_out != nullptr, c.pick = g->cur_token;
     ZG_TRY(emit_sampler_chain(c, StepTail{mode, pen_on, false, false, edit_on}, s));  // main.zig:200-206
     ZG_HIP(hipMemcpyAsync(g->h_ints + B, g->cur_token, B * sizeof(int), hipMemcpyDeviceToHost, s));
     if (probs_out) ZG_TRY(copy_out_f32(probs_out, g->logits, B * V, s));
@@ -126,19 +129,56 @@ static int sample_impl(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n
     return ZG_OK;
 }
 
+// The uniform entry points of the family: what they have always checked first, then the table of `batch` equal rows.  penalties
+// null: none, the history is not read.
+static int sample_uniform(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
+                          const size_t* history, size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits, const float* uniforms,
+                          uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len, const char* who) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_sample_options(opt, who));
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null handle", who);
+    if (pen) ZG_TRY(check_penalties(pen, who));
+    zg_row_sampling rows[kRowsMax];
+    // (a min_p that build_edits is about to refuse travels no further than that refusal)
+    const float min_p = edits && edits->min_p >= 0.0f && edits->min_p < 1.0f ? edits->min_p : 0.0f;
+    uniform_rows(rows, g->batch, *opt, min_p, pen, seed);
+    return sample_impl(g, seq_len, tokens, n_tokens, rows, false, pen != nullptr, history, history_stride, history_lens, edits, uniforms, tokens_out,
+                       probs_out, probs_len, who);
+}
+
+// Beside rows nothing else may say what the sampler does: the edits of a per-row call carry lists only
+static int check_each_args(const zg_gpt* g, const zg_row_sampling* rows, size_t n_rows, const zg_logit_edits* edits, const char* who) {
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null handle", who);
+    ZG_REQUIRE(rows != nullptr, ZG_ERR_ARG, "%s: rows is null", who);
+    ZG_REQUIRE(n_rows == g->batch, ZG_ERR_ARG, "%s: %zu rows for a handle of batch %zu", who, n_rows, g->batch);
+    ZG_REQUIRE(!edits || edits->min_p == 0.0f, ZG_ERR_ARG, "%s: edits->min_p %f beside rows (min-p is the row's)", who, edits->min_p);
+    return ZG_OK;
+}
+
+int zg_gpt_sample_each(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_row_sampling* rows, size_t n_rows, const size_t* history,
+                       size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits, const float* uniforms, size_t* tokens_out,
+                       float* probs_out, size_t probs_len) {
+    ZG_TRY(require_init());
+    ZG_TRY(check_each_args(g, rows, n_rows, edits, "gpt_sample_each"));
+    StepTail plan;
+    ZG_TRY(plan_rows(rows, n_rows, g->cfg.vocab_size, 0, "gpt_sample_each", nullptr, nullptr, nullptr, &plan));
+    return sample_impl(g, seq_len, tokens, n_tokens, rows, true, plan.pen, history, history_stride, history_lens, edits ? edits : &kNoEdits, uniforms,
+                       tokens_out, probs_out, probs_len, "gpt_sample_each");
+}
+
 int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp, const float* uniforms,
                   uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(temp > 0.0f, ZG_ERR_ARG, "gpt_sample: bad argument");
     const zg_sample_options plain{temp, 0, 1.0f};
-    return sample_impl(g, seq_len, tokens, n_tokens, &plain, nullptr, nullptr, 0, nullptr, &kNoEdits, uniforms, seed, tokens_out, probs_out, probs_len,
+    return sample_uniform(g, seq_len, tokens, n_tokens, &plain, nullptr, nullptr, 0, nullptr, &kNoEdits, uniforms, seed, tokens_out, probs_out, probs_len,
                        "gpt_sample");
 }
 
 // zg_gpt_sample behind top-k / nucleus truncation (filters off: exactly zg_gpt_sample's launches)
 int zg_gpt_sample_ex(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const float* uniforms,
                      uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
-    return sample_impl(g, seq_len, tokens, n_tokens, opt, nullptr, nullptr, 0, nullptr, &kNoEdits, uniforms, seed, tokens_out, probs_out, probs_len,
+    return sample_uniform(g, seq_len, tokens, n_tokens, opt, nullptr, nullptr, 0, nullptr, &kNoEdits, uniforms, seed, tokens_out, probs_out, probs_len,
                        "gpt_sample_ex");
 }
 
@@ -148,7 +188,7 @@ int zg_gpt_sample_pen(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_
                       float* probs_out, size_t probs_len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(pen != nullptr, ZG_ERR_ARG, "gpt_sample_pen: penalties is null");
-    return sample_impl(g, seq_len, tokens, n_tokens, opt, pen, history, history_stride, history_lens, &kNoEdits, uniforms, seed, tokens_out, probs_out,
+    return sample_uniform(g, seq_len, tokens, n_tokens, opt, pen, history, history_stride, history_lens, &kNoEdits, uniforms, seed, tokens_out, probs_out,
                        probs_len, "gpt_sample_pen");
 }
 
@@ -156,7 +196,7 @@ int zg_gpt_sample_pen(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_
 int zg_gpt_sample_edit(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, const zg_sample_options* opt, const zg_logit_penalties* pen,
                        const size_t* history, size_t history_stride, const size_t* history_lens, const zg_logit_edits* edits, const float* uniforms,
                        uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len) {
-    return sample_impl(g, seq_len, tokens, n_tokens, opt, pen, history, history_stride, history_lens, edits, uniforms, seed, tokens_out, probs_out,
+    return sample_uniform(g, seq_len, tokens, n_tokens, opt, pen, history, history_stride, history_lens, edits, uniforms, seed, tokens_out, probs_out,
                        probs_len, "gpt_sample_edit");
 }
 
@@ -178,13 +218,12 @@ struct GenRequest {
     size_t stride;
     const size_t* lens;
     size_t n_steps, past;
-    SamplerMode mode;       // GREEDY (opt unused), or PLAIN: draw with opt — gen_begin raises it to the filters opt switches on
-    zg_sample_options opt;
-    uint64_t seed;
-    // penalties (a sampler only; pen_on false: none, the request is what it was without them) and the caller's prior of every row of
-    // the ONE handle such a request goes to: [rows][prior_stride], prior_lens[rows] tokens each, or null
+    SamplerMode mode = GREEDY;  // GREEDY (sp unused), or the sampler the chain is launched as (plan_rows: the union of the rows' needs)
+    SampleParams sp[kRowsMax];  // ... and each row's parameters as the kernels read them, for the ONE handle a sampler request goes to
+    // penalties (a sampler only; pen_on false: none, the request is what it was without them), pp: each row's; and the caller's prior
+    // of every row of that handle: [rows][prior_stride], prior_lens[rows] tokens each, or null
     bool pen_on = false;
-    zg_logit_penalties pen{1.0f, 0.0f, 0.0f};
+    PenParams pp[kRowsMax];
     const size_t* prior = nullptr;
     size_t prior_stride = 0;
     const size_t* prior_lens = nullptr;
@@ -195,13 +234,10 @@ struct GenRequest {
     bool stop_on = false;
     zg_stop_conditions stop{};
     // logit edits, checked, the set built in the ONE handle's edit.build: edit_on — the
-    // edit stage runs; min_p — the sampler's threshold (0: off).  Both off: the request is what it was
+    // edit stage runs (min-p is the sampler's: in sp).  Off: the request is what it was
     bool edit_on = false;
-    float min_p = 0.0f;
-    GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, const zg_sample_options* opt_or_null = nullptr, uint64_t seed = 0,
-               size_t past = 0)
-        : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past), mode(opt_or_null ? PLAIN : GREEDY),
-          opt(opt_or_null ? *opt_or_null : zg_sample_options{1.0f, 0, 1.0f}), seed(seed) {}
+    GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, size_t past = 0)
+        : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past) {}
 };
 
 // Steps the host may be ahead of the stop stage's progress word before it feeds the next piece, where the caller names none:
@@ -257,10 +293,10 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
         g->gen.lookahead = r.stop.lookahead ? std::min(r.stop.lookahead, C) : kStopLookahead;  // (beyond the context: never waits)
     }
     if (r.mode != GREEDY) {
-        g->gen.tail.sampler = fill_sample_params(g->samp.h_params, V, r.opt, r.seed, r.min_p);
-        ZG_HIP(hipMemcpyAsync(g->samp.params, g->samp.h_params, sizeof(SampleParams), hipMemcpyHostToDevice, s));
+        memcpy(g->samp.h_params, r.sp, B * sizeof(SampleParams));
+        ZG_HIP(hipMemcpyAsync(g->samp.params, g->samp.h_params, B * sizeof(SampleParams), hipMemcpyHostToDevice, s));
     }
-    if (pen_on) ZG_TRY(stage_penalties(g, r.pen, past, r.prior, r.prior_stride, r.prior_lens, s));
+    if (pen_on) ZG_TRY(stage_penalties(g, r.pp, r.prior, r.prior_stride, r.prior_lens, s));
     if (edit_on) ZG_TRY(stage_edits(g, s));
     g->lp.valid = false;
     if (r.lp_on) {
@@ -442,29 +478,35 @@ static int gen_run(zg_gpt* const* handles, size_t n_handles, GenRequest req) {
 // penalties and the sampler (StepTail.edit; min-p is the sampler's: SampleParams.min_p_off, alone MINP_ONLY).  A
 // stage whose argument is null or all off leaves the request what it was without it.  Penalties, conditions and edits go to ONE
 // handle, the first (zg_gpt_generate_enqueue_many has none of them).
-static int generate_request(zg_gpt* const* handles, size_t n_handles, const zg_generate_request& q, const char* who) {
+// each (zg_gpt_generate_each_enqueue): the table of the call, one zg_row_sampling per row of the handle, in the place of q.options /
+// q.penalties / q.edits->min_p / q.seed; null: the uniform request, whose table is `batch` equal rows.
+static int generate_request(zg_gpt* const* handles, size_t n_handles, const zg_generate_request& q, const char* who, const zg_row_sampling* each = nullptr,
+                            size_t n_each = 0) {
     ZG_TRY(require_init());
     zg_gpt* const g = handles[0];
     ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null argument", who);
+    if (each || n_each) {
+        ZG_REQUIRE(!q.options && !q.penalties, ZG_ERR_ARG, "%s: options / penalties beside rows (they are the rows')", who);
+        ZG_TRY(check_each_args(g, each, n_each, q.edits, who));
+    }
     if (q.options) ZG_TRY(check_sample_options(q.options, who));
     ZG_REQUIRE(q.options || !q.penalties, ZG_ERR_ARG, "%s: penalties without sampler options (greedy picking with penalties is top_k = 1)", who);
-    GenRequest r(q.prompts, q.prompt_stride, q.prompt_lens, q.n_steps, q.options, q.seed, q.past_len);
+    GenRequest r(q.prompts, q.prompt_stride, q.prompt_lens, q.n_steps, q.past_len);
     if (q.logprobs) {
         r.lp_on = true;
         r.top_n = q.top_n;
     }
-    if (q.penalties) {
-        ZG_TRY(check_penalties(q.penalties, who));
-        if (!penalties_off(*q.penalties)) {
-            r.pen_on = true;
-            r.pen = *q.penalties;
-            r.prior = q.prior;
-            r.prior_stride = q.prior_stride;
-            r.prior_lens = q.prior_lens;
-        } else {  // all off: the request stays what it was without them, but the lists are still the caller's to get right
-            ZG_TRY(check_pen_handle(g, who));
-            ZG_TRY(check_history(g, q.prior, q.prior_stride, q.prior_lens, 0, who));
-        }
+    if (q.penalties) ZG_TRY(check_penalties(q.penalties, who));
+    StepTail plan;
+    if (each) ZG_TRY(plan_rows(each, n_each, g->cfg.vocab_size, q.past_len, who, r.sp, r.pp, nullptr, &plan));
+    if (each ? plan.pen : (q.penalties && !penalties_off(*q.penalties))) {
+        r.pen_on = true;
+        r.prior = q.prior;
+        r.prior_stride = q.prior_stride;
+        r.prior_lens = q.prior_lens;
+    } else if (q.penalties) {  // all off: the request stays what it was without them, but the lists are still the caller's to get right
+        ZG_TRY(check_pen_handle(g, who));
+        ZG_TRY(check_history(g, q.prior, q.prior_stride, q.prior_lens, 0, who));
     }
     if (q.stop && (q.stop->n_ids || q.stop->n_seqs)) {
         ZG_REQUIRE(g->batch <= (size_t)kStopMaxRows, ZG_ERR_UNSUPPORTED, "%s: batch %zu above %d", who, g->batch, kStopMaxRows);
@@ -474,9 +516,14 @@ static int generate_request(zg_gpt* const* handles, size_t n_handles, const zg_g
     }
     if (q.edits) {
         ZG_TRY(build_edits(q.edits, g->cfg.vocab_size, who, g->edit.build.data(), &r.edit_on));
-        ZG_REQUIRE(q.options || edits_off(*q.edits), ZG_ERR_ARG, "%s: edits without sampler options (greedy picking with edits is top_k = 1)", who);
-        r.min_p = q.edits->min_p;
+        ZG_REQUIRE(q.options || each || edits_off(*q.edits), ZG_ERR_ARG, "%s: edits without sampler options (greedy picking with edits is top_k = 1)", who);
     }
+    if (q.options) {  // the uniform table: what plan_rows makes of `batch` equal rows (checked above: it cannot refuse them)
+        zg_row_sampling rows[kRowsMax];
+        uniform_rows(rows, g->batch, *q.options, q.edits ? q.edits->min_p : 0.0f, q.penalties, q.seed);
+        ZG_TRY(plan_rows(rows, g->batch, g->cfg.vocab_size, q.past_len, who, r.sp, r.pp, nullptr, &plan));
+    }
+    if (q.options || each) r.mode = plan.sampler;
     return gen_run(handles, n_handles, r);
 }
 
@@ -564,6 +611,12 @@ int zg_gpt_generate_stop_enqueue(zg_gpt* g, size_t past_len, const size_t* promp
 int zg_gpt_generate_request_enqueue(zg_gpt* g, const zg_generate_request* r) {
     ZG_REQUIRE(r != nullptr && r->size == sizeof(zg_generate_request), ZG_ERR_ARG, "generate_request: null request, or its size field is not sizeof(zg_generate_request)");
     return generate_request(&g, 1, *r, "generate_request");
+}
+
+int zg_gpt_generate_each_enqueue(zg_gpt* g, const zg_generate_request* r, const zg_row_sampling* rows, size_t n_rows) {
+    ZG_REQUIRE(r != nullptr && r->size == sizeof(zg_generate_request), ZG_ERR_ARG, "generate_each: null request, or its size field is not sizeof(zg_generate_request)");
+    ZG_REQUIRE(rows != nullptr, ZG_ERR_ARG, "generate_each: rows is null");
+    return generate_request(&g, 1, *r, "generate_each", rows, n_rows);
 }
 
 int zg_gpt_generate_stop_result(zg_gpt* g, size_t* end_out, size_t* finish_cols_out, int* reasons_out) {

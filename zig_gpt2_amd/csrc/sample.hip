@@ -174,18 +174,25 @@ __global__ __launch_bounds__(512) void embed_step_kernel(StepCtrl* ctrl, const f
 // NaN probabilities (no interval holds the point) give the last index.  vocab <= 64 x 4096.
 constexpr int kSegMax = 4096;  // segment sums per row; [kSegMax] = the row maximum / temp, [kSegMax + 1] = the total
 
+// The parameters are one entry per row (params[b]; a uniform call stages equal entries), and a row's FORM is its own: PLAIN when
+// its entry switches on neither filter nor min-p.  A plain row keeps the plain kernels' arithmetic — plain_weight below, the row
+// maximum scaled by 1 / temp in [kSegMax], no threshold — also inside a chain launched for a neighbour's filters: the branch is
+// uniform over the workgroup, which serves one row.
+__device__ __forceinline__ bool row_is_plain(const SampleParams& p) { return p.top_k == 0u && !(p.top_p < 1.0f) && !(p.min_p_off > -INFINITY); }
+__device__ __forceinline__ float plain_weight(float x, float inv_temp, float mx) { return __expf(x * inv_temp - mx); }
+
 __global__ __launch_bounds__(256) void sample_seg_kernel(const float* __restrict__ logits, int vocab, const SampleParams* params, float inv_temp_arg,
                                                          const float* __restrict__ part_val, int n_part, int part_stride, float* __restrict__ seg_out) {
     __shared__ float s_red[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
-    const float inv_temp = params ? params->inv_temp : inv_temp_arg;
+    const float inv_temp = params ? params[b].inv_temp : inv_temp_arg;
     const float* x = logits + (size_t)b * vocab;
     float* so = seg_out + (size_t)b * (kSegMax + 2);
     const float mx = row_max_from_partials(part_val + (size_t)b * part_stride, n_part, s_red) * inv_temp;
     const int nseg = (vocab + 63) >> 6;
     for (int sg = blockIdx.x * 4 + wave; sg < nseg; sg += gridDim.x * 4) {
         const int i = sg * 64 + lane;
-        const float e = i < vocab ? __expf(x[i] * inv_temp - mx) : 0.0f;
+        const float e = i < vocab ? plain_weight(x[i], inv_temp, mx) : 0.0f;
         const float t = wave_allsum(e);
         if (lane == 0) so[sg] = t;
     }
@@ -193,18 +200,20 @@ __global__ __launch_bounds__(256) void sample_seg_kernel(const float* __restrict
 }
 
 // FILT (top-k / top-p, sample_filter.h): elements under the row's threshold tau[b] weigh nothing, and where rounding leaves
-// the point past every interval the pick falls on the last KEPT element (never on a dropped one)
+// the point past every interval the pick falls on the last KEPT element (never on a dropped one).  A plain row of a FILT launch
+// (row_is_plain) runs the text of the plain instance: `filt` is FILT narrowed by the row's own form.
 template <bool FILT>
 __global__ __launch_bounds__(64) void sample_pick_kernel(const float* __restrict__ logits, int vocab, const SampleParams* params, float inv_temp_arg,
                                                          const float* __restrict__ u_arr, const StepCtrl* ctrl, float* __restrict__ seg_io,
                                                          int* __restrict__ token_out, const float* __restrict__ tau_arr) {
     const int lane = threadIdx.x, b = blockIdx.x;
-    const float tau = FILT ? tau_arr[b] : 0.0f;
-    const float inv_temp = params ? params->inv_temp : inv_temp_arg;
+    const bool filt = FILT && !row_is_plain(params[b]);
+    const float tau = filt ? tau_arr[b] : 0.0f;
+    const float inv_temp = params ? params[b].inv_temp : inv_temp_arg;
     const float* x = logits + (size_t)b * vocab;
     float* so = seg_io + (size_t)b * (kSegMax + 2);
     // no uniforms given: the counter PRNG of (seed, sequence length of the step whose logits these are, sequence)
-    const float u = u_arr ? u_arr[b] : counter_uniform(params->seed, (unsigned long long)ctrl->seq_len, (unsigned long long)b);
+    const float u = u_arr ? u_arr[b] : counter_uniform(params[b].seed, (unsigned long long)ctrl->seq_len, (unsigned long long)b);
     const int nseg = (vocab + 63) >> 6;
     const int run = (nseg + 63) >> 6, s0 = lane * run, s1 = min(s0 + run, nseg);
     const float mx = so[kSegMax];
@@ -240,8 +249,8 @@ __global__ __launch_bounds__(64) void sample_pick_kernel(const float* __restrict
         before = __shfl(before, owner, 64);
         const int i = sg * 64 + lane;
         const float xi = i < vocab ? x[i] : 0.0f;
-        const bool kept = i < vocab && (!FILT || xi >= tau);
-        float c = kept ? __expf(FILT ? (xi - mx) * inv_temp : xi * inv_temp - mx) : 0.0f;
+        const bool kept = i < vocab && (!filt || xi >= tau);
+        float c = kept ? (filt ? __expf((xi - mx) * inv_temp) : plain_weight(xi, inv_temp, mx)) : 0.0f;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
             const float up = __shfl_up(c, off, 64);
@@ -250,13 +259,13 @@ __global__ __launch_bounds__(64) void sample_pick_kernel(const float* __restrict
         const unsigned long long in = __builtin_amdgcn_ballot_w64(kept && point < before + c);
         // (rounding between the segment sum and its lane-by-lane scan can leave the point just past the last lane: that lane then)
         pick = sg * 64 + (in != 0ull ? __builtin_ctzll(in) : min(63, vocab - 1 - sg * 64));
-        if (FILT && in == 0ull) {
+        if (filt && in == 0ull) {
             const unsigned long long kb = __builtin_amdgcn_ballot_w64(kept);
             if (kb != 0ull) pick = sg * 64 + 63 - __builtin_clzll(kb);
             else hit = 0ull;  // (the walk ended on a segment that keeps nothing: as below)
         }
     }
-    if (FILT && hit == 0ull) {  // the point at or past the total (u x total rounded up): the last kept element of the last segment that weighs anything
+    if (filt && hit == 0ull) {  // the point at or past the total (u x total rounded up): the last kept element of the last segment that weighs anything
         int ls = -1;
         for (int k = s0; k < s1; ++k)
             if (so[k] > 0.0f) ls = k;
@@ -274,12 +283,14 @@ __global__ __launch_bounds__(64) void sample_pick_kernel(const float* __restrict
     }
 }
 
-__global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vocab, float inv_temp, const float* __restrict__ seg_io) {
+__global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vocab, const SampleParams* params, float inv_temp_arg,
+                                                           const float* __restrict__ seg_io) {
     const int b = blockIdx.y;
+    const float inv_temp = params ? params[b].inv_temp : inv_temp_arg;
     float* x = logits + (size_t)b * vocab;
     const float* so = seg_io + (size_t)b * (kSegMax + 2);
     const float mx = so[kSegMax], inv = 1.0f / so[kSegMax + 1];
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) x[i] = __expf(x[i] * inv_temp - mx) * inv;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) x[i] = plain_weight(x[i], inv_temp, mx) * inv;
 }
 
 #include "sample_filter.h"
@@ -308,7 +319,7 @@ int sample_launches(float* logits, int batch, int vocab, const SampleParams* par
                        (const float*)nullptr);
     ZG_HIP(hipGetLastError());
     if (write_probs) {
-        hipLaunchKernelGGL(sample_probs_kernel, dim3(std::min(256, (vocab + 255) / 256), batch), dim3(256), 0, s, logits, vocab, inv_temp, seg_ws);
+        hipLaunchKernelGGL(sample_probs_kernel, dim3(std::min(256, (vocab + 255) / 256), batch), dim3(256), 0, s, logits, vocab, params, inv_temp, seg_ws);
         ZG_HIP(hipGetLastError());
     }
     return ZG_OK;
@@ -325,9 +336,10 @@ int launch_embed_step(const EmbedArgs& a, hipStream_t s) {
     return ZG_OK;
 }
 
-int launch_sample(float* logits, int batch, int vocab, float temp, const float* u, const float* part_val, int n_part, int part_stride, float* seg_ws,
-                  int* token_out, bool write_probs, hipStream_t s) {
-    return sample_launches(logits, batch, vocab, nullptr, 1.0f / temp, u, nullptr, part_val, n_part, part_stride, seg_ws, token_out, write_probs, s);
+int launch_sample(float* logits, int batch, int vocab, const SampleParams* params, float temp, const float* u, const float* part_val, int n_part,
+                  int part_stride, float* seg_ws, int* token_out, bool write_probs, hipStream_t s) {
+    ZG_REQUIRE(u != nullptr, ZG_ERR_ARG, "sampler: a per-call launch without its uniforms");
+    return sample_launches(logits, batch, vocab, params, params ? 0.0f : 1.0f / temp, u, nullptr, part_val, n_part, part_stride, seg_ws, token_out, write_probs, s);
 }
 
 int launch_sample_step(float* logits, int batch, int vocab, const SampleParams* params, const StepCtrl* ctrl, const float* part_val, int n_part,

@@ -25,6 +25,11 @@
 // min-p (include/zgpt2.h zg_logit_edits): tau_m = row maximum + SampleParams.min_p_off joins the threshold where sample_seg_filt_kernel
 // completes it — kept = { x >= max(tau_k, tau_p, tau_m) } —, and alone (both filters off) it is a chain of zero levels: no selection
 // launch, sample_seg_filt_kernel with tau = tau_m and the threshold-aware pick / probability kernels behind it.
+// Per-row parameters: n_levels is the chain's, the descents are the row's own (filt_kind: K then nothing, nothing
+// then P, K then P, or none).  Where a row has no descent it still zeroes its share of the histogram in turn — so the rotation
+// above holds for every row whatever its neighbours run — and hands its state on unchanged; a top-k-only row of a six-level chain
+// keeps tau_k's key as its prefix (no nucleus descent at top_p 1, which could cut elements whose fixed-point mass rounds to 0), a
+// row with neither filter ends with tau = -inf before min-p, and a plain row takes the plain kernels' arithmetic (sample.hip).
 
 constexpr int kFiltBins = 2048;
 constexpr float kFiltScale = 4294967296.0f;  // fixed-point masses: e in [0, 1] x 2^32; a row of 2^18 elements sums below 2^51 (exact in a double)
@@ -58,9 +63,13 @@ __device__ __forceinline__ float filter_unkey(unsigned k) { return __uint_as_flo
 
 __device__ __forceinline__ int filt_shift(int lv) { return lv == 0 ? 21 : lv == 1 ? 10 : 0; }
 __device__ __forceinline__ int filt_bins(int lv) { return lv == 2 ? 1024 : 2048; }
-// kind of descent d (0 / 1) of a chain of n_levels launches: one filter = 3 (top-k if it is on, else the nucleus), both = 6
+// kind of descent d (0 / 1) of ONE ROW in a chain of n_levels launches: three launches hold the row's one filter (top-k if it is
+// on, else the nucleus), six hold top-k in the first three and the nucleus in the last three — each only where the row has it
 enum { FILT_SKIP = 0, FILT_K = 1, FILT_P = 2 };
-__device__ __forceinline__ int filt_kind(int n_levels, int d, bool k_on) { return n_levels == 3 ? (k_on ? FILT_K : FILT_P) : d == 0 ? (k_on ? FILT_K : FILT_SKIP) : FILT_P; }
+__device__ __forceinline__ int filt_kind(int n_levels, int d, bool k_on, bool p_on) {
+    if (n_levels == 3) return k_on ? FILT_K : p_on ? FILT_P : FILT_SKIP;
+    return d == 0 ? (k_on ? FILT_K : FILT_SKIP) : (p_on ? FILT_P : FILT_SKIP);
+}
 
 __device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, int off) {
     const unsigned lo = __shfl_up((unsigned)v, off, 64), hi = __shfl_up((unsigned)(v >> 32), off, 64);
@@ -172,12 +181,12 @@ __device__ __forceinline__ void filter_zero(const FilterRow& r, int which) {
 }
 
 // the search a launch at position pos (> 1) owes its predecessor; leaves the state as the build of position pos wants it
-__device__ void filter_advance(const FilterRow& r, int pos, int n_levels, bool k_on, float top_p, FilterState& st) {
+__device__ void filter_advance(const FilterRow& r, int pos, int n_levels, bool k_on, bool p_on, float top_p, FilterState& st) {
     st = r.st[(pos - 1) & 1];
-    const int dp = (pos - 2) / 3, lp = (pos - 2) % 3, kind = filt_kind(n_levels, dp, k_on);
+    const int dp = (pos - 2) / 3, lp = (pos - 2) % 3, kind = filt_kind(n_levels, dp, k_on, p_on);
     const int h = (pos - 1) % 3;
     if (kind != FILT_SKIP) filter_search(r.cnt + h * kFiltBins, r.mass + h * kFiltBins, lp, kind == FILT_P, kind == FILT_P && lp == 0, top_p, st);
-    if (lp == 2 && dp == 0 && n_levels == 6) {  // tau_k is known: the nucleus descent starts over, above it
+    if (lp == 2 && dp == 0 && n_levels == 6 && p_on) {  // tau_k is known: the nucleus descent starts over, above it (a row without one keeps tau_k's key)
         st.lo_key = kind == FILT_SKIP ? 0u : st.prefix;
         st.prefix = 0u;
         st.mass_above = 0ull;
@@ -192,14 +201,14 @@ __global__ __launch_bounds__(256) void filter_level_kernel(const float* __restri
     __shared__ float s_red[4];
     const int tid = threadIdx.x, b = blockIdx.y;
     const FilterRow r = filter_row(ws, b);
-    const float inv_temp = params->inv_temp, top_p = params->top_p;
-    const unsigned top_k = params->top_k;
-    const bool k_on = top_k != 0u && top_k < (unsigned)vocab;
+    const float inv_temp = params[b].inv_temp, top_p = params[b].top_p;
+    const unsigned top_k = params[b].top_k;
+    const bool k_on = top_k != 0u && top_k < (unsigned)vocab, p_on = top_p < 1.0f;
     filter_zero(r, (pos + 1) % 3);
     FilterState st{0u, top_k, 0u, 0u, 0ull, 0ull};
-    if (pos > 1) filter_advance(r, pos, n_levels, k_on, top_p, st);
+    if (pos > 1) filter_advance(r, pos, n_levels, k_on, p_on, top_p, st);
     if (blockIdx.x == 0 && tid == 0) r.st[pos & 1] = st;
-    const int d = (pos - 1) / 3, lv = (pos - 1) % 3, kind = filt_kind(n_levels, d, k_on);
+    const int d = (pos - 1) / 3, lv = (pos - 1) % 3, kind = filt_kind(n_levels, d, k_on, p_on);
     if (kind == FILT_SKIP) return;
     const int nb = filt_bins(lv), sh = filt_shift(lv);
     for (int i = tid; i < nb; i += 256) {
@@ -237,24 +246,38 @@ __global__ __launch_bounds__(256) void sample_seg_filt_kernel(const float* __res
     __shared__ float s_red[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
     const FilterRow r = filter_row(ws, b);
-    const float inv_temp = params->inv_temp;
-    const unsigned top_k = params->top_k;
+    const float inv_temp = params[b].inv_temp, top_p = params[b].top_p;
+    const unsigned top_k = params[b].top_k;
+    const bool k_on = top_k != 0u && top_k < (unsigned)vocab, p_on = top_p < 1.0f;
+    const bool plain = row_is_plain(params[b]);
     const int pos = n_levels + 1;
     float tau = -INFINITY;
     if (n_levels != 0) {  // (0: min-p alone — no chain ran, the workspace is not touched)
         filter_zero(r, (pos + 1) % 3);
         FilterState st;
-        filter_advance(r, pos, n_levels, top_k != 0u && top_k < (unsigned)vocab, params->top_p, st);
-        tau = filter_unkey(st.prefix);
+        filter_advance(r, pos, n_levels, k_on, p_on, top_p, st);
+        if (k_on || p_on) tau = filter_unkey(st.prefix);  // (a row without a filter: the chain was its neighbours')
     }
     const float* x = logits + (size_t)b * vocab;
     float* so = seg_out + (size_t)b * (kSegMax + 2);
     const float mx = row_max_from_partials(part_val + (size_t)b * part_stride, n_part, s_red);  // [kSegMax] holds the row maximum itself here
+    const int nseg = (vocab + 63) >> 6;
+    if (plain) {  // sample_seg_kernel's text: the maximum scaled by 1 / temp, nothing cut
+        const float mxs = mx * inv_temp;
+        if (blockIdx.x == 0 && tid == 0) ws.tau[b] = -INFINITY;
+        for (int sg = blockIdx.x * 4 + wave; sg < nseg; sg += gridDim.x * 4) {
+            const int i = sg * 64 + lane;
+            const float e = i < vocab ? plain_weight(x[i], inv_temp, mxs) : 0.0f;
+            const float t = wave_allsum(e);
+            if (lane == 0) so[sg] = t;
+        }
+        if (blockIdx.x == 0 && tid == 0) so[kSegMax] = mxs;
+        return;
+    }
     // min-p (applied last, as HF does): tau_m = max + temp x log(min_p), one fp32 add; off (-inf): tau keeps its own bits, a NaN's too
-    const float d = params->min_p_off;
+    const float d = params[b].min_p_off;
     if (d > -INFINITY) tau = fmaxf(tau, mx + d);
     if (blockIdx.x == 0 && tid == 0) ws.tau[b] = tau;
-    const int nseg = (vocab + 63) >> 6;
     for (int sg = blockIdx.x * 4 + wave; sg < nseg; sg += gridDim.x * 4) {
         const int i = sg * 64 + lane;
         const float v = i < vocab ? x[i] : 0.0f;
@@ -271,7 +294,11 @@ __global__ __launch_bounds__(256) void sample_probs_filt_kernel(float* logits, i
     const int b = blockIdx.y;
     float* x = logits + (size_t)b * vocab;
     const float* so = seg_io + (size_t)b * (kSegMax + 2);
-    const float mx = so[kSegMax], inv = 1.0f / so[kSegMax + 1], inv_temp = params->inv_temp, tau = tau_arr[b];
+    const float mx = so[kSegMax], inv = 1.0f / so[kSegMax + 1], inv_temp = params[b].inv_temp, tau = tau_arr[b];
+    if (row_is_plain(params[b])) {  // sample_probs_kernel's text ([kSegMax] holds the scaled maximum for such a row)
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) x[i] = plain_weight(x[i], inv_temp, mx) * inv;
+        return;
+    }
     for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) {
         const float v = x[i];
         x[i] = v >= tau ? __expf((v - mx) * inv_temp) * inv : 0.0f;

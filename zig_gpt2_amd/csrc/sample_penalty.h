@@ -13,6 +13,8 @@
 //                            penalised row, n_part slices per row (slice j = the indices j * 256 + t (mod n_part * 256)).
 // A token >= vocab is skipped (a corrupted record never becomes an address); lengths read from device memory are clamped to the
 // strides and to max_hist, so the table always has a free slot.  The filter workspace is not touched.
+// The values are the row's own (params[b]): a row whose penalties are off is counted like any other and never written
+// back — it keeps its bits, a NaN's payload and a -0.0 included, beside neighbours that are penalised.
 
 constexpr unsigned kPenEmpty = 0xffffffffu;
 
@@ -38,7 +40,7 @@ __global__ __launch_bounds__(256) void penalty_apply_kernel(float* __restrict__ 
     const int n_prior = h.prior ? min(max(h.prior_len[b], 0), min(h.prior_stride, cap)) : 0;
     int past = 0, n_rec = 0;
     if (h.ctrl && h.rec) {  // the loop's record of this row: positions past .. step - 2 (the step in flight is step - 1)
-        past = min(max(params->past_len, 0), h.rec_stride);
+        past = min(max(params[b].past_len, 0), h.rec_stride);
         n_rec = min(max(h.ctrl->step - 1 - past, 0), min(h.rec_stride - past, cap - n_prior));
     }
     __syncthreads();
@@ -57,13 +59,14 @@ __global__ __launch_bounds__(256) void penalty_apply_kernel(float* __restrict__ 
         }
     }
     __syncthreads();
-    const float r = params->repetition, presence = params->presence, frequency = params->frequency;
+    const float r = params[b].repetition, presence = params[b].presence, frequency = params[b].frequency;
+    const bool off = r == 1.0f && presence == 0.0f && frequency == 0.0f;  // (uniform over the workgroup)
     float* x = logits + (size_t)b * vocab;
     for (int i = tid; i < slots; i += 256) {
         const unsigned tok = keys[i];
         if (tok >= (unsigned)vocab) continue;  // empty
         const unsigned c = cnt[i];
-        x[tok] = penalized_logit(x[tok], r, presence, frequency, c);
+        if (!off) x[tok] = penalized_logit(x[tok], r, presence, frequency, c);
         if (counts_out) counts_out[(size_t)b * vocab + tok] = c;
     }
 }

@@ -44,7 +44,7 @@ struct SamplerChain {
     float* part_val;  // row-maximum partials [batch][n_part] as lm_head's epilogue leaves them, and their indices
     int* part_idx;
     int n_part;
-    const PenParams* pen;
+    const PenParams* pen;  // [batch]: one entry per row, as params below (a uniform call stages equal entries)
     PenHistory hist;
     unsigned* counts;  // (zg_debug_penalize_rows: the counts of every row's history)
     const EditTable* edit_tab;
@@ -54,7 +54,8 @@ struct SamplerChain {
     FilterWs filt;
     const StepCtrl* ctrl;  // the loop's draws ...
     const float* u;        // ... or a call's
-    float temp;
+    float temp;            // a per-call plain sampler with per_row false takes it by value and reads no params
+    bool per_row;          // ... with per_row true it reads params[b] like every other sampler
     bool write_probs;
     int* pick;
 };
@@ -68,6 +69,9 @@ bool penalties_off(const zg_logit_penalties& p);
 bool edits_off(const zg_logit_edits& e);
 int build_edits(const zg_logit_edits* e, size_t vocab, const char* who, char* block, bool* stage_on);
 SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed, float min_p);
+int plan_rows(const zg_row_sampling* rows, size_t n_rows, size_t vocab, size_t past_len, const char* who, SampleParams* sp, PenParams* pp, int* forms,
+              StepTail* tail);
+void uniform_rows(zg_row_sampling* rows, size_t n_rows, const zg_sample_options& o, float min_p, const zg_logit_penalties* pen_or_null, uint64_t seed);
 int check_penalties(const zg_logit_penalties* p, const char* who);
 int check_sample_options(const zg_sample_options* o, const char* who);
 int check_stop(const zg_stop_conditions* c, size_t vocab, const char* who);

@@ -1,5 +1,6 @@
 // sampler_chain.hip — the handle-free host side of the sampler: the sampler chain behind lm_head, emitted by emit_sampler_chain for
 // every user, and the checks and fills of what a sampler call is given (options, penalties, edits, stop conditions, top_n).
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -35,7 +36,7 @@ int emit_sampler_chain(const SamplerChain& c, StepTail t, hipStream_t s) {
         return launch_sample_filtered(c.logits, c.batch, c.vocab, c.params, filter_launches(t.sampler), c.u, c.ctrl, c.part_val, c.n_part, c.n_part, c.seg_ws,
                                       c.filt, c.pick, c.write_probs, s);
     if (c.ctrl) return launch_sample_step(c.logits, c.batch, c.vocab, c.params, c.ctrl, c.part_val, c.n_part, c.n_part, c.seg_ws, c.pick, s);
-    return launch_sample(c.logits, c.batch, c.vocab, c.temp, c.u, c.part_val, c.n_part, c.n_part, c.seg_ws, c.pick, c.write_probs, s);
+    return launch_sample(c.logits, c.batch, c.vocab, c.per_row ? c.params : nullptr, c.temp, c.u, c.part_val, c.n_part, c.n_part, c.seg_ws, c.pick, c.write_probs, s);
 }
 
 // How many alternatives a log-probability record may be asked for: the one check of every entry point that takes a top_n
@@ -114,6 +115,40 @@ SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_op
     return k_on && p_on ? TWO_FILTERS : (k_on || p_on) ? ONE_FILTER : min_p != 0.0f ? MINP_ONLY : PLAIN;
 }
 
+// A table of one zg_row_sampling per row, checked (the message names the row) and laid out as the kernels read it: sp[b] / pp[b],
+// the host images of SampleParams / PenParams (either may be null: nothing is filled there), forms[b] = the sampler form row b has
+// by its own parameters — exactly fill_sample_params' —, and *tail = what the chain is launched as, the union of the rows' needs:
+// the levels of the row that needs most, the threshold-aware tail if any row has a filter or min-p, the penalty stage if any row
+// is penalised.  The one place a row's parameters become a launch; every sampler call, uniform ones included, comes through here.
+int plan_rows(const zg_row_sampling* rows, size_t n_rows, size_t vocab, size_t past_len, const char* who, SampleParams* sp, PenParams* pp, int* forms,
+              StepTail* tail) {
+    ZG_REQUIRE(rows != nullptr && n_rows >= 1, ZG_ERR_ARG, "%s: rows is null or empty", who);
+    SamplerMode u = PLAIN;
+    bool pen = false;
+    for (size_t b = 0; b < n_rows; ++b) {
+        char row[96];
+        snprintf(row, sizeof row, "%s: row %zu", who, b);
+        const zg_row_sampling& r = rows[b];
+        ZG_TRY(check_sample_options(&r.options, row));
+        ZG_REQUIRE(r.min_p >= 0.0f && r.min_p < 1.0f, ZG_ERR_ARG, "%s: min_p %f outside [0, 1)", row, r.min_p);  // (a NaN fails it)
+        ZG_TRY(check_penalties(&r.penalties, row));
+        SampleParams one;
+        const SamplerMode m = fill_sample_params(sp ? &sp[b] : &one, vocab, r.options, r.seed, r.min_p);
+        if (pp) pp[b] = PenParams{r.penalties.repetition, r.penalties.presence, r.penalties.frequency, (int)past_len};
+        if (forms) forms[b] = (int)m;
+        // (PLAIN < MINP_ONLY < ONE_FILTER < TWO_FILTERS by what is launched: the tail kernels, then three levels, then six)
+        if (filter_launches(m) > filter_launches(u) || (u == PLAIN && m == MINP_ONLY)) u = m;
+        pen = pen || !penalties_off(r.penalties);
+    }
+    *tail = StepTail{u, pen};
+    return ZG_OK;
+}
+
+// the table of a uniform call: n_rows equal entries
+void uniform_rows(zg_row_sampling* rows, size_t n_rows, const zg_sample_options& o, float min_p, const zg_logit_penalties* pen_or_null, uint64_t seed) {
+    for (size_t b = 0; b < n_rows; ++b) rows[b] = zg_row_sampling{o, min_p, pen_or_null ? *pen_or_null : zg_logit_penalties{1.0f, 0.0f, 0.0f}, seed};
+}
+
 int check_penalties(const zg_logit_penalties* p, const char* who) {
     ZG_REQUIRE(p != nullptr, ZG_ERR_ARG, "%s: penalties is null", who);
     ZG_REQUIRE(p->repetition > 0.0f, ZG_ERR_ARG, "%s: repetition penalty %f (must be > 0)", who, p->repetition);  // (a NaN fails it)
@@ -161,6 +196,18 @@ void fill_stop(StopConds* d, const zg_stop_conditions& c) {
 }  // namespace zg
 
 extern "C" {
+
+// plan_rows' face (tests; no GPU, no zg_init): out[0] the sampler form the chain is launched in, out[1] whether the penalty stage
+// runs, out[2 + b] the form of row b
+int zg_debug_each_plan(const zg_row_sampling* rows, size_t n_rows, size_t vocab, int* out, size_t n_out) {
+    ZG_REQUIRE(out != nullptr && vocab >= 1 && n_rows <= 64 && n_out >= 2 + n_rows, ZG_ERR_ARG, "debug_each_plan: %zu rows, vocab %zu, %zu outputs", n_rows, vocab,
+               n_out);
+    StepTail t;
+    ZG_TRY(plan_rows(rows, n_rows, vocab, 0, "debug_each_plan", nullptr, nullptr, out + 2, &t));
+    out[0] = (int)t.sampler;
+    out[1] = t.pen ? 1 : 0;
+    return ZG_OK;
+}
 
 int zg_debug_min_p_offset(float temp, float min_p, float* d_out) {
     ZG_REQUIRE(d_out != nullptr && temp > 0.0f && min_p >= 0.0f && min_p < 1.0f, ZG_ERR_ARG, "debug_min_p_offset: temp %f, min_p %f", temp, min_p);

@@ -374,9 +374,11 @@ int launch_attn_prefill(const float* qkv, bf16_t* out, int B, int pos0, int P, i
 // ------------------------------------------------------------------------------------ step head and sampler stages (sample.hip)
 // GPT.sample tail: in-place softmax(logits / temp) per sequence + inverse-CDF draw with uniform u[b].
 // part_val / n_part / part_stride: the per-workgroup maxima lm_head's argmax epilogue left (the row maximum without a pass over the
-// logits); seg_ws: sample_workspace_floats(batch) floats; write_probs: leave softmax(logits / temp) in the logits rows
-int launch_sample(float* logits, int batch, int vocab, float temp, const float* u, const float* part_val, int n_part, int part_stride, float* seg_ws,
-                  int* token_out, bool write_probs, hipStream_t s);
+// logits); seg_ws: sample_workspace_floats(batch) floats; write_probs: leave softmax(logits / temp) in the logits rows.
+// params null: `temp` for every row, by value (nothing is staged for a uniform call); else params[b].inv_temp of device memory
+struct SampleParams;
+int launch_sample(float* logits, int batch, int vocab, const SampleParams* params, float temp, const float* u, const float* part_val, int n_part,
+                  int part_stride, float* seg_ws, int* token_out, bool write_probs, hipStream_t s);
 size_t sample_workspace_floats(int batch);
 
 // Decode-step head kernel: token selection (+ argmax finalisation of the previous step) and
@@ -414,7 +416,9 @@ struct EmbedArgs {
 int launch_embed_step(const EmbedArgs& a, hipStream_t s);
 // GPT.sample's tail (src/main.zig:200-206) inside the generate loop: temperature and seed live in device memory (one captured
 // graph serves every call), the uniform of (sequence b, position T) is the library's counter PRNG of (seed, T, b) — what
-// zg_gpt_sample uses when it is given no uniforms
+// zg_gpt_sample uses when it is given no uniforms.  Every launcher below takes an ARRAY of one entry per row, params[b] (DESIGN
+// §3.11): a uniform call stages `batch` equal entries; the form of row b — plain, one descent, two, min-p alone — is read off its
+// own entry on the device, whatever chain the launch belongs to.
 struct SampleParams {
     float inv_temp;
     unsigned top_k;  // 0: off (the truncated sampler only; read on the device, so one captured graph serves every value)
@@ -425,8 +429,9 @@ struct SampleParams {
 int launch_sample_step(float* logits, int batch, int vocab, const SampleParams* params, const StepCtrl* ctrl, const float* part_val, int n_part,
                        int part_stride, float* seg_ws, int* token_out, hipStream_t s);
 // The sampler behind top-k / top-p truncation (sample_filter.h: an exact radix select of the threshold, one launch per 11-bit
-// level, then the segment sums / pick / probabilities with weight 0 under the threshold).  n_levels: 3 = ONE filter is on (top-k
-// if params->top_k is, else the nucleus), 6 = both (top-k, then the nucleus over what it kept) — the launches are the same for
+// level, then the segment sums / pick / probabilities with weight 0 under the threshold).  n_levels is the CHAIN's, the largest any
+// row needs: 3 = ONE filter is on (top-k if params[b].top_k is, else the nucleus), 6 = both (top-k, then the nucleus over what it
+// kept); a row that needs fewer passes its state through the launches it has no descent in — the launches are the same for
 // every option value, so a captured chain serves them all; 0 = min-p alone: no selection launch, the threshold-aware tail kernels
 // with tau = row maximum + params->min_p_off (with 3 or 6 the same threshold is folded into max(tau_k, tau_p)).  params lives in device memory; u (device, [batch]) or, when null, the
 // counter PRNG of (params->seed, ctrl->seq_len, b).  fws: filter_workspace_bytes(batch) bytes whose first
@@ -453,6 +458,7 @@ int launch_row_max_partials(const float* logits, int batch, int vocab, float* pa
 // rec[b][params->past_len .. ctrl->step - 2] — the tokens recorded when the step in flight (ctrl->step - 1) is sampled.  All of it is
 // read on the device, so one captured launch serves every position and every value.  max_hist: the longest history a row may have
 // (<= kPenMaxHistory: the table of 2 max_hist slots lives in the LDS); anything longer is cut, a token >= vocab is skipped.
+// params is an array of one entry per row; a row whose entry is {1, 0, 0} is counted but not rewritten (it keeps its bits).
 struct PenParams {
     float repetition, presence, frequency;
     int past_len;  // first recorded position that belongs to the history (generate loop)

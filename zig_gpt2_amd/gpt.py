@@ -469,6 +469,46 @@ class GPT:
         edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
         self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=False, edits=edits)
 
+    # ------------------------------------------------------------------ per-row sampling parameters
+    def generate_each(self, prompts, n_steps, rows, past_len=0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0,
+                      logit_bias=None, allowed_token_ids=None, banned_token_ids=None):
+        """generate_sample / generate_from with the sampler parameters taken per row (zg_gpt_generate_each_enqueue): `rows` is one
+        dict per row with generate_sample's keyword names — temp, top_k, top_p, min_p, repetition_penalty, presence_penalty,
+        frequency_penalty — plus seed; a row's temp 0 / None is greedy (temp 1, top_k 1).  Row b gets, bit for bit, what
+        generate_sample with rows[b]'s values for every row gives row b.  prior, logprobs, the stop conditions and the three edit
+        lists are per call and work as there; returns what generate_from returns: columns past_len .. (end or past_len + n_steps) - 1."""
+        table = _lib.row_sampling(rows)
+        mat, lens, stride = self._prompts(prompts)
+        edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, 0.0)
+        have_stop = stop_token_ids is not None or stop is not None
+        conds, keep_conds = _lib.stop_conditions(stop_token_ids, stop, lookahead) if have_stop else (None, ())
+        pp, pstride, plens, keep = self._token_lists(prior)
+        r = _lib.generate_request(past_len=past_len, prompts=ptr(mat), prompt_stride=stride, prompt_lens=ptr(lens), n_steps=n_steps, prior=pp,
+                                  prior_stride=pstride, prior_lens=plens, logprobs=int(logprobs is not None), top_n=int(logprobs or 0),
+                                  stop=None if conds is None else C.addressof(conds), edits=None if edits is None else C.addressof(edits[0]))
+        check(self._L.zg_gpt_generate_each_enqueue(self.h, C.addressof(r), C.addressof(table), len(rows)))
+        del keep, keep_conds
+        n = self.stop_result()[0] - past_len if conds is not None and (conds.n_ids or conds.n_seqs) else n_steps
+        out = self.generate_fetch_range(past_len, n)
+        return out if logprobs is None else (out,) + self.generate_fetch_logprobs(past_len, n, logprobs)
+
+    def sample_each(self, seq_len, tokens, rows, uniforms=None, history=None, want_probs=False, logit_bias=None, allowed_token_ids=None,
+                    banned_token_ids=None):
+        """`sample` with the sampler parameters taken per row (zg_gpt_sample_each; `rows` as generate_each).  uniforms None: the
+        draw of row b is the counter PRNG of (rows[b]'s seed, seq_len, b).  history: one token list per row, read when any row is
+        penalised.  Returns tokens [batch] (and probs)."""
+        table = _lib.row_sampling(rows)
+        tokens = np.ascontiguousarray(np.atleast_1d(tokens), dtype=np.uint64)
+        u = None if uniforms is None else np.ascontiguousarray(np.atleast_1d(uniforms), dtype=np.float32)
+        out = np.zeros(self.batch, np.uint64)
+        probs = np.empty((self.batch, self.config.vocab_size), np.float32) if want_probs else None
+        edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, 0.0)
+        hp, hstride, hlens, keep = self._token_lists(history)
+        check(self._L.zg_gpt_sample_each(self.h, seq_len, ptr(tokens), tokens.size, C.addressof(table), len(rows), hp, hstride, hlens,
+                                         None if edits is None else C.addressof(edits[0]), ptr(u), ptr(out), ptr(probs), ops._n(probs)))
+        del keep
+        return (out, probs) if want_probs else out
+
     PROFILE_CLASSES = ["embed", "ln1_c_attn_kv", "attention", "merge_attn_proj_resid", "ln2_c_fc_gelu",
                        "mlp_proj_resid", "lnf_lm_head_argmax", "step_total"]
 
