@@ -287,6 +287,13 @@ enum {
                                       alone, and the edit stage in front of all four sampler forms (plain, one filter, two filters,
                                       min-p alone), unpenalised; with ZG_GPT_LOGPROBS_ / _STOP_GENERATE beside it their twins too (the
                                       rule: ZG_GPT_SAMPLED_GENERATE; a penalised and edited generation captures its graphs when it begins) */
+    ZG_GPT_GUIDED_GENERATE = 1 << 15, /* guided decoding (zg_guide): carve, behind everything else in the arena, the
+                                      transition table (256 x vocab uint16), the keep bitmap of every state (256 x ceil(vocab / 32)
+                                      words), the row states and the state record — about 27 MB at GPT-2 124M — and capture the guided
+                                      twins of every sampler graph that create captures (the rule: ZG_GPT_SAMPLED_GENERATE; a greedy
+                                      graph has no guided twin).  Without it zg_gpt_guide_load, zg_gpt_generate_guided_enqueue and
+                                      zg_gpt_generate_fetch_guide_states are ZG_ERR_UNSUPPORTED and the handle has bit for bit the layout
+                                      and behaviour it has without this flag's existence */
     ZG_GPT_WEIGHTS_B24 = 1 << 8  /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
                                     value rounded to nearest even at 16 mantissa bits (never to inf), row r of an [out][in]
                                     matrix = [in bf16-shaped upper halves | in low bytes].  3/4 of fp32's weight bytes, 2^-17
@@ -813,6 +820,71 @@ int zg_debug_edit_rows(const float* logits, size_t batch, size_t vocab, const zg
                        float* probs_out_or_null, float* thresholds_out_or_null);
 /* d of min-p as the library computes it (temp > 0, min_p in [0, 1), else ZG_ERR_ARG).  Needs neither a GPU nor zg_init. */
 int zg_debug_min_p_offset(float temp, float min_p, float* d_out);
+/* ---- Guided decoding: a token-level automaton in the device loop — "one of these labels", "digits, then a newline",
+ * a regex or a JSON schema compiled to a finite-state machine over tokens (Outlines; vLLM guided_choice / guided_regex).  The static
+ * form is zg_logit_edits.allowed_ids: one keep set per call.  Here the keep set depends on where in the grammar a row stands.
+ * An automaton is n_states states (1 .. ZG_GUIDE_MAX_STATES) and a dense table next [n_states][vocab] of uint16_t:
+ * next[s][i] == ZG_GUIDE_DEAD: token i is not allowed in state s; any other value (< n_states) is the state behind picking i.  Every
+ * state allows at least one token — a finished row keeps decoding in lock step, and a row of -inf alone never reaches a kernel:
+ * "done" is a state that loops on the end token, and ending the generation stays the stop stage's business (stop token ids).  One
+ * table may hold several automata in disjoint state ranges: every row names its own start state, so per-row grammars are free.
+ * The stage.  state[b] is the row's state when a picked column p (p >= past_len + prompt_lens[b]) is drawn.  The guide comes last
+ * among the stages that rewrite the row — penalties, then edits, then the guide, then temperature / top-k / top-p / min-p:
+ *   y[i] = next[state[b]][i] != ZG_GUIDE_DEAD ? x[i] : -inf
+ * with x the row as the edit stage leaves it; a kept index is not written (its bits are untouched).  Everything behind the stage
+ * sees y: the sampler, zg_gpt_argmax, the log-probability record and the stop stage.  Behind the pick tok of that column,
+ * state[b] = next[state[b]][tok].  Prompt columns neither mask nor advance.  A row whose start state is ZG_GUIDE_NONE is unguided:
+ * the stage does not write it and it keeps its bits beside guided neighbours (its row-maximum partials may be rebuilt in another
+ * slicing, as for an unpenalised row of §3.11).  A pick whose transition is dead or out of range can only come from a row holding
+ * NaN; it leaves the state unchanged.  Nothing read from device memory becomes an address before it is clamped.
+ * The oracle: row b of a guided call returns, BIT FOR BIT — tokens, the log-probability record, finish columns and reasons — what
+ * the host loop over zg_gpt_sample_edit (per-row parameters: zg_gpt_sample_each) returns that passes allowed_ids = the call's
+ * allow-list intersected with { i : next[state][i] != ZG_GUIDE_DEAD } and walks the automaton itself; at batch > 1 that loop is run
+ * once per row on the same handle and that row compared (sequences never interact).
+ * Cost: with a guide the tail has one launch in the edit stage's place (or one more where the call has no edits) and one small
+ * launch behind the sampler; with edits AND a guide the row is still rewritten by ONE launch.  The table and the bitmaps live in
+ * device memory: one captured graph serves every grammar.  There is no per-token twin: a caller who draws token by token has
+ * allowed_ids and walks the automaton on the host. */
+#define ZG_GUIDE_MAX_STATES 256
+#define ZG_GUIDE_DEAD 0xFFFFu
+#define ZG_GUIDE_NONE ((size_t)-1)
+typedef struct {
+    size_t n_states;       /* 1 .. ZG_GUIDE_MAX_STATES */
+    const uint16_t* next;  /* [n_states][vocab_size], host memory */
+} zg_guide;
+/* Check a table, build the keep bitmap of every state on the host, upload both, and keep the host bitmaps for the checks of later
+ * calls.  Synchronous (it drains the handle's stream first): the one slow call, once per grammar and not per request.  NULL
+ * unloads.  ZG_ERR_ARG: n_states 0 or above ZG_GUIDE_MAX_STATES, NULL next, a transition >= n_states that is not ZG_GUIDE_DEAD, a
+ * state that allows nothing (the message names it) — the table the handle held stays loaded.  Needs ZG_GPT_GUIDED_GENERATE. */
+int zg_gpt_guide_load(zg_gpt* g, const zg_guide* guide_or_null);
+/* zg_gpt_generate_request_enqueue (rows_or_null NULL) or zg_gpt_generate_each_enqueue (rows given; n_rows == the handle's batch)
+ * with a guide: start_states [batch], the state each row is in when its first picked column is drawn, or ZG_GUIDE_NONE.  Every
+ * other argument follows those calls' rules; zg_generate_request is unchanged.  All start states ZG_GUIDE_NONE: exactly the unguided
+ * call — the same graphs, no added launch.  A second turn (past_len > 0) continues a row from next[state[p]][tok[p]] of its last
+ * picked column p: the caller computes it from zg_gpt_generate_fetch_guide_states and the tokens, and passes it as the start state.
+ * Refusals, all before anything is enqueued or the handle's state is touched.  ZG_ERR_UNSUPPORTED: the handle lacks
+ * ZG_GPT_GUIDED_GENERATE.  ZG_ERR_ARG: NULL start_states; a guided row with no table loaded; a start state >= n_states; greedy
+ * (options NULL without rows) with any guided row — as with edits, greedy is top_k = 1; an empty kept set: with an allow or ban list
+ * beside a guided row, EVERY state of the table (whichever the rows can reach) must keep a token the lists keep. */
+int zg_gpt_generate_guided_enqueue(zg_gpt* g, const zg_generate_request* r, const zg_row_sampling* rows_or_null, size_t n_rows,
+                                   const size_t* start_states);
+/* states_out [batch][n] (len >= batch * n): for columns first .. first + n - 1, the state in which the column's pick was drawn, or
+ * ZG_GUIDE_NONE for a prompt column and for an unguided row.  Serves columns < end of the last generation, which must have come
+ * through zg_gpt_generate_guided_enqueue (else ZG_ERR_ARG); columns below a continuation's past_len hold what earlier calls recorded. */
+int zg_gpt_generate_fetch_guide_states(zg_gpt* g, size_t first, size_t n, size_t* states_out, size_t len);
+/* Test entry: the mask kernel — with the edit stage's part in the same launch when edits (the three lists; min_p 0) are given —
+ * and then the advance kernel, alone on the caller's rows: logits [batch <= 64][vocab <= 262144] (host or device, as edited_out),
+ * states [batch] (ZG_GUIDE_NONE: unguided) and picks [batch] on the host; every row stands at a picked column.  edited_out
+ * [batch][vocab]: the rows as the stage leaves them; part_val_out / part_idx_out [batch][n_part], n_part = min(64, ceil(vocab /
+ * 256)): the rebuilt partials, slice j = the indices i with (i / 256) mod n_part == j; next_states_out [batch]: the states behind the
+ * picks (a pick >= vocab or a dead transition: unchanged).  The refusals of a load and of a call.  Needs zg_init only. */
+int zg_debug_guide_rows(const float* logits, size_t batch, size_t vocab, const zg_guide* guide, const size_t* states,
+                        const zg_logit_edits* edits_or_null, const size_t* picks, float* edited_out, float* part_val_out,
+                        int32_t* part_idx_out, size_t* next_states_out);
+/* The refusal zg_gpt_guide_load of `guide` on a handle of `vocab` tokens, followed (n >= 1) by a guided call with these edits, start
+ * states [n] and — greedy != 0 — without sampler options would return, or ZG_OK.  Needs neither a GPU nor zg_init. */
+int zg_debug_guide_check(const zg_guide* guide, size_t vocab, const zg_logit_edits* edits_or_null, const size_t* start_states, size_t n,
+                         int greedy);
 /* tokens of positions first .. first + n - 1 of the last generation(s): out_tokens [batch, n] */
 int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len);
 /* Test entry: the sampler kernels of zg_gpt_sample_ex on the caller's logits [batch <= 64, vocab <= 262144] (host or device, as

@@ -80,6 +80,12 @@ def row_sampling(rows):
     return arr
 
 
+class Guide(C.Structure):
+    """zg_guide of include/zgpt2.h."""
+
+    _fields_ = [("n_states", sz), ("next", vp)]
+
+
 class GenerateRequest(C.Structure):
     """zg_generate_request of include/zgpt2.h (`size` is filled by generate_request())."""
 
@@ -200,6 +206,11 @@ SIGNATURES = {
     "zg_debug_sample_rows_each": (C.c_int, [vp, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]),
     "zg_debug_penalize_rows_each": (C.c_int, [vp, sz, sz, vp, sz, vp, sz, vp, vp, vp]),
     "zg_debug_each_plan": (C.c_int, [vp, sz, sz, vp, sz]),
+    "zg_gpt_guide_load": (C.c_int, [vp, vp]),
+    "zg_gpt_generate_guided_enqueue": (C.c_int, [vp, vp, vp, sz, vp]),
+    "zg_gpt_generate_fetch_guide_states": (C.c_int, [vp, sz, sz, vp, sz]),
+    "zg_debug_guide_rows": (C.c_int, [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "zg_debug_guide_check": (C.c_int, [vp, sz, vp, vp, sz, C.c_int]),
     "zg_gpt_score": (C.c_int, [vp, sz, vp, sz, sz, sz, vp, sz]),
     "zg_debug_score_rows": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, vp, vp]),
     "zg_gpt_time_kernel": (C.c_int, [vp, C.c_int, C.c_int, f32p, szp]),
@@ -222,6 +233,8 @@ GPT_LOGPROBS_GENERATE = 2048
 GPT_SCORE = 4096
 GPT_STOP_GENERATE = 8192
 GPT_EDITED_GENERATE = 16384
+GPT_GUIDED_GENERATE = 32768
+GUIDE_MAX_STATES, GUIDE_DEAD, GUIDE_NONE = 256, 0xFFFF, (1 << 64) - 1
 EDIT_MAX_BIAS = 512
 LOGPROBS_TOP_MAX = 20
 STOP_MAX_IDS, STOP_MAX_SEQS, STOP_MAX_SEQ_LEN = 16, 8, 16

@@ -46,6 +46,7 @@ struct PinnedCtrl {
     alignas(64) float uniforms[8];   // the per-token family's draws (batch <= 8): h_ints[0 .. batch) is still being read by the forward's token upload
     alignas(128) PenParams pen[kRowsMax];      // pen.h_params: one entry per row
     alignas(32) int top_n;           // lp.h_top
+    alignas(32) int guide_state[kRowsMax];  // guide.h_state: the start state of every row (-1: no guide)
 };
 static_assert(sizeof(SampleParams) == 24 && sizeof(PenParams) == 16 && offsetof(PinnedCtrl, samp) == 128 && offsetof(PinnedCtrl, fault) == 384 &&
                   offsetof(PinnedCtrl, uniforms) == 448 && offsetof(PinnedCtrl, pen) == 512 && offsetof(PinnedCtrl, top_n) == 640,
@@ -214,6 +215,18 @@ struct zg_gpt {
         char* h_block;
         std::vector<char> build;
     } edit;
+    // generate — guided decoding (sample_guide.h), carved under ZG_GPT_GUIDED_GENERATE only (all null without): the
+    // transition table [256][vocab] uint16, the keep bitmap of every state [256][words], the device word n_states (0: no table), each
+    // row's state ([kRowsMax]; its pinned mirror h_state: PinnedCtrl.guide_state) and the state record [batch][ctx] (-1: none); on the
+    // host the bitmaps of the loaded table, kept for the checks of later calls
+    struct {
+        unsigned short* next;
+        unsigned* keep;
+        int *n_states, *state, *rec, *h_state;
+        std::vector<unsigned> h_keep;
+        size_t loaded;  // states of the table the handle holds (0: none)
+        bool valid;     // the last generation came through zg_gpt_generate_guided_enqueue: the record can be fetched
+    } guide;
     // generate — a generation in flight between gen_begin and gen_end (zg_gpt_generate_enqueue / _many), and what the last one left
     struct {
         size_t pos, n, min_prompt, since_sync;
@@ -296,7 +309,7 @@ struct StepKey {
     bool with_logits, multi;
     StepTail tail;
 };
-constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2 * 2 * 2;  // the radices of step_index
+constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2 * 2 * 2 * 2;  // the radices of step_index
 
 // What body() enqueues on stream cs, captured and instantiated into *out.  Nothing is left behind on failure.
 template <class Body>

@@ -163,6 +163,17 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
     // (and the edit stage's bias table with the keep bitmap behind it)
     g->edit.tab = (EditTable*)P(edit_block_bytes(V));
     g->edit.keep = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g->edit.tab) + sizeof(EditTable));
+    // (and behind everything: the guide's table, bitmaps, states and record — handles without the flag keep the layout they had)
+    g->guide.next = nullptr;
+    g->guide.keep = nullptr;
+    g->guide.n_states = g->guide.state = g->guide.rec = nullptr;
+    if (g->flags & ZG_GPT_GUIDED_GENERATE) {
+        g->guide.next = (unsigned short*)P((size_t)ZG_GUIDE_MAX_STATES * V * 2);
+        g->guide.keep = (unsigned*)P((size_t)ZG_GUIDE_MAX_STATES * guide_keep_words(V) * 4);
+        g->guide.n_states = (int*)P(256);
+        g->guide.state = (int*)P(kRowsMax * 4);
+        g->guide.rec = (int*)P(B * C * 4);
+    }
     g->state_bytes = (cv.off + 255) & ~(size_t)255;
 }
 
@@ -274,6 +285,7 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
     g->pen.h_params = g->h_ctrl->pen;
     g->pen.h_prior = g->h_ints + batch * c.context_size + batch;
     g->lp.h_top = &g->h_ctrl->top_n;
+    g->guide.h_state = g->h_ctrl->guide_state;
     ZG_REQUIRE(!(g->flags & ZG_GPT_PENALIZED_GENERATE) || c.context_size <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED,
                "ZG_GPT_PENALIZED_GENERATE: context_size %zu beyond the %d tokens the penalty kernel's LDS table holds", c.context_size, kPenMaxHistory);
     {   // decode steps per graph in the generate loop: a graph launch costs ~7 us of idle queue (124M: 224.8 us per token

@@ -535,6 +535,69 @@ int zg_debug_sample_rows_each(const float* logits, size_t batch, size_t vocab, c
     return debug_sample_rows(logits, batch, vocab, nullptr, rows, edits, uniforms, edited_out, tokens_out, probs_out, thresholds_out, "debug_sample_rows_each");
 }
 
+// The guide's two kernels on the caller's rows (tests): the mask — with the edit stage's part in the same launch when
+// the edits carry a list —, then the advance on the caller's picks.  Every row stands at a picked column (no control block).
+// Allocates per call.
+int zg_debug_guide_rows(const float* logits, size_t batch, size_t vocab, const zg_guide* guide, const size_t* states, const zg_logit_edits* edits,
+                        const size_t* picks, float* edited_out, float* part_val_out, int32_t* part_idx_out, size_t* next_states_out) {
+    ZG_TRY(require_init());
+    const char* who = "debug_guide_rows";
+    ZG_REQUIRE(logits && states && picks && edited_out && part_val_out && part_idx_out && next_states_out && batch >= 1 && batch <= 64 && vocab >= 1 &&
+                   vocab <= (size_t)64 * 4096,
+               ZG_ERR_ARG, "%s: bad argument", who);
+    ZG_REQUIRE(!edits || edits->min_p == 0.0f, ZG_ERR_ARG, "%s: edits->min_p %f (the lists only)", who, edits->min_p);
+    const size_t words = guide_keep_words(vocab);
+    std::vector<unsigned> h_keep((size_t)ZG_GUIDE_MAX_STATES * words);
+    ZG_TRY(build_guide(guide, vocab, who, h_keep.data()));
+    std::vector<char> block(edits ? edit_block_bytes(vocab) : 0);
+    bool stage_on = false, any = false;
+    if (edits) ZG_TRY(build_edits(edits, vocab, who, block.data(), &stage_on));
+    std::vector<int> h_state(batch), h_pick(batch);
+    ZG_TRY(check_guide_call(h_keep.data(), guide->n_states, vocab, stage_on ? reinterpret_cast<const unsigned*>(block.data() + sizeof(EditTable)) : nullptr,
+                            states, batch, false, who, h_state.data(), &any));
+    for (size_t b = 0; b < batch; ++b) h_pick[b] = (int)std::min(picks[b], (size_t)INT_MAX);
+    const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256), n_states = (int)guide->n_states;
+    hipStream_t s = ctx().stream;
+    DevScratch ds;
+    float *d_logits, *d_val;
+    int *d_idx, *d_n, *d_state, *d_pick;
+    unsigned short* d_next;
+    unsigned* d_keep;
+    char* d_edit;
+    ZG_TRY(ds.carve([&] {
+        d_logits = ds.take<float>(batch * vocab * 4);
+        d_val = ds.take<float>(batch * n_part * 4);
+        d_idx = ds.take<int>(batch * n_part * 4);
+        d_next = ds.take<unsigned short>((size_t)n_states * vocab * 2);
+        d_keep = ds.take<unsigned>((size_t)n_states * words * 4);
+        d_n = ds.take<int>(4);
+        d_state = ds.take<int>(batch * 4);
+        d_pick = ds.take<int>(batch * 4);
+        d_edit = ds.take<char>(block.size());
+    }));
+    ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemcpyAsync(d_next, guide->next, (size_t)n_states * vocab * 2, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_keep, h_keep.data(), (size_t)n_states * words * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_n, &n_states, 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_state, h_state.data(), batch * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_pick, h_pick.data(), batch * 4, hipMemcpyHostToDevice, s));
+    if (stage_on) ZG_HIP(hipMemcpyAsync(d_edit, block.data(), block.size(), hipMemcpyHostToDevice, s));
+    SamplerChain c{};
+    c.logits = d_logits, c.batch = B, c.vocab = V, c.part_val = d_val, c.part_idx = d_idx, c.n_part = n_part;
+    c.edit_tab = reinterpret_cast<const EditTable*>(d_edit);
+    c.edit_keep = reinterpret_cast<const unsigned*>(d_edit + sizeof(EditTable));
+    c.guide = GuideArgs{d_next, d_keep, d_n, d_state, nullptr, 0, nullptr, nullptr};
+    ZG_TRY(emit_sampler_chain(c, StepTail{GREEDY, false, false, false, stage_on, true}, s));  // (the row stage alone: no sampler)
+    ZG_HIP(hipMemcpyAsync(edited_out, d_logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemcpyAsync(part_val_out, d_val, batch * n_part * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(part_idx_out, d_idx, batch * n_part * 4, hipMemcpyDeviceToHost, s));
+    ZG_TRY(launch_guide_advance(c.guide, d_pick, B, V, s));
+    ZG_HIP(hipMemcpyAsync(h_state.data(), d_state, batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    for (size_t b = 0; b < batch; ++b) next_states_out[b] = h_state[b] < 0 ? ZG_GUIDE_NONE : (size_t)h_state[b];
+    return ZG_OK;
+}
+
 // The penalty kernels on the caller's rows (tests): the launches of the penalised step, in place on a copy — the body of
 // zg_debug_penalize_rows (pen: the same for every row) and of zg_debug_penalize_rows_each (each: the row's own).  Allocates per call.
 static int debug_penalize_rows(const float* logits, size_t batch, size_t vocab, const zg_logit_penalties* pen, const zg_row_sampling* each,

@@ -236,6 +236,11 @@ struct GenRequest {
     // logit edits, checked, the set built in the ONE handle's edit.build: edit_on — the
     // edit stage runs (min-p is the sampler's: in sp).  Off: the request is what it was
     bool edit_on = false;
+    // guided decoding: guide_call — the request came through zg_gpt_generate_guided_enqueue (the state record is the
+    // call's to fill); guide_on — some row is guided: the mask and the advance run, from guide_state[b] (-1: the row has no guide).
+    // Off: the request is what it was
+    bool guide_call = false, guide_on = false;
+    int guide_state[kRowsMax];
     GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, size_t past = 0)
         : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past) {}
 };
@@ -281,7 +286,8 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     if (g->pass.x != nullptr && min_prompt >= prefill_min())
         first = min_prompt < n_steps ? min_prompt : n_steps;
     const bool edit_on = r.edit_on && r.mode != GREEDY;
-    g->gen.tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on, edit_on};  // (normalized: pen_on / edit_on only with a sampler, and the steps it is for have lm_head)
+    const bool guide_on = r.guide_on && r.mode != GREEDY;
+    g->gen.tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on, edit_on, guide_on};  // (normalized: pen_on / edit_on / guide_on only with a sampler, and the steps it is for have lm_head)
     g->gen.stop_valid = false;
     g->gen.stop = r.stop_on;
     if (r.stop_on) {  // the conditions of this call; no row has finished; the stage has seen nothing (the stream is drained: the words are the host's)
@@ -298,6 +304,15 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     }
     if (pen_on) ZG_TRY(stage_penalties(g, r.pp, r.prior, r.prior_stride, r.prior_lens, s));
     if (edit_on) ZG_TRY(stage_edits(g, s));
+    g->guide.valid = false;
+    if (r.guide_call) {  // the new columns record "none" (every byte 0xff) until the advance of a guided row's picked column says otherwise
+        ZG_HIP(hipMemset2DAsync(g->guide.rec + past, C * sizeof(int), 0xff, n_steps * sizeof(int), B, s));
+        g->guide.valid = true;
+    }
+    if (guide_on) {  // every row's start state through the pinned control block (the stream is drained: the mirror is the host's)
+        memcpy(g->guide.h_state, r.guide_state, B * sizeof(int));
+        ZG_HIP(hipMemcpyAsync(g->guide.state, g->guide.h_state, B * sizeof(int), hipMemcpyHostToDevice, s));
+    }
     g->lp.valid = false;
     if (r.lp_on) {
         ZG_TRY(stage_top_n(g, r.top_n, s));
@@ -480,8 +495,9 @@ static int gen_run(zg_gpt* const* handles, size_t n_handles, GenRequest req) {
 // handle, the first (zg_gpt_generate_enqueue_many has none of them).
 // each (zg_gpt_generate_each_enqueue): the table of the call, one zg_row_sampling per row of the handle, in the place of q.options /
 // q.penalties / q.edits->min_p / q.seed; null: the uniform request, whose table is `batch` equal rows.
+// guide (zg_gpt_generate_guided_enqueue): the start state of every row of the handle, which has ZG_GPT_GUIDED_GENERATE; null: no guide.
 static int generate_request(zg_gpt* const* handles, size_t n_handles, const zg_generate_request& q, const char* who, const zg_row_sampling* each = nullptr,
-                            size_t n_each = 0) {
+                            size_t n_each = 0, const size_t* guide = nullptr) {
     ZG_TRY(require_init());
     zg_gpt* const g = handles[0];
     ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null argument", who);
@@ -524,6 +540,12 @@ static int generate_request(zg_gpt* const* handles, size_t n_handles, const zg_g
         ZG_TRY(plan_rows(rows, g->batch, g->cfg.vocab_size, q.past_len, who, r.sp, r.pp, nullptr, &plan));
     }
     if (q.options || each) r.mode = plan.sampler;
+    if (guide) {  // (behind the edits: an empty kept set is judged against the call's own keep bitmap, built above in edit.build)
+        const unsigned* call_keep = r.edit_on ? reinterpret_cast<const unsigned*>(g->edit.build.data() + sizeof(EditTable)) : nullptr;
+        ZG_TRY(check_guide_call(g->guide.loaded ? g->guide.h_keep.data() : nullptr, g->guide.loaded, g->cfg.vocab_size, call_keep, guide, g->batch,
+                                !q.options && !each, who, r.guide_state, &r.guide_on));
+        r.guide_call = true;
+    }
     return gen_run(handles, n_handles, r);
 }
 
@@ -617,6 +639,65 @@ int zg_gpt_generate_each_enqueue(zg_gpt* g, const zg_generate_request* r, const 
     ZG_REQUIRE(r != nullptr && r->size == sizeof(zg_generate_request), ZG_ERR_ARG, "generate_each: null request, or its size field is not sizeof(zg_generate_request)");
     ZG_REQUIRE(rows != nullptr, ZG_ERR_ARG, "generate_each: rows is null");
     return generate_request(&g, 1, *r, "generate_each", rows, n_rows);
+}
+
+// ---- Guided decoding
+
+// The table of a handle: checked and turned into bitmaps by build_guide (into a scratch, so that a refused table leaves the loaded
+// one standing), then uploaded.  Synchronous; drains first — a generation in flight may be reading what is replaced.
+int zg_gpt_guide_load(zg_gpt* g, const zg_guide* guide) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "guide_load: null handle");
+    ZG_REQUIRE(g->flags & ZG_GPT_GUIDED_GENERATE, ZG_ERR_UNSUPPORTED, "guide_load: the handle was created without ZG_GPT_GUIDED_GENERATE");
+    const size_t V = g->cfg.vocab_size, words = guide_keep_words(V);
+    std::vector<unsigned> keep;
+    if (guide) {
+        keep.assign((size_t)ZG_GUIDE_MAX_STATES * words, 0u);
+        ZG_TRY(build_guide(guide, V, "guide_load", keep.data()));
+    }
+    hipStream_t s = gs(g);
+    ZG_HIP(hipStreamSynchronize(s));
+    const int n = guide ? (int)guide->n_states : 0;
+    g->guide.loaded = 0;  // (a failed upload leaves no table rather than half of one)
+    ZG_HIP(hipMemcpy(g->guide.n_states, &n, sizeof(int), hipMemcpyHostToDevice));
+    if (guide) {
+        ZG_HIP(hipMemcpy(g->guide.next, guide->next, (size_t)n * V * sizeof(uint16_t), hipMemcpyHostToDevice));
+        ZG_HIP(hipMemcpy(g->guide.keep, keep.data(), (size_t)n * words * 4, hipMemcpyHostToDevice));
+    }
+    ZG_HIP(hipDeviceSynchronize());
+    g->guide.h_keep.swap(keep);
+    g->guide.loaded = (size_t)n;
+    return ZG_OK;
+}
+
+int zg_gpt_generate_guided_enqueue(zg_gpt* g, const zg_generate_request* r, const zg_row_sampling* rows, size_t n_rows, const size_t* start_states) {
+    ZG_REQUIRE(r != nullptr && r->size == sizeof(zg_generate_request), ZG_ERR_ARG, "generate_guided: null request, or its size field is not sizeof(zg_generate_request)");
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "generate_guided: null handle");
+    ZG_REQUIRE(g->flags & ZG_GPT_GUIDED_GENERATE, ZG_ERR_UNSUPPORTED, "generate_guided: the handle was created without ZG_GPT_GUIDED_GENERATE");
+    ZG_REQUIRE(start_states != nullptr, ZG_ERR_ARG, "generate_guided: start_states is null");
+    ZG_REQUIRE(rows != nullptr || n_rows == 0, ZG_ERR_ARG, "generate_guided: %zu rows but rows is null", n_rows);
+    return generate_request(&g, 1, *r, "generate_guided", rows, n_rows, start_states);
+}
+
+int zg_gpt_generate_fetch_guide_states(zg_gpt* g, size_t first, size_t n, size_t* states_out, size_t len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && states_out, ZG_ERR_ARG, "generate_fetch_guide_states: null argument");
+    ZG_REQUIRE(g->flags & ZG_GPT_GUIDED_GENERATE, ZG_ERR_UNSUPPORTED, "generate_fetch_guide_states: the handle was created without ZG_GPT_GUIDED_GENERATE");
+    ZG_REQUIRE(g->guide.valid, ZG_ERR_ARG, "generate_fetch_guide_states: the last generation did not come through zg_gpt_generate_guided_enqueue");
+    const size_t C = g->cfg.context_size, B = g->batch;
+    ZG_REQUIRE(first <= C && n <= C - first && len >= B * n, ZG_ERR_SHAPE, "generate_fetch_guide_states: positions %zu .. %zu of %zu, %zu elements", first,
+               first + n, C, len);
+    if (n == 0) return ZG_OK;
+    hipStream_t s = gs(g);
+    ZG_HIP(hipMemcpyAsync(g->h_ints, g->guide.rec, B * C * sizeof(int), hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    for (size_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < n; ++i) {
+            const int st = g->h_ints[b * C + first + i];
+            states_out[b * n + i] = st < 0 ? ZG_GUIDE_NONE : (size_t)st;
+        }
+    return ZG_OK;
 }
 
 int zg_gpt_generate_stop_result(zg_gpt* g, size_t* end_out, size_t* finish_cols_out, int* reasons_out) {

@@ -87,12 +87,12 @@ PenHistory pen_history(const zg_gpt* g, bool loop) {
 }
 
 size_t step_index(StepKey k) {
-    return ((((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp) * 2 + k.tail.stop) * 2 + k.tail.edit;
+    return (((((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp) * 2 + k.tail.stop) * 2 + k.tail.edit) * 2 + k.tail.guide;
 }
 
 // The tails whose graphs zg_gpt_create captures besides the default one, by the handle's flags: each *_GENERATE flag names the
 // samplers it is for, ZG_GPT_LOGPROBS_GENERATE the twins with the log-probability stage of the default tail and of those, and
-// ZG_GPT_STOP_GENERATE the twins with the stop stage of all of these
+// ZG_GPT_GUIDED_GENERATE the guided twins of the sampler tails, ZG_GPT_STOP_GENERATE the twins with the stop stage of all of these
 std::vector<StepTail> tails_of_flags(unsigned flags) {
     std::vector<StepTail> t;
     if (flags & ZG_GPT_SAMPLED_GENERATE) t.push_back({PLAIN, false, false});
@@ -104,15 +104,19 @@ std::vector<StepTail> tails_of_flags(unsigned flags) {
         t.push_back({MINP_ONLY, false, false});
         for (SamplerMode m : {PLAIN, ONE_FILTER, TWO_FILTERS, MINP_ONLY}) t.push_back({m, false, false, false, true});
     }
+    if (flags & ZG_GPT_GUIDED_GENERATE) {  // the guided twin of every sampler tail above (a greedy pick has none)
+        const size_t n = t.size();
+        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, false, false, t[i].edit, true});
+    }
     if (flags & ZG_GPT_LOGPROBS_GENERATE) {
         const size_t n = t.size();
         t.push_back({GREEDY, false, true});
-        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, true, false, t[i].edit});
+        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, true, false, t[i].edit, t[i].guide});
     }
     if (flags & ZG_GPT_STOP_GENERATE) {  // the stop twins of the default tail and of everything above
         const size_t n = t.size();
         t.push_back({GREEDY, false, false, true});
-        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, t[i].lp, true, t[i].edit});
+        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, t[i].lp, true, t[i].edit, t[i].guide});
     }
     return t;
 }
@@ -328,6 +332,8 @@ SamplerChain handle_chain(const zg_gpt* g, bool loop) {
     c.part_val = g->part_val, c.part_idx = g->part_idx, c.n_part = g->lm_grid;
     c.pen = g->pen.params, c.hist = pen_history(g, loop);
     c.edit_tab = g->edit.tab, c.edit_keep = g->edit.keep;
+    c.guide = GuideArgs{g->guide.next, g->guide.keep, g->guide.n_states, g->guide.state, g->guide.rec, (int)g->cfg.context_size, loop ? g->ctrl : nullptr,
+                        g->prompt_len};
     c.params = g->samp.params, c.seg_ws = g->samp.ws, c.filt = g->samp.filt;
     if (loop) c.ctrl = g->ctrl, c.pick = g->samp.sampled;
     return c;
@@ -488,6 +494,8 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
     const int* const picks = tail.sampler == GREEDY ? nullptr : g->samp.sampled;  // (the greedy graphs have no sampler node)
     ZG_TRY(emit_sampler_chain(handle_chain(g, true), tail, s));
     if (tail.lp) ZG_TRY(logprobs(picks));
+    // the guide's advance: the state record of this column, then the transition of the pick (a guided tail has a sampler)
+    if (tail.guide) ZG_TRY(launch_guide_advance(handle_chain(g, true).guide, picks, (int)g->batch, (int)g->cfg.vocab_size, s));
     if (tail.stop) ZG_TRY(stop(picks));
     return ZG_OK;
 }

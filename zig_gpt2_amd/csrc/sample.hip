@@ -1,6 +1,6 @@
 // sample.hip — the head of a decode step and the stages of the device sampler behind lm_head (model tier): embed_step_kernel,
 // the plain sampler's three kernels, and — as included headers, one per stage — truncation (sample_filter.h), penalties
-// (sample_penalty.h), logit edits (sample_edit.h), log-probabilities (sample_logprob.h), scoring (sample_score.h) and the stop
+// (sample_penalty.h), logit edits (sample_edit.h), guided decoding (sample_guide.h), log-probabilities (sample_logprob.h), scoring (sample_score.h) and the stop
 // conditions (sample_stop.h), with every stage's launcher and workspace carver.  What the stages share — the pick from lm_head's
 // argmax partials, the row maximum, the rebuild of a slice's partial — is in sample_common.h; the order of picks itself
 // (pick_before), clamp_token and counter_uniform are in zg_common.h.
@@ -296,6 +296,7 @@ __global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vo
 #include "sample_filter.h"
 #include "sample_penalty.h"
 #include "sample_edit.h"
+#include "sample_guide.h"
 #include "sample_logprob.h"
 #include "sample_score.h"
 #include "sample_stop.h"
@@ -424,6 +425,25 @@ int launch_logit_edit(float* logits, int batch, int vocab, const EditTable* tab,
     ZG_REQUIRE(logits && tab && keep && part_val && part_idx && batch >= 1 && vocab >= 1 && n_part >= 1 && n_part <= 4096, ZG_ERR_ARG,
                "logit edits: missing argument");
     hipLaunchKernelGGL(logit_edit_kernel, dim3(n_part, batch), dim3(256), 0, s, logits, vocab, tab, keep, part_val, part_idx);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_guide_mask(float* logits, int batch, int vocab, const EditTable* tab, const unsigned* keep, const GuideArgs& g, float* part_val, int* part_idx,
+                      int n_part, hipStream_t s) {
+    ZG_REQUIRE(logits && g.keep && g.n_states && g.state && (g.ctrl == nullptr || g.prompt_len) && (tab == nullptr) == (keep == nullptr) && part_val && part_idx &&
+                   batch >= 1 && vocab >= 1 && n_part >= 1 && n_part <= 4096,
+               ZG_ERR_ARG, "guide mask: missing argument");
+    hipLaunchKernelGGL(guide_mask_kernel, dim3(n_part, batch), dim3(256), 0, s, logits, vocab, tab, keep, g, part_val, part_idx);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_guide_advance(const GuideArgs& g, const int* picks, int batch, int vocab, hipStream_t s) {
+    ZG_REQUIRE(g.next && g.n_states && g.state && (g.ctrl == nullptr || g.prompt_len) && (g.rec == nullptr || g.rec_stride >= 1) && picks && batch >= 1 &&
+                   batch <= 64 && vocab >= 1,
+               ZG_ERR_ARG, "guide advance: missing argument");
+    hipLaunchKernelGGL(guide_advance_kernel, dim3(1), dim3(64), 0, s, g, picks, batch, vocab);  // one lane per row
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

@@ -23,13 +23,16 @@ static inline bool threshold_sampler(SamplerMode m) { return m == ONE_FILTER || 
 struct StepTail {
     SamplerMode sampler = GREEDY;
     bool pen = false, lp = false, stop = false, edit = false;
-    bool operator==(const StepTail& o) const { return sampler == o.sampler && pen == o.pen && lp == o.lp && stop == o.stop && edit == o.edit; }
+    bool guide = false;  // guided decoding: the mask behind (and in one launch with) the edits, the advance behind the sampler
+    bool operator==(const StepTail& o) const {
+        return sampler == o.sampler && pen == o.pen && lp == o.lp && stop == o.stop && edit == o.edit && guide == o.guide;
+    }
 };
 // The tail a step can have: nothing is drawn from a step without lm_head (the default tail), and a greedy pick has neither
-// penalties nor edits
+// penalties, edits nor a guide
 static inline StepTail normalized(StepTail t, bool with_logits) {
     if (!with_logits) return StepTail{};
-    if (t.sampler == GREEDY) t.pen = t.edit = false;
+    if (t.sampler == GREEDY) t.pen = t.edit = t.guide = false;
     return t;
 }
 
@@ -49,6 +52,7 @@ struct SamplerChain {
     unsigned* counts;  // (zg_debug_penalize_rows: the counts of every row's history)
     const EditTable* edit_tab;
     const unsigned* edit_keep;
+    GuideArgs guide;  // the automaton, the rows' states and (the loop) the column in flight
     const SampleParams* params;
     float* seg_ws;
     FilterWs filt;
@@ -68,6 +72,10 @@ void unpack_top(const int* ids, const float* vals, size_t rows, size_t top_n, si
 bool penalties_off(const zg_logit_penalties& p);
 bool edits_off(const zg_logit_edits& e);
 int build_edits(const zg_logit_edits* e, size_t vocab, const char* who, char* block, bool* stage_on);
+size_t guide_keep_words(size_t vocab);
+int build_guide(const zg_guide* gd, size_t vocab, const char* who, unsigned* keep);
+int check_guide_call(const unsigned* guide_keep, size_t n_states, size_t vocab, const unsigned* call_keep, const size_t* start_states, size_t n, bool greedy,
+                     const char* who, int* states_out, bool* any_out);
 SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed, float min_p);
 int plan_rows(const zg_row_sampling* rows, size_t n_rows, size_t vocab, size_t past_len, const char* who, SampleParams* sp, PenParams* pp, int* forms,
               StepTail* tail);

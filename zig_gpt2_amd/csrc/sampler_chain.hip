@@ -1,11 +1,12 @@
 // sampler_chain.hip — the handle-free host side of the sampler: the sampler chain behind lm_head, emitted by emit_sampler_chain for
-// every user, and the checks and fills of what a sampler call is given (options, penalties, edits, stop conditions, top_n).
+// every user, and the checks and fills of what a sampler call is given (options, penalties, edits, stop conditions, top_n, a guide).
 #include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
 #include <cmath>
 #include <utility>
+#include <vector>
 
 #include "sampler_chain.h"
 
@@ -29,8 +30,12 @@ size_t edit_block_bytes(size_t vocab) { return sizeof(EditTable) + (vocab + 31) 
 int emit_sampler_chain(const SamplerChain& c, StepTail t, hipStream_t s) {
     // the penalties act on the raw logits, the edits on the row the penalties leave (HF's processor order); the row-maximum
     // partials every sampler starts from are rebuilt only behind the LAST stage that rewrites the row — the edit launch does it itself
-    if (t.pen) ZG_TRY(launch_penalize(c.logits, c.batch, c.vocab, c.pen, c.hist, c.part_val, c.part_idx, c.n_part, c.counts, s, !t.edit));
-    if (t.edit) ZG_TRY(launch_logit_edit(c.logits, c.batch, c.vocab, c.edit_tab, c.edit_keep, c.part_val, c.part_idx, c.n_part, s));
+    // and the guide's mask IS the edit launch where both are on: one launch rewrites the row for both and rebuilds
+    if (t.pen) ZG_TRY(launch_penalize(c.logits, c.batch, c.vocab, c.pen, c.hist, c.part_val, c.part_idx, c.n_part, c.counts, s, !t.edit && !t.guide));
+    if (t.guide)
+        ZG_TRY(launch_guide_mask(c.logits, c.batch, c.vocab, t.edit ? c.edit_tab : nullptr, t.edit ? c.edit_keep : nullptr, c.guide, c.part_val, c.part_idx,
+                                 c.n_part, s));
+    else if (t.edit) ZG_TRY(launch_logit_edit(c.logits, c.batch, c.vocab, c.edit_tab, c.edit_keep, c.part_val, c.part_idx, c.n_part, s));
     if (t.sampler == GREEDY) return ZG_OK;
     if (threshold_sampler(t.sampler))  // a filter or min-p: the selection launches, then the tail kernels that read tau
         return launch_sample_filtered(c.logits, c.batch, c.vocab, c.params, filter_launches(t.sampler), c.u, c.ctrl, c.part_val, c.n_part, c.n_part, c.seg_ws,
@@ -100,6 +105,62 @@ int build_edits(const zg_logit_edits* e, size_t vocab, const char* who, char* bl
     for (size_t w = 0; w < words; ++w) kept += (size_t)__builtin_popcount(keep[w]);
     // (both lists are the host's: a row of -inf alone never reaches a kernel)
     ZG_REQUIRE(kept >= 1, ZG_ERR_ARG, "%s: the allow and ban lists leave no token", who);
+    return ZG_OK;
+}
+
+// ---- Guided decoding (include/zgpt2.h zg_guide).  The one place that checks a table and builds what the mask reads
+size_t guide_keep_words(size_t vocab) { return (vocab + 31) / 32; }
+
+// The refusals of a table over `vocab` tokens, and the keep bitmap of every state into keep [n_states][guide_keep_words(vocab)]
+// (plain host memory of ZG_GUIDE_MAX_STATES rows): bit i of row s set iff next[s][i] is a state.  Bits behind the vocabulary stay
+// clear.  Nothing else is touched.
+int build_guide(const zg_guide* gd, size_t vocab, const char* who, unsigned* keep) {
+    ZG_REQUIRE(gd != nullptr && gd->next != nullptr, ZG_ERR_ARG, "%s: the guide or its table is null", who);
+    ZG_REQUIRE(gd->n_states >= 1 && gd->n_states <= (size_t)ZG_GUIDE_MAX_STATES, ZG_ERR_ARG, "%s: %zu states outside 1..%d", who, gd->n_states,
+               ZG_GUIDE_MAX_STATES);
+    const size_t words = guide_keep_words(vocab);
+    memset(keep, 0, gd->n_states * words * 4);
+    for (size_t st = 0; st < gd->n_states; ++st) {
+        const uint16_t* row = gd->next + st * vocab;
+        unsigned* k = keep + st * words;
+        size_t kept = 0;
+        for (size_t i = 0; i < vocab; ++i) {
+            if (row[i] == ZG_GUIDE_DEAD) continue;
+            ZG_REQUIRE(row[i] < gd->n_states, ZG_ERR_ARG, "%s: state %zu goes to state %u of %zu on token %zu", who, st, (unsigned)row[i], gd->n_states, i);
+            k[i >> 5] |= 1u << (i & 31);
+            ++kept;
+        }
+        ZG_REQUIRE(kept >= 1, ZG_ERR_ARG, "%s: state %zu allows no token", who, st);
+    }
+    return ZG_OK;
+}
+
+// The refusals of a guided call: start_states [n] against the loaded table (guide_keep null: none is loaded), its keep bitmaps
+// against the call's own keep set (call_keep null: the call has no lists) — EVERY state of the table must keep a token, a popcount of
+// the AND per state —, and greedy picking beside a guided row.  states_out [n] (optional): the states as the device holds them, -1
+// for ZG_GUIDE_NONE; *any_out: some row is guided.  With no guided row nothing of the table is asked.
+int check_guide_call(const unsigned* guide_keep, size_t n_states, size_t vocab, const unsigned* call_keep, const size_t* start_states, size_t n, bool greedy,
+                     const char* who, int* states_out, bool* any_out) {
+    ZG_REQUIRE(start_states != nullptr, ZG_ERR_ARG, "%s: start_states is null", who);
+    bool any = false;
+    for (size_t b = 0; b < n; ++b) {
+        const bool none = start_states[b] == ZG_GUIDE_NONE;
+        any = any || !none;
+        if (!none) {
+            ZG_REQUIRE(guide_keep != nullptr, ZG_ERR_ARG, "%s: row %zu starts in state %zu but no guide is loaded", who, b, start_states[b]);
+            ZG_REQUIRE(start_states[b] < n_states, ZG_ERR_ARG, "%s: row %zu starts in state %zu of %zu", who, b, start_states[b], n_states);
+        }
+        if (states_out) states_out[b] = none ? -1 : (int)start_states[b];
+    }
+    *any_out = any;
+    if (!any) return ZG_OK;
+    ZG_REQUIRE(!greedy, ZG_ERR_ARG, "%s: a guide without sampler options (greedy picking with a guide is top_k = 1)", who);
+    const size_t words = guide_keep_words(vocab);
+    for (size_t st = 0; call_keep && st < n_states; ++st) {
+        size_t kept = 0;
+        for (size_t w = 0; w < words; ++w) kept += (size_t)__builtin_popcount(guide_keep[st * words + w] & call_keep[w]);
+        ZG_REQUIRE(kept >= 1, ZG_ERR_ARG, "%s: the allow and ban lists leave state %zu no token", who, st);
+    }
     return ZG_OK;
 }
 
@@ -207,6 +268,19 @@ int zg_debug_each_plan(const zg_row_sampling* rows, size_t n_rows, size_t vocab,
     out[0] = (int)t.sampler;
     out[1] = t.pen ? 1 : 0;
     return ZG_OK;
+}
+
+// build_guide's and check_guide_call's face (tests, and the Python builders; no GPU, no zg_init): a load of `guide`, then a call
+int zg_debug_guide_check(const zg_guide* guide, size_t vocab, const zg_logit_edits* edits, const size_t* start_states, size_t n, int greedy) {
+    ZG_REQUIRE(vocab >= 1 && vocab <= (size_t)64 * 4096 && n <= 64, ZG_ERR_ARG, "debug_guide_check: vocab %zu, %zu rows", vocab, n);
+    std::vector<unsigned> keep((size_t)ZG_GUIDE_MAX_STATES * guide_keep_words(vocab));
+    ZG_TRY(build_guide(guide, vocab, "debug_guide_check", keep.data()));
+    if (n == 0) return ZG_OK;
+    std::vector<char> block(edit_block_bytes(vocab));
+    bool stage_on = false, any = false;
+    if (edits) ZG_TRY(build_edits(edits, vocab, "debug_guide_check", block.data(), &stage_on));
+    return check_guide_call(keep.data(), guide->n_states, vocab, stage_on ? reinterpret_cast<const unsigned*>(block.data() + sizeof(EditTable)) : nullptr,
+                            start_states, n, greedy != 0, "debug_guide_check", nullptr, &any);
 }
 
 int zg_debug_min_p_offset(float temp, float min_p, float* d_out) {

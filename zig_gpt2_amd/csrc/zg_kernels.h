@@ -493,6 +493,34 @@ struct EditTable {
 int launch_logit_edit(float* logits, int batch, int vocab, const EditTable* tab, const unsigned* keep, float* part_val, int* part_idx, int n_part,
                       hipStream_t s);
 
+// Guided decoding: a token-level automaton per row (sample_guide.h; include/zgpt2.h zg_guide).  next [n_states][vocab] uint16: the
+// state behind picking a token, kGuideDead where the state does not allow it; keep [n_states][(vocab + 31) / 32]: the same as one
+// bitmap per state, built by the host; *n_states (device word, <= kGuideMaxStates); state [batch]: where each row stands, negative
+// (or >= *n_states) for a row without a guide.  All of it is read on the device and clamped before it becomes an address, so one
+// captured launch serves every table.  ctrl / prompt_len: the column in flight is ctrl->seq_len - 1 and row b is guided there only
+// when that is a picked column (>= prompt_len[b]); ctrl null: every row stands at a picked column, column 0.
+//   launch_guide_mask     the twin of launch_logit_edit (its grid, slices and single-writer rule): -inf where the row's state, ANDed
+//                         with the call's keep set when edits are given (tab / keep, both or neither), drops an index; the bias of
+//                         a kept index; the slice maxima rebuilt into part_val / part_idx.  A row without a guide and without edits
+//                         is only read.
+//   launch_guide_advance  one small workgroup behind the sampler: for a guided row at a picked column, rec[b][column] = state[b]
+//                         (rec may be null), then state[b] = next[state[b]][picks[b]] unless that is dead or out of range.
+constexpr int kGuideMaxStates = 256;       // ZG_GUIDE_MAX_STATES of the header
+constexpr unsigned kGuideDead = 0xffffu;   // ZG_GUIDE_DEAD
+struct GuideArgs {
+    const unsigned short* next;
+    const unsigned* keep;
+    const int* n_states;
+    int* state;
+    int* rec;
+    int rec_stride;
+    const StepCtrl* ctrl;
+    const int* prompt_len;
+};
+int launch_guide_mask(float* logits, int batch, int vocab, const EditTable* tab_or_null, const unsigned* keep_or_null, const GuideArgs& g, float* part_val,
+                      int* part_idx, int n_part, hipStream_t s);
+int launch_guide_advance(const GuideArgs& g, const int* picks, int batch, int vocab, hipStream_t s);
+
 // The log-probability stage behind the sampler (sample_logprob.h; include/zgpt2.h zg_gpt_generate_logprobs_enqueue): for every row,
 // the log-probability of the token the step records and the *top_n (device memory, 0 .. 20) largest logits with theirs, written
 // into column ctrl->seq_len - 1 of the record buffers (ctrl null: column 0) — NaN where that column is below prompt_len[b] (null:

@@ -32,7 +32,7 @@ class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
                  sampled_generate=False, weights_b24=False, truncated_generate=False, penalized_generate=False, logprobs_generate=False,
-                 score=False, stop_generate=False, edited_generate=False):
+                 score=False, stop_generate=False, edited_generate=False, guided=False):
         """share_weights_with / own_stream / stream_priority: zg_gpt_options of zg_gpt_create_ex (a handle of an independent
         prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config).
         weights_b24: matrices stored as 24-bit floats (ZG_GPT_WEIGHTS_B24: each fp32 weight rounded to 16 mantissa bits, 3/4 of
@@ -42,7 +42,9 @@ class GPT:
         logprobs_generate: the same for the log-probability twins of every graph create captures (ZG_GPT_LOGPROBS_GENERATE).
         score: carve what `score` / `loglikelihood` need (ZG_GPT_SCORE); without it they raise ZG_ERR_UNSUPPORTED.
         stop_generate: the stop twins of every graph create captures (ZG_GPT_STOP_GENERATE), as the other *_generate flags.
-        edited_generate: the graphs of generations with logit edits or min-p (ZG_GPT_EDITED_GENERATE), as the other *_generate flags."""
+        edited_generate: the graphs of generations with logit edits or min-p (ZG_GPT_EDITED_GENERATE), as the other *_generate flags.
+        guided: guided decoding (ZG_GPT_GUIDED_GENERATE) — carve the automaton's table, bitmaps, states and record, and
+        capture the guided twins of the sampler graphs create captures; without it `load_guide` and guide_states raise ZG_ERR_UNSUPPORTED."""
         self.config, self.batch = config, batch
         L = _lib.load()
         flags = (_lib.GPT_WEIGHTS_F32 if weights_f32 else 0) | (0 if use_graph else _lib.GPT_NO_GRAPH)
@@ -59,6 +61,7 @@ class GPT:
         flags |= _lib.GPT_SCORE if score else 0
         flags |= _lib.GPT_STOP_GENERATE if stop_generate else 0
         flags |= _lib.GPT_EDITED_GENERATE if edited_generate else 0
+        flags |= _lib.GPT_GUIDED_GENERATE if guided else 0
         cfg = _lib.GptConfig(config.vocab_size, config.context_size, config.n_layer, config.n_heads, config.n_embed)
         h = C.c_void_p()
         if share_weights_with is None and not own_stream:
@@ -272,9 +275,10 @@ class GPT:
             raise ValueError("allowed_token_ids is empty: no token could be picked")
         return _lib.logit_edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
 
-    def _request_enqueue(self, past, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, conds, edits):
+    def _request_enqueue(self, past, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, conds, edits, guide_states=None):
         """zg_gpt_generate_request_enqueue: the one call every generation with penalties, log-probabilities, stop conditions or
-        edits goes through.  conds: a zg_stop_conditions or None; edits: `_edits(...)`."""
+        edits goes through.  conds: a zg_stop_conditions or None; edits: `_edits(...)`.  guide_states (one start state per row, None
+        for a row without a guide): the same request through zg_gpt_generate_guided_enqueue."""
         if (pen is not None or edits is not None) and temp is None:
             raise ValueError("penalties and edits need a sampler: greedy picking with them is temp=1.0, top_k=1")
         opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
@@ -283,8 +287,36 @@ class GPT:
                                   options=None if opt is None else C.addressof(opt), penalties=None if pen is None else C.addressof(pen), prior=pp,
                                   prior_stride=pstride, prior_lens=plens, seed=seed, logprobs=int(logprobs is not None), top_n=int(logprobs or 0),
                                   stop=None if conds is None else C.addressof(conds), edits=None if edits is None else C.addressof(edits[0]))
-        check(self._L.zg_gpt_generate_request_enqueue(self.h, C.addressof(r)))
+        if guide_states is None:
+            check(self._L.zg_gpt_generate_request_enqueue(self.h, C.addressof(r)))
+        else:
+            states = self._guide_states(guide_states)
+            check(self._L.zg_gpt_generate_guided_enqueue(self.h, C.addressof(r), None, 0, ptr(states)))
         del keep
+
+    # ------------------------------------------------------------------ guided decoding
+    def load_guide(self, guide):
+        """zg_gpt_guide_load: the automaton (a guide.Guide) later generations' guide_states refer to; None unloads.  The one slow
+        call of the feature: once per grammar, not per request."""
+        if guide is None:
+            check(self._L.zg_gpt_guide_load(self.h, None))
+        else:
+            g = guide.c_struct()
+            check(self._L.zg_gpt_guide_load(self.h, C.addressof(g)))
+
+    def _guide_states(self, guide_states):
+        states = np.array([_lib.GUIDE_NONE if st is None else int(st) for st in guide_states], np.uint64)
+        if states.size != self.batch:
+            raise ValueError(f"guide_states: {states.size} start states for a batch of {self.batch}")
+        return states
+
+    def generate_fetch_guide_states(self, first, n):
+        """zg_gpt_generate_fetch_guide_states of columns first .. first + n - 1: [batch, n] uint64, the state each column's pick was
+        drawn in, or guide.NONE for a prompt column and for an unguided row.  A second turn starts a row in
+        guide.step(state of its last picked column, the token there)."""
+        out = np.zeros((self.batch, n), np.uint64)
+        check(self._L.zg_gpt_generate_fetch_guide_states(self.h, first, n, ptr(out), out.size))
+        return out
 
     def _token_lists(self, lists):
         """One token list per row (None: none) -> (ptr or None, stride, ptr to lengths or None), with the arrays kept alive."""
@@ -295,13 +327,14 @@ class GPT:
             mat, stride = np.zeros((self.batch, 1), np.uint64), 1
         return ptr(mat), stride, ptr(lens), (mat, lens)
 
-    def _generate_stop(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits=None):
+    def _generate_stop(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits=None,
+                       guide_states=None):
         """A generation with stop conditions (the request call): what `_generate` returns, cut at `end` —
         columns past_len .. end - 1.  `stop_result()` tells where every row finished and why."""
         past = past_len or 0
         mat, lens, stride = self._prompts(prompts)
         conds, keep_conds = _lib.stop_conditions(stop_token_ids, stop, lookahead)
-        self._request_enqueue(past, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, conds, edits)
+        self._request_enqueue(past, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, conds, edits, guide_states)
         del keep_conds
         n = self.stop_result()[0] - past if conds.n_ids or conds.n_seqs else n_steps  # (no conditions: the plain call ran)
         out = self.generate_fetch_range(past, n)
@@ -317,7 +350,7 @@ class GPT:
         check(self._L.zg_gpt_generate_stop_result(self.h, C.byref(end), ptr(cols), ptr(reasons)))
         return end.value, [None if int(c) == _lib.STOP_NONE else int(c) for c in cols], [int(r) for r in reasons]
 
-    def _generate(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=True, edits=None):
+    def _generate(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=True, edits=None, guide_states=None):
         """Every generation of this class: enqueue through the entry point its arguments ask for, then (fetch) return what the
         public method returns.  past_len None: not a continuation.  temp None: greedy.  pen: `_penalties(...)`.  logprobs: top_n or
         None.  edits: `_edits(...)`.  With penalties, log-probabilities and edits off the plain entry points run
@@ -330,8 +363,8 @@ class GPT:
         opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
         opt_p = None if opt is None else C.addressof(opt)
         out = None
-        if logprobs is not None or pen is not None or edits is not None:
-            self._request_enqueue(past_len or 0, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, None, edits)
+        if logprobs is not None or pen is not None or edits is not None or guide_states is not None:
+            self._request_enqueue(past_len or 0, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, None, edits, guide_states)
         elif past_len is not None:
             check(self._L.zg_gpt_generate_from_enqueue(self.h, past_len, *head, opt_p, seed))
         elif fetch:  # the calls that enqueue and fetch in one
@@ -432,34 +465,39 @@ class GPT:
 
     def generate_from(self, past_len, prompts, n_steps, temp=None, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
                       frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0, logit_bias=None,
-                      allowed_token_ids=None, banned_token_ids=None, min_p=0.0):
+                      allowed_token_ids=None, banned_token_ids=None, min_p=0.0, guide_states=None):
         """generate entered at position past_len (zg_gpt_generate_from_enqueue): `prompts` are the new tokens of each row, fed
         behind the past_len cached positions; returns the tokens of positions past_len .. past_len + n_steps - 1 ([batch, n_steps]).
         temp=None: greedy; otherwise the sampler of generate_sample (top_k / top_p as there).  Penalties as generate_sample; the
         tokens below past_len count only when passed as `prior` (one list per row).  logprobs=top_n: as `generate`, for the
         columns past_len .. past_len + n_steps - 1.  stop_token_ids / stop / lookahead: as `generate`; the columns are absolute and
-        what is returned is columns past_len .. end - 1.  logit_bias / allowed_token_ids / banned_token_ids / min_p: as `sample`."""
+        what is returned is columns past_len .. end - 1.  logit_bias / allowed_token_ids / banned_token_ids / min_p: as `sample`.
+        guide_states: as `generate_sample`; a second turn passes the states `generate_fetch_guide_states` and the tokens lead to."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
         edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
         if stop_token_ids is not None or stop is not None:
-            return self._generate_stop(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits)
-        return self._generate(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, edits=edits)
+            return self._generate_stop(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits,
+                                       guide_states)
+        return self._generate(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, edits=edits, guide_states=guide_states)
 
     def generate_sample(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
                         frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0, logit_bias=None,
-                        allowed_token_ids=None, banned_token_ids=None, min_p=0.0):
+                        allowed_token_ids=None, banned_token_ids=None, min_p=0.0, guide_states=None):
         """generate (src/main.zig:322-342) as the reference runs it — every token behind the prompt drawn by GPT.sample — with the
         loop on the device; the tokens of the host loop over `sample(T, tok, temp, seed=seed)`.  top_k / top_p: as `sample`.
         repetition_penalty / presence_penalty / frequency_penalty: on the tokens the row holds when a pick is drawn — `prior` (one
         list per row, optional) followed by the row's prompt and picks so far (zg_gpt_generate_pen_enqueue; defaults: today's call).
         logprobs=top_n: as `generate` — of the row the sampler received, at temperature 1 and before truncation.
         stop_token_ids / stop / lookahead: as `generate`.  logit_bias ({id: value}) / allowed_token_ids / banned_token_ids: edits of
-        every step's row behind the penalties; min_p: min-p truncation (defaults: today's call)."""
+        every step's row behind the penalties; min_p: min-p truncation (defaults: today's call).
+        guide_states (a `guided` handle with a guide loaded): one start state of the loaded automaton per row, None for
+        a row without a guide — every pick of a guided row is one its state allows, and the state follows the picks on the device."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
         edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
         if stop_token_ids is not None or stop is not None:
-            return self._generate_stop(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits)
-        return self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, edits=edits)
+            return self._generate_stop(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits,
+                                       guide_states)
+        return self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, edits=edits, guide_states=guide_states)
 
     def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
                                 frequency_penalty=0.0, prior=None, logprobs=None, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
@@ -471,12 +509,13 @@ class GPT:
 
     # ------------------------------------------------------------------ per-row sampling parameters
     def generate_each(self, prompts, n_steps, rows, past_len=0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0,
-                      logit_bias=None, allowed_token_ids=None, banned_token_ids=None):
+                      logit_bias=None, allowed_token_ids=None, banned_token_ids=None, guide_states=None):
         """generate_sample / generate_from with the sampler parameters taken per row (zg_gpt_generate_each_enqueue): `rows` is one
         dict per row with generate_sample's keyword names — temp, top_k, top_p, min_p, repetition_penalty, presence_penalty,
         frequency_penalty — plus seed; a row's temp 0 / None is greedy (temp 1, top_k 1).  Row b gets, bit for bit, what
         generate_sample with rows[b]'s values for every row gives row b.  prior, logprobs, the stop conditions and the three edit
-        lists are per call and work as there; returns what generate_from returns: columns past_len .. (end or past_len + n_steps) - 1."""
+        lists are per call and work as there; returns what generate_from returns: columns past_len .. (end or past_len + n_steps) - 1.
+        guide_states: as `generate_sample` (zg_gpt_generate_guided_enqueue with the table)."""
         table = _lib.row_sampling(rows)
         mat, lens, stride = self._prompts(prompts)
         edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, 0.0)
@@ -486,7 +525,11 @@ class GPT:
         r = _lib.generate_request(past_len=past_len, prompts=ptr(mat), prompt_stride=stride, prompt_lens=ptr(lens), n_steps=n_steps, prior=pp,
                                   prior_stride=pstride, prior_lens=plens, logprobs=int(logprobs is not None), top_n=int(logprobs or 0),
                                   stop=None if conds is None else C.addressof(conds), edits=None if edits is None else C.addressof(edits[0]))
-        check(self._L.zg_gpt_generate_each_enqueue(self.h, C.addressof(r), C.addressof(table), len(rows)))
+        if guide_states is None:
+            check(self._L.zg_gpt_generate_each_enqueue(self.h, C.addressof(r), C.addressof(table), len(rows)))
+        else:
+            states = self._guide_states(guide_states)
+            check(self._L.zg_gpt_generate_guided_enqueue(self.h, C.addressof(r), C.addressof(table), len(rows), ptr(states)))
         del keep, keep_conds
         n = self.stop_result()[0] - past_len if conds is not None and (conds.n_ids or conds.n_seqs) else n_steps
         out = self.generate_fetch_range(past_len, n)
