@@ -381,6 +381,69 @@ print("ok")
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
 
 
+def test_a_call_that_fails_after_staging_releases_both_arenas():
+    """A call that fails after it has staged something must leave nothing behind: the arenas empty, the twin and the mirrors usable.
+    Own process, ZGPT2_STAGING_MB=1: the device arena and the pinned arena are 1048576 bytes each; offsets round up to 256.
+    (a) Linear 64 -> 8 on 8192 rows: the 2048-byte weight is staged (both arenas at 2048), the 2 MiB input fits neither -> -4.
+    (b) the same weight on 3633 rows: weight 2048 + input 930048 = 932096 in both arenas, the output (116256, stored in place in the
+        pinned arena) ends at 1048352 <= 1048576.  With (a)'s 2048 bytes still held the output would end at 1050400 in the pinned
+        arena and, sent to the device arena instead, at 1050400 there too: the call could only fail.
+    (c) an in-place LayerNorm and a Linear on its result (served from the device twin), then zg_attn_forward on host caches (a
+        mirror), shapes and tolerances of the pool test above."""
+    import subprocess
+    import sys
+
+    code = """
+import os, sys
+sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+import numpy as np
+import oracle
+from zig_gpt2_amd import _lib, ops, synth
+zg = _lib.load(); _lib.check(zg.zg_init(0))
+z = lambda n: np.zeros(n, np.float32)
+k, n = 64, 8
+w = synth.fill_normal(801, n * k, 0, 0.1).reshape(n, k)
+x = synth.fill_normal(802, 8192 * k, 0, 1.0)
+y = z(8192 * n)
+st = zg.zg_linear_forward(k, n, _lib.ptr(w), None, _lib.ptr(x), x.size, _lib.ptr(y), y.size)
+assert st == -4, st  # ZG_ERR_STAGING
+assert b"ZGPT2_STAGING_MB" in zg.zg_last_error(), zg.zg_last_error()
+rows = 3633
+assert 2048 + rows * k * 4 + rows * n * 4 <= (1 << 20) < 2 * 2048 + rows * k * 4 + rows * n * 4
+xb, yb = x[: rows * k], z(rows * n)
+st = zg.zg_linear_forward(k, n, _lib.ptr(w), None, _lib.ptr(xb), xb.size, _lib.ptr(yb), yb.size)
+assert st == 0, (st, zg.zg_last_error())
+ref = (xb.reshape(rows, k).astype(np.float64) @ w.astype(np.float64).T).ravel()
+assert np.abs(yb - ref).max() < 1e-4 * np.abs(ref).max(), np.abs(yb - ref).max()
+e, hds, T = 128, 2, 3
+caw = synth.fill_normal(70, 3 * e * e, 0, 0.08).reshape(3 * e, e); cab = synth.fill_normal(71, 3 * e, 0, 0.05)
+cpw = synth.fill_normal(72, e * e, 0, 0.08).reshape(e, e); cpb = synth.fill_normal(73, e, 0, 0.05)
+g, b = synth.fill_normal(803, e, 1, 0.1), synth.fill_normal(804, e, 0, 0.1)
+h = synth.fill_normal(805, e, 0.2, 1.5)
+exp = oracle.layernorm_forward(e, g, b, h.copy())
+ops.LayerNorm(e, g, b).forward(h)  # the library keeps a device twin of h
+assert np.abs(h - exp).max() < 1e-4 * max(1.0, np.abs(exp).max())
+qkv = z(3 * e)
+ops.Linear(e, 3 * e, caw, cab).forward(h, qkv)  # served from the twin
+ref = h.astype(np.float64) @ caw.astype(np.float64).T + cab
+assert np.abs(qkv - ref).max() < 1e-4 * max(1.0, np.abs(ref).max())
+attn = ops.CausalSelfAttention(hds, e, ops.Linear(e, 3 * e, caw, cab), ops.Linear(e, e, cpw, cpb))
+oref = oracle.CausalSelfAttention(hds, e, caw, cab, cpw, cpb, T)
+kc, vc = z(T * e), z(T * e)
+xs = np.concatenate([h, synth.fill_normal(806, (T - 1) * e, 0, 1.0)]).reshape(T, e)
+for s in range(T):
+    out = z(e)
+    attn.forward(s + 1, xs[s], kc[: (s + 1) * e], vc[: (s + 1) * e], out, z(3 * e), z(e), z(T * e), z(T * e), z(T))
+    exp = oref.forward(s + 1, xs[s])
+    assert np.abs(out - exp).max() < 1e-4 * max(1.0, np.abs(exp).max()), s
+assert np.allclose(kc, oref.k_cache, atol=1e-6) and np.allclose(vc, oref.v_cache, atol=1e-6)
+print("ok")
+"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, ZGPT2_STAGING_MB="1"), capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
+
+
 def test_device_twin_of_an_elementwise_result_is_only_used_for_unchanged_bytes(zg):
     """The op tier keeps the result of an in-place LayerNorm / gelu on a HOST buffer in device memory as well, and the next Linear
     that is handed the same buffer reads that twin instead of uploading the bytes again (in src/main.zig every Linear's input is

@@ -188,12 +188,12 @@ int upload_f32(const float* src, size_t n, void* dst, bool as_bf16, hipStream_t 
             return ZG_OK;
         }
         // chunk through the staging arena
-        const size_t cap = c.stage_cap / 4;
+        const size_t cap = c.stage.cap / 4;
         ZG_REQUIRE(cap > 0, ZG_ERR_STAGING, "no staging arena");
         for (size_t o = 0; o < n; o += cap) {
             const size_t m = (n - o < cap) ? (n - o) : cap;
-            ZG_HIP(hipMemcpyAsync(c.stage, src + o, m * 4, hipMemcpyHostToDevice, s));
-            ZG_TRY(launch_f32_to_bf16(reinterpret_cast<const float*>(c.stage), reinterpret_cast<bf16_t*>(dst) + o, m, s));
+            ZG_HIP(hipMemcpyAsync(c.stage.base, src + o, m * 4, hipMemcpyHostToDevice, s));
+            ZG_TRY(launch_f32_to_bf16(reinterpret_cast<const float*>(c.stage.base), reinterpret_cast<bf16_t*>(dst) + o, m, s));
             ZG_HIP(hipStreamSynchronize(s));
         }
         return ZG_OK;
@@ -210,13 +210,13 @@ int upload_f32(const float* src, size_t n, void* dst, bool as_bf16, hipStream_t 
 int upload_b24(const float* src, size_t n, size_t K, void* dst, bf16_t* planes, hipStream_t s) {
     Ctx& c = ctx();
     ZG_REQUIRE(K > 0 && K % 8 == 0 && n % K == 0 && K <= 65536, ZG_ERR_SHAPE, "B24 matrix: %zu elements in rows of %zu", n, K);
-    const size_t rows = n / K, cap_rows = c.stage_cap / (4 * K);
+    const size_t rows = n / K, cap_rows = c.stage.cap / (4 * K);
     ZG_REQUIRE(cap_rows > 0, ZG_ERR_STAGING, "no staging arena for a %zu-float row", K);
     const hipMemcpyKind kind = is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     for (size_t r = 0; r < rows; r += cap_rows) {
         const size_t m = rows - r < cap_rows ? rows - r : cap_rows;
-        ZG_HIP(hipMemcpyAsync(c.stage, src + r * K, m * K * 4, kind, s));
-        ZG_TRY(launch_f32_to_b24(reinterpret_cast<const float*>(c.stage), m, (int)K, reinterpret_cast<char*>(dst) + r * 3 * K, s));
+        ZG_HIP(hipMemcpyAsync(c.stage.base, src + r * K, m * K * 4, kind, s));
+        ZG_TRY(launch_f32_to_b24(reinterpret_cast<const float*>(c.stage.base), m, (int)K, reinterpret_cast<char*>(dst) + r * 3 * K, s));
         ZG_HIP(hipStreamSynchronize(s));
     }
     if (planes) {

@@ -1,270 +1,9 @@
-// api_ops.hip — runtime + op tier of the C ABI (include/zgpt2.h): one entry point per public decl
-// of the reference's src/ops.zig, same argument meaning, Zig slices passed as (ptr, len).
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-
+// api_ops.hip — op tier of the C ABI (include/zgpt2.h): one entry point per public decl of the reference's src/ops.zig, same
+// argument meaning, Zig slices passed as (ptr, len); zg_gemm_bf16_nt and zg_f32_to_bf16; their launch helpers.  The runtime
+// they stand on — ctx(), the staging scope Call, the device twin and the KV-cache mirrors — is zg_runtime.hip.
 #include "zg_runtime.h"
 
 namespace zg {
-
-static thread_local char g_err[512] = "";
-
-int decode_paths_off() {
-    const char* e = getenv("ZGPT2_DECODE_PATHS_OFF");
-    return e ? atoi(e) : 0;
-}
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-static thread_local char g_kernel[160] = "";
-void note_kernel(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_kernel, sizeof(g_kernel), fmt, ap);
-    va_end(ap);
-}
-
-int hip_fail(hipError_t e, const char* what, const char* file, int line) {
-    set_error("HIP error %d (%s) at %s:%d: %s", (int)e, hipGetErrorString(e), file, line, what);
-    (void)hipGetLastError();
-    return ZG_ERR_HIP;
-}
-
-Ctx& ctx() {
-    static Ctx c;
-    return c;
-}
-
-int require_init() {
-    ZG_REQUIRE(ctx().inited, ZG_ERR_NOT_INITIALIZED, "zg_init has not been called");
-    return ZG_OK;
-}
-
-bool is_device_ptr(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // plain host memory: not an error for us
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-
-// ------------------------------------------------------------------------------------- Call
-Call::Call() : mark_(ctx().stage_off), pin_mark_(ctx().pin_off), s_(ctx().stream) {}
-
-int Call::alloc(size_t bytes, void** dev) {
-    Ctx& c = ctx();
-    const size_t off = (c.stage_off + 255) & ~(size_t)255;
-    ZG_REQUIRE(off + bytes <= c.stage_cap, ZG_ERR_STAGING,
-               "host buffers of this call need %zu more bytes than the %zu-byte staging arena "
-               "(raise ZGPT2_STAGING_MB / zg_init_ex, pass device pointers, or zg_register_tensor the weights)",
-               off + bytes - c.stage_cap, c.stage_cap);
-    *dev = c.stage + off;
-    c.stage_off = off + bytes;
-    return ZG_OK;
-}
-
-char* Call::pin_alloc(size_t bytes) {  // nullptr: does not fit (the caller takes the pageable path)
-    Ctx& c = ctx();
-    const size_t off = (c.pin_off + 255) & ~(size_t)255;
-    if (c.pin == nullptr || off + bytes > c.pin_cap) return nullptr;
-    c.pin_off = off + bytes;
-    return c.pin + off;
-}
-
-size_t Call::arena_left() const {
-    const Ctx& c = ctx();
-    const size_t off = (c.stage_off + 255) & ~(size_t)255;
-    return off < c.stage_cap ? c.stage_cap - off : 0;
-}
-
-// what a kernel may touch in place over PCIe: a few wavefronts' worth of traffic, not a matrix
-static constexpr size_t kZeroCopyMax = (size_t)1 << 20;
-
-int Call::stage_in(const void* p, size_t bytes, bool is_param, bool once, const void** dev) {
-    if (bytes == 0 || p == nullptr) {
-        *dev = p;
-        return ZG_OK;
-    }
-    // Only parameters may come from the registry, and only on an exact (pointer, size) match: the key is a bare
-    // host address, and host code frees and reuses addresses (the reference's tests allocate same-sized buffers
-    // with page_allocator right after freeing the weights).
-    if (is_param) {
-        auto it = ctx().registry.find(p);
-        if (it != ctx().registry.end() && it->second.bytes == bytes) {
-            *dev = it->second.dev;
-            return ZG_OK;
-        }
-    }
-    if (is_device_ptr(p)) {
-        *dev = p;
-        return ZG_OK;
-    }
-    {   // the previous op's result, still on the device?  (same buffer, same length, and the caller has not changed a byte of it)
-        Ctx& c = ctx();
-        if (!is_param && !once && p == c.shadow_ptr && bytes == c.shadow_bytes && memcmp(p, c.shadow_host, bytes) == 0) {
-            *dev = c.shadow_dev;
-            return ZG_OK;
-        }
-    }
-    char* pin = pin_alloc(bytes);
-    if (pin != nullptr) {
-        memcpy(pin, p, bytes);
-        if (once && bytes <= kZeroCopyMax) {
-            *dev = pin;
-            return ZG_OK;
-        }
-    }
-    void* d = nullptr;
-    ZG_TRY(alloc(bytes, &d));
-    ZG_HIP(hipMemcpyAsync(d, pin ? pin : p, bytes, hipMemcpyHostToDevice, s_));
-    *dev = d;
-    return ZG_OK;
-}
-
-int Call::stage_out(void* p, size_t bytes, bool copy_in, bool once, void** dev) {
-    if (bytes == 0 || p == nullptr) {
-        *dev = p;
-        return ZG_OK;
-    }
-    if (is_device_ptr(p)) {
-        *dev = p;
-        return ZG_OK;
-    }
-    ZG_REQUIRE(n_outs_ < 24, ZG_ERR_STAGING, "too many staged outputs");
-    char* pin = pin_alloc(bytes);
-    if (pin != nullptr && copy_in) memcpy(pin, p, bytes);
-    if (pin != nullptr && once && bytes <= kZeroCopyMax) {  // the kernel stores straight into the pinned slot
-        outs_[n_outs_++] = Out{p, nullptr, pin, bytes};
-        *dev = pin;
-        return ZG_OK;
-    }
-    void* d = nullptr;
-    ZG_TRY(alloc(bytes, &d));
-    if (copy_in) ZG_HIP(hipMemcpyAsync(d, pin ? pin : p, bytes, hipMemcpyHostToDevice, s_));
-    outs_[n_outs_++] = Out{p, d, pin, bytes};
-    *dev = d;
-    return ZG_OK;
-}
-
-int Call::also_out(void* host, const void* dev_part, size_t bytes) {
-    if (bytes == 0 || host == nullptr || is_device_ptr(host)) return ZG_OK;
-    ZG_REQUIRE(n_outs_ < 24, ZG_ERR_STAGING, "too many staged outputs");
-    // inside an output that travels through the pinned arena anyway: the CPU copies from there, no second transfer
-    const char* d = static_cast<const char*>(dev_part);
-    for (int i = 0; i < n_outs_; ++i) {
-        const char* base = static_cast<const char*>(outs_[i].dev);
-        if (base != nullptr && outs_[i].pin != nullptr && d >= base && d + bytes <= base + outs_[i].bytes) {
-            outs_[n_outs_++] = Out{host, nullptr, outs_[i].pin + (d - base), bytes};
-            return ZG_OK;
-        }
-    }
-    outs_[n_outs_++] = Out{host, const_cast<void*>(dev_part), pin_alloc(bytes), bytes};
-    return ZG_OK;
-}
-
-void Call::reserve(unsigned** flag, unsigned* seq) {
-    Ctx& c = ctx();
-    *flag = nullptr;
-    *seq = 0;
-    if (c.done_flag == nullptr || c.calls_since_sync + 1 >= 256) return;
-    for (int i = 0; i < n_outs_; ++i)
-        if (outs_[i].dev != nullptr) return;  // a transfer must follow the kernel: its completion is not the call's
-    reserved_seq_ = ++c.done_seq;
-    reserved_ = true;
-    *flag = c.done_flag;
-    *seq = reserved_seq_;
-}
-
-int Call::finish() {
-    Ctx& c = ctx();
-    const bool poll = c.done_flag != nullptr && c.calls_since_sync + 1 < 256;
-    // Outputs that live in device memory.  A few small ones (the common case: _qkv and _q of an attention call) leave for the pinned
-    // arena in the SAME launch that announces the call's completion; anything else by DMA — outputs that lie back to back in both
-    // arenas (consecutive out() calls of 256-byte multiples) in one transfer.
-    CopySegs segs{};
-    size_t seg_bytes = 0;
-    bool fused = poll && !(reserved_ && announced_);
-    for (int i = 0; i < n_outs_ && fused; ++i) {
-        if (outs_[i].dev == nullptr) continue;
-        if (outs_[i].pin == nullptr || segs.n == 4 || (outs_[i].bytes & 3) || outs_[i].bytes > (64u << 10)) fused = false;
-        else {
-            segs.src[segs.n] = outs_[i].dev;
-            segs.dst[segs.n] = outs_[i].pin;
-            segs.bytes[segs.n++] = (unsigned)outs_[i].bytes;
-            seg_bytes += outs_[i].bytes;
-        }
-    }
-    fused = fused && segs.n > 0 && seg_bytes <= (64u << 10);
-    if (!fused)
-        for (int i = 0; i < n_outs_; ++i) {
-            if (outs_[i].dev == nullptr) continue;
-            size_t bytes = outs_[i].bytes;
-            int j = i;
-            while (outs_[i].pin != nullptr && j + 1 < n_outs_ && outs_[j + 1].dev != nullptr && outs_[j + 1].pin != nullptr &&
-                   static_cast<char*>(outs_[i].dev) + bytes == static_cast<char*>(outs_[j + 1].dev) && outs_[i].pin + bytes == outs_[j + 1].pin) {
-                bytes += outs_[j + 1].bytes;
-                ++j;
-            }
-            ZG_HIP(hipMemcpyAsync(outs_[i].pin ? (void*)outs_[i].pin : outs_[i].host, outs_[i].dev, bytes, hipMemcpyDeviceToHost, s_));
-            i = j;
-        }
-    // Op-tier calls are synchronous on return: the reference's host code reads the buffers next.  The host polls a pinned
-    // completion word stored in stream order behind the call's work (cheaper than the runtime's wake-up); every 256th call —
-    // and any call whose word does not arrive — drains the stream the ordinary way, which also surfaces asynchronous errors.
-    bool drained = false, polled = false;
-    if (c.done_flag != nullptr && ++c.calls_since_sync < 256) {
-        // (a reserved sequence number nobody announced is simply skipped: the next one is larger)
-        const bool own = reserved_ && announced_;
-        const unsigned seq = own ? reserved_seq_ : ++c.done_seq;
-        const int st = own ? ZG_OK : fused ? launch_copy_out_done(segs, c.done_flag, seq, s_) : launch_done_flag(c.done_flag, seq, s_);
-        polled = st == ZG_OK;
-        if (st == ZG_OK)
-            for (long spins = 0; spins < (1L << 24) && !drained; ++spins) {
-                drained = __atomic_load_n(c.done_flag, __ATOMIC_ACQUIRE) == seq;
-                if (!drained) __builtin_ia32_pause();
-            }
-        else if (fused)
-            return st;  // (the outputs have not left: the call failed)
-    }
-    if (!drained) {
-        if (polled) ++c.done_missed;
-        ZG_HIP(hipStreamSynchronize(s_));
-        c.calls_since_sync = 0;
-    }
-    for (int i = 0; i < n_outs_; ++i)
-        if (outs_[i].pin != nullptr) memcpy(outs_[i].host, outs_[i].pin, outs_[i].bytes);
-    c.stage_off = mark_;
-    c.pin_off = pin_mark_;
-    n_outs_ = 0;
-    reserved_ = announced_ = false;
-    return ZG_OK;
-}
-
-// A failed call must still release the arenas.
-struct CallGuard {
-    Call& c;
-    bool done = false;
-    explicit CallGuard(Call& cc) : c(cc) {}
-    ~CallGuard() {
-        if (!done) {
-            (void)hipStreamSynchronize(c.stream());
-            ctx().stage_off = 0;
-            ctx().pin_off = 0;
-        }
-    }
-};
 
 // Linear.forward for batch >= 16 on the matrix cores (ops.zig:21-46 with M = inputs.len / in_features, :22).
 // The op tier is fp32 in, fp32 out, arbitrary fp32 weights: both operands are split EXACTLY into three bf16
@@ -297,28 +36,35 @@ static int linear_mfma(Call& call, size_t in_f, size_t out_f, const float* w, co
     return launch_gemm_planes(xp, wp, bias, y, (int)m, (int)out_f, pl, (int)out_f, false, false, call.stream());
 }
 
+// One GEMV launch of the op tier: fp32 weights, no prologue, y[M][N] = W[N][K] x[M][K] (+ bias) (+ resid under EPI_RESIDUAL).
+static int op_gemv(const float* W, const float* bias, size_t N, size_t K, size_t M, const float* x, size_t x_stride, float* y, size_t y_stride,
+                   int epilogue, const float* resid, size_t resid_stride, hipStream_t s) {
+    GemvArgs a{};
+    a.W = W;
+    a.bias = bias;
+    a.N = (int)N;
+    a.K = (int)K;
+    a.M = (int)M;
+    a.prologue = PRO_NONE;
+    a.epilogue = epilogue;
+    a.x = x;
+    a.x_stride = (int)x_stride;
+    a.y = y;
+    a.y_stride = (int)y_stride;
+    a.resid = resid;
+    a.resid_stride = (int)resid_stride;
+    a.zero = ctx().d_zero;
+    return launch_gemv(a, gemv_plan(a, WT_F32), WT_F32, s);
+}
+
 static int linear_device(size_t in_f, size_t out_f, const float* w, const float* bias, const float* x,
                          size_t m, float* y, hipStream_t s) {
     if (m == 0 || out_f == 0) return ZG_OK;
     ZG_REQUIRE(in_f > 0 && in_f <= 8192, ZG_ERR_UNSUPPORTED, "Linear: in_features %zu outside 1..8192", in_f);
     size_t mb = 8;
     while (mb > 1 && (mb * in_f + 8 * mb + 64) * sizeof(float) > 160 * 1024) mb >>= 1;
-    for (size_t m0 = 0; m0 < m; m0 += mb) {
-        GemvArgs a{};
-        a.W = w;
-        a.bias = bias;
-        a.N = (int)out_f;
-        a.K = (int)in_f;
-        a.M = (int)((m - m0 < mb) ? (m - m0) : mb);
-        a.prologue = PRO_NONE;
-        a.epilogue = EPI_STORE;
-        a.x = x + m0 * in_f;
-        a.x_stride = (int)in_f;
-        a.y = y + m0 * out_f;
-        a.y_stride = (int)out_f;
-        a.zero = ctx().d_zero;
-        ZG_TRY(launch_gemv(a, gemv_plan(a, WT_F32), WT_F32, s));
-    }
+    for (size_t m0 = 0; m0 < m; m0 += mb)
+        ZG_TRY(op_gemv(w, bias, out_f, in_f, (m - m0 < mb) ? (m - m0) : mb, x + m0 * in_f, in_f, y + m0 * out_f, out_f, EPI_STORE, nullptr, 0, s));
     return ZG_OK;
 }
 
@@ -348,22 +94,9 @@ static int linear_device_wide(Call& call, size_t in_f, size_t out_f, const float
             for (size_t n0 = 0; n0 < out_f; n0 += rows) {
                 const size_t nb = out_f - n0 < rows ? out_f - n0 : rows;
                 ZG_HIP(hipMemcpy2DAsync(wc, kc * 4, w + n0 * in_f + k0, in_f * 4, kc * 4, nb, hipMemcpyDeviceToDevice, s));
-                GemvArgs a{};
-                a.W = wc;
-                a.bias = (k0 == 0 && bias) ? bias + n0 : nullptr;
-                a.N = (int)nb;
-                a.K = (int)kc;
-                a.M = (int)mb;
-                a.prologue = PRO_NONE;
-                a.epilogue = k0 == 0 ? EPI_STORE : EPI_RESIDUAL;
-                a.x = xc;
-                a.x_stride = (int)kc;
-                a.y = y + m0 * out_f + n0;
-                a.y_stride = (int)out_f;
-                a.resid = k0 == 0 ? nullptr : a.y;
-                a.resid_stride = (int)out_f;
-                a.zero = ctx().d_zero;
-                ZG_TRY(launch_gemv(a, gemv_plan(a, WT_F32), WT_F32, s));
+                float* yb = y + m0 * out_f + n0;
+                ZG_TRY(op_gemv(wc, (k0 == 0 && bias) ? bias + n0 : nullptr, nb, kc, mb, xc, kc, yb, out_f, k0 == 0 ? EPI_STORE : EPI_RESIDUAL,
+                               k0 == 0 ? nullptr : yb, out_f, s));
             }
         }
     }
@@ -372,11 +105,11 @@ static int linear_device_wide(Call& call, size_t in_f, size_t out_f, const float
 
 static int attn_core(const float* q, const float* k, const float* v, long stride_b, long stride_h,
                      long stride_t, size_t batch, size_t n_heads, size_t seq_len, float* out, hipStream_t s, size_t head_dim = 64) {
-    Ctx& c = ctx();
+    const auto& part = ctx().attn_part;
     if (batch == 0 || n_heads == 0) return ZG_OK;  // k.len below one sequence: the reference's loop over the batch does nothing (ops.zig:259-261)
     const int splits = (int)((seq_len + kAttnChunk - 1) / kAttnChunk);
     // (a shape whose split partials do not fit the op tier's buffer — very long sequences x many heads — takes the general kernel too)
-    if (head_dim != 64 || batch * n_heads * splits * kPartStride > c.attn_part_floats)
+    if (head_dim != 64 || batch * n_heads * splits * kPartStride > part.floats)
         return launch_attn_any_dim(q, k, v, stride_b, stride_h, stride_t, (int)batch, (int)n_heads, (int)head_dim, (int)seq_len, out, s);
     AttnArgs a{};
     a.q = q;
@@ -392,9 +125,9 @@ static int attn_core(const float* q, const float* k, const float* v, long stride
     a.seq_len = (int)seq_len;
     a.t_hi = (int)seq_len;
     a.max_splits = splits;
-    a.part = c.attn_part;
+    a.part = part.buf;
     ZG_TRY(launch_attn_decode(a, s));
-    return launch_attn_merge(c.attn_part, (int)batch, (int)n_heads, 64, splits, (int)seq_len, out, s);
+    return launch_attn_merge(part.buf, (int)batch, (int)n_heads, 64, splits, (int)seq_len, out, s);
 }
 
 }  // namespace zg
@@ -402,147 +135,6 @@ static int attn_core(const float* q, const float* k, const float* v, long stride
 using namespace zg;
 
 extern "C" {
-
-const char* zg_last_error(void) { return zg::g_err; }
-
-static size_t env_mb(const char* name, size_t dflt) {
-    if (const char* e = getenv(name)) {
-        const long v = atol(e);
-        if (v >= 0) return (size_t)v;
-    }
-    return dflt;
-}
-
-int zg_init_ex(int device, size_t staging_bytes) {
-    Ctx& c = ctx();
-    if (c.inited) {
-        ZG_REQUIRE(c.device == device, ZG_ERR_ARG, "already initialised on device %d", c.device);
-        return ZG_OK;
-    }
-    int n = 0;
-    ZG_HIP(hipGetDeviceCount(&n));
-    ZG_REQUIRE(device >= 0 && device < n, ZG_ERR_ARG, "device %d out of range (%d visible)", device, n);
-    ZG_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    ZG_HIP(hipGetDeviceProperties(&prop, device));
-    ZG_REQUIRE(strncmp(prop.gcnArchName, "gfx950", 6) == 0, ZG_ERR_UNSUPPORTED,
-               "libzgpt2_hip is built for gfx950 (MI355X) only; device %d is %s", device, prop.gcnArchName);
-    ZG_HIP(hipStreamCreateWithFlags(&c.own_stream, hipStreamNonBlocking));
-    c.stream = c.own_stream;
-    c.stage_cap = staging_bytes;
-    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&c.stage), c.stage_cap));
-    // pinned twin of the staging arena for the small host buffers of src/main.zig's State (a few KB each; the logits 200 KB)
-    c.pin_cap = std::min(staging_bytes, env_mb("ZGPT2_PINNED_MB", 32) << 20);
-    if (c.pin_cap > 0) ZG_HIP(hipHostMalloc(reinterpret_cast<void**>(&c.pin), c.pin_cap, hipHostMallocDefault));
-    c.pin_off = 0;
-    // device pool for the mirrors of caller-owned KV caches (zg_attn_forward): 124M needs 75 MB, GPT-2 XL 630 MB of 288 GB
-    c.kv_pool_cap = env_mb("ZGPT2_KV_MIRROR_MB", 1024) << 20;
-    if (c.kv_pool_cap > 0) ZG_HIP(hipMalloc(reinterpret_cast<void**>(&c.kv_pool), c.kv_pool_cap));
-    c.kv_pool_off = 0;
-    c.shadow_cap = (size_t)1 << 20;
-    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&c.shadow_dev), c.shadow_cap));
-    c.shadow_host = static_cast<char*>(malloc(c.shadow_cap));
-    ZG_REQUIRE(c.shadow_host != nullptr, ZG_ERR_HIP, "zg_init: out of host memory");
-    c.shadow_ptr = nullptr;
-    c.shadow_bytes = 0;
-    ZG_HIP(hipHostMalloc(reinterpret_cast<void**>(&c.d_flag), 64, hipHostMallocDefault));
-    *c.d_flag = 0;
-    c.done_flag = reinterpret_cast<unsigned*>(c.d_flag) + 8;
-    *c.done_flag = 0;
-    c.done_seq = c.calls_since_sync = 0;
-    if (env_mb("ZGPT2_OP_POLL", 1) == 0) c.done_flag = nullptr;  // measurement switch: drain every op-tier call with hipStreamSynchronize
-    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&c.d_zero), 64));
-    ZG_HIP(hipMemset(c.d_zero, 0, 64));
-    c.attn_part_floats = (size_t)4 << 20;
-    ZG_HIP(hipMalloc(reinterpret_cast<void**>(&c.attn_part), c.attn_part_floats * sizeof(float)));
-    c.stage_off = 0;
-    c.device = device;
-    c.inited = true;
-    return ZG_OK;
-}
-
-int zg_init(int device) {
-    size_t mb = 512;
-    if (const char* e = getenv("ZGPT2_STAGING_MB")) {
-        const long v = atol(e);
-        if (v > 0) mb = (size_t)v;
-    }
-    return zg_init_ex(device, mb << 20);
-}
-
-int zg_shutdown(void) {
-    Ctx& c = ctx();
-    if (!c.inited) return ZG_OK;
-    (void)hipStreamSynchronize(c.stream);
-    for (auto& kv : c.registry) (void)hipFree(kv.second.dev);
-    c.registry.clear();
-    c.kv_mirrors.clear();
-    (void)hipFree(c.stage);
-    if (c.pin) (void)hipHostFree(c.pin);
-    if (c.kv_pool) (void)hipFree(c.kv_pool);
-    if (c.shadow_dev) (void)hipFree(c.shadow_dev);
-    free(c.shadow_host);
-    (void)hipHostFree(c.d_flag);
-    (void)hipFree(c.d_zero);
-    (void)hipFree(c.attn_part);
-    (void)hipStreamDestroy(c.own_stream);
-    c = Ctx();
-    return ZG_OK;
-}
-
-int zg_set_stream(void* hip_stream) {
-    ZG_TRY(require_init());
-    Ctx& c = ctx();
-    ZG_HIP(hipStreamSynchronize(c.stream));
-    c.stream = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c.own_stream;
-    return ZG_OK;
-}
-
-int zg_synchronize(void) {
-    ZG_TRY(require_init());
-    ZG_HIP(hipStreamSynchronize(ctx().stream));
-    return ZG_OK;
-}
-
-int zg_register_tensor(const float* host_ptr, size_t len) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(host_ptr && len, ZG_ERR_ARG, "zg_register_tensor: null/empty tensor");
-    Ctx& c = ctx();
-    if (is_device_ptr(host_ptr)) return ZG_OK;
-    auto it = c.registry.find(host_ptr);
-    if (it != c.registry.end()) {
-        (void)hipFree(it->second.dev);
-        c.registry.erase(it);
-    }
-    void* d = nullptr;
-    ZG_HIP(hipMalloc(&d, len * sizeof(float)));
-    ZG_HIP(hipMemcpy(d, host_ptr, len * sizeof(float), hipMemcpyHostToDevice));
-    c.registry[host_ptr] = Registered{d, len * sizeof(float)};
-    return ZG_OK;
-}
-
-int zg_unregister_tensor(const float* host_ptr) {
-    ZG_TRY(require_init());
-    Ctx& c = ctx();
-    c.kv_mirrors.erase(host_ptr);  // (a KV-cache mirror keyed by this address: the next zg_attn_forward uploads the cache again)
-    auto it = c.registry.find(host_ptr);
-    if (it == c.registry.end()) return ZG_OK;  // never registered (or a device pointer): nothing to drop
-    ZG_HIP(hipStreamSynchronize(c.stream));
-    (void)hipFree(it->second.dev);
-    c.registry.erase(it);
-    return ZG_OK;
-}
-
-int zg_unregister_all(void) {
-    ZG_TRY(require_init());
-    Ctx& c = ctx();
-    ZG_HIP(hipStreamSynchronize(c.stream));
-    for (auto& kv : c.registry) (void)hipFree(kv.second.dev);
-    c.registry.clear();
-    c.kv_mirrors.clear();
-    c.kv_pool_off = 0;  // the pool is a bump allocator: it empties when every mirror is gone
-    return ZG_OK;
-}
 
 // ------------------------------------------------------------------------------ Linear
 int zg_linear_forward(size_t in_features, size_t out_features, const float* weight,
@@ -557,7 +149,6 @@ int zg_linear_forward(size_t in_features, size_t out_features, const float* weig
     ZG_REQUIRE(outputs_len >= batch * out_features, ZG_ERR_SHAPE,
                "Linear: outputs.len %zu < batch %zu * out_features %zu", outputs_len, batch, out_features);
     Call call;
-    CallGuard guard(call);
     const float *w, *b, *x;
     float* y;
     ZG_TRY(call.param(weight, in_features * out_features, &w));
@@ -569,9 +160,7 @@ int zg_linear_forward(size_t in_features, size_t out_features, const float* weig
         ZG_TRY(linear_mfma(call, in_features, out_features, w, b, x, batch, y));
     else
         ZG_TRY(linear_device_wide(call, in_features, out_features, w, b, x, batch, y));
-    ZG_TRY(call.finish());
-    guard.done = true;
-    return ZG_OK;
+    return call.finish();
 }
 
 // ------------------------------------------------------------------------------ MFMA GEMM
@@ -586,137 +175,14 @@ int zg_gemm_bf16_nt(const uint16_t* A, const uint16_t* B, const float* bias_or_n
                                ctx().stream);
 }
 
-int zg_debug_prefill_linear(const uint16_t* A, const uint16_t* W, const float* bias, void* C, size_t M, size_t N, size_t K, int epilogue,
-                            int force_kernel, int slices, float* ws, size_t ws_floats) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(A && W && C && is_device_ptr(A) && is_device_ptr(W) && is_device_ptr(C) && (!bias || is_device_ptr(bias)) && (!ws || is_device_ptr(ws)),
-               ZG_ERR_ARG, "debug_prefill_linear: device pointers");
-    ZG_REQUIRE(M >= 1 && M < (1u << 30) && N >= 64 && N < (1u << 30) && K >= 64 && K < (1u << 30) && epilogue >= 0 && epilogue <= 2 && force_kernel >= 0 &&
-                   force_kernel <= 2 && slices >= 0,
-               ZG_ERR_ARG, "debug_prefill_linear: arguments");
-    const int epi = epilogue == 0 ? PF_F32 : epilogue == 1 ? PF_RESID : PF_GELU_SPLIT;
-    const PrefillForce force{force_kernel, slices};
-    return launch_prefill_gemm(A, W, bias, C, (int)M, (int)N, (int)K, epi == PF_GELU_SPLIT ? 0 : (int)N, epi, ws, ws_floats, nullptr, ctx().stream, nullptr,
-                               kSplit, &force);
-}
-
-int zg_debug_attn_prefill(const float* qkv, uint16_t* out, size_t batch, size_t n_tokens, size_t n_embed, size_t n_heads, const float* k_cache,
-                          const float* v_cache, size_t ctx_len, float* ws, size_t ws_floats, int key_tiles) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(qkv && out && is_device_ptr(qkv) && is_device_ptr(out) && (!k_cache || (v_cache && is_device_ptr(k_cache) && is_device_ptr(v_cache))) &&
-                   (!ws || is_device_ptr(ws)),
-               ZG_ERR_ARG, "debug_attn_prefill: device pointers");
-    ZG_REQUIRE(batch >= 1 && n_tokens >= 1 && n_heads >= 1 && n_embed == 64 * n_heads && batch * n_tokens < (1u << 24) && n_embed < (1u << 16) && (!k_cache || ctx_len >= n_tokens) &&
-                   key_tiles >= 0 && key_tiles <= 255,
-               ZG_ERR_ARG, "debug_attn_prefill: arguments");
-    return launch_attn_prefill(qkv, out, (int)batch, 0, (int)n_tokens, (int)n_embed, (int)n_heads, ws, ws_floats, PrefillKv{k_cache, v_cache, 0, 0, (int)ctx_len},
-                               ctx().stream, key_tiles);
-}
-
-int zg_debug_attn_prefill_at(const float* qkv, uint16_t* out, size_t batch, size_t past_len, size_t n_tokens, size_t n_embed, size_t n_heads,
-                             const void* k_cache, const void* v_cache, int kv_mode, size_t ctx_len, float* ws, size_t ws_floats, int key_tiles) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(qkv && out && k_cache && v_cache && is_device_ptr(qkv) && is_device_ptr(out) && is_device_ptr(k_cache) && is_device_ptr(v_cache) &&
-                   (!ws || is_device_ptr(ws)),
-               ZG_ERR_ARG, "debug_attn_prefill_at: device pointers");
-    ZG_REQUIRE(batch >= 1 && n_tokens >= 1 && n_heads >= 1 && n_embed == 64 * n_heads && batch * n_tokens < (1u << 24) && n_embed < (1u << 16) &&
-                   ctx_len < (1u << 22) && past_len + n_tokens <= ctx_len && kv_mode >= 0 && kv_mode <= 2 && key_tiles >= 0 && key_tiles <= 255,
-               ZG_ERR_ARG, "debug_attn_prefill_at: arguments");
-    return launch_attn_prefill(qkv, out, (int)batch, (int)past_len, (int)n_tokens, (int)n_embed, (int)n_heads, ws, ws_floats,
-                               PrefillKv{k_cache, v_cache, kv_mode, batch * ctx_len * n_embed * 2, (int)ctx_len}, ctx().stream, key_tiles);
-}
-
-int zg_debug_prefill_route(int force_kernel, int slices) {
-    ZG_REQUIRE(force_kernel >= 0 && (force_kernel <= 2 || force_kernel >= 16) && slices >= 0, ZG_ERR_ARG, "debug_prefill_route: arguments");
-    prefill_force_route(force_kernel, slices);
-    return ZG_OK;
-}
-
-unsigned long long zg_debug_gemm_launches(void) { return gemm_mfma_launch_count(); }
-int zg_debug_gemm_stamps(unsigned long long* out, size_t n_words) { return gemm_debug_stamps(out, n_words); }
-// The op tier's completion word in front of its wrap / what became of it (tests; include/zgpt2.h).  The library stream is drained
-// first: no call is in flight whose number the word still has to take.
-int zg_debug_ops_set_done_seq(unsigned seq) {
-    ZG_TRY(require_init());
-    Ctx& c = ctx();
-    ZG_HIP(hipStreamSynchronize(c.stream));
-    c.done_seq = seq;
-    return ZG_OK;
-}
-int zg_debug_ops_done_state(unsigned long long* out, size_t n_out) {
-    ZG_TRY(require_init());
-    ZG_REQUIRE(out && n_out >= 3, ZG_ERR_ARG, "ops_done_state: need 3 words");
-    Ctx& c = ctx();
-    ZG_HIP(hipStreamSynchronize(c.stream));
-    out[0] = c.done_seq;
-    out[1] = c.done_flag ? __atomic_load_n(c.done_flag, __ATOMIC_ACQUIRE) : 0u;
-    out[2] = c.done_missed;
-    return ZG_OK;
-}
-int zg_debug_last_kernel(char* out, size_t n) {
-    if (!out || n == 0) return ZG_ERR_ARG;
-    snprintf(out, n, "%s", zg::g_kernel);
-    return ZG_OK;
-}
-
-// Plans a described decode-regime Linear (gemv_plan) without a GPU or zg_init.  Only null / non-null of the operands matters to
-// the planner, so present ones are any non-null address; nothing is dereferenced.
-int zg_debug_gemv_plan(int M, int N, int K, int prologue, int epilogue, int weight_type, unsigned operands, int sk_tiles, int t_hi, int* out,
-                       size_t n_out) {
-    ZG_REQUIRE(out != nullptr && n_out >= ZG_GEMV_PLAN_INTS, ZG_ERR_ARG, "debug_gemv_plan: %d ints of output", ZG_GEMV_PLAN_INTS);
-    static float some[2];
-    const bool ragged = (operands & ZG_PLAN_RAGGED_STRIDES) != 0;  // row strides wider than the rows
-    GemvArgs a{};
-    a.M = M;
-    a.N = N;
-    a.K = K;
-    a.prologue = prologue;
-    a.epilogue = epilogue;
-    a.head_dim = 64;
-    a.t_hi = t_hi;
-    a.x_stride = K + (ragged ? 8 : 0);
-    a.y_stride = a.resid_stride = N + (ragged ? 8 : 0);
-    if (operands & ZG_PLAN_LN_FOLDED) a.ln_c2 = a.ln_c3 = some;
-    if (operands & ZG_PLAN_PLANES_IN) a.pl_in = reinterpret_cast<const bf16_t*>(some);
-    if (operands & ZG_PLAN_STATS_IN) a.st_in = some;
-    if (operands & ZG_PLAN_SPLIT_K) {
-        a.sk_ws = some;
-        a.sk_cnt = reinterpret_cast<int*>(some);
-        a.sk_tiles = sk_tiles;
-    }
-    const GemvPlan p = gemv_plan(a, weight_type);
-    const int v[ZG_GEMV_PLAN_INTS] = {p.route, p.grid, p.kslices, p.block, p.lds, p.mt, p.lpr, p.cpl, p.ks, p.nw, p.line, p.gpl, p.alias, p.pairs,
-                                      p.steps, p.rows_per_wave, p.waves_per_wg, p.row_group, p.rows_per_wg, p.pf_tiles, p.supported,
-                                      p.can_take_planes, p.can_write_planes, p.pl4_with_planes};
-    memcpy(out, v, sizeof(v));
-    return ZG_OK;
-}
-
-// Plans a described whole-prompt Linear (prefill_gemm_plan) without a GPU or zg_init.  Presence flags stand in for the operands;
-// nothing is dereferenced.  The process-wide pin of zg_debug_prefill_route is not read: the force is this call's.
-int zg_debug_prefill_plan(int M, int N, int K, int ldc, int epilogue, int nsplit, size_t ws_floats, unsigned operands, size_t sk_ws_bytes,
-                          unsigned sk_flags_words, int force_kernel, int force_slices, int* out, size_t n_out) {
-    ZG_REQUIRE(out != nullptr && n_out >= ZG_PREFILL_PLAN_INTS, ZG_ERR_ARG, "debug_prefill_plan: %d ints of output", ZG_PREFILL_PLAN_INTS);
-    PrefillGemmShape sh{M, N, K, ldc, epilogue, nsplit, ws_floats, (operands & ZG_PFPLAN_WS) != 0, (operands & ZG_PFPLAN_LN) != 0,
-                        (operands & ZG_PFPLAN_QKV) ? N / 3 : 0, (operands & ZG_PFPLAN_SK_WS) != 0, (operands & ZG_PFPLAN_SK_FLAGS) != 0, sk_ws_bytes,
-                        sk_flags_words, PrefillForce{force_kernel, force_slices}};
-    const PrefillGemmPlan p = prefill_gemm_plan(sh);
-    static_assert(ZG_PREFILL_PLAN_INTS == 21, "prefill_plan_ints packs 21");
-    prefill_plan_ints(p, out);
-    return ZG_OK;
-}
-
 int zg_f32_to_bf16(const float* src, uint16_t* dst_device, size_t len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(src && dst_device && is_device_ptr(dst_device), ZG_ERR_ARG, "f32_to_bf16: bad argument");
     Call call;
-    CallGuard guard(call);
     const float* s;
     ZG_TRY(call.in(src, len, &s));
     ZG_TRY(launch_f32_to_bf16(s, dst_device, len, call.stream()));
-    ZG_TRY(call.finish());
-    guard.done = true;
-    return ZG_OK;
+    return call.finish();
 }
 
 // ------------------------------------------------------------------------------ Embedding
@@ -727,21 +193,14 @@ int zg_embedding_forward(size_t emb_dim, const float* weight, size_t weight_len,
     ZG_REQUIRE(embeddings_len >= idxs_len * emb_dim, ZG_ERR_SHAPE,
                "Embedding: embeddings.len %zu < %zu indices * emb_dim %zu", embeddings_len, idxs_len, emb_dim);
     Call call;
-    CallGuard guard(call);
     const float* w;
     const size_t* ix;
     float* out;
     ZG_TRY(call.param(weight, weight_len, &w));
     ZG_TRY(call.in_once(idxs, idxs_len, &ix));
     ZG_TRY(call.out_once(embeddings, idxs_len * emb_dim, &out));
-    unsigned* df;
-    unsigned ds;
-    bool own = false;
-    call.reserve(&df, &ds);
-    ZG_TRY(launch_embedding(w, emb_dim, ix, idxs_len, weight_len / emb_dim, out, ctx().d_flag, call.stream(), df, ds, &own));
-    call.announced(own);
+    ZG_TRY(launch_embedding(w, emb_dim, ix, idxs_len, weight_len / emb_dim, out, ctx().d_flag, call.stream(), call.reserve()));
     ZG_TRY(call.finish());
-    guard.done = true;
     if (*static_cast<volatile int*>(ctx().d_flag)) {  // raised by the kernel (pinned host word), read behind the call's drain
         *ctx().d_flag = 0;
         set_error("embedding: index out of range (>= %zu rows)", weight_len / emb_dim);
@@ -759,29 +218,17 @@ int zg_layernorm_forward(size_t n_features, const float* weight, const float* bi
     ZG_REQUIRE(inputs_len == rows * n_features, ZG_ERR_SHAPE,
                "LayerNorm: inputs.len %zu is not a multiple of n_features %zu", inputs_len, n_features);
     Call call;
-    CallGuard guard(call);
     const float *g, *b;
     float* x;
     ZG_TRY(call.param(weight, n_features, &g));
     ZG_TRY(call.param(bias, n_features, &b));
     ZG_TRY(call.inout_once(inputs, inputs_len, &x));
-    unsigned* df;
-    unsigned ds;
-    bool own = false;
-    call.reserve(&df, &ds);
-    Ctx& c = ctx();
-    const size_t bytes = inputs_len * sizeof(float);
-    const bool twin = static_cast<void*>(x) != static_cast<void*>(inputs) && bytes <= c.shadow_cap;  // a host buffer: keep a device twin of the result
-    c.shadow_ptr = nullptr;
-    ZG_TRY(launch_layernorm(x, (int)rows, (int)n_features, g, b, eps, call.stream(), df, ds, &own, twin ? c.shadow_dev : nullptr));
-    call.announced(own);
+    DoneSlot* done = call.reserve();
+    Shadow& shadow = ctx().shadow;
+    float* twin = shadow.offer(inputs, x, inputs_len * sizeof(float));
+    ZG_TRY(launch_layernorm(x, (int)rows, (int)n_features, g, b, eps, call.stream(), done, twin));
     ZG_TRY(call.finish());
-    guard.done = true;
-    if (twin) {
-        memcpy(c.shadow_host, inputs, bytes);
-        c.shadow_ptr = inputs;
-        c.shadow_bytes = bytes;
-    }
+    if (twin) shadow.keep(inputs, inputs_len * sizeof(float));
     return ZG_OK;
 }
 
@@ -790,26 +237,14 @@ int zg_gelu(float* inputs, size_t inputs_len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(inputs || inputs_len == 0, ZG_ERR_ARG, "gelu: null argument");
     Call call;
-    CallGuard guard(call);
     float* x;
     ZG_TRY(call.inout_once(inputs, inputs_len, &x));
-    unsigned* df;
-    unsigned ds;
-    bool own = false;
-    call.reserve(&df, &ds);
-    Ctx& c = ctx();
-    const size_t bytes = inputs_len * sizeof(float);
-    const bool twin = static_cast<void*>(x) != static_cast<void*>(inputs) && bytes <= c.shadow_cap;
-    c.shadow_ptr = nullptr;
-    ZG_TRY(launch_gelu(x, inputs_len, call.stream(), df, ds, &own, twin ? c.shadow_dev : nullptr));
-    call.announced(own);
+    DoneSlot* done = call.reserve();
+    Shadow& shadow = ctx().shadow;
+    float* twin = shadow.offer(inputs, x, inputs_len * sizeof(float));
+    ZG_TRY(launch_gelu(x, inputs_len, call.stream(), done, twin));
     ZG_TRY(call.finish());
-    guard.done = true;
-    if (twin) {
-        memcpy(c.shadow_host, inputs, bytes);
-        c.shadow_ptr = inputs;
-        c.shadow_bytes = bytes;
-    }
+    if (twin) shadow.keep(inputs, inputs_len * sizeof(float));
     return ZG_OK;
 }
 
@@ -817,18 +252,10 @@ int zg_softmax(float* inputs, size_t inputs_len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(inputs || inputs_len == 0, ZG_ERR_ARG, "softmax: null argument");
     Call call;
-    CallGuard guard(call);
     float* x;
     ZG_TRY(call.inout_once(inputs, inputs_len, &x));
-    unsigned* df;
-    unsigned ds;
-    bool own = false;
-    call.reserve(&df, &ds);
-    ZG_TRY(launch_softmax(x, inputs_len, call.stream(), df, ds, &own));
-    call.announced(own);
-    ZG_TRY(call.finish());
-    guard.done = true;
-    return ZG_OK;
+    ZG_TRY(launch_softmax(x, inputs_len, call.stream(), call.reserve()));
+    return call.finish();
 }
 
 // ------------------------------------------------------------------------------ split / transpose
@@ -842,15 +269,12 @@ int zg_split_qkv(size_t n_embed, size_t seq_len, const float* inputs, size_t inp
     ZG_REQUIRE(outputs_len >= rows * n_embed, ZG_ERR_SHAPE, "split_qkv: outputs.len %zu < %zu", outputs_len,
                rows * n_embed);
     Call call;
-    CallGuard guard(call);
     const float* in;
     float* out;
     ZG_TRY(call.in_once(inputs, inputs_len, &in));
     ZG_TRY(call.out_once(outputs, rows * n_embed, &out));
     ZG_TRY(launch_split_qkv(in, rows, n_embed, split_idx, out, call.stream()));
-    ZG_TRY(call.finish());
-    guard.done = true;
-    return ZG_OK;
+    return call.finish();
 }
 
 int zg_transpose(size_t seq_len, size_t n_heads, size_t head_dim, const float* inputs,
@@ -863,15 +287,12 @@ int zg_transpose(size_t seq_len, size_t n_heads, size_t head_dim, const float* i
     ZG_REQUIRE(outputs_len >= batch * per, ZG_ERR_SHAPE, "transpose: outputs.len %zu < %zu", outputs_len, batch * per);
     ZG_REQUIRE(n_heads <= 65535 && batch <= 65535, ZG_ERR_UNSUPPORTED, "transpose: n_heads/batch > 65535");
     Call call;
-    CallGuard guard(call);
     const float* in;
     float* out;
     ZG_TRY(call.in_once(inputs, inputs_len, &in));
     ZG_TRY(call.out_once(outputs, batch * per, &out));
     ZG_TRY(launch_transpose(in, batch, seq_len, n_heads, head_dim, out, call.stream()));
-    ZG_TRY(call.finish());
-    guard.done = true;
-    return ZG_OK;
+    return call.finish();
 }
 
 // ------------------------------------------------------------------------------ sdpa
@@ -889,7 +310,6 @@ int zg_scaled_dot_product_attention(const float* q, size_t q_len, const float* k
                    _attn_len >= seq_len,
                ZG_ERR_SHAPE, "sdpa: slice lengths inconsistent with batch %zu", batch);
     Call call;
-    CallGuard guard(call);
     const float *dq, *dk, *dv;
     float* out;
     ZG_TRY(call.in(q, batch * n_heads * head_dim, &dq));
@@ -898,9 +318,7 @@ int zg_scaled_dot_product_attention(const float* q, size_t q_len, const float* k
     ZG_TRY(call.out_once(outputs, batch * n_heads * head_dim, &out));
     ZG_TRY(attn_core(dq, dk, dv, (long)(n_heads * seq_len * head_dim), (long)(seq_len * head_dim), (long)head_dim,
                      batch, n_heads, seq_len, out, call.stream(), head_dim));
-    ZG_TRY(call.finish());
-    guard.done = true;
-    return ZG_OK;
+    return call.finish();
 }
 
 // ------------------------------------------------------------------------------ CausalSelfAttention
@@ -928,9 +346,7 @@ int zg_attn_forward(size_t n_heads, size_t n_embed, const float* c_attn_weight, 
                "attn: null argument");
     ZG_REQUIRE(hd <= 2048, ZG_ERR_UNSUPPORTED, "attn: head_dim %zu beyond 2048", hd);
     Call call;
-    CallGuard guard(call);
     hipStream_t s = call.stream();
-    Ctx& c = ctx();
     const float *caw, *cab, *cpw, *cpb, *x;
     float *kc = nullptr, *vc = nullptr, *out, *qkv, *q;
     ZG_TRY(call.param(c_attn_weight, 3 * E * E, &caw));
@@ -943,60 +359,12 @@ int zg_attn_forward(size_t n_heads, size_t n_embed, const float* c_attn_weight, 
     // (same pointer, same width, seq_len = rows held + 1) nothing goes up and only the new row comes back; anything else
     // — a first sight, a restart, a jump — uploads rows 0 .. T-2 again.  A caller that EDITS earlier rows in place between two
     // consecutive positions must drop the mirror (zg_unregister_tensor(cache)).  No room in the pool: the whole cache is staged.
-    KvMirror* mir[2] = {nullptr, nullptr};
-    float* host_cache[2] = {k_cache, v_cache};
-    float** dev_cache[2] = {&kc, &vc};
-    {   // The pool is a bump allocator and mirrors of caches the caller has long freed stay in it.  When this call's caches would
-        // not fit what is left, every mirror is dropped and the pool starts over (the live caches upload once more at their next
-        // call) — before any pointer into the map is taken.
-        size_t need_bytes = 0;
-        for (int i = 0; i < 2; ++i) {
-            if (is_device_ptr(host_cache[i])) continue;
-            auto it = c.kv_mirrors.find(host_cache[i]);
-            if (it == c.kv_mirrors.end() || it->second.cap_floats < seq_len * E) need_bytes += std::max(seq_len * E * 2, (size_t)1024 * E) * sizeof(float) + 256;
-        }
-        if (need_bytes > 0 && c.kv_pool_off > 0 && c.kv_pool_off + need_bytes > c.kv_pool_cap && need_bytes <= c.kv_pool_cap) {
-            c.kv_mirrors.clear();
-            c.kv_pool_off = 0;
-        }
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (is_device_ptr(host_cache[i])) {
-            *dev_cache[i] = host_cache[i];
-            continue;
-        }
-        KvMirror* m = nullptr;
-        auto it = c.kv_mirrors.find(host_cache[i]);
-        if (it != c.kv_mirrors.end()) m = &it->second;
-        const size_t need = seq_len * E;
-        if (m == nullptr || m->cap_floats < need) {  // a slot for this cache: the reference's context (1024 rows) or twice what is needed
-            const size_t cap = std::max(need * 2, (size_t)1024 * E);
-            const size_t off = (c.kv_pool_off + 255) & ~(size_t)255;
-            if (c.kv_pool != nullptr && off + cap * sizeof(float) <= c.kv_pool_cap) {
-                KvMirror fresh;
-                fresh.dev = reinterpret_cast<float*>(c.kv_pool + off);
-                fresh.cap_floats = cap;
-                fresh.n_embed = E;
-                fresh.rows = 0;
-                c.kv_pool_off = off + cap * sizeof(float);
-                m = &(c.kv_mirrors[host_cache[i]] = fresh);  // (an outgrown slot stays behind until zg_unregister_all)
-            } else {
-                m = nullptr;
-                c.kv_mirrors.erase(host_cache[i]);
-            }
-        }
-        if (m == nullptr) {  // pool exhausted: rows 0..T-2 go up, row T-1 comes back, every call
-            ZG_TRY(call.inout(host_cache[i], seq_len * E, dev_cache[i]));
-            continue;
-        }
-        if (m->n_embed != E || m->rows + 1 != seq_len) {
-            if (seq_len > 1) ZG_HIP(hipMemcpyAsync(m->dev, host_cache[i], (seq_len - 1) * E * sizeof(float), hipMemcpyHostToDevice, s));
-            m->n_embed = E;
-        }
-        m->rows = 0;  // (valid again once this call has succeeded)
-        mir[i] = m;
-        *dev_cache[i] = m->dev;
-    }
+    KvMirrors& mirrors = ctx().mirrors;
+    KvMirror* mir[2];
+    float* const host_cache[2] = {k_cache, v_cache};
+    mirrors.make_room(host_cache, seq_len, E);
+    ZG_TRY(mirrors.attach(k_cache, seq_len, E, call, &kc, &mir[0]));
+    ZG_TRY(mirrors.attach(v_cache, seq_len, E, call, &vc, &mir[1]));
     ZG_TRY(call.out_once(outputs, E, &out));  // stored once by c_proj
     ZG_TRY(call.out(_qkv, 3 * E, &qkv));      // read back by the append and the attention: device memory
     ZG_TRY(call.out(_q, E, &q));
@@ -1012,7 +380,6 @@ int zg_attn_forward(size_t n_heads, size_t n_embed, const float* c_attn_weight, 
     // c_proj (ops.zig:172)
     ZG_TRY(linear_device(E, E, cpw, cpb, q, 1, out, s));
     ZG_TRY(call.finish());
-    guard.done = true;
     for (KvMirror* m : mir)
         if (m) m->rows = seq_len;
     return ZG_OK;

@@ -57,7 +57,7 @@ __device__ inline void announce_done(const DoneWord d) {
 __global__ __launch_bounds__(256) void layernorm_kernel(float* x, int rows, int n, const float* g,
                                                         const float* b, float eps, DoneWord done, float* shadow) {
     // shadow (op tier, may be null): a device-memory twin of the result — x itself may be pinned host memory the NEXT op's
-    // kernels should not read across PCIe (api_ops.hip: the output of one op is the input of the next Linear in src/main.zig)
+    // kernels should not read across PCIe (zg_runtime.h Shadow: the output of one op is the input of the next Linear in src/main.zig)
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row < rows) {
@@ -271,35 +271,35 @@ inline int grid_for(size_t n, int block = 256, int cap = 2048) {
 
 }  // namespace
 
-// done_flag != nullptr: the caller would like the kernel to announce its own completion; *announced tells whether this launch
-// does (a one-workgroup grid), otherwise the caller's one-thread launch follows as usual.
-int launch_layernorm(float* x, int rows, int n, const float* g, const float* b, float eps, hipStream_t s, unsigned* done_flag, unsigned done_seq,
-                     bool* announced, float* shadow) {
-    if (announced) *announced = false;
+// done offers a word (done->flag != nullptr): the caller would like the kernel to announce its own completion; done->taken tells
+// whether this launch does (a one-workgroup grid), otherwise the caller's one-thread launch follows as usual.
+static bool offered(const DoneSlot* done) { return done != nullptr && done->flag != nullptr; }
+static DoneWord word_of(const DoneSlot* done, bool own) { return DoneWord{own ? done->flag : nullptr, done ? done->seq : 0u}; }
+
+int launch_layernorm(float* x, int rows, int n, const float* g, const float* b, float eps, hipStream_t s, DoneSlot* done, float* shadow) {
     if (rows == 0) return ZG_OK;
-    const bool own = done_flag != nullptr && rows <= 4;
-    hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, rows, n, g, b, eps, DoneWord{own ? done_flag : nullptr, done_seq}, shadow);
+    const bool own = offered(done) && rows <= 4;
+    hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, rows, n, g, b, eps, word_of(done, own), shadow);
     ZG_HIP(hipGetLastError());
-    if (announced) *announced = own;
+    if (done) done->taken = own;
     return ZG_OK;
 }
 
-int launch_gelu(float* x, size_t n, hipStream_t s, unsigned* done_flag, unsigned done_seq, bool* announced, float* shadow) {
-    if (announced) *announced = false;
+int launch_gelu(float* x, size_t n, hipStream_t s, DoneSlot* done, float* shadow) {
     if (n == 0) return ZG_OK;
-    const bool own = done_flag != nullptr && n <= 4096;  // one workgroup of 1024 lanes, one vector of four each: a single pass
-    hipLaunchKernelGGL(gelu_kernel, dim3(own ? 1 : grid_for(n / 4 + 1)), dim3(own ? 1024 : 256), 0, s, x, n, DoneWord{own ? done_flag : nullptr, done_seq}, shadow);
+    const bool own = offered(done) && n <= 4096;  // one workgroup of 1024 lanes, one vector of four each: a single pass
+    hipLaunchKernelGGL(gelu_kernel, dim3(own ? 1 : grid_for(n / 4 + 1)), dim3(own ? 1024 : 256), 0, s, x, n, word_of(done, own), shadow);
     ZG_HIP(hipGetLastError());
-    if (announced) *announced = own;
+    if (done) done->taken = own;
     return ZG_OK;
 }
 
-int launch_softmax(float* x, size_t n, hipStream_t s, unsigned* done_flag, unsigned done_seq, bool* announced) {
-    if (announced) *announced = false;
+int launch_softmax(float* x, size_t n, hipStream_t s, DoneSlot* done) {
     if (n == 0) return ZG_OK;
-    hipLaunchKernelGGL(softmax_kernel, dim3(1), dim3(1024), 0, s, x, n, DoneWord{done_flag, done_seq});
+    const bool own = offered(done);
+    hipLaunchKernelGGL(softmax_kernel, dim3(1), dim3(1024), 0, s, x, n, word_of(done, own));
     ZG_HIP(hipGetLastError());
-    if (announced) *announced = done_flag != nullptr;
+    if (done) done->taken = own;
     return ZG_OK;
 }
 
@@ -365,14 +365,13 @@ int launch_epoch_add(unsigned* epoch, unsigned n, hipStream_t s) {
 }
 
 int launch_embedding(const float* w, size_t emb_dim, const size_t* idx, size_t n_idx, size_t n_rows,
-                     float* out, int* d_oob, hipStream_t s, unsigned* done_flag, unsigned done_seq, bool* announced) {
-    if (announced) *announced = false;
+                     float* out, int* d_oob, hipStream_t s, DoneSlot* done) {
     if (n_idx == 0) return ZG_OK;
     // (d_oob is a pinned host word: the caller reads it behind its own drain of the stream)
-    const bool own = done_flag != nullptr && n_idx == 1;
-    hipLaunchKernelGGL(embedding_kernel, dim3((unsigned)n_idx), dim3(256), 0, s, w, emb_dim, idx, n_rows, out, d_oob, DoneWord{own ? done_flag : nullptr, done_seq});
+    const bool own = offered(done) && n_idx == 1;
+    hipLaunchKernelGGL(embedding_kernel, dim3((unsigned)n_idx), dim3(256), 0, s, w, emb_dim, idx, n_rows, out, d_oob, word_of(done, own));
     ZG_HIP(hipGetLastError());
-    if (announced) *announced = own;
+    if (done) done->taken = own;
     return ZG_OK;
 }
 

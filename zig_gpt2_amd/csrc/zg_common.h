@@ -13,6 +13,7 @@ void set_error(const char* fmt, ...);
 // Diagnostic: the launchers of the decode kernels note the instantiation they picked (zg_debug_last_kernel; bench.py quotes
 // it as the roofline's kernel symbol instead of a hand-kept table).
 void note_kernel(const char* fmt, ...);
+const char* last_kernel();  // this thread's latest note
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
 // Test hook ZGPT2_DECODE_PATHS_OFF (bit mask, read per call): the lock-step decode's newer paths switched off so that the paths
 // they replaced — still the route of shapes the newer kernels do not take — can be held to the same tokens (tests/test_planes_gpu.py).

@@ -1,4 +1,5 @@
-// zg_runtime.h — process-wide runtime state of libzgpt2_hip (device, stream, host-staging arena).
+// zg_runtime.h — process-wide runtime of libzgpt2_hip (zg_runtime.hip): device and stream, the tensor registry, the op tier's
+// staging scope with its two arenas and its completion word, and the two caches kept between op-tier calls.
 #pragma once
 #include <unordered_map>
 
@@ -6,9 +7,18 @@
 
 namespace zg {
 
+class Call;
+
 struct Registered {
     void* dev;
     size_t bytes;
+};
+
+// zg_register_tensor's device copies of host parameters, keyed by host address.  Written by the registry entry points
+// (zg_runtime.hip); read by Call::stage_in for parameters only.
+struct Registry {
+    std::unordered_map<const void*, Registered> map;
+    void drop_all();  // frees every device copy (the caller has drained the stream)
 };
 
 // Device mirror of a caller-owned host KV cache (zg_attn_forward, ops.zig:129-173): the caller appends one row per call and
@@ -20,42 +30,88 @@ struct KvMirror {
     size_t rows = 0;  // rows 0 .. rows-1 of the mirror equal the caller's cache
 };
 
+// The mirrors and the device pool they live in (allocated in zg_init: no forward allocates).  The pool is a bump allocator.
+// Written by its own functions only; zg_attn_forward commits `rows` of the mirrors attach() handed it once its call has succeeded.
+struct KvMirrors {
+    char* pool = nullptr;
+    size_t cap = 0;
+    size_t off = 0;
+    std::unordered_map<const void*, KvMirror> map;
+    int init(size_t pool_bytes);
+    void release();
+    // Mirrors of caches the caller has long freed stay in the pool.  When the two caches of a call would not fit what is left, every
+    // mirror is dropped and the pool starts over (the live caches upload once more at their next call) — before attach() takes
+    // any pointer into the map.
+    void make_room(float* const host_cache[2], size_t seq_len, size_t E);
+    // One cache of a zg_attn_forward call at position seq_len: *dev is what the kernels read and append to — the pointer itself
+    // (device memory), its mirror (*mirror set; rows 0 .. seq_len-2 uploaded unless this call continues the sequence the mirror
+    // holds), or, with no room in the pool, the whole cache staged through `call`.
+    int attach(float* host_cache, size_t seq_len, size_t E, Call& call, float** dev, KvMirror** mirror);
+    void drop(const void* host_cache) { map.erase(host_cache); }  // the next zg_attn_forward uploads the cache again
+    void drop_all();  // the pool empties when every mirror is gone
+};
+
+// The result of the last in-place elementwise op on a HOST buffer, kept twice: in device memory (what the next Linear reads
+// instead of uploading the same bytes again — in src/main.zig every Linear's input is the previous op's output) and in host
+// memory (what the caller's buffer is compared with before the device twin is trusted).  Written by offer / keep only
+// (zg_layernorm_forward, zg_gelu); read by Call::stage_in through match.
+struct Shadow {
+    float* dev = nullptr;
+    char* host = nullptr;
+    size_t cap = 0;
+    const void* ptr = nullptr;
+    size_t bytes = 0;
+    int init(size_t cap_bytes);
+    void release();
+    // In front of the launch: the twin held so far is no longer valid; returns where the kernel stores the new one, or nullptr
+    // (the buffer was not staged — a device pointer — or is larger than the twin).
+    float* offer(const void* buf, const void* staged, size_t n_bytes);
+    // Behind a finish() that succeeded, for a buffer offer() returned a twin for: the caller's bytes are the twin's from here on.
+    void keep(const void* buf, size_t n_bytes);
+    // The device twin of exactly these bytes (same buffer, same length, and the caller has not changed a byte of it), or nullptr.
+    const float* match(const void* p, size_t n_bytes) const;
+};
+
 struct Ctx {
+    // zg_init_ex / zg_shutdown / zg_set_stream; read by every unit
     bool inited = false;
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;  // the stream every launch uses (own_stream unless zg_set_stream)
-    char* stage = nullptr;         // device staging arena for host-pointer callers (op tier)
-    size_t stage_cap = 0;
-    size_t stage_off = 0;
+    // device staging arena for host-pointer callers (op tier).  off: Call (alloc, finish, ~Call).  The model tier's uploads
+    // (api_gpt.hip) pass through base .. base + cap between calls.
+    struct {
+        char* base = nullptr;
+        size_t cap = 0;
+        size_t off = 0;
+    } stage;
     // pinned host arena of the op tier: the caller's pageable buffers are copied here by the CPU, and the GPU either reads /
-    // writes this memory in place (buffers a kernel touches once) or moves it with ONE asynchronous DMA each way
-    char* pin = nullptr;
-    size_t pin_cap = 0;
-    size_t pin_off = 0;
-    // device pool of the KV-cache mirrors (allocated in zg_init: no forward allocates)
-    char* kv_pool = nullptr;
-    size_t kv_pool_cap = 0;
-    size_t kv_pool_off = 0;
-    std::unordered_map<const void*, KvMirror> kv_mirrors;
-    // the result of the last in-place elementwise op on a HOST buffer, kept twice: in device memory (what the next Linear reads
-    // instead of uploading the same bytes again — in src/main.zig every Linear's input is the previous op's output) and in host
-    // memory (what the caller's buffer is compared with before the device twin is trusted)
-    float* shadow_dev = nullptr;
-    char* shadow_host = nullptr;
-    size_t shadow_cap = 0;
-    const void* shadow_ptr = nullptr;
-    size_t shadow_bytes = 0;
-    unsigned* done_flag = nullptr;  // pinned completion word of op-tier calls (d_flag + 8), its sequence number, calls since a real drain
-    unsigned done_seq = 0;
-    unsigned calls_since_sync = 0;
-    unsigned long long done_missed = 0;  // calls that polled to the end without seeing their number and drained the stream (zg_debug_ops_done_state)
-    int* d_flag = nullptr;         // pinned host int the kernels raise for index-range checks (read after the call's drain)
-    float* d_zero = nullptr;       // 64 zero bytes (stand-in operand for absent bias / residual)
-    float* attn_part = nullptr;    // op-tier attention partials (sized at init)
-    size_t attn_part_floats = 0;
-    std::unordered_map<const void*, Registered> registry;
-    unsigned long long* dbg = nullptr;  // -DZG_STAMPS diagnostic buffer
+    // writes this memory in place (buffers a kernel touches once) or moves it with ONE asynchronous DMA each way.
+    // off: Call (pin_alloc, finish, ~Call)
+    struct {
+        char* base = nullptr;
+        size_t cap = 0;
+        size_t off = 0;
+    } pin;
+    KvMirrors mirrors;
+    Shadow shadow;
+    // the completion word of op-tier calls.  Call (reserve, finish); seq also zg_debug_ops_set_done_seq
+    struct {
+        unsigned* flag = nullptr;  // pinned completion word of op-tier calls (d_flag + 8), its sequence number, calls since a real drain
+        unsigned seq = 0;
+        unsigned calls_since_sync = 0;
+        unsigned long long missed = 0;  // calls that polled to the end without seeing their number and drained the stream (zg_debug_ops_done_state)
+    } done;
+    // zg_init_ex; read by the op tier, the kernels' launchers and the model tier
+    int* d_flag = nullptr;    // pinned host int the kernels raise for index-range checks (read after the call's drain)
+    float* d_zero = nullptr;  // 64 zero bytes (stand-in operand for absent bias / residual)
+    // op-tier attention partials (sized at init).  zg_init_ex; the kernels of attn_core (api_ops.hip) write through it
+    struct {
+        float* buf = nullptr;
+        size_t floats = 0;
+    } attn_part;
+    Registry registry;
+    unsigned long long* dbg = nullptr;  // -DZG_STAMPS diagnostic buffer (the model tier's debug unit)
 };
 
 Ctx& ctx();
@@ -68,9 +124,13 @@ bool is_device_ptr(const void* p);
 //   *_once                a kernel reads / writes every element ONCE: the kernel works on the pinned arena in place (PCIe
 //                         zero-copy), no DMA at all — the common case for the small activation vectors of src/main.zig:119-195
 // Buffers that do not fit the pinned arena go through hipMemcpyAsync on the caller's pageable memory, as before.
+// A scope that ends without a finish() that succeeded — the call failed — drains the stream and empties both arenas.
 class Call {
   public:
     Call();
+    ~Call();
+    Call(const Call&) = delete;
+    Call& operator=(const Call&) = delete;
     // Activations (inputs, indices, q / k / v): always the caller's bytes of THIS call.
     template <typename T>
     int in(const T* p, size_t n, const T** dev) {
@@ -111,11 +171,10 @@ class Call {
     // A second host destination for a part of an output already staged with out() (the cache rows inside _qkv).
     int also_out(void* host, const void* dev_part, size_t bytes);
     // A call whose LAST kernel is a single workgroup writing zero-copy outputs may let that kernel store the completion word
-    // itself: reserve() hands out the word and the sequence number finish() will poll for (flag == nullptr: not available —
-    // polling is off, the periodic real drain is due, or an output of this call still needs a DMA behind the kernel);
-    // announced(true) tells finish() that the kernel took it, so the one-thread launch is skipped.
-    void reserve(unsigned** flag, unsigned* seq);
-    void announced(bool yes) { announced_ = yes; }
+    // itself: reserve() offers that launch the word and the sequence number finish() will poll for (flag == nullptr: not available —
+    // polling is off, the periodic real drain is due, or an output of this call still needs a DMA behind the kernel); a launch
+    // that sets `taken` tells finish() that the kernel stores the word, so the one-thread launch is skipped.
+    DoneSlot* reserve();
     // Copies outputs back (if any were staged), synchronises the stream, releases the arenas.
     int finish();
     hipStream_t stream() const { return s_; }
@@ -133,8 +192,8 @@ class Call {
     };
     Out outs_[24];
     int n_outs_ = 0;
-    unsigned reserved_seq_ = 0;
-    bool reserved_ = false, announced_ = false;
+    DoneSlot slot_{nullptr, 0, false};
+    bool finished_ = false;
     size_t mark_, pin_mark_;
     hipStream_t s_;
 };
