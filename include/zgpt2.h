@@ -51,10 +51,19 @@ typedef enum {
  * ZGPT2_STAGING_MB).  Idempotent. */
 int zg_init(int device);
 int zg_init_ex(int device, size_t staging_bytes);
+/* Drain the library stream and free everything zg_init_ex made (arenas, registered tensors, KV-cache mirrors, the own stream).
+ * Every zg_gpt handle must be destroyed BEFORE this call: the model tier stages through the runtime's arena and launches on its
+ * stream.  A caller-owned stream given to zg_set_stream is drained, never destroyed.  Afterwards every entry that needs the
+ * runtime returns ZG_ERR_NOT_INITIALIZED until zg_init is called again (a fresh runtime: nothing registered, no mirrors); a
+ * second zg_shutdown is ZG_OK. */
 int zg_shutdown(void);
 const char* zg_last_error(void);
-/* Launch on a caller-owned hipStream_t (e.g. torch's current stream); NULL restores the library's
- * own stream. */
+/* Launch on a caller-owned hipStream_t — a stream the caller created, e.g. a torch.cuda.Stream() made current — so that the
+ * library's work is ordered with the caller's on that stream.  The stream the library leaves is drained first.  A NULL handle
+ * means the library's OWN stream (and restores it): the legacy default stream, whose handle is 0 — torch's default stream — cannot
+ * be selected, and work a caller queues there is NOT ordered with the library's (the own stream is non-blocking).  Handles without
+ * a private stream follow the change: their decode graphs are captured again on the first call that sees the new stream.  The
+ * stream must outlive its use: restore NULL (or shut down) before destroying it.  Same thread as every other call. */
 int zg_set_stream(void* hip_stream);
 int zg_synchronize(void);
 /* Upload a host PARAMETER tensor (Linear / Embedding weight, bias, LayerNorm vectors) once and keep a
@@ -144,7 +153,8 @@ int zg_softmax(float* inputs, size_t inputs_len);
  * takes such a Linear through its GEMV kernels); K a multiple of 64 and at least 128.  Asynchronous on
  * the library stream.  zg_linear_forward itself takes this path for batch >= 16 (fp32 operands split
  * exactly into bf16 planes, so the result stays fp32-sgemm grade).
- * zg_f32_to_bf16 converts a device or host fp32 array into a device bf16 array (round to nearest even). */
+ * zg_f32_to_bf16 converts a device or host fp32 array into a device bf16 array (round to nearest even; FLT_MAX rounds to inf; a
+ * NaN stays a NaN of its sign, quiet, with its upper payload bits — as the bf16 weight upload of zg_gpt_load_*). */
 int zg_gemm_bf16_nt(const uint16_t* A, const uint16_t* B, const float* bias_or_null, void* C, size_t M,
                     size_t N, size_t K, int gelu, int out_bf16);
 /* Diagnostic: number of matrix-core GEMM launches so far in this process (tests assert which path a
@@ -485,7 +495,13 @@ int zg_debug_gpt_tag_census(zg_gpt* g, unsigned epoch24, unsigned sk_flag_value,
 int zg_gpt_sample(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, float temp,
                   const float* uniforms, uint64_t seed, size_t* tokens_out, float* probs_out, size_t probs_len);
 
-/* ln_f output of the last forward, [batch, n_embed] (state.x, main.zig:189). */
+/* ln_f output of the last forward, [batch, n_embed] (state.x, main.zig:189): of the last zg_gpt_forward / zg_gpt_sample* step,
+ * of the last position of a zg_gpt_prefill / zg_gpt_extend / zg_gpt_score pass, of the last step of a generation.  The device
+ * keeps the residual stream in front of ln_f (ln_f runs folded into lm_head), so the vector is computed here, out of place:
+ * what the next zg_gpt_argmax, step or continuation reads is untouched.  Behind a pass without logits — whose last Block stops
+ * at its cache append — this call runs the rest of that Block first, from what the pass left in the handle and with the weights
+ * the handle holds at that moment: a zg_gpt_load_* between such a pass and this call is the caller's to avoid.  Drains the handle's
+ * stream; no step or pass pays for it. */
 int zg_gpt_hidden(zg_gpt* g, float* x_out, size_t len);
 
 /* generate — src/main.zig:322-342 with greedy argmax instead of the sampler, for `batch`

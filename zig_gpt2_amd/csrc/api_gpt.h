@@ -100,6 +100,14 @@ struct zg_gpt {
     // the session: positions the caches hold, and the row behind the last one written since the rows behind a pass
     // were last cleared — a continuation clears [its end, context) only when something may be there
     size_t cached_len, kv_dirty_hi;
+    // zg_gpt_hidden — where the residual stream of the last forward lives: x (a decode step; a pass with logits copies its last rows
+    // there), or the last of the P rows per sequence of pass.x.  A pass without logits stops its last Block behind the cache append
+    // (enqueue_prefill): HID_PASS_OPEN, and zg_gpt_hidden runs the rest of that Block once, from pass.qkv and the caches, before it
+    // reads the rows (HID_PASS_DONE).  No step or pass pays for it.
+    struct {
+        int src;  // HID_X / HID_PASS_OPEN / HID_PASS_DONE
+        size_t pos0, P;
+    } hidden;
 
     // What follows belongs to one unit each, which the comment names.  Every group is an aggregate that value-initialises to zeros
     // (new zg_gpt() zeroes the whole handle: release() relies on it); carve() and build_handle fill the pointers of all of them.
@@ -363,7 +371,8 @@ int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, StepTai
 
 // ---- api_gpt_pass.hip: the whole-prompt pass
 int ensure_score_weights(zg_gpt* g, hipStream_t s);
-int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipStream_t s, StepTaps* taps = nullptr);
+enum { HID_X = 0, HID_PASS_OPEN, HID_PASS_DONE };  // zg_gpt.hidden.src
+int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipStream_t s, StepTaps* taps = nullptr, bool resume_last_block = false);
 size_t prefill_min();
 int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t stride, size_t n, int compute_logits, float* logits_out, size_t logits_len,
               const char* who, const ScoreCall* sc = nullptr, StepTaps* taps = nullptr);

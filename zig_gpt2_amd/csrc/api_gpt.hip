@@ -455,6 +455,7 @@ int forward_enqueue(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_to
     if (seq_len > g->kv_dirty_hi) g->kv_dirty_hi = seq_len;
     ZG_TRY(note_steps(g, 1, s));
     ZG_TRY(ensure_ln_folded(g, s));
+    g->hidden.src = HID_X;
     if (taps) {
         StepOpts o;
         o.taps = taps;
@@ -677,7 +678,20 @@ int zg_gpt_hidden(zg_gpt* g, float* x_out, size_t len) {
     ZG_TRY(require_init());
     ZG_REQUIRE(g && x_out && len >= g->batch * g->cfg.n_embed, ZG_ERR_ARG, "gpt_hidden: bad argument");
     hipStream_t s = gs(g);
-    ZG_TRY(copy_out_f32(x_out, g->x, g->batch * g->cfg.n_embed, s));
+    const size_t B = g->batch, E = g->cfg.n_embed;
+    // ln_f exists only folded into lm_head (lm_head_args): here it runs out of place, in h4 — scratch every step and pass rewrites
+    // before reading it.  x stays the residual stream the next argmax / sample / step expects.
+    if (g->hidden.src == HID_X) ZG_TRY(launch_copy_f32(g->x, g->h4, B * E, s));
+    else {
+        const size_t P = g->hidden.P;
+        if (g->hidden.src == HID_PASS_OPEN) {
+            ZG_TRY(ensure_ln_folded(g, s));
+            ZG_TRY(enqueue_prefill(g, g->hidden.pos0, P, true, s, nullptr, true));
+        }
+        ZG_HIP(hipMemcpy2DAsync(g->h4, E * 4, g->pass.x + (P - 1) * E, P * E * 4, E * 4, B, hipMemcpyDeviceToDevice, s));
+    }
+    ZG_TRY(launch_layernorm(g->h4, (int)B, (int)E, g->ln_f_g, g->ln_f_b, 1e-5f, s));
+    ZG_TRY(copy_out_f32(x_out, g->h4, B * E, s));
     ZG_HIP(hipStreamSynchronize(s));
     return check_fault(g);
 }

@@ -687,6 +687,7 @@ int zg_gpt_profile_step(zg_gpt* g, size_t seq_len, int iters, float* us_out, siz
     hipStream_t s = gs(g);
     ZG_HIP(hipStreamSynchronize(s));
     ZG_TRY(ensure_ln_folded(g, s));
+    g->hidden.src = HID_X;  // (steps ran: x is what they left)
     ZG_TRY(note_steps(g, (size_t)iters, s));
     for (size_t b = 0; b < g->batch; ++b) g->h_ints[b] = (int)(b % g->cfg.vocab_size);
     ZG_HIP(hipMemcpyAsync(g->forced, g->h_ints, g->batch * sizeof(int), hipMemcpyHostToDevice, s));
@@ -738,6 +739,7 @@ int zg_gpt_time_kernel(zg_gpt* g, int which_and_options, int iters, float* avg_u
     if (t_opt >= 1 && t_opt <= g->cfg.context_size) T = t_opt;
     ZG_HIP(hipStreamSynchronize(s));
     ZG_TRY(ensure_ln_folded(g, s));
+    g->hidden.src = HID_X;
     const int chain = 64, reps = (iters + chain - 1) / chain;
     // one epoch per replay of the chain, warm-up included — and class 0 IS the embed kernel, which advances the epoch itself at
     // every one of the chain's launches

@@ -407,6 +407,7 @@ static int gen_pump(zg_gpt* g, bool* more) {
         hipGraphExec_t e;  // sequence lengths st + 1 .. st + K share a bucket (K divides 64); captured by gen_begin (first use: the backstop)
         ZG_TRY(graph_exec(g, {true, true, g->gen.tail}, bucket_of(st + 1), s, &e));
         ZG_HIP(hipGraphLaunch(e, s));
+        g->hidden.src = HID_X;
         g->gen.pos = st + K;
     } else {
         ZG_TRY(run_step(g, st >= g->gen.min_prompt, st + 1, s, g->gen.tail));

@@ -103,7 +103,10 @@ int ensure_score_weights(zg_gpt* g, hipStream_t s) {
 // pos0 > 0 (a continuation): the P rows are positions pos0 .. pos0 + P - 1 (tokens g->prompt[b][pos0 + t]); they are appended
 // behind the pos0 cached rows, and the attention reads every key, old and new, from the caches in their storage format.
 // taps (zg_debug_gpt_pass_taps): behind every launch, copies of what it wrote (include/zgpt2.h lists them); the launches are the same.
-int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipStream_t s, StepTaps* taps) {
+// resume_last_block (zg_gpt_hidden behind a pass that stopped there): only what such a pass left out — the last Block from its
+// attention on, over the q columns pass.qkv still holds, the caches and the residual stream in pass.x.  hidden records which of the
+// two the handle is behind.
+int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipStream_t s, StepTaps* taps, bool resume_last_block) {
     const bool f32w = g->wt != WT_BF16;
     const int np = f32w ? kWeightPlanes : (g->flags & ZG_GPT_PREFILL_2PLANE) ? 2 : kSplit;
     const size_t E = g->cfg.n_embed, L = g->cfg.n_layer, H = g->cfg.n_heads, C = g->cfg.context_size;
@@ -121,35 +124,44 @@ int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipS
         prefill_plan_ints(plan, v);
         return tap_words(taps, cls, l, ZG_TAP_PLAN, v, ZG_PREFILL_PLAN_INTS);
     };
-    ZG_TRY(launch_embed_prefill(g->prompt, (int)C, B, (int)P, g->wte, g->wpe, g->wt, iE, g->pass.x, s, (int)pos0));
-    ZG_TRY(tap_x(0, 0));
-    ZG_TRY(launch_ln_split(g->pass.x, M, iE, g->layers[0].ln_1_g, g->layers[0].ln_1_b, 1e-5f, g->pass.a, s));
-    ZG_TRY(tap_a(1, 0, 0));
-    for (size_t l = 0; l < L; ++l) {
+    const bool resume = resume_last_block;
+    g->hidden.src = HID_X;  // until every launch below is enqueued: a pass that fails halfway leaves no claim on pass.x
+    if (!resume) {
+        ZG_TRY(launch_embed_prefill(g->prompt, (int)C, B, (int)P, g->wte, g->wpe, g->wt, iE, g->pass.x, s, (int)pos0));
+        ZG_TRY(tap_x(0, 0));
+        ZG_TRY(launch_ln_split(g->pass.x, M, iE, g->layers[0].ln_1_g, g->layers[0].ln_1_b, 1e-5f, g->pass.a, s));
+        ZG_TRY(tap_a(1, 0, 0));
+    }
+    for (size_t l = resume ? L - 1 : 0; l < L; ++l) {
         const zg_layer& y = g->layers[l];
-        // pass.a holds split(ln_1(x)) here: from the line above or from the tail of the previous Block's last GEMM
-        // c_attn with the cache append of ops.zig:152-157 in its epilogue
-        PrefillQkv qa{(int)P, iE, (int)H, (int)C, g->kv_mode, y.k_cache, y.v_cache, g->batch * C * E * 2};
-        qa.pos0 = (int)pos0;
-        if (!f32w && g->pass.sk_flags != nullptr) {  // (the persistent GEMM may hand half tiles over between workgroups: gemm_s4.hip SK)
-            qa.sk_ws = g->pass.ws;
-            qa.sk_ws_bytes = g->pass.ws_floats * 4;
-            qa.sk_flags = g->pass.sk_flags;
-            qa.sk_flags_words = (unsigned)kSkFlagWords;
-            ZG_TRY(next_sk_epoch(g, s, &qa.sk_epoch));
-            g->pass.sk_used = true;
+        if (!resume) {
+            // pass.a holds split(ln_1(x)) here: from the line above or from the tail of the previous Block's last GEMM
+            // c_attn with the cache append of ops.zig:152-157 in its epilogue
+            PrefillQkv qa{(int)P, iE, (int)H, (int)C, g->kv_mode, y.k_cache, y.v_cache, g->batch * C * E * 2};
+            qa.pos0 = (int)pos0;
+            if (!f32w && g->pass.sk_flags != nullptr) {  // (the persistent GEMM may hand half tiles over between workgroups: gemm_s4.hip SK)
+                qa.sk_ws = g->pass.ws;
+                qa.sk_ws_bytes = g->pass.ws_floats * 4;
+                qa.sk_flags = g->pass.sk_flags;
+                qa.sk_flags_words = (unsigned)kSkFlagWords;
+                ZG_TRY(next_sk_epoch(g, s, &qa.sk_epoch));
+                g->pass.sk_used = true;
+            }
+            if (taps) ZG_TRY(tap_caches(g, taps, -1, l, 0, T_tap, s));
+            ZG_TRY(launch_prefill_gemm(g->pass.a, f32w ? y.c_attn_p : (const bf16_t*)y.c_attn_w, y.c_attn_b, g->pass.qkv, M, 3 * iE, iE, 3 * iE, PF_QKV,
+                                       g->pass.ws, g->pass.ws_floats, nullptr, s, &qa, np, nullptr, plan_out));
+            if (taps) {  // q, then the k | v columns: the persistent kernel leaves those to an fp32 cache (gemm_s4.hip S4_QKV)
+                const unsigned kv_cols = plan.family == PFF_S4 && g->kv_mode == 0 ? ZG_TAP_NOT_WRITTEN : 0u;
+                ZG_TRY(tap_plan(2, l));
+                ZG_TRY(tap_put(taps, 2, l, ZG_TAP_Q, ZG_TAP_F32, 0, g->pass.qkv, Mz, E * 4, 3 * E * 4, s));
+                ZG_TRY(tap_put(taps, 2, l, ZG_TAP_QKV_KV, ZG_TAP_F32, kv_cols, g->pass.qkv + E, Mz, 2 * E * 4, 3 * E * 4, s));
+                ZG_TRY(tap_caches(g, taps, 2, l, 0, T_tap, s));
+            }
+            if (l + 1 == L && !last_block_full) {
+                g->hidden = {HID_PASS_OPEN, pos0, P};
+                return ZG_OK;
+            }
         }
-        if (taps) ZG_TRY(tap_caches(g, taps, -1, l, 0, T_tap, s));
-        ZG_TRY(launch_prefill_gemm(g->pass.a, f32w ? y.c_attn_p : (const bf16_t*)y.c_attn_w, y.c_attn_b, g->pass.qkv, M, 3 * iE, iE, 3 * iE, PF_QKV,
-                                   g->pass.ws, g->pass.ws_floats, nullptr, s, &qa, np, nullptr, plan_out));
-        if (taps) {  // q, then the k | v columns: the persistent kernel leaves those to an fp32 cache (gemm_s4.hip S4_QKV)
-            const unsigned kv_cols = plan.family == PFF_S4 && g->kv_mode == 0 ? ZG_TAP_NOT_WRITTEN : 0u;
-            ZG_TRY(tap_plan(2, l));
-            ZG_TRY(tap_put(taps, 2, l, ZG_TAP_Q, ZG_TAP_F32, 0, g->pass.qkv, Mz, E * 4, 3 * E * 4, s));
-            ZG_TRY(tap_put(taps, 2, l, ZG_TAP_QKV_KV, ZG_TAP_F32, kv_cols, g->pass.qkv + E, Mz, 2 * E * 4, 3 * E * 4, s));
-            ZG_TRY(tap_caches(g, taps, 2, l, 0, T_tap, s));
-        }
-        if (l + 1 == L && !last_block_full) break;
         // K and V: the caches — except a whole prompt on an fp16 / B24 cache, which reads the unrounded k / v columns of qkv (an fp32
         // cache is read directly: the c_attn epilogue then need not store those columns)
         PrefillKv kv;
@@ -176,6 +188,7 @@ int enqueue_prefill(zg_gpt* g, size_t pos0, size_t P, bool last_block_full, hipS
         ZG_TRY(tap_x(6, l));
         ZG_TRY(tap_a(6, l, more ? 0u : ZG_TAP_NOT_WRITTEN));
     }
+    g->hidden = {HID_PASS_DONE, pos0, P};
     return ZG_OK;
 }
 
@@ -215,6 +228,7 @@ int pass_impl(zg_gpt* g, size_t past_len, const size_t* tokens, size_t stride, s
     ZG_TRY(enqueue_prefill(g, past_len, n, compute_logits != 0, s, taps));
     if (compute_logits) {
         ZG_HIP(hipMemcpy2DAsync(g->x, E * 4, g->pass.x + (n - 1) * E, n * E * 4, E * 4, B, hipMemcpyDeviceToDevice, s));
+        g->hidden.src = HID_X;
         ZG_TRY(stage_ctrl(g, end - 1, end, 1, s));
         ZG_TRY(enqueue_lm_head(g, s));
         if (logits_out) ZG_TRY(copy_out_f32(logits_out, g->logits, B * V, s));

@@ -646,6 +646,7 @@ int capture_all(zg_gpt* g, hipStream_t s) {
 // are disabled / the stream cannot be captured.
 int run_step(zg_gpt* g, bool with_logits, size_t seq_len, hipStream_t s, StepTail tail) {
     ZG_TRY(ensure_ln_folded(g, s));
+    g->hidden.src = HID_X;
     tail = normalized(tail, with_logits);
     if ((g->flags & ZG_GPT_NO_GRAPH) || s == nullptr) {
         StepOpts o;

@@ -65,8 +65,13 @@ __device__ __forceinline__ float bf16_lo(uint32_t packed) { return __uint_as_flo
 __device__ __forceinline__ float bf16_hi(uint32_t packed) {
     return __uint_as_float(packed & 0xFFFF0000u);
 }
+// fp32 -> bf16, round to nearest even, in integer arithmetic (zg_f32_to_bf16 and the bf16 weight upload: f32_to_bf16_kernel is its one
+// caller; the GEMM and decode epilogues convert through cvt_pk_bf16 below, which keeps NaNs by itself).  The rounding increment
+// alone would carry a NaN with low payload bits out of its class (0x7FFFFFFF -> -0.0, 0xFFFFFFFF -> +0.0, 0x7F800001 -> +inf): a
+// NaN keeps its sign and upper payload and gets the quiet bit, as the hardware conversion leaves it.
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float x) {
     uint32_t b = __float_as_uint(x);
+    if ((b & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((b >> 16) | 0x0040u);
     b += 0x7FFFu + ((b >> 16) & 1u);
     return (uint16_t)(b >> 16);
 }

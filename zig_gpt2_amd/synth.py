@@ -34,10 +34,14 @@ def _rand_u64(seed, n, offset=0):
 
 
 def round_bf16(x):
-    """Round fp32 array to the nearest bf16 (ties to even), returned as fp32."""
+    """Round fp32 array to the nearest bf16 (ties to even), returned as fp32.  A NaN stays a NaN of its sign (upper payload kept,
+    quiet bit set), as the library's zg_f32_to_bf16 and weight upload leave it: the rounding increment alone would carry a NaN
+    with low payload bits into a zero or an infinity."""
     b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-    b = (b + np.uint32(0x7FFF) + ((b >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)
-    return b.view(np.float32)
+    r = (b + np.uint32(0x7FFF) + ((b >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)
+    nan = (b & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    r = np.where(nan, (b & np.uint32(0xFFFF0000)) | np.uint32(0x00400000), r).astype(np.uint32)
+    return r.view(np.float32)
 
 
 def round_b24(x):
