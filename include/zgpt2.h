@@ -304,6 +304,10 @@ enum {
                                       graph has no guided twin).  Without it zg_gpt_guide_load, zg_gpt_generate_guided_enqueue and
                                       zg_gpt_generate_fetch_guide_states are ZG_ERR_UNSUPPORTED and the handle has bit for bit the layout
                                       and behaviour it has without this flag's existence */
+    ZG_GPT_BANNED_GENERATE = 1 << 16, /* capture at create the banned twins (zg_ban_rules) of every sampler graph the other
+                                      flags name (the rule: ZG_GPT_SAMPLED_GENERATE; a greedy graph has no banned twin, and there is no
+                                      guided + banned twin).  Without it zg_gpt_generate_banned_enqueue works all the same: the graphs
+                                      are captured when the generation begins, as for penalties */
     ZG_GPT_WEIGHTS_B24 = 1 << 8  /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
                                     value rounded to nearest even at 16 mantissa bits (never to inf), row r of an [out][in]
                                     matrix = [in bf16-shaped upper halves | in low bytes].  3/4 of fp32's weight bytes, 2^-17
@@ -901,6 +905,69 @@ int zg_debug_guide_rows(const float* logits, size_t batch, size_t vocab, const z
  * states [n] and — greedy != 0 — without sampler options would return, or ZG_OK.  Needs neither a GPU nor zg_init. */
 int zg_debug_guide_check(const zg_guide* guide, size_t vocab, const zg_logit_edits* edits_or_null, const size_t* start_states, size_t n,
                          int greedy);
+/* ---- History-dependent token bans in the device loop: HF no_repeat_ngram_size, multi-token vLLM bad_words / HF
+ * bad_words_ids (zg_logit_edits.banned_ids covers single tokens only), and vLLM min_tokens / HF min_new_tokens.  The ban stage sits
+ * between the penalties and the edits: for every row it computes, on the device and from the row's history, the set of tokens
+ * forbidden at the column in flight, and writes -inf there.  Everything behind it sees the row it leaves: the edits (a bias on a
+ * banned token leaves it -inf), the sampler, zg_gpt_argmax, the log-probability record (-inf, an ordinary value in the top-N order)
+ * and the stop stage.  -inf masks commute with each other and with the edit stage, so the placement changes no result.
+ * The history h[0 .. L) of row b at step s is what zg_gpt_generate_pen_enqueue defines for the penalties, read IN ORDER: prior[b]
+ * followed by the tokens recorded at positions past_len .. s - 1 (the second feeding of the last prompt token is not a second
+ * occurrence; tokens recorded below past_len are not read).  picked = (column in flight) - (past_len + prompt_lens[b]), negative
+ * on a prompt column.
+ *   n-gram, n = no_repeat_ngram[b] (0: off; 1 .. ZG_BAN_MAX_NGRAM): if L >= n - 1, for every i in 0 .. L - n with
+ *     h[i .. i + n - 1) == h[L - n + 1 .. L), ban h[i + n - 1].  n == 1 bans every token of the history.
+ *   bad words: up to ZG_BAN_MAX_WORDS words of 1 .. ZG_BAN_MAX_WORD_LEN tokens, per call; word k is words[k * word_stride ..
+ *     + word_lens[k]).  A word w of m tokens bans w[m - 1] when L >= m - 1 and h[L - m + 1 .. L) == w[0 .. m - 1); a word of one
+ *     token is always banned.  Unlike a stop sequence, a match may reach into the prompt and the prior (HF's semantics).
+ *   min tokens: while 0 <= picked < min_tokens[b], every id of suppress_ids (up to ZG_BAN_MAX_SUPPRESS, per call) is banned.  Stop
+ *     SEQUENCES are not affected.
+ * A history token >= vocab matches nothing and bans nothing; it never becomes an address.  Several matches may ban the same token:
+ * all store the same -inf.  A row whose rules are all off is not written: it keeps its bits (a NaN payload, -0.0) beside active
+ * neighbours.
+ * The oracle: the device loop returns, token for token, the host loop over zg_gpt_sample_edit / zg_gpt_sample_each that passes
+ * banned_ids = the call's own list united with the set above (tests/ban_ref.py; zig_gpt2_amd/bans.py banned_now is the host twin
+ * for callers who draw token by token — there is no per-token C entry).
+ * Cost: two launches per step (the ban launch and the rebuild of the row-maximum partials), one beside edits, whose launch
+ * rebuilds.  The rules live in device memory (about 5 KB) and are read there: one captured graph serves every rule set. */
+#define ZG_BAN_MAX_NGRAM 16
+#define ZG_BAN_MAX_WORDS 64
+#define ZG_BAN_MAX_WORD_LEN 16
+#define ZG_BAN_MAX_SUPPRESS 16
+typedef struct {
+    size_t size;                       /* sizeof(zg_ban_rules), else ZG_ERR_ARG */
+    const size_t* no_repeat_ngram;     /* [batch] or NULL (all off) */
+    const size_t* words; size_t word_stride; const size_t* word_lens; size_t n_words;
+    const size_t* suppress_ids; size_t n_suppress;
+    const size_t* min_tokens;          /* [batch] or NULL (all 0) */
+} zg_ban_rules;
+/* zg_gpt_generate_request_enqueue (rows_or_null NULL) or zg_gpt_generate_each_enqueue (rows given; n_rows == the handle's batch)
+ * with the ban stage.  Results through the existing fetch calls.  bans NULL or all off (every n 0, no word, and no suppress id or
+ * every min_tokens 0): exactly the call without them — the same graphs, no added launch, identical bits.
+ * Refusals, all before anything is enqueued or the handle's state is touched; the message names the row or word.  ZG_ERR_ARG: a
+ * wrong size; a NULL array with a non-zero count; n above ZG_BAN_MAX_NGRAM; a word length of 0, above ZG_BAN_MAX_WORD_LEN or above
+ * word_stride; counts above the maxima; greedy (options NULL without rows) with any rule on — as with edits, greedy is top_k = 1;
+ * and rules that could leave a row without a token: with kept the size of the call's static keep set (vocab_size without allow /
+ * ban lists) and D(b) = (n_b > 0 ? min(prior_lens[b] + n_steps, vocab_size) : 0) + n_words + (min_tokens[b] > 0 ? n_suppress : 0),
+ * the call is refused when kept < 1 + max_b D(b) — a conservative bound: a row of -inf alone never reaches a kernel.  ZG_ERR_SHAPE: a
+ * word or suppress token >= vocab_size.  ZG_ERR_UNSUPPORTED: context_size > 8192 (the history sits in the LDS, as for the
+ * penalties).  A guide goes through its own entry: bans and a guide cannot be combined (a grammar compiles its bad words into the
+ * table). */
+int zg_gpt_generate_banned_enqueue(zg_gpt* g, const zg_generate_request* r, const zg_row_sampling* rows_or_null, size_t n_rows,
+                                   const zg_ban_rules* bans);
+/* The refusal a banned call with these rules on a handle of `batch` rows, `vocab` tokens and `context` positions would return —
+ * with these edits, n_steps and prior lengths (NULL: none), greedy != 0: without sampler options, guided != 0: beside a guided row
+ * (ZG_ERR_ARG) — or ZG_OK.  Needs neither a GPU nor zg_init. */
+int zg_debug_ban_check(const zg_ban_rules* bans, size_t batch, size_t vocab, size_t context, const zg_logit_edits* edits_or_null,
+                       size_t n_steps, const size_t* prior_lens_or_null, int greedy, int guided);
+/* Test entry: the ban launch, then either the rebuild of the partials or (edits given: the three lists, min_p 0) the edit launch,
+ * alone on the caller's rows: logits [batch <= 64][vocab <= 262144] (host or device, as edited_out), history [batch][history_stride]
+ * with history_lens [batch] (each <= 8192) and picked [batch] (int64_t, negative: a prompt column) on the host.  edited_out
+ * [batch][vocab]: the rows as the stages leave them; part_val_out / part_idx_out [batch][n_part], n_part = min(64, ceil(vocab /
+ * 256)): the rebuilt partials, slices as zg_debug_guide_rows documents them.  The argument refusals of a call.  Needs zg_init only. */
+int zg_debug_ban_rows(const float* logits, size_t batch, size_t vocab, const zg_ban_rules* bans, const size_t* history,
+                      size_t history_stride, const size_t* history_lens, const int64_t* picked, const zg_logit_edits* edits_or_null,
+                      float* edited_out, float* part_val_out, int32_t* part_idx_out);
 /* tokens of positions first .. first + n - 1 of the last generation(s): out_tokens [batch, n] */
 int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len);
 /* Test entry: the sampler kernels of zg_gpt_sample_ex on the caller's logits [batch <= 64, vocab <= 262144] (host or device, as

@@ -86,6 +86,13 @@ class Guide(C.Structure):
     _fields_ = [("n_states", sz), ("next", vp)]
 
 
+class BanRules(C.Structure):
+    """zg_ban_rules of include/zgpt2.h (`size` is filled by ban_rules())."""
+
+    _fields_ = [("size", sz), ("no_repeat_ngram", vp), ("words", vp), ("word_stride", sz), ("word_lens", vp), ("n_words", sz), ("suppress_ids", vp),
+                ("n_suppress", sz), ("min_tokens", vp)]
+
+
 class GenerateRequest(C.Structure):
     """zg_generate_request of include/zgpt2.h (`size` is filled by generate_request())."""
 
@@ -211,6 +218,9 @@ SIGNATURES = {
     "zg_gpt_generate_fetch_guide_states": (C.c_int, [vp, sz, sz, vp, sz]),
     "zg_debug_guide_rows": (C.c_int, [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
     "zg_debug_guide_check": (C.c_int, [vp, sz, vp, vp, sz, C.c_int]),
+    "zg_gpt_generate_banned_enqueue": (C.c_int, [vp, vp, vp, sz, vp]),
+    "zg_debug_ban_check": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, C.c_int, C.c_int]),
+    "zg_debug_ban_rows": (C.c_int, [vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]),
     "zg_gpt_score": (C.c_int, [vp, sz, vp, sz, sz, sz, vp, sz]),
     "zg_debug_score_rows": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, vp, vp]),
     "zg_gpt_time_kernel": (C.c_int, [vp, C.c_int, C.c_int, f32p, szp]),
@@ -234,6 +244,8 @@ GPT_SCORE = 4096
 GPT_STOP_GENERATE = 8192
 GPT_EDITED_GENERATE = 16384
 GPT_GUIDED_GENERATE = 32768
+GPT_BANNED_GENERATE = 65536
+BAN_MAX_NGRAM, BAN_MAX_WORDS, BAN_MAX_WORD_LEN, BAN_MAX_SUPPRESS = 16, 64, 16, 16
 GUIDE_MAX_STATES, GUIDE_DEAD, GUIDE_NONE = 256, 0xFFFF, (1 << 64) - 1
 EDIT_MAX_BIAS = 512
 LOGPROBS_TOP_MAX = 20
@@ -255,6 +267,33 @@ def stop_conditions(stop_token_ids=None, stop=None, lookahead=0):
         mat[k, : len(q)] = q
     c = StopConditions(ptr(ids) if ids.size else None, ids.size, ptr(mat) if seqs else None, stride, ptr(lens) if seqs else None, len(seqs), int(lookahead))
     return c, (ids, mat, lens)
+
+
+def ban_rules(batch, no_repeat_ngram_size=0, bad_words_ids=None, min_tokens=0, suppress_token_ids=None):
+    """zg_ban_rules for `batch` rows from an n-gram size and a min-tokens count (an int for every row, or one per row), a list of bad
+    words (token-id lists) and the suppress ids: (the structure, the arrays it points into — keep them alive while it is in use)."""
+    import numpy as np
+
+    def per_row(v, name):
+        a = np.asarray(v, dtype=np.int64).reshape(-1)
+        if np.ndim(v) == 0:
+            a = np.repeat(a, batch)
+        if a.size != batch or (a < 0).any():
+            raise ValueError(f"{name}: {v!r} for a batch of {batch}")
+        return np.ascontiguousarray(a, dtype=np.uint64)
+
+    ngram = per_row(no_repeat_ngram_size, "no_repeat_ngram_size")
+    mins = per_row(min_tokens, "min_tokens")
+    words = [np.ascontiguousarray(w, dtype=np.uint64).reshape(-1) for w in (bad_words_ids or [])]
+    lens = np.ascontiguousarray([len(w) for w in words], dtype=np.uint64)
+    stride = max([len(w) for w in words] + [1])
+    mat = np.zeros((len(words), stride), np.uint64)
+    for k, w in enumerate(words):
+        mat[k, : len(w)] = w
+    supp = np.ascontiguousarray([] if suppress_token_ids is None else suppress_token_ids, dtype=np.uint64).reshape(-1)
+    r = BanRules(C.sizeof(BanRules), ptr(ngram), ptr(mat) if words else None, stride, ptr(lens) if words else None, len(words),
+                 ptr(supp) if supp.size else None, supp.size, ptr(mins))
+    return r, (ngram, mins, mat, lens, supp)
 
 
 def logit_edits(logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_p=0.0):

@@ -235,6 +235,13 @@ struct zg_gpt {
         size_t loaded;  // states of the table the handle holds (0: none)
         bool valid;     // the last generation came through zg_gpt_generate_guided_enqueue: the record can be fetched
     } guide;
+    // generate — history-dependent bans (sample_ban.h): the rules of the call in flight — one small block carved
+    // behind everything else in the arena —, its pinned mirror, and plain host memory in which a call's rules are laid out once they
+    // are checked (build).  The history is the penalties' (pen.prior staged whenever penalties OR bans are on, and the loop's record)
+    struct {
+        BanRules *rules, *h_rules;
+        BanRules build;
+    } ban;
     // generate — a generation in flight between gen_begin and gen_end (zg_gpt_generate_enqueue / _many), and what the last one left
     struct {
         size_t pos, n, min_prompt, since_sync;
@@ -317,7 +324,7 @@ struct StepKey {
     bool with_logits, multi;
     StepTail tail;
 };
-constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2 * 2 * 2 * 2;  // the radices of step_index
+constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2 * 2 * 2 * 2 * 2;  // the radices of step_index
 
 // What body() enqueues on stream cs, captured and instantiated into *out.  Nothing is left behind on failure.
 template <class Body>

@@ -174,6 +174,8 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
         g->guide.state = (int*)P(kRowsMax * 4);
         g->guide.rec = (int*)P(B * C * 4);
     }
+    // (and behind that: the ban stage's rules, about 5 KB — no buffer above moves)
+    g->ban.rules = (BanRules*)P(sizeof(BanRules));
     g->state_bytes = (cv.off + 255) & ~(size_t)255;
 }
 
@@ -240,6 +242,7 @@ void release(zg_gpt* g) {
     if (g->lp.h_rec) (void)hipHostFree(g->lp.h_rec);
     if (g->stop.pinned) (void)hipHostFree(g->stop.pinned);
     if (g->edit.h_block) (void)hipHostFree(g->edit.h_block);
+    if (g->ban.h_rules) (void)hipHostFree(g->ban.h_rules);
     delete g;
 }
 
@@ -276,6 +279,8 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->stop.pinned), sizeof(*g->stop.pinned), hipHostMallocDefault);
     // (the edit stage's mirror: the bias table and the keep bitmap)
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->edit.h_block), edit_block_bytes(c.vocab_size), hipHostMallocDefault);
+    // (the ban stage's mirror: the rules of a call)
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&g->ban.h_rules), sizeof(BanRules), hipHostMallocDefault);
     if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(control mirrors)", __FILE__, __LINE__);
     g->edit.build.assign(edit_block_bytes(c.vocab_size), 0);
     memset(g->stop.pinned, 0, sizeof(*g->stop.pinned));

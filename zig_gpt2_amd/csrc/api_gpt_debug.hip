@@ -598,6 +598,76 @@ int zg_debug_guide_rows(const float* logits, size_t batch, size_t vocab, const z
     return ZG_OK;
 }
 
+// The ban stage on the caller's rows (tests): the ban launch, then the rebuild of the partials or — edits with a list
+// given — the edit launch, which rebuilds them itself.  The history is the caller's, in order, a token outside the vocabulary
+// included (it must match nothing); `picked` says where each row stands (no control block).  The rules are checked as a call's are,
+// except for the bound that keeps a row from being emptied: a harness row may be left all -inf.  Allocates per call.
+int zg_debug_ban_rows(const float* logits, size_t batch, size_t vocab, const zg_ban_rules* bans, const size_t* history, size_t history_stride,
+                      const size_t* history_lens, const int64_t* picked, const zg_logit_edits* edits, float* edited_out, float* part_val_out,
+                      int32_t* part_idx_out) {
+    ZG_TRY(require_init());
+    const char* who = "debug_ban_rows";
+    ZG_REQUIRE(logits && bans && history_lens && picked && edited_out && part_val_out && part_idx_out && batch >= 1 && batch <= (size_t)kBanMaxRows && vocab >= 1 &&
+                   vocab <= (size_t)64 * 4096,
+               ZG_ERR_ARG, "%s: bad argument", who);
+    ZG_REQUIRE(!edits || edits->min_p == 0.0f, ZG_ERR_ARG, "%s: edits->min_p %f (the lists only)", who, edits->min_p);
+    size_t longest = 0;
+    for (size_t b = 0; b < batch; ++b) {
+        ZG_REQUIRE(history_lens[b] <= history_stride && (history_lens[b] == 0 || history), ZG_ERR_SHAPE, "%s: row %zu lists %zu tokens (stride %zu)", who, b,
+                   history_lens[b], history_stride);
+        longest = std::max(longest, history_lens[b]);
+    }
+    ZG_REQUIRE(longest <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED, "%s: a history of %zu tokens exceeds the %d the LDS holds", who, longest, kPenMaxHistory);
+    std::vector<char> block(edits ? edit_block_bytes(vocab) : 0);
+    bool stage_on = false, on = false;
+    if (edits) ZG_TRY(build_edits(edits, vocab, who, block.data(), &stage_on));
+    ZG_TRY(check_bans(bans, batch, vocab, longest, (size_t)-1, 0, nullptr, false, false, who, &on));
+    std::vector<BanRules> rules(1);
+    fill_bans(rules.data(), *bans, batch, 0);
+    const int B = (int)batch, V = (int)vocab, n_part = std::min(64, (V + 255) / 256);
+    const size_t stride = std::max(longest, (size_t)1);
+    std::vector<int> h_hist(batch * stride, 0), h_len(batch), h_picked(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        h_len[b] = (int)history_lens[b];
+        h_picked[b] = (int)std::min<int64_t>(std::max<int64_t>(picked[b], -1), INT_MAX);
+        for (size_t i = 0; i < history_lens[b]; ++i) h_hist[b * stride + i] = (int)std::min(history[b * history_stride + i], (size_t)INT_MAX);
+    }
+    hipStream_t s = ctx().stream;
+    DevScratch ds;
+    float *d_logits, *d_val;
+    int *d_idx, *d_hist, *d_len, *d_picked;
+    BanRules* d_rules;
+    char* d_edit;
+    ZG_TRY(ds.carve([&] {
+        d_logits = ds.take<float>(batch * vocab * 4);
+        d_val = ds.take<float>(batch * n_part * 4);
+        d_idx = ds.take<int>(batch * n_part * 4);
+        d_hist = ds.take<int>(batch * stride * 4);
+        d_len = ds.take<int>(batch * 4);
+        d_picked = ds.take<int>(batch * 4);
+        d_rules = ds.take<BanRules>(sizeof(BanRules));
+        d_edit = ds.take<char>(block.size());
+    }));
+    ZG_HIP(hipMemcpyAsync(d_logits, logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemcpyAsync(d_hist, h_hist.data(), batch * stride * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_len, h_len.data(), batch * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_picked, h_picked.data(), batch * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_rules, rules.data(), sizeof(BanRules), hipMemcpyHostToDevice, s));
+    if (stage_on) ZG_HIP(hipMemcpyAsync(d_edit, block.data(), block.size(), hipMemcpyHostToDevice, s));
+    SamplerChain c{};
+    c.logits = d_logits, c.batch = B, c.vocab = V, c.part_val = d_val, c.part_idx = d_idx, c.n_part = n_part;
+    c.edit_tab = reinterpret_cast<const EditTable*>(d_edit);
+    c.edit_keep = reinterpret_cast<const unsigned*>(d_edit + sizeof(EditTable));
+    c.hist.prior = d_hist, c.hist.prior_len = d_len, c.hist.prior_stride = (int)stride, c.hist.max_hist = (int)longest;
+    c.ban = BanArgs{d_rules, nullptr, d_picked};
+    ZG_TRY(emit_sampler_chain(c, StepTail{GREEDY, false, false, false, stage_on, false, true}, s));  // (the row stages alone: no sampler)
+    ZG_HIP(hipMemcpyAsync(edited_out, d_logits, batch * vocab * 4, hipMemcpyDefault, s));
+    ZG_HIP(hipMemcpyAsync(part_val_out, d_val, batch * n_part * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(part_idx_out, d_idx, batch * n_part * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    return ZG_OK;
+}
+
 // The penalty kernels on the caller's rows (tests): the launches of the penalised step, in place on a copy — the body of
 // zg_debug_penalize_rows (pen: the same for every row) and of zg_debug_penalize_rows_each (each: the row's own).  Allocates per call.
 static int debug_penalize_rows(const float* logits, size_t batch, size_t vocab, const zg_logit_penalties* pen, const zg_row_sampling* each,

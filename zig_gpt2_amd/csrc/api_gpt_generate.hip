@@ -38,6 +38,13 @@ static int stage_edits(zg_gpt* g, hipStream_t s) {
     return ZG_OK;
 }
 
+// The rules laid out in ban.build through their pinned mirror into the arena; the precondition is stage_edits'.
+static int stage_bans(zg_gpt* g, hipStream_t s) {
+    memcpy(g->ban.h_rules, &g->ban.build, sizeof(BanRules));
+    ZG_HIP(hipMemcpyAsync(g->ban.rules, g->ban.h_rules, sizeof(BanRules), hipMemcpyHostToDevice, s));
+    return ZG_OK;
+}
+
 // the counting kernel keeps a row's distinct tokens in an LDS table sized by the context
 static int check_pen_handle(const zg_gpt* g, const char* who) {
     ZG_REQUIRE(g->cfg.context_size <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED, "%s: context_size %zu beyond the %d tokens the penalty kernel's LDS table holds",
@@ -241,6 +248,9 @@ struct GenRequest {
     // Off: the request is what it was
     bool guide_call = false, guide_on = false;
     int guide_state[kRowsMax];
+    // history-dependent bans, checked, the rules laid out in the ONE handle's ban.build: ban_on — the ban stage runs, on
+    // the history the penalties read (prior, above).  Off: the request is what it was
+    bool ban_on = false;
     GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, size_t past = 0)
         : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past) {}
 };
@@ -262,7 +272,8 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
             ZG_REQUIRE(r.prompts[b * r.stride + i] < V, ZG_ERR_SHAPE, "generate: token %zu >= vocab %zu", r.prompts[b * r.stride + i], V);
     }
     const bool pen_on = r.pen_on && r.mode != GREEDY;
-    if (pen_on) {  // (a row's history, prior and recorded, never exceeds the context: the kernel's table is sized by it)
+    const bool ban_on = r.ban_on && r.mode != GREEDY;
+    if (pen_on || ban_on) {  // (a row's history, prior and recorded, never exceeds the context: the kernels' LDS is sized by it)
         ZG_TRY(check_pen_handle(g, "generate_pen"));
         ZG_TRY(check_history(g, r.prior, r.prior_stride, r.prior_lens, n_steps, "generate_pen"));
     }
@@ -287,7 +298,7 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
         first = min_prompt < n_steps ? min_prompt : n_steps;
     const bool edit_on = r.edit_on && r.mode != GREEDY;
     const bool guide_on = r.guide_on && r.mode != GREEDY;
-    g->gen.tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on, edit_on, guide_on};  // (normalized: pen_on / edit_on / guide_on only with a sampler, and the steps it is for have lm_head)
+    g->gen.tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on, edit_on, guide_on, ban_on};  // (normalized: pen_on / edit_on / guide_on / ban_on only with a sampler, and the steps it is for have lm_head)
     g->gen.stop_valid = false;
     g->gen.stop = r.stop_on;
     if (r.stop_on) {  // the conditions of this call; no row has finished; the stage has seen nothing (the stream is drained: the words are the host's)
@@ -302,7 +313,8 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
         memcpy(g->samp.h_params, r.sp, B * sizeof(SampleParams));
         ZG_HIP(hipMemcpyAsync(g->samp.params, g->samp.h_params, B * sizeof(SampleParams), hipMemcpyHostToDevice, s));
     }
-    if (pen_on) ZG_TRY(stage_penalties(g, r.pp, r.prior, r.prior_stride, r.prior_lens, s));
+    if (pen_on || ban_on) ZG_TRY(stage_penalties(g, r.pp, r.prior, r.prior_stride, r.prior_lens, s));  // (the prior is the history of both stages)
+    if (ban_on) ZG_TRY(stage_bans(g, s));
     if (edit_on) ZG_TRY(stage_edits(g, s));
     g->guide.valid = false;
     if (r.guide_call) {  // the new columns record "none" (every byte 0xff) until the advance of a guided row's picked column says otherwise
@@ -497,8 +509,9 @@ static int gen_run(zg_gpt* const* handles, size_t n_handles, GenRequest req) {
 // each (zg_gpt_generate_each_enqueue): the table of the call, one zg_row_sampling per row of the handle, in the place of q.options /
 // q.penalties / q.edits->min_p / q.seed; null: the uniform request, whose table is `batch` equal rows.
 // guide (zg_gpt_generate_guided_enqueue): the start state of every row of the handle, which has ZG_GPT_GUIDED_GENERATE; null: no guide.
+// bans (zg_gpt_generate_banned_enqueue): the ban rules of the call; null or all off: the request is what it was.
 static int generate_request(zg_gpt* const* handles, size_t n_handles, const zg_generate_request& q, const char* who, const zg_row_sampling* each = nullptr,
-                            size_t n_each = 0, const size_t* guide = nullptr) {
+                            size_t n_each = 0, const size_t* guide = nullptr, const zg_ban_rules* bans = nullptr) {
     ZG_TRY(require_init());
     zg_gpt* const g = handles[0];
     ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "%s: null argument", who);
@@ -541,6 +554,16 @@ static int generate_request(zg_gpt* const* handles, size_t n_handles, const zg_g
         ZG_TRY(plan_rows(rows, g->batch, g->cfg.vocab_size, q.past_len, who, r.sp, r.pp, nullptr, &plan));
     }
     if (q.options || each) r.mode = plan.sampler;
+    if (bans) {  // (behind the edits: the rules are judged against the size of the call's own keep set, built above in edit.build)
+        ZG_TRY(check_bans(bans, g->batch, g->cfg.vocab_size, g->cfg.context_size, edits_kept(r.edit_on ? g->edit.build.data() : nullptr, g->cfg.vocab_size),
+                          q.n_steps, q.prior ? q.prior_lens : nullptr, !q.options && !each, guide != nullptr, who, &r.ban_on));
+        if (r.ban_on) {
+            fill_bans(&g->ban.build, *bans, g->batch, q.past_len);
+            r.prior = q.prior;
+            r.prior_stride = q.prior_stride;
+            r.prior_lens = q.prior_lens;
+        }
+    }
     if (guide) {  // (behind the edits: an empty kept set is judged against the call's own keep bitmap, built above in edit.build)
         const unsigned* call_keep = r.edit_on ? reinterpret_cast<const unsigned*>(g->edit.build.data() + sizeof(EditTable)) : nullptr;
         ZG_TRY(check_guide_call(g->guide.loaded ? g->guide.h_keep.data() : nullptr, g->guide.loaded, g->cfg.vocab_size, call_keep, guide, g->batch,
@@ -640,6 +663,13 @@ int zg_gpt_generate_each_enqueue(zg_gpt* g, const zg_generate_request* r, const 
     ZG_REQUIRE(r != nullptr && r->size == sizeof(zg_generate_request), ZG_ERR_ARG, "generate_each: null request, or its size field is not sizeof(zg_generate_request)");
     ZG_REQUIRE(rows != nullptr, ZG_ERR_ARG, "generate_each: rows is null");
     return generate_request(&g, 1, *r, "generate_each", rows, n_rows);
+}
+
+// ---- History-dependent bans: the request call or, with rows, the per-row call, plus the rules
+int zg_gpt_generate_banned_enqueue(zg_gpt* g, const zg_generate_request* r, const zg_row_sampling* rows, size_t n_rows, const zg_ban_rules* bans) {
+    ZG_REQUIRE(r != nullptr && r->size == sizeof(zg_generate_request), ZG_ERR_ARG, "generate_banned: null request, or its size field is not sizeof(zg_generate_request)");
+    ZG_REQUIRE(rows != nullptr || n_rows == 0, ZG_ERR_ARG, "generate_banned: %zu rows but rows is null", n_rows);
+    return generate_request(&g, 1, *r, "generate_banned", rows, n_rows, nullptr, bans);
 }
 
 // ---- Guided decoding

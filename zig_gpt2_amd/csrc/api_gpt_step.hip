@@ -87,12 +87,12 @@ PenHistory pen_history(const zg_gpt* g, bool loop) {
 }
 
 size_t step_index(StepKey k) {
-    return (((((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp) * 2 + k.tail.stop) * 2 + k.tail.edit) * 2 + k.tail.guide;
+    return ((((((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp) * 2 + k.tail.stop) * 2 + k.tail.edit) * 2 + k.tail.guide) * 2 + k.tail.ban;
 }
 
 // The tails whose graphs zg_gpt_create captures besides the default one, by the handle's flags: each *_GENERATE flag names the
 // samplers it is for, ZG_GPT_LOGPROBS_GENERATE the twins with the log-probability stage of the default tail and of those, and
-// ZG_GPT_GUIDED_GENERATE the guided twins of the sampler tails, ZG_GPT_STOP_GENERATE the twins with the stop stage of all of these
+// ZG_GPT_GUIDED_GENERATE the guided twins of the sampler tails, ZG_GPT_BANNED_GENERATE their banned twins, ZG_GPT_STOP_GENERATE the twins with the stop stage of all of these
 std::vector<StepTail> tails_of_flags(unsigned flags) {
     std::vector<StepTail> t;
     if (flags & ZG_GPT_SAMPLED_GENERATE) t.push_back({PLAIN, false, false});
@@ -108,15 +108,20 @@ std::vector<StepTail> tails_of_flags(unsigned flags) {
         const size_t n = t.size();
         for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, false, false, t[i].edit, true});
     }
+    if (flags & ZG_GPT_BANNED_GENERATE) {  // the banned twin of every unguided sampler tail above (no greedy, no guided + banned twin)
+        const size_t n = t.size();
+        for (size_t i = 0; i < n; ++i)
+            if (!t[i].guide) t.push_back({t[i].sampler, t[i].pen, false, false, t[i].edit, false, true});
+    }
     if (flags & ZG_GPT_LOGPROBS_GENERATE) {
         const size_t n = t.size();
         t.push_back({GREEDY, false, true});
-        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, true, false, t[i].edit, t[i].guide});
+        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, true, false, t[i].edit, t[i].guide, t[i].ban});
     }
     if (flags & ZG_GPT_STOP_GENERATE) {  // the stop twins of the default tail and of everything above
         const size_t n = t.size();
         t.push_back({GREEDY, false, false, true});
-        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, t[i].lp, true, t[i].edit, t[i].guide});
+        for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, t[i].lp, true, t[i].edit, t[i].guide, t[i].ban});
     }
     return t;
 }
@@ -334,6 +339,7 @@ SamplerChain handle_chain(const zg_gpt* g, bool loop) {
     c.edit_tab = g->edit.tab, c.edit_keep = g->edit.keep;
     c.guide = GuideArgs{g->guide.next, g->guide.keep, g->guide.n_states, g->guide.state, g->guide.rec, (int)g->cfg.context_size, loop ? g->ctrl : nullptr,
                         g->prompt_len};
+    c.ban = BanArgs{g->ban.rules, g->prompt_len, nullptr};
     c.params = g->samp.params, c.seg_ws = g->samp.ws, c.filt = g->samp.filt;
     if (loop) c.ctrl = g->ctrl, c.pick = g->samp.sampled;
     return c;

@@ -1,6 +1,6 @@
 // sample.hip — the head of a decode step and the stages of the device sampler behind lm_head (model tier): embed_step_kernel,
 // the plain sampler's three kernels, and — as included headers, one per stage — truncation (sample_filter.h), penalties
-// (sample_penalty.h), logit edits (sample_edit.h), guided decoding (sample_guide.h), log-probabilities (sample_logprob.h), scoring (sample_score.h) and the stop
+// (sample_penalty.h), history-dependent bans (sample_ban.h), logit edits (sample_edit.h), guided decoding (sample_guide.h), log-probabilities (sample_logprob.h), scoring (sample_score.h) and the stop
 // conditions (sample_stop.h), with every stage's launcher and workspace carver.  What the stages share — the pick from lm_head's
 // argmax partials, the row maximum, the rebuild of a slice's partial — is in sample_common.h; the order of picks itself
 // (pick_before), clamp_token and counter_uniform are in zg_common.h.
@@ -295,6 +295,7 @@ __global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vo
 
 #include "sample_filter.h"
 #include "sample_penalty.h"
+#include "sample_ban.h"
 #include "sample_edit.h"
 #include "sample_guide.h"
 #include "sample_logprob.h"
@@ -415,6 +416,23 @@ int launch_penalize(float* logits, int batch, int vocab, const PenParams* params
     hipLaunchKernelGGL(penalty_apply_kernel, dim3(batch), dim3(256), lds, s, logits, vocab, params, h, slots, counts_out);
     ZG_HIP(hipGetLastError());
     if (!rebuild) return ZG_OK;
+    hipLaunchKernelGGL(row_argmax_partials_kernel, dim3(n_part, batch), dim3(256), 0, s, logits, vocab, part_val, part_idx);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_ban(float* logits, int batch, int vocab, const BanArgs& a, const PenHistory& h, hipStream_t s) {
+    ZG_REQUIRE(logits && a.rules && (h.ctrl ? a.prompt_len != nullptr : a.picked != nullptr) && batch >= 1 && batch <= kBanMaxRows && vocab >= 1, ZG_ERR_ARG,
+               "bans: missing argument");
+    ZG_REQUIRE(h.max_hist >= 0 && h.max_hist <= kPenMaxHistory, ZG_ERR_UNSUPPORTED, "bans: a history of %d tokens exceeds the %d the LDS holds", h.max_hist,
+               kPenMaxHistory);
+    hipLaunchKernelGGL(ban_apply_kernel, dim3(batch), dim3(256), (size_t)h.max_hist * sizeof(int), s, logits, vocab, a, h);  // (at most 32 KB: no opt-in)
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_row_argmax_partials(const float* logits, int batch, int vocab, float* part_val, int* part_idx, int n_part, hipStream_t s) {
+    ZG_REQUIRE(logits && part_val && part_idx && batch >= 1 && vocab >= 1 && n_part >= 1 && n_part <= 4096, ZG_ERR_ARG, "row_argmax_partials: bad argument");
     hipLaunchKernelGGL(row_argmax_partials_kernel, dim3(n_part, batch), dim3(256), 0, s, logits, vocab, part_val, part_idx);
     ZG_HIP(hipGetLastError());
     return ZG_OK;

@@ -24,15 +24,16 @@ struct StepTail {
     SamplerMode sampler = GREEDY;
     bool pen = false, lp = false, stop = false, edit = false;
     bool guide = false;  // guided decoding: the mask behind (and in one launch with) the edits, the advance behind the sampler
+    bool ban = false;    // history-dependent bans: the ban launch between the penalties and the edits
     bool operator==(const StepTail& o) const {
-        return sampler == o.sampler && pen == o.pen && lp == o.lp && stop == o.stop && edit == o.edit && guide == o.guide;
+        return sampler == o.sampler && pen == o.pen && lp == o.lp && stop == o.stop && edit == o.edit && guide == o.guide && ban == o.ban;
     }
 };
 // The tail a step can have: nothing is drawn from a step without lm_head (the default tail), and a greedy pick has neither
-// penalties, edits nor a guide
+// penalties, edits, a guide nor bans
 static inline StepTail normalized(StepTail t, bool with_logits) {
     if (!with_logits) return StepTail{};
-    if (t.sampler == GREEDY) t.pen = t.edit = t.guide = false;
+    if (t.sampler == GREEDY) t.pen = t.edit = t.guide = t.ban = false;
     return t;
 }
 
@@ -53,6 +54,7 @@ struct SamplerChain {
     const EditTable* edit_tab;
     const unsigned* edit_keep;
     GuideArgs guide;  // the automaton, the rows' states and (the loop) the column in flight
+    BanArgs ban;      // the rules of the call and where each row stands (the history is `hist`, the penalties')
     const SampleParams* params;
     float* seg_ws;
     FilterWs filt;
@@ -76,6 +78,10 @@ size_t guide_keep_words(size_t vocab);
 int build_guide(const zg_guide* gd, size_t vocab, const char* who, unsigned* keep);
 int check_guide_call(const unsigned* guide_keep, size_t n_states, size_t vocab, const unsigned* call_keep, const size_t* start_states, size_t n, bool greedy,
                      const char* who, int* states_out, bool* any_out);
+int check_bans(const zg_ban_rules* r, size_t batch, size_t vocab, size_t context, size_t kept, size_t n_steps, const size_t* prior_lens, bool greedy,
+               bool guided, const char* who, bool* on_out);
+void fill_bans(BanRules* d, const zg_ban_rules& r, size_t batch, size_t past_len);
+size_t edits_kept(const char* block_or_null, size_t vocab);
 SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed, float min_p);
 int plan_rows(const zg_row_sampling* rows, size_t n_rows, size_t vocab, size_t past_len, const char* who, SampleParams* sp, PenParams* pp, int* forms,
               StepTail* tail);

@@ -31,7 +31,14 @@ int emit_sampler_chain(const SamplerChain& c, StepTail t, hipStream_t s) {
     // the penalties act on the raw logits, the edits on the row the penalties leave (HF's processor order); the row-maximum
     // partials every sampler starts from are rebuilt only behind the LAST stage that rewrites the row — the edit launch does it itself
     // and the guide's mask IS the edit launch where both are on: one launch rewrites the row for both and rebuilds
-    if (t.pen) ZG_TRY(launch_penalize(c.logits, c.batch, c.vocab, c.pen, c.hist, c.part_val, c.part_idx, c.n_part, c.counts, s, !t.edit && !t.guide));
+    // the ban stage sits between the two and only stores -inf: behind it the partials are rebuilt by the edit (or mask)
+    // launch where one follows, else by the rebuild launch alone
+    const bool rewritten_later = t.edit || t.guide;
+    if (t.pen) ZG_TRY(launch_penalize(c.logits, c.batch, c.vocab, c.pen, c.hist, c.part_val, c.part_idx, c.n_part, c.counts, s, !t.ban && !rewritten_later));
+    if (t.ban) {
+        ZG_TRY(launch_ban(c.logits, c.batch, c.vocab, c.ban, c.hist, s));
+        if (!rewritten_later) ZG_TRY(launch_row_argmax_partials(c.logits, c.batch, c.vocab, c.part_val, c.part_idx, c.n_part, s));
+    }
     if (t.guide)
         ZG_TRY(launch_guide_mask(c.logits, c.batch, c.vocab, t.edit ? c.edit_tab : nullptr, t.edit ? c.edit_keep : nullptr, c.guide, c.part_val, c.part_idx,
                                  c.n_part, s));
@@ -164,6 +171,82 @@ int check_guide_call(const unsigned* guide_keep, size_t n_states, size_t vocab, 
     return ZG_OK;
 }
 
+// ---- History-dependent bans (include/zgpt2.h zg_ban_rules).  The one place that checks a rule set and lays it out
+
+// the size of a call's static keep set: the popcount of the keep bitmap behind the bias table of a built edit block (build_edits
+// with the stage on), or the whole vocabulary without one
+size_t edits_kept(const char* block, size_t vocab) {
+    if (!block) return vocab;
+    const unsigned* keep = reinterpret_cast<const unsigned*>(block + sizeof(EditTable));
+    size_t kept = 0;
+    for (size_t w = 0; w < (vocab + 31) / 32; ++w) kept += (size_t)__builtin_popcount(keep[w]);
+    return kept;
+}
+
+// The refusals of a rule set for a call of `batch` rows over `vocab` tokens on a handle of `context` positions, whose static keep
+// set holds `kept` tokens, which runs n_steps steps behind priors of prior_lens[b] tokens (null: none), picks greedily (greedy) or
+// has a guided row (guided).  r null: no rules.  *on_out: some rule is on — off, the call is the one without rules and nothing but
+// the arguments' own validity is asked.
+int check_bans(const zg_ban_rules* r, size_t batch, size_t vocab, size_t context, size_t kept, size_t n_steps, const size_t* prior_lens, bool greedy,
+               bool guided, const char* who, bool* on_out) {
+    *on_out = false;
+    if (!r) return ZG_OK;
+    ZG_REQUIRE(r->size == sizeof(zg_ban_rules), ZG_ERR_ARG, "%s: the size field of the ban rules is %zu, not sizeof(zg_ban_rules)", who, r->size);
+    ZG_REQUIRE(batch >= 1 && batch <= (size_t)kBanMaxRows, ZG_ERR_ARG, "%s: ban rules for %zu rows (1 .. %d)", who, batch, kBanMaxRows);
+    ZG_REQUIRE((r->n_words == 0 || (r->words && r->word_lens)) && (r->n_suppress == 0 || r->suppress_ids), ZG_ERR_ARG,
+               "%s: ban rules: a null array with a non-zero count", who);
+    ZG_REQUIRE(r->n_words <= (size_t)ZG_BAN_MAX_WORDS && r->n_suppress <= (size_t)ZG_BAN_MAX_SUPPRESS, ZG_ERR_ARG,
+               "%s: %zu bad words / %zu suppress ids above %d / %d", who, r->n_words, r->n_suppress, ZG_BAN_MAX_WORDS, ZG_BAN_MAX_SUPPRESS);
+    bool on = r->n_words != 0;
+    for (size_t b = 0; r->no_repeat_ngram && b < batch; ++b) {
+        ZG_REQUIRE(r->no_repeat_ngram[b] <= (size_t)ZG_BAN_MAX_NGRAM, ZG_ERR_ARG, "%s: row %zu: no_repeat_ngram %zu above %d", who, b, r->no_repeat_ngram[b],
+                   ZG_BAN_MAX_NGRAM);
+        on = on || r->no_repeat_ngram[b] != 0;
+    }
+    for (size_t b = 0; r->min_tokens && b < batch; ++b) on = on || (r->min_tokens[b] != 0 && r->n_suppress != 0);
+    for (size_t k = 0; k < r->n_words; ++k)
+        ZG_REQUIRE(r->word_lens[k] >= 1 && r->word_lens[k] <= (size_t)ZG_BAN_MAX_WORD_LEN && r->word_lens[k] <= r->word_stride, ZG_ERR_ARG,
+                   "%s: bad word %zu has length %zu (1 .. %d, stride %zu)", who, k, r->word_lens[k], ZG_BAN_MAX_WORD_LEN, r->word_stride);
+    for (size_t k = 0; k < r->n_words; ++k)
+        for (size_t i = 0; i < r->word_lens[k]; ++i)
+            ZG_REQUIRE(r->words[k * r->word_stride + i] < vocab, ZG_ERR_SHAPE, "%s: token %zu of bad word %zu >= vocab %zu", who, r->words[k * r->word_stride + i], k,
+                       vocab);
+    for (size_t j = 0; j < r->n_suppress; ++j)
+        ZG_REQUIRE(r->suppress_ids[j] < vocab, ZG_ERR_SHAPE, "%s: suppress id %zu >= vocab %zu", who, r->suppress_ids[j], vocab);
+    if (!on) return ZG_OK;
+    ZG_REQUIRE(context <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED, "%s: context_size %zu beyond the %d tokens of history the ban kernel's LDS holds", who,
+               context, kPenMaxHistory);
+    ZG_REQUIRE(!greedy, ZG_ERR_ARG, "%s: ban rules without sampler options (greedy picking with bans is top_k = 1)", who);
+    ZG_REQUIRE(!guided, ZG_ERR_ARG, "%s: ban rules beside a guided row (a grammar compiles its bad words into the table)", who);
+    // a row of -inf alone never reaches a kernel: the most the rules can ban in any row, at any step, leaves a token of the keep set
+    for (size_t b = 0; b < batch; ++b) {
+        const size_t n = r->no_repeat_ngram ? r->no_repeat_ngram[b] : 0, mt = r->min_tokens ? r->min_tokens[b] : 0;
+        const size_t hist = std::min((prior_lens ? prior_lens[b] : 0) + n_steps, vocab);
+        const size_t d = (n > 0 ? hist : 0) + r->n_words + (mt > 0 ? r->n_suppress : 0);
+        ZG_REQUIRE(kept >= 1 + d, ZG_ERR_ARG, "%s: row %zu: the ban rules could forbid %zu tokens of the %zu the call keeps (no token would be left)", who, b, d,
+                   kept);
+    }
+    *on_out = true;
+    return ZG_OK;
+}
+
+// Checked rules as the kernel reads them (a null array: all off)
+void fill_bans(BanRules* d, const zg_ban_rules& r, size_t batch, size_t past_len) {
+    memset(d, 0, sizeof(*d));
+    d->n_words = (int)r.n_words;
+    d->n_suppress = (int)r.n_suppress;
+    d->past_len = (int)past_len;
+    for (size_t b = 0; b < batch; ++b) {
+        d->ngram[b] = r.no_repeat_ngram ? (int)r.no_repeat_ngram[b] : 0;
+        d->min_tokens[b] = r.min_tokens ? (int)std::min(r.min_tokens[b], (size_t)INT32_MAX) : 0;
+    }
+    for (size_t j = 0; j < r.n_suppress; ++j) d->suppress[j] = (int)r.suppress_ids[j];
+    for (size_t k = 0; k < r.n_words; ++k) {
+        d->word_len[k] = (int)r.word_lens[k];
+        for (size_t i = 0; i < r.word_lens[k]; ++i) d->words[k][i] = (int)r.words[k * r.word_stride + i];
+    }
+}
+
 // The options of a sampler call over `vocab` logits into *p, the host image of SampleParams (the caller uploads it); returns the
 // sampler they need: the plain one with both filters and min-p off, the threshold-aware tail alone for min-p alone
 SamplerMode fill_sample_params(SampleParams* p, size_t vocab, const zg_sample_options& o, uint64_t seed, float min_p) {
@@ -281,6 +364,18 @@ int zg_debug_guide_check(const zg_guide* guide, size_t vocab, const zg_logit_edi
     if (edits) ZG_TRY(build_edits(edits, vocab, "debug_guide_check", block.data(), &stage_on));
     return check_guide_call(keep.data(), guide->n_states, vocab, stage_on ? reinterpret_cast<const unsigned*>(block.data() + sizeof(EditTable)) : nullptr,
                             start_states, n, greedy != 0, "debug_guide_check", nullptr, &any);
+}
+
+// check_bans' face (tests; no GPU, no zg_init): the refusal of a banned call with these rules, the edits' own refusals included
+int zg_debug_ban_check(const zg_ban_rules* bans, size_t batch, size_t vocab, size_t context, const zg_logit_edits* edits, size_t n_steps,
+                       const size_t* prior_lens, int greedy, int guided) {
+    ZG_REQUIRE(vocab >= 1 && vocab <= (size_t)64 * 4096 && batch >= 1 && batch <= (size_t)kBanMaxRows, ZG_ERR_ARG, "debug_ban_check: vocab %zu, %zu rows", vocab,
+               batch);
+    std::vector<char> block(edit_block_bytes(vocab));
+    bool stage_on = false, on = false;
+    if (edits) ZG_TRY(build_edits(edits, vocab, "debug_ban_check", block.data(), &stage_on));
+    return check_bans(bans, batch, vocab, context, edits_kept(stage_on ? block.data() : nullptr, vocab), n_steps, prior_lens, greedy != 0, guided != 0,
+                      "debug_ban_check", &on);
 }
 
 int zg_debug_min_p_offset(float temp, float min_p, float* d_out) {

@@ -527,6 +527,38 @@ int launch_guide_mask(float* logits, int batch, int vocab, const EditTable* tab_
                       int* part_idx, int n_part, hipStream_t s);
 int launch_guide_advance(const GuideArgs& g, const int* picks, int batch, int vocab, hipStream_t s);
 
+// History-dependent token bans (sample_ban.h; include/zgpt2.h zg_ban_rules): no-repeat n-grams, multi-token bad words and the
+// suppress list of min-tokens, between the penalties and the edits.  BanRules is the device block of a call's rules (one block,
+// read on the device and clamped there, so one captured launch serves every rule set): row b's n-gram size and min-tokens, the
+// words table, the suppress ids, and past_len — the first recorded position that belongs to the history (generate loop).
+// ONE launch, one workgroup of 256 threads per row: the row's history (PenHistory, read IN ORDER: prior, then the loop's record;
+// lengths clamped as penalty_apply_kernel clamps them, max_hist <= kPenMaxHistory ints of LDS) goes into the LDS, its suffix is
+// compared against every window and every word, and each match stores -inf to its token after a bounds check.  picked of row b:
+// ctrl->seq_len - 1 - prompt_len[b] (the loop), or picked[b] (ctrl null: the row harness).  A row whose rules are all off at this
+// column returns before it touches anything.  The row-maximum partials are NOT rebuilt here: launch_row_argmax_partials, or the
+// edit launch behind it, does that.
+constexpr int kBanMaxNgram = 16;     // ZG_BAN_MAX_NGRAM of the header
+constexpr int kBanMaxWords = 64;     // ZG_BAN_MAX_WORDS
+constexpr int kBanMaxWordLen = 16;   // ZG_BAN_MAX_WORD_LEN
+constexpr int kBanMaxSuppress = 16;  // ZG_BAN_MAX_SUPPRESS
+constexpr int kBanMaxRows = 64;      // rows of the harness (a handle has at most 8)
+struct BanRules {
+    int n_words, n_suppress, past_len, pad;
+    int ngram[kBanMaxRows];
+    int min_tokens[kBanMaxRows];
+    int suppress[kBanMaxSuppress];
+    int word_len[kBanMaxWords];
+    int words[kBanMaxWords][kBanMaxWordLen];
+};
+struct BanArgs {
+    const BanRules* rules;
+    const int* prompt_len;  // [batch] (with hist.ctrl), absolute
+    const int* picked;      // [batch] (without hist.ctrl)
+};
+int launch_ban(float* logits, int batch, int vocab, const BanArgs& a, const PenHistory& h, hipStream_t s);
+// part_val / part_idx [batch][n_part] rebuilt from the rows as they stand (launch_penalize's second launch, alone)
+int launch_row_argmax_partials(const float* logits, int batch, int vocab, float* part_val, int* part_idx, int n_part, hipStream_t s);
+
 // The log-probability stage behind the sampler (sample_logprob.h; include/zgpt2.h zg_gpt_generate_logprobs_enqueue): for every row,
 // the log-probability of the token the step records and the *top_n (device memory, 0 .. 20) largest logits with theirs, written
 // into column ctrl->seq_len - 1 of the record buffers (ctrl null: column 0) — NaN where that column is below prompt_len[b] (null:

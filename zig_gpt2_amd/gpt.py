@@ -32,7 +32,7 @@ class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
                  sampled_generate=False, weights_b24=False, truncated_generate=False, penalized_generate=False, logprobs_generate=False,
-                 score=False, stop_generate=False, edited_generate=False, guided=False):
+                 score=False, stop_generate=False, edited_generate=False, guided=False, banned_generate=False):
         """share_weights_with / own_stream / stream_priority: zg_gpt_options of zg_gpt_create_ex (a handle of an independent
         prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config).
         weights_b24: matrices stored as 24-bit floats (ZG_GPT_WEIGHTS_B24: each fp32 weight rounded to 16 mantissa bits, 3/4 of
@@ -44,7 +44,9 @@ class GPT:
         stop_generate: the stop twins of every graph create captures (ZG_GPT_STOP_GENERATE), as the other *_generate flags.
         edited_generate: the graphs of generations with logit edits or min-p (ZG_GPT_EDITED_GENERATE), as the other *_generate flags.
         guided: guided decoding (ZG_GPT_GUIDED_GENERATE) — carve the automaton's table, bitmaps, states and record, and
-        capture the guided twins of the sampler graphs create captures; without it `load_guide` and guide_states raise ZG_ERR_UNSUPPORTED."""
+        capture the guided twins of the sampler graphs create captures; without it `load_guide` and guide_states raise ZG_ERR_UNSUPPORTED.
+        banned_generate: the banned twins (no_repeat_ngram_size / bad_words_ids / min_tokens; ZG_GPT_BANNED_GENERATE) of the
+        sampler graphs create captures, as the other *_generate flags; without it such a generation captures its graphs when it begins."""
         self.config, self.batch = config, batch
         L = _lib.load()
         flags = (_lib.GPT_WEIGHTS_F32 if weights_f32 else 0) | (0 if use_graph else _lib.GPT_NO_GRAPH)
@@ -62,6 +64,7 @@ class GPT:
         flags |= _lib.GPT_STOP_GENERATE if stop_generate else 0
         flags |= _lib.GPT_EDITED_GENERATE if edited_generate else 0
         flags |= _lib.GPT_GUIDED_GENERATE if guided else 0
+        flags |= _lib.GPT_BANNED_GENERATE if banned_generate else 0
         cfg = _lib.GptConfig(config.vocab_size, config.context_size, config.n_layer, config.n_heads, config.n_embed)
         h = C.c_void_p()
         if share_weights_with is None and not own_stream:
@@ -275,19 +278,35 @@ class GPT:
             raise ValueError("allowed_token_ids is empty: no token could be picked")
         return _lib.logit_edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
 
-    def _request_enqueue(self, past, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, conds, edits, guide_states=None):
+    def _bans(self, no_repeat_ngram_size, bad_words_ids, min_tokens, suppress_token_ids, stop_token_ids=None):
+        """(zg_ban_rules, its arrays), or None while every rule is off (the call is then today's, through today's entry point).
+        no_repeat_ngram_size / min_tokens: one value for every row, or one per row.  suppress_token_ids None: the call's stop_token_ids."""
+        if suppress_token_ids is None:
+            suppress_token_ids = stop_token_ids
+        n_on = bool(np.any(np.asarray(no_repeat_ngram_size) != 0))
+        min_on = bool(np.any(np.asarray(min_tokens) != 0)) and suppress_token_ids is not None and len(suppress_token_ids) > 0
+        if not n_on and not bad_words_ids and not min_on:
+            return None
+        return _lib.ban_rules(self.batch, no_repeat_ngram_size, bad_words_ids, min_tokens, suppress_token_ids)
+
+    def _request_enqueue(self, past, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, conds, edits, guide_states=None, bans=None):
         """zg_gpt_generate_request_enqueue: the one call every generation with penalties, log-probabilities, stop conditions or
         edits goes through.  conds: a zg_stop_conditions or None; edits: `_edits(...)`.  guide_states (one start state per row, None
-        for a row without a guide): the same request through zg_gpt_generate_guided_enqueue."""
-        if (pen is not None or edits is not None) and temp is None:
-            raise ValueError("penalties and edits need a sampler: greedy picking with them is temp=1.0, top_k=1")
+        for a row without a guide): the same request through zg_gpt_generate_guided_enqueue.  bans (`_bans(...)`): through
+        zg_gpt_generate_banned_enqueue."""
+        if (pen is not None or edits is not None or bans is not None) and temp is None:
+            raise ValueError("penalties, edits and bans need a sampler: greedy picking with them is temp=1.0, top_k=1")
+        if bans is not None and guide_states is not None:
+            raise ValueError("ban rules and a guide cannot be combined: a grammar compiles its bad words into the table")
         opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
-        pp, pstride, plens, keep = self._token_lists(prior if pen is not None else None)
+        pp, pstride, plens, keep = self._token_lists(prior if pen is not None or bans is not None else None)
         r = _lib.generate_request(past_len=past, prompts=ptr(mat), prompt_stride=stride, prompt_lens=ptr(lens), n_steps=n_steps,
                                   options=None if opt is None else C.addressof(opt), penalties=None if pen is None else C.addressof(pen), prior=pp,
                                   prior_stride=pstride, prior_lens=plens, seed=seed, logprobs=int(logprobs is not None), top_n=int(logprobs or 0),
                                   stop=None if conds is None else C.addressof(conds), edits=None if edits is None else C.addressof(edits[0]))
-        if guide_states is None:
+        if bans is not None:
+            check(self._L.zg_gpt_generate_banned_enqueue(self.h, C.addressof(r), None, 0, C.addressof(bans[0])))
+        elif guide_states is None:
             check(self._L.zg_gpt_generate_request_enqueue(self.h, C.addressof(r)))
         else:
             states = self._guide_states(guide_states)
@@ -328,13 +347,13 @@ class GPT:
         return ptr(mat), stride, ptr(lens), (mat, lens)
 
     def _generate_stop(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits=None,
-                       guide_states=None):
+                       guide_states=None, bans=None):
         """A generation with stop conditions (the request call): what `_generate` returns, cut at `end` —
         columns past_len .. end - 1.  `stop_result()` tells where every row finished and why."""
         past = past_len or 0
         mat, lens, stride = self._prompts(prompts)
         conds, keep_conds = _lib.stop_conditions(stop_token_ids, stop, lookahead)
-        self._request_enqueue(past, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, conds, edits, guide_states)
+        self._request_enqueue(past, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, conds, edits, guide_states, bans)
         del keep_conds
         n = self.stop_result()[0] - past if conds.n_ids or conds.n_seqs else n_steps  # (no conditions: the plain call ran)
         out = self.generate_fetch_range(past, n)
@@ -350,21 +369,21 @@ class GPT:
         check(self._L.zg_gpt_generate_stop_result(self.h, C.byref(end), ptr(cols), ptr(reasons)))
         return end.value, [None if int(c) == _lib.STOP_NONE else int(c) for c in cols], [int(r) for r in reasons]
 
-    def _generate(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=True, edits=None, guide_states=None):
+    def _generate(self, past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=True, edits=None, guide_states=None, bans=None):
         """Every generation of this class: enqueue through the entry point its arguments ask for, then (fetch) return what the
         public method returns.  past_len None: not a continuation.  temp None: greedy.  pen: `_penalties(...)`.  logprobs: top_n or
         None.  edits: `_edits(...)`.  With penalties, log-probabilities and edits off the plain entry points run
         (zg_gpt_generate_greedy / _enqueue, zg_gpt_generate_sample[_ex][_enqueue], zg_gpt_generate_from_enqueue), else the request
         call (zg_gpt_generate_request_enqueue)."""
-        if (pen is not None or edits is not None) and temp is None:
-            raise ValueError("penalties and edits need a sampler: greedy picking with them is temp=1.0, top_k=1")
+        if (pen is not None or edits is not None or bans is not None) and temp is None:
+            raise ValueError("penalties, edits and bans need a sampler: greedy picking with them is temp=1.0, top_k=1")
         mat, lens, stride = self._prompts(prompts)
         head = (ptr(mat), stride, ptr(lens), n_steps)
         opt = None if temp is None else _lib.SampleOptions(temp, top_k, top_p)
         opt_p = None if opt is None else C.addressof(opt)
         out = None
-        if logprobs is not None or pen is not None or edits is not None or guide_states is not None:
-            self._request_enqueue(past_len or 0, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, None, edits, guide_states)
+        if logprobs is not None or pen is not None or edits is not None or guide_states is not None or bans is not None:
+            self._request_enqueue(past_len or 0, mat, stride, lens, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, None, edits, guide_states, bans)
         elif past_len is not None:
             check(self._L.zg_gpt_generate_from_enqueue(self.h, past_len, *head, opt_p, seed))
         elif fetch:  # the calls that enqueue and fetch in one
@@ -465,24 +484,29 @@ class GPT:
 
     def generate_from(self, past_len, prompts, n_steps, temp=None, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
                       frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0, logit_bias=None,
-                      allowed_token_ids=None, banned_token_ids=None, min_p=0.0, guide_states=None):
+                      allowed_token_ids=None, banned_token_ids=None, min_p=0.0, guide_states=None, no_repeat_ngram_size=0, bad_words_ids=None,
+                      min_tokens=0, suppress_token_ids=None):
         """generate entered at position past_len (zg_gpt_generate_from_enqueue): `prompts` are the new tokens of each row, fed
         behind the past_len cached positions; returns the tokens of positions past_len .. past_len + n_steps - 1 ([batch, n_steps]).
         temp=None: greedy; otherwise the sampler of generate_sample (top_k / top_p as there).  Penalties as generate_sample; the
         tokens below past_len count only when passed as `prior` (one list per row).  logprobs=top_n: as `generate`, for the
         columns past_len .. past_len + n_steps - 1.  stop_token_ids / stop / lookahead: as `generate`; the columns are absolute and
         what is returned is columns past_len .. end - 1.  logit_bias / allowed_token_ids / banned_token_ids / min_p: as `sample`.
-        guide_states: as `generate_sample`; a second turn passes the states `generate_fetch_guide_states` and the tokens lead to."""
+        guide_states: as `generate_sample`; a second turn passes the states `generate_fetch_guide_states` and the tokens lead to.
+        no_repeat_ngram_size / bad_words_ids / min_tokens / suppress_token_ids: as `generate_sample`; the history they read is `prior`
+        followed by the new tokens and the picks — an n-gram or a bad word may straddle all three."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
         edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
+        bans = self._bans(no_repeat_ngram_size, bad_words_ids, min_tokens, suppress_token_ids, stop_token_ids)
         if stop_token_ids is not None or stop is not None:
             return self._generate_stop(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits,
-                                       guide_states)
-        return self._generate(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, edits=edits, guide_states=guide_states)
+                                       guide_states, bans)
+        return self._generate(past_len, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, edits=edits, guide_states=guide_states, bans=bans)
 
     def generate_sample(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
                         frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0, logit_bias=None,
-                        allowed_token_ids=None, banned_token_ids=None, min_p=0.0, guide_states=None):
+                        allowed_token_ids=None, banned_token_ids=None, min_p=0.0, guide_states=None, no_repeat_ngram_size=0, bad_words_ids=None,
+                        min_tokens=0, suppress_token_ids=None):
         """generate (src/main.zig:322-342) as the reference runs it — every token behind the prompt drawn by GPT.sample — with the
         loop on the device; the tokens of the host loop over `sample(T, tok, temp, seed=seed)`.  top_k / top_p: as `sample`.
         repetition_penalty / presence_penalty / frequency_penalty: on the tokens the row holds when a pick is drawn — `prior` (one
@@ -491,31 +515,46 @@ class GPT:
         stop_token_ids / stop / lookahead: as `generate`.  logit_bias ({id: value}) / allowed_token_ids / banned_token_ids: edits of
         every step's row behind the penalties; min_p: min-p truncation (defaults: today's call).
         guide_states (a `guided` handle with a guide loaded): one start state of the loaded automaton per row, None for
-        a row without a guide — every pick of a guided row is one its state allows, and the state follows the picks on the device."""
+        a row without a guide — every pick of a guided row is one its state allows, and the state follows the picks on the device.
+        History-dependent bans, computed on the device at every step (zg_gpt_generate_banned_enqueue; defaults: today's
+        call): no_repeat_ngram_size=n — no n-gram occurs twice in `prior` + prompt + picks (HF); bad_words_ids — token-id lists, the last
+        token of a word is forbidden while the row ends in its first tokens (vLLM bad_words / HF bad_words_ids; the match may reach
+        into the prompt); min_tokens — suppress_token_ids (default: stop_token_ids) cannot be picked until a row has that many picks.
+        `bans.banned_now` is the host twin for callers who draw token by token."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
         edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
+        bans = self._bans(no_repeat_ngram_size, bad_words_ids, min_tokens, suppress_token_ids, stop_token_ids)
         if stop_token_ids is not None or stop is not None:
             return self._generate_stop(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, stop_token_ids, stop, lookahead, edits,
-                                       guide_states)
-        return self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, edits=edits, guide_states=guide_states)
+                                       guide_states, bans)
+        return self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, edits=edits, guide_states=guide_states, bans=bans)
 
     def generate_sample_enqueue(self, prompts, n_steps, temp, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
                                 frequency_penalty=0.0, prior=None, logprobs=None, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                                min_p=0.0):
+                                min_p=0.0, no_repeat_ngram_size=0, bad_words_ids=None, min_tokens=0, suppress_token_ids=None):
         """generate_sample without the fetch; results through generate_fetch and (logprobs=top_n) generate_fetch_logprobs."""
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty)
         edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, min_p)
-        self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=False, edits=edits)
+        bans = self._bans(no_repeat_ngram_size, bad_words_ids, min_tokens, suppress_token_ids)
+        self._generate(None, prompts, n_steps, temp, seed, top_k, top_p, pen, prior, logprobs, fetch=False, edits=edits, bans=bans)
 
     # ------------------------------------------------------------------ per-row sampling parameters (DESIGN §3.11)
     def generate_each(self, prompts, n_steps, rows, past_len=0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0,
-                      logit_bias=None, allowed_token_ids=None, banned_token_ids=None, guide_states=None):
+                      logit_bias=None, allowed_token_ids=None, banned_token_ids=None, guide_states=None, bad_words_ids=None, suppress_token_ids=None):
         """generate_sample / generate_from with the sampler parameters taken per row (zg_gpt_generate_each_enqueue): `rows` is one
         dict per row with generate_sample's keyword names — temp, top_k, top_p, min_p, repetition_penalty, presence_penalty,
         frequency_penalty — plus seed; a row's temp 0 / None is greedy (temp 1, top_k 1).  Row b gets, bit for bit, what
         generate_sample with rows[b]'s values for every row gives row b.  prior, logprobs, the stop conditions and the three edit
         lists are per call and work as there; returns what generate_from returns: columns past_len .. (end or past_len + n_steps) - 1.
-        guide_states: as `generate_sample` (zg_gpt_generate_guided_enqueue with the table)."""
+        guide_states: as `generate_sample` (zg_gpt_generate_guided_enqueue with the table).
+        A row's dict may also carry no_repeat_ngram_size and min_tokens; bad_words_ids and suppress_token_ids (default:
+        stop_token_ids) are per call (zg_gpt_generate_banned_enqueue with the table)."""
+        ban_keys = ("no_repeat_ngram_size", "min_tokens")
+        bans = self._bans([int(r.get("no_repeat_ngram_size", 0)) for r in rows], bad_words_ids, [int(r.get("min_tokens", 0)) for r in rows],
+                          suppress_token_ids, stop_token_ids) if len(rows) == self.batch else None
+        if bans is not None and guide_states is not None:
+            raise ValueError("ban rules and a guide cannot be combined: a grammar compiles its bad words into the table")
+        rows = [{k: v for k, v in r.items() if k not in ban_keys} for r in rows]
         table = _lib.row_sampling(rows)
         mat, lens, stride = self._prompts(prompts)
         edits = self._edits(logit_bias, allowed_token_ids, banned_token_ids, 0.0)
@@ -525,7 +564,9 @@ class GPT:
         r = _lib.generate_request(past_len=past_len, prompts=ptr(mat), prompt_stride=stride, prompt_lens=ptr(lens), n_steps=n_steps, prior=pp,
                                   prior_stride=pstride, prior_lens=plens, logprobs=int(logprobs is not None), top_n=int(logprobs or 0),
                                   stop=None if conds is None else C.addressof(conds), edits=None if edits is None else C.addressof(edits[0]))
-        if guide_states is None:
+        if bans is not None:
+            check(self._L.zg_gpt_generate_banned_enqueue(self.h, C.addressof(r), C.addressof(table), len(rows), C.addressof(bans[0])))
+        elif guide_states is None:
             check(self._L.zg_gpt_generate_each_enqueue(self.h, C.addressof(r), C.addressof(table), len(rows)))
         else:
             states = self._guide_states(guide_states)
