@@ -308,7 +308,10 @@ enum {
                                       flags name (the rule: ZG_GPT_SAMPLED_GENERATE; a greedy graph has no banned twin, and there is no
                                       guided + banned twin).  Without it zg_gpt_generate_banned_enqueue works all the same: the graphs
                                       are captured when the generation begins, as for penalties */
-    ZG_GPT_WEIGHTS_B24 = 1 << 8  /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
+    ZG_GPT_BEAM_GENERATE = 1 << 17, /* capture at create the decode graphs of zg_gpt_generate_beam_enqueue (zg_beam_options; DESIGN
+                                      §3.14): the one beam tail, which has no twins.  Without it the call works all the same: the
+                                      graphs are captured when the generation begins, as for ZG_GPT_BANNED_GENERATE */
+    ZG_GPT_WEIGHTS_B24 = 1 << 8 /* store the matrices (wte, wpe, c_attn, c_proj, c_fc, mlp c_proj) as 24-bit floats: each fp32
                                     value rounded to nearest even at 16 mantissa bits (never to inf), row r of an [out][in]
                                     matrix = [in bf16-shaped upper halves | in low bytes].  3/4 of fp32's weight bytes, 2^-17
                                     per weight — for fp32 checkpoints, which bf16 storage takes outside the 1e-3 bound.
@@ -968,6 +971,86 @@ int zg_debug_ban_check(const zg_ban_rules* bans, size_t batch, size_t vocab, siz
 int zg_debug_ban_rows(const float* logits, size_t batch, size_t vocab, const zg_ban_rules* bans, const size_t* history,
                       size_t history_stride, const size_t* history_lens, const int64_t* picked, const zg_logit_edits* edits_or_null,
                       float* edited_out, float* part_val_out, int32_t* part_idx_out);
+/* ---- Forking rows of the KV caches.  Row b's caches — positions [0, zg_gpt_cached_len) of every layer, K and V,
+ * in whatever format the handle stores them — become byte for byte those of row src_rows[b].  Rows with src_rows[b] == b are not
+ * touched, and neither is any position at or beyond the cached length.  One launch on the handle's stream: no host round trip,
+ * nothing allocated, nothing drained.  Only the caches are copied: logits, the residual stream and recorded tokens stay each row's
+ * own, so a forked row is continued with zg_gpt_forward(cached_len + 1, ...) / zg_gpt_extend on tokens the caller chooses — "prefill
+ * once, draw n continuations", or a tree search driven from the host.
+ * Refusals, before anything is enqueued: n_rows != batch or a NULL array: ZG_ERR_ARG; src_rows[b] >= batch: ZG_ERR_SHAPE; a source
+ * that is itself a destination (src_rows[src_rows[b]] != src_rows[b]): ZG_ERR_ARG — with every source a fixed point no workgroup
+ * reads what another writes, and the copy needs no second buffer. */
+int zg_gpt_kv_fork(zg_gpt* g, const size_t* src_rows, size_t n_rows);
+/* Diagnostic (tests): the raw cache bytes of positions first_pos .. first_pos + n_pos - 1 of one row of one layer's K (which 0) or
+ * V (which 1) cache: [n_heads][n_pos][64] elements in storage format (fp32, fp16, or the bf16 plane of a 24-bit cache), followed
+ * for a 24-bit cache by its byte plane [n_heads][n_pos][64].  Drains the handle's stream.  out is host memory of out_bytes >= that. */
+int zg_debug_gpt_kv_rows(zg_gpt* g, size_t layer, int which, size_t row, size_t first_pos, size_t n_pos, void* out, size_t out_bytes);
+
+/* ---- Beam search in the device loop.  The handle's batch B is split into G = B / num_beams groups of W = num_beams
+ * slots; group g owns rows g W .. g W + W - 1, whose prompts must be equal (all prompt_lens equal n_p).  Picked columns are p >= c0 =
+ * past_len + n_p, under the library's column convention (step p picks column p).  Every slot carries a cumulative fp32 score; at c0
+ * only the first slot of a group is live, with score 0.  A step of a group that is not done:
+ *   - candidates (score[s] + top_logprobs[s][p][j], s, j) over its live slots and the top 2 W entries j of each slot's row (the
+ *     log-probability stage's lists, raw logits at temperature 1): one rounded fp32 add.  Order: value descending, s ascending, j
+ *     ascending; NaN never wins.  The first 2 W are kept and walked in order, rank r = 0 ...
+ *   - a candidate whose token is eos_id is offered to the group's pool of finished hypotheses if r < W and skipped otherwise (the
+ *     rule of HF generate); its normalised score is value / lenpow[p - c0 + 1], lenpow[L] = (float)pow((double)L, (double)
+ *     length_penalty), one correctly rounded fp32 division.  Any other candidate becomes the next beam until W are taken.
+ *   - the pool holds at most W entries (sum, norm, parent slot, column); a full pool takes an offer only if its norm is strictly
+ *     greater than the worst entry's, in its place.  The worst entry is the one of lowest norm and, among equal norms, the one at
+ *     the highest index of the pool.
+ *   - slots in rank order: a beam keeps its parent's slot unless an earlier beam took it; the beams left over take the free slots
+ *     in ascending order.  Every slot's caches then become its parent's (the kernel of zg_gpt_kv_fork, its table read on the device).
+ *   - the group is done when its pool is full and (early_stopping != 0, or worst norm >= best new beam's score / lenpow[p - c0 +
+ *     1]).  The slots of a done group keep decoding in lock step; nothing of theirs is read afterwards.
+ * The recorded lists of column p are indexed by the slot as it stood BEFORE step p — the parent's slot; the recorded token, parent
+ * and score of column p by the slot after it.
+ * The generation ends early once every group is done, paced as a stop generation is (zg_stop_conditions.lookahead; 0: the
+ * library's default): with f the column at which the last group was done, f + 1 <= end <= min(past_len + n_steps, f + 1 +
+ * lookahead + 64).  Without eos_id (ZG_BEAM_NO_EOS) nothing ends early and nothing is paced.  Afterwards zg_gpt_cached_len == end.
+ * The request carries past_len, prompts, prompt_stride, prompt_lens and n_steps; options, penalties, prior, logprobs, top_n, stop
+ * and edits must be NULL / 0 (ZG_ERR_ARG): beams over a penalised, edited, guided or banned distribution need a per-slot history
+ * that follows the fork.  Further refusals, all before anything is enqueued or the handle's state is touched —
+ * ZG_ERR_ARG: a wrong size field; num_beams outside 1 .. ZG_BEAM_MAX; batch % num_beams != 0; 2 num_beams > vocab_size; a
+ * length_penalty that is not finite; unequal prompt lengths, or unequal prompts within a group; n_steps <= n_p (nothing would be
+ * picked).  ZG_ERR_SHAPE: eos_id >= vocab_size
+ * (and not ZG_BEAM_NO_EOS).  The batch <= 8 rows of a handle are the home of up to 8 beams. */
+#define ZG_BEAM_MAX 8
+#define ZG_BEAM_NO_EOS ((size_t)-1)
+typedef struct {
+    size_t size;           /* sizeof(zg_beam_options), else ZG_ERR_ARG */
+    size_t num_beams;
+    size_t eos_id;         /* ZG_BEAM_NO_EOS: none */
+    float length_penalty;
+    int early_stopping;
+    size_t lookahead;
+} zg_beam_options;
+int zg_gpt_generate_beam_enqueue(zg_gpt* g, const zg_generate_request* r, const zg_beam_options* beam);
+/* The n_return <= num_beams best hypotheses of every group of the last beam generation, best first.  Drains the stream and
+ * finalises on the host: a group that is not done offers the beams in its slots as hypotheses of length end - c0 (norm = score /
+ * lenpow[end - c0]) to its pool under the pool's rule, in slot order; the pool is sorted by norm descending (equal norms: pool
+ * index ascending) and each entry is backtracked through the recorded parents and tokens.  tokens_out [G][n_return][stride]
+ * receives the picked tokens only, eos last where there is one; lens_out [G][n_return] their count (0 for a hypothesis the group
+ * does not have, with score and sum NaN); scores_out the norms, sum_logprobs_out the cumulative scores.  ZG_ERR_ARG unless the
+ * last generation was a beam generation and 1 <= n_return <= num_beams; ZG_ERR_SHAPE when stride is below a length to store. */
+int zg_gpt_generate_fetch_beams(zg_gpt* g, size_t n_return, size_t* tokens_out, size_t stride, size_t* lens_out, float* scores_out,
+                                float* sum_logprobs_out);
+/* The recorded parents (the slot, as a row of the handle, each slot's beam came from) and cumulative scores of columns first ..
+ * first + n - 1 of the last beam generation: parents_out, scores_out [batch][n], len >= batch * n.  Columns below c0 or at and
+ * beyond end hold what an earlier call left.  The top-2W lists leave through zg_gpt_generate_fetch_logprobs with top_n = 2 num_beams. */
+int zg_gpt_generate_fetch_beam_trace(zg_gpt* g, size_t first, size_t n, int* parents_out, float* scores_out, size_t len);
+/* The refusal zg_gpt_generate_beam_enqueue would return for these options and this request on a handle of `batch` rows, `vocab`
+ * tokens and `context` positions with cached_len cached positions — or ZG_OK.  Needs neither a GPU nor zg_init. */
+int zg_debug_beam_check(const zg_generate_request* r, const zg_beam_options* beam, size_t batch, size_t vocab, size_t context, size_t cached_len);
+/* Test entry: the beam kernel alone, launched once per column c0 .. c0 + n_cols - 1 over the caller's lists top_ids (int32) and
+ * top_logprobs [n_cols][batch][2 num_beams] (host), state carried from column to column; c0 = first_col.  Outputs (host): tokens_out,
+ * parents_out (int32) and scores_out [n_cols][batch] by the slot after each step, logprobs_out [n_cols][batch] the chosen entries'
+ * bits; pool_out [batch][4] floats (sum, norm, parent, column of entry g W + k; NaN rows beyond pool_n), pool_n_out and
+ * done_cols_out [batch / num_beams] (int32; -1: not done), *done_col_out the host word (0: not every group is done).  eos_id,
+ * length_penalty and early_stopping from `beam`.  The refusals of the options.  Needs zg_init only. */
+int zg_debug_beam_rows(const int32_t* top_ids, const float* top_logprobs, size_t n_cols, size_t batch, size_t vocab, size_t first_col,
+                       const zg_beam_options* beam, int32_t* tokens_out, int32_t* parents_out, float* scores_out, float* logprobs_out, float* pool_out,
+                       int32_t* pool_n_out, int32_t* done_cols_out, size_t* done_col_out);
 /* tokens of positions first .. first + n - 1 of the last generation(s): out_tokens [batch, n] */
 int zg_gpt_generate_fetch_range(zg_gpt* g, size_t first, size_t n, size_t* out_tokens, size_t out_len);
 /* Test entry: the sampler kernels of zg_gpt_sample_ex on the caller's logits [batch <= 64, vocab <= 262144] (host or device, as

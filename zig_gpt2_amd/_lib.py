@@ -108,6 +108,18 @@ def generate_request(**fields):
     return r
 
 
+class BeamOptions(C.Structure):
+    """zg_beam_options of include/zgpt2.h (`size` is filled by beam_options())."""
+
+    _fields_ = [("size", sz), ("num_beams", sz), ("eos_id", sz), ("length_penalty", C.c_float), ("early_stopping", C.c_int), ("lookahead", sz)]
+
+
+def beam_options(num_beams, eos_token_id=None, length_penalty=1.0, early_stopping=True, lookahead=0):
+    """A zg_beam_options with its size set; eos_token_id None: ZG_BEAM_NO_EOS."""
+    return BeamOptions(C.sizeof(BeamOptions), int(num_beams), BEAM_NO_EOS if eos_token_id is None else int(eos_token_id), float(length_penalty),
+                       int(bool(early_stopping)), int(lookahead))
+
+
 class GptOptions(C.Structure):
     """zg_gpt_options of include/zgpt2.h."""
 
@@ -221,6 +233,13 @@ SIGNATURES = {
     "zg_gpt_generate_banned_enqueue": (C.c_int, [vp, vp, vp, sz, vp]),
     "zg_debug_ban_check": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, C.c_int, C.c_int]),
     "zg_debug_ban_rows": (C.c_int, [vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]),
+    "zg_gpt_kv_fork": (C.c_int, [vp, vp, sz]),
+    "zg_debug_gpt_kv_rows": (C.c_int, [vp, sz, C.c_int, sz, sz, sz, vp, sz]),
+    "zg_gpt_generate_beam_enqueue": (C.c_int, [vp, vp, vp]),
+    "zg_gpt_generate_fetch_beams": (C.c_int, [vp, sz, vp, sz, vp, vp, vp]),
+    "zg_gpt_generate_fetch_beam_trace": (C.c_int, [vp, sz, sz, vp, vp, sz]),
+    "zg_debug_beam_check": (C.c_int, [vp, vp, sz, sz, sz, sz]),
+    "zg_debug_beam_rows": (C.c_int, [vp, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, szp]),
     "zg_gpt_score": (C.c_int, [vp, sz, vp, sz, sz, sz, vp, sz]),
     "zg_debug_score_rows": (C.c_int, [vp, sz, sz, sz, vp, sz, vp, vp, vp]),
     "zg_gpt_time_kernel": (C.c_int, [vp, C.c_int, C.c_int, f32p, szp]),
@@ -245,6 +264,8 @@ GPT_STOP_GENERATE = 8192
 GPT_EDITED_GENERATE = 16384
 GPT_GUIDED_GENERATE = 32768
 GPT_BANNED_GENERATE = 65536
+GPT_BEAM_GENERATE = 131072
+BEAM_MAX, BEAM_NO_EOS = 8, (1 << 64) - 1
 BAN_MAX_NGRAM, BAN_MAX_WORDS, BAN_MAX_WORD_LEN, BAN_MAX_SUPPRESS = 16, 64, 16, 16
 GUIDE_MAX_STATES, GUIDE_DEAD, GUIDE_NONE = 256, 0xFFFF, (1 << 64) - 1
 EDIT_MAX_BIAS = 512

@@ -47,6 +47,7 @@ struct PinnedCtrl {
     alignas(128) PenParams pen[kRowsMax];      // pen.h_params: one entry per row
     alignas(32) int top_n;           // lp.h_top
     alignas(32) int guide_state[kRowsMax];  // guide.h_state: the start state of every row (-1: no guide)
+    alignas(64) BeamState beam;      // beam.h_state: the options and the start state of a beam generation
 };
 static_assert(sizeof(SampleParams) == 24 && sizeof(PenParams) == 16 && offsetof(PinnedCtrl, samp) == 128 && offsetof(PinnedCtrl, fault) == 384 &&
                   offsetof(PinnedCtrl, uniforms) == 448 && offsetof(PinnedCtrl, pen) == 512 && offsetof(PinnedCtrl, top_n) == 640,
@@ -242,6 +243,18 @@ struct zg_gpt {
         BanRules *rules, *h_rules;
         BanRules build;
     } ban;
+    // generate — beam search (sample_beam.h): the options and the groups' state, the trace of parents and cumulative
+    // scores [batch][ctx] and the table lenpow [ctx + 1] — one block carved behind everything else in the arena —, the pinned mirror of
+    // the state (PinnedCtrl.beam), and what the last beam generation was: fetch_beams finalises on the host from these
+    struct {
+        BeamState *state, *h_state;
+        int* parent;
+        float *score, *lenpow;
+        bool valid;             // the last generation came through zg_gpt_generate_beam_enqueue
+        size_t W, c0;
+        bool has_eos;
+        float length_penalty;
+    } beam;
     // generate — a generation in flight between gen_begin and gen_end (zg_gpt_generate_enqueue / _many), and what the last one left
     struct {
         size_t pos, n, min_prompt, since_sync;
@@ -324,7 +337,7 @@ struct StepKey {
     bool with_logits, multi;
     StepTail tail;
 };
-constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2 * 2 * 2 * 2 * 2;  // the radices of step_index
+constexpr size_t kStepShapes = 2 * 2 * kSamplerModes * 2 * 2 * 2 * 2 * 2 * 2 * 2;  // the radices of step_index
 
 // What body() enqueues on stream cs, captured and instantiated into *out.  Nothing is left behind on failure.
 template <class Body>
@@ -354,6 +367,7 @@ int note_steps(zg_gpt* g, size_t n, hipStream_t s);
 int stage_ctrl(zg_gpt* g, size_t step, size_t seq_len, int mode, hipStream_t s);
 int copy_out_f32(float* dst, const float* src, size_t n, hipStream_t s);
 int clear_for_pass(zg_gpt* g, hipStream_t s, size_t past, size_t end);
+int enqueue_kv_fork(zg_gpt* g, int t_hi, const int* src, const int* len, unsigned src_imm, int len_imm, hipStream_t s);
 int forward_enqueue(zg_gpt* g, size_t seq_len, const size_t* tokens, size_t n_tokens, int compute_logits, float* logits_out, size_t logits_len,
                     StepTaps* taps = nullptr);
 

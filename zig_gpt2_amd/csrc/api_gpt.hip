@@ -176,6 +176,11 @@ void carve(zg_gpt* g, char* wbase, char* sbase) {
     }
     // (and behind that: the ban stage's rules, about 5 KB — no buffer above moves)
     g->ban.rules = (BanRules*)P(sizeof(BanRules));
+    // (and behind that: the beam stage's state, its trace [batch][ctx] of parents and scores and the table lenpow — no buffer above moves)
+    g->beam.state = (BeamState*)P(sizeof(BeamState));
+    g->beam.parent = (int*)P(B * C * 4);
+    g->beam.score = (float*)P(B * C * 4);
+    g->beam.lenpow = (float*)P((C + 1) * 4);
     g->state_bytes = (cv.off + 255) & ~(size_t)255;
 }
 
@@ -291,6 +296,7 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
     g->pen.h_prior = g->h_ints + batch * c.context_size + batch;
     g->lp.h_top = &g->h_ctrl->top_n;
     g->guide.h_state = g->h_ctrl->guide_state;
+    g->beam.h_state = &g->h_ctrl->beam;
     ZG_REQUIRE(!(g->flags & ZG_GPT_PENALIZED_GENERATE) || c.context_size <= (size_t)kPenMaxHistory, ZG_ERR_UNSUPPORTED,
                "ZG_GPT_PENALIZED_GENERATE: context_size %zu beyond the %d tokens the penalty kernel's LDS table holds", c.context_size, kPenMaxHistory);
     {   // decode steps per graph in the generate loop: a graph launch costs ~7 us of idle queue (124M: 224.8 us per token
@@ -318,6 +324,17 @@ int build_handle(zg_gpt* g, const zg_gpt_options* opt) {
 // from_row > 0 (a whole-prompt pass writes rows 0 .. from_row - 1 itself): only the rows behind it, strip by strip — eight
 // 1023-token prompts would otherwise pay a 600 MB memset (0.12 ms of a 5.4 ms pass) for one stale row per head.
 // keep_head (a continuation: rows below from_row are the session): never the memset of the whole region.
+// The caches of all layers lie one behind the other, K then V, the same number of bytes apart: that distance.
+static int kv_cache_stride(const zg_gpt* g, size_t* out) {
+    const size_t L = g->cfg.n_layer, elems = g->batch * g->cfg.context_size * g->cfg.n_embed;
+    const size_t stride = L > 1 ? (size_t)(reinterpret_cast<char*>(g->layers[1].k_cache) - reinterpret_cast<char*>(g->layers[0].k_cache)) / 2
+                                : (size_t)(reinterpret_cast<char*>(g->layers[0].v_cache) - reinterpret_cast<char*>(g->layers[0].k_cache));
+    ZG_REQUIRE(stride >= elems * kv_elem_bytes(g) && reinterpret_cast<char*>(g->layers[0].v_cache) - reinterpret_cast<char*>(g->layers[0].k_cache) == (ptrdiff_t)stride,
+               ZG_ERR_UNSUPPORTED, "kv caches: cache stride");
+    *out = stride;
+    return ZG_OK;
+}
+
 static int clear_kv(zg_gpt* g, hipStream_t s, size_t from_row = 0, bool keep_head = false) {
     if (g->kv_region_bytes == 0 || g->arena == nullptr) return ZG_OK;
     const size_t C = g->cfg.context_size, E = g->cfg.n_embed, B = g->batch, L = g->cfg.n_layer;
@@ -326,11 +343,9 @@ static int clear_kv(zg_gpt* g, hipStream_t s, size_t from_row = 0, bool keep_hea
         ZG_HIP(hipMemsetAsync(g->layers[0].k_cache, 0, g->kv_region_bytes, s));
         return ZG_OK;
     }
-    const size_t elems = B * C * E, kvb = kv_elem_bytes(g);
-    const size_t stride = L > 1 ? (size_t)(reinterpret_cast<char*>(g->layers[1].k_cache) - reinterpret_cast<char*>(g->layers[0].k_cache)) / 2
-                                : (size_t)(reinterpret_cast<char*>(g->layers[0].v_cache) - reinterpret_cast<char*>(g->layers[0].k_cache));
-    ZG_REQUIRE(stride >= elems * kvb && reinterpret_cast<char*>(g->layers[0].v_cache) - reinterpret_cast<char*>(g->layers[0].k_cache) == (ptrdiff_t)stride,
-               ZG_ERR_UNSUPPORTED, "kv clear: cache stride");
+    const size_t elems = B * C * E;
+    size_t stride = 0;
+    ZG_TRY(kv_cache_stride(g, &stride));
     const int strips = (int)(B * g->cfg.n_heads);
     ZG_TRY(launch_kv_clear_tail(g->layers[0].k_cache, (int)(2 * L), stride, 0, g->kv_mode == 0 ? 256 : 128, strips, (int)C, (int)from_row, s));
     if (g->kv_mode == 2) ZG_TRY(launch_kv_clear_tail(g->layers[0].k_cache, (int)(2 * L), stride, elems * 2, 64, strips, (int)C, (int)from_row, s));
@@ -431,6 +446,26 @@ int clear_for_pass(zg_gpt* g, hipStream_t s, size_t past, size_t end) {
     else if (g->kv_dirty_hi > end) ZG_TRY(clear_kv(g, s, end, true));
     g->kv_dirty_hi = end;
     return ZG_OK;
+}
+
+// The row-to-row copy of all caches (elementwise.hip, kv_fork_kernel) on stream s, its grid sized for t_hi positions.  src / len in
+// device memory (a captured beam step), or null: the table src_imm (four bits per row) and the length len_imm travel by value.
+int enqueue_kv_fork(zg_gpt* g, int t_hi, const int* src, const int* len, unsigned src_imm, int len_imm, hipStream_t s) {
+    KvForkArgs a{};
+    a.base = reinterpret_cast<char*>(g->layers[0].k_cache);
+    ZG_TRY(kv_cache_stride(g, &a.cache_stride));
+    a.lo_off = g->batch * g->cfg.context_size * g->cfg.n_embed * 2;
+    a.n_caches = (int)(2 * g->cfg.n_layer);
+    a.batch = (int)g->batch;
+    a.heads = (int)g->cfg.n_heads;
+    a.ctx = (int)g->cfg.context_size;
+    a.kv_mode = g->kv_mode;
+    a.t_hi = t_hi;
+    a.src = src;
+    a.len = len;
+    a.src_imm = src_imm;
+    a.len_imm = len_imm;
+    return launch_kv_fork(a, s);
 }
 
 // GPT.forward enqueued on the handle's stream, nothing drained (zg_gpt_forward drains; zg_gpt_sample puts its sampler behind it first)
@@ -666,6 +701,24 @@ int zg_gpt_cached_len(zg_gpt* g, size_t* len_out) {
     ZG_REQUIRE(g && len_out, ZG_ERR_ARG, "gpt_cached_len: null argument");
     *len_out = g->cached_len;
     return ZG_OK;
+}
+
+int zg_gpt_kv_fork(zg_gpt* g, const size_t* src_rows, size_t n_rows) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && src_rows, ZG_ERR_ARG, "gpt_kv_fork: null argument");
+    const size_t B = g->batch;
+    ZG_REQUIRE(n_rows == B, ZG_ERR_ARG, "gpt_kv_fork: %zu source rows for batch %zu", n_rows, B);
+    for (size_t b = 0; b < B; ++b) ZG_REQUIRE(src_rows[b] < B, ZG_ERR_SHAPE, "gpt_kv_fork: row %zu copies row %zu of %zu", b, src_rows[b], B);
+    unsigned table = 0;
+    bool moves = false;
+    for (size_t b = 0; b < B; ++b) {
+        ZG_REQUIRE(src_rows[src_rows[b]] == src_rows[b], ZG_ERR_ARG, "gpt_kv_fork: row %zu copies row %zu, which is itself overwritten (from row %zu)", b,
+                   src_rows[b], src_rows[src_rows[b]]);
+        table |= (unsigned)src_rows[b] << (4 * b);
+        moves = moves || src_rows[b] != b;
+    }
+    if (!moves || g->cached_len == 0) return ZG_OK;
+    return enqueue_kv_fork(g, bucket_t_hi(g, g->cached_len), nullptr, nullptr, table, (int)g->cached_len, gs(g));
 }
 
 int zg_gpt_argmax(zg_gpt* g, size_t* tokens_out, size_t n_tokens) {

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <vector>
 
 #include "api_gpt.h"
@@ -285,6 +286,105 @@ int zg_debug_stop_rows(const size_t* tokens, size_t batch, size_t stride, const 
         reasons_out[b] = fin[b] < 0 ? -1 : reason[b];
     }
     *done_col_out = host.p->done_col;
+    return ZG_OK;
+}
+
+// The beam kernel alone over the caller's lists (tests; include/zgpt2.h): launched eagerly once per column, state carried, on a
+// scratch record whose columns are the caller's (column 0 here is first_col of the call).  Allocates per call.
+int zg_debug_beam_rows(const int32_t* top_ids, const float* top_logprobs, size_t n_cols, size_t batch, size_t vocab, size_t first_col,
+                       const zg_beam_options* beam, int32_t* tokens_out, int32_t* parents_out, float* scores_out, float* logprobs_out, float* pool_out,
+                       int32_t* pool_n_out, int32_t* done_cols_out, size_t* done_col_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(top_ids && top_logprobs && tokens_out && parents_out && scores_out && logprobs_out && pool_out && pool_n_out && done_cols_out && done_col_out &&
+                   n_cols >= 1 && n_cols <= 4096 && first_col <= (size_t)1 << 20 && vocab >= 1 && vocab <= 0x7fffffff,
+               ZG_ERR_ARG, "debug_beam_rows: bad argument");
+    ZG_REQUIRE(beam != nullptr && beam->size == sizeof(zg_beam_options), ZG_ERR_ARG, "debug_beam_rows: null options, or their size field is not sizeof(zg_beam_options)");
+    const size_t W = beam->num_beams;
+    ZG_REQUIRE(W >= 1 && W <= ZG_BEAM_MAX && batch >= 1 && batch <= (size_t)kBeamRows && batch % W == 0 && 2 * W <= vocab, ZG_ERR_ARG,
+               "debug_beam_rows: num_beams %zu for %zu rows and %zu tokens", W, batch, vocab);
+    ZG_REQUIRE(std::isfinite(beam->length_penalty), ZG_ERR_ARG, "debug_beam_rows: length_penalty is not finite");
+    ZG_REQUIRE(beam->eos_id == ZG_BEAM_NO_EOS || beam->eos_id < vocab, ZG_ERR_SHAPE, "debug_beam_rows: eos_id %zu >= vocab %zu", beam->eos_id, vocab);
+    const size_t K = ZG_LOGPROBS_TOP_MAX, T = 2 * W, G = batch / W;
+    // the record layout the stage reads: [batch][n_cols][20]
+    std::vector<int> h_ids(batch * n_cols * K, 0);
+    std::vector<float> h_lp(batch * n_cols * K, 0.0f), h_pow(n_cols + 1);
+    for (size_t c = 0; c < n_cols; ++c)
+        for (size_t b = 0; b < batch; ++b)
+            for (size_t j = 0; j < T; ++j) {
+                h_ids[(b * n_cols + c) * K + j] = top_ids[(c * batch + b) * T + j];
+                h_lp[(b * n_cols + c) * K + j] = top_logprobs[(c * batch + b) * T + j];
+            }
+    fill_lenpow(h_pow.data(), n_cols + 1, beam->length_penalty);
+    BeamState h_st;
+    fill_beam_state(&h_st, *beam, 0);
+    struct Pinned {
+        StopHost* p = nullptr;
+        ~Pinned() { (void)hipHostFree(p); }
+    } host;
+    ZG_HIP(hipHostMalloc(reinterpret_cast<void**>(&host.p), sizeof(StopHost), hipHostMallocDefault));
+    host.p->progress = host.p->done_col = 0u;
+    hipStream_t s = ctx().stream;
+    DevScratch ds;
+    BeamArgs a{};
+    int *d_ids, *d_tok;  // d_tok: the picks of every column, [n_cols][batch] — `sampled` copied behind each launch
+    float *d_lp, *d_pow;
+    ZG_TRY(ds.carve([&] {
+        d_ids = ds.take<int>(h_ids.size() * 4);
+        d_tok = ds.take<int>(n_cols * batch * 4);
+        d_lp = ds.take<float>(h_lp.size() * 4);
+        d_pow = ds.take<float>(h_pow.size() * 4);
+        a.st = ds.take<BeamState>(sizeof(BeamState));
+        a.sampled = ds.take<int>(batch * 4);
+        a.parent = ds.take<int>(batch * n_cols * 4);
+        a.score = ds.take<float>(batch * n_cols * 4);
+        a.logprob = ds.take<float>(batch * n_cols * 4);
+    }));
+    ZG_HIP(hipMemcpyAsync(d_ids, h_ids.data(), h_ids.size() * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_lp, h_lp.data(), h_lp.size() * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(d_pow, h_pow.data(), h_pow.size() * 4, hipMemcpyHostToDevice, s));
+    ZG_HIP(hipMemcpyAsync(a.st, &h_st, sizeof(BeamState), hipMemcpyHostToDevice, s));
+    a.lenpow = d_pow;
+    a.n_lenpow = (int)n_cols + 1;
+    a.batch = (int)batch;
+    a.vocab = (int)vocab;
+    a.top_ids = d_ids;
+    a.top_logprobs = d_lp;
+    a.stride = (int)n_cols;
+    a.host = host.p;
+    for (size_t c = 0; c < n_cols; ++c) {
+        a.col = (int)c;
+        ZG_TRY(launch_beam(a, s));
+        ZG_HIP(hipMemcpyAsync(d_tok + c * batch, a.sampled, batch * 4, hipMemcpyDeviceToDevice, s));
+    }
+    std::vector<int> par(batch * n_cols);
+    std::vector<float> sc(batch * n_cols), lpv(batch * n_cols);
+    ZG_HIP(hipMemcpyAsync(tokens_out, d_tok, n_cols * batch * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(par.data(), a.parent, par.size() * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(sc.data(), a.score, sc.size() * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(lpv.data(), a.logprob, lpv.size() * 4, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(&h_st, a.st, sizeof(BeamState), hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_REQUIRE(host.p->progress == (unsigned)n_cols, ZG_ERR_HIP, "debug_beam_rows: the kernel reported column %u of %zu", host.p->progress, n_cols);
+    for (size_t c = 0; c < n_cols; ++c)
+        for (size_t b = 0; b < batch; ++b) {
+            parents_out[c * batch + b] = par[b * n_cols + c];
+            scores_out[c * batch + b] = sc[b * n_cols + c];
+            logprobs_out[c * batch + b] = lpv[b * n_cols + c];
+        }
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (size_t gr = 0; gr < G; ++gr) {
+        pool_n_out[gr] = h_st.pool_n[gr];
+        done_cols_out[gr] = h_st.done_col[gr] < 0 ? -1 : h_st.done_col[gr] + (int)first_col;
+        for (size_t k = 0; k < W; ++k) {
+            const size_t e = gr * W + k;
+            const bool has = (int)k < h_st.pool_n[gr];
+            pool_out[e * 4 + 0] = has ? h_st.pool_sum[e] : nan;
+            pool_out[e * 4 + 1] = has ? h_st.pool_norm[e] : nan;
+            pool_out[e * 4 + 2] = has ? (float)h_st.pool_parent[e] : nan;
+            pool_out[e * 4 + 3] = has ? (float)(h_st.pool_col[e] + (int)first_col) : nan;
+        }
+    }
+    *done_col_out = host.p->done_col ? host.p->done_col + first_col : 0;
     return ZG_OK;
 }
 
@@ -902,6 +1002,27 @@ int zg_debug_gpt_tag_census(zg_gpt* g, unsigned epoch24, unsigned sk_flag_value,
         ZG_HIP(hipMemcpy(f, g->pass.sk_flags, sizeof(f), hipMemcpyDeviceToHost));
         for (const unsigned w : f) counts[3] += w == sk_flag_value;
     }
+    return ZG_OK;
+}
+
+// The raw cache bytes of one row (tests of zg_gpt_kv_fork; include/zgpt2.h): [H][n_pos][64] elements in storage format, then, for a
+// 24-bit cache, the byte plane [H][n_pos][64].  Drains the stream.
+int zg_debug_gpt_kv_rows(zg_gpt* g, size_t layer, int which, size_t row, size_t first_pos, size_t n_pos, void* out, size_t out_bytes) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && out && (which == 0 || which == 1), ZG_ERR_ARG, "debug_gpt_kv_rows: bad argument");
+    const size_t C = g->cfg.context_size, H = g->cfg.n_heads, E = g->cfg.n_embed, B = g->batch;
+    ZG_REQUIRE(layer < g->cfg.n_layer && row < B && n_pos >= 1 && first_pos < C && n_pos <= C - first_pos, ZG_ERR_SHAPE,
+               "debug_gpt_kv_rows: layer %zu, row %zu, positions %zu + %zu", layer, row, first_pos, n_pos);
+    const size_t eb = g->kv_mode == 0 ? 4 : 2, need = H * n_pos * 64 * (eb + (g->kv_mode == 2 ? 1 : 0));
+    ZG_REQUIRE(out_bytes >= need, ZG_ERR_SHAPE, "debug_gpt_kv_rows: %zu bytes for %zu", out_bytes, need);
+    hipStream_t s = gs(g);
+    const char* p = reinterpret_cast<const char*>(which ? g->layers[layer].v_cache : g->layers[layer].k_cache);
+    const size_t at = (row * H * C + first_pos) * 64;  // elements; a head's strip is C * 64 of them
+    ZG_HIP(hipMemcpy2DAsync(out, n_pos * 64 * eb, p + at * eb, C * 64 * eb, n_pos * 64 * eb, H, hipMemcpyDeviceToHost, s));
+    if (g->kv_mode == 2)
+        ZG_HIP(hipMemcpy2DAsync(reinterpret_cast<char*>(out) + H * n_pos * 64 * 2, n_pos * 64, p + B * C * E * 2 + at, C * 64, n_pos * 64, H,
+                                hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
     return ZG_OK;
 }
 

@@ -1,11 +1,13 @@
 // api_gpt_generate.hip — model tier of the C ABI: drawing tokens from a handle.  The per-token calls (sample_impl) and the
 // generation request, which exists once (every zg_gpt_generate*_enqueue fills a zg_generate_request, generate_request alone
 // makes the GenRequest gen_run runs); a whole generation is enqueued without a host round trip per token.
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
 #include <chrono>
+#include <limits>
 #include <string>
 #include <thread>
 #include <vector>
@@ -251,6 +253,10 @@ struct GenRequest {
     // history-dependent bans, checked, the rules laid out in the ONE handle's ban.build: ban_on — the ban stage runs, on
     // the history the penalties read (prior, above).  Off: the request is what it was
     bool ban_on = false;
+    // beam search, checked (check_beam): the greedy slot plus the log-probability stage (lp_on, top_n = 2 W, set by the
+    // builder) with the beam launch and the cache fork behind it.  Off: the request is what it was
+    bool beam_on = false;
+    zg_beam_options beam{};
     GenRequest(const size_t* prompts, size_t stride, const size_t* lens, size_t n_steps, size_t past = 0)
         : prompts(prompts), stride(stride), lens(lens), n_steps(n_steps), past(past) {}
 };
@@ -298,9 +304,27 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
         first = min_prompt < n_steps ? min_prompt : n_steps;
     const bool edit_on = r.edit_on && r.mode != GREEDY;
     const bool guide_on = r.guide_on && r.mode != GREEDY;
-    g->gen.tail = StepTail{r.mode, pen_on, r.lp_on, r.stop_on, edit_on, guide_on, ban_on};  // (normalized: pen_on / edit_on / guide_on / ban_on only with a sampler, and the steps it is for have lm_head)
+    g->gen.tail = normalized(StepTail{r.mode, pen_on, r.lp_on, r.stop_on, edit_on, guide_on, ban_on, r.beam_on}, true);  // (normalized: pen_on / edit_on / guide_on / ban_on only with a sampler, and the steps it is for have lm_head)
     g->gen.stop_valid = false;
     g->gen.stop = r.stop_on;
+    g->beam.valid = false;
+    if (r.beam_on) {  // the options and the groups' start state through the pinned control block, lenpow through the record's mirror (the stream is drained)
+        const size_t c0 = past + r.lens[0];
+        fill_beam_state(g->beam.h_state, r.beam, c0);
+        ZG_HIP(hipMemcpyAsync(g->beam.state, g->beam.h_state, sizeof(BeamState), hipMemcpyHostToDevice, s));
+        fill_lenpow(g->lp.h_rec, C + 1, r.beam.length_penalty);
+        ZG_HIP(hipMemcpyAsync(g->beam.lenpow, g->lp.h_rec, (C + 1) * sizeof(float), hipMemcpyHostToDevice, s));
+        g->beam.valid = true;
+        g->beam.W = r.beam.num_beams;
+        g->beam.c0 = c0;
+        g->beam.has_eos = r.beam.eos_id != ZG_BEAM_NO_EOS;
+        g->beam.length_penalty = r.beam.length_penalty;
+        if (g->beam.has_eos) {  // the beam stage ends the call early the way the stop stage does: the same two words, the same pacing
+            g->gen.stop = true;
+            g->stop.pinned->host.progress = g->stop.pinned->host.done_col = 0u;
+            g->gen.lookahead = r.beam.lookahead ? std::min(r.beam.lookahead, C) : kStopLookahead;
+        }
+    }
     if (r.stop_on) {  // the conditions of this call; no row has finished; the stage has seen nothing (the stream is drained: the words are the host's)
         fill_stop(&g->stop.pinned->conds, r.stop);
         ZG_HIP(hipMemcpyAsync(g->stop.conds, &g->stop.pinned->conds, sizeof(StopConds), hipMemcpyHostToDevice, s));
@@ -335,7 +359,7 @@ static int gen_begin(zg_gpt* g, const GenRequest& r) {
     }
     ZG_HIP(hipMemcpyAsync(g->prompt, g->h_ints, B * C * sizeof(int), hipMemcpyHostToDevice, s));
     ZG_HIP(hipMemcpyAsync(g->prompt_len, g->h_ints + B * C, B * sizeof(int), hipMemcpyHostToDevice, s));
-    ZG_TRY(stage_ctrl(g, past + first, past + first, r.mode != GREEDY ? 2 : 0, s));
+    ZG_TRY(stage_ctrl(g, past + first, past + first, r.mode != GREEDY || r.beam_on ? 2 : 0, s));  // (mode 2: the embed kernel feeds `sampled`, the sampler's or the beam stage's)
     ZG_TRY(clear_for_pass(g, s, past, past + first));
     g->cached_len = g->kv_dirty_hi = past + n_steps;  // the last position the loop feeds
     ZG_TRY(ensure_ln_folded(g, s));
@@ -444,7 +468,7 @@ static int gen_end(zg_gpt* g, int rs) {
     ZG_TRY(launch_embed_step(embed_args(g, 1), s));  // record the pick of the last step
     if (g->gen.stop) {  // the column actually reached: the one place that corrects what gen_begin set up front
         g->gen.n = g->cached_len = g->kv_dirty_hi = g->gen.stop_end = g->gen.pos;
-        g->gen.stop_valid = true;
+        g->gen.stop_valid = !g->gen.tail.beam;  // (a beam generation ends early by its pools: it has no finish columns to report)
     }
     g->steps_enqueued = g->gen.n;
     return ZG_OK;
@@ -774,6 +798,133 @@ int zg_gpt_generate_fetch_logprobs(zg_gpt* g, size_t first, size_t n, size_t top
     ZG_TRY(check_fault(g));
     memcpy(logprobs_out, h_lp, B * n * sizeof(float));
     unpack_top(h_ids, h_top, B * n, top_n, top_ids_out, top_logprobs_out);
+    return ZG_OK;
+}
+
+// ---- Beam search: the request call plus the options.  A beam step is a greedy slot with the log-probability stage
+// at top_n = 2 W; the beam launch and the cache fork follow it (enqueue_step).
+int zg_gpt_generate_beam_enqueue(zg_gpt* g, const zg_generate_request* r, const zg_beam_options* beam) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g != nullptr, ZG_ERR_ARG, "generate_beam: null handle");
+    ZG_TRY(check_beam(r, beam, g->batch, g->cfg.vocab_size, g->cfg.context_size, g->cached_len, "generate_beam"));
+    GenRequest q(r->prompts, r->prompt_stride, r->prompt_lens, r->n_steps, r->past_len);
+    q.lp_on = true;
+    q.top_n = 2 * beam->num_beams;
+    q.beam_on = true;
+    q.beam = *beam;
+    return gen_run(&g, 1, q);
+}
+
+namespace {
+
+// A finished hypothesis on the host: a pool entry of the device (eos: the token behind column col - 1 of slot `parent`), or the
+// beam a slot holds when the generation ends (its last token in column col - 1 of that slot)
+struct BeamHyp {
+    float sum, norm;
+    int parent, col;
+    bool eos;
+};
+
+// beam_key of sample_beam.h: NaN below every number, -0.0 equal to +0.0
+unsigned host_beam_key(float v) {
+    if (v != v) return 0u;
+    if (v == 0.0f) return 0x80000000u;
+    unsigned u;
+    memcpy(&u, &v, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// the pool's rule (sample_beam.h): room, or strictly better than the worst entry — lowest norm, among equals the highest index
+void beam_pool_offer(std::vector<BeamHyp>& pool, size_t W, const BeamHyp& h) {
+    if (pool.size() < W) {
+        pool.push_back(h);
+        return;
+    }
+    size_t w = 0;
+    for (size_t k = 1; k < pool.size(); ++k)
+        if (host_beam_key(pool[k].norm) <= host_beam_key(pool[w].norm)) w = k;
+    if (host_beam_key(h.norm) > host_beam_key(pool[w].norm)) pool[w] = h;
+}
+
+}  // namespace
+
+int zg_gpt_generate_fetch_beams(zg_gpt* g, size_t n_return, size_t* tokens_out, size_t stride, size_t* lens_out, float* scores_out, float* sum_logprobs_out) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && tokens_out && lens_out && scores_out && sum_logprobs_out, ZG_ERR_ARG, "generate_fetch_beams: null argument");
+    ZG_REQUIRE(g->beam.valid, ZG_ERR_ARG, "generate_fetch_beams: the last generation did not come through zg_gpt_generate_beam_enqueue");
+    const size_t C = g->cfg.context_size, B = g->batch, W = g->beam.W, G = B / W, c0 = g->beam.c0, end = g->gen.n;
+    ZG_REQUIRE(n_return >= 1 && n_return <= W, ZG_ERR_ARG, "generate_fetch_beams: n_return %zu outside 1..%zu", n_return, W);
+    ZG_REQUIRE(end > c0 && end <= C, ZG_ERR_ARG, "generate_fetch_beams: the generation ended at column %zu, its first pick was column %zu", end, c0);
+    hipStream_t s = gs(g);
+    int* const h_tok = g->h_ints;                 // [B][C] the recorded tokens
+    int* const h_par = g->h_ints + B * C + B;     // [B][C] the recorded parents (the staging of the penalties' history: idle here)
+    ZG_HIP(hipMemcpyAsync(h_tok, g->out_tokens, B * C * sizeof(int), hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(h_par, g->beam.parent, B * C * sizeof(int), hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpyAsync(g->beam.h_state, g->beam.state, sizeof(BeamState), hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    const BeamState& st = *g->beam.h_state;
+    const float lp_end = (float)pow((double)(end - c0), (double)g->beam.length_penalty);
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    std::vector<size_t> seq;
+    // every length is known before anything is written: a stride too short for one of them refuses the whole call
+    std::vector<std::vector<BeamHyp>> pools(G);
+    for (size_t gr = 0; gr < G; ++gr) {
+        std::vector<BeamHyp>& pool = pools[gr];
+        const size_t n = (size_t)std::min(std::max(st.pool_n[gr], 0), (int)W);
+        for (size_t k = 0; k < n; ++k) pool.push_back({st.pool_sum[gr * W + k], st.pool_norm[gr * W + k], st.pool_parent[gr * W + k], st.pool_col[gr * W + k], true});
+        if (st.done_col[gr] < 0)
+            for (size_t t = 0; t < W; ++t) beam_pool_offer(pool, W, {st.score[gr * W + t], st.score[gr * W + t] / lp_end, (int)(gr * W + t), (int)end, false});
+        std::stable_sort(pool.begin(), pool.end(), [](const BeamHyp& x, const BeamHyp& y) { return host_beam_key(x.norm) > host_beam_key(y.norm); });
+        for (size_t i = 0; i < n_return && i < pool.size(); ++i) {
+            const size_t len = (size_t)pool[i].col - c0 + (pool[i].eos ? 1 : 0);
+            ZG_REQUIRE((size_t)pool[i].col >= c0 && (size_t)pool[i].col <= end && len <= stride, ZG_ERR_SHAPE,
+                       "generate_fetch_beams: a hypothesis of %zu tokens (column %d) for a stride of %zu", len, pool[i].col, stride);
+        }
+    }
+    for (size_t gr = 0; gr < G; ++gr)
+        for (size_t i = 0; i < n_return; ++i) {
+            const size_t o = gr * n_return + i;
+            if (i >= pools[gr].size()) {
+                lens_out[o] = 0;
+                scores_out[o] = sum_logprobs_out[o] = nan;
+                continue;
+            }
+            const BeamHyp& h = pools[gr][i];
+            seq.clear();
+            if (h.eos) seq.push_back((size_t)st.eos);
+            size_t cur = (size_t)h.parent;
+            for (size_t c = (size_t)h.col; c-- > c0;) {  // columns col - 1 .. c0, following the parents (held inside the group)
+                cur = std::min(std::max(cur, gr * W), gr * W + W - 1);
+                seq.push_back((size_t)h_tok[cur * C + c]);
+                cur = (size_t)std::max(h_par[cur * C + c], 0);
+            }
+            std::reverse(seq.begin(), seq.end());
+            for (size_t k = 0; k < seq.size(); ++k) tokens_out[o * stride + k] = seq[k];
+            lens_out[o] = seq.size();
+            scores_out[o] = h.norm;
+            sum_logprobs_out[o] = h.sum;
+        }
+    return ZG_OK;
+}
+
+int zg_gpt_generate_fetch_beam_trace(zg_gpt* g, size_t first, size_t n, int* parents_out, float* scores_out, size_t len) {
+    ZG_TRY(require_init());
+    ZG_REQUIRE(g && parents_out && scores_out, ZG_ERR_ARG, "generate_fetch_beam_trace: null argument");
+    ZG_REQUIRE(g->beam.valid, ZG_ERR_ARG, "generate_fetch_beam_trace: the last generation did not come through zg_gpt_generate_beam_enqueue");
+    const size_t C = g->cfg.context_size, B = g->batch;
+    ZG_REQUIRE(first <= C && n <= C - first && len >= B * n, ZG_ERR_SHAPE, "generate_fetch_beam_trace: positions %zu .. %zu of %zu, %zu elements", first,
+               first + n, C, len);
+    if (n == 0) return ZG_OK;
+    hipStream_t s = gs(g);
+    int* const h_par = g->h_ints;
+    float* const h_sc = g->lp.h_rec;
+    ZG_HIP(hipMemcpy2DAsync(h_par, n * 4, g->beam.parent + first, C * 4, n * 4, B, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipMemcpy2DAsync(h_sc, n * 4, g->beam.score + first, C * 4, n * 4, B, hipMemcpyDeviceToHost, s));
+    ZG_HIP(hipStreamSynchronize(s));
+    ZG_TRY(check_fault(g));
+    memcpy(parents_out, h_par, B * n * sizeof(int));
+    memcpy(scores_out, h_sc, B * n * sizeof(float));
     return ZG_OK;
 }
 

@@ -87,7 +87,7 @@ PenHistory pen_history(const zg_gpt* g, bool loop) {
 }
 
 size_t step_index(StepKey k) {
-    return ((((((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp) * 2 + k.tail.stop) * 2 + k.tail.edit) * 2 + k.tail.guide) * 2 + k.tail.ban;
+    return (((((((((size_t)k.with_logits * 2 + k.multi) * kSamplerModes + k.tail.sampler) * 2 + k.tail.pen) * 2 + k.tail.lp) * 2 + k.tail.stop) * 2 + k.tail.edit) * 2 + k.tail.guide) * 2 + k.tail.ban) * 2 + k.tail.beam;
 }
 
 // The tails whose graphs zg_gpt_create captures besides the default one, by the handle's flags: each *_GENERATE flag names the
@@ -123,6 +123,7 @@ std::vector<StepTail> tails_of_flags(unsigned flags) {
         t.push_back({GREEDY, false, false, true});
         for (size_t i = 0; i < n; ++i) t.push_back({t[i].sampler, t[i].pen, t[i].lp, true, t[i].edit, t[i].guide, t[i].ban});
     }
+    if (flags & ZG_GPT_BEAM_GENERATE) t.push_back(normalized({GREEDY, false, true, false, false, false, false, true}, true));  // the one beam tail: it has no twins
     return t;
 }
 
@@ -500,6 +501,28 @@ int enqueue_step(zg_gpt* g, bool with_logits, int t_hi, hipStream_t s, const Ste
     const int* const picks = tail.sampler == GREEDY ? nullptr : g->samp.sampled;  // (the greedy graphs have no sampler node)
     ZG_TRY(emit_sampler_chain(handle_chain(g, true), tail, s));
     if (tail.lp) ZG_TRY(logprobs(picks));
+    // beam search: the next beams from the lists the stage above has just recorded, into `sampled` (the next step's
+    // embed kernel runs in mode 2), then every slot's cache becomes its parent's over the positions this step has filled
+    if (tail.beam) {
+        BeamArgs a{};
+        a.st = g->beam.state;
+        a.lenpow = g->beam.lenpow;
+        a.n_lenpow = (int)g->cfg.context_size + 1;
+        a.batch = (int)g->batch;
+        a.vocab = (int)g->cfg.vocab_size;
+        a.top_ids = g->lp.rec.top_ids;
+        a.top_logprobs = g->lp.rec.top_logprobs;
+        a.stride = (int)g->cfg.context_size;
+        a.ctrl = g->ctrl;
+        a.col = -1;
+        a.sampled = g->samp.sampled;
+        a.parent = g->beam.parent;
+        a.score = g->beam.score;
+        a.logprob = g->lp.rec.logprob;
+        a.host = &g->stop.pinned->host;
+        ZG_TRY(launch_beam(a, s));
+        ZG_TRY(enqueue_kv_fork(g, t_hi, g->beam.state->src, &g->ctrl->seq_len, 0u, 0, s));
+    }
     // the guide's advance: the state record of this column, then the transition of the pick (a guided tail has a sampler)
     if (tail.guide) ZG_TRY(launch_guide_advance(handle_chain(g, true).guide, picks, (int)g->batch, (int)g->cfg.vocab_size, s));
     if (tail.stop) ZG_TRY(stop(picks));

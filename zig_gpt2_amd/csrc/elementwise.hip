@@ -421,6 +421,52 @@ int launch_kv_clear_tail(void* base, int n_caches, size_t cache_stride, size_t p
     return ZG_OK;
 }
 
+// One workgroup per (64-position tile, head, cache x destination row): at most 16 KB of one head's strip, as 16-byte loads that are
+// all issued before the first store.  The row's source and the cached length are clamped before they become addresses; a
+// row that is its own source leaves on a uniform branch before any load, and so does a tile at or behind the cached length.
+static __global__ __launch_bounds__(256) void kv_fork_kernel(KvForkArgs a) {
+    const int tile = blockIdx.x, h = blockIdx.y, cache = blockIdx.z / a.batch, b = blockIdx.z % a.batch;
+    int src = a.src != nullptr ? a.src[b] : (int)((a.src_imm >> (4 * b)) & 15u);
+    src = min(max(src, 0), a.batch - 1);
+    if (src == b) return;
+    int T = a.len != nullptr ? *a.len : a.len_imm;
+    T = min(max(T, 0), min(a.t_hi, a.ctx));
+    const int p0 = tile * 64;
+    if (p0 >= T) return;
+    const int n = min(64, T - p0);
+    char* const plane = a.base + (size_t)cache * a.cache_stride;
+    const size_t so = (((size_t)src * a.heads + h) * a.ctx + p0) * 64, dof = (((size_t)b * a.heads + h) * a.ctx + p0) * 64;  // elements
+    const int eb = a.kv_mode == 0 ? 4 : 2;
+    const int n16 = n * 4 * eb;  // 16-byte units of n rows of 64 elements: at most 1024
+    const u32x4* sp = reinterpret_cast<const u32x4*>(plane + so * eb);
+    u32x4* dp = reinterpret_cast<u32x4*>(plane + dof * eb);
+    u32x4 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = threadIdx.x + k * 256;
+        if (i < n16) v[k] = sp[i];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = threadIdx.x + k * 256;
+        if (i < n16) dp[i] = v[k];
+    }
+    if (a.kv_mode == 2) {  // the byte plane: n rows of 64 bytes
+        const int i = threadIdx.x;
+        if (i < n * 4) reinterpret_cast<u32x4*>(plane + a.lo_off + dof)[i] = reinterpret_cast<const u32x4*>(plane + a.lo_off + so)[i];
+    }
+}
+
+int launch_kv_fork(const KvForkArgs& a, hipStream_t s) {
+    ZG_REQUIRE(a.base != nullptr && a.batch >= 1 && a.batch <= 8 && a.heads >= 1 && a.heads < 65536 && a.n_caches >= 1 && a.n_caches * a.batch < 65536 &&
+                   a.ctx >= 1 && a.t_hi >= 1 && a.kv_mode >= 0 && a.kv_mode <= 2 && a.cache_stride % 16 == 0 && a.lo_off % 16 == 0,
+               ZG_ERR_ARG, "kv fork: bad argument");
+    const int tiles = (std::min(a.t_hi, a.ctx) + 63) / 64;
+    hipLaunchKernelGGL(kv_fork_kernel, dim3(tiles, a.heads, a.n_caches * a.batch), dim3(256), 0, s, a);
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
 int launch_f32_to_b24(const float* in, size_t rows, int K, void* out, hipStream_t s) {
     if (rows == 0) return ZG_OK;
     ZG_REQUIRE(K % 8 == 0, ZG_ERR_UNSUPPORTED, "f32_to_b24: K=%d must be a multiple of 8", K);

@@ -1,7 +1,7 @@
 // sample.hip — the head of a decode step and the stages of the device sampler behind lm_head (model tier): embed_step_kernel,
 // the plain sampler's three kernels, and — as included headers, one per stage — truncation (sample_filter.h), penalties
-// (sample_penalty.h), history-dependent bans (sample_ban.h), logit edits (sample_edit.h), guided decoding (sample_guide.h), log-probabilities (sample_logprob.h), scoring (sample_score.h) and the stop
-// conditions (sample_stop.h), with every stage's launcher and workspace carver.  What the stages share — the pick from lm_head's
+// (sample_penalty.h), history-dependent bans (sample_ban.h), logit edits (sample_edit.h), guided decoding (sample_guide.h), log-probabilities (sample_logprob.h), scoring (sample_score.h), the stop
+// conditions (sample_stop.h) and beam search (sample_beam.h), with every stage's launcher and workspace carver.  What the stages share — the pick from lm_head's
 // argmax partials, the row maximum, the rebuild of a slice's partial — is in sample_common.h; the order of picks itself
 // (pick_before), clamp_token and counter_uniform are in zg_common.h.
 #include <algorithm>
@@ -301,6 +301,7 @@ __global__ __launch_bounds__(256) void sample_probs_kernel(float* logits, int vo
 #include "sample_logprob.h"
 #include "sample_score.h"
 #include "sample_stop.h"
+#include "sample_beam.h"
 
 // What every sampler chain checks of the vocabulary, and the grid of its segment kernel: four segments of 64 per workgroup
 int seg_grid(int vocab, int* nb) {
@@ -524,6 +525,15 @@ int launch_stop(const StopArgs& a, hipStream_t s) {
                    (a.col >= 0 ? a.col < a.stride : a.ctrl != nullptr) && (a.picks || a.pick_from_record || (a.part_val && a.part_idx && a.n_part >= 1)),
                ZG_ERR_ARG, "stop stage: missing argument");
     hipLaunchKernelGGL(stop_step_kernel, dim3(1), dim3(a.batch > 4 ? 512 : 256), 0, s, a);  // one wave per row
+    ZG_HIP(hipGetLastError());
+    return ZG_OK;
+}
+
+int launch_beam(const BeamArgs& a, hipStream_t s) {
+    ZG_REQUIRE(a.st && a.lenpow && a.n_lenpow >= 2 && a.top_ids && a.top_logprobs && a.sampled && a.parent && a.score && a.logprob && a.stride >= 1 &&
+                   a.batch >= 1 && a.batch <= kBeamRows && a.vocab >= 1 && (a.col >= 0 ? a.col < a.stride : a.ctrl != nullptr),
+               ZG_ERR_ARG, "beam stage: missing argument");
+    hipLaunchKernelGGL(beam_step_kernel, dim3(1), dim3(64 * kBeamRows), 0, s, a);  // one wave per group
     ZG_HIP(hipGetLastError());
     return ZG_OK;
 }

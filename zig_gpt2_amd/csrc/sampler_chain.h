@@ -25,14 +25,21 @@ struct StepTail {
     bool pen = false, lp = false, stop = false, edit = false;
     bool guide = false;  // guided decoding: the mask behind (and in one launch with) the edits, the advance behind the sampler
     bool ban = false;    // history-dependent bans: the ban launch between the penalties and the edits
+    bool beam = false;   // beam search: the beam launch and the cache fork behind the log-probability stage
     bool operator==(const StepTail& o) const {
-        return sampler == o.sampler && pen == o.pen && lp == o.lp && stop == o.stop && edit == o.edit && guide == o.guide && ban == o.ban;
+        return sampler == o.sampler && pen == o.pen && lp == o.lp && stop == o.stop && edit == o.edit && guide == o.guide && ban == o.ban && beam == o.beam;
     }
 };
-// The tail a step can have: nothing is drawn from a step without lm_head (the default tail), and a greedy pick has neither
-// penalties, edits, a guide nor bans
+// The tail a step can have: nothing is drawn from a step without lm_head (the default tail), a greedy pick has neither
+// penalties, edits, a guide nor bans, and a beam step is a greedy slot plus the log-probability stage (the beam stage has its own
+// early end: no stop stage)
 static inline StepTail normalized(StepTail t, bool with_logits) {
     if (!with_logits) return StepTail{};
+    if (t.beam) {
+        t.sampler = GREEDY;
+        t.lp = true;
+        t.stop = false;
+    }
     if (t.sampler == GREEDY) t.pen = t.edit = t.guide = t.ban = false;
     return t;
 }
@@ -90,5 +97,8 @@ int check_penalties(const zg_logit_penalties* p, const char* who);
 int check_sample_options(const zg_sample_options* o, const char* who);
 int check_stop(const zg_stop_conditions* c, size_t vocab, const char* who);
 void fill_stop(StopConds* d, const zg_stop_conditions& c);
+int check_beam(const zg_generate_request* q, const zg_beam_options* o, size_t batch, size_t vocab, size_t context, size_t cached_len, const char* who);
+void fill_beam_state(BeamState* d, const zg_beam_options& o, size_t c0);
+void fill_lenpow(float* d, size_t n, float length_penalty);
 
 }  // namespace zg

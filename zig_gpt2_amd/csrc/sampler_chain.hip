@@ -337,9 +337,61 @@ void fill_stop(StopConds* d, const zg_stop_conditions& c) {
     }
 }
 
+// The refusals of a beam generation (include/zgpt2.h zg_beam_options), on what the handle is: its rows, vocabulary, context and
+// cached positions.  The prompts are judged as far as the beam rules need them (equal lengths, equal within a group); their
+// tokens and the room in the context are the generation's own checks.
+int check_beam(const zg_generate_request* q, const zg_beam_options* o, size_t batch, size_t vocab, size_t context, size_t cached_len, const char* who) {
+    ZG_REQUIRE(q != nullptr && q->size == sizeof(zg_generate_request), ZG_ERR_ARG, "%s: null request, or its size field is not sizeof(zg_generate_request)", who);
+    ZG_REQUIRE(o != nullptr && o->size == sizeof(zg_beam_options), ZG_ERR_ARG, "%s: null options, or their size field is not sizeof(zg_beam_options)", who);
+    ZG_REQUIRE(!q->options && !q->penalties && !q->prior && !q->prior_stride && !q->prior_lens && !q->logprobs && !q->top_n && !q->stop && !q->edits, ZG_ERR_ARG,
+               "%s: options, penalties, prior, logprobs, stop and edits must be NULL / 0 (beams over such a distribution are not offered)", who);
+    const size_t W = o->num_beams;
+    ZG_REQUIRE(W >= 1 && W <= ZG_BEAM_MAX, ZG_ERR_ARG, "%s: num_beams %zu outside 1..%d", who, W, ZG_BEAM_MAX);
+    ZG_REQUIRE(batch >= 1 && batch <= (size_t)kBeamRows && batch % W == 0, ZG_ERR_ARG, "%s: a batch of %zu is no multiple of num_beams %zu", who, batch, W);
+    ZG_REQUIRE(2 * W <= vocab, ZG_ERR_ARG, "%s: 2 x num_beams %zu above the vocabulary of %zu", who, W, vocab);
+    ZG_REQUIRE(std::isfinite(o->length_penalty), ZG_ERR_ARG, "%s: length_penalty is not finite", who);
+    ZG_REQUIRE(o->eos_id == ZG_BEAM_NO_EOS || o->eos_id < vocab, ZG_ERR_SHAPE, "%s: eos_id %zu >= vocab %zu", who, o->eos_id, vocab);
+    ZG_REQUIRE(q->prompts && q->prompt_lens, ZG_ERR_ARG, "%s: null prompts", who);
+    ZG_REQUIRE(q->past_len <= cached_len && q->past_len <= context, ZG_ERR_ARG, "%s: past_len %zu beyond the %zu cached positions", who, q->past_len, cached_len);
+    const size_t np = q->prompt_lens[0];
+    for (size_t b = 1; b < batch; ++b)
+        ZG_REQUIRE(q->prompt_lens[b] == np, ZG_ERR_ARG, "%s: prompt %zu has %zu tokens, prompt 0 has %zu (beam rows run in lock step)", who, b, q->prompt_lens[b], np);
+    ZG_REQUIRE(np >= 1 && np <= q->prompt_stride, ZG_ERR_SHAPE, "%s: prompts of %zu tokens in rows of %zu", who, np, q->prompt_stride);
+    ZG_REQUIRE(q->n_steps > np, ZG_ERR_ARG, "%s: n_steps %zu picks nothing behind prompts of %zu tokens", who, q->n_steps, np);
+    for (size_t b = 0; b < batch; ++b)
+        for (size_t i = 0; i < np; ++i)
+            ZG_REQUIRE(q->prompts[b * q->prompt_stride + i] == q->prompts[(b / W) * W * q->prompt_stride + i], ZG_ERR_ARG,
+                       "%s: prompt %zu differs from prompt %zu of its group at token %zu", who, b, (b / W) * W, i);
+    return ZG_OK;
+}
+
+// The state a beam generation starts from (sample_beam.h): the options, slot g W of every group live with score 0, empty pools
+void fill_beam_state(BeamState* d, const zg_beam_options& o, size_t c0) {
+    memset(d, 0, sizeof(*d));
+    d->W = (int)o.num_beams;
+    d->eos = o.eos_id == ZG_BEAM_NO_EOS ? -1 : (int)o.eos_id;
+    d->early = o.early_stopping != 0;
+    d->c0 = (int)c0;
+    for (int s = 0; s < kBeamRows; ++s) {
+        d->score[s] = s % d->W == 0 ? 0.0f : -INFINITY;
+        d->src[s] = s;
+        d->done_col[s] = -1;
+    }
+}
+
+// lenpow[L] = (float)pow((double)L, (double)length_penalty), L = 0 .. n - 1
+void fill_lenpow(float* d, size_t n, float length_penalty) {
+    for (size_t L = 0; L < n; ++L) d[L] = (float)pow((double)L, (double)length_penalty);
+}
+
 }  // namespace zg
 
 extern "C" {
+
+// check_beam's face (tests; no GPU, no zg_init)
+int zg_debug_beam_check(const zg_generate_request* r, const zg_beam_options* beam, size_t batch, size_t vocab, size_t context, size_t cached_len) {
+    return check_beam(r, beam, batch, vocab, context, cached_len, "debug_beam_check");
+}
 
 // plan_rows' face (tests; no GPU, no zg_init): out[0] the sampler form the chain is launched in, out[1] whether the penalty stage
 // runs, out[2 + b] the form of row b

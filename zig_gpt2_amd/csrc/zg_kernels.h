@@ -231,6 +231,22 @@ int launch_wte_planes(const void* wte, int weight_type, size_t V, size_t V64, in
 // plane of [strips][ctx] rows of row_bytes at plane_off (api_gpt.hip clear_kv: what a new sequence must not inherit)
 int launch_kv_clear_tail(void* base, int n_caches, size_t cache_stride, size_t plane_off, int row_bytes, int strips, int ctx, int from_row,
                          hipStream_t s);
+// Row b of every cache becomes a copy of row src[b] over positions [0, len) (zg_gpt_kv_fork).  The caches are n_caches blocks
+// cache_stride bytes apart from base, each [batch][heads][ctx][64] elements of 4 (kv_mode 0) or 2 bytes, with kv_mode 2's byte plane
+// of the same element strides lo_off bytes further on.  The grid is fixed by the bucket bound t_hi (a multiple of 64 at or above
+// len); the table and the length come from device memory (src, len), or, where those are null, by value: src_imm holds four bits per
+// row, len_imm the length.  PRECONDITION: every source is its own source (src[src[b]] == src[b]): then no workgroup reads what
+// another writes.
+struct KvForkArgs {
+    char* base;
+    size_t cache_stride, lo_off;
+    int n_caches, batch, heads, ctx, kv_mode, t_hi;
+    const int* src;
+    const int* len;
+    unsigned src_imm;
+    int len_imm;
+};
+int launch_kv_fork(const KvForkArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------ MFMA GEMM
 // C[M,N] = A[M,K] * B[N,K]^T (+ bias) (optional GELU); bf16 operands, fp32 accumulate; C bf16 or fp32.
@@ -630,6 +646,42 @@ struct StopArgs {
     StopHost* host;
 };
 int launch_stop(const StopArgs& a, hipStream_t s);
+// The beam stage of a step (sample_beam.h; include/zgpt2.h zg_beam_options): one launch, one workgroup, one wave per group, behind
+// the log-probability stage whose top-2W lists of the column in flight it reads.  The options and everything a group carries from
+// step to step live in ONE device block, so one captured launch serves every call.  Pool entries and the per-group words are
+// indexed by g * W + k: there are never more of them than rows.
+constexpr int kBeamMax = 8, kBeamRows = 8;  // ZG_BEAM_MAX; rows of a handle
+struct BeamState {
+    // the options of the call, staged by the host
+    int W;       // beams per group (1 .. kBeamMax)
+    int eos;     // the token that ends a hypothesis, -1: none
+    int early;   // early_stopping != 0
+    int c0;      // the first picked column
+    // carried from step to step
+    float score[kBeamRows];        // cumulative score of the beam in each slot
+    int src[kBeamRows];            // slot each slot's beam came from in the last step: the table of that step's cache fork
+    int pool_n[kBeamRows];         // [g]: entries of group g's pool
+    int done_col[kBeamRows];       // [g]: the column at which group g was done, -1 while it is not
+    float pool_sum[kBeamRows], pool_norm[kBeamRows];  // [g * W + k]
+    int pool_parent[kBeamRows], pool_col[kBeamRows];
+};
+struct BeamArgs {
+    BeamState* st;
+    const float* lenpow;       // [n_lenpow]: lenpow[L] = (float)pow(L, length_penalty)
+    int n_lenpow;
+    int batch, vocab;
+    const int* top_ids;        // the lists: [batch][stride][20], by the slot as it stood before the step
+    const float* top_logprobs;
+    int stride;
+    const StepCtrl* ctrl;      // the column in flight is ctrl->seq_len - 1 ...
+    int col;                   // ... unless this is >= 0 (zg_debug_beam_rows)
+    int* sampled;              // [batch] out: the token of the beam now in each slot
+    int* parent;               // [batch][stride] out
+    float* score;              // [batch][stride] out
+    float* logprob;            // [batch][stride] out: the chosen list entry's bits
+    StopHost* host;            // pinned, optional: progress / done_col as the stop stage stores them
+};
+int launch_beam(const BeamArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------ multi-GPU (dist.hip)
 int dist_broadcast(void* buf, size_t bytes, int root, hipStream_t s);  // in place, over the communicator of zg_dist_init

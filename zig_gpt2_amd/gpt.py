@@ -32,7 +32,7 @@ class GPT:
     def __init__(self, config: GPTConfig, batch=1, weights_f32=False, use_graph=True, kv_f16=False, prefill=True,
                  prefill_planes=3, prefetch=True, kv_b24=False, share_weights_with=None, own_stream=False, stream_priority=0,
                  sampled_generate=False, weights_b24=False, truncated_generate=False, penalized_generate=False, logprobs_generate=False,
-                 score=False, stop_generate=False, edited_generate=False, guided=False, banned_generate=False):
+                 score=False, stop_generate=False, edited_generate=False, guided=False, banned_generate=False, beam_generate=False):
         """share_weights_with / own_stream / stream_priority: zg_gpt_options of zg_gpt_create_ex (a handle of an independent
         prompt group on the same GPU: private stream, weight region borrowed from another GPT of the same config).
         weights_b24: matrices stored as 24-bit floats (ZG_GPT_WEIGHTS_B24: each fp32 weight rounded to 16 mantissa bits, 3/4 of
@@ -46,8 +46,10 @@ class GPT:
         guided: guided decoding (ZG_GPT_GUIDED_GENERATE) — carve the automaton's table, bitmaps, states and record, and
         capture the guided twins of the sampler graphs create captures; without it `load_guide` and guide_states raise ZG_ERR_UNSUPPORTED.
         banned_generate: the banned twins (no_repeat_ngram_size / bad_words_ids / min_tokens; ZG_GPT_BANNED_GENERATE) of the
-        sampler graphs create captures, as the other *_generate flags; without it such a generation captures its graphs when it begins."""
+        sampler graphs create captures, as the other *_generate flags; without it such a generation captures its graphs when it begins.
+        beam_generate: the graphs of `beam_search` (ZG_GPT_BEAM_GENERATE) at create instead of when the first one begins."""
         self.config, self.batch = config, batch
+        self._kv_bytes = 2 if kv_f16 else 3 if kv_b24 else 4  # bytes of a cache element (kv_rows)
         L = _lib.load()
         flags = (_lib.GPT_WEIGHTS_F32 if weights_f32 else 0) | (0 if use_graph else _lib.GPT_NO_GRAPH)
         flags |= _lib.GPT_KV_F16 if kv_f16 else 0
@@ -65,6 +67,7 @@ class GPT:
         flags |= _lib.GPT_EDITED_GENERATE if edited_generate else 0
         flags |= _lib.GPT_GUIDED_GENERATE if guided else 0
         flags |= _lib.GPT_BANNED_GENERATE if banned_generate else 0
+        flags |= _lib.GPT_BEAM_GENERATE if beam_generate else 0
         cfg = _lib.GptConfig(config.vocab_size, config.context_size, config.n_layer, config.n_heads, config.n_embed)
         h = C.c_void_p()
         if share_weights_with is None and not own_stream:
@@ -481,6 +484,57 @@ class GPT:
         out = np.zeros((self.batch, n), np.uint64)
         check(self._L.zg_gpt_generate_fetch_range(self.h, first, n, ptr(out), out.size))
         return out
+
+    # ------------------------------------------------------------------ cache forks and beam search
+    def fork_rows(self, src):
+        """zg_gpt_kv_fork: row b's KV caches over the cached positions become those of row src[b] (src[b] == b: untouched).  Enqueued
+        on the handle's stream; every source must be its own source."""
+        src = np.ascontiguousarray(np.atleast_1d(src), dtype=np.uint64)
+        check(self._L.zg_gpt_kv_fork(self.h, ptr(src), src.size))
+
+    def kv_rows(self, layer, which, row, first_pos, n_pos):
+        """zg_debug_gpt_kv_rows: the raw bytes (uint8) of positions first_pos .. first_pos + n_pos - 1 of one row of layer `layer`'s
+        K (which 0) or V (which 1) cache, [n_heads][n_pos][64] elements, a 24-bit cache's byte plane behind its bf16 plane."""
+        out = np.zeros(self.config.n_heads * n_pos * 64 * self._kv_bytes, np.uint8)
+        check(self._L.zg_debug_gpt_kv_rows(self.h, layer, which, row, first_pos, n_pos, ptr(out), out.size))
+        return out
+
+    def beam_search_enqueue(self, prompts, n_steps, num_beams, eos_token_id=None, length_penalty=1.0, early_stopping=True, past_len=0, lookahead=0):
+        """zg_gpt_generate_beam_enqueue: `prompts` holds one prompt per group (batch // num_beams of them) or one per row."""
+        prompts = list(prompts)
+        if len(prompts) * num_beams == self.batch and num_beams > 1:
+            prompts = [p for p in prompts for _ in range(num_beams)]
+        mat, lens, stride = self._prompts(prompts)
+        req = _lib.generate_request(past_len=past_len, prompts=ptr(mat), prompt_stride=stride, prompt_lens=ptr(lens), n_steps=n_steps)
+        opt = _lib.beam_options(num_beams, eos_token_id, length_penalty, early_stopping, lookahead)
+        check(self._L.zg_gpt_generate_beam_enqueue(self.h, C.addressof(req), C.addressof(opt)))
+        self._beam_width = int(num_beams)
+
+    def generate_fetch_beams(self, num_return_sequences, max_len=None):
+        """zg_gpt_generate_fetch_beams: per group a list of (tokens uint64 array, score, sum_logprob), best first."""
+        n, stride = int(num_return_sequences), int(max_len or self.config.context_size)
+        tok = np.zeros((self.batch, n, stride), np.uint64)  # (at least [G][n][stride])
+        lens = np.zeros((self.batch, n), np.uint64)
+        scores, sums = np.zeros((self.batch, n), np.float32), np.zeros((self.batch, n), np.float32)
+        check(self._L.zg_gpt_generate_fetch_beams(self.h, n, ptr(tok), stride, ptr(lens), ptr(scores), ptr(sums)))
+        G = self.batch // self._beam_width
+        return [[(tok[g, i, : int(lens[g, i])].copy(), scores[g, i], sums[g, i]) for i in range(n) if lens[g, i] > 0] for g in range(G)]
+
+    def generate_fetch_beam_trace(self, first, n):
+        """zg_gpt_generate_fetch_beam_trace of columns first .. first + n - 1: (parents [batch, n] int32, scores [batch, n] float32),
+        indexed by the slot after each step."""
+        par = np.zeros((self.batch, n), np.int32)
+        sc = np.zeros((self.batch, n), np.float32)
+        check(self._L.zg_gpt_generate_fetch_beam_trace(self.h, first, n, ptr(par), ptr(sc), par.size))
+        return par, sc
+
+    def beam_search(self, prompts, n_steps, num_beams, eos_token_id=None, length_penalty=1.0, early_stopping=True, num_return_sequences=1, past_len=0,
+                    lookahead=0):
+        """Beam search in the device loop (HF generate(num_beams=...); DESIGN §3.14): the handle's batch is batch // num_beams groups
+        of num_beams beams, `prompts` one prompt per group.  Returns per group a list of (tokens, score, sum_logprob), best first:
+        the picked tokens only (eos last where there is one), score = sum_logprob / len ** length_penalty."""
+        self.beam_search_enqueue(prompts, n_steps, num_beams, eos_token_id, length_penalty, early_stopping, past_len, lookahead)
+        return self.generate_fetch_beams(num_return_sequences)
 
     def generate_from(self, past_len, prompts, n_steps, temp=None, seed=0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0,
                       frequency_penalty=0.0, prior=None, logprobs=None, stop_token_ids=None, stop=None, lookahead=0, logit_bias=None,
